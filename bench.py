@@ -1,13 +1,19 @@
 """bench.py -- headline benchmark of the dense-GP hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cm|c3|c4-weak|c4-strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cm|c3|c4-weak|c4-strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 `python bench.py --gpus N` WITHOUT a launcher spawns the N ranks itself (torch.distributed.run, 127.0.0.1, a free port) and
 refuses to run when the node has fewer than N devices; `--dry-launch` exercises that launch / timing protocol on CPU (gloo).
 
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs of the last timed
+step written to DIR if `--dump-outputs DIR` is given (`elbo.npy`, `elbo_terms.npy`: float64), one JSON line.
+`--full` adds every other leg to the same line: the roofline leg and per-kernel GEMM figures, the stream self-check, the
+CPU baseline with the oracle parity of the last timed step, the PCIe-inclusive / read-back-late / Python-mirror rates,
+the training step, the other BASELINE configs and GPR C2 (`--no-*` prune those legs of a `--full` run).
+
 Metric (BASELINE.json): SVGP ELBO steps/s at N=1e6, M=2048, D=8 (config "Cm", the default workload), with the GPR
-config C2 (N=16384: K build + Cholesky + predict, GF/s vs fp64 peak) reported alongside in the same JSON line (key
-"gpr_cholesky", N=1 only).
+config C2 (N=16384: K build + Cholesky + predict, GF/s vs fp64 peak) reported alongside in the same JSON line under
+`--full` (key "gpr_cholesky", N=1 only).
 
 A "step" = one forward minibatch ELBO evaluation (SVGP.elbo, gpflow/models/svgp.py:166-181): Kuu / Kuf builds,
 Cholesky of Kuu, the triangular solves, the q_sqrt projection, the variational expectations, KL, the (multi-GPU)
@@ -20,8 +26,8 @@ Workloads:
   c4-weak    N=1e7, M=2048, D=16, 8192 rows per GPU (weak)
   c4-strong  N=1e7, M=2048, D=16, global minibatch 8192 rows, 8192/G rows per GPU (strong scaling)
 `value` = 8192-row minibatch evaluations per second over the whole job for the weak workloads, global steps per second
-for c4-strong.  The last step's ELBO is checked against the CPU oracle ON THE SAME ARRAYS (`parity_rel_err`), and that
-oracle call is what `cpu_baseline` times.
+for c4-strong.  Under `--full` the last step's ELBO is checked against the CPU oracle ON THE SAME ARRAYS
+(`parity_rel_err`), and that oracle call is what `cpu_baseline` times.
 """
 from __future__ import annotations
 
@@ -124,6 +130,16 @@ def make_inputs(n_data, m_ind, d_in, seed, device):
     X, Y, Z, q_mu, q_sqrt = to(Xh), to(Yh), to(Zh), to(q_mu_h), to(q_sqrt_h)
     ls = np.sqrt(d_in) * (0.8 + 0.05 * np.arange(d_in))
     return X, Y, Z, q_mu, q_sqrt, ls
+
+
+def dump_outputs(out_dir: str, terms: np.ndarray, elbo: float) -> list:
+    """What a caller of the timed step receives from its last timed step, as float64 .npy files in out_dir:
+    `elbo` (shape [1]) and `elbo_terms` (shape [2]: the data term summed over the global minibatch, the KL)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"elbo": np.array([elbo], dtype=np.float64), "elbo_terms": np.asarray(terms, dtype=np.float64).reshape(2)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def cpu_baseline_and_parity(Xb, Yb, Z, q_mu, q_sqrt, ls, n_data, gpu_elbo, budget_s: float = 14.0):
@@ -552,10 +568,18 @@ def main():  # noqa: C901
     ap.add_argument("--dry-launch", action="store_true",
                     help="exercise ONLY the multi-rank launch protocol on CPU (gloo): rank spawn, rendezvous, barrier-bracketed "
                          "timing, MAX over ranks, the single JSON line from rank 0 -- no device work, `value` is null")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64): elbo, elbo_terms "
+                         "(rank 0; nothing under --dry-launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: roofline, stream self-check, CPU baseline + oracle parity, "
+                         "PCIe / Python-mirror rates, training step, other BASELINE configs, GPR C2 (pruned by the --no-* options)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Not under a launcher: become one.  `python bench.py --gpus N` starts N ranks itself (one process per GPU,
         # torch.distributed.run on 127.0.0.1, a free port) and rank 0 prints the single JSON line with n_gpus = N.
@@ -643,16 +667,21 @@ def main():  # noqa: C901
         elapsed = float(t.cpu()[0])
     assert last["info"] == 0 and np.isfinite(last["elbo"]), last
     timed_last = dict(last)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # `out` still holds the scalars the last timed step published (all-reduced over the ranks): nothing ran since
+        dumped = dump_outputs(args.dump_outputs, out.cpu().numpy(), timed_last["elbo"])
 
-    # ---- roofline leg (dominant kernel = the fp64 MFMA GEMM): HIP events around every GEMM launch ----
+    # ---- roofline leg (--full; dominant kernel = the fp64 MFMA GEMM): HIP events around every GEMM launch ----
     roof = None
-    nprof = 5
-    if rank == 0:
+    nprof = 5 if args.full else 0
+    if args.full and rank == 0:
         lib.gpk_profile_gemm_enable(1)
     for s in range(nprof):  # every rank steps (the all-reduce is collective); only rank 0 records
         step(args.warmup + args.steps + s)
-    fence()
-    if rank == 0:
+    if args.full:
+        fence()
+    if args.full and rank == 0:
         def by_kind(kind, min_flops=0.0):
             ms, n_launch, fl = ctypes.c_double(), ctypes.c_long(), ctypes.c_double()
             lib.gpk_profile_gemm_collect_kind(int(kind), ctypes.c_double(min_flops), ctypes.byref(ms), ctypes.byref(n_launch),
@@ -745,13 +774,17 @@ def main():  # noqa: C901
         "step_frac_of_fp64_peak": svgp_step_flops(m_ind, b_rows, P_LAT) * steps_per_s / 1e12 / FP64_PEAK_TFLOPS,
         "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default"),
         "library": lib.gpk_version().decode(),
-        "stream_selfcheck": stream_selfcheck(lib),
-        "roofline": roof,
+        "full": bool(args.full),
     }
+    if dumped:
+        res["dumped_outputs"] = dumped
+    if args.full:
+        res["stream_selfcheck"] = stream_selfcheck(lib)
+        res["roofline"] = roof
     if selftest:
         res["rccl_selftest"] = ("world-size-1 nccl process group: every step above carries the 8-byte all-reduce (RCCL "
                                 "initialised AFTER the library placed its streams); compare ms_per_step with a run without the flag")
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # parity of the LAST TIMED step against the oracle on the same arrays (all shards of that global minibatch; the
         # data are replicated on every rank), and the oracle's own wall-clock as the CPU baseline
         s_last = timed_last["step"]
@@ -764,7 +797,7 @@ def main():  # noqa: C901
         res["oracle_elbo"] = ref
         res["parity_rel_err"] = err
         res["parity_ok"] = bool(err <= 1e-8)
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # PCIe-inclusive rate (never `value`): the same step when the minibatch arrives in (pinned) HOST memory, as it
         # does for a caller handing NumPy arrays to the Python mirror -- rows x (D + 1) doubles per step
         hX = [X[i * b_rows:(i + 1) * b_rows].cpu().pin_memory() for i in range(4)]
@@ -822,13 +855,13 @@ def main():  # noqa: C901
             v = float(model.elbo((X[lo:lo + b_rows], Y[lo:lo + b_rows])))
         res["python_mirror_steps_per_s"] = 30.0 / (time.perf_counter() - t1)
         res["python_mirror_last_elbo"] = v
-    if world == 1 and not args.no_train:
+    if args.full and world == 1 and not args.no_train:
         res["train_step"] = train_step_leg(X, Y, Z, q_mu, q_sqrt, ls, n_data, b_rows)
-    if world == 1 and not args.no_other:
+    if args.full and world == 1 and not args.no_other:
         X = Y = None
         torch.cuda.empty_cache()
         res["other_workloads"] = other_workloads_leg(device, with_oracle=not args.no_cpu_baseline)
-    if world == 1 and not args.no_gpr:
+    if args.full and world == 1 and not args.no_gpr:
         X = Y = None
         torch.cuda.empty_cache()
         res["gpr_cholesky"] = gpr_leg(ops, lib, device, with_oracle=not args.no_cpu_baseline)

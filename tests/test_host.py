@@ -277,6 +277,18 @@ def test_bench_spawns_its_own_ranks():
     assert rec["dry_launch"] is True and rec["allreduce_check"] is True
 
 
+def test_bench_rejects_a_run_without_timed_steps():
+    """`ms_per_step` is the wall-clock of the timed region over --steps: a run with no timed step is refused up front."""
+    import subprocess
+    import sys
+    for extra in (["--steps", "0"], ["--steps", "2", "--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--dump-outputs", "unused"] + extra,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and "--steps must be >= 1" in r.stderr, r.stderr[-2000:]
+        assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert not os.path.exists(os.path.join(ROOT, "unused")) and not os.path.exists("unused")
+
+
 def test_bench_refuses_fewer_devices_than_ranks():
     """Without enough devices a multi-rank bench must fail loudly, not run a silent 1-GPU job."""
     import subprocess

@@ -3,7 +3,7 @@
 root=${GRAFT_REPO_ROOT:-$(pwd)}; cd $root
 run() {
   for rep in $(seq 1 ${AB_REPS:-2}); do
-    env $1 timeout 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline ${AB_FLAGS:---no-train --no-extras} 2>/dev/null | python -c "
+    env $1 timeout 300 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline ${AB_FLAGS:---no-train --no-extras} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); o=d.get('other_workloads',{})
 g=lambda k: o.get(k,{}).get('ms_per_step',0)

@@ -2,7 +2,7 @@
 # A/B of the streamed q_sqrt projection on the SVGP step (same box):  tools/ab_proj.sh "ENV=.. ENV2=.." ...
 run() {
   for rep in 1 2; do
-    env $1 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-gpr 2>/dev/null | python -c "
+    env $1 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-gpr 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']
