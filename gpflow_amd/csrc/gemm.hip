@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p, int gx, int
 
   int kb = 0, ke = p.k;
   const int koff = bz * p.k_off_step;   // (K-split of a triangular product: this batch entry holds columns koff .. koff + k of the operands)
-  if (p.b_tri && n0 + BN <= p.b_tri_rows) {
+  if (p.b_tri && (n0 + BN < p.n ? n0 + BN : p.n) <= p.b_tri_rows) {   // (the tile's existing rows; a partial last tile too)
     if (p.b_tri == 1) {
       int f = n0 + p.b_tri_off - koff;
       kb = (f > 0 ? f : 0) & ~(BK - 1);
@@ -553,7 +553,7 @@ __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int til
   const double* __restrict__ B = p.B + (long)bz * p.strideB;
   int kb = 0, ke = p.k;
   const int koff = bz * p.k_off_step;   // (see gemm_nt_kernel)
-  if (p.b_tri && n0 + BN <= p.b_tri_rows) {
+  if (p.b_tri && (n0 + BN < p.n ? n0 + BN : p.n) <= p.b_tri_rows) {   // (the tile's existing rows; a partial last tile too)
     if (p.b_tri == 1) {
       const int f = n0 + p.b_tri_off - koff;
       kb = (f > 0 ? f : 0) & ~(BK - 1);
@@ -1093,7 +1093,7 @@ __global__ __launch_bounds__(SM_THREADS) void gemm_nt_small(GemmArgs p, int ldk,
   const double* __restrict__ A = p.A + (long)bz * p.strideA;
   const double* __restrict__ B = p.B + (long)bz * p.strideB;
   int kb = 0, ke = p.k;
-  if (p.b_tri && n0 + SM_BN <= p.b_tri_rows) {
+  if (p.b_tri && (n0 + SM_BN < p.n ? n0 + SM_BN : p.n) <= p.b_tri_rows) {   // (the tile's existing rows; a partial last tile too)
     if (p.b_tri == 1) {
       const int f = n0 + p.b_tri_off;
       kb = (f > 0 ? f : 0) & ~(BK - 1);
@@ -2024,11 +2024,42 @@ static int launch_select(hipStream_t s, const GemmArgs& a) {
 }
 
 
+namespace {
+// K = 0: C = beta C (exact zeros for beta = 0, C not read), on the tiles a 128 x 128 launch would write
+__global__ __launch_bounds__(256) void gemm_nt_empty_k_kernel(double* __restrict__ C, int row0, int n, long ldc, long strideC,
+                                                              double beta, int c_lower) {
+  double* Cz = C + (long)blockIdx.z * strideC;
+  const int i = row0 + (int)blockIdx.y;
+  for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
+    if (c_lower && (j & ~127) > (i & ~127)) continue;
+    double* c = Cz + (long)i * ldc + j;
+    *c = beta != 0.0 ? beta * *c : 0.0;
+  }
+}
+}  // namespace
+
 extern "C" int gpk_gemm_nt(void* stream, int m, int n, int k, double alpha, const double* A,
                            long lda, const double* B, long ldb, double beta, double* C, long ldc,
                            int b_tri, int c_lower, int batch, long strideA, long strideB,
                            long strideC) {
-  if (m < 0 || n < 0 || k < 0 || !A || !B || !C) return GPK_E_ARG;
+  // (gpk.h: an operand without elements may be NULL -- A / B when m, n or k is 0, C when m or n is 0)
+  if (m < 0 || n < 0 || k < 0 || batch < 0) return GPK_E_ARG;
+  if ((b_tri & ~0x133) || (b_tri & 3) == 3 || ((b_tri >> 4) & 3) == 3 || ((b_tri & 0x100) && (k & 15))) return GPK_E_ARG;
+  if (m == 0 || n == 0) return 0;
+  if (!C) return GPK_E_ARG;
+  if (k == 0) {
+    // no product: C = beta C (BLAS), on the tiles the K > 0 launches write (c_lower: 128-wide tiles on or below the diagonal)
+    const int nbatch = batch > 0 ? batch : 1;
+    if (nbatch > 65535) return GPK_E_ARG;
+    for (int i0 = 0; i0 < m; i0 += 65535) {
+      dim3 grid((unsigned)std::min(gpk_cdiv(n, 256), 64), (unsigned)std::min(m - i0, 65535), (unsigned)nbatch);
+      hipLaunchKernelGGL(gemm_nt_empty_k_kernel, grid, dim3(256), 0, (hipStream_t)stream, C, i0, n, ldc,
+                         nbatch > 1 ? strideC : 0L, beta, c_lower);
+      GPK_LAUNCH_CHECK();
+    }
+    return 0;
+  }
+  if (!A || !B) return GPK_E_ARG;
   GemmArgs g{};
   g.A = A; g.lda = lda; g.strideA = strideA;
   g.B = B; g.ldb = ldb; g.strideB = strideB;
@@ -2039,7 +2070,6 @@ extern "C" int gpk_gemm_nt(void* stream, int m, int n, int k, double alpha, cons
   // and the triangular statements are about the UNSPLIT column index.  The caller sums the `batch` partial products.
   const int ksplit = (b_tri >> 8) & 1;
   g.a_tri = (m <= k * (ksplit ? (batch > 0 ? batch : 1) : 1)) ? ((b_tri >> 4) & 3) : 0;  // (a hint: ignoring it is always correct)
-  if ((b_tri & ~0x133) || g.b_tri == 3 || g.a_tri == 3 || (ksplit && (k & 15))) return GPK_E_ARG;
   g.k_off_step = ksplit ? k : 0;
   g.epi = 0; g.batch = batch > 0 ? batch : 1;
   // (A/B: the tile queue for every batched launch -- the split-K products of the reverse pass, 1088 equal tiles -- is level:

@@ -1039,8 +1039,9 @@ extern "C" int gpk_trtri_blocks(void* stream, const double* L, int n, long ldl, 
 // n -- ran the N = 16384, T = 4096 predict solve at 7 TFLOP/s.)
 extern "C" int gpk_trsm(void* stream, int trans, const double* L, long ldl, const double* invd,
                         int n, double* B, int m, long ldb, int batch, long strideL, long strideB) {
-  if (!L || !invd || !B || n < 0 || m < 0) return GPK_E_ARG;
+  if (n < 0 || m < 0) return GPK_E_ARG;
   if (n == 0 || m == 0) return 0;
+  if (!L || !invd || !B) return GPK_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (batch <= 0) batch = 1;
   const long strideInv = (long)gpk_cdiv(n, NB) * NB * NB;
@@ -1083,7 +1084,7 @@ namespace {
 // the GEMM alone: partials [P][nt = 2 * tiles_n][rows] in ws, one per 64 output columns
 int project_parts(hipStream_t s, const double* At, int rows, int m, long ldat, long strideAt, const double* LqT, long ldl, int P, void* ws,
                   size_t ws_bytes) {
-  if (!At || !LqT || rows < 0 || m <= 0 || P <= 0 || strideAt < 0) return GPK_E_ARG;
+  if ((!At && rows > 0) || !LqT || rows < 0 || m <= 0 || P <= 0 || strideAt < 0) return GPK_E_ARG;
   if (!ws || ws_bytes < gpk_project_workspace_bytes(rows, m, P)) return GPK_E_WORKSPACE;
   if (rows == 0) return 0;
   const int nt = 2 * gpk_gemm_tiles_n(m);
@@ -1098,7 +1099,7 @@ int project_parts(hipStream_t s, const double* At, int rows, int m, long ldat, l
 
 extern "C" int gpk_project_batched(void* stream, const double* At, int rows, int m, long ldat, long strideAt,
                                    const double* LqT, long ldl, int P, double* ssq, void* ws, size_t ws_bytes) {
-  if (!ssq) return GPK_E_ARG;
+  if (!ssq && rows > 0) return GPK_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int rc = project_parts(s, At, rows, m, ldat, strideAt, LqT, ldl, P, ws, ws_bytes);
   if (rc || rows == 0) return rc;
@@ -1283,7 +1284,7 @@ extern "C" int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, in
                                    double mean_const, const double* q_mu, const double* q_sqrt,
                                    int q_diag, int whiten, double* out, int* info, void* ws,
                                    size_t ws_bytes) {
-  if (!Z || !Xb || !Yb || !q_mu || !q_sqrt || !out || !info || m <= 0 || rows < 0 || P <= 0 || P > 16)
+  if (!Z || (rows > 0 && (!Xb || !Yb)) || !q_mu || !q_sqrt || !out || !info || m <= 0 || rows < 0 || P <= 0 || P > 16)
     return GPK_E_ARG;
   const ElboLayout l = elbo_layout(m, rows, P, q_diag, whiten);
   if (!ws || ws_bytes < l.total) return GPK_E_WORKSPACE;
@@ -1590,7 +1591,7 @@ extern "C" int gpk_svgp_elbo_shard_sep(void* stream, const int* family_host, con
                                        const double* noise_rows, double jitter, double mean_const, const double* q_mu,
                                        const double* q_sqrt, double* out,
                                        int* info, void* ws, size_t ws_bytes) {
-  if (!family_host || !Z || !Xb || !Yb || !q_mu || !q_sqrt || !ls_host || !variance_host || !out || !info || m <= 0 || rows < 0 ||
+  if (!family_host || !Z || (rows > 0 && (!Xb || !Yb)) || !q_mu || !q_sqrt || !ls_host || !variance_host || !out || !info || m <= 0 || rows < 0 ||
       P <= 0 || P > 16 || d <= 0 || strideZ < 0)
     return GPK_E_ARG;
   const ElboSepLayout l = elbo_sep_layout(m, rows, P);

@@ -241,8 +241,11 @@ extern "C" int gpk_kernel_matrix(void* stream, int family, const double* X1, int
                                  const double* X2, int n2, long ldx2, int d, const double* ls_host,
                                  int ard, double variance, double diag_add, int lower_only,
                                  double* K, long ldk) {
-  if (!X1 || !K || !ls_host || n1 < 0 || d <= 0 || d > GPK_MAX_D) return GPK_E_ARG;
+  // (gpk.h: an operand without elements may be NULL)
+  if (!ls_host || n1 < 0 || (X2 && n2 < 0) || d <= 0 || d > GPK_MAX_D) return GPK_E_ARG;
   if (family < GPK_KERN_SE || family > GPK_KERN_MATERN52) return GPK_E_UNSUPPORTED;
+  if (n1 == 0 || (X2 && n2 == 0)) return 0;
+  if (!X1 || !K) return GPK_E_ARG;
   RbfArgs a{};
   a.X1 = X1; a.ldx1 = ldx1; a.n1 = n1;
   a.sym = (X2 == nullptr);
@@ -270,9 +273,11 @@ extern "C" int gpk_kernel_matrix_combine(void* stream, int family, int op, const
                                          const double* X2, int n2, long ldx2, int d, const double* ls_host, int ard,
                                          double variance, double diag_add, const double* G, long ldg, double* out,
                                          long ldo) {
-  if (!X1 || !G || !out || !ls_host || n1 < 0 || n2 < 0 || d <= 0 || d > GPK_MAX_D) return GPK_E_ARG;
+  if (!ls_host || n1 < 0 || (X2 && n2 < 0) || d <= 0 || d > GPK_MAX_D) return GPK_E_ARG;
   if (family < GPK_KERN_SE || family > GPK_KERN_MATERN52) return GPK_E_UNSUPPORTED;
   if (op < 1 || op > 3) return GPK_E_ARG;
+  if (n1 == 0 || (X2 && n2 == 0)) return 0;
+  if (!X1 || !G || !out) return GPK_E_ARG;
   RbfArgs a{};
   a.X1 = X1; a.ldx1 = ldx1; a.n1 = n1;
   a.sym = 0;
@@ -294,6 +299,8 @@ extern "C" int gpk_kernel_matrix_hadamard(void* stream, int family, const double
                                           const double* X2, int n2, long ldx2, int d, const double* ls_host,
                                           int ard, double variance, const double* G, long ldg, double* out,
                                           long ldo) {
+  if (n1 < 0 || n2 < 0) return GPK_E_ARG;
+  if (n1 == 0 || n2 == 0) return 0;
   if (!X2) return GPK_E_ARG;
   return gpk_kernel_matrix_combine(stream, family, 1, X1, n1, ldx1, X2, n2, ldx2, d, ls_host, ard, variance, 0.0, G, ldg,
                                    out, ldo);

@@ -505,8 +505,9 @@ extern "C" size_t gpk_reduce_workspace_bytes(int n) {
 extern "C" int gpk_transpose(void* stream, const double* in, int rows, int cols, long ldin,
                              double* out, long ldout, int mode, int batch, long stride_in,
                              long stride_out) {
-  if (!in || !out || rows < 0 || cols < 0) return GPK_E_ARG;
+  if (rows < 0 || cols < 0) return GPK_E_ARG;
   if (rows == 0 || cols == 0) return 0;
+  if (!in || !out) return GPK_E_ARG;
   dim3 grid((unsigned)gpk_cdiv(cols, 32), (unsigned)gpk_cdiv(rows, 32),
             (unsigned)(batch > 0 ? batch : 1));
   hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, rows, cols, ldin,
@@ -519,8 +520,9 @@ extern "C" int gpk_transpose(void* stream, const double* in, int rows, int cols,
 extern "C" int gpk_row_stats(void* stream, const double* At, int rows, int m, long ldat,
                              const double* V, const double* W, int P, double alpha, double beta,
                              double* sumsq, double* mv, double* wsq) {
-  if (!At || rows < 0 || m < 0) return GPK_E_ARG;
+  if (rows < 0 || m < 0) return GPK_E_ARG;
   if (rows == 0) return 0;
+  if (!At) return GPK_E_ARG;
   const int np = (V || W) ? P : 0;
   const dim3 grid((unsigned)gpk_cdiv(rows, 4));
   int p0 = 0;
@@ -545,8 +547,9 @@ int gpk_launch_row_stats_sep(hipStream_t s, const double* At, long strideAt, int
 
 extern "C" int gpk_row_dot(void* stream, const double* A, long lda, const double* B, long ldb,
                            int rows, int cols, double alpha, double beta, double* out) {
-  if (!A || !B || !out || rows < 0 || cols < 0) return GPK_E_ARG;
+  if (rows < 0 || cols < 0) return GPK_E_ARG;
   if (rows == 0) return 0;
+  if (!A || !B || !out) return GPK_E_ARG;
   hipLaunchKernelGGL(row_dot_kernel, dim3((unsigned)gpk_cdiv(rows, 4)), dim3(256), 0,
                      (hipStream_t)stream, A, lda, B, ldb, rows, cols, alpha, beta, out);
   GPK_LAUNCH_CHECK();
@@ -570,8 +573,9 @@ int gpk_launch_sum_parts(hipStream_t s, const double* part, int nt, int rows, lo
 
 extern "C" int gpk_combine_parts(void* stream, const double* parts, int nparts, long stride_part, int m, int n, long ldp,
                                  double alpha, int lower, double diag_scale, double* out, long ldo) {
-  if (!parts || !out || nparts <= 0 || m < 0 || n < 0 || ldp < n || ldo < n) return GPK_E_ARG;
+  if (nparts <= 0 || m < 0 || n < 0 || ldp < n || ldo < n) return GPK_E_ARG;
   if (m == 0 || n == 0) return 0;
+  if (!parts || !out) return GPK_E_ARG;
   dim3 grid((unsigned)gpk_cdiv(gpk_cdiv(n, 2), 256), (unsigned)(m < 65535 ? m : 65535));
 #define GPK_COMBINE(NP)                                                                                               \
   hipLaunchKernelGGL((combine_parts_kernel<NP>), grid, dim3(256), 0, (hipStream_t)stream, parts, nparts, stride_part, m, n, \
@@ -595,7 +599,7 @@ extern "C" int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, 
                                        const double* ssq, const double* knn_host,
                                        int knn_per_latent, double noise_variance, const double* noise_rows,
                                        double mean_const, double* fvar_out, double* out, void* ws, size_t ws_bytes) {
-  if (!Y || !fmean || !knn_host || !out || P <= 0 || P > 16 || rows < 0) return GPK_E_ARG;
+  if ((rows > 0 && (!Y || !fmean)) || !knn_host || !out || P <= 0 || P > 16 || rows < 0) return GPK_E_ARG;
   if (!ws || ws_bytes < gpk_reduce_workspace_bytes(rows)) return GPK_E_WORKSPACE;
   VarexpArgs a{};
   a.Y = Y; a.ldy = ldy; a.fmean = fmean; a.rows = rows; a.P = P;
@@ -680,7 +684,7 @@ int gpk_launch_sum_log_diag_sq(hipStream_t s, const double* L, int n, long ldl, 
 
 extern "C" int gpk_sumsq(void* stream, const double* A, int rows, int cols, long lda, int upper_only,
                          double* out, void* ws, size_t ws_bytes) {
-  if (!A || !out || rows < 0 || cols < 0) return GPK_E_ARG;
+  if ((!A && rows > 0 && cols > 0) || !out || rows < 0 || cols < 0) return GPK_E_ARG;
   if (!ws || ws_bytes < gpk_reduce_workspace_bytes(rows)) return GPK_E_WORKSPACE;
   int nb = rows < MAXPART ? rows : MAXPART;
   if (nb < 1) nb = 1;
@@ -921,8 +925,9 @@ __global__ __launch_bounds__(256) void symmetrize_kernel(double* __restrict__ S,
 }  // namespace
 
 extern "C" int gpk_moment_rows(void* stream, const double* B, long ldb, int n2, int d, double* Vt, long ldv) {
-  if (!B || !Vt || n2 < 0 || d <= 0 || ldb < d || ldv < n2) return GPK_E_ARG;
+  if (n2 < 0 || d <= 0 || ldb < d || ldv < n2) return GPK_E_ARG;
   if (n2 == 0) return 0;
+  if (!B || !Vt) return GPK_E_ARG;
   hipLaunchKernelGGL(moment_rows_kernel, dim3((unsigned)gpk_cdiv(n2, 256)), dim3(256), 0, (hipStream_t)stream, B, ldb, n2, d, Vt, ldv);
   GPK_LAUNCH_CHECK();
   return 0;
@@ -941,8 +946,9 @@ extern "C" int gpk_stationary_adjoint_tail(void* stream, const double* R, long l
 
 extern "C" int gpk_adam_step(void* stream, double* p, const double* g, double* m, double* v, long n, double beta1, double beta2,
                              double epsilon, double step, int maximise) {
-  if (!p || !g || !m || !v || n < 0) return GPK_E_ARG;
+  if (n < 0) return GPK_E_ARG;
   if (n == 0) return 0;
+  if (!p || !g || !m || !v) return GPK_E_ARG;
   const long nb = (n + 255) / 256;
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, beta1, beta2,
                      epsilon, step, maximise ? -1.0 : 1.0);
@@ -951,8 +957,9 @@ extern "C" int gpk_adam_step(void* stream, double* p, const double* g, double* m
 }
 
 extern "C" int gpk_symmetrize(void* stream, double* S, int n, long lds) {
-  if (!S || n < 0 || lds < n) return GPK_E_ARG;
+  if (n < 0 || lds < n) return GPK_E_ARG;
   if (n == 0) return 0;
+  if (!S) return GPK_E_ARG;
   const unsigned nb = (unsigned)gpk_cdiv(n, 32);
   hipLaunchKernelGGL(symmetrize_kernel, dim3(nb, nb), dim3(256), 0, (hipStream_t)stream, S, n, lds);
   GPK_LAUNCH_CHECK();
@@ -961,8 +968,9 @@ extern "C" int gpk_symmetrize(void* stream, double* S, int n, long lds) {
 
 extern "C" int gpk_lowrank_axpy(void* stream, double alpha, const double* X, long ldx, const double* U, long ldu, const double* V, long ldv,
                                 int m, int n, int k, double* out, long ldo) {
-  if (!X || !U || !V || !out || m < 0 || n < 0 || k <= 0 || k > 16 || ldx < n || ldo < n || ldu < k || ldv < k) return GPK_E_ARG;
+  if (m < 0 || n < 0 || k <= 0 || k > 16 || ldx < n || ldo < n || ldu < k || ldv < k) return GPK_E_ARG;
   if (m == 0 || n == 0) return 0;
+  if (!X || !U || !V || !out) return GPK_E_ARG;
   dim3 grid((unsigned)gpk_cdiv(gpk_cdiv(n, 2), 256), (unsigned)(m < 2048 ? m : 2048));
   hipLaunchKernelGGL(lowrank_axpy_kernel, grid, dim3(256), 0, (hipStream_t)stream, alpha, X, ldx, U, ldu, V, ldv, m, n, k, out, ldo);
   GPK_LAUNCH_CHECK();

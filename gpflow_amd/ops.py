@@ -53,6 +53,8 @@ def _rowmajor(t: torch.Tensor, name: str) -> int:
     """Leading dimension of a 2-D row-major view (last stride 1)."""
     if t.dim() != 2:
         raise ValueError(f"{name}: expected a matrix, got shape {tuple(t.shape)}")
+    if t.numel() == 0:   # no elements: the strides of an empty tensor mean nothing (include/gpk.h, empty operands)
+        return int(max(t.shape[1], 1))
     if t.shape[1] > 1 and t.stride(1) != 1:
         raise _lib.GpkError(f"{name}: last dimension must be contiguous")
     if t.shape[0] > 1:
@@ -109,6 +111,8 @@ def kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, variance: flo
         if lower_only:
             out.zero_()
     _chk(out, "out", 2)
+    if n1 == 0 or n2 == 0:   # nothing to compute (and X2 = NULL would mean K(X1, X1) at the C-ABI)
+        return out
     ls, ard = _ls_host(lengthscales, d)
     rc = lib.gpk_kernel_matrix(_stream(), KERNEL_FAMILIES[family], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
                                X2.data_ptr() if X2 is not None else None, n2,
@@ -135,6 +139,8 @@ def kernel_matrix_hadamard(X1: torch.Tensor, X2: torch.Tensor, G: torch.Tensor, 
     if out is None:
         out = torch.empty((n1, n2), dtype=torch.float64, device=X1.device)
     _chk(out, "out", 2)
+    if n1 == 0 or n2 == 0:
+        return out
     ls, ard = _ls_host(lengthscales, d)
     rc = lib.gpk_kernel_matrix_hadamard(_stream(), KERNEL_FAMILIES[family], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
                                         X2.data_ptr(), n2, _rowmajor(X2, "X2"), d, ls, ard, float(variance),
@@ -166,6 +172,8 @@ def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch
     if out is None:
         out = torch.empty((n1, n2), dtype=torch.float64, device=X1.device)
     _chk(out, "out", 2)
+    if n1 == 0 or n2 == 0:   # nothing to compute (and X2 = NULL would mean K(X1, X1) at the C-ABI)
+        return out
     ls, ard = _ls_host(lengthscales, d)
     rc = lib.gpk_kernel_matrix_combine(_stream(), KERNEL_FAMILIES[family], {"mul": 1, "add": 2, "dr2": 3}[op], X1.data_ptr(), n1,
                                        _rowmajor(X1, "X1"), X2.data_ptr() if X2 is not None else None, n2,

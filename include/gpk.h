@@ -11,6 +11,10 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls only enqueue work,
  *     they never synchronise; scratch comes from the caller's workspace;
  *   - small hyper-parameter vectors (lengthscales) are HOST pointers, copied into kernel arguments;
+ *   - empty operands: a pointer to an operand with no elements (0 rows or 0 columns) may be NULL -- a fresh empty tensor
+ *     has no storage -- and the call then writes what the empty case defines: nothing for an empty output, the plain
+ *     sum over no terms for a reduction (e.g. gpk_gaussian_varexp_sum with rows = 0 writes 0, gpk_svgp_elbo_shard writes
+ *     [0, KL]), and beta C for gpk_gemm_nt with k = 0 (exact zeros for beta = 0; C is not read then);
  *   - return value: 0 ok, <0 bad argument (GPK_E_*), >0 HIP runtime error code (hipError_t);
  *   - numerical failure (non-positive pivot) is reported LAPACK-style through a device int
  *     `info` (0 = ok, j+1 = first bad pivot column) that the caller reads when it next syncs

@@ -196,8 +196,13 @@ def trsm_(B, L, invd, *, trans=0):
 
 
 def gemm_nt(A, B, *, alpha=1.0, beta=0.0, C=None, b_tri=0, c_lower=False, a_tri=0, k_split=False, zero_skipped=True):
+    # the device refuses these flag values (gpk_gemm_nt: GPK_E_ARG)
+    assert b_tri in (0, 1, 2) and a_tri in (0, 1, 2), (b_tri, a_tri)
     if k_split:   # batch entries = consecutive K chunks of one product; the structure statements are about the unsplit column index
         assert A.dim() == 3 and B.dim() == 3 and A.shape[0] == B.shape[0] and A.shape[2] % 16 == 0
+        if b_tri:   # the hint must be TRUE of the concatenated B as well: the device skips the K ranges it declares zero
+            B2 = _np(torch.cat(list(B), dim=1))
+            assert np.all((np.tril(B2, -1) if b_tri == 1 else np.triu(B2, 1)) == 0), "b_tri set on a K-split B without that structure"
     if a_tri:   # the hint must be TRUE: the device kernel skips the K range it declares zero
         A2 = _np(torch.cat(list(A), dim=1)) if k_split else _np(A if A.dim() == 2 else A[0])
         assert np.all((np.tril(A2, -1) if a_tri == 1 else np.triu(A2, 1)) == 0), "a_tri set on a matrix without that structure"
@@ -279,6 +284,7 @@ def diag_add_(A, v):
 def gaussian_varexp_sum(Y, fmean, *, s0, ssq, knn, noise_variance, mean_const=0.0, s0_per_latent=False,
                         want_fvar=False):
     P = fmean.shape[1]
+    assert 1 <= P <= 16, P    # gpk_gaussian_varexp_sum: GPK_E_ARG outside 1 .. 16 latents
     knn = np.broadcast_to(np.atleast_1d(np.asarray(knn, dtype=np.float64)), (P,)) if np.size(knn) in (1, P) else None
     fv = np.tile(knn[None, :], (fmean.shape[0], 1)).astype(np.float64)
     if s0 is not None:
@@ -293,6 +299,7 @@ def gaussian_varexp_sum(Y, fmean, *, s0, ssq, knn, noise_variance, mean_const=0.
 
 def gauss_kl_white(q_mu, q_sqrt):
     M, P = q_mu.shape
+    assert M >= 1 and P >= 1, (M, P)    # gpk_gauss_kl_white: GPK_E_ARG
     if q_sqrt.dim() == 2:      # q_diag: std-devs [M, P]
         s = _np(q_sqrt)
         kl = 0.5 * ((_np(q_mu) ** 2).sum() - M * P - np.log(s ** 2).sum() + (s * s).sum())
@@ -326,6 +333,7 @@ def sumsq(A, *, upper_only=False):
 
 def sum_log_diag(L):
     L3 = L if L.dim() == 3 else L.unsqueeze(0)
+    assert min(L3.shape[1], L3.shape[2]) >= 1, tuple(L.shape)    # gpk_sum_log_diag: GPK_E_ARG for n = 0
     return torch.from_numpy(np.log(np.diagonal(_np(L3), axis1=1, axis2=2)).sum(1))
 
 
@@ -343,6 +351,7 @@ def project(At, LqT):
 def gpr_lml(X, Y, *, variance, lengthscales, noise_variance, mean_const=0.0, family="SquaredExponential", ws=None):
     """The fused driver, emulated by the same chain of primitives it runs (potrf.hip: gpk_gpr_lml)."""
     n, P = Y.shape
+    assert n >= 1 and P >= 1, (n, P)    # gpk_gpr_lml: GPK_E_ARG
     T = torch.empty((n + P, n), dtype=torch.float64)
     nv = _noise(noise_variance, n)
     kernel_matrix(X, None, variance=variance, lengthscales=lengthscales, family=family, diag_add=0.0 if isinstance(nv, np.ndarray) else nv,
@@ -366,6 +375,7 @@ def svgp_elbo_shard_sep(Z, Xb, Yb, q_mu, q_sqrt, *, variances, lengthscales, fam
     """gpk_svgp_elbo_shard_sep emulated by its chain of primitives (whitened; one kernel per latent; full q_sqrt)."""
     P = q_mu.shape[1]
     M, rows = Z.shape[-2], Xb.shape[0]
+    assert 1 <= P <= 16 and M >= 1, (P, M)    # gpk_svgp_elbo_shard_sep: GPK_E_ARG
     ls = np.asarray(lengthscales, dtype=np.float64)
     T = torch.empty((P, M + rows, M), dtype=torch.float64)
     for p in range(P):
@@ -398,6 +408,7 @@ def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_va
                     family="SquaredExponential", ws=None, out=None, info=None, whiten=True):
     """gpk_svgp_elbo_shard emulated by its own chain of primitives (shared kernel; whitened, or un-whitened on one trapezoid)."""
     M, rows, P = Z.shape[0], Xb.shape[0], q_mu.shape[1]
+    assert 1 <= P <= 16 and M >= 1, (P, M)    # gpk_svgp_elbo_shard: GPK_E_ARG
     kw = dict(variance=variance, lengthscales=lengthscales, family=family)
     if not whiten and q_sqrt.dim() == 2:
         # un-whitened, diagonal q_sqrt: [Kuu ; Kfu ; q_mu^T ; I] -> A^T, (Lm^-1 q_mu)^T, Lm^-T (potrf.hip, round 5)
@@ -516,4 +527,5 @@ def symmetrize_(S):
 
 
 def lowrank_axpy(alpha, X, U, V):
+    assert 0 < U.shape[1] <= 16 and tuple(V.shape) == (X.shape[1], U.shape[1]) and U.shape[0] == X.shape[0]   # gpk_lowrank_axpy
     return alpha * X + U @ V.t()
