@@ -376,16 +376,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p, int gx, int
 // previous rest-update.  Here a thread issues ALL its loads -- eight slabs of A and B (32 x 16 bytes) and its 16 values of C --
 // before the first barrier; the slabs then go through the same two 18-KB LDS buffers with the same fragment layout, slab order
 // and epilogue arithmetic as the generic kernel (bit-identical results).  36 KB of LDS: fits beside any other workgroup.
-// prio: s_setprio of the whole workgroup (its waves share their SIMDs with MFMA-bound waves of the bulk kernel).
-__global__ __launch_bounds__(256, 2) void gemm_nt_pre64(GemmArgs p, int gx, int gy, int total, int compact, int prio) {
+__global__ __launch_bounds__(256, 2) void gemm_nt_pre64(GemmArgs p, int gx, int gy, int total, int compact) {
   constexpr int BM = 64, BN = 64, MAXS = 8;
   constexpr int BUF = (BM + BN) * LDSS;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (p.sig_ptr && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0)
     __hip_atomic_store(p.sig_ptr, p.sig_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (prio == 1) __builtin_amdgcn_s_setprio(1);
-  else if (prio == 2) __builtin_amdgcn_s_setprio(2);
-  else if (prio == 3) __builtin_amdgcn_s_setprio(3);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;   // wave w: rows 16 w .. 16 w + 15, all 64 columns
   const int bz = blockIdx.y;
@@ -494,7 +490,7 @@ bool pre64_ok(const GemmArgs& a) {
   return true;
 }
 
-int launch_pre64(hipStream_t s, const GemmArgs& a, int prio) {
+int launch_pre64(hipStream_t s, const GemmArgs& a) {
   constexpr size_t LDS_BYTES = 2 * (size_t)(64 + 64) * LDSS * sizeof(double);
   const int gx = gpk_cdiv(a.n, 64), gy = gpk_cdiv(a.m, 64);
   if (gx <= 0 || gy <= 0) return 0;
@@ -515,7 +511,7 @@ int launch_pre64(hipStream_t s, const GemmArgs& a, int prio) {
   // (A/B, level: few tiles asking for 80 KB of LDS so that they cannot share a compute unit with a capped bulk workgroup and run on the CUs
   //  the cap leaves free -- Cm 1.734 - 1.745 against 1.741 - 1.758 ms, profiles/r06_ab_rest_pre64.log; s_setprio 1 / 3 likewise)
   hipLaunchKernelGGL(gemm_nt_pre64, dim3((unsigned)total, (unsigned)(a.batch > 0 ? a.batch : 1), 1), dim3(256), LDS_BYTES, s, a, gx, gy,
-                     total, compact, prio);
+                     total, compact);
   GPK_LAUNCH_CHECK();
   return 0;
 }
@@ -890,27 +886,26 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_fast(GemmArgs p, int gx, int g
 // counters of the tile-queue launches: a ring of device words per device, never reset -- a launch of `fetches` fetches (one per tile
 // and one failing fetch per workgroup) on a word leaves it at a value the host knows, which is the base of the next launch on that
 // word (two launches would have to be 1024 launches apart AND in flight together to meet on a word).  No memset, no packet.
-int queue_slot(unsigned fetches, int words, int** out, unsigned* base) {   // words: 1, or 8 (one per XCD, all advancing alike)
+int queue_slot(unsigned fetches, int** out, unsigned* base) {
   constexpr int kRing = 1024, kMaxDev = 16;
   static std::mutex mu;
-  static int* ring[2][kMaxDev] = {};
-  static unsigned* value[2][kMaxDev] = {};
-  static unsigned next[2][kMaxDev] = {};
-  const int w = words == 8 ? 1 : 0;
+  static int* ring[kMaxDev] = {};
+  static unsigned* value[kMaxDev] = {};
+  static unsigned next[kMaxDev] = {};
   int dev = 0;
   GPK_HIP(hipGetDevice(&dev));
   if (dev < 0 || dev >= kMaxDev) return GPK_E_UNSUPPORTED;
   std::lock_guard<std::mutex> lock(mu);
-  if (!ring[w][dev]) {
-    GPK_HIP(hipMalloc((void**)&ring[w][dev], sizeof(int) * kRing * words));
-    GPK_HIP(hipMemset(ring[w][dev], 0, sizeof(int) * kRing * words));
-    value[w][dev] = (unsigned*)calloc(kRing, sizeof(unsigned));
-    if (!value[w][dev]) return GPK_E_ARG;
+  if (!ring[dev]) {
+    GPK_HIP(hipMalloc((void**)&ring[dev], sizeof(int) * kRing));
+    GPK_HIP(hipMemset(ring[dev], 0, sizeof(int) * kRing));
+    value[dev] = (unsigned*)calloc(kRing, sizeof(unsigned));
+    if (!value[dev]) return GPK_E_ARG;
   }
-  const unsigned slot = next[w][dev]++ % kRing;
-  *out = ring[w][dev] + (size_t)slot * words;
-  *base = value[w][dev][slot];
-  value[w][dev][slot] += fetches;
+  const unsigned slot = next[dev]++ % kRing;
+  *out = ring[dev] + slot;
+  *base = value[dev][slot];
+  value[dev][slot] += fetches;
   return 0;
 }
 
@@ -970,20 +965,8 @@ int launch_fast(hipStream_t s, const GemmArgs& a) {
       return 0;
     }
   }
-  // Tail split (round 5 EXPERIMENT, off: measured no gain).  The N = 16384 trailing updates take 146 us + 0.414 us per tile
-  // (7139 tiles: 3102 us ... 1224 tiles: 653 us), i.e. ~0.7 of a 205-us tile round of ramp and drain per launch, 9 % of the
-  // 25 ms those launches sum to.  If that were the partly filled LAST round, running the remainder as 64 x 64 quarters on the
-  // generic kernel (four times the workgroups, a quarter of the tile time) would recover most of it; built and measured
-  // (profiles/r05_ab_gpr_tail_split.log): 31.4 - 31.6 against 31.25 ms -- the overhead does not depend on the remainder
-  // (5459 tiles = 11.006 rounds take 11.45 round times, 4949 = 9.98 rounds 10.3): workgroups drift apart over fifteen rounds
-  // and the drain is the same ~0.7 round whatever the tile count.
   int tail_tiles = 0;
-  if (EPI == 0 && a.c_lower && a.max_wgs == 0 && nb == 1 && !a.b_tri && !a.a_tri && GPK_TUNE(TAIL_SPLIT, 0)) {
-    const int slots = 2 * (a.stagger_first > 0 ? a.stagger_first : 256);
-    const int r = total % slots;
-    if (total >= 2 * slots && r > 0 && r * 100 <= slots * GPK_TUNE(TAIL_SPLIT_PCT, 50)) tail_tiles = r;
-  }
-  // The same split DOES pay for the capped launches of the extra-row stream (round 5): 224 persistent workgroups walk 768 / 512 /
+  // Tail split of the capped launches of the extra-row stream (round 5): 224 persistent workgroups walk 768 / 512 /
   // 256 tiles in 4 / 3 / 2 rounds of ~78 us where 3.43 / 2.29 / 1.14 would do -- a few rounds, no drift, and that stream is the
   // critical path of the SVGP step.  The whole rounds stay on the persistent workgroups; the remainder runs as 64 x 64 quarters
   // on every compute unit, for about a third of a round.
@@ -1025,7 +1008,7 @@ int launch_fast(hipStream_t s, const GemmArgs& a) {
     const unsigned wgs = (unsigned)(all < qw ? all : qw);
     int* q = nullptr;
     unsigned qbase = 0;
-    const int rcq = queue_slot((unsigned)all + wgs, 1, &q, &qbase);
+    const int rcq = queue_slot((unsigned)all + wgs, &q, &qbase);
     if (rcq) return rcq;
     b.queue = q;
     b.queue_base = (int)qbase;
@@ -1078,13 +1061,7 @@ bool fast_ok(const GemmArgs& a) {
 // only overwrites rows the workgroup alone has read.
 constexpr int SM_BM = 16, SM_BN = 128, SM_THREADS = 512;
 
-// kparts = 2 (round 6): K is staged in two halves -- (16 + 128) rows of 64 + 2 doubles = 74 KB instead of 146 KB -- so that a
-// workgroup of this kernel FITS BESIDE a capped bulk workgroup of the extra-row stream (84 KB, launch_fast) on the same compute
-// unit.  With the whole-K image the chain's solve / strip needed compute units free of bulk work: 32 of 256 during the capped
-// updates of an SVGP step, i.e. three rounds of ~10 us for 88 workgroups (profiles/r06_step_timeline.txt: 18 - 50 us per
-// launch instead of 7.5).  One more staging round trip per launch (~2 us) when the chip is empty, which is why it is a choice of
-// the caller (GemmArgs::small_kparts).
-__global__ __launch_bounds__(SM_THREADS) void gemm_nt_small(GemmArgs p, int ldk, int kparts) {
+__global__ __launch_bounds__(SM_THREADS) void gemm_nt_small(GemmArgs p, int ldk) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1144,40 +1121,34 @@ __global__ __launch_bounds__(SM_THREADS) void gemm_nt_small(GemmArgs p, int ldk,
         acc0[e] = sc * C[(long)row * p.ldc + cc];
       }
     }
-    const int kch = kc / kparts;   // (kparts == 2: the launcher made sure kc is a multiple of 32)
-    for (int part = 0; part < kparts; ++part) {
-      const int kbp = kb + part * kch;
-      // ---- stage: row q of the 144 (16 A rows; 128 B rows: first pass only unless K is staged in parts), one LDS-DMA
-      // instruction each ----------------------------------------------------------------------------------------------
-      if (2 * lane < kch) {
-        for (int q = wave; q < ((first || kparts > 1) ? SM_BM + SM_BN : SM_BM); q += SM_THREADS / 64) {
-          const double* src;
-          if (q < SM_BM) {
-            int rr = m0 + q;
-            rr = rr < p.m ? rr : p.m - 1;
-            src = A + (long)rr * p.lda + kbp;
-          } else {
-            int rr = n0 + q - SM_BM;
-            rr = rr < p.n ? rr : p.n - 1;
-            src = B + (long)rr * p.ldb + kbp;
-          }
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 2 * lane),
-                                           (__attribute__((address_space(3))) void*)(smem + q * ldk), 16, 0, 0);
+    // ---- stage: row q of the 144 (16 A rows; 128 B rows: first pass only), one LDS-DMA instruction each ----------------
+    if (2 * lane < kc) {
+      for (int q = wave; q < (first ? SM_BM + SM_BN : SM_BM); q += SM_THREADS / 64) {
+        const double* src;
+        if (q < SM_BM) {
+          int rr = m0 + q;
+          rr = rr < p.m ? rr : p.m - 1;
+          src = A + (long)rr * p.lda + kb;
+        } else {
+          int rr = n0 + q - SM_BM;
+          rr = rr < p.n ? rr : p.n - 1;
+          src = B + (long)rr * p.ldb + kb;
         }
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 2 * lane),
+                                         (__attribute__((address_space(3))) void*)(smem + q * ldk), 16, 0, 0);
       }
-      __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): the LDS-DMA rows of this wave have landed (and the C preload)
-      __syncthreads();
-      const double* ap = As + r * ldk + g;
-      const double* bp = Bs + (wave * 16 + r) * ldk + g;
-      const int nkk = kch >> 2;
+    }
+    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): the LDS-DMA rows of this wave have landed (and the C preload)
+    __syncthreads();
+    const double* ap = As + r * ldk + g;
+    const double* bp = Bs + (wave * 16 + r) * ldk + g;
+    const int nkk = kc >> 2;
 #pragma unroll 4
-      for (int kk = 0; kk < nkk; kk += 2) {
-        const double a0 = ap[kk * 4], b0 = bp[kk * 4];
-        const double a1 = ap[kk * 4 + 4], b1 = bp[kk * 4 + 4];
-        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc1, 0, 0, 0);
-      }
-      if (part + 1 < kparts) __syncthreads();  // the image in LDS is about to be replaced by the next part
+    for (int kk = 0; kk < nkk; kk += 2) {
+      const double a0 = ap[kk * 4], b0 = bp[kk * 4];
+      const double a1 = ap[kk * 4 + 4], b1 = bp[kk * 4 + 4];
+      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc1, 0, 0, 0);
     }
     first = false;
     if (col < p.n) {
@@ -1191,166 +1162,8 @@ __global__ __launch_bounds__(SM_THREADS) void gemm_nt_small(GemmArgs p, int ldk,
   }
 }
 
-// =====================================================================================================
-// Fused panel kernel of a single-leaf panel of the latency chain (round 6): the in-place panel solve  S = A21 X^T  AND the strip
-//  C[:, next block column] -= S S_top^T  in ONE launch -- the two one-shot launches above, back to back on the panel stream, cost
-// 7.3 + 7.7 us, most of it launch ramp, a second staging round trip of the rows a workgroup had just produced, and the drain
-// of the first kernel.  A workgroup owns 16 rows as before.  Phase 1 is gemm_nt_small's solve (same staging, same arithmetic:
-// two alternating accumulators over K = 128); the solved rows go to global memory AND stay in LDS as the A operand of phase 2.
-// Phase 2 needs the solved rows of the NEXT diagonal block (the first `nbw` workgroups' rows) as its B tile: those workgroups
-// count themselves in `cnt[0]` once their rows are released; everybody polls it (bounded), then stages the B tile from L2 and
-// runs gemm_nt_small's update on it.  The last workgroup through phase 1 (`cnt[1]`) publishes "panel solved" (sig_ptr) -- earlier
-// than the strip's entry signal used to.  Workgroups are dispatched in index order, so the producers (indices 0 .. nbw-1)
-// are resident before any consumer can occupy a compute unit; the results are bit-identical to the two-launch form.
-struct PanelFusedArgs {
-  double* P; long lda;            // rows below the leaf of the panel's columns: [m, 128] (in / out)
-  const double* X;                // the leaf's block inverse [128, 128], row stride 128
-  double* C;                      // the next block column of the same rows: [m, n2]
-  int m, n2;                      // rows; columns of the strip (<= 128)
-  int* cnt;                       // two zeroed words: producers done, workgroups through phase 1
-  int* sig_ptr; int sig_val;      // "panel solved"
-  const int* wait_ptr; int wait_val; int* wait_info;   // "previous rest-update done" (before C is touched)
-};
-
-__global__ __launch_bounds__(SM_THREADS) void panel_fused_kernel(PanelFusedArgs p) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  constexpr int K = 128, ldk = K + 2;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  const int m0 = blockIdx.x * SM_BM;
-  const int nwg = gridDim.x, nbw = (p.n2 + SM_BM - 1) / SM_BM < nwg ? (p.n2 + SM_BM - 1) / SM_BM : nwg;
-  double* As = smem;
-  double* Bs = smem + SM_BM * ldk;
-  // ---- phase 1: S = A21 X^T (X lower triangular: b_tri 2 with one column tile = the whole K) ----------------------------------
-  for (int q = wave; q < SM_BM + SM_BN; q += SM_THREADS / 64) {
-    const double* src;
-    if (q < SM_BM) {
-      int rr = m0 + q;
-      rr = rr < p.m ? rr : p.m - 1;
-      src = p.P + (long)rr * p.lda;
-    } else {
-      src = p.X + (long)(q - SM_BM) * K;
-    }
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 2 * lane),
-                                     (__attribute__((address_space(3))) void*)(smem + q * ldk), 16, 0, 0);
-  }
-  __builtin_amdgcn_s_waitcnt(0x0070);
-  __syncthreads();
-  const double* ap = As + r * ldk + g;
-  const double* bp = Bs + (wave * 16 + r) * ldk + g;
-  d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = acc0;
-#pragma unroll 4
-  for (int kk = 0; kk < K / 4; kk += 2) {
-    const double a0 = ap[kk * 4], b0 = bp[kk * 4];
-    const double a1 = ap[kk * 4 + 4], b1 = bp[kk * 4 + 4];
-    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc1, 0, 0, 0);
-  }
-  // The producers of the B tile (the first nbw workgroups) write their rows THROUGH to memory (agent-scope stores) and count
-  // themselves in; everybody else stores normally -- their rows are released by the end of the kernel, and "panel solved" is
-  // announced by the entry signal of the next kernel of the panel stream (the next leaf).  (A __threadfence() per workgroup --
-  // an L2 write-back each -- made the first version of this kernel 10 us slower than the two launches it replaces.)
-  const bool producer = (int)blockIdx.x < nbw;
-  double sv[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    sv[e] = 1.0 * (acc0[e] + acc1[e]);
-    const int row = m0 + g + 4 * e;
-    if (row < p.m) {
-      double* dst = p.P + (long)row * p.lda + wave * 16 + r;
-      if (producer) __hip_atomic_store(dst, sv[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else *dst = sv[e];
-    }
-  }
-  if (producer) __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0): this thread's write-through stores have been acknowledged
-  __syncthreads();                       // every wave is done reading As / Bs
-#pragma unroll
-  for (int e = 0; e < 4; ++e) As[(g + 4 * e) * ldk + wave * 16 + r] = sv[e];   // the solved rows: A operand of phase 2
-  __syncthreads();
-  if (tid == 0) {
-    if (producer) __hip_atomic_fetch_add(p.cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    // ---- wait: the B tile's rows are solved; the previous rest-update has left the strip's columns
-    const long long t0 = wall_clock64();
-    bool timed_out = false;
-    while (__hip_atomic_load(p.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nbw) {
-      if (wall_clock64() - t0 >= 50000000LL) { timed_out = true; break; }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    if (p.wait_ptr) {
-      while ((int)(__hip_atomic_load(p.wait_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - p.wait_val) < 0) {
-        if (wall_clock64() - t0 >= 50000000LL) { timed_out = true; break; }
-        __builtin_amdgcn_s_sleep(2);
-      }
-    }
-    if (timed_out && p.wait_info) atomicMax(p.wait_info, 0x7fffffff);
-  }
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  // ---- phase 2: C[rows, 0:n2] -= S S_top^T, lower tiles only (c_lower: a workgroup whose rows lie above the block is skipped) ----
-  if (p.n2 <= 0) return;
-  for (int q = wave; q < SM_BN; q += SM_THREADS / 64) {
-    int rr = q < p.n2 ? q : p.n2 - 1;
-    rr = rr < p.m ? rr : p.m - 1;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.P + (long)rr * p.lda + 2 * lane),
-                                     (__attribute__((address_space(3))) void*)(Bs + q * ldk), 16, 0, 0);
-  }
-  const int col = wave * 16 + r;
-  d4 c0 = {0.0, 0.0, 0.0, 0.0}, c1 = c0;
-  {
-    const int cc = col < p.n2 ? col : p.n2 - 1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      int row = m0 + g + 4 * e;
-      row = row < p.m ? row : p.m - 1;
-      c0[e] = -1.0 * p.C[(long)row * p.lda + cc];     // (beta / alpha) C with alpha = -1, beta = 1, as gemm_nt_small does
-    }
-  }
-  __builtin_amdgcn_s_waitcnt(0x0070);
-  __syncthreads();
-#pragma unroll 4
-  for (int kk = 0; kk < K / 4; kk += 2) {
-    const double a0 = ap[kk * 4], b0 = bp[kk * 4];
-    const double a1 = ap[kk * 4 + 4], b1 = bp[kk * 4 + 4];
-    c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, c1, 0, 0, 0);
-  }
-  if (col < p.n2) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int row = m0 + g + 4 * e;
-      if (row < p.m) p.C[(long)row * p.lda + col] = -1.0 * (c0[e] + c1[e]);
-    }
-  }
-}
-
-}  // namespace
-
-bool gpk_panel_fused_ok(const double* P, long lda, const double* X, int m, int nb, int n2) {
-  return nb == 128 && m > 0 && n2 > 0 && n2 <= 128 && !(lda & 1) && !(reinterpret_cast<uintptr_t>(P) & 15) &&
-         !(reinterpret_cast<uintptr_t>(X) & 15) && gpk_cdiv(m, SM_BM) <= GPK_TUNE(SMALL_MAX_WGS, 512) && lda <= (1L << 21);
-}
-
-int gpk_launch_panel_fused(hipStream_t s, double* P, long lda, const double* X, double* C, int m, int n2, int* cnt, int* sig_ptr,
-                           int sig_val, const int* wait_ptr, int wait_val, int* wait_info) {
-  constexpr size_t lds = (size_t)(SM_BM + SM_BN) * 130 * sizeof(double);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(panel_fused_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  GPK_HIP(attr);
-  PanelFusedArgs a{P, lda, X, C, m, n2, cnt, sig_ptr, sig_val, wait_ptr, wait_val, wait_info};
-  hipLaunchKernelGGL(panel_fused_kernel, dim3((unsigned)gpk_cdiv(m, SM_BM)), dim3(SM_THREADS), lds, s, a);
-  GPK_LAUNCH_CHECK();
-  return 0;
-}
-
-namespace {
-
 int launch_small(hipStream_t s, const GemmArgs& a) {
-  // K staged in two halves (GemmArgs::small_kparts == 2) when every K range of the launch splits into whole 16-slabs: plain
-  // K = 64 / 128 operands, or the single-column-tile triangular solve against a leaf's block inverse (b_tri 2, K range = n <= 128)
-  const bool parts2 = a.small_kparts == 2 && !(a.k & 31) && (!a.b_tri || (a.b_tri == 2 && a.n <= SM_BN && a.b_tri_off == 0 && !(a.n & 31)));
-  const int kparts = parts2 ? 2 : 1;
-  const int ldk = a.k / kparts + 2;
+  const int ldk = a.k + 2;
   const size_t lds = (size_t)(SM_BM + SM_BN) * ldk * sizeof(double);
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_small),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1362,7 +1175,7 @@ int launch_small(hipStream_t s, const GemmArgs& a) {
   else if (a.small_loop && a.max_wgs <= 0 && gy * gxs > 512u) gy = (512u + gxs - 1) / gxs;
   dim3 grid(gxs, gy, (unsigned)(a.batch > 0 ? a.batch : 1));
   g_last_kind = 1;
-  hipLaunchKernelGGL(gemm_nt_small, grid, dim3(SM_THREADS), lds, s, a, ldk, kparts);
+  hipLaunchKernelGGL(gemm_nt_small, grid, dim3(SM_THREADS), lds, s, a, ldk);
   GPK_LAUNCH_CHECK();
   return 0;
 }
@@ -1384,7 +1197,6 @@ struct GroupSolveArgs {
   const double* X;               // block inverses of the group, consecutive [nb][128][128]
   int rows, nb;
   long strideE, strideEo, strideL, strideX;   // batched form (blockIdx.y = problem): element offsets between problems
-  int stage_barrier;                          // (A/B build) a workgroup barrier at EVERY pipeline stage of group_solve2_kernel
   int j0, j1;                                 // group_solve2_kernel: leaf blocks [j0, j1) are solved by THIS launch (the blocks before j0 by
                                               // earlier ones); the updated, still unsolved blocks >= j1 go back to E (E == Eo then)
 };
@@ -1497,9 +1309,8 @@ constexpr int GS2_LDK = 130;                     // A rows: 128 + 2 doubles
 template <int QK, int RING>
 constexpr size_t gs2_lds() { return (size_t)(32 * GS2_LDK + RING * 128 * QK) * sizeof(double); }
 
-// QK = K columns per pipeline stage.  32: 40 stages of 16 MFMAs per wave, 132 KB of LDS (a compute unit of its own).
-// 16: 80 stages of 8 MFMAs, 80.5 KB -- a workgroup then fits BESIDE one 73.7 KB workgroup of the tiled GEMM, so the in-group
-// solve no longer waits for the compute units that the chain's rest-update (launched at the same flag) has just taken.
+// QK = K columns per pipeline stage.  32 (the only width instantiated): 40 stages of 16 MFMAs per wave, 132 KB of LDS (a compute
+// unit of its own).
 // s_waitcnt vmcnt(n * DPW) for a wave-uniform n in 0 .. NMAX (the instruction takes an immediate)
 template <int DPW, int NMAX>
 __device__ __forceinline__ void gs2_wait_vm(int n) {
@@ -1618,7 +1429,7 @@ __global__ __launch_bounds__(512) void group_solve2_kernel(GroupSolveArgs p) {
         gs2_wait_vm<DPW, AHEAD - 1>(behind);
       }
       asm volatile("" ::: "memory");
-      if (a_changed || p.stage_barrier) {
+      if (a_changed) {
         __builtin_amdgcn_s_waitcnt(0xC07F);                      // lgkmcnt(0): this wave's A rows are in LDS
         __builtin_amdgcn_s_barrier();
       }
@@ -1736,7 +1547,6 @@ int launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo, lon
   GroupSolveArgs a{};
   a.E = E; a.lde = lde; a.Eo = Eo; a.ldeo = ldeo; a.L = Lgg; a.ldl = ldl; a.X = X; a.rows = rows; a.nb = nb;
   a.strideE = strideE; a.strideEo = strideEo; a.strideL = strideL; a.strideX = strideX;
-  a.stage_barrier = GPK_TUNE(GS2_STAGE_BARRIER, 0);
   a.j0 = j0; a.j1 = j1;
   // Which kernel: the pipelined one (32 rows per workgroup) runs its 10 block products in ~63 us whatever the row count; the
   // staged one (16 rows) needs ~45 us per ROUND of 256 workgroups (one per CU).  tools/group_solve_probe.py, 512 columns, us:
@@ -1746,13 +1556,8 @@ int launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo, lon
   const bool partial = j0 > 0 || j1 < nb;
   const long slivers16 = (long)gpk_cdiv(rows, 16) * batch;
   if (GPK_TUNE(GROUP_SOLVE_V2, 1) && (partial || slivers16 > GPK_TUNE(GROUP_SOLVE_V2_MIN_SLIVERS, 256))) {
-    // (stage width 16 -- co-resident with a tiled-GEMM workgroup -- measured 3 % SLOWER on the SVGP step, same box: 2.14 - 2.16 against
-    //  2.02 - 2.10 ms, profiles/r05_ab_extra_row_stream.log: twice the barriers, and the wait for compute units was not the larger loss)
-    switch (GPK_TUNE(GROUP_SOLVE_QK, 32) * 100 + GPK_TUNE(GROUP_SOLVE_RING, 3)) {
-      case 1603: return launch_group_solve2<16, 3>(s, a, rows, batch, max_wgs);
-      case 1605: return launch_group_solve2<16, 5>(s, a, rows, batch, max_wgs);
-      default: return launch_group_solve2<32, 3>(s, a, rows, batch, max_wgs);
-    }
+    // (stage width 16 and a ring of 5: DESIGN 6, "Closed experiments whose code was removed")
+    return launch_group_solve2<32, 3>(s, a, rows, batch, max_wgs);
   }
   unsigned gx = (unsigned)gpk_cdiv(rows, 16);
   if (max_wgs > 0 && gx * (unsigned)batch > (unsigned)max_wgs) gx = (unsigned)std::max(1, max_wgs / batch);
@@ -1925,7 +1730,6 @@ extern "C" int gpk_profile_gemm_collect(double* total_ms, long* launches, double
 
 static int launch_select(hipStream_t s, const GemmArgs& a);
 
-// the same per-launch timing for kernels outside this file (kind 7: the single-launch SVGP step kernel, mega.hip)
 // grow the record table of the profiling facility.  The table pointer is published right after realloc (the old block may
 // have moved) and the capacity only ever covers records whose two events exist: a failed hipEventCreate leaves a shorter,
 // consistent table instead of a dangling pointer (advisor, round 4).
@@ -1943,19 +1747,6 @@ static int prof_grow() {
     g_prof_cap = i + 1;
   }
   return 0;
-}
-
-int gpk_prof_begin(hipStream_t s, double flops, int kind) {
-  if (!g_prof_on) return -1;
-  if (g_prof_n == g_prof_cap && (prof_grow() != 0 || g_prof_n == g_prof_cap)) return -1;
-  ProfRec& r = g_prof[g_prof_n];
-  r.flops = flops;
-  r.kind = kind;
-  if (hipEventRecord(r.e0, s) != hipSuccess) return -1;
-  return g_prof_n++;
-}
-void gpk_prof_end(int idx, hipStream_t s) {
-  if (idx >= 0 && idx < g_prof_n) (void)hipEventRecord(g_prof[idx].e1, s);
 }
 
 int gpk_launch_gemm(hipStream_t s, const GemmArgs& a) {
@@ -1977,10 +1768,8 @@ int gpk_launch_gemm(hipStream_t s, const GemmArgs& a) {
 
 static int launch_select(hipStream_t s, const GemmArgs& a) {
   const long tiles = (long)gpk_cdiv(a.m, 128) * gpk_cdiv(a.n, 128) * (a.batch > 0 ? a.batch : 1);
-  if (a.tile64 == 2 && a.epi == 0) return launch_cfg<32, 64, 2, 2>(s, a);
-  if (a.tile64 == 3 && a.epi == 0) return launch_cfg<64, 128, 1, 4>(s, a);
   if (a.tile64 && a.epi == 0) {
-    if (GPK_TUNE(REST_PRE64, 1) && pre64_ok(a)) return launch_pre64(s, a, GPK_TUNE(REST_PRIO, 0));
+    if (GPK_TUNE(REST_PRE64, 1) && pre64_ok(a)) return launch_pre64(s, a);
     return launch_cfg<64, 64, 4, 1>(s, a);
   }
   if (!a.no_small && small_ok(a)) return launch_small(s, a);  // K <= 128, <= 512 workgroups: the latency path
@@ -2072,9 +1861,6 @@ extern "C" int gpk_gemm_nt(void* stream, int m, int n, int k, double alpha, cons
   g.a_tri = (m <= k * (ksplit ? (batch > 0 ? batch : 1) : 1)) ? ((b_tri >> 4) & 3) : 0;  // (a hint: ignoring it is always correct)
   g.k_off_step = ksplit ? k : 0;
   g.epi = 0; g.batch = batch > 0 ? batch : 1;
-  // (A/B: the tile queue for every batched launch -- the split-K products of the reverse pass, 1088 equal tiles -- is level:
-  //  training step 5.89 / 6.01 without, 6.07 / 5.95 with it, profiles/r06_ab_train_tri_products.log)
-  g.tile_queue = (g.batch > 1 || GPK_TUNE(GEMM_NT_QUEUE_SINGLE, 0)) && GPK_TUNE(GEMM_NT_QUEUE_BATCH, 0);
   if (kGpkExp) g.max_wgs = GPK_TUNE(GEMM_NT_MAX_WGS, 0);   // (A/B build only: tools/capped_gemm_probe.py)
   return gpk_launch_gemm((hipStream_t)stream, g);
 }

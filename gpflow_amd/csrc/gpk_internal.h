@@ -81,8 +81,6 @@ struct GemmArgs {
   int no_small;     // never take the one-shot LDS-DMA latency kernel (150 KB of LDS per workgroup: needs a CU free of GEMM workgroups)
   int small_loop;   // K <= 128 launches with MORE than 512 row slivers may still take the one-shot latency kernel: its workgroups
                     // then walk the row blocks with their B tile staged once (the in-group updates of the extra rows)
-  int small_kparts; // one-shot latency kernel only: 2 = stage K in two halves (74 KB of LDS per workgroup instead of 146: it then fits
-                    // beside a capped bulk workgroup on the same compute unit), else the whole K at once
   int max_wgs;      // fast path only: cap on the number of (persistent) workgroups per batch entry, 0 = one per tile
   int pair_k_align; // set by the launcher for paired triangular-K launches: time-aligned K traversal (gemm_nt_fast)
   // In-kernel stream hand-offs of the factorisation's latency chain (one-shot latency kernel only; potrf.hip, round 5).  An
@@ -97,7 +95,7 @@ struct GemmArgs {
   int* wait_info;   // device int that receives INT_MAX if the bounded wait expires (the factorisation's status word)
   int tile_queue;   // fast path, epi 0: persistent workgroups that take their tiles from a device counter (launches with more than 512 tiles)
   int* queue; int queue_base;   // set by the launcher only: that counter and its value before this launch
-  int tile64;       // epi 0 only: take the generic kernel's 64 x 64 tiles (36 KB of LDS per workgroup: fits beside any other workgroup on a CU)
+  int tile64;       // epi 0 only (flag): take the generic kernel's 64 x 64 tiles (36 KB of LDS per workgroup: fits beside any other workgroup on a CU)
   int tile_snake;   // set by the launcher only (generic kernel, under-filled triangular-K projections): heavy / light tiles alternate per CU
   int tail_first1;  // set by the launcher only (generic 64 x 64 kernel; launch_fast, "tail split"): 1 + first position, 0 = off
 };
@@ -110,36 +108,13 @@ bool gpk_gemm_takes_latency_kernel(const GemmArgs& a);   // the launch would run
 int gpk_launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo, long ldeo, int rows, const double* Lgg, long ldl,
                            const double* X, int nb, int batch = 1, long strideE = 0, long strideEo = 0, long strideL = 0,
                            long strideX = 0, int max_wgs = 0, int j0 = 0, int j1 = -1);   // max_wgs > 0: at most that many workgroups, walking the 16-row slivers
-// fused panel solve + strip of a single-leaf panel (gemm.hip, round 6): P rows below the leaf [m, 128] (solved in place), X the
-// leaf's block inverse, C the next block column of the same rows [m, n2]; cnt: two zeroed device words of this launch
-bool gpk_panel_fused_ok(const double* P, long lda, const double* X, int m, int nb, int n2);
-int gpk_launch_panel_fused(hipStream_t s, double* P, long lda, const double* X, double* C, int m, int n2, int* cnt, int* sig_ptr,
-                           int sig_val, const int* wait_ptr, int wait_val, int* wait_info);
 int gpk_gemm_tiles_n(int n);   // number of column tiles the launcher will use for n columns
 int gpk_profile_gemm_is_on();  // per-launch event timing active (bench roofline leg)
-int gpk_prof_begin(hipStream_t s, double flops, int kind);   // same facility for other kernels; returns a record index or -1
-void gpk_prof_end(int idx, hipStream_t s);
-
-// ---- single-launch SVGP step (mega.hip): A/B build only (`make exp`, GPK_MEGA=1).  Round 5 applied the stop rule of the
-// round-4 review: 2.7 - 3.0 ms at Cm against 2.0 - 2.1 ms for the multi-launch route, so the kernel, its workspace regions and
-// its entry points are compiled into libgpk_exp.so only and the product library carries no trace of them.
-#ifdef GPK_EXPERIMENTAL
-#ifndef GPK_MEGA_DEFAULT
-#define GPK_MEGA_DEFAULT 0
-#endif
-size_t gpk_mega_flag_ints(int m);
-int gpk_mega_supported(int m, int rows, int P, int ncu);
-int gpk_launch_svgp_mega(hipStream_t s, int proto, int ncu, double* T, long ld, int m, int rows, double* invd, double* Lfin, const double* LqT,
-                         long ldl, double* Cacc, const double* q_mu, int P, const double* Y, long ldy, double* s0, double* fmean,
-                         double* ssq, double* partial, int* flags, int* info, double* out, double variance, double noise,
-                         double mean_const, int min_wgs);
-#endif
 
 // ---- leaf (leaf.hip): NB x NB Cholesky + inverse of the diagonal block --------------------------
 // A: pointer to the diagonal block (row-major, lda); nb <= NB valid rows/cols.
-// sig_ptr: chain-flag word the leaf stores sig_val into on ENTRY ("everything queued before it on s has completed"), or nullptr
 int gpk_launch_leaf(hipStream_t s, double* A, long lda, long strideA, int nb, double* invd,
-                    long strideInv, int* info, int col0, int batch, int already_factored, int* sig_ptr = nullptr, int sig_val = 0);
+                    long strideInv, int* info, int col0, int batch, int already_factored);
 
 // ---- rbf.hip ---------------------------------------------------------------------------------
 // (entry point gpk_kernel_matrix is defined there)
@@ -147,7 +122,6 @@ int gpk_launch_leaf(hipStream_t s, double* A, long lda, long strideA, int nb, do
 // ---- reduce.hip: small kernels -------------------------------------------------------------------
 int gpk_launch_zero_upper(hipStream_t s, double* A, int n, long lda, int batch, long strideA);
 int gpk_launch_set_identity(hipStream_t s, double* A, int n, long lda, int batch = 1, long strideA = 0);
-int gpk_launch_diag_add_scalar(hipStream_t s, double* A, int n, long lda, double v);   // A[i,i] += v
 int gpk_probe_concurrent_kernels(hipStream_t a, hipStream_t b, int* scratch, int* concurrent);   // init-time probe (reduce.hip)
 int gpk_launch_noop(hipStream_t s);  // empty kernel (stream hand-off probe)
 int gpk_launch_wait_flag(hipStream_t s, const int* ptr, int val, int* info);   // one-wave gate: returns when (int)(*ptr - val) >= 0 (bounded)
@@ -158,16 +132,11 @@ int gpk_launch_final(hipStream_t s, int nterms, const double* const* part, const
                      const double* scale, double add, double* out);
 int gpk_launch_sumsq_stage1(hipStream_t s, const double* A, int rows, int cols, long lda,
                             int upper_only, double* part, int* count);
-struct VarexpExtra {   // optional inputs of the variational-expectation stage (reduce.hip, round 6)
-  const double* ssq_part = nullptr; int ssq_nt = 0; long ssq_stride = 0;   // ssq as the projection's slot partials [P][nt][rows]
-  const int* wait_ptr = nullptr; int wait_val = 0; int* wait_info = nullptr;   // word of the row statistics' stream (bounded wait)
-};
 int gpk_launch_varexp_stage1(hipStream_t s, const double* Y, long ldy, const double* fmean, int rows,
                              int P, const double* s0, int s0_per_latent, const double* ssq,
                              const double* knn_host, int knn_per_latent, double noise,
                              double mean_const, double* fvar_out, double* part, int* count,
-                             const double* noise_rows = nullptr,   // per-row noise variances [rows] or nullptr (constant `noise`)
-                             const VarexpExtra* ex = nullptr);
+                             const double* noise_rows = nullptr);   // per-row noise variances [rows] or nullptr (constant `noise`)
 int gpk_launch_kl_white_stage1(hipStream_t s, const double* q_mu, const double* q_sqrt, int m, int P,
                                int q_diag, double* part, int* count);
 int gpk_launch_kl_unwhite_diag_stage1(hipStream_t s, const double* LinvT, long ldl, int m, const double* W, int P, double* part,

@@ -1,8 +1,7 @@
 // Round-6 leaf: the 128 x 128 diagonal-block factorisation A = L L^T, X = L^-1 as a two-wave pivot pipeline plus six helper waves,
 // synchronised through LDS counters -- no workgroup barrier after the first instruction.
 // (Lane-level model and hazard check of the schedule: tools/leaf2_model.py; probe with in-kernel time stamps: tools/leaf_probe.hip.
-//  The round 1 - 5 leaf, leaf_device.h, still inverts an existing factor's diagonal block -- FACTORED -- and is what the A/B-only
-//  single-launch step kernel runs.)
+//  What is left of the round 1 - 5 leaf, leaf_device.h, inverts an existing factor's diagonal block.)
 //
 // What was measured on the old leaf (32 us alone: load 3.4, factor 22, invert 3.7, store 2.9): wave 0 factors the 16 x 16 diagonal
 // tiles, ~100 wave-uniform VALU instructions per 4-column panel (~900 cycles), and between two diagonal tiles it went through two

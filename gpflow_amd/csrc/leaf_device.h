@@ -1,6 +1,7 @@
-// Device code of the 128 x 128 diagonal-block factorisation (leaf): shared by the stand-alone leaf kernel (leaf.hip) and
-// the single-launch SVGP step kernel (mega.hip), which runs the same leaf inside a persistent workgroup.
-// (Moved verbatim out of leaf.hip in round 4; the description of the algorithm is at the top of leaf.hip.)
+// Device code of the round 1 - 5 leaf (description at the top of leaf.hip), reduced to what the library uses it for: the inverse of
+// the 128 x 128 diagonal block of an EXISTING factor (leaf_kernel<true>), and the tile helpers that the round-6 leaf (leaf2_device.h)
+// shares with it.  Its Cholesky arithmetic went with the A/B-only kernels that ran it: DESIGN 6, "Closed experiments whose code was
+// removed".
 #pragma once
 #include "gpk_internal.h"
 
@@ -41,180 +42,64 @@ __device__ __forceinline__ d4 mfma4(double a, double b, d4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
-// ---- 16x16 diagonal tile: Cholesky + inverse in the registers of one wave ---------------------------------
-// c = lane & 15, g = lane >> 4.  On entry (FACTORED = false) d[e] = S[g+4e][c] of the symmetric tile; on
-// entry (FACTORED = true) d[e] = L[c][4e+g] (zero above the diagonal).  On exit d[e] = L[c][4e+g] and
-// x[e] = X[4e+g][c]  (X = L^-1, exact zeros above the diagonal).
-template <bool FACTORED, int P>
-__device__ __forceinline__ void diag_panel(d4& d, d4& x, int c, int g, int lane, int& bad_col, int col0) {
+// ---- 16x16 diagonal tile of an existing factor: its inverse in the registers of one wave ---------------------
+// c = lane & 15, g = lane >> 4.  On entry d[e] = L[c][4e+g] (zero above the diagonal).  On exit x[e] = X[4e+g][c]
+// (X = L^-1, exact zeros above the diagonal).
+template <int P>
+__device__ __forceinline__ void diag_panel(const d4& d, d4& x, int c, int g) {
   if constexpr (P < 4) {
-    // 4x4 pivot block  s[a][b] = S[4P+a][4P+b]  (a >= b), wave-uniform
-    auto pick = [&](int a, int b) -> double {
-      // !FACTORED: d[P] of lane (c = 4P+b, g = a);  FACTORED: d[P] of lane (c = 4P+a, g = b)
-      return FACTORED ? readlane_d(d[P], 4 * P + a + 16 * b) : readlane_d(d[P], 4 * P + b + 16 * a);
-    };
+    // 4x4 pivot block  s[a][b] = L[4P+a][4P+b]  (a >= b), wave-uniform: d[P] of lane (c = 4P+a, g = b)
+    auto pick = [&](int a, int b) -> double { return readlane_d(d[P], 4 * P + a + 16 * b); };
     const double s00 = pick(0, 0), s10 = pick(1, 0), s20 = pick(2, 0), s30 = pick(3, 0);
     const double s11 = pick(1, 1), s21 = pick(2, 1), s31 = pick(3, 1);
     const double s22 = pick(2, 2), s32 = pick(3, 2), s33 = pick(3, 3);
-    double yop;
     const int slot = (c < 4 && g <= c) ? c * 4 + g : -1;  // lane (m = c, k = g) holds Y[m][k] of the A-operand
-#ifdef GPK_LEAF_FRACTION_FREE
-    constexpr bool kRecurrence = FACTORED;   // (A/B only, `make ffleaf`: the fraction-free pivot block below)
-#else
-    constexpr bool kRecurrence = true;
-#endif
-    if constexpr (kRecurrence) {
-      double l10, l20, l30, l21, l31, l32, r0, r1, r2, r3;
-      if constexpr (FACTORED) {
-        l10 = s10; l20 = s20; l30 = s30; l21 = s21; l31 = s31; l32 = s32;
-        r0 = 1.0 / s00; r1 = 1.0 / s11; r2 = 1.0 / s22; r3 = 1.0 / s33;
-      } else {
-        r0 = rsqrt_nr(s00);
-        l10 = s10 * r0; l20 = s20 * r0; l30 = s30 * r0;
-        const double p1 = fma(-l10, l10, s11);
-        r1 = rsqrt_nr(p1);
-        l21 = fma(-l20, l10, s21) * r1;
-        l31 = fma(-l30, l10, s31) * r1;
-        const double p2 = fma(-l21, l21, fma(-l20, l20, s22));
-        r2 = rsqrt_nr(p2);
-        l32 = fma(-l31, l21, fma(-l30, l20, s32)) * r2;
-        const double p3 = fma(-l32, l32, fma(-l31, l31, fma(-l30, l30, s33)));
-        r3 = rsqrt_nr(p3);
-        int idx = -1;
-        idx = !(p3 > 0.0) ? 3 : idx;
-        idx = !(p2 > 0.0) ? 2 : idx;
-        idx = !(p1 > 0.0) ? 1 : idx;
-        idx = !(s00 > 0.0) ? 0 : idx;
-        bad_col = (bad_col < 0 && idx >= 0) ? col0 + 4 * P + idx : bad_col;
-      }
-      // Y = inv(L4), lower triangular
-      const double y10 = -r1 * (l10 * r0);
-      const double y21 = -r2 * (l21 * r1);
-      const double y32 = -r3 * (l32 * r2);
-      const double y20 = -r2 * fma(l21, y10, l20 * r0);
-      const double y31 = -r3 * fma(l32, y21, l31 * r1);
-      const double y30 = -r3 * fma(l32, y20, fma(l31, y10, l30 * r0));
-      // flat select chain on the per-lane slot index (no divergent control flow: every Y value is wave-uniform)
-      yop = 0.0;
-      yop = (slot == 0) ? r0 : yop;
-      yop = (slot == 4) ? y10 : yop;
-      yop = (slot == 5) ? r1 : yop;
-      yop = (slot == 8) ? y20 : yop;
-      yop = (slot == 9) ? y21 : yop;
-      yop = (slot == 10) ? r2 : yop;
-      yop = (slot == 12) ? y30 : yop;
-      yop = (slot == 13) ? y31 : yop;
-      yop = (slot == 14) ? y32 : yop;
-      yop = (slot == 15) ? r3 : yop;
-    } else {
-      // ROUND-5 EXPERIMENT, NOT THE PRODUCT PATH (compiled only with -DGPK_LEAF_FRACTION_FREE): Y = inv(chol(S4)) without a
-      // square root or a division on the dependent path.  The recurrence above (pivot -> rsqrt -> scale the column -> next
-      // pivot) is ~36 DEPENDENT fp64 ops per 4-column panel; the form below needs 15 levels.  Measured on the chip it is 0.5 - 1.5 %
-      // SLOWER at step level (profiles/r05_ab_leaf_fraction_free.log: factor phase 23 - 25 us either way): wave 0 is bound by the
-      // ISSUE of ~100 wave-uniform VALU instructions per panel (7 - 9 cycles each), not by their dependent latency, and this form
-      // issues ~15 more of them.  Kept as the record of that finding.  Fraction-free elimination:
-      //   t_ij = s00 s_ij - s_i0 s_j0,   u_ij = t11 t_ij - t_i1 t_j1,   w33 = u22 u33 - u32^2
-      // are the Schur complements scaled by the previous pivots (s00 = p0, t11 = p0 p1, u22 = p0^2 p1 p2, w33 = p0^4 p1^2 p2 p3),
-      // the same row operations applied to the identity give the rows N_k of the unit-lower inverse times those scales, and
-      //   Y[k][:] = (q0 q1 ... qk) N_k   with  q0 = rsqrt(s00), q1 = rsqrt(t11), q2 = rsqrt(u22), q3 = rsqrt(w33):
-      // six dependent ops to the last scaled pivot, the four rsqrt refinements run beside each other, 15 levels in all.
-      // Same backward error as the recurrence (tools/leaf_ff_check.py: |Y S Y^T - I| equal to within a factor 1.5 for
-      // condition numbers 1e1 ... 1e12).  Range: intermediate magnitudes reach pivot^8, so entries beyond ~1e+-35 over/underflow
-      // -- and are then REPORTED as a non-positive pivot, never silently accepted (NaN / 0 fail the `> 0` tests below).
-      const double t11 = fma(s00, s11, -(s10 * s10));
-      const double t21 = fma(s00, s21, -(s20 * s10));
-      const double t31 = fma(s00, s31, -(s30 * s10));
-      const double t22 = fma(s00, s22, -(s20 * s20));
-      const double t32 = fma(s00, s32, -(s30 * s20));
-      const double t33 = fma(s00, s33, -(s30 * s30));
-      const double u22 = fma(t11, t22, -(t21 * t21));
-      const double u32 = fma(t11, t32, -(t31 * t21));
-      const double u33 = fma(t11, t33, -(t31 * t31));
-      const double w33 = fma(u22, u33, -(u32 * u32));
-      // the four rsqrt refinements (rsqrt_nr, written out) level by level, so that the in-order issue of the wave sees four
-      // independent ops per level instead of four serial six-op chains; the rows of the scaled unit-lower inverse fill the slots
-      const double y0 = __builtin_amdgcn_rsq(s00), y1 = __builtin_amdgcn_rsq(t11), y2 = __builtin_amdgcn_rsq(u22),
-                   y3 = __builtin_amdgcn_rsq(w33);
-      const double a = t11 * s00;
-      const double f0 = s00 * y0, f1 = t11 * y1, f2 = u22 * y2, f3 = w33 * y3;
-      const double n20 = fma(t21, s10, -(t11 * s20)), n21 = -(t21 * s00);
-      const double e0 = fma(-f0, y0, 1.0), e1 = fma(-f1, y1, 1.0), e2 = fma(-f2, y2, 1.0), e3 = fma(-f3, y3, 1.0);
-      const double m30 = fma(t31, s10, -(t11 * s30)), m31 = -(t31 * s00);
-      const double g0 = fma(0.375, e0, 0.5), g1 = fma(0.375, e1, 0.5), g2 = fma(0.375, e2, 0.5), g3 = fma(0.375, e3, 0.5);
-      const double h0 = y0 * e0, h1 = y1 * e1, h2 = y2 * e2, h3 = y3 * e3;
-      const double n30 = fma(u22, m30, -(u32 * n20)), n31 = fma(u22, m31, -(u32 * n21)), n32 = -(u32 * a), n33 = u22 * a;
-      const double q0 = fma(h0, g0, y0), q1 = fma(h1, g1, y1), q2 = fma(h2, g2, y2), q3 = fma(h3, g3, y3);
-      // first non-positive pivot of this panel, branch-free (all values are wave-uniform); the scaled pivots have the sign
-      // of the true ones as long as every earlier pivot is positive, which is all the "first failure" needs
-      int idx = -1;
-      idx = !(w33 > 0.0) ? 3 : idx;
-      idx = !(u22 > 0.0) ? 2 : idx;
-      idx = !(t11 > 0.0) ? 1 : idx;
-      idx = !(s00 > 0.0) ? 0 : idx;
-      bad_col = (bad_col < 0 && idx >= 0) ? col0 + 4 * P + idx : bad_col;
-      // per-lane operand  Y[m][k] = N[m][k] * rho_m:  the N entries are ready early (select chain off the critical path), the
-      // cumulative products rho_m = q0 ... qm last -- ONE select and one multiply behind q3
-      double nsel = 0.0;
-      nsel = (slot == 0) ? 1.0 : nsel;
-      nsel = (slot == 4) ? -s10 : nsel;
-      nsel = (slot == 5) ? s00 : nsel;
-      nsel = (slot == 8) ? n20 : nsel;
-      nsel = (slot == 9) ? n21 : nsel;
-      nsel = (slot == 10) ? a : nsel;
-      nsel = (slot == 12) ? n30 : nsel;
-      nsel = (slot == 13) ? n31 : nsel;
-      nsel = (slot == 14) ? n32 : nsel;
-      nsel = (slot == 15) ? n33 : nsel;
-      const double rho1 = q0 * q1, q23 = q2 * q3, rho2 = rho1 * q2, rho3 = rho1 * q23;
-      double rsel = q0;
-      rsel = (c == 1) ? rho1 : rsel;
-      rsel = (c == 2) ? rho2 : rsel;
-      rsel = (c == 3) ? rho3 : rsel;
-      yop = nsel * rsel;
-    }
+    const double l10 = s10, l20 = s20, l30 = s30, l21 = s21, l31 = s31, l32 = s32;
+    const double r0 = 1.0 / s00, r1 = 1.0 / s11, r2 = 1.0 / s22, r3 = 1.0 / s33;
+    // Y = inv(L4), lower triangular
+    const double y10 = -r1 * (l10 * r0);
+    const double y21 = -r2 * (l21 * r1);
+    const double y32 = -r3 * (l32 * r2);
+    const double y20 = -r2 * fma(l21, y10, l20 * r0);
+    const double y31 = -r3 * fma(l32, y21, l31 * r1);
+    const double y30 = -r3 * fma(l32, y20, fma(l31, y10, l30 * r0));
+    // flat select chain on the per-lane slot index (no divergent control flow: every Y value is wave-uniform)
+    double yop = 0.0;
+    yop = (slot == 0) ? r0 : yop;
+    yop = (slot == 4) ? y10 : yop;
+    yop = (slot == 5) ? r1 : yop;
+    yop = (slot == 8) ? y20 : yop;
+    yop = (slot == 9) ? y21 : yop;
+    yop = (slot == 10) ? r2 : yop;
+    yop = (slot == 12) ? y30 : yop;
+    yop = (slot == 13) ? y31 : yop;
+    yop = (slot == 14) ? y32 : yop;
+    yop = (slot == 15) ? r3 : yop;
     const d4 zero = {0.0, 0.0, 0.0, 0.0};
-    // panel of L:  D[m][n] = sum_k Y[m][k] S[n][4P+k]  ->  reg 0 of lane (n, g) = L[n][4P+g]
-    double lp;
-    if constexpr (FACTORED) {
-      lp = d[P];
-    } else {
-      const d4 t = mfma4(yop, d[P], zero);
-      lp = (c >= 4 * P + g) ? t[0] : 0.0;  // rows above the panel and the upper part of the 4x4 block
-    }
-    if constexpr (!FACTORED && P < 3) d = mfma4(-lp, lp, d);  // S -= Lp Lp^T  (critical: next pivots)
+    const double lp = d[P];   // panel of L: reg P of lane (n, g) = L[n][4P+g]
     // new rows of X:  Xp[m][n] = sum_k Y[m][k] Xtmp[4P+k][n]  ->  reg 0 of lane (n, g) = X[4P+g][n]
     const d4 u = mfma4(yop, x[P], zero);
     const double xp = u[0];
     if constexpr (P < 3) x = mfma4(-lp, xp, x);  // Xtmp[m][:] -= L[m][4P+k] X[4P+k][:]
-    d[P] = lp;
     x[P] = xp;
-    diag_panel<FACTORED, P + 1>(d, x, c, g, lane, bad_col, col0);
+    diag_panel<P + 1>(d, x, c, g);
   }
 }
 
-template <bool FACTORED>
-__device__ __forceinline__ void diag16(double* __restrict__ S, int k, int lane, int& bad_col, int col0) {
+__device__ __forceinline__ void diag16(double* __restrict__ S, int k, int lane) {
   const int c = lane & 15, g = lane >> 4;
   const int kb = k * SB;
   d4 d, x;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int j = g + 4 * e;  // the other index
-    if constexpr (FACTORED) {
-      d[e] = (c >= j) ? S[(kb + c) * LD + kb + j] : 0.0;           // L[c][4e+g]
-    } else {
-      d[e] = (j >= c) ? S[(kb + j) * LD + kb + c] : S[(kb + c) * LD + kb + j];  // S[g+4e][c], symmetric
-    }
+    d[e] = (c >= j) ? S[(kb + c) * LD + kb + j] : 0.0;           // L[c][4e+g]
     x[e] = (j == c) ? 1.0 : 0.0;
   }
-  diag_panel<FACTORED, 0>(d, x, c, g, lane, bad_col, col0 + kb);
+  diag_panel<0>(d, x, c, g);
   double* __restrict__ Xd = S + XD_OFF + k * (SB * XLD);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int j = 4 * e + g;
-    if (!FACTORED && c >= j) S[(kb + c) * LD + kb + j] = d[e];  // L[c][j]
-    Xd[j * XLD + c] = x[e];                                     // X[j][c]
-  }
+  for (int e = 0; e < 4; ++e) Xd[(4 * e + g) * XLD + c] = x[e];   // X[j][c]
 }
 
 // ---- 16x16 tile products on LDS-resident operands --------------------------------------------------------
@@ -264,14 +149,6 @@ __device__ __forceinline__ d4 reg_mma(const double* __restrict__ S, TRef A, d4 t
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) acc = mfma4(NEG ? -a[kk] : a[kk], t[kk], acc);
   return acc;
-}
-
-// linear index u over the lower-triangular tile list  (i, j), j0 <= j <= i, row-major from i = j0
-__device__ __forceinline__ void tri_decode(int u, int j0, int& i, int& j) {
-  int row = 0;
-  while (u > row) { u -= row + 1; ++row; }
-  i = j0 + row;
-  j = j0 + u;
 }
 
 // ---- pieces of the recursive-doubling assembly of X = L^-1 (X21 = -X22 (L21 X11) at block sizes 16, 32, 64) ------
@@ -331,18 +208,12 @@ __device__ __forceinline__ d4 inv_level3_X(const double* __restrict__ S, int a, 
   return acc;
 }
 
-// The leaf as a device function (one workgroup of NT threads, LDS block S of LEAF_LDS bytes): used by the
-// stand-alone kernel below.
-// WT: the results (L block, inverse block) are written with agent-scope write-through stores, so that workgroups on other
-// XCDs can read them after a flag hand-off without this workgroup flushing its L2 (mega.hip).
-template <bool FACTORED, bool WT = false>
-__device__ __forceinline__ void leaf_body(double* __restrict__ S, double* __restrict__ A, long lda, int nb,
-                                          double* __restrict__ inv, int* __restrict__ info, int col0,
-                                          long long* __restrict__ dbg) {
+// The inverse as a device function (one workgroup of NT threads, LDS block S of LEAF_LDS bytes): A is never written.
+__device__ __forceinline__ void leaf_body(double* __restrict__ S, const double* __restrict__ A, long lda, int nb,
+                                          double* __restrict__ inv) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nsb = (nb + SB - 1) / SB;
-  const long long t_begin = dbg ? wall_clock64() : 0;
 
   // ---- load: lower triangle of A (identity beyond nb), zero strict upper; all loads issued up front ----
   {
@@ -376,98 +247,19 @@ __device__ __forceinline__ void leaf_body(double* __restrict__ S, double* __rest
     }
   }
   __syncthreads();
-  const long long t_loaded = dbg ? wall_clock64() : 0;
 
-  int bad_col = -1;
-  const bool overlap_inv = !FACTORED && nsb == NSB;
-  if constexpr (FACTORED) {
-    if (wave < nsb) diag16<true>(S, wave, lane, bad_col, 0);
-    __syncthreads();
-  } else {
-    if (wave == 0) diag16<false>(S, 0, lane, bad_col, 0);
-    __syncthreads();
-    for (int k = 0; k < nsb - 1; ++k) {
-      // ---- B:  L_ik = A_ik X_kk^T,  i = k+1 .. nsb-1 ---------------------------------------------
-      for (int i = k + 1 + wave; i < nsb; i += NW) {
-        Frag f;
-        frag_load(S, tile_L(i, k), tile_Xd(k), lane, f);
-        const d4 r = frag_mma<false>(f, (d4){0.0, 0.0, 0.0, 0.0});
-        tile_store(S, tile_L(i, k), lane, r);
-      }
-      __syncthreads();
-      // ---- C:  A_ij -= L_ik L_jk^T ; wave 0: tile (k+1,k+1) then the next diagonal tile ------------
-      if (wave == 0) {
-        Frag f;
-        frag_load(S, tile_L(k + 1, k), tile_L(k + 1, k), lane, f);
-        d4 acc = tile_load(S, tile_L(k + 1, k + 1), lane);
-        acc = frag_mma<true>(f, acc);
-        tile_store(S, tile_L(k + 1, k + 1), lane, acc);
-        // the tile was written and is re-read by this wave only (LDS ops of one wave stay ordered)
-        diag16<false>(S, k + 1, lane, bad_col, 0);
-      } else {
-        const int rem = nsb - 1 - k;                 // rows k+1 .. nsb-1
-        const int ntile = rem * (rem + 1) / 2;       // u = 0 is tile (k+1,k+1): wave 0's
-        int u = wave;                                // waves 1..7 -> u = 1.., stride 7
-        Frag f0, f1;
-        d4 c0, c1;
-        int i0 = 0, j0 = 0, i1 = 0, j1 = 0;
-        if (u < ntile) {
-          tri_decode(u, k + 1, i0, j0);
-          frag_load(S, tile_L(i0, k), tile_L(j0, k), lane, f0);
-          c0 = tile_load(S, tile_L(i0, j0), lane);
-        }
-        while (u < ntile) {
-          const int u1 = u + (NW - 1);
-          if (u1 < ntile) {
-            tri_decode(u1, k + 1, i1, j1);
-            frag_load(S, tile_L(i1, k), tile_L(j1, k), lane, f1);
-            c1 = tile_load(S, tile_L(i1, j1), lane);
-          }
-          c0 = frag_mma<true>(f0, c0);
-          tile_store(S, tile_L(i0, j0), lane, c0);
-          if (u1 >= ntile) break;
-          const int u2 = u1 + (NW - 1);
-          if (u2 < ntile) {
-            tri_decode(u2, k + 1, i0, j0);
-            frag_load(S, tile_L(i0, k), tile_L(j0, k), lane, f0);
-            c0 = tile_load(S, tile_L(i0, j0), lane);
-          }
-          c1 = frag_mma<true>(f1, c1);
-          tile_store(S, tile_L(i1, j1), lane, c1);
-          u = u2;
-        }
-        // idle time of waves 1..7 while wave 0 runs the pivot chain: the parts of X = L^-1 whose inputs are
-        // already final (full 128 leaf only; inputs were completed before the barrier that opened this phase)
-        if (overlap_inv) {
-          if ((k & 1) && wave == 1) inv_level1(S, (k - 1) >> 1, lane);             // k = 1, 3, 5: nodes 0, 1, 2
-          if (k == 4 && wave <= 4) inv_level2(S, 0, (wave - 1) >> 1, (wave - 1) & 1, lane);
-          if (k == 5 && wave >= 2) {                                               // 16 T tiles on waves 2..7
-            for (int id = wave - 2; id < 16; id += NW - 2) inv_level3_T(S, id & 3, id >> 2, lane);
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  const long long t_factored = dbg ? wall_clock64() : 0;
+  if (wave < nsb) diag16(S, wave, lane);
+  __syncthreads();
 
   // ---- off-diagonal tiles of X by recursive doubling:  X21 = -X22 (L21 X11) ----------------------------------
-  if (overlap_inv) {
-    // levels 1 (nodes 0..2), 2 (node 0) and the T phase of level 3 were done in the shadow of the pivot chain
-    if (wave == 0) inv_level1(S, 3, lane);
-    __syncthreads();
-    if (wave < 4) inv_level2(S, 1, wave >> 1, wave & 1, lane);
-    __syncthreads();
-  } else {
-    if (wave < 4) inv_level1(S, wave, lane);
-    __syncthreads();
-    inv_level2(S, wave >> 2, (wave >> 1) & 1, wave & 1, lane);
-    __syncthreads();
-    // level 3 phase 1: 16 T tiles, two per wave
+  if (wave < 4) inv_level1(S, wave, lane);
+  __syncthreads();
+  inv_level2(S, wave >> 2, (wave >> 1) & 1, wave & 1, lane);
+  __syncthreads();
+  // level 3 phase 1: 16 T tiles, two per wave
 #pragma unroll
-    for (int h = 0; h < 2; ++h) inv_level3_T(S, 2 * (wave & 1) + h, wave >> 1, lane);
-    __syncthreads();
-  }
+  for (int h = 0; h < 2; ++h) inv_level3_T(S, 2 * (wave & 1) + h, wave >> 1, lane);
+  __syncthreads();
   {
     // level 3 phase 2: 16 tiles, two per wave, pairing heavy with light rows: wave -> b = wave>>1, a in (1,2) or (0,3)
     d4 rr[2];
@@ -486,28 +278,15 @@ __device__ __forceinline__ void leaf_body(double* __restrict__ S, double* __rest
     }
   }
   __syncthreads();
-  const long long t_inverted = dbg ? wall_clock64() : 0;
 
-  // ---- write L (lower triangle, valid part) and the inverse block ------------------------------------
+  // ---- write the inverse block ------------------------------------------------------------------------
   {
     const int jp = 2 * (tid & 63), r0 = tid >> 6;
-    const bool vec = ((lda & 1) == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
     constexpr int NIT = NB / NW;
     const double* __restrict__ Xd = S + XD_OFF;
 #pragma unroll 4
     for (int it = 0; it < NIT; ++it) {
       const int i = r0 + NW * it;
-      if (!FACTORED && i < nb && jp <= i) {
-        const d2 lv = *reinterpret_cast<const d2*>(&S[i * LD + jp]);
-        double* dst = A + (long)i * lda + jp;
-        if constexpr (WT) {
-          __hip_atomic_store(dst, lv.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (jp + 1 <= i) __hip_atomic_store(dst + 1, lv.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          if (vec && jp + 1 <= i) *reinterpret_cast<d2*>(dst) = lv;
-          else { dst[0] = lv.x; if (jp + 1 <= i) dst[1] = lv.y; }
-        }
-      }
       auto xval = [&](int j) -> double {
         if (j > i) return 0.0;
         if ((j >> 4) == (i >> 4)) return Xd[(i >> 4) * (SB * XLD) + (i & 15) * XLD + (j & 15)];
@@ -516,26 +295,7 @@ __device__ __forceinline__ void leaf_body(double* __restrict__ S, double* __rest
       d2 xv;
       xv.x = xval(jp);
       xv.y = xval(jp + 1);
-      if constexpr (WT) {
-        __hip_atomic_store(&inv[i * NB + jp], xv.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&inv[i * NB + jp + 1], xv.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        *reinterpret_cast<d2*>(&inv[i * NB + jp]) = xv;
-      }
-    }
-  }
-  if (dbg && tid == 0) {
-    const long long t_end = wall_clock64();
-    dbg[0] = t_loaded - t_begin; dbg[1] = t_factored - t_loaded; dbg[2] = t_inverted - t_factored;
-    dbg[3] = t_end - t_inverted; dbg[4] = t_end - t_begin; dbg[5] = t_begin;
-  }
-  if (!FACTORED && info) {
-    // bad_col is wave-0 state; lane 0 of wave 0 reports (first failing pivot of the matrix wins)
-    // (the leaf of column 0 resets the word: see leaf2_device.h)
-    if (tid == 0) {
-      const int v = bad_col >= 0 ? col0 + bad_col + 1 : 0;
-      if (col0 == 0) info[0] = v;
-      else if (v != 0 && info[0] == 0) info[0] = v;
+      *reinterpret_cast<d2*>(&inv[i * NB + jp]) = xv;
     }
   }
 }

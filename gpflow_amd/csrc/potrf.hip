@@ -38,10 +38,8 @@ struct Bulk {
   int cap = 0;    // cap on the persistent workgroups of the big (K >= 256) updates, 0 = one workgroup per tile
   int group_cap = 0;   // cap on the workgroups of the fused in-group solve, 0 = one per 16-row sliver
   int kmin = 256;      // updates with K below this are not capped
-  int queue_cus = 0;   // > 0: the big updates run as persistent workgroups fed from a tile queue, two per compute unit of this many CUs
   void apply(GemmArgs& g) const {
     if (cap > 0 && g.k >= kmin) g.max_wgs = cap;
-    if (queue_cus > 0 && g.k >= kmin) { g.tile_queue = 1; g.stagger_first = queue_cus; }
   }
 };
 }  // namespace
@@ -92,7 +90,6 @@ struct Aux {
   // packet-free hand-offs of the latency chain (potrf_core, "chain flags"): one word per panel for "panel solved" (F) and for
   // "rest-update done" (R), written with the epoch of the factorisation that owns them (monotonic per device)
   int* flags = nullptr;
-  int* cnt = nullptr;    // two counters per panel for the fused panel kernel (producers done / workgroups through the solve), zeroed per call
   int epoch = 0;
   int concurrent = -1;   // 1: kernels of two streams were seen running at the same time (init-time probe); 0: serialised by a tool
 };
@@ -244,9 +241,8 @@ int aux_get(int dev, int need, Aux** out) {
     a.ready = true;
   }
   if (!a.flags) {
-    GPK_HIP(hipMalloc((void**)&a.flags, sizeof(int) * (4 * kMaxFlagPanels + 8)));   // F, R, the fused panels' counters, the x_tail words
-    GPK_HIP(hipMemset(a.flags, 0, sizeof(int) * (4 * kMaxFlagPanels + 8)));
-    a.cnt = a.flags + 2 * kMaxFlagPanels;
+    GPK_HIP(hipMalloc((void**)&a.flags, sizeof(int) * 2 * kMaxFlagPanels));   // F, R
+    GPK_HIP(hipMemset(a.flags, 0, sizeof(int) * 2 * kMaxFlagPanels));
     // in-kernel hand-offs need kernels of two streams to RUN concurrently: under rocprofv3 --pmc (or any tool that serialises
     // kernels) they would deadlock, so the chain then keeps its events (gpk_probe_concurrent_kernels: <= 2 ms, once per device)
     int conc = 0;
@@ -279,7 +275,7 @@ int current_device(int* dev) {
 
 // factor the outer panel [c0,c1) of the square part (rows up to `rows`) on stream s
 int factor_panel(hipStream_t s, double* A, int rows, int c0, int c1, long lda, int batch, long strideA,
-                 double* invd, long strideInv, int* info, int chain_wgs = 0, int chain_kparts = 0) {
+                 double* invd, long strideInv, int* info, int chain_wgs = 0) {
   int rc;
   for (int j0 = c0; j0 < c1; j0 += NB) {
     const int j1 = (j0 + NB < c1) ? j0 + NB : c1;
@@ -296,7 +292,6 @@ int factor_panel(hipStream_t s, double* A, int rows, int c0, int c1, long lda, i
                            strideInv, strideA);
     g.b_tri = 2;
     g.max_wgs = chain_wgs;
-    g.small_kparts = chain_kparts;
     rc = gpk_launch_gemm(s, g);
     if (rc) return rc;
     const int ncols = c1 - j1;
@@ -304,7 +299,6 @@ int factor_panel(hipStream_t s, double* A, int rows, int c0, int c1, long lda, i
       GemmArgs u = gemm_base(below, ncols, nb, -1.0, panel, lda, panel, lda, 1.0,
                              A + (long)j1 * lda + j1, lda, batch, strideA, strideA, strideA);
       u.c_lower = 1;
-      u.small_kparts = chain_kparts;
       rc = gpk_launch_gemm(s, u);
       if (rc) return rc;
     }
@@ -421,9 +415,6 @@ int solve_group_bwd(hipStream_t s, double* Bm, long ldb, int rows, const double*
 // p_prologue: work of the CALLER that the first leaf waits for and nothing else does -- the fused drivers' Kuu build.  It is
 // enqueued ON the panel stream, so the first leaf follows it back to back (0.3 us) instead of behind an event record on the caller's
 // stream and a wait on the panel stream (~15 us per step, round 5).
-// b_prologue (large factorisations): work of the CALLER that everything EXCEPT the first panel's columns waits for -- the GPR
-// driver builds only those columns before the call and the rest of K(X, X) here, on the bulk stream, beside the first panel's
-// chain, which nothing else would overlap (first_panel_columns below tells it how many columns that is).
 // x_prologue: work of the CALLER that belongs on the bulk stream before the first extra-row group (the SVGP driver's Kfu
 // build, transposes, KL).  It is enqueued after the first panel's chain kernels: every host call issued before the first
 // leaf delays the whole step, and nothing on the bulk stream is needed for ~4 panels.
@@ -432,33 +423,15 @@ int solve_group_bwd(hipStream_t s, double* Bm, long ldb, int rows, const double*
 // per panel against ~55 us of kernels -- so every launch issued there delays the chain (round 5: the second leaf started 52 us
 // after the first strip had finished), and the rest-update stream has a leaf's time of slack per panel.
 typedef std::function<int(hipStream_t)> StreamWork;
-// x_tail (round 6): work of the CALLER that reads the solved extra rows and that the caller's NEXT kernel does not need -- the SVGP
-// drivers' row statistics (28 us of HBM reads at Cm) beside the projection GEMM.  If the factorisation hands its extra rows over with
-// flag words (small sizes, gate kernels) it enqueues the work on the extra-row stream right behind the last solve, publishes a second
-// word behind it and reports that word: the caller's consumer waits for it in-kernel (VarexpExtra).  The caller's stream is released by a
-// one-wave gate on the first word (~1 us behind the solve; the event pair it replaces cost ~10 us).  Otherwise `used` stays false and
-// the caller runs the work itself.  MEASURED (profiles/r06_ab_x_tail.log, two repetitions per setting on one box): no gain -- Cm 1.79 / 1.80 ms
-// without / with it, C3 0.70 / 0.73: the 2048 light workgroups of the statistics take the wave slots the projection's first tiles want and
-// the projection ends as much later as it started earlier.  Likewise the slot partials summed inside the variational-expectation kernel
-// instead of a sum_parts launch (level).  Both are A/B knobs (GPK_XTAIL, GPK_VAREXP_SUMS_PARTS), off.
-struct XTail {
-  const StreamWork* work = nullptr;
-  bool used = false;
-  const int* done_ptr = nullptr;
-  int done_val = 0;
-};
 struct PotrfHooks {
   const StreamWork* x_prologue = nullptr;
-  const StreamWork* b_prologue = nullptr;
   const StreamWork* p_prologue = nullptr;
   const StreamWork* late_work = nullptr;
-  XTail* x_tail = nullptr;
 };
 
 int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, long strideA, double* invd, int zero_upper,
                int* info, const PotrfHooks& hooks = PotrfHooks(), int tri = 0, bool tri_prefilled = false) {
   const StreamWork* x_prologue = hooks.x_prologue;
-  const StreamWork* b_prologue = hooks.b_prologue;
   const StreamWork* p_prologue = hooks.p_prologue;
   const StreamWork* late_work = hooks.late_work;
   if (!A || !invd || n < 0 || extra < 0 || lda < n) return GPK_E_ARG;
@@ -530,7 +503,7 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> lock(g_aux[dev].mu);
   Aux* aux = nullptr;
-  rc = aux_get(dev, 2 * npanels + 8, &aux);   // (+ fork, three joins, the b_prologue event)
+  rc = aux_get(dev, 2 * npanels + 8, &aux);   // (+ fork, three joins)
   if (rc) return rc;
   const bool large = n >= 4096;
   hipStream_t P = aux->P, B = large ? aux->B : aux->Bs;
@@ -547,18 +520,7 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
   // (round 5, with the packet-free chain: 224 -- one workgroup on 224 compute units, 32 left to the chain's one-shot kernels --
   //  is level with 320 on the whitened step and 2 - 5 % faster on the un-whitened one, whose extra-row stream is a quarter
   //  longer; a batch of problems keeps 320: C5 separate 2.04 against 2.02 ms; 240 / 248 lose 5 %, profiles/r05_ab_caps.log)
-  // (round 6 EXPERIMENT, off.)  With many extra rows the chain's one-shot kernels can stage K in two halves (gemm_nt_small, kparts = 2:
-  // 74 KB of LDS) so that they fit BESIDE a capped bulk workgroup (84 KB) on the same compute unit instead of queueing through the few
-  // CUs the cap leaves free (three rounds of ~10 us per launch while an update holds 224 CUs, profiles/r06_step_timeline.txt), and the
-  // cap could then go up.  Measured, same box (profiles/r06_ab_halfk.log): Cm 1.76 ms without, 1.80 with it at the same cap of
-  // 224, 1.85 / 1.88 at caps of 240 / 254 -- the second staging round trip costs more than the queueing, and more bulk workgroups
-  // slow the extra-row stream itself.  Kept as an A/B knob (GPK_CHAIN_HALFK=1).
-  const bool chain_halfk = useX && !large && batch == 1 && nbo == NB && extra >= GPK_TUNE(CHAIN_HALFK_MIN_ROWS, 6144) &&
-                           GPK_TUNE(CHAIN_HALFK, 0);
-  const int chain_kparts = chain_halfk ? 2 : 0;
-  if (!large) bulk.cap = batch > 1 ? GPK_TUNE(EXTRA_MAX_WGS_BATCHED, 320)
-                                   : (chain_halfk ? GPK_TUNE(EXTRA_MAX_WGS_HALFK, 248) : GPK_TUNE(EXTRA_MAX_WGS, 224));
-  if (large && GPK_TUNE(XQUEUE_LARGE, 0)) bulk.queue_cus = aux->bulk_cus;   // (A/B, off: GPR predict's test-row updates, level at 54.4 - 55.0 ms)
+  if (!large) bulk.cap = batch > 1 ? GPK_TUNE(EXTRA_MAX_WGS_BATCHED, 320) : GPK_TUNE(EXTRA_MAX_WGS, 224);
   if (!large) bulk.group_cap = GPK_TUNE(GROUP_SOLVE_MAX_WGS, 0);
   if (!large) bulk.kmin = GPK_TUNE(EXTRA_CAP_KMIN, 256);
   hipEvent_t* evF = aux->ev;            // [npanels] panel p factored, rows below solved (recorded on P)
@@ -582,27 +544,8 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
     rc = (*p_prologue)(P);
     if (rc) return rc;
   }
-  // (round 6 EXPERIMENT, off: the fused panel kernel -- solve + strip in one launch, gemm.hip -- is bit-identical and level with the two
-  //  launches it replaces: 1024-row shard 0.976 against 0.985 ms, Cm 1.795 / 1.79, C3 0.766 / 0.764 (profiles/r06_ab_panel_fused.log).  What
-  //  it saves in launch ramp and re-staging it spends on the cross-workgroup hand-over of the B tile through memory.  A/B: GPK_PANEL_FUSED=1.)
-  const bool panel_fused_on = GPK_TUNE(PANEL_FUSED, 0) && batch == 1 && aux->cnt != nullptr;
-  int* pending_sig = nullptr;   // "panel solved" word of a fused panel that the NEXT kernel of the panel stream still has to announce
-  if (panel_fused_on)   // the fused panel kernels' counters (everything of earlier calls that used them has completed: P waited for the fork)
-    GPK_HIP(hipMemsetAsync(aux->cnt, 0, sizeof(int) * 2 * (size_t)std::min(npanels, kMaxFlagPanels), P));
   hipStream_t last_bulk = B;
   int last_rest = -1;  // panel index whose evR marks the most recent rest-update
-  hipEvent_t evBpro = aux->ev[2 * npanels + 4];
-  bool bpro_pending = false;
-  if (b_prologue) {
-    rc = (*b_prologue)(B);
-    if (rc) return rc;
-    if (B != S) {
-      GPK_HIP(hipEventRecord(evBpro, B));
-      bpro_pending = true;
-      if (useX && X != B) GPK_HIP(hipStreamWaitEvent(X, evBpro, 0));
-      if (aux->Bs != B) GPK_HIP(hipStreamWaitEvent(aux->Bs, evBpro, 0));
-    }
-  }
   const bool use_flags = GPK_TUNE(CHAIN_FLAGS, 1) && (batch == 1 || GPK_TUNE(CHAIN_FLAGS_BATCHED, 1)) && aux->flags != nullptr &&
                          aux->concurrent == 1;
   int* flagF = aux->flags;
@@ -665,31 +608,8 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
     const int xgroup_now = (xg0 == 0 && !large) ? xgroup_first : xgroup;
     const bool x_waits_here = useX && (c1 == n || ((c1 - xg0) >= xgroup_now || (large && c1 - xg0 >= nbo)) ||
                                        (tail_zone && (c1 == n - 2 * NB || c1 == n - NB)));
-    // Fused panel kernel (round 6): a full single-leaf panel that hands over with flags runs  leaf -> ONE kernel (panel solve +
-    // strip, gemm.hip: panel_fused_kernel)  instead of  leaf -> solve -> strip.  "Panel solved" is published by the last workgroup
-    // through the solve; the wait for the previous rest-update sits between the two phases.
-    double* const invb_p = invd + (long)(c0 / NB) * NB * NB;
-    const bool fused_panel = panel_fused_on && use_flags && p < kMaxFlagPanels && c1 < n && (c1 - c0) == NB && !bpro_pending &&
-                             chain_wgs == 0 && chain_kparts == 0 && !(x_waits_here && X == aux->B) && (last_rest < 0 || rest_flagged) &&
-                             gpk_panel_fused_ok(A + (long)c1 * lda + c0, lda, invb_p, R - c1, NB, c2 - c1);
-    if (fused_panel) {
-      // ("panel p-1 solved" of a fused predecessor rides on this leaf's entry)
-      rc = gpk_launch_leaf(P, A + (long)c0 * lda + c0, lda, strideA, NB, invb_p, strideInv, info, c0, batch, 0, pending_sig, epoch);
-      pending_sig = nullptr;
-      if (rc) return rc;
-      rc = gpk_launch_panel_fused(P, A + (long)c1 * lda + c0, lda, invb_p, A + (long)c1 * lda + c1, R - c1, c2 - c1, aux->cnt + 2 * p,
-                                  nullptr, epoch, last_rest >= 0 ? flagR + last_rest : nullptr, epoch, info);
-      if (rc) return rc;
-      pending_sig = flagF + p;   // announced by the entry of the next kernel on the panel stream
-    } else {
-      if (pending_sig) {
-        rc = gpk_launch_set_flag(P, pending_sig, epoch);
-        pending_sig = nullptr;
-        if (rc) return rc;
-      }
-      rc = factor_panel(P, A, R, c0, c1, lda, batch, strideA, invd, strideInv, info, chain_wgs, chain_kparts);
-      if (rc) return rc;
-    }
+    rc = factor_panel(P, A, R, c0, c1, lda, batch, strideA, invd, strideInv, info, chain_wgs);
+    if (rc) return rc;
     const double* Pn = A + (long)c1 * lda + c0;  // rows c1.. of the solved panel
     GemmArgs strip{};
     if (c1 < n) {
@@ -697,7 +617,6 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
                         strideA, strideA);
       strip.c_lower = 1;
       strip.max_wgs = chain_wgs;
-      strip.small_kparts = chain_kparts;
     }
     // Chain flags (round 5).  Between two kernels of the panel stream an event record costs 4.6 us and an event wait 6.3 us of
     // queue-packet processing (rocprofv3 timelines, profiles/r05_rows1024_events_timeline.txt, r05_ab_chain_flags.log); two kernels back to back start
@@ -710,15 +629,11 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
     // (stream memory operations only on the plain streams: on the CU-masked bulk stream of large factorisations a
     // hipStreamWriteValue32 was observed to overtake the kernel queued before it -- wrong factor at n = 5000 -- so a panel whose
     // extra-row group waits on that stream keeps its event, and so does a strip whose rest-update ran there)
-    const bool flagged = fused_panel || (use_flags && p < kMaxFlagPanels && c1 < n && (c1 - c0) <= NB &&
-                                         gpk_gemm_takes_latency_kernel(strip) && !(x_waits_here && X == aux->B));
+    const bool flagged = use_flags && p < kMaxFlagPanels && c1 < n && (c1 - c0) <= NB &&
+                         gpk_gemm_takes_latency_kernel(strip) && !(x_waits_here && X == aux->B);
     panel_flagged[p] = flagged ? 1 : 0;
     if (!flagged) GPK_HIP(hipEventRecord(evF[p], P));
-    if (c1 < n && !fused_panel) {
-      if (bpro_pending) {   // the strip is the first kernel of the chain that leaves the first panel's columns
-        GPK_HIP(hipStreamWaitEvent(P, evBpro, 0));
-        bpro_pending = false;
-      }
+    if (c1 < n) {
       // columns c1:c2 also received the most recent rest-update (on a bulk stream): order the two
       if (last_rest >= 0) {
         if (flagged && rest_flagged) {
@@ -781,8 +696,6 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
       else if (rest_small_wgs > 0) { u.small_loop = 1; u.max_wgs = rest_small_wgs; }
       if (Bp == aux->B && large) {
         u.stagger_first = aux->bulk_cus;
-        // persistent workgroups (two per CU of the masked stream) that walk the tile list: no workgroup launch per tile
-        if (GPK_TUNE(TRAIL_PERSIST, 0)) u.max_wgs = GPK_TUNE(TRAIL_PERSIST, 0) * aux->bulk_cus;
         // (round 6) persistent workgroups -- two per compute unit of the bulk stream -- that take their tiles from a device counter
         // (gemm.hip, "Tile QUEUE"): no workgroup launch per tile and no drift between static tile lists; the kernel alone gains 7 %
         // (as dispatched 0.591 -> 0.632 of the chip's peak from 240 CUs).  They never leave their CUs, though, so the look-ahead panel no
@@ -802,19 +715,8 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
       GemmArgs ua = gemm_base(R - c2, c3 - c2, c1 - c0, -1.0, P2, lda, P2, lda, 1.0, A + (long)c2 * lda + c2, lda, batch, strideA,
                               strideA, strideA);
       ua.c_lower = 1;
-      ua.small_kparts = chain_kparts;
-      // In the tiled regime (many extra rows, above) the whole rest-update was ONE tiled launch that shares its compute units with the
-      // extra-row stream's capped workgroups and takes 60 - 95 us there instead of 30 (profiles/r06_step_timeline.txt) -- longer than the
-      // chain's own 41 us, and the next strip waited for all of it.  The same split there -- the next block column first, as 64 x 64 tiles
-      // of the generic kernel (36 KB of LDS: they fit beside anything), the remainder behind it -- was measured SLOWER: Cm 1.85 against 1.79 ms
-      // (latency kernel 1.84, 128 x 128 tiles 1.95; profiles/r06_ab_rest_split_tiled.log): the extra-row stream is co-critical and every extra
-      // launch beside it costs more than the strip gains.  A/B knob, off.
-      const int split_tiled = u.no_small ? GPK_TUNE(REST_SPLIT_TILED, 0) : 0;   // 1: 64 x 64 tiles, 2: latency kernel, 3: 128 x 128 tiles
-      if (split_tiled == 1) ua.tile64 = 1;
-      else if (split_tiled == 3) ua.no_small = 1;
       const bool split = GPK_TUNE(REST_SPLIT, 1) && use_flags && p < kMaxFlagPanels && Bp != aux->B && panel_flagged[p] &&
-                         (!u.no_small || split_tiled) && !u.small_loop && (c2 - c1) <= NB &&
-                         (split_tiled == 1 || split_tiled == 3 || gpk_gemm_takes_latency_kernel(ua)) &&
+                         !u.no_small && !u.small_loop && (c2 - c1) <= NB && gpk_gemm_takes_latency_kernel(ua) &&
                          !(last_rest >= 0 && last_bulk != Bp);
       if (split) {
         // (the gate, not an in-kernel wait: up to 120 workgroups of 150 KB spinning from the moment they are enqueued -- a leaf and
@@ -906,22 +808,6 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
       for (int h0 = g0; h0 < c1; h0 += NBO) {
         const int h1 = std::min(h0 + NBO, c1);
         const int xrows = tri ? extra - tri + h1 : extra;  // (identity rows below column h1 are still exactly zero here)
-        // (round 6, late) The in-group solve of a later group is 256 workgroups of 132 KB for ~63 us: every compute unit is taken and
-        // the chain -- whose kernels all need a whole CU's LDS -- stands still for as long (leaves of 85 / 66 us in the step timeline
-        // exactly beside the solves of groups 1 and 2).  Block by block (the progressive form, all of it issued here: the panels are done)
-        // the chain gets a compute unit between two launches.  MEASURED: the four block launches sum to ~170 us against 63 for the fused one and
-        // the extra-row stream has no such slack: Cm 1.78 -> 1.84 ms (profiles/r06_ab_group_by_blocks.log).  A/B knob, off.
-        const int nbk = (h1 - h0) / NB;
-        const bool by_blocks = GPK_TUNE(XGROUP_BY_BLOCKS, 0) && progressive && h0 > 0 && c1 < n && nbk >= 2 && (h1 - h0) == nbk * NB &&
-                               group_solve_fused_ok(nbk, h0, h1, xrows, A, lda, invd, batch, strideA, strideInv);
-        if (by_blocks) {
-          for (int j = 0; j < nbk; ++j) {
-            rc = solve_group_fwd(X, bulk, E, lda, E, lda, xrows, A, lda, invd, strideInv, n, h0, h1, batch, strideA, strideA, strideA, j,
-                                 GPK_TUNE(XGROUP_BLOCK_WGS, 0));
-            if (rc) return rc;
-          }
-          continue;
-        }
         rc = solve_group_fwd(X, bulk, E, lda, E, lda, xrows, A, lda, invd, strideInv, n, h0, h1, batch, strideA, strideA,
                              strideA);
         if (rc) return rc;
@@ -936,38 +822,11 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
     GPK_HIP(hipStreamWaitEvent(S, evJoinB, 0));
   }
   if (useX && X != last_bulk) {
-    XTail* xt = hooks.x_tail;
-    if (xt && xt->work && use_flags && gate_kernels && !large && X != S && GPK_TUNE(XTAIL, 0)) {
-      int* flagE = aux->flags + 4 * kMaxFlagPanels;   // [2]: extra rows solved / tail work done
-      rc = gpk_launch_set_flag(X, flagE, epoch);
-      if (rc) return rc;
-      rc = gpk_launch_wait_flag(S, flagE, epoch, info);
-      if (rc) return rc;
-      rc = (*xt->work)(X);
-      if (rc) return rc;
-      rc = gpk_launch_set_flag(X, flagE + 1, epoch);
-      if (rc) return rc;
-      xt->used = true;
-      xt->done_ptr = flagE + 1;
-      xt->done_val = epoch;
-    } else {
-      GPK_HIP(hipEventRecord(evJoinX, X));
-      GPK_HIP(hipStreamWaitEvent(S, evJoinX, 0));
-    }
+    GPK_HIP(hipEventRecord(evJoinX, X));
+    GPK_HIP(hipStreamWaitEvent(S, evJoinX, 0));
   }
   if (zero_upper) return gpk_launch_zero_upper(S, A, n, lda, batch, strideA);
   return 0;
-}
-}  // namespace
-
-namespace {
-// number of leading columns the FIRST outer panel of a factorisation of size n covers (same rule as potrf_core's cuts)
-int first_panel_columns(int n) {
-  const int nbo_large = (GPK_TUNE(NBO, 640) / NB) * NB;
-  const int nbo = (n >= 4096) ? (nbo_large >= NB ? nbo_large : NBO) : NB;
-  const int narrow_tail = (nbo > NB) ? (GPK_TUNE(NARROW_TAIL, 4096) / NB) * NB : 0;
-  const int w = (nbo > NB && n > narrow_tail) ? nbo : NB;
-  return w < n ? w : n;
 }
 }  // namespace
 
@@ -1047,10 +906,8 @@ extern "C" int gpk_trsm(void* stream, int trans, const double* L, long ldl, cons
   const long strideInv = (long)gpk_cdiv(n, NB) * NB * NB;
   int rc;
   if (trans == 0) {
-    Bulk trsm_bulk;
-    if (batch <= 1 && n >= 4096 && GPK_TUNE(TRSM_QUEUE, 0)) trsm_bulk.queue_cus = 256;   // (A/B, off: the cached-posterior solve 19.3 -> 20.2 ms with the queue)
     for (int g0 = 0; g0 < n; g0 += NBO) {
-      rc = solve_group_fwd(s, trsm_bulk, B, ldb, B, ldb, m, L, ldl, invd, strideInv, n, g0, std::min(g0 + NBO, n), batch,
+      rc = solve_group_fwd(s, Bulk{}, B, ldb, B, ldb, m, L, ldl, invd, strideInv, n, g0, std::min(g0 + NBO, n), batch,
                            strideB, strideB, strideL);
       if (rc) return rc;
     }
@@ -1152,44 +1009,18 @@ extern "C" int gpk_gpr_lml(void* stream, int family, const double* X, int n, int
   int rc;
   // K(X,X) + noise I, lower tiles only (gpr.py:100-101); a heteroskedastic likelihood (noise_rows: one variance per data
   // row, likelihoods/scalar_continuous.py:92-111) adds its vector to the diagonal instead (model_utils.py:46-50).
-  // Large n (round 5 EXPERIMENT, off): the first outer panel's chain (5 leaves and their in-panel solves, ~0.5 ms) has nothing
-  // to overlap with -- so only ITS columns are built before the factorisation starts and the remaining (n - w)^2 block is
-  // built on the factorisation's bulk stream beside that chain (b_prologue).  Same formula per element: bit-identical
-  // (tests at n = 4224 / 5000).  Measured at N = 16384: 31.13 - 31.21 against 31.17 - 31.23 ms (profiles/r05_ab_gpr_split_build.log):
-  // the build's 65536 workgroups take every compute unit and the chain's one-workgroup leaves queue behind them, so the 0.4 ms
-  // of build overlap ~0.05 ms of chain.  Kept behind GPK_GPR_SPLIT_BUILD in the A/B build.
-  const int w0 = first_panel_columns(n);
-  const bool split_build = n >= 4096 && w0 < n && GPK_TUNE(GPR_SPLIT_BUILD, 0);
-  std::function<int(hipStream_t)> bpro;
-  if (!split_build) {
-    rc = gpk_kernel_matrix(stream, family, X, n, ldx, nullptr, 0, 0, d, ls_host, ard, variance,
-                           noise_rows ? 0.0 : noise_variance, 1, T, l.ld);
+  rc = gpk_kernel_matrix(stream, family, X, n, ldx, nullptr, 0, 0, d, ls_host, ard, variance,
+                         noise_rows ? 0.0 : noise_variance, 1, T, l.ld);
+  if (rc) return rc;
+  if (noise_rows) {
+    rc = gpk_diag_add(stream, T, n, l.ld, noise_rows);
     if (rc) return rc;
-    if (noise_rows) {
-      rc = gpk_diag_add(stream, T, n, l.ld, noise_rows);
-      if (rc) return rc;
-    }
-  } else {
-    // columns [0, w0): all rows (the w0 x w0 top block gets its upper triangle too; the factorisation never reads it)
-    rc = gpk_kernel_matrix(stream, family, X, n, ldx, X, w0, ldx, d, ls_host, ard, variance, 0.0, 0, T, l.ld);
-    if (rc) return rc;
-    rc = noise_rows ? gpk_diag_add(stream, T, w0, l.ld, noise_rows) : gpk_launch_diag_add_scalar(s, T, w0, l.ld, noise_variance);
-    if (rc) return rc;
-    bpro = [&, w0](hipStream_t bs) -> int {
-      double* Kb = T + (long)w0 * l.ld + w0;
-      int r = gpk_kernel_matrix((void*)bs, family, X + (long)w0 * ldx, n - w0, ldx, nullptr, 0, 0, d, ls_host, ard, variance,
-                                noise_rows ? 0.0 : noise_variance, 1, Kb, l.ld);
-      if (r) return r;
-      return noise_rows ? gpk_diag_add((void*)bs, Kb, n - w0, l.ld, noise_rows + w0) : 0;
-    };
   }
   // (Y - m)^T as P extra rows (gpr.py:103, logdensities.py:149)
   rc = gpk_launch_transpose_shift(s, Y, n, P, ldy, T + (long)n * l.ld, l.ld, -mean_const);
   if (rc) return rc;
   // L = chol(K); extra rows -> alpha^T = (L^-1 (Y-m))^T  (gpr.py:102, logdensities.py:150)
-  PotrfHooks hk;
-  hk.b_prologue = split_build ? &bpro : nullptr;
-  rc = potrf_core(s, T, n, P, l.ld, 1, 0, invd, 0, info, hk);
+  rc = potrf_core(s, T, n, P, l.ld, 1, 0, invd, 0, info);
   if (rc) return rc;
   // p = -0.5 sum alpha^2 - 0.5 N log 2pi - sum log diag L, summed over the P columns
   rc = gpk_sum_log_diag(stream, T, n, l.ld, 1, 0, logdet);
@@ -1208,7 +1039,7 @@ extern "C" int gpk_gpr_lml(void* stream, int family, const double* X, int n, int
 namespace {
 struct ElboLayout {
   long ld; int nt;
-  size_t off_T, off_invd, off_LqT, off_s0, off_fmean, off_ssq, off_proj, off_part0, off_part1, off_part2, off_V, off_C, off_flags, off_Lfin, total;
+  size_t off_T, off_invd, off_LqT, off_s0, off_fmean, off_ssq, off_proj, off_part0, off_part1, off_part2, off_V, total;
 };
 
 ElboLayout elbo_layout(int m, int rows, int P, int q_diag, int whiten) {
@@ -1216,8 +1047,8 @@ ElboLayout elbo_layout(int m, int rows, int P, int q_diag, int whiten) {
   l.ld = (long)gpk_align_up((size_t)m, 8);
   l.nt = 2 * gpk_gemm_tiles_n(m);
   size_t o = 0;
-  // (minibatch rows padded to whole 32-row blocks: the single-launch step kernel runs full blocks only; the padding rows are
-  // never initialised, never read by the multi-launch route and left out of the step kernel's final sum)
+  // (minibatch rows padded to whole 32-row blocks -- the single-launch step kernel's layout, DESIGN 6 "Closed experiments whose code
+  // was removed"; kept so that the workspace size does not change: the padding rows are never initialised and never read)
   const size_t rows_pad = gpk_align_up((size_t)rows, 32);
   // T [m + rows_pad rows], then -- directly behind it, so that the un-whitened form can use ONE trapezoid [Kuu ; Kfu ; q_mu^T ;
   // tril(q_sqrt_p)^T] with the minibatch rows unpadded -- room for P + P m more rows; the whitened form keeps its LqT there
@@ -1236,41 +1067,10 @@ ElboLayout elbo_layout(int m, int rows, int P, int q_diag, int whiten) {
   l.off_part1 = o; o += gpk_align_up((size_t)GPK_REDUCE_MAXPART * sizeof(double), 256);
   l.off_part2 = o; o += gpk_align_up((size_t)(GPK_REDUCE_MAXPART + 64) * sizeof(double), 256);
   l.off_V = o; o += gpk_align_up((size_t)m * P * sizeof(double), 256);
-  // single-launch step kernel (mega.hip; A/B build only, GPK_MEGA=1): projection accumulator [P, rows, ld], flag words and the
-  // write-once copy of the factor.  The product library reserves nothing for it (round 4 did: +134 MB at Cm).
-  l.off_C = l.off_flags = l.off_Lfin = o;
-#ifdef GPK_EXPERIMENTAL
-  if (!q_diag && GPK_TUNE(MEGA, GPK_MEGA_DEFAULT) && gpk_mega_supported(m, rows, P, 1 << 20)) {
-    l.off_C = o; o += gpk_align_up((size_t)P * rows_pad * l.ld * sizeof(double), 256);
-    l.off_flags = o; o += gpk_align_up(gpk_mega_flag_ints(m) * sizeof(int), 256);
-    l.off_Lfin = o; o += gpk_align_up((size_t)m * l.ld * sizeof(double), 256);
-  }
-#endif
   l.total = o;
   return l;
 }
-
-int device_cus(int* ncu) {
-  static int cached[16] = {0};
-  int dev = 0;
-  GPK_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return GPK_E_UNSUPPORTED;
-  if (!cached[dev]) {
-    hipDeviceProp_t prop;
-    GPK_HIP(hipGetDeviceProperties(&prop, dev));
-    cached[dev] = prop.multiProcessorCount;
-  }
-  *ncu = cached[dev];
-  return 0;
-}
 }  // namespace
-
-#ifdef GPK_EXPERIMENTAL
-// (A/B build only) byte offset of the step kernel's flag words / leaf time stamps inside the fused driver's workspace
-extern "C" __attribute__((visibility("default"))) long gpk_exp_svgp_flags_offset(int m, int rows, int P) {
-  return (long)elbo_layout(m, rows, P, 0, 1).off_flags;
-}
-#endif
 
 extern "C" size_t gpk_svgp_elbo_workspace_bytes(int m, int rows, int d, int P, int q_diag, int whiten) {
   (void)d;
@@ -1438,34 +1238,6 @@ extern "C" int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, in
   // and the panel chain starts right after the much smaller Kuu build.  Work that depends on neither factorisation
   // nor minibatch solve -- tril(q_sqrt)^T for the projection and the whole KL term -- goes to that stream too, which
   // idles until the first 512 columns of Lm exist; gpk_potrf joins it.
-#ifdef GPK_EXPERIMENTAL
-  // ---- single-launch route (mega.hip): builds + KL on the caller's stream, then ONE persistent kernel for everything
-  // that depends on the factorisation.  Taken when the shapes fit one row block per compute unit.
-  if (!q_diag && !noise_rows && GPK_TUNE(MEGA, GPK_MEGA_DEFAULT) && rows > 0) {
-    int ncu = 0;
-    rc = device_cus(&ncu);
-    if (rc) return rc;
-    if (gpk_mega_supported(m, rows, P, ncu)) {
-      rc = gpk_kernel_matrix(stream, family, Z, m, ldz, nullptr, 0, 0, d, ls_host, ard, variance, jitter, 1, T, l.ld);
-      if (rc) return rc;
-      rc = gpk_kernel_matrix(stream, family, Xb, rows, ldxb, Z, m, ldz, d, ls_host, ard, variance, 0.0, 0, Kfu, l.ld);
-      if (rc) return rc;
-      rc = gpk_transpose(stream, q_sqrt, m, m, m, LqT, l.ld, 1, P, (long)m * m, (long)m * l.ld);
-      if (rc) return rc;
-      int ck = 0;
-      rc = gpk_launch_kl_white_stage1(s, q_mu, q_sqrt, m, P, q_diag, part1, &ck);
-      if (rc) return rc;
-      const double* pk[1] = {part1};
-      const double halfk = 0.5;
-      rc = gpk_launch_final(s, 1, pk, &ck, &halfk, -0.5 * (double)m * (double)P, out + 1);
-      if (rc) return rc;
-      GPK_HIP(hipMemsetAsync(info, 0, sizeof(int), s));
-      return gpk_launch_svgp_mega(s, GPK_TUNE(MEGA_PROTO, 1), ncu, T, l.ld, m, rows, invd, (double*)(w + l.off_Lfin), LqT, l.ld, (double*)(w + l.off_C), q_mu, P,
-                                  Yb, ldyb, s0, fmean, ssq, part0, (int*)(w + l.off_flags), info, out, variance, noise_variance,
-                                  mean_const, GPK_TUNE(MEGA_MIN_WGS, 96));
-    }
-  }
-#endif
   const bool side = m > GPK_NB && m < 4096 && rows > 256;
   // Kuu + jitter I (posteriors.py:835, covariances/kuus.py:29-34), lower tiles only: the chain's first leaf waits for
   // nothing else, so the factorisation enqueues it on its panel stream, directly in front of that leaf
@@ -1500,33 +1272,19 @@ extern "C" int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, in
   const std::function<int(hipStream_t)> stats = [&](hipStream_t xs) -> int {
     return gpk_row_stats((void*)xs, Kfu, rows, m, l.ld, q_mu, q_diag ? q_sqrt : nullptr, P, 1.0, 0.0, s0, fmean, q_diag ? ssq : nullptr);
   };
-  XTail xt;
-  if (!q_diag && rows > 0) {   // (beside the projection GEMM; with a diagonal q_sqrt nothing would run beside it)
-    xt.work = &stats;
-    hk.x_tail = &xt;
-  }
   rc = potrf_core(s, T, m, rows, l.ld, 1, 0, invd, 0, info, hk);
   if (rc) return rc;
-  if (!xt.used) {
-    rc = stats(s);
-    if (rc) return rc;
-  }
-  VarexpExtra ex;
-  if (xt.used) { ex.wait_ptr = xt.done_ptr; ex.wait_val = xt.done_val; ex.wait_info = info; }
+  rc = stats(s);
+  if (rc) return rc;
   if (!q_diag) {
     // L = band_part(q_sqrt,-1,0); LTA = L^T A; ssq = sum LTA^2   (util.py:151-164)
     if (!side) {
       rc = gpk_transpose(stream, q_sqrt, m, m, m, LqT, l.ld, 1, P, (long)m * m, (long)m * l.ld);
       if (rc) return rc;
     }
-    // (the column-slot partials of the projection are summed by the variational-expectation kernel: no sum_parts launch)
     rc = project_parts(s, Kfu, rows, m, l.ld, 0, LqT, l.ld, P, w + l.off_proj, gpk_project_workspace_bytes(rows, m, P));
     if (rc) return rc;
-    if (rows > 0 && GPK_TUNE(VAREXP_SUMS_PARTS, 0)) {
-      ex.ssq_part = (const double*)(w + l.off_proj);
-      ex.ssq_nt = 2 * gpk_gemm_tiles_n(m);
-      ex.ssq_stride = (long)ex.ssq_nt * rows;
-    } else if (rows > 0) {
+    if (rows > 0) {
       rc = gpk_launch_sum_parts(s, (const double*)(w + l.off_proj), 2 * gpk_gemm_tiles_n(m), rows, (long)2 * gpk_gemm_tiles_n(m) * rows, P, ssq);
       if (rc) return rc;
     }
@@ -1534,7 +1292,7 @@ extern "C" int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, in
   // sum_b var_exp_b  (likelihoods/scalar_continuous.py:139-148, svgp.py:174,181)
   int c0 = 0;
   rc = gpk_launch_varexp_stage1(s, Yb, ldyb, fmean, rows, P, s0, 0, ssq, &variance, 0, noise_variance,
-                                mean_const, nullptr, part0, &c0, noise_rows, &ex);
+                                mean_const, nullptr, part0, &c0, noise_rows);
   if (rc) return rc;
   const double* p0[1] = {part0};
   const double one = 1.0;

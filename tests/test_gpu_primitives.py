@@ -408,8 +408,8 @@ def test_per_row_noise_variances(gpu):
 def test_svgp_elbo_shard_column_groups(gpu, m, rows, d, P):
     """The fused shard over the column-group shapes of the extra-row solve / q_sqrt projection, against the oracle: one
     group (m = 256), ragged last group (640 = 512 + 128), shrinking tail groups (1024, 1152), several latents, ragged
-    row counts; bulk GEMMs ticketed under the software CU reservation.  (With the A/B library, GPK_LIBRARY=libgpk_exp.so,
-    the same test covers GPK_STREAM_PROJ=0/1 and GPK_SOFT_RESERVE=0/1 from the environment: tools/ab.sh.)"""
+    row counts; bulk GEMMs capped beside the latency chain.  (With the A/B library, GPK_LIBRARY=libgpk_exp.so, the same
+    test runs under whatever GPK_<NAME> tunables the environment sets: tools/ab.sh.)"""
     from gpflow_amd import ops
     rng = np.random.default_rng(13)
     X = rng.normal(size=(rows, d))

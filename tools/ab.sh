@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B runs of bench.py under the tunables of the EXPERIMENTAL library (make -C gpflow_amd/csrc exp):
-#   tools/ab.sh "GPK_FLOW=0" "GPK_SOFT_RESERVED_CUS=48" ...
+#   tools/ab.sh "GPK_EXTRA_MAX_WGS=256" "GPK_RESERVED_CUS=48" ...
 # The first line is always the product library with no tunables.  Every run is under a 75 s timeout.
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 run() {

@@ -27,4 +27,4 @@ for k in (256, 512, 1024, 2048):
             ts.append(e0.elapsed_time(e1) * 1e3)
         us = float(np.median(ts))
         res.append("K=%d beta=%g: %.0f us (%.1f / round, MFMA floor %.1f)" % (k, beta, us, us / 4, 2.0 * 128 * 128 * k / 307.2e3))
-print("cap=%s pc=%s\n  " % (os.environ.get("GPK_GEMM_NT_MAX_WGS", "0"), os.environ.get("GPK_CAP_PREFETCH_C", "1")) + "\n  ".join(res))
+print("cap=%s\n  " % os.environ.get("GPK_GEMM_NT_MAX_WGS", "0") + "\n  ".join(res))

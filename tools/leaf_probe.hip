@@ -1,6 +1,6 @@
 // Stand-alone probe of the leaf kernels (round 6): correctness against a host Cholesky / inverse for full and ragged blocks,
-// the non-positive-pivot report, in-kernel phase timers and the per-launch time of back-to-back launches, for
-//   v1  leaf_device.h   (rounds 1 - 5)          v2  leaf2_device.h  (round 6)
+// the non-positive-pivot report, in-kernel phase timers and the per-launch time of back-to-back launches of the round-6 leaf
+// (v2, leaf2_device.h).  (The round 1 - 5 leaf, v1, no longer factors: DESIGN 6, "Closed experiments whose code was removed".)
 // Build + run on the GPU box:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=on tools/leaf_probe.hip -o /tmp/leaf_probe && /tmp/leaf_probe
 #include "../gpflow_amd/csrc/leaf2_device.h"
 #include <cmath>
@@ -13,10 +13,9 @@
 using namespace gpk_leaf;
 
 template <int V>
-__global__ __launch_bounds__(V == 1 ? NT : gpk_leaf2::NT2) void k_leaf(double* A, long lda, int nb, double* inv, int* info, long long* dbg) {
+__global__ __launch_bounds__(gpk_leaf2::NT2) void k_leaf(double* A, long lda, int nb, double* inv, int* info, long long* dbg) {
   extern __shared__ __attribute__((aligned(16))) double S[];
-  if constexpr (V == 1) leaf_body<false>(S, A, lda, nb, inv, info, 0, dbg);
-  else if constexpr (V == 2) gpk_leaf2::leaf2_body<false>(S, A, lda, nb, inv, info, 0, dbg);
+  if constexpr (V == 2) gpk_leaf2::leaf2_body<false>(S, A, lda, nb, inv, info, 0, dbg);
   else gpk_leaf2::leaf2_body<true>(S, A, lda, nb, inv, info, 0, dbg);
 }
 
@@ -53,12 +52,11 @@ static void host_chol(const std::vector<double>& A, int n, std::vector<double>& 
 
 template <int V>
 static void launch(double* dA, long lda, int nb, double* dinv, int* dinfo, long long* ddbg) {
-  hipLaunchKernelGGL((k_leaf<V>), dim3(1), dim3(V == 1 ? NT : gpk_leaf2::NT2), gpk_leaf2::LEAF2_LDS, 0, dA, lda, nb, dinv, dinfo, ddbg);
+  hipLaunchKernelGGL((k_leaf<V>), dim3(1), dim3(gpk_leaf2::NT2), gpk_leaf2::LEAF2_LDS, 0, dA, lda, nb, dinv, dinfo, ddbg);
 }
 
 int main(int argc, char** argv) {
   const int reps = argc > 1 ? atoi(argv[1]) : 200;
-  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_leaf<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gpk_leaf2::LEAF2_LDS));
   CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_leaf<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gpk_leaf2::LEAF2_LDS));
   CK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_leaf<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gpk_leaf2::LEAF2_LDS));
   const int lda = 136;
@@ -84,14 +82,15 @@ int main(int argc, char** argv) {
         A[(size_t)i * nb + j] = s;
       }
     host_chol(A, nb, L, X);
-    for (int v = 1; v <= 2; ++v) {
+    {
+      const int v = 2;
       std::vector<double> hA((size_t)128 * lda, -7.0), hinv((size_t)128 * 128, -9.0);   // sentinels: nothing outside the block may change
       for (int i = 0; i < nb; ++i)
         for (int j = 0; j < nb; ++j) hA[(size_t)i * lda + j] = A[(size_t)i * nb + j];
       CK(hipMemcpy(dA, hA.data(), sizeof(double) * hA.size(), hipMemcpyHostToDevice));
       CK(hipMemcpy(dinv, hinv.data(), sizeof(double) * hinv.size(), hipMemcpyHostToDevice));
       CK(hipMemset(dinfo, 0, sizeof(int)));
-      if (v == 1) launch<1>(dA, lda, nb, dinv, dinfo, nullptr); else launch<2>(dA, lda, nb, dinv, dinfo, nullptr);
+      launch<2>(dA, lda, nb, dinv, dinfo, nullptr);
       CK(hipDeviceSynchronize());
       std::vector<double> oA(hA.size()), oinv(hinv.size());
       int info = -1;
@@ -117,7 +116,8 @@ int main(int argc, char** argv) {
     }
   }
   // non-positive pivot: A[77][77] made very negative -> info = 78; NaN input -> info = its column + 1
-  for (int v = 1; v <= 2; ++v)
+  {
+    const int v = 2;
     for (int bad : {0, 3, 77, 127}) {
       std::vector<double> hA((size_t)128 * lda, 0.0);
       for (int i = 0; i < 128; ++i) hA[(size_t)i * lda + i] = 2.0 + 0.01 * i;
@@ -125,12 +125,13 @@ int main(int argc, char** argv) {
       hA[(size_t)bad * lda + bad] = -3.0;
       CK(hipMemcpy(dA, hA.data(), sizeof(double) * hA.size(), hipMemcpyHostToDevice));
       CK(hipMemset(dinfo, 0, sizeof(int)));
-      if (v == 1) launch<1>(dA, lda, 128, dinv, dinfo, nullptr); else launch<2>(dA, lda, 128, dinv, dinfo, nullptr);
+      launch<2>(dA, lda, 128, dinv, dinfo, nullptr);
       int info = -1;
       CK(hipMemcpy(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost));
       printf("v%d bad pivot at %3d -> info %d %s\n", v, bad, info, info == bad + 1 ? "ok" : "FAIL");
       if (info != bad + 1) ++fails;
     }
+  }
   // timing: full block
   {
     const int nb = 128;
@@ -142,15 +143,16 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&dA0, sizeof(double) * hA.size()));
     CK(hipMemcpy(dA0, hA.data(), sizeof(double) * hA.size(), hipMemcpyHostToDevice));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    for (int v = 1; v <= 2; ++v) {
+    {
+      const int v = 2;
       long long dbg[8];
       for (int r = 0; r < 3; ++r) {
         CK(hipMemcpy(dA, dA0, sizeof(double) * hA.size(), hipMemcpyDeviceToDevice));
-        if (v == 1) launch<1>(dA, lda, nb, dinv, dinfo, ddbg); else launch<2>(dA, lda, nb, dinv, dinfo, ddbg);
+        launch<2>(dA, lda, nb, dinv, dinfo, ddbg);
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(dbg, ddbg, sizeof(dbg), hipMemcpyDeviceToHost));
-        printf("v%d phases (us, 100 MHz clock): %s %.2f  factor %.2f  invert %.2f  %s %.2f  total %.2f\n", v, v == 1 ? "load" : "-",
-               dbg[0] / 100.0, dbg[1] / 100.0, dbg[2] / 100.0, v == 1 ? "store" : "tail", dbg[3] / 100.0, dbg[4] / 100.0);
+        printf("v%d phases (us, 100 MHz clock): %s %.2f  factor %.2f  invert %.2f  %s %.2f  total %.2f\n", v, "-",
+               dbg[0] / 100.0, dbg[1] / 100.0, dbg[2] / 100.0, "tail", dbg[3] / 100.0, dbg[4] / 100.0);
       }
       // back-to-back launches on one stream (the factor of a factor is meaningless; the time is not data dependent as long as
       // the pivots stay positive: refresh the block with a device copy every launch, timed separately and subtracted)
@@ -161,7 +163,7 @@ int main(int argc, char** argv) {
       CK(hipEventRecord(e0, 0));
       for (int r = 0; r < reps; ++r) {
         CK(hipMemcpyAsync(dA, dA0, sizeof(double) * hA.size(), hipMemcpyDeviceToDevice, 0));
-        if (v == 1) launch<1>(dA, lda, nb, dinv, dinfo, nullptr); else launch<2>(dA, lda, nb, dinv, dinfo, nullptr);
+        launch<2>(dA, lda, nb, dinv, dinfo, nullptr);
       }
       CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms_both, e0, e1));
       printf("v%d back-to-back: %.2f us per launch (copy + leaf %.2f, copy alone %.2f)\n", v, (ms_both - ms_copy) * 1e3 / reps,
