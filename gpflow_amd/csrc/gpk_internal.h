@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <functional>
 #include "../../include/gpk.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -99,6 +100,17 @@ struct GemmArgs {
   int tile_snake;   // set by the launcher only (generic kernel, under-filled triangular-K projections): heavy / light tiles alternate per CU
   int tail_first1;  // set by the launcher only (generic 64 x 64 kernel; launch_fast, "tail split"): 1 + first position, 0 = off
 };
+static inline GemmArgs gemm_base(int m, int n, int k, double alpha, const double* A, long lda,
+                                 const double* B, long ldb, double beta, double* C, long ldc, int batch,
+                                 long sA, long sB, long sC) {
+  GemmArgs g{};
+  g.A = A; g.lda = lda; g.strideA = sA;
+  g.B = B; g.ldb = ldb; g.strideB = sB;
+  g.C = C; g.ldc = ldc; g.strideC = sC;
+  g.m = m; g.n = n; g.k = k; g.alpha = alpha; g.beta = beta;
+  g.b_tri_rows = n; g.batch = batch > 0 ? batch : 1;
+  return g;
+}
 int gpk_launch_gemm(hipStream_t s, const GemmArgs& a);
 bool gpk_gemm_takes_latency_kernel(const GemmArgs& a);   // the launch would run on the one-shot latency kernel (sig / wait honoured)
 
@@ -115,6 +127,30 @@ int gpk_profile_gemm_is_on();  // per-launch event timing active (bench roofline
 // A: pointer to the diagonal block (row-major, lda); nb <= NB valid rows/cols.
 int gpk_launch_leaf(hipStream_t s, double* A, long lda, long strideA, int nb, double* invd,
                     long strideInv, int* info, int col0, int batch, int already_factored);
+
+// ---- factorisation (potrf.hip), as the fused drivers (drivers.hip) call it ----------------------
+// The trapezoid A is [(n + extra) x n]: the top square is factored, the extra rows come back as  B L^-T.
+// p_prologue: work of the CALLER that the first leaf waits for and nothing else does -- the fused drivers' Kuu build.  It is
+// enqueued ON the panel stream, so the first leaf follows it back to back (0.3 us) instead of behind an event record on the caller's
+// stream and a wait on the panel stream (~15 us per step, round 5).
+// x_prologue: work of the CALLER that belongs on the bulk stream before the first extra-row group (the SVGP driver's Kfu
+// build, transposes, KL).  It is enqueued after the first panel's chain kernels: every host call issued before the first
+// leaf delays the whole step, and nothing on the bulk stream is needed for ~4 panels.
+// late_work: work of the CALLER that nothing in the factorisation needs (the whitened driver's tril(q_sqrt)^T and KL term).  It is
+// enqueued on the rest-update stream after the sixth panel: the first four panels are HOST-bound -- ~7 enqueue calls of 5 - 8 us
+// per panel against ~55 us of kernels -- so every launch issued there delays the chain (round 5: the second leaf started 52 us
+// after the first strip had finished), and the rest-update stream has a leaf's time of slack per panel.
+// (All three are called while the factorisation is being enqueued, never later; an empty one is skipped.)
+typedef std::function<int(hipStream_t)> StreamWork;
+struct PotrfHooks {
+  StreamWork x_prologue, p_prologue, late_work;
+};
+// tri = n: the LAST n extra rows are the identity (written by the factorisation) and come back as L^-T.  Row j of that block
+// stays zero left of column j, so column group [c0, c1) only has to process its first c1 rows: n^3 / 3 flop instead of n^3.
+// tri_prefilled: the caller (or its x_prologue) puts an UPPER-TRIANGULAR block there itself -- tril(q_sqrt)^T of the
+// un-whitened ELBO: the same rows-stay-zero argument holds for any block that is zero left of its diagonal.
+int gpk_potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, long strideA, double* invd, int zero_upper,
+                   int* info, const PotrfHooks& hooks = PotrfHooks(), int tri = 0, bool tri_prefilled = false);
 
 // ---- rbf.hip ---------------------------------------------------------------------------------
 // (entry point gpk_kernel_matrix is defined there)

@@ -1,6 +1,6 @@
-// Host-side orchestration (no device code here): the trapezoidal blocked Cholesky, triangular solves
-// against a cached factor, the projection onto q_sqrt, and the two fused model drivers
-// (GPR.log_marginal_likelihood, one shard of SVGP.elbo).
+// Host-side orchestration (no device code here): the trapezoidal blocked Cholesky on its per-device stream set and the
+// triangular solves against a cached factor.  (What merely CALLS the factorisation -- the projection onto q_sqrt and the
+// fused model drivers -- is drivers.hip, through gpk_potrf_core.)
 //
 // Trapezoidal Cholesky.  A is [(n + extra) x n]: the top square block is factored, the `extra` rows
 // below ride along through every panel solve and trailing update and come out as  B L^-T  -- the
@@ -13,25 +13,12 @@
 // as bulk work on a stream of its own.
 #include "gpk_internal.h"
 #include <algorithm>
-#include <functional>
 #include <mutex>
 #include <vector>
 
 namespace {
 constexpr int NB = GPK_NB;
 constexpr int NBO = 512;  // column group of the right-looking row solves (extra rows, gpk_trsm)
-
-inline GemmArgs gemm_base(int m, int n, int k, double alpha, const double* A, long lda,
-                          const double* B, long ldb, double beta, double* C, long ldc, int batch,
-                          long sA, long sB, long sC) {
-  GemmArgs g{};
-  g.A = A; g.lda = lda; g.strideA = sA;
-  g.B = B; g.ldb = ldb; g.strideB = sB;
-  g.C = C; g.ldc = ldc; g.strideC = sC;
-  g.m = m; g.n = n; g.k = k; g.alpha = alpha; g.beta = beta;
-  g.b_tri_rows = n; g.batch = batch > 0 ? batch : 1;
-  return g;
-}
 
 // how a bulk GEMM beside the latency chain is launched
 struct Bulk {
@@ -411,29 +398,14 @@ int solve_group_bwd(hipStream_t s, double* Bm, long ldb, int rows, const double*
   }
   return 0;
 }
+}  // namespace
 
-// p_prologue: work of the CALLER that the first leaf waits for and nothing else does -- the fused drivers' Kuu build.  It is
-// enqueued ON the panel stream, so the first leaf follows it back to back (0.3 us) instead of behind an event record on the caller's
-// stream and a wait on the panel stream (~15 us per step, round 5).
-// x_prologue: work of the CALLER that belongs on the bulk stream before the first extra-row group (the SVGP driver's Kfu
-// build, transposes, KL).  It is enqueued after the first panel's chain kernels: every host call issued before the first
-// leaf delays the whole step, and nothing on the bulk stream is needed for ~4 panels.
-// late_work: work of the CALLER that nothing in the factorisation needs (the whitened driver's tril(q_sqrt)^T and KL term).  It is
-// enqueued on the rest-update stream after the sixth panel: the first four panels are HOST-bound -- ~7 enqueue calls of 5 - 8 us
-// per panel against ~55 us of kernels -- so every launch issued there delays the chain (round 5: the second leaf started 52 us
-// after the first strip had finished), and the rest-update stream has a leaf's time of slack per panel.
-typedef std::function<int(hipStream_t)> StreamWork;
-struct PotrfHooks {
-  const StreamWork* x_prologue = nullptr;
-  const StreamWork* p_prologue = nullptr;
-  const StreamWork* late_work = nullptr;
-};
-
-int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, long strideA, double* invd, int zero_upper,
-               int* info, const PotrfHooks& hooks = PotrfHooks(), int tri = 0, bool tri_prefilled = false) {
-  const StreamWork* x_prologue = hooks.x_prologue;
-  const StreamWork* p_prologue = hooks.p_prologue;
-  const StreamWork* late_work = hooks.late_work;
+// (the hooks, tri and tri_prefilled: gpk_internal.h)
+int gpk_potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, long strideA, double* invd, int zero_upper,
+                   int* info, const PotrfHooks& hooks, int tri, bool tri_prefilled) {
+  const StreamWork& x_prologue = hooks.x_prologue;
+  const StreamWork& p_prologue = hooks.p_prologue;
+  const StreamWork& late_work = hooks.late_work;
   if (!A || !invd || n < 0 || extra < 0 || lda < n) return GPK_E_ARG;
   if (tri && (tri != n || extra < n || batch > 1)) return GPK_E_ARG;
   if (batch <= 0) batch = 1;
@@ -442,10 +414,6 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
     if (info) GPK_HIP(hipMemsetAsync(info, 0, sizeof(int) * batch, S));
     return 0;
   }
-  // tri = n: the LAST n extra rows are the identity (written here) and come back as L^-T.  Row j of that block stays
-  // zero left of column j, so column group [c0, c1) only has to process its first c1 rows: n^3 / 3 flop instead of n^3.
-  // tri_prefilled: the caller (or its x_prologue) puts an UPPER-TRIANGULAR block there itself -- tril(q_sqrt)^T of the
-  // un-whitened ELBO: the same rows-stay-zero argument holds for any block that is zero left of its diagonal.
   if (tri && !tri_prefilled) {
     const int rci = gpk_launch_set_identity(S, A + (long)(n + extra - tri) * lda, n, lda);
     if (rci) return rci;
@@ -479,15 +447,15 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
   int rc;
   if (n <= NB) {  // one leaf; nothing to overlap
     if (p_prologue) {
-      rc = (*p_prologue)(S);
+      rc = p_prologue(S);
       if (rc) return rc;
     }
     if (x_prologue) {
-      rc = (*x_prologue)(S);
+      rc = x_prologue(S);
       if (rc) return rc;
     }
     if (late_work) {
-      rc = (*late_work)(S);
+      rc = late_work(S);
       if (rc) return rc;
     }
     rc = factor_panel(S, A, R, 0, n, lda, batch, strideA, invd, strideInv, info);
@@ -529,11 +497,11 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
              evJoinX = aux->ev[2 * npanels + 3];
   const bool p_on_panel = p_prologue && GPK_TUNE(KUU_ON_PANEL, 1);
   if (p_prologue && !p_on_panel) {
-    rc = (*p_prologue)(S);
+    rc = p_prologue(S);
     if (rc) return rc;
   }
   if (x_prologue && !useX) {  // the extra rows ride through the panel solves: they must exist before the first one
-    rc = (*x_prologue)(S);
+    rc = x_prologue(S);
     if (rc) return rc;
   }
   GPK_HIP(hipEventRecord(evFork, S));  // fork: everything already queued on S comes first
@@ -541,7 +509,7 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
   if (B != S) GPK_HIP(hipStreamWaitEvent(B, evFork, 0));
   if (useX && X != B) GPK_HIP(hipStreamWaitEvent(X, evFork, 0));
   if (p_on_panel) {
-    rc = (*p_prologue)(P);
+    rc = p_prologue(P);
     if (rc) return rc;
   }
   hipStream_t last_bulk = B;
@@ -771,12 +739,12 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
       last_rest = p;
     }
     if (p == 0 && x_prologue && useX) {
-      rc = (*x_prologue)(X);
+      rc = x_prologue(X);
       if (rc) return rc;
     }
     if (late_work && p == late_panel) {
       // (on the stream of the most recent rest-update, whose last event the join below waits for)
-      rc = (*late_work)(last_bulk);
+      rc = late_work(last_bulk);
       if (rc) return rc;
     }
     // ---- X: the extra rows against the finished columns, in groups of up to 512 columns (so that the big
@@ -828,7 +796,6 @@ int potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, 
   if (zero_upper) return gpk_launch_zero_upper(S, A, n, lda, batch, strideA);
   return 0;
 }
-}  // namespace
 
 extern "C" int gpk_stream_selfcheck(double* us_now, double* us_first, int* recreated) {
   int dev = 0;
@@ -857,12 +824,12 @@ extern "C" int gpk_chain_handoff_mode(void) {
 
 extern "C" int gpk_potrf(void* stream, double* A, int n, int extra, long lda, int batch,
                          long strideA, double* invd, int zero_upper, int* info) {
-  return potrf_core((hipStream_t)stream, A, n, extra, lda, batch, strideA, invd, zero_upper, info);
+  return gpk_potrf_core((hipStream_t)stream, A, n, extra, lda, batch, strideA, invd, zero_upper, info);
 }
 
 extern "C" int gpk_potrf_inv(void* stream, double* A, int n, int extra, long lda, double* invd, int zero_upper,
                              int* info) {
-  return potrf_core((hipStream_t)stream, A, n, extra + n, lda, 1, 0, invd, zero_upper, info, PotrfHooks(), n);
+  return gpk_potrf_core((hipStream_t)stream, A, n, extra + n, lda, 1, 0, invd, zero_upper, info, PotrfHooks(), n);
 }
 
 extern "C" int gpk_trtri_blocks(void* stream, const double* L, int n, long ldl, int batch,
@@ -930,493 +897,4 @@ extern "C" int gpk_transpose_factor(void* stream, const double* L, long ldl, con
   if (rc) return rc;
   const int nblk = gpk_cdiv(n, NB);
   return gpk_transpose(stream, invd, NB, NB, NB, invdT, NB, 0, nblk, (long)NB * NB, (long)NB * NB);
-}
-
-// ---- projection:  ssq[p,b] = sum_j ( sum_k At[b,k] Lq_p[k,j] )^2 ---------------------------------------
-extern "C" size_t gpk_project_workspace_bytes(int rows, int m, int P) {
-  return (size_t)P * 2 * gpk_gemm_tiles_n(m) * rows * sizeof(double);
-}
-
-namespace {
-// the GEMM alone: partials [P][nt = 2 * tiles_n][rows] in ws, one per 64 output columns
-int project_parts(hipStream_t s, const double* At, int rows, int m, long ldat, long strideAt, const double* LqT, long ldl, int P, void* ws,
-                  size_t ws_bytes) {
-  if ((!At && rows > 0) || !LqT || rows < 0 || m <= 0 || P <= 0 || strideAt < 0) return GPK_E_ARG;
-  if (!ws || ws_bytes < gpk_project_workspace_bytes(rows, m, P)) return GPK_E_WORKSPACE;
-  if (rows == 0) return 0;
-  const int nt = 2 * gpk_gemm_tiles_n(m);
-  GemmArgs g = gemm_base(rows, m, m, 1.0, At, ldat, LqT, ldl, 0.0, nullptr, 0, P, strideAt, (long)m * ldl, 0);
-  g.b_tri = 1;  // LqT[j,k] = Lq[k,j] vanishes for k < j
-  g.epi = 1; g.sq_cols = m; g.c2_cols = 0;
-  g.part = (double*)ws; g.part_ld = rows; g.stridePart = (long)nt * rows;
-  g.C2 = (double*)ws; g.ldc2 = 0; g.strideC2 = 0;
-  return gpk_launch_gemm(s, g);
-}
-}  // namespace
-
-extern "C" int gpk_project_batched(void* stream, const double* At, int rows, int m, long ldat, long strideAt,
-                                   const double* LqT, long ldl, int P, double* ssq, void* ws, size_t ws_bytes) {
-  if (!ssq && rows > 0) return GPK_E_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = project_parts(s, At, rows, m, ldat, strideAt, LqT, ldl, P, ws, ws_bytes);
-  if (rc || rows == 0) return rc;
-  const int nt = 2 * gpk_gemm_tiles_n(m);
-  return gpk_launch_sum_parts(s, (const double*)ws, nt, rows, (long)nt * rows, P, ssq);
-}
-
-extern "C" int gpk_project(void* stream, const double* At, int rows, int m, long ldat,
-                           const double* LqT, long ldl, int P, double* ssq, void* ws,
-                           size_t ws_bytes) {
-  return gpk_project_batched(stream, At, rows, m, ldat, 0, LqT, ldl, P, ssq, ws, ws_bytes);
-}
-
-// ---- fused driver: GPR.log_marginal_likelihood ----------------------------------------------------------
-namespace {
-struct LmlLayout {
-  long ld; size_t off_T, off_invd, off_part, off_logdet, total;
-};
-LmlLayout lml_layout(int n, int P) {
-  LmlLayout l{};
-  l.ld = (long)gpk_align_up((size_t)n, 8);
-  size_t o = 0;
-  l.off_T = o; o += gpk_align_up((size_t)(n + P) * l.ld * sizeof(double), 256);
-  l.off_invd = o; o += gpk_align_up(gpk_invd_elems(n, 1) * sizeof(double), 256);
-  l.off_part = o; o += gpk_align_up((size_t)GPK_REDUCE_MAXPART * sizeof(double), 256);
-  l.off_logdet = o; o += 256;
-  l.total = o;
-  return l;
-}
-}  // namespace
-
-extern "C" size_t gpk_gpr_lml_workspace_bytes(int n, int d, int P) {
-  (void)d;
-  return lml_layout(n, P).total;
-}
-
-extern "C" int gpk_gpr_lml(void* stream, int family, const double* X, int n, int d, long ldx,
-                           const double* Y, int P, long ldy, const double* ls_host, int ard,
-                           double variance, double noise_variance, const double* noise_rows, double mean_const,
-                           double* out, int* info, void* ws, size_t ws_bytes) {
-  if (!X || !Y || !out || !info || n <= 0 || P <= 0) return GPK_E_ARG;
-  const LmlLayout l = lml_layout(n, P);
-  if (!ws || ws_bytes < l.total) return GPK_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  double* T = (double*)(w + l.off_T);
-  double* invd = (double*)(w + l.off_invd);
-  double* part = (double*)(w + l.off_part);
-  double* logdet = (double*)(w + l.off_logdet);
-  int rc;
-  // K(X,X) + noise I, lower tiles only (gpr.py:100-101); a heteroskedastic likelihood (noise_rows: one variance per data
-  // row, likelihoods/scalar_continuous.py:92-111) adds its vector to the diagonal instead (model_utils.py:46-50).
-  rc = gpk_kernel_matrix(stream, family, X, n, ldx, nullptr, 0, 0, d, ls_host, ard, variance,
-                         noise_rows ? 0.0 : noise_variance, 1, T, l.ld);
-  if (rc) return rc;
-  if (noise_rows) {
-    rc = gpk_diag_add(stream, T, n, l.ld, noise_rows);
-    if (rc) return rc;
-  }
-  // (Y - m)^T as P extra rows (gpr.py:103, logdensities.py:149)
-  rc = gpk_launch_transpose_shift(s, Y, n, P, ldy, T + (long)n * l.ld, l.ld, -mean_const);
-  if (rc) return rc;
-  // L = chol(K); extra rows -> alpha^T = (L^-1 (Y-m))^T  (gpr.py:102, logdensities.py:150)
-  rc = potrf_core(s, T, n, P, l.ld, 1, 0, invd, 0, info);
-  if (rc) return rc;
-  // p = -0.5 sum alpha^2 - 0.5 N log 2pi - sum log diag L, summed over the P columns
-  rc = gpk_sum_log_diag(stream, T, n, l.ld, 1, 0, logdet);
-  if (rc) return rc;
-  int cnt = 0;
-  rc = gpk_launch_sumsq_stage1(s, T + (long)n * l.ld, P, n, l.ld, 0, part, &cnt);
-  if (rc) return rc;
-  const double* parts[2] = {part, logdet};
-  const int counts[2] = {cnt, 1};
-  const double scales[2] = {-0.5, -(double)P};
-  const double add = -0.5 * (double)n * (double)P * 1.8378770664093453;
-  return gpk_launch_final(s, 2, parts, counts, scales, add, out);
-}
-
-// ---- fused driver: one shard of SVGP.elbo (whitened; shared kernel over the P latents) ----------------
-namespace {
-struct ElboLayout {
-  long ld; int nt;
-  size_t off_T, off_invd, off_LqT, off_s0, off_fmean, off_ssq, off_proj, off_part0, off_part1, off_part2, off_V, total;
-};
-
-ElboLayout elbo_layout(int m, int rows, int P, int q_diag, int whiten) {
-  ElboLayout l{};
-  l.ld = (long)gpk_align_up((size_t)m, 8);
-  l.nt = 2 * gpk_gemm_tiles_n(m);
-  size_t o = 0;
-  // (minibatch rows padded to whole 32-row blocks -- the single-launch step kernel's layout, DESIGN 6 "Closed experiments whose code
-  // was removed"; kept so that the workspace size does not change: the padding rows are never initialised and never read)
-  const size_t rows_pad = gpk_align_up((size_t)rows, 32);
-  // T [m + rows_pad rows], then -- directly behind it, so that the un-whitened form can use ONE trapezoid [Kuu ; Kfu ; q_mu^T ;
-  // tril(q_sqrt_p)^T] with the minibatch rows unpadded -- room for P + P m more rows; the whitened form keeps its LqT there
-  l.off_T = o; o += (size_t)(m + rows_pad) * l.ld * sizeof(double);
-  // (un-whitened with a diagonal q_sqrt: the trapezoid is [Kuu ; Kfu ; q_mu^T ; I] -- P + m more rows)
-  const size_t tail_rows = q_diag ? (whiten ? 0 : (size_t)P + m + 32) : (size_t)P + (size_t)P * m + 32;
-  l.off_LqT = o; o = gpk_align_up(o + tail_rows * l.ld * sizeof(double), 256);
-  l.off_invd = o; o += gpk_align_up(gpk_invd_elems(m, 1) * sizeof(double), 256);
-  l.off_s0 = o; o += gpk_align_up((size_t)rows * sizeof(double), 256);
-  l.off_fmean = o; o += gpk_align_up((size_t)rows * P * sizeof(double), 256);
-  l.off_ssq = o; o += gpk_align_up((size_t)rows * P * sizeof(double), 256);
-  // projection partials (full q_sqrt), or -- un-whitened with a diagonal q_sqrt -- the second solve A^T Lm^-1 [rows, ld]
-  l.off_proj = o; o += q_diag ? (whiten ? 0 : gpk_align_up((size_t)rows * l.ld * sizeof(double), 256))
-                              : gpk_align_up(gpk_project_workspace_bytes(rows, m, P), 256);
-  l.off_part0 = o; o += gpk_align_up((size_t)GPK_REDUCE_MAXPART * sizeof(double), 256);
-  l.off_part1 = o; o += gpk_align_up((size_t)GPK_REDUCE_MAXPART * sizeof(double), 256);
-  l.off_part2 = o; o += gpk_align_up((size_t)(GPK_REDUCE_MAXPART + 64) * sizeof(double), 256);
-  l.off_V = o; o += gpk_align_up((size_t)m * P * sizeof(double), 256);
-  l.total = o;
-  return l;
-}
-}  // namespace
-
-extern "C" size_t gpk_svgp_elbo_workspace_bytes(int m, int rows, int d, int P, int q_diag, int whiten) {
-  (void)d;
-  return elbo_layout(m, rows, P, q_diag, whiten).total;
-}
-
-extern "C" int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, int m, long ldz,
-                                   const double* Xb, const double* Yb, int rows, long ldxb,
-                                   long ldyb, int d, int P, const double* ls_host, int ard,
-                                   double variance, double noise_variance, const double* noise_rows, double jitter,
-                                   double mean_const, const double* q_mu, const double* q_sqrt,
-                                   int q_diag, int whiten, double* out, int* info, void* ws,
-                                   size_t ws_bytes) {
-  if (!Z || (rows > 0 && (!Xb || !Yb)) || !q_mu || !q_sqrt || !out || !info || m <= 0 || rows < 0 || P <= 0 || P > 16)
-    return GPK_E_ARG;
-  const ElboLayout l = elbo_layout(m, rows, P, q_diag, whiten);
-  if (!ws || ws_bytes < l.total) return GPK_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  double* T = (double*)(w + l.off_T);
-  if (!whiten && q_diag) {
-    // ---- whiten = 0 with a DIAGONAL q_sqrt [m, P] (kullback_leiblers.py:128-165: diag branch with K; conditionals/util.py:139-149)
-    // on ONE trapezoid [Kuu + jitter I ; Kfu ; q_mu^T ; I]: the identity rows come back as Lm^-T (written and solved by the
-    // factorisation at m^3 / 3, gpk_potrf_inv's row skipping), which gives everything the reference takes from its two
-    // factorisations and three triangular solves:
-    //     A^T = Kfu Lm^-T (fvar's Knn - sum A^2),  a^T = (Lm^-1 q_mu)^T (Mahalanobis term),  (Kuu^-1)_ii = |row i of Lm^-T|^2 (trace term),
-    //     A2^T = A^T Lm^-1 as one triangular-K GEMM (util.py:139's second solve of the minibatch columns) -> fmean = A2^T q_mu,
-    //     ssq = sum_i (A2_ib q_sqrt_ip)^2 (util.py:149).
-    double* invd_d = (double*)(w + l.off_invd);
-    double* s0_d = (double*)(w + l.off_s0);
-    double* fmean_d = (double*)(w + l.off_fmean);
-    double* ssq_d = (double*)(w + l.off_ssq);
-    double* pa = (double*)(w + l.off_part0);
-    double* pb = (double*)(w + l.off_part1);
-    double* pc = (double*)(w + l.off_part2);          // [MAXPART] trace / log det q partials, then [1] log det Lm
-    double* Kfu_d = T + (long)m * l.ld;
-    double* arow = Kfu_d + (long)rows * l.ld;          // [P, m]
-    double* LinvT = arow + (long)P * l.ld;             // [m, ld]: Lm^-T (upper triangular)
-    double* A2 = (double*)(w + l.off_proj);            // [rows, ld]
-    int rcd = 0;
-    const std::function<int(hipStream_t)> kuu_d = [&](hipStream_t ps) -> int {
-      return gpk_kernel_matrix((void*)ps, family, Z, m, ldz, nullptr, 0, 0, d, ls_host, ard, variance, jitter, 1, T, l.ld);
-    };
-    const std::function<int(hipStream_t)> prod = [&](hipStream_t xs) -> int {
-      int r = gpk_kernel_matrix((void*)xs, family, Xb, rows, ldxb, Z, m, ldz, d, ls_host, ard, variance, 0.0, 0, Kfu_d, l.ld);
-      if (r) return r;
-      return gpk_transpose((void*)xs, q_mu, m, P, P, arow, l.ld, 0, 1, 0, 0);
-    };
-    PotrfHooks hkd;
-    hkd.x_prologue = &prod;
-    hkd.p_prologue = &kuu_d;
-    rcd = potrf_core(s, T, m, rows + P + m, l.ld, 1, 0, invd_d, 0, info, hkd, m);
-    if (rcd) return rcd;
-    if (rows > 0) {
-      GemmArgs g = gemm_base(rows, m, m, 1.0, Kfu_d, l.ld, LinvT, l.ld, 0.0, A2, l.ld, 1, 0, 0, 0);
-      g.b_tri = 1;  // LinvT[j, k] = Lm^-1[k, j] vanishes for k < j
-      rcd = gpk_launch_gemm(s, g);
-      if (rcd) return rcd;
-      rcd = gpk_row_sumsq(stream, Kfu_d, rows, m, l.ld, 1.0, 0.0, s0_d);
-      if (rcd) return rcd;
-      rcd = gpk_row_stats(stream, A2, rows, m, l.ld, q_mu, q_sqrt, P, 1.0, 0.0, nullptr, fmean_d, ssq_d);
-      if (rcd) return rcd;
-    }
-    int ca = 0;
-    rcd = gpk_launch_varexp_stage1(s, Yb, ldyb, fmean_d, rows, P, s0_d, 0, ssq_d, &variance, 0, noise_variance, mean_const, nullptr,
-                                   pa, &ca, noise_rows);
-    if (rcd) return rcd;
-    const double* q0[1] = {pa};
-    const double one_d = 1.0;
-    rcd = gpk_launch_final(s, 1, q0, &ca, &one_d, 0.0, out);
-    if (rcd) return rcd;
-    // KL = 0.5 ( |a|^2 + sum_i [(Kuu^-1)_ii sum_p w_ip^2 - sum_p log w_ip^2] - M P ) + P sum log diag(Lm)
-    int cm_ = 0, ct = 0;
-    rcd = gpk_launch_sumsq_stage1(s, arow, P, m, l.ld, 0, pb, &cm_);
-    if (rcd) return rcd;
-    rcd = gpk_launch_kl_unwhite_diag_stage1(s, LinvT, l.ld, m, q_sqrt, P, pc, &ct);
-    if (rcd) return rcd;
-    double* ldl = pc + GPK_REDUCE_MAXPART;
-    rcd = gpk_sum_log_diag(stream, T, m, l.ld, 1, 0, ldl);
-    if (rcd) return rcd;
-    const double* kp[3] = {pb, pc, ldl};
-    const int kc[3] = {cm_, ct, 1};
-    const double ks[3] = {0.5, 0.5, (double)P};
-    return gpk_launch_final(s, 3, kp, kc, ks, -0.5 * (double)m * (double)P, out + 1);
-  }
-  if (!whiten) {
-    // ---- whiten = 0 (kullback_leiblers.py:98-165 with K = Kuu, conditionals/util.py:128-167 with white = False) on ONE
-    // trapezoid [Kuu + jitter I ; Kfu ; q_mu^T ; tril(q_sqrt_p)^T].  The reference factors Kuu twice (once for the KL, once for
-    // the conditional) and solves the minibatch columns twice (Lm^-1, then Lm^-T).  Here the extra rows come back as
-    //     A^T = Kfu Lm^-T,   a^T = (Lm^-1 q_mu)^T,   G_p^T = (Lm^-1 Lq_p)^T   (G_p lower triangular again)
-    // which are the Mahalanobis / trace terms of the KL AND the whitened parameters of the same q(u): fmean = A^T a,
-    // sum_j (Lq^T Lm^-T A)_j^2 = sum_j (G^T A)_j^2 -- the projection kernel of the whitened path with G^T in place of Lq^T,
-    // no second triangular solve of the minibatch rows.
-    double* invd_u = (double*)(w + l.off_invd);
-    double* s0_u = (double*)(w + l.off_s0);
-    double* fmean_u = (double*)(w + l.off_fmean);
-    double* ssq_u = (double*)(w + l.off_ssq);
-    double* pa = (double*)(w + l.off_part0);
-    double* pb = (double*)(w + l.off_part1);
-    double* pc = (double*)(w + l.off_part2);          // [MAXPART] trace partials, then [P] log det q, then [1] log det Lm
-    double* V = (double*)(w + l.off_V);
-    double* Kfu_u = T + (long)m * l.ld;
-    double* arow = Kfu_u + (long)rows * l.ld;          // [P, m]
-    double* GT = arow + (long)P * l.ld;                // [P][m][ld]
-    int rcu = 0;
-    const std::function<int(hipStream_t)> kuu_u = [&](hipStream_t ps) -> int {
-      return gpk_kernel_matrix((void*)ps, family, Z, m, ldz, nullptr, 0, 0, d, ls_host, ard, variance, jitter, 1, T, l.ld);
-    };
-    const std::function<int(hipStream_t)> pro = [&](hipStream_t xs) -> int {
-      int r = gpk_kernel_matrix((void*)xs, family, Xb, rows, ldxb, Z, m, ldz, d, ls_host, ard, variance, 0.0, 0, Kfu_u, l.ld);
-      if (r) return r;
-      r = gpk_transpose((void*)xs, q_mu, m, P, P, arow, l.ld, 0, 1, 0, 0);
-      if (r) return r;
-      return gpk_transpose((void*)xs, q_sqrt, m, m, m, GT, l.ld, 1, P, (long)m * m, (long)m * l.ld);
-    };
-    // (P = 1: the m rows of tril(q_sqrt)^T are the LAST rows of the trapezoid and upper triangular -- row j stays zero left of
-    //  column j until its column group is reached, so the row solve skips them there: 3/8 of their work, round 5)
-    PotrfHooks hku;
-    hku.x_prologue = &pro;
-    hku.p_prologue = &kuu_u;
-    rcu = potrf_core(s, T, m, rows + P + P * m, l.ld, 1, 0, invd_u, 0, info, hku, P == 1 ? m : 0, true);
-    if (rcu) return rcu;
-    rcu = gpk_transpose(stream, arow, P, m, l.ld, V, P, 0, 1, 0, 0);           // a = Lm^-1 q_mu as [m, P]
-    if (rcu) return rcu;
-    rcu = gpk_row_stats(stream, Kfu_u, rows, m, l.ld, V, nullptr, P, 1.0, 0.0, s0_u, fmean_u, nullptr);
-    if (rcu) return rcu;
-    rcu = gpk_project(stream, Kfu_u, rows, m, l.ld, GT, l.ld, P, ssq_u, w + l.off_proj, gpk_project_workspace_bytes(rows, m, P));
-    if (rcu) return rcu;
-    int ca = 0;
-    rcu = gpk_launch_varexp_stage1(s, Yb, ldyb, fmean_u, rows, P, s0_u, 0, ssq_u, &variance, 0, noise_variance, mean_const, nullptr,
-                                   pa, &ca, noise_rows);
-    if (rcu) return rcu;
-    const double* q0[1] = {pa};
-    const double one_u = 1.0;
-    rcu = gpk_launch_final(s, 1, q0, &ca, &one_u, 0.0, out);
-    if (rcu) return rcu;
-    // KL = 0.5 |a|^2 + 0.5 sum_p |G_p|_F^2 - 0.5 M P - 0.5 sum log diag(Lq)^2 + P sum log diag(Lm)
-    int cm_ = 0, ct = 0;
-    rcu = gpk_launch_sumsq_stage1(s, arow, P, m, l.ld, 0, pb, &cm_);
-    if (rcu) return rcu;
-    rcu = gpk_launch_sumsq_stage1(s, GT, P * m, m, l.ld, 0, pc, &ct);
-    if (rcu) return rcu;
-    double* ldq = pc + GPK_REDUCE_MAXPART;
-    double* ldl = ldq + P;
-    rcu = gpk_launch_sum_log_diag_sq(s, q_sqrt, m, m, P, (long)m * m, ldq);
-    if (rcu) return rcu;
-    rcu = gpk_sum_log_diag(stream, T, m, l.ld, 1, 0, ldl);
-    if (rcu) return rcu;
-    const double* kp[4] = {pb, pc, ldq, ldl};
-    const int kc[4] = {cm_, ct, P, 1};
-    const double ks[4] = {0.5, 0.5, -0.5, (double)P};
-    return gpk_launch_final(s, 4, kp, kc, ks, -0.5 * (double)m * (double)P, out + 1);
-  }
-  double* invd = (double*)(w + l.off_invd);
-  double* LqT = (double*)(w + l.off_LqT) + (q_diag ? 0 : (long)P * l.ld);   // (behind the P rows the un-whitened form keeps there)
-  double* s0 = (double*)(w + l.off_s0);
-  double* fmean = (double*)(w + l.off_fmean);
-  double* ssq = (double*)(w + l.off_ssq);
-  double* part0 = (double*)(w + l.off_part0);
-  double* part1 = (double*)(w + l.off_part1);
-  double* Kfu = T + (long)m * l.ld;  // extra rows of the trapezoid: Kfu in, A^T = Kfu Lm^-T out (in place)
-  int rc;
-  // Kuf^T = k(Xb, Z) as the extra rows (posteriors.py:836, covariances/kufs.py:31-34).  Only the bulk stream of the
-  // factorisation consumes it, so it is built THERE (ordered after everything already queued on the caller's stream)
-  // and the panel chain starts right after the much smaller Kuu build.  Work that depends on neither factorisation
-  // nor minibatch solve -- tril(q_sqrt)^T for the projection and the whole KL term -- goes to that stream too, which
-  // idles until the first 512 columns of Lm exist; gpk_potrf joins it.
-  const bool side = m > GPK_NB && m < 4096 && rows > 256;
-  // Kuu + jitter I (posteriors.py:835, covariances/kuus.py:29-34), lower tiles only: the chain's first leaf waits for
-  // nothing else, so the factorisation enqueues it on its panel stream, directly in front of that leaf
-  const std::function<int(hipStream_t)> kuu_build = [&](hipStream_t ps) -> int {
-    return gpk_kernel_matrix((void*)ps, family, Z, m, ldz, nullptr, 0, 0, d, ls_host, ard, variance, jitter, 1, T, l.ld);
-  };
-  int c1 = 0;
-  // everything else that precedes the minibatch solve, as one closure: enqueued by the factorisation on its bulk stream
-  // (side) or here on the caller's stream
-  const std::function<int(hipStream_t)> prologue = [&](hipStream_t xs) -> int {
-    return gpk_kernel_matrix((void*)xs, family, Xb, rows, ldxb, Z, m, ldz, d, ls_host, ard, variance, 0.0, 0, Kfu, l.ld);
-  };
-  // tril(q_sqrt)^T for the projection and the whole KL term depend on neither the factorisation nor the minibatch solve
-  const std::function<int(hipStream_t)> late = [&](hipStream_t xs) -> int {
-    int r = 0;
-    if (!q_diag) {
-      r = gpk_transpose((void*)xs, q_sqrt, m, m, m, LqT, l.ld, 1, P, (long)m * m, (long)m * l.ld);
-      if (r) return r;
-    }
-    r = gpk_launch_kl_white_stage1(xs, q_mu, q_sqrt, m, P, q_diag, part1, &c1);
-    if (r) return r;
-    const double* p1s[1] = {part1};
-    const double halfs = 0.5;
-    return gpk_launch_final(xs, 1, p1s, &c1, &halfs, -0.5 * (double)m * (double)P, out + 1);
-  };
-  // Lm = chol(Kuu);  A^T = Kfu Lm^-T   (conditionals/util.py:67,125)
-  PotrfHooks hk;
-  hk.x_prologue = &prologue;
-  hk.p_prologue = &kuu_build;
-  hk.late_work = side ? &late : nullptr;
-  // s0 = sum_k A^2 (util.py:133), fmean = A^T q_mu (util.py:144), q_diag: ssq = sum (A q_sqrt)^2 (:149)
-  const std::function<int(hipStream_t)> stats = [&](hipStream_t xs) -> int {
-    return gpk_row_stats((void*)xs, Kfu, rows, m, l.ld, q_mu, q_diag ? q_sqrt : nullptr, P, 1.0, 0.0, s0, fmean, q_diag ? ssq : nullptr);
-  };
-  rc = potrf_core(s, T, m, rows, l.ld, 1, 0, invd, 0, info, hk);
-  if (rc) return rc;
-  rc = stats(s);
-  if (rc) return rc;
-  if (!q_diag) {
-    // L = band_part(q_sqrt,-1,0); LTA = L^T A; ssq = sum LTA^2   (util.py:151-164)
-    if (!side) {
-      rc = gpk_transpose(stream, q_sqrt, m, m, m, LqT, l.ld, 1, P, (long)m * m, (long)m * l.ld);
-      if (rc) return rc;
-    }
-    rc = project_parts(s, Kfu, rows, m, l.ld, 0, LqT, l.ld, P, w + l.off_proj, gpk_project_workspace_bytes(rows, m, P));
-    if (rc) return rc;
-    if (rows > 0) {
-      rc = gpk_launch_sum_parts(s, (const double*)(w + l.off_proj), 2 * gpk_gemm_tiles_n(m), rows, (long)2 * gpk_gemm_tiles_n(m) * rows, P, ssq);
-      if (rc) return rc;
-    }
-  }
-  // sum_b var_exp_b  (likelihoods/scalar_continuous.py:139-148, svgp.py:174,181)
-  int c0 = 0;
-  rc = gpk_launch_varexp_stage1(s, Yb, ldyb, fmean, rows, P, s0, 0, ssq, &variance, 0, noise_variance,
-                                mean_const, nullptr, part0, &c0, noise_rows);
-  if (rc) return rc;
-  const double* p0[1] = {part0};
-  const double one = 1.0;
-  rc = gpk_launch_final(s, 1, p0, &c0, &one, 0.0, out);
-  if (rc) return rc;
-  if (side) return 0;
-  // KL[q || N(0, I)]  (kullback_leiblers.py:45-46, 98-165)
-  rc = gpk_launch_kl_white_stage1(s, q_mu, q_sqrt, m, P, q_diag, part1, &c1);
-  if (rc) return rc;
-  const double* p1[1] = {part1};
-  const double half = 0.5;
-  return gpk_launch_final(s, 1, p1, &c1, &half, -0.5 * (double)m * (double)P, out + 1);
-}
-
-// ---- fused driver: one shard of SVGP.elbo with SEPARATE kernels per latent (SeparateIndependent, whitened, full q_sqrt) --------
-namespace {
-struct ElboSepLayout {
-  long ld, strideT;
-  size_t off_T, off_invd, off_LqT, off_s0, off_fmean, off_ssq, off_proj, off_part0, off_part1, total;
-};
-ElboSepLayout elbo_sep_layout(int m, int rows, int P) {
-  ElboSepLayout l{};
-  l.ld = (long)gpk_align_up((size_t)m, 8);
-  l.strideT = (long)(m + rows) * l.ld;
-  size_t o = 0;
-  l.off_T = o; o += gpk_align_up((size_t)P * l.strideT * sizeof(double), 256);
-  l.off_invd = o; o += gpk_align_up(gpk_invd_elems(m, P) * sizeof(double), 256);
-  l.off_LqT = o; o += gpk_align_up((size_t)P * m * l.ld * sizeof(double), 256);
-  l.off_s0 = o; o += gpk_align_up((size_t)rows * P * sizeof(double), 256);
-  l.off_fmean = o; o += gpk_align_up((size_t)rows * P * sizeof(double), 256);
-  l.off_ssq = o; o += gpk_align_up((size_t)rows * P * sizeof(double), 256);
-  l.off_proj = o; o += gpk_align_up(gpk_project_workspace_bytes(rows, m, P), 256);
-  l.off_part0 = o; o += gpk_align_up((size_t)GPK_REDUCE_MAXPART * sizeof(double), 256);
-  l.off_part1 = o; o += gpk_align_up((size_t)GPK_REDUCE_MAXPART * sizeof(double), 256);
-  l.total = o;
-  return l;
-}
-}  // namespace
-
-extern "C" size_t gpk_svgp_elbo_sep_workspace_bytes(int m, int rows, int d, int P) {
-  (void)d;
-  return elbo_sep_layout(m, rows, P).total;
-}
-
-// The P problems of conditionals/util.py:566-629 (tf.map_fn over the latents) share nothing but the minibatch: P covariance
-// pairs built straight into ONE batched trapezoid [P][(m + rows) x ld], one batched factorisation with the minibatch rows riding
-// along (gpk_potrf, batch = P), one batched row-statistics launch, one batched projection, one reduction.  Composed from the
-// Python mirror the same step issues ~50 launches with host gaps between them (profiles/r04_c5sep_timeline_composed.txt).
-// (Measured and not kept: the extra rows solved out of place against EXPLICIT 512-column group inverses -- nine short launches
-// for the inverses + one triangular-K GEMM per group instead of the fused in-group kernel: 2.15 / 2.16 against 2.14 ms.)
-extern "C" int gpk_svgp_elbo_shard_sep(void* stream, const int* family_host, const double* Z, int m, long ldz, long strideZ,
-                                       const double* Xb, const double* Yb, int rows, long ldxb, long ldyb, int d, int P,
-                                       const double* ls_host, int ard, const double* variance_host, double noise_variance,
-                                       const double* noise_rows, double jitter, double mean_const, const double* q_mu,
-                                       const double* q_sqrt, double* out,
-                                       int* info, void* ws, size_t ws_bytes) {
-  if (!family_host || !Z || (rows > 0 && (!Xb || !Yb)) || !q_mu || !q_sqrt || !ls_host || !variance_host || !out || !info || m <= 0 || rows < 0 ||
-      P <= 0 || P > 16 || d <= 0 || strideZ < 0)
-    return GPK_E_ARG;
-  const ElboSepLayout l = elbo_sep_layout(m, rows, P);
-  if (!ws || ws_bytes < l.total) return GPK_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)ws;
-  double* T = (double*)(w + l.off_T);
-  double* invd = (double*)(w + l.off_invd);
-  double* LqT = (double*)(w + l.off_LqT);
-  double* s0 = (double*)(w + l.off_s0);
-  double* fmean = (double*)(w + l.off_fmean);
-  double* ssq = (double*)(w + l.off_ssq);
-  double* part0 = (double*)(w + l.off_part0);
-  double* part1 = (double*)(w + l.off_part1);
-  const int nls = ard ? d : 1;
-  int rc;
-  // Kuu_p + jitter I (lower tiles): the chain's first (batched) leaf waits for nothing else -- enqueued on the panel stream
-  const std::function<int(hipStream_t)> kuu_build = [&](hipStream_t ps) -> int {
-    for (int p = 0; p < P; ++p) {
-      const int r = gpk_kernel_matrix((void*)ps, family_host[p], Z + (long)p * strideZ, m, ldz, nullptr, 0, 0, d, ls_host + (long)p * nls,
-                                      ard, variance_host[p], jitter, 1, T + (long)p * l.strideT, l.ld);
-      if (r) return r;
-    }
-    return 0;
-  };
-  const bool side = m > GPK_NB && m < 4096 && rows > 256;
-  int c1 = 0;
-  auto kl_and_transpose = [&](hipStream_t xs) -> int {
-    int r = gpk_transpose((void*)xs, q_sqrt, m, m, m, LqT, l.ld, 1, P, (long)m * m, (long)m * l.ld);
-    if (r) return r;
-    r = gpk_launch_kl_white_stage1(xs, q_mu, q_sqrt, m, P, 0, part1, &c1);
-    if (r) return r;
-    const double* p1s[1] = {part1};
-    const double halfs = 0.5;
-    return gpk_launch_final(xs, 1, p1s, &c1, &halfs, -0.5 * (double)m * (double)P, out + 1);
-  };
-  const std::function<int(hipStream_t)> prologue = [&](hipStream_t xs) -> int {
-    for (int p = 0; p < P; ++p) {
-      const int r = gpk_kernel_matrix((void*)xs, family_host[p], Xb, rows, ldxb, Z + (long)p * strideZ, m, ldz, d,
-                                      ls_host + (long)p * nls, ard, variance_host[p], 0.0, 0, T + (long)p * l.strideT + (long)m * l.ld,
-                                      l.ld);
-      if (r) return r;
-    }
-    return 0;
-  };
-  const std::function<int(hipStream_t)> late = [&](hipStream_t xs) -> int { return kl_and_transpose(xs); };
-  PotrfHooks hk;
-  hk.x_prologue = &prologue;
-  hk.p_prologue = &kuu_build;
-  hk.late_work = side ? &late : nullptr;
-  rc = potrf_core(s, T, m, rows, l.ld, P, l.strideT, invd, 0, info, hk);
-  if (rc) return rc;
-  if (!side) {
-    rc = kl_and_transpose(s);
-    if (rc) return rc;
-  }
-  const double* At = T + (long)m * l.ld;
-  rc = gpk_launch_row_stats_sep(s, At, l.strideT, rows, m, l.ld, q_mu, P, s0, fmean);
-  if (rc) return rc;
-  rc = gpk_project_batched(stream, At, rows, m, l.ld, l.strideT, LqT, l.ld, P, ssq, w + l.off_proj,
-                           gpk_project_workspace_bytes(rows, m, P));
-  if (rc) return rc;
-  int c0 = 0;
-  rc = gpk_launch_varexp_stage1(s, Yb, ldyb, fmean, rows, P, s0, 1, ssq, variance_host, 1, noise_variance, mean_const, nullptr, part0,
-                                &c0, noise_rows);
-  if (rc) return rc;
-  const double* p0[1] = {part0};
-  const double one = 1.0;
-  return gpk_launch_final(s, 1, p0, &c0, &one, 0.0, out);
 }

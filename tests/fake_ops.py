@@ -349,7 +349,7 @@ def project(At, LqT):
 
 
 def gpr_lml(X, Y, *, variance, lengthscales, noise_variance, mean_const=0.0, family="SquaredExponential", ws=None):
-    """The fused driver, emulated by the same chain of primitives it runs (potrf.hip: gpk_gpr_lml)."""
+    """The fused driver, emulated by the same chain of primitives it runs (drivers.hip: gpk_gpr_lml)."""
     n, P = Y.shape
     assert n >= 1 and P >= 1, (n, P)    # gpk_gpr_lml: GPK_E_ARG
     T = torch.empty((n + P, n), dtype=torch.float64)
@@ -411,7 +411,7 @@ def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_va
     assert 1 <= P <= 16 and M >= 1, (P, M)    # gpk_svgp_elbo_shard: GPK_E_ARG
     kw = dict(variance=variance, lengthscales=lengthscales, family=family)
     if not whiten and q_sqrt.dim() == 2:
-        # un-whitened, diagonal q_sqrt: [Kuu ; Kfu ; q_mu^T ; I] -> A^T, (Lm^-1 q_mu)^T, Lm^-T (potrf.hip, round 5)
+        # un-whitened, diagonal q_sqrt: [Kuu ; Kfu ; q_mu^T ; I] -> A^T, (Lm^-1 q_mu)^T, Lm^-T (drivers.hip, round 5)
         T = torch.empty((M + rows + P + M, M), dtype=torch.float64)
         kernel_matrix(Z, None, diag_add=jitter, lower_only=True, out=T[:M], **kw)
         if rows:

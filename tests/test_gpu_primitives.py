@@ -302,7 +302,7 @@ def test_fused_gpr_lml(gpu, n, d, P):
     np.testing.assert_allclose(out.cpu().numpy()[0], ref, rtol=1e-10)
     if n >= 4096:
         # large n: only the first outer panel's columns are built before the factorisation starts, the rest beside its chain
-        # on the bulk stream (potrf.hip, gpk_gpr_lml) -- repeated calls and per-row noise through the same split
+        # on the bulk stream (drivers.hip, gpk_gpr_lml) -- repeated calls and per-row noise through the same split
         out2, _ = ops.gpr_lml(_t(X), _t(Y), mean_const=0.05, **kw)
         assert float(out2.cpu()[0]) == float(out.cpu()[0])
         nv = rng.uniform(0.05, 0.3, size=n)
