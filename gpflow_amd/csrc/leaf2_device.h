@@ -143,7 +143,11 @@ __device__ __forceinline__ void panel_pivot(d4& d, int c, int g, int lane, const
   pub[P * 128 + lane] = yop;
   word_set(sync + W_FLAG, seq0 + 2 * P + 1);
   const d4 zero = {0.0, 0.0, 0.0, 0.0};
-  const d4 t = mfma4(yop, d[P], zero);
+  // Inside the 4 x 4 diagonal block the operand also holds the entries BELOW the diagonal (row 4P + g > column c): they belong to
+  // later rows and meet only the structural zeros of yop, but 0 * NaN is NaN -- a NaN in row i would reach the rows of its panel
+  // above it and the status would name the panel's first column.  Zeroed here, row n of L depends on rows <= n alone.
+  const double bop = (c >= 4 * P && c - g < 4 * P) ? 0.0 : d[P];
+  const d4 t = mfma4(yop, bop, zero);
   const double lp = (c >= 4 * P + g) ? t[0] : 0.0;   // rows above the panel and the upper part of the 4 x 4 block
   if constexpr (P < 3) {
     pub[P * 128 + 64 + lane] = lp;

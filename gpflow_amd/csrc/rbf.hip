@@ -36,7 +36,7 @@ constexpr int T = 64;
 template <int family>
 __device__ __forceinline__ double kern_eval(double r2, double variance) {
   if (family == GPK_KERN_SE) return variance * exp(-0.5 * r2);
-  const double r = sqrt(fmax(r2, 1e-36));
+  const double r = sqrt(r2 < 1e-36 ? 1e-36 : r2);   // (not fmax: a NaN r2 has to come out as NaN, as tf.maximum gives)
   if (family == GPK_KERN_MATERN12) return variance * exp(-r);
   if (family == GPK_KERN_MATERN32) {
     const double sqrt3 = 1.7320508075688772;
@@ -52,7 +52,7 @@ __device__ __forceinline__ double kern_eval(double r2, double variance) {
 template <int family>
 __device__ __forceinline__ double kern_dr2(double r2, double variance) {
   if (family == GPK_KERN_SE) return variance * exp(-0.5 * r2);
-  if (!(r2 > 1e-36)) return 0.0;
+  if (r2 <= 1e-36) return 0.0;   // (a NaN r2 is not clamped: it reaches sqrt and comes out as NaN)
   const double r = sqrt(r2);
   if (family == GPK_KERN_MATERN12) return variance * exp(-r) / r;
   if (family == GPK_KERN_MATERN32) {

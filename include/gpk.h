@@ -16,7 +16,7 @@
  *     sum over no terms for a reduction (e.g. gpk_gaussian_varexp_sum with rows = 0 writes 0, gpk_svgp_elbo_shard writes
  *     [0, KL]), and beta C for gpk_gemm_nt with k = 0 (exact zeros for beta = 0; C is not read then);
  *   - return value: 0 ok, <0 bad argument (GPK_E_*), >0 HIP runtime error code (hipError_t);
- *   - numerical failure (non-positive pivot) is reported LAPACK-style through a device int
+ *   - numerical failure (non-positive or NaN pivot) is reported LAPACK-style through a device int
  *     `info` (0 = ok, j+1 = first bad pivot column) that the caller reads when it next syncs
  *     (TF raises InvalidArgumentError "Cholesky decomposition was not successful" at the same spot);
  *     INT_MAX = an internal stream hand-off of the factorisation timed out (0.5 s; never observed -- the bounded wait exists so

@@ -77,7 +77,7 @@ def _dr2(X1, X2, variance, lengthscales, family):
     r2 = -2.0 * a @ b.T + (a * a).sum(1)[:, None] + (b * b).sum(1)[None, :]
     if family == "SquaredExponential":
         return variance * np.exp(-0.5 * r2)
-    ok = r2 > 1e-36
+    ok = ~(r2 <= 1e-36)                          # (a NaN r2 is not clamped: it comes out as NaN, like tf.maximum's gradient)
     r = np.sqrt(np.where(ok, r2, 1.0))
     if family == "Matern12":
         f = variance * np.exp(-r) / r
@@ -127,17 +127,20 @@ def invd_alloc(n, batch=1):
 
 
 def _chol_info(K):
-    """(L, info): info = j + 1 of the first non-positive pivot (LAPACK convention), L garbage from there on."""
-    try:
-        return np.linalg.cholesky(K), 0
-    except np.linalg.LinAlgError:
-        n = K.shape[0]
-        for j in range(1, n + 1):
-            try:
-                np.linalg.cholesky(K[:j, :j])
-            except np.linalg.LinAlgError:
-                return np.full_like(K, np.nan), j
-        return np.full_like(K, np.nan), n
+    """(L, info): info = j + 1 of the first pivot that is not > 0 -- non-positive or NaN (include/gpk.h, "info") -- tested
+    explicitly on every pivot (LAPACK does not promise to raise on a NaN one).  Row by row, so that a row of L is a function
+    of the rows of K up to it and of nothing else: rows < info - 1 are final and bitwise what a successful factorisation of
+    the same leading rows gives; the rest is NaN."""
+    n = K.shape[0]
+    L = np.full_like(K, np.nan)
+    with np.errstate(all="ignore"):
+        for j in range(n):
+            row = sla.solve_triangular(L[:j, :j], K[j, :j], lower=True, check_finite=False) if j else K[j, :0]
+            piv = K[j, j] - row @ row
+            if not piv > 0:
+                return L, j + 1
+            L[j, :j], L[j, j], L[j, j + 1:] = row, np.sqrt(piv), 0.0
+    return L, 0
 
 
 def potrf_(T, n, *, zero_upper=False, invd=None, identity_rows=False):
@@ -154,11 +157,13 @@ def potrf_(T, n, *, zero_upper=False, invd=None, identity_rows=False):
     K = np.tril(_np(T[:n]))
     K = K + np.tril(K, -1).T          # only the lower triangle is read
     L, bad = _chol_info(K)
-    if bad:
+    if bad:   # rows before the bad pivot are final (they depend on nothing after them); everything else is left as it was
+        up = np.triu(_np(T[:bad - 1]), 1)
+        T[:bad - 1] = torch.from_numpy(L[:bad - 1] + (0.0 if zero_upper else up))
         return _invd(n, 1, +1.0), torch.tensor([bad], dtype=torch.int32)
     E = _np(T[n:])
-    S = sla.solve_triangular(L, E.T, lower=True).T if E.shape[0] else E
-    up = _np(T[:n]) * np.triu(np.ones((n, n)), 1)
+    S = sla.solve_triangular(L, E.T, lower=True, check_finite=False).T if E.shape[0] else E
+    up = np.triu(_np(T[:n]), 1)
     T[:n] = torch.from_numpy(L + (0.0 if zero_upper else up))
     T[n:] = torch.from_numpy(S)
     return _invd(n, 1, +1.0), torch.zeros(1, dtype=torch.int32)
@@ -186,12 +191,12 @@ def trsm_(B, L, invd, *, trans=0):
     if trans == 0:
         assert float(invd.reshape(-1)[0]) == 1.0, "trans=0 needs (L, invd)"
         Ll = np.tril(_np(L))
-        B.copy_(torch.from_numpy(sla.solve_triangular(Ll, _np(B).T, lower=True).T))
+        B.copy_(torch.from_numpy(sla.solve_triangular(Ll, _np(B).T, lower=True, check_finite=False).T))
     else:
         assert float(invd.reshape(-1)[0]) == -1.0, "trans=1 needs (LT, invdT) from transpose_factor"
         Ll = np.triu(_np(L)).T      # the argument is L^T (upper); only that triangle is read
         # B L^-1 = (L^-T B^T)^T
-        B.copy_(torch.from_numpy(sla.solve_triangular(Ll.T, _np(B).T, lower=False).T))
+        B.copy_(torch.from_numpy(sla.solve_triangular(Ll.T, _np(B).T, lower=False, check_finite=False).T))
     return B
 
 
@@ -385,8 +390,9 @@ def svgp_elbo_shard_sep(Z, Xb, Yb, q_mu, q_sqrt, *, variances, lengthscales, fam
         if rows:
             kernel_matrix(Xb, Zp, out=T[p, M:], **kw)
     _, inf = potrf_(T, M)
-    res = torch.zeros(2, dtype=torch.float64)
+    res = torch.full((2,), float("nan"), dtype=torch.float64)   # undefined after a failed factorisation: poisoned
     if not bool((inf != 0).any()):
+        res.zero_()
         s0 = torch.stack([row_stats(T[p, M:].contiguous(), V=q_mu[:, p:p + 1].contiguous())[0] for p in range(P)])
         fmean = torch.stack([row_stats(T[p, M:].contiguous(), V=q_mu[:, p:p + 1].contiguous())[1][:, 0] for p in range(P)], dim=1)
         ssq = project(T[:, M:], transpose(q_sqrt, mode=1))
@@ -418,8 +424,9 @@ def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_va
             kernel_matrix(Xb, Z, out=T[M:M + rows], **kw)
         T[M + rows:M + rows + P] = q_mu.t()
         _, inf = potrf_(T, M, identity_rows=True)
-        res = torch.zeros(2, dtype=torch.float64)
+        res = torch.full((2,), float("nan"), dtype=torch.float64)   # undefined after a failed factorisation: poisoned
         if int(inf[0]) == 0:
+            res.zero_()
             At = T[M:M + rows].contiguous()
             LinvT = T[M + rows + P:].contiguous()
             A2 = gemm_nt(At, LinvT, b_tri=1) if rows else At
@@ -444,8 +451,9 @@ def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_va
         T[M + rows:M + rows + P] = q_mu.t()
         T[M + rows + P:] = transpose(q_sqrt, mode=1).reshape(P * M, M)
         _, inf = potrf_(T, M)
-        res = torch.zeros(2, dtype=torch.float64)
+        res = torch.full((2,), float("nan"), dtype=torch.float64)   # undefined after a failed factorisation: poisoned
         if int(inf[0]) == 0:
+            res.zero_()
             At = T[M:M + rows].contiguous()
             V = T[M + rows:M + rows + P].t().contiguous()
             GT = T[M + rows + P:].reshape(P, M, M).contiguous()
@@ -467,8 +475,9 @@ def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_va
     if rows:
         kernel_matrix(Xb, Z, out=T[M:], **kw)
     _, inf = potrf_(T, M)
-    res = torch.zeros(2, dtype=torch.float64)
+    res = torch.full((2,), float("nan"), dtype=torch.float64)   # undefined after a failed factorisation: poisoned
     if int(inf[0]) == 0:
+        res.zero_()
         At = T[M:]
         if q_sqrt.dim() == 2:
             s0, fmean, wsq = row_stats(At, V=q_mu, W=q_sqrt)
