@@ -142,6 +142,8 @@ struct ElboArgs {
   double noise_variance; const double* noise_rows;
   double jitter, mean_const;
   double* out; int* info;
+  int lik = 0;                         // 0: Gaussian (noise_variance, noise_rows); else a GPK_LIK_* code with lik_params (host)
+  const double* lik_params = nullptr;
 };
 // the workspace of a shard.  T is the trapezoid [Kuu + jitter I ; Kfu ; ...] (separate kernels: P of them, strideT apart)
 struct ElboWs {
@@ -235,11 +237,16 @@ int transpose_q_sqrt(hipStream_t s, const ElboArgs& a, const ElboWs& w) {
   return gpk_transpose((void*)s, a.q_sqrt, a.m, a.m, a.m, w.LqT, w.ld, 1, a.P, (long)a.m * a.m, (long)a.m * w.ld);
 }
 
-// sum_b var_exp_b -> out[0]  (likelihoods/scalar_continuous.py:139-148, svgp.py:174,181); knn_host: the kernel variance(s)
+// sum_b var_exp_b -> out[0]  (likelihoods/scalar_continuous.py:139-148, svgp.py:174,181); knn_host: the kernel variance(s).
+// The only stage of a shard that knows the likelihood: Gaussian in closed form, the others by Gauss-Hermite quadrature.
 int varexp_to_out(hipStream_t s, const ElboArgs& a, const ElboWs& w, const double* knn_host, int per_latent) {
   int count = 0;
-  const int rc = gpk_launch_varexp_stage1(s, a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, per_latent, w.ssq, knn_host, per_latent,
-                                          a.noise_variance, a.mean_const, nullptr, w.part0, &count, a.noise_rows);
+  const int rc = a.lik
+      ? gpk_launch_likelihood_varexp_stage1(s, a.lik, a.lik_params, a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, per_latent, w.ssq,
+                                            knn_host, per_latent, a.mean_const, nullptr, nullptr, nullptr, nullptr, w.part0, nullptr,
+                                            &count)
+      : gpk_launch_varexp_stage1(s, a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, per_latent, w.ssq, knn_host, per_latent,
+                                 a.noise_variance, a.mean_const, nullptr, w.part0, &count, a.noise_rows);
   if (rc) return rc;
   return final_one(s, w.part0, count, 1.0, 0.0, a.out);
 }
@@ -380,6 +387,24 @@ extern "C" size_t gpk_svgp_elbo_workspace_bytes(int m, int rows, int d, int P, i
   return elbo_layout(nullptr, m, rows, P, q_diag, whiten).total;
 }
 
+namespace {
+// the shard behind both entry points: argument checks, workspace, then the form (whiten, q_diag) picks its schedule
+int elbo_shard(void* stream, const ElboArgs& a, int whiten, void* ws, size_t ws_bytes) {
+  if (!a.Z || (a.rows > 0 && (!a.Xb || !a.Yb)) || !a.q_mu || !a.q_sqrt || !a.out || !a.info || a.m <= 0 || a.rows < 0 || a.P <= 0 ||
+      a.P > 16)
+    return GPK_E_ARG;
+  if (a.lik) {
+    const int rc = gpk_likelihood_check(a.lik, a.lik_params);
+    if (rc) return rc;
+  }
+  const ElboWs w = elbo_layout(ws, a.m, a.rows, a.P, a.q_diag, whiten);
+  if (!ws || ws_bytes < w.total) return GPK_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  if (whiten) return elbo_whitened(s, a, w);
+  return a.q_diag ? elbo_unwhitened_diag(s, a, w) : elbo_unwhitened_full(s, a, w);
+}
+}  // namespace
+
 extern "C" int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, int m, long ldz,
                                    const double* Xb, const double* Yb, int rows, long ldxb,
                                    long ldyb, int d, int P, const double* ls_host, int ard,
@@ -387,15 +412,21 @@ extern "C" int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, in
                                    double mean_const, const double* q_mu, const double* q_sqrt,
                                    int q_diag, int whiten, double* out, int* info, void* ws,
                                    size_t ws_bytes) {
-  if (!Z || (rows > 0 && (!Xb || !Yb)) || !q_mu || !q_sqrt || !out || !info || m <= 0 || rows < 0 || P <= 0 || P > 16)
-    return GPK_E_ARG;
-  const ElboWs w = elbo_layout(ws, m, rows, P, q_diag, whiten);
-  if (!ws || ws_bytes < w.total) return GPK_E_WORKSPACE;
   const ElboArgs a{{family, d, ls_host, ard, variance}, Z, m, ldz, Xb, Yb, rows, ldxb, ldyb, P, q_mu, q_sqrt, q_diag,
                    noise_variance, noise_rows, jitter, mean_const, out, info};
-  hipStream_t s = (hipStream_t)stream;
-  if (whiten) return elbo_whitened(s, a, w);
-  return q_diag ? elbo_unwhitened_diag(s, a, w) : elbo_unwhitened_full(s, a, w);
+  return elbo_shard(stream, a, whiten, ws, ws_bytes);
+}
+
+extern "C" int gpk_svgp_elbo_shard_lik(void* stream, int family, const double* Z, int m, long ldz, const double* Xb,
+                                       const double* Yb, int rows, long ldxb, long ldyb, int d, int P, const double* ls_host,
+                                       int ard, double variance, int lik, const double* lik_params_host, double jitter,
+                                       double mean_const, const double* q_mu, const double* q_sqrt, int q_diag, int whiten,
+                                       double* out, int* info, void* ws, size_t ws_bytes) {
+  if (!lik) return GPK_E_UNSUPPORTED;   // (0 is the Gaussian stage of gpk_svgp_elbo_shard, not a likelihood code)
+  ElboArgs a{{family, d, ls_host, ard, variance}, Z, m, ldz, Xb, Yb, rows, ldxb, ldyb, P, q_mu, q_sqrt, q_diag,
+             0.0, nullptr, jitter, mean_const, out, info};
+  a.lik = lik; a.lik_params = lik_params_host;
+  return elbo_shard(stream, a, whiten, ws, ws_bytes);
 }
 
 // ---- fused driver: one shard of SVGP.elbo with SEPARATE kernels per latent (SeparateIndependent, whitened, full q_sqrt) --------

@@ -173,6 +173,12 @@ int gpk_launch_varexp_stage1(hipStream_t s, const double* Y, long ldy, const dou
                              const double* knn_host, int knn_per_latent, double noise,
                              double mean_const, double* fvar_out, double* part, int* count,
                              const double* noise_rows = nullptr);   // per-row noise variances [rows] or nullptr (constant `noise`)
+// the quadrature stage of gpk_likelihood_varexp_sum (same operands); part1 (partials of sum dVE/dscale) may be null
+int gpk_likelihood_check(int lik, const double* params);   // 0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters)
+int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const double* Y, long ldy, const double* fmean,
+                                        int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
+                                        const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
+                                        double* rows_out, double* dmu_out, double* dvar_out, double* part, double* part1, int* count);
 int gpk_launch_kl_white_stage1(hipStream_t s, const double* q_mu, const double* q_sqrt, int m, int P,
                                int q_diag, double* part, int* count);
 int gpk_launch_kl_unwhite_diag_stage1(hipStream_t s, const double* LinvT, long ldl, int m, const double* W, int P, double* part,

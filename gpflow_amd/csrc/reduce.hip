@@ -274,6 +274,130 @@ __global__ __launch_bounds__(RB) void varexp_kernel(VarexpArgs a) {
   if (threadIdx.x == 0) a.part[blockIdx.x] = r;
 }
 
+// ---- non-Gaussian variational expectations, stage 1 (likelihoods/base.py: ScalarLikelihood through NDiagGHQuadrature,
+// quadrature/gauss_hermite.py; scalar_discrete.py Bernoulli / Poisson; scalar_continuous.py StudentT) -----------------------
+//   VE[b,p] = sum_h (w_h / sqrt(pi)) g(mu + sqrt(2 v) x_h),  g = log p(y | f),  with d/dmu and d/dv of that same sum.
+// numpy.polynomial.hermite.hermgauss(20), the reference's DEFAULT_NUM_GAUSS_HERMITE_POINTS (gpk_gauss_hermite returns this table)
+#define GPK_GH20_X                                                                                                          \
+  -5.387480890011233, -4.603682449550744, -3.944764040115625, -3.3478545673832163, -2.7888060584281305, -2.2549740020892757, \
+      -1.7385377121165861, -1.234076215395323, -0.7374737285453944, -0.24534070830090124, 0.24534070830090124,              \
+      0.7374737285453944, 1.234076215395323, 1.7385377121165861, 2.2549740020892757, 2.7888060584281305, 3.3478545673832163, \
+      3.944764040115625, 4.603682449550744, 5.387480890011233
+#define GPK_GH20_W                                                                                                          \
+  2.2293936455341447e-13, 4.3993409922731747e-10, 1.0860693707692782e-07, 7.80255647853206e-06, 0.00022833863601635365,     \
+      0.0032437733422378567, 0.024810520887463643, 0.1090172060200233, 0.28667550536283415, 0.4622436696006101,              \
+      0.4622436696006101, 0.28667550536283415, 0.1090172060200233, 0.024810520887463643, 0.0032437733422378567,              \
+      0.00022833863601635365, 7.80255647853206e-06, 1.0860693707692782e-07, 4.3993409922731747e-10, 2.2293936455341447e-13
+constexpr int GH_N = 20;
+__constant__ const double gh_x_dev[GH_N] = {GPK_GH20_X};
+__constant__ const double gh_w_dev[GH_N] = {GPK_GH20_W};
+const double gh_x_host[GH_N] = {GPK_GH20_X};
+const double gh_w_host[GH_N] = {GPK_GH20_W};
+
+struct LikVarexpArgs {
+  const double* Y; long ldy; const double* fmean; int rows, P;
+  const double* s0; int s0_per_latent; const double* ssq;
+  double knn[16]; int knn_per_latent;
+  double mean_const;
+  double par0, par1, c0;   // Poisson: binsize, -, log(binsize);  StudentT: scale, df, the f-independent part of log p
+  double *fvar_out, *rows_out, *dmu_out, *dvar_out;
+  double *part, *part1;    // stage-1 partials of sum VE and (part1 may be null) of sum dVE/dscale
+};
+
+// One element (b, p) is shared by LPE = 4 adjacent lanes, five nodes each (8192 x P elements with a serial 20-node loop of fp64
+// erfc + log + exp per thread would leave most of the chip idle); the four partial sums meet through two xor shuffles, so all
+// four lanes hold the same bits.  The closed-form Poisson branch has no nodes: one lane per element.  A wave pass covers
+// floor((64 / LPE) / P) WHOLE rows, so that the row sums of rows_out are a fixed-order shuffle loop inside one wave.
+// Non-finite inputs: NaN / Inf in fmean or fvar travel through the arithmetic; a non-finite label adds y - y = NaN to every output
+// of its element (the comparison y == 1 of the Bernoulli density would otherwise read a NaN label as class 0).
+template <int LIK>
+__global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
+  constexpr int LPE = (LIK == GPK_LIK_POISSON_EXP) ? 1 : 4;
+  constexpr int NPL = GH_N / 4;      // nodes per lane (quadrature branches)
+  constexpr int G = 64 / LPE;        // elements per wave pass
+  __shared__ double sh[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int g = lane / LPE, k = lane % LPE;
+  const int rpw = G / a.P;                        // whole rows per wave pass (P <= 16 <= G)
+  const int jr = g / a.P, p = g - jr * a.P;       // this group's row within the pass, its latent
+  const int row_lane0 = (jr * a.P * LPE) & 63;    // lane of the row's first element
+  const long npass = ((long)a.rows + rpw - 1) / rpw;
+  double acc = 0.0, acc1 = 0.0;
+  for (long u = (long)blockIdx.x * (RB / 64) + w; u < npass; u += (long)gridDim.x * (RB / 64)) {
+    const long b = u * rpw + jr;
+    const bool act = jr < rpw && b < a.rows;
+    double y = 0.0, mu = 0.0, fv = 1.0;           // (idle lanes of a pass run on harmless values and are masked below)
+    if (act) {
+      fv = a.knn[a.knn_per_latent ? p : 0];
+      if (a.s0) fv -= a.s0_per_latent ? a.s0[(long)p * a.rows + b] : a.s0[b];
+      if (a.ssq) fv += a.ssq[(long)p * a.rows + b];
+      mu = a.fmean[b * a.P + p] + a.mean_const;
+      y = a.Y[b * a.ldy + p];
+    }
+    const double ynan = y - y;
+    double ve, dmu, dvar, dsc = 0.0;
+    if (LIK == GPK_LIK_POISSON_EXP) {
+      // scalar_discrete.py: Poisson.variational_expectations with the exp link, closed form
+      const double e = exp(mu + 0.5 * fv) * a.par0;
+      ve = y * mu - e - lgamma(y + 1.0) + y * a.c0;
+      dmu = y - e;
+      dvar = -0.5 * e;
+    } else {
+      const double sd = sqrt(2.0 * fv);
+      const double sgn = (y == 1.0) ? 1.0 : -1.0;
+      double sv = 0.0, sm = 0.0, sx = 0.0, ss = 0.0;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) {
+        const double x = gh_x_dev[k * NPL + j];
+        const double wn = gh_w_dev[k * NPL + j] * 0.5641895835477563;   // w_h / sqrt(pi)
+        const double f = fma(sd, x, mu);
+        double gv, gp;
+        if (LIK == GPK_LIK_BERNOULLI_PROBIT) {
+          // log(y == 1 ? p : 1 - p), p = inv_probit(f) = 0.5 (1 + erf(f / sqrt 2)) (1 - 2e-3) + 1e-3;  1 - p = inv_probit(-f), taken
+          // through erfc so that the small side keeps its relative accuracy
+          const double q = 0.5 * erfc(-sgn * f * 0.7071067811865476) * (1.0 - 2e-3) + 1e-3;
+          gv = log(q);
+          gp = sgn * ((1.0 - 2e-3) * 0.3989422804014327) * exp(-0.5 * f * f) / q;
+        } else {
+          // logdensities.py student_t:  c0 - (df + 1) / 2 log(1 + ((y - f) / scale)^2 / df)
+          const double r = (y - f) / a.par0;
+          const double den = a.par1 + r * r;
+          gv = a.c0 - 0.5 * (a.par1 + 1.0) * log1p(r * r / a.par1);
+          gp = (a.par1 + 1.0) * r / (a.par0 * den);
+          ss += wn * (((a.par1 + 1.0) * r * r / den - 1.0) / a.par0);
+        }
+        sv += wn * gv;
+        sm += wn * gp;
+        sx += wn * gp * x;
+      }
+      sv += __shfl_xor(sv, 1); sm += __shfl_xor(sm, 1); sx += __shfl_xor(sx, 1); ss += __shfl_xor(ss, 1);
+      sv += __shfl_xor(sv, 2); sm += __shfl_xor(sm, 2); sx += __shfl_xor(sx, 2); ss += __shfl_xor(ss, 2);
+      ve = sv;
+      dmu = sm;
+      dvar = sx / sd;
+      dsc = ss;
+    }
+    ve += ynan; dmu += ynan; dvar += ynan;
+    double rs = 0.0;   // the row's P elements sit in adjacent groups of this wave: summed in the order p = 0, 1, ...
+    for (int q = 0; q < a.P; ++q) rs += __shfl(ve, (row_lane0 + q * LPE) & 63);
+    if (act && k == 0) {
+      const long e = b * a.P + p;
+      if (a.fvar_out) a.fvar_out[e] = fv;
+      if (a.dmu_out) a.dmu_out[e] = dmu;
+      if (a.dvar_out) a.dvar_out[e] = dvar;
+      if (a.rows_out && p == 0) a.rows_out[b] = rs;
+      acc += ve;
+      acc1 += dsc;
+    }
+  }
+  const double r0 = block_sum(acc, sh);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = r0;
+  if (a.part1) {   // (kernel argument: uniform)
+    const double r1 = block_sum(acc1, sh);
+    if (threadIdx.x == 0) a.part1[blockIdx.x] = r1;
+  }
+}
+
 // ---- whitened KL, stage 1: sum q_mu^2 - sum log diag^2 + sum tril^2 -----------------------------------
 __global__ __launch_bounds__(RB) void kl_white_kernel(const double* q_mu, const double* q_sqrt, int m,
                                                       int P, int q_diag, double* part) {
@@ -580,6 +704,79 @@ extern "C" int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, 
   FinalArgs f{};
   f.nterms = 1; f.part[0] = a.part; f.count[0] = nb; f.scale[0] = 1.0; f.add = 0.0; f.out = out;
   return stage2((hipStream_t)stream, f);
+}
+
+extern "C" int gpk_gauss_hermite(int n, double* x_host, double* w_host) {
+  if (!x_host || !w_host) return GPK_E_ARG;
+  if (n != GH_N) return GPK_E_UNSUPPORTED;
+  for (int i = 0; i < GH_N; ++i) { x_host[i] = gh_x_host[i]; w_host[i] = gh_w_host[i]; }
+  return 0;
+}
+
+// 0 if (lik, lik_params_host) names a likelihood the quadrature stage implements
+int gpk_likelihood_check(int lik, const double* params) {
+  switch (lik) {
+    case GPK_LIK_BERNOULLI_PROBIT: return 0;
+    case GPK_LIK_POISSON_EXP: return (params && params[0] > 0.0) ? 0 : GPK_E_ARG;
+    case GPK_LIK_STUDENT_T: return (params && params[0] > 0.0 && params[1] > 0.0) ? 0 : GPK_E_ARG;
+    default: return GPK_E_UNSUPPORTED;
+  }
+}
+
+int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const double* Y, long ldy, const double* fmean,
+                                        int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
+                                        const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
+                                        double* rows_out, double* dmu_out, double* dvar_out, double* part, double* part1, int* count) {
+  const int rc = gpk_likelihood_check(lik, params);
+  if (rc) return rc;
+  LikVarexpArgs a{};
+  a.Y = Y; a.ldy = ldy; a.fmean = fmean; a.rows = rows; a.P = P;
+  a.s0 = s0; a.s0_per_latent = s0_per_latent; a.ssq = ssq;
+  for (int i = 0; i < (knn_per_latent ? P : 1); ++i) a.knn[i] = knn_host[i];
+  a.knn_per_latent = knn_per_latent; a.mean_const = mean_const;
+  a.fvar_out = fvar_out; a.rows_out = rows_out; a.dmu_out = dmu_out; a.dvar_out = dvar_out;
+  a.part = part; a.part1 = part1;
+  const int per_wave = (lik == GPK_LIK_POISSON_EXP ? 64 : 16) / P;   // whole rows per wave pass
+  long nb = (((long)rows + per_wave - 1) / per_wave + RB / 64 - 1) / (RB / 64);
+  if (nb < 1) nb = 1;
+  if (nb > MAXPART) nb = MAXPART;
+  const dim3 grid((unsigned)nb), block(RB);
+  if (lik == GPK_LIK_BERNOULLI_PROBIT) {
+    hipLaunchKernelGGL((lik_varexp_kernel<GPK_LIK_BERNOULLI_PROBIT>), grid, block, 0, s, a);
+  } else if (lik == GPK_LIK_POISSON_EXP) {
+    a.par0 = params[0]; a.c0 = log(params[0]);
+    hipLaunchKernelGGL((lik_varexp_kernel<GPK_LIK_POISSON_EXP>), grid, block, 0, s, a);
+  } else {
+    const double scale = params[0], df = params[1];
+    a.par0 = scale; a.par1 = df;
+    a.c0 = lgamma(0.5 * (df + 1.0)) - lgamma(0.5 * df) - 0.5 * (log(scale * scale) + log(df) + log(3.141592653589793));
+    hipLaunchKernelGGL((lik_varexp_kernel<GPK_LIK_STUDENT_T>), grid, block, 0, s, a);
+  }
+  GPK_LAUNCH_CHECK();
+  *count = (int)nb;
+  return 0;
+}
+
+extern "C" int gpk_likelihood_varexp_sum(void* stream, int lik, const double* lik_params_host, const double* Y, long ldy,
+                                         const double* fmean, int rows, int P, const double* s0, int s0_per_latent,
+                                         const double* ssq, const double* knn_host, int knn_per_latent, double mean_const,
+                                         double* fvar_out, double* rows_out, double* dmu_out, double* dvar_out, double* out,
+                                         void* ws, size_t ws_bytes) {
+  if ((rows > 0 && (!Y || !fmean)) || !knn_host || !out || P <= 0 || P > 16 || rows < 0) return GPK_E_ARG;
+  if (!ws || ws_bytes < gpk_reduce_workspace_bytes(rows)) return GPK_E_WORKSPACE;
+  double* part = (double*)ws;
+  int nb = 0;
+  const int rc = gpk_launch_likelihood_varexp_stage1((hipStream_t)stream, lik, lik_params_host, Y, ldy, fmean, rows, P, s0,
+                                                     s0_per_latent, ssq, knn_host, knn_per_latent, mean_const, fvar_out, rows_out,
+                                                     dmu_out, dvar_out, part, part + MAXPART, &nb);
+  if (rc) return rc;
+  for (int t = 0; t < 2; ++t) {   // out[0] = sum VE, out[1] = sum dVE/dscale (StudentT; the others' partials are zeros)
+    FinalArgs f{};
+    f.nterms = 1; f.part[0] = part + t * MAXPART; f.count[0] = nb; f.scale[0] = 1.0; f.add = 0.0; f.out = out + t;
+    const int r2 = stage2((hipStream_t)stream, f);
+    if (r2) return r2;
+  }
+  return 0;
 }
 
 extern "C" int gpk_gauss_kl_white(void* stream, const double* q_mu, const double* q_sqrt, int m,

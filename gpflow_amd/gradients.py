@@ -412,7 +412,7 @@ class KernelSpec:
 def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor,
                        *, variance: float = None, lengthscales=None, noise_variance: float, jitter: float, scale: float = 1.0,
                        mean_const: float = 0.0, kl_weight: float = 1.0, family: str = "SquaredExponential",
-                       kernel_spec: "KernelSpec" = None
+                       kernel_spec: "KernelSpec" = None, likelihood=None
                        ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor]:
     """F = scale * sum_b var_exp_b - kl_weight * KL for the whitened SVGP with a stationary kernel (or, `kernel_spec`, a Sum /
     Product of stationary kernels: then grads["variance"] is [n_members] and grads["lengthscales"] a list), a Gaussian likelihood
@@ -420,7 +420,11 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
 
     Returns (F [1], grads, info).  `scale` = num_data / minibatch size (svgp.py:176-180).  For a row shard of a
     data-parallel step pass the GLOBAL scale and kl_weight = 1 / world_size: the SUM over ranks of F and of every
-    gradient is then the full-batch value (one all-reduce of the packed gradient, distributed.all_reduce_grads)."""
+    gradient is then the full-batch value (one all-reduce of the packed gradient, distributed.all_reduce_grads).
+
+    likelihood = (name, params) of ops.likelihood_varexp_sum (Bernoulli, Poisson, StudentT) replaces the Gaussian: the variational
+    expectations and the seeds r = dF/dfmean, c = dF/dfvar -- now one value per (row, latent) -- come from the quadrature kernel;
+    `noise_variance` is ignored, grads has no "noise_variance" and, for "student_t", a "likelihood_scale"."""
     M, D = Z.shape
     B = Xb.shape[0]
     P = q_mu.shape[1]
@@ -448,16 +452,28 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
         s0, fmean, _ = ops.row_stats(At, V=q_mu)                                        # rowsum(At^2), At q_mu
         W = ops.gemm_nt(At, LqT, b_tri=1)                                               # [P, B, M]: W_p = At Lq_p
         ssq = torch.stack([ops.row_stats(W[p])[0] for p in range(P)])                   # [P, B]
-    ve, _ = ops.gaussian_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], noise_variance=noise_variance,
-                                    mean_const=mean_const)
+    if likelihood is not None:
+        lik_out, _, dmu, dvar, _ = ops.likelihood_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], lik=likelihood[0],
+                                                             params=likelihood[1], mean_const=mean_const, want_grads=True)
+        ve = lik_out[0:1]
+    else:
+        ve, _ = ops.gaussian_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], noise_variance=noise_variance,
+                                        mean_const=mean_const)
     kl = ops.gauss_kl_white(q_mu, q_sqrt)
     F = torch.mul(ve, scale).sub_(kl, alpha=kl_weight)
 
     # ---------------------------------------------------------------- backward
     # het: one noise variance per row (a heteroskedastic Gaussian likelihood, round 5): dF/dfvar is a per-row vector, applied as a
     # row scaling of the factors it multiplied as a scalar (elementwise glue on [B, M] arrays); the scalar path is unchanged
-    het = torch.is_tensor(noise_variance) and noise_variance.dim() >= 1
-    if het:
+    # cmat: dF/dfvar per (row, latent) [B, P] from the quadrature kernel (a non-Gaussian likelihood): the heteroskedastic branch with
+    # W_p scaled by its own column and sum_p c_bp where that branch has P c_b
+    het = likelihood is None and torch.is_tensor(noise_variance) and noise_variance.dim() >= 1
+    cmat = None
+    if likelihood is not None:
+        c = None
+        r = dmu.mul_(scale)                                                             # dF/dfmean [B, P]
+        cmat = dvar.mul_(scale)                                                         # dF/dfvar  [B, P]
+    elif het:
         nv = noise_variance.reshape(-1)
         cvec = (-0.5 * scale) / nv                                                      # dF/dfvar per row [B]
         c = None
@@ -468,14 +484,21 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
         if mean_const != 0.0:
             r.sub_(mean_const)
         r.mul_(scale / noise_variance)
-    plain = not q_diag and not het and P <= 16
+    plain = not q_diag and not het and cmat is None and P <= 16
     # (plain: r q_mu^T - 2 c P At in ONE pass over At; it was a K = P GEMM, then an axpy pass behind the products below)
     Atb = ops.lowrank_axpy(-2.0 * c * P, At, r, q_mu) if plain else ops.gemm_nt(r, q_mu)  # r q_mu^T  [B, M]
     if q_diag:                                                                          # + 2c At (sum_p q_p^2 - P) per column
-        if het:
+        if cmat is not None:                                                            # + 2 At .* (c (q^2 - 1)^T)
+            Atb.addcmul_(At, ops.gemm_nt(cmat, q_sqrt * q_sqrt - 1.0), value=2.0)
+        elif het:
             Atb.addcmul_(At * (2.0 * cvec)[:, None], ((q_sqrt * q_sqrt).sum(1) - P)[None, :])
         else:
             Atb.addcmul_(At, (2.0 * c) * ((q_sqrt * q_sqrt).sum(1) - P)[None, :])
+    elif cmat is not None:
+        Wc = W * cmat.t()[:, :, None]                                                   # rows of W_p scaled by c_bp
+        for p in range(P):
+            ops.gemm_nt(Wc[p], Lq[p], alpha=2.0, beta=1.0, C=Atb, b_tri=2)
+        Atb.addcmul_(At, cmat.sum(1)[:, None], value=-2.0)                              # - 2 (sum_p c_bp) At
     elif het:
         Wc = W * cvec[None, :, None]                                                    # rows of W_p scaled by c_b
         for p in range(P):
@@ -497,11 +520,13 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
         g_mu = ops.row_stats(A, V=r, want_sumsq=False)[1].sub_(q_mu, alpha=kl_weight)
         if q_diag:
             return g_mu, None, None
-        Wg, ag = (Wc, 2.0) if het else (W, 2.0 * c)
+        Wg, ag = (Wc, 2.0) if (het or cmat is not None) else (W, 2.0 * c)
         return g_mu, [ops.transpose(Wg[p]) for p in range(P)], ag
 
     def branch_q_products(WgT, ag):
         if q_diag:   # d/dq = 2c colsum(At^2) q - (q - 1/q)   (KL of a diagonal q: kullback_leiblers.py:131-133,146-148)
+            if cmat is not None:   # 2 sum_b c_bp At[b, m]^2 as [M, P]
+                return ops.gemm_nt(A * A, cmat.t().contiguous(), alpha=2.0) * q_sqrt - kl_weight * (q_sqrt - 1.0 / q_sqrt)
             if het:
                 colsq2c = 2.0 * ((At * At) * cvec[:, None]).sum(0)                      # 2 sum_b c_b At[b, m]^2
                 return colsq2c[:, None] * q_sqrt - kl_weight * (q_sqrt - 1.0 / q_sqrt)
@@ -546,8 +571,8 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
         Lbar = splitk_gemm_nt(Kuf_bar, A, c_lower=True, alpha=-1.0)            # -tril(Kfu_bar^T At)
         Kuu_bar = cholesky_adjoint(LT, LinvT, Lbar, before_products=release_side)
         dkd = spec.dkdiag()                                                             # Knn = kdiag in every fvar
-        csum = cvec.sum() * P if het else c * B * P
-        one_kernel = spec.n == 1 and spec.tree is None and spec.cols[0] is None and not het
+        csum = cmat.sum() if cmat is not None else cvec.sum() * P if het else c * B * P
+        one_kernel = spec.n == 1 and spec.tree is None and spec.cols[0] is None and not het and cmat is None
         if one_kernel:
             # one stationary kernel over all input columns: the second adjoint ADDS its variance / lengthscale / Z gradients to the
             # first one's in its own tail launch, and the Knn term of d/dvariance rides along (no elementwise launches at all)
@@ -575,6 +600,11 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     else:
         g_var, g_ls = spec.pack([a + b + csum * dk for a, b, dk in zip(dv1, dv2, dkd)], [a + b for a, b in zip(dl1, dl2)])
         Zbar = Zb1 + Zb2
+    if likelihood is not None:
+        grads = {"variance": g_var, "lengthscales": g_ls, "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)}
+        if likelihood[0] == "student_t":
+            grads["likelihood_scale"] = lik_out[1:2] * scale
+        return F, grads, info
     if het:
         # dF/d sigma_n^2 = scale sum_p (-1 / (2 s2_n) + ((y - f)^2 + fvar) / (2 s2_n^2)): one entry per row (likelihood parameters
         # are reached through Gaussian.noise_param_grads)

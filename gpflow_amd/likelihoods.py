@@ -1,8 +1,9 @@
-"""Gaussian likelihood (gpflow/likelihoods/scalar_continuous.py:41-148) -- the conjugate case that
-keeps the whole ELBO on the dense path."""
+"""Likelihoods: Gaussian (gpflow/likelihoods/scalar_continuous.py:41-148) -- the conjugate case that keeps the whole ELBO on
+the dense path -- and the scalar non-conjugate ones whose variational expectations are Gauss-Hermite quadrature on the device
+(Bernoulli, Poisson: scalar_discrete.py; StudentT: scalar_continuous.py; ScalarLikelihood: base.py)."""
 from __future__ import annotations
 
-from math import sqrt
+from math import lgamma, log, pi, sqrt
 from typing import Optional
 
 import numpy as np
@@ -127,3 +128,176 @@ class Gaussian(Likelihood):
         Y = ops.to_device(Y)
         logv = torch.log(v) if torch.is_tensor(v) else float(np.log(v))
         return (-0.5 * LOG2PI - 0.5 * logv - 0.5 * ((Y - Fmu) ** 2 + Fvar) / v).sum(-1)
+
+
+DEFAULT_NUM_GAUSS_HERMITE_POINTS = 20   # quadrature/gauss_hermite.py
+
+
+def inv_probit(x: torch.Tensor) -> torch.Tensor:
+    """utilities/ops.py inv_probit: the probit link with its 1e-3 jitter"""
+    jitter = 1e-3
+    return 0.5 * (1.0 + torch.special.erf(x / sqrt(2.0))) * (1 - 2 * jitter) + jitter
+
+
+exp = torch.exp   # the Poisson link (the reference passes tf.exp)
+
+
+class ScalarLikelihood(Likelihood):
+    """likelihoods/base.py ScalarLikelihood: one latent per output column, everything elementwise over [N, P]; integrals against
+    N(f | mu, v) are 20-point Gauss-Hermite sums, sum_h (w_h / sqrt pi) g(mu + sqrt(2 v) x_h) (quadrature/gauss_hermite.py).
+    `variational_expectations`, the hot one, runs in gpk_likelihood_varexp_sum; the prediction-side integrals are elementwise
+    device glue over the [20] node table, like the Gaussian methods above.  No clamp of Fvar anywhere: a negative value gives NaN
+    through the square root, as in the reference."""
+
+    device_lik: str = ""   # the likelihood's name in ops.LIKELIHOOD_CODES
+
+    def device_params(self) -> tuple:
+        """the lik_params_host of the C-ABI at the current parameter values"""
+        return ()
+
+    # elementwise pieces, F and Y broadcastable device tensors
+    def _log_density(self, F, Y):
+        raise NotImplementedError
+
+    def _conditional_mean(self, F):
+        raise NotImplementedError
+
+    def _conditional_variance(self, F):
+        raise NotImplementedError
+
+    def log_prob(self, X, F, Y):
+        return self._log_density(ops.to_device(F), ops.to_device(Y)).sum(-1)
+
+    def conditional_mean(self, X, F):
+        return self._conditional_mean(ops.to_device(F))
+
+    def conditional_variance(self, X, F):
+        return self._conditional_variance(ops.to_device(F))
+
+    @staticmethod
+    def _nodes(like: torch.Tensor):
+        """(x [H], w / sqrt(pi) [H]) next to `like`: the table the kernels use (ops.gauss_hermite)"""
+        x, w = ops.gauss_hermite(DEFAULT_NUM_GAUSS_HERMITE_POINTS)
+        return (torch.as_tensor(x, dtype=torch.float64, device=like.device),
+                torch.as_tensor(w / np.sqrt(np.pi), dtype=torch.float64, device=like.device))
+
+    def _points(self, Fmu, Fvar):
+        """f_h = mu + sqrt(2 v) x_h as [..., H], and the normalised weights [H]"""
+        Fmu, Fvar = ops.to_device(Fmu), ops.to_device(Fvar)
+        x, wn = self._nodes(Fmu)
+        return Fmu[..., None] + torch.sqrt(2.0 * Fvar)[..., None] * x, wn
+
+    def variational_expectations(self, X, Fmu, Fvar, Y) -> torch.Tensor:
+        """base.py ScalarLikelihood.variational_expectations -- per-row values [N], summed over the P outputs; the kernel takes
+        at most 16 output columns per call."""
+        Fmu, Fvar, Y = ops.to_device(Fmu), ops.to_device(Fvar), ops.to_device(Y)
+        lead, P = Fmu.shape[:-1], Fmu.shape[-1]
+        Fm, Fv, Yd = Fmu.reshape(-1, P), Fvar.reshape(-1, P), Y.reshape(-1, P)
+        total = None
+        for c0 in range(0, P, 16):
+            c1 = min(c0 + 16, P)
+            rows = ops.likelihood_varexp_sum(Yd[:, c0:c1], Fm[:, c0:c1].contiguous(), s0=None, ssq=Fv[:, c0:c1].t().contiguous(),
+                                             knn=[0.0], lik=self.device_lik, params=self.device_params(), want_rows=True)[1]
+            total = rows if total is None else total + rows
+        return total.reshape(lead)
+
+    def predict_mean_and_var(self, X, Fmu, Fvar):
+        """base.py: E_y = int E[y|f], V_y = int (Var[y|f] + E[y|f]^2) - E_y^2"""
+        f, wn = self._points(Fmu, Fvar)
+        cm = self._conditional_mean(f)
+        E_y = (cm * wn).sum(-1)
+        V_y = ((self._conditional_variance(f) + cm * cm) * wn).sum(-1) - E_y * E_y
+        return E_y, V_y
+
+    def predict_log_density(self, X, Fmu, Fvar, Y):
+        """base.py: log int p(y|f) N(f) df in log space, logsumexp_h(log(w_h / sqrt pi) + log p(y | f_h)), summed over P -> [N]"""
+        f, wn = self._points(Fmu, Fvar)
+        return torch.logsumexp(torch.log(wn) + self._log_density(f, ops.to_device(Y)[..., None]), dim=-1).sum(-1)
+
+
+class Bernoulli(ScalarLikelihood):
+    """Bernoulli(invlink=inv_probit), scalar_discrete.py: log p(y|f) = log(y == 1 ? p : 1 - p), p = inv_probit(f).  Only the probit
+    link is built.  A non-finite label gives NaN (the comparison alone would read it as class 0)."""
+
+    device_lik = "bernoulli_probit"
+
+    def __init__(self, invlink=inv_probit):
+        if invlink is not inv_probit:
+            raise NotImplementedError("Bernoulli: only the inv_probit link is implemented")
+        self.invlink = invlink
+
+    def _log_density(self, F, Y):
+        return self._log_density_of_p(inv_probit(F), Y)
+
+    def _conditional_mean(self, F):
+        return inv_probit(F)
+
+    def _conditional_variance(self, F):
+        p = inv_probit(F)
+        return p - p * p
+
+    def predict_mean_and_var(self, X, Fmu, Fvar):
+        """scalar_discrete.py: closed form under the probit link"""
+        p = inv_probit(ops.to_device(Fmu) / torch.sqrt(1 + ops.to_device(Fvar)))
+        return p, p - p * p
+
+    def predict_log_density(self, X, Fmu, Fvar, Y):
+        p = self.predict_mean_and_var(X, Fmu, Fvar)[0]
+        return self._log_density_of_p(p, ops.to_device(Y)).sum(-1)
+
+    @staticmethod
+    def _log_density_of_p(p, Y):
+        return torch.log(torch.where(Y == 1, p, 1 - p)) + (Y - Y)
+
+
+class Poisson(ScalarLikelihood):
+    """Poisson(invlink=exp, binsize=1.0), scalar_discrete.py: log p = y log(lambda) - lambda - lgamma(y + 1), lambda = exp(f) binsize.
+    Only the exp link is built; its variational expectations are the reference's closed form."""
+
+    device_lik = "poisson_exp"
+
+    def __init__(self, invlink=exp, binsize: float = 1.0):
+        if invlink not in (exp, np.exp):
+            raise NotImplementedError("Poisson: only the exp link is implemented")
+        self.invlink = exp
+        self.binsize = float(binsize)
+        if not self.binsize > 0.0:
+            raise ValueError("Poisson: binsize must be positive")
+
+    def device_params(self) -> tuple:
+        return (self.binsize,)
+
+    def _log_density(self, F, Y):
+        return Y * (F + log(self.binsize)) - torch.exp(F) * self.binsize - torch.lgamma(Y + 1.0)
+
+    def _conditional_mean(self, F):
+        return torch.exp(F) * self.binsize
+
+    def _conditional_variance(self, F):
+        return torch.exp(F) * self.binsize
+
+
+class StudentT(ScalarLikelihood):
+    """StudentT(scale=1.0, df=3.0), scalar_continuous.py: `scale` a positive Parameter, `df` a plain float."""
+
+    device_lik = "student_t"
+
+    def __init__(self, scale=1.0, df: float = 3.0):
+        self.df = float(df)
+        self.scale = Parameter(scale, transform=positive())
+
+    def device_params(self) -> tuple:
+        return (float(self.scale.numpy()), self.df)
+
+    def _log_density(self, F, Y):
+        """logdensities.py student_t"""
+        scale, df = float(self.scale.numpy()), self.df
+        const = lgamma(0.5 * (df + 1.0)) - lgamma(0.5 * df) - 0.5 * (log(scale * scale) + log(df) + log(pi))
+        return const - 0.5 * (df + 1.0) * torch.log(1.0 + ((Y - F) / scale) ** 2 / df)
+
+    def _conditional_mean(self, F):
+        return F
+
+    def _conditional_variance(self, F):
+        scale = float(self.scale.numpy())
+        return torch.full_like(F, scale * scale * self.df / (self.df - 2.0))

@@ -13,7 +13,7 @@ from ..inducing_variables import (InducingPoints, SharedIndependentInducingVaria
                                   inducingpoint_wrapper)
 from ..kernels import Kernel, SharedIndependent
 from ..kernels.stationaries import Stationary
-from ..likelihoods import Gaussian, Likelihood
+from ..likelihoods import Gaussian, Likelihood, ScalarLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
 from .training_mixins import ExternalDataTrainingLossMixin
@@ -63,9 +63,10 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
     # ---- fused device path ---------------------------------------------------------------------
     def _fused_config(self):
         """(stationary kernel, Z tensor, mean constant) when the whole ELBO shard is one C-ABI call:
-        Gaussian likelihood, constant mean, and one stationary kernel shared by all latents (plain kernel +
+        Gaussian likelihood or one of the quadrature likelihoods (Bernoulli, Poisson, StudentT: gpk_svgp_elbo_shard_lik), constant
+        mean, and one stationary kernel shared by all latents (plain kernel +
         InducingPoints, or SharedIndependent + SharedIndependentInducingVariables); whitened or not, full or diagonal q_sqrt."""
-        if not isinstance(self.likelihood, Gaussian):
+        if not (isinstance(self.likelihood, Gaussian) or self._device_likelihood()):
             return None
         c = self.mean_function.constant_value()
         if c is None:
@@ -76,6 +77,11 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         if not (isinstance(k, Stationary) and isinstance(iv, InducingPoints)):
             return None
         return k, iv.Z.device_value(), c
+
+    def _device_likelihood(self) -> bool:
+        """a non-Gaussian likelihood whose variational expectations the library computes (ops.LIKELIHOOD_CODES), at most 16 latents"""
+        lik = self.likelihood
+        return isinstance(lik, ScalarLikelihood) and lik.device_lik in ops.LIKELIHOOD_CODES and self.q_mu.shape[1] <= 16
 
     def _fused_separate_config(self):
         """(member kernels, Z [m, d] | [P, m, d], mean constant) when the ELBO shard of a SeparateIndependent model is one
@@ -214,10 +220,16 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             key = (m, rows, d, P, q_sqrt.dim() == 2, bool(self.whiten))
             if self._ws is None or self._ws[0] != key:
                 self._ws = (key, ops.svgp_elbo_workspace(m, rows, d, P, q_sqrt.dim() == 2, self.whiten))
-            out, info = ops.svgp_elbo_shard(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt, variance=var,
-                                            lengthscales=ls, noise_variance=self.likelihood.noise_for(X),
-                                            jitter=config.default_jitter(), mean_const=c, family=family,
-                                            ws=self._ws[1], whiten=self.whiten)
+            if isinstance(self.likelihood, Gaussian):
+                out, info = ops.svgp_elbo_shard(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt, variance=var,
+                                                lengthscales=ls, noise_variance=self.likelihood.noise_for(X),
+                                                jitter=config.default_jitter(), mean_const=c, family=family,
+                                                ws=self._ws[1], whiten=self.whiten)
+            else:
+                out, info = ops.svgp_elbo_shard_lik(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt, variance=var, lengthscales=ls,
+                                                    lik=self.likelihood.device_lik, params=self.likelihood.device_params(),
+                                                    jitter=config.default_jitter(), mean_const=c, family=family,
+                                                    ws=self._ws[1], whiten=self.whiten)
             ops.check_info(info)
             return out
         sep = self._fused_separate_config()
@@ -334,6 +346,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         from ..mean_functions import Constant
         lik, mf = self.likelihood, self.mean_function
         # scope checks first: a model outside the reverse pass is refused before anything touches the device
+        if isinstance(lik, ScalarLikelihood):
+            return self._elbo_and_grad_quadrature(data)
         sep = self._separate_gradient_config()
         from ..kernels.base import gradient_spec
         combo = gradient_spec(self.kernel, int(tuple(data[0].shape)[-1])) if sep is None else None   # Sum / Product of stationary kernels
@@ -403,6 +417,52 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
                 gu = np.asarray(gc, dtype=np.float64).reshape(u.shape) * par.transform.forward_grad(u)
             out[par] = out[par] + gu if par in out else gu
         return self._add_log_prior(Fv, out)   # (+ log prior density of the trainable parameters: model.py:56-76)
+
+    def _elbo_and_grad_quadrature(self, data):
+        """elbo_and_grad with a quadrature likelihood (Bernoulli, Poisson, StudentT): the whitened reverse pass seeded per (row,
+        latent) by the kernel's own d/dfmean, d/dfvar (gradients.svgp_elbo_and_grad, likelihood=).  Whitened, ONE isotropic
+        stationary kernel over all input columns (optionally shared by the latents), InducingPoints, full or diagonal q_sqrt,
+        constant mean; everything else is refused before anything touches the device."""
+        from .. import gradients
+        from ..base import FillTriangular
+        from ..kernels.stationaries import IsotropicStationary
+        from ..likelihoods import StudentT
+        from ..mean_functions import Constant
+        lik, mf, k, iv = self.likelihood, self.mean_function, self.kernel, self.inducing_variable
+        if isinstance(k, SharedIndependent) and isinstance(iv, SharedIndependentInducingVariables):
+            k, iv = k.kernel, iv.inducing_variable
+        c = mf.constant_value()
+        if not (self.whiten and self._device_likelihood() and isinstance(k, IsotropicStationary) and k.family in ops.KERNEL_FAMILIES
+                and k.has_default_active_dims and isinstance(iv, InducingPoints) and c is not None):
+            raise NotImplementedError("gradients with a Bernoulli / Poisson / StudentT likelihood: whitened SVGP with one "
+                                      "SquaredExponential / Matern kernel (optionally shared by independent latents) over all input "
+                                      "columns, InducingPoints, constant mean, at most 16 latents")
+        X, Y = ops.to_device(data[0]), ops.to_device(data[1])
+        scale = 1.0 if self.num_data is None else float(self.num_data) / float(X.shape[0])
+        family, var, ls = k.hyper()
+        F, g, info = gradients.svgp_elbo_and_grad(iv.Z.device_value(), X.contiguous(), Y, self.q_mu.device_value(),
+                                                  self.q_sqrt.device_value(), variance=var, lengthscales=ls, noise_variance=None,
+                                                  jitter=config.default_jitter(), scale=scale, mean_const=float(c), family=family,
+                                                  likelihood=(lik.device_lik, lik.device_params()))
+        ops.check_info(info)
+        host = {n: t.cpu().numpy() for n, t in g.items()}
+        pairs = [(k.variance, host["variance"]), (k.lengthscales, host["lengthscales"]), (iv.Z, host["Z"]),
+                 (self.q_mu, host["q_mu"]), (self.q_sqrt, host["q_sqrt"])]
+        if isinstance(lik, StudentT):
+            pairs.append((lik.scale, host["likelihood_scale"]))
+        if isinstance(mf, Constant) and hasattr(mf, "c"):   # (Zero is a Constant without a parameter, functions.py:195-204)
+            pairs.append((mf.c, host["mean_const"]))
+        out = {}
+        for par, gc in pairs:
+            if not par.trainable:
+                continue
+            u = par.unconstrained_variable
+            if isinstance(par.transform, FillTriangular):
+                gu = par.transform.inverse(np.asarray(gc, dtype=np.float64)).reshape(u.shape)
+            else:
+                gu = np.asarray(gc, dtype=np.float64).reshape(u.shape) * par.transform.forward_grad(u)
+            out[par] = out[par] + gu if par in out else gu
+        return self._add_log_prior(float(F.cpu()[0]), out)
 
     def _elbo_and_grad_combination(self, data, combo):
         """elbo_and_grad for a Sum / Product of stationary kernels (kernels/base.py:216-220, 305-315), members possibly over

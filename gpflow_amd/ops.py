@@ -431,6 +431,67 @@ def gaussian_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[to
     return out, fvar
 
 
+LIKELIHOOD_CODES = {"bernoulli_probit": 1, "poisson_exp": 2, "student_t": 3}   # include/gpk.h: GPK_LIK_*
+
+
+def _lik_args(lik: str, params):
+    """(code, host array | None) of the (lik, lik_params_host) pair of the C-ABI: params is () for "bernoulli_probit", (binsize,)
+    for "poisson_exp", (scale, df) for "student_t"."""
+    if lik not in LIKELIHOOD_CODES:
+        raise ValueError(f"unknown likelihood {lik!r}: one of {sorted(LIKELIHOOD_CODES)}")
+    params = [float(v) for v in params]
+    if len(params) != {"bernoulli_probit": 0, "poisson_exp": 1, "student_t": 2}[lik]:
+        raise ValueError(f"likelihood {lik!r}: wrong number of parameters ({len(params)})")
+    return LIKELIHOOD_CODES[lik], (_lib.host_doubles(params) if params else None)
+
+
+def gauss_hermite(n: int = 20) -> Tuple[np.ndarray, np.ndarray]:
+    """(x [n], w [n]) = numpy.polynomial.hermite.hermgauss(n) as the kernels hold it (gpk_gauss_hermite; host only, n = 20)."""
+    lib = _lib.load()
+    x, w = (_lib.c_double * int(n))(), (_lib.c_double * int(n))()
+    _lib.check(lib.gpk_gauss_hermite(int(n), x, w), "gpk_gauss_hermite")
+    return np.array(x, dtype=np.float64), np.array(w, dtype=np.float64)
+
+
+def likelihood_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[torch.Tensor], ssq: Optional[torch.Tensor],
+                          knn: Sequence[float], lik: str, params=(), mean_const: float = 0.0, s0_per_latent: bool = False,
+                          want_fvar: bool = False, want_rows: bool = False, want_grads: bool = False):
+    """Gauss-Hermite variational expectations of a non-Gaussian scalar likelihood (gpk_likelihood_varexp_sum), fvar = knn - s0 + ssq.
+    Returns (out [2], rows | None, dmu | None, dvar | None, fvar | None): out[0] = sum over rows and outputs, out[1] = its
+    derivative w.r.t. the StudentT scale (0 otherwise); rows [rows] = sums over the outputs; dmu, dvar [rows, P] = d/dfmean,
+    d/dfvar of every term."""
+    lib = _lib.load()
+    _chk(Y, "Y", 2)
+    _chk(fmean, "fmean", 2)
+    rows, P = fmean.shape
+    if not fmean.is_contiguous():
+        raise ValueError("fmean must be contiguous")
+    if Y.shape[0] != rows or Y.shape[1] < P:
+        raise ValueError("Y must have one row per row of fmean and at least P columns")
+    for name, t, shape in (("s0", s0, (P, rows) if s0_per_latent else (rows,)), ("ssq", ssq, (P, rows))):
+        if t is not None:
+            _chk(t, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous {shape}")
+    code, par = _lik_args(lik, params)
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=Y.device)
+    out = new(2)
+    fvar = new(rows, P) if want_fvar else None
+    rws = new(rows) if want_rows else None
+    dmu, dvar = (new(rows, P), new(rows, P)) if want_grads else (None, None)
+    ws = _ws(int(lib.gpk_reduce_workspace_bytes(rows)))
+    knn = list(np.atleast_1d(np.asarray(knn, dtype=np.float64)))
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    rc = lib.gpk_likelihood_varexp_sum(_stream(), code, par, Y.data_ptr(), _rowmajor(Y, "Y"), fmean.data_ptr(), rows, P,
+                                       ptr(s0), int(s0_per_latent), ptr(ssq), _lib.host_doubles(knn), int(len(knn) > 1),
+                                       float(mean_const), ptr(fvar), ptr(rws), ptr(dmu), ptr(dvar), out.data_ptr(),
+                                       ws.data_ptr(), ws.numel() * 8)
+    _lib.check(rc, "gpk_likelihood_varexp_sum")
+    return out, rws, dmu, dvar, fvar
+
+
 def gauss_kl_white(q_mu: torch.Tensor, q_sqrt: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     _chk(q_mu, "q_mu", 2)
@@ -744,4 +805,41 @@ def svgp_elbo_shard(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: t
                                  q_mu.data_ptr(), q_sqrt.data_ptr(), int(q_diag), int(bool(whiten)), out.data_ptr(),
                                  info.data_ptr(), ws.data_ptr(), ws.numel() * 8)
     _lib.check(rc, "gpk_svgp_elbo_shard")
+    return out, info
+
+
+def svgp_elbo_shard_lik(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor, *,
+                        variance: float, lengthscales, lik: str, params=(), jitter: float, mean_const: float = 0.0,
+                        family: str = "SquaredExponential", ws: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None,
+                        whiten: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """svgp_elbo_shard with a non-Gaussian likelihood (lik, params as likelihood_varexp_sum) in place of the noise variance:
+    out[0] = sum_b of the quadrature variational expectations over this shard, out[1] = KL.  Same forms, same workspace."""
+    lib = _lib.load()
+    for name, t in (("Z", Z), ("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)):
+        _chk(t, name, 2)
+    _chk(q_sqrt, "q_sqrt")
+    m, d = Z.shape
+    rows = Xb.shape[0]
+    P = q_mu.shape[1]
+    q_diag = q_sqrt.dim() == 2
+    if Xb.shape[1] != d or Yb.shape[0] != rows or Yb.shape[1] != P or q_mu.shape[0] != m:
+        raise ValueError("inconsistent shapes")
+    if not (q_mu.is_contiguous() and q_sqrt.is_contiguous()):
+        raise ValueError("q_mu / q_sqrt must be contiguous")
+    code, par = _lik_args(lik, params)
+    nbytes = int(lib.gpk_svgp_elbo_workspace_bytes(m, rows, d, P, int(q_diag), int(bool(whiten))))
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _ws(nbytes)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=Z.device)
+    if info is None:
+        info = torch.zeros(1, dtype=torch.int32, device=Z.device)
+    ls, ard = _ls_host(lengthscales, d)
+    rc = lib.gpk_svgp_elbo_shard_lik(_stream(), KERNEL_FAMILIES[family], Z.data_ptr(), m, _rowmajor(Z, "Z"), Xb.data_ptr(),
+                                     Yb.data_ptr(), rows, _rowmajor(Xb, "Xb"), _rowmajor(Yb, "Yb"), d, P, ls, ard,
+                                     float(variance), code, par, float(jitter), float(mean_const), q_mu.data_ptr(),
+                                     q_sqrt.data_ptr(), int(q_diag), int(bool(whiten)), out.data_ptr(), info.data_ptr(),
+                                     ws.data_ptr(), ws.numel() * 8)
+    _lib.check(rc, "gpk_svgp_elbo_shard_lik")
     return out, info

@@ -232,6 +232,37 @@ int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, const doubl
                             const double* noise_rows, double mean_const, double* fvar_out, double* out, void* ws,
                             size_t ws_bytes);
 
+/* Non-Gaussian variational expectations by Gauss-Hermite quadrature -- the counterpart of gpk_gaussian_varexp_sum for the
+ * scalar likelihoods of likelihoods/scalar_discrete.py and scalar_continuous.py (ScalarLikelihood.variational_expectations,
+ * likelihoods/base.py, through quadrature/gauss_hermite.py with DEFAULT_NUM_GAUSS_HERMITE_POINTS = 20):
+ *   fvar[b,p] = knn - s0[b | p,b] + ssq[p,b],   mu = fmean[b,p] + mean_const,   sum_h (w_h / sqrt pi) g(mu + sqrt(2 fvar) x_h)
+ *   VE[b,p]   = that sum with g(f) = log p(Y[b,p] | f)
+ *   out[0] = sum_b sum_p VE[b,p];   out[1] = sum_b sum_p dVE/dscale (GPK_LIK_STUDENT_T; 0 for the others)
+ *   rows_out [rows]   = sum_p VE[b,p]                      (what variational_expectations returns)
+ *   dmu_out, dvar_out [rows,P] = dVE/dfmean, dVE/dfvar: the exact derivatives of the quadrature sum,
+ *                       sum_h (w_h / sqrt pi) g'(f_h)  and  sum_h (w_h / sqrt pi) g'(f_h) x_h / sqrt(2 fvar)
+ * Operands as gpk_gaussian_varexp_sum (Y/ldy, fmean contiguous [rows,P], s0 / ssq / fvar_out optional, knn a HOST pointer,
+ * 1 <= P <= 16, rows = 0 writes out = [0, 0]); rows_out, dmu_out, dvar_out optional.  lik and lik_params_host (HOST pointer):
+ *   GPK_LIK_BERNOULLI_PROBIT  g = log(y == 1 ? p : 1 - p), p = 0.5 (1 + erf(f / sqrt 2)) (1 - 2e-3) + 1e-3;  no parameters (NULL)
+ *   GPK_LIK_POISSON_EXP       params = {binsize}: the reference's closed form (no quadrature)
+ *                             VE = y mu - exp(mu + fvar / 2) binsize - lgamma(y + 1) + y log(binsize)
+ *   GPK_LIK_STUDENT_T         params = {scale, df}: g = lgamma((df+1)/2) - lgamma(df/2) - (log scale^2 + log df + log pi) / 2
+ *                                                       - (df + 1) / 2 log(1 + ((y - f) / scale)^2 / df)
+ * An unknown code returns GPK_E_UNSUPPORTED, a missing or non-positive parameter GPK_E_ARG.  fvar is not clamped: a negative
+ * value gives NaN through the square root, as in the reference.  NaN / Inf in Y, fmean or fvar reach out and the element's
+ * own rows_out / dmu_out / dvar_out entries (a non-finite label adds y - y to each of them), and nothing else.
+ * Deterministic: four lanes share an element and combine in a fixed shuffle order, then the two-stage reduction. */
+#define GPK_LIK_BERNOULLI_PROBIT 1
+#define GPK_LIK_POISSON_EXP 2
+#define GPK_LIK_STUDENT_T 3
+int gpk_likelihood_varexp_sum(void* stream, int lik, const double* lik_params_host, const double* Y, long ldy,
+                              const double* fmean, int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
+                              const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
+                              double* rows_out, double* dmu_out, double* dvar_out, double* out, void* ws, size_t ws_bytes);
+/* The quadrature table the kernels use: n nodes x_host and weights w_host of numpy.polynomial.hermite.hermgauss(n).  Host only
+ * (no stream, no device); n = 20 is the only table: anything else returns GPK_E_UNSUPPORTED. */
+int gpk_gauss_hermite(int n, double* x_host, double* w_host);
+
 /* whitened KL (kullback_leiblers.py:98-165 with K None):
  *   out[0] = 0.5 * ( sum q_mu^2 - M*P - sum log diag(Lq)^2 + sum tril(Lq)^2 )
  * q_sqrt [P,m,m] (q_diag = 0) or [m,P] (q_diag = 1). */
@@ -314,6 +345,15 @@ int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, int m, long l
                         const double* noise_rows, double jitter, double mean_const, const double* q_mu,
                         const double* q_sqrt, int q_diag, int whiten, double* out, int* info,
                         void* ws, size_t ws_bytes);
+
+/* gpk_svgp_elbo_shard with a non-Gaussian likelihood: (lik, lik_params_host) as in gpk_likelihood_varexp_sum take the place
+ * of (noise_variance, noise_rows); out[0] is then the sum of the quadrature variational expectations.  Every form of the shard
+ * (whitened or not, full or diagonal q_sqrt), its schedule and its workspace (gpk_svgp_elbo_workspace_bytes) are the same:
+ * only the last stage differs. */
+int gpk_svgp_elbo_shard_lik(void* stream, int family, const double* Z, int m, long ldz, const double* Xb, const double* Yb,
+                            int rows, long ldxb, long ldyb, int d, int P, const double* ls_host, int ard, double variance,
+                            int lik, const double* lik_params_host, double jitter, double mean_const, const double* q_mu,
+                            const double* q_sqrt, int q_diag, int whiten, double* out, int* info, void* ws, size_t ws_bytes);
 
 /* The same for SEPARATE kernels per latent (SeparateIndependent, conditionals/util.py:566-629 behind
  * SeparateIndependentPosterior posteriors.py:863-887), whitened, full q_sqrt [P,m,m]: P covariance pairs into one batched
