@@ -10,10 +10,15 @@ extern "C" size_t gpk_project_workspace_bytes(int rows, int m, int P) {
 }
 
 namespace {
-// the GEMM alone: partials [P][nt = 2 * tiles_n][rows] in ws, one per 64 output columns
+// the GEMM alone: partials [P][nt = 2 * tiles_n][rows] in ws, one per 64 output columns.
+// V [m, P] (may be null) asks for the row statistics of At as well: s0[b] = sum_k At[b,k]^2, fmean[b,p] = sum_k At[b,k] V[k,p].
+// They come out of the GEMM itself where it runs on the 128 x 128 fast tile and P <= 4 (the headline: no pass over At of their
+// own); everywhere else -- more latents, the small-tile and generic kernels, one At per latent -- from gpk_row_stats, in front of
+// the GEMM as before.  This is the only place that decides.
 int project_parts(hipStream_t s, const double* At, int rows, int m, long ldat, long strideAt, const double* LqT, long ldl, int P, void* ws,
-                  size_t ws_bytes) {
+                  size_t ws_bytes, const double* V = nullptr, double* s0 = nullptr, double* fmean = nullptr) {
   if ((!At && rows > 0) || !LqT || rows < 0 || m <= 0 || P <= 0 || strideAt < 0) return GPK_E_ARG;
+  if (V && ((rows > 0 && (!s0 || !fmean)) || strideAt != 0)) return GPK_E_ARG;
   if (!ws || ws_bytes < gpk_project_workspace_bytes(rows, m, P)) return GPK_E_WORKSPACE;
   if (rows == 0) return 0;
   const int nt = 2 * gpk_gemm_tiles_n(m);
@@ -22,9 +27,27 @@ int project_parts(hipStream_t s, const double* At, int rows, int m, long ldat, l
   g.epi = 1; g.sq_cols = m; g.c2_cols = 0;
   g.part = (double*)ws; g.part_ld = rows; g.stridePart = (long)nt * rows;
   g.C2 = (double*)ws; g.ldc2 = 0; g.strideC2 = 0;
+  if (V) {
+    g.stat_sumsq = s0; g.stat_mv = fmean; g.stat_V = V; g.stat_P = P;
+    if (!gpk_gemm_fuses_row_stats(g)) {
+      g.stat_sumsq = g.stat_mv = nullptr; g.stat_V = nullptr; g.stat_P = 0;
+      const int rc = gpk_row_stats((void*)s, At, rows, m, ldat, V, nullptr, P, 1.0, 0.0, s0, fmean, nullptr);
+      if (rc) return rc;
+    }
+  }
   return gpk_launch_gemm(s, g);
 }
 }  // namespace
+
+extern "C" int gpk_project_stats(void* stream, const double* At, int rows, int m, long ldat, const double* LqT, long ldl, int P,
+                                 const double* V, double* s0, double* fmean, double* ssq, void* ws, size_t ws_bytes) {
+  if (!V || (rows > 0 && !ssq)) return GPK_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = project_parts(s, At, rows, m, ldat, 0, LqT, ldl, P, ws, ws_bytes, V, s0, fmean);
+  if (rc || rows == 0) return rc;
+  const int nt = 2 * gpk_gemm_tiles_n(m);
+  return gpk_launch_sum_parts(s, (const double*)ws, nt, rows, (long)nt * rows, P, ssq);
+}
 
 extern "C" int gpk_project_batched(void* stream, const double* At, int rows, int m, long ldat, long strideAt,
                                    const double* LqT, long ldl, int P, double* ssq, void* ws, size_t ws_bytes) {
@@ -239,7 +262,17 @@ int transpose_q_sqrt(hipStream_t s, const ElboArgs& a, const ElboWs& w) {
 
 // sum_b var_exp_b -> out[0]  (likelihoods/scalar_continuous.py:139-148, svgp.py:174,181); knn_host: the kernel variance(s).
 // The only stage of a shard that knows the likelihood: Gaussian in closed form, the others by Gauss-Hermite quadrature.
-int varexp_to_out(hipStream_t s, const ElboArgs& a, const ElboWs& w, const double* knn_host, int per_latent) {
+// slot != null (Gaussian, shared kernel): ssq is still nt slot partials [P][nt][rows] and `ticket` a zeroed word -- one launch
+// sums the slots, forms the expectations and reduces them (gpk_launch_varexp_tail)
+int varexp_to_out(hipStream_t s, const ElboArgs& a, const ElboWs& w, const double* knn_host, int per_latent,
+                  const double* slot = nullptr, int nt = 0, int* ticket = nullptr) {
+  if (slot && !a.lik)
+    return gpk_launch_varexp_tail(s, a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, slot, nt, (long)nt * a.rows, knn_host[0],
+                                  a.noise_variance, a.mean_const, a.noise_rows, w.part0, ticket, a.out);
+  if (slot) {   // the quadrature likelihoods keep their launches
+    const int rc = gpk_launch_sum_parts(s, slot, nt, a.rows, (long)nt * a.rows, a.P, w.ssq);
+    if (rc) return rc;
+  }
   int count = 0;
   const int rc = a.lik
       ? gpk_launch_likelihood_varexp_stage1(s, a.lik, a.lik_params, a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, per_latent, w.ssq,
@@ -251,9 +284,12 @@ int varexp_to_out(hipStream_t s, const ElboArgs& a, const ElboWs& w, const doubl
   return final_one(s, w.part0, count, 1.0, 0.0, a.out);
 }
 // KL[q || N(0, I)] -> out[1]  (kullback_leiblers.py:45-46, 98-165)
+// Its first kernel also zeroes the ticket of the shard's one-launch tail (tail_ticket): every whitened shard runs it before that
+// tail, on the caller's stream or on a stream the factorisation joins before it returns.
+int* tail_ticket(const ElboWs& w) { return (int*)(w.part2 + GPK_REDUCE_MAXPART + 32); }   // (part2: not otherwise used by the whitened form)
 int kl_white_to_out(hipStream_t s, const ElboArgs& a, const ElboWs& w) {
   int count = 0;
-  const int rc = gpk_launch_kl_white_stage1(s, a.q_mu, a.q_sqrt, a.m, a.P, a.q_diag, w.part1, &count);
+  const int rc = gpk_launch_kl_white_stage1(s, a.q_mu, a.q_sqrt, a.m, a.P, a.q_diag, w.part1, &count, w.part2 ? tail_ticket(w) : nullptr);
   if (rc) return rc;
   return final_one(s, w.part1, count, 0.5, -0.5 * (double)a.m * (double)a.P, a.out + 1);
 }
@@ -276,22 +312,21 @@ int elbo_whitened(hipStream_t s, const ElboArgs& a, const ElboWs& w) {
   // Lm = chol(Kuu);  A^T = Kfu Lm^-T   (conditionals/util.py:67,125)
   int rc = gpk_potrf_core(s, w.T, a.m, a.rows, w.ld, 1, 0, w.invd, 0, a.info, hk);
   if (rc) return rc;
-  // s0 = sum_k A^2 (util.py:133), fmean = A^T q_mu (util.py:144), q_diag: ssq = sum (A q_sqrt)^2 (:149)
-  rc = gpk_row_stats((void*)s, w.Kfu, a.rows, a.m, w.ld, a.q_mu, a.q_diag ? a.q_sqrt : nullptr, a.P, 1.0, 0.0, w.s0, w.fmean,
-                     a.q_diag ? w.ssq : nullptr);
-  if (rc) return rc;
-  if (!a.q_diag) {
-    // L = band_part(q_sqrt,-1,0); LTA = L^T A; ssq = sum LTA^2   (util.py:151-164)
-    if (!side) {
-      rc = transpose_q_sqrt(s, a, w);
-      if (rc) return rc;
-    }
-    rc = gpk_project((void*)s, w.Kfu, a.rows, a.m, w.ld, w.LqT, w.ld, a.P, w.ssq, w.proj, gpk_project_workspace_bytes(a.rows, a.m, a.P));
+  if (!side) {   // (in front of the tail, whose ticket it zeroes)
+    rc = transpose_q_sqrt_and_kl(s, a, w);
     if (rc) return rc;
   }
-  rc = varexp_to_out(s, a, w, &a.k.variance, 0);
-  if (rc || side) return rc;
-  return kl_white_to_out(s, a, w);
+  // s0 = sum_k A^2 (util.py:133), fmean = A^T q_mu (util.py:144), q_diag: ssq = sum (A q_sqrt)^2 (:149)
+  if (a.q_diag) {
+    rc = gpk_row_stats((void*)s, w.Kfu, a.rows, a.m, w.ld, a.q_mu, a.q_sqrt, a.P, 1.0, 0.0, w.s0, w.fmean, w.ssq);
+    if (rc) return rc;
+    return a.lik ? varexp_to_out(s, a, w, &a.k.variance, 0) : varexp_to_out(s, a, w, &a.k.variance, 0, w.ssq, 1, tail_ticket(w));
+  }
+  // L = band_part(q_sqrt,-1,0); LTA = L^T A; ssq = sum LTA^2   (util.py:151-164), s0 and fmean out of the same GEMM
+  rc = project_parts(s, w.Kfu, a.rows, a.m, w.ld, 0, w.LqT, w.ld, a.P, w.proj, gpk_project_workspace_bytes(a.rows, a.m, a.P), a.q_mu,
+                     w.s0, w.fmean);
+  if (rc) return rc;
+  return varexp_to_out(s, a, w, &a.k.variance, 0, w.proj, 2 * gpk_gemm_tiles_n(a.m), tail_ticket(w));
 }
 
 // ---- whiten = 0 (kullback_leiblers.py:98-165 with K = Kuu, conditionals/util.py:128-167 with white = False) on ONE
@@ -315,9 +350,11 @@ int elbo_unwhitened_full(hipStream_t s, const ElboArgs& a, const ElboWs& w) {
   if (rc) return rc;
   rc = gpk_transpose((void*)s, w.arow, P, m, w.ld, w.V, P, 0, 1, 0, 0);           // a = Lm^-1 q_mu as [m, P]
   if (rc) return rc;
-  rc = gpk_row_stats((void*)s, w.Kfu, a.rows, m, w.ld, w.V, nullptr, P, 1.0, 0.0, w.s0, w.fmean, nullptr);
+  // (s0 and fmean = A^T a out of the projection GEMM, as in the whitened form; the tail keeps its three launches -- this form has
+  //  no earlier kernel that zeroes a ticket, and part2 is in use)
+  rc = project_parts(s, w.Kfu, a.rows, m, w.ld, 0, w.LqT, w.ld, P, w.proj, gpk_project_workspace_bytes(a.rows, m, P), w.V, w.s0, w.fmean);
   if (rc) return rc;
-  rc = gpk_project((void*)s, w.Kfu, a.rows, m, w.ld, w.LqT, w.ld, P, w.ssq, w.proj, gpk_project_workspace_bytes(a.rows, m, P));
+  rc = gpk_launch_sum_parts(s, w.proj, 2 * gpk_gemm_tiles_n(m), a.rows, (long)2 * gpk_gemm_tiles_n(m) * a.rows, P, w.ssq);
   if (rc) return rc;
   rc = varexp_to_out(s, a, w, &a.k.variance, 0);
   if (rc) return rc;

@@ -534,7 +534,14 @@ int launch_pre64(hipStream_t s, const GemmArgs& a) {
 // slab, so the epilogue is store-only.
 // rev != 0: the K slabs are walked from the LAST to the first (same slabs, same per-slab arithmetic; the sum over slabs is
 // taken in the opposite order).  Used by the paired triangular-K launches: see gemm_nt_fast.
-template <int EPI>
+// SP = 1 (EPI 1; GemmArgs::stat_*): row statistics of A from the staging registers.  Between its global load and its LDS store a
+// thread holds A[srow + 32 q, 2 (t & 7) + {0, 1}] of a slab -- the 256 threads hold the slab exactly once -- so sum a^2 and
+// sum a V[k, p] cost 16 FMAs and two 8-byte loads of V per thread and slab, no pass over A of their own (row_stats_kernel: 134 MB,
+// 28 us in front of the headline projection).  Batch entry p is latent p: it takes column p of V, so the registers do not grow
+// with P (all latents in one workgroup: 67 spilled registers, the P = 4 projection 12 % slower).  The accumulation is
+// unconditional -- a branch inside the slab would cut the basic block the sched_group_barriers arrange -- and only a workgroup
+// whose K range is all of [0, k) (column tile 0) reduces the eight lanes of a row and stores.
+template <int EPI, int SP = 0>
 __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int tile_n, double* smem, int rev = 0, int bz_queue = -1) {
   constexpr int BM = 128, BN = 128;
   constexpr int BUF = (BM + BN) * LDSS;
@@ -586,6 +593,13 @@ __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int til
   }
   const int woff = srow * LDSS + scol;
   d2 st[8];
+  double ssq[4], smv[4], sv[2];
+  const char* vbase = nullptr;   // V[kb + scol, bz]
+  if constexpr (SP > 0) {
+    vbase = reinterpret_cast<const char*>(p.stat_V + (long)(kb + scol) * p.stat_P + bz);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { ssq[q] = 0.0; smv[q] = 0.0; }
+  }
   auto gload = [&](int s) {
     const long so = rev ? (long)(nk - 1 - s) : (long)s;
     const char* ab = abase + so * (BK * 8);
@@ -594,6 +608,23 @@ __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int til
     for (int q = 0; q < 4; ++q) st[q] = *reinterpret_cast<const d2*>(ab + oa[q]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) st[4 + q] = *reinterpret_cast<const d2*>(bb + ob[q]);
+    if constexpr (SP > 0) {
+      const char* vb = vbase + so * (BK * 8) * p.stat_P;
+      sv[0] = *reinterpret_cast<const double*>(vb);
+      sv[1] = *reinterpret_cast<const double*>(vb + p.stat_P * 8);
+    }
+  };
+  // the A half of the staged slab (st[0..3]) into the row statistics; called where that slab goes to LDS
+  auto stat_acc = [&]() {
+    if constexpr (SP > 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        ssq[q] = fma(st[q].x, st[q].x, ssq[q]);
+        ssq[q] = fma(st[q].y, st[q].y, ssq[q]);
+        smv[q] = fma(st[q].x, sv[0], smv[q]);
+        smv[q] = fma(st[q].y, sv[1], smv[q]);
+      }
+    }
   };
   auto lstore1 = [&](int buf, int q) {
     const int row = (q < 4) ? 32 * q : BM + 32 * (q - 4);
@@ -685,6 +716,7 @@ __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int til
   if (nk > 0) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) lstore1(0, q);
+    stat_acc();
     __syncthreads();
     fload(0, 0, 0);
   }
@@ -697,7 +729,7 @@ __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int til
     fload(cur, 1, 1);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { GPK_MFMA_ROW(0, i); }
-    if constexpr (MORE) __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);  // 8 global loads
+    if constexpr (MORE) __builtin_amdgcn_sched_group_barrier(0x020, 8 + 2 * SP, 0);  // 8 global loads (+ the V values of the row statistics)
     __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                      // 8 fragment reads
     __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);                     // 16 MFMA
     __builtin_amdgcn_sched_barrier(0);
@@ -713,6 +745,7 @@ __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int til
     if constexpr (MORE) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) lstore1(cur ^ 1, q);
+      stat_acc();
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) { GPK_MFMA_ROW(0, i); }
@@ -793,6 +826,24 @@ __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int til
       s += __shfl_xor(s, 32);
       if (lane_g == 0 && row < p.m) part[(long)(tile_n * 2 + wn) * p.part_ld + row] = s;
     }
+    if constexpr (SP > 0) {
+      if (tile_n == 0) {   // (kb = 0, ke = k there: gpk_gemm_fuses_row_stats)
+        // the eight lanes t & 7 of a row hold its 16 columns of every slab; a row lives in one wave
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+          for (int o = 1; o < 8; o <<= 1) {
+            ssq[q] += __shfl_xor(ssq[q], o);
+            smv[q] += __shfl_xor(smv[q], o);
+          }
+          const int row = m0 + srow + 32 * q;
+          if ((tid & 7) == 0 && row < p.m) {
+            if (bz == 0) p.stat_sumsq[row] = ssq[q];
+            p.stat_mv[(long)row * p.stat_P + bz] = smv[q];
+          }
+        }
+      }
+    }
   }
 }
 
@@ -803,7 +854,7 @@ __device__ __forceinline__ void fast_tile(const GemmArgs& p, int tile_m, int til
 // and the launch finishes together instead of waiting for the full-K tiles.
 // QUEUE (round 6, late): the queue form is its own instantiation -- with the queue loops and the static walk in ONE kernel it carried
 // three inlined copies of the tile, 25 000 instructions and 241 spilled registers.
-template <int EPI, bool PAIR, bool QUEUE = false>
+template <int EPI, bool PAIR, bool QUEUE = false, int SP = 0>
 __global__ __launch_bounds__(256, 2) void gemm_nt_fast(GemmArgs p, int gx, int gy, int total, int compact) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (p.sig_ptr && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0)   // entry signal (GemmArgs::sig_ptr)
@@ -863,7 +914,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_fast(GemmArgs p, int gx, int g
       } else {
         tile_order(t, p.b_tri, gx, gy, total, compact, tile_m, tile_n);
       }
-      fast_tile<EPI>(p, tile_m, tile_n, smem);
+      fast_tile<EPI, SP>(p, tile_m, tile_n, smem);
       if (t + (int)gridDim.x < total) __syncthreads();  // both LDS buffers are about to be refilled
     }
   } else {
@@ -875,7 +926,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_fast(GemmArgs p, int gx, int g
     // finish at the same slab), so a slab of A is fetched once per XCD and hit by the other seven.  (b_tri = 1 only.)
     const int align = (EPI == 1 && p.b_tri == 1) ? p.pair_k_align : 0;
     const int tile_m = blockIdx.x % gy, j = blockIdx.x / gy;
-    fast_tile<EPI>(p, tile_m, j, smem, align);
+    fast_tile<EPI, SP>(p, tile_m, j, smem, align);
     if (gx - 1 - j != j) {
       __syncthreads();  // both LDS buffers are about to be refilled
       fast_tile<EPI>(p, tile_m, gx - 1 - j, smem, 0);
@@ -909,16 +960,29 @@ int queue_slot(unsigned fetches, int** out, unsigned* base) {
   return 0;
 }
 
+constexpr size_t FAST_LDS_BYTES = 2 * (size_t)256 * LDSS * sizeof(double);
+// one instantiation of the static walk (PAIR or not; SP = 1: row statistics ride along, EPI 1)
+template <int EPI, bool PAIR, int SP>
+int launch_fast_kernel(hipStream_t s, dim3 grid, size_t lds_bytes, const GemmArgs& a, int gx, int gy, int total, int compact) {
+  // (function-local static: initialised once, thread-safe; unpaired capped launches ask for more than the tile needs, launch_fast)
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_fast<EPI, PAIR, false, SP>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, PAIR ? (int)FAST_LDS_BYTES : 160 * 1024);
+  GPK_HIP(attr);
+  hipLaunchKernelGGL((gemm_nt_fast<EPI, PAIR, false, SP>), grid, dim3(256), lds_bytes, s, a, gx, gy, total, compact);
+  GPK_LAUNCH_CHECK();
+  return 0;
+}
+template <int EPI, bool PAIR>
+int launch_fast_walk(hipStream_t s, dim3 grid, size_t lds_bytes, const GemmArgs& a, int gx, int gy, int total, int compact) {
+  if constexpr (EPI == 1) {
+    if (a.stat_sumsq) return launch_fast_kernel<1, PAIR, 1>(s, grid, lds_bytes, a, gx, gy, total, compact);
+  }
+  return launch_fast_kernel<EPI, PAIR, 0>(s, grid, lds_bytes, a, gx, gy, total, compact);
+}
+
 template <int EPI>
 int launch_fast(hipStream_t s, const GemmArgs& a) {
-  constexpr size_t LDS_BYTES = 2 * (size_t)256 * LDSS * sizeof(double);
-  // (function-local statics: initialised once, thread-safe)
-  static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_fast<EPI, false>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  // (capped launches ask for more, below)
-  static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_fast<EPI, true>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-  GPK_HIP(attr0);
-  GPK_HIP(attr1);
+  constexpr size_t LDS_BYTES = FAST_LDS_BYTES;
   const int gx = gpk_cdiv(a.n, 128), gy = gpk_cdiv(a.m, 128);
   if (gx <= 0 || gy <= 0) return 0;
   int total = gx * gy, compact = 0;
@@ -950,19 +1014,14 @@ int launch_fast(hipStream_t s, const GemmArgs& a) {
       b.stagger_first = 256;
       b.stagger_ticks = 0;
       g_last_kind = 2 + 2 * EPI;
-      hipLaunchKernelGGL((gemm_nt_fast<EPI, false>), dim3((unsigned)total, nb, 1), dim3(256), LDS_BYTES, s, b, gx, gy, total, compact);
-      GPK_LAUNCH_CHECK();
-      return 0;
+      return launch_fast_walk<EPI, false>(s, dim3((unsigned)total, nb, 1), LDS_BYTES, b, gx, gy, total, compact);
     }
     if (pair_ok && gx >= 4 && a.b_tri_rows >= a.n) {
       total = ((gx + 1) / 2) * gy;
       g_last_kind = 2 + 2 * EPI + 1;
       GemmArgs ap = a;
       ap.pair_k_align = GPK_TUNE(PAIR_K_ALIGN, 1);
-      hipLaunchKernelGGL((gemm_nt_fast<EPI, true>), dim3((unsigned)total, nb, 1), dim3(256), LDS_BYTES, s, ap, gx, gy,
-                         total, compact);
-      GPK_LAUNCH_CHECK();
-      return 0;
+      return launch_fast_walk<EPI, true>(s, dim3((unsigned)total, nb, 1), LDS_BYTES, ap, gx, gy, total, compact);
     }
   }
   int tail_tiles = 0;
@@ -1021,9 +1080,8 @@ int launch_fast(hipStream_t s, const GemmArgs& a) {
     GPK_LAUNCH_CHECK();
     return 0;
   }
-  hipLaunchKernelGGL((gemm_nt_fast<EPI, false>), dim3(nwg, nb, 1), dim3(256), lds_bytes, s, b, gx, gy, total,
-                     compact);
-  GPK_LAUNCH_CHECK();
+  const int rcw = launch_fast_walk<EPI, false>(s, dim3(nwg, nb, 1), lds_bytes, b, gx, gy, total, compact);
+  if (rcw) return rcw;
   if (tail_tiles > 0) {
     using Cfg = TileCfg<64, 64, 4, 1>;
     static const hipError_t attrt = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<64, 64, 4, 1>),
@@ -1766,7 +1824,24 @@ int gpk_launch_gemm(hipStream_t s, const GemmArgs& a) {
   return rc;
 }
 
+// under-filled projections leave gemm_nt_fast for the generic kernel's small tiles (launch_select)
+static bool proj_small_tiles(const GemmArgs& a) {
+  if (!(a.epi == 1 && a.b_tri == 1 && !(a.beta != 0.0 && a.C) && a.m > 64)) return false;
+  const long pairs = (long)((gpk_cdiv(a.n, 128) + 1) / 2) * gpk_cdiv(a.m, 128) * (a.batch > 0 ? a.batch : 1);
+  return pairs < GPK_TUNE(PROJ_SMALL_TILE_BELOW, 200);
+}
+
+// Row statistics ride along (GemmArgs::stat_*) where launch_select ends in launch_fast<1> AND the workgroup of column tile 0 walks
+// the whole K range: no K split, no structure in A, B dense or upper-triangular from column 0.
+bool gpk_gemm_fuses_row_stats(const GemmArgs& a) {
+  if (a.epi != 1 || !a.stat_sumsq || !a.stat_mv || !a.stat_V || a.stat_P < 1 || a.stat_P > 4) return false;
+  if (a.m <= 0 || a.n <= 0 || a.k_off_step || a.a_tri || a.b_tri == 2 || (a.b_tri == 1 && a.b_tri_off != 0)) return false;
+  if ((a.beta != 0.0 && a.C) || a.batch != a.stat_P || (a.batch > 1 && a.strideA != 0)) return false;   // (batch entry p = latent p of one shared A)
+  return !proj_small_tiles(a) && fast_ok(a);
+}
+
 static int launch_select(hipStream_t s, const GemmArgs& a) {
+  if (a.stat_sumsq && !gpk_gemm_fuses_row_stats(a)) return GPK_E_UNSUPPORTED;   // (the caller asks first: drivers.hip, project_parts)
   const long tiles = (long)gpk_cdiv(a.m, 128) * gpk_cdiv(a.n, 128) * (a.batch > 0 ? a.batch : 1);
   if (a.tile64 && a.epi == 0) {
     if (GPK_TUNE(REST_PRE64, 1) && pre64_ok(a)) return launch_pre64(s, a);
@@ -1781,7 +1856,7 @@ static int launch_select(hipStream_t s, const GemmArgs& a) {
     const long eff = a.c_lower ? tiles / 2 : tiles;
     if (eff < GPK_TUNE(HALF_TILE_BELOW, 300)) return launch_cfg<64, 128, 1, 4>(s, a);
   }
-  if (a.epi == 1 && a.b_tri == 1 && !(a.beta != 0.0 && a.C) && a.m > 64) {
+  if (proj_small_tiles(a)) {
     // under-filled projections (a rank's 1024-row shard of a strong-scaled step: 8 row tiles x 8 column pairs = 64
     // workgroups, ONE of them per four CUs, 296 us for 4.3 GFLOP; a CU cannot finish a 128 x 128 x 16 slab in less than
     // 1.7 us however many workgroups it holds): 64 x 64 tiles, unpaired -- sixteen times the workgroups.
@@ -1789,17 +1864,15 @@ static int launch_select(hipStream_t s, const GemmArgs& a) {
     // 1024 x 2048: 296 / 194 / 155 us, 300 x 1024 (P = 2): 162 / 98 / 62 us, 2048 x 2048: 306 / 268 / 221 us; from 256 pairs
     // on the paired 128-row tiles win (4096 x 2048: 327 us against 483 us on 64 x 128).
     const long pairs = (long)((gpk_cdiv(a.n, 128) + 1) / 2) * gpk_cdiv(a.m, 128) * (a.batch > 0 ? a.batch : 1);
-    if (pairs < GPK_TUNE(PROJ_SMALL_TILE_BELOW, 200)) {
-      // (every 64-column partial slot the reduction reads must be written: 64-wide tiles only if they cover the same
-      // slots as the 128-wide ones, else 64 x 128 tiles)
-      GemmArgs b = a;
-      b.tile_snake = GPK_TUNE(PROJ_SNAKE, 1);
-      if (gpk_cdiv(a.n, 64) == 2 * gpk_cdiv(a.n, 128)) {
-        if (pairs < GPK_TUNE(PROJ_TILE32_BELOW, 100)) return launch_cfg<32, 64, 2, 2>(s, b);
-        return launch_cfg<64, 64, 4, 1>(s, b);
-      }
-      return launch_cfg<64, 128, 2, 2>(s, b);
+    // (every 64-column partial slot the reduction reads must be written: 64-wide tiles only if they cover the same
+    // slots as the 128-wide ones, else 64 x 128 tiles)
+    GemmArgs b = a;
+    b.tile_snake = GPK_TUNE(PROJ_SNAKE, 1);
+    if (gpk_cdiv(a.n, 64) == 2 * gpk_cdiv(a.n, 128)) {
+      if (pairs < GPK_TUNE(PROJ_TILE32_BELOW, 100)) return launch_cfg<32, 64, 2, 2>(s, b);
+      return launch_cfg<64, 64, 4, 1>(s, b);
     }
+    return launch_cfg<64, 128, 2, 2>(s, b);
   }
   if (fast_ok(a) && (a.epi == 1 || (a.n > 64 && (tiles >= 24 || a.m <= 64)))) {
     return a.epi == 1 ? launch_fast<1>(s, a) : launch_fast<0>(s, a);

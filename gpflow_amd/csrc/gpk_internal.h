@@ -76,6 +76,11 @@ struct GemmArgs {
   int sq_cols;
   double* part; long part_ld; long stridePart;   // [2*tiles_n, m]
   double* C2; long ldc2; long strideC2; int c2_cols;
+  // epilogue 1 on gemm_nt_fast only (ask gpk_gemm_fuses_row_stats): the row statistics of A ride along.  The workgroup of column
+  // tile 0 walks all of [0, k) with its A slabs staged in registers; it also forms  stat_sumsq[r] = sum_k A[r,k]^2  and
+  // stat_mv[r, p] = sum_k A[r,k] stat_V[k, p]  (stat_V [k, stat_P] row-major, stat_P = batch <= 4) and writes them itself: one wave per
+  // row, fixed order, no atomics.  The batch shares A (strideA = 0): entry p forms column p of stat_mv, entry 0 stat_sumsq as well.
+  double* stat_sumsq; double* stat_mv; const double* stat_V; int stat_P;
   int batch;
   int stagger_first;  // fast path only: number of CUs the launch stream may use (first workgroup of the 2nd resident set), 0 = 256
   int stagger_ticks;  // fast path only: start delay (100 MHz ticks) of the second resident workgroup set, 0 = none
@@ -113,6 +118,7 @@ static inline GemmArgs gemm_base(int m, int n, int k, double alpha, const double
 }
 int gpk_launch_gemm(hipStream_t s, const GemmArgs& a);
 bool gpk_gemm_takes_latency_kernel(const GemmArgs& a);   // the launch would run on the one-shot latency kernel (sig / wait honoured)
+bool gpk_gemm_fuses_row_stats(const GemmArgs& a);        // an epi 1 launch with stat_* set would run on gemm_nt_fast and fill them (else: GPK_E_UNSUPPORTED)
 
 // fused in-group solve of `rows` right-hand-side rows against nb <= 4 leaf blocks of the factor (gemm.hip); E / Eo point at
 // the group's first column, Lgg at L[c0, c0], X at the group's first block inverse
@@ -179,8 +185,15 @@ int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* pa
                                         int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
                                         const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
                                         double* rows_out, double* dmu_out, double* dvar_out, double* part, double* part1, int* count);
+// the Gaussian tail of a shard in ONE launch: ssq[p,b] = sum of the nt slot partials slot[p][t][b] in slot order, the variational
+// expectations exactly as gpk_launch_varexp_stage1 forms them, one partial per block, and the LAST block to finish (ticket counter)
+// sums the partials in index order into out[0].  *ticket must be 0 at entry and is left at the block count.
+int gpk_launch_varexp_tail(hipStream_t s, const double* Y, long ldy, const double* fmean, int rows, int P, const double* s0,
+                           const double* slot, int nt, long strideSlot, double knn, double noise, double mean_const,
+                           const double* noise_rows, double* part, int* ticket, double* out);
+// zero_word (may be null): an int the kernel sets to 0 -- the ticket of a gpk_launch_varexp_tail that is stream-ordered behind it
 int gpk_launch_kl_white_stage1(hipStream_t s, const double* q_mu, const double* q_sqrt, int m, int P,
-                               int q_diag, double* part, int* count);
+                               int q_diag, double* part, int* count, int* zero_word = nullptr);
 int gpk_launch_kl_unwhite_diag_stage1(hipStream_t s, const double* LinvT, long ldl, int m, const double* W, int P, double* part,
                                       int* count);
 int gpk_launch_sum_log_diag_sq(hipStream_t s, const double* L, int n, long ldl, int batch, long strideL, double* out);

@@ -248,9 +248,21 @@ struct VarexpArgs {
   double knn[16]; int knn_per_latent;
   double noise, mean_const; double* fvar_out; double* part;
   const double* noise_rows;   // per-row noise variances [rows] (heteroskedastic Gaussian, scalar_continuous.py:92-111) or nullptr
+  // TAIL only: ssq arrives as nt slot partials [P][nt][rows] (strideSlot between latents); ticket / out: see varexp_kernel
+  const double* slot; int nt; long strideSlot; int* ticket; double* out;
 };
+// TAIL = false: stage 1 of the two-stage reduction (one partial per block).
+// TAIL = true: the whole tail of a shard behind the projection GEMM in one launch -- what sum_parts_kernel, this kernel and
+// final_sum_kernel did as three dependent launches of 5 - 10 us each.  The slot partials of an element are summed in slot order
+// (sum_parts_kernel's bits), their loads issued sixteen at a time: one element per thread with a load per add was 38 us for
+// 8192 x 32 partials on eight blocks.  So the grid is one element per thread here (gpk_launch_varexp_tail), not four.  The block
+// that draws the last ticket sums the block partials in index order, as final_sum_kernel does.  The ticket word must be 0 at entry: no memset packet, and not a
+// reset by the last block either (the first call on a fresh workspace has to be right) -- kl_white_kernel, which every whitened
+// shard runs earlier in the same step on a stream that is joined before this launch, zeroes it (drivers.hip: kl_white_to_out).
+template <bool TAIL>
 __global__ __launch_bounds__(RB) void varexp_kernel(VarexpArgs a) {
   __shared__ double sh[4];
+  __shared__ int s_last;
   const double log2pi = 1.8378770664093453;
   const double c0 = -0.5 * log2pi - 0.5 * log(a.noise);
   double acc = 0.0;
@@ -259,7 +271,20 @@ __global__ __launch_bounds__(RB) void varexp_kernel(VarexpArgs a) {
     const int b = (int)(e / a.P), p = (int)(e - (long)b * a.P);
     double fv = a.knn[a.knn_per_latent ? p : 0];
     if (a.s0) fv -= a.s0_per_latent ? a.s0[(long)p * a.rows + b] : a.s0[b];
-    if (a.ssq) fv += a.ssq[(long)p * a.rows + b];
+    if constexpr (TAIL) {
+      const double* q = a.slot + (long)p * a.strideSlot + b;
+      double s = 0.0;
+      int t = 0;
+      for (; t + 16 <= a.nt; t += 16) {
+        double v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = q[(long)(t + i) * a.rows];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s += v[i];
+      }
+      for (; t < a.nt; ++t) s += q[(long)t * a.rows];
+      fv += s;
+    } else if (a.ssq) fv += a.ssq[(long)p * a.rows + b];
     const double mu = a.fmean[e] + a.mean_const;
     const double dy = a.Y[(long)b * a.ldy + p] - mu;
     if (a.fvar_out) a.fvar_out[e] = fv;
@@ -272,6 +297,19 @@ __global__ __launch_bounds__(RB) void varexp_kernel(VarexpArgs a) {
   }
   const double r = block_sum(acc, sh);
   if (threadIdx.x == 0) a.part[blockIdx.x] = r;
+  if constexpr (TAIL) {
+    if (threadIdx.x == 0) {
+      __threadfence();   // the partial is visible device-wide before the ticket is
+      s_last = atomicAdd(a.ticket, 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();     // every other block's partial was released before its ticket
+    double v = 0.0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += RB) v += __hip_atomic_load(a.part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double t = block_sum(v, sh);
+    if (threadIdx.x == 0) *a.out = 0.0 + 1.0 * t;   // (final_sum_kernel's add + scale * sum)
+  }
 }
 
 // ---- non-Gaussian variational expectations, stage 1 (likelihoods/base.py: ScalarLikelihood through NDiagGHQuadrature,
@@ -400,8 +438,10 @@ __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
 
 // ---- whitened KL, stage 1: sum q_mu^2 - sum log diag^2 + sum tril^2 -----------------------------------
 __global__ __launch_bounds__(RB) void kl_white_kernel(const double* q_mu, const double* q_sqrt, int m,
-                                                      int P, int q_diag, double* part) {
+                                                      int P, int q_diag, double* part, int* zero_word) {
   __shared__ double sh[4];
+  // (the ticket of the shard's varexp_kernel<true>, stream-ordered behind this kernel)
+  if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0;
   double acc = 0.0;
   const long nmu = (long)m * P;
   const long stride = (long)gridDim.x * RB, start = (long)blockIdx.x * RB + threadIdx.x;
@@ -699,7 +739,7 @@ extern "C" int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, 
   a.knn_per_latent = knn_per_latent; a.noise = noise_variance; a.mean_const = mean_const;
   a.fvar_out = fvar_out; a.part = (double*)ws; a.noise_rows = noise_rows;
   const int nb = nblocks_for((long)rows * P);
-  hipLaunchKernelGGL(varexp_kernel, dim3(nb), dim3(RB), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(varexp_kernel<false>, dim3(nb), dim3(RB), 0, (hipStream_t)stream, a);
   GPK_LAUNCH_CHECK();
   FinalArgs f{};
   f.nterms = 1; f.part[0] = a.part; f.count[0] = nb; f.scale[0] = 1.0; f.add = 0.0; f.out = out;
@@ -787,7 +827,7 @@ extern "C" int gpk_gauss_kl_white(void* stream, const double* q_mu, const double
   const int nb = nblocks_for(elems);
   double* part = (double*)ws;
   hipLaunchKernelGGL(kl_white_kernel, dim3(nb), dim3(RB), 0, (hipStream_t)stream, q_mu, q_sqrt, m, P,
-                     q_diag, part);
+                     q_diag, part, (int*)nullptr);
   GPK_LAUNCH_CHECK();
   FinalArgs f{};
   f.nterms = 1; f.part[0] = part; f.count[0] = nb; f.scale[0] = 0.5;
@@ -892,16 +932,31 @@ int gpk_launch_varexp_stage1(hipStream_t s, const double* Y, long ldy, const dou
   a.knn_per_latent = knn_per_latent; a.noise = noise; a.mean_const = mean_const;
   a.fvar_out = fvar_out; a.part = part; a.noise_rows = noise_rows;
   const int nb = nblocks_for((long)rows * P);
-  hipLaunchKernelGGL(varexp_kernel, dim3(nb), dim3(RB), 0, s, a);
+  hipLaunchKernelGGL(varexp_kernel<false>, dim3(nb), dim3(RB), 0, s, a);
   GPK_LAUNCH_CHECK();
   *count = nb;
   return 0;
 }
+int gpk_launch_varexp_tail(hipStream_t s, const double* Y, long ldy, const double* fmean, int rows, int P, const double* s0,
+                           const double* slot, int nt, long strideSlot, double knn, double noise, double mean_const,
+                           const double* noise_rows, double* part, int* ticket, double* out) {
+  if (!slot || !part || !ticket || !out || nt < 0) return GPK_E_ARG;
+  VarexpArgs a{};
+  a.Y = Y; a.ldy = ldy; a.fmean = fmean; a.rows = rows; a.P = P;
+  a.s0 = s0; a.knn[0] = knn; a.noise = noise; a.mean_const = mean_const;
+  a.part = part; a.noise_rows = noise_rows;
+  a.slot = slot; a.nt = nt; a.strideSlot = strideSlot; a.ticket = ticket; a.out = out;
+  long nb = ((long)rows * P + RB - 1) / RB;
+  nb = nb < 1 ? 1 : (nb > MAXPART ? MAXPART : nb);
+  hipLaunchKernelGGL(varexp_kernel<true>, dim3((unsigned)nb), dim3(RB), 0, s, a);
+  GPK_LAUNCH_CHECK();
+  return 0;
+}
 int gpk_launch_kl_white_stage1(hipStream_t s, const double* q_mu, const double* q_sqrt, int m, int P,
-                               int q_diag, double* part, int* count) {
+                               int q_diag, double* part, int* count, int* zero_word) {
   const long elems = q_diag ? (long)m * P : (long)P * m * m;
   const int nb = nblocks_for(elems);
-  hipLaunchKernelGGL(kl_white_kernel, dim3(nb), dim3(RB), 0, s, q_mu, q_sqrt, m, P, q_diag, part);
+  hipLaunchKernelGGL(kl_white_kernel, dim3(nb), dim3(RB), 0, s, q_mu, q_sqrt, m, P, q_diag, part, zero_word);
   GPK_LAUNCH_CHECK();
   *count = nb;
   return 0;

@@ -404,6 +404,29 @@ def project(At: torch.Tensor, LqT: torch.Tensor) -> torch.Tensor:
     return ssq
 
 
+def project_stats(At: torch.Tensor, LqT: torch.Tensor, V: torch.Tensor):
+    """(s0 [rows], fmean [rows, P] = At V, ssq [P, rows]): `project` and the row statistics of the same At [rows, m] in one
+    driver call, as the fused SVGP step takes them (gpk_project_stats)."""
+    lib = _lib.load()
+    _chk(At, "At", 2)
+    _chk(LqT, "LqT", 3)
+    _chk(V, "V", 2)
+    rows, m = At.shape
+    P = LqT.shape[0]
+    if LqT.shape[1] != m or LqT.shape[2] != m or not LqT.is_contiguous():
+        raise ValueError("LqT must be contiguous [P, m, m]")
+    if V.shape != (m, P) or not V.is_contiguous():
+        raise ValueError("V must be contiguous [m, P]")
+    s0 = torch.empty(rows, dtype=torch.float64, device=At.device)
+    fmean = torch.empty((rows, P), dtype=torch.float64, device=At.device)
+    ssq = torch.empty((P, rows), dtype=torch.float64, device=At.device)
+    ws = _ws(int(lib.gpk_project_workspace_bytes(rows, m, P)))
+    rc = lib.gpk_project_stats(_stream(), At.data_ptr(), rows, m, _rowmajor(At, "At"), LqT.data_ptr(), m, P, V.data_ptr(),
+                               s0.data_ptr(), fmean.data_ptr(), ssq.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+    _lib.check(rc, "gpk_project_stats")
+    return s0, fmean, ssq
+
+
 def gaussian_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[torch.Tensor],
                         ssq: Optional[torch.Tensor], knn: Sequence[float], noise_variance,
                         mean_const: float = 0.0, s0_per_latent: bool = False, want_fvar: bool = False):

@@ -213,6 +213,12 @@ int gpk_project(void* stream, const double* At, int rows, int m, long ldat, cons
  * conditional (util.py:566-629), whose tf.map_fn over the P problems becomes ONE launch over the batched trapezoid. */
 int gpk_project_batched(void* stream, const double* At, int rows, int m, long ldat, long strideAt,
                         const double* LqT, long ldl, int P, double* ssq, void* ws, size_t ws_bytes);
+/* gpk_project together with the row statistics of the same At, as the fused SVGP drivers take them:
+ *   s0[b] = sum_k At[b,k]^2,  fmean[b,p] = sum_k At[b,k] V[k,p]   (V [m,P] row-major)
+ * Where the projection runs on its 128 x 128 tile and P <= 4 they come out of the GEMM itself -- no second pass over At;
+ * otherwise from gpk_row_stats.  Deterministic either way: two calls on the same inputs give the same bits. */
+int gpk_project_stats(void* stream, const double* At, int rows, int m, long ldat, const double* LqT, long ldl, int P,
+                      const double* V, double* s0, double* fmean, double* ssq, void* ws, size_t ws_bytes);
 
 /* ---- scalar tails (deterministic two-stage reductions) ---------------------------------------------
  * Gaussian variational expectations summed over rows and outputs
