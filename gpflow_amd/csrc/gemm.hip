@@ -1593,7 +1593,7 @@ int launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo, lon
   if (rows <= 0) return 0;
   if (j1 < 0) j1 = nb;
   if (j0 < 0 || j0 >= j1 || j1 > nb) return GPK_E_ARG;
-  if ((j0 > 0 || j1 < nb) && (E != Eo || lde != ldeo || strideE != strideEo || !GPK_TUNE(GROUP_SOLVE_V2, 1))) return GPK_E_UNSUPPORTED;
+  if ((j0 > 0 || j1 < nb) && (E != Eo || lde != ldeo || strideE != strideEo || !gpk_group_solve_takes_parts())) return GPK_E_UNSUPPORTED;
   if (batch < 1) batch = 1;
   if (!E || !Eo || !Lgg || !X || nb < 1 || nb > 4) return GPK_E_ARG;
   if ((ldl & 1) || (reinterpret_cast<uintptr_t>(Lgg) & 15) || (reinterpret_cast<uintptr_t>(X) & 15)) return GPK_E_UNSUPPORTED;
@@ -1684,6 +1684,8 @@ int gpk_launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo,
                            int j0, int j1) {
   return launch_group_solve(s, E, lde, Eo, ldeo, rows, Lgg, ldl, X, nb, batch, strideE, strideEo, strideL, strideX, max_wgs, j0, j1);
 }
+// (only the pipelined kernel, group_solve2, solves blocks [j0, j1) of a group and hands the later blocks back updated)
+bool gpk_group_solve_takes_parts() { return GPK_TUNE(GROUP_SOLVE_V2, 1) != 0; }
 
 // ---- optional per-launch timing (bench.py roofline leg): HIP events around every GEMM launch, on the
 // stream the kernel is launched on.  Off by default; adds two event records per launch when on. -------

@@ -11,31 +11,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 #include <stdio.h>
 #include <stdlib.h>
-
-// Tunables.  The PRODUCT build (libgpk.so) has none at run time: every GPK_TUNE is its compile-time default and the
-// library never reads the environment.  Only the A/B build (`make exp` -> libgpk_exp.so, -DGPK_EXPERIMENTAL, used by
-// tools/ab*.sh on the GPU box and never loaded by the package unless GPK_LIBRARY points at it) reads GPK_<NAME> once.
-#ifdef GPK_EXPERIMENTAL
-#define GPK_TUNE(name, def)                                                                      \
-  ([]() -> int {                                                                                 \
-    static const int v__ = getenv("GPK_" #name) ? atoi(getenv("GPK_" #name)) : (int)(def);       \
-    return v__;                                                                                  \
-  }())
-#define GPK_TRACE(...)                                        \
-  do {                                                        \
-    if (GPK_TUNE(DEBUG, 0)) fprintf(stderr, "[gpk] " __VA_ARGS__); \
-  } while (0)
-#else
-#define GPK_TUNE(name, def) ((int)(def))
-#define GPK_TRACE(...) do { } while (0)
-#endif
-
-// kGpkExp: host branches that only exist in the A/B build are constant-folded away in the product library.
-#ifdef GPK_EXPERIMENTAL
-constexpr bool kGpkExp = true;
-#else
-constexpr bool kGpkExp = false;
-#endif
+#include "gpk_tune.h"   // GPK_TUNE, GPK_TRACE, kGpkExp
 
 #define GPK_HIP(call)                                                                                   \
   do {                                                                                                  \
@@ -44,6 +20,12 @@ constexpr bool kGpkExp = false;
       GPK_TRACE("%s:%d: %s -> %d\n", __FILE__, __LINE__, #call, (int)e__);                              \
       return (int)e__;                                                                                  \
     }                                                                                                   \
+  } while (0)
+// (a library call that returns 0 or an error code)
+#define GPK_TRY(call)                 \
+  do {                                \
+    const int rc__ = (call);          \
+    if (rc__) return rc__;            \
   } while (0)
 #define GPK_LAUNCH_CHECK()                                                                              \
   do {                                                                                                  \
@@ -126,6 +108,7 @@ bool gpk_gemm_fuses_row_stats(const GemmArgs& a);        // an epi 1 launch with
 int gpk_launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo, long ldeo, int rows, const double* Lgg, long ldl,
                            const double* X, int nb, int batch = 1, long strideE = 0, long strideEo = 0, long strideL = 0,
                            long strideX = 0, int max_wgs = 0, int j0 = 0, int j1 = -1);   // max_wgs > 0: at most that many workgroups, walking the 16-row slivers
+bool gpk_group_solve_takes_parts();   // a partial in-group solve (j0 > 0 or j1 < nb) exists: the progressive first group of potrf.hip asks
 int gpk_gemm_tiles_n(int n);   // number of column tiles the launcher will use for n columns
 int gpk_profile_gemm_is_on();  // per-launch event timing active (bench roofline leg)
 

@@ -11,24 +11,26 @@
 // For n < 4096 (the SVGP sizes) the outer panel IS one 128-column block: the factorisation is a latency chain
 // leaf -> panel solve -> strip, and everything that is not on that chain (the solve of the minibatch rows) runs beside it
 // as bulk work on a stream of its own.
+//
+// How the scheduler is laid out (gpk_potrf_core is an outline over these):
+//   potrf_plan.h   WHAT to do: make_potrf_plan() turns (n, extra, batch, tri) and two device facts into the schedule as data -- panel
+//                  cuts, wide / narrow panels, ride or extra-row stream, group ends, tail zone, progressive first group, the regime of
+//                  each rest-update, which hand-off may be a flag word, streams by role.  No HIP header; every threshold and the A/B
+//                  measurement behind it is there; tested without a device (tests/test_potrf_plan.py).
+//   ChainSync      HOW streams hand over: flag word (written on a kernel's entry or by a set-flag kernel), gate kernel or stream wait,
+//                  event recorded only on demand.
+//   PotrfRun       the enqueue calls: enqueue_chain / enqueue_rest_update / enqueue_extra_rows per panel.  The three predicates that
+//                  depend on the operands are applied there (and once in gpk_potrf_core, for the progressive group), ANDed with the
+//                  plan's *_candidate fields.
 #include "gpk_internal.h"
+#include "potrf_plan.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
 
 namespace {
-constexpr int NB = GPK_NB;
-constexpr int NBO = 512;  // column group of the right-looking row solves (extra rows, gpk_trsm)
-
-// how a bulk GEMM beside the latency chain is launched
-struct Bulk {
-  int cap = 0;    // cap on the persistent workgroups of the big (K >= 256) updates, 0 = one workgroup per tile
-  int group_cap = 0;   // cap on the workgroups of the fused in-group solve, 0 = one per 16-row sliver
-  int kmin = 256;      // updates with K below this are not capped
-  void apply(GemmArgs& g) const {
-    if (cap > 0 && g.k >= kmin) g.max_wgs = cap;
-  }
-};
+constexpr int NB = kPotrfNB;
+constexpr int NBO = kPotrfNBO;   // column group of the right-looking row solves (extra rows, gpk_trsm)
 }  // namespace
 
 extern "C" const char* gpk_version(void) {
@@ -55,7 +57,7 @@ extern "C" size_t gpk_invd_elems(int n, int batch) {
 //   Bs  rest-updates of SMALL factorisations and of the single-leaf panels at the end of large ones (they are ON the
 //       critical path there): all CUs.  (Rounds 1-2 ran that end of a large factorisation with wide panels and a second
 //       masked stream over half the CUs; round 3 measured every hand-off from that stream to P at ~55 us while both are
-//       busy -- their hardware queues share a microengine pipe -- and replaced it: potrf_core, "Panel boundaries".)
+//       busy -- their hardware queues share a microengine pipe -- and replaced it: potrf_plan.h, "Panel boundaries".)
 //   X   bulk stream of small factorisations: the right-looking solve of the extra rows (the SVGP minibatch).  Unmasked:
 //       CU-masked queues dispatch its short kernels slowly and quantise its big updates badly (profiles/r03_*).
 // One std::recursive_mutex per device serialises the ENQUEUE of factorisations (shared streams, event pool); the
@@ -74,13 +76,12 @@ struct Aux {
   double check_us[3] = {0, 0, 0}, check_first_us[3] = {0, 0, 0};
   int recreated = 0;
   hipStream_t shift = nullptr;   // (kept alive: the extra stream that moved the re-created set onto other hardware queues)
-  // packet-free hand-offs of the latency chain (potrf_core, "chain flags"): one word per panel for "panel solved" (F) and for
+  // packet-free hand-offs of the latency chain (ChainSync, "Chain flags"): one word per panel for "panel solved" (F) and for
   // "rest-update done" (R), written with the epoch of the factorisation that owns them (monotonic per device)
   int* flags = nullptr;
   int epoch = 0;
   int concurrent = -1;   // 1: kernels of two streams were seen running at the same time (init-time probe); 0: serialised by a tool
 };
-constexpr int kMaxFlagPanels = 512;
 Aux g_aux[16];
 
 int masked_stream(hipStream_t* out, int ncu, int first, int last) {  // CUs [first, last)
@@ -113,7 +114,7 @@ int aux_create(Aux& a, int dev) {
   GPK_HIP(hipStreamCreateWithFlags(&a.X, hipStreamNonBlocking));
   GPK_HIP(hipStreamCreateWithFlags(&a.pad, hipStreamNonBlocking));
   GPK_HIP(hipStreamCreateWithFlags(&a.Bs, hipStreamNonBlocking));
-  int reserved = GPK_TUNE(RESERVED_CUS, 32);   // (8 until round 6: see the tile queue of the trailing updates, potrf_core)
+  int reserved = GPK_TUNE(RESERVED_CUS, 32);   // (8 until round 6: see the tile queue of the trailing updates, potrf_plan.h)
   if (ncu > 1024 || reserved < 0 || reserved >= ncu) reserved = 0;
   int rc = masked_stream(&a.B, ncu, reserved, ncu);
   if (rc) return rc;
@@ -179,7 +180,7 @@ int concurrent_us(hipStream_t* st, int ns, double* us) {
 }
 
 // (caller holds a.mu)
-int aux_get(int dev, int need, Aux** out) {
+int aux_get(int dev, Aux** out) {
   Aux& a = g_aux[dev];
   if (!a.ready) {
     if (a.init_rc) return a.init_rc;
@@ -236,21 +237,25 @@ int aux_get(int dev, int need, Aux** out) {
     const int rcp = gpk_probe_concurrent_kernels(a.X, a.P, a.flags, &conc);
     a.concurrent = (rcp == 0 && conc) ? 1 : 0;
   }
-  if (a.nev < need) {
-    hipEvent_t* n = (hipEvent_t*)realloc(a.ev, sizeof(hipEvent_t) * need);
-    if (!n) return GPK_E_ARG;
-    a.ev = n;
-    // The events only order streams of ONE device against each other (never inspected from the host), so they carry no
-    // system-scope fence: the producing kernels' own release at the end of their dispatch makes the data visible to the
-    // device.  Round 3, same box: chain of n = 2048 alone 0.98 -> 0.925 ms, SVGP step 2.085 -> 2.063 ms, GPR N = 16384
-    // 32.75 -> 32.45 ms, the 1024-row rank shard 1.447 -> 1.388 ms, all bit-identical (profiles/r03_ab_svgp_schedules.log).
-    // (Round 1 had measured this flag slower on a different schedule: 283 vs 308 steps/s.)
-    for (int i = a.nev; i < need; ++i) {
-      GPK_HIP(hipEventCreateWithFlags(&a.ev[i], hipEventDisableTiming | (GPK_TUNE(EV_NOFENCE, 1) ? hipEventDisableSystemFence : 0)));
-      a.nev = i + 1;
-    }
-  }
   *out = &a;
+  return 0;
+}
+
+// grow the event pool to `need` (caller holds a.mu)
+int aux_reserve_events(Aux& a, int need) {
+  if (a.nev >= need) return 0;
+  hipEvent_t* n = (hipEvent_t*)realloc(a.ev, sizeof(hipEvent_t) * need);
+  if (!n) return GPK_E_ARG;
+  a.ev = n;
+  // The events only order streams of ONE device against each other (never inspected from the host), so they carry no
+  // system-scope fence: the producing kernels' own release at the end of their dispatch makes the data visible to the
+  // device.  Round 3, same box: chain of n = 2048 alone 0.98 -> 0.925 ms, SVGP step 2.085 -> 2.063 ms, GPR N = 16384
+  // 32.75 -> 32.45 ms, the 1024-row rank shard 1.447 -> 1.388 ms, all bit-identical (profiles/r03_ab_svgp_schedules.log).
+  // (Round 1 had measured this flag slower on a different schedule: 283 vs 308 steps/s.)
+  for (int i = a.nev; i < need; ++i) {
+    GPK_HIP(hipEventCreateWithFlags(&a.ev[i], hipEventDisableTiming | (GPK_TUNE(EV_NOFENCE, 1) ? hipEventDisableSystemFence : 0)));
+    a.nev = i + 1;
+  }
   return 0;
 }
 
@@ -311,7 +316,7 @@ bool group_solve_fused_ok(int nbk, int c0, int c1, int rows, const double* L, lo
          !(reinterpret_cast<uintptr_t>(invd + (long)(c0 / NB) * NB * NB) & 15) && GPK_TUNE(GROUP_FUSED, 1);
 }
 
-int solve_group_fwd(hipStream_t s, const Bulk& bulk, double* E, long lde, double* Eo, long ldeo, int rows, const double* L,
+int solve_group_fwd(hipStream_t s, const PotrfBulk& bulk, double* E, long lde, double* Eo, long ldeo, int rows, const double* L,
                     long ldl, const double* invd, long strideInv, int n, int c0, int c1, int batch, long strideE,
                     long strideEo, long strideL, int part_j0 = -1, int part_cap = 0) {
   int rc;
@@ -400,12 +405,289 @@ int solve_group_bwd(hipStream_t s, double* Bm, long ldb, int rows, const double*
 }
 }  // namespace
 
+// ---- how the streams of one factorisation hand over to each other -------------------------------------------------------------
+// Chain flags (round 5).  Between two kernels of the panel stream an event record costs 4.6 us and an event wait 6.3 us of
+// queue-packet processing (rocprofv3 timelines, profiles/r05_rows1024_events_timeline.txt, r05_ab_chain_flags.log); two kernels back to back start
+// 0.3 us apart.  Single-leaf panels (the SVGP sizes and the narrow tail of a large factorisation: leaf -> solve -> strip,
+// 16 - 32 times per factorisation) therefore hand over WITHOUT packets on this stream:
+//   "panel p solved"     the strip kernel stores the epoch into F[p] on entry (its predecessor, the solve, has completed
+//                        and released); the rest-update and extra-row streams wait for it with hipStreamWaitValue32;
+//   "rest-update done"   hipStreamWriteValue32(R[p]) behind the rest-update on ITS stream; the next strip's workgroups
+//                        spin on it in-kernel (normally already there: the rest-update has a leaf's time of slack).
+// (stream memory operations only on the plain streams: on the CU-masked bulk stream of large factorisations a
+// hipStreamWriteValue32 was observed to overtake the kernel queued before it -- wrong factor at n = 5000 -- so a panel whose
+// extra-row group waits on that stream keeps its event, and so does a strip whose rest-update ran there: PotrfPanel::flag_candidate
+// and rest_flag, potrf_plan.h)
+// WHICH hand-off is a flag word is the plan's decision (AND what the operands allow); this struct issues it and remembers what the
+// next hand-off needs to know.  One per call of gpk_potrf_core, on its stack.
+namespace {
+struct ChainSync {
+  hipStream_t P;
+  hipEvent_t* evF;   // [npanels] panel p factored, rows below solved (recorded on P)
+  hipEvent_t* evR;   // [npanels] rest of the trailing update of panel p done (on B)
+  hipEvent_t evFork, evJoinP, evJoinB, evJoinX;
+  int* flagF;        // [kMaxFlagPanels] "panel p solved", written with the epoch of the factorisation that owns it
+  int* flagR;        // [kMaxFlagPanels] "rest-update p done"
+  int epoch;
+  int* info;         // the status word: receives INT_MAX if a bounded in-kernel wait expires
+  bool gate_kernels;
+  // (A/B build only, GPK_FAULT_DROP_REST_FLAG=p: the "rest-update p done" word is never written -- the next strip's bounded
+  //  in-kernel wait must expire, the status word become INT_MAX and the call return instead of hanging: tests/test_gpu_handoff.py)
+  int drop_rest_flag;
+  bool panel_flagged = false;   // the panel solved most recently announces itself by F[p], not by evF[p]
+  bool rest_flagged = false;    // the most recent rest-update was followed by a write of R[last_rest]
+  bool evr_recorded = false;
+  int last_rest = -1;           // panel index whose evR marks the most recent rest-update
+  hipStream_t last_bulk;        // ... and the stream it ran on
+
+  ChainSync(Aux& aux, const PotrfPlan& plan, hipStream_t B, int* info_)
+      : P(aux.P), evF(aux.ev), evR(aux.ev + plan.npanels()), evFork(aux.ev[2 * plan.npanels()]), evJoinP(aux.ev[2 * plan.npanels() + 1]),
+        evJoinB(aux.ev[2 * plan.npanels() + 2]), evJoinX(aux.ev[2 * plan.npanels() + 3]), flagF(aux.flags),
+        flagR(aux.flags + kMaxFlagPanels), epoch(++aux.epoch), info(info_), gate_kernels(plan.gate_kernels),
+        drop_rest_flag(kGpkExp ? GPK_TUNE(FAULT_DROP_REST_FLAG, -1) : -1), last_bulk(B) {}
+
+  // fork: everything already queued on S comes first (X = nullptr: no extra-row stream of its own)
+  int fork(hipStream_t S, hipStream_t B, hipStream_t X) {
+    GPK_HIP(hipEventRecord(evFork, S));
+    GPK_HIP(hipStreamWaitEvent(P, evFork, 0));
+    if (B != S) GPK_HIP(hipStreamWaitEvent(B, evFork, 0));
+    if (X) GPK_HIP(hipStreamWaitEvent(X, evFork, 0));
+    return 0;
+  }
+
+  // Panel p is solved on P; `strip` (the look-ahead update, launched next on P) announces it on entry if the panel is flagged,
+  // else the event is recorded here.  (What the other streams wait for: the flag word of a flagged panel, else the event.)
+  int panel_solved(int p, bool flagged, GemmArgs& strip) {
+    panel_flagged = flagged;
+    if (flagged) {
+      strip.sig_ptr = flagF + p;
+      strip.sig_val = epoch;
+    } else GPK_HIP(hipEventRecord(evF[p], P));
+    return 0;
+  }
+
+  // columns c1:c2 also received the most recent rest-update (on a bulk stream): order the two -- the strip's workgroups wait for
+  // R[last_rest] in-kernel, or P waits for the event
+  int strip_waits_for_rest(GemmArgs& strip) {
+    if (last_rest < 0) return 0;
+    if (panel_flagged && rest_flagged) {
+      strip.wait_ptr = flagR + last_rest;
+      strip.wait_val = epoch;
+      strip.wait_info = info;
+      return 0;
+    }
+    GPK_TRY(need_evr());
+    GPK_HIP(hipStreamWaitEvent(P, evR[last_rest], 0));
+    return 0;
+  }
+
+  // stream st waits for "panel p solved" (p: the panel of the last panel_solved)
+  // (a flagged panel: our own one-wave gate kernel, 0.3 us behind its predecessor, instead of the runtime's wait packet, 5 - 7 us;
+  //  never on the CU-masked stream, whose stream memory operations were seen out of order -- see above)
+  int wait_panel(hipStream_t st, int p) {
+    if (panel_flagged) {
+      if (gate_kernels) return gpk_launch_wait_flag(st, flagF + p, epoch, info);
+      GPK_HIP(hipStreamWaitValue32(st, flagF + p, (uint32_t)epoch, hipStreamWaitValueGte, 0xffffffffu));
+    } else GPK_HIP(hipStreamWaitEvent(st, evF[p], 0));
+    return 0;
+  }
+
+  // the event of the most recent rest-update, recorded when first needed: its stream is in order, so a record issued later covers it
+  int need_evr() {
+    if (!evr_recorded && last_rest >= 0) {
+      GPK_HIP(hipEventRecord(evR[last_rest], last_bulk));
+      evr_recorded = true;
+    }
+    return 0;
+  }
+
+  // the most recent rest-update ran on st (or there was none): a rest-update on st needs no hand-off from it
+  bool previous_rest_on(hipStream_t st) const { return last_rest < 0 || last_bulk == st; }
+  // ... else st waits for it.  (Only where the narrow panels of a large factorisation take over from the wide ones: the rest-updates
+  // change from the masked stream to Bs once, and never back -- wide panels come before narrow ones.)
+  int order_rest_after_previous(hipStream_t st) {
+    if (previous_rest_on(st)) return 0;
+    GPK_TRY(need_evr());
+    GPK_HIP(hipStreamWaitEvent(st, evR[last_rest], 0));
+    return 0;
+  }
+
+  // How "rest-update p done" is announced: by the event (recorded now); by a write of R[p] behind the update on its stream (set-flag
+  // kernel or stream write); or by the update's last kernel itself ON ENTRY (rest_flag_on_entry: the remainder of a split
+  // rest-update, which follows the column the next strip needs).  A flagged rest-update gets its event only if somebody asks
+  // for it: need_evr.
+  enum RestSignal { kEvent, kFlagWrite, kFlagOnEntry };
+  void rest_flag_on_entry(int p, GemmArgs& g) const {
+    if (p == drop_rest_flag) return;
+    g.sig_ptr = flagR + p;
+    g.sig_val = epoch;
+  }
+  int rest_done(hipStream_t st, int p, RestSignal how) {
+    rest_flagged = how != kEvent;
+    evr_recorded = !rest_flagged;
+    last_bulk = st;
+    last_rest = p;
+    if (how == kEvent) GPK_HIP(hipEventRecord(evR[p], st));
+    if (how != kFlagWrite || p == drop_rest_flag) return 0;
+    if (gate_kernels) return gpk_launch_set_flag(st, flagR + p, epoch);
+    GPK_HIP(hipStreamWriteValue32(st, flagR + p, (uint32_t)epoch, 0));
+    return 0;
+  }
+
+  // join: P has waited for every rest-update it depends on; B's last event covers the rest (X = nullptr: as fork)
+  int join(hipStream_t S, hipStream_t X) {
+    GPK_HIP(hipEventRecord(evJoinP, P));
+    GPK_HIP(hipStreamWaitEvent(S, evJoinP, 0));
+    if (last_bulk != S) {
+      GPK_HIP(hipEventRecord(evJoinB, last_bulk));  // rest-updates are chained through evR, the last one covers all
+      GPK_HIP(hipStreamWaitEvent(S, evJoinB, 0));
+    }
+    if (X && X != last_bulk) {
+      GPK_HIP(hipEventRecord(evJoinX, X));
+      GPK_HIP(hipStreamWaitEvent(S, evJoinX, 0));
+    }
+    return 0;
+  }
+};
+
+// ---- one factorisation being enqueued: the plan, the operands, the streams -----------------------------------------------------
+struct PotrfRun {
+  const PotrfPlan& plan;
+  ChainSync& sync;
+  double* A; long lda; int batch; long strideA;
+  double* invd; long strideInv;
+  int* info;
+  hipStream_t P, B_masked, Bs, X;   // X: the stream of the extra rows (plan.X)
+  bool progressive;                 // plan.progressive_candidate AND what the operands allow
+  double* E() const { return A + (long)plan.n * lda; }   // the extra rows
+  hipStream_t rest_stream(const PotrfPanel& q) const { return q.rest_stream == PotrfStream::B_masked ? B_masked : Bs; }
+
+  int enqueue_chain(int p);
+  int enqueue_rest_update(int p);
+  int enqueue_extra_rows(int p);
+};
+
+// ---- P: the critical path.  Panel p, then the strip = columns of panel p+1 (look-ahead) -----------
+int PotrfRun::enqueue_chain(int p) {
+  const PotrfPanel& q = plan.panels[p];
+  const int c0 = q.c0, c1 = q.c1, c2 = q.c2, R = plan.R;
+  GPK_TRY(factor_panel(P, A, R, c0, c1, lda, batch, strideA, invd, strideInv, info, plan.chain_wgs));
+  const bool has_strip = c1 < plan.n;
+  const double* Pn = A + (long)c1 * lda + c0;  // rows c1.. of the solved panel
+  GemmArgs strip{};
+  if (has_strip) {
+    strip = gemm_base(R - c1, c2 - c1, c1 - c0, -1.0, Pn, lda, Pn, lda, 1.0, A + (long)c1 * lda + c1, lda, batch, strideA,
+                      strideA, strideA);
+    strip.c_lower = 1;
+    strip.max_wgs = plan.chain_wgs;
+  }
+  // (operand-dependent, so not in the plan: only the one-shot latency kernel honours sig_ptr / wait_ptr, and whether the strip
+  //  runs on it depends on gemm.hip's limits and the alignment of A)
+  const bool flagged = q.flag_candidate && gpk_gemm_takes_latency_kernel(strip);
+  GPK_TRY(sync.panel_solved(p, flagged, strip));
+  if (!has_strip) return 0;
+  GPK_TRY(sync.strip_waits_for_rest(strip));
+  return gpk_launch_gemm(P, strip);
+}
+
+// ---- B: rest of the outer trailing update  A[c2:, c2:] -= P[c2:] P[c2:]^T, lower tiles only --------
+// While the trailing matrix is large the factorisation is bound by these GEMMs (masked stream B); they start as soon
+// as panel p is solved.  (Which regime -- tiled, 64 x 64 tiles, tile queue, walking workgroups -- and why: potrf_plan.h.)
+int PotrfRun::enqueue_rest_update(int p) {
+  const PotrfPanel& q = plan.panels[p];
+  const int c0 = q.c0, c1 = q.c1, c2 = q.c2, c3 = q.c3, n = plan.n, R = plan.R;
+  if (c2 >= n) return 0;
+  hipStream_t Bp = rest_stream(q);
+  const double* P2 = A + (long)c2 * lda + c0;
+  GemmArgs u = gemm_base(R - c2, n - c2, c1 - c0, -1.0, P2, lda, P2, lda, 1.0,
+                         A + (long)c2 * lda + c2, lda, batch, strideA, strideA, strideA);
+  u.c_lower = 1;
+  if (q.rest_tile64_candidate) {
+    u.no_small = 1;
+    u.tile64 = plan.rest_tile64;
+  }
+  else if (q.rest_small_loop) { u.small_loop = 1; u.max_wgs = plan.rest_small_wgs; }
+  if (q.rest_tile_queue) {
+    u.stagger_first = plan.bulk_cus;
+    u.tile_queue = plan.trail_queue;
+  }
+  // Split rest-update (round 6).  With the 25-us leaf the chain of a single-leaf panel is leaf 25 + solve 7 + strip 8 = 40 us,
+  // and the rest-update stream had become the longer one: wait packet 6 + one 30-us tiled launch + write packet 7 + the
+  // in-kernel wait of the next strip = 45 us per panel (profiles/r06_rows1024_new_leaf_timeline.txt).  The next strip only
+  // needs the NEXT block column of the rest-update, so that column goes first, on the one-shot latency kernel (~8 us, beside
+  // strip p) behind a gate on "panel p solved"; the remainder follows on the same stream and announces the
+  // column on ITS entry (GemmArgs::sig_ptr) -- no packet in between, and the remainder has a whole panel period of slack.
+  // ("waiting for panel p solved": the one-wave gate kernel of wait_panel.)
+  GemmArgs ua = gemm_base(R - c2, c3 - c2, c1 - c0, -1.0, P2, lda, P2, lda, 1.0, A + (long)c2 * lda + c2, lda, batch, strideA,
+                          strideA, strideA);
+  ua.c_lower = 1;
+  // (operand-dependent, so not in the plan: the first column must run on the one-shot latency kernel -- gemm.hip's limits, the
+  //  alignment of A; the panel must really have been flagged; and the previous rest-update must have run on this stream)
+  const bool split = q.rest_split_candidate && sync.panel_flagged && gpk_gemm_takes_latency_kernel(ua) && sync.previous_rest_on(Bp);
+  // (the gate, not an in-kernel wait: up to 120 workgroups of 150 KB spinning from the moment they are enqueued -- a leaf and
+  //  a solve before their flag -- would hold the compute units the chain and the extra-row stream need)
+  GPK_TRY(sync.wait_panel(Bp, p));
+  if (!split) {
+    GPK_TRY(sync.order_rest_after_previous(Bp));
+    GPK_TRY(gpk_launch_gemm(Bp, u));
+    return sync.rest_done(Bp, p, q.rest_flag ? ChainSync::kFlagWrite : ChainSync::kEvent);
+  }
+  GPK_TRY(gpk_launch_gemm(Bp, ua));
+  if (c3 >= n) return sync.rest_done(Bp, p, ChainSync::kFlagWrite);
+  const double* P3 = A + (long)c3 * lda + c0;
+  GemmArgs ub = gemm_base(R - c3, n - c3, c1 - c0, -1.0, P3, lda, P3, lda, 1.0, A + (long)c3 * lda + c3, lda, batch,
+                          strideA, strideA, strideA);
+  ub.c_lower = 1;
+  ub.no_small = u.no_small;
+  ub.tile64 = u.tile64;
+  sync.rest_flag_on_entry(p, ub);
+  GPK_TRY(gpk_launch_gemm(Bp, ub));
+  return sync.rest_done(Bp, p, ChainSync::kFlagOnEntry);
+}
+
+// ---- X: the extra rows against the finished columns, in groups of up to 512 columns (so that the big
+// right-looking update is a K = 512 GEMM).  Where the groups end, the shrinking groups at the end of the small sizes and the
+// progressive first group: potrf_plan.h, plan_extra_rows.
+int PotrfRun::enqueue_extra_rows(int p) {
+  const PotrfPanel& q = plan.panels[p];
+  const int n = plan.n, extra = plan.extra, tri = plan.tri;
+  if (progressive && q.x_progressive_block >= 0) {
+    GPK_TRY(sync.wait_panel(X, p));
+    const int xrows = tri ? extra - tri + plan.prog_end : extra;
+    return solve_group_fwd(X, plan.bulk, E(), lda, E(), lda, xrows, A, lda, invd, strideInv, n, 0, plan.prog_end, batch, strideA, strideA,
+                           strideA, q.x_progressive_block, plan.prog_cap);
+  }
+  if (!q.x_group_end) return 0;
+  GPK_TRY(sync.wait_panel(X, p));
+  // (columns [g0, c1) may span several 512-groups when the outer panel is wider than a group)
+  for (int h0 = q.x_group_begin; h0 < q.c1; h0 += NBO) {
+    const int h1 = std::min(h0 + NBO, q.c1);
+    const int xrows = tri ? extra - tri + h1 : extra;  // (identity rows below column h1 are still exactly zero here)
+    GPK_TRY(solve_group_fwd(X, plan.bulk, E(), lda, E(), lda, xrows, A, lda, invd, strideInv, n, h0, h1, batch, strideA, strideA,
+                            strideA));
+  }
+  return 0;
+}
+
+// n <= NB: one leaf on the caller's stream; nothing to overlap, no device state
+int potrf_single_leaf(hipStream_t S, const PotrfPlan& plan, double* A, long lda, int batch, long strideA, double* invd, long strideInv,
+                      int zero_upper, int* info, const PotrfHooks& hooks) {
+  const int n = plan.n;
+  for (const StreamWork* w : {&hooks.p_prologue, &hooks.x_prologue, &hooks.late_work}) {
+    if (*w) GPK_TRY((*w)(S));
+  }
+  GPK_TRY(factor_panel(S, A, plan.R, 0, n, lda, batch, strideA, invd, strideInv, info));
+  if (plan.useX) {
+    double* E = A + (long)n * lda;
+    GPK_TRY(solve_group_fwd(S, PotrfBulk{}, E, lda, E, lda, plan.extra, A, lda, invd, strideInv, n, 0, n, batch, strideA, strideA, strideA));
+  }
+  return zero_upper ? gpk_launch_zero_upper(S, A, n, lda, batch, strideA) : 0;
+}
+}  // namespace
+
 // (the hooks, tri and tri_prefilled: gpk_internal.h)
 int gpk_potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int batch, long strideA, double* invd, int zero_upper,
                    int* info, const PotrfHooks& hooks, int tri, bool tri_prefilled) {
-  const StreamWork& x_prologue = hooks.x_prologue;
-  const StreamWork& p_prologue = hooks.p_prologue;
-  const StreamWork& late_work = hooks.late_work;
   if (!A || !invd || n < 0 || extra < 0 || lda < n) return GPK_E_ARG;
   if (tri && (tri != n || extra < n || batch > 1)) return GPK_E_ARG;
   if (batch <= 0) batch = 1;
@@ -414,387 +696,49 @@ int gpk_potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int bat
     if (info) GPK_HIP(hipMemsetAsync(info, 0, sizeof(int) * batch, S));
     return 0;
   }
-  if (tri && !tri_prefilled) {
-    const int rci = gpk_launch_set_identity(S, A + (long)(n + extra - tri) * lda, n, lda);
-    if (rci) return rci;
-  }
+  if (tri && !tri_prefilled) GPK_TRY(gpk_launch_set_identity(S, A + (long)(n + extra - tri) * lda, n, lda));
   const long strideInv = (long)gpk_cdiv(n, NB) * NB * NB;
-  // outer panel width for n >= 4096 (A/B at N = 16384, profiles/r03_ab_gpr_nbo.log); one leaf block for the SVGP sizes,
-  // where the whole factorisation is a latency chain
-  const int nbo_large = (GPK_TUNE(NBO, 640) / NB) * NB;
-  const int nbo = (n >= 4096) ? (nbo_large >= NB ? nbo_large : NBO) : NB;
-  // Panel boundaries.  The END of a large factorisation is a latency chain again (trailing matrix too small to hide the
-  // panel): there a wide panel costs 5 leaves + 4 in-panel updates + one K = 640 look-ahead strip of < 256 tiles, i.e. ONE
-  // under-filled tile time of ~170 us -- 450 - 480 us per 640 columns (in-kernel time stamps, tools/leaf_phase_probe.py) --
-  // while single-leaf panels cost 56 - 63 us each once their K = 128 rest-updates keep up.  So the last `narrow_tail`
-  // columns are factored with the SVGP-size scheme (nbo = NB).  A/B at N = 16384, same box (profiles/r03_ab_gpr_nbo.log):
-  // off 32.7 ms, 2048 -> 32.65, 3072 -> 32.4, 4096 -> 31.9, 5120 -> 32.2, 6144 -> 32.5, 8192 -> 33.2.
-  const int narrow_tail = (nbo > NB) ? (GPK_TUNE(NARROW_TAIL, 4096) / NB) * NB : 0;
-  std::vector<int> cuts;
-  for (int c = 0; c < n;) {
-    cuts.push_back(c);
-    c += (nbo > NB && n - c > narrow_tail) ? nbo : NB;
-  }
-  cuts.push_back(n);
-  const int npanels = (int)cuts.size() - 1;
-  // Few extra rows (GPR: the P columns of Y) simply ride along through the panel solves and trailing
-  // updates of the square part; many extra rows (SVGP: the minibatch; GPR: the test rows of predict_f) are solved
-  // right-looking, group by group, as bulk work overlapped with the factorisation.
-  const bool ride = extra > 0 && extra <= 256;
-  const int R = ride ? n + extra : n;  // rows handled together with the square part
-  const bool useX = extra > 0 && !ride;
-  double* E = A + (long)n * lda;       // the extra rows
-  int rc;
-  if (n <= NB) {  // one leaf; nothing to overlap
-    if (p_prologue) {
-      rc = p_prologue(S);
-      if (rc) return rc;
-    }
-    if (x_prologue) {
-      rc = x_prologue(S);
-      if (rc) return rc;
-    }
-    if (late_work) {
-      rc = late_work(S);
-      if (rc) return rc;
-    }
-    rc = factor_panel(S, A, R, 0, n, lda, batch, strideA, invd, strideInv, info);
-    if (rc) return rc;
-    if (useX) {
-      rc = solve_group_fwd(S, Bulk{}, E, lda, E, lda, extra, A, lda, invd, strideInv, n, 0, n, batch, strideA, strideA, strideA);
-      if (rc) return rc;
-    }
-    return zero_upper ? gpk_launch_zero_upper(S, A, n, lda, batch, strideA) : 0;
-  }
-  int dev = 0;
-  rc = current_device(&dev);
-  if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> lock(g_aux[dev].mu);
+  // the per-device streams, events and flag words (held to the end of the enqueue); a single leaf needs none of them
   Aux* aux = nullptr;
-  rc = aux_get(dev, 2 * npanels + 8, &aux);   // (+ fork, three joins)
-  if (rc) return rc;
-  const bool large = n >= 4096;
-  hipStream_t P = aux->P, B = large ? aux->B : aux->Bs;
-  // ONE bulk stream beside the chain: for large factorisations the extra rows share the (hardware-masked) stream of the
-  // trailing updates; for small ones they have the unmasked stream X.  Round 3 re-measured every alternative on the SVGP
-  // step (profiles/r03_ab_svgp_schedules.log): a masked extra-row stream with 8 ... 128 reserved CUs, two row halves on
-  // two streams, the projection streamed or split onto a side stream, one GEMM per column group against an explicit
-  // group inverse -- each 5 ... 40 % slower than this scheme.
-  hipStream_t X = large ? aux->B : aux->X;
-  Bulk bulk;
-  // cap on the persistent workgroups of the big extra-row updates, so that some CUs stay free for the panel stream's
-  // one-shot kernels (A/B on the SVGP step, round 1: cap 320 -> 448 steps/s, no cap 435, cap 224 -> 431; round 3: 256 ->
-  // 419, 320 -> 441, 384 -> 447)
-  // (round 5, with the packet-free chain: 224 -- one workgroup on 224 compute units, 32 left to the chain's one-shot kernels --
-  //  is level with 320 on the whitened step and 2 - 5 % faster on the un-whitened one, whose extra-row stream is a quarter
-  //  longer; a batch of problems keeps 320: C5 separate 2.04 against 2.02 ms; 240 / 248 lose 5 %, profiles/r05_ab_caps.log)
-  if (!large) bulk.cap = batch > 1 ? GPK_TUNE(EXTRA_MAX_WGS_BATCHED, 320) : GPK_TUNE(EXTRA_MAX_WGS, 224);
-  if (!large) bulk.group_cap = GPK_TUNE(GROUP_SOLVE_MAX_WGS, 0);
-  if (!large) bulk.kmin = GPK_TUNE(EXTRA_CAP_KMIN, 256);
-  hipEvent_t* evF = aux->ev;            // [npanels] panel p factored, rows below solved (recorded on P)
-  hipEvent_t* evR = aux->ev + npanels;  // [npanels] rest of the trailing update of panel p done (on B)
-  hipEvent_t evFork = aux->ev[2 * npanels], evJoinP = aux->ev[2 * npanels + 1], evJoinB = aux->ev[2 * npanels + 2],
-             evJoinX = aux->ev[2 * npanels + 3];
-  const bool p_on_panel = p_prologue && GPK_TUNE(KUU_ON_PANEL, 1);
-  if (p_prologue && !p_on_panel) {
-    rc = p_prologue(S);
-    if (rc) return rc;
+  std::unique_lock<std::recursive_mutex> lock;
+  if (n > NB) {
+    int dev = 0;
+    GPK_TRY(current_device(&dev));
+    lock = std::unique_lock<std::recursive_mutex>(g_aux[dev].mu);
+    GPK_TRY(aux_get(dev, &aux));
   }
-  if (x_prologue && !useX) {  // the extra rows ride through the panel solves: they must exist before the first one
-    rc = x_prologue(S);
-    if (rc) return rc;
+  PotrfPlan plan = make_potrf_plan(PotrfShape{n, extra, batch, tri},
+                                   aux ? PotrfDevice{aux->bulk_cus, aux->flags != nullptr && aux->concurrent == 1} : PotrfDevice{0, false});
+  if (plan.single_leaf) return potrf_single_leaf(S, plan, A, lda, batch, strideA, invd, strideInv, zero_upper, info, hooks);
+  GPK_TRY(aux_reserve_events(*aux, plan.nevents));
+  // (operand-dependent, so not in the plan: the progressive first group needs the partial in-group solve of gemm.hip and operands the
+  //  fused in-group kernel takes -- 16-byte-aligned factor and block inverses, even lda)
+  const bool progressive = plan.progressive_candidate && gpk_group_solve_takes_parts() &&
+                           group_solve_fused_ok(plan.prog_end / NB, 0, plan.prog_end, tri ? extra - tri + plan.prog_end : extra, A, lda, invd,
+                                                batch, strideA, strideInv);
+  if (plan.progressive_candidate && !progressive) plan.plan_extra_rows(false);
+  hipStream_t B = plan.large ? aux->B : aux->Bs;
+  hipStream_t X = plan.large ? aux->B : aux->X;
+  hipStream_t Xown = (plan.useX && X != B) ? X : nullptr;   // the extra rows have a stream of their own to fork and join
+
+  const bool p_on_panel = hooks.p_prologue && GPK_TUNE(KUU_ON_PANEL, 1);
+  if (hooks.p_prologue && !p_on_panel) GPK_TRY(hooks.p_prologue(S));
+  // the extra rows ride through the panel solves: they must exist before the first one
+  if (hooks.x_prologue && !plan.useX) GPK_TRY(hooks.x_prologue(S));
+  ChainSync sync(*aux, plan, B, info);
+  PotrfRun run{plan, sync, A, lda, batch, strideA, invd, strideInv, info, aux->P, aux->B, aux->Bs, X, progressive};
+  GPK_TRY(sync.fork(S, B, Xown));
+  if (p_on_panel) GPK_TRY(hooks.p_prologue(aux->P));
+  for (int p = 0; p < plan.npanels(); ++p) {
+    GPK_TRY(run.enqueue_chain(p));
+    GPK_TRY(run.enqueue_rest_update(p));
+    if (p == 0 && hooks.x_prologue && plan.useX) GPK_TRY(hooks.x_prologue(X));
+    // (on the stream of the most recent rest-update, whose last event the join below waits for)
+    if (hooks.late_work && p == plan.late_panel) GPK_TRY(hooks.late_work(sync.last_bulk));
+    GPK_TRY(run.enqueue_extra_rows(p));
   }
-  GPK_HIP(hipEventRecord(evFork, S));  // fork: everything already queued on S comes first
-  GPK_HIP(hipStreamWaitEvent(P, evFork, 0));
-  if (B != S) GPK_HIP(hipStreamWaitEvent(B, evFork, 0));
-  if (useX && X != B) GPK_HIP(hipStreamWaitEvent(X, evFork, 0));
-  if (p_on_panel) {
-    rc = p_prologue(P);
-    if (rc) return rc;
-  }
-  hipStream_t last_bulk = B;
-  int last_rest = -1;  // panel index whose evR marks the most recent rest-update
-  const bool use_flags = GPK_TUNE(CHAIN_FLAGS, 1) && (batch == 1 || GPK_TUNE(CHAIN_FLAGS_BATCHED, 1)) && aux->flags != nullptr &&
-                         aux->concurrent == 1;
-  int* flagF = aux->flags;
-  int* flagR = aux->flags + kMaxFlagPanels;
-  const bool gate_kernels = GPK_TUNE(GATE_KERNELS, 1) != 0;
-  const int epoch = ++aux->epoch;
-  bool rest_flagged = false;   // the most recent rest-update was followed by a write of R[last_rest]
-  std::vector<char> panel_flagged(npanels, 0);
-  int xg0 = 0;         // first column of the current extra-row group
-  // (512 columns for M = 2048: 256 / 384 measured slower there.  For M <= 1024 the extra-row stream would start after half of
-  // the chain: 256 columns for a batch of problems -- C5 separate 2.036 -> 1.977 ms -- and 128 for a single one -- C3 0.834 ->
-  // 0.803 ms, C5 shared 1.314 -> 1.30 ms, but C5 separate 1.97 -> 2.11; profiles/r04_ab_c5.log, r04_ab_xgroup_small.log)
-  // (round 6, with the chain at 41 us per panel instead of 62 the extra-row stream is the longer of the two at M = 1024 and wider groups
-  //  -- fewer, longer-K updates of its 8192 rows -- win: 128 / 256 / 384 / 512 columns: C3 0.757 / 0.713 / 0.688 / 0.716 ms, C5 shared
-  //  1.24 / 1.20 / 1.19 / 1.21 ms, two repetitions each on one box, profiles/r06_ab_extra_row_groups.log)
-  const int xgroup_small = batch > 1 ? GPK_TUNE(XGROUP_SMALL_BATCH, 256) : GPK_TUNE(XGROUP_SMALL, 384);
-  // (round 6: with FEW extra rows -- a rank's shard of a strong-scaled step -- M = 2048 prefers 256-column groups too: 4096 / 2048 / 1024
-  //  rows 1.353 / 1.049 / 0.938 -> 1.308 / 1.019 / 0.918 ms, while 8192 rows lose 5 %: tools/strong_scaling_emulation.py under GPK_XGROUP,
-  //  profiles/r06_ab_extra_row_groups.log)
-  const int xgroup_wide = (batch == 1 && n < 4096 && extra < GPK_TUNE(XGROUP_FEW_ROWS_BELOW, 6144)) ? GPK_TUNE(XGROUP_FEW_ROWS, 256) : GPK_TUNE(XGROUP, NBO);
-  const int xgroup = std::max(NB, ((n <= 1024 ? xgroup_small : xgroup_wide) / NB) * NB);
-  // (round 5 knobs: width of the FIRST extra-row group -- the extra-row stream idles until it is factored -- and the row count above
-  //  which the shrinking groups at the end are dropped: with many rows that stream, not the chain, finishes last)
-  const int xgroup_first = std::max(NB, (GPK_TUNE(XGROUP_FIRST, 0) > 0 ? (GPK_TUNE(XGROUP_FIRST, 0) / NB) * NB : xgroup));
-  // (A/B, profiles/r05_ab_extra_row_stream.log: M = 2048 x 8192 rows 1.97 - 1.99 -> 1.934 ms without the shrinking groups;
-  //  M = 1024, whose every panel is a group already, keeps them: 0.76 against 0.78 ms)
-  // (round 6, late: with the 41-us chain period the extra-row stream finishes last at M = 1024 too -- the two single-block groups at the end ran as
-  //  three launches BEHIND the last leaf: C3 0.683 - 0.690 -> 0.662 - 0.678 ms, C5 shared 1.18 -> 1.15, profiles/r06_ab_tail_zone_small.log)
-  const int tail_zone_max_rows = n > 1024 ? GPK_TUNE(XTAIL_ZONE_MAX_ROWS, 6144) : GPK_TUNE(XTAIL_ZONE_MAX_ROWS_SMALL, 6144);
-  // (A/B, profiles/r05_ab_extra_row_stream.log: latency kernel everywhere 1.903 1.907 | tiled from 150 workgroups 1.867 1.869 |
-  //  from 250: 1.886 1.896 | always: 1.883 1.897; caps of 16 / 32 / 64 walking workgroups on the latency kernel: 2.41 / 2.06 / 1.94)
-  // (all three "many extra rows" switches -- this one, the progressive first group, no shrinking groups at the end -- were measured
-  //  at 8192 rows (gain) and 4096 rows (loss: 1.71 -> 1.82 ms for this one, tools/strong_scaling_emulation.py): threshold 6144)
-  const bool rest_tiled = useX && !large && batch == 1 && extra >= GPK_TUNE(REST_TILED_MIN_ROWS, 3000);   // (6144 until the 64 x 64 tiles below: 4096 rows 1.33 -> 1.27 ms with them, profiles/r06_ab_rest_update_tile64.log)
-  const int rest_tiled_min_wgs = n > 1024 ? GPK_TUNE(REST_TILED_MIN_WGS, 30) : GPK_TUNE(REST_TILED_MIN_WGS_SMALL, 150);
-  const int rest_small_wgs = (useX && !large && batch == 1 && extra >= 6144) ? GPK_TUNE(REST_SMALL_WGS, 0) : 0;
-  const int prog_end = std::min(xgroup_first, n);
-  const int prog_cap = GPK_TUNE(XFIRST_PART_WGS, 128);
-  const bool progressive = useX && !large && nbo == NB && batch == 1 && GPK_TUNE(XFIRST_PROGRESSIVE, 1) && GPK_TUNE(GROUP_SOLVE_V2, 1) &&
-                           prog_end >= 2 * NB && extra >= GPK_TUNE(XFIRST_PROGRESSIVE_MIN_ROWS, 6144) &&
-                           group_solve_fused_ok(prog_end / NB, 0, prog_end, tri ? extra - tri + prog_end : extra, A, lda, invd, batch, strideA,
-                                                strideInv);
-  const int late_panel = std::min(npanels - 1, GPK_TUNE(LATE_WORK_PANEL, 5));
-  // the event of the most recent rest-update, recorded when first needed: its stream is in order, so a record issued later covers it
-  bool evr_recorded = false;
-  auto need_evr = [&]() -> int {
-    if (!evr_recorded && last_rest >= 0) {
-      GPK_HIP(hipEventRecord(evR[last_rest], last_bulk));
-      evr_recorded = true;
-    }
-    return 0;
-  };
-  for (int p = 0; p < npanels; ++p) {
-    const int c0 = cuts[p], c1 = cuts[p + 1];
-    const int c2 = (p + 2 <= npanels) ? cuts[p + 2] : n;
-    const bool narrow = large && (c1 - c0 <= NB) && nbo > NB;  // single-leaf panel in the chain-bound end of a large factorisation
-    // ---- P: the critical path.  Panel p, then the strip = columns of panel p+1 (look-ahead) -----------
-    const int chain_wgs = (!large && batch == 1) ? GPK_TUNE(CHAIN_MAX_WGS, 0) : 0;
-    const bool tail_zone = !large && (nbo == NB) && (n >= 8 * NB) && (extra < tail_zone_max_rows);
-    const int xgroup_now = (xg0 == 0 && !large) ? xgroup_first : xgroup;
-    const bool x_waits_here = useX && (c1 == n || ((c1 - xg0) >= xgroup_now || (large && c1 - xg0 >= nbo)) ||
-                                       (tail_zone && (c1 == n - 2 * NB || c1 == n - NB)));
-    rc = factor_panel(P, A, R, c0, c1, lda, batch, strideA, invd, strideInv, info, chain_wgs);
-    if (rc) return rc;
-    const double* Pn = A + (long)c1 * lda + c0;  // rows c1.. of the solved panel
-    GemmArgs strip{};
-    if (c1 < n) {
-      strip = gemm_base(R - c1, c2 - c1, c1 - c0, -1.0, Pn, lda, Pn, lda, 1.0, A + (long)c1 * lda + c1, lda, batch, strideA,
-                        strideA, strideA);
-      strip.c_lower = 1;
-      strip.max_wgs = chain_wgs;
-    }
-    // Chain flags (round 5).  Between two kernels of the panel stream an event record costs 4.6 us and an event wait 6.3 us of
-    // queue-packet processing (rocprofv3 timelines, profiles/r05_rows1024_events_timeline.txt, r05_ab_chain_flags.log); two kernels back to back start
-    // 0.3 us apart.  Single-leaf panels (the SVGP sizes and the narrow tail of a large factorisation: leaf -> solve -> strip,
-    // 16 - 32 times per factorisation) therefore hand over WITHOUT packets on this stream:
-    //   "panel p solved"     the strip kernel stores the epoch into F[p] on entry (its predecessor, the solve, has completed
-    //                        and released); the rest-update and extra-row streams wait for it with hipStreamWaitValue32;
-    //   "rest-update done"   hipStreamWriteValue32(R[p]) behind the rest-update on ITS stream; the next strip's workgroups
-    //                        spin on it in-kernel (normally already there: the rest-update has a leaf's time of slack).
-    // (stream memory operations only on the plain streams: on the CU-masked bulk stream of large factorisations a
-    // hipStreamWriteValue32 was observed to overtake the kernel queued before it -- wrong factor at n = 5000 -- so a panel whose
-    // extra-row group waits on that stream keeps its event, and so does a strip whose rest-update ran there)
-    const bool flagged = use_flags && p < kMaxFlagPanels && c1 < n && (c1 - c0) <= NB &&
-                         gpk_gemm_takes_latency_kernel(strip) && !(x_waits_here && X == aux->B);
-    panel_flagged[p] = flagged ? 1 : 0;
-    if (!flagged) GPK_HIP(hipEventRecord(evF[p], P));
-    if (c1 < n) {
-      // columns c1:c2 also received the most recent rest-update (on a bulk stream): order the two
-      if (last_rest >= 0) {
-        if (flagged && rest_flagged) {
-          strip.wait_ptr = flagR + last_rest;
-          strip.wait_val = epoch;
-          strip.wait_info = info;
-        } else {
-          rc = need_evr();
-          if (rc) return rc;
-          GPK_HIP(hipStreamWaitEvent(P, evR[last_rest], 0));
-        }
-      }
-      if (flagged) {
-        strip.sig_ptr = flagF + p;
-        strip.sig_val = epoch;
-      }
-      rc = gpk_launch_gemm(P, strip);
-      if (rc) return rc;
-    }
-    // (what the other streams wait for: the flag word of a flagged panel, else the event)
-    // (a flagged panel: our own one-wave gate kernel, 0.3 us behind its predecessor, instead of the runtime's wait packet, 5 - 7 us;
-    //  never on the CU-masked stream, whose stream memory operations were seen out of order -- see above)
-    auto wait_panel = [&](hipStream_t st) -> int {
-      if (panel_flagged[p]) {
-        if (gate_kernels) return gpk_launch_wait_flag(st, flagF + p, epoch, info);
-        GPK_HIP(hipStreamWaitValue32(st, flagF + p, (uint32_t)epoch, hipStreamWaitValueGte, 0xffffffffu));
-      } else GPK_HIP(hipStreamWaitEvent(st, evF[p], 0));
-      return 0;
-    };
-    // (A/B build only, GPK_FAULT_DROP_REST_FLAG=p: the "rest-update p done" word is never written -- the next strip's bounded
-    //  in-kernel wait must expire, the status word become INT_MAX and the call return instead of hanging: tests/test_gpu_handoff.py)
-    const bool drop_rest_flag = kGpkExp && GPK_TUNE(FAULT_DROP_REST_FLAG, -1) == p;
-    auto write_rest_flag = [&](hipStream_t st) -> int {
-      if (drop_rest_flag) return 0;
-      if (gate_kernels) return gpk_launch_set_flag(st, flagR + p, epoch);
-      GPK_HIP(hipStreamWriteValue32(st, flagR + p, (uint32_t)epoch, 0));
-      return 0;
-    };
-    // ---- B: rest of the outer trailing update  A[c2:, c2:] -= P[c2:] P[c2:]^T, lower tiles only --------
-    // While the trailing matrix is large the factorisation is bound by these GEMMs (masked stream B); they start as soon
-    // as panel p is solved.
-    if (c2 < n) {
-      hipStream_t Bp = narrow ? aux->Bs : B;
-      const double* P2 = A + (long)c2 * lda + c0;
-      GemmArgs u = gemm_base(R - c2, n - c2, c1 - c0, -1.0, P2, lda, P2, lda, 1.0,
-                             A + (long)c2 * lda + c2, lda, batch, strideA, strideA, strideA);
-      u.c_lower = 1;
-      // (round 5) While the extra-row stream's capped updates hold 224 compute units, a rest-update on the one-shot latency kernel
-      // -- up to 512 workgroups of 150 KB each -- queues through the 32 free ones for ~140 us and the chain's strips queue behind
-      // it; the tiled kernel's 74-KB workgroups fit beside the capped ones.
-      if (rest_tiled && (long)gpk_cdiv(u.m, 16) * gpk_cdiv(u.n, 128) >= rest_tiled_min_wgs) {
-        u.no_small = 1;
-        // (round 6, late) ... and there a 128 x 128 tile of the rest-update shares its compute unit with a capped MFMA-bound workgroup of the
-        // extra-row stream and takes 60 - 95 us instead of 30 -- longer than the chain's period, and every strip WAITS for the previous
-        // rest-update (the strips of the step timeline: 30 - 67 us, of which 8 are work).  As 64 x 64 tiles of the generic kernel (four times
-        // the workgroups, 36 KB of LDS: they fit anywhere) it is short again: Cm 1.771 -> 1.750 ms, with the tiled regime from 30
-        // workgroups on (M > 1024) 1.72 - 1.74; 32 x 64 and 64 x 128 tiles lose (profiles/r06_ab_rest_update_tile64.log).
-        u.tile64 = GPK_TUNE(REST_TILE64, 1);
-      }
-      else if (rest_small_wgs > 0) { u.small_loop = 1; u.max_wgs = rest_small_wgs; }
-      if (Bp == aux->B && large) {
-        u.stagger_first = aux->bulk_cus;
-        // (round 6) persistent workgroups -- two per compute unit of the bulk stream -- that take their tiles from a device counter
-        // (gemm.hip, "Tile QUEUE"): no workgroup launch per tile and no drift between static tile lists; the kernel alone gains 7 %
-        // (as dispatched 0.591 -> 0.632 of the chip's peak from 240 CUs).  They never leave their CUs, though, so the look-ahead panel no
-        // longer finds gaps there and needs more CUs of its own: with 8 reserved the whole factorisation LOSES 7 % (33.0 against 30.8 ms),
-        // with 32 (four per XCD) it gains 1.7 % (29.94 / 30.07 against 30.58 / 30.43 ms; 24: 32.0, 40: 31.6;
-        // profiles/r06_ab_gpr_tile_queue.log).
-        u.tile_queue = GPK_TUNE(TRAIL_QUEUE, 1);
-      }
-      // Split rest-update (round 6).  With the 25-us leaf the chain of a single-leaf panel is leaf 25 + solve 7 + strip 8 = 40 us,
-      // and the rest-update stream had become the longer one: wait packet 6 + one 30-us tiled launch + write packet 7 + the
-      // in-kernel wait of the next strip = 45 us per panel (profiles/r06_rows1024_new_leaf_timeline.txt).  The next strip only
-      // needs the NEXT block column of the rest-update, so that column goes first, on the one-shot latency kernel (~8 us, beside
-      // strip p) behind a gate on "panel p solved"; the remainder follows on the same stream and announces the
-      // column on ITS entry (GemmArgs::sig_ptr) -- no packet in between, and the remainder has a whole panel period of slack.
-      // ("waiting for panel p solved": the one-wave gate kernel of wait_panel.)
-      const int c3 = (p + 3 <= npanels) ? cuts[p + 3] : n;
-      GemmArgs ua = gemm_base(R - c2, c3 - c2, c1 - c0, -1.0, P2, lda, P2, lda, 1.0, A + (long)c2 * lda + c2, lda, batch, strideA,
-                              strideA, strideA);
-      ua.c_lower = 1;
-      const bool split = GPK_TUNE(REST_SPLIT, 1) && use_flags && p < kMaxFlagPanels && Bp != aux->B && panel_flagged[p] &&
-                         !u.no_small && !u.small_loop && (c2 - c1) <= NB && gpk_gemm_takes_latency_kernel(ua) &&
-                         !(last_rest >= 0 && last_bulk != Bp);
-      if (split) {
-        // (the gate, not an in-kernel wait: up to 120 workgroups of 150 KB spinning from the moment they are enqueued -- a leaf and
-        //  a solve before their flag -- would hold the compute units the chain and the extra-row stream need)
-        rc = wait_panel(Bp);
-        if (rc) return rc;
-        rc = gpk_launch_gemm(Bp, ua);
-        if (rc) return rc;
-        if (c3 < n) {
-          const double* P3 = A + (long)c3 * lda + c0;
-          GemmArgs ub = gemm_base(R - c3, n - c3, c1 - c0, -1.0, P3, lda, P3, lda, 1.0, A + (long)c3 * lda + c3, lda, batch,
-                                  strideA, strideA, strideA);
-          ub.c_lower = 1;
-          ub.no_small = u.no_small;
-          ub.tile64 = u.tile64;
-          if (!drop_rest_flag) {
-            ub.sig_ptr = flagR + p;
-            ub.sig_val = epoch;
-          }
-          rc = gpk_launch_gemm(Bp, ub);
-          if (rc) return rc;
-        } else {
-          rc = write_rest_flag(Bp);
-          if (rc) return rc;
-        }
-        rest_flagged = true;
-      } else {
-        if (narrow) {
-          // the unmasked stream of the SVGP-size scheme.  (A stream masked to half the CUs would keep CUs free for the leaf,
-          // but its hand-offs to P took ~55 us instead of ~5: 190 us per panel instead of 56, GPR N = 16384 36.6 vs 32.0 ms.)
-          rc = wait_panel(Bp);
-          if (rc) return rc;
-          if (last_rest >= 0 && last_bulk != Bp) {
-            rc = need_evr();
-            if (rc) return rc;
-            GPK_HIP(hipStreamWaitEvent(Bp, evR[last_rest], 0));
-          }
-        } else {
-          rc = wait_panel(B);
-          if (rc) return rc;
-        }
-        rc = gpk_launch_gemm(Bp, u);
-        if (rc) return rc;
-        rest_flagged = use_flags && p < kMaxFlagPanels && Bp != aux->B;
-        if (rest_flagged) {
-          rc = write_rest_flag(Bp);
-          if (rc) return rc;
-        } else GPK_HIP(hipEventRecord(evR[p], Bp));
-      }
-      evr_recorded = !rest_flagged;   // (a flagged rest-update gets its event only if somebody asks for it: need_evr)
-      last_bulk = Bp;
-      last_rest = p;
-    }
-    if (p == 0 && x_prologue && useX) {
-      rc = x_prologue(X);
-      if (rc) return rc;
-    }
-    if (late_work && p == late_panel) {
-      // (on the stream of the most recent rest-update, whose last event the join below waits for)
-      rc = late_work(last_bulk);
-      if (rc) return rc;
-    }
-    // ---- X: the extra rows against the finished columns, in groups of up to 512 columns (so that the big
-    // right-looking update is a K = 512 GEMM).  For the small sizes the groups shrink towards the end (.., n-256,
-    // n-128, n): whatever is left of the extra-row work when the LAST leaf finishes is exposed latency.
-    // Progressive first group (round 5).  The extra-row stream has nothing to do until the first group (four panels, ~245 us) is
-    // factored, and then spends ~100 us on that group's in-group solve before its first large update can start.  Instead, as soon
-    // as panel j of the first group is solved, ONE leaf block of the in-group solve runs (S_j = E_j X_j^T and the K = 128 update of
-    // the group's later blocks: 4 + 3 + 2 + 1 block products), on a capped number of workgroups so that the chain -- alone on the
-    // critical path there -- keeps its compute units.  When the fourth panel is done only one block product is left.
-    if (progressive && xg0 == 0 && c1 <= prog_end) {
-      rc = wait_panel(X);
-      if (rc) return rc;
-      const int xrows = tri ? extra - tri + prog_end : extra;
-      rc = solve_group_fwd(X, bulk, E, lda, E, lda, xrows, A, lda, invd, strideInv, n, 0, prog_end, batch, strideA, strideA, strideA,
-                           c0 / NB, prog_cap);
-      if (rc) return rc;
-      if (c1 == prog_end) xg0 = c1;
-      continue;
-    }
-    const bool tail_group = tail_zone && (c1 == n - 2 * NB || c1 == n - NB);
-    const bool full_group = ((c1 - xg0) >= xgroup_now || (large && c1 - xg0 >= nbo)) && !(tail_zone && c1 > n - 2 * NB && c1 < n);
-    if (useX && (c1 == n || full_group || tail_group)) {
-      const int g0 = xg0;
-      xg0 = c1;
-      rc = wait_panel(X);
-      if (rc) return rc;
-      // (columns [g0, c1) may span several 512-groups when the outer panel is wider than a group)
-      for (int h0 = g0; h0 < c1; h0 += NBO) {
-        const int h1 = std::min(h0 + NBO, c1);
-        const int xrows = tri ? extra - tri + h1 : extra;  // (identity rows below column h1 are still exactly zero here)
-        rc = solve_group_fwd(X, bulk, E, lda, E, lda, xrows, A, lda, invd, strideInv, n, h0, h1, batch, strideA, strideA,
-                             strideA);
-        if (rc) return rc;
-      }
-    }
-  }
-  // join: P has waited for every rest-update it depends on; B's last event covers the rest
-  GPK_HIP(hipEventRecord(evJoinP, P));
-  GPK_HIP(hipStreamWaitEvent(S, evJoinP, 0));
-  if (last_bulk != S) {
-    GPK_HIP(hipEventRecord(evJoinB, last_bulk));  // rest-updates are chained through evR, the last one covers all
-    GPK_HIP(hipStreamWaitEvent(S, evJoinB, 0));
-  }
-  if (useX && X != last_bulk) {
-    GPK_HIP(hipEventRecord(evJoinX, X));
-    GPK_HIP(hipStreamWaitEvent(S, evJoinX, 0));
-  }
-  if (zero_upper) return gpk_launch_zero_upper(S, A, n, lda, batch, strideA);
-  return 0;
+  GPK_TRY(sync.join(S, plan.useX ? X : nullptr));
+  return zero_upper ? gpk_launch_zero_upper(S, A, n, lda, batch, strideA) : 0;
 }
 
 extern "C" int gpk_stream_selfcheck(double* us_now, double* us_first, int* recreated) {
@@ -874,7 +818,7 @@ extern "C" int gpk_trsm(void* stream, int trans, const double* L, long ldl, cons
   int rc;
   if (trans == 0) {
     for (int g0 = 0; g0 < n; g0 += NBO) {
-      rc = solve_group_fwd(s, Bulk{}, B, ldb, B, ldb, m, L, ldl, invd, strideInv, n, g0, std::min(g0 + NBO, n), batch,
+      rc = solve_group_fwd(s, PotrfBulk{}, B, ldb, B, ldb, m, L, ldl, invd, strideInv, n, g0, std::min(g0 + NBO, n), batch,
                            strideB, strideB, strideL);
       if (rc) return rc;
     }

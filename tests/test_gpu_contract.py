@@ -451,6 +451,7 @@ POTRF_CASES = [
     (257, 0, False, 0),     # reduction-block edge, three panels
     (513, 513, True, 0),    # 512-column group + 1, extra-row stream
     (130, 7, False, 3),     # batched (SeparateIndependent), batch stride
+    (384, 300, False, 2),   # batched with an extra-row stream (256-column groups)
 ]
 CASE_TABLES["potrf_"] = POTRF_CASES
 

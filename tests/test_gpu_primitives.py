@@ -85,7 +85,11 @@ def test_gemm_nt_tri_and_batch(gpu):
     np.testing.assert_allclose(np.tril(out), np.tril(ref), rtol=0, atol=1e-11)
 
 
-@pytest.mark.parametrize("n,extra", [(1, 0), (17, 3), (128, 0), (129, 5), (300, 40), (640, 130), (1100, 257), (5000, 700)])
+# (the later shapes: one per branch of the schedule plan -- csrc/potrf_plan.h -- that the first eight do not reach: a single leaf with an
+#  extra-row solve, the tiled rest-update, the progressive first group, a large factorisation of narrow panels only without / with an
+#  extra-row stream, one wide panel and then narrow ones)
+@pytest.mark.parametrize("n,extra", [(1, 0), (17, 3), (128, 0), (129, 5), (300, 40), (640, 130), (1100, 257), (5000, 700),
+                                     (100, 300), (1024, 3000), (512, 6144), (4096, 0), (4096, 300), (4736, 1)])
 def test_potrf_trapezoid(gpu, n, extra):
     from gpflow_amd import ops
     rng = np.random.default_rng(4)
@@ -113,7 +117,8 @@ def test_potrf_trapezoid(gpu, n, extra):
         np.testing.assert_allclose(inv[b][: j1 - j0, : j1 - j0] @ D, np.eye(j1 - j0), rtol=0, atol=1e-11)
 
 
-@pytest.mark.parametrize("n,extra", [(40, 0), (128, 3), (200, 30), (300, 0), (640, 130), (1152, 700), (2048, 1), (4224, 300)])
+@pytest.mark.parametrize("n,extra", [(40, 0), (128, 3), (200, 30), (300, 0), (640, 130), (1152, 700), (2048, 1), (4224, 300),
+                                     (512, 6144)])   # (progressive first group with identity rows)
 def test_potrf_identity_rows(gpu, n, extra):
     """gpk_potrf_inv: the library writes the identity rows and returns L^-T, skipping the rows that are still zero.
     Same values as the dense route (identity rows handed in explicitly; 1e-11: the row count picks the GEMM variant and
@@ -404,7 +409,8 @@ def test_per_row_noise_variances(gpu):
     np.testing.assert_allclose(o[0] - o[1], ref, rtol=1e-8)
 
 
-@pytest.mark.parametrize("m,rows,d,P", [(256, 300, 3, 1), (640, 1000, 8, 2), (1024, 2500, 8, 1), (1152, 777, 4, 3)])
+@pytest.mark.parametrize("m,rows,d,P", [(256, 300, 3, 1), (640, 1000, 8, 2), (1024, 2500, 8, 1), (1152, 777, 4, 3),
+                                      (1024, 3000, 8, 1)])   # (tiled rest-updates)
 def test_svgp_elbo_shard_column_groups(gpu, m, rows, d, P):
     """The fused shard over the column-group shapes of the extra-row solve / q_sqrt projection, against the oracle: one
     group (m = 256), ragged last group (640 = 512 + 128), shrinking tail groups (1024, 1152), several latents, ragged
