@@ -22,12 +22,9 @@
 
 namespace {
 
-constexpr int BK = 16;
-constexpr int LDSS = BK + 2;
-// kernel the launcher picked last (bench profiling facility only; see gpk_profile_gemm_collect_kind):
-// 1 gemm_nt_small, 2 + 2 EPI + PAIR gemm_nt_fast<EPI, PAIR>, 6 gemm_nt_kernel
-thread_local int g_last_kind = 0;  // (per host thread: the GEMM entry points are reentrant)
-constexpr int GROUP_N = 8;
+constexpr int BK = kGemmBK;
+constexpr int LDSS = kGemmLDSS;
+constexpr int GROUP_N = kGemmGroupN;
 
 template <int BM, int BN, int WGM, int WGN>
 struct TileCfg {
@@ -483,39 +480,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_pre64(GemmArgs p, int gx, int 
   }
 }
 
-bool pre64_ok(const GemmArgs& a) {
-  if (a.epi != 0 || a.k <= 0 || a.k > 128 || (a.k & 15) || a.b_tri || a.a_tri || a.k_off_step || a.tile_snake || a.tail_first1) return false;
-  if ((a.lda & 1) || (a.ldb & 1) || (a.strideA & 1) || (a.strideB & 1)) return false;
-  if ((reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.B) & 15)) return false;
-  return true;
-}
-
-int launch_pre64(hipStream_t s, const GemmArgs& a) {
-  constexpr size_t LDS_BYTES = 2 * (size_t)(64 + 64) * LDSS * sizeof(double);
-  const int gx = gpk_cdiv(a.n, 64), gy = gpk_cdiv(a.m, 64);
-  if (gx <= 0 || gy <= 0) return 0;
-  int total = gx * gy, compact = 0;
-  if (a.c_lower) {   // (the numbering of launch_cfg: tiles on or below the diagonal, column groups of GROUP_N)
-    compact = 1;
-    total = 0;
-    for (int first = 0; first < gx; first += GROUP_N) {
-      const int gsz = (gx - first) < GROUP_N ? (gx - first) : GROUP_N;
-      const int avail = gy - first;
-      if (avail <= 0) break;
-      const int tr = avail < gsz ? avail : gsz;
-      total += tr * (tr + 1) / 2 + (avail > gsz ? (avail - gsz) * gsz : 0);
-    }
-    if (total <= 0) return 0;
-  }
-  g_last_kind = 6;
-  // (A/B, level: few tiles asking for 80 KB of LDS so that they cannot share a compute unit with a capped bulk workgroup and run on the CUs
-  //  the cap leaves free -- Cm 1.734 - 1.745 against 1.741 - 1.758 ms, profiles/r06_ab_rest_pre64.log; s_setprio 1 / 3 likewise)
-  hipLaunchKernelGGL(gemm_nt_pre64, dim3((unsigned)total, (unsigned)(a.batch > 0 ? a.batch : 1), 1), dim3(256), LDS_BYTES, s, a, gx, gy,
-                     total, compact);
-  GPK_LAUNCH_CHECK();
-  return 0;
-}
-
 
 // =====================================================================================================
 // Fast path: 128 x 128 x 16 tiles, every K range a multiple of 16, 16-byte aligned rows.
@@ -960,153 +924,6 @@ int queue_slot(unsigned fetches, int** out, unsigned* base) {
   return 0;
 }
 
-constexpr size_t FAST_LDS_BYTES = 2 * (size_t)256 * LDSS * sizeof(double);
-// one instantiation of the static walk (PAIR or not; SP = 1: row statistics ride along, EPI 1)
-template <int EPI, bool PAIR, int SP>
-int launch_fast_kernel(hipStream_t s, dim3 grid, size_t lds_bytes, const GemmArgs& a, int gx, int gy, int total, int compact) {
-  // (function-local static: initialised once, thread-safe; unpaired capped launches ask for more than the tile needs, launch_fast)
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_fast<EPI, PAIR, false, SP>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, PAIR ? (int)FAST_LDS_BYTES : 160 * 1024);
-  GPK_HIP(attr);
-  hipLaunchKernelGGL((gemm_nt_fast<EPI, PAIR, false, SP>), grid, dim3(256), lds_bytes, s, a, gx, gy, total, compact);
-  GPK_LAUNCH_CHECK();
-  return 0;
-}
-template <int EPI, bool PAIR>
-int launch_fast_walk(hipStream_t s, dim3 grid, size_t lds_bytes, const GemmArgs& a, int gx, int gy, int total, int compact) {
-  if constexpr (EPI == 1) {
-    if (a.stat_sumsq) return launch_fast_kernel<1, PAIR, 1>(s, grid, lds_bytes, a, gx, gy, total, compact);
-  }
-  return launch_fast_kernel<EPI, PAIR, 0>(s, grid, lds_bytes, a, gx, gy, total, compact);
-}
-
-template <int EPI>
-int launch_fast(hipStream_t s, const GemmArgs& a) {
-  constexpr size_t LDS_BYTES = FAST_LDS_BYTES;
-  const int gx = gpk_cdiv(a.n, 128), gy = gpk_cdiv(a.m, 128);
-  if (gx <= 0 || gy <= 0) return 0;
-  int total = gx * gy, compact = 0;
-  if (a.c_lower && EPI == 0) {
-    compact = 1;
-    total = 0;
-    for (int first = 0; first < gx; first += GROUP_N) {
-      const int gsz = (gx - first) < GROUP_N ? (gx - first) : GROUP_N;
-      const int avail = gy - first;
-      if (avail <= 0) break;
-      const int tr = avail < gsz ? avail : gsz;
-      total += tr * (tr + 1) / 2 + (avail > gsz ? (avail - gsz) * gsz : 0);
-    }
-    if (total <= 0) return 0;
-  }
-  const unsigned nb = (unsigned)(a.batch > 0 ? a.batch : 1);
-  // triangular-K operands (K range shrinking with the column tile for b_tri 1, growing for b_tri 2): paired column
-  // tiles.  EPI 0 too (the tri-K GEMMs of the reverse pass, gradients.py: 45 -> 60 TFLOP/s class) unless the launch
-  // is lower-only or capped.
-  {
-    const bool pair_ok = (EPI == 1) ? (a.b_tri == 1)
-                                    : ((a.b_tri == 1 || a.b_tri == 2) && !a.c_lower && a.max_wgs == 0 && a.b_tri_off == 0 && a.k_off_step == 0);
-    // (round 6) pairs that fill the chip at most once -- C3's projection: 4 x 64 = 256 workgroups, one per CU, whose K loop runs at
-    // 79 % alone -- run unpaired instead, heavy and light tile of a pair as TWO workgroups of one CU (88 % together)
-    if (EPI == 1 && pair_ok && gx >= 4 && !(gx & 1) && a.b_tri_rows >= a.n && a.max_wgs == 0 &&
-        (long)(gx / 2) * gy * nb <= GPK_TUNE(PROJ_UNPAIR_UPTO, 256)) {
-      GemmArgs b = a;
-      b.tile_snake = 1;
-      b.stagger_first = 256;
-      b.stagger_ticks = 0;
-      g_last_kind = 2 + 2 * EPI;
-      return launch_fast_walk<EPI, false>(s, dim3((unsigned)total, nb, 1), LDS_BYTES, b, gx, gy, total, compact);
-    }
-    if (pair_ok && gx >= 4 && a.b_tri_rows >= a.n) {
-      total = ((gx + 1) / 2) * gy;
-      g_last_kind = 2 + 2 * EPI + 1;
-      GemmArgs ap = a;
-      ap.pair_k_align = GPK_TUNE(PAIR_K_ALIGN, 1);
-      return launch_fast_walk<EPI, true>(s, dim3((unsigned)total, nb, 1), LDS_BYTES, ap, gx, gy, total, compact);
-    }
-  }
-  int tail_tiles = 0;
-  // Tail split of the capped launches of the extra-row stream (round 5): 224 persistent workgroups walk 768 / 512 /
-  // 256 tiles in 4 / 3 / 2 rounds of ~78 us where 3.43 / 2.29 / 1.14 would do -- a few rounds, no drift, and that stream is the
-  // critical path of the SVGP step.  The whole rounds stay on the persistent workgroups; the remainder runs as 64 x 64 quarters
-  // on every compute unit, for about a third of a round.
-  if (EPI == 0 && !a.c_lower && a.max_wgs > 0 && a.max_wgs < total && nb == 1 && !a.b_tri && !a.a_tri &&
-      GPK_TUNE(TAIL_SPLIT_CAPPED, 1)) {
-    const int r = total % a.max_wgs;
-    if (r > 0 && r * 100 <= a.max_wgs * GPK_TUNE(TAIL_SPLIT_CAPPED_PCT, 60)) tail_tiles = r;
-  }
-  const int total_all = total;
-  total -= tail_tiles;
-  unsigned nwg = (unsigned)total;
-  if (a.max_wgs > 0 && (unsigned)a.max_wgs < nwg) nwg = (unsigned)a.max_wgs;
-  GemmArgs b = a;
-  g_last_kind = 2 + 2 * EPI;
-  {
-    // half a tile in 100 MHz ticks: a 128x128x16 slab costs ~1.7 us per workgroup when two share a CU
-    // (A/B, 16384^2 x 512, beta = 1: 60.7 -> 63.0 TFLOP/s; lower-only 55.8 -> 58.8; percent of a half tile, 0 = off)
-    const int stagger_on = GPK_TUNE(GEMM_STAGGER, 100);
-    if (b.stagger_first <= 0) b.stagger_first = 256;
-    b.stagger_ticks = (stagger_on && EPI == 0 && !a.b_tri && total >= 1024 && (nwg == (unsigned)total || nwg >= 2u * (unsigned)b.stagger_first))
-                          ? (int)((a.k / 16) * 170 * stagger_on / 200)
-                          : 0;
-  }
-  // A CAPPED launch (persistent workgroups, fewer than compute units x 2) asks for more than half of a CU's LDS, so that no two
-  // of its workgroups can share a compute unit.  Without that the dispatcher doubles them up on whatever CUs are free at launch
-  // time -- the chain's strip holds 80 - 120 CUs for ~10 us -- and, the tile walk being static, the doubled-up pairs run at half
-  // speed for the WHOLE kernel: the first extra-row update of an SVGP step took 318 or 483 us depending on what it was launched
-  // beside (profiles/r05_step_timeline_before_extra_row_work.txt, round 5).
-  size_t lds_bytes = LDS_BYTES;
-  if (EPI == 0 && a.max_wgs > 0 && nwg < (unsigned)total && nb == 1) {
-    const int kb = GPK_TUNE(CAP_EXCL_LDS_KB, 84);
-    if (kb > 0 && kb <= 160 && (size_t)kb * 1024 > LDS_BYTES) lds_bytes = (size_t)kb * 1024;
-  }
-  if (EPI == 0 && tail_tiles == 0 && a.max_wgs == 0 &&
-      ((a.k_off_step && GPK_TUNE(KSPLIT_QUEUE, 1)) || (a.tile_queue && (long)total * nb > 512))) {
-    b.stagger_ticks = 0;
-    const long all = (long)total * nb;
-    const long qw = a.stagger_first > 0 ? 2L * a.stagger_first : GPK_TUNE(QUEUE_WGS, 512);   // (two per compute unit of the launch stream)
-    const unsigned wgs = (unsigned)(all < qw ? all : qw);
-    int* q = nullptr;
-    unsigned qbase = 0;
-    const int rcq = queue_slot((unsigned)all + wgs, &q, &qbase);
-    if (rcq) return rcq;
-    b.queue = q;
-    b.queue_base = (int)qbase;
-    if constexpr (EPI == 0) {
-      static const hipError_t attrq = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_fast<0, false, true>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-      GPK_HIP(attrq);
-      hipLaunchKernelGGL((gemm_nt_fast<0, false, true>), dim3(wgs, 1, 1), dim3(256), LDS_BYTES, s, b, gx, gy, total, compact);
-    }
-    GPK_LAUNCH_CHECK();
-    return 0;
-  }
-  const int rcw = launch_fast_walk<EPI, false>(s, dim3(nwg, nb, 1), lds_bytes, b, gx, gy, total, compact);
-  if (rcw) return rcw;
-  if (tail_tiles > 0) {
-    using Cfg = TileCfg<64, 64, 4, 1>;
-    static const hipError_t attrt = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<64, 64, 4, 1>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-    GPK_HIP(attrt);
-    GemmArgs t = a;
-    t.tail_first1 = total_all - tail_tiles + 1;
-    hipLaunchKernelGGL((gemm_nt_kernel<64, 64, 4, 1>), dim3((unsigned)(4 * tail_tiles), 1, 1), dim3(256), Cfg::LDS_BYTES, s, t, gx,
-                       gy, 4 * tail_tiles, compact);
-    GPK_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// 16-byte aligned rows and K ranges that are multiples of 16 everywhere (per-tile b_tri ranges too)
-bool fast_ok(const GemmArgs& a) {
-  if (GPK_TUNE(GEMM_NO_FAST, 0)) return false;
-  if (a.k <= 0 || (a.k & 15) || (a.b_tri && (a.b_tri_off & 15))) return false;
-  if ((a.lda & 1) || (a.ldb & 1) || (a.strideA & 1) || (a.strideB & 1)) return false;
-  if ((reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.B) & 15)) return false;
-  if (a.epi == 0 && a.beta != 0.0 && a.alpha == 0.0) return false;
-  if (a.lda > (1L << 21) || a.ldb > (1L << 21)) return false;  // 32-bit byte offsets inside a tile
-  return true;
-}
-
 
 // =====================================================================================================
 // Latency path for the short GEMMs on the critical path of the factorisation (panel solve  A21 inv(L11)^T,
@@ -1117,7 +934,7 @@ bool fast_ok(const GemmArgs& a) {
 // one barrier, then each of the 8 waves runs its 16x16 output tile over the full K with two
 // independent accumulators.  One column tile covers n <= 128, so the in-place solve (C aliases A)
 // only overwrites rows the workgroup alone has read.
-constexpr int SM_BM = 16, SM_BN = 128, SM_THREADS = 512;
+constexpr int SM_BM = kGemmSmallBM, SM_BN = kGemmSmallBN, SM_THREADS = kGemmSmallThreads;
 
 __global__ __launch_bounds__(SM_THREADS) void gemm_nt_small(GemmArgs p, int ldk) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1220,472 +1037,86 @@ __global__ __launch_bounds__(SM_THREADS) void gemm_nt_small(GemmArgs p, int ldk)
   }
 }
 
-int launch_small(hipStream_t s, const GemmArgs& a) {
-  const int ldk = a.k + 2;
-  const size_t lds = (size_t)(SM_BM + SM_BN) * ldk * sizeof(double);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_small),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)((SM_BM + SM_BN) * 130 * sizeof(double)));
-  GPK_HIP(attr);
-  unsigned gy = (unsigned)gpk_cdiv(a.m, SM_BM);
-  const unsigned gxs = (unsigned)gpk_cdiv(a.n, SM_BN);
-  if (a.max_wgs > 0 && gy * gxs > (unsigned)a.max_wgs) gy = ((unsigned)a.max_wgs + gxs - 1) / gxs;  // row blocks walked in-kernel
-  else if (a.small_loop && a.max_wgs <= 0 && gy * gxs > 512u) gy = (512u + gxs - 1) / gxs;
-  dim3 grid(gxs, gy, (unsigned)(a.batch > 0 ? a.batch : 1));
-  g_last_kind = 1;
-  hipLaunchKernelGGL(gemm_nt_small, grid, dim3(SM_THREADS), lds, s, a, ldk);
+// one launch of a tiled kernel (trailing arguments gx, gy, total, compact); its LDS limit is raised once (function-local static:
+// initialised once, thread-safe; MAX_LDS = 0: the default limit does)
+template <auto KERNEL, int MAX_LDS>
+int launch_tiled(hipStream_t s, dim3 grid, size_t lds_bytes, const GemmArgs& a, const GemmPlan& p, int total) {
+  if constexpr (MAX_LDS > 0) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
+    GPK_HIP(attr);
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds_bytes, s, a, p.gx, p.gy, total, p.compact);
   GPK_LAUNCH_CHECK();
   return 0;
 }
-
-// =====================================================================================================
-// Fused in-group solve of right-hand-side ROWS against a column group of the factor (nb <= 4 leaf blocks):
-//     for j = 0 .. nb-1:   S_j = E_j X_j^T                       (X_j = L_jj^-1, the leaf's block inverse)
-//                          E_j' -= S_j L_j'j^T   for j' > j       (the rest of the group)
-// i.e. exactly the 2 nb - 1 launches of the latency kernel above that the right-looking row solve issues per group
-// (4 solves + 3 updates at nb = 4), with the SAME arithmetic per element (two alternating accumulators over K = 128,
-// the update accumulated onto -C and negated) -- so the results are bit-identical -- but as ONE launch: a workgroup owns
-// 16 rows, keeps their nb x (16 x 128) panel in accumulator registers for the whole group (8 waves x one 16 x 16 tile
-// per block), and only the 10 operand tiles X_j / L_j'j stream through LDS.  The extra-row stream of an SVGP step spent
-// ~150 us per group in those seven dependent launches (mostly launch ramp and drain on a 256-CU chip); this is one.
-struct GroupSolveArgs {
-  const double* E; long lde;     // rows to solve, columns of the group start at E (in/out unless Eo differs)
-  double* Eo; long ldeo;         // solved rows out (may alias E)
-  const double* L; long ldl;     // L[c0, c0]: top-left element of the group's diagonal block
-  const double* X;               // block inverses of the group, consecutive [nb][128][128]
-  int rows, nb;
-  long strideE, strideEo, strideL, strideX;   // batched form (blockIdx.y = problem): element offsets between problems
-  int j0, j1;                                 // group_solve2_kernel: leaf blocks [j0, j1) are solved by THIS launch (the blocks before j0 by
-                                              // earlier ones); the updated, still unsolved blocks >= j1 go back to E (E == Eo then)
-};
-
-__global__ __launch_bounds__(512) void group_solve_kernel(GroupSolveArgs p) {
-  constexpr int LDK = 130, NBK = 128;
-  {
-    const long b = blockIdx.y;
-    p.E += b * p.strideE; p.Eo += b * p.strideEo; p.L += b * p.strideL; p.X += b * p.strideX;
-  }
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  double* As = smem;               // [16][LDK]
-  double* Bs = smem + 16 * LDK;    // [128][LDK]
-  // (gridDim.x < number of 16-row slivers: the workgroup walks the slivers with stride gridDim.x -- a cap on the resident
-  //  workgroups keeps compute units free for the factorisation's chain, GROUP_SOLVE_MAX_WGS in potrf.hip)
-  for (int m0 = blockIdx.x * 16; m0 < p.rows; m0 += gridDim.x * 16) {
-  if (m0 != (int)blockIdx.x * 16) __syncthreads();   // the previous sliver's last operand tile is no longer read
-  int rowi[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int rr = m0 + g + 4 * e;
-    rowi[e] = rr < p.rows ? rr : p.rows - 1;
-  }
-  const int colw = wave * 16 + r;  // this lane's column inside a 128-block
-  d4 c[4];
-#pragma unroll
-  for (int jb = 0; jb < 4; ++jb) {
-    if (jb < p.nb) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) c[jb][e] = p.E[(long)rowi[e] * p.lde + jb * NBK + colw];
-    }
-  }
-  const double* ap = As + r * LDK + g;
-  const double* bp = Bs + (wave * 16 + r) * LDK + g;
-  auto stage_b = [&](const double* src, long ld) {  // 128 rows of 128 doubles, one LDS-DMA instruction each
-    for (int q = wave; q < NBK; q += 8)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (long)q * ld + 2 * lane),
-                                       (__attribute__((address_space(3))) void*)(Bs + q * LDK), 16, 0, 0);
-  };
-  auto put_a = [&](const d4& v) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) As[(g + 4 * e) * LDK + colw] = v[e];
-  };
-  auto product = [&](d4& acc0, d4& acc1) {
-#pragma unroll 4
-    for (int kk = 0; kk < 32; kk += 2) {
-      const double a0 = ap[kk * 4], b0 = bp[kk * 4];
-      const double a1 = ap[kk * 4 + 4], b1 = bp[kk * 4 + 4];
-      acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc1, 0, 0, 0);
-    }
-  };
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (j >= p.nb) break;
-    // ---- S_j = E_j X_j^T ------------------------------------------------------------------------------------------
-    if (j > 0) __syncthreads();  // previous readers of As / Bs are done
-    put_a(c[j]);
-    stage_b(p.X + (long)j * NBK * NBK, NBK);
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): this wave's LDS-DMA rows have landed
-    __syncthreads();
-    d4 s0 = {0.0, 0.0, 0.0, 0.0}, s1 = {0.0, 0.0, 0.0, 0.0};
-    product(s0, s1);
-    d4 sj;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sj[e] = 1.0 * (s0[e] + s1[e]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int rr = m0 + g + 4 * e;
-      if (rr < p.rows) p.Eo[(long)rr * p.ldeo + j * NBK + colw] = sj[e];
-    }
-    if (j + 1 >= p.nb) break;
-    __syncthreads();  // everyone has read E_j / X_j
-    put_a(sj);
-    // ---- E_j' -= S_j L_j'j^T ----------------------------------------------------------------------------------------
-#pragma unroll
-    for (int jp = 1; jp < 4; ++jp) {
-      if (jp <= j || jp >= p.nb) continue;
-      if (jp > j + 1) __syncthreads();  // the previous operand tile is no longer read
-      stage_b(p.L + (long)jp * NBK * p.ldl + (long)j * NBK, p.ldl);
-      __builtin_amdgcn_s_waitcnt(0x0070);
-      __syncthreads();
-      d4 u0, u1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) u0[e] = -1.0 * c[jp][e];  // (beta / alpha) C with alpha = -1, beta = 1
-      product(u0, u1);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) c[jp][e] = -1.0 * (u0[e] + u1[e]);
-    }
-  }
-  }  // sliver loop
-}
-
-
-// Round 5: the same in-group solve with 32 rows per workgroup and the operand tiles PIPELINED through LDS.
-// The kernel above stages each 128 x 128 operand tile whole (133 KB, nothing else fits) and waits for it: 10 exposed L2 round trips
-// per 16-row sliver, 512 workgroups at one per compute unit = two rounds, ~111 us per 8192 x 512 group on the extra-row stream --
-// which is the critical path of the SVGP step from the fourth panel on (profiles/r05_step_timeline_before_extra_row_work.txt).  Here
-//   * a workgroup owns TWO 16-row tiles: every B fragment read from LDS feeds two MFMAs, 256 workgroups = one round at 8192 rows;
-//   * the operand tiles of all products of the group form ONE stream of K-quarters (128 rows x 32 K = 32 KB, up to 40 of them)
-//     that runs two quarters ahead of the MFMAs through a ring of three LDS buffers, across product boundaries -- their addresses
-//     do not depend on any result;
-//   * the quarters are unpadded; the 16-byte chunk c of tile row r sits in slot c ^ (r & 15) (the permutation is applied on the
-//     GLOBAL address of the LDS-DMA lane), so the 32 lanes of a ds_read_b64 group still hit 64 distinct banks.
-// Per element the arithmetic is unchanged (K ascending, two alternating accumulators, the update accumulated onto -C and negated).
-constexpr int GS2_LDK = 130;                     // A rows: 128 + 2 doubles
-template <int QK, int RING>
-constexpr size_t gs2_lds() { return (size_t)(32 * GS2_LDK + RING * 128 * QK) * sizeof(double); }
-
-// QK = K columns per pipeline stage.  32 (the only width instantiated): 40 stages of 16 MFMAs per wave, 132 KB of LDS (a compute
-// unit of its own).
-// s_waitcnt vmcnt(n * DPW) for a wave-uniform n in 0 .. NMAX (the instruction takes an immediate)
-template <int DPW, int NMAX>
-__device__ __forceinline__ void gs2_wait_vm(int n) {
-  if constexpr (NMAX > 0) {
-    if (n >= NMAX) {
-      constexpr int c = NMAX * DPW;
-      static_assert(c < 64, "vmcnt");
-      __builtin_amdgcn_s_waitcnt(0x0F70 | (c & 15) | ((c >> 4) << 14));
-      return;
-    }
-    gs2_wait_vm<DPW, NMAX - 1>(n);
-  } else {
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-  }
-}
-
-// RING = stage buffers; the operand stream runs RING - 1 stages ahead of the MFMAs.
-template <int QK, int RING>
-__global__ __launch_bounds__(512) void group_solve2_kernel(GroupSolveArgs p) {
-  constexpr int LDK = GS2_LDK, NBK = 128;
-  constexpr int AHEAD = RING - 1;
-  constexpr int NQ = NBK / QK;            // stages per product
-  constexpr int QELEMS = 128 * QK;        // doubles per stage buffer
-  constexpr int CH = QK / 2;              // 16-byte chunks per row of a stage
-  constexpr int DROWS = 64 / CH;          // rows per LDS-DMA instruction
-  constexpr int DPW = (128 / DROWS) / 8;  // LDS-DMA instructions per wave and stage
-  static_assert(QK == 32 || QK == 16, "stage width");
-  {
-    const long b = blockIdx.y;
-    p.E += b * p.strideE; p.Eo += b * p.strideEo; p.L += b * p.strideL; p.X += b * p.strideX;
-  }
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  double* As = smem;                 // [32][LDK]
-  double* Bq = smem + 32 * LDK;      // [RING][128][QK], chunk-swizzled
-  const int nb = p.nb, j0 = p.j0, j1 = p.j1;
-  int nprod = 0;
-  for (int j = j0; j < j1; ++j) nprod += nb - j;
-  const int nstages = NQ * nprod;
-  // swizzle of a tile row's chunks: QK = 32 -> row & 15 (16 chunks), QK = 16 -> (row >> 1) & 7 (8 chunks, two rows per 64 banks)
-  auto swz = [](int row) -> int { return QK == 32 ? (row & 15) : ((row >> 1) & 7); };
-  // LDS-DMA of one stage: 64 lanes x 16 bytes = DROWS rows x CH chunks per instruction.  The operand tiles come in issue order
-  // (j = j0: X_j0, L_(j0+1)j0, ...; then j0 + 1: ...), tracked by (pj, pjp, pq): block column, block row (pjp == pj: the block
-  // inverse X_pj), stage inside the tile.  Per lane only a 32-bit element offset inside the tile, for either row stride.
-  const int drow = lane / CH, dslot = lane % CH;
-  const int drow0 = wave * DPW * DROWS + drow;   // this lane's row in the wave's first copy; copy i adds i * DROWS
-  int issue = 0, pj = j0, pjp = j0, pq = 0;
-  auto issue_stage = [&]() {
-    if (issue < nstages) {
-      const bool isx = pjp == pj;
-      const double* src = (isx ? p.X + (long)pj * NBK * NBK : p.L + (long)pjp * NBK * p.ldl + (long)pj * NBK) + pq * QK;
-      const unsigned ld = isx ? (unsigned)NBK : (unsigned)p.ldl;   // (rows < 128, ld < 2^21: 32-bit element offsets)
-      double* dst = Bq + (issue % RING) * QELEMS;
-#pragma unroll
-      for (int i = 0; i < DPW; ++i) {
-        const int rb = wave * DPW + i;
-        const int row = drow0 + i * DROWS;
-        const double* gsrc = src + ((unsigned)row * ld + (unsigned)((dslot ^ swz(row)) << 1));
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                         (__attribute__((address_space(3))) void*)(dst + rb * 128), 16, 0, 0);
-      }
-      if (++pq == NQ) {
-        pq = 0;
-        if (pjp + 1 < nb) ++pjp;
-        else { ++pj; pjp = pj; }
-      }
-    }
-    ++issue;
-  };
-  // fragment addresses: B[row 16 w + r][k = 4 kk + g] of a stage -> chunk 2 kk + (g >> 1), half g & 1
-  const int brow = (wave * 16 + r) * QK + (g & 1);
-  const int bsw = swz(r), bgh = g >> 1;
-  const double* ap = As + r * LDK + g;
-  for (int m0 = blockIdx.x * 32; m0 < p.rows; m0 += gridDim.x * 32) {
-    if (m0 != (int)blockIdx.x * 32) __syncthreads();   // the previous sliver's buffers are no longer read
-    issue = 0; pj = j0; pjp = j0; pq = 0;
-    int cs = 0;
-#pragma unroll
-    for (int a = 0; a < AHEAD; ++a) issue_stage();
-    const int colw = wave * 16 + r;
-    int rowi[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int rr = m0 + 16 * t + g + 4 * e;
-        rowi[t][e] = rr < p.rows ? rr : p.rows - 1;
-      }
-    d4 c[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        if (jb >= j0 && jb < nb) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) c[t][jb][e] = p.E[(long)rowi[t][e] * p.lde + jb * NBK + colw];
-        }
-      }
-    auto put_a = [&](const d4& v0, const d4& v1) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        As[(g + 4 * e) * LDK + colw] = v0[e];
-        As[(16 + g + 4 * e) * LDK + colw] = v1[e];
-      }
-    };
-    // one stage of the current product: acc[t][0] takes the even K groups of four, acc[t][1] the odd ones
-    // The B rows a wave reads (tile rows 16 w .. 16 w + 15 = its output columns) are the rows IT copies: the operand stream needs
-    // no workgroup barrier at all, only the wave's own vmcnt -- the eight waves drift apart and fill each other's LDS waits.  The
-    // A rows are shared: one barrier after each put_a (first stage of a product whose A operand changed).
-    auto stage = [&](int q, d4 (&acc)[2][2], bool a_changed) {
-      // stage cs has landed when at most the stages behind it are in flight: min(AHEAD - 1, stages left) x DPW of this wave's copies
-      {
-        const int behind = nstages - 1 - cs < AHEAD - 1 ? nstages - 1 - cs : AHEAD - 1;
-        gs2_wait_vm<DPW, AHEAD - 1>(behind);
-      }
-      asm volatile("" ::: "memory");
-      if (a_changed) {
-        __builtin_amdgcn_s_waitcnt(0xC07F);                      // lgkmcnt(0): this wave's A rows are in LDS
-        __builtin_amdgcn_s_barrier();
-      }
-      issue_stage();   // stage cs + AHEAD replaces stage cs - 1 of this wave's rows, whose fragments it has consumed
-      // fragments double-buffered in registers, the three LDS reads of step kk + 1 between the two MFMAs of step kk.  (Measured
-      // and not kept: the same pipeline hand-issued three steps deep with counted lgkmcnt waits -- 64.3 against 62.3 us per launch,
-      // and rings of 5 / 7 stage buffers -- 72 - 84 us: neither the LDS round trip nor the L2 one is what a sliver waits for; the
-      // seven barrier pairs around the changes of the shared A rows and the 20-odd us of launch, load and store are.)
-      const double* bq = Bq + (cs % RING) * QELEMS + brow;
-      double fb[2], fa0[2], fa1[2];
-      auto frag = [&](int kk, int f) {
-        fb[f] = bq[((2 * kk + bgh) ^ bsw) << 1];
-        fa0[f] = ap[q * QK + kk * 4];
-        fa1[f] = ap[16 * LDK + q * QK + kk * 4];
-      };
-      frag(0, 0);
-#pragma unroll
-      for (int kk = 0; kk < QK / 4; ++kk) {
-        if (kk + 1 < QK / 4) frag(kk + 1, (kk + 1) & 1);
-        acc[0][kk & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa0[kk & 1], fb[kk & 1], acc[0][kk & 1], 0, 0, 0);
-        acc[1][kk & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa1[kk & 1], fb[kk & 1], acc[1][kk & 1], 0, 0, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // 1 MFMA
-        if (kk + 1 < QK / 4) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);   // 3 DS reads
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // 1 MFMA
-      }
-      ++cs;
-    };
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (j < j0) continue;
-      if (j >= j1) break;
-      // ---- S_j = E_j X_j^T --------------------------------------------------------------------------------------------
-      if (j > j0) __syncthreads();   // every wave has finished reading the previous A rows
-      put_a(c[0][j], c[1][j]);
-      d4 acc[2][2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) { acc[t][0] = (d4){0.0, 0.0, 0.0, 0.0}; acc[t][1] = (d4){0.0, 0.0, 0.0, 0.0}; }
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) stage(q, acc, q == 0);
-      d4 sj[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sj[t][e] = 1.0 * (acc[t][0][e] + acc[t][1][e]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int rr = m0 + 16 * t + g + 4 * e;
-          if (rr < p.rows) p.Eo[(long)rr * p.ldeo + j * NBK + colw] = sj[t][e];
-        }
-      }
-      if (j + 1 >= nb) break;
-      __syncthreads();   // everyone has read E_j
-      put_a(sj[0], sj[1]);
-      // ---- E_j' -= S_j L_j'j^T ----------------------------------------------------------------------------------------
-#pragma unroll
-      for (int jp = 1; jp < 4; ++jp) {
-        if (jp <= j || jp >= nb) continue;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[t][0][e] = -1.0 * c[t][jp][e];  // (beta / alpha) C with alpha = -1, beta = 1
-          acc[t][1] = (d4){0.0, 0.0, 0.0, 0.0};
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) stage(q, acc, q == 0 && jp == j + 1);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) c[t][jp][e] = -1.0 * (acc[t][0][e] + acc[t][1][e]);
-      }
-    }
-    // a partial launch hands the updated, unsolved blocks back (in place)
-#pragma unroll
-    for (int jp = 1; jp < 4; ++jp) {
-      if (jp < j1 || jp >= nb) continue;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int rr = m0 + 16 * t + g + 4 * e;
-          if (rr < p.rows) p.Eo[(long)rr * p.ldeo + jp * NBK + colw] = c[t][jp][e];
-        }
-    }
-  }  // sliver loop
-}
-
-template <int QK, int RING>
-int launch_group_solve2(hipStream_t s, const GroupSolveArgs& a, int rows, int batch, int max_wgs) {
-  static const hipError_t attr2 = hipFuncSetAttribute(reinterpret_cast<const void*>(group_solve2_kernel<QK, RING>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)gs2_lds<QK, RING>());
-  GPK_HIP(attr2);
-  unsigned gx2 = (unsigned)gpk_cdiv(rows, 32);
-  if (max_wgs > 0 && gx2 * (unsigned)batch > (unsigned)max_wgs) gx2 = (unsigned)std::max(1, max_wgs / batch);
-  constexpr size_t lds = gs2_lds<QK, RING>();
-  hipLaunchKernelGGL((group_solve2_kernel<QK, RING>), dim3(gx2, (unsigned)batch), dim3(512), lds, s, a);
-  GPK_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo, long ldeo, int rows, const double* Lgg, long ldl,
-                       const double* X, int nb, int batch, long strideE, long strideEo, long strideL, long strideX, int max_wgs,
-                       int j0, int j1) {
-  if (rows <= 0) return 0;
-  if (j1 < 0) j1 = nb;
-  if (j0 < 0 || j0 >= j1 || j1 > nb) return GPK_E_ARG;
-  if ((j0 > 0 || j1 < nb) && (E != Eo || lde != ldeo || strideE != strideEo || !gpk_group_solve_takes_parts())) return GPK_E_UNSUPPORTED;
-  if (batch < 1) batch = 1;
-  if (!E || !Eo || !Lgg || !X || nb < 1 || nb > 4) return GPK_E_ARG;
-  if ((ldl & 1) || (reinterpret_cast<uintptr_t>(Lgg) & 15) || (reinterpret_cast<uintptr_t>(X) & 15)) return GPK_E_UNSUPPORTED;
-  if (batch > 1 && ((strideL & 1) || (strideX & 1))) return GPK_E_UNSUPPORTED;   // (16-byte LDS-DMA of every problem's tiles)
-  constexpr size_t LDS = (size_t)(16 + 128) * 130 * sizeof(double);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(group_solve_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-  GPK_HIP(attr);
-  GroupSolveArgs a{};
-  a.E = E; a.lde = lde; a.Eo = Eo; a.ldeo = ldeo; a.L = Lgg; a.ldl = ldl; a.X = X; a.rows = rows; a.nb = nb;
-  a.strideE = strideE; a.strideEo = strideEo; a.strideL = strideL; a.strideX = strideX;
-  a.j0 = j0; a.j1 = j1;
-  // Which kernel: the pipelined one (32 rows per workgroup) runs its 10 block products in ~63 us whatever the row count; the
-  // staged one (16 rows) needs ~45 us per ROUND of 256 workgroups (one per CU).  tools/group_solve_probe.py, 512 columns, us:
-  //   rows 1024: 41 / 62   2048: 47 / 64   4096: 54 / 66   8192: 101 / 74   (staged / pipelined)
-  // so the pipelined kernel takes over where the staged one would need a second round.  (The first version of this switch sent
-  // everything to the pipelined kernel: the 1024- / 2048- / 4096-row rank shards of the strong-scaling workload lost 5 / 9 / 5 %.)
-  const bool partial = j0 > 0 || j1 < nb;
-  const long slivers16 = (long)gpk_cdiv(rows, 16) * batch;
-  if (GPK_TUNE(GROUP_SOLVE_V2, 1) && (partial || slivers16 > GPK_TUNE(GROUP_SOLVE_V2_MIN_SLIVERS, 256))) {
-    // (stage width 16 and a ring of 5: DESIGN 6, "Closed experiments whose code was removed")
-    return launch_group_solve2<32, 3>(s, a, rows, batch, max_wgs);
-  }
-  unsigned gx = (unsigned)gpk_cdiv(rows, 16);
-  if (max_wgs > 0 && gx * (unsigned)batch > (unsigned)max_wgs) gx = (unsigned)std::max(1, max_wgs / batch);
-  hipLaunchKernelGGL(group_solve_kernel, dim3(gx, (unsigned)batch), dim3(512), LDS, s, a);
-  GPK_LAUNCH_CHECK();
-  return 0;
-}
-
-// small-K latency path: K <= 128 in whole 16-slabs, 16-byte aligned rows, modest row count
-bool small_ok(const GemmArgs& a) {
-  if (GPK_TUNE(GEMM_NO_SMALL, 0) || a.epi != 0) return false;
-  if (a.k <= 0 || a.k > 128 || (a.k & 15) || (a.b_tri && (a.b_tri_off & 15)) || a.k_off_step) return false;
-  if ((a.lda & 1) || (a.ldb & 1) || (a.strideA & 1) || (a.strideB & 1)) return false;
-  if ((reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.B) & 15)) return false;
-  if (a.beta != 0.0 && a.alpha == 0.0) return false;
-  const long max_wgs = GPK_TUNE(SMALL_MAX_WGS, 512);
-  if (a.small_loop && a.batch <= 1) return true;
-  return (long)gpk_cdiv(a.m, SM_BM) * gpk_cdiv(a.n, SM_BN) * (a.batch > 0 ? a.batch : 1) <= max_wgs && a.batch < 65536;
-}
-
 template <int BM, int BN, int WGM, int WGN>
-int launch_cfg(hipStream_t s, const GemmArgs& a) {
-  using Cfg = TileCfg<BM, BN, WGM, WGN>;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_kernel<BM, BN, WGM, WGN>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES);
-  GPK_HIP(attr);
-  const int gx = gpk_cdiv(a.n, BN), gy = gpk_cdiv(a.m, BM);
-  if (gx <= 0 || gy <= 0) return 0;
-  int total = gx * gy, compact = 0;
-  if (a.c_lower && BM == BN && a.epi == 0) {
-    compact = 1;
-    total = 0;
-    for (int first = 0; first < gx; first += GROUP_N) {
-      const int gsz = (gx - first) < GROUP_N ? (gx - first) : GROUP_N;
-      const int avail = gy - first;
-      if (avail <= 0) break;
-      const int tr = avail < gsz ? avail : gsz;
-      total += tr * (tr + 1) / 2 + (avail > gsz ? (avail - gsz) * gsz : 0);
-    }
-    if (total <= 0) return 0;
-  }
+int launch_generic(hipStream_t s, dim3 grid, const GemmArgs& a, const GemmPlan& p, int total) {
+  constexpr size_t LDS = TileCfg<BM, BN, WGM, WGN>::LDS_BYTES;
+  static_assert(LDS == gemm_tile_lds(BM, BN), "the plan's LDS bytes are the kernel's");
+  return launch_tiled<gemm_nt_kernel<BM, BN, WGM, WGN>, (int)LDS>(s, grid, LDS, a, p, total);
+}
+
+// Carries out what make_gemm_plan decided (gemm_plan.h): no decision is taken here.
+int launch_plan(hipStream_t s, const GemmArgs& a, const GemmPlan& p) {
+  if (p.kernel == GemmKernel::none) return 0;
+  if (p.kernel == GemmKernel::unsupported) return GPK_E_UNSUPPORTED;
   GemmArgs b = a;
-  unsigned gridx = (unsigned)total;
-  if (b.tile_snake) {   // (see the kernel: needs whole rounds of 256 workgroups per batch entry, or a single problem)
-    const int nbatch = a.batch > 0 ? a.batch : 1;
-    if (a.b_tri != 1 || compact || total < 256 || (total == 256 && nbatch < 2)) b.tile_snake = 0;
-    else if ((gy & 7) == 0 && (total & 255) == 0) b.tile_snake = 2;
-    else if (nbatch == 1) { b.tile_snake = 1; gridx = (unsigned)((total + 255) & ~255); }
-    else b.tile_snake = 0;
+  b.tile_snake = p.tile_snake; b.stagger_first = p.stagger_first; b.stagger_ticks = p.stagger_ticks; b.pair_k_align = p.pair_k_align;
+  const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+  switch (p.kernel) {
+    case GemmKernel::small: {
+      static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_small),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                         (int)((SM_BM + SM_BN) * 130 * sizeof(double)));
+      GPK_HIP(attr);
+      hipLaunchKernelGGL(gemm_nt_small, grid, dim3(p.threads), p.lds_bytes, s, b, p.ldk);
+      GPK_LAUNCH_CHECK();
+      return 0;
+    }
+    case GemmKernel::pre64: return launch_tiled<gemm_nt_pre64, 0>(s, grid, p.lds_bytes, b, p, p.total);
+    case GemmKernel::generic:
+      switch (p.tile) {
+        case GemmTile::t128x128: return launch_generic<128, 128, 2, 2>(s, grid, b, p, p.total);
+        case GemmTile::t128x64: return launch_generic<128, 64, 2, 2>(s, grid, b, p, p.total);
+        case GemmTile::t64x128_1x4: return launch_generic<64, 128, 1, 4>(s, grid, b, p, p.total);
+        case GemmTile::t64x128_2x2: return launch_generic<64, 128, 2, 2>(s, grid, b, p, p.total);
+        case GemmTile::t64x64: return launch_generic<64, 64, 4, 1>(s, grid, b, p, p.total);
+        case GemmTile::t32x64: return launch_generic<32, 64, 2, 2>(s, grid, b, p, p.total);
+      }
+      return GPK_E_UNSUPPORTED;
+    default: break;   // fast
   }
-  dim3 grid(gridx, (unsigned)(a.batch > 0 ? a.batch : 1), 1);
-  g_last_kind = 6;
-  hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WGM, WGN>), grid, dim3(256), Cfg::LDS_BYTES, s, b, gx, gy, total,
-                     compact);
-  GPK_LAUNCH_CHECK();
-  return 0;
+  // (unpaired capped launches ask for more LDS than the tile needs: the limit of the unpaired walk is the whole 160 KB)
+  constexpr int FAST = (int)kGemmFastLds, WHOLE = 160 * 1024;
+  if (p.queue) {
+    unsigned qbase = 0;
+    GPK_TRY(queue_slot(p.queue_fetches, &b.queue, &qbase));
+    b.queue_base = (int)qbase;
+    return launch_tiled<gemm_nt_fast<0, false, true>, FAST>(s, grid, p.lds_bytes, b, p, p.total);
+  }
+  int rc = GPK_E_UNSUPPORTED;
+  switch (4 * p.epi + 2 * p.pair + p.sp) {
+    case 0: rc = launch_tiled<gemm_nt_fast<0, false, false, 0>, WHOLE>(s, grid, p.lds_bytes, b, p, p.total); break;
+    case 2: rc = launch_tiled<gemm_nt_fast<0, true, false, 0>, FAST>(s, grid, p.lds_bytes, b, p, p.total); break;
+    case 4: rc = launch_tiled<gemm_nt_fast<1, false, false, 0>, WHOLE>(s, grid, p.lds_bytes, b, p, p.total); break;
+    case 5: rc = launch_tiled<gemm_nt_fast<1, false, false, 1>, WHOLE>(s, grid, p.lds_bytes, b, p, p.total); break;
+    case 6: rc = launch_tiled<gemm_nt_fast<1, true, false, 0>, FAST>(s, grid, p.lds_bytes, b, p, p.total); break;
+    case 7: rc = launch_tiled<gemm_nt_fast<1, true, false, 1>, FAST>(s, grid, p.lds_bytes, b, p, p.total); break;
+  }
+  if (rc || p.tail_tiles == 0) return rc;
+  GemmArgs t = a;   // (the caller's args: the quarters of the last, partial round)
+  t.tail_first1 = p.tail_first1;
+  return launch_generic<64, 64, 4, 1>(s, dim3(p.tail_grid_x, 1, 1), t, p, (int)p.tail_grid_x);
 }
 
 }  // namespace
 
 int gpk_gemm_tiles_n(int n) { return gpk_cdiv(n, 128); }
-bool gpk_gemm_takes_latency_kernel(const GemmArgs& a) { return a.m > 0 && a.n > 0 && !a.no_small && small_ok(a); }
-
-int gpk_launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo, long ldeo, int rows, const double* Lgg, long ldl,
-                           const double* X, int nb, int batch, long strideE, long strideEo, long strideL, long strideX, int max_wgs,
-                           int j0, int j1) {
-  return launch_group_solve(s, E, lde, Eo, ldeo, rows, Lgg, ldl, X, nb, batch, strideE, strideEo, strideL, strideX, max_wgs, j0, j1);
+bool gpk_gemm_takes_latency_kernel(const GemmArgs& a) { return make_gemm_plan(a).kernel == GemmKernel::small; }
+bool gpk_gemm_fuses_row_stats(const GemmArgs& a) {
+  const GemmPlan p = make_gemm_plan(a);
+  return p.kernel == GemmKernel::fast && p.sp;
 }
-// (only the pipelined kernel, group_solve2, solves blocks [j0, j1) of a group and hands the later blocks back updated)
-bool gpk_group_solve_takes_parts() { return GPK_TUNE(GROUP_SOLVE_V2, 1) != 0; }
 
 // ---- optional per-launch timing (bench.py roofline leg): HIP events around every GEMM launch, on the
 // stream the kernel is launched on.  Off by default; adds two event records per launch when on. -------
@@ -1708,6 +1139,25 @@ double algorithmic_flops(const GemmArgs& a) {
   }
   return 2.0 * outs * kk * (a.batch > 0 ? a.batch : 1);
 }
+
+// total_ms / launches / flops of the recorded launches with at least min_flops (any_kind, or those of kernel `kind`); synchronises the device
+int prof_collect(bool any_kind, int kind, double min_flops, double* total_ms, long* launches, double* flops) {
+  GPK_HIP(hipDeviceSynchronize());
+  double ms = 0.0, fl = 0.0;
+  long cnt = 0;
+  for (int i = 0; i < g_prof_n; ++i) {
+    if ((!any_kind && g_prof[i].kind != kind) || g_prof[i].flops < min_flops) continue;
+    float t = 0.f;
+    GPK_HIP(hipEventElapsedTime(&t, g_prof[i].e0, g_prof[i].e1));
+    ms += t;
+    fl += g_prof[i].flops;
+    ++cnt;
+  }
+  if (total_ms) *total_ms = ms;
+  if (launches) *launches = cnt;
+  if (flops) *flops = fl;
+  return 0;
+}
 }  // namespace
 
 int gpk_profile_gemm_is_on() { return g_prof_on ? 1 : 0; }
@@ -1721,20 +1171,7 @@ extern "C" void gpk_profile_gemm_enable(int on) {
 // least min_flops (0 = all); synchronises the device.  keep != 0 leaves the records in place for another query.
 extern "C" int gpk_profile_gemm_collect_min(double min_flops, int keep, double* total_ms, long* launches,
                                             double* flops) {
-  GPK_HIP(hipDeviceSynchronize());
-  double ms = 0.0, fl = 0.0;
-  long cnt = 0;
-  for (int i = 0; i < g_prof_n; ++i) {
-    if (g_prof[i].flops < min_flops) continue;
-    float t = 0.f;
-    GPK_HIP(hipEventElapsedTime(&t, g_prof[i].e0, g_prof[i].e1));
-    ms += t;
-    fl += g_prof[i].flops;
-    ++cnt;
-  }
-  if (total_ms) *total_ms = ms;
-  if (launches) *launches = cnt;
-  if (flops) *flops = fl;
+  GPK_TRY(prof_collect(true, 0, min_flops, total_ms, launches, flops));
   if (!keep) g_prof_n = 0;
   return 0;
 }
@@ -1768,27 +1205,11 @@ extern "C" int gpk_profile_gemm_window(double min_flops, double* window_ms, doub
 // the same, restricted to launches of ONE kernel (kind: 1 gemm_nt_small, 2 gemm_nt_fast<0,false>, 3 <0,true>, 4 <1,false>,
 // 5 <1,true>, 6 gemm_nt_kernel) -- directly comparable with rocprofv3's per-kernel average.  Records are kept.
 extern "C" int gpk_profile_gemm_collect_kind(int kind, double min_flops, double* total_ms, long* launches, double* flops) {
-  GPK_HIP(hipDeviceSynchronize());
-  double ms = 0.0, fl = 0.0;
-  long cnt = 0;
-  for (int i = 0; i < g_prof_n; ++i) {
-    if (g_prof[i].kind != kind || g_prof[i].flops < min_flops) continue;
-    float t = 0.f;
-    GPK_HIP(hipEventElapsedTime(&t, g_prof[i].e0, g_prof[i].e1));
-    ms += t;
-    fl += g_prof[i].flops;
-    ++cnt;
-  }
-  if (total_ms) *total_ms = ms;
-  if (launches) *launches = cnt;
-  if (flops) *flops = fl;
-  return 0;
+  return prof_collect(false, kind, min_flops, total_ms, launches, flops);
 }
 extern "C" int gpk_profile_gemm_collect(double* total_ms, long* launches, double* flops) {
   return gpk_profile_gemm_collect_min(0.0, 0, total_ms, launches, flops);
 }
-
-static int launch_select(hipStream_t s, const GemmArgs& a);
 
 // grow the record table of the profiling facility.  The table pointer is published right after realloc (the old block may
 // have moved) and the capacity only ever covers records whose two events exist: a failed hipEventCreate leaves a shorter,
@@ -1810,8 +1231,8 @@ static int prof_grow() {
 }
 
 int gpk_launch_gemm(hipStream_t s, const GemmArgs& a) {
-  if (a.m <= 0 || a.n <= 0) return 0;
-  if (!g_prof_on) return launch_select(s, a);
+  const GemmPlan plan = make_gemm_plan(a);
+  if (!g_prof_on || plan.kernel == GemmKernel::none) return launch_plan(s, a, plan);
   if (g_prof_n == g_prof_cap) {
     const int rcg = prof_grow();
     if (rcg) return rcg;
@@ -1819,73 +1240,13 @@ int gpk_launch_gemm(hipStream_t s, const GemmArgs& a) {
   }
   ProfRec& r = g_prof[g_prof_n++];
   r.flops = algorithmic_flops(a);
+  r.kind = plan.kind;
   GPK_HIP(hipEventRecord(r.e0, s));
-  const int rc = launch_select(s, a);
-  r.kind = g_last_kind;
+  const int rc = launch_plan(s, a, plan);
   GPK_HIP(hipEventRecord(r.e1, s));
   return rc;
 }
 
-// under-filled projections leave gemm_nt_fast for the generic kernel's small tiles (launch_select)
-static bool proj_small_tiles(const GemmArgs& a) {
-  if (!(a.epi == 1 && a.b_tri == 1 && !(a.beta != 0.0 && a.C) && a.m > 64)) return false;
-  const long pairs = (long)((gpk_cdiv(a.n, 128) + 1) / 2) * gpk_cdiv(a.m, 128) * (a.batch > 0 ? a.batch : 1);
-  return pairs < GPK_TUNE(PROJ_SMALL_TILE_BELOW, 200);
-}
-
-// Row statistics ride along (GemmArgs::stat_*) where launch_select ends in launch_fast<1> AND the workgroup of column tile 0 walks
-// the whole K range: no K split, no structure in A, B dense or upper-triangular from column 0.
-bool gpk_gemm_fuses_row_stats(const GemmArgs& a) {
-  if (a.epi != 1 || !a.stat_sumsq || !a.stat_mv || !a.stat_V || a.stat_P < 1 || a.stat_P > 4) return false;
-  if (a.m <= 0 || a.n <= 0 || a.k_off_step || a.a_tri || a.b_tri == 2 || (a.b_tri == 1 && a.b_tri_off != 0)) return false;
-  if ((a.beta != 0.0 && a.C) || a.batch != a.stat_P || (a.batch > 1 && a.strideA != 0)) return false;   // (batch entry p = latent p of one shared A)
-  return !proj_small_tiles(a) && fast_ok(a);
-}
-
-static int launch_select(hipStream_t s, const GemmArgs& a) {
-  if (a.stat_sumsq && !gpk_gemm_fuses_row_stats(a)) return GPK_E_UNSUPPORTED;   // (the caller asks first: drivers.hip, project_parts)
-  const long tiles = (long)gpk_cdiv(a.m, 128) * gpk_cdiv(a.n, 128) * (a.batch > 0 ? a.batch : 1);
-  if (a.tile64 && a.epi == 0) {
-    if (GPK_TUNE(REST_PRE64, 1) && pre64_ok(a)) return launch_pre64(s, a);
-    return launch_cfg<64, 64, 4, 1>(s, a);
-  }
-  if (!a.no_small && small_ok(a)) return launch_small(s, a);  // K <= 128, <= 512 workgroups: the latency path
-  if (a.epi == 1 && a.beta != 0.0 && a.C && !fast_ok(a)) return GPK_E_UNSUPPORTED;  // only the fast tile preloads C for epi 1
-  if (a.epi == 0 && a.k >= GPK_TUNE(HALF_TILE_KMIN, 1024) && a.m > 64 && a.n > 64 && (a.max_wgs == 0 || a.max_wgs >= tiles)) {
-    // under-filled long-K launches (the M^3 triangular products of the reverse pass: 256 tiles of 128 x 128 = ONE
-    // workgroup per CU, so the launch lasts as long as its longest tile, 283 us at M = 2048) go to 64 x 128 tiles:
-    // twice the workgroups, half the longest tile.  Training step 7.15 -> 6.90 ms (same box, 300; 600: 7.00).
-    const long eff = a.c_lower ? tiles / 2 : tiles;
-    if (eff < GPK_TUNE(HALF_TILE_BELOW, 300)) return launch_cfg<64, 128, 1, 4>(s, a);
-  }
-  if (proj_small_tiles(a)) {
-    // under-filled projections (a rank's 1024-row shard of a strong-scaled step: 8 row tiles x 8 column pairs = 64
-    // workgroups, ONE of them per four CUs, 296 us for 4.3 GFLOP; a CU cannot finish a 128 x 128 x 16 slab in less than
-    // 1.7 us however many workgroups it holds): 64 x 64 tiles, unpaired -- sixteen times the workgroups.
-    // tools/proj_small_probe.py (profiles/r03_projection_few_rows.txt), paired 128-row tiles / 64 x 128 / 64 x 64:
-    // 1024 x 2048: 296 / 194 / 155 us, 300 x 1024 (P = 2): 162 / 98 / 62 us, 2048 x 2048: 306 / 268 / 221 us; from 256 pairs
-    // on the paired 128-row tiles win (4096 x 2048: 327 us against 483 us on 64 x 128).
-    const long pairs = (long)((gpk_cdiv(a.n, 128) + 1) / 2) * gpk_cdiv(a.m, 128) * (a.batch > 0 ? a.batch : 1);
-    // (every 64-column partial slot the reduction reads must be written: 64-wide tiles only if they cover the same
-    // slots as the 128-wide ones, else 64 x 128 tiles)
-    GemmArgs b = a;
-    b.tile_snake = GPK_TUNE(PROJ_SNAKE, 1);
-    if (gpk_cdiv(a.n, 64) == 2 * gpk_cdiv(a.n, 128)) {
-      if (pairs < GPK_TUNE(PROJ_TILE32_BELOW, 100)) return launch_cfg<32, 64, 2, 2>(s, b);
-      return launch_cfg<64, 64, 4, 1>(s, b);
-    }
-    return launch_cfg<64, 128, 2, 2>(s, b);
-  }
-  if (fast_ok(a) && (a.epi == 1 || (a.n > 64 && (tiles >= 24 || a.m <= 64)))) {
-    return a.epi == 1 ? launch_fast<1>(s, a) : launch_fast<0>(s, a);
-  }
-  if (a.epi == 1) return launch_cfg<128, 128, 2, 2>(s, a);
-  if (a.n <= 64) return launch_cfg<128, 64, 2, 2>(s, a);
-  // narrow / small problems: 64-row tiles double the number of workgroups (256 CUs to fill)
-  const long tiles128 = (long)gpk_cdiv(a.m, 128) * gpk_cdiv(a.n, 128) * (a.batch > 0 ? a.batch : 1);
-  if (tiles128 < 192 && a.m > 64) return launch_cfg<64, 128, 1, 4>(s, a);
-  return launch_cfg<128, 128, 2, 2>(s, a);
-}
 
 
 namespace {

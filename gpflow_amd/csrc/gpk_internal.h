@@ -39,70 +39,13 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 static inline size_t gpk_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int gpk_cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// ---- GEMM (gemm.hip):  C = alpha * A * B^T + beta * C ----------------------------------------
-struct GemmArgs {
-  const double* A; long lda; long strideA;   // [m,k]
-  const double* B; long ldb; long strideB;   // [n,k]
-  double* C; long ldc; long strideC;         // [m,n]
-  int m, n, k;
-  double alpha, beta;
-  int c_lower;      // skip tiles strictly above the diagonal (row r / col c of C: skip if c0 > r_last)
-  int b_tri;        // 0 dense, 1 B[j,kk]==0 for kk<j, 2 B[j,kk]==0 for kk>j (+ b_tri_off on kk)
-  int a_tri;        // structure of A, a hint that only shortens the K range of a tile: 1 A[i,kk]==0 for kk<i (upper), 2 for kk>i (lower)
-  int b_tri_off;    // the triangular structure is B[j,kk] vs kk - b_tri_off
-  int b_tri_rows;   // structure applies to rows j < b_tri_rows of B only (rows beyond are dense)
-  int k_off_step;   // batch entry z is the K chunk [z k_off_step, z k_off_step + k) of ONE product: a_tri / b_tri refer to the unsplit column index
-  // epilogue 1 ("project"): columns < sq_cols are squared and row-summed into part[(tile_n*2+wn), row];
-  // columns >= sq_cols (the q_mu rows of the operand) are stored to C2[row, col - sq_cols]; C unused.
-  int epi;
-  int sq_cols;
-  double* part; long part_ld; long stridePart;   // [2*tiles_n, m]
-  double* C2; long ldc2; long strideC2; int c2_cols;
-  // epilogue 1 on gemm_nt_fast only (ask gpk_gemm_fuses_row_stats): the row statistics of A ride along.  The workgroup of column
-  // tile 0 walks all of [0, k) with its A slabs staged in registers; it also forms  stat_sumsq[r] = sum_k A[r,k]^2  and
-  // stat_mv[r, p] = sum_k A[r,k] stat_V[k, p]  (stat_V [k, stat_P] row-major, stat_P = batch <= 4) and writes them itself: one wave per
-  // row, fixed order, no atomics.  The batch shares A (strideA = 0): entry p forms column p of stat_mv, entry 0 stat_sumsq as well.
-  double* stat_sumsq; double* stat_mv; const double* stat_V; int stat_P;
-  int batch;
-  int stagger_first;  // fast path only: number of CUs the launch stream may use (first workgroup of the 2nd resident set), 0 = 256
-  int stagger_ticks;  // fast path only: start delay (100 MHz ticks) of the second resident workgroup set, 0 = none
-  int no_small;     // never take the one-shot LDS-DMA latency kernel (150 KB of LDS per workgroup: needs a CU free of GEMM workgroups)
-  int small_loop;   // K <= 128 launches with MORE than 512 row slivers may still take the one-shot latency kernel: its workgroups
-                    // then walk the row blocks with their B tile staged once (the in-group updates of the extra rows)
-  int max_wgs;      // fast path only: cap on the number of (persistent) workgroups per batch entry, 0 = one per tile
-  int pair_k_align; // set by the launcher for paired triangular-K launches: time-aligned K traversal (gemm_nt_fast)
-  // In-kernel stream hand-offs of the factorisation's latency chain (one-shot latency kernel only; potrf.hip, round 5).  An
-  // event record / wait between two kernels of one stream costs 4.6 / 6.3 us on MI355X, back-to-back kernels 0.3 us:
-  //   sig_ptr:  workgroup (0,0,0) stores sig_val there on entry -- "everything queued before this kernel on its stream has
-  //             completed" (in-order queue: the previous kernel's end-of-kernel release is done), read by
-  //             hipStreamWaitValue32 on other streams or by another kernel's wait_ptr (every GEMM kernel honours sig_ptr);
-  //   wait_ptr: every workgroup spins (bounded) until (int)(*wait_ptr - wait_val) >= 0, then acquires at agent scope: the
-  //             word is written by hipStreamWriteValue32 behind the producing kernel on ITS stream.
-  int* sig_ptr; int sig_val;
-  const int* wait_ptr; int wait_val;
-  int* wait_info;   // device int that receives INT_MAX if the bounded wait expires (the factorisation's status word)
-  int tile_queue;   // fast path, epi 0: persistent workgroups that take their tiles from a device counter (launches with more than 512 tiles)
-  int* queue; int queue_base;   // set by the launcher only: that counter and its value before this launch
-  int tile64;       // epi 0 only (flag): take the generic kernel's 64 x 64 tiles (36 KB of LDS per workgroup: fits beside any other workgroup on a CU)
-  int tile_snake;   // set by the launcher only (generic kernel, under-filled triangular-K projections): heavy / light tiles alternate per CU
-  int tail_first1;  // set by the launcher only (generic 64 x 64 kernel; launch_fast, "tail split"): 1 + first position, 0 = off
-};
-static inline GemmArgs gemm_base(int m, int n, int k, double alpha, const double* A, long lda,
-                                 const double* B, long ldb, double beta, double* C, long ldc, int batch,
-                                 long sA, long sB, long sC) {
-  GemmArgs g{};
-  g.A = A; g.lda = lda; g.strideA = sA;
-  g.B = B; g.ldb = ldb; g.strideB = sB;
-  g.C = C; g.ldc = ldc; g.strideC = sC;
-  g.m = m; g.n = n; g.k = k; g.alpha = alpha; g.beta = beta;
-  g.b_tri_rows = n; g.batch = batch > 0 ? batch : 1;
-  return g;
-}
+// ---- GEMM (gemm.hip): GemmArgs, gemm_base and the selection as data (GemmPlan, make_gemm_plan) --------
+#include "gemm_plan.h"
 int gpk_launch_gemm(hipStream_t s, const GemmArgs& a);
-bool gpk_gemm_takes_latency_kernel(const GemmArgs& a);   // the launch would run on the one-shot latency kernel (sig / wait honoured)
-bool gpk_gemm_fuses_row_stats(const GemmArgs& a);        // an epi 1 launch with stat_* set would run on gemm_nt_fast and fill them (else: GPK_E_UNSUPPORTED)
+bool gpk_gemm_takes_latency_kernel(const GemmArgs& a);   // make_gemm_plan(a) picks the one-shot latency kernel (sig / wait honoured)
+bool gpk_gemm_fuses_row_stats(const GemmArgs& a);        // make_gemm_plan(a) picks gemm_nt_fast<1> with the row statistics riding along (stat_* set and not this: GPK_E_UNSUPPORTED)
 
-// fused in-group solve of `rows` right-hand-side rows against nb <= 4 leaf blocks of the factor (gemm.hip); E / Eo point at
+// fused in-group solve of `rows` right-hand-side rows against nb <= 4 leaf blocks of the factor (group_solve.hip); E / Eo point at
 // the group's first column, Lgg at L[c0, c0], X at the group's first block inverse
 // (batch > 1: blockIdx.y walks the problems, strides in elements)
 int gpk_launch_group_solve(hipStream_t s, const double* E, long lde, double* Eo, long ldeo, int rows, const double* Lgg, long ldl,
