@@ -39,11 +39,11 @@ LOG2PI = float(np.log(2.0 * np.pi))
 # each) and {Lm_bar -> Cholesky adjoint -> Kuu adjoint} (M^3 products of 256 tiles: one workgroup per CU, time of the
 # longest tile).  On a device they run on two streams so that the under-filled launches share the chip.
 OVERLAP_BRANCHES = True
-# the side branch's chip-filling GEMMs start only when the main branch's HBM-bound preparation is enqueued (svgp_elbo_and_grad)
+# the side branch's chip-filling GEMMs start only when the main branch's HBM-bound preparation is enqueued (_SideBranch.release)
+GATE_SIDE_BRANCH = os.environ.get("GPFLOW_AMD_GATE_SIDE_BRANCH", "1") != "0"
 # K chunks of the triangular x triangular products of the Cholesky adjoint (1 = unsplit)
 TRI_PRODUCT_CHUNKS = int(os.environ.get("GPFLOW_AMD_TRI_PRODUCT_CHUNKS", "4"))
 TRI_PRODUCT_MIN_N = 1024   # below this the unsplit launches are short anyway
-GATE_SIDE_BRANCH = os.environ.get("GPFLOW_AMD_GATE_SIDE_BRANCH", "1") != "0"
 _side_streams: Dict[int, "torch.cuda.Stream"] = {}
 
 
@@ -102,7 +102,7 @@ def cholesky_adjoint(LT: torch.Tensor, LinvT: torch.Tensor, Lbar: torch.Tensor, 
     """Symmetric K_bar with  <K_bar, dK> = <L_bar, dL>  for K = L L^T:  K_bar = sym(L^-T Phi(L^T L_bar) L^-1), with
     LT = L^T, LinvT = L^-T (both upper, zero below the diagonal) and L_bar lower.  Three triangular-K GEMMs; the
     explicit inverse comes for free from the factorisation (identity rows appended to the trapezoid).
-    before_products: called once the HBM-bound preparation is enqueued (see svgp_elbo_and_grad: the side branch's big GEMM is gated on it)."""
+    before_products: called once the HBM-bound preparation is enqueued (see _SideBranch.release: the side branch's big GEMM is gated on it)."""
     # every B operand below is the transpose of a lower-triangular matrix: B[j, kk] = 0 for kk < j  -> b_tri = 1
     # (a_tri: A is triangular as well -- upper L^T / L^-T, lower Phi -- so a tile's K range is the intersection of both)
     LbarT = ops.transpose(Lbar)
@@ -186,14 +186,16 @@ def stationary_kernel_adjoint(A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Ten
     return dvar, dls, Abar
 
 
-se_kernel_adjoint = stationary_kernel_adjoint   # (the name of rounds 1-2)
+def _ls_grad(dl: torch.Tensor, ls) -> torch.Tensor:
+    """d/dlengthscales as the member holds them: an isotropic member has ONE lengthscale, the sum of the per-column entries"""
+    return dl.sum().reshape(1) if np.size(ls) == 1 else dl
 
 
 class KernelSpec:
     """What the reverse pass needs to know about the covariance function: ONE stationary kernel, or a Sum / Product of
     stationary kernels -- flat, or nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220 `Sum`, :305-315 `Product`; the reference
     differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).  members: [(family, variance,
-    lengthscales)], op: None | "add" | "mul".
+    lengthscales)], op: None | "add" | "mul" | tree.
 
       build    the combined matrix, members folded in place by `gpk_kernel_matrix_combine` (no second matrix);
       kdiag    K(x, x): sum or product of the variances (stationary members), dkdiag[i] = d kdiag / d variance_i;
@@ -207,14 +209,14 @@ class KernelSpec:
         self.members = [(f, float(v), np.asarray(ls, dtype=np.float64)) for f, v, ls in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
-        # (k0 + k1) * k2 (kernels/base.py:223-329: a Combination holds kernels, which may be Combinations of the other kind)
-        self.tree = None
-        if isinstance(op, (tuple, list)):
-            self.tree = self._check_tree(op, len(self.members))
-            op = None
-        self.op = op if len(self.members) > 1 else None
-        if self.tree is None and len(self.members) > 1 and op not in ("add", "mul"):
+        # (k0 + k1) * k2 (kernels/base.py:223-329: a Combination holds kernels, which may be Combinations of the other kind).
+        # Kept as ONE tree: the leaf 0 for one member (whatever combination is wrapped round it), (op, [0 .. n-1]) for a flat one.
+        n = len(self.members)
+        if op in ("add", "mul"):
+            op = (op, list(range(n)))
+        elif n > 1 and not isinstance(op, (tuple, list)):
             raise ValueError("a kernel combination needs op 'add' or 'mul'")
+        self.tree = 0 if n == 1 else self._check_tree(op, n)
         cols = [None] * len(self.members) if cols is None else list(cols)
         if len(cols) != len(self.members):
             raise ValueError("one column selection per member")
@@ -242,68 +244,6 @@ class KernelSpec:
             raise ValueError("every member must appear exactly once in the combination tree")
         return out
 
-    # ---- nested combinations: the same three operations, recursively over the tree -----------------------------------
-    def _build_node(self, node, X1, X2, out):
-        if isinstance(node, int):
-            f, v, ls = self.members[node]
-            return ops.kernel_matrix(self._sl(node, X1), self._sl(node, X2), variance=v, lengthscales=ls, family=f, diag_add=0.0,
-                                     lower_only=False, out=out)
-        op, ch = node
-        out = self._build_node(ch[0], X1, X2, out)
-        for c in ch[1:]:
-            if isinstance(c, int):      # a stationary member folds in place (K recomputed in registers, no second matrix)
-                f, v, ls = self.members[c]
-                ops.kernel_matrix_combine(self._sl(c, X1), self._sl(c, X2), out, op=op, variance=v, lengthscales=ls, family=f,
-                                          diag_add=0.0, out=out)
-            else:                        # a sub-combination needs its own matrix once
-                tmp = self._build_node(c, X1, X2, None)
-                out.add_(tmp) if op == "add" else out.mul_(tmp)
-        return out
-
-    def _kd_node(self, node) -> float:
-        if isinstance(node, int):
-            return self.members[node][1]
-        vals = [self._kd_node(c) for c in node[1]]
-        return float(np.prod(vals)) if node[0] == "mul" else float(np.sum(vals))
-
-    def _dkd_node(self, node) -> dict:
-        if isinstance(node, int):
-            return {node: 1.0}
-        op, ch = node
-        out = {}
-        kds = [self._kd_node(c) for c in ch]
-        for ci, c in enumerate(ch):
-            fac = float(np.prod([k for j, k in enumerate(kds) if j != ci])) if op == "mul" else 1.0
-            for i, d in self._dkd_node(c).items():
-                out[i] = fac * d
-        return out
-
-    def _adjoint_node(self, node, A, Bm, Kbar, symmetric, acc):
-        if isinstance(node, int):
-            f, v, ls = self.members[node]
-            Ai = self._sl(node, A)
-            Bi = Ai if (symmetric and Bm is A) else self._sl(node, Bm)
-            dv, dl, Ab = stationary_kernel_adjoint(Ai, Bi, Kbar, symmetric=symmetric, variance=v, lengthscales=ls, family=f)
-            if np.ndim(ls) == 0 or np.size(ls) == 1:
-                dl = dl.sum().reshape(1)
-            acc[node] = (dv.reshape(1), dl, Ab)
-            return
-        op, ch = node
-        for c in ch:
-            Kb = Kbar
-            if op == "mul":          # d/dK_c = Kbar .* prod of the OTHER children's matrices
-                Kb = Kbar.clone()
-                for o in ch:
-                    if o is c:
-                        continue
-                    if isinstance(o, int):
-                        fo, vo, lo = self.members[o]
-                        ops.kernel_matrix_combine(self._sl(o, A), None if symmetric else self._sl(o, Bm), Kb, op="mul", variance=vo,
-                                                  lengthscales=lo, family=fo, out=Kb)
-                    else:
-                        Kb.mul_(self._build_node(o, A, None if symmetric else Bm, None))
-            self._adjoint_node(c, A, Bm, Kb, symmetric, acc)
-
     @property
     def n(self) -> int:
         return len(self.members)
@@ -318,34 +258,54 @@ class KernelSpec:
         return X.index_select(1, self._idx[key]).contiguous()
 
     def build(self, X1, X2, out=None, diag_add: float = 0.0):
-        if self.tree is not None:
-            out = self._build_node(self.tree, X1, X2, out)
-            if diag_add != 0.0 and X2 is None:
-                out.diagonal().add_(float(diag_add))
-            return out
-        last = self.n - 1
-        f, v, ls = self.members[0]
-        out = ops.kernel_matrix(self._sl(0, X1), self._sl(0, X2), variance=v, lengthscales=ls, family=f,
-                                diag_add=diag_add if last == 0 else 0.0, lower_only=False, out=out)
-        for i, (f, v, ls) in enumerate(self.members[1:], start=1):
-            ops.kernel_matrix_combine(self._sl(i, X1), self._sl(i, X2), out, op=self.op, variance=v, lengthscales=ls, family=f,
-                                      diag_add=diag_add if i == last else 0.0, out=out)
+        return self._build(self.tree, X1, X2, out, diag_add)
+
+    def _build(self, node, X1, X2, out, diag_add=0.0):
+        if isinstance(node, int):
+            f, v, ls = self.members[node]
+            return ops.kernel_matrix(self._sl(node, X1), self._sl(node, X2), variance=v, lengthscales=ls, family=f,
+                                     diag_add=diag_add, lower_only=False, out=out)
+        op, ch = node
+        if len(ch) == 1:
+            return self._build(ch[0], X1, X2, out, diag_add)
+        last = len(ch) - 1
+        out = self._build(ch[0], X1, X2, out)
+        for j, c in enumerate(ch[1:], start=1):
+            if isinstance(c, int):      # a stationary member folds in place (K recomputed in registers, no second matrix);
+                f, v, ls = self.members[c]   # diag_add rides in the LAST member's launch
+                ops.kernel_matrix_combine(self._sl(c, X1), self._sl(c, X2), out, op=op, variance=v, lengthscales=ls, family=f,
+                                          diag_add=diag_add if j == last else 0.0, out=out)
+            else:                        # a sub-combination needs its own matrix once
+                tmp = self._build(c, X1, X2, None)
+                out.add_(tmp) if op == "add" else out.mul_(tmp)
+        if diag_add != 0.0 and not isinstance(ch[last], int):
+            out.diagonal().add_(float(diag_add))
         return out
 
+    def _kd(self, node) -> float:
+        if isinstance(node, int):
+            return self.members[node][1]
+        vals = [self._kd(c) for c in node[1]]
+        return float(np.prod(vals)) if node[0] == "mul" else float(np.sum(vals))
+
     def kdiag(self) -> float:
-        if self.tree is not None:
-            return self._kd_node(self.tree)
-        vs = [v for _, v, _ in self.members]
-        return float(np.prod(vs)) if self.op == "mul" else float(np.sum(vs))
+        return self._kd(self.tree)
+
+    def _dkd(self, node) -> dict:
+        if isinstance(node, int):
+            return {node: 1.0}
+        op, ch = node
+        kd = self._kd(node)
+        out = {}
+        for c in ch:
+            fac = kd / self._kd(c) if op == "mul" else 1.0
+            for i, d in self._dkd(c).items():
+                out[i] = fac * d
+        return out
 
     def dkdiag(self):
-        if self.tree is not None:
-            d = self._dkd_node(self.tree)
-            return [d[i] for i in range(self.n)]
-        if self.op == "mul":
-            kd = self.kdiag()
-            return [kd / v for _, v, _ in self.members]
-        return [1.0] * self.n
+        d = self._dkd(self.tree)
+        return [d[i] for i in range(self.n)]
 
     def warm(self, device, D: int) -> "KernelSpec":
         """device copies of the members' lengthscales, made now (see `ls_device`)"""
@@ -354,51 +314,43 @@ class KernelSpec:
         return self
 
     def adjoint(self, A, Bm, Kbar, symmetric: bool):
-        dvs, dls, Abar = [], [], None
-        full = all(c is None for c in self.cols)
-        if self.tree is not None:
-            acc = {}
-            self._adjoint_node(self.tree, A, Bm, Kbar, symmetric, acc)
-            for i in range(self.n):
-                dv, dl, Ab = acc[i]
-                dvs.append(dv)
-                dls.append(dl)
-                if full:
-                    Abar = Ab if Abar is None else Abar + Ab
-                else:
-                    if Abar is None:
-                        Abar = torch.zeros_like(A)
-                    if self.cols[i] is None:
-                        Abar += Ab
-                    else:
-                        self._sl(i, A)    # (makes sure the index tensor of member i exists on this device)
-                        Abar.index_add_(1, self._idx[(i, str(A.device))], Ab)
-            return dvs, dls, Abar
-        for i, (f, v, ls) in enumerate(self.members):
-            Kb = Kbar
-            if self.op == "mul":
-                Kb = Kbar.clone()
-                for j, (fj, vj, lj) in enumerate(self.members):
-                    if j != i:
-                        ops.kernel_matrix_combine(self._sl(j, A), None if symmetric else self._sl(j, Bm), Kb, op="mul", variance=vj,
-                                                  lengthscales=lj, family=fj, out=Kb)
-            Ai = self._sl(i, A)
-            Bi = Ai if (symmetric and Bm is A) else self._sl(i, Bm)
-            dv, dl, Ab = stationary_kernel_adjoint(Ai, Bi, Kb, symmetric=symmetric, variance=v, lengthscales=ls, family=f)
-            if np.ndim(ls) == 0 or np.size(ls) == 1:
-                dl = dl.sum().reshape(1)
-            dvs.append(dv.reshape(1))
-            dls.append(dl)
-            if full:
-                Abar = Ab if Abar is None else Abar + Ab
+        """([d/dvariance_i [1]], [d/dlengthscales_i], A_bar [n1, D]) given Kbar, members in index order"""
+        acc = {"dv": [None] * self.n, "dl": [None] * self.n, "Abar": None}
+        self._adjoint(self.tree, A, Bm, Kbar, symmetric, acc)
+        return acc["dv"], acc["dl"], acc["Abar"]
+
+    def _adjoint(self, node, A, Bm, Kbar, symmetric, acc):
+        if isinstance(node, int):
+            f, v, ls = self.members[node]
+            Ai = self._sl(node, A)
+            Bi = Ai if (symmetric and Bm is A) else self._sl(node, Bm)
+            dv, dl, Ab = stationary_kernel_adjoint(Ai, Bi, Kbar, symmetric=symmetric, variance=v, lengthscales=ls, family=f)
+            acc["dl"][node], acc["dv"][node] = _ls_grad(dl, ls), dv.reshape(1)
+            if all(c is None for c in self.cols):
+                acc["Abar"] = Ab if acc["Abar"] is None else acc["Abar"] + Ab
             else:   # scatter the member's input gradient back into the columns it read
-                if Abar is None:
-                    Abar = torch.zeros_like(A)
-                if self.cols[i] is None:
-                    Abar += Ab
+                if acc["Abar"] is None:
+                    acc["Abar"] = torch.zeros_like(A)
+                if self.cols[node] is None:
+                    acc["Abar"] += Ab
                 else:
-                    Abar.index_add_(1, self._idx[(i, str(A.device))], Ab)
-        return dvs, dls, Abar
+                    acc["Abar"].index_add_(1, self._idx[(node, str(A.device))], Ab)
+            return
+        op, ch = node
+        for jc, c in enumerate(ch):
+            Kb = Kbar
+            if op == "mul":          # d/dK_c = Kbar .* prod of the OTHER children's matrices
+                Kb = Kbar.clone()
+                for jo, o in enumerate(ch):
+                    if jo == jc:
+                        continue
+                    if isinstance(o, int):
+                        fo, vo, lo = self.members[o]
+                        ops.kernel_matrix_combine(self._sl(o, A), None if symmetric else self._sl(o, Bm), Kb, op="mul", variance=vo,
+                                                  lengthscales=lo, family=fo, out=Kb)
+                    else:
+                        Kb.mul_(self._build(o, A, None if symmetric else Bm, None))
+            self._adjoint(c, A, Bm, Kb, symmetric, acc)
 
     def pack(self, dvs, dls):
         """gradient entries: one member -> ("variance" [1], "lengthscales" [D or 1]) as before; several -> "variance" [n] and
@@ -407,6 +359,207 @@ class KernelSpec:
             return dvs[0], dls[0]
         return torch.cat(dvs), list(dls)
 
+
+class _Seed:
+    """The seeds of the data term  scale * sum_bp var_exp(fmean_bp, fvar_bp):  r = dF/dfmean [B, P]  and  c = dF/dfvar  in the form
+    the likelihood gives it:
+      a scalar          Gaussian, one noise variance:  c = -scale / (2 s2)  for every (b, p);
+      a vector [B]      Gaussian, one noise variance per row (heteroskedastic, round 5): a row scaling of the factors the scalar
+                        multiplied (elementwise glue on [B, M] arrays);
+      a matrix [B, P]   a quadrature likelihood (Bernoulli, Poisson, StudentT; `lik_grads` = the kernel's dmu, dvar): the per-row form
+                        with W_p scaled by its own column, and sum_p c_bp where that form has P c_b.
+    The methods are the places where c enters the two SVGP passes; each issues the calls of the form it holds, so the passes read as
+    their derivation and the scalar path costs what it cost."""
+
+    def __init__(self, Yb, fmean, *, scale, mean_const, noise_variance=None, lik_grads=None):
+        self.B, self.P = fmean.shape
+        self.scale, self.nv = scale, noise_variance
+        self.Yb, self.fmean, self.mean_const = Yb, fmean, mean_const
+        if lik_grads is not None:
+            self.r = lik_grads[0].mul_(scale)                                           # dF/dfmean [B, P]
+            self.c = lik_grads[1].mul_(scale)                                           # dF/dfvar  [B, P]
+        elif torch.is_tensor(noise_variance) and noise_variance.dim() >= 1:
+            self.nv = nv = noise_variance.reshape(-1)
+            self.c = (-0.5 * scale) / nv                                                # dF/dfvar per row [B]
+            self.r = (scale / nv)[:, None] * (Yb - fmean - mean_const)                  # dF/dfmean [B, P]
+        else:
+            self.c = -0.5 * scale / noise_variance                                      # dF/dfvar (every b, p)
+            self.r = torch.sub(Yb, fmean)                                               # dF/dfmean [B, P] = (scale / s2) (y - f - m)
+            if mean_const != 0.0:
+                self.r.sub_(mean_const)
+            self.r.mul_(scale / noise_variance)
+        self.dim = self.c.dim() if torch.is_tensor(self.c) else 0
+
+    @property
+    def scalar(self) -> bool:
+        return self.dim == 0
+
+    def add_W_LqT(self, Atb, W, Lq):
+        """Atb += 2 sum_p c W_p Lq_p^T  (Lq_p lower: b_tri 2).  Returns (Wg, ag): the (row-scaled) W and the factor with which the
+        q_sqrt products  ag tril(At^T Wg_p)  carry the same c."""
+        if self.dim == 0:
+            Wg, ag = W, 2.0 * self.c
+        else:                                                                           # rows of W_p scaled by c_b / c_bp
+            Wg, ag = W * (self.c[None, :, None] if self.dim == 1 else self.c.t()[:, :, None]), 2.0
+        for p in range(self.P):
+            ops.gemm_nt(Wg[p], Lq[p], alpha=ag, beta=1.0, C=Atb, b_tri=2)
+        return Wg, ag
+
+    def add_At(self, Atb, At):
+        """Atb += -2 (sum_p c) At"""
+        if self.dim == 0:
+            Atb.add_(At, alpha=-2.0 * self.c * self.P)
+        elif self.dim == 1:
+            Atb.addcmul_(At, self.c[:, None], value=-2.0 * self.P)
+        else:
+            Atb.addcmul_(At, self.c.sum(1)[:, None], value=-2.0)
+
+    def add_qdiag_term(self, Atb, At, q_sqrt, s=None):
+        """q_diag, per column m:  Atb += 2 At .* (c (q^2 - 1)^T) = 2c At (sum_p q_mp^2 - P)  -- the W and the At term of the full form
+        in one; with s = sum_p q_mp^2 given (the un-whitened pass, whose At term is separate) the weight is s itself."""
+        if self.dim == 2:
+            Atb.addcmul_(At, ops.gemm_nt(self.c, q_sqrt * q_sqrt - 1.0), value=2.0)
+            return
+        w = lambda: (((q_sqrt * q_sqrt).sum(1) - self.P) if s is None else s)[None, :]  # noqa: E731
+        if self.dim == 1:
+            Atb.addcmul_(At * (2.0 * self.c)[:, None], w())
+        else:
+            Atb.addcmul_(At, (2.0 * self.c) * w())
+
+    def weighted_colsq(self, A, At):
+        """q_diag:  2 sum_b c At[b, m]^2  as [M, 1] or, per latent, [M, P]  (A = At^T)"""
+        if self.dim == 2:
+            return ops.gemm_nt(A * A, self.c.t().contiguous(), alpha=2.0)
+        if self.dim == 1:
+            return (2.0 * ((At * At) * self.c[:, None]).sum(0))[:, None]
+        return (2.0 * self.c) * ops.row_stats(A)[0][:, None]
+
+    def csum(self):
+        """sum_bp c: what every fvar's Knn = kdiag collects"""
+        return self.c.sum() if self.dim == 2 else self.c.sum() * self.P if self.dim == 1 else self.c * self.B * self.P
+
+    def noise_grad(self, ve, s0, ssq, kdiag):
+        """dF/d sigma^2 of the Gaussian likelihood: [1], or one entry per row (likelihood parameters are then reached through
+        Gaussian.noise_param_grads)"""
+        B, P, scale, nv = self.B, self.P, self.scale, self.nv
+        if self.dim == 1:
+            # dF/d sigma_n^2 = scale sum_p (-1 / (2 s2_n) + ((y - f)^2 + fvar) / (2 s2_n^2))
+            fvar = (kdiag - s0)[:, None] + ssq.t()
+            resid = self.Yb - self.fmean - self.mean_const
+            return scale * (-0.5 * P / nv + 0.5 * (resid * resid + fvar).sum(1) / (nv * nv))
+        # sum_bp ((y - f)^2 + fvar) recovered from the forward value:  ve = B P k0 - Q / (2 s2)
+        #   d/ds2 = scale (-B P / (2 s2) + Q / (2 s2^2)) = (scale / s2) (B P (k0 - 1/2) - ve)          (two launches)
+        k0 = -0.5 * LOG2PI - 0.5 * float(np.log(nv))
+        return torch.mul(ve, -scale / nv).add_(scale / nv * B * P * (k0 - 0.5)).reshape(1)
+
+
+def _factorise(spec: KernelSpec, Z, X, jitter):
+    """trapezoid = [Kuu + jitter I ; Kfu ; I]: the factorisation returns Lm, At = Kfu Lm^-T and, from the identity rows, Lm^-T
+    itself -- the explicit inverse that turns every triangular solve of the backward into one GEMM.  Returns (Lm, At, Lm^-T, info)."""
+    M, n = Z.shape[0], X.shape[0]
+    T = torch.empty((M + n + M, M), dtype=torch.float64, device=Z.device)
+    spec.build(Z, None, T[:M], diag_add=jitter)                                         # Kuu + jitter I
+    if n:
+        spec.build(X, Z, T[M:M + n])                                                    # Kfu
+    _, info = ops.potrf_(T, M, zero_upper=True, identity_rows=True)                     # (the last M rows: I -> Lm^-T)
+    return T[:M], T[M:M + n], T[M + n:], info
+
+
+def _project(At, q_mu, q_sqrt, **fmean_stats):
+    """The rows' statistics under q(u):  s0 = rowsum(At^2), fmean = At q_mu, ssq = rowsum(W_p^2) with W_p = At Lq_p  [P, B, M].
+    Returns (s0, fmean, ssq, Lq, LqT, W); q_diag (q_sqrt [M, P] of standard deviations: svgp.py:90-148, conditionals/util.py:149,
+    164) never forms W -- one pass with weights, Lq = LqT = W = None.  `fmean_stats` goes to the fmean pass of the full form."""
+    if q_sqrt.dim() == 2:
+        return (*ops.row_stats(At, V=q_mu, W=q_sqrt.contiguous()), None, None, None)    # rowsum(At^2), At q_mu, sum_k At^2 q^2
+    P = q_sqrt.shape[0]
+    Lq = _tril(q_sqrt)                                                                  # band_part(q_sqrt, -1, 0)
+    LqT = ops.transpose(q_sqrt, mode=1)                                                 # [P, M, M] = tril(q_sqrt)^T
+    s0, fmean, _ = ops.row_stats(At, V=q_mu, **fmean_stats)                             # rowsum(At^2), At q_mu
+    W = ops.gemm_nt(At, LqT, b_tri=1)                                                   # [P, B, M]: W_p = At Lq_p
+    ssq = torch.stack([ops.row_stats(W[p])[0] for p in range(P)])                       # [P, B]
+    return s0, fmean, ssq, Lq, LqT, W
+
+
+def _covariance_tail(spec: KernelSpec, Z, Xb, Kuf_bar, LT, LinvT, Lbar, knn_bar, *, first=None, packed=False, before_products=None):
+    """From Kuf_bar [M, B] and Lm_bar to (d/dvariance, d/dlengthscales, Z_bar):  Kuu_bar by the Cholesky adjoint (LT = Lm^T), the
+    kernel adjoints of Kuf and of Kuu, and  knn_bar * d kdiag / d variance_i  for the Knn = kdiag in every fvar.
+    first: the Kuf adjoint where the caller already has it (SGPR sums it over the shards); before_products: see cholesky_adjoint."""
+    Kuu_bar = cholesky_adjoint(LT, LinvT, Lbar, before_products=before_products)
+    dkd = spec.dkdiag()
+    if packed:
+        # one stationary kernel over all input columns: the second adjoint ADDS its variance / lengthscale / Z gradients to the
+        # first one's in its own tail launch, and the Knn term of d/dvariance rides along (no elementwise launches at all)
+        fam1, var1, ls1 = spec.members[0]
+        into = stationary_kernel_adjoint(Z, Xb, Kuf_bar, variance=var1, lengthscales=ls1, symmetric=False, family=fam1,
+                                         dvar_add=knn_bar * dkd[0], return_packed=True)
+        small_g, Zbar = stationary_kernel_adjoint(Z, Z, Kuu_bar, variance=var1, lengthscales=ls1, symmetric=True, family=fam1,
+                                                  packed_into=into, return_packed=True)
+        return small_g[0:1], _ls_grad(small_g[1:], ls1), Zbar
+    dv1, dl1, Zb1 = first if first is not None else spec.adjoint(Z, Xb, Kuf_bar, symmetric=False)
+    dv2, dl2, Zb2 = spec.adjoint(Z, Z, Kuu_bar, symmetric=True)
+    g_var, g_ls = spec.pack([a + b + knn_bar * dk for a, b, dk in zip(dv1, dv2, dkd)], [a + b for a, b in zip(dl1, dl2)])
+    return g_var, g_ls, Zb1 + Zb2
+
+
+class _SideBranch:
+    """The {q_mu_bar, Lq_bar} branch of the whitened reverse pass, beside the main one ({Lm_bar -> Cholesky adjoint -> kernel adjoints})
+    that is enqueued inside the `with`: `prep()` -> (first result, *arguments of products), `products(*arguments)` -> second result;
+    `results` = (first, second) once the block has ended.
+
+    On a device (and OVERLAP_BRANCHES) the branch runs on the side stream: prep at the fork, products when the main branch calls
+    `release` (cholesky_adjoint's before_products).  Without one, both run inline after the main branch."""
+
+    def __init__(self, like: torch.Tensor, prep, products):
+        self.prep, self.products = prep, products
+        self.dev = like.device
+        self.side = _side_stream(self.dev) if (OVERLAP_BRANCHES and like.is_cuda) else None
+        self.pending = False
+        self.results = None
+
+    def __enter__(self):
+        if self.side is not None:
+            # The side branch reads A, W, r, Lq, q_mu (allocated on the main stream) and allocates its split-K partials from
+            # the side stream's pool (~270 MB per latent at M = 2048).  The join sits in __exit__: if anything on the
+            # main branch raises, the caller still waits for the side stream before its locals go back to the allocator.
+            self.main = torch.cuda.current_stream(self.dev)
+            self.side.wait_stream(self.main)
+            with torch.cuda.stream(self.side):
+                self.first, *self.args = self.prep()
+            self.pending = True
+            if not GATE_SIDE_BRANCH:
+                self.release()
+        return self
+
+    # The main branch is the LONGER one (Lm_bar, three dependent M^3 products, two kernel adjoints: ~2.5 ms against ~1.6) and
+    # its short HBM-bound kernels starve while a chip-filling GEMM of the other stream has workgroups waiting for a slot: the
+    # combine / transpose pair behind the Lm_bar product took 298 + 239 us beside the side branch's GEMM, 41 + 11 us alone
+    # (profiles/r06_train_timeline_before.txt).  So the side branch's GEMMs wait until that preparation is enqueued; from
+    # there on the main branch only runs under-filled products that are bound by their longest tile, not by the CUs they get.
+    def release(self):
+        if not self.pending:
+            return
+        self.pending = False
+        with torch.cuda.stream(self.side):
+            if GATE_SIDE_BRANCH:
+                ev = torch.cuda.Event()
+                ev.record(self.main)
+                self.side.wait_event(ev)
+            self.second = self.products(*self.args)
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.side is not None:
+            if exc_type is None:
+                self.release()
+            self.main.wait_stream(self.side)
+        if exc_type is None:
+            if self.side is not None:
+                self.first.record_stream(self.main)
+                self.second.record_stream(self.main)
+            else:
+                self.first, *args = self.prep()
+                self.second = self.products(*args)
+            self.results = (self.first, self.second)
+        return False
 
 
 def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor,
@@ -426,7 +579,6 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     expectations and the seeds r = dF/dfmean, c = dF/dfvar -- now one value per (row, latent) -- come from the quadrature kernel;
     `noise_variance` is ignored, grads has no "noise_variance" and, for "student_t", a "likelihood_scale"."""
     M, D = Z.shape
-    B = Xb.shape[0]
     P = q_mu.shape[1]
     q_diag = q_sqrt.dim() == 2
     if tuple(q_sqrt.shape) not in ((P, M, M), (M, P)):
@@ -436,22 +588,8 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
 
     # ---------------------------------------------------------------- forward (intermediates kept)
-    # trapezoid = [Kuu + jitter I ; Kfu ; I]: the factorisation returns Lm, At = Kfu Lm^-T and, from the identity
-    # rows, Lm^-T itself -- the explicit inverse that turns every triangular solve of the backward into one GEMM
-    T = torch.empty((M + B + M, M), dtype=torch.float64, device=dev)
-    spec.build(Z, None, T[:M], diag_add=jitter)                                         # Kuu + jitter I
-    spec.build(Xb, Z, T[M:M + B])                                                       # Kfu
-    invd, info = ops.potrf_(T, M, zero_upper=True, identity_rows=True)                  # (the last M rows: I -> Lm^-T)
-    L, At, LinvT = T[:M], T[M:M + B], T[M + B:]
-    if q_diag:   # q_sqrt [M, P] holds standard deviations (svgp.py:90-148, conditionals/util.py:149,164)
-        s0, fmean, ssq = ops.row_stats(At, V=q_mu, W=q_sqrt.contiguous())                # rowsum(At^2), At q_mu, sum_k At^2 q^2
-        Lq = LqT = W = None
-    else:
-        Lq = _tril(q_sqrt)                                                                 # band_part(q_sqrt, -1, 0)
-        LqT = ops.transpose(q_sqrt, mode=1)                                             # [P, M, M] = tril(q_sqrt)^T
-        s0, fmean, _ = ops.row_stats(At, V=q_mu)                                        # rowsum(At^2), At q_mu
-        W = ops.gemm_nt(At, LqT, b_tri=1)                                               # [P, B, M]: W_p = At Lq_p
-        ssq = torch.stack([ops.row_stats(W[p])[0] for p in range(P)])                   # [P, B]
+    L, At, LinvT, info = _factorise(spec, Z, Xb, jitter)
+    s0, fmean, ssq, Lq, LqT, W = _project(At, q_mu, q_sqrt)
     if likelihood is not None:
         lik_out, _, dmu, dvar, _ = ops.likelihood_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], lik=likelihood[0],
                                                              params=likelihood[1], mean_const=mean_const, want_grads=True)
@@ -463,52 +601,18 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     F = torch.mul(ve, scale).sub_(kl, alpha=kl_weight)
 
     # ---------------------------------------------------------------- backward
-    # het: one noise variance per row (a heteroskedastic Gaussian likelihood, round 5): dF/dfvar is a per-row vector, applied as a
-    # row scaling of the factors it multiplied as a scalar (elementwise glue on [B, M] arrays); the scalar path is unchanged
-    # cmat: dF/dfvar per (row, latent) [B, P] from the quadrature kernel (a non-Gaussian likelihood): the heteroskedastic branch with
-    # W_p scaled by its own column and sum_p c_bp where that branch has P c_b
-    het = likelihood is None and torch.is_tensor(noise_variance) and noise_variance.dim() >= 1
-    cmat = None
-    if likelihood is not None:
-        c = None
-        r = dmu.mul_(scale)                                                             # dF/dfmean [B, P]
-        cmat = dvar.mul_(scale)                                                         # dF/dfvar  [B, P]
-    elif het:
-        nv = noise_variance.reshape(-1)
-        cvec = (-0.5 * scale) / nv                                                      # dF/dfvar per row [B]
-        c = None
-        r = (scale / nv)[:, None] * (Yb - fmean - mean_const)                           # dF/dfmean [B, P]
-    else:
-        c = -0.5 * scale / noise_variance                                               # dF/dfvar (every b, p)
-        r = torch.sub(Yb, fmean)                                                        # dF/dfmean [B, P] = (scale / s2) (y - f - m)
-        if mean_const != 0.0:
-            r.sub_(mean_const)
-        r.mul_(scale / noise_variance)
-    plain = not q_diag and not het and cmat is None and P <= 16
+    seed = _Seed(Yb, fmean, scale=scale, mean_const=mean_const, noise_variance=noise_variance,
+                 lik_grads=(dmu, dvar) if likelihood is not None else None)
+    r = seed.r
+    plain = not q_diag and seed.scalar and P <= 16
     # (plain: r q_mu^T - 2 c P At in ONE pass over At; it was a K = P GEMM, then an axpy pass behind the products below)
-    Atb = ops.lowrank_axpy(-2.0 * c * P, At, r, q_mu) if plain else ops.gemm_nt(r, q_mu)  # r q_mu^T  [B, M]
-    if q_diag:                                                                          # + 2c At (sum_p q_p^2 - P) per column
-        if cmat is not None:                                                            # + 2 At .* (c (q^2 - 1)^T)
-            Atb.addcmul_(At, ops.gemm_nt(cmat, q_sqrt * q_sqrt - 1.0), value=2.0)
-        elif het:
-            Atb.addcmul_(At * (2.0 * cvec)[:, None], ((q_sqrt * q_sqrt).sum(1) - P)[None, :])
-        else:
-            Atb.addcmul_(At, (2.0 * c) * ((q_sqrt * q_sqrt).sum(1) - P)[None, :])
-    elif cmat is not None:
-        Wc = W * cmat.t()[:, :, None]                                                   # rows of W_p scaled by c_bp
-        for p in range(P):
-            ops.gemm_nt(Wc[p], Lq[p], alpha=2.0, beta=1.0, C=Atb, b_tri=2)
-        Atb.addcmul_(At, cmat.sum(1)[:, None], value=-2.0)                              # - 2 (sum_p c_bp) At
-    elif het:
-        Wc = W * cvec[None, :, None]                                                    # rows of W_p scaled by c_b
-        for p in range(P):
-            ops.gemm_nt(Wc[p], Lq[p], alpha=2.0, beta=1.0, C=Atb, b_tri=2)
-        Atb.addcmul_(At, cvec[:, None], value=-2.0 * P)
+    Atb = ops.lowrank_axpy(-2.0 * seed.c * P, At, r, q_mu) if plain else ops.gemm_nt(r, q_mu)  # r q_mu^T  [B, M]
+    if q_diag:
+        seed.add_qdiag_term(Atb, At, q_sqrt)                                            # + 2c At (sum_p q_p^2 - P) per column
     else:
-        for p in range(P):                                                              # + 2c W_p Lq_p^T (Lq_p lower: b_tri 2)
-            ops.gemm_nt(W[p], Lq[p], alpha=2.0 * c, beta=1.0, C=Atb, b_tri=2)
+        Wg, ag = seed.add_W_LqT(Atb, W, Lq)                                             # + 2c sum_p W_p Lq_p^T
         if not plain:
-            Atb.add_(At, alpha=-2.0 * c * P)                                            # - 2 c P At
+            seed.add_At(Atb, At)                                                        # - 2 c P At
     A = ops.transpose(At)                                                               # [M, B]
     Kfu_bar = ops.gemm_nt(Atb, LinvT, b_tri=1)                                          # At_bar Lm^-1  [B, M]
     Kuf_bar = ops.transpose(Kfu_bar)                                                    # [M, B]
@@ -518,106 +622,30 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
         # At^T r - q_mu: a thin product -- ONE pass over A (gpk_row_stats' At V form), not a GEMM with a 64-column tile for P columns
         # (that launch took 67 us alone and 523 us beside the main branch's product, profiles/r06_train_timeline_fused_glue.txt)
         g_mu = ops.row_stats(A, V=r, want_sumsq=False)[1].sub_(q_mu, alpha=kl_weight)
-        if q_diag:
-            return g_mu, None, None
-        Wg, ag = (Wc, 2.0) if (het or cmat is not None) else (W, 2.0 * c)
-        return g_mu, [ops.transpose(Wg[p]) for p in range(P)], ag
+        return g_mu, (None if q_diag else [ops.transpose(Wg[p]) for p in range(P)])
 
-    def branch_q_products(WgT, ag):
+    def branch_q_products(WgT):
         if q_diag:   # d/dq = 2c colsum(At^2) q - (q - 1/q)   (KL of a diagonal q: kullback_leiblers.py:131-133,146-148)
-            if cmat is not None:   # 2 sum_b c_bp At[b, m]^2 as [M, P]
-                return ops.gemm_nt(A * A, cmat.t().contiguous(), alpha=2.0) * q_sqrt - kl_weight * (q_sqrt - 1.0 / q_sqrt)
-            if het:
-                colsq2c = 2.0 * ((At * At) * cvec[:, None]).sum(0)                      # 2 sum_b c_b At[b, m]^2
-                return colsq2c[:, None] * q_sqrt - kl_weight * (q_sqrt - 1.0 / q_sqrt)
-            colsq = ops.row_stats(A)[0]
-            return (2.0 * c) * colsq[:, None] * q_sqrt - kl_weight * (q_sqrt - 1.0 / q_sqrt)
+            return seed.weighted_colsq(A, At) * q_sqrt - kl_weight * (q_sqrt - 1.0 / q_sqrt)
         g = torch.stack([splitk_gemm_nt(A, WgT[p], c_lower=True, alpha=ag) for p in range(P)]) if P > 1 else \
             splitk_gemm_nt(A, WgT[0], c_lower=True, alpha=ag).unsqueeze(0)
         g.sub_(Lq, alpha=kl_weight)                                                     # 2c tril(At^T W_p) - Lq_p
         g.diagonal(dim1=1, dim2=2).add_(kl_weight / Lq.diagonal(dim1=1, dim2=2))
         return g
 
-    side = _side_stream(dev) if (OVERLAP_BRANCHES and Z.is_cuda) else None
+    one_kernel = spec.n == 1 and spec.cols[0] is None and seed.scalar                   # (the packed tail of _covariance_tail)
     LT = ops.transpose(L, mode=1)
-    if side is not None:
-        # The side branch reads A, W, r, Lq, q_mu (allocated on the main stream) and allocates its split-K partials from
-        # the side stream's pool (~270 MB per latent at M = 2048).  The join below sits in a `finally`: if anything on the
-        # main branch raises, the function still waits for the side stream before its locals go back to the allocator.
-        main = torch.cuda.current_stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            g_qmu, WgT, ag = branch_q_prep()
-        g_qs_box = []
-
-        # The main branch is the LONGER one (Lm_bar, three dependent M^3 products, two kernel adjoints: ~2.5 ms against ~1.6) and
-        # its short HBM-bound kernels starve while a chip-filling GEMM of the other stream has workgroups waiting for a slot: the
-        # combine / transpose pair behind the Lm_bar product took 298 + 239 us beside the side branch's GEMM, 41 + 11 us alone
-        # (profiles/r06_train_timeline_before.txt).  So the side branch's GEMMs wait until that preparation is enqueued; from
-        # there on the main branch only runs under-filled products that are bound by their longest tile, not by the CUs they get.
-        def release_side():
-            with torch.cuda.stream(side):
-                if GATE_SIDE_BRANCH:
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                    side.wait_event(ev)
-                g_qs_box.append(branch_q_products(WgT, ag))
-        if not GATE_SIDE_BRANCH:
-            release_side()
-            release_side = None
-    else:
-        release_side = None
-    try:
-        Lbar = splitk_gemm_nt(Kuf_bar, A, c_lower=True, alpha=-1.0)            # -tril(Kfu_bar^T At)
-        Kuu_bar = cholesky_adjoint(LT, LinvT, Lbar, before_products=release_side)
-        dkd = spec.dkdiag()                                                             # Knn = kdiag in every fvar
-        csum = cmat.sum() if cmat is not None else cvec.sum() * P if het else c * B * P
-        one_kernel = spec.n == 1 and spec.tree is None and spec.cols[0] is None and not het and cmat is None
-        if one_kernel:
-            # one stationary kernel over all input columns: the second adjoint ADDS its variance / lengthscale / Z gradients to the
-            # first one's in its own tail launch, and the Knn term of d/dvariance rides along (no elementwise launches at all)
-            fam1, var1, ls1 = spec.members[0]
-            packed = stationary_kernel_adjoint(Z, Xb, Kuf_bar, variance=var1, lengthscales=ls1, symmetric=False, family=fam1,
-                                               dvar_add=csum * dkd[0], return_packed=True)
-            small_g, Zbar = stationary_kernel_adjoint(Z, Z, Kuu_bar, variance=var1, lengthscales=ls1, symmetric=True, family=fam1,
-                                                      packed_into=packed, return_packed=True)
-        else:
-            dv1, dl1, Zb1 = spec.adjoint(Z, Xb, Kuf_bar, symmetric=False)
-            dv2, dl2, Zb2 = spec.adjoint(Z, Z, Kuu_bar, symmetric=True)
-    finally:
-        if side is not None:
-            main.wait_stream(side)
-    if side is not None:
-        g_qs = g_qs_box[0]
-        g_qmu.record_stream(main)
-        g_qs.record_stream(main)
-    else:
-        g_qmu, WgT, ag = branch_q_prep()
-        g_qs = branch_q_products(WgT, ag)
-    if one_kernel:
-        g_var = small_g[0:1]
-        g_ls = small_g[1:] if not (np.ndim(ls1) == 0 or np.size(ls1) == 1) else small_g[1:].sum().reshape(1)
-    else:
-        g_var, g_ls = spec.pack([a + b + csum * dk for a, b, dk in zip(dv1, dv2, dkd)], [a + b for a, b in zip(dl1, dl2)])
-        Zbar = Zb1 + Zb2
-    if likelihood is not None:
-        grads = {"variance": g_var, "lengthscales": g_ls, "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)}
-        if likelihood[0] == "student_t":
-            grads["likelihood_scale"] = lik_out[1:2] * scale
-        return F, grads, info
-    if het:
-        # dF/d sigma_n^2 = scale sum_p (-1 / (2 s2_n) + ((y - f)^2 + fvar) / (2 s2_n^2)): one entry per row (likelihood parameters
-        # are reached through Gaussian.noise_param_grads)
-        fvar = (spec.kdiag() - s0)[:, None] + ssq.t()
-        resid = Yb - fmean - mean_const
-        g_noise = scale * (-0.5 * P / nv + 0.5 * (resid * resid + fvar).sum(1) / (nv * nv))
-    else:
-        # sum_bp ((y - f)^2 + fvar) recovered from the forward value:  ve = B P k0 - Q / (2 s2)
-        #   d/ds2 = scale (-B P / (2 s2) + Q / (2 s2^2)) = (scale / s2) (B P (k0 - 1/2) - ve)          (two launches)
-        k0 = -0.5 * LOG2PI - 0.5 * float(np.log(noise_variance))
-        g_noise = torch.mul(ve, -scale / noise_variance).add_(scale / noise_variance * B * P * (k0 - 0.5)).reshape(1)
-    grads = {"variance": g_var, "lengthscales": g_ls, "noise_variance": g_noise,
-             "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)}
+    with _SideBranch(Z, branch_q_prep, branch_q_products) as branch:
+        Lbar = splitk_gemm_nt(Kuf_bar, A, c_lower=True, alpha=-1.0)                     # -tril(Kfu_bar^T At)
+        g_var, g_ls, Zbar = _covariance_tail(spec, Z, Xb, Kuf_bar, LT, LinvT, Lbar, seed.csum(), packed=one_kernel,
+                                             before_products=branch.release)
+    g_qmu, g_qs = branch.results
+    grads = {"variance": g_var, "lengthscales": g_ls}
+    if likelihood is None:
+        grads["noise_variance"] = seed.noise_grad(ve, s0, ssq, spec.kdiag())
+    grads.update({"Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)})
+    if likelihood is not None and likelihood[0] == "student_t":
+        grads["likelihood_scale"] = lik_out[1:2] * scale
     return F, grads, info
 
 
@@ -715,12 +743,7 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
         return t
 
     eye = torch.eye(M, dtype=torch.float64, device=dev)
-    T = torch.empty((M + n + M, M), dtype=torch.float64, device=dev)
-    spec.build(Z, None, T[:M], diag_add=jitter)
-    if n:
-        spec.build(X, Z, T[M:M + n])
-    _, info = ops.potrf_(T, M, zero_upper=True, identity_rows=True)
-    L, At, LinvT = T[:M], T[M:M + n], T[M + n:]
+    L, At, LinvT, info = _factorise(spec, Z, X, jitter)
     err = (Y - mean_const).contiguous()
     stats = torch.zeros(M * M + M * P + 4, dtype=torch.float64, device=dev)
     if n:
@@ -786,10 +809,8 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
     offs = np.concatenate([[0], np.cumsum(nlsm)])
     dl1 = [part[o + nmem + offs[i]:o + nmem + offs[i + 1]] for i in range(nmem)]
     Zb1, g_mean = part[o + nmem + nl_tot:o + nmem + nl_tot + M * D].reshape(M, D), part[-1]
-    Kuu_bar = cholesky_adjoint(ops.transpose(L, mode=1), LinvT, Lbar)
-    dv2, dl2, Zb2 = spec.adjoint(Z, Z, Kuu_bar, symmetric=True)
-    g_var, g_ls = spec.pack([a + b - 0.5 * P * sum_w * dk for a, b, dk in zip(dv1, dv2, spec.dkdiag())],
-                            [a + b for a, b in zip(dl1, dl2)])
+    g_var, g_ls, Zbar = _covariance_tail(spec, Z, None, None, ops.transpose(L, mode=1), LinvT, Lbar, -0.5 * P * sum_w,
+                                         first=(dv1, dl1, Zb1))             # (Knn = kdiag in the trace term: -P var sum_w / 2)
     if het:
         g_noise = g_noise_rows if g_noise_rows is not None else torch.zeros(0, dtype=torch.float64, device=dev)
     else:
@@ -797,7 +818,7 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
         g_noise = (-P * (-0.5 * (M - torch.diagonal(Binv).sum()) / s2 + 0.5 * N / s2 - 0.5 * (N * kdiag - q) / s2 ** 2)
                    + 0.5 * e2 / s2 ** 2 - 0.5 * wa / s2 ** 2 - 0.5 * ww / s2).reshape(1)
     status = torch.maximum(info, info2)
-    grads = {"variance": g_var, "lengthscales": g_ls, "noise_variance": g_noise, "Z": Zb1 + Zb2,
+    grads = {"variance": g_var, "lengthscales": g_ls, "noise_variance": g_noise, "Z": Zbar,
              "mean_const": g_mean.reshape(1)}
     return F.reshape(1), grads, status
 
@@ -822,7 +843,6 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
     `SVGPTrainer` when `whiten=False`; parity vs the autograd oracle on the emulated primitives
     (tests/test_gradients_cpu.py) and on the GPU (tests/test_gpu_gradients.py)."""
     M, D = Z.shape
-    B = Xb.shape[0]
     P = q_mu.shape[1]
     q_diag = q_sqrt.dim() == 2
     if tuple(q_sqrt.shape) not in ((P, M, M), (M, P)):
@@ -832,11 +852,7 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
     spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family)
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
     k = float(kl_weight)
-    T = torch.empty((M + B + M, M), dtype=torch.float64, device=dev)
-    spec.build(Z, None, T[:M], diag_add=jitter)
-    spec.build(Xb, Z, T[M:M + B])
-    _, info = ops.potrf_(T, M, zero_upper=True, identity_rows=True)
-    L, At, LinvT = T[:M], T[M:M + B], T[M + B:]
+    L, At, LinvT, info = _factorise(spec, Z, Xb, jitter)
     Linv = ops.transpose(LinvT)                                                         # lower
     A2t = ops.gemm_nt(At, LinvT, b_tri=1)                                               # At Linv   (util.py:139)
     s0 = ops.row_stats(At)[0]
@@ -844,16 +860,12 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
     if q_diag:
         qd = q_sqrt.contiguous()
         s = (qd * qd).sum(1)                                                            # sum_p q_mp^2  [M]
-        _, fmean, ssq = ops.row_stats(A2t, V=q_mu, W=qd)                                # A2t q_mu, sum_m A2t^2 q_mp^2
+        _, fmean, ssq = _project(A2t, q_mu, qd)[:3]                                     # A2t q_mu, sum_m A2t^2 q_mp^2
         kinv_diag = ops.row_stats(LinvT)[0]                                             # diag(Kuu^-1) = rowsum((Lm^-T)^2)
         kl = 0.5 * (ops.sumsq(alphat)[0] - M * P - torch.log(qd * qd).sum() + (kinv_diag * s).sum()) \
             + P * ops.sum_log_diag(L)[0]
     else:
-        Lq = _tril(q_sqrt)
-        LqT = ops.transpose(q_sqrt, mode=1)
-        _, fmean, _ = ops.row_stats(A2t, V=q_mu, want_sumsq=False)
-        W = ops.gemm_nt(A2t, LqT, b_tri=1)                                              # [P, B, M]
-        ssq = torch.stack([ops.row_stats(W[p])[0] for p in range(P)])
+        _, fmean, ssq, Lq, LqT, W = _project(A2t, q_mu, q_sqrt, want_sumsq=False)       # W_p = A2t Lq_p  [P, B, M]
         V = ops.gemm_nt(Linv, LqT, b_tri=1, a_tri=2)                                    # [P, M, M]: V_p = Linv Lq_p
         if V.dim() == 2:
             V = V.unsqueeze(0)
@@ -863,36 +875,15 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
                                     mean_const=mean_const)
     F = scale * ve - k * kl
     # ---- backward
-    # het: one noise variance per row (a heteroskedastic Gaussian likelihood): dF/dfvar is a per-row vector c_b, applied as a row
-    # scaling of the factors the scalar multiplied (same treatment as the whitened pass); the scalar path is unchanged
-    het = torch.is_tensor(noise_variance) and noise_variance.dim() >= 1
-    if het:
-        nv = noise_variance.reshape(-1)
-        cvec = (-0.5 * scale) / nv
-        c = None
-        r = (scale / nv)[:, None] * (Yb - fmean - mean_const)
-    else:
-        c = -0.5 * scale / noise_variance
-        r = (scale / noise_variance) * (Yb - fmean - mean_const)
-    A2tb = ops.gemm_nt(r, q_mu)
-    Wc = None
+    seed = _Seed(Yb, fmean, scale=scale, mean_const=mean_const, noise_variance=noise_variance)
+    r = seed.r
+    A2tb = ops.gemm_nt(r, q_mu)                                                         # r q_mu^T
     if q_diag:
-        if het:
-            A2tb.addcmul_(A2t * (2.0 * cvec)[:, None], s[None, :])
-        else:
-            A2tb.addcmul_(A2t, (2.0 * c) * s[None, :])
-    elif het:
-        Wc = W * cvec[None, :, None]                                                    # rows of W_p scaled by c_b
-        for p in range(P):
-            ops.gemm_nt(Wc[p], Lq[p], alpha=2.0, beta=1.0, C=A2tb, b_tri=2)
+        seed.add_qdiag_term(A2tb, A2t, qd, s)                                           # + 2c A2t diag(sum_p q_p^2)
     else:
-        for p in range(P):
-            ops.gemm_nt(W[p], Lq[p], alpha=2.0 * c, beta=1.0, C=A2tb, b_tri=2)
+        Wg, ag = seed.add_W_LqT(A2tb, W, Lq)                                            # + 2c sum_p W_p Lq_p^T
     Atb = ops.gemm_nt(A2tb, Linv, b_tri=2)                                              # A2t_bar Linv^T
-    if het:
-        Atb.addcmul_(At, cvec[:, None], value=-2.0 * P)
-    else:
-        Atb.add_(At, alpha=-2.0 * c * P)
+    seed.add_At(Atb, At)                                                                # - 2 c P At
     A = ops.transpose(At)
     A2 = ops.transpose(A2t)
     Kfu_bar = ops.gemm_nt(Atb, LinvT, b_tri=1)
@@ -901,10 +892,8 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
     Kinv_qmu_t = ops.gemm_nt(alphat, LinvT, b_tri=1)                                    # (Linv^T alpha)^T  [P, M]
     g_qmu = ops.row_stats(A2, V=r, want_sumsq=False)[1] - k * Kinv_qmu_t.t()
     if q_diag:   # d/dq_mp = 2c colsum(A2t^2)_m q_mp - k ((Kuu^-1)_mm q_mp - 1 / q_mp)
-        colsq2c = 2.0 * ((A2t * A2t) * cvec[:, None]).sum(0) if het else (2.0 * c) * ops.row_stats(A2)[0]
-        g_qs = colsq2c[:, None] * qd - k * (kinv_diag[:, None] * qd - 1.0 / qd)
+        g_qs = seed.weighted_colsq(A2, A2t) * qd - k * (kinv_diag[:, None] * qd - 1.0 / qd)
     else:
-        Wg, ag = (Wc, 2.0) if het else (W, 2.0 * c)
         g_qs = torch.stack([splitk_gemm_nt(A2, ops.transpose(Wg[p]), c_lower=True, alpha=ag) for p in range(P)])
         for p in range(P):
             KinvLq = ops.gemm_nt(LinvT, ops.transpose(V[p], mode=1), b_tri=1, a_tri=1)  # Linv^T V_p = Kuu^-1 Lq_p (V_p lower)
@@ -921,20 +910,7 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
     X2 = ops.gemm_nt(X1, Linv, b_tri=2)                                                 # (.) Linv^T
     Lbar = splitk_gemm_nt(Kuf_bar, A, c_lower=True, alpha=-1.0) - torch.tril(X2)
     Lbar.diagonal().sub_(k * P / L.diagonal())
-    Kuu_bar = cholesky_adjoint(ops.transpose(L, mode=1), LinvT, Lbar)
-    dv1, dl1, Zb1 = spec.adjoint(Z, Xb, Kuf_bar, symmetric=False)
-    dv2, dl2, Zb2 = spec.adjoint(Z, Z, Kuu_bar, symmetric=True)
-    csum = cvec.sum() * P if het else c * B * P
-    g_var, g_ls = spec.pack([a + b + csum * dk for a, b, dk in zip(dv1, dv2, spec.dkdiag())],
-                            [a + b for a, b in zip(dl1, dl2)])
-    if het:   # dF/d sigma_n^2 per row (likelihood parameters are reached through Gaussian.noise_param_grads)
-        fvar = (spec.kdiag() - s0)[:, None] + ssq.t()
-        resid = Yb - fmean - mean_const
-        g_noise = scale * (-0.5 * P / nv + 0.5 * (resid * resid + fvar).sum(1) / (nv * nv))
-    else:
-        k0 = -0.5 * LOG2PI - 0.5 * float(np.log(noise_variance))
-        Q = 2.0 * noise_variance * (B * P * k0 - ve)
-        g_noise = (scale * (-0.5 * B * P / noise_variance + 0.5 * Q / noise_variance ** 2)).reshape(1)
-    grads = {"variance": g_var, "lengthscales": g_ls, "noise_variance": g_noise,
-             "Z": Zb1 + Zb2, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)}
+    g_var, g_ls, Zbar = _covariance_tail(spec, Z, Xb, Kuf_bar, ops.transpose(L, mode=1), LinvT, Lbar, seed.csum())
+    grads = {"variance": g_var, "lengthscales": g_ls, "noise_variance": seed.noise_grad(ve, s0, ssq, spec.kdiag()),
+             "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)}
     return F, grads, info

@@ -186,7 +186,6 @@ def gradient_spec(kernel, input_dim=None):
         ks.append(k)
         return len(ks) - 1
     tree = walk(kernel)
-    nested = any(not isinstance(c, int) for c in tree[1])
     cols = []
     for k in ks:
         if k.has_default_active_dims:
@@ -197,7 +196,7 @@ def gradient_spec(kernel, input_dim=None):
             cols.append(np.arange(int(input_dim))[k.active_dims])
         else:
             cols.append(np.asarray(k.active_dims, dtype=np.int64))
-    spec = gradients.KernelSpec([k.hyper() for k in ks], tree if nested else kernel._op, cols=cols)
+    spec = gradients.KernelSpec([k.hyper() for k in ks], tree, cols=cols)
     return spec, [(k.variance, k.lengthscales) for k in ks]
 
 

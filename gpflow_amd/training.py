@@ -258,7 +258,7 @@ class SVGPTrainer:
             spec0 = self.combo[0]
             members = [(f, float(np.ravel(self.constrained(nv))[0]), self.constrained(nl))
                        for (f, _, _), (nv, nl) in zip(spec0.members, self.member_names)]
-            spec = gradients.KernelSpec(members, spec0.tree if spec0.tree is not None else spec0.op, spec0.cols)
+            spec = gradients.KernelSpec(members, spec0.tree, spec0.cols)
             scatter = lambda gz: gz  # noqa: E731  (the spec slices for its members and scatters their input gradients itself)
             F, g, info = fn(self.dev["Z"], Xb.contiguous(), Yb, self.dev["q_mu"], q_sqrt, noise_variance=noise,
                             jitter=config.default_jitter(), scale=scale, mean_const=self.mean_const, kl_weight=1.0 / world,

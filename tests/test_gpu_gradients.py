@@ -76,6 +76,35 @@ def test_svgp_elbo_and_grad_vs_autograd_oracle(gpu, M, B, D, P, ard):
         np.testing.assert_allclose(got.reshape(ref.shape), ref, rtol=0, atol=tol, err_msg=name)
 
 
+@pytest.mark.parametrize("M,B,D,P,min_n", [(150, 300, 3, 2, None), (256, 512, 2, 1, 64)])
+def test_side_branch_schedules_give_the_same_gradients(gpu, monkeypatch, M, B, D, P, min_n):
+    """The three ways gradients._SideBranch can place the {q_mu, q_sqrt} branch -- inline after the main branch (OVERLAP_BRANCHES
+    off), on the side stream from the fork on (no gate), on the side stream with its products gated on the main branch's
+    preparation -- run the same kernels on the same operands: each meets the tolerance of
+    test_svgp_elbo_and_grad_vs_autograd_oracle.  (Every reduction has a fixed order, so the three should also agree bit for bit;
+    whether they do on a device has not been measured -- profiles/reverse_pass_refactor.txt section 3 -- so that is not asserted.)
+    The second shape also takes the K-split Cholesky-adjoint products (TRI_PRODUCT_MIN_N lowered to 64: M = 256, four chunks)."""
+    from gpflow_amd import gradients, ops
+    if min_n is not None:
+        monkeypatch.setattr(gradients, "TRI_PRODUCT_MIN_N", min_n)
+    X, Y, Z, q_mu, q_sqrt, kw = _problem(M, B, D, P, 2)
+    v, go = orcg.svgp_elbo_value_and_grads(X, Y, Z, q_mu, q_sqrt, num_data=1000, mean=0.1, **kw)
+    t = ops.to_device
+    args = (t(Z), t(X), t(Y), t(q_mu), t(q_sqrt))
+    names = ("variance", "lengthscales", "noise_variance", "Z", "q_mu", "q_sqrt", "mean_const")
+    for overlap, gate in [(False, True), (True, False), (True, True)]:
+        monkeypatch.setattr(gradients, "OVERLAP_BRANCHES", overlap)
+        monkeypatch.setattr(gradients, "GATE_SIDE_BRANCH", gate)
+        F, g, info = gradients.svgp_elbo_and_grad(*args, jitter=1e-6, scale=1000.0 / B, mean_const=0.1, **kw)
+        ops.check_info(info)
+        got = {"F": F.cpu().numpy(), **{n: g[n].cpu().numpy() for n in names}}
+        assert abs(float(got["F"][0]) - v) <= 1e-9 * abs(v), (overlap, gate)
+        for n in names:
+            ref = np.asarray(go[n])
+            np.testing.assert_allclose(got[n].reshape(ref.shape), ref, rtol=0, atol=1e-8 * max(1.0, np.abs(ref).max()),
+                                       err_msg=f"{n} overlap={overlap} gate={gate}")
+
+
 @pytest.mark.parametrize("M,B,D,P,ard", [(150, 300, 3, 2, True), (64, 200, 2, 1, False), (384, 1024, 8, 1, True)])
 def test_unwhitened_svgp_elbo_and_grad_vs_autograd_oracle(gpu, M, B, D, P, ard):
     """whiten=False (conditionals/util.py:137-139, kullback_leiblers.py:98-165 with K = Kuu): value and every gradient

@@ -83,6 +83,44 @@ def test_adjoint_composition_on_emulated_primitives(monkeypatch, M, B, D, P, ard
                                    err_msg=name)
 
 
+def test_benchmark_form_issues_a_fixed_list_of_primitive_calls(monkeypatch):
+    """The timed training step is svgp_elbo_and_grad in this form (whitened, full q_sqrt, one noise variance, one SquaredExponential
+    kernel): the ordered names of its `ops.*` calls, outermost only, are pinned so that a launch is not added to it unnoticed.  (P = 2:
+    the per-latent calls appear twice.  A deliberate change to the step changes this list with it.)"""
+    import types
+    import torch
+    from gpflow_amd import gradients
+    import fake_ops
+    calls, depth = [], [0]
+
+    def logged(name, fn):
+        def call(*a, **kw):
+            if depth[0] == 0:
+                calls.append(name)
+            depth[0] += 1
+            try:
+                return fn(*a, **kw)
+            finally:
+                depth[0] -= 1
+        return call
+    proxy = types.SimpleNamespace(**{n: logged(n, getattr(fake_ops, n)) for n in dir(fake_ops)
+                                     if not n.startswith("_") and callable(getattr(fake_ops, n))})
+    monkeypatch.setattr(gradients, "ops", proxy)
+    X, Y, Z, q_mu, q_sqrt, kw = _problem(64, 200, 3, 2, 2)
+    t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64))  # noqa: E731
+    gradients.svgp_elbo_and_grad(t(Z), t(X), t(Y), t(q_mu), t(q_sqrt), jitter=1e-6, scale=5.0, mean_const=0.1, **kw)
+    assert calls == [
+        "kernel_matrix", "kernel_matrix", "potrf_",                                            # trapezoid, factorisation
+        "combine_parts", "combine_parts", "transpose", "row_stats", "gemm_nt", "row_stats", "row_stats",   # projection
+        "gaussian_varexp_sum", "gauss_kl_white",
+        "lowrank_axpy", "gemm_nt", "gemm_nt", "transpose", "gemm_nt", "transpose",             # At_bar, Kfu_bar, Kuf_bar
+        "transpose", "gemm_nt", "combine_parts",                                               # Lm^T; Lm_bar
+        "transpose", "gemm_nt", "combine_parts", "gemm_nt", "transpose", "gemm_nt", "symmetrize_",   # Cholesky adjoint
+        "kernel_matrix_hadamard", "moment_rows", "gemm_nt", "stationary_adjoint_tail",         # kernel adjoint of Kuf
+        "kernel_matrix_hadamard", "moment_rows", "gemm_nt", "stationary_adjoint_tail",         # ... of Kuu, into the same pack
+        "row_stats", "transpose", "transpose", "gemm_nt", "combine_parts", "gemm_nt", "combine_parts"]   # q_mu_bar, Lq_bar
+
+
 def _small_model(M=40, B=120, D=2, P=2, seed=5):
     import gpflow_amd as gpflow
     X, Y, Z, q_mu, q_sqrt, kw = _problem(M, B, D, P, seed)
