@@ -8,8 +8,9 @@ Each case runs the device call and the `fake_ops` call on the same NumPy inputs 
   3. inputs of non-underscore functions are bitwise unchanged;
   4. a second identical device call is bit-identical (no floating-point atomics in the library);
   5. inputs outside the contract are refused on both sides.
-Every case carries a comment naming the boundary or branch it targets.  The CPU-tier guard at the end fails when a
-primitive shared by `fake_ops` and `ops` has no case table here.
+Every case carries a comment naming the boundary or branch it targets; for GEMM_CASES and PROJECT_CASES the branch is pinned, on the
+CPU, by tests/test_gpu_gemm_launch.py (test_contract_tables_are_on_their_branches): a row added here gets its pin there.  The
+CPU-tier guard at the end fails when a primitive shared by `fake_ops` and `ops` has no case table here.
 """
 import contextlib
 import math
@@ -165,14 +166,16 @@ GEMM_CASES = [
     (129, 255, 1024, 1.0, 0.0, 0, False, "c", 0),   # K >= 1024, few tiles: half-tile long-K branch (64 x 128)
     (127, 128, 129, 0.0, 1.5, 0, False, "c", 0),    # alpha = 0, beta != 0: off fast / small, generic kernel
     (128, 127, 48, 1.3, -0.7, 0, False, "c", 0),    # beta != 0 in the small kernel's (beta / alpha) C prologue
-    (256, 257, 160, -1.1, 0.9, 0, False, "c", 0),   # beta != 0 in the fast tile's C preload, partial column tile
+    (256, 257, 160, -1.1, 0.9, 0, False, "c", 0),   # beta != 0, partial column tile; 6 tiles < 24 and m > 64: the 64 x 128 generic tile
+    (64, 257, 160, -1.1, 0.9, 0, False, "c", 0),    # m <= 64: beta != 0 in the FAST tile's C preload, partial column tile
     (255, 256, 256, 1.0, 0.0, 1, False, "c", 0),    # b_tri = 1 (B upper): K range from n0 & ~15, B[:, < n0] is NaN
     (257, 300, 300, 1.0, 0.0, 2, False, "c", 0),    # b_tri = 2 (B lower): K range ends at n0 + 128, the rest is NaN
     (300, 300, 64, 1.0, 0.0, 0, True, "c", 0),      # c_lower: tiles above the diagonal keep their sentinel
     (257, 257, 256, 0.5, 0.25, 1, True, "c", 0),    # c_lower with b_tri and beta != 0
     (65, 63, 33, 1.0, 0.0, 0, False, "ld", 0),      # odd leading dimensions: generic kernel
     (129, 130, 64, 1.0, 0.0, 0, False, "off", 0),   # 8- but not 16-byte aligned pointers: off the small path
-    (129, 256, 256, 1.0, 0.5, 0, False, "off", 0),  # misaligned: off the fast path onto the generic kernel, beta != 0
+    (129, 256, 256, 1.0, 0.5, 0, False, "off", 0),  # misaligned, beta != 0, on the 64 x 128 generic tile (4 tiles: generic when aligned too)
+    (64, 256, 256, 1.0, 0.5, 0, False, "off", 0),   # m <= 64, misaligned: off the fast path onto the 128 x 128 generic tile, beta != 0
     (100, 70, 48, 1.0, 0.0, 0, False, "col", 0),    # column slices
     (64, 80, 32, 1.0, 0.0, 0, False, "c", 3),       # batch > 1: small kernel over the batch
     (130, 140, 144, 1.0, 0.0, 0, False, "c", 2),    # batch > 1, generic tiles over grid.y
@@ -838,9 +841,11 @@ PROJECT_CASES = [
     (40, 128, 2, False, "c"),     # rows <= 64, m % 16 == 0, aligned: fast tile with the squaring epilogue (kind 4 / 5)
     (300, 129, 2, False, "ld"),   # few rows, m odd: 64 x 128 few-rows branch (64-wide tiles would miss a partial slot)
     (257, 128, 4, False, "c"),    # few rows, pairs < 100, whole 64-column slots: the 32 x 64 few-rows branch
-    (1300, 512, 1, False, "c"),   # pairs 100 .. 199: the 64 x 64 few-rows branch
+    (1300, 512, 1, False, "c"),   # pairs 22 < 100: the 32 x 64 few-rows tile under the snake order (328 tiles on a grid of 512)
+    (1300, 512, 5, False, "c"),   # pairs 110 (100 .. 199): the 64 x 64 few-rows branch
     (65, 64, 3, True, "c"),       # batched At [P, rows, m] (SeparateIndependent)
-    (129, 96, 2, False, "off"),   # misaligned At: off the fast path
+    (129, 96, 2, False, "off"),   # misaligned At on the 32 x 64 few-rows tile (scalar loads)
+    (40, 96, 2, False, "off"),    # rows <= 64, misaligned At: off the fast path onto the 128 x 128 generic tile, squaring epilogue
 ]
 CASE_TABLES["project"] = PROJECT_CASES
 
