@@ -45,6 +45,12 @@ extern "C" size_t gpk_invd_elems(int n, int batch) {
   return (size_t)(batch > 0 ? batch : 1) * gpk_cdiv(n, NB) * NB * NB;
 }
 
+namespace {
+// gpk.h, "invd": the block inverses are stored and staged 16 bytes at a time (leaf2_device.h, group_solve.hip), whatever the
+// alignment of the factor -- checked on the host by every entry point that takes one, before anything is launched
+bool invd_aligned(const double* invd) { return (reinterpret_cast<uintptr_t>(invd) & 15) == 0; }
+}  // namespace
+
 // ---- per-device internal state (created lazily, once; see gpk.h "Internal state and threading") -------------------
 // The factorisation runs on streams of its own, forked from / joined to the caller's stream with events only:
 //   P   "panel" stream, high priority: the latency-bound critical path (leaf, panel solve, inner updates, strip) of
@@ -768,17 +774,19 @@ extern "C" int gpk_chain_handoff_mode(void) {
 
 extern "C" int gpk_potrf(void* stream, double* A, int n, int extra, long lda, int batch,
                          long strideA, double* invd, int zero_upper, int* info) {
+  if (!invd_aligned(invd)) return GPK_E_ARG;
   return gpk_potrf_core((hipStream_t)stream, A, n, extra, lda, batch, strideA, invd, zero_upper, info);
 }
 
 extern "C" int gpk_potrf_inv(void* stream, double* A, int n, int extra, long lda, double* invd, int zero_upper,
                              int* info) {
+  if (!invd_aligned(invd)) return GPK_E_ARG;
   return gpk_potrf_core((hipStream_t)stream, A, n, extra + n, lda, 1, 0, invd, zero_upper, info, PotrfHooks(), n);
 }
 
 extern "C" int gpk_trtri_blocks(void* stream, const double* L, int n, long ldl, int batch,
                                 long strideL, double* invd) {
-  if (!L || !invd || n < 0) return GPK_E_ARG;
+  if (!L || !invd || n < 0 || !invd_aligned(invd)) return GPK_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (batch <= 0) batch = 1;
   const int nblk = gpk_cdiv(n, NB);
@@ -809,7 +817,7 @@ extern "C" int gpk_trtri_blocks(void* stream, const double* L, int n, long ldl, 
 // n -- ran the N = 16384, T = 4096 predict solve at 7 TFLOP/s.)
 extern "C" int gpk_trsm(void* stream, int trans, const double* L, long ldl, const double* invd,
                         int n, double* B, int m, long ldb, int batch, long strideL, long strideB) {
-  if (n < 0 || m < 0) return GPK_E_ARG;
+  if (n < 0 || m < 0 || !invd_aligned(invd)) return GPK_E_ARG;
   if (n == 0 || m == 0) return 0;
   if (!L || !invd || !B) return GPK_E_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -835,7 +843,7 @@ extern "C" int gpk_trsm(void* stream, int trans, const double* L, long ldl, cons
 
 extern "C" int gpk_transpose_factor(void* stream, const double* L, long ldl, const double* invd,
                                     int n, double* LT, long ldlt, double* invdT) {
-  if (!L || !invd || !LT || !invdT || n < 0) return GPK_E_ARG;
+  if (!L || !invd || !LT || !invdT || n < 0 || !invd_aligned(invd) || !invd_aligned(invdT)) return GPK_E_ARG;
   if (n == 0) return 0;
   int rc = gpk_transpose(stream, L, n, n, ldl, LT, ldlt, 1, 1, 0, 0);
   if (rc) return rc;

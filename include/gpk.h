@@ -118,7 +118,11 @@ int gpk_kernel_matrix_hadamard(void* stream, int family, const double* X1, int n
  * unless zero_upper != 0.  `batch` matrices at stride strideA (SeparateIndependent: the
  * tf.map_fn loop of conditionals/util.py:618 becomes one batched launch sequence).
  * invd: [batch, ceil(n/NB), NB, NB] output, the inverses of L's diagonal blocks (reused by gpk_trsm);
- * gpk_invd_elems() gives its size in doubles.  info: device int[batch] (may be NULL). */
+ * gpk_invd_elems() gives its size in doubles.  invd must be 16-byte aligned (a buffer of gpk_invd_elems() doubles from any
+ * allocator is): the inverses are stored and staged 16 bytes at a time whatever the alignment of A.  gpk_potrf, gpk_potrf_inv,
+ * gpk_trtri_blocks, gpk_trsm and gpk_transpose_factor (invd and invdT) return GPK_E_ARG for one that is not, before anything
+ * is launched.  A itself may have any 8-byte alignment, leading dimension and batch stride.
+ * info: device int[batch] (may be NULL). */
 size_t gpk_invd_elems(int n, int batch);
 int gpk_potrf(void* stream, double* A, int n, int extra, long lda, int batch, long strideA,
               double* invd, int zero_upper, int* info);

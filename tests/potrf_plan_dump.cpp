@@ -1,6 +1,8 @@
 // Prints the schedule plan of the trapezoidal Cholesky for one shape: tests/test_potrf_plan.py builds this with plain g++ (no ROCm
 // include path -- which is the check that potrf_plan.h needs no HIP header) and reads the lines back.
-//   potrf_plan_dump n extra batch tri bulk_cus flags_usable
+//   potrf_plan_dump n extra batch tri bulk_cus flags_usable [replan]
+// replan != 0: the extra-row groups as gpk_potrf_core plans them again (plan_extra_rows(false)) when the operands rule the progressive
+// first group out.
 #include <cstdio>
 #include <cstdlib>
 #include "../gpflow_amd/csrc/potrf_plan.h"
@@ -8,10 +10,11 @@
 static const char* name(PotrfStream s) { return s == PotrfStream::B_masked ? "B_masked" : s == PotrfStream::Bs ? "Bs" : "X"; }
 
 int main(int argc, char** argv) {
-  if (argc != 7) return 2;
+  if (argc != 7 && argc != 8) return 2;
   const PotrfShape shape{atoi(argv[1]), atoi(argv[2]), atoi(argv[3]), atoi(argv[4])};
   const PotrfDevice dev{atoi(argv[5]), atoi(argv[6]) != 0};
-  const PotrfPlan pl = make_potrf_plan(shape, dev);
+  PotrfPlan pl = make_potrf_plan(shape, dev);
+  if (argc == 8 && atoi(argv[7]) != 0) pl.plan_extra_rows(false);
 #define I(f) printf(#f " %d\n", (int)pl.f)
   I(single_leaf); I(large); I(nbo); I(ride); I(useX); I(R); I(chain_wgs); I(xgroup); I(xgroup_first); I(tail_zone); I(rest_tiled);
   I(rest_tiled_min_wgs); I(rest_small_wgs); I(rest_tile64); I(trail_queue); I(bulk_cus); I(progressive_candidate); I(prog_end);

@@ -74,32 +74,67 @@ def _np(t):
     return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
 
 
-def _on(x, layout="c", dev="cuda"):
+def _on(x, layout="c", dev="cuda", base=False):
     """NumPy -> fp64 tensor on `dev` in one of the operand layouts the kernels distinguish:
     c: fresh contiguous tensor (a zero-row one has no storage: data_ptr() == 0);
     view0: a zero-row VIEW into live storage (non-null pointer);
     ld: row-major view with an odd leading dimension;
     off: storage starting one element in -- 8-byte but not 16-byte aligned;
-    col: a column slice (odd start, ld = cols + 2), as active_dims produces.
-    Padding around a view is NaN, inside the allocation."""
+    col: a column slice (odd start, ld = cols + 2), as active_dims produces;
+    pad: the first cols columns of a wider buffer whose leading dimension is even (the smallest even value >= cols + 2): base and
+         every row 16-byte aligned, as in c, but ld != cols;
+    bpad / bodd (3-D input only; any other layout of a 3-D input is c): contiguous entries carved from one 1-D buffer at batch stride
+         rows * cols + 2 (even) / rows * cols + 1 (odd: every second entry is 8-byte aligned only).
+    Padding around a view is NaN, inside the allocation.  base=True: returns (view, allocation), for _outside_view."""
     x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 3 and layout in ("bpad", "bodd"):
+        b, r, c = x.shape
+        stride = r * c + (2 if layout == "bpad" else 1)
+        buf = torch.full((b * stride,), NAN, dtype=torch.float64, device=dev)
+        v = torch.as_strided(buf, (b, r, c), (stride, c, 1))
+        v.copy_(torch.from_numpy(x))
+        return (v, buf) if base else v
     if layout == "c" or x.ndim != 2:
-        return torch.tensor(x, dtype=torch.float64, device=dev)
+        v = torch.tensor(x, dtype=torch.float64, device=dev)
+        return (v, v) if base else v
     r, c = x.shape
     if layout == "view0":
         assert r == 0
-        return torch.full((2, max(c, 1)), NAN, dtype=torch.float64, device=dev)[:0, :c]
+        buf = torch.full((2, max(c, 1)), NAN, dtype=torch.float64, device=dev)
+        return (buf[:0, :c], buf) if base else buf[:0, :c]
     if layout == "ld":
         ld = c + 1 if (c + 1) % 2 else c + 2
-        v = torch.full((r, ld), NAN, dtype=torch.float64, device=dev)[:, :c]
+        buf = torch.full((r, ld), NAN, dtype=torch.float64, device=dev)
+        v = buf[:, :c]
+    elif layout == "pad":
+        buf = torch.full((r, c + 2 + c % 2), NAN, dtype=torch.float64, device=dev)
+        v = buf[:, :c]
     elif layout == "off":
-        v = torch.full((r * c + 1,), NAN, dtype=torch.float64, device=dev)[1:].view(r, c)
+        buf = torch.full((r * c + 1,), NAN, dtype=torch.float64, device=dev)
+        v = buf[1:].view(r, c)
     elif layout == "col":
-        v = torch.full((r, c + 2), NAN, dtype=torch.float64, device=dev)[:, 1:1 + c]
+        buf = torch.full((r, c + 2), NAN, dtype=torch.float64, device=dev)
+        v = buf[:, 1:1 + c]
     else:
         raise KeyError(layout)
     v.copy_(torch.from_numpy(x))
-    return v
+    return (v, buf) if base else v
+
+
+def _outside_view(v, buf):
+    """The elements of the allocation `buf` that are not part of its view `v` (from v's offset and strides), as a NumPy array."""
+    off = (v.data_ptr() - buf.data_ptr()) // 8 if v.numel() else 0
+    idx = np.full((), off, dtype=np.int64)
+    for size, stride in zip(v.shape, v.stride()):
+        idx = idx[..., None] + np.arange(size, dtype=np.int64) * stride
+    inside = np.zeros(buf.numel(), dtype=bool)
+    inside[idx.reshape(-1)] = True
+    return _np(buf).reshape(-1)[~inside]
+
+
+def _padding_untouched(v, buf):
+    """every element of the allocation outside the view is bitwise the NaN _on filled it with"""
+    return bool(np.all(_bits(_outside_view(v, buf)) == _bits(np.array([NAN]))[0]))
 
 
 def _impls():

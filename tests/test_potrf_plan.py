@@ -30,9 +30,11 @@ def _value(text):
     return int(text) if text.lstrip("-").isdigit() else text
 
 
-def plan(dumper, n, extra, batch=1, tri=0, bulk_cus=224, flags_usable=1):
-    out = subprocess.run([dumper] + [str(v) for v in (n, extra, batch, tri, bulk_cus, flags_usable)], check=True, capture_output=True,
-                         text=True).stdout
+def plan(dumper, n, extra, batch=1, tri=0, bulk_cus=224, flags_usable=1, replan=0):
+    """replan=1: with the extra-row groups planned again without the progressive first group (what gpk_potrf_core does when the operands
+    rule it out)"""
+    out = subprocess.run([dumper] + [str(v) for v in (n, extra, batch, tri, bulk_cus, flags_usable, replan)], check=True,
+                         capture_output=True, text=True).stdout
     whole, panels = {}, []
     for line in out.splitlines():
         key, *rest = line.split()
