@@ -431,7 +431,7 @@ int elbo_shard(void* stream, const ElboArgs& a, int whiten, void* ws, size_t ws_
       a.P > 16)
     return GPK_E_ARG;
   if (a.lik) {
-    const int rc = gpk_likelihood_check(a.lik, a.lik_params);
+    const int rc = gpk_likelihood_check(a.lik, a.lik_params, a.P);
     if (rc) return rc;
   }
   const ElboWs w = elbo_layout(ws, a.m, a.rows, a.P, a.q_diag, whiten);

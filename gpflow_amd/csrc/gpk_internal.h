@@ -106,7 +106,7 @@ int gpk_launch_varexp_stage1(hipStream_t s, const double* Y, long ldy, const dou
                              double mean_const, double* fvar_out, double* part, int* count,
                              const double* noise_rows = nullptr);   // per-row noise variances [rows] or nullptr (constant `noise`)
 // the quadrature stage of gpk_likelihood_varexp_sum (same operands); part1 (partials of sum dVE/dscale) may be null
-int gpk_likelihood_check(int lik, const double* params);   // 0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters)
+int gpk_likelihood_check(int lik, const double* params, int P);   // 0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters, classes)
 int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const double* Y, long ldy, const double* fmean,
                                         int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
                                         const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,

@@ -337,7 +337,8 @@ struct LikVarexpArgs {
   const double* s0; int s0_per_latent; const double* ssq;
   double knn[16]; int knn_per_latent;
   double mean_const;
-  double par0, par1, c0;   // Poisson: binsize, -, log(binsize);  StudentT: scale, df, the f-independent part of log p
+  double par0, par1, c0;   // Poisson: binsize, -, log(binsize);  StudentT: scale, df, the f-independent part of log p;
+                           // MultiClass: log(1 - eps), log(eps / (C - 1)), their difference
   double *fvar_out, *rows_out, *dmu_out, *dvar_out;
   double *part, *part1;    // stage-1 partials of sum VE and (part1 may be null) of sum dVE/dscale
 };
@@ -433,6 +434,105 @@ __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
   if (a.part1) {   // (kernel argument: uniform)
     const double r1 = block_sum(acc1, sh);
     if (threadIdx.x == 0) a.part1[blockIdx.x] = r1;
+  }
+}
+
+// ---- MultiClass / RobustMax variational expectations, stage 1 (likelihoods/multiclass.py: MultiClass._variational_expectations,
+// RobustMax.prob_is_largest) ------------------------------------------------------------------------------------------------
+//   y = Y[b, 0] (ONE label column),  s = sqrt(max(2 v_y, 1e-10)),  X_h = mu_y + s x_h,  d_kh = (X_h - mu_k) / sqrt(max(v_k, 1e-10)),
+//   c_kh = Phi(d_kh) (1 - 2e-4) + 1e-4,  Pi_h = prod_{k != y} c_kh,  p = sum_h (w_h / sqrt pi) Pi_h,
+//   VE_b = p log(1 - eps) + (1 - p) log(eps / (C - 1)),  and the exact derivatives of that sum w.r.t. all C means and variances.
+// The lane layout of lik_varexp_kernel carries over -- four adjacent lanes per (row, latent) group, five nodes each, floor(16 / P)
+// whole rows per wave pass -- but the P groups of a row are coupled: group k evaluates c_kh and t_kh = (1 - 2e-4) phi(d_kh) /
+// (sqrt(v_k) c_kh) at its nodes (group y: c = 1, t = 0), the product over the row's groups is a fixed-order shuffle loop (k = 0, 1,
+// ...), and each group then forms its own sums  a1 = sum_h w Pi t,  a2 = sum_h w Pi t d,  a3 = sum_h w Pi t x:
+//   dVE/dmu_k = -kappa a1,  dVE/dv_k = -kappa a2 / (2 sqrt v_k)   (k != y);   kappa = log(1 - eps) - log(eps / (C - 1))
+//   dVE/dmu_y = kappa sum_k a1_k,  dVE/dv_y = kappa sum_k a3_k / s   (the sums over h and k of the definition, k outermost)
+// The clamps are comparisons, so a NaN variance stays NaN; where one is active the derivative w.r.t. that variance is exactly 0
+// (tf.clip_by_value under autodiff).  A label that is no integer in [0, P) adds NaN to every output of its row.
+// par0 = log(1 - eps), par1 = log(eps / (C - 1)), c0 = kappa.
+__global__ __launch_bounds__(RB) void lik_multiclass_kernel(LikVarexpArgs a) {
+  constexpr int NPL = GH_N / 4;      // nodes per lane
+  __shared__ double sh[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int g = lane >> 2, k = lane & 3;
+  const int rpw = 16 / a.P;                       // whole rows per wave pass (2 <= P <= 16)
+  const int jr = g / a.P, p = g - jr * a.P;       // this group's row within the pass, its latent (class)
+  const int row_lane0 = (jr * a.P * 4) & 63;      // lane of the row's first group
+  const long npass = ((long)a.rows + rpw - 1) / rpw;
+  double acc = 0.0;
+  for (long u = (long)blockIdx.x * (RB / 64) + w; u < npass; u += (long)gridDim.x * (RB / 64)) {
+    const long b = u * rpw + jr;
+    const bool act = jr < rpw && b < a.rows;
+    double y = 0.0, mu = 0.0, fv = 1.0;           // (idle lanes of a pass run on harmless values and are masked below)
+    if (act) {
+      fv = a.knn[a.knn_per_latent ? p : 0];
+      if (a.s0) fv -= a.s0_per_latent ? a.s0[(long)p * a.rows + b] : a.s0[b];
+      if (a.ssq) fv += a.ssq[(long)p * a.rows + b];
+      mu = a.fmean[b * a.P + p] + a.mean_const;
+      y = a.Y[b * a.ldy];
+    }
+    const bool lab_ok = y >= 0.0 && y < (double)a.P && y == floor(y);   // (false for NaN and +-Inf)
+    const int yi = lab_ok ? (int)y : 0;
+    const double ynan = lab_ok ? 0.0 : __builtin_nan("");
+    const bool isy = p == yi;
+    const int ylane = (row_lane0 + yi * 4) & 63;
+    const double mu_y = __shfl(mu, ylane), fv_y = __shfl(fv, ylane);
+    const double tv = 2.0 * fv_y;
+    const bool clamp_y = tv < 1e-10, clamp_k = fv < 1e-10;
+    const double s = sqrt(clamp_y ? 1e-10 : tv);
+    const double sdk = sqrt(clamp_k ? 1e-10 : fv);
+    double c[NPL], t[NPL], d[NPL], pi[NPL];
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      d[j] = (fma(s, gh_x_dev[k * NPL + j], mu_y) - mu) / sdk;
+      const double cc = 0.5 * erfc(-d[j] * 0.7071067811865476) * (1.0 - 2e-4) + 1e-4;
+      const double tt = ((1.0 - 2e-4) * 0.3989422804014327) * exp(-0.5 * d[j] * d[j]) / (sdk * cc);
+      c[j] = isy ? 1.0 : cc;
+      t[j] = isy ? 0.0 : tt;
+      pi[j] = 1.0;
+    }
+    for (int q = 0; q < a.P; ++q) {   // the row's P groups sit in adjacent groups of this wave: multiplied in the order k = 0, 1, ...
+      const int src = (row_lane0 + q * 4 + k) & 63;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) pi[j] *= __shfl(c[j], src);
+    }
+    double sp = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      const double wp = gh_w_dev[k * NPL + j] * 0.5641895835477563 * pi[j];   // (w_h / sqrt(pi)) Pi_h
+      const double wt = wp * t[j];
+      sp += wp;
+      a1 += wt;
+      a2 += wt * d[j];
+      a3 += wt * gh_x_dev[k * NPL + j];
+    }
+    sp += __shfl_xor(sp, 1); a1 += __shfl_xor(a1, 1); a2 += __shfl_xor(a2, 1); a3 += __shfl_xor(a3, 1);
+    sp += __shfl_xor(sp, 2); a1 += __shfl_xor(a1, 2); a2 += __shfl_xor(a2, 2); a3 += __shfl_xor(a3, 2);
+    double s1 = 0.0, s3 = 0.0;   // group y collects the others' sums in the order k = 0, 1, ... (its own are zeros)
+    for (int q = 0; q < a.P; ++q) {
+      const int src = (row_lane0 + q * 4) & 63;
+      s1 += __shfl(a1, src);
+      s3 += __shfl(a3, src);
+    }
+    const double ve = sp * a.par0 + (1.0 - sp) * a.par1 + ynan;   // (every lane of the row holds the same bits of sp)
+    const double dmu = (isy ? a.c0 * s1 : -a.c0 * a1) + ynan;
+    const double dvar = (isy ? (clamp_y ? 0.0 : a.c0 * s3 / s) : (clamp_k ? 0.0 : -a.c0 * a2 / (2.0 * sdk))) + ynan;
+    if (act && k == 0) {
+      const long e = b * a.P + p;
+      if (a.fvar_out) a.fvar_out[e] = fv;
+      if (a.dmu_out) a.dmu_out[e] = dmu;
+      if (a.dvar_out) a.dvar_out[e] = dvar;
+      if (p == 0) {   // one group per row
+        if (a.rows_out) a.rows_out[b] = ve;
+        acc += ve;
+      }
+    }
+  }
+  const double r0 = block_sum(acc, sh);
+  if (threadIdx.x == 0) {
+    a.part[blockIdx.x] = r0;
+    if (a.part1) a.part1[blockIdx.x] = 0.0;
   }
 }
 
@@ -753,9 +853,11 @@ extern "C" int gpk_gauss_hermite(int n, double* x_host, double* w_host) {
   return 0;
 }
 
-// 0 if (lik, lik_params_host) names a likelihood the quadrature stage implements
-int gpk_likelihood_check(int lik, const double* params) {
+// 0 if (lik, lik_params_host) names a likelihood the quadrature stage implements for P latents
+int gpk_likelihood_check(int lik, const double* params, int P) {
   switch (lik) {
+    case GPK_LIK_MULTICLASS_ROBUSTMAX:   // params = {epsilon}; P is the number of classes
+      return (P >= 2 && P <= 16 && params && params[0] > 0.0 && params[0] < 1.0) ? 0 : GPK_E_ARG;
     case GPK_LIK_BERNOULLI_PROBIT: return 0;
     case GPK_LIK_POISSON_EXP: return (params && params[0] > 0.0) ? 0 : GPK_E_ARG;
     case GPK_LIK_STUDENT_T: return (params && params[0] > 0.0 && params[1] > 0.0) ? 0 : GPK_E_ARG;
@@ -767,7 +869,7 @@ int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* pa
                                         int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
                                         const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
                                         double* rows_out, double* dmu_out, double* dvar_out, double* part, double* part1, int* count) {
-  const int rc = gpk_likelihood_check(lik, params);
+  const int rc = gpk_likelihood_check(lik, params, P);
   if (rc) return rc;
   LikVarexpArgs a{};
   a.Y = Y; a.ldy = ldy; a.fmean = fmean; a.rows = rows; a.P = P;
@@ -776,7 +878,7 @@ int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* pa
   a.knn_per_latent = knn_per_latent; a.mean_const = mean_const;
   a.fvar_out = fvar_out; a.rows_out = rows_out; a.dmu_out = dmu_out; a.dvar_out = dvar_out;
   a.part = part; a.part1 = part1;
-  const int per_wave = (lik == GPK_LIK_POISSON_EXP ? 64 : 16) / P;   // whole rows per wave pass
+  const int per_wave = (lik == GPK_LIK_POISSON_EXP ? 64 : 16) / P;   // whole rows per wave pass (MultiClass: per row, not per element)
   long nb = (((long)rows + per_wave - 1) / per_wave + RB / 64 - 1) / (RB / 64);
   if (nb < 1) nb = 1;
   if (nb > MAXPART) nb = MAXPART;
@@ -786,6 +888,10 @@ int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* pa
   } else if (lik == GPK_LIK_POISSON_EXP) {
     a.par0 = params[0]; a.c0 = log(params[0]);
     hipLaunchKernelGGL((lik_varexp_kernel<GPK_LIK_POISSON_EXP>), grid, block, 0, s, a);
+  } else if (lik == GPK_LIK_MULTICLASS_ROBUSTMAX) {
+    const double eps = params[0];
+    a.par0 = log1p(-eps); a.par1 = log(eps / (double)(P - 1)); a.c0 = a.par0 - a.par1;
+    hipLaunchKernelGGL(lik_multiclass_kernel, grid, block, 0, s, a);
   } else {
     const double scale = params[0], df = params[1];
     a.par0 = scale; a.par1 = df;

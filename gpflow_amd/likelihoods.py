@@ -1,6 +1,7 @@
 """Likelihoods: Gaussian (gpflow/likelihoods/scalar_continuous.py:41-148) -- the conjugate case that keeps the whole ELBO on
 the dense path -- and the scalar non-conjugate ones whose variational expectations are Gauss-Hermite quadrature on the device
-(Bernoulli, Poisson: scalar_discrete.py; StudentT: scalar_continuous.py; ScalarLikelihood: base.py)."""
+(Bernoulli, Poisson: scalar_discrete.py; StudentT: scalar_continuous.py; ScalarLikelihood: base.py), and MultiClass with the
+RobustMax link (multiclass.py), whose latents are coupled under one quadrature sum per row."""
 from __future__ import annotations
 
 from math import lgamma, log, pi, sqrt
@@ -301,3 +302,131 @@ class StudentT(ScalarLikelihood):
     def _conditional_variance(self, F):
         scale = float(self.scale.numpy())
         return torch.full_like(F, scale * scale * self.df / (self.df - 2.0))
+
+
+class RobustMax:
+    """RobustMax(num_classes, epsilon=1e-3), multiclass.py: the class with the largest latent gets probability 1 - epsilon, every
+    other one epsilon / (num_classes - 1).  epsilon is a plain float (not trainable, as in the reference)."""
+
+    def __init__(self, num_classes: int, epsilon: float = 1e-3):
+        self.num_classes = int(num_classes)
+        self.epsilon = float(epsilon)
+        if self.num_classes < 2:
+            raise ValueError("RobustMax: at least two classes")
+        if not 0.0 < self.epsilon < 1.0:
+            raise ValueError("RobustMax: epsilon must lie in (0, 1)")
+
+    @property
+    def eps_k1(self) -> float:
+        return self.epsilon / (self.num_classes - 1.0)
+
+    def __call__(self, F):
+        """one-hot [..., C] with 1 - epsilon on the argmax of F and eps_k1 elsewhere"""
+        F = ops.to_device(F)
+        hot = torch.nn.functional.one_hot(torch.argmax(F, dim=-1), self.num_classes).to(F.dtype)
+        return hot * (1.0 - self.epsilon - self.eps_k1) + self.eps_k1
+
+    @staticmethod
+    def _labels(Y, C: int):
+        """(class index [N], 0 | NaN [N]) of a label column [N, 1]: a label that is no integer in [0, C) gives NaN (the choice the
+        kernel makes, include/gpk.h: the reference would index garbage)"""
+        y = Y.reshape(-1)
+        ok = (y >= 0) & (y < C) & (y == torch.floor(y))
+        return torch.where(ok, y, torch.zeros_like(y)).long(), torch.where(ok, torch.zeros_like(y), torch.full_like(y, float("nan")))
+
+    def prob_is_largest(self, Y, mu, var, gh_x, gh_w):
+        """P(f_y > f_k for all k != y) under independent N(mu_k, var_k), [N, 1]: the Gauss-Hermite sum over the label's latent of the
+        product of the other latents' normal CDFs (with the reference's clamps and its 1e-4 CDF jitter)."""
+        Y, mu, var = ops.to_device(Y), ops.to_device(mu), ops.to_device(var)
+        gh_x = torch.as_tensor(gh_x, dtype=torch.float64, device=mu.device)
+        gh_w = torch.as_tensor(gh_w, dtype=torch.float64, device=mu.device)
+        idx, ynan = self._labels(Y, self.num_classes)
+        on = torch.nn.functional.one_hot(idx, self.num_classes).to(mu.dtype)                       # [N, C]
+        mu_y, var_y = (on * mu).sum(1, keepdim=True), (on * var).sum(1, keepdim=True)
+        X = mu_y + torch.sqrt(torch.clamp(2.0 * var_y, min=1e-10)) * gh_x                          # [N, H]
+        dist = (X[:, None, :] - mu[:, :, None]) / torch.sqrt(torch.clamp(var, min=1e-10))[:, :, None]
+        cdfs = 0.5 * torch.special.erfc(-dist / sqrt(2.0)) * (1.0 - 2e-4) + 1e-4
+        cdfs = cdfs * (1.0 - on)[:, :, None] + on[:, :, None]
+        return torch.prod(cdfs, dim=1) @ (gh_w / sqrt(pi)).reshape(-1, 1) + ynan[:, None]
+
+
+class MultiClass(Likelihood):
+    """MultiClass(num_classes, invlink=None), multiclass.py: labels Y [N, 1] in 0 .. C - 1, one latent per class.  Only the
+    RobustMax link (the default) is built; Softmax is Monte-Carlo in the reference.  `variational_expectations`, the hot one, runs
+    in gpk_likelihood_varexp_sum (GPK_LIK_MULTICLASS_ROBUSTMAX); the prediction-side integrals are device glue over the 20-node
+    table.  The C latents of a row are coupled, so they cannot be chunked like the columns of a ScalarLikelihood: C <= 16."""
+
+    device_lik = "multiclass_robustmax"
+    MAX_DEVICE_CLASSES = 16
+
+    def __init__(self, num_classes: int, invlink=None):
+        self.num_classes = int(num_classes)
+        if invlink is None:
+            invlink = RobustMax(self.num_classes)
+        if not isinstance(invlink, RobustMax):
+            raise NotImplementedError("MultiClass: only the RobustMax link is implemented")
+        if invlink.num_classes != self.num_classes:
+            raise ValueError("MultiClass: the link has another number of classes")
+        self.invlink = invlink
+
+    def device_params(self) -> tuple:
+        return (self.invlink.epsilon,)
+
+    def check_device_classes(self, num_latents=None):
+        """ValueError if the latents are not one per class; NotImplementedError past the kernel's limit"""
+        if num_latents is not None and int(num_latents) != self.num_classes:
+            raise ValueError(f"MultiClass({self.num_classes}) needs {self.num_classes} latent GPs, got {int(num_latents)}")
+        if self.num_classes > self.MAX_DEVICE_CLASSES:
+            raise NotImplementedError(f"MultiClass: at most {self.MAX_DEVICE_CLASSES} classes (the latents of a row are coupled in "
+                                      f"one kernel pass and cannot be chunked), got {self.num_classes}")
+
+    def _flat(self, *tensors):
+        out = []
+        for t in tensors:
+            t = ops.to_device(t)
+            out.append(t.reshape(-1, t.shape[-1]))
+        return out
+
+    def log_prob(self, X, F, Y):
+        F, Y = ops.to_device(F), ops.to_device(Y)
+        Ff, Yf = self._flat(F, Y)
+        idx, ynan = RobustMax._labels(Yf, self.num_classes)
+        hits = torch.argmax(Ff, dim=-1) == idx
+        eps = self.invlink.epsilon
+        lp = torch.where(hits, torch.full_like(ynan, log(1.0 - eps)), torch.full_like(ynan, log(self.invlink.eps_k1))) + ynan
+        return lp.reshape(F.shape[:-1])
+
+    def conditional_mean(self, X, F):
+        return self.invlink(F)
+
+    def conditional_variance(self, X, F):
+        p = self.invlink(F)
+        return p - p * p
+
+    def variational_expectations(self, X, Fmu, Fvar, Y) -> torch.Tensor:
+        """multiclass.py MultiClass._variational_expectations: p log(1 - eps) + (1 - p) log(eps / (C - 1)) per row, [N]"""
+        self.check_device_classes(tuple(Fmu.shape)[-1])   # (refused before anything touches the device)
+        Fmu = ops.to_device(Fmu)
+        Fm, Fv, Yd = self._flat(Fmu, Fvar, Y)
+        rows = ops.likelihood_varexp_sum(Yd[:, :1], Fm.contiguous(), s0=None, ssq=Fv.t().contiguous(), knn=[0.0], lik=self.device_lik,
+                                         params=self.device_params(), want_rows=True)[1]
+        return rows.reshape(Fmu.shape[:-1])
+
+    def _density(self, Fm, Fv, Yd):
+        """_predict_non_logged_density on flat operands: p (1 - eps) + (1 - p) eps / (C - 1), [N]"""
+        x, w = ops.gauss_hermite(DEFAULT_NUM_GAUSS_HERMITE_POINTS)
+        p = self.invlink.prob_is_largest(Yd, Fm, Fv, x, w)[:, 0]
+        return p * (1.0 - self.invlink.epsilon) + (1.0 - p) * self.invlink.eps_k1
+
+    def predict_mean_and_var(self, X, Fmu, Fvar):
+        """multiclass.py: the density of every class in turn, ([..., C], ps - ps^2)"""
+        Fmu = ops.to_device(Fmu)
+        Fm, Fv = self._flat(Fmu, Fvar)
+        ps = torch.stack([self._density(Fm, Fv, torch.full((Fm.shape[0], 1), float(i), dtype=Fm.dtype, device=Fm.device))
+                          for i in range(self.num_classes)], dim=1).reshape(Fmu.shape[:-1] + (self.num_classes,))
+        return ps, ps - ps * ps
+
+    def predict_log_density(self, X, Fmu, Fvar, Y):
+        Fmu = ops.to_device(Fmu)
+        Fm, Fv, Yd = self._flat(Fmu, Fvar, Y)
+        return torch.log(self._density(Fm, Fv, Yd[:, :1])).reshape(Fmu.shape[:-1])

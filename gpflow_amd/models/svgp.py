@@ -13,7 +13,7 @@ from ..inducing_variables import (InducingPoints, SharedIndependentInducingVaria
                                   inducingpoint_wrapper)
 from ..kernels import Kernel, SharedIndependent
 from ..kernels.stationaries import Stationary
-from ..likelihoods import Gaussian, Likelihood, ScalarLikelihood
+from ..likelihoods import Gaussian, Likelihood, MultiClass, ScalarLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
 from .training_mixins import ExternalDataTrainingLossMixin
@@ -63,7 +63,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
     # ---- fused device path ---------------------------------------------------------------------
     def _fused_config(self):
         """(stationary kernel, Z tensor, mean constant) when the whole ELBO shard is one C-ABI call:
-        Gaussian likelihood or one of the quadrature likelihoods (Bernoulli, Poisson, StudentT: gpk_svgp_elbo_shard_lik), constant
+        Gaussian likelihood or one of the quadrature likelihoods (Bernoulli, Poisson, StudentT, MultiClass: gpk_svgp_elbo_shard_lik), constant
         mean, and one stationary kernel shared by all latents (plain kernel +
         InducingPoints, or SharedIndependent + SharedIndependentInducingVariables); whitened or not, full or diagonal q_sqrt."""
         if not (isinstance(self.likelihood, Gaussian) or self._device_likelihood()):
@@ -79,8 +79,12 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         return k, iv.Z.device_value(), c
 
     def _device_likelihood(self) -> bool:
-        """a non-Gaussian likelihood whose variational expectations the library computes (ops.LIKELIHOOD_CODES), at most 16 latents"""
+        """a non-Gaussian likelihood whose variational expectations the library computes (ops.LIKELIHOOD_CODES), at most 16 latents;
+        MultiClass raises where its classes and the latents do not fit (see below) instead of falling back"""
         lik = self.likelihood
+        if isinstance(lik, MultiClass):   # one latent per class, coupled within a row: no chunking past the kernel's 16
+            lik.check_device_classes(self.q_mu.shape[1])   # (ValueError: latents != classes; NotImplementedError: more than 16)
+            return True
         return isinstance(lik, ScalarLikelihood) and lik.device_lik in ops.LIKELIHOOD_CODES and self.q_mu.shape[1] <= 16
 
     def _fused_separate_config(self):
@@ -209,6 +213,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
     def elbo_terms(self, data):
         """(sum_b var_exp_b over the given rows, KL) as a 2-element device tensor -- the two pieces
         svgp.py:172-174 combines; the first is what gets all-reduced when the minibatch is sharded."""
+        if isinstance(self.likelihood, MultiClass):   # (refused before anything touches the device)
+            self.likelihood.check_device_classes(self.q_mu.shape[1])
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])
         fused = self._fused_config()
         if fused is not None:
@@ -346,7 +352,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         from ..mean_functions import Constant
         lik, mf = self.likelihood, self.mean_function
         # scope checks first: a model outside the reverse pass is refused before anything touches the device
-        if isinstance(lik, ScalarLikelihood):
+        if isinstance(lik, (ScalarLikelihood, MultiClass)):
             return self._elbo_and_grad_quadrature(data)
         sep = self._separate_gradient_config()
         from ..kernels.base import gradient_spec
@@ -419,7 +425,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         return self._add_log_prior(Fv, out)   # (+ log prior density of the trainable parameters: model.py:56-76)
 
     def _elbo_and_grad_quadrature(self, data):
-        """elbo_and_grad with a quadrature likelihood (Bernoulli, Poisson, StudentT): the whitened reverse pass seeded per (row,
+        """elbo_and_grad with a quadrature likelihood (Bernoulli, Poisson, StudentT, MultiClass): the whitened reverse pass seeded per (row,
         latent) by the kernel's own d/dfmean, d/dfvar (gradients.svgp_elbo_and_grad, likelihood=).  Whitened, ONE isotropic
         stationary kernel over all input columns (optionally shared by the latents), InducingPoints, full or diagonal q_sqrt,
         constant mean; everything else is refused before anything touches the device."""
@@ -434,7 +440,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         c = mf.constant_value()
         if not (self.whiten and self._device_likelihood() and isinstance(k, IsotropicStationary) and k.family in ops.KERNEL_FAMILIES
                 and k.has_default_active_dims and isinstance(iv, InducingPoints) and c is not None):
-            raise NotImplementedError("gradients with a Bernoulli / Poisson / StudentT likelihood: whitened SVGP with one "
+            raise NotImplementedError("gradients with a Bernoulli / Poisson / StudentT / MultiClass likelihood: whitened SVGP with one "
                                       "SquaredExponential / Matern kernel (optionally shared by independent latents) over all input "
                                       "columns, InducingPoints, constant mean, at most 16 latents")
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])

@@ -454,18 +454,29 @@ def gaussian_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[to
     return out, fvar
 
 
-LIKELIHOOD_CODES = {"bernoulli_probit": 1, "poisson_exp": 2, "student_t": 3}   # include/gpk.h: GPK_LIK_*
+LIKELIHOOD_CODES = {"bernoulli_probit": 1, "poisson_exp": 2, "student_t": 3, "multiclass_robustmax": 4}   # include/gpk.h: GPK_LIK_*
+_LIKELIHOOD_NPAR = {"bernoulli_probit": 0, "poisson_exp": 1, "student_t": 2, "multiclass_robustmax": 1}
+ROW_LIKELIHOODS = ("multiclass_robustmax",)   # the latents of a row are coupled: Y is ONE column of labels, P >= 2 classes
 
 
 def _lik_args(lik: str, params):
     """(code, host array | None) of the (lik, lik_params_host) pair of the C-ABI: params is () for "bernoulli_probit", (binsize,)
-    for "poisson_exp", (scale, df) for "student_t"."""
+    for "poisson_exp", (scale, df) for "student_t", (epsilon,) for "multiclass_robustmax"."""
     if lik not in LIKELIHOOD_CODES:
         raise ValueError(f"unknown likelihood {lik!r}: one of {sorted(LIKELIHOOD_CODES)}")
     params = [float(v) for v in params]
-    if len(params) != {"bernoulli_probit": 0, "poisson_exp": 1, "student_t": 2}[lik]:
+    if len(params) != _LIKELIHOOD_NPAR[lik]:
         raise ValueError(f"likelihood {lik!r}: wrong number of parameters ({len(params)})")
     return LIKELIHOOD_CODES[lik], (_lib.host_doubles(params) if params else None)
+
+
+def _lik_y_columns(lik: str, P: int) -> int:
+    """how many columns of Y the likelihood reads: P, or one label column for a ROW_LIKELIHOODS member (which needs P >= 2 classes)"""
+    if lik not in ROW_LIKELIHOODS:
+        return P
+    if P < 2:
+        raise ValueError(f"likelihood {lik!r} needs at least two classes (P = {P})")
+    return 1
 
 
 def gauss_hermite(n: int = 20) -> Tuple[np.ndarray, np.ndarray]:
@@ -482,15 +493,16 @@ def likelihood_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[
     """Gauss-Hermite variational expectations of a non-Gaussian scalar likelihood (gpk_likelihood_varexp_sum), fvar = knn - s0 + ssq.
     Returns (out [2], rows | None, dmu | None, dvar | None, fvar | None): out[0] = sum over rows and outputs, out[1] = its
     derivative w.r.t. the StudentT scale (0 otherwise); rows [rows] = sums over the outputs; dmu, dvar [rows, P] = d/dfmean,
-    d/dfvar of every term."""
+    d/dfvar of every term.  "multiclass_robustmax" (params = (epsilon,)): Y is ONE column of class labels, the P >= 2 latents of a
+    row are its classes, rows [rows] is the row's value and dmu, dvar its derivatives w.r.t. all P means and variances."""
     lib = _lib.load()
     _chk(Y, "Y", 2)
     _chk(fmean, "fmean", 2)
     rows, P = fmean.shape
     if not fmean.is_contiguous():
         raise ValueError("fmean must be contiguous")
-    if Y.shape[0] != rows or Y.shape[1] < P:
-        raise ValueError("Y must have one row per row of fmean and at least P columns")
+    if Y.shape[0] != rows or Y.shape[1] < _lik_y_columns(lik, P):
+        raise ValueError("Y must have one row per row of fmean and at least P columns (one label column for 'multiclass_robustmax')")
     for name, t, shape in (("s0", s0, (P, rows) if s0_per_latent else (rows,)), ("ssq", ssq, (P, rows))):
         if t is not None:
             _chk(t, name)
@@ -837,7 +849,8 @@ def svgp_elbo_shard_lik(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_m
                         out: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None,
                         whiten: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """svgp_elbo_shard with a non-Gaussian likelihood (lik, params as likelihood_varexp_sum) in place of the noise variance:
-    out[0] = sum_b of the quadrature variational expectations over this shard, out[1] = KL.  Same forms, same workspace."""
+    out[0] = sum_b of the quadrature variational expectations over this shard, out[1] = KL.  Same forms, same workspace.
+    "multiclass_robustmax": Yb is ONE column of labels."""
     lib = _lib.load()
     for name, t in (("Z", Z), ("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)):
         _chk(t, name, 2)
@@ -846,7 +859,7 @@ def svgp_elbo_shard_lik(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_m
     rows = Xb.shape[0]
     P = q_mu.shape[1]
     q_diag = q_sqrt.dim() == 2
-    if Xb.shape[1] != d or Yb.shape[0] != rows or Yb.shape[1] != P or q_mu.shape[0] != m:
+    if Xb.shape[1] != d or Yb.shape[0] != rows or Yb.shape[1] != _lik_y_columns(lik, P) or q_mu.shape[0] != m:
         raise ValueError("inconsistent shapes")
     if not (q_mu.is_contiguous() and q_sqrt.is_contiguous()):
         raise ValueError("q_mu / q_sqrt must be contiguous")

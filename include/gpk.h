@@ -261,10 +261,31 @@ int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, const doubl
  * An unknown code returns GPK_E_UNSUPPORTED, a missing or non-positive parameter GPK_E_ARG.  fvar is not clamped: a negative
  * value gives NaN through the square root, as in the reference.  NaN / Inf in Y, fmean or fvar reach out and the element's
  * own rows_out / dmu_out / dvar_out entries (a non-finite label adds y - y to each of them), and nothing else.
- * Deterministic: four lanes share an element and combine in a fixed shuffle order, then the two-stage reduction. */
+ * Deterministic: four lanes share an element and combine in a fixed shuffle order, then the two-stage reduction.
+ *
+ *   GPK_LIK_MULTICLASS_ROBUSTMAX  params = {epsilon}: MultiClass with the RobustMax link (likelihoods/multiclass.py).  NOT a scalar
+ *   likelihood: the P latents of a row are the P classes, coupled under one quadrature sum.  With y the row's label,
+ *     s = sqrt(max(2 fvar_y, 1e-10)),  X_h = mu_y + s x_h,  d_kh = (X_h - mu_k) / sqrt(max(fvar_k, 1e-10)),
+ *     c_kh = 0.5 erfc(-d_kh / sqrt 2) (1 - 2e-4) + 1e-4,  p = sum_h (w_h / sqrt pi) prod_{k != y} c_kh   (k ascending)
+ *     VE_b = p log(1 - epsilon) + (1 - p) log(epsilon / (P - 1))
+ *   Classes: 2 <= P <= 16; P = 1 is GPK_E_ARG.  Epsilon: 0 < epsilon < 1, else (or NULL) GPK_E_ARG.
+ *   Labels: Y has ONE column: the label of row b is Y[b * ldy] for every latent; ldy >= 1 is all that is required.  A label that
+ *   is not an integer in [0, P) -- NaN and +-Inf included -- makes the row's outputs NaN (rows_out[b], all P entries of dmu_out /
+ *   dvar_out, its term of out[0]) and affects nothing else.  This is a choice: the reference would index garbage there.
+ *   Outputs: out[0] = sum_b VE_b (a row counts once, not once per latent); out[1] = 0; rows_out[b] = VE_b; dmu_out, dvar_out
+ *   [rows,P] = the exact derivatives of VE_b w.r.t. all P means and variances of the row; fvar_out[b,k] = the UNCLAMPED
+ *   knn - s0 + ssq.  The optional operands and outputs and rows = 0 behave as for the other codes.
+ *   Clamps: unlike the scalar likelihoods a negative (or tiny) fvar is clamped here and does not become NaN -- the reference's
+ *   behaviour for this likelihood.  The clamps are comparisons: a NaN variance stays NaN.  Where a clamp is active the
+ *   derivative w.r.t. that variance is exactly 0 (tf.clip_by_value under autodiff).
+ *   Non-finite inputs: a NaN in fmean[b,:] or fvar[b,:] reaches row b's outputs and out[0], and no other row: the row is the
+ *   unit here, not the element.
+ *   Deterministic: four lanes per (row, class) group, the product over the row's classes and the sums over them are fixed-order
+ *   shuffle loops inside one wave, then the two-stage reduction; no floating-point atomics. */
 #define GPK_LIK_BERNOULLI_PROBIT 1
 #define GPK_LIK_POISSON_EXP 2
 #define GPK_LIK_STUDENT_T 3
+#define GPK_LIK_MULTICLASS_ROBUSTMAX 4
 int gpk_likelihood_varexp_sum(void* stream, int lik, const double* lik_params_host, const double* Y, long ldy,
                               const double* fmean, int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
                               const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
@@ -359,7 +380,7 @@ int gpk_svgp_elbo_shard(void* stream, int family, const double* Z, int m, long l
 /* gpk_svgp_elbo_shard with a non-Gaussian likelihood: (lik, lik_params_host) as in gpk_likelihood_varexp_sum take the place
  * of (noise_variance, noise_rows); out[0] is then the sum of the quadrature variational expectations.  Every form of the shard
  * (whitened or not, full or diagonal q_sqrt), its schedule and its workspace (gpk_svgp_elbo_workspace_bytes) are the same:
- * only the last stage differs. */
+ * only the last stage differs.  GPK_LIK_MULTICLASS_ROBUSTMAX: Yb has ONE column (the labels), P >= 2 is the number of classes. */
 int gpk_svgp_elbo_shard_lik(void* stream, int family, const double* Z, int m, long ldz, const double* Xb, const double* Yb,
                             int rows, long ldxb, long ldyb, int d, int P, const double* ls_host, int ard, double variance,
                             int lik, const double* lik_params_host, double jitter, double mean_const, const double* q_mu,
