@@ -77,11 +77,6 @@ struct Carver {
     return p;
   }
 };
-
-// one-term final reduction:  *out = scale * sum(part[0:count]) + add
-int final_one(hipStream_t s, const double* part, int count, double scale, double add, double* out) {
-  return gpk_launch_final(s, 1, &part, &count, &scale, add, out);
-}
 }  // namespace
 
 // ---- fused driver: GPR.log_marginal_likelihood ----------------------------------------------------------
@@ -179,7 +174,7 @@ struct ElboWs {
   double *invd, *s0, *fmean, *ssq;
   double* proj;   // projection partials (full q_sqrt), or -- un-whitened with a diagonal q_sqrt -- the second solve A^T Lm^-1 [rows, ld]
   double *part0, *part1;
-  double* part2;  // [MAXPART] partials, then up to P + 1 single terms of the un-whitened KL
+  double* part2;  // [GPK_REDUCE_MAXPART] partials, then up to P + 1 single terms of the un-whitened KL
   double* V;      // [m, P]
   size_t total;
 };
@@ -266,22 +261,15 @@ int transpose_q_sqrt(hipStream_t s, const ElboArgs& a, const ElboWs& w) {
 // sums the slots, forms the expectations and reduces them (gpk_launch_varexp_tail)
 int varexp_to_out(hipStream_t s, const ElboArgs& a, const ElboWs& w, const double* knn_host, int per_latent,
                   const double* slot = nullptr, int nt = 0, int* ticket = nullptr) {
+  const LatentMoments mo = gpk_latent_moments(a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, per_latent, w.ssq, knn_host, per_latent,
+                                              a.mean_const, nullptr);
   if (slot && !a.lik)
-    return gpk_launch_varexp_tail(s, a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, slot, nt, (long)nt * a.rows, knn_host[0],
-                                  a.noise_variance, a.mean_const, a.noise_rows, w.part0, ticket, a.out);
-  if (slot) {   // the quadrature likelihoods keep their launches
-    const int rc = gpk_launch_sum_parts(s, slot, nt, a.rows, (long)nt * a.rows, a.P, w.ssq);
-    if (rc) return rc;
-  }
+    return gpk_launch_varexp_tail(s, mo, slot, nt, (long)nt * a.rows, a.noise_variance, a.noise_rows, w.part0, ticket, a.out);
+  if (slot) GPK_TRY(gpk_launch_sum_parts(s, slot, nt, a.rows, (long)nt * a.rows, a.P, w.ssq));   // the quadrature likelihoods keep their launches
   int count = 0;
-  const int rc = a.lik
-      ? gpk_launch_likelihood_varexp_stage1(s, a.lik, a.lik_params, a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, per_latent, w.ssq,
-                                            knn_host, per_latent, a.mean_const, nullptr, nullptr, nullptr, nullptr, w.part0, nullptr,
-                                            &count)
-      : gpk_launch_varexp_stage1(s, a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, per_latent, w.ssq, knn_host, per_latent,
-                                 a.noise_variance, a.mean_const, nullptr, w.part0, &count, a.noise_rows);
-  if (rc) return rc;
-  return final_one(s, w.part0, count, 1.0, 0.0, a.out);
+  GPK_TRY(a.lik ? gpk_launch_likelihood_varexp_stage1(s, a.lik, a.lik_params, mo, nullptr, nullptr, nullptr, w.part0, nullptr, &count)
+                : gpk_launch_varexp_stage1(s, mo, a.noise_variance, a.noise_rows, w.part0, &count));
+  return gpk_launch_final_one(s, w.part0, count, 1.0, 0.0, a.out);
 }
 // KL[q || N(0, I)] -> out[1]  (kullback_leiblers.py:45-46, 98-165)
 // Its first kernel also zeroes the ticket of the shard's one-launch tail (tail_ticket): every whitened shard runs it before that
@@ -291,7 +279,7 @@ int kl_white_to_out(hipStream_t s, const ElboArgs& a, const ElboWs& w) {
   int count = 0;
   const int rc = gpk_launch_kl_white_stage1(s, a.q_mu, a.q_sqrt, a.m, a.P, a.q_diag, w.part1, &count, w.part2 ? tail_ticket(w) : nullptr);
   if (rc) return rc;
-  return final_one(s, w.part1, count, 0.5, -0.5 * (double)a.m * (double)a.P, a.out + 1);
+  return gpk_launch_final_one(s, w.part1, count, 0.5, -0.5 * (double)a.m * (double)a.P, a.out + 1);
 }
 // the late_work of the whitened forms (side_schedule), on whichever stream issues it
 int transpose_q_sqrt_and_kl(hipStream_t s, const ElboArgs& a, const ElboWs& w) {

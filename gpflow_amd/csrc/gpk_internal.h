@@ -87,44 +87,51 @@ int gpk_potrf_core(hipStream_t S, double* A, int n, int extra, long lda, int bat
 // ---- rbf.hip ---------------------------------------------------------------------------------
 // (entry point gpk_kernel_matrix is defined there)
 
-// ---- reduce.hip: small kernels -------------------------------------------------------------------
+#define GPK_REDUCE_MAXPART 1024   // most stage-1 blocks (partials) of a two-stage reduction
+
+// ---- rowops.hip: layout and row passes ---------------------------------------------------------------
 int gpk_launch_zero_upper(hipStream_t s, double* A, int n, long lda, int batch, long strideA);
 int gpk_launch_set_identity(hipStream_t s, double* A, int n, long lda, int batch = 1, long strideA = 0);
-int gpk_probe_concurrent_kernels(hipStream_t a, hipStream_t b, int* scratch, int* concurrent);   // init-time probe (reduce.hip)
+int gpk_launch_row_stats_sep(hipStream_t s, const double* At, long strideAt, int rows, int m, long ldat, const double* V, int P,
+                             double* sumsq, double* mv);
+int gpk_launch_transpose_shift(hipStream_t s, const double* in, int rows, int cols, long ldin, double* out, long ldout, double shift);
+
+// ---- sync.hip: stream hand-offs ----------------------------------------------------------------------
+int gpk_probe_concurrent_kernels(hipStream_t a, hipStream_t b, int* scratch, int* concurrent);   // init-time probe
 int gpk_launch_noop(hipStream_t s);  // empty kernel (stream hand-off probe)
 int gpk_launch_wait_flag(hipStream_t s, const int* ptr, int val, int* info);   // one-wave gate: returns when (int)(*ptr - val) >= 0 (bounded)
 int gpk_launch_set_flag(hipStream_t s, int* ptr, int val);                     // one-thread store behind everything queued on s
-int gpk_launch_sum_parts(hipStream_t s, const double* part, int nt, int rows, long stridePart, int P,
-                         double* ssq);
-int gpk_launch_final(hipStream_t s, int nterms, const double* const* part, const int* count,
-                     const double* scale, double add, double* out);
-int gpk_launch_sumsq_stage1(hipStream_t s, const double* A, int rows, int cols, long lda,
-                            int upper_only, double* part, int* count);
-int gpk_launch_varexp_stage1(hipStream_t s, const double* Y, long ldy, const double* fmean, int rows,
-                             int P, const double* s0, int s0_per_latent, const double* ssq,
-                             const double* knn_host, int knn_per_latent, double noise,
-                             double mean_const, double* fvar_out, double* part, int* count,
-                             const double* noise_rows = nullptr);   // per-row noise variances [rows] or nullptr (constant `noise`)
-// the quadrature stage of gpk_likelihood_varexp_sum (same operands); part1 (partials of sum dVE/dscale) may be null
-int gpk_likelihood_check(int lik, const double* params, int P);   // 0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters, classes)
-int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const double* Y, long ldy, const double* fmean,
-                                        int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
-                                        const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
-                                        double* rows_out, double* dmu_out, double* dvar_out, double* part, double* part1, int* count);
-// the Gaussian tail of a shard in ONE launch: ssq[p,b] = sum of the nt slot partials slot[p][t][b] in slot order, the variational
-// expectations exactly as gpk_launch_varexp_stage1 forms them, one partial per block, and the LAST block to finish (ticket counter)
-// sums the partials in index order into out[0].  *ticket must be 0 at entry and is left at the block count.
-int gpk_launch_varexp_tail(hipStream_t s, const double* Y, long ldy, const double* fmean, int rows, int P, const double* s0,
-                           const double* slot, int nt, long strideSlot, double knn, double noise, double mean_const,
-                           const double* noise_rows, double* part, int* ticket, double* out);
+
+// ---- reduce.hip: two-stage reductions (stage 1 leaves `count` partials in `part`) and sums of split-K partials ----
+int gpk_launch_sum_parts(hipStream_t s, const double* part, int nt, int rows, long stridePart, int P, double* ssq);
+int gpk_launch_final(hipStream_t s, int nterms, const double* const* part, const int* count, const double* scale, double add, double* out);
+int gpk_launch_final_one(hipStream_t s, const double* part, int count, double scale, double add, double* out);   // the one-term form
+int gpk_launch_sumsq_stage1(hipStream_t s, const double* A, int rows, int cols, long lda, int upper_only, double* part, int* count);
 // zero_word (may be null): an int the kernel sets to 0 -- the ticket of a gpk_launch_varexp_tail that is stream-ordered behind it
-int gpk_launch_kl_white_stage1(hipStream_t s, const double* q_mu, const double* q_sqrt, int m, int P,
-                               int q_diag, double* part, int* count, int* zero_word = nullptr);
+int gpk_launch_kl_white_stage1(hipStream_t s, const double* q_mu, const double* q_sqrt, int m, int P, int q_diag, double* part, int* count,
+                               int* zero_word = nullptr);
 int gpk_launch_kl_unwhite_diag_stage1(hipStream_t s, const double* LinvT, long ldl, int m, const double* W, int P, double* part,
                                       int* count);
 int gpk_launch_sum_log_diag_sq(hipStream_t s, const double* L, int n, long ldl, int batch, long strideL, double* out);
-int gpk_launch_row_stats_sep(hipStream_t s, const double* At, long strideAt, int rows, int m, long ldat, const double* V, int P,
-                             double* sumsq, double* mv);
-int gpk_launch_transpose_shift(hipStream_t s, const double* in, int rows, int cols, long ldin,
-                               double* out, long ldout, double shift);
-#define GPK_REDUCE_MAXPART 1024
+
+// ---- varexp.hip: the variational-expectation stages ---------------------------------------------------
+// What every stage reads of element (b, p): label Y[b, p], mean fmean[b, p] + mean_const, variance knn - s0 + ssq (s0 [rows] or
+// [P, rows], ssq [P, rows] or null, knn one value or one per latent: copied from knn_host); fvar_out (may be null) receives the variance.
+struct LatentMoments {
+  const double* Y; long ldy; const double* fmean; int rows, P;
+  const double* s0; int s0_per_latent; const double* ssq;
+  double knn[16]; int knn_per_latent; double mean_const; double* fvar_out;
+};
+LatentMoments gpk_latent_moments(const double* Y, long ldy, const double* fmean, int rows, int P, const double* s0, int s0_per_latent,
+                                 const double* ssq, const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out);
+// Gaussian; noise_rows: per-row noise variances [rows] or nullptr (constant `noise`)
+int gpk_launch_varexp_stage1(hipStream_t s, const LatentMoments& m, double noise, const double* noise_rows, double* part, int* count);
+// the Gaussian tail of a shard in ONE launch: ssq[p,b] = sum of the nt slot partials slot[p][t][b] in slot order (m.ssq is not read),
+// the variational expectations exactly as gpk_launch_varexp_stage1 forms them, one partial per block, and the LAST block to finish
+// (ticket counter) sums the partials in index order into out[0].  *ticket must be 0 at entry and is left at the block count.
+int gpk_launch_varexp_tail(hipStream_t s, const LatentMoments& m, const double* slot, int nt, long strideSlot, double noise,
+                           const double* noise_rows, double* part, int* ticket, double* out);
+// the quadrature stage of gpk_likelihood_varexp_sum; part1 (partials of sum dVE/dscale) may be null
+int gpk_likelihood_check(int lik, const double* params, int P);   // 0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters, classes)
+int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const LatentMoments& m, double* rows_out,
+                                        double* dmu_out, double* dvar_out, double* part, double* part1, int* count);

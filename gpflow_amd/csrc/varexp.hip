@@ -1,0 +1,430 @@
+// The variational-expectation stage of an ELBO shard: Gaussian in closed form (varexp_kernel), scalar likelihoods by Gauss-Hermite
+// quadrature (lik_varexp_kernel), MultiClass / RobustMax (lik_multiclass_kernel).  Stage 1 of the two-stage reductions of reduce.hip.
+#include "reduce_device.h"
+
+namespace {
+
+// fvar[b,p] = knn - s0 + ssq, in this order and each step a statement of its own: with -ffp-contract=on the bits depend on it.
+// slot_sum (varexp_kernel<true>): the last term, already summed from the slot partials in slot order, in place of m.ssq.
+__device__ __forceinline__ double latent_var(const LatentMoments& m, long b, int p, const double* slot_sum = nullptr) {
+  double fv = m.knn[m.knn_per_latent ? p : 0];
+  if (m.s0) fv -= m.s0_per_latent ? m.s0[(long)p * m.rows + b] : m.s0[b];
+  if (slot_sum) fv += *slot_sum;
+  else if (m.ssq) fv += m.ssq[(long)p * m.rows + b];
+  return fv;
+}
+
+// ---- Gaussian variational expectations, stage 1 -----------------------------------------------------
+struct VarexpArgs {
+  LatentMoments m;
+  double noise; double* part;
+  const double* noise_rows;   // per-row noise variances [rows] (heteroskedastic Gaussian, scalar_continuous.py:92-111) or nullptr
+  // TAIL only: ssq arrives as nt slot partials [P][nt][rows] (strideSlot between latents); ticket / out: see varexp_kernel
+  const double* slot; int nt; long strideSlot; int* ticket; double* out;
+};
+// TAIL = false: stage 1 of the two-stage reduction (one partial per block).
+// TAIL = true: the whole tail of a shard behind the projection GEMM in one launch -- what sum_parts_kernel, this kernel and
+// final_sum_kernel did as three dependent launches of 5 - 10 us each.  The slot partials of an element are summed in slot order
+// (sum_parts_kernel's bits), their loads issued sixteen at a time: one element per thread with a load per add was 38 us for
+// 8192 x 32 partials on eight blocks.  So the grid is one element per thread here (gpk_launch_varexp_tail), not four.  The block
+// that draws the last ticket sums the block partials in index order, as final_sum_kernel does.  The ticket word must be 0 at entry: no memset packet, and not a
+// reset by the last block either (the first call on a fresh workspace has to be right) -- kl_white_kernel, which every whitened
+// shard runs earlier in the same step on a stream that is joined before this launch, zeroes it (drivers.hip: kl_white_to_out).
+template <bool TAIL>
+__global__ __launch_bounds__(RB) void varexp_kernel(VarexpArgs a) {
+  __shared__ double sh[4];
+  __shared__ int s_last;
+  const double log2pi = 1.8378770664093453;
+  const double c0 = -0.5 * log2pi - 0.5 * log(a.noise);
+  double acc = 0.0;
+  const LatentMoments& m = a.m;
+  const long total = (long)m.rows * m.P;
+  for (long e = (long)blockIdx.x * RB + threadIdx.x; e < total; e += (long)gridDim.x * RB) {
+    const int b = (int)(e / m.P), p = (int)(e - (long)b * m.P);
+    double fv;
+    if constexpr (TAIL) {
+      const double* q = a.slot + (long)p * a.strideSlot + b;
+      double s = 0.0;
+      int t = 0;
+      for (; t + 16 <= a.nt; t += 16) {
+        double v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = q[(long)(t + i) * m.rows];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s += v[i];
+      }
+      for (; t < a.nt; ++t) s += q[(long)t * m.rows];
+      fv = latent_var(m, b, p, &s);
+    } else fv = latent_var(m, b, p);
+    const double mu = m.fmean[e] + m.mean_const;
+    const double dy = m.Y[(long)b * m.ldy + p] - mu;
+    if (m.fvar_out) m.fvar_out[e] = fv;
+    if (a.noise_rows) {   // (workgroup-uniform branch)
+      const double nv = a.noise_rows[b];
+      acc += (-0.5 * log2pi - 0.5 * log(nv)) - 0.5 * (dy * dy + fv) / nv;
+    } else {
+      acc += c0 - 0.5 * (dy * dy + fv) / a.noise;
+    }
+  }
+  const double r = block_sum(acc, sh);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = r;
+  if constexpr (TAIL) {
+    if (threadIdx.x == 0) {
+      __threadfence();   // the partial is visible device-wide before the ticket is
+      s_last = atomicAdd(a.ticket, 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();     // every other block's partial was released before its ticket
+    double v = 0.0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += RB) v += __hip_atomic_load(a.part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double t = block_sum(v, sh);
+    if (threadIdx.x == 0) *a.out = 0.0 + 1.0 * t;   // (final_sum_kernel's add + scale * sum)
+  }
+}
+
+// ---- non-Gaussian variational expectations, stage 1 (likelihoods/base.py: ScalarLikelihood through NDiagGHQuadrature,
+// quadrature/gauss_hermite.py; scalar_discrete.py Bernoulli / Poisson; scalar_continuous.py StudentT) -----------------------
+//   VE[b,p] = sum_h (w_h / sqrt(pi)) g(mu + sqrt(2 v) x_h),  g = log p(y | f),  with d/dmu and d/dv of that same sum.
+// numpy.polynomial.hermite.hermgauss(20), the reference's DEFAULT_NUM_GAUSS_HERMITE_POINTS (gpk_gauss_hermite returns this table)
+#define GPK_GH20_X                                                                                                          \
+  -5.387480890011233, -4.603682449550744, -3.944764040115625, -3.3478545673832163, -2.7888060584281305, -2.2549740020892757, \
+      -1.7385377121165861, -1.234076215395323, -0.7374737285453944, -0.24534070830090124, 0.24534070830090124,              \
+      0.7374737285453944, 1.234076215395323, 1.7385377121165861, 2.2549740020892757, 2.7888060584281305, 3.3478545673832163, \
+      3.944764040115625, 4.603682449550744, 5.387480890011233
+#define GPK_GH20_W                                                                                                          \
+  2.2293936455341447e-13, 4.3993409922731747e-10, 1.0860693707692782e-07, 7.80255647853206e-06, 0.00022833863601635365,     \
+      0.0032437733422378567, 0.024810520887463643, 0.1090172060200233, 0.28667550536283415, 0.4622436696006101,              \
+      0.4622436696006101, 0.28667550536283415, 0.1090172060200233, 0.024810520887463643, 0.0032437733422378567,              \
+      0.00022833863601635365, 7.80255647853206e-06, 1.0860693707692782e-07, 4.3993409922731747e-10, 2.2293936455341447e-13
+constexpr int GH_N = 20;
+__constant__ const double gh_x_dev[GH_N] = {GPK_GH20_X};
+__constant__ const double gh_w_dev[GH_N] = {GPK_GH20_W};
+const double gh_x_host[GH_N] = {GPK_GH20_X};
+const double gh_w_host[GH_N] = {GPK_GH20_W};
+
+struct LikVarexpArgs {
+  LatentMoments m;
+  double par0, par1, c0;   // Poisson: binsize, -, log(binsize);  StudentT: scale, df, the f-independent part of log p;
+                           // MultiClass: log(1 - eps), log(eps / (C - 1)), their difference
+  double *rows_out, *dmu_out, *dvar_out;
+  double *part, *part1;    // stage-1 partials of sum VE and (part1 may be null) of sum dVE/dscale
+};
+
+// One element (b, p) is shared by LPE = 4 adjacent lanes, five nodes each (8192 x P elements with a serial 20-node loop of fp64
+// erfc + log + exp per thread would leave most of the chip idle); the four partial sums meet through two xor shuffles, so all
+// four lanes hold the same bits.  The closed-form Poisson branch has no nodes: one lane per element.  A wave pass covers
+// floor((64 / LPE) / P) WHOLE rows, so that the row sums of rows_out are a fixed-order shuffle loop inside one wave.
+// This layout is written down once, for both kernels and for the launcher's grid:
+__host__ __device__ constexpr int quad_lpe(int lik) { return lik == GPK_LIK_POISSON_EXP ? 1 : 4; }   // lanes per element
+__host__ __device__ constexpr int quad_rows_per_pass(int lpe, int P) { return (64 / lpe) / P; }      // (P <= 16 <= 64 / lpe)
+template <int LPE>
+struct QuadLanes {
+  int k, p;        // this lane's node quarter and latent
+  int jr, rpw;     // its group's row within a pass, whole rows per pass
+  int row_lane0;   // lane of the row's first group
+  long npass;
+  __device__ explicit QuadLanes(const LatentMoments& m) {
+    const int lane = threadIdx.x & 63, g = lane / LPE;
+    k = lane % LPE; rpw = quad_rows_per_pass(LPE, m.P);
+    jr = g / m.P; p = g - jr * m.P;
+    row_lane0 = (jr * m.P * LPE) & 63;
+    npass = ((long)m.rows + rpw - 1) / rpw;
+  }
+  // row b, label (column ycol of Y), mean and variance of this lane's element in pass u; false: an idle lane, which runs on
+  // harmless values and is masked by the caller
+  __device__ bool load(const LatentMoments& m, long u, int ycol, long& b, double& y, double& mu, double& fv) const {
+    b = u * rpw + jr;
+    const bool act = jr < rpw && b < m.rows;
+    y = 0.0; mu = 0.0; fv = 1.0;
+    if (act) {
+      fv = latent_var(m, b, p);
+      mu = m.fmean[b * m.P + p] + m.mean_const;
+      y = m.Y[b * m.ldy + ycol];
+    }
+    return act;
+  }
+};
+
+// Non-finite inputs: NaN / Inf in fmean or fvar travel through the arithmetic; a non-finite label adds y - y = NaN to every output
+// of its element (the comparison y == 1 of the Bernoulli density would otherwise read a NaN label as class 0).
+template <int LIK>
+__global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
+  constexpr int LPE = quad_lpe(LIK);
+  constexpr int NPL = GH_N / 4;      // nodes per lane (quadrature branches)
+  __shared__ double sh[4];
+  const LatentMoments& m = a.m;
+  const QuadLanes<LPE> L(m);
+  const int w = threadIdx.x >> 6, k = L.k, p = L.p;
+  double acc = 0.0, acc1 = 0.0;
+  for (long u = (long)blockIdx.x * (RB / 64) + w; u < L.npass; u += (long)gridDim.x * (RB / 64)) {
+    long b; double y, mu, fv;
+    const bool act = L.load(m, u, p, b, y, mu, fv);
+    const double ynan = y - y;
+    double ve, dmu, dvar, dsc = 0.0;
+    if (LIK == GPK_LIK_POISSON_EXP) {
+      // scalar_discrete.py: Poisson.variational_expectations with the exp link, closed form
+      const double e = exp(mu + 0.5 * fv) * a.par0;
+      ve = y * mu - e - lgamma(y + 1.0) + y * a.c0;
+      dmu = y - e;
+      dvar = -0.5 * e;
+    } else {
+      const double sd = sqrt(2.0 * fv);
+      const double sgn = (y == 1.0) ? 1.0 : -1.0;
+      double sv = 0.0, sm = 0.0, sx = 0.0, ss = 0.0;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) {
+        const double x = gh_x_dev[k * NPL + j];
+        const double wn = gh_w_dev[k * NPL + j] * 0.5641895835477563;   // w_h / sqrt(pi)
+        const double f = fma(sd, x, mu);
+        double gv, gp;
+        if (LIK == GPK_LIK_BERNOULLI_PROBIT) {
+          // log(y == 1 ? p : 1 - p), p = inv_probit(f) = 0.5 (1 + erf(f / sqrt 2)) (1 - 2e-3) + 1e-3;  1 - p = inv_probit(-f), taken
+          // through erfc so that the small side keeps its relative accuracy
+          const double q = 0.5 * erfc(-sgn * f * 0.7071067811865476) * (1.0 - 2e-3) + 1e-3;
+          gv = log(q);
+          gp = sgn * ((1.0 - 2e-3) * 0.3989422804014327) * exp(-0.5 * f * f) / q;
+        } else {
+          // logdensities.py student_t:  c0 - (df + 1) / 2 log(1 + ((y - f) / scale)^2 / df)
+          const double r = (y - f) / a.par0;
+          const double den = a.par1 + r * r;
+          gv = a.c0 - 0.5 * (a.par1 + 1.0) * log1p(r * r / a.par1);
+          gp = (a.par1 + 1.0) * r / (a.par0 * den);
+          ss += wn * (((a.par1 + 1.0) * r * r / den - 1.0) / a.par0);
+        }
+        sv += wn * gv;
+        sm += wn * gp;
+        sx += wn * gp * x;
+      }
+      sv += __shfl_xor(sv, 1); sm += __shfl_xor(sm, 1); sx += __shfl_xor(sx, 1); ss += __shfl_xor(ss, 1);
+      sv += __shfl_xor(sv, 2); sm += __shfl_xor(sm, 2); sx += __shfl_xor(sx, 2); ss += __shfl_xor(ss, 2);
+      ve = sv;
+      dmu = sm;
+      dvar = sx / sd;
+      dsc = ss;
+    }
+    ve += ynan; dmu += ynan; dvar += ynan;
+    double rs = 0.0;   // the row's P elements sit in adjacent groups of this wave: summed in the order p = 0, 1, ...
+    for (int q = 0; q < m.P; ++q) rs += __shfl(ve, (L.row_lane0 + q * LPE) & 63);
+    if (act && k == 0) {
+      const long e = b * m.P + p;
+      if (m.fvar_out) m.fvar_out[e] = fv;
+      if (a.dmu_out) a.dmu_out[e] = dmu;
+      if (a.dvar_out) a.dvar_out[e] = dvar;
+      if (a.rows_out && p == 0) a.rows_out[b] = rs;
+      acc += ve;
+      acc1 += dsc;
+    }
+  }
+  const double r0 = block_sum(acc, sh);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = r0;
+  if (a.part1) {   // (kernel argument: uniform)
+    const double r1 = block_sum(acc1, sh);
+    if (threadIdx.x == 0) a.part1[blockIdx.x] = r1;
+  }
+}
+
+// ---- MultiClass / RobustMax variational expectations, stage 1 (likelihoods/multiclass.py: MultiClass._variational_expectations,
+// RobustMax.prob_is_largest) ------------------------------------------------------------------------------------------------
+//   y = Y[b, 0] (ONE label column),  s = sqrt(max(2 v_y, 1e-10)),  X_h = mu_y + s x_h,  d_kh = (X_h - mu_k) / sqrt(max(v_k, 1e-10)),
+//   c_kh = Phi(d_kh) (1 - 2e-4) + 1e-4,  Pi_h = prod_{k != y} c_kh,  p = sum_h (w_h / sqrt pi) Pi_h,
+//   VE_b = p log(1 - eps) + (1 - p) log(eps / (C - 1)),  and the exact derivatives of that sum w.r.t. all C means and variances.
+// The lane layout of lik_varexp_kernel carries over -- four adjacent lanes per (row, latent) group, five nodes each, floor(16 / P)
+// whole rows per wave pass -- but the P groups of a row are coupled: group k evaluates c_kh and t_kh = (1 - 2e-4) phi(d_kh) /
+// (sqrt(v_k) c_kh) at its nodes (group y: c = 1, t = 0), the product over the row's groups is a fixed-order shuffle loop (k = 0, 1,
+// ...), and each group then forms its own sums  a1 = sum_h w Pi t,  a2 = sum_h w Pi t d,  a3 = sum_h w Pi t x:
+//   dVE/dmu_k = -kappa a1,  dVE/dv_k = -kappa a2 / (2 sqrt v_k)   (k != y);   kappa = log(1 - eps) - log(eps / (C - 1))
+//   dVE/dmu_y = kappa sum_k a1_k,  dVE/dv_y = kappa sum_k a3_k / s   (the sums over h and k of the definition, k outermost)
+// The clamps are comparisons, so a NaN variance stays NaN; where one is active the derivative w.r.t. that variance is exactly 0
+// (tf.clip_by_value under autodiff).  A label that is no integer in [0, P) adds NaN to every output of its row.
+// par0 = log(1 - eps), par1 = log(eps / (C - 1)), c0 = kappa.
+__global__ __launch_bounds__(RB) void lik_multiclass_kernel(LikVarexpArgs a) {
+  constexpr int NPL = GH_N / 4;      // nodes per lane
+  __shared__ double sh[4];
+  const LatentMoments& m = a.m;
+  const QuadLanes<4> L(m);
+  const int w = threadIdx.x >> 6, k = L.k, p = L.p, row_lane0 = L.row_lane0;   // (p: the class)
+  double acc = 0.0;
+  for (long u = (long)blockIdx.x * (RB / 64) + w; u < L.npass; u += (long)gridDim.x * (RB / 64)) {
+    long b; double y, mu, fv;
+    const bool act = L.load(m, u, 0, b, y, mu, fv);
+    const bool lab_ok = y >= 0.0 && y < (double)m.P && y == floor(y);   // (false for NaN and +-Inf)
+    const int yi = lab_ok ? (int)y : 0;
+    const double ynan = lab_ok ? 0.0 : __builtin_nan("");
+    const bool isy = p == yi;
+    const int ylane = (row_lane0 + yi * 4) & 63;
+    const double mu_y = __shfl(mu, ylane), fv_y = __shfl(fv, ylane);
+    const double tv = 2.0 * fv_y;
+    const bool clamp_y = tv < 1e-10, clamp_k = fv < 1e-10;
+    const double s = sqrt(clamp_y ? 1e-10 : tv);
+    const double sdk = sqrt(clamp_k ? 1e-10 : fv);
+    double c[NPL], t[NPL], d[NPL], pi[NPL];
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      d[j] = (fma(s, gh_x_dev[k * NPL + j], mu_y) - mu) / sdk;
+      const double cc = 0.5 * erfc(-d[j] * 0.7071067811865476) * (1.0 - 2e-4) + 1e-4;
+      const double tt = ((1.0 - 2e-4) * 0.3989422804014327) * exp(-0.5 * d[j] * d[j]) / (sdk * cc);
+      c[j] = isy ? 1.0 : cc;
+      t[j] = isy ? 0.0 : tt;
+      pi[j] = 1.0;
+    }
+    for (int q = 0; q < m.P; ++q) {   // the row's P groups sit in adjacent groups of this wave: multiplied in the order k = 0, 1, ...
+      const int src = (row_lane0 + q * 4 + k) & 63;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) pi[j] *= __shfl(c[j], src);
+    }
+    double sp = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      const double wp = gh_w_dev[k * NPL + j] * 0.5641895835477563 * pi[j];   // (w_h / sqrt(pi)) Pi_h
+      const double wt = wp * t[j];
+      sp += wp;
+      a1 += wt;
+      a2 += wt * d[j];
+      a3 += wt * gh_x_dev[k * NPL + j];
+    }
+    sp += __shfl_xor(sp, 1); a1 += __shfl_xor(a1, 1); a2 += __shfl_xor(a2, 1); a3 += __shfl_xor(a3, 1);
+    sp += __shfl_xor(sp, 2); a1 += __shfl_xor(a1, 2); a2 += __shfl_xor(a2, 2); a3 += __shfl_xor(a3, 2);
+    double s1 = 0.0, s3 = 0.0;   // group y collects the others' sums in the order k = 0, 1, ... (its own are zeros)
+    for (int q = 0; q < m.P; ++q) {
+      const int src = (row_lane0 + q * 4) & 63;
+      s1 += __shfl(a1, src);
+      s3 += __shfl(a3, src);
+    }
+    const double ve = sp * a.par0 + (1.0 - sp) * a.par1 + ynan;   // (every lane of the row holds the same bits of sp)
+    const double dmu = (isy ? a.c0 * s1 : -a.c0 * a1) + ynan;
+    const double dvar = (isy ? (clamp_y ? 0.0 : a.c0 * s3 / s) : (clamp_k ? 0.0 : -a.c0 * a2 / (2.0 * sdk))) + ynan;
+    if (act && k == 0) {
+      const long e = b * m.P + p;
+      if (m.fvar_out) m.fvar_out[e] = fv;
+      if (a.dmu_out) a.dmu_out[e] = dmu;
+      if (a.dvar_out) a.dvar_out[e] = dvar;
+      if (p == 0) {   // one group per row
+        if (a.rows_out) a.rows_out[b] = ve;
+        acc += ve;
+      }
+    }
+  }
+  const double r0 = block_sum(acc, sh);
+  if (threadIdx.x == 0) {
+    a.part[blockIdx.x] = r0;
+    if (a.part1) a.part1[blockIdx.x] = 0.0;
+  }
+}
+
+}  // namespace
+
+LatentMoments gpk_latent_moments(const double* Y, long ldy, const double* fmean, int rows, int P, const double* s0, int s0_per_latent,
+                                 const double* ssq, const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out) {
+  LatentMoments m{Y, ldy, fmean, rows, P, s0, s0_per_latent, ssq, {}, knn_per_latent, mean_const, fvar_out};
+  for (int i = 0; i < (knn_per_latent ? P : 1); ++i) m.knn[i] = knn_host[i];
+  return m;
+}
+
+int gpk_launch_varexp_stage1(hipStream_t s, const LatentMoments& m, double noise, const double* noise_rows, double* part, int* count) {
+  VarexpArgs a{};
+  a.m = m; a.noise = noise; a.noise_rows = noise_rows; a.part = part;
+  const int nb = nblocks_for((long)m.rows * m.P);
+  hipLaunchKernelGGL(varexp_kernel<false>, dim3(nb), dim3(RB), 0, s, a);
+  GPK_LAUNCH_CHECK();
+  *count = nb;
+  return 0;
+}
+int gpk_launch_varexp_tail(hipStream_t s, const LatentMoments& m, const double* slot, int nt, long strideSlot, double noise,
+                           const double* noise_rows, double* part, int* ticket, double* out) {
+  if (!slot || !part || !ticket || !out || nt < 0) return GPK_E_ARG;
+  VarexpArgs a{};
+  a.m = m; a.noise = noise; a.noise_rows = noise_rows; a.part = part;
+  a.slot = slot; a.nt = nt; a.strideSlot = strideSlot; a.ticket = ticket; a.out = out;
+  long nb = ((long)m.rows * m.P + RB - 1) / RB;
+  nb = nb < 1 ? 1 : (nb > GPK_REDUCE_MAXPART ? GPK_REDUCE_MAXPART : nb);
+  hipLaunchKernelGGL(varexp_kernel<true>, dim3((unsigned)nb), dim3(RB), 0, s, a);
+  GPK_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, const double* fmean, int rows, int P, const double* s0,
+                                       int s0_per_latent, const double* ssq, const double* knn_host, int knn_per_latent,
+                                       double noise_variance, const double* noise_rows, double mean_const, double* fvar_out,
+                                       double* out, void* ws, size_t ws_bytes) {
+  if ((rows > 0 && (!Y || !fmean)) || !knn_host || !out || P <= 0 || P > 16 || rows < 0) return GPK_E_ARG;
+  if (!ws || ws_bytes < gpk_reduce_workspace_bytes(rows)) return GPK_E_WORKSPACE;
+  const LatentMoments m = gpk_latent_moments(Y, ldy, fmean, rows, P, s0, s0_per_latent, ssq, knn_host, knn_per_latent, mean_const, fvar_out);
+  int nb = 0;
+  GPK_TRY(gpk_launch_varexp_stage1((hipStream_t)stream, m, noise_variance, noise_rows, (double*)ws, &nb));
+  return gpk_launch_final_one((hipStream_t)stream, (double*)ws, nb, 1.0, 0.0, out);
+}
+
+extern "C" int gpk_gauss_hermite(int n, double* x_host, double* w_host) {
+  if (!x_host || !w_host) return GPK_E_ARG;
+  if (n != GH_N) return GPK_E_UNSUPPORTED;
+  for (int i = 0; i < GH_N; ++i) { x_host[i] = gh_x_host[i]; w_host[i] = gh_w_host[i]; }
+  return 0;
+}
+
+// The one host-side description of a likelihood code: which (params, P) it accepts, its kernel, and the three constants the kernel
+// reads.  0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters, classes).
+namespace {
+struct LikPlan { void (*kernel)(LikVarexpArgs); double par0, par1, c0; };
+int lik_plan(int lik, const double* q, int P, LikPlan* o) {
+  *o = LikPlan{};
+  switch (lik) {
+    case GPK_LIK_BERNOULLI_PROBIT: o->kernel = lik_varexp_kernel<GPK_LIK_BERNOULLI_PROBIT>; return 0;
+    case GPK_LIK_POISSON_EXP:   // params = {binsize}
+      if (!(q && q[0] > 0.0)) return GPK_E_ARG;
+      o->kernel = lik_varexp_kernel<GPK_LIK_POISSON_EXP>;
+      o->par0 = q[0]; o->c0 = log(q[0]);
+      return 0;
+    case GPK_LIK_STUDENT_T:   // params = {scale, df}
+      if (!(q && q[0] > 0.0 && q[1] > 0.0)) return GPK_E_ARG;
+      o->kernel = lik_varexp_kernel<GPK_LIK_STUDENT_T>;
+      o->par0 = q[0]; o->par1 = q[1];
+      o->c0 = lgamma(0.5 * (q[1] + 1.0)) - lgamma(0.5 * q[1]) - 0.5 * (log(q[0] * q[0]) + log(q[1]) + log(3.141592653589793));
+      return 0;
+    case GPK_LIK_MULTICLASS_ROBUSTMAX:   // params = {epsilon}; P is the number of classes
+      if (!(P >= 2 && P <= 16 && q && q[0] > 0.0 && q[0] < 1.0)) return GPK_E_ARG;
+      o->kernel = lik_multiclass_kernel;
+      o->par0 = log1p(-q[0]); o->par1 = log(q[0] / (double)(P - 1)); o->c0 = o->par0 - o->par1;
+      return 0;
+    default: return GPK_E_UNSUPPORTED;
+  }
+}
+}  // namespace
+int gpk_likelihood_check(int lik, const double* params, int P) {
+  LikPlan plan;
+  return lik_plan(lik, params, P, &plan);
+}
+
+int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const LatentMoments& m, double* rows_out,
+                                        double* dmu_out, double* dvar_out, double* part, double* part1, int* count) {
+  LikPlan plan;
+  GPK_TRY(lik_plan(lik, params, m.P, &plan));
+  LikVarexpArgs a{};
+  a.m = m; a.par0 = plan.par0; a.par1 = plan.par1; a.c0 = plan.c0;
+  a.rows_out = rows_out; a.dmu_out = dmu_out; a.dvar_out = dvar_out; a.part = part; a.part1 = part1;
+  const int per_wave = quad_rows_per_pass(quad_lpe(lik), m.P);   // (MultiClass: per row, not per element)
+  long nb = (((long)m.rows + per_wave - 1) / per_wave + RB / 64 - 1) / (RB / 64);
+  nb = nb < 1 ? 1 : (nb > GPK_REDUCE_MAXPART ? GPK_REDUCE_MAXPART : nb);
+  void* kargs[] = {&a};
+  (void)hipLaunchKernel((const void*)plan.kernel, dim3((unsigned)nb), dim3(RB), kargs, 0, s);   // (status: read and cleared below)
+  GPK_LAUNCH_CHECK();
+  *count = (int)nb;
+  return 0;
+}
+
+extern "C" int gpk_likelihood_varexp_sum(void* stream, int lik, const double* lik_params_host, const double* Y, long ldy,
+                                         const double* fmean, int rows, int P, const double* s0, int s0_per_latent,
+                                         const double* ssq, const double* knn_host, int knn_per_latent, double mean_const,
+                                         double* fvar_out, double* rows_out, double* dmu_out, double* dvar_out, double* out,
+                                         void* ws, size_t ws_bytes) {
+  if ((rows > 0 && (!Y || !fmean)) || !knn_host || !out || P <= 0 || P > 16 || rows < 0) return GPK_E_ARG;
+  if (!ws || ws_bytes < gpk_reduce_workspace_bytes(rows)) return GPK_E_WORKSPACE;
+  const LatentMoments m = gpk_latent_moments(Y, ldy, fmean, rows, P, s0, s0_per_latent, ssq, knn_host, knn_per_latent, mean_const, fvar_out);
+  double* part = (double*)ws;
+  int nb = 0;
+  GPK_TRY(gpk_launch_likelihood_varexp_stage1((hipStream_t)stream, lik, lik_params_host, m, rows_out, dmu_out, dvar_out, part,
+                                              part + GPK_REDUCE_MAXPART, &nb));
+  // out[0] = sum VE, out[1] = sum dVE/dscale (StudentT; the others' partials are zeros)
+  GPK_TRY(gpk_launch_final_one((hipStream_t)stream, part, nb, 1.0, 0.0, out));
+  return gpk_launch_final_one((hipStream_t)stream, part + GPK_REDUCE_MAXPART, nb, 1.0, 0.0, out + 1);
+}
