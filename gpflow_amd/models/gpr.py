@@ -62,55 +62,22 @@ class GPR(GPModel, InternalDataTrainingLossMixin):
 
     def log_marginal_likelihood_and_grad(self):
         """(LML as a float, {Parameter: dLML/d(unconstrained value) as NumPy}) for the trainable parameters -- what
-        `optimizers/scipy.py:322-331` obtains from TF autodiff.  SquaredExponential or Matern12 / 32 / 52 kernel (with `active_dims`), constant / zero
-        mean, constant noise variance (gradients.gpr_lml_and_grad); anything else raises NotImplementedError."""
-        import numpy as np
+        `optimizers/scipy.py:322-331` obtains from TF autodiff.  SquaredExponential or Matern12 / 32 / 52 kernel (with `active_dims`) or a Sum /
+        Product of them, constant / zero mean, constant or heteroskedastic noise (gradients.gpr_lml_and_grad); anything else raises
+        NotImplementedError."""
         from .. import gradients
-        from ..kernels.stationaries import IsotropicStationary
-        from ..mean_functions import Constant
-        k, lik, mf = self.kernel, self.likelihood, self.mean_function
-        c = mf.constant_value()
-        from ..kernels.base import gradient_spec
-        combo = gradient_spec(k, self.data[0].shape[1])   # Sum / Product of stationary kernels (kernels/base.py:216-220, 305-315)
-        het = lik.is_heteroskedastic   # round 5: d LML / d sigma_n^2 per row, chained through the noise function's own reverse pass
-        if combo is None and not (isinstance(k, IsotropicStationary) and k.family in ops.KERNEL_FAMILIES) or c is None \
-                or not (lik.has_variance_parameter or het):
-            raise NotImplementedError("gradients: SquaredExponential / Matern kernel (or a Sum / Product of them), constant mean, "
-                                      "Gaussian likelihood with a variance parameter")
+        from . import reverse
+        lik = self.likelihood
+        route, c = reverse.regression_route(self)   # (refused before anything touches the device)
         X, Y = self.data
-        if combo is not None:
-            spec, members = combo
-            lml, g, info = gradients.gpr_lml_and_grad(ops.to_device(X).contiguous(), Y, noise_variance=lik.noise_for(X),
-                                                      mean_const=c, kernel_spec=spec)
-            ops.check_info(info)
-            gv = g["variance"].cpu().numpy()
-            pairs = []
-            for i, (pv, pl) in enumerate(members):
-                pairs += [(pv, gv[i]), (pl, g["lengthscales"][i].cpu().numpy())]
-            host = {"mean_const": g["mean_const"].cpu().numpy()}
-            noise_pairs = [(lik.variance, g["noise_variance"].cpu().numpy())] if not het else \
-                [(par, gv.cpu().numpy()) for par, gv in lik.noise_param_grads(X, g["noise_variance"])]
-            pairs += noise_pairs
-        else:
-            Xs, _ = k.slice(X, None)    # active_dims (kernels/base.py:90-109); nothing is differentiated w.r.t. X
-            family, var, ls = k.hyper()
-            lml, g, info = gradients.gpr_lml_and_grad(Xs.contiguous(), Y, variance=var, lengthscales=ls,
-                                                      noise_variance=lik.noise_for(X), mean_const=c, family=family)
-            ops.check_info(info)
-            host = {n: t.cpu().numpy() for n, t in g.items() if n != "noise_variance"}
-            pairs = [(k.variance, host["variance"]), (k.lengthscales, host["lengthscales"])]
-            pairs += [(lik.variance, g["noise_variance"].cpu().numpy())] if not het else \
-                [(par, gv.cpu().numpy()) for par, gv in lik.noise_param_grads(X, g["noise_variance"])]
-        if isinstance(mf, Constant) and hasattr(mf, "c"):   # (Zero is a Constant without a parameter, functions.py:195-204)
-            pairs.append((mf.c, host["mean_const"]))
-        out = {}
-        for par, gc in pairs:
-            if par.trainable:
-                u = par.unconstrained_variable
-                gu = np.asarray(gc, dtype=np.float64).reshape(u.shape) * par.transform.forward_grad(u)
-                out[par] = out[par] + gu if par in out else gu   # (a Parameter shared by several members: k + k, tied lengthscales)
+        _, Xs, _ = route.inputs(None, X)            # active_dims (kernels/base.py:90-109); nothing is differentiated w.r.t. X
+        # (a heteroskedastic likelihood: d LML / d sigma_n^2 per row, chained through the noise function's own reverse pass)
+        lml, g, info = gradients.gpr_lml_and_grad(Xs, Y, noise_variance=lik.noise_for(X), mean_const=c, kernel_spec=route.spec)
+        ops.check_info(info)
+        pairs = route.kernel_pairs(g) + reverse.noise_pairs(lik, X, g["noise_variance"]) \
+            + reverse.mean_pairs(self.mean_function, g["mean_const"].cpu().numpy())
         # with parameter priors this is the log POSTERIOR density and its gradient: -training_loss (model.py:56-76)
-        return self._add_log_prior(float(lml.cpu()[0]), out)
+        return self._add_log_prior(float(lml.cpu()[0]), reverse.to_unconstrained(pairs))
 
     objective_and_grad = log_marginal_likelihood_and_grad   # what optimizers.Scipy calls
 

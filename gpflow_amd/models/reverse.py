@@ -1,0 +1,177 @@
+"""What the model-level entry points of the hand-written reverse pass share (SVGP.elbo_and_grad, GPR / SGPR.objective_and_grad,
+training.SVGPTrainer, optimizers.NaturalGradient): which models are covered, how ONE covariance function reaches `gradients.*`
+(always as a `gradients.KernelSpec`), and how what comes back becomes {Parameter: d objective / d(unconstrained value)}."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import gradients, ops
+from ..base import FillTriangular
+from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
+from ..kernels import SeparateIndependent, SharedIndependent
+from ..kernels.base import Combination, gradient_spec
+from ..kernels.stationaries import IsotropicStationary
+from ..likelihoods import Gaussian
+from ..mean_functions import Constant
+
+
+def shared_pair(kernel, inducing_variable):
+    """(kernel, inducing variable) with SharedIndependent + SharedIndependentInducingVariables unwrapped: P latents over one Kuu / Kuf
+    (BASELINE config C5)"""
+    if isinstance(kernel, SharedIndependent) and isinstance(inducing_variable, SharedIndependentInducingVariables):
+        return kernel.kernel, inducing_variable.inducing_variable
+    return kernel, inducing_variable
+
+
+def sliced(k, Z, X):
+    """Inputs restricted to the kernel's active_dims + the scatter of a gradient w.r.t. the sliced Z back to Z's shape
+    (gpflow/kernels/base.py:90-109: the kernel only ever sees these columns, so dF/dZ is zero elsewhere)."""
+    if k.has_default_active_dims:
+        return Z, X, (lambda gz: gz)
+    Xs, Zs = k.slice(X, Z)
+    dims = k._active_dims
+    cols = torch.arange(Z.shape[1], device=Z.device)[dims] if isinstance(dims, slice) else torch.as_tensor(dims, device=Z.device)
+
+    def scatter(gz):
+        full = torch.zeros_like(Z)
+        full.index_add_(1, cols, gz)   # (a repeated active column collects both contributions, like tf.gather's gradient)
+        return full
+    return Zs, Xs, scatter
+
+
+def minibatch_scale(num_data, rows) -> float:
+    """svgp.py:172-174: the data term of a minibatch of `rows` rows stands for `num_data` rows"""
+    return 1.0 if num_data is None else float(num_data) / float(rows)
+
+
+def _supported_stationary(k) -> bool:
+    return isinstance(k, IsotropicStationary) and k.family in ops.KERNEL_FAMILIES
+
+
+class CovarianceRoute:
+    """One covariance function as the reverse pass takes it: `spec` (gradients.KernelSpec), `members` [(variance Parameter,
+    lengthscales Parameter)] in the spec's order, the inputs as `gradients.*` gets them and the scatter of dF/dZ back to Z's columns.
+      one SquaredExponential / Matern kernel: a one-member spec over ALL columns of inputs sliced by its `active_dims` out here
+        (a spec with `cols` would leave the packed covariance tail of gradients.svgp_elbo_and_grad);
+      a Sum / Product of them, flat or nested: kernels.base.gradient_spec -- the spec slices for its members itself.
+    Anything else raises NotImplementedError."""
+
+    def __init__(self, kernel, input_dim=None):
+        self.kernel = kernel
+        self.is_combination = isinstance(kernel, Combination)
+        if self.is_combination:
+            self.spec, self.members = gradient_spec(kernel, input_dim)
+        elif _supported_stationary(kernel):
+            family, var, ls = kernel.hyper()
+            self.spec, self.members = gradients.KernelSpec.single(var, ls, family), [(kernel.variance, kernel.lengthscales)]
+        else:
+            raise NotImplementedError("gradients: a SquaredExponential / Matern kernel, or a Sum / Product (possibly nested) of them")
+
+    def inputs(self, Z, X):
+        """(Z, X, scatter) as passed to `gradients.*`; Z None (GPR): X alone is sliced"""
+        if self.is_combination:
+            return Z, X.contiguous(), (lambda gz: gz)
+        if Z is None:
+            return None, self.kernel.slice(X, None)[0].contiguous(), None
+        return sliced(self.kernel, Z, X)
+
+    def spec_at(self, values):
+        """the spec with the members' [(variance, lengthscales)] replaced (the trainer's current values)"""
+        return gradients.KernelSpec([(f, v, ls) for (f, _, _), (v, ls) in zip(self.spec.members, values)], self.spec.tree, self.spec.cols)
+
+    def member_grads(self, g):
+        """[(d/dvariance_i [1], d/dlengthscales_i)] from the `grads` of a `gradients.*` call: the one place that knows the two packings
+        of KernelSpec.pack (one member: "variance" [1] and "lengthscales" a tensor; several: "variance" [n] and a list)"""
+        gv, gl = g["variance"].reshape(-1), ([g["lengthscales"]] if self.spec.n == 1 else g["lengthscales"])
+        return [(gv[i:i + 1], gl[i].reshape(-1)) for i in range(self.spec.n)]
+
+    def kernel_pairs(self, g):
+        """[(Parameter, dF/d constrained as NumPy)] of the members, in member order (the variances come back in one copy)"""
+        gv = g["variance"].reshape(-1).cpu().numpy()
+        gl = [g["lengthscales"]] if self.spec.n == 1 else g["lengthscales"]
+        return [pair for i, (pv, pl) in enumerate(self.members) for pair in ((pv, gv[i:i + 1]), (pl, gl[i].reshape(-1).cpu().numpy()))]
+
+
+def noise_pairs(lik, X, g_noise, reduce=None):
+    """[(Parameter, gradient)] of a Gaussian likelihood's noise: the `variance` Parameter, or -- heteroskedastic, g_noise = dF/d sigma_n^2
+    per row of X on the device -- the Parameters of the noise Function (Gaussian.noise_param_grads).  reduce: applied to each Function
+    gradient before it is read back (SGPR: the sum over the row shards)."""
+    if not lik.is_heteroskedastic:
+        return [(lik.variance, g_noise.cpu().numpy() if torch.is_tensor(g_noise) else g_noise)]
+    out = []
+    for par, gv in lik.noise_param_grads(X, g_noise):
+        out.append((par, (gv if reduce is None else reduce(gv.contiguous())).cpu().numpy()))
+    return out
+
+
+def mean_pairs(mean_function, g_mean):
+    """a Constant mean with a parameter (Zero is a Constant without one, functions.py:195-204)"""
+    return [(mean_function.c, g_mean)] if isinstance(mean_function, Constant) and hasattr(mean_function, "c") else []
+
+
+def to_unconstrained(pairs):
+    """{Parameter: dF/d(unconstrained value)} from [(Parameter, dF/d constrained value)], trainable Parameters only, keys in the order of
+    their first pair (optimizers.Scipy packs its vector in it).  A Parameter that occurs twice (k + k, tied lengthscales) collects the
+    sum, as autodiff returns it; fill-triangular is a linear embedding: the vector entries are the lower-triangular ones."""
+    out = {}
+    for par, gc in pairs:
+        if not par.trainable:
+            continue
+        u = par.unconstrained_variable
+        if isinstance(par.transform, FillTriangular):
+            gu = par.transform.inverse(np.asarray(gc, dtype=np.float64)).reshape(u.shape)
+        else:
+            gu = np.asarray(gc, dtype=np.float64).reshape(u.shape) * par.transform.forward_grad(u)
+        out[par] = out[par] + gu if par in out else gu
+    return out
+
+
+# ---- scope: one check per model family, before anything touches the device ---------------------------------------------------------
+def _gaussian_noise(lik, heteroskedastic=True) -> bool:
+    return isinstance(lik, Gaussian) and (lik.has_variance_parameter or (heteroskedastic and lik.is_heteroskedastic))
+
+
+def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
+    """([(CovarianceRoute, InducingPoints)], mean constant, separate) for an SVGP inside the reverse pass, else NotImplementedError: whitened or
+    not, InducingPoints, constant mean, Gaussian likelihood (a variance Parameter or a noise Function), and
+      one SquaredExponential / Matern kernel, with `active_dims`, possibly shared by the latents (SharedIndependent +
+        SharedIndependentInducingVariables), full or diagonal q_sqrt -- one route;
+      a Sum / Product of such kernels, full or diagonal q_sqrt -- one route;
+      SeparateIndependent over shared or separate inducing points, every member ONE SquaredExponential / Matern kernel, full
+        q_sqrt -- one route per latent, and `separate` is True (also for a single member: the callers name and slice by it).
+    quadrature (a Bernoulli / Poisson / StudentT / MultiClass likelihood, `likelihood=` of gradients.svgp_elbo_and_grad): whitened,
+    one kernel over all input columns, at most 16 latents.  narrow (natural gradients on q(u)): one kernel over all input columns,
+    full q_sqrt, constant noise."""
+    k, iv = model.kernel, model.inducing_variable
+    plain = not (quadrature or narrow)
+    lik_ok = (model.whiten and model._device_likelihood()) if quadrature else _gaussian_noise(model.likelihood, not narrow)
+    q_full = model.q_sqrt.numpy().ndim == 3
+    separate = isinstance(k, SeparateIndependent)
+    if separate and plain:
+        ivs = list(iv.inducing_variable_list) if isinstance(iv, SeparateIndependentInducingVariables) else \
+            [iv.inducing_variable] * len(k.kernels) if isinstance(iv, SharedIndependentInducingVariables) else []
+        pairs, ok = list(zip(k.kernels, ivs)), q_full and len(ivs) == len(k.kernels) and all(_supported_stationary(kk) for kk in k.kernels)
+    else:
+        pairs, ok = [shared_pair(k, iv)], q_full or not narrow
+        if isinstance(pairs[0][0], Combination):          # (as the model's own kernel only: not shared through SharedIndependent)
+            ok = ok and plain and pairs[0][0] is k
+        elif not plain:
+            ok = ok and pairs[0][0].has_default_active_dims
+    c = model.mean_function.constant_value()
+    if not (ok and lik_ok and c is not None and all(isinstance(v, InducingPoints) for _, v in pairs)):
+        raise NotImplementedError(
+            "gradients: SVGP over InducingPoints with a constant mean and a SquaredExponential / Matern kernel (shared by independent "
+            "latents, or one per latent with a full q_sqrt) or a Sum / Product of them, and a Gaussian likelihood -- or, whitened with one "
+            "kernel over all input columns and at most 16 latents, a Bernoulli / Poisson / StudentT / MultiClass likelihood; natural "
+            "gradients: one kernel over all input columns, full q_sqrt, constant noise")
+    return [(CovarianceRoute(kk, int(v.Z.shape[1])), v) for kk, v in pairs], float(c), separate
+
+
+def regression_route(model):
+    """(CovarianceRoute, mean constant) for a GPR / SGPR inside the reverse pass, else NotImplementedError"""
+    c = model.mean_function.constant_value()
+    if c is None or not _gaussian_noise(model.likelihood):
+        raise NotImplementedError("gradients: SquaredExponential / Matern kernel (or a Sum / Product of them), constant mean, Gaussian "
+                                  "likelihood with a noise variance held as a `variance` Parameter, or a noise Function of the inputs")
+    return CovarianceRoute(model.kernel, model.data[0].shape[1]), float(c)

@@ -166,7 +166,8 @@ class SGPR(GPModel, InternalDataTrainingLossMixin):
     def _config(self):
         k, iv, lik = self.kernel, self.inducing_variable, self.likelihood
         c = self.mean_function.constant_value()
-        from ..kernels.base import Combination, gradient_spec
+        from ..kernels.base import Combination
+        from .reverse import CovarianceRoute
         if not (isinstance(k, (Stationary, Combination)) and isinstance(iv, InducingPoints) and isinstance(lik, Gaussian)
                 and c is not None):
             raise NotImplementedError("SGPR here: stationary kernel (or a Sum / Product of them), InducingPoints, Gaussian "
@@ -176,8 +177,9 @@ class SGPR(GPModel, InternalDataTrainingLossMixin):
         s2 = None if lik.is_heteroskedastic else lik.noise_variance()
         if isinstance(k, Combination):
             # members slice for themselves (kernels/base.py:283-293): the spec works on the full columns
-            spec, _ = gradient_spec(k, self.data[0].shape[1])
-            return spec, self.data[0].contiguous(), iv.Z.device_value().contiguous(), float(c), s2
+            route = CovarianceRoute(k, self.data[0].shape[1])
+            Z, X, _ = route.inputs(iv.Z.device_value().contiguous(), self.data[0])
+            return route.spec, X, Z, float(c), s2
         family, var, ls = k.hyper()
         X, Z = k.slice(self.data[0], iv.Z.device_value())
         return gradients.KernelSpec.single(var, ls, family), X, Z, float(c), s2
@@ -234,63 +236,27 @@ class SGPR(GPModel, InternalDataTrainingLossMixin):
         (gradients.sgpr_elbo_and_grad; SquaredExponential or Matern12 / 32 / 52 kernel, `active_dims` allowed: dELBO/dZ
         is zero in the columns the kernel does not see).  On a row-sharded model every rank gets the complete ELBO and
         gradient: two all-reduces of M^2 + O(M) doubles per evaluation (gradients.sgpr_elbo_and_grad)."""
-        from ..kernels.stationaries import IsotropicStationary
-        from ..mean_functions import Constant
-        from .svgp import SVGP
-        from ..kernels.base import Combination, gradient_spec
-        kw, Xc, Zc, c, s2 = self._config()
-        het = s2 is None
-        if not het and not self.likelihood.has_variance_parameter:
-            raise NotImplementedError("gradients: the reverse pass takes a noise variance held as a `variance` Parameter, or a noise "
-                                      "Function of the inputs")
-        if het:   # one sigma_n^2 per row of this (shard of the) data; dF/d sigma_n^2 comes back per row (gradients.sgpr_elbo_and_grad)
+        from . import reverse
+        _, _, _, c, s2 = self._config()    # (first, as ever: the forward scope -- InducingPoints among it -- is refused here)
+        if s2 is None:   # one sigma_n^2 per row of this (shard of the) data; dF/d sigma_n^2 comes back per row (gradients.sgpr_elbo_and_grad)
             s2 = self._noise_rows().reshape(-1).contiguous()
+        route, _ = reverse.regression_route(self)
+        Z, X, scatter = route.inputs(self.inducing_variable.Z.device_value(), self.data[0])
+        F, g, info = gradients.sgpr_elbo_and_grad(Z, X, self.data[1], noise_variance=s2, jitter=config.default_jitter(), mean_const=c,
+                                                  sharded=self.sharded, group=self.group, num_data=self.num_data, kernel_spec=route.spec)
+        ops.check_info(info)
 
-        def noise_pairs(g_noise):
-            if not het:
-                return [(self.likelihood.variance, g_noise.cpu().numpy())]
-            out_ = []
-            for par, gv in self.likelihood.noise_param_grads(self.data[0], g_noise):   # chain rule through the noise function: this shard's rows
-                gv = gv.contiguous()
-                if self.sharded:
-                    import torch.distributed as dist
-                    dist.all_reduce(gv, op=dist.ReduceOp.SUM, group=self.group)
-                out_.append((par, gv.cpu().numpy()))
-            return out_
-        if isinstance(self.kernel, Combination):
-            # a Sum / Product of stationary kernels (members possibly over different active_dims): the members' adjoints one by one
-            spec, members = gradient_spec(self.kernel, self.data[0].shape[1])
-            F, g, info = gradients.sgpr_elbo_and_grad(Zc, Xc, self.data[1], noise_variance=s2, jitter=config.default_jitter(),
-                                                      mean_const=c, sharded=self.sharded, group=self.group,
-                                                      num_data=self.num_data, kernel_spec=spec)
-            ops.check_info(info)
-            gv = g["variance"].cpu().numpy()
-            host = {n: t.cpu().numpy() for n, t in g.items() if n not in ("variance", "lengthscales", "noise_variance")}
-            pairs = []
-            for i, (pv, pl) in enumerate(members):
-                pairs += [(pv, gv[i]), (pl, g["lengthscales"][i].cpu().numpy())]
-            pairs += noise_pairs(g["noise_variance"]) + [(self.inducing_variable.Z, host["Z"])]
-        else:
-            if not (isinstance(self.kernel, IsotropicStationary) and self.kernel.family in ops.KERNEL_FAMILIES):
-                raise NotImplementedError("gradients: SquaredExponential / Matern kernel")
-            family, var, ls = self.kernel.hyper()
-            Z, X, scatter = SVGP._sliced(self.kernel, self.inducing_variable.Z.device_value(), self.data[0])
-            F, g, info = gradients.sgpr_elbo_and_grad(Z, X, self.data[1], noise_variance=s2, jitter=config.default_jitter(),
-                                                      mean_const=c, sharded=self.sharded, group=self.group,
-                                                      num_data=self.num_data, variance=var, lengthscales=ls, family=family)
-            ops.check_info(info)
-            host = {n: (scatter(t) if n == "Z" else t).cpu().numpy() for n, t in g.items() if n != "noise_variance"}
-            pairs = [(self.kernel.variance, host["variance"]), (self.kernel.lengthscales, host["lengthscales"]),
-                     (self.inducing_variable.Z, host["Z"])] + noise_pairs(g["noise_variance"])
-        if isinstance(self.mean_function, Constant) and hasattr(self.mean_function, "c"):
-            pairs.append((self.mean_function.c, host["mean_const"]))
-        out = {}
-        for par, gc in pairs:
-            if par.trainable:
-                u = par.unconstrained_variable
-                gu = np.asarray(gc, dtype=np.float64).reshape(u.shape) * par.transform.forward_grad(u)
-                out[par] = out[par] + gu if par in out else gu
-        return self._add_log_prior(float(F.cpu()[0]), out)   # (+ log prior density: -training_loss, model.py:56-76)
+        def reduce(gv):   # the noise Function's parameters see this shard's rows: summed over the ranks
+            if self.sharded:
+                import torch.distributed as dist
+                dist.all_reduce(gv, op=dist.ReduceOp.SUM, group=self.group)
+            return gv
+        # (the order of the pairs is the order of the returned dict, which optimizers.Scipy packs by)
+        z_pairs = [(self.inducing_variable.Z, scatter(g["Z"]).cpu().numpy())]
+        n_pairs = reverse.noise_pairs(self.likelihood, self.data[0], g["noise_variance"], reduce)
+        pairs = route.kernel_pairs(g) + (n_pairs + z_pairs if route.is_combination else z_pairs + n_pairs) \
+            + reverse.mean_pairs(self.mean_function, g["mean_const"].cpu().numpy())
+        return self._add_log_prior(float(F.cpu()[0]), reverse.to_unconstrained(pairs))   # (+ log prior density: -training_loss, model.py:56-76)
 
     # ---- prediction ------------------------------------------------------------------------------
     def predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -11,11 +11,12 @@ from ..base import Parameter, positive, triangular
 from ..conditionals import conditional
 from ..inducing_variables import (InducingPoints, SharedIndependentInducingVariables,
                                   inducingpoint_wrapper)
-from ..kernels import Kernel, SharedIndependent
+from ..kernels import Kernel
 from ..kernels.stationaries import Stationary
 from ..likelihoods import Gaussian, Likelihood, MultiClass, ScalarLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
+from .reverse import shared_pair
 from .training_mixins import ExternalDataTrainingLossMixin
 
 
@@ -71,9 +72,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         c = self.mean_function.constant_value()
         if c is None:
             return None
-        k, iv = self.kernel, self.inducing_variable
-        if isinstance(k, SharedIndependent) and isinstance(iv, SharedIndependentInducingVariables):
-            k, iv = k.kernel, iv.inducing_variable
+        k, iv = shared_pair(self.kernel, self.inducing_variable)
         if not (isinstance(k, Stationary) and isinstance(iv, InducingPoints)):
             return None
         return k, iv.Z.device_value(), c
@@ -127,9 +126,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         shared by the latents over inducing points, full q_sqrt."""
         if self.whiten or self.q_sqrt.device_value().dim() != 3:
             return None
-        k, iv = self.kernel, self.inducing_variable
-        if isinstance(k, SharedIndependent) and isinstance(iv, SharedIndependentInducingVariables):
-            k, iv = k.kernel, iv.inducing_variable
+        k, iv = shared_pair(self.kernel, self.inducing_variable)
         if not (isinstance(k, Stationary) and isinstance(iv, InducingPoints)):
             return None
         return k, iv.Z.device_value()
@@ -279,240 +276,61 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             scale = 1.0
         return terms[0] * scale - terms[1]
 
-    def gradient_config(self, allow_active_dims: bool = False, allow_q_diag: bool = False, allow_heteroskedastic: bool = False):
-        """(kernel, InducingPoints, mean constant) if the hand-written reverse pass covers this model: whitened or not,
-        Gaussian likelihood with a variance parameter, full q_sqrt, constant mean, and ONE isotropic stationary kernel
-        (SquaredExponential / Matern12 / 32 / 52; `active_dims` and `q_diag` only where the caller
-        handles them itself: `elbo_and_grad`) over InducingPoints -- either directly or as SharedIndependent +
-        SharedIndependentInducingVariables (BASELINE config C5: P latents share Kuu / Kuf).  SeparateIndependent kernels
-        are differentiated latent by latent (`_separate_gradient_config`).  Raises NotImplementedError."""
-        from ..kernels.stationaries import IsotropicStationary
-        k, iv, lik = self.kernel, self.inducing_variable, self.likelihood
-        if isinstance(k, SharedIndependent) and isinstance(iv, SharedIndependentInducingVariables):
-            k, iv = k.kernel, iv.inducing_variable
-        c = self.mean_function.constant_value()
-        noise_ok = isinstance(lik, Gaussian) and (lik.has_variance_parameter or (allow_heteroskedastic and lik.is_heteroskedastic))
-        if not (isinstance(k, IsotropicStationary) and k.family in ops.KERNEL_FAMILIES and noise_ok
-                and isinstance(iv, InducingPoints) and c is not None
-                and (self.q_sqrt.numpy().ndim == 3 or (allow_q_diag and self.q_sqrt.numpy().ndim == 2))
-                and (allow_active_dims or k.has_default_active_dims)):
-            raise NotImplementedError("gradients: SVGP with a SquaredExponential / Matern kernel (optionally shared by independent "
-                                      "latents, or one per latent), Gaussian likelihood, InducingPoints, full q_sqrt, constant mean")
-        return k, iv, float(c)
-
-    def _separate_gradient_config(self):
-        """[(isotropic stationary kernel_p, InducingPoints_p)] per latent for SeparateIndependent kernels (over shared or
-        separate inducing points), else None."""
-        from ..covariances import _pairs  # noqa: F401  (same pairing rule as Kuu / Kuf)
-        from ..kernels import SeparateIndependent
-        from ..kernels.stationaries import IsotropicStationary
-        from ..inducing_variables import SeparateIndependentInducingVariables
-        k, iv, lik = self.kernel, self.inducing_variable, self.likelihood
-        if not isinstance(k, SeparateIndependent):
-            return None
-        if isinstance(iv, SeparateIndependentInducingVariables):
-            ivs = list(iv.inducing_variable_list)
-        elif isinstance(iv, SharedIndependentInducingVariables):
-            ivs = [iv.inducing_variable] * len(k.kernels)
-        else:
-            return None
-        c = self.mean_function.constant_value()
-        if not (all(isinstance(kk, IsotropicStationary) and kk.family in ops.KERNEL_FAMILIES for kk in k.kernels) and all(isinstance(v, InducingPoints) for v in ivs)
-                and isinstance(lik, Gaussian) and (lik.has_variance_parameter or lik.is_heteroskedastic) and c is not None
-                and self.q_sqrt.numpy().ndim == 3
-                and len(ivs) == len(k.kernels)):
-            raise NotImplementedError("gradients: SeparateIndependent needs SquaredExponential / Matern members over InducingPoints, a "
-                                      "Gaussian likelihood, full q_sqrt and a constant mean")
-        return list(zip(k.kernels, ivs)), float(c)
-
-    @staticmethod
-    def _sliced(k, Z, X):
-        """Inputs restricted to the kernel's active_dims + the scatter of a gradient w.r.t. the sliced Z back to Z's shape
-        (gpflow/kernels/base.py:90-109: the kernel only ever sees these columns, so dF/dZ is zero elsewhere)."""
-        if k.has_default_active_dims:
-            return Z, X, (lambda gz: gz)
-        Xs, Zs = k.slice(X, Z)
-        dims = k._active_dims
-        cols = torch.arange(Z.shape[1], device=Z.device)[dims] if isinstance(dims, slice) else torch.as_tensor(dims, device=Z.device)
-
-        def scatter(gz):
-            full = torch.zeros_like(Z)
-            full.index_add_(1, cols, gz)   # (a repeated active column collects both contributions, like tf.gather's gradient)
-            return full
-        return Zs, Xs, scatter
-
     def elbo_and_grad(self, data):
         """(ELBO on `data` as a float, {Parameter: dELBO/d(unconstrained value) as NumPy}) for the trainable parameters
         -- the pair `optimizers/scipy.py:322-331` gets from TF autodiff over `training_loss_closure(data)`.  Whitened or
-        not, SquaredExponential or Matern12 / 32 / 52 kernel (with `active_dims`; shared by the latents or one per latent), Gaussian likelihood,
-        InducingPoints, full q_sqrt (gradients.svgp_elbo_and_grad).  For minibatch training keep the variables on the
-        device instead: training.SVGPTrainer."""
+        not, SquaredExponential or Matern12 / 32 / 52 kernel (with `active_dims`; shared by the latents or one per latent) or a Sum /
+        Product of them, Gaussian likelihood (constant or heteroskedastic noise), or -- whitened, one kernel -- a quadrature likelihood
+        (Bernoulli, Poisson, StudentT, MultiClass: the reverse pass seeded per (row, latent) by the kernel's own d/dfmean, d/dfvar);
+        InducingPoints, full or diagonal q_sqrt: the scope of reverse.svgp_routes, refused before anything touches the device.
+        For minibatch training keep the variables on the device instead: training.SVGPTrainer."""
         from .. import gradients
-        from ..base import FillTriangular
-        from ..mean_functions import Constant
-        lik, mf = self.likelihood, self.mean_function
-        # scope checks first: a model outside the reverse pass is refused before anything touches the device
-        if isinstance(lik, (ScalarLikelihood, MultiClass)):
-            return self._elbo_and_grad_quadrature(data)
-        sep = self._separate_gradient_config()
-        from ..kernels.base import gradient_spec
-        combo = gradient_spec(self.kernel, int(tuple(data[0].shape)[-1])) if sep is None else None   # Sum / Product of stationary kernels
-        if combo is not None:
-            return self._elbo_and_grad_combination(data, combo)
-        # (a heteroskedastic Gaussian likelihood -- per-row dF/d sigma_n^2 chained through the noise function -- in the single-kernel
-        #  reverse passes, whitened and un-whitened: round 5)
-        single = self.gradient_config(allow_active_dims=True, allow_q_diag=True, allow_heteroskedastic=True) if sep is None else None
-        X, Y = ops.to_device(data[0]), ops.to_device(data[1])
-        scale = 1.0 if self.num_data is None else float(self.num_data) / float(X.shape[0])
-        fn = gradients.svgp_elbo_and_grad if self.whiten else gradients.svgp_elbo_and_grad_unwhitened
-        het = lik.is_heteroskedastic
-        common = dict(noise_variance=lik.noise_for(X), jitter=config.default_jitter(), scale=scale)
-        pairs = []
-        if sep is None:
-            k, iv, c = single
-            Zs, Xs, scatter = self._sliced(k, iv.Z.device_value(), X)
-            family, var, ls = k.hyper()
-            F, g, info = fn(Zs, Xs, Y, self.q_mu.device_value(), self.q_sqrt.device_value(), variance=var, lengthscales=ls,
-                            mean_const=float(c), family=family, **common)
-            ops.check_info(info)
-            Fv = float(F.cpu()[0])
-            host = {n: (scatter(t) if n == "Z" else t).cpu().numpy() for n, t in g.items()}
-            pairs = [(k.variance, host["variance"]), (k.lengthscales, host["lengthscales"]), (iv.Z, host["Z"])]
-            g_noise, g_mean, g_qmu, g_qs = host["noise_variance"], host["mean_const"], host["q_mu"], host["q_sqrt"]
-            if het:
-                pairs += [(par, gv.cpu().numpy()) for par, gv in lik.noise_param_grads(X, g["noise_variance"])]
-        else:
-            # SeparateIndependent (conditionals/util.py:566-629): L independent single-output problems that share the
-            # likelihood, the mean constant and the rows of the minibatch; ELBO and the shared gradients are their sums
-            members, c = sep
-            q_mu, q_sqrt = self.q_mu.device_value(), self.q_sqrt.device_value()
-            Fv, g_noise, g_mean = 0.0, 0.0, 0.0
-            g_qmu = np.zeros(tuple(q_mu.shape))
-            g_qs = np.zeros(tuple(q_sqrt.shape))
-            zgrads = {}
-            for p_, (k, iv) in enumerate(members):
-                Zs, Xs, scatter = self._sliced(k, iv.Z.device_value(), X)
-                family, var, ls = k.hyper()
-                F, g, info = fn(Zs, Xs, Y[:, p_:p_ + 1].contiguous(), q_mu[:, p_:p_ + 1].contiguous(), q_sqrt[p_:p_ + 1].contiguous(),
-                                variance=var, lengthscales=ls, mean_const=float(c), family=family, **common)
-                ops.check_info(info)
-                Fv += float(F.cpu()[0])
-                host = {n: (scatter(t) if n == "Z" else t).cpu().numpy() for n, t in g.items()}
-                pairs += [(k.variance, host["variance"]), (k.lengthscales, host["lengthscales"])]
-                zgrads[id(iv.Z)] = (iv.Z, zgrads.get(id(iv.Z), (None, 0.0))[1] + host["Z"])  # shared Z: contributions add up
-                g_noise = g_noise + host["noise_variance"]
-                g_mean = g_mean + host["mean_const"]
-                g_qmu[:, p_:p_ + 1] = host["q_mu"]
-                g_qs[p_:p_ + 1] = host["q_sqrt"]
-            pairs += list(zgrads.values())
-            if het:   # the latents share the likelihood: their per-row dF/d sigma_n^2 add up before the noise Function's reverse pass
-                pairs += [(par, gv.cpu().numpy()) for par, gv in lik.noise_param_grads(X, ops.to_device(np.asarray(g_noise)))]
-        if not het:
-            pairs.append((lik.variance, g_noise))
-        pairs += [(self.q_mu, g_qmu), (self.q_sqrt, g_qs)]
-        if isinstance(mf, Constant) and hasattr(mf, "c"):   # (Zero is a Constant without a parameter, functions.py:195-204)
-            pairs.append((mf.c, g_mean))
-        out = {}
-        for par, gc in pairs:
-            if not par.trainable:
-                continue
-            u = par.unconstrained_variable
-            if isinstance(par.transform, FillTriangular):   # linear embedding: the vector entries are the lower-triangular ones
-                gu = par.transform.inverse(np.asarray(gc, dtype=np.float64)).reshape(u.shape)
-            else:
-                gu = np.asarray(gc, dtype=np.float64).reshape(u.shape) * par.transform.forward_grad(u)
-            out[par] = out[par] + gu if par in out else gu
-        return self._add_log_prior(Fv, out)   # (+ log prior density of the trainable parameters: model.py:56-76)
-
-    def _elbo_and_grad_quadrature(self, data):
-        """elbo_and_grad with a quadrature likelihood (Bernoulli, Poisson, StudentT, MultiClass): the whitened reverse pass seeded per (row,
-        latent) by the kernel's own d/dfmean, d/dfvar (gradients.svgp_elbo_and_grad, likelihood=).  Whitened, ONE isotropic
-        stationary kernel over all input columns (optionally shared by the latents), InducingPoints, full or diagonal q_sqrt,
-        constant mean; everything else is refused before anything touches the device."""
-        from .. import gradients
-        from ..base import FillTriangular
-        from ..kernels.stationaries import IsotropicStationary
         from ..likelihoods import StudentT
-        from ..mean_functions import Constant
-        lik, mf, k, iv = self.likelihood, self.mean_function, self.kernel, self.inducing_variable
-        if isinstance(k, SharedIndependent) and isinstance(iv, SharedIndependentInducingVariables):
-            k, iv = k.kernel, iv.inducing_variable
-        c = mf.constant_value()
-        if not (self.whiten and self._device_likelihood() and isinstance(k, IsotropicStationary) and k.family in ops.KERNEL_FAMILIES
-                and k.has_default_active_dims and isinstance(iv, InducingPoints) and c is not None):
-            raise NotImplementedError("gradients with a Bernoulli / Poisson / StudentT / MultiClass likelihood: whitened SVGP with one "
-                                      "SquaredExponential / Matern kernel (optionally shared by independent latents) over all input "
-                                      "columns, InducingPoints, constant mean, at most 16 latents")
+        from . import reverse
+        lik = self.likelihood
+        quad = isinstance(lik, (ScalarLikelihood, MultiClass))
+        routes, c, separate = reverse.svgp_routes(self, quadrature=quad)
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])
-        scale = 1.0 if self.num_data is None else float(self.num_data) / float(X.shape[0])
-        family, var, ls = k.hyper()
-        F, g, info = gradients.svgp_elbo_and_grad(iv.Z.device_value(), X.contiguous(), Y, self.q_mu.device_value(),
-                                                  self.q_sqrt.device_value(), variance=var, lengthscales=ls, noise_variance=None,
-                                                  jitter=config.default_jitter(), scale=scale, mean_const=float(c), family=family,
-                                                  likelihood=(lik.device_lik, lik.device_params()))
-        ops.check_info(info)
-        host = {n: t.cpu().numpy() for n, t in g.items()}
-        pairs = [(k.variance, host["variance"]), (k.lengthscales, host["lengthscales"]), (iv.Z, host["Z"]),
-                 (self.q_mu, host["q_mu"]), (self.q_sqrt, host["q_sqrt"])]
-        if isinstance(lik, StudentT):
-            pairs.append((lik.scale, host["likelihood_scale"]))
-        if isinstance(mf, Constant) and hasattr(mf, "c"):   # (Zero is a Constant without a parameter, functions.py:195-204)
-            pairs.append((mf.c, host["mean_const"]))
-        out = {}
-        for par, gc in pairs:
-            if not par.trainable:
-                continue
-            u = par.unconstrained_variable
-            if isinstance(par.transform, FillTriangular):
-                gu = par.transform.inverse(np.asarray(gc, dtype=np.float64)).reshape(u.shape)
-            else:
-                gu = np.asarray(gc, dtype=np.float64).reshape(u.shape) * par.transform.forward_grad(u)
-            out[par] = out[par] + gu if par in out else gu
-        return self._add_log_prior(float(F.cpu()[0]), out)
-
-    def _elbo_and_grad_combination(self, data, combo):
-        """elbo_and_grad for a Sum / Product of stationary kernels (kernels/base.py:216-220, 305-315), members possibly over
-        different `active_dims`: the whitened or un-whitened reverse pass with the members' adjoints taken one by one
-        (gradients.KernelSpec)."""
-        from .. import gradients
-        from ..base import FillTriangular
-        from ..mean_functions import Constant
-        spec, members = combo
-        lik, mf, iv = self.likelihood, self.mean_function, self.inducing_variable
-        c = mf.constant_value()
-        # (a diagonal q_sqrt [M, P] goes through the same two reverse passes: the covariance spec and the q_diag branches of
-        #  gradients.svgp_elbo_and_grad / _unwhitened are independent of each other)
-        het = isinstance(lik, Gaussian) and lik.is_heteroskedastic   # (per-row dF/d sigma_n^2 chained through the noise Function)
-        if not (isinstance(lik, Gaussian) and (lik.has_variance_parameter or het) and isinstance(iv, InducingPoints) and c is not None):
-            raise NotImplementedError("gradients with a kernel combination: Gaussian likelihood (a variance parameter or a noise "
-                                      "Function), InducingPoints, constant mean")
-        X, Y = ops.to_device(data[0]), ops.to_device(data[1])
-        scale = 1.0 if self.num_data is None else float(self.num_data) / float(X.shape[0])
+        kw = dict(jitter=config.default_jitter(), scale=reverse.minibatch_scale(self.num_data, X.shape[0]), mean_const=c)
+        if quad:
+            kw.update(noise_variance=None, likelihood=(lik.device_lik, lik.device_params()))
+        else:
+            kw["noise_variance"] = lik.noise_for(X)
         fn = gradients.svgp_elbo_and_grad if self.whiten else gradients.svgp_elbo_and_grad_unwhitened
-        F, g, info = fn(iv.Z.device_value(), X.contiguous(), Y, self.q_mu.device_value(), self.q_sqrt.device_value(),
-                        noise_variance=lik.noise_for(X), jitter=config.default_jitter(), scale=scale,
-                        mean_const=float(c), kernel_spec=spec)
-        ops.check_info(info)
-        gv = g["variance"].cpu().numpy()
-        pairs = []
-        for i, (pv, pl) in enumerate(members):
-            pairs += [(pv, gv[i]), (pl, g["lengthscales"][i].cpu().numpy())]
-        pairs += [(iv.Z, g["Z"].cpu().numpy()), (self.q_mu, g["q_mu"].cpu().numpy()), (self.q_sqrt, g["q_sqrt"].cpu().numpy())]
-        pairs += [(par, gv.cpu().numpy()) for par, gv in lik.noise_param_grads(X, g["noise_variance"])] if het else \
-            [(lik.variance, g["noise_variance"].cpu().numpy())]
-        if isinstance(mf, Constant) and hasattr(mf, "c"):   # (Zero is a Constant without a parameter, functions.py:195-204)
-            pairs.append((mf.c, g["mean_const"].cpu().numpy()))
-        out = {}
-        for par, gc in pairs:
-            if not par.trainable:
-                continue
-            u = par.unconstrained_variable
-            if isinstance(par.transform, FillTriangular):
-                gu = par.transform.inverse(np.asarray(gc, dtype=np.float64)).reshape(u.shape)
-            else:
-                gu = np.asarray(gc, dtype=np.float64).reshape(u.shape) * par.transform.forward_grad(u)
-            out[par] = out[par] + gu if par in out else gu
-        return self._add_log_prior(float(F.cpu()[0]), out)
+        q_mu, q_sqrt = self.q_mu.device_value(), self.q_sqrt.device_value()
+        # one route; or SeparateIndependent (conditionals/util.py:566-629): L independent single-output problems that share the
+        # likelihood, the mean constant and the rows of the minibatch -- ELBO and the shared gradients are their sums, taken on the host
+        Fv, kernel_pairs, zgrads, hosts, noise_rows = 0.0, [], {}, [], []
+        for p_, (route, iv) in enumerate(routes):
+            cols = slice(p_, p_ + 1) if separate else slice(None)
+            Zs, Xs, scatter = route.inputs(iv.Z.device_value(), X)
+            F, g, info = fn(Zs, Xs, Y[:, cols].contiguous(), q_mu[:, cols].contiguous(), q_sqrt[cols].contiguous(),
+                            kernel_spec=route.spec, **kw)
+            ops.check_info(info)
+            Fv += float(F.cpu()[0])
+            kernel_pairs += route.kernel_pairs(g)
+            host = {n: g[n].cpu().numpy() for n in g if n not in ("variance", "lengthscales", "Z")}
+            gz = scatter(g["Z"]).cpu().numpy()
+            zgrads[id(iv.Z)] = (iv.Z, zgrads[id(iv.Z)][1] + gz if id(iv.Z) in zgrads else gz)   # shared Z: contributions add up
+            hosts.append(host)
+            noise_rows.append(g.get("noise_variance"))     # (on the device: what the noise Function's reverse pass takes)
+        total = lambda n: sum((h[n] for h in hosts[1:]), hosts[0][n])  # noqa: E731
+        q_pairs = [(self.q_mu, np.concatenate([h["q_mu"] for h in hosts], axis=1)),
+                   (self.q_sqrt, np.concatenate([h["q_sqrt"] for h in hosts], axis=0))]
+        if quad:
+            lik_pairs = [(lik.scale, hosts[0]["likelihood_scale"])] if isinstance(lik, StudentT) else []
+        else:
+            # (the latents share the likelihood: their per-row dF/d sigma_n^2 add up before the noise Function's reverse pass)
+            g_noise = total("noise_variance")
+            if lik.is_heteroskedastic:
+                g_noise = ops.to_device(np.asarray(g_noise)) if separate else noise_rows[0]
+            lik_pairs = reverse.noise_pairs(lik, X, g_noise)
+        # (the order of the pairs is the order of the returned dict, which optimizers.Scipy packs by: the noise comes before q(u)
+        #  unless the route is a combination)
+        noise_first = not quad and not routes[0][0].is_combination
+        pairs = kernel_pairs + list(zgrads.values()) + (lik_pairs + q_pairs if noise_first else q_pairs + lik_pairs) \
+            + reverse.mean_pairs(self.mean_function, total("mean_const"))
+        return self._add_log_prior(Fv, reverse.to_unconstrained(pairs))   # (+ log prior density of the trainable parameters: model.py:56-76)
 
     def posterior(self, precompute_cache=posteriors.PrecomputeCacheType.TENSOR):
         """svgp.py:210-240"""

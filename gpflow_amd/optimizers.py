@@ -68,16 +68,14 @@ class NaturalGradient:
 
     def minimize(self, model, data) -> None:
         from . import config, gradients, natgrad, ops
-        k, iv, c = model.gradient_config()
-        lik = model.likelihood
+        from .models import reverse
+        (route, iv), = reverse.svgp_routes(model, narrow=True)[0]
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])
-        scale = 1.0 if model.num_data is None else float(model.num_data) / float(X.shape[0])
-        family, var, ls = k.hyper()
         q_mu, q_sqrt = model.q_mu.device_value(), model.q_sqrt.device_value()
         fn = gradients.svgp_elbo_and_grad if model.whiten else gradients.svgp_elbo_and_grad_unwhitened
-        _, g, info = fn(iv.Z.device_value(), X, Y, q_mu, q_sqrt, variance=var, lengthscales=ls,
-                                                  noise_variance=lik.noise_variance(), jitter=config.default_jitter(),
-                                                  scale=scale, mean_const=float(c), family=family)
+        _, g, info = fn(iv.Z.device_value(), X, Y, q_mu, q_sqrt, kernel_spec=route.spec, noise_variance=model.likelihood.noise_variance(),
+                        jitter=config.default_jitter(), scale=reverse.minibatch_scale(model.num_data, X.shape[0]),
+                        mean_const=model.mean_function.constant_value())
         ops.check_info(info)
         mu, sq = natgrad.natgrad_update(q_mu, q_sqrt, -g["q_mu"], -g["q_sqrt"], self.gamma,
                                         xi_transform=self.xi_transform)   # loss = -ELBO

@@ -59,39 +59,20 @@ class SVGPTrainer:
         """natgrad_gamma: if given, (q_mu, q_sqrt) take a natural-gradient step of that size per iteration
         (optimizers/natgrad.py; natgrad.natgrad_update on the device) and Adam handles the remaining parameters -- the
         hybrid recipe of the reference's natural-gradient notebook, from ONE gradient evaluation per step."""
-        # NotImplementedError outside the scope of the reverse pass
-        # a Sum / Product of stationary kernels (flat or nested, members over their own columns): the covariance spec is rebuilt from the
-        # trainer's current member values every step (gradients.KernelSpec); one stationary kernel keeps the scalar arguments
-        from .kernels.base import Combination, gradient_spec
-        self.combo = None
-        self.sep = None
+        # NotImplementedError outside the scope of the reverse pass (models/reverse.py).  One route per covariance function: one for a
+        # stationary kernel or a Sum / Product of them (flat or nested, members over their own columns), P for one kernel per latent
+        # over SHARED inducing points (BASELINE config C5, separate): P single-output problems that share Z, the likelihood, the mean
+        # constant and the minibatch rows; their objectives and shared gradients add up (conditionals/util.py:566-629).  The
+        # covariance spec is rebuilt from the trainer's current member values every step (CovarianceRoute.spec_at).
+        from .inducing_variables import SharedIndependentInducingVariables
         from .kernels import SeparateIndependent
-        if isinstance(model.kernel, SeparateIndependent):
-            # one kernel per latent over SHARED inducing points (BASELINE config C5, separate): P single-output problems that share Z, the
-            # likelihood, the mean constant and the minibatch rows; their objectives and shared gradients add up (conditionals/util.py:566-629)
-            from .inducing_variables import SharedIndependentInducingVariables
-            if not isinstance(model.inducing_variable, SharedIndependentInducingVariables):
-                raise NotImplementedError("the trainer with separate kernels per latent: shared inducing points")
-            sepc = model._separate_gradient_config()             # (raises outside the reverse pass)
-            members, c = sepc
-            self.sep = [k_ for k_, _ in members]
-            iv = members[0][1]
-            k = None
-        elif isinstance(model.kernel, Combination):
-            from .inducing_variables import InducingPoints
-            from .likelihoods import Gaussian
-            iv, c = model.inducing_variable, model.mean_function.constant_value()
-            lik0 = model.likelihood
-            if not (isinstance(iv, InducingPoints) and c is not None and isinstance(lik0, Gaussian)
-                    and (lik0.has_variance_parameter or lik0.is_heteroskedastic)):
-                raise NotImplementedError("the trainer with a kernel combination: Gaussian likelihood, InducingPoints, constant mean")
-            spec0, members = gradient_spec(model.kernel, int(iv.Z.shape[1]))   # (raises for members outside the reverse pass)
-            self.combo = (spec0, members)
-            k = None
-        else:
-            k, iv, c = model.gradient_config(allow_active_dims=True, allow_q_diag=True, allow_heteroskedastic=True)
+        from .models import reverse
+        if isinstance(model.kernel, SeparateIndependent) and not isinstance(model.inducing_variable, SharedIndependentInducingVariables):
+            raise NotImplementedError("the trainer with separate kernels per latent: shared inducing points")
+        routes, c, self.separate = reverse.svgp_routes(model)
+        iv = routes[0][1]
+        self.routes = [r for r, _ in routes]
         lik = model.likelihood
-        self.kernel = k
         self.q_diag = model.q_sqrt.numpy().ndim == 2
         if self.q_diag and natgrad_gamma is not None:
             raise NotImplementedError("natural gradients need the full q_sqrt [P, M, M] (optimizers/natgrad.py:280-368)")
@@ -100,34 +81,22 @@ class SVGPTrainer:
         # q_sqrt) it is evaluated and added on the device (`_device_prior`, round 5)
         self.model, self.group = model, group
         self.natgrad_gamma = None if natgrad_gamma is None else float(natgrad_gamma)
-        self.mean_const = float(c)
-        self.family = k.family if k is not None else None
+        self.mean_const = c
         self.opt = _Adam(learning_rate, beta_1, beta_2, epsilon)
-        # host side: unconstrained scalars (their constrained values are host arguments of the C-ABI)
-        if self.sep is not None:
-            self.host, self.member_names, seen = {}, [], {}
-            for k_ in self.sep:                                   # (a Parameter shared by several latents' kernels: one entry, summed gradient)
-                names = []
-                for par, pre in ((k_.variance, "kvar"), (k_.lengthscales, "kls")):
+        # host side: unconstrained scalars (their constrained values are host arguments of the C-ABI).  One host entry per distinct
+        # Parameter (a Parameter shared by several members or latents -- k + k, tied lengthscales -- collects the SUM of its members'
+        # gradients, as autodiff returns it): "variance" / "lengthscales" for one stationary kernel, else member i of route r reads
+        # "kvar_<a>" / "kls_<b>"
+        plain = not self.separate and not self.routes[0].is_combination
+        self.host, self.member_names, seen = {}, [], {}
+        for route in self.routes:
+            self.member_names.append([])
+            for pars in route.members:
+                for par, pre, name in zip(pars, ("kvar", "kls"), ("variance", "lengthscales")):
                     if id(par) not in seen:
-                        seen[id(par)] = f"{pre}_{len(seen)}"
+                        seen[id(par)] = name if plain else f"{pre}_{len(seen)}"
                         self.host[seen[id(par)]] = par
-                    names.append(seen[id(par)])
-                self.member_names.append(tuple(names))
-        elif self.combo is None:
-            self.host = {"variance": k.variance, "lengthscales": k.lengthscales}
-        else:
-            # one host entry per distinct Parameter (a Parameter shared by several members -- k + k, tied lengthscales -- collects the
-            # SUM of its members' gradients, as autodiff returns it); member i reads "kvar_<a>" / "kls_<b>"
-            self.host, self.member_names, seen = {}, [], {}
-            for pv, pl in self.combo[1]:
-                names = []
-                for par, pre in ((pv, "kvar"), (pl, "kls")):
-                    if id(par) not in seen:
-                        seen[id(par)] = f"{pre}_{len(seen)}"
-                        self.host[seen[id(par)]] = par
-                    names.append(seen[id(par)])
-                self.member_names.append(tuple(names))
+                self.member_names[-1].append(tuple(seen[id(par)] for par in pars))
         # noise: a constant variance, or (a heteroskedastic Gaussian likelihood, likelihoods/scalar_continuous.py:52-111) the Parameters of
         # the noise Function -- they stay on the host like the other hyper-parameters; sigma_n^2 at the minibatch rows is formed on the
         # device every step and dF/d sigma_n^2 comes back per row, chained through the Function there (Gaussian.noise_param_grads)
@@ -140,13 +109,11 @@ class SVGPTrainer:
                 self.host[f"noise_fn_{i}"] = p
         else:
             self.host["noise_variance"] = lik.variance
-        from .mean_functions import Constant
-        mf = model.mean_function
-        if isinstance(mf, Constant) and hasattr(mf, "c"):   # (Zero is a Constant without a parameter, functions.py:195-204)
+        for par, _ in reverse.mean_pairs(model.mean_function, None):
             # Constant.c is a trainable Parameter like any other (gpflow/functions.py:173-192): it joins the host set
-            if np.size(mf.c.numpy()) != 1:
+            if np.size(par.numpy()) != 1:
                 raise NotImplementedError("the reverse pass covers a scalar Constant mean")
-            self.host["mean_const"] = mf.c
+            self.host["mean_const"] = par
         self.u = {n: np.array(p.unconstrained_variable, dtype=np.float64, copy=True) for n, p in self.host.items()}
         # device side (identity / fill-triangular transforms: the constrained array IS the variable)
         self.dev = {"Z": ops.to_device(iv.Z.numpy()).clone(), "q_mu": ops.to_device(model.q_mu.numpy()).clone(),
@@ -203,13 +170,11 @@ class SVGPTrainer:
         (models/model.py:56-76), the same quantity `SVGP.elbo_and_grad` reports -- as a device tensor [1] (no host
         synchronisation beyond the scalar-gradient read-back)."""
         import torch.distributed as dist
+        from .models import reverse
         Xb, Yb = ops.to_device(data[0]), ops.to_device(data[1])
         world = dist.get_world_size(self.group) if (dist.is_available() and dist.is_initialized()) else 1
         rows = int(global_batch) if global_batch is not None else Xb.shape[0] * world
-        scale = 1.0 if self.model.num_data is None else float(self.model.num_data) / float(rows)
-        if self.combo is None and self.sep is None:
-            var = float(self.constrained("variance"))
-            ls = self.constrained("lengthscales")
+        scale = reverse.minibatch_scale(self.model.num_data, rows)
         if self.het:
             # SIDE EFFECT, by design: the noise Function evaluates itself from its own Parameters, so the trainer's current values of
             # them are written into the model on every step -- unlike the kernel / Z / q parameters, which reach the model only through
@@ -223,54 +188,31 @@ class SVGPTrainer:
         if "mean_const" in self.host:
             self.mean_const = float(np.ravel(self.constrained("mean_const"))[0])
         fn = gradients.svgp_elbo_and_grad if self.model.whiten else gradients.svgp_elbo_and_grad_unwhitened
-        from .models.svgp import SVGP
         q_sqrt = torch.nn.functional.softplus(self.dev["q_sqrt"]) + self.q_lower if self.q_diag else self.dev["q_sqrt"]
-        if self.sep is not None:
-            if Yb.shape[1] != len(self.sep):
-                raise ValueError(f"{len(self.sep)} separate kernels need {len(self.sep)} output columns, got {Yb.shape[1]}")
-            scatter = lambda gz: gz  # noqa: E731  (each latent's input gradient is scattered below)
-            F, info = None, None
-            g = {"Z": torch.zeros_like(self.dev["Z"]), "q_mu": torch.zeros_like(self.dev["q_mu"]), "q_sqrt": torch.zeros_like(q_sqrt)}
-            for p_, (k_, (nv_, nl_)) in enumerate(zip(self.sep, self.member_names)):
-                Zs, Xs, sc = SVGP._sliced(k_, self.dev["Z"], Xb)
-                Fp, gp, ip = fn(Zs, Xs, Yb[:, p_:p_ + 1].contiguous(), self.dev["q_mu"][:, p_:p_ + 1].contiguous(),
-                                q_sqrt[p_:p_ + 1].contiguous(), variance=float(np.ravel(self.constrained(nv_))[0]),
-                                lengthscales=self.constrained(nl_), noise_variance=noise, jitter=config.default_jitter(), scale=scale,
-                                mean_const=self.mean_const, kl_weight=1.0 / world, family=k_.family)
-                F = Fp if F is None else F + Fp
-                info = ip if info is None else torch.maximum(info, ip)
-                g["Z"] += sc(gp["Z"])
-                g["q_mu"][:, p_:p_ + 1] = gp["q_mu"]
-                g["q_sqrt"][p_:p_ + 1] = gp["q_sqrt"]
-                for name in ("noise_variance", "mean_const"):
-                    g[name] = g[name] + gp[name] if name in g else gp[name]
-                gvp, glp = gp["variance"].reshape(1), gp["lengthscales"].reshape(-1)
-                g[nv_] = g[nv_] + gvp if nv_ in g else gvp
-                g[nl_] = g[nl_] + glp if nl_ in g else glp
-        elif self.combo is None:
-            Zs, Xs, scatter = SVGP._sliced(self.kernel, self.dev["Z"], Xb)      # active_dims (kernels/base.py:90-109)
-            F, g, info = fn(
-                Zs, Xs, Yb, self.dev["q_mu"], q_sqrt, variance=var, lengthscales=ls,
-                noise_variance=noise, jitter=config.default_jitter(), scale=scale, mean_const=self.mean_const,
-                kl_weight=1.0 / world, family=self.family)
-            g = dict(g)
-        else:
-            spec0 = self.combo[0]
-            members = [(f, float(np.ravel(self.constrained(nv))[0]), self.constrained(nl))
-                       for (f, _, _), (nv, nl) in zip(spec0.members, self.member_names)]
-            spec = gradients.KernelSpec(members, spec0.tree, spec0.cols)
-            scatter = lambda gz: gz  # noqa: E731  (the spec slices for its members and scatters their input gradients itself)
-            F, g, info = fn(self.dev["Z"], Xb.contiguous(), Yb, self.dev["q_mu"], q_sqrt, noise_variance=noise,
-                            jitter=config.default_jitter(), scale=scale, mean_const=self.mean_const, kl_weight=1.0 / world,
-                            kernel_spec=spec)
-            g = dict(g)
-            gv, gl = g.pop("variance"), g.pop("lengthscales")
-            if spec.n == 1:
-                gv, gl = gv.reshape(1), [gl]
-            for i, (nv, nl) in enumerate(self.member_names):    # per-member gradients onto their (possibly shared) Parameters
-                g[nv] = g[nv] + gv[i].reshape(1) if nv in g else gv[i].reshape(1)
-                gli = gl[i].reshape(-1)
-                g[nl] = g[nl] + gli if nl in g else gli
+        if self.separate and Yb.shape[1] != len(self.routes):
+            raise ValueError(f"{len(self.routes)} separate kernels need {len(self.routes)} output columns, got {Yb.shape[1]}")
+        F, info, g, g_q = None, None, {}, ([], [])
+
+        def add(name, t):   # per-member and per-latent gradients onto their (possibly shared) entries
+            g[name] = g[name] + t if name in g else t
+        for p_, (route, names) in enumerate(zip(self.routes, self.member_names)):
+            cols = slice(p_, p_ + 1) if self.separate else slice(None)
+            Zs, Xs, scatter = route.inputs(self.dev["Z"], Xb)      # active_dims (kernels/base.py:90-109)
+            spec = route.spec_at([(float(np.ravel(self.constrained(nv))[0]), self.constrained(nl)) for nv, nl in names])
+            Fp, gp, ip = fn(Zs, Xs, Yb[:, cols].contiguous(), self.dev["q_mu"][:, cols].contiguous(), q_sqrt[cols].contiguous(),
+                            noise_variance=noise, jitter=config.default_jitter(), scale=scale, mean_const=self.mean_const,
+                            kl_weight=1.0 / world, kernel_spec=spec)
+            F = Fp if F is None else F + Fp
+            info = ip if info is None else torch.maximum(info, ip)
+            for (nv, nl), (gv, gl) in zip(names, route.member_grads(gp)):
+                add(nv, gv)
+                add(nl, gl)
+            add("Z", scatter(gp["Z"]))
+            add("noise_variance", gp["noise_variance"])
+            add("mean_const", gp["mean_const"])
+            g_q[0].append(gp["q_mu"])
+            g_q[1].append(gp["q_sqrt"])
+        g["q_mu"], g["q_sqrt"] = (g_q[0][0], g_q[1][0]) if not self.separate else (torch.cat(g_q[0], dim=1), torch.cat(g_q[1], dim=0))
         if self.het:
             # per-row dF/d sigma_n^2 -> the noise Function's parameters (this shard's rows; summed over the ranks below)
             rows_g = g.pop("noise_variance")
@@ -280,7 +222,6 @@ class SVGPTrainer:
             for i, p in enumerate(self.noise_pars):
                 g[f"noise_fn_{i}"] = acc[id(p)].reshape(-1).contiguous() if id(p) in acc else \
                     torch.zeros(int(np.size(self.u[f"noise_fn_{i}"])), dtype=torch.float64, device=Xb.device)
-        g["Z"] = scatter(g["Z"])
         if self.q_diag:
             g["q_sqrt"] = g["q_sqrt"] * torch.sigmoid(self.dev["q_sqrt"])      # d softplus(u) / du
         g["_status"] = info.to(torch.float64).reshape(-1)[:1]   # rides in the packed all-reduce: > 0 iff ANY rank failed

@@ -328,3 +328,148 @@ def test_check_info_names_a_timed_out_handoff():
         ops.check_info(torch.tensor([2 ** 31 - 1], dtype=torch.int32))
     with pytest.raises(_lib.GpkError, match="non-positive pivot at column 4"):
         ops.check_info(torch.tensor([5], dtype=torch.int32))
+
+
+# ---------------------------------------------------------------- models/reverse.py: what the gradient entry points share
+def test_to_unconstrained_chain_rule_sums_and_order():
+    from gpflow_amd.base import Parameter, positive, triangular
+    from gpflow_amd.models.reverse import to_unconstrained
+    a, b = Parameter(np.array([0.7, 1.9]), transform=positive()), Parameter(np.array(2.0))
+    frozen = Parameter(np.array(1.5), transform=positive(), trainable=False)
+    M, P = 3, 2
+    tri = Parameter(np.stack([np.tril(np.arange(1.0, 10.0).reshape(M, M))] * P), transform=triangular())
+    ga1, ga2, gtri = np.array([0.5, -2.0]), np.array([4.0, 8.0]), np.arange(100.0, 100.0 + P * M * M).reshape(P, M, M)
+    out = to_unconstrained([(b, np.array(3.0)), (a, ga1), (frozen, np.array(9.0)), (tri, gtri), (a, ga2)])
+    assert list(out) == [b, a, tri]                                      # first occurrence, pair order; the frozen one is absent
+    u = a.unconstrained_variable
+    np.testing.assert_array_equal(out[a], ga1 * a.transform.forward_grad(u) + ga2 * a.transform.forward_grad(u))   # the sum, in pair order
+    assert out[b] == 3.0 and np.shape(out[b]) == np.shape(b.unconstrained_variable)   # identity transform: forward_grad = 1
+    # fill-triangular: an index map onto the lower-triangular entries -- the junk above the diagonal is dropped, nothing is scaled
+    low = tri.transform.inverse(np.tril(gtri))
+    np.testing.assert_array_equal(out[tri], low.reshape(tri.unconstrained_variable.shape))
+    assert out[tri].size == P * M * (M + 1) // 2 and sorted(np.ravel(out[tri])) == sorted(gtri[:, np.tril_indices(M)[0], np.tril_indices(M)[1]].ravel())
+
+
+def test_covariance_route_normalises_both_packings_of_the_kernel_gradients():
+    """KernelSpec.pack returns "variance" [1] + "lengthscales" a tensor for one member, "variance" [n] + a list for several: the route
+    pairs both with the members' Parameters, in member order; a Parameter shared by two members then collects the sum."""
+    import torch
+    import gpflow_amd as gpflow
+    from gpflow_amd.models.reverse import CovarianceRoute, to_unconstrained
+    K = gpflow.kernels
+    one = K.Matern32(variance=0.7, lengthscales=[1.3, 0.8], active_dims=[0, 2])
+    r1 = CovarianceRoute(one, 3)
+    assert r1.spec.n == 1 and r1.spec.cols == [None] and r1.members == [(one.variance, one.lengthscales)]
+    g1 = {"variance": torch.tensor([2.0]), "lengthscales": torch.tensor([3.0, 4.0])}
+    assert r1.spec.pack([g1["variance"]], [g1["lengthscales"]])[1] is g1["lengthscales"]
+    pairs = r1.kernel_pairs(g1)
+    assert [p for p, _ in pairs] == [one.variance, one.lengthscales]
+    np.testing.assert_array_equal(pairs[0][1], [2.0]); np.testing.assert_array_equal(pairs[1][1], [3.0, 4.0])
+    k0, k2 = K.SquaredExponential(variance=1.3, lengthscales=0.9), K.Matern52(variance=0.9, lengthscales=0.8)
+    k1 = K.Matern32(variance=0.7, lengthscales=1.1, active_dims=[1])
+    k1.variance = k0.variance                                            # one Parameter, two members
+    r3 = CovarianceRoute((k0 + k1) * k2, 3)
+    assert r3.spec.n == 3 and r3.spec.tree == ("mul", [("add", [0, 1]), 2]) and r3.members[1][0] is k0.variance
+    dvs, dls = [torch.tensor([1.0]), torch.tensor([10.0]), torch.tensor([100.0])], [torch.tensor([5.0]), torch.tensor([6.0]), torch.tensor([7.0])]
+    g3 = dict(zip(("variance", "lengthscales"), r3.spec.pack(dvs, dls)))
+    assert g3["variance"].shape == (3,) and isinstance(g3["lengthscales"], list)
+    pairs = r3.kernel_pairs(g3)
+    assert [p for p, _ in pairs] == [k0.variance, k0.lengthscales, k0.variance, k1.lengthscales, k2.variance, k2.lengthscales]
+    assert [float(np.ravel(v)[0]) for _, v in pairs] == [1.0, 5.0, 10.0, 6.0, 100.0, 7.0]
+    out = to_unconstrained(pairs)
+    assert list(out) == [k0.variance, k0.lengthscales, k1.lengthscales, k2.variance, k2.lengthscales]
+    u = k0.variance.unconstrained_variable
+    np.testing.assert_array_equal(out[k0.variance], 1.0 * k0.variance.transform.forward_grad(u) + 10.0 * k0.variance.transform.forward_grad(u))
+    # the device form the trainer takes: one [1] and one flat tensor per member
+    assert [(tuple(a.shape), tuple(b.shape)) for a, b in r3.member_grads(g3)] == [((1,), (1,))] * 3
+    assert [(tuple(a.shape), tuple(b.shape)) for a, b in r1.member_grads(g1)] == [((1,), (2,))]
+    with pytest.raises(NotImplementedError):
+        CovarianceRoute(K.SharedIndependent(k2, 2), 3)
+
+
+def test_every_gradient_entry_point_refuses_before_the_device(monkeypatch):
+    """Every (entry point, model) pair that tools/reverse_pass_log.py's model matrix records as refused: the same exception type, and
+    `ops.to_device` is never reached.  (GPR / SGPR hold their data on the device: it is 'uploaded' to the CPU while they are built.  One
+    more refusal of that matrix is not here: the SGPR with a constant noise that is no `variance` Parameter says so after its `_config`,
+    which has fetched Z by then -- tests/test_gpu_sgpr.py.)"""
+    import torch
+    import gpflow_amd as gpflow
+    from gpflow_amd import ops, training
+    K, L, IV, MF = gpflow.kernels, gpflow.likelihoods, gpflow.inducing_variables, gpflow.mean_functions
+    rng = np.random.default_rng(0)
+    N, M, D = 6, 4, 3
+    X, Z, Y = rng.normal(size=(N, D)), rng.normal(size=(M, D)), rng.normal(size=(N, 2))
+    se, m32 = lambda **kw: K.SquaredExponential(**kw), lambda **kw: K.Matern32(**kw)  # noqa: E731
+    gauss = lambda: L.Gaussian(0.2)  # noqa: E731
+    het = lambda: L.Gaussian(scale=gpflow.functions.Linear(A=np.array([[-0.1], [0.05], [0.02]]), b=np.array([0.6])))  # noqa: E731
+    shared_z = lambda: IV.SharedIndependentInducingVariables(IV.InducingPoints(Z.copy()))  # noqa: E731
+    separate_z = lambda: IV.SeparateIndependentInducingVariables([IV.InducingPoints(Z.copy()), IV.InducingPoints(Z + 0.1)])  # noqa: E731
+    sep = lambda: K.SeparateIndependent([se(), m32()])  # noqa: E731
+
+    def same_z_twice():   # (one InducingPoints object for both latents is still not the SHARED inducing variable the trainer asks for)
+        p0 = IV.InducingPoints(Z.copy())
+        return IV.SeparateIndependentInducingVariables([p0, p0])
+    linear = lambda q: MF.Linear(A=np.ones((D, q)), b=np.zeros(q))  # noqa: E731
+
+    def svgp(k, lik, iv=None, P=1, **kw):
+        return gpflow.models.SVGP(k, lik, Z.copy() if iv is None else iv, num_latent_gps=P, **kw)
+
+    def k_sum():
+        k0 = se()
+        return k0 + k0
+    elbo = lambda m, P=1: (lambda: m.elbo_and_grad((X, Y[:, :P])))  # noqa: E731
+    trainer = lambda m, **kw: (lambda: training.SVGPTrainer(m, **kw))  # noqa: E731
+    natgrad = lambda m, P=1: (lambda: gpflow.optimizers.NaturalGradient(1.0).minimize(m, (X, Y[:, :P])))  # noqa: E731
+    table = [(elbo(svgp(sep(), lik(), iv(), P=2, q_diag=True, whiten=wh), 2), NotImplementedError)
+             for wh in (True, False) for iv in (shared_z, separate_z) for lik in (gauss, het)]
+    table += [(elbo(svgp(se(), L.Bernoulli(), whiten=False)), NotImplementedError),
+              (elbo(svgp(m32(active_dims=[0, 2]), L.Bernoulli())), NotImplementedError),
+              (elbo(svgp(k_sum(), L.Bernoulli())), NotImplementedError),
+              (elbo(svgp(se(), L.MultiClass(3), P=2)), ValueError),
+              (elbo(svgp(se(), gauss(), mean_function=linear(1))), NotImplementedError),
+              (elbo(svgp(se() + K.SeparateIndependent([se()]), gauss())), NotImplementedError),
+              (elbo(svgp(K.SharedIndependent(k_sum(), 1), gauss(), shared_z())), NotImplementedError),
+              (elbo(svgp(K.SeparateIndependent([se()]), gauss())), NotImplementedError),
+              (elbo(svgp(K.SeparateIndependent([se() + m32(), se()]), gauss(), shared_z(), P=2), 2), NotImplementedError),
+              (trainer(svgp(K.SeparateIndependent([se() + m32(), se()]), gauss(), shared_z(), P=2)), NotImplementedError),
+              (trainer(svgp(sep(), gauss(), same_z_twice(), P=2)), NotImplementedError),
+              (trainer(svgp(sep(), gauss(), separate_z(), P=2)), NotImplementedError),
+              (trainer(svgp(se(), gauss(), q_diag=True), natgrad_gamma=0.5), NotImplementedError),
+              (trainer(svgp(se(), L.Bernoulli())), NotImplementedError),
+              (trainer(svgp(se(), gauss(), mean_function=linear(1))), NotImplementedError),
+              (natgrad(svgp(m32(active_dims=[0, 2]), gauss())), NotImplementedError),
+              (natgrad(svgp(se(), gauss(), q_diag=True)), NotImplementedError),
+              (natgrad(svgp(se(), het())), NotImplementedError),
+              (natgrad(svgp(k_sum(), gauss())), NotImplementedError),
+              (natgrad(svgp(sep(), gauss(), shared_z(), P=2), 2), NotImplementedError),
+              (natgrad(svgp(se(), L.Bernoulli())), NotImplementedError)]
+    monkeypatch.setattr(ops, "to_device", lambda x, dtype=torch.float64: torch.as_tensor(np.asarray(x), dtype=dtype))
+    table += [(gpflow.models.GPR((X, Y), se(), mean_function=linear(2)).objective_and_grad, NotImplementedError),
+              (gpflow.models.GPR((X, Y), se(), likelihood=L.Gaussian(scale=0.4)).objective_and_grad, NotImplementedError),
+              (gpflow.models.SGPR((X, Y), se(), Z.copy(), mean_function=linear(2)).objective_and_grad, NotImplementedError)]
+
+    def reached(*a, **kw):
+        pytest.fail("ops.to_device was reached before the refusal")
+    monkeypatch.setattr(ops, "to_device", reached)
+    for i, (call, exc) in enumerate(table):
+        with pytest.raises(exc) as e:
+            call()
+        assert e.type is exc, (i, e.type)
+
+
+def test_trainer_treats_one_separate_kernel_as_separate(monkeypatch):
+    """SeparateIndependent decides the trainer's naming and its column check, not the number of members: one member still reads
+    kvar_ / kls_ entries (Adam's state is keyed by them) and still wants one output column per member."""
+    import torch
+    import gpflow_amd as gpflow
+    from gpflow_amd import ops, training
+    K, IV = gpflow.kernels, gpflow.inducing_variables
+    rng = np.random.default_rng(1)
+    X, Z, Y = rng.normal(size=(6, 3)), rng.normal(size=(4, 3)), rng.normal(size=(6, 2))
+    monkeypatch.setattr(ops, "to_device", lambda x, dtype=torch.float64: torch.as_tensor(np.asarray(x), dtype=dtype))
+    m = gpflow.models.SVGP(K.SeparateIndependent([K.SquaredExponential()]), gpflow.likelihoods.Gaussian(0.2),
+                           IV.SharedIndependentInducingVariables(IV.InducingPoints(Z)), num_latent_gps=1)
+    tr = training.SVGPTrainer(m)
+    assert list(tr.host) == ["kvar_0", "kls_1", "noise_variance"]
+    with pytest.raises(ValueError, match="1 separate kernels need 1 output columns"):
+        tr.step((X, Y))

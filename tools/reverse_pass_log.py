@@ -1,12 +1,22 @@
 """What the reverse pass ISSUES, and what it returns, for a tree of this repository -- no device needed.
 
     python tools/reverse_pass_log.py dump  <tree> <out.pkl>     run the matrix below on <tree>'s gpflow_amd/gradients.py
+    python tools/reverse_pass_log.py dump-models <tree> <out.pkl> [device]
+                                                                the MODEL layer of <tree> (`model_cases`): what SVGP.elbo_and_grad, GPR /
+                                                                SGPR.objective_and_grad, SVGPTrainer and NaturalGradient issue and return
     python tools/reverse_pass_log.py compare <a.pkl> <b.pkl>    compare two dumps case by case
 
 `gradients.ops` is tests/fake_ops.py + tests/fake_likelihood_ops.py (of the SAME tree) behind a logging proxy: one line per outermost
 `ops.*` call (name, shape and strides of every tensor argument, every scalar argument); a TorchDispatchMode adds one line per aten op
 issued OUTSIDE an `ops.*` call (the torch glue).  Each case runs twice and the second run is kept (`ls_device` caches).  Kept per
 case: the log and the bytes of F, every gradient and info.  Written for the refactor recorded in profiles/reverse_pass_refactor.txt.
+
+`dump-models` patches every `gpflow_amd.ops` name the three fakes define (as the `gp` fixture of tests/test_multiclass_emulated.py does)
+behind the same logging wrapper -- or, with `device`, patches nothing and logs nothing: the same matrix on the real library.  Kept per
+case: the `ops.*` log, the returned value, every gradient under a key that carries its position in the returned dict and the
+position of its Parameter in `model.parameters`; for the trainer F, every `u` / `dev` entry after two steps and the names of `host` in
+order (in the key).  A refusal is kept as its exception type.  The model functions run twice on one model: `<case>` is the second run
+(Parameter.device_value caches warm), `<case>#cold` the first.  Written for the refactor recorded in profiles/model_layer_refactor.txt.
 """
 import itertools
 import pickle
@@ -29,13 +39,7 @@ def _desc(a):
     return type(a).__name__
 
 
-def load(tree):
-    sys.path[:0] = [tree, tree + "/tests"]
-    import torch
-    from torch.utils._python_dispatch import TorchDispatchMode
-    import fake_likelihood_ops
-    import fake_ops
-    from gpflow_amd import gradients
+def _logger():
     log, depth = [], [0]
 
     def wrap(name, fn):
@@ -48,6 +52,17 @@ def load(tree):
             finally:
                 depth[0] -= 1
         return call
+    return log, depth, wrap
+
+
+def load(tree):
+    sys.path[:0] = [tree, tree + "/tests"]
+    import torch
+    from torch.utils._python_dispatch import TorchDispatchMode
+    import fake_likelihood_ops
+    import fake_ops
+    from gpflow_amd import gradients
+    log, depth, wrap = _logger()
 
     proxy = types.SimpleNamespace()
     for mod in (fake_ops, fake_likelihood_ops):
@@ -150,6 +165,208 @@ def dump(tree, path):
     print([e[0][4:] for e in res["chunks1/white/full/scalar/se_ard/P2"][0] if e[0].startswith("ops.")])
 
 
+def model_cases(gp):
+    """[(name, kind, make)] of the model-layer matrix at M = 20, N = 64, D = 3.  kind "grad": make() -> (model, function returning
+    (value, {Parameter: gradient})); "trainer": make() -> (model, trainer kwargs, data); "natgrad": make() -> (model, data)."""
+    K, L, IV, F = gp.kernels, gp.likelihoods, gp.inducing_variables, gp.functions
+    M, N, D = 20, 64, 3
+    rng = np.random.default_rng(11)
+    X, Z = rng.normal(size=(N, D)), rng.normal(size=(M, D))
+    Y2 = np.sin(X.sum(1, keepdims=True)) + 0.1 * rng.normal(size=(N, 2))
+    q_mu = 0.3 * rng.normal(size=(M, 3))
+    q_full = np.stack([np.tril(0.05 * rng.normal(size=(M, M))) + 0.6 * np.eye(M) for _ in range(3)])
+    q_diag = 0.4 + 0.2 * np.abs(rng.normal(size=(M, 3)))
+    se = lambda **kw: K.SquaredExponential(variance=1.3, lengthscales=0.9, **kw)  # noqa: E731
+    m32 = lambda **kw: K.Matern32(variance=0.7, lengthscales=1.3, **kw)  # noqa: E731
+    pts = lambda dz=0.0: IV.InducingPoints(Z + dz)  # noqa: E731
+
+    def shared_sum():
+        k0 = se()
+        return k0 + k0
+    plain = {"se": se, "m32_active": lambda: m32(active_dims=[0, 2]), "sum_shared": shared_sum,
+             "nested": lambda: (se() + m32(active_dims=[1])) * K.Matern52(variance=0.9, lengthscales=0.8)}
+    multi = {"shared": lambda: (K.SharedIndependent(se(), 2), IV.SharedIndependentInducingVariables(pts())),
+             "sep_shared_z": lambda: (K.SeparateIndependent([se(), m32()]), IV.SharedIndependentInducingVariables(pts())),
+             "sep_separate_z": lambda: (K.SeparateIndependent([se(), m32()]),
+                                        IV.SeparateIndependentInducingVariables([pts(), pts(0.1)]))}
+    noise = {"const": lambda: L.Gaussian(0.2),
+             "het": lambda: L.Gaussian(scale=F.Linear(A=np.array([[-0.1], [0.05], [0.02]]), b=np.array([0.6])))}
+
+    def svgp(kname, lik, *, whiten=True, diag=False, mean=None, P=None, num_data=5 * N):
+        k, iv = multi[kname]() if kname in multi else (plain[kname](), Z.copy())
+        P = (2 if kname in multi else 1) if P is None else P
+        return gp.models.SVGP(k, lik, iv, q_mu=q_mu[:, :P].copy(), q_sqrt=(q_diag[:, :P] if diag else q_full[:P]).copy(), q_diag=diag,
+                              whiten=whiten, num_latent_gps=P, num_data=num_data, mean_function=mean)
+
+    def svgp_over(k, iv, lik, P):
+        return gp.models.SVGP(k, lik, iv, q_mu=q_mu[:, :P].copy(), q_sqrt=q_full[:P].copy(), num_latent_gps=P, num_data=5 * N)
+    shared_pts = lambda: IV.SharedIndependentInducingVariables(pts())  # noqa: E731
+    # SeparateIndependent at its edges: a member that is a Sum (refused), ONE member (still "separate": kvar_ / kls_ names, one output
+    # column per member), the same InducingPoints object twice in a SeparateIndependentInducingVariables (refused by the trainer)
+    sep_edge = {"sep_sum_member": lambda lik=None: svgp_over(K.SeparateIndependent([se() + m32(), se()]), shared_pts(), lik or L.Gaussian(0.2), 2),
+                "sep_one_member": lambda lik=None: svgp_over(K.SeparateIndependent([se()]), shared_pts(), lik or L.Gaussian(0.2), 1)}
+
+    def same_points_twice():
+        p0 = pts()
+        return svgp_over(K.SeparateIndependent([se(), m32()]), IV.SeparateIndependentInducingVariables([p0, p0]), L.Gaussian(0.2), 2)
+
+    def elbo_case(mk, Y):
+        def make():
+            m = mk()
+            return m, lambda: m.elbo_and_grad((X, Y))
+        return make
+    out = []
+    for wh, diag, kname, nz in itertools.product((True, False), (False, True), (*plain, *multi), noise):
+        out.append((f"svgp/{'white' if wh else 'unwhite'}/{'diag' if diag else 'full'}/{kname}/{nz}", "grad",
+                    elbo_case(lambda wh=wh, diag=diag, kname=kname, nz=nz: svgp(kname, noise[nz](), whiten=wh, diag=diag),
+                              Y2[:, :2 if kname in multi else 1])))
+    liks = {"bernoulli": (L.Bernoulli, 1, (Y2[:, :1] > 0).astype(np.float64)), "poisson": (L.Poisson, 1, np.floor(np.exp(Y2[:, :1]))),
+            "student_t": (L.StudentT, 1, Y2[:, :1]), "multiclass3": (lambda: L.MultiClass(3), 3, rng.integers(0, 3, size=(N, 1)).astype(np.float64))}
+    for (lname, (mk, P, Yl)), diag in itertools.product(liks.items(), (False, True)):
+        out.append((f"svgp/quadrature/{lname}/{'diag' if diag else 'full'}", "grad",
+                    elbo_case(lambda mk=mk, P=P, diag=diag: svgp("se", mk(), diag=diag, P=P), Yl)))
+    # quadrature likelihoods outside their narrower scope (refused)
+    for tag, kw, kname in (("unwhite", dict(whiten=False), "se"), ("active", {}, "m32_active"), ("sum", {}, "sum_shared")):
+        out.append((f"svgp/quadrature/bernoulli/{tag}", "grad",
+                    elbo_case(lambda kw=kw, kname=kname: svgp(kname, L.Bernoulli(), **kw), liks["bernoulli"][2])))
+
+    def frozen_ls():
+        m = svgp("se", L.Gaussian(0.2))
+        gp.set_trainable(m.kernel.lengthscales, False)
+        return m
+
+    def with_prior(m):
+        m.kernel.variance.prior = gp.priors.LogNormal(0.1, 0.8)
+        return m
+    extra = {"constant_mean": lambda: svgp("se", L.Gaussian(0.2), mean=gp.mean_functions.Constant(0.25)),
+             "constant_mean_sum": lambda: svgp("sum_shared", L.Gaussian(0.2), mean=gp.mean_functions.Constant(0.25)),
+             "frozen_lengthscale": frozen_ls, "variance_prior": lambda: with_prior(svgp("se", L.Gaussian(0.2))),
+             "no_num_data": lambda: svgp("se", L.Gaussian(0.2), num_data=None),
+             "linear_mean": lambda: svgp("se", L.Gaussian(0.2), mean=gp.mean_functions.Linear(A=np.ones((D, 1)), b=np.zeros(1))),
+             "odd_member": lambda: gp.models.SVGP(se() + K.SeparateIndependent([se()]), L.Gaussian(0.2), Z.copy()),
+             "shared_sum": lambda: gp.models.SVGP(K.SharedIndependent(shared_sum(), 1), L.Gaussian(0.2),
+                                                  IV.SharedIndependentInducingVariables(pts()), num_latent_gps=1),
+             "separate_over_points": lambda: gp.models.SVGP(K.SeparateIndependent([se()]), L.Gaussian(0.2), Z.copy())}
+    for name, mk in extra.items():
+        out.append((f"svgp/extra/{name}", "grad", elbo_case(mk, Y2[:, :1])))
+    out.append(("svgp/extra/sep_sum_member", "grad", elbo_case(sep_edge["sep_sum_member"], Y2[:, :2])))
+    out.append(("svgp/extra/sep_one_member", "grad", elbo_case(sep_edge["sep_one_member"], Y2[:, :1])))
+    out.append(("svgp/extra/sep_one_member_het", "grad", elbo_case(lambda: sep_edge["sep_one_member"](noise["het"]()), Y2[:, :1])))
+    out.append(("svgp/extra/sep_same_points_twice", "grad", elbo_case(same_points_twice, Y2[:, :2])))
+    for cls, (kname, nz) in itertools.product(("gpr", "sgpr"), itertools.product(plain, noise)):
+        def make(cls=cls, kname=kname, nz=nz):
+            m = gp.models.GPR((X, Y2), plain[kname](), likelihood=noise[nz]()) if cls == "gpr" else \
+                gp.models.SGPR((X, Y2), plain[kname](), Z.copy(), likelihood=noise[nz]())
+            return m, m.objective_and_grad
+        out.append((f"{cls}/{kname}/{nz}", "grad", make))
+    for cls in ("gpr", "sgpr"):
+        def make(cls=cls):
+            m = gp.models.GPR((X, Y2), se(), mean_function=gp.mean_functions.Constant(0.25), noise_variance=0.2) if cls == "gpr" else \
+                gp.models.SGPR((X, Y2), se(), Z.copy(), mean_function=gp.mean_functions.Constant(0.25), noise_variance=0.2)
+            return m, m.objective_and_grad
+        out.append((f"{cls}/constant_mean", "grad", make))
+        def linear_mean(cls=cls):
+            mf = gp.mean_functions.Linear(A=np.ones((D, 2)), b=np.zeros(2))
+            m = gp.models.GPR((X, Y2), se(), mean_function=mf) if cls == "gpr" else gp.models.SGPR((X, Y2), se(), Z.copy(), mean_function=mf)
+            return m, m.objective_and_grad
+        out.append((f"{cls}/linear_mean", "grad", linear_mean))
+
+        def noise_scale(cls=cls):   # (a constant noise that is not a `variance` Parameter; the SGPR says so after its _config)
+            m = gp.models.GPR((X, Y2), se(), likelihood=L.Gaussian(scale=0.4)) if cls == "gpr" else \
+                gp.models.SGPR((X, Y2), se(), Z.copy(), likelihood=L.Gaussian(scale=0.4))
+            return m, m.objective_and_grad
+        out.append((f"{cls}/noise_scale", "grad", noise_scale))
+    trainers = {"single": (lambda: svgp("se", L.Gaussian(0.2), mean=gp.mean_functions.Constant(0.25)), {}),
+                "unwhite_single": (lambda: svgp("se", L.Gaussian(0.2), whiten=False), {}),
+                "diag_active": (lambda: svgp("m32_active", L.Gaussian(0.2), diag=True), {}),
+                "sum_shared": (lambda: svgp("sum_shared", L.Gaussian(0.2)), {}),
+                "nested": (lambda: svgp("nested", L.Gaussian(0.2), whiten=False), {}),
+                "shared": (lambda: svgp("shared", L.Gaussian(0.2)), {}),
+                "sep_shared_z": (lambda: svgp("sep_shared_z", L.Gaussian(0.2)), {}),
+                "het": (lambda: svgp("se", noise["het"]()), {}),
+                "het_sep": (lambda: svgp("sep_shared_z", noise["het"]()), {}),
+                "het_nested": (lambda: svgp("nested", noise["het"]()), {}),
+                "natgrad": (lambda: svgp("se", L.Gaussian(0.2)), dict(natgrad_gamma=0.5)),
+                "variance_prior": (lambda: with_prior(svgp("se", L.Gaussian(0.2))), {}),
+                "sep_one_member": (sep_edge["sep_one_member"], {}),
+                # refused
+                "sep_one_member_two_columns": (sep_edge["sep_one_member"], {}),     # (by step: ValueError)
+                "sep_sum_member": (sep_edge["sep_sum_member"], {}),
+                "sep_same_points_twice": (same_points_twice, {}),
+                "sep_separate_z": (lambda: svgp("sep_separate_z", L.Gaussian(0.2)), {}),
+                "diag_natgrad": (lambda: svgp("se", L.Gaussian(0.2), diag=True), dict(natgrad_gamma=0.5)),
+                "bernoulli": (lambda: svgp("se", L.Bernoulli()), {}),
+                "linear_mean": (extra["linear_mean"], {})}
+    for name, (mk, kw) in trainers.items():
+        P = 2 if name in ("shared", "sep_shared_z", "het_sep", "sep_separate_z", "sep_one_member_two_columns", "sep_sum_member",
+                          "sep_same_points_twice") else 1
+        out.append((f"trainer/{name}", "trainer", lambda mk=mk, kw=kw, P=P: (mk(), dict(learning_rate=1e-2, **kw), (X, Y2[:, :P]))))
+    nat = {"accepted": lambda: svgp("se", L.Gaussian(0.2)), "accepted_unwhite_shared": lambda: svgp("shared", L.Gaussian(0.2), whiten=False),
+           "active": lambda: svgp("m32_active", L.Gaussian(0.2)), "diag": lambda: svgp("se", L.Gaussian(0.2), diag=True),
+           "het": lambda: svgp("se", noise["het"]()), "sum": lambda: svgp("sum_shared", L.Gaussian(0.2)),
+           "separate": lambda: svgp("sep_shared_z", L.Gaussian(0.2)), "bernoulli": lambda: svgp("se", L.Bernoulli())}
+    for name, mk in nat.items():
+        P = 2 if name in ("accepted_unwhite_shared", "separate") else 1
+        out.append((f"natgrad/{name}", "natgrad", lambda mk=mk, P=P: (mk(), (X, Y2[:, :P]))))
+    return out
+
+
+def dump_models(tree, path, device=None):
+    sys.path[:0] = [tree, tree + "/tests"]
+    import torch
+    import gpflow_amd as gp
+    from gpflow_amd import ops, training
+    log, depth, wrap = _logger()
+    if device is None:
+        import fake_likelihood_ops
+        import fake_multiclass_ops
+        import fake_ops
+        for mod in (fake_ops, fake_likelihood_ops, fake_multiclass_ops):
+            for name in dir(mod):
+                v = getattr(mod, name)
+                if name.startswith("_") or not callable(v) or not hasattr(ops, name) or isinstance(v, types.ModuleType):
+                    continue
+                setattr(ops, name, wrap(name, v))
+    arr = lambda v: np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64))  # noqa: E731
+    pack = lambda vals: {k: (tuple(arr(v).shape), arr(v).tobytes()) for k, v in vals.items()}  # noqa: E731
+    res = {}
+    for name, kind, make in model_cases(gp):
+        del log[:]
+        try:
+            if kind == "grad":
+                model, fn = make()
+                pos = {id(p): i for i, p in enumerate(model.parameters)}
+                for run in ("#cold", ""):
+                    del log[:]
+                    value, grads = fn()
+                    vals = {"F": value}
+                    for j, (p, g) in enumerate(grads.items()):
+                        vals[f"grad{j:02d}:parameter{pos[id(p)]}"] = g
+                    res[name + run] = (list(log), pack(vals))
+                continue
+            if kind == "trainer":
+                model, kw, data = make()
+                tr = training.SVGPTrainer(model, **kw)
+                for _ in range(2):
+                    Fv = tr.step(data)
+                vals = {"F": Fv, "host_names=" + ",".join(tr.host): np.zeros(0)}
+                vals.update({f"u:{n}": v for n, v in tr.u.items()})
+                vals.update({f"dev:{n}": v for n, v in tr.dev.items()})
+            else:
+                model, data = make()
+                gp.optimizers.NaturalGradient(1.0).minimize(model, data)
+                vals = {"q_mu": model.q_mu.numpy(), "q_sqrt": model.q_sqrt.numpy()}
+            res[name] = (list(log), pack(vals))
+        except (NotImplementedError, ValueError) as e:
+            res[name] = (list(log), {"refused:" + type(e).__name__: ((), b"")})
+    with open(path, "wb") as f:
+        pickle.dump(res, f)
+    refused = [n for n, (_, v) in res.items() if any(k.startswith("refused:") for k in v)]
+    print(len(res), "entries;", len(refused), "refusals:")
+    for n in refused:
+        print("   ", n, next(iter(res[n][1])), "after", len(res[n][0]), "ops.* calls")
+
+
 def compare(pa, pb):
     """per case: are the logs identical / the same lines in another order / different lines, and are the returned bytes identical"""
     a, b = pickle.load(open(pa, "rb")), pickle.load(open(pb, "rb"))
@@ -188,4 +405,4 @@ def compare(pa, pb):
 
 
 if __name__ == "__main__":
-    {"dump": dump, "compare": compare}[sys.argv[1]](*sys.argv[2:])
+    {"dump": dump, "dump-models": dump_models, "compare": compare}[sys.argv[1]](*sys.argv[2:])
