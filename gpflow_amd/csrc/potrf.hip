@@ -593,6 +593,16 @@ int PotrfRun::enqueue_chain(int p) {
   GPK_TRY(sync.panel_solved(p, flagged, strip));
   if (!has_strip) return 0;
   GPK_TRY(sync.strip_waits_for_rest(strip));
+  // A strip that waits in-kernel holds a compute unit per workgroup while it waits (150 KB of LDS each: nothing else fits beside one),
+  // and it is the high-priority stream's.  With as many waiting workgroups as compute units -- 480 for four problems of M = 2048, 249
+  // behind the first narrow panel of n = 4736 -- a rest-update that is late finds no compute unit, its word is never written and the
+  // bounded wait expires: the status word at INT_MAX of NEXT.md section 5.  So the waiters of one launch stay within the compute units of
+  // the bulk stream's mask (all but the 32 the chain keeps anyway) and walk their row blocks; launches below that are as before.
+  // (tests/test_potrf_schedule.py, assertion 7)
+  if (strip.wait_ptr && plan.bulk_cus > 0) {
+    const int room = std::max(1, plan.bulk_cus / batch);
+    if (strip.max_wgs <= 0 || strip.max_wgs > room) strip.max_wgs = room;
+  }
   return gpk_launch_gemm(P, strip);
 }
 

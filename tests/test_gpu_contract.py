@@ -986,6 +986,11 @@ SVGP_CASES = [
     (65, 200, 2, 2, False, False, "c"),     # un-whitened full q_sqrt (the one trapezoid)
     (64, 100, 2, 3, True, False, "off"),    # un-whitened diagonal q_sqrt (identity rows -> Lm^-T); misaligned rows
     (16, 0, 2, 2, False, False, "c"),       # un-whitened, zero rows
+    # schedule classes that only tests/test_potrf_schedule.py (CPU, no numbers) saw: the un-whitened full form at sizes where the
+    # factorisation runs on its own streams.  d = 8 keeps kappa(Kuu), and with it the derived bound, meaningful.
+    (640, 300, 8, 1, False, False, "c"),    # P = 1: the prefilled triangular rows (tril(q_sqrt)^T) skipped across two extra-row groups
+    (1152, 1040, 8, 1, False, False, "c"),  # ... across three groups and in the tail zone (shrinking groups at the end)
+    (640, 300, 8, 2, False, False, "off"),  # P = 2: the same form without the skip; misaligned rows
 ]
 CASE_TABLES["svgp_elbo_shard"] = SVGP_CASES
 
@@ -1016,15 +1021,21 @@ def test_svgp_elbo_shard_contract(gpu, case):
         assert abs(dv[1] - kl) <= (2 * (M * M * P + 2) + 4) * U * (abs(kl) + M * M * P), (dv[1], kl)
 
 
-CASE_TABLES["svgp_elbo_shard_sep"] = [(16, 0, 2, "c"), (16, 0, 3, "view0"), (65, 130, 2, "c"), (129, 64, 4, "ld")]
+CASE_TABLES["svgp_elbo_shard_sep"] = [(16, 0, 2, "c"), (16, 0, 3, "view0"), (65, 130, 2, "c"), (129, 64, 4, "ld"),
+                                      (640, 1040, 2, "c"), (640, 1040, 3, "ld")]
 # zero rows fresh / view; leaf edges with P = 2 / 4 and an odd ld
+# M = 640 (input dimension SEP_D_LARGE, so that kappa(Kuu) keeps the derived bound meaningful): the batched factorisation on its own
+# streams -- two extra-row column groups of 256 and a ragged third (128), each through the fused batched in-group solve (rows >= 1024;
+# the driver lays the trapezoids out itself, with an even ld and batch stride whatever the layout of the minibatch rows, so the odd-ld
+# row takes that solve too and differs in how Xb / Yb are read); late work (tril(q_sqrt)^T, the KL term) on the rest-update stream
+SEP_D_LARGE = 8
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("M,rows,P,layout", CASE_TABLES["svgp_elbo_shard_sep"])
 def test_svgp_elbo_shard_sep_contract(gpu, M, rows, P, layout):
     rng = np.random.default_rng(M + rows)
-    Z, X, Y, q_mu, qs = _svgp_inputs(rng, M, rows, 2, P, False)
+    Z, X, Y, q_mu, qs = _svgp_inputs(rng, M, rows, SEP_D_LARGE if M >= 640 else 2, P, False)
     kw = dict(variances=list(1.0 + 0.1 * np.arange(P)), lengthscales=list(0.8 + 0.1 * np.arange(P)),
               families=["SquaredExponential", "Matern32", "Matern52", "Matern12"][:P], noise_variance=0.3, jitter=1e-6)
     res = {}

@@ -70,6 +70,10 @@ POTRF_ROWS = [
     # batched ride
     Row(130, 7, 3, False, ("c", "bpad", "bodd"),
         dict(path="ride", ends=[], prog=[], tiled=0, flags=1, splits=1, split_rem=0, tile64=0, cap=320, R=137)),
+    # batched ride whose second strip waits in-kernel with 4 x 57 = 228 workgroups: capped at the 224 compute units of the bulk
+    # stream's mask (56 per problem), so one workgroup per problem walks two row blocks (tests/test_potrf_schedule.py, assertion 7)
+    Row(1152, 8, 4, True, ("c",),
+        dict(path="ride", ends=[], prog=[], tiled=0, flags=8, splits=8, split_rem=6, tile64=0, cap=320, R=1160)),
     # gpk_potrf_inv: the identity rows are written by the call (set_identity with lda != n) and shorten the groups' row ranges
     Row(640, 1024, 1, False, ("pad", "ld"),
         dict(path="X", xstream="X", ends=[384, 640], prog=[], tiled=0, flags=4, splits=4, split_rem=2, tile64=0), identity=True),
