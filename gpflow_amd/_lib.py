@@ -60,6 +60,9 @@ _SIGS = {
                                         c_size_t]),
     "gpk_likelihood_varexp_sum": (c_int, [c_void_p, c_int, C.POINTER(c_double), _dp, c_long, _dp, c_int, c_int, _dp, c_int, _dp,
                                           C.POINTER(c_double), c_int, c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_size_t]),
+    "gpk_mixed_varexp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gpk_mixed_gaussian_varexp_sum": (c_int, [c_void_p, _dp, c_long, _dp, c_int, c_int, c_int, C.POINTER(c_double), _dp, c_int, _dp,
+                                              C.POINTER(c_double), c_int, c_double, c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_size_t]),
     "gpk_gauss_hermite": (c_int, [c_int, C.POINTER(c_double), C.POINTER(c_double)]),
     "gpk_gauss_kl_white": (c_int, [c_void_p, _dp, _dp, c_int, c_int, c_int, _dp, _dp, c_size_t]),
     "gpk_sum_log_diag": (c_int, [c_void_p, _dp, c_int, c_long, c_int, c_long, _dp]),
@@ -79,6 +82,10 @@ _SIGS = {
     "gpk_svgp_elbo_shard_sep": (c_int, [c_void_p, C.POINTER(c_int), _dp, c_int, c_long, c_long, _dp, _dp, c_int, c_long, c_long,
                                         c_int, c_int, C.POINTER(c_double), c_int, C.POINTER(c_double), c_double, _dp, c_double,
                                         c_double, _dp, _dp, _dp, _dp, _dp, c_size_t]),
+    "gpk_svgp_elbo_lcm_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "gpk_svgp_elbo_shard_lcm": (c_int, [c_void_p, C.POINTER(c_int), _dp, c_int, c_long, c_long, _dp, _dp, c_int, c_long, c_long,
+                                        c_int, c_int, c_int, C.POINTER(c_double), C.POINTER(c_double), c_int, C.POINTER(c_double),
+                                        c_double, c_double, c_double, _dp, _dp, _dp, _dp, _dp, c_size_t]),
     "gpk_moment_rows": (c_int, [c_void_p, _dp, c_long, c_int, c_int, _dp, c_long]),
     "gpk_stationary_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, c_int, _dp, c_double, c_int, _dp, _dp, c_long,
                                             _dp, c_int, c_double]),

@@ -179,6 +179,25 @@ def expand_independent_outputs(fvar: torch.Tensor, full_cov: bool, full_output_c
     return fvar
 
 
+def mix_latent_gp(W: torch.Tensor, g_mean: torch.Tensor, g_var: torch.Tensor, full_cov: bool, full_output_cov: bool):
+    """gpflow/conditionals/util.py:242-300: moments of f = W g from those of the L independent latents g.  W [P, L],
+    g_mean [..., N, L]; g_var [..., N, L], or [..., L, N, N] with full_cov.  f_mean [..., N, P] = g_mean W^T and f_var
+      [..., N, P]        g_var (W^2)^T
+      [..., N, P, P]     W diag(g_var_n) W^T                 (full_output_cov)
+      [..., P, N, N]     sum_l W_pl^2 g_var_l                (full_cov)
+      [..., N, P, N, P]  sum_l W_pl W_ql g_var_l[n, m]       (both)"""
+    f_mean = g_mean @ W.t()
+    if full_cov and full_output_cov:
+        f_var = torch.einsum("...lnm,pl,ql->...npmq", g_var, W, W)
+    elif full_cov:
+        f_var = torch.einsum("...lnm,pl->...pnm", g_var, W ** 2)
+    elif full_output_cov:
+        f_var = torch.einsum("...nl,pl,ql->...npq", g_var, W, W)
+    else:
+        f_var = g_var @ (W ** 2).t()
+    return f_mean, f_var
+
+
 def separate_independent_conditional_implementation(Kmns, Kmms, Knns, f, *, full_cov: bool = False,
                                                     q_sqrt=None, white: bool = False):
     """gpflow/conditionals/util.py:566-629: P independent GPs.  The reference loops with tf.map_fn;

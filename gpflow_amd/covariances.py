@@ -8,14 +8,14 @@ import torch
 from . import ops
 from .inducing_variables import (InducingPoints, SeparateIndependentInducingVariables,
                                  SharedIndependentInducingVariables)
-from .kernels import Kernel, MultioutputKernel, SeparateIndependent, SharedIndependent
+from .kernels import Kernel, LinearCoregionalization, MultioutputKernel, SeparateIndependent, SharedIndependent
 
 
 def _pairs(inducing_variable, kernel):
     """(Z tensor, latent kernel) per latent GP for the Separate* combinations
     (multioutput/kuus.py:65-121, kufs.py:63-115)."""
-    if isinstance(kernel, SeparateIndependent):
-        ks = list(kernel.kernels)
+    if isinstance(kernel, (SeparateIndependent, LinearCoregionalization)):   # (the latter: Kuu / Kuf of its L LATENT GPs)
+        ks = list(kernel.latent_kernels)
     elif isinstance(kernel, SharedIndependent):
         ks = None
     else:

@@ -1,6 +1,7 @@
 // Host-side orchestration (no device code here) of everything that CALLS the factorisation (potrf.hip, gpk_potrf_core): the
 // projection onto q_sqrt and the fused model drivers -- GPR.log_marginal_likelihood, one shard of SVGP.elbo in its three forms
-// (whitened; un-whitened with a full or a diagonal q_sqrt), and the shard with separate kernels per latent.  The forms are
+// (whitened; un-whitened with a full or a diagonal q_sqrt), and the shard with separate kernels per latent, whose latents stay
+// independent (SeparateIndependent) or are mixed into the outputs (LinearCoregionalization).  The forms are
 // built from the same named pieces; WHICH kernel goes on which stream in which order is measured schedule and differs per form.
 #include "gpk_internal.h"
 
@@ -466,26 +467,25 @@ extern "C" size_t gpk_svgp_elbo_sep_workspace_bytes(int m, int rows, int d, int 
 // Python mirror the same step issues ~50 launches with host gaps between them (profiles/r04_c5sep_timeline_composed.txt).
 // (Measured and not kept: the extra rows solved out of place against EXPLICIT 512-column group inverses -- nine short launches
 // for the inverses + one triangular-K GEMM per group instead of the fused in-group kernel: 2.15 / 2.16 against 2.14 ms.)
-extern "C" int gpk_svgp_elbo_shard_sep(void* stream, const int* family_host, const double* Z, int m, long ldz, long strideZ,
-                                       const double* Xb, const double* Yb, int rows, long ldxb, long ldyb, int d, int P,
-                                       const double* ls_host, int ard, const double* variance_host, double noise_variance,
-                                       const double* noise_rows, double jitter, double mean_const, const double* q_mu,
-                                       const double* q_sqrt, double* out,
-                                       int* info, void* ws, size_t ws_bytes) {
-  if (!family_host || !Z || (rows > 0 && (!Xb || !Yb)) || !q_mu || !q_sqrt || !ls_host || !variance_host || !out || !info || m <= 0 || rows < 0 ||
-      P <= 0 || P > 16 || d <= 0 || strideZ < 0)
+// The body behind gpk_svgp_elbo_shard_sep and gpk_svgp_elbo_shard_lcm: a.P latents; `tail` is the one stage that differs -- what
+// turns the latent moments (w.fmean [rows, P], w.s0 / w.ssq [P, rows], the kernel variances) into out[0].
+namespace {
+typedef int (*SepTailFn)(hipStream_t, const ElboArgs&, const ElboWs&, const double* variance_host, const void* ctx);
+int elbo_shard_separate(void* stream, const ElboArgs& a, const int* family_host, long strideZ, const double* variance_host,
+                        SepTailFn tail, const void* ctx, void* ws, size_t ws_bytes) {
+  const int m = a.m, rows = a.rows, P = a.P, d = a.k.d;
+  if (!family_host || !a.Z || (rows > 0 && (!a.Xb || !a.Yb)) || !a.q_mu || !a.q_sqrt || !a.k.ls_host || !variance_host || !a.out ||
+      !a.info || m <= 0 || rows < 0 || P <= 0 || P > 16 || d <= 0 || strideZ < 0)
     return GPK_E_ARG;
   const ElboWs w = elbo_sep_layout(ws, m, rows, P);
   if (!ws || ws_bytes < w.total) return GPK_E_WORKSPACE;
-  const ElboArgs a{{0, d, ls_host, ard, 0.0}, Z, m, ldz, Xb, Yb, rows, ldxb, ldyb, P, q_mu, q_sqrt, 0,
-                   noise_variance, noise_rows, jitter, mean_const, out, info};
   hipStream_t s = (hipStream_t)stream;
-  const int nls = ard ? d : 1;
+  const int nls = a.k.ard ? d : 1;
   // latent p: its kernel, its inducing points, its trapezoid
   auto each_latent = [&](BuildFn build, hipStream_t st, double* T0) -> int {
     for (int p = 0; p < P; ++p) {
-      const KernelDesc kp{family_host[p], d, ls_host + (long)p * nls, ard, variance_host[p]};
-      const int r = build(st, kp, a, Z + (long)p * strideZ, T0 + (long)p * w.strideT, w.ld);
+      const KernelDesc kp{family_host[p], d, a.k.ls_host + (long)p * nls, a.k.ard, variance_host[p]};
+      const int r = build(st, kp, a, a.Z + (long)p * strideZ, T0 + (long)p * w.strideT, w.ld);
       if (r) return r;
     }
     return 0;
@@ -496,16 +496,60 @@ extern "C" int gpk_svgp_elbo_shard_sep(void* stream, const int* family_host, con
   hk.p_prologue = [&](hipStream_t ps) { return each_latent(build_kuu, ps, w.T); };
   hk.x_prologue = [&](hipStream_t xs) { return each_latent(build_kfu, xs, w.Kfu); };
   if (side) hk.late_work = [&a, &w](hipStream_t bs) { return transpose_q_sqrt_and_kl(bs, a, w); };
-  int rc = gpk_potrf_core(s, w.T, m, rows, w.ld, P, w.strideT, w.invd, 0, info, hk);
+  int rc = gpk_potrf_core(s, w.T, m, rows, w.ld, P, w.strideT, w.invd, 0, a.info, hk);
   if (rc) return rc;
   if (!side) {
     rc = transpose_q_sqrt_and_kl(s, a, w);
     if (rc) return rc;
   }
-  rc = gpk_launch_row_stats_sep(s, w.Kfu, w.strideT, rows, m, w.ld, q_mu, P, w.s0, w.fmean);
+  rc = gpk_launch_row_stats_sep(s, w.Kfu, w.strideT, rows, m, w.ld, a.q_mu, P, w.s0, w.fmean);
   if (rc) return rc;
   rc = gpk_project_batched(stream, w.Kfu, rows, m, w.ld, w.strideT, w.LqT, w.ld, P, w.ssq, w.proj,
                            gpk_project_workspace_bytes(rows, m, P));
   if (rc) return rc;
+  return tail(s, a, w, variance_host, ctx);
+}
+
+int sep_tail_independent(hipStream_t s, const ElboArgs& a, const ElboWs& w, const double* variance_host, const void*) {
   return varexp_to_out(s, a, w, variance_host, 1);
+}
+// LinearCoregionalization: the P outputs of a row read all L = a.P latents of that row (mix_latent_gp); the mean constant is
+// added after the mixing
+struct LcmTail { int P; const double* W_host; };
+int sep_tail_mixed(hipStream_t s, const ElboArgs& a, const ElboWs& w, const double* variance_host, const void* ctx) {
+  const LcmTail& t = *(const LcmTail*)ctx;
+  const LatentMoments g = gpk_latent_moments(a.Yb, a.ldyb, w.fmean, a.rows, a.P, w.s0, 1, w.ssq, variance_host, 1, a.mean_const, nullptr);
+  int count = 0;
+  GPK_TRY(gpk_launch_mixed_varexp_stage1(s, g, t.P, t.W_host, a.noise_variance, nullptr, nullptr, nullptr, w.part0, nullptr, nullptr, &count));
+  return gpk_launch_final_one(s, w.part0, count, 1.0, 0.0, a.out);
+}
+}  // namespace
+
+extern "C" int gpk_svgp_elbo_shard_sep(void* stream, const int* family_host, const double* Z, int m, long ldz, long strideZ,
+                                       const double* Xb, const double* Yb, int rows, long ldxb, long ldyb, int d, int P,
+                                       const double* ls_host, int ard, const double* variance_host, double noise_variance,
+                                       const double* noise_rows, double jitter, double mean_const, const double* q_mu,
+                                       const double* q_sqrt, double* out,
+                                       int* info, void* ws, size_t ws_bytes) {
+  const ElboArgs a{{0, d, ls_host, ard, 0.0}, Z, m, ldz, Xb, Yb, rows, ldxb, ldyb, P, q_mu, q_sqrt, 0,
+                   noise_variance, noise_rows, jitter, mean_const, out, info};
+  return elbo_shard_separate(stream, a, family_host, strideZ, variance_host, sep_tail_independent, nullptr, ws, ws_bytes);
+}
+
+// ---- fused driver: one shard of SVGP.elbo for a LinearCoregionalization kernel (L latents mixed into P outputs) -----------------
+extern "C" size_t gpk_svgp_elbo_lcm_workspace_bytes(int m, int rows, int d, int L, int P) {
+  (void)d; (void)P;   // (the mixing stage needs one set of partials, which the layout of the L latents already has)
+  return elbo_sep_layout(nullptr, m, rows, L).total;
+}
+
+extern "C" int gpk_svgp_elbo_shard_lcm(void* stream, const int* family_host, const double* Z, int m, long ldz, long strideZ,
+                                       const double* Xb, const double* Yb, int rows, long ldxb, long ldyb, int d, int L, int P,
+                                       const double* W_host, const double* ls_host, int ard, const double* variance_host,
+                                       double noise_variance, double jitter, double mean_const, const double* q_mu,
+                                       const double* q_sqrt, double* out, int* info, void* ws, size_t ws_bytes) {
+  if (!W_host || P <= 0 || P > 16 || !(noise_variance > 0.0)) return GPK_E_ARG;
+  const ElboArgs a{{0, d, ls_host, ard, 0.0}, Z, m, ldz, Xb, Yb, rows, ldxb, ldyb, L, q_mu, q_sqrt, 0,
+                   noise_variance, nullptr, jitter, mean_const, out, info};
+  const LcmTail t{P, W_host};
+  return elbo_shard_separate(stream, a, family_host, strideZ, variance_host, sep_tail_mixed, &t, ws, ws_bytes);
 }

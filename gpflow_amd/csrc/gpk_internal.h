@@ -131,6 +131,13 @@ int gpk_launch_varexp_stage1(hipStream_t s, const LatentMoments& m, double noise
 // (ticket counter) sums the partials in index order into out[0].  *ticket must be 0 at entry and is left at the block count.
 int gpk_launch_varexp_tail(hipStream_t s, const LatentMoments& m, const double* slot, int nt, long strideSlot, double noise,
                            const double* noise_rows, double* part, int* ticket, double* out);
+// the mixed Gaussian stage of gpk_mixed_gaussian_varexp_sum: `g` describes the L = g.P latents (g.fmean = gmean, g.mean_const is
+// added AFTER the mixing), W_host [P, L].  part0 receives `count` partials of sum VE; part1 (sum dVE/ds2) and partW (`count`
+// partials [P L] of dW, block after block) may be null.  The caller has checked L, P and the noise.
+// (weak: tests/potrf_schedule_run.cpp links drivers.hip against its own stubs of the launchers, one per kernel it restates; a
+//  launcher without a stub there is only reached by a driver that runner does not call, and must not keep it from linking)
+__attribute__((weak)) int gpk_launch_mixed_varexp_stage1(hipStream_t s, const LatentMoments& g, int P, const double* W_host, double noise, double* fmean_out,
+                                   double* fvar_out, double* dgmu_out, double* part0, double* part1, double* partW, int* count);
 // the quadrature stage of gpk_likelihood_varexp_sum; part1 (partials of sum dVE/dscale) may be null
 int gpk_likelihood_check(int lik, const double* params, int P);   // 0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters, classes)
 int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const LatentMoments& m, double* rows_out,

@@ -1,5 +1,6 @@
 // The variational-expectation stage of an ELBO shard: Gaussian in closed form (varexp_kernel), scalar likelihoods by Gauss-Hermite
-// quadrature (lik_varexp_kernel), MultiClass / RobustMax (lik_multiclass_kernel).  Stage 1 of the two-stage reductions of reduce.hip.
+// quadrature (lik_varexp_kernel), MultiClass / RobustMax (lik_multiclass_kernel), Gaussian on linearly mixed latents
+// (mixed_varexp_kernel: LinearCoregionalization).  Stage 1 of the two-stage reductions of reduce.hip.
 #include "reduce_device.h"
 
 namespace {
@@ -312,6 +313,110 @@ __global__ __launch_bounds__(RB) void lik_multiclass_kernel(LikVarexpArgs a) {
   }
 }
 
+// ---- Gaussian variational expectations of linearly mixed latents, stage 1 (kernels/multioutput/kernels.py LinearCoregionalization,
+// conditionals/util.py mix_latent_gp, then likelihoods/scalar_continuous.py Gaussian._variational_expectations) -----------------
+//   f[b,p] = sum_l W[p,l] gmean[b,l] + mean_const,  fvar[b,p] = sum_l W[p,l]^2 gvar[b,l],  gvar = knn - s0 + ssq (latent_var)
+// and the adjoints of sum VE w.r.t. gmean and W (include/gpk.h).  GW = max(L, P) adjacent lanes share a row: lane j of the group
+// is latent j (j < L) AND output j (j < P), so the loads of gmean, s0 / ssq and Y of a wave pass are floor(64 / GW) whole rows,
+// contiguous.  The P outputs read all L latents of their row and the L latents all P residuals: fixed-order shuffle loops inside
+// the wave (l = 0, 1, ... and p = 0, 1, ...), as in lik_multiclass_kernel.  dW: lane (row group, p) keeps L running sums over its
+// rows; at the end the row groups of a wave are summed in group order, the waves in wave order (LDS), one [P L] partial per block.
+struct MixedVarexpArgs {
+  LatentMoments g;    // the L = g.P latents: gmean = g.fmean, Y / ldy the P outputs', g.mean_const added after the mixing
+  int P;
+  double noise;
+  double W[256];      // [P, L] row-major
+  double *fmean_out, *fvar_out, *dgmu_out;
+  double *part0, *part1, *partW;   // stage-1 partials of sum VE, of sum dVE/ds2 (may be null), of dW [blocks][P L] (may be null)
+};
+__host__ __device__ constexpr int mixed_rows_per_pass(int L, int P) { return 64 / (L > P ? L : P); }
+
+__global__ __launch_bounds__(RB) void mixed_varexp_kernel(MixedVarexpArgs a) {
+  __shared__ double sh[4];
+  __shared__ double sW[256];
+  __shared__ double sAcc[RB / 64][256];
+  const LatentMoments& g = a.g;
+  const int L = g.P, P = a.P, GW = L > P ? L : P;
+  for (int i = threadIdx.x; i < P * L; i += RB) sW[i] = a.W[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int rpw = mixed_rows_per_pass(L, P), jr = lane / GW, j = lane - jr * GW;
+  const int row_lane0 = (jr * GW) & 63;           // lane of the row's first latent / output
+  const bool isl = j < L, isp = j < P;
+  const int wrow = (isp ? j : 0) * L, wcol = isl ? j : 0;   // this lane's row and column of W
+  const long npass = ((long)g.rows + rpw - 1) / rpw;
+  const double c0 = -0.5 * 1.8378770664093453 - 0.5 * log(a.noise);
+  double acc0 = 0.0, acc1 = 0.0;
+  double accW[16];
+#pragma unroll
+  for (int l = 0; l < 16; ++l) accW[l] = 0.0;
+  for (long u = (long)blockIdx.x * (RB / 64) + w; u < npass; u += (long)gridDim.x * (RB / 64)) {
+    const long b = u * rpw + jr;
+    const bool act = jr < rpw && b < g.rows;   // (an idle lane runs on harmless values and is masked below)
+    double gm = 0.0, gv = 0.0, y = 0.0;
+    if (act && isl) { gv = latent_var(g, b, j); gm = g.fmean[b * L + j]; }
+    if (act && isp) y = g.Y[b * g.ldy + j];
+    double f = 0.0, fv = 0.0;
+    for (int l = 0; l < L; ++l) {   // the row's L latents sit in adjacent lanes of this wave: summed in the order l = 0, 1, ...
+      const double wl = sW[wrow + l];
+      f += wl * __shfl(gm, (row_lane0 + l) & 63);
+      fv += (wl * wl) * __shfl(gv, (row_lane0 + l) & 63);
+    }
+    f += g.mean_const;
+    const double dy = y - f;
+    double dg = 0.0;
+    for (int p = 0; p < P; ++p) dg += sW[p * L + wcol] * __shfl(dy, (row_lane0 + p) & 63);   // (p = 0, 1, ...)
+    dg /= a.noise;
+    if (a.partW) {   // (kernel argument: uniform)
+#pragma unroll
+      for (int l = 0; l < 16; ++l) {
+        if (l < L) {
+          const double t = dy * __shfl(gm, (row_lane0 + l) & 63) - sW[wrow + l] * __shfl(gv, (row_lane0 + l) & 63);
+          if (act && isp) accW[l] += t;
+        }
+      }
+    }
+    if (act && isp) {
+      const long e = b * P + j;
+      const double q = dy * dy + fv;
+      acc0 += c0 - 0.5 * q / a.noise;
+      acc1 += -0.5 / a.noise + 0.5 * q / (a.noise * a.noise);
+      if (a.fmean_out) a.fmean_out[e] = f;
+      if (a.fvar_out) a.fvar_out[e] = fv;
+    }
+    if (act && isl && a.dgmu_out) a.dgmu_out[b * L + j] = dg;
+  }
+  const double r0 = block_sum(acc0, sh);
+  if (threadIdx.x == 0) a.part0[blockIdx.x] = r0;
+  if (a.part1) {
+    const double r1 = block_sum(acc1, sh);
+    if (threadIdx.x == 0) a.part1[blockIdx.x] = r1;
+  }
+  if (a.partW) {
+#pragma unroll
+    for (int l = 0; l < 16; ++l) {
+      if (l < L) {
+        double s = 0.0;
+        for (int r = 0; r < rpw; ++r) s += __shfl(accW[l], r * GW + j);   // the wave's row groups, in group order
+        if (jr == 0 && isp) sAcc[w][j * L + l] = s;
+      }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < P * L; i += RB) {
+      double s = 0.0;
+      for (int k = 0; k < RB / 64; ++k) s += sAcc[k][i];                  // the waves, in wave order
+      a.partW[(long)blockIdx.x * (P * L) + i] = s / a.noise;
+    }
+  }
+}
+
+// stage-1 blocks of the mixed stage: RB / 64 wave passes of mixed_rows_per_pass rows per block and grid-stride round
+int mixed_blocks(int rows, int L, int P) {
+  const int rpw = mixed_rows_per_pass(L, P);
+  long nb = (((long)rows + rpw - 1) / rpw + RB / 64 - 1) / (RB / 64);
+  return (int)(nb < 1 ? 1 : (nb > GPK_REDUCE_MAXPART ? GPK_REDUCE_MAXPART : nb));
+}
+
 }  // namespace
 
 LatentMoments gpk_latent_moments(const double* Y, long ldy, const double* fmean, int rows, int P, const double* s0, int s0_per_latent,
@@ -353,6 +458,49 @@ extern "C" int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, 
   int nb = 0;
   GPK_TRY(gpk_launch_varexp_stage1((hipStream_t)stream, m, noise_variance, noise_rows, (double*)ws, &nb));
   return gpk_launch_final_one((hipStream_t)stream, (double*)ws, nb, 1.0, 0.0, out);
+}
+
+int gpk_launch_mixed_varexp_stage1(hipStream_t s, const LatentMoments& g, int P, const double* W_host, double noise, double* fmean_out,
+                                   double* fvar_out, double* dgmu_out, double* part0, double* part1, double* partW, int* count) {
+  MixedVarexpArgs a{};
+  a.g = g; a.P = P; a.noise = noise;
+  for (int i = 0; i < P * g.P; ++i) a.W[i] = W_host[i];
+  a.fmean_out = fmean_out; a.fvar_out = fvar_out; a.dgmu_out = dgmu_out;
+  a.part0 = part0; a.part1 = part1; a.partW = partW;
+  const int nb = mixed_blocks(g.rows, g.P, P);
+  hipLaunchKernelGGL(mixed_varexp_kernel, dim3(nb), dim3(RB), 0, s, a);
+  GPK_LAUNCH_CHECK();
+  *count = nb;
+  return 0;
+}
+
+extern "C" size_t gpk_mixed_varexp_workspace_bytes(int rows, int L, int P) {
+  const size_t parts = (size_t)2 * GPK_REDUCE_MAXPART * sizeof(double);
+  if (rows < 0 || L < 1 || L > 16 || P < 1 || P > 16) return parts;
+  return parts + (size_t)mixed_blocks(rows, L, P) * P * L * sizeof(double);
+}
+
+extern "C" int gpk_mixed_gaussian_varexp_sum(void* stream, const double* Y, long ldy, const double* gmean, int rows, int L, int P,
+                                             const double* W_host, const double* s0, int s0_per_latent, const double* ssq,
+                                             const double* knn_host, int knn_per_latent, double noise_variance, double mean_const,
+                                             double* fmean_out, double* fvar_out, double* dgmu_out, double* dW_out, double* out,
+                                             void* ws, size_t ws_bytes) {
+  if ((rows > 0 && (!Y || !gmean)) || !W_host || !knn_host || !out || L <= 0 || L > 16 || P <= 0 || P > 16 || rows < 0 ||
+      !(noise_variance > 0.0))
+    return GPK_E_ARG;
+  if (!ws || ws_bytes < gpk_mixed_varexp_workspace_bytes(rows, L, P)) return GPK_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const LatentMoments g = gpk_latent_moments(Y, ldy, gmean, rows, L, s0, s0_per_latent, ssq, knn_host, knn_per_latent, mean_const, nullptr);
+  double* part = (double*)ws;
+  double* partW = part + 2 * GPK_REDUCE_MAXPART;
+  int nb = 0;
+  GPK_TRY(gpk_launch_mixed_varexp_stage1(s, g, P, W_host, noise_variance, fmean_out, fvar_out, dgmu_out, part,
+                                         part + GPK_REDUCE_MAXPART, dW_out ? partW : nullptr, &nb));
+  GPK_TRY(gpk_launch_final_one(s, part, nb, 1.0, 0.0, out));
+  GPK_TRY(gpk_launch_final_one(s, part + GPK_REDUCE_MAXPART, nb, 1.0, 0.0, out + 1));
+  if (!dW_out) return 0;
+  // dW = the blocks' [P L] partials summed in block order
+  return gpk_combine_parts(stream, partW, nb, (long)P * L, 1, P * L, (long)P * L, 1.0, 0, 1.0, dW_out, (long)P * L);
 }
 
 extern "C" int gpk_gauss_hermite(int n, double* x_host, double* w_host) {

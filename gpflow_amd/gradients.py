@@ -367,15 +367,19 @@ class _Seed:
       a vector [B]      Gaussian, one noise variance per row (heteroskedastic, round 5): a row scaling of the factors the scalar
                         multiplied (elementwise glue on [B, M] arrays);
       a matrix [B, P]   a quadrature likelihood (Bernoulli, Poisson, StudentT; `lik_grads` = the kernel's dmu, dvar): the per-row form
-                        with W_p scaled by its own column, and sum_p c_bp where that form has P c_b.
+                        with W_p scaled by its own column, and sum_p c_bp where that form has P c_b;
+      given (r, c)      a later stage mixes the latents (LinearCoregionalization): r [B, P] and the scalar c arrive ready-made, already
+                        carrying `scale` -- the scalar form with nothing derived from Yb.
     The methods are the places where c enters the two SVGP passes; each issues the calls of the form it holds, so the passes read as
     their derivation and the scalar path costs what it cost."""
 
-    def __init__(self, Yb, fmean, *, scale, mean_const, noise_variance=None, lik_grads=None):
+    def __init__(self, Yb, fmean, *, scale, mean_const, noise_variance=None, lik_grads=None, given=None):
         self.B, self.P = fmean.shape
         self.scale, self.nv = scale, noise_variance
         self.Yb, self.fmean, self.mean_const = Yb, fmean, mean_const
-        if lik_grads is not None:
+        if given is not None:
+            self.r, self.c = given[0], float(given[1])
+        elif lik_grads is not None:
             self.r = lik_grads[0].mul_(scale)                                           # dF/dfmean [B, P]
             self.c = lik_grads[1].mul_(scale)                                           # dF/dfvar  [B, P]
         elif torch.is_tensor(noise_variance) and noise_variance.dim() >= 1:
@@ -588,8 +592,8 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
 
     # ---------------------------------------------------------------- forward (intermediates kept)
-    L, At, LinvT, info = _factorise(spec, Z, Xb, jitter)
-    s0, fmean, ssq, Lq, LqT, W = _project(At, q_mu, q_sqrt)
+    fwd = _svgp_forward(spec, Z, Xb, q_mu, q_sqrt, jitter)
+    s0, fmean, ssq = fwd.s0, fwd.fmean, fwd.ssq
     if likelihood is not None:
         lik_out, _, dmu, dvar, _ = ops.likelihood_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], lik=likelihood[0],
                                                              params=likelihood[1], mean_const=mean_const, want_grads=True)
@@ -603,6 +607,38 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     # ---------------------------------------------------------------- backward
     seed = _Seed(Yb, fmean, scale=scale, mean_const=mean_const, noise_variance=noise_variance,
                  lik_grads=(dmu, dvar) if likelihood is not None else None)
+    g_var, g_ls, Zbar, g_qmu, g_qs = _svgp_backward(spec, Z, Xb, q_mu, q_sqrt, fwd, seed, kl_weight)
+    grads = {"variance": g_var, "lengthscales": g_ls}
+    if likelihood is None:
+        grads["noise_variance"] = seed.noise_grad(ve, s0, ssq, spec.kdiag())
+    grads.update({"Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": seed.r.sum().reshape(1)})
+    if likelihood is not None and likelihood[0] == "student_t":
+        grads["likelihood_scale"] = lik_out[1:2] * scale
+    return F, grads, fwd.info
+
+
+class _SvgpForward:
+    """What the whitened forward keeps for its backward: Lm, At = Kfu Lm^-T, Lm^-T, info (_factorise) and s0, fmean, ssq, Lq, LqT, W
+    (_project)."""
+
+    def __init__(self, factors, stats):
+        self.L, self.At, self.LinvT, self.info = factors
+        self.s0, self.fmean, self.ssq, self.Lq, self.LqT, self.W = stats
+
+
+def _svgp_forward(spec: KernelSpec, Z, Xb, q_mu, q_sqrt, jitter) -> _SvgpForward:
+    """the part of the whitened forward in front of the likelihood: factorisation and the rows' statistics under q(u)"""
+    factors = _factorise(spec, Z, Xb, jitter)
+    return _SvgpForward(factors, _project(factors[1], q_mu, q_sqrt))
+
+
+def _svgp_backward(spec: KernelSpec, Z, Xb, q_mu, q_sqrt, fwd: _SvgpForward, seed: _Seed, kl_weight: float):
+    """The whitened reverse pass from the seeds (r = dF/dfmean, c = dF/dfvar: _Seed) of the data term and -kl_weight KL to
+    (d/dvariance, d/dlengthscales, Z_bar, q_mu_bar, q_sqrt_bar).  A stage between the latent moments and the likelihood (the mixing
+    of a LinearCoregionalization model) only changes the seed: svgp_elbo_and_grad_lcm runs this once per latent."""
+    P = q_mu.shape[1]
+    q_diag = q_sqrt.dim() == 2
+    L, At, LinvT, Lq, W = fwd.L, fwd.At, fwd.LinvT, fwd.Lq, fwd.W
     r = seed.r
     plain = not q_diag and seed.scalar and P <= 16
     # (plain: r q_mu^T - 2 c P At in ONE pass over At; it was a K = P GEMM, then an axpy pass behind the products below)
@@ -640,13 +676,52 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
         g_var, g_ls, Zbar = _covariance_tail(spec, Z, Xb, Kuf_bar, LT, LinvT, Lbar, seed.csum(), packed=one_kernel,
                                              before_products=branch.release)
     g_qmu, g_qs = branch.results
-    grads = {"variance": g_var, "lengthscales": g_ls}
-    if likelihood is None:
-        grads["noise_variance"] = seed.noise_grad(ve, s0, ssq, spec.kdiag())
-    grads.update({"Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)})
-    if likelihood is not None and likelihood[0] == "student_t":
-        grads["likelihood_scale"] = lik_out[1:2] * scale
-    return F, grads, info
+    return g_var, g_ls, Zbar, g_qmu, g_qs
+
+
+def svgp_elbo_and_grad_lcm(Zs, Xs, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor, W, *, kernel_specs,
+                           noise_variance: float, jitter: float, scale: float = 1.0, mean_const: float = 0.0,
+                           kl_weight: float = 1.0):
+    """svgp_elbo_and_grad for a LinearCoregionalization model: L latent GPs (latent l: kernel_specs[l] over Zs[l] [M, D_l] and the
+    minibatch as its kernel sees it, Xs[l]) mixed into the P columns of Yb by W [P, L] (host array), f = W g + mean_const; whitened,
+    q_mu [M, L], full q_sqrt [L, M, M], Gaussian likelihood with one noise variance.
+
+    The seeds of latent l depend on the forward of EVERY latent, so the pass has three phases: the per-latent forwards (intermediates
+    kept), ONE mixing stage (ops.mixed_gaussian_varexp_sum: F's data term, dF/dgmean, dF/dW, dF/ds2), then the per-latent backward of
+    svgp_elbo_and_grad seeded with r_l = scale dgmu[:, l] and the scalar c_l = -scale sum_p W_pl^2 / (2 s2).
+    Returns (F [1], grads, infos): grads["latents"] is the list of per-latent {"variance", "lengthscales", "Z", "q_mu" [M, 1], "q_sqrt"
+    [1, M, M]}; "W" [P, L], "noise_variance" [1] and "mean_const" [1] belong to the mixing stage."""
+    W = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
+    Lnum = len(kernel_specs)
+    M = q_mu.shape[0]
+    if W.ndim != 2 or W.shape[1] != Lnum or q_mu.shape[1] != Lnum or tuple(q_sqrt.shape) != (Lnum, M, M):
+        raise ValueError("svgp_elbo_and_grad_lcm needs W [P, L], q_mu [M, L] and a full q_sqrt [L, M, M] for its L kernel_specs")
+    for spec, Z in zip(kernel_specs, Zs):
+        spec.warm(Z.device, Z.shape[1])
+    # ---------------------------------------------------------------- phase 1: the latents' forwards
+    cols = [(q_mu[:, l:l + 1].contiguous(), q_sqrt[l:l + 1].contiguous()) for l in range(Lnum)]
+    fwds = [_svgp_forward(kernel_specs[l], Zs[l], Xs[l], *cols[l], jitter) for l in range(Lnum)]
+    gmean = torch.cat([f.fmean for f in fwds], dim=1)                                   # [B, L]
+    s0, ssq = torch.stack([f.s0 for f in fwds]), torch.cat([f.ssq for f in fwds])       # [L, B]
+    # ---------------------------------------------------------------- phase 2: the mixing stage
+    out, fmean, _, dgmu, dW = ops.mixed_gaussian_varexp_sum(Yb, gmean, W, s0=s0, ssq=ssq, knn=[spec.kdiag() for spec in kernel_specs],
+                                                            noise_variance=noise_variance, mean_const=mean_const,
+                                                            s0_per_latent=True, want_moments=True, want_grads=True)
+    kl = ops.gauss_kl_white(q_mu, q_sqrt)
+    F = torch.mul(out[0:1], scale).sub_(kl, alpha=kl_weight)
+    r = dgmu.mul_(scale)                                                                # dF/dgmean [B, L]
+    c = -0.5 * scale / noise_variance * (W * W).sum(0)                                  # dF/dgvar[:, l]: the same for every row
+    # ---------------------------------------------------------------- phase 3: the latents' backwards
+    latents = []
+    for l in range(Lnum):
+        seed = _Seed(Yb, fwds[l].fmean, scale=scale, mean_const=0.0, noise_variance=noise_variance,
+                     given=(r[:, l:l + 1].contiguous(), c[l]))
+        g_var, g_ls, Zbar, g_qmu, g_qs = _svgp_backward(kernel_specs[l], Zs[l], Xs[l], *cols[l], fwds[l], seed, kl_weight)
+        latents.append({"variance": g_var, "lengthscales": g_ls, "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs})
+    P = W.shape[0]
+    grads = {"latents": latents, "W": dW.mul_(scale), "noise_variance": out[1:2] * scale,
+             "mean_const": ((Yb[:, :P] - fmean).sum() * (scale / noise_variance)).reshape(1)}
+    return F, grads, torch.cat([f.info.reshape(-1) for f in fwds])
 
 
 def gpr_lml_and_grad(X: torch.Tensor, Y: torch.Tensor, *, variance: float = None, lengthscales=None, noise_variance: float,

@@ -1,11 +1,13 @@
 """Kernels on the hot path (gpflow/kernels): stationary family built by the HIP covariance builder, their sums and
-products (`+` / `*`, kernels/base.py:216-329), plus the multi-output wrappers SharedIndependent / SeparateIndependent."""
+products (`+` / `*`, kernels/base.py:216-329), plus the multi-output wrappers SharedIndependent / SeparateIndependent
+and the mixing kernel LinearCoregionalization."""
 from .base import Combination, Kernel, Product, Sum
 from .stationaries import (Stationary, IsotropicStationary, SquaredExponential, Matern12, Matern32,
                            Matern52)
-from .multioutput import MultioutputKernel, SharedIndependent, SeparateIndependent
+from .multioutput import MultioutputKernel, SharedIndependent, SeparateIndependent, LinearCoregionalization
 
 RBF = SquaredExponential  # gpflow/kernels/__init__.py:50
 
 __all__ = ["Kernel", "Combination", "Sum", "Product", "Stationary", "IsotropicStationary", "SquaredExponential", "RBF", "Matern12",
-           "Matern32", "Matern52", "MultioutputKernel", "SharedIndependent", "SeparateIndependent"]
+           "Matern32", "Matern52", "MultioutputKernel", "SharedIndependent", "SeparateIndependent",
+           "LinearCoregionalization"]

@@ -6,6 +6,7 @@ from typing import Optional, Sequence
 import torch
 
 from .. import ops
+from ..base import Parameter
 from .base import Kernel
 
 
@@ -84,3 +85,49 @@ class SeparateIndependent(MultioutputKernel):
     def K_diag(self, X, full_output_cov: bool = False):
         stacked = torch.stack([k.K_diag(X) for k in self.kernels], dim=1)  # [N, P]
         return torch.diag_embed(stacked) if full_output_cov else stacked
+
+
+class LinearCoregionalization(MultioutputKernel):
+    """The linear model of coregionalisation (kernels.py:274-340): L independent latent GPs g, one kernel each, mixed into P
+    correlated outputs f = W g; W [P, L] is a Parameter without a transform."""
+
+    def __init__(self, kernels: Sequence[Kernel], W, name: Optional[str] = None):
+        super().__init__(name=name)
+        self.kernels = list(kernels)
+        self.W = Parameter(W)  # [P, L]
+
+    @property
+    def num_latent_gps(self) -> int:
+        return len(self.kernels)
+
+    @property
+    def latent_kernels(self):
+        return tuple(self.kernels)
+
+    def mixing_host(self):
+        """W [P, L] as a host array, checked against the number of member kernels"""
+        W = self.W.numpy()
+        if W.ndim != 2 or W.shape[1] != len(self.kernels):
+            raise ValueError(f"LinearCoregionalization: W must be [P, L] with L = {len(self.kernels)} member kernels, "
+                             f"got shape {tuple(W.shape)}")
+        return W
+
+    def mixing(self) -> torch.Tensor:
+        """the same on the device"""
+        self.mixing_host()
+        return self.W.device_value()
+
+    def Kgg(self, X, X2=None):
+        return torch.stack([k.K(X, X2) for k in self.kernels], dim=0)  # [L, N, N2]
+
+    def K(self, X, X2=None, full_output_cov: bool = True):
+        Kxx, W = self.Kgg(X, X2), self.mixing()
+        if full_output_cov:
+            return torch.einsum("lnm,kl,ql->nkmq", Kxx, W, W)  # [N, P, N2, P]
+        return torch.einsum("lnm,kl,kl->knm", Kxx, W, W)  # [P, N, N2]
+
+    def K_diag(self, X, full_output_cov: bool = True):
+        Kd, W = torch.stack([k.K_diag(X) for k in self.kernels], dim=1), self.mixing()  # [N, L]
+        if full_output_cov:
+            return torch.einsum("nl,kl,ql->nkq", Kd, W, W)  # [N, P, P]
+        return Kd @ (W ** 2).t()  # [N, P]

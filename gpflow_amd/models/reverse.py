@@ -9,7 +9,7 @@ import torch
 from .. import gradients, ops
 from ..base import FillTriangular
 from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
-from ..kernels import SeparateIndependent, SharedIndependent
+from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
 from ..kernels.base import Combination, gradient_spec
 from ..kernels.stationaries import IsotropicStationary
 from ..likelihoods import Gaussian
@@ -142,8 +142,10 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
         q_sqrt -- one route per latent, and `separate` is True (also for a single member: the callers name and slice by it).
     quadrature (a Bernoulli / Poisson / StudentT / MultiClass likelihood, `likelihood=` of gradients.svgp_elbo_and_grad): whitened,
     one kernel over all input columns, at most 16 latents.  narrow (natural gradients on q(u)): one kernel over all input columns,
-    full q_sqrt, constant noise."""
+    full q_sqrt, constant noise.  A LinearCoregionalization kernel: `_lcm_routes` -- one route per latent, and its own refusals."""
     k, iv = model.kernel, model.inducing_variable
+    if isinstance(k, LinearCoregionalization):
+        return _lcm_routes(model, quadrature=quadrature, narrow=narrow)
     plain = not (quadrature or narrow)
     lik_ok = (model.whiten and model._device_likelihood()) if quadrature else _gaussian_noise(model.likelihood, not narrow)
     q_full = model.q_sqrt.numpy().ndim == 3
@@ -166,6 +168,42 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
             "kernel over all input columns and at most 16 latents, a Bernoulli / Poisson / StudentT / MultiClass likelihood; natural "
             "gradients: one kernel over all input columns, full q_sqrt, constant noise")
     return [(CovarianceRoute(kk, int(v.Z.shape[1])), v) for kk, v in pairs], float(c), separate
+
+
+def _latent_inducing_points(iv, n):
+    """the inducing variable of each of n latents: shared, or one per latent; [] where they do not fit"""
+    if isinstance(iv, SeparateIndependentInducingVariables):
+        return list(iv.inducing_variable_list) if len(iv.inducing_variable_list) == n else []
+    return [iv.inducing_variable] * n if isinstance(iv, SharedIndependentInducingVariables) else []
+
+
+def _lcm_routes(model, *, quadrature, narrow):
+    """svgp_routes for a LinearCoregionalization kernel: one route per LATENT, `separate` True.  The reverse pass of the mixing stage
+    (gradients.svgp_elbo_and_grad_lcm) covers the whitened model with a full q_sqrt, a Gaussian likelihood with a `variance`
+    Parameter, a constant mean and one SquaredExponential / Matern kernel per latent over shared or per-latent inducing points;
+    every other form is refused here by the limit it breaks."""
+    k, lik = model.kernel, model.likelihood
+    no = lambda what: NotImplementedError(f"gradients: LinearCoregionalization {what}")   # noqa: E731
+    if narrow:
+        raise no("is outside the natural gradients (one kernel over all input columns, no mixing stage)")
+    if quadrature or not isinstance(lik, Gaussian):
+        raise no("with a non-Gaussian likelihood: the quadrature likelihoods on the mixed outputs run forward only (SVGP.elbo)")
+    if lik.is_heteroskedastic or not lik.has_variance_parameter:
+        raise no("with a heteroskedastic likelihood: the mixing stage takes ONE noise variance, held as a `variance` Parameter")
+    if not model.whiten:
+        raise no("un-whitened: the reverse pass of the mixing stage is whitened only")
+    if model.q_sqrt.numpy().ndim != 3:
+        raise no("with a diagonal q_sqrt: the reverse pass of the mixing stage takes the full q_sqrt [L, M, M]")
+    c = model.mean_function.constant_value()
+    if c is None:
+        raise no("needs a constant mean")
+    ivs = _latent_inducing_points(model.inducing_variable, len(k.kernels))
+    if not ivs or not all(isinstance(v, InducingPoints) for v in ivs) or not all(_supported_stationary(kk) for kk in k.kernels):
+        raise no("needs one SquaredExponential / Matern kernel per latent over inducing points, shared or one set per latent")
+    W = k.W.numpy()
+    if W.ndim != 2 or W.shape[1] != len(k.kernels) or model.q_mu.shape[1] != len(k.kernels) or max(W.shape) > 16:
+        raise no(f"needs W [P, L] and q_mu [M, L] for its L = {len(k.kernels)} latents, at most 16 latents and 16 outputs")
+    return [(CovarianceRoute(kk, int(v.Z.shape[1])), v) for kk, v in zip(k.kernels, ivs)], float(c), True
 
 
 def regression_route(model):

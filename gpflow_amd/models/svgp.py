@@ -100,15 +100,16 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         sep = self._separate_stationary_members()
         return None if sep is None else sep + (c,)
 
-    def _separate_stationary_members(self):
-        """(member kernels, Z [m, d] | [P, m, d]) for SeparateIndependent stationary members over all input columns and
-        inducing points (shared, or one equally sized set per latent), full q_sqrt; else None."""
+    def _separate_stationary_members(self, kernel_class=None):
+        """(member kernels, Z [m, d] | [P, m, d]) for SeparateIndependent (or `kernel_class`: LinearCoregionalization, whose members
+        are its latents) stationary members over all input columns and inducing points (shared, or one equally sized set per
+        latent), full q_sqrt; else None."""
         from ..kernels import SeparateIndependent
         from ..inducing_variables import SeparateIndependentInducingVariables
         if self.q_sqrt.device_value().dim() != 3:
             return None
         k, iv = self.kernel, self.inducing_variable
-        if not isinstance(k, SeparateIndependent):
+        if not isinstance(k, kernel_class or SeparateIndependent):
             return None
         if not all(isinstance(kk, Stationary) and kk.has_default_active_dims for kk in k.kernels):
             return None
@@ -120,6 +121,35 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             if len({tuple(z.shape) for z in Zs}) == 1:
                 return k.kernels, torch.stack(Zs).contiguous()
         return None
+
+    def _check_mixing_widths(self, Y) -> None:
+        """LinearCoregionalization: W [P, L] against its L member kernels, the L columns of q_mu and the P columns of Y -- a
+        ValueError before anything touches the device"""
+        from ..kernels import LinearCoregionalization
+        if not isinstance(self.kernel, LinearCoregionalization):
+            return
+        W = self.kernel.mixing_host()
+        if W.shape[1] != self.q_mu.shape[1]:
+            raise ValueError(f"LinearCoregionalization: {W.shape[1]} latent kernels, but q_mu has {self.q_mu.shape[1]} columns "
+                             "(num_latent_gps is the number of LATENT GPs)")
+        if np.shape(Y)[-1] != W.shape[0]:
+            raise ValueError(f"LinearCoregionalization: W mixes into {W.shape[0]} outputs, Y has {np.shape(Y)[-1]} columns")
+
+    def _fused_lcm_config(self):
+        """(member kernels, Z [m, d] | [L, m, d], W [P, L], mean constant) when the ELBO shard of a LinearCoregionalization model
+        is one C-ABI call (gpk_svgp_elbo_shard_lcm): the conditions of `_fused_separate_config` on its L latents, and a CONSTANT
+        noise variance (the mixing stage has no per-row form); at most 16 latents and 16 outputs."""
+        from ..kernels import LinearCoregionalization
+        if not isinstance(self.kernel, LinearCoregionalization):
+            return None
+        W = self.kernel.mixing_host()
+        if not self.whiten or not isinstance(self.likelihood, Gaussian) or self.likelihood.is_heteroskedastic:
+            return None
+        c = self.mean_function.constant_value()
+        if c is None or max(W.shape) > 16:
+            return None
+        sep = self._separate_stationary_members(LinearCoregionalization)
+        return None if sep is None else sep + (W, c)
 
     def _unwhitened_shared_factor_config(self):
         """(stationary kernel, Z) when the un-whitened ELBO can run on ONE factorisation of Kuu: one stationary kernel
@@ -207,11 +237,23 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         ops.check_info(info)
         return torch.stack([var_exp.sum(), kl])
 
+    @staticmethod
+    def _member_hypers(kernels, d):
+        """([(family, variance, lengthscales)] per member, lengthscales [P] or [P, d]) as the per-latent shards take them"""
+        hyp = [k.hyper() for k in kernels]
+        ls = [np.atleast_1d(h[2]) for h in hyp]
+        if any(l.size > 1 for l in ls):   # mixed isotropic / ARD members: every row spelled out
+            ls = np.stack([np.broadcast_to(l, (d,)) for l in ls])
+        else:
+            ls = np.concatenate(ls)
+        return hyp, ls
+
     def elbo_terms(self, data):
         """(sum_b var_exp_b over the given rows, KL) as a 2-element device tensor -- the two pieces
         svgp.py:172-174 combines; the first is what gets all-reduced when the minibatch is sharded."""
         if isinstance(self.likelihood, MultiClass):   # (refused before anything touches the device)
             self.likelihood.check_device_classes(self.q_mu.shape[1])
+        self._check_mixing_widths(data[1])
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])
         fused = self._fused_config()
         if fused is not None:
@@ -238,19 +280,28 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         sep = self._fused_separate_config()
         if sep is not None:
             kernels, Zs, c = sep
-            hyp = [k.hyper() for k in kernels]
             P, m, d, rows = len(kernels), Zs.shape[-2], Zs.shape[-1], X.shape[0]
-            ls = [np.atleast_1d(h[2]) for h in hyp]
-            if any(l.size > 1 for l in ls):   # mixed isotropic / ARD members: every row spelled out
-                ls = np.stack([np.broadcast_to(l, (d,)) for l in ls])
-            else:
-                ls = np.concatenate(ls)
+            hyp, ls = self._member_hypers(kernels, d)
             key = ("sep", m, rows, d, P)
             if self._ws is None or self._ws[0] != key:
                 self._ws = (key, ops.svgp_elbo_sep_workspace(m, rows, d, P))
             out, info = ops.svgp_elbo_shard_sep(Zs, X.contiguous(), Y, self.q_mu.device_value(), self.q_sqrt.device_value(),
                                                 variances=[h[1] for h in hyp], lengthscales=ls, families=[h[0] for h in hyp],
                                                 noise_variance=self.likelihood.noise_for(X),
+                                                jitter=config.default_jitter(), mean_const=c, ws=self._ws[1])
+            ops.check_info(info)
+            return out
+        lcm = self._fused_lcm_config()
+        if lcm is not None:
+            kernels, Zs, W, c = lcm
+            hyp, ls = self._member_hypers(kernels, Zs.shape[-1])
+            L, m, d, rows = len(kernels), Zs.shape[-2], Zs.shape[-1], X.shape[0]
+            key = ("lcm", m, rows, d, L, W.shape[0])
+            if self._ws is None or self._ws[0] != key:
+                self._ws = (key, ops.svgp_elbo_lcm_workspace(m, rows, d, L, W.shape[0]))
+            out, info = ops.svgp_elbo_shard_lcm(Zs, X.contiguous(), Y, self.q_mu.device_value(), self.q_sqrt.device_value(), W,
+                                                variances=[h[1] for h in hyp], lengthscales=ls, families=[h[0] for h in hyp],
+                                                noise_variance=float(self.likelihood.noise_for(X)),
                                                 jitter=config.default_jitter(), mean_const=c, ws=self._ws[1])
             ops.check_info(info)
             return out
@@ -282,7 +333,9 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         not, SquaredExponential or Matern12 / 32 / 52 kernel (with `active_dims`; shared by the latents or one per latent) or a Sum /
         Product of them, Gaussian likelihood (constant or heteroskedastic noise), or -- whitened, one kernel -- a quadrature likelihood
         (Bernoulli, Poisson, StudentT, MultiClass: the reverse pass seeded per (row, latent) by the kernel's own d/dfmean, d/dfvar);
-        InducingPoints, full or diagonal q_sqrt: the scope of reverse.svgp_routes, refused before anything touches the device.
+        InducingPoints, full or diagonal q_sqrt; or a LinearCoregionalization kernel (whitened, full q_sqrt, one noise variance: the
+        per-latent passes around one mixing stage, `_elbo_and_grad_lcm`): the scope of reverse.svgp_routes, refused before anything
+        touches the device.
         For minibatch training keep the variables on the device instead: training.SVGPTrainer."""
         from .. import gradients
         from ..likelihoods import StudentT
@@ -290,7 +343,11 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         lik = self.likelihood
         quad = isinstance(lik, (ScalarLikelihood, MultiClass))
         routes, c, separate = reverse.svgp_routes(self, quadrature=quad)
+        self._check_mixing_widths(data[1])
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])
+        from ..kernels import LinearCoregionalization
+        if isinstance(self.kernel, LinearCoregionalization):
+            return self._elbo_and_grad_lcm(routes, c, X, Y)
         kw = dict(jitter=config.default_jitter(), scale=reverse.minibatch_scale(self.num_data, X.shape[0]), mean_const=c)
         if quad:
             kw.update(noise_variance=None, likelihood=(lik.device_lik, lik.device_params()))
@@ -331,6 +388,29 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         pairs = kernel_pairs + list(zgrads.values()) + (lik_pairs + q_pairs if noise_first else q_pairs + lik_pairs) \
             + reverse.mean_pairs(self.mean_function, total("mean_const"))
         return self._add_log_prior(Fv, reverse.to_unconstrained(pairs))   # (+ log prior density of the trainable parameters: model.py:56-76)
+
+    def _elbo_and_grad_lcm(self, routes, c, X, Y):
+        """`elbo_and_grad` of a LinearCoregionalization model (the scope of reverse.svgp_routes for it): the per-latent passes share
+        the mixing stage, which also carries the gradients of W, the noise variance and the mean constant."""
+        from .. import gradients
+        from . import reverse
+        lik = self.likelihood
+        ins = [route.inputs(iv.Z.device_value(), X) for route, iv in routes]
+        F, g, info = gradients.svgp_elbo_and_grad_lcm(
+            [i[0] for i in ins], [i[1] for i in ins], Y, self.q_mu.device_value(), self.q_sqrt.device_value(), self.kernel.W.numpy(),
+            kernel_specs=[route.spec for route, _ in routes], noise_variance=float(lik.noise_for(X)),
+            jitter=config.default_jitter(), scale=reverse.minibatch_scale(self.num_data, X.shape[0]), mean_const=c)
+        ops.check_info(info)
+        kernel_pairs, zgrads = [], {}
+        for (route, iv), (_, _, scatter), gl in zip(routes, ins, g["latents"]):
+            kernel_pairs += route.kernel_pairs(gl)
+            gz = scatter(gl["Z"]).cpu().numpy()
+            zgrads[id(iv.Z)] = (iv.Z, zgrads[id(iv.Z)][1] + gz if id(iv.Z) in zgrads else gz)   # shared Z: contributions add up
+        q_pairs = [(self.q_mu, torch.cat([gl["q_mu"] for gl in g["latents"]], dim=1).cpu().numpy()),
+                   (self.q_sqrt, torch.cat([gl["q_sqrt"] for gl in g["latents"]], dim=0).cpu().numpy())]
+        pairs = kernel_pairs + [(self.kernel.W, g["W"].cpu().numpy())] + list(zgrads.values()) \
+            + reverse.noise_pairs(lik, X, g["noise_variance"]) + q_pairs + reverse.mean_pairs(self.mean_function, g["mean_const"].cpu().numpy())
+        return self._add_log_prior(float(F.cpu()[0]), reverse.to_unconstrained(pairs))
 
     def posterior(self, precompute_cache=posteriors.PrecomputeCacheType.TENSOR):
         """svgp.py:210-240"""

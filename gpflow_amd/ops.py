@@ -479,6 +479,61 @@ def _lik_y_columns(lik: str, P: int) -> int:
     return 1
 
 
+def _mixing_weights(W, L: int):
+    """W [P, L] as a host array for the (W_host) argument of the C-ABI; 1 <= L, P <= 16 (include/gpk.h)."""
+    Wh = np.ascontiguousarray(W.detach().cpu().numpy() if isinstance(W, torch.Tensor) else np.asarray(W, dtype=np.float64),
+                              dtype=np.float64)
+    if Wh.ndim != 2 or Wh.shape[1] != L:
+        raise ValueError(f"W must be [P, L] with L = {L} latents, got shape {tuple(Wh.shape)}")
+    if not (1 <= L <= 16 and 1 <= Wh.shape[0] <= 16):
+        raise ValueError(f"mixing of L = {L} latents into P = {Wh.shape[0]} outputs: both must lie in [1, 16]")
+    return Wh
+
+
+def mixed_gaussian_varexp_sum(Y: torch.Tensor, gmean: torch.Tensor, W, *, s0: Optional[torch.Tensor], ssq: Optional[torch.Tensor],
+                              knn: Sequence[float], noise_variance: float, mean_const: float = 0.0, s0_per_latent: bool = False,
+                              want_moments: bool = False, want_grads: bool = False):
+    """Gaussian variational expectations of linearly mixed latents (gpk_mixed_gaussian_varexp_sum): f = gmean W^T + mean_const,
+    fvar = gvar (W^2)^T with gvar = knn - s0 + ssq over the L latents; Y [rows, P], gmean [rows, L], W [P, L] (host or device).
+    Returns (out [2], fmean | None, fvar | None, dgmu | None, dW | None): out[0] = sum over rows and outputs, out[1] = its
+    derivative w.r.t. the noise variance; fmean, fvar [rows, P] (want_moments); dgmu [rows, L] = d out[0] / d gmean and
+    dW [P, L] = d out[0] / d W (want_grads)."""
+    lib = _lib.load()
+    _chk(Y, "Y", 2)
+    _chk(gmean, "gmean", 2)
+    rows, L = gmean.shape
+    if not gmean.is_contiguous():
+        raise ValueError("gmean must be contiguous")
+    Wh = _mixing_weights(W, L)
+    P = Wh.shape[0]
+    if Y.shape[0] != rows or Y.shape[1] < P:
+        raise ValueError("Y must have one row per row of gmean and at least P columns")
+    for name, t, shape in (("s0", s0, (L, rows) if s0_per_latent else (rows,)), ("ssq", ssq, (L, rows))):
+        if t is not None:
+            _chk(t, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous {shape}")
+    if not float(noise_variance) > 0.0:
+        raise ValueError("noise_variance must be positive")
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=Y.device)
+    out = new(2)
+    fmean, fvar = (new(rows, P), new(rows, P)) if want_moments else (None, None)
+    dgmu, dW = (new(rows, L), new(P, L)) if want_grads else (None, None)
+    ws = _ws(int(lib.gpk_mixed_varexp_workspace_bytes(rows, L, P)))
+    knn = list(np.atleast_1d(np.asarray(knn, dtype=np.float64)))
+    if len(knn) not in (1, L):
+        raise ValueError(f"knn: one value, or one per latent ({L})")
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    rc = lib.gpk_mixed_gaussian_varexp_sum(_stream(), Y.data_ptr(), _rowmajor(Y, "Y"), gmean.data_ptr(), rows, L, P,
+                                           _lib.host_doubles(Wh.reshape(-1).tolist()), ptr(s0), int(s0_per_latent), ptr(ssq),
+                                           _lib.host_doubles(knn), int(len(knn) > 1), float(noise_variance), float(mean_const),
+                                           ptr(fmean), ptr(fvar), ptr(dgmu), ptr(dW), out.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+    _lib.check(rc, "gpk_mixed_gaussian_varexp_sum")
+    return out, fmean, fvar, dgmu, dW
+
+
 def gauss_hermite(n: int = 20) -> Tuple[np.ndarray, np.ndarray]:
     """(x [n], w [n]) = numpy.polynomial.hermite.hermgauss(n) as the kernels hold it (gpk_gauss_hermite; host only, n = 20)."""
     lib = _lib.load()
@@ -797,6 +852,59 @@ def svgp_elbo_shard_sep(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_m
                                      q_mu.data_ptr(), q_sqrt.data_ptr(), out.data_ptr(), info.data_ptr(), ws.data_ptr(),
                                      ws.numel() * 8)
     _lib.check(rc, "gpk_svgp_elbo_shard_sep")
+    return out, info
+
+
+def svgp_elbo_lcm_workspace(m: int, rows: int, d: int, L: int, P: int) -> torch.Tensor:
+    lib = _lib.load()
+    return _ws(int(lib.gpk_svgp_elbo_lcm_workspace_bytes(m, rows, d, L, P)))
+
+
+def svgp_elbo_shard_lcm(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor, W, *,
+                        variances, lengthscales, families, noise_variance: float, jitter: float, mean_const: float = 0.0,
+                        ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                        info: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Whitened shard of a LinearCoregionalization model: L latents with one kernel each -- Z [m, d] (shared) or [L, m, d],
+    variances [L], lengthscales [L] or [L, d], families [L], q_mu [m, L], q_sqrt [L, m, m] as svgp_elbo_shard_sep takes them --
+    mixed into the P columns of Yb by W [P, L] (host or device): f = W g + mean_const.  out[0] = sum_b var_exp_b, out[1] = KL
+    over the L latents; info [L].  Returns (out, info)."""
+    lib = _lib.load()
+    for name, t in (("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)):
+        _chk(t, name, 2)
+    _chk(Z, "Z")
+    _chk(q_sqrt, "q_sqrt", 3)
+    L = q_mu.shape[1]
+    Wh = _mixing_weights(W, L)
+    P = Wh.shape[0]
+    shared = Z.dim() == 2
+    m, d = Z.shape[-2], Z.shape[-1]
+    rows = Xb.shape[0]
+    if (not shared and (Z.dim() != 3 or Z.shape[0] != L)) or Xb.shape[1] != d or Yb.shape[0] != rows or Yb.shape[1] != P \
+            or q_mu.shape[0] != m or tuple(q_sqrt.shape) != (L, m, m) or len(families) != L:
+        raise ValueError("inconsistent shapes")
+    if not (Z.is_contiguous() and q_mu.is_contiguous() and q_sqrt.is_contiguous()):
+        raise ValueError("Z / q_mu / q_sqrt must be contiguous")
+    ls = np.asarray(lengthscales, dtype=np.float64)
+    var = np.asarray(variances, dtype=np.float64).reshape(-1)
+    if var.size != L or ls.shape[0] != L or (ls.ndim == 2 and ls.shape[1] != d) or ls.ndim > 2:
+        raise ValueError("variances / lengthscales: one entry (row) per latent")
+    if not float(noise_variance) > 0.0:
+        raise ValueError("noise_variance must be positive")
+    ard = int(ls.ndim == 2)
+    nbytes = int(lib.gpk_svgp_elbo_lcm_workspace_bytes(m, rows, d, L, P))
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _ws(nbytes)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=Xb.device)
+    if info is None:
+        info = torch.zeros(L, dtype=torch.int32, device=Xb.device)
+    fam = (_lib.C.c_int * L)(*[KERNEL_FAMILIES[f] for f in families])
+    rc = lib.gpk_svgp_elbo_shard_lcm(_stream(), fam, Z.data_ptr(), m, d, 0 if shared else m * d, Xb.data_ptr(), Yb.data_ptr(), rows,
+                                     _rowmajor(Xb, "Xb"), _rowmajor(Yb, "Yb"), d, L, P, _lib.host_doubles(Wh.reshape(-1).tolist()),
+                                     _lib.host_doubles(ls.reshape(-1).tolist()), ard, _lib.host_doubles(var.tolist()),
+                                     float(noise_variance), float(jitter), float(mean_const), q_mu.data_ptr(), q_sqrt.data_ptr(),
+                                     out.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+    _lib.check(rc, "gpk_svgp_elbo_shard_lcm")
     return out, info
 
 

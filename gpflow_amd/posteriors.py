@@ -11,11 +11,11 @@ import torch
 from . import config, covariances, ops
 from .base import Module
 from .conditionals import (Factor, base_conditional, conditional_tail, expand_independent_outputs,
-                           factor_with_rows, separate_independent_trapezoid_tail, tail_over_batches)
+                           factor_with_rows, mix_latent_gp, separate_independent_trapezoid_tail, tail_over_batches)
 from .inducing_variables import (InducingPoints, InducingVariables,
                                  SeparateIndependentInducingVariables,
                                  SharedIndependentInducingVariables)
-from .kernels import Kernel, MultioutputKernel, SeparateIndependent, SharedIndependent
+from .kernels import Kernel, LinearCoregionalization, MultioutputKernel, SeparateIndependent, SharedIndependent
 
 
 class PrecomputeCacheType(enum.Enum):
@@ -333,7 +333,7 @@ class IndependentPosterior(BasePosterior):
         separate = Kfu.dim() == 3
         # Kff carries a latent axis only for separate KERNELS; a shared kernel over separate inducing variables has
         # Kfu [L,N,M] but one Kff, broadcast over the latents (posteriors.py:794-822)
-        kff_per_latent = isinstance(self.kernel, SeparateIndependent)
+        kff_per_latent = isinstance(self.kernel, (SeparateIndependent, LinearCoregionalization))
         Lnum = Qinv.shape[0]
         if separate:
             mean = torch.stack([ops.row_stats(Kfu[l], V=alpha[l].contiguous(), want_sumsq=False)[1][:, 0] for l in range(Lnum)],
@@ -430,8 +430,25 @@ class IndependentPosteriorMultiOutput(IndependentPosterior):
         return self._post_process_mean_and_cov(fmean, fvar, full_cov, full_output_cov)
 
 
+class LinearCoregionalizationPosterior(IndependentPosteriorMultiOutput):
+    """posteriors.py:890-925: the independent-latent conditional over the member kernels of a LinearCoregionalization kernel
+    (fused, or from the precompute cache), then mix_latent_gp.  The mean function is added after the mixing (AbstractPosterior)."""
+
+    def _post_process_mean_and_cov(self, mean, cov, full_cov: bool, full_output_cov: bool):
+        return mix_latent_gp(self.kernel.mixing(), mean, cov, full_cov, full_output_cov)
+
+    def _get_Kff(self, Xnew, full_cov: bool):
+        return torch.stack([k(Xnew, full_cov=full_cov) for k in self.kernel.latent_kernels], dim=0)
+
+
 def get_posterior_class(kernel, inducing_variable) -> Type[BasePosterior]:
     """posteriors.py:1039-1086 (rows on the path; everything else is out of scope)."""
+    if isinstance(kernel, LinearCoregionalization):
+        if isinstance(inducing_variable, (SeparateIndependentInducingVariables, SharedIndependentInducingVariables)):
+            return LinearCoregionalizationPosterior
+        raise NotImplementedError(
+            "LinearCoregionalization with plain InducingPoints (FullyCorrelatedPosterior) is out of scope: wrap them in "
+            "SharedIndependentInducingVariables or SeparateIndependentInducingVariables")
     if isinstance(kernel, (SharedIndependent, SeparateIndependent)):
         if isinstance(inducing_variable, (SeparateIndependentInducingVariables,
                                           SharedIndependentInducingVariables)):

@@ -65,8 +65,11 @@ class SVGPTrainer:
         # constant and the minibatch rows; their objectives and shared gradients add up (conditionals/util.py:566-629).  The
         # covariance spec is rebuilt from the trainer's current member values every step (CovarianceRoute.spec_at).
         from .inducing_variables import SharedIndependentInducingVariables
-        from .kernels import SeparateIndependent
+        from .kernels import LinearCoregionalization, SeparateIndependent
         from .models import reverse
+        if isinstance(model.kernel, LinearCoregionalization):
+            raise NotImplementedError("the trainer does not cover LinearCoregionalization: its step has no mixing stage "
+                                      "(SVGP.elbo_and_grad with optimizers.Scipy does)")
         if isinstance(model.kernel, SeparateIndependent) and not isinstance(model.inducing_variable, SharedIndependentInducingVariables):
             raise NotImplementedError("the trainer with separate kernels per latent: shared inducing points")
         routes, c, self.separate = reverse.svgp_routes(model)

@@ -290,6 +290,37 @@ int gpk_likelihood_varexp_sum(void* stream, int lik, const double* lik_params_ho
                               const double* fmean, int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
                               const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
                               double* rows_out, double* dmu_out, double* dvar_out, double* out, void* ws, size_t ws_bytes);
+/* Gaussian variational expectations of LINEARLY MIXED latents -- the stage between the latent moments and the likelihood of a
+ * LinearCoregionalization model (kernels/multioutput/kernels.py LinearCoregionalization, conditionals/util.py mix_latent_gp):
+ * L latent GPs g, P outputs f = W g, W [P, L] row-major on the HOST, 1 <= L, P <= 16.  The latent operands are those of
+ * gpk_gaussian_varexp_sum with L in the place of P: gmean [rows, L] contiguous, s0 [rows] or [L, rows] (s0_per_latent), ssq
+ * [L, rows], either may be NULL; knn a HOST pointer, L values if knn_per_latent else 1.  Y [rows, P] with row stride ldy.
+ *   gvar[b,l] = knn - s0 + ssq                                      (in this order)
+ *   f[b,p]    = sum_l W[p,l] gmean[b,l] + mean_const                (l ascending; the constant is added AFTER the mixing)
+ *   fvar[b,p] = sum_l W[p,l]^2 gvar[b,l]
+ *   VE[b,p]   = -0.5 log 2pi - 0.5 log s2 - 0.5 ((Y[b,p] - f[b,p])^2 + fvar[b,p]) / s2,      s2 = noise_variance
+ *   out[0]    = sum_b sum_p VE[b,p]
+ *   out[1]    = d out[0] / d s2 = sum_bp ( -0.5 / s2 + 0.5 ((Y - f)^2 + fvar) / s2^2 )
+ *   dgmu[b,l] = ( sum_p W[p,l] (Y[b,p] - f[b,p]) ) / s2             (d out[0] / d gmean[b,l]; p ascending)
+ *   dW[p,l]   = ( sum_b (Y[b,p] - f[b,p]) gmean[b,l] - W[p,l] gvar[b,l] ) / s2      (d out[0] / d W[p,l]; DEVICE, [P, L])
+ * d out[0] / d gvar[b,l] = -sum_p W[p,l]^2 / (2 s2) is the same for every row and is left to the caller.
+ * fmean_out, fvar_out [rows, P], dgmu_out [rows, L] and dW_out are optional (NULL).  rows = 0 writes out = [0, 0] and dW = 0 and
+ * reads no row operand.  GPK_E_ARG: L or P outside [1, 16], W_host / knn_host / out NULL, noise_variance not > 0 (NaN included);
+ * GPK_E_WORKSPACE: ws smaller than gpk_mixed_varexp_workspace_bytes(rows, L, P).  A refused call writes nothing.
+ * fvar is not clamped: a negative gvar gives a smaller (or negative) fvar, as in the reference.
+ * Non-finite inputs: a NaN / Inf in gmean[b,:], gvar[b,:] or Y[b,p] travels through the arithmetic into out, into dW and into
+ * those of row b's fmean / fvar / dgmu entries that depend on it (gmean[b,l]: f[b,:] and dgmu[b,:]; gvar[b,l]: fvar[b,:];
+ * Y[b,p]: dgmu[b,:]; a zero weight does not shield: 0 * NaN = NaN).  It reaches no other row's per-row outputs.
+ * Deterministic: max(L, P) adjacent lanes share a row, whole rows per wave pass; the sums over l and p are fixed-order shuffle
+ * loops inside the wave; out and dW go through two-stage reductions (dW: one [P L] partial per stage-1 block, summed in block
+ * order); no floating-point atomics, no in-kernel waits. */
+size_t gpk_mixed_varexp_workspace_bytes(int rows, int L, int P);
+int gpk_mixed_gaussian_varexp_sum(void* stream, const double* Y, long ldy, const double* gmean, int rows, int L, int P,
+                                  const double* W_host, const double* s0, int s0_per_latent, const double* ssq,
+                                  const double* knn_host, int knn_per_latent, double noise_variance, double mean_const,
+                                  double* fmean_out, double* fvar_out, double* dgmu_out, double* dW_out, double* out, void* ws,
+                                  size_t ws_bytes);
+
 /* The quadrature table the kernels use: n nodes x_host and weights w_host of numpy.polynomial.hermite.hermgauss(n).  Host only
  * (no stream, no device); n = 20 is the only table: anything else returns GPK_E_UNSUPPORTED. */
 int gpk_gauss_hermite(int n, double* x_host, double* w_host);
@@ -397,6 +428,18 @@ int gpk_svgp_elbo_shard_sep(void* stream, const int* family_host, const double* 
                             const double* ls_host, int ard, const double* variance_host, double noise_variance,
                             const double* noise_rows, double jitter, double mean_const, const double* q_mu,
                             const double* q_sqrt, double* out, int* info, void* ws, size_t ws_bytes);
+
+/* The same schedule for a LinearCoregionalization model: L latent GPs (one kernel each, as above, with L in the place of P: q_mu
+ * [m, L], q_sqrt [L, m, m], info L ints) mixed into the P columns of Yb by W_host [P, L] (HOST, row-major), f = W g + mean_const.
+ * Factorisation, row statistics and projection are those of gpk_svgp_elbo_shard_sep over the L latents; the last stage is
+ * gpk_mixed_gaussian_varexp_sum's.  out[0] = the shard's sum of variational expectations, out[1] = the KL over the L latents.
+ * Whitened, full q_sqrt, constant noise variance.  1 <= L, P <= 16. */
+size_t gpk_svgp_elbo_lcm_workspace_bytes(int m, int rows, int d, int L, int P);
+int gpk_svgp_elbo_shard_lcm(void* stream, const int* family_host, const double* Z, int m, long ldz, long strideZ,
+                            const double* Xb, const double* Yb, int rows, long ldxb, long ldyb, int d, int L, int P,
+                            const double* W_host, const double* ls_host, int ard, const double* variance_host,
+                            double noise_variance, double jitter, double mean_const, const double* q_mu, const double* q_sqrt,
+                            double* out, int* info, void* ws, size_t ws_bytes);
 
 /* ---- result mailbox in mapped host memory ------------------------------------------------------------------------
  * Copies n doubles from device memory `src` (and one int from `info`, may be NULL) into `host_dst`, a buffer of PINNED,
