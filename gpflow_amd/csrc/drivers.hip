@@ -481,6 +481,9 @@ int elbo_shard_separate(void* stream, const ElboArgs& a, const int* family_host,
   if (!ws || ws_bytes < w.total) return GPK_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const int nls = a.k.ard ? d : 1;
+  // (ls_host is strided by nls: there is no room for the trailing alpha of a RationalQuadratic member, gpk.h)
+  for (int p = 0; p < P; ++p)
+    if (family_host[p] == GPK_KERN_RQ) return GPK_E_UNSUPPORTED;
   // latent p: its kernel, its inducing points, its trapezoid
   auto each_latent = [&](BuildFn build, hipStream_t st, double* T0) -> int {
     for (int p = 0; p < P; ++p) {

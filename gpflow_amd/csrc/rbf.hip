@@ -1,4 +1,5 @@
-// Covariance-matrix builder for stationary kernels (SquaredExponential + Matern family), gfx950.
+// Covariance-matrix builder for stationary kernels (SquaredExponential, Matern family, Exponential, RationalQuadratic) and the
+// static ones (White, Constant), gfx950.
 //
 // Replaces, in ONE pass over the output (the reference materialises >= 6 full N x N2 tensors):
 //   Stationary.scale            gpflow/kernels/stationaries.py:77-79      X / lengthscales
@@ -14,6 +15,7 @@
 // so rounding has the same structure (the diagonal is exp(-0.5 * ~1e-16), not exactly sigma^2).
 #include "gpk_internal.h"
 #include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -29,15 +31,23 @@ struct RbfArgs {
   int comb_diag;              // COMB: X2 is X1 and diag_add goes onto the diagonal of the combined result
   int lds_mirror;             // symmetric full build: write the mirror tile as full rows through LDS
   int nt_store;               // non-temporal stores for complete tiles
+  double alpha;               // GPK_KERN_RQ only: the trailing entry of ls_host (gpk.h)
 };
 
 constexpr int T = 64;
 
+// Static families (statics.py): no distance -- White is variance on the diagonal of K(X, X) (X2 == NULL) and 0 elsewhere, whatever the
+// values of X2; Constant is variance everywhere.  Their tiles never stage or read X.
 template <int family>
-__device__ __forceinline__ double kern_eval(double r2, double variance) {
+constexpr bool kern_static = (family == GPK_KERN_WHITE || family == GPK_KERN_CONSTANT);
+
+template <int family>
+__device__ __forceinline__ double kern_eval(double r2, double variance, double alpha) {
   if (family == GPK_KERN_SE) return variance * exp(-0.5 * r2);
+  if (family == GPK_KERN_RQ) return variance * exp(-alpha * log1p(r2 / (2.0 * alpha)));   // (1 + r2 / (2 alpha))^-alpha, on r2: no clamp
   const double r = sqrt(r2 < 1e-36 ? 1e-36 : r2);   // (not fmax: a NaN r2 has to come out as NaN, as tf.maximum gives)
   if (family == GPK_KERN_MATERN12) return variance * exp(-r);
+  if (family == GPK_KERN_EXPONENTIAL) return variance * exp(-0.5 * r);
   if (family == GPK_KERN_MATERN32) {
     const double sqrt3 = 1.7320508075688772;
     return variance * (1.0 + sqrt3 * r) * exp(-sqrt3 * r);
@@ -50,17 +60,26 @@ __device__ __forceinline__ double kern_eval(double r2, double variance) {
 // from (for the SquaredExponential it is k itself).  r = sqrt(max(r2, 1e-36)) has derivative 0 where the clamp is
 // active (stationaries.py:103-116 under TF autodiff: tf.maximum passes nothing to the clamped argument).
 template <int family>
-__device__ __forceinline__ double kern_dr2(double r2, double variance) {
+__device__ __forceinline__ double kern_dr2(double r2, double variance, double alpha) {
   if (family == GPK_KERN_SE) return variance * exp(-0.5 * r2);
+  if (family == GPK_KERN_RQ) return variance * exp(-(alpha + 1.0) * log1p(r2 / (2.0 * alpha)));
   if (r2 <= 1e-36) return 0.0;   // (a NaN r2 is not clamped: it reaches sqrt and comes out as NaN)
   const double r = sqrt(r2);
   if (family == GPK_KERN_MATERN12) return variance * exp(-r) / r;
+  if (family == GPK_KERN_EXPONENTIAL) return variance * exp(-0.5 * r) / (2.0 * r);
   if (family == GPK_KERN_MATERN32) {
     const double sqrt3 = 1.7320508075688772;
     return 3.0 * variance * exp(-sqrt3 * r);
   }
   const double sqrt5 = 2.23606797749979;
   return (5.0 / 3.0) * variance * (1.0 + sqrt5 * r) * exp(-sqrt5 * r);
+}
+
+// dk/dalpha of the RationalQuadratic: with u = r2 / (2 alpha) and k = variance exp(-alpha log1p(u)), du/dalpha = -u / alpha gives
+// k (u / (1 + u) - log1p(u)); the logarithm is the one k itself needs.
+__device__ __forceinline__ double kern_dalpha_rq(double r2, double variance, double alpha) {
+  const double u = r2 / (2.0 * alpha), l = log1p(u);
+  return variance * exp(-alpha * l) * (u / (1.0 + u) - l);
 }
 
 // MIRROR (symmetric full build): only tiles on or below the diagonal are computed; each is also written
@@ -71,7 +90,7 @@ __device__ __forceinline__ double kern_dr2(double r2, double variance) {
 // 329) and the elementwise factor of the kernel backward, without materialising the second matrix.
 // COMB = 3: out = G .* (-2 dk/dr2); with comb_diag (X2 is X1) the diagonal is written as exact zeros: r2_ii = 0 for
 // every parameter value, so it carries no gradient (autodiff of the expansion formula gets rounding noise there,
-// amplified by 1/r for Matern12).
+// amplified by 1/r for Matern12).  COMB = 4 (GPK_KERN_RQ only): out = G .* dk/dalpha, diagonal as for COMB = 3.
 template <int FAMILY, int COMB = 0>
 __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -86,61 +105,72 @@ __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
   if (p.sym && c0 > r0 + T - 1) return;  // strictly upper tile: skipped (lower_only) or written by its mirror
   const int tid = threadIdx.x;
 
-  // stage + scale (true division, as the reference) -- thread t handles (row t>>2, dims (t&3)::4)
-  for (int e = tid; e < T * d; e += 256) {
-    const int row = e / d, dd = e - row * d;
-    const double l = p.ard ? p.ls[dd] : p.ls[0];
-    const int g1 = r0 + row, g2 = c0 + row;
-    x1t[dd * T + row] = (g1 < p.n1) ? p.X1[(long)g1 * p.ldx1 + dd] / l : 0.0;
-    x2t[dd * T + row] = (g2 < p.n2) ? p.X2[(long)g2 * p.ldx2 + dd] / l : 0.0;
-  }
-  __syncthreads();
-  if (tid < 2 * T) {
-    const double* src = (tid < T) ? x1t : x2t;
-    const int row = tid & (T - 1);
-    double s = 0.0;
-    for (int dd = 0; dd < d; ++dd) {
-      const double v = src[dd * T + row];
-      s += v * v;
-    }
-    ((tid < T) ? nr1 : nr2)[row] = s;
-  }
-  __syncthreads();
-
-  const int tx = tid & 15, ty = tid >> 4;
   double dot[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dot[i][j] = 0.0;
-  for (int dd = 0; dd < d; ++dd) {
-    const d2* a2 = reinterpret_cast<const d2*>(&x1t[dd * T + ty * 4]);
-    const d2* b2 = reinterpret_cast<const d2*>(&x2t[dd * T + tx * 4]);
-    const d2 a01 = a2[0], a23 = a2[1], b01 = b2[0], b23 = b2[1];
-    const double a[4] = {a01.x, a01.y, a23.x, a23.y};
-    const double b[4] = {b01.x, b01.y, b23.x, b23.y};
+  const int tx = tid & 15, ty = tid >> 4;
+  if constexpr (!kern_static<FAMILY>) {
+    // stage + scale (true division, as the reference) -- thread t handles (row t>>2, dims (t&3)::4)
+    for (int e = tid; e < T * d; e += 256) {
+      const int row = e / d, dd = e - row * d;
+      const double l = p.ard ? p.ls[dd] : p.ls[0];
+      const int g1 = r0 + row, g2 = c0 + row;
+      x1t[dd * T + row] = (g1 < p.n1) ? p.X1[(long)g1 * p.ldx1 + dd] / l : 0.0;
+      x2t[dd * T + row] = (g2 < p.n2) ? p.X2[(long)g2 * p.ldx2 + dd] / l : 0.0;
+    }
+    __syncthreads();
+    if (tid < 2 * T) {
+      const double* src = (tid < T) ? x1t : x2t;
+      const int row = tid & (T - 1);
+      double s = 0.0;
+      for (int dd = 0; dd < d; ++dd) {
+        const double v = src[dd * T + row];
+        s += v * v;
+      }
+      ((tid < T) ? nr1 : nr2)[row] = s;
+    }
+    __syncthreads();
+
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) dot[i][j] = fma(a[i], b[j], dot[i][j]);
-  }
+      for (int j = 0; j < 4; ++j) dot[i][j] = 0.0;
+    for (int dd = 0; dd < d; ++dd) {
+      const d2* a2 = reinterpret_cast<const d2*>(&x1t[dd * T + ty * 4]);
+      const d2* b2 = reinterpret_cast<const d2*>(&x2t[dd * T + tx * 4]);
+      const d2 a01 = a2[0], a23 = a2[1], b01 = b2[0], b23 = b2[1];
+      const double a[4] = {a01.x, a01.y, a23.x, a23.y};
+      const double b[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dot[i][j] = fma(a[i], b[j], dot[i][j]);
+    }
+  }  // !kern_static
   const bool full = (r0 + T <= p.n1) && (c0 + T <= p.n2) && ((p.ldk & 1) == 0) &&
                     ((reinterpret_cast<uintptr_t>(p.K) & 15) == 0);
   double v[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int gr = r0 + ty * 4 + i;
-    const double ni = nr1[ty * 4 + i];
+    double ni = 0.0;
+    if constexpr (!kern_static<FAMILY>) ni = nr1[ty * 4 + i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int gc = c0 + tx * 4 + j;
-      const double r2 = (-2.0 * dot[i][j]) + (ni + nr2[tx * 4 + j]);
-      double k = (COMB == 3) ? kern_dr2<FAMILY>(r2, p.variance) : kern_eval<FAMILY>(r2, p.variance);
+      double k;
+      if constexpr (kern_static<FAMILY>) {
+        k = (COMB >= 3) ? 0.0
+            : (FAMILY == GPK_KERN_CONSTANT || ((p.sym || p.comb_diag) && gr == gc)) ? p.variance : 0.0;
+      } else {
+        const double r2 = (-2.0 * dot[i][j]) + (ni + nr2[tx * 4 + j]);
+        k = (COMB == 4)   ? kern_dalpha_rq(r2, p.variance, p.alpha)
+            : (COMB == 3) ? kern_dr2<FAMILY>(r2, p.variance, p.alpha)
+                          : kern_eval<FAMILY>(r2, p.variance, p.alpha);
+      }
       if (p.sym && gr == gc) k += p.diag_add;
       if constexpr (COMB != 0) {
         const double g = (gr < p.n1 && gc < p.n2) ? p.G[(long)gr * p.ldg + gc] : 0.0;
         k = (COMB == 2) ? k + g : k * g;
-        if (p.comb_diag && gr == gc) k = (COMB == 3) ? 0.0 : k + p.diag_add;
+        if (p.comb_diag && gr == gc) k = (COMB >= 3) ? 0.0 : k + p.diag_add;
       }
       v[i][j] = k;
     }
@@ -214,25 +244,41 @@ __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
 }  // namespace
 
 namespace {
+template <int FAMILY, int COMB>
+int launch_family(hipStream_t st, const RbfArgs& a, dim3 grid, size_t lds) {
+  static const int max_lds = (int)(((size_t)2 * GPK_MAX_D * T + 2 * T) * sizeof(double));
+  static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(rbf_kernel<FAMILY, COMB>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+  GPK_HIP(at);
+  hipLaunchKernelGGL((rbf_kernel<FAMILY, COMB>), grid, dim3(256), lds, st, a);
+  GPK_LAUNCH_CHECK();
+  return 0;
+}
+
 template <int COMB>
 int launch_combine(hipStream_t st, int family, const RbfArgs& a, dim3 grid, size_t lds) {
-  static const int max_lds = (int)(((size_t)2 * GPK_MAX_D * T + 2 * T) * sizeof(double));
-  static const hipError_t at0 = hipFuncSetAttribute(reinterpret_cast<const void*>(rbf_kernel<GPK_KERN_SE, COMB>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  static const hipError_t at1 = hipFuncSetAttribute(reinterpret_cast<const void*>(rbf_kernel<GPK_KERN_MATERN12, COMB>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  static const hipError_t at2 = hipFuncSetAttribute(reinterpret_cast<const void*>(rbf_kernel<GPK_KERN_MATERN32, COMB>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  static const hipError_t at3 = hipFuncSetAttribute(reinterpret_cast<const void*>(rbf_kernel<GPK_KERN_MATERN52, COMB>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  GPK_HIP(at0); GPK_HIP(at1); GPK_HIP(at2); GPK_HIP(at3);
   switch (family) {
-    case GPK_KERN_SE: hipLaunchKernelGGL((rbf_kernel<GPK_KERN_SE, COMB>), grid, dim3(256), lds, st, a); break;
-    case GPK_KERN_MATERN12: hipLaunchKernelGGL((rbf_kernel<GPK_KERN_MATERN12, COMB>), grid, dim3(256), lds, st, a); break;
-    case GPK_KERN_MATERN32: hipLaunchKernelGGL((rbf_kernel<GPK_KERN_MATERN32, COMB>), grid, dim3(256), lds, st, a); break;
-    default: hipLaunchKernelGGL((rbf_kernel<GPK_KERN_MATERN52, COMB>), grid, dim3(256), lds, st, a); break;
+    case GPK_KERN_SE: return launch_family<GPK_KERN_SE, COMB>(st, a, grid, lds);
+    case GPK_KERN_MATERN12: return launch_family<GPK_KERN_MATERN12, COMB>(st, a, grid, lds);
+    case GPK_KERN_MATERN32: return launch_family<GPK_KERN_MATERN32, COMB>(st, a, grid, lds);
+    case GPK_KERN_MATERN52: return launch_family<GPK_KERN_MATERN52, COMB>(st, a, grid, lds);
+    case GPK_KERN_EXPONENTIAL: return launch_family<GPK_KERN_EXPONENTIAL, COMB>(st, a, grid, lds);
+    case GPK_KERN_RQ: return launch_family<GPK_KERN_RQ, COMB>(st, a, grid, lds);
+    case GPK_KERN_WHITE: return launch_family<GPK_KERN_WHITE, COMB>(st, a, grid, lds);
+    case GPK_KERN_CONSTANT: return launch_family<GPK_KERN_CONSTANT, COMB>(st, a, grid, lds);
   }
-  GPK_LAUNCH_CHECK();
+  return GPK_E_UNSUPPORTED;
+}
+
+// the lengthscales and, for GPK_KERN_RQ, the trailing alpha of ls_host (gpk.h) into the kernel's arguments
+int read_hypers(RbfArgs& a, int family, const double* ls_host, int ard, int d) {
+  const int nls = ard ? d : 1;
+  for (int i = 0; i < nls; ++i) a.ls[i] = ls_host[i];
+  a.alpha = 1.0;
+  if (family == GPK_KERN_RQ) {
+    a.alpha = ls_host[nls];
+    if (!(a.alpha > 0.0) || !std::isfinite(a.alpha)) return GPK_E_ARG;
+  }
   return 0;
 }
 }  // namespace
@@ -243,7 +289,7 @@ extern "C" int gpk_kernel_matrix(void* stream, int family, const double* X1, int
                                  double* K, long ldk) {
   // (gpk.h: an operand without elements may be NULL)
   if (!ls_host || n1 < 0 || (X2 && n2 < 0) || d <= 0 || d > GPK_MAX_D) return GPK_E_ARG;
-  if (family < GPK_KERN_SE || family > GPK_KERN_MATERN52) return GPK_E_UNSUPPORTED;
+  if (family < GPK_KERN_SE || family > GPK_KERN_CONSTANT) return GPK_E_UNSUPPORTED;
   if (n1 == 0 || (X2 && n2 == 0)) return 0;
   if (!X1 || !K) return GPK_E_ARG;
   RbfArgs a{};
@@ -252,7 +298,7 @@ extern "C" int gpk_kernel_matrix(void* stream, int family, const double* X1, int
   a.X2 = a.sym ? X1 : X2; a.ldx2 = a.sym ? ldx1 : ldx2; a.n2 = a.sym ? n1 : n2;
   a.d = d; a.K = K; a.ldk = ldk; a.variance = variance; a.diag_add = diag_add;
   a.family = family; a.lower_only = lower_only; a.ard = ard;
-  for (int i = 0; i < (ard ? d : 1); ++i) a.ls[i] = ls_host[i];
+  if (const int rc = read_hypers(a, family, ls_host, ard, d)) return rc;
   if (a.n1 == 0 || a.n2 == 0) return 0;
   // (A/B on the full 16384^2 build: mirror tile through LDS 0.479 ms, register layout 0.422 ms; nt stores 0.455 / 0.429)
   a.lds_mirror = GPK_TUNE(RBF_LDS_MIRROR, 0);
@@ -274,8 +320,9 @@ extern "C" int gpk_kernel_matrix_combine(void* stream, int family, int op, const
                                          double variance, double diag_add, const double* G, long ldg, double* out,
                                          long ldo) {
   if (!ls_host || n1 < 0 || (X2 && n2 < 0) || d <= 0 || d > GPK_MAX_D) return GPK_E_ARG;
-  if (family < GPK_KERN_SE || family > GPK_KERN_MATERN52) return GPK_E_UNSUPPORTED;
-  if (op < 1 || op > 3) return GPK_E_ARG;
+  if (family < GPK_KERN_SE || family > GPK_KERN_CONSTANT) return GPK_E_UNSUPPORTED;
+  if (op < 1 || op > 4) return GPK_E_ARG;
+  if (op == 4 && family != GPK_KERN_RQ) return GPK_E_UNSUPPORTED;
   if (n1 == 0 || (X2 && n2 == 0)) return 0;
   if (!X1 || !G || !out) return GPK_E_ARG;
   RbfArgs a{};
@@ -286,10 +333,13 @@ extern "C" int gpk_kernel_matrix_combine(void* stream, int family, int op, const
   a.d = d; a.K = out; a.ldk = ldo; a.variance = variance; a.diag_add = a.comb_diag ? diag_add : 0.0;
   a.family = family; a.lower_only = 0; a.ard = ard;
   a.G = G; a.ldg = ldg;
-  for (int i = 0; i < (ard ? d : 1); ++i) a.ls[i] = ls_host[i];
+  if (const int rc = read_hypers(a, family, ls_host, ard, d)) return rc;
   if (a.n1 == 0 || a.n2 == 0) return 0;
+  // White against a second set of points is zero: G + 0 in place is G
+  if (family == GPK_KERN_WHITE && op == 2 && X2 && out == G && ldo == ldg) return 0;
   const size_t lds = ((size_t)2 * d * T + 2 * T) * sizeof(double);
   dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
+  if (op == 4) return launch_family<GPK_KERN_RQ, 4>((hipStream_t)stream, a, grid, lds);
   if (op == 3) return launch_combine<3>((hipStream_t)stream, family, a, grid, lds);
   return op == 1 ? launch_combine<1>((hipStream_t)stream, family, a, grid, lds)
                  : launch_combine<2>((hipStream_t)stream, family, a, grid, lds);

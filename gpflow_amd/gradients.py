@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .ops import STATIC_FAMILIES   # (White, Constant: no distance, no lengthscale or input gradient)
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -151,9 +152,10 @@ def ls_device(lengthscales, D: int, device) -> torch.Tensor:
 
 def stationary_kernel_adjoint(A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, variance: float, lengthscales,
                               symmetric: bool, family: str = "SquaredExponential", packed_into=None, dvar_add: float = 0.0,
-                              return_packed: bool = False):
+                              return_packed: bool = False, alpha=None):
     """Adjoint of K = variance * f(r(A / ls, Bm / ls)) [n1, n2] given Kbar [n1, n2], f one of the stationary families of
-    `ops.KERNEL_FAMILIES` (stationaries.py:209-210 SquaredExponential, :254-313 Matern12 / 32 / 52).
+    `ops.KERNEL_FAMILIES` (stationaries.py:209-210 SquaredExponential, :254-313 Matern12 / 32 / 52; Exponential; RationalQuadratic
+    with its `alpha`; the static families have no distance and never come here: KernelSpec._adjoint).
 
     Returns (d/dvariance, d/dlengthscales [D], A_bar [n1, D]); with symmetric=True (Bm is A, Kbar symmetric) A_bar
     collects both arguments.  B_bar of the non-symmetric case is not needed on this path (B = the minibatch).
@@ -161,17 +163,22 @@ def stationary_kernel_adjoint(A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Ten
     With r2 the scaled squared distance, dF/dtheta = sum_ij Kbar_ij dK_ij/dr2 dr2_ij/dtheta.  G = Kbar .* (-2 dK/dr2) is
     one elementwise pass that recomputes r2 from the inputs (`gpk_kernel_matrix_combine` op 3); for the
     SquaredExponential -2 dK/dr2 = K, so G also carries d/dvariance = sum(Kbar .* K) / variance; the Matern families
-    take that sum from a second pass (op 1)."""
+    take that sum from a second pass (op 1).  d/dvariance = sum(Kbar .* K) / variance holds for every family.  The RationalQuadratic
+    adds d/dalpha = sum(Kbar .* dK/dalpha) (op 4, into the same buffer) and returns it as a fourth value [1]."""
     n1, D = A.shape
     ls = ls_device(lengthscales, D, A.device)
+    akw = {} if alpha is None else {"alpha": alpha}   # (the keyword exists for the family that has it: ops._ls_host)
     if family == "SquaredExponential":
         G = ops.kernel_matrix_hadamard(A, Bm, Kbar, variance=variance, lengthscales=lengthscales)   # Kbar .* K
         sum_kbar_k = None
     else:
-        G = ops.kernel_matrix_hadamard(A, Bm, Kbar, variance=variance, lengthscales=lengthscales, family=family)
+        G = ops.kernel_matrix_hadamard(A, Bm, Kbar, variance=variance, lengthscales=lengthscales, family=family, **akw)
         sum_kbar_k = G.sum()
+        if family == "RationalQuadratic":
+            dalpha = ops.kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="dalpha", variance=variance,
+                                               lengthscales=lengthscales, family=family, out=G, **akw).sum().reshape(1)
         ops.kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="dr2", variance=variance,
-                                  lengthscales=lengthscales, family=family, out=G)
+                                  lengthscales=lengthscales, family=family, out=G, **akw)
     Vt = ops.moment_rows(Bm)                         # [1, B, B^2]^T
     R = splitk_gemm_nt(G, Vt)                        # [n1, 1 + 2D] = G [1, B, B^2]: row sums rs, G B, G B^2
     # one launch for what follows (it was a dozen elementwise / reduction launches on [n1, D] arrays):  T = G B - A rs;
@@ -183,6 +190,8 @@ def stationary_kernel_adjoint(A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Ten
                                                   symmetric=symmetric, sum_kbar_k=sum_kbar_k, into=packed_into, dvar_add=dvar_add)
     if return_packed:
         return (packed_into[0] if packed_into is not None else dls._base), Abar
+    if family == "RationalQuadratic":
+        return dvar, dls, Abar, dalpha
     return dvar, dls, Abar
 
 
@@ -193,9 +202,14 @@ def _ls_grad(dl: torch.Tensor, ls) -> torch.Tensor:
 
 class KernelSpec:
     """What the reverse pass needs to know about the covariance function: ONE stationary kernel, or a Sum / Product of
-    stationary kernels -- flat, or nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220 `Sum`, :305-315 `Product`; the reference
+    stationary / static kernels -- flat, or nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220 `Sum`, :305-315 `Product`; the reference
     differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).  members: [(family, variance,
-    lengthscales)], op: None | "add" | "mul" | tree.
+    lengthscales) or (family, variance, lengthscales, alpha)], op: None | "add" | "mul" | tree.  A RationalQuadratic member carries its
+    `alpha` (kept beside the triples, in `alphas`); a static member (White, Constant) a dummy lengthscale 1.0.
+
+    A member's SHAPE gradient -- the `dl` entry of `adjoint` -- is laid out like `ls_host` of the C-ABI: the lengthscale entries,
+    then alpha where the family has one; a static member's is empty (no lengthscale, no input gradient: A_bar is zero and no
+    contraction is launched for it).  `kernel_grads` splits it into the "lengthscales" / "alpha" entries of a `grads` dict.
 
       build    the combined matrix, members folded in place by `gpk_kernel_matrix_combine` (no second matrix);
       kdiag    K(x, x): sum or product of the variances (stationary members), dkdiag[i] = d kdiag / d variance_i;
@@ -206,7 +220,11 @@ class KernelSpec:
         """members: [(family, variance, lengthscales)]; cols[i]: the input columns member i sees (its `active_dims` as an index
         list, kernels/base.py:90-109) or None for all of them.  Members that see different columns are built and differentiated on
         their own column slices; their input gradients are scattered back into the full columns and add up."""
-        self.members = [(f, float(v), np.asarray(ls, dtype=np.float64)) for f, v, ls in members]
+        self.members = [(m[0], float(m[1]), np.asarray(m[2], dtype=np.float64)) for m in members]
+        self.alphas = [float(m[3]) if len(m) > 3 and m[3] is not None else None for m in members]
+        for (f, _, _), a in zip(self.members, self.alphas):
+            if (f == "RationalQuadratic") != (a is not None):
+                raise ValueError("alpha belongs to 'RationalQuadratic' members, and every such member needs one")
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
         # (k0 + k1) * k2 (kernels/base.py:223-329: a Combination holds kernels, which may be Combinations of the other kind).
@@ -224,8 +242,28 @@ class KernelSpec:
         self._idx = {}
 
     @staticmethod
-    def single(variance, lengthscales, family="SquaredExponential"):
-        return KernelSpec([(family, variance, lengthscales)], None)
+    def single(variance, lengthscales, family="SquaredExponential", alpha=None):
+        return KernelSpec([(family, variance, 1.0 if lengthscales is None else lengthscales, alpha)], None)
+
+    def _akw(self, i: int) -> dict:
+        """member i's extra keyword of the ops builders: alpha for a RationalQuadratic member, nothing for the others"""
+        return {} if self.alphas[i] is None else {"alpha": self.alphas[i]}
+
+    def is_static(self, i: int) -> bool:
+        return self.members[i][0] in STATIC_FAMILIES
+
+    def n_lengthscales(self, i: int) -> int:
+        """lengthscale entries member i holds (1 = isotropic, 0 = static)"""
+        return 0 if self.is_static(i) else int(np.size(self.members[i][2]))
+
+    def n_shape(self, i: int) -> int:
+        """entries of member i's shape gradient: its lengthscales, then alpha"""
+        return self.n_lengthscales(i) + (self.alphas[i] is not None)
+
+    @property
+    def packable(self) -> bool:
+        """one member whose two adjoints fit the packed tail of `_covariance_tail` ([variance, lengthscales] and A_bar in one launch)"""
+        return self.n == 1 and self.cols[0] is None and self.alphas[0] is None and not self.is_static(0)
 
     @staticmethod
     def _check_tree(node, n):
@@ -264,7 +302,7 @@ class KernelSpec:
         if isinstance(node, int):
             f, v, ls = self.members[node]
             return ops.kernel_matrix(self._sl(node, X1), self._sl(node, X2), variance=v, lengthscales=ls, family=f,
-                                     diag_add=diag_add, lower_only=False, out=out)
+                                     diag_add=diag_add, lower_only=False, out=out, **self._akw(node))
         op, ch = node
         if len(ch) == 1:
             return self._build(ch[0], X1, X2, out, diag_add)
@@ -274,7 +312,7 @@ class KernelSpec:
             if isinstance(c, int):      # a stationary member folds in place (K recomputed in registers, no second matrix);
                 f, v, ls = self.members[c]   # diag_add rides in the LAST member's launch
                 ops.kernel_matrix_combine(self._sl(c, X1), self._sl(c, X2), out, op=op, variance=v, lengthscales=ls, family=f,
-                                          diag_add=diag_add if j == last else 0.0, out=out)
+                                          diag_add=diag_add if j == last else 0.0, out=out, **self._akw(c))
             else:                        # a sub-combination needs its own matrix once
                 tmp = self._build(c, X1, X2, None)
                 out.add_(tmp) if op == "add" else out.mul_(tmp)
@@ -310,22 +348,31 @@ class KernelSpec:
     def warm(self, device, D: int) -> "KernelSpec":
         """device copies of the members' lengthscales, made now (see `ls_device`)"""
         for i, (_, _, ls) in enumerate(self.members):
-            ls_device(ls, D if self.cols[i] is None else len(self.cols[i]), device)
+            if not self.is_static(i):
+                ls_device(ls, D if self.cols[i] is None else len(self.cols[i]), device)
         return self
 
     def adjoint(self, A, Bm, Kbar, symmetric: bool):
-        """([d/dvariance_i [1]], [d/dlengthscales_i], A_bar [n1, D]) given Kbar, members in index order"""
+        """([d/dvariance_i [1]], [shape gradient_i: d/dlengthscales_i, then d/dalpha_i], A_bar [n1, D]) given Kbar, members in index
+        order"""
         acc = {"dv": [None] * self.n, "dl": [None] * self.n, "Abar": None}
         self._adjoint(self.tree, A, Bm, Kbar, symmetric, acc)
-        return acc["dv"], acc["dl"], acc["Abar"]
+        return acc["dv"], acc["dl"], (acc["Abar"] if acc["Abar"] is not None else torch.zeros_like(A))   # (static members only: zero)
 
     def _adjoint(self, node, A, Bm, Kbar, symmetric, acc):
         if isinstance(node, int):
             f, v, ls = self.members[node]
+            if self.is_static(node):
+                # d/dvariance = sum(Kbar .* K) / variance read off directly: every entry (Constant), the diagonal of K(A, A) (White:
+                # NOT through the X2-given hadamard, which is zeros for it), nothing where White sees two sets of points
+                dv = Kbar.sum() if f == "Constant" else torch.diagonal(Kbar).sum() if symmetric else Kbar.new_zeros(())
+                acc["dl"][node], acc["dv"][node] = Kbar.new_zeros(0), dv.reshape(1)
+                return
             Ai = self._sl(node, A)
             Bi = Ai if (symmetric and Bm is A) else self._sl(node, Bm)
-            dv, dl, Ab = stationary_kernel_adjoint(Ai, Bi, Kbar, symmetric=symmetric, variance=v, lengthscales=ls, family=f)
-            acc["dl"][node], acc["dv"][node] = _ls_grad(dl, ls), dv.reshape(1)
+            dv, dl, Ab, *da = stationary_kernel_adjoint(Ai, Bi, Kbar, symmetric=symmetric, variance=v, lengthscales=ls, family=f,
+                                                        alpha=self.alphas[node])
+            acc["dl"][node], acc["dv"][node] = torch.cat([_ls_grad(dl, ls), *da]), dv.reshape(1)
             if all(c is None for c in self.cols):
                 acc["Abar"] = Ab if acc["Abar"] is None else acc["Abar"] + Ab
             else:   # scatter the member's input gradient back into the columns it read
@@ -347,7 +394,7 @@ class KernelSpec:
                     if isinstance(o, int):
                         fo, vo, lo = self.members[o]
                         ops.kernel_matrix_combine(self._sl(o, A), None if symmetric else self._sl(o, Bm), Kb, op="mul", variance=vo,
-                                                  lengthscales=lo, family=fo, out=Kb)
+                                                  lengthscales=lo, family=fo, out=Kb, **self._akw(o))
                     else:
                         Kb.mul_(self._build(o, A, None if symmetric else Bm, None))
             self._adjoint(c, A, Bm, Kb, symmetric, acc)
@@ -358,6 +405,20 @@ class KernelSpec:
         if self.n == 1:
             return dvs[0], dls[0]
         return torch.cat(dvs), list(dls)
+
+    def kernel_grads(self, g_var, g_shape) -> dict:
+        """the kernel's entries of a `grads` dict from what `pack` returned: "variance", "lengthscales" (a static member's is empty)
+        and -- only when a member has one -- "alpha": [1] for one member, else a list with None for the members without"""
+        nl = [self.n_lengthscales(i) for i in range(self.n)]
+        if self.n == 1:
+            out = {"variance": g_var, "lengthscales": g_shape[:nl[0]] if self.n_shape(0) != nl[0] else g_shape}
+            if self.alphas[0] is not None:
+                out["alpha"] = g_shape[nl[0]:]
+            return out
+        out = {"variance": g_var, "lengthscales": [g[:n] if g.numel() != n else g for g, n in zip(g_shape, nl)]}
+        if any(a is not None for a in self.alphas):
+            out["alpha"] = [g[n:] if a is not None else None for g, n, a in zip(g_shape, nl, self.alphas)]
+        return out
 
 
 class _Seed:
@@ -569,11 +630,14 @@ class _SideBranch:
 def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor,
                        *, variance: float = None, lengthscales=None, noise_variance: float, jitter: float, scale: float = 1.0,
                        mean_const: float = 0.0, kl_weight: float = 1.0, family: str = "SquaredExponential",
-                       kernel_spec: "KernelSpec" = None, likelihood=None
+                       kernel_spec: "KernelSpec" = None, likelihood=None, alpha=None
                        ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor]:
     """F = scale * sum_b var_exp_b - kl_weight * KL for the whitened SVGP with a stationary kernel (or, `kernel_spec`, a Sum /
     Product of stationary kernels: then grads["variance"] is [n_members] and grads["lengthscales"] a list), a Gaussian likelihood
     and a full q_sqrt [P, M, M], and dF/d{variance, lengthscales, noise_variance, Z, q_mu, q_sqrt, mean_const}.
+
+    `family` is any name of ops.KERNEL_FAMILIES; "RationalQuadratic" takes `alpha` and adds grads["alpha"] [1] (for a `kernel_spec` with
+    several members: a list, None where a member has no alpha); a static family (White, Constant) has an empty grads["lengthscales"].
 
     Returns (F [1], grads, info).  `scale` = num_data / minibatch size (svgp.py:176-180).  For a row shard of a
     data-parallel step pass the GLOBAL scale and kl_weight = 1 / world_size: the SUM over ranks of F and of every
@@ -588,7 +652,7 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     if tuple(q_sqrt.shape) not in ((P, M, M), (M, P)):
         raise ValueError("svgp_elbo_and_grad needs q_sqrt [P, M, M] or, for q_diag, [M, P]")
     dev = Z.device
-    spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family)
+    spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family, alpha)
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
 
     # ---------------------------------------------------------------- forward (intermediates kept)
@@ -608,7 +672,7 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     seed = _Seed(Yb, fmean, scale=scale, mean_const=mean_const, noise_variance=noise_variance,
                  lik_grads=(dmu, dvar) if likelihood is not None else None)
     g_var, g_ls, Zbar, g_qmu, g_qs = _svgp_backward(spec, Z, Xb, q_mu, q_sqrt, fwd, seed, kl_weight)
-    grads = {"variance": g_var, "lengthscales": g_ls}
+    grads = spec.kernel_grads(g_var, g_ls)
     if likelihood is None:
         grads["noise_variance"] = seed.noise_grad(ve, s0, ssq, spec.kdiag())
     grads.update({"Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": seed.r.sum().reshape(1)})
@@ -669,7 +733,7 @@ def _svgp_backward(spec: KernelSpec, Z, Xb, q_mu, q_sqrt, fwd: _SvgpForward, see
         g.diagonal(dim1=1, dim2=2).add_(kl_weight / Lq.diagonal(dim1=1, dim2=2))
         return g
 
-    one_kernel = spec.n == 1 and spec.cols[0] is None and seed.scalar                   # (the packed tail of _covariance_tail)
+    one_kernel = spec.packable and seed.scalar                   # (the packed tail of _covariance_tail)
     LT = ops.transpose(L, mode=1)
     with _SideBranch(Z, branch_q_prep, branch_q_products) as branch:
         Lbar = splitk_gemm_nt(Kuf_bar, A, c_lower=True, alpha=-1.0)                     # -tril(Kfu_bar^T At)
@@ -717,7 +781,7 @@ def svgp_elbo_and_grad_lcm(Zs, Xs, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt:
         seed = _Seed(Yb, fwds[l].fmean, scale=scale, mean_const=0.0, noise_variance=noise_variance,
                      given=(r[:, l:l + 1].contiguous(), c[l]))
         g_var, g_ls, Zbar, g_qmu, g_qs = _svgp_backward(kernel_specs[l], Zs[l], Xs[l], *cols[l], fwds[l], seed, kl_weight)
-        latents.append({"variance": g_var, "lengthscales": g_ls, "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs})
+        latents.append({**kernel_specs[l].kernel_grads(g_var, g_ls), "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs})
     P = W.shape[0]
     grads = {"latents": latents, "W": dW.mul_(scale), "noise_variance": out[1:2] * scale,
              "mean_const": ((Yb[:, :P] - fmean).sum() * (scale / noise_variance)).reshape(1)}
@@ -725,8 +789,8 @@ def svgp_elbo_and_grad_lcm(Zs, Xs, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt:
 
 
 def gpr_lml_and_grad(X: torch.Tensor, Y: torch.Tensor, *, variance: float = None, lengthscales=None, noise_variance: float,
-                     mean_const: float = 0.0, family: str = "SquaredExponential", kernel_spec: "KernelSpec" = None
-                     ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor]:
+                     mean_const: float = 0.0, family: str = "SquaredExponential", kernel_spec: "KernelSpec" = None,
+                     alpha=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor]:
     """GPR.log_marginal_likelihood (gpr.py:91-107) and its gradient w.r.t. {variance, lengthscales, noise_variance,
     mean_const} for a SquaredExponential kernel -- what `optimizers/scipy.py:322-331` asks TF autodiff for.
 
@@ -738,7 +802,7 @@ def gpr_lml_and_grad(X: torch.Tensor, Y: torch.Tensor, *, variance: float = None
     N, D = X.shape
     P = Y.shape[1]
     dev = X.device
-    spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family)
+    spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family, alpha)
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
     T = torch.empty((N + P + N, N), dtype=torch.float64, device=dev)
     het = torch.is_tensor(noise_variance) and noise_variance.dim() >= 1   # one variance per data row (heteroskedastic likelihood)
@@ -762,7 +826,7 @@ def gpr_lml_and_grad(X: torch.Tensor, Y: torch.Tensor, *, variance: float = None
     dvs, dlss, _ = spec.adjoint(X, X, Kbar, symmetric=True)
     dvar, dls = spec.pack(dvs, dlss)
     # d LML / d sigma_n^2 = Kbar_nn: their sum for a constant noise variance, the vector for a heteroskedastic likelihood
-    grads = {"variance": dvar, "lengthscales": dls,
+    grads = {**spec.kernel_grads(dvar, dls),
              "noise_variance": torch.diagonal(Kbar).clone() if het else torch.diagonal(Kbar).sum().reshape(1),
              "mean_const": betat.sum().reshape(1)}
     return lml.reshape(1), grads, info
@@ -771,7 +835,7 @@ def gpr_lml_and_grad(X: torch.Tensor, Y: torch.Tensor, *, variance: float = None
 def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, variance: float = None, lengthscales=None,
                        noise_variance: float, jitter: float, mean_const: float = 0.0,
                        family: str = "SquaredExponential", group=None, sharded: bool = False,
-                       num_data: Optional[int] = None, kernel_spec: "KernelSpec" = None
+                       num_data: Optional[int] = None, kernel_spec: "KernelSpec" = None, alpha=None
                        ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor]:
     """SGPR.elbo (sgpr.py:181-290) and its gradient w.r.t. {variance, lengthscales, noise_variance, Z, mean_const}.
     With At = Kfu Lm^-T, S = At^T At, a = At^T err, q = |At|^2, e2 = |err|^2, B = I + S / s2, w = B^-1 a / s2:
@@ -805,11 +869,11 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
     if not sharded and N != n:
         raise ValueError("num_data differs from the number of rows of a model that is not sharded")
     # (kernel_spec: a Sum / Product of stationary kernels, members possibly over different input columns -- round 5)
-    spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family)
+    spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family, alpha)
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
     kdiag = spec.kdiag()
     nmem = spec.n
-    nlsm = [int(np.size(ls)) for _, _, ls in spec.members]     # lengthscale entries per member (1 = isotropic)
+    nlsm = [spec.n_shape(i) for i in range(nmem)]              # shape-gradient entries per member (lengthscales: 1 = isotropic; + alpha)
 
     def all_reduce(t):
         if sharded:
@@ -893,7 +957,7 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
         g_noise = (-P * (-0.5 * (M - torch.diagonal(Binv).sum()) / s2 + 0.5 * N / s2 - 0.5 * (N * kdiag - q) / s2 ** 2)
                    + 0.5 * e2 / s2 ** 2 - 0.5 * wa / s2 ** 2 - 0.5 * ww / s2).reshape(1)
     status = torch.maximum(info, info2)
-    grads = {"variance": g_var, "lengthscales": g_ls, "noise_variance": g_noise, "Z": Zbar,
+    grads = {**spec.kernel_grads(g_var, g_ls), "noise_variance": g_noise, "Z": Zbar,
              "mean_const": g_mean.reshape(1)}
     return F.reshape(1), grads, status
 
@@ -901,7 +965,7 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
 def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: torch.Tensor,
                                   q_sqrt: torch.Tensor, *, variance: float = None, lengthscales=None, noise_variance: float,
                                   jitter: float, scale: float = 1.0, mean_const: float = 0.0, kl_weight: float = 1.0,
-                                  family: str = "SquaredExponential", kernel_spec: "KernelSpec" = None
+                                  family: str = "SquaredExponential", kernel_spec: "KernelSpec" = None, alpha=None
                        ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor]:
     """The `whiten=False` SVGP: q(u) = N(q_mu, Lq Lq^T) on u itself (conditionals/util.py:137-139, kullback_leiblers.py:
     98-165 with K = Kuu).  With Linv = Lm^-1 (from the identity rows of the trapezoid):
@@ -924,7 +988,7 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
         raise ValueError("svgp_elbo_and_grad_unwhitened needs q_sqrt [P, M, M] or, for q_diag, [M, P]")
     dev = Z.device
     # (kernel_spec: a Sum / Product of stationary kernels, members possibly over different input columns -- round 5)
-    spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family)
+    spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family, alpha)
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
     k = float(kl_weight)
     L, At, LinvT, info = _factorise(spec, Z, Xb, jitter)
@@ -986,6 +1050,6 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
     Lbar = splitk_gemm_nt(Kuf_bar, A, c_lower=True, alpha=-1.0) - torch.tril(X2)
     Lbar.diagonal().sub_(k * P / L.diagonal())
     g_var, g_ls, Zbar = _covariance_tail(spec, Z, Xb, Kuf_bar, ops.transpose(L, mode=1), LinvT, Lbar, seed.csum())
-    grads = {"variance": g_var, "lengthscales": g_ls, "noise_variance": seed.noise_grad(ve, s0, ssq, spec.kdiag()),
+    grads = {**spec.kernel_grads(g_var, g_ls), "noise_variance": seed.noise_grad(ve, s0, ssq, spec.kdiag()),
              "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)}
     return F, grads, info

@@ -89,6 +89,20 @@ class Kernel(Module, metaclass=abc.ABCMeta):
         return self.K(X, X2)
 
 
+def is_device_leaf(k) -> bool:
+    """True for a kernel that gpk_kernel_matrix builds from host hyperparameters: it answers `hyper()` -> (family, variance,
+    lengthscales; a dummy 1.0 for a static kernel), `hyper_alpha()` -> alpha | None and `hyper_extra()` -> that as the builders'
+    extra keyword, and has K_diag = variance.  The one notion
+    Combination.K_into, gradient_spec and the model routes share."""
+    return bool(getattr(k, "device_leaf", False)) and getattr(k, "family", None) in ops.KERNEL_FAMILIES
+
+
+def leaf_parameters(k):
+    """the Parameters of a device-built leaf, in the order of its hyperparameters: (variance, lengthscales), with alpha behind them
+    for a RationalQuadratic, (variance,) for a static kernel"""
+    return tuple(p for p in (k.variance, getattr(k, "lengthscales", None), getattr(k, "alpha", None)) if p is not None)
+
+
 class Combination(Kernel):
     """A list of kernels reduced elementwise (gpflow/kernels/base.py:223-329); nested instances of the same class are
     flattened (:247-255).  Every member slices its own active_dims, so the combination itself never slices."""
@@ -117,9 +131,8 @@ class Combination(Kernel):
         return True
 
     def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
-        """The first member is built into `out`; every further stationary member is folded in by
+        """The first member is built into `out`; every further device-built member (stationary or static) is folded in by
         gpk_kernel_matrix_combine (K recomputed in registers: one read + one write of `out`, no second matrix)."""
-        from .stationaries import Stationary
         X = ops.to_device(X)
         X2 = ops.to_device(X2) if X2 is not None else None
         ks = list(self.kernels)
@@ -130,10 +143,10 @@ class Combination(Kernel):
         for i, k in enumerate(ks[1:], start=1):
             Xs, X2s = k.slice(X, X2)
             dadd = diag_add if i == last else 0.0
-            if isinstance(k, Stationary):
+            if is_device_leaf(k):
                 family, var, ls = k.hyper()
                 ops.kernel_matrix_combine(Xs, X2s, out, op=self._op, variance=var, lengthscales=ls, family=family,
-                                          diag_add=dadd, out=out)
+                                          diag_add=dadd, out=out, **k.hyper_extra())
             else:
                 Ki = k.K_into(Xs, X2s, None)
                 out.add_(Ki) if self._op == "add" else out.mul_(Ki)
@@ -171,6 +184,7 @@ def gradient_spec(kernel, input_dim=None):
     and scatters its input gradient back (round 5) -- `input_dim`, the number of input columns, resolves slices.  None if `kernel`
     is not such a combination."""
     from .stationaries import IsotropicStationary
+    from .statics import Static
     from .. import gradients
     if not isinstance(kernel, Combination):
         return None
@@ -180,9 +194,9 @@ def gradient_spec(kernel, input_dim=None):
     def walk(k):
         if isinstance(k, Combination):
             return (k._op, [walk(c) for c in k.kernels])
-        if not (isinstance(k, IsotropicStationary) and k.family in ops.KERNEL_FAMILIES):
-            raise NotImplementedError("gradients of a kernel combination: Sums / Products (possibly nested) of SquaredExponential / "
-                                      "Matern members (kernels/base.py:216-220, 305-315)")
+        if not (isinstance(k, (IsotropicStationary, Static)) and is_device_leaf(k)):
+            raise NotImplementedError("gradients of a kernel combination: Sums / Products (possibly nested) of isotropic-stationary "
+                                      "and static members (kernels/base.py:216-220, 305-315)")
         ks.append(k)
         return len(ks) - 1
     tree = walk(kernel)
@@ -196,8 +210,8 @@ def gradient_spec(kernel, input_dim=None):
             cols.append(np.arange(int(input_dim))[k.active_dims])
         else:
             cols.append(np.asarray(k.active_dims, dtype=np.int64))
-    spec = gradients.KernelSpec([k.hyper() for k in ks], tree, cols=cols)
-    return spec, [(k.variance, k.lengthscales) for k in ks]
+    spec = gradients.KernelSpec([k.hyper() + (k.hyper_alpha(),) for k in ks], tree, cols=cols)
+    return spec, [leaf_parameters(k) for k in ks]
 
 
 class Sum(Combination):

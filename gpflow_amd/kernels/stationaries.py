@@ -15,6 +15,7 @@ from .base import Kernel
 
 class Stationary(Kernel):
     family = "SquaredExponential"
+    device_leaf = True   # built by gpk_kernel_matrix from hyper() (+ hyper_alpha()): what Combination.K_into and gradient_spec ask
 
     def __init__(self, variance=1.0, lengthscales=1.0, **kwargs: Any):
         for kwarg in kwargs:
@@ -48,10 +49,19 @@ class Stationary(Kernel):
         """(family, variance, lengthscales) as host values for the C-ABI."""
         return self.family, float(self.variance.numpy()), np.asarray(self.lengthscales.numpy(), dtype=np.float64)
 
+    def hyper_alpha(self):
+        """the family's extra shape parameter as a host value (RationalQuadratic), None where the family has none"""
+        return None
+
+    def hyper_extra(self) -> dict:
+        """the same as the extra keyword of the ops builders: {"alpha": value}, or {} for a family without one"""
+        a = self.hyper_alpha()
+        return {} if a is None else {"alpha": a}
+
     def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
         family, var, ls = self.hyper()
         return ops.kernel_matrix(X, X2, variance=var, lengthscales=ls, family=family, diag_add=diag_add,
-                                 lower_only=lower_only, out=out)
+                                 lower_only=lower_only, out=out, **self.hyper_extra())
 
 
 class IsotropicStationary(Stationary):
@@ -78,6 +88,24 @@ class IsotropicStationary(Stationary):
 class SquaredExponential(IsotropicStationary):
     """stationaries.py:194-210"""
     family = "SquaredExponential"
+
+
+class Exponential(IsotropicStationary):
+    """stationaries.py `Exponential`: variance exp(-r / 2), r = sqrt(max(r2, 1e-36))"""
+    family = "Exponential"
+
+
+class RationalQuadratic(IsotropicStationary):
+    """stationaries.py `RationalQuadratic`: variance (1 + r2 / (2 alpha))^-alpha, a scale mixture of SquaredExponential kernels with different
+    lengthscales; alpha -> infinity recovers the SquaredExponential."""
+    family = "RationalQuadratic"
+
+    def __init__(self, variance=1.0, lengthscales=1.0, alpha=1.0, active_dims=None, name=None):
+        super().__init__(variance=variance, lengthscales=lengthscales, active_dims=active_dims, name=name)
+        self.alpha = Parameter(alpha, transform=positive())
+
+    def hyper_alpha(self):
+        return float(self.alpha.numpy())
 
 
 class Matern12(IsotropicStationary):

@@ -7,7 +7,7 @@ import torch
 
 from .. import ops, posteriors
 from ..kernels import Kernel
-from ..kernels.stationaries import Stationary
+from ..kernels.base import is_device_leaf
 from ..likelihoods import Gaussian
 from ..logdensities import multivariate_normal
 from ..mean_functions import MeanFunction
@@ -40,12 +40,12 @@ class GPR(GPModel, InternalDataTrainingLossMixin):
         otherwise it is composed from the same primitives."""
         X, Y = self.data
         c = self.mean_function.constant_value()
-        if isinstance(self.kernel, Stationary) and c is not None:
+        if is_device_leaf(self.kernel) and c is not None:
             Xs, _ = self.kernel.slice(X, None)
             family, var, ls = self.kernel.hyper()
             out, info = ops.gpr_lml(Xs, Y, variance=var, lengthscales=ls,
                                     noise_variance=self.likelihood.noise_for(X), mean_const=c,
-                                    family=family, ws=self._ws)
+                                    family=family, ws=self._ws, **self.kernel.hyper_extra())
             ops.check_info(info)
             return out[0]
         K = self.kernel(X)

@@ -22,7 +22,7 @@ import torch
 from .. import config, gradients, ops
 from ..inducing_variables import InducingPoints, inducingpoint_wrapper
 from ..kernels import Kernel
-from ..kernels.stationaries import Stationary
+from ..kernels.base import is_device_leaf
 from ..likelihoods import Gaussian
 from ..mean_functions import MeanFunction
 from ..posteriors import assert_params_false
@@ -168,7 +168,7 @@ class SGPR(GPModel, InternalDataTrainingLossMixin):
         c = self.mean_function.constant_value()
         from ..kernels.base import Combination
         from .reverse import CovarianceRoute
-        if not (isinstance(k, (Stationary, Combination)) and isinstance(iv, InducingPoints) and isinstance(lik, Gaussian)
+        if not ((is_device_leaf(k) or isinstance(k, Combination)) and isinstance(iv, InducingPoints) and isinstance(lik, Gaussian)
                 and c is not None):
             raise NotImplementedError("SGPR here: stationary kernel (or a Sum / Product of them), InducingPoints, Gaussian "
                                       "likelihood, constant mean")
@@ -182,7 +182,7 @@ class SGPR(GPModel, InternalDataTrainingLossMixin):
             return route.spec, X, Z, float(c), s2
         family, var, ls = k.hyper()
         X, Z = k.slice(self.data[0], iv.Z.device_value())
-        return gradients.KernelSpec.single(var, ls, family), X, Z, float(c), s2
+        return gradients.KernelSpec.single(var, ls, family, k.hyper_alpha()), X, Z, float(c), s2
 
     def _noise_rows(self):
         return self.likelihood.noise_for(self.data[0]) if self.likelihood.is_heteroskedastic else None

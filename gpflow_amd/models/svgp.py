@@ -12,7 +12,7 @@ from ..conditionals import conditional
 from ..inducing_variables import (InducingPoints, SharedIndependentInducingVariables,
                                   inducingpoint_wrapper)
 from ..kernels import Kernel
-from ..kernels.stationaries import Stationary
+from ..kernels.base import is_device_leaf
 from ..likelihoods import Gaussian, Likelihood, MultiClass, ScalarLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
@@ -73,7 +73,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         if c is None:
             return None
         k, iv = shared_pair(self.kernel, self.inducing_variable)
-        if not (isinstance(k, Stationary) and isinstance(iv, InducingPoints)):
+        if not (is_device_leaf(k) and isinstance(iv, InducingPoints)):
             return None
         return k, iv.Z.device_value(), c
 
@@ -111,7 +111,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         k, iv = self.kernel, self.inducing_variable
         if not isinstance(k, kernel_class or SeparateIndependent):
             return None
-        if not all(isinstance(kk, Stationary) and kk.has_default_active_dims for kk in k.kernels):
+        if not all(is_device_leaf(kk) and kk.has_default_active_dims for kk in k.kernels):
             return None
         if isinstance(iv, SharedIndependentInducingVariables) and isinstance(iv.inducing_variable, InducingPoints):
             return k.kernels, iv.inducing_variable.Z.device_value().contiguous()
@@ -157,7 +157,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         if self.whiten or self.q_sqrt.device_value().dim() != 3:
             return None
         k, iv = shared_pair(self.kernel, self.inducing_variable)
-        if not (isinstance(k, Stationary) and isinstance(iv, InducingPoints)):
+        if not (is_device_leaf(k) and isinstance(iv, InducingPoints)):
             return None
         return k, iv.Z.device_value()
 
@@ -240,6 +240,9 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
     @staticmethod
     def _member_hypers(kernels, d):
         """([(family, variance, lengthscales)] per member, lengthscales [P] or [P, d]) as the per-latent shards take them"""
+        if any(k.hyper_alpha() is not None for k in kernels):
+            raise NotImplementedError("SeparateIndependent / LinearCoregionalization with a RationalQuadratic member: the fused per-latent "
+                                      "shard strides its lengthscales by latent and has no slot for alpha (include/gpk.h)")
         hyp = [k.hyper() for k in kernels]
         ls = [np.atleast_1d(h[2]) for h in hyp]
         if any(l.size > 1 for l in ls):   # mixed isotropic / ARD members: every row spelled out
@@ -269,12 +272,12 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
                 out, info = ops.svgp_elbo_shard(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt, variance=var,
                                                 lengthscales=ls, noise_variance=self.likelihood.noise_for(X),
                                                 jitter=config.default_jitter(), mean_const=c, family=family,
-                                                ws=self._ws[1], whiten=self.whiten)
+                                                ws=self._ws[1], whiten=self.whiten, **k.hyper_extra())
             else:
                 out, info = ops.svgp_elbo_shard_lik(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt, variance=var, lengthscales=ls,
                                                     lik=self.likelihood.device_lik, params=self.likelihood.device_params(),
                                                     jitter=config.default_jitter(), mean_const=c, family=family,
-                                                    ws=self._ws[1], whiten=self.whiten)
+                                                    ws=self._ws[1], whiten=self.whiten, **k.hyper_extra())
             ops.check_info(info)
             return out
         sep = self._fused_separate_config()
@@ -366,7 +369,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             ops.check_info(info)
             Fv += float(F.cpu()[0])
             kernel_pairs += route.kernel_pairs(g)
-            host = {n: g[n].cpu().numpy() for n in g if n not in ("variance", "lengthscales", "Z")}
+            host = {n: g[n].cpu().numpy() for n in g if n not in ("variance", "lengthscales", "alpha", "Z")}
             gz = scatter(g["Z"]).cpu().numpy()
             zgrads[id(iv.Z)] = (iv.Z, zgrads[id(iv.Z)][1] + gz if id(iv.Z) in zgrads else gz)   # shared Z: contributions add up
             hosts.append(host)

@@ -14,7 +14,9 @@ import torch
 from . import _lib
 
 NB = 128
-KERNEL_FAMILIES = {"SquaredExponential": 0, "Matern12": 1, "Matern32": 2, "Matern52": 3}
+KERNEL_FAMILIES = {"SquaredExponential": 0, "Matern12": 1, "Matern32": 2, "Matern52": 3,
+                   "Exponential": 4, "RationalQuadratic": 5, "White": 6, "Constant": 7}
+STATIC_FAMILIES = ("White", "Constant")   # no distance: the inputs are never read, no lengthscale or input gradient
 MAX_D = 64
 
 
@@ -69,12 +71,21 @@ def _ws(nbytes: int) -> torch.Tensor:
     return torch.empty((max(int(nbytes), 8) + 7) // 8, dtype=torch.float64, device=device())
 
 
-def _ls_host(lengthscales, d: int):
+def _ls_host(lengthscales, d: int, family: str = "SquaredExponential", alpha=None):
+    """(host array, ard) of the C-ABI: the lengthscales and, for "RationalQuadratic", its alpha as one more trailing entry
+    (include/gpk.h, next to the family codes)."""
     ls = np.atleast_1d(np.asarray(lengthscales, dtype=np.float64))
     ard = ls.size > 1
     if ard and ls.size != d:
         raise ValueError(f"lengthscales has {ls.size} entries, input dimension is {d}")
-    return _lib.host_doubles(ls.tolist()), int(ard)
+    vals = ls.tolist()
+    if family == "RationalQuadratic":
+        if alpha is None:
+            raise ValueError("family 'RationalQuadratic' needs alpha")
+        vals.append(float(alpha))
+    elif alpha is not None:
+        raise ValueError(f"alpha belongs to the 'RationalQuadratic' family, not to {family!r}")
+    return _lib.host_doubles(vals), int(ard)
 
 
 def _noise_args(noise_variance, rows: int):
@@ -92,7 +103,7 @@ def _noise_args(noise_variance, rows: int):
 # ------------------------------------------------------------------------------------------------
 def kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, variance: float, lengthscales,
                   family: str = "SquaredExponential", diag_add: float = 0.0, lower_only: bool = False,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  alpha=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2]."""
     lib = _lib.load()
     _chk(X1, "X1", 2)
@@ -113,7 +124,7 @@ def kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, variance: flo
     _chk(out, "out", 2)
     if n1 == 0 or n2 == 0:   # nothing to compute (and X2 = NULL would mean K(X1, X1) at the C-ABI)
         return out
-    ls, ard = _ls_host(lengthscales, d)
+    ls, ard = _ls_host(lengthscales, d, family, alpha)
     rc = lib.gpk_kernel_matrix(_stream(), KERNEL_FAMILIES[family], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
                                X2.data_ptr() if X2 is not None else None, n2,
                                _rowmajor(X2, "X2") if X2 is not None else 0, d, ls, ard,
@@ -124,7 +135,7 @@ def kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, variance: flo
 
 
 def kernel_matrix_hadamard(X1: torch.Tensor, X2: torch.Tensor, G: torch.Tensor, *, variance: float, lengthscales,
-                           family: str = "SquaredExponential", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           family: str = "SquaredExponential", alpha=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """G .* K(X1, X2) with K recomputed on the fly -> [n1, n2] (the elementwise factor of the kernel backward)."""
     lib = _lib.load()
     _chk(X1, "X1", 2)
@@ -141,7 +152,7 @@ def kernel_matrix_hadamard(X1: torch.Tensor, X2: torch.Tensor, G: torch.Tensor, 
     _chk(out, "out", 2)
     if n1 == 0 or n2 == 0:
         return out
-    ls, ard = _ls_host(lengthscales, d)
+    ls, ard = _ls_host(lengthscales, d, family, alpha)
     rc = lib.gpk_kernel_matrix_hadamard(_stream(), KERNEL_FAMILIES[family], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
                                         X2.data_ptr(), n2, _rowmajor(X2, "X2"), d, ls, ard, float(variance),
                                         G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
@@ -150,12 +161,12 @@ def kernel_matrix_hadamard(X1: torch.Tensor, X2: torch.Tensor, G: torch.Tensor, 
 
 
 def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, variance: float,
-                          lengthscales, family: str = "SquaredExponential", diag_add: float = 0.0,
+                          lengthscales, family: str = "SquaredExponential", diag_add: float = 0.0, alpha=None,
                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = G .* K(X1, X2) (op "mul"), G + K(X1, X2) (op "add") or G .* (-2 dK/dr2)(X1, X2) (op "dr2": the factor of the
     lengthscale / input gradients of a stationary kernel; r2 = scaled squared distance), K recomputed on the fly; `out`
     may be G itself.  X2 None: K(X1, X1); `diag_add` goes onto the diagonal of the combined result ("mul" / "add"), and
-    "dr2" writes exact zeros on the diagonal."""
+    "dr2" writes exact zeros on the diagonal.  op "dalpha" ("RationalQuadratic" only): G .* dK/dalpha, diagonal as "dr2"."""
     lib = _lib.load()
     _chk(X1, "X1", 2)
     _chk(G, "G", 2)
@@ -174,8 +185,8 @@ def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch
     _chk(out, "out", 2)
     if n1 == 0 or n2 == 0:   # nothing to compute (and X2 = NULL would mean K(X1, X1) at the C-ABI)
         return out
-    ls, ard = _ls_host(lengthscales, d)
-    rc = lib.gpk_kernel_matrix_combine(_stream(), KERNEL_FAMILIES[family], {"mul": 1, "add": 2, "dr2": 3}[op], X1.data_ptr(), n1,
+    ls, ard = _ls_host(lengthscales, d, family, alpha)
+    rc = lib.gpk_kernel_matrix_combine(_stream(), KERNEL_FAMILIES[family], {"mul": 1, "add": 2, "dr2": 3, "dalpha": 4}[op], X1.data_ptr(), n1,
                                        _rowmajor(X1, "X1"), X2.data_ptr() if X2 is not None else None, n2,
                                        _rowmajor(X2, "X2") if X2 is not None else 0, d, ls, ard, float(variance),
                                        float(diag_add), G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(),
@@ -735,7 +746,7 @@ def symmetrize_(S: torch.Tensor) -> torch.Tensor:
 
 # ------------------------------------------------------------------------------------------------ fused
 def gpr_lml(X: torch.Tensor, Y: torch.Tensor, *, variance: float, lengthscales, noise_variance,
-            mean_const: float = 0.0, family: str = "SquaredExponential",
+            mean_const: float = 0.0, family: str = "SquaredExponential", alpha=None,
             ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(LML scalar tensor, info) -- gpk_gpr_lml.  noise_variance: a float, or one variance per data row [n]."""
     lib = _lib.load()
@@ -750,7 +761,7 @@ def gpr_lml(X: torch.Tensor, Y: torch.Tensor, *, variance: float, lengthscales, 
         ws = _ws(nbytes)
     out = torch.empty(1, dtype=torch.float64, device=X.device)
     info = torch.zeros(1, dtype=torch.int32, device=X.device)
-    ls, ard = _ls_host(lengthscales, d)
+    ls, ard = _ls_host(lengthscales, d, family, alpha)
     nv, nv_rows, _keep = _noise_args(noise_variance, n)
     rc = lib.gpk_gpr_lml(_stream(), KERNEL_FAMILIES[family], X.data_ptr(), n, d, _rowmajor(X, "X"),
                          Y.data_ptr(), P, _rowmajor(Y, "Y"), ls, ard, float(variance),
@@ -915,7 +926,7 @@ def svgp_elbo_workspace(m: int, rows: int, d: int, P: int, q_diag: bool, whiten:
 
 def svgp_elbo_shard(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: torch.Tensor,
                     q_sqrt: torch.Tensor, *, variance: float, lengthscales, noise_variance,
-                    jitter: float, mean_const: float = 0.0, family: str = "SquaredExponential",
+                    jitter: float, mean_const: float = 0.0, family: str = "SquaredExponential", alpha=None,
                     ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                     info: Optional[torch.Tensor] = None, whiten: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """One shard of SVGP.elbo: out[0] = sum_b var_exp_b over this shard, out[1] = KL.  Returns (out, info).
@@ -939,7 +950,7 @@ def svgp_elbo_shard(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: t
         out = torch.empty(2, dtype=torch.float64, device=Z.device)
     if info is None:
         info = torch.zeros(1, dtype=torch.int32, device=Z.device)
-    ls, ard = _ls_host(lengthscales, d)
+    ls, ard = _ls_host(lengthscales, d, family, alpha)
     nv, nv_rows, _keep = _noise_args(noise_variance, rows)
     rc = lib.gpk_svgp_elbo_shard(_stream(), KERNEL_FAMILIES[family], Z.data_ptr(), m, _rowmajor(Z, "Z"),
                                  Xb.data_ptr(), Yb.data_ptr(), rows, _rowmajor(Xb, "Xb"),
@@ -953,7 +964,7 @@ def svgp_elbo_shard(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: t
 
 def svgp_elbo_shard_lik(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor, *,
                         variance: float, lengthscales, lik: str, params=(), jitter: float, mean_const: float = 0.0,
-                        family: str = "SquaredExponential", ws: Optional[torch.Tensor] = None,
+                        family: str = "SquaredExponential", alpha=None, ws: Optional[torch.Tensor] = None,
                         out: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None,
                         whiten: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """svgp_elbo_shard with a non-Gaussian likelihood (lik, params as likelihood_varexp_sum) in place of the noise variance:
@@ -979,7 +990,7 @@ def svgp_elbo_shard_lik(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_m
         out = torch.empty(2, dtype=torch.float64, device=Z.device)
     if info is None:
         info = torch.zeros(1, dtype=torch.int32, device=Z.device)
-    ls, ard = _ls_host(lengthscales, d)
+    ls, ard = _ls_host(lengthscales, d, family, alpha)
     rc = lib.gpk_svgp_elbo_shard_lik(_stream(), KERNEL_FAMILIES[family], Z.data_ptr(), m, _rowmajor(Z, "Z"), Xb.data_ptr(),
                                      Yb.data_ptr(), rows, _rowmajor(Xb, "Xb"), _rowmajor(Yb, "Yb"), d, P, ls, ard,
                                      float(variance), code, par, float(jitter), float(mean_const), q_mu.data_ptr(),

@@ -69,6 +69,20 @@ extern "C" {
 #define GPK_KERN_MATERN12 1 /* :254-255 */
 #define GPK_KERN_MATERN32 2 /* :281-283 */
 #define GPK_KERN_MATERN52 3 /* :311-313 */
+#define GPK_KERN_EXPONENTIAL 4 /* Exponential.K_r: variance exp(-r / 2), r = sqrt(max(r2, 1e-36)) */
+#define GPK_KERN_RQ 5          /* RationalQuadratic.K_r2: variance (1 + r2 / (2 alpha))^-alpha, on r2 (no clamp) */
+/* static families (gpflow/kernels/statics.py): no distance, X is never read (a NaN in X does not reach the output) */
+#define GPK_KERN_WHITE 6    /* White.K: X2 == NULL: variance on the diagonal, 0 elsewhere;  ANY non-NULL X2: zeros -- decided by the
+                             * pointer, never by comparing values */
+#define GPK_KERN_CONSTANT 7 /* Constant.K: variance everywhere */
+/* K(x, x) = variance for all eight families: the one assumption the fused drivers make about a kernel.
+ *
+ * GPK_KERN_RQ carries one more hyperparameter and no C signature changes for it: `ls_host` then holds one more TRAILING entry,
+ * alpha at index (ard ? d : 1).  Every entry point that forwards one ls_host honours it (gpk_kernel_matrix, _combine, _hadamard,
+ * gpk_gpr_lml, gpk_svgp_elbo_shard, _lik); alpha <= 0 or a non-finite alpha is GPK_E_ARG.  It is evaluated as
+ * variance * exp(-alpha log1p(r2 / (2 alpha))).  gpk_svgp_elbo_shard_sep and _lcm stride ls_host by (ard ? d : 1) per latent and
+ * answer GPK_E_UNSUPPORTED for a GPK_KERN_RQ member; the other families pass through them (ls_host is not read for the static ones
+ * beyond being non-NULL; pass 1.0). */
 
 const char* gpk_version(void);
 
@@ -88,14 +102,18 @@ int gpk_kernel_matrix(void* stream, int family, const double* X1, int n1, long l
  * (utilities/model_utils.py:33-38, 46-50) -- the heteroskedastic counterpart of gpk_kernel_matrix's scalar diag_add. */
 int gpk_diag_add(void* stream, double* A, int n, long lda, const double* v);
 
-/* out = G .* k(X1, X2) (op 1), G + k(X1, X2) (op 2) or G .* (-2 dk/dr2)(X1, X2) (op 3), k recomputed from the inputs (one read of G, one write; G may
+/* out = G .* k(X1, X2) (op 1), G + k(X1, X2) (op 2), G .* (-2 dk/dr2)(X1, X2) (op 3) or G .* (dk/dalpha)(X1, X2) (op 4), k recomputed from the inputs (one read of G, one write; G may
  * alias out).  Replaces the tf.multiply / tf.add_n reductions of Product / Sum kernels (kernels/base.py:216-220,
  * 283-329): the second factor / term is folded into the first matrix in place instead of being materialised.
  * X2 == NULL: K(X1, X1), and diag_add goes onto the diagonal of the COMBINED result (noise / jitter).
  * op 3 is the reverse pass of the Matern family (stationaries.py:254-313: r = sqrt(max(r2, 1e-36)), K_r): with
  * r2 the SCALED squared distance, every lengthscale / input gradient contracts Kbar .* dk/dr2 with d r2 / d theta;
  * -2 dk/dr2 equals k for the SquaredExponential, so the same contraction code serves all four families.  X2 == NULL
- * writes exact zeros on the diagonal (r2_ii = 0 identically: no gradient flows through it). */
+ * writes exact zeros on the diagonal (r2_ii = 0 identically: no gradient flows through it).
+ * -2 dk/dr2: Exponential variance exp(-r / 2) / (2 r), 0 where r2 <= 1e-36 (the clamp passes no gradient, a NaN r2 stays NaN);
+ * RationalQuadratic variance exp(-(alpha + 1) log1p(u)), u = r2 / (2 alpha); White and Constant 0.
+ * op 4: GPK_KERN_RQ only (any other family: GPK_E_UNSUPPORTED), dk/dalpha = k (u / (1 + u) - log1p(u)); X2 == NULL writes exact
+ * zeros on the diagonal as op 3 does.  White, op 2, X2 given, out == G: nothing to do, returns without a launch. */
 int gpk_kernel_matrix_combine(void* stream, int family, int op, const double* X1, int n1, long ldx1,
                               const double* X2, int n2, long ldx2, int d, const double* ls_host, int ard,
                               double variance, double diag_add, const double* G, long ldg, double* out, long ldo);
