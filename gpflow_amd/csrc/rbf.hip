@@ -29,8 +29,6 @@ struct RbfArgs {
   double ls[GPK_MAX_D];
   const double* G; long ldg;  // COMB instantiations only: the output is G .* k(X1, X2) (1) or G + k(X1, X2) (2)
   int comb_diag;              // COMB: X2 is X1 and diag_add goes onto the diagonal of the combined result
-  int lds_mirror;             // symmetric full build: write the mirror tile as full rows through LDS
-  int nt_store;               // non-temporal stores for complete tiles
   double alpha;               // GPK_KERN_RQ only: the trailing entry of ls_host (gpk.h)
 };
 
@@ -180,13 +178,8 @@ __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
     const int gr = r0 + ty * 4 + i;
     if (full) {
       d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + c0 + tx * 4);
-      if (p.nt_store) {
-        __builtin_nontemporal_store((d2){v[i][0], v[i][1]}, out);
-        __builtin_nontemporal_store((d2){v[i][2], v[i][3]}, out + 1);
-      } else {
-        out[0] = (d2){v[i][0], v[i][1]};
-        out[1] = (d2){v[i][2], v[i][3]};
-      }
+      out[0] = (d2){v[i][0], v[i][1]};
+      out[1] = (d2){v[i][2], v[i][3]};
     } else if (gr < p.n1) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -195,34 +188,8 @@ __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
       }
     }
   }
-  if (mirror && r0 != c0 && full && p.lds_mirror) {
-    // The transposed copy, written as FULL ROWS: in the register layout a wave's store instruction of the mirror tile
-    // touches 16 rows x 4 pieces of 32 B (the lane index runs along the mirror tile's ROWS) -- a quarter of a 128-B line
-    // per piece.  Going through LDS ([64][65] doubles, after the input slabs are dead) lets every thread write the same
-    // 4 x 32 contiguous bytes per row as in the direct tile: 512 B contiguous per row per 16 lanes.
-    __syncthreads();                     // x1t / x2t / norms are no longer read
-    double* tl = sm;                     // [T][T + 1]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tl[(ty * 4 + i) * (T + 1) + tx * 4 + j] = v[i][j];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {        // mirror row c0 + ty*4 + i, mirror columns r0 + tx*4 + j  =  S[tx*4 + j][ty*4 + i]
-      const int gr = c0 + ty * 4 + i;
-      double m[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) m[j] = tl[(tx * 4 + j) * (T + 1) + ty * 4 + i];
-      d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + r0 + tx * 4);
-      if (p.nt_store) {
-        __builtin_nontemporal_store((d2){m[0], m[1]}, out);
-        __builtin_nontemporal_store((d2){m[2], m[3]}, out + 1);
-      } else {
-        out[0] = (d2){m[0], m[1]};
-        out[1] = (d2){m[2], m[3]};
-      }
-    }
-  } else if (mirror && r0 != c0) {  // transposed copy: rows c0 + tx*4 + j, columns r0 + ty*4 + i
+  // (full 16384^2 build: mirror tile through LDS 0.479 ms, this register layout 0.422; nt stores 0.455 / 0.429 -- profiles/r02_ab_kernel_builder.log)
+  if (mirror && r0 != c0) {  // transposed copy: rows c0 + tx*4 + j, columns r0 + ty*4 + i
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int gr = c0 + tx * 4 + j;
@@ -300,11 +267,7 @@ extern "C" int gpk_kernel_matrix(void* stream, int family, const double* X1, int
   a.family = family; a.lower_only = lower_only; a.ard = ard;
   if (const int rc = read_hypers(a, family, ls_host, ard, d)) return rc;
   if (a.n1 == 0 || a.n2 == 0) return 0;
-  // (A/B on the full 16384^2 build: mirror tile through LDS 0.479 ms, register layout 0.422 ms; nt stores 0.455 / 0.429)
-  a.lds_mirror = GPK_TUNE(RBF_LDS_MIRROR, 0);
-  a.nt_store = GPK_TUNE(RBF_NT_STORE, 0);
-  size_t lds = ((size_t)2 * d * T + 2 * T) * sizeof(double);
-  if (a.sym && !a.lower_only && a.lds_mirror) lds = std::max(lds, (size_t)T * (T + 1) * sizeof(double));
+  const size_t lds = ((size_t)2 * d * T + 2 * T) * sizeof(double);
   dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
   return launch_combine<0>((hipStream_t)stream, family, a, grid, lds);
 }

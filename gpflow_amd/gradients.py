@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .ops import STATIC_FAMILIES   # (White, Constant: no distance, no lengthscale or input gradient)
+from .leaf import Leaf
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -150,35 +150,35 @@ def ls_device(lengthscales, D: int, device) -> torch.Tensor:
     return t
 
 
-def stationary_kernel_adjoint(A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, variance: float, lengthscales,
-                              symmetric: bool, family: str = "SquaredExponential", packed_into=None, dvar_add: float = 0.0,
-                              return_packed: bool = False, alpha=None):
-    """Adjoint of K = variance * f(r(A / ls, Bm / ls)) [n1, n2] given Kbar [n1, n2], f one of the stationary families of
-    `ops.KERNEL_FAMILIES` (stationaries.py:209-210 SquaredExponential, :254-313 Matern12 / 32 / 52; Exponential; RationalQuadratic
-    with its `alpha`; the static families have no distance and never come here: KernelSpec._adjoint).
+def stationary_kernel_adjoint(leaf: Leaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, symmetric: bool, packed_into=None,
+                              dvar_add: float = 0.0, return_packed: bool = False):
+    """Adjoint of K = variance * f(r(A / ls, Bm / ls)) [n1, n2] given Kbar [n1, n2], `leaf` of one of the stationary families
+    (stationaries.py:209-210 SquaredExponential, :254-313 Matern12 / 32 / 52; Exponential; RationalQuadratic with its `alpha`; the
+    static families have no distance and never come here: KernelSpec._adjoint).
 
-    Returns (d/dvariance, d/dlengthscales [D], A_bar [n1, D]); with symmetric=True (Bm is A, Kbar symmetric) A_bar
-    collects both arguments.  B_bar of the non-symmetric case is not needed on this path (B = the minibatch).
+    Returns (d/dvariance, shape gradient, A_bar [n1, D]); the shape gradient is laid out like the leaf's `ls_host` for every family:
+    d/dlengthscales as the leaf holds them ([1] isotropic, else [D]), then one entry per extra.  With symmetric=True (Bm is A, Kbar
+    symmetric) A_bar collects both arguments.  B_bar of the non-symmetric case is not needed on this path (B = the minibatch).
 
     With r2 the scaled squared distance, dF/dtheta = sum_ij Kbar_ij dK_ij/dr2 dr2_ij/dtheta.  G = Kbar .* (-2 dK/dr2) is
     one elementwise pass that recomputes r2 from the inputs (`gpk_kernel_matrix_combine` op 3); for the
     SquaredExponential -2 dK/dr2 = K, so G also carries d/dvariance = sum(Kbar .* K) / variance; the Matern families
-    take that sum from a second pass (op 1).  d/dvariance = sum(Kbar .* K) / variance holds for every family.  The RationalQuadratic
-    adds d/dalpha = sum(Kbar .* dK/dalpha) (op 4, into the same buffer) and returns it as a fourth value [1]."""
+    take that sum from a second pass (op 1).  d/dvariance = sum(Kbar .* K) / variance holds for every family.  An extra `x` of
+    the family (the RationalQuadratic's alpha) adds d/dx = sum(Kbar .* dK/dx) (op "d" + x: "dalpha", into the same buffer)."""
     n1, D = A.shape
+    variance, lengthscales = leaf.variance, leaf.lengthscales
     ls = ls_device(lengthscales, D, A.device)
-    akw = {} if alpha is None else {"alpha": alpha}   # (the keyword exists for the family that has it: ops._ls_host)
-    if family == "SquaredExponential":
+    dextras = []
+    if leaf.family == "SquaredExponential":
         G = ops.kernel_matrix_hadamard(A, Bm, Kbar, variance=variance, lengthscales=lengthscales)   # Kbar .* K
         sum_kbar_k = None
     else:
-        G = ops.kernel_matrix_hadamard(A, Bm, Kbar, variance=variance, lengthscales=lengthscales, family=family, **akw)
+        kw = leaf.keywords()
+        G = ops.kernel_matrix_hadamard(A, Bm, Kbar, **kw)
         sum_kbar_k = G.sum()
-        if family == "RationalQuadratic":
-            dalpha = ops.kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="dalpha", variance=variance,
-                                               lengthscales=lengthscales, family=family, out=G, **akw).sum().reshape(1)
-        ops.kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="dr2", variance=variance,
-                                  lengthscales=lengthscales, family=family, out=G, **akw)
+        for name in leaf.row.extras:
+            dextras.append(ops.kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="d" + name, out=G, **kw).sum().reshape(1))
+        ops.kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="dr2", out=G, **kw)
     Vt = ops.moment_rows(Bm)                         # [1, B, B^2]^T
     R = splitk_gemm_nt(G, Vt)                        # [n1, 1 + 2D] = G [1, B, B^2]: row sums rs, G B, G B^2
     # one launch for what follows (it was a dozen elementwise / reduction launches on [n1, D] arrays):  T = G B - A rs;
@@ -190,26 +190,23 @@ def stationary_kernel_adjoint(A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Ten
                                                   symmetric=symmetric, sum_kbar_k=sum_kbar_k, into=packed_into, dvar_add=dvar_add)
     if return_packed:
         return (packed_into[0] if packed_into is not None else dls._base), Abar
-    if family == "RationalQuadratic":
-        return dvar, dls, Abar, dalpha
-    return dvar, dls, Abar
+    return dvar, torch.cat([_ls_grad(dls, leaf), *dextras]), Abar
 
 
-def _ls_grad(dl: torch.Tensor, ls) -> torch.Tensor:
-    """d/dlengthscales as the member holds them: an isotropic member has ONE lengthscale, the sum of the per-column entries"""
-    return dl.sum().reshape(1) if np.size(ls) == 1 else dl
+def _ls_grad(dl: torch.Tensor, leaf: Leaf) -> torch.Tensor:
+    """d/dlengthscales as the leaf holds them: an isotropic one has ONE lengthscale, the sum of the per-column entries"""
+    return dl.sum().reshape(1) if leaf.n_lengthscales == 1 else dl
 
 
 class KernelSpec:
     """What the reverse pass needs to know about the covariance function: ONE stationary kernel, or a Sum / Product of
     stationary / static kernels -- flat, or nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220 `Sum`, :305-315 `Product`; the reference
-    differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).  members: [(family, variance,
-    lengthscales) or (family, variance, lengthscales, alpha)], op: None | "add" | "mul" | tree.  A RationalQuadratic member carries its
-    `alpha` (kept beside the triples, in `alphas`); a static member (White, Constant) a dummy lengthscale 1.0.
+    differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).  members: leaves (leaf.Leaf), given as such or as
+    tuples (family, variance, lengthscales[, alpha]); op: None | "add" | "mul" | tree.
 
-    A member's SHAPE gradient -- the `dl` entry of `adjoint` -- is laid out like `ls_host` of the C-ABI: the lengthscale entries,
-    then alpha where the family has one; a static member's is empty (no lengthscale, no input gradient: A_bar is zero and no
-    contraction is launched for it).  `kernel_grads` splits it into the "lengthscales" / "alpha" entries of a `grads` dict.
+    A member's SHAPE gradient -- the `dl` entry of `adjoint` -- is laid out like the leaf's `ls_host`: the lengthscale entries,
+    then the extras; a static member's is empty (no lengthscale, no input gradient: A_bar is zero and no contraction is launched
+    for it).  `kernel_grads` has the leaves split it into the "lengthscales" / "alpha" entries of a `grads` dict.
 
       build    the combined matrix, members folded in place by `gpk_kernel_matrix_combine` (no second matrix);
       kdiag    K(x, x): sum or product of the variances (stationary members), dkdiag[i] = d kdiag / d variance_i;
@@ -217,14 +214,10 @@ class KernelSpec:
                and goes through `stationary_kernel_adjoint`; the input gradients of the members add up."""
 
     def __init__(self, members, op=None, cols=None):
-        """members: [(family, variance, lengthscales)]; cols[i]: the input columns member i sees (its `active_dims` as an index
+        """members: leaves or tuples, see the class; cols[i]: the input columns member i sees (its `active_dims` as an index
         list, kernels/base.py:90-109) or None for all of them.  Members that see different columns are built and differentiated on
         their own column slices; their input gradients are scattered back into the full columns and add up."""
-        self.members = [(m[0], float(m[1]), np.asarray(m[2], dtype=np.float64)) for m in members]
-        self.alphas = [float(m[3]) if len(m) > 3 and m[3] is not None else None for m in members]
-        for (f, _, _), a in zip(self.members, self.alphas):
-            if (f == "RationalQuadratic") != (a is not None):
-                raise ValueError("alpha belongs to 'RationalQuadratic' members, and every such member needs one")
+        self.members = [m if isinstance(m, Leaf) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
         # (k0 + k1) * k2 (kernels/base.py:223-329: a Combination holds kernels, which may be Combinations of the other kind).
@@ -243,27 +236,12 @@ class KernelSpec:
 
     @staticmethod
     def single(variance, lengthscales, family="SquaredExponential", alpha=None):
-        return KernelSpec([(family, variance, 1.0 if lengthscales is None else lengthscales, alpha)], None)
-
-    def _akw(self, i: int) -> dict:
-        """member i's extra keyword of the ops builders: alpha for a RationalQuadratic member, nothing for the others"""
-        return {} if self.alphas[i] is None else {"alpha": self.alphas[i]}
-
-    def is_static(self, i: int) -> bool:
-        return self.members[i][0] in STATIC_FAMILIES
-
-    def n_lengthscales(self, i: int) -> int:
-        """lengthscale entries member i holds (1 = isotropic, 0 = static)"""
-        return 0 if self.is_static(i) else int(np.size(self.members[i][2]))
-
-    def n_shape(self, i: int) -> int:
-        """entries of member i's shape gradient: its lengthscales, then alpha"""
-        return self.n_lengthscales(i) + (self.alphas[i] is not None)
+        return KernelSpec([Leaf(family, variance, lengthscales, alpha=alpha)], None)
 
     @property
     def packable(self) -> bool:
         """one member whose two adjoints fit the packed tail of `_covariance_tail` ([variance, lengthscales] and A_bar in one launch)"""
-        return self.n == 1 and self.cols[0] is None and self.alphas[0] is None and not self.is_static(0)
+        return self.n == 1 and self.cols[0] is None and self.members[0].is_plain
 
     @staticmethod
     def _check_tree(node, n):
@@ -300,19 +278,17 @@ class KernelSpec:
 
     def _build(self, node, X1, X2, out, diag_add=0.0):
         if isinstance(node, int):
-            f, v, ls = self.members[node]
-            return ops.kernel_matrix(self._sl(node, X1), self._sl(node, X2), variance=v, lengthscales=ls, family=f,
-                                     diag_add=diag_add, lower_only=False, out=out, **self._akw(node))
+            return ops.kernel_matrix(self._sl(node, X1), self._sl(node, X2), diag_add=diag_add, lower_only=False, out=out,
+                                     **self.members[node].keywords())
         op, ch = node
         if len(ch) == 1:
             return self._build(ch[0], X1, X2, out, diag_add)
         last = len(ch) - 1
         out = self._build(ch[0], X1, X2, out)
         for j, c in enumerate(ch[1:], start=1):
-            if isinstance(c, int):      # a stationary member folds in place (K recomputed in registers, no second matrix);
-                f, v, ls = self.members[c]   # diag_add rides in the LAST member's launch
-                ops.kernel_matrix_combine(self._sl(c, X1), self._sl(c, X2), out, op=op, variance=v, lengthscales=ls, family=f,
-                                          diag_add=diag_add if j == last else 0.0, out=out, **self._akw(c))
+            if isinstance(c, int):      # a leaf folds in place (K recomputed in registers, no second matrix);
+                ops.kernel_matrix_combine(self._sl(c, X1), self._sl(c, X2), out, op=op,   # diag_add rides in the LAST member's launch
+                                          diag_add=diag_add if j == last else 0.0, out=out, **self.members[c].keywords())
             else:                        # a sub-combination needs its own matrix once
                 tmp = self._build(c, X1, X2, None)
                 out.add_(tmp) if op == "add" else out.mul_(tmp)
@@ -322,7 +298,7 @@ class KernelSpec:
 
     def _kd(self, node) -> float:
         if isinstance(node, int):
-            return self.members[node][1]
+            return self.members[node].variance
         vals = [self._kd(c) for c in node[1]]
         return float(np.prod(vals)) if node[0] == "mul" else float(np.sum(vals))
 
@@ -347,9 +323,9 @@ class KernelSpec:
 
     def warm(self, device, D: int) -> "KernelSpec":
         """device copies of the members' lengthscales, made now (see `ls_device`)"""
-        for i, (_, _, ls) in enumerate(self.members):
-            if not self.is_static(i):
-                ls_device(ls, D if self.cols[i] is None else len(self.cols[i]), device)
+        for i, leaf in enumerate(self.members):
+            if not leaf.is_static:
+                ls_device(leaf.lengthscales, D if self.cols[i] is None else len(self.cols[i]), device)
         return self
 
     def adjoint(self, A, Bm, Kbar, symmetric: bool):
@@ -361,18 +337,17 @@ class KernelSpec:
 
     def _adjoint(self, node, A, Bm, Kbar, symmetric, acc):
         if isinstance(node, int):
-            f, v, ls = self.members[node]
-            if self.is_static(node):
+            leaf = self.members[node]
+            if leaf.is_static:
                 # d/dvariance = sum(Kbar .* K) / variance read off directly: every entry (Constant), the diagonal of K(A, A) (White:
                 # NOT through the X2-given hadamard, which is zeros for it), nothing where White sees two sets of points
-                dv = Kbar.sum() if f == "Constant" else torch.diagonal(Kbar).sum() if symmetric else Kbar.new_zeros(())
+                dv = Kbar.sum() if leaf.family == "Constant" else torch.diagonal(Kbar).sum() if symmetric else Kbar.new_zeros(())
                 acc["dl"][node], acc["dv"][node] = Kbar.new_zeros(0), dv.reshape(1)
                 return
             Ai = self._sl(node, A)
             Bi = Ai if (symmetric and Bm is A) else self._sl(node, Bm)
-            dv, dl, Ab, *da = stationary_kernel_adjoint(Ai, Bi, Kbar, symmetric=symmetric, variance=v, lengthscales=ls, family=f,
-                                                        alpha=self.alphas[node])
-            acc["dl"][node], acc["dv"][node] = torch.cat([_ls_grad(dl, ls), *da]), dv.reshape(1)
+            dv, dl, Ab = stationary_kernel_adjoint(leaf, Ai, Bi, Kbar, symmetric=symmetric)
+            acc["dl"][node], acc["dv"][node] = dl, dv.reshape(1)
             if all(c is None for c in self.cols):
                 acc["Abar"] = Ab if acc["Abar"] is None else acc["Abar"] + Ab
             else:   # scatter the member's input gradient back into the columns it read
@@ -392,9 +367,8 @@ class KernelSpec:
                     if jo == jc:
                         continue
                     if isinstance(o, int):
-                        fo, vo, lo = self.members[o]
-                        ops.kernel_matrix_combine(self._sl(o, A), None if symmetric else self._sl(o, Bm), Kb, op="mul", variance=vo,
-                                                  lengthscales=lo, family=fo, out=Kb, **self._akw(o))
+                        ops.kernel_matrix_combine(self._sl(o, A), None if symmetric else self._sl(o, Bm), Kb, op="mul", out=Kb,
+                                                  **self.members[o].keywords())
                     else:
                         Kb.mul_(self._build(o, A, None if symmetric else Bm, None))
             self._adjoint(c, A, Bm, Kb, symmetric, acc)
@@ -409,16 +383,10 @@ class KernelSpec:
     def kernel_grads(self, g_var, g_shape) -> dict:
         """the kernel's entries of a `grads` dict from what `pack` returned: "variance", "lengthscales" (a static member's is empty)
         and -- only when a member has one -- "alpha": [1] for one member, else a list with None for the members without"""
-        nl = [self.n_lengthscales(i) for i in range(self.n)]
         if self.n == 1:
-            out = {"variance": g_var, "lengthscales": g_shape[:nl[0]] if self.n_shape(0) != nl[0] else g_shape}
-            if self.alphas[0] is not None:
-                out["alpha"] = g_shape[nl[0]:]
-            return out
-        out = {"variance": g_var, "lengthscales": [g[:n] if g.numel() != n else g for g, n in zip(g_shape, nl)]}
-        if any(a is not None for a in self.alphas):
-            out["alpha"] = [g[n:] if a is not None else None for g, n, a in zip(g_shape, nl, self.alphas)]
-        return out
+            return {"variance": g_var, **self.members[0].split_shape(g_shape)}
+        parts = [leaf.split_shape(g) for leaf, g in zip(self.members, g_shape)]
+        return {"variance": g_var, **{name: [p.get(name) for p in parts] for name in dict.fromkeys(k for p in parts for k in p)}}
 
 
 class _Seed:
@@ -554,12 +522,10 @@ def _covariance_tail(spec: KernelSpec, Z, Xb, Kuf_bar, LT, LinvT, Lbar, knn_bar,
     if packed:
         # one stationary kernel over all input columns: the second adjoint ADDS its variance / lengthscale / Z gradients to the
         # first one's in its own tail launch, and the Knn term of d/dvariance rides along (no elementwise launches at all)
-        fam1, var1, ls1 = spec.members[0]
-        into = stationary_kernel_adjoint(Z, Xb, Kuf_bar, variance=var1, lengthscales=ls1, symmetric=False, family=fam1,
-                                         dvar_add=knn_bar * dkd[0], return_packed=True)
-        small_g, Zbar = stationary_kernel_adjoint(Z, Z, Kuu_bar, variance=var1, lengthscales=ls1, symmetric=True, family=fam1,
-                                                  packed_into=into, return_packed=True)
-        return small_g[0:1], _ls_grad(small_g[1:], ls1), Zbar
+        leaf = spec.members[0]
+        into = stationary_kernel_adjoint(leaf, Z, Xb, Kuf_bar, symmetric=False, dvar_add=knn_bar * dkd[0], return_packed=True)
+        small_g, Zbar = stationary_kernel_adjoint(leaf, Z, Z, Kuu_bar, symmetric=True, packed_into=into, return_packed=True)
+        return small_g[0:1], _ls_grad(small_g[1:], leaf), Zbar
     dv1, dl1, Zb1 = first if first is not None else spec.adjoint(Z, Xb, Kuf_bar, symmetric=False)
     dv2, dl2, Zb2 = spec.adjoint(Z, Z, Kuu_bar, symmetric=True)
     g_var, g_ls = spec.pack([a + b + knn_bar * dk for a, b, dk in zip(dv1, dv2, dkd)], [a + b for a, b in zip(dl1, dl2)])
@@ -873,7 +839,7 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
     kdiag = spec.kdiag()
     nmem = spec.n
-    nlsm = [spec.n_shape(i) for i in range(nmem)]              # shape-gradient entries per member (lengthscales: 1 = isotropic; + alpha)
+    nlsm = [leaf.n_shape for leaf in spec.members]             # shape-gradient entries per member (lengthscales: 1 = isotropic; + extras)
 
     def all_reduce(t):
         if sharded:

@@ -9,6 +9,7 @@ import torch
 
 from ..base import Module
 from .. import ops
+from ..leaf import BY_NAME, Leaf
 
 ActiveDims = Union[slice, Sequence[int]]
 
@@ -89,18 +90,31 @@ class Kernel(Module, metaclass=abc.ABCMeta):
         return self.K(X, X2)
 
 
+class DeviceLeaf(Kernel):
+    """A kernel that gpk_kernel_matrix builds from host hyperparameters (the stationary and the static families): `family` names its
+    row of leaf.FAMILIES, `leaf()` is its current values and `leaf_params()` the Parameters behind them, in the same order;
+    K_diag = variance."""
+    family: Optional[str] = None
+    device_leaf = True
+
+    def leaf_params(self) -> tuple:
+        return tuple(getattr(self, name) for name in BY_NAME[self.family].parameters)
+
+    def leaf(self) -> Leaf:
+        return Leaf.of(self.family, [p.numpy() for p in self.leaf_params()])
+
+    def K_diag(self, X) -> torch.Tensor:
+        """stationaries.py:82-83, `Static.K_diag`: exactly the variance"""
+        X = ops.to_device(X)
+        return torch.full(X.shape[:-1], float(self.variance.numpy()), dtype=torch.float64, device=X.device)
+
+    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
+        return ops.kernel_matrix(X, X2, diag_add=diag_add, lower_only=lower_only, out=out, **self.leaf().keywords())
+
+
 def is_device_leaf(k) -> bool:
-    """True for a kernel that gpk_kernel_matrix builds from host hyperparameters: it answers `hyper()` -> (family, variance,
-    lengthscales; a dummy 1.0 for a static kernel), `hyper_alpha()` -> alpha | None and `hyper_extra()` -> that as the builders'
-    extra keyword, and has K_diag = variance.  The one notion
-    Combination.K_into, gradient_spec and the model routes share."""
+    """True for a DeviceLeaf of a known family.  The one notion Combination.K_into, gradient_spec and the model routes share."""
     return bool(getattr(k, "device_leaf", False)) and getattr(k, "family", None) in ops.KERNEL_FAMILIES
-
-
-def leaf_parameters(k):
-    """the Parameters of a device-built leaf, in the order of its hyperparameters: (variance, lengthscales), with alpha behind them
-    for a RationalQuadratic, (variance,) for a static kernel"""
-    return tuple(p for p in (k.variance, getattr(k, "lengthscales", None), getattr(k, "alpha", None)) if p is not None)
 
 
 class Combination(Kernel):
@@ -144,9 +158,7 @@ class Combination(Kernel):
             Xs, X2s = k.slice(X, X2)
             dadd = diag_add if i == last else 0.0
             if is_device_leaf(k):
-                family, var, ls = k.hyper()
-                ops.kernel_matrix_combine(Xs, X2s, out, op=self._op, variance=var, lengthscales=ls, family=family,
-                                          diag_add=dadd, out=out, **k.hyper_extra())
+                ops.kernel_matrix_combine(Xs, X2s, out, op=self._op, diag_add=dadd, out=out, **k.leaf().keywords())
             else:
                 Ki = k.K_into(Xs, X2s, None)
                 out.add_(Ki) if self._op == "add" else out.mul_(Ki)
@@ -210,8 +222,7 @@ def gradient_spec(kernel, input_dim=None):
             cols.append(np.arange(int(input_dim))[k.active_dims])
         else:
             cols.append(np.asarray(k.active_dims, dtype=np.int64))
-    spec = gradients.KernelSpec([k.hyper() + (k.hyper_alpha(),) for k in ks], tree, cols=cols)
-    return spec, [leaf_parameters(k) for k in ks]
+    return gradients.KernelSpec([k.leaf() for k in ks], tree, cols=cols), [k.leaf_params() for k in ks]
 
 
 class Sum(Combination):

@@ -5,44 +5,21 @@ from __future__ import annotations
 
 from typing import Optional
 
-import numpy as np
 import torch
 
 from ..base import Parameter, positive
 from .. import ops
-from .base import ActiveDims, Kernel
+from .base import ActiveDims, DeviceLeaf
 
 
-class Static(Kernel):
+class Static(DeviceLeaf):
     """statics.py `Static`.  `family` names the device code; the builder decides White's diagonal by whether X2 is None, never by
     comparing values, as `White.K` does."""
     family = "Constant"
-    device_leaf = True
 
     def __init__(self, variance=1.0, active_dims: Optional[ActiveDims] = None, name: Optional[str] = None):
         super().__init__(active_dims=active_dims, name=name)
         self.variance = Parameter(variance, transform=positive())
-
-    def K_diag(self, X) -> torch.Tensor:
-        """`Static.K_diag`: fill(X.shape[:-1], variance)"""
-        X = ops.to_device(X)
-        return torch.full(X.shape[:-1], float(self.variance.numpy()), dtype=torch.float64, device=X.device)
-
-    def hyper(self):
-        """(family, variance, lengthscales) as host values for the C-ABI; a static kernel has no lengthscale and hands the
-        builder a dummy 1.0 that is never read."""
-        return self.family, float(self.variance.numpy()), np.asarray(1.0, dtype=np.float64)
-
-    def hyper_alpha(self):
-        return None
-
-    def hyper_extra(self) -> dict:
-        return {}
-
-    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
-        family, var, ls = self.hyper()
-        return ops.kernel_matrix(X, X2, variance=var, lengthscales=ls, family=family, diag_add=diag_add,
-                                 lower_only=lower_only, out=out)
 
     def K(self, X, X2=None) -> torch.Tensor:
         X = ops.to_device(X)

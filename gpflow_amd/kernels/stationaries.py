@@ -5,17 +5,15 @@ from __future__ import annotations
 
 from typing import Any, Optional
 
-import numpy as np
 import torch
 
 from ..base import Parameter, positive
 from .. import ops
-from .base import Kernel
+from .base import DeviceLeaf
 
 
-class Stationary(Kernel):
+class Stationary(DeviceLeaf):
     family = "SquaredExponential"
-    device_leaf = True   # built by gpk_kernel_matrix from hyper() (+ hyper_alpha()): what Combination.K_into and gradient_spec ask
 
     def __init__(self, variance=1.0, lengthscales=1.0, **kwargs: Any):
         for kwarg in kwargs:
@@ -38,30 +36,6 @@ class Stationary(Kernel):
     @property
     def ard(self) -> bool:
         return self.lengthscales.numpy().ndim > 0
-
-    def K_diag(self, X) -> torch.Tensor:
-        """stationaries.py:82-83: exactly sigma^2"""
-        X = ops.to_device(X)
-        return torch.full(X.shape[:-1], float(self.variance.numpy()), dtype=torch.float64, device=X.device)
-
-    # device entry used by the covariance dispatchers and the fused model paths ------------------
-    def hyper(self):
-        """(family, variance, lengthscales) as host values for the C-ABI."""
-        return self.family, float(self.variance.numpy()), np.asarray(self.lengthscales.numpy(), dtype=np.float64)
-
-    def hyper_alpha(self):
-        """the family's extra shape parameter as a host value (RationalQuadratic), None where the family has none"""
-        return None
-
-    def hyper_extra(self) -> dict:
-        """the same as the extra keyword of the ops builders: {"alpha": value}, or {} for a family without one"""
-        a = self.hyper_alpha()
-        return {} if a is None else {"alpha": a}
-
-    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
-        family, var, ls = self.hyper()
-        return ops.kernel_matrix(X, X2, variance=var, lengthscales=ls, family=family, diag_add=diag_add,
-                                 lower_only=lower_only, out=out, **self.hyper_extra())
 
 
 class IsotropicStationary(Stationary):
@@ -103,9 +77,6 @@ class RationalQuadratic(IsotropicStationary):
     def __init__(self, variance=1.0, lengthscales=1.0, alpha=1.0, active_dims=None, name=None):
         super().__init__(variance=variance, lengthscales=lengthscales, active_dims=active_dims, name=name)
         self.alpha = Parameter(alpha, transform=positive())
-
-    def hyper_alpha(self):
-        return float(self.alpha.numpy())
 
 
 class Matern12(IsotropicStationary):

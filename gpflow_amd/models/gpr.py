@@ -42,10 +42,8 @@ class GPR(GPModel, InternalDataTrainingLossMixin):
         c = self.mean_function.constant_value()
         if is_device_leaf(self.kernel) and c is not None:
             Xs, _ = self.kernel.slice(X, None)
-            family, var, ls = self.kernel.hyper()
-            out, info = ops.gpr_lml(Xs, Y, variance=var, lengthscales=ls,
-                                    noise_variance=self.likelihood.noise_for(X), mean_const=c,
-                                    family=family, ws=self._ws, **self.kernel.hyper_extra())
+            out, info = ops.gpr_lml(Xs, Y, noise_variance=self.likelihood.noise_for(X), mean_const=c, ws=self._ws,
+                                    **self.kernel.leaf().keywords())
             ops.check_info(info)
             return out[0]
         K = self.kernel(X)

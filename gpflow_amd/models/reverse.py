@@ -10,7 +10,7 @@ from .. import gradients
 from ..base import FillTriangular
 from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
-from ..kernels.base import Combination, gradient_spec, is_device_leaf, leaf_parameters
+from ..kernels.base import Combination, gradient_spec, is_device_leaf
 from ..kernels.statics import Static
 from ..kernels.stationaries import IsotropicStationary
 from ..likelihoods import Gaussian
@@ -53,9 +53,9 @@ def _supported_stationary(k) -> bool:
 
 
 class CovarianceRoute:
-    """One covariance function as the reverse pass takes it: `spec` (gradients.KernelSpec), `members` [(variance Parameter,
-    lengthscales Parameter)] in the spec's order (a RationalQuadratic member: (variance, lengthscales, alpha); a static one:
-    (variance,)), the inputs as `gradients.*` gets them and the scatter of dF/dZ back to Z's columns.
+    """One covariance function as the reverse pass takes it: `spec` (gradients.KernelSpec), `members` [the Parameters of each leaf,
+    in the leaf's order: DeviceLeaf.leaf_params] in the spec's order, the inputs as `gradients.*` gets them and the scatter of dF/dZ
+    back to Z's columns.
       one SquaredExponential / Matern kernel: a one-member spec over ALL columns of inputs sliced by its `active_dims` out here
         (a spec with `cols` would leave the packed covariance tail of gradients.svgp_elbo_and_grad);
       a Sum / Product of them, flat or nested: kernels.base.gradient_spec -- the spec slices for its members itself.
@@ -67,8 +67,7 @@ class CovarianceRoute:
         if self.is_combination:
             self.spec, self.members = gradient_spec(kernel, input_dim)
         elif _supported_stationary(kernel):
-            family, var, ls = kernel.hyper()
-            self.spec, self.members = gradients.KernelSpec.single(var, ls, family, kernel.hyper_alpha()), [leaf_parameters(kernel)]
+            self.spec, self.members = gradients.KernelSpec([kernel.leaf()]), [kernel.leaf_params()]
         else:
             raise NotImplementedError("gradients: a SquaredExponential / Matern / Exponential / RationalQuadratic / White / Constant "
                                       "kernel, or a Sum / Product (possibly nested) of them")
@@ -82,25 +81,17 @@ class CovarianceRoute:
         return sliced(self.kernel, Z, X)
 
     def spec_at(self, values):
-        """the spec with the members' values replaced, each laid out as its `members` entry: (variance, lengthscales), with alpha
-        behind them for a RationalQuadratic member, (variance,) for a static one (the trainer's current values)"""
-        def member(i, f, vals):
-            v, rest = vals[0], list(vals[1:])
-            ls = 1.0 if self.spec.is_static(i) else rest.pop(0)
-            return (f, v, ls, rest.pop(0) if self.spec.alphas[i] is not None else None)
-        return gradients.KernelSpec([member(i, f, vals) for i, ((f, _, _), vals) in enumerate(zip(self.spec.members, values))],
-                                    self.spec.tree, self.spec.cols)
+        """the spec with the members' values replaced, each laid out as its `members` entry (the trainer's current values)"""
+        return gradients.KernelSpec([leaf.replace(vals) for leaf, vals in zip(self.spec.members, values)], self.spec.tree, self.spec.cols)
 
     def member_grads(self, g):
-        """[(d/dvariance_i [1], d/dlengthscales_i)] from the `grads` of a `gradients.*` call, each entry laid out as the member's
-        `members` entry (d/dalpha_i [1] behind them for a RationalQuadratic member, d/dvariance_i alone for a static one): the one place
-        that knows the two packings of KernelSpec.pack / kernel_grads (one member: "variance" [1], "lengthscales" a tensor, "alpha" [1];
-        several: "variance" [n] and lists)"""
+        """[(d/dvariance_i [1], ...)] from the `grads` of a `gradients.*` call, each entry laid out as the member's `members` entry: the
+        one place that knows the two packings of KernelSpec.pack / kernel_grads (one member: "variance" [1] and one tensor per name;
+        several: "variance" [n] and one list per name)"""
         one = self.spec.n == 1
-        gv, gl = g["variance"].reshape(-1), ([g["lengthscales"]] if one else g["lengthscales"])
-        ga = ([g["alpha"]] if one else g["alpha"]) if "alpha" in g else [None] * self.spec.n
-        return [(gv[i:i + 1],) + (() if self.spec.is_static(i) else (gl[i].reshape(-1),)) + (() if ga[i] is None else (ga[i].reshape(-1),))
-                for i in range(self.spec.n)]
+        gv = g["variance"].reshape(-1)
+        return [(gv[i:i + 1],) + tuple((g[name] if one else g[name][i]).reshape(-1) for name in leaf.row.parameters[1:])
+                for i, leaf in enumerate(self.spec.members)]
 
     def kernel_pairs(self, g):
         """[(Parameter, dF/d constrained as NumPy)] of the members, in member order (the variances come back in one copy)"""

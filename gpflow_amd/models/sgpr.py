@@ -180,9 +180,8 @@ class SGPR(GPModel, InternalDataTrainingLossMixin):
             route = CovarianceRoute(k, self.data[0].shape[1])
             Z, X, _ = route.inputs(iv.Z.device_value().contiguous(), self.data[0])
             return route.spec, X, Z, float(c), s2
-        family, var, ls = k.hyper()
         X, Z = k.slice(self.data[0], iv.Z.device_value())
-        return gradients.KernelSpec.single(var, ls, family, k.hyper_alpha()), X, Z, float(c), s2
+        return gradients.KernelSpec([k.leaf()]), X, Z, float(c), s2
 
     def _noise_rows(self):
         return self.likelihood.noise_for(self.data[0]) if self.likelihood.is_heteroskedastic else None

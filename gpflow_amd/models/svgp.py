@@ -13,6 +13,7 @@ from ..inducing_variables import (InducingPoints, SharedIndependentInducingVaria
                                   inducingpoint_wrapper)
 from ..kernels import Kernel
 from ..kernels.base import is_device_leaf
+from ..leaf import latent_keywords
 from ..likelihoods import Gaussian, Likelihood, MultiClass, ScalarLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
@@ -237,20 +238,6 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         ops.check_info(info)
         return torch.stack([var_exp.sum(), kl])
 
-    @staticmethod
-    def _member_hypers(kernels, d):
-        """([(family, variance, lengthscales)] per member, lengthscales [P] or [P, d]) as the per-latent shards take them"""
-        if any(k.hyper_alpha() is not None for k in kernels):
-            raise NotImplementedError("SeparateIndependent / LinearCoregionalization with a RationalQuadratic member: the fused per-latent "
-                                      "shard strides its lengthscales by latent and has no slot for alpha (include/gpk.h)")
-        hyp = [k.hyper() for k in kernels]
-        ls = [np.atleast_1d(h[2]) for h in hyp]
-        if any(l.size > 1 for l in ls):   # mixed isotropic / ARD members: every row spelled out
-            ls = np.stack([np.broadcast_to(l, (d,)) for l in ls])
-        else:
-            ls = np.concatenate(ls)
-        return hyp, ls
-
     def elbo_terms(self, data):
         """(sum_b var_exp_b over the given rows, KL) as a 2-element device tensor -- the two pieces
         svgp.py:172-174 combines; the first is what gets all-reduced when the minibatch is sharded."""
@@ -262,50 +249,46 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         if fused is not None:
             k, Z, c = fused
             Xs, Zs = k.slice(X, Z)
-            family, var, ls = k.hyper()
             m, rows, d, P = Zs.shape[0], Xs.shape[0], Zs.shape[1], self.q_mu.shape[1]
             q_sqrt = self.q_sqrt.device_value()
             key = (m, rows, d, P, q_sqrt.dim() == 2, bool(self.whiten))
             if self._ws is None or self._ws[0] != key:
                 self._ws = (key, ops.svgp_elbo_workspace(m, rows, d, P, q_sqrt.dim() == 2, self.whiten))
             if isinstance(self.likelihood, Gaussian):
-                out, info = ops.svgp_elbo_shard(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt, variance=var,
-                                                lengthscales=ls, noise_variance=self.likelihood.noise_for(X),
-                                                jitter=config.default_jitter(), mean_const=c, family=family,
-                                                ws=self._ws[1], whiten=self.whiten, **k.hyper_extra())
+                out, info = ops.svgp_elbo_shard(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt, noise_variance=self.likelihood.noise_for(X),
+                                                jitter=config.default_jitter(), mean_const=c, ws=self._ws[1], whiten=self.whiten,
+                                                **k.leaf().keywords())
             else:
-                out, info = ops.svgp_elbo_shard_lik(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt, variance=var, lengthscales=ls,
+                out, info = ops.svgp_elbo_shard_lik(Zs, Xs, Y, self.q_mu.device_value(), q_sqrt,
                                                     lik=self.likelihood.device_lik, params=self.likelihood.device_params(),
-                                                    jitter=config.default_jitter(), mean_const=c, family=family,
-                                                    ws=self._ws[1], whiten=self.whiten, **k.hyper_extra())
+                                                    jitter=config.default_jitter(), mean_const=c, ws=self._ws[1], whiten=self.whiten,
+                                                    **k.leaf().keywords())
             ops.check_info(info)
             return out
         sep = self._fused_separate_config()
         if sep is not None:
             kernels, Zs, c = sep
             P, m, d, rows = len(kernels), Zs.shape[-2], Zs.shape[-1], X.shape[0]
-            hyp, ls = self._member_hypers(kernels, d)
+            members = latent_keywords([k.leaf() for k in kernels], d)
             key = ("sep", m, rows, d, P)
             if self._ws is None or self._ws[0] != key:
                 self._ws = (key, ops.svgp_elbo_sep_workspace(m, rows, d, P))
             out, info = ops.svgp_elbo_shard_sep(Zs, X.contiguous(), Y, self.q_mu.device_value(), self.q_sqrt.device_value(),
-                                                variances=[h[1] for h in hyp], lengthscales=ls, families=[h[0] for h in hyp],
                                                 noise_variance=self.likelihood.noise_for(X),
-                                                jitter=config.default_jitter(), mean_const=c, ws=self._ws[1])
+                                                jitter=config.default_jitter(), mean_const=c, ws=self._ws[1], **members)
             ops.check_info(info)
             return out
         lcm = self._fused_lcm_config()
         if lcm is not None:
             kernels, Zs, W, c = lcm
-            hyp, ls = self._member_hypers(kernels, Zs.shape[-1])
+            members = latent_keywords([k.leaf() for k in kernels], Zs.shape[-1])
             L, m, d, rows = len(kernels), Zs.shape[-2], Zs.shape[-1], X.shape[0]
             key = ("lcm", m, rows, d, L, W.shape[0])
             if self._ws is None or self._ws[0] != key:
                 self._ws = (key, ops.svgp_elbo_lcm_workspace(m, rows, d, L, W.shape[0]))
             out, info = ops.svgp_elbo_shard_lcm(Zs, X.contiguous(), Y, self.q_mu.device_value(), self.q_sqrt.device_value(), W,
-                                                variances=[h[1] for h in hyp], lengthscales=ls, families=[h[0] for h in hyp],
                                                 noise_variance=float(self.likelihood.noise_for(X)),
-                                                jitter=config.default_jitter(), mean_const=c, ws=self._ws[1])
+                                                jitter=config.default_jitter(), mean_const=c, ws=self._ws[1], **members)
             ops.check_info(info)
             return out
         shared = self._unwhitened_shared_factor_config()

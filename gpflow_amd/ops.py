@@ -12,11 +12,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from .leaf import FAMILIES, Leaf
 
 NB = 128
-KERNEL_FAMILIES = {"SquaredExponential": 0, "Matern12": 1, "Matern32": 2, "Matern52": 3,
-                   "Exponential": 4, "RationalQuadratic": 5, "White": 6, "Constant": 7}
-STATIC_FAMILIES = ("White", "Constant")   # no distance: the inputs are never read, no lengthscale or input gradient
+KERNEL_FAMILIES = {f.name: f.code for f in FAMILIES}                      # name -> GPK_KERN_* (include/gpk.h)
+STATIC_FAMILIES = tuple(f.name for f in FAMILIES if not f.has_distance)   # the inputs are never read, no lengthscale or input gradient
 MAX_D = 64
 
 
@@ -72,20 +72,8 @@ def _ws(nbytes: int) -> torch.Tensor:
 
 
 def _ls_host(lengthscales, d: int, family: str = "SquaredExponential", alpha=None):
-    """(host array, ard) of the C-ABI: the lengthscales and, for "RationalQuadratic", its alpha as one more trailing entry
-    (include/gpk.h, next to the family codes)."""
-    ls = np.atleast_1d(np.asarray(lengthscales, dtype=np.float64))
-    ard = ls.size > 1
-    if ard and ls.size != d:
-        raise ValueError(f"lengthscales has {ls.size} entries, input dimension is {d}")
-    vals = ls.tolist()
-    if family == "RationalQuadratic":
-        if alpha is None:
-            raise ValueError("family 'RationalQuadratic' needs alpha")
-        vals.append(float(alpha))
-    elif alpha is not None:
-        raise ValueError(f"alpha belongs to the 'RationalQuadratic' family, not to {family!r}")
-    return _lib.host_doubles(vals), int(ard)
+    """(host array, ard) of the C-ABI for a leaf given by keywords: Leaf.host"""
+    return Leaf(family, 1.0, lengthscales, alpha=alpha).host(d)
 
 
 def _noise_args(noise_variance, rows: int):
@@ -101,35 +89,49 @@ def _noise_args(noise_variance, rows: int):
 
 
 # ------------------------------------------------------------------------------------------------
+def _kernel_operands(X1, X2, G, out, *, x2_optional: bool = True, zero_new: bool = False,
+                     columns_differ: str = "X1 and X2 must have the same number of columns"):
+    """What the kernel_matrix* wrappers check before they look at the leaf: devices and dtypes, the shapes of X2 (None: K(X1, X1),
+    where the wrapper allows it) / G (None: no second factor) / out (allocated when None, zero-filled if `zero_new`), d in
+    [1, MAX_D].  Returns (n1, n2, d, out); n1 == 0 or n2 == 0: nothing to compute, the wrapper returns `out` (and X2 = NULL would
+    mean K(X1, X1) at the C-ABI)."""
+    _chk(X1, "X1", 2)
+    n1, d = X1.shape
+    if X2 is not None or not x2_optional:
+        _chk(X2, "X2", 2)
+    if G is not None:
+        _chk(G, "G", 2)
+    if X2 is not None and X2.shape[1] != d:
+        raise ValueError(columns_differ)
+    n2 = X2.shape[0] if X2 is not None else n1
+    if G is not None and tuple(G.shape) != (n1, n2):
+        raise ValueError("inconsistent shapes")
+    if d < 1 or d > MAX_D:
+        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
+    if out is None:
+        out = torch.empty((n1, n2), dtype=torch.float64, device=X1.device)
+        if zero_new:
+            out.zero_()
+    _chk(out, "out", 2)
+    return n1, n2, d, out
+
+
+def _x2_args(X2, n2):
+    """(pointer, rows, leading dimension) of the optional second input"""
+    return (X2.data_ptr(), n2, _rowmajor(X2, "X2")) if X2 is not None else (None, n2, 0)
+
+
 def kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, variance: float, lengthscales,
                   family: str = "SquaredExponential", diag_add: float = 0.0, lower_only: bool = False,
                   alpha=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2]."""
     lib = _lib.load()
-    _chk(X1, "X1", 2)
-    n1, d = X1.shape
-    if d < 1 or d > MAX_D:
-        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
-    if X2 is not None:
-        _chk(X2, "X2", 2)
-        if X2.shape[1] != d:
-            raise ValueError("X1 and X2 must have the same number of columns")
-        n2 = X2.shape[0]
-    else:
-        n2 = n1
-    if out is None:
-        out = torch.empty((n1, n2), dtype=torch.float64, device=X1.device)
-        if lower_only:
-            out.zero_()
-    _chk(out, "out", 2)
-    if n1 == 0 or n2 == 0:   # nothing to compute (and X2 = NULL would mean K(X1, X1) at the C-ABI)
+    n1, n2, d, out = _kernel_operands(X1, X2, None, out, zero_new=lower_only)
+    if n1 == 0 or n2 == 0:
         return out
-    ls, ard = _ls_host(lengthscales, d, family, alpha)
-    rc = lib.gpk_kernel_matrix(_stream(), KERNEL_FAMILIES[family], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
-                               X2.data_ptr() if X2 is not None else None, n2,
-                               _rowmajor(X2, "X2") if X2 is not None else 0, d, ls, ard,
-                               float(variance), float(diag_add), int(lower_only), out.data_ptr(),
-                               _rowmajor(out, "out"))
+    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
+    rc = lib.gpk_kernel_matrix(_stream(), leaf.code, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, *leaf.host(d),
+                               leaf.variance, float(diag_add), int(lower_only), out.data_ptr(), _rowmajor(out, "out"))
     _lib.check(rc, "gpk_kernel_matrix")
     return out
 
@@ -138,24 +140,13 @@ def kernel_matrix_hadamard(X1: torch.Tensor, X2: torch.Tensor, G: torch.Tensor, 
                            family: str = "SquaredExponential", alpha=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """G .* K(X1, X2) with K recomputed on the fly -> [n1, n2] (the elementwise factor of the kernel backward)."""
     lib = _lib.load()
-    _chk(X1, "X1", 2)
-    _chk(X2, "X2", 2)
-    _chk(G, "G", 2)
-    n1, d = X1.shape
-    n2 = X2.shape[0]
-    if X2.shape[1] != d or tuple(G.shape) != (n1, n2):
-        raise ValueError("inconsistent shapes")
-    if d < 1 or d > MAX_D:
-        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
-    if out is None:
-        out = torch.empty((n1, n2), dtype=torch.float64, device=X1.device)
-    _chk(out, "out", 2)
+    n1, n2, d, out = _kernel_operands(X1, X2, G, out, x2_optional=False, columns_differ="inconsistent shapes")
     if n1 == 0 or n2 == 0:
         return out
-    ls, ard = _ls_host(lengthscales, d, family, alpha)
-    rc = lib.gpk_kernel_matrix_hadamard(_stream(), KERNEL_FAMILIES[family], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
-                                        X2.data_ptr(), n2, _rowmajor(X2, "X2"), d, ls, ard, float(variance),
-                                        G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
+    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
+    rc = lib.gpk_kernel_matrix_hadamard(_stream(), leaf.code, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d,
+                                        *leaf.host(d), leaf.variance, G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(),
+                                        _rowmajor(out, "out"))
     _lib.check(rc, "gpk_kernel_matrix_hadamard")
     return out
 
@@ -168,29 +159,13 @@ def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch
     may be G itself.  X2 None: K(X1, X1); `diag_add` goes onto the diagonal of the combined result ("mul" / "add"), and
     "dr2" writes exact zeros on the diagonal.  op "dalpha" ("RationalQuadratic" only): G .* dK/dalpha, diagonal as "dr2"."""
     lib = _lib.load()
-    _chk(X1, "X1", 2)
-    _chk(G, "G", 2)
-    n1, d = X1.shape
-    if X2 is not None:
-        _chk(X2, "X2", 2)
-        if X2.shape[1] != d:
-            raise ValueError("X1 and X2 must have the same number of columns")
-    n2 = X2.shape[0] if X2 is not None else n1
-    if tuple(G.shape) != (n1, n2):
-        raise ValueError("inconsistent shapes")
-    if d < 1 or d > MAX_D:
-        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
-    if out is None:
-        out = torch.empty((n1, n2), dtype=torch.float64, device=X1.device)
-    _chk(out, "out", 2)
-    if n1 == 0 or n2 == 0:   # nothing to compute (and X2 = NULL would mean K(X1, X1) at the C-ABI)
+    n1, n2, d, out = _kernel_operands(X1, X2, G, out)
+    if n1 == 0 or n2 == 0:
         return out
-    ls, ard = _ls_host(lengthscales, d, family, alpha)
-    rc = lib.gpk_kernel_matrix_combine(_stream(), KERNEL_FAMILIES[family], {"mul": 1, "add": 2, "dr2": 3, "dalpha": 4}[op], X1.data_ptr(), n1,
-                                       _rowmajor(X1, "X1"), X2.data_ptr() if X2 is not None else None, n2,
-                                       _rowmajor(X2, "X2") if X2 is not None else 0, d, ls, ard, float(variance),
-                                       float(diag_add), G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(),
-                                       _rowmajor(out, "out"))
+    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
+    rc = lib.gpk_kernel_matrix_combine(_stream(), leaf.code, {"mul": 1, "add": 2, "dr2": 3, "dalpha": 4}[op], X1.data_ptr(), n1,
+                                       _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, *leaf.host(d), leaf.variance,
+                                       float(diag_add), G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
     _lib.check(rc, "gpk_kernel_matrix_combine")
     return out
 
@@ -761,10 +736,11 @@ def gpr_lml(X: torch.Tensor, Y: torch.Tensor, *, variance: float, lengthscales, 
         ws = _ws(nbytes)
     out = torch.empty(1, dtype=torch.float64, device=X.device)
     info = torch.zeros(1, dtype=torch.int32, device=X.device)
-    ls, ard = _ls_host(lengthscales, d, family, alpha)
+    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
+    ls, ard = leaf.host(d)
     nv, nv_rows, _keep = _noise_args(noise_variance, n)
-    rc = lib.gpk_gpr_lml(_stream(), KERNEL_FAMILIES[family], X.data_ptr(), n, d, _rowmajor(X, "X"),
-                         Y.data_ptr(), P, _rowmajor(Y, "Y"), ls, ard, float(variance),
+    rc = lib.gpk_gpr_lml(_stream(), leaf.code, X.data_ptr(), n, d, _rowmajor(X, "X"),
+                         Y.data_ptr(), P, _rowmajor(Y, "Y"), ls, ard, leaf.variance,
                          nv, nv_rows, float(mean_const), out.data_ptr(), info.data_ptr(),
                          ws.data_ptr(), ws.numel() * 8)
     _lib.check(rc, "gpk_gpr_lml")
@@ -817,6 +793,46 @@ class HostMailbox:
         return self._vals.copy(), int(tail[0])
 
 
+def _shard_setup(Z, Xb, Yb, q_mu, q_sqrt, ws, out, info, *, y_columns, workspace_bytes, latents: Optional[int] = None):
+    """What the four svgp_elbo_shard* wrappers share: the operand checks, the contiguity of the variational parameters, and `ws` (of
+    `workspace_bytes(m, rows, d, n)` bytes at least) / `out` [2] / `info`, allocated where not given.  n = the columns of q_mu;
+    y_columns(n): the columns Yb must have (the likelihood's rule).  latents None: one kernel, Z [m, d], q_sqrt full or diagonal,
+    info [1]; else the shards with one kernel per latent, `latents` of them given: Z [m, d] (shared) or [n, m, d], q_sqrt
+    [n, m, m], info [n].  Returns (m, d, rows, n, ws, out, info)."""
+    per_latent = latents is not None
+    for name, t in (("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)) if per_latent else (("Z", Z), ("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)):
+        _chk(t, name, 2)
+    if per_latent:
+        _chk(Z, "Z")
+    _chk(q_sqrt, "q_sqrt", 3 if per_latent else None)
+    m, d = Z.shape[-2], Z.shape[-1]
+    rows, n = Xb.shape[0], q_mu.shape[1]
+    if (per_latent and Z.dim() != 2 and (Z.dim() != 3 or Z.shape[0] != n)) or Xb.shape[1] != d or Yb.shape[0] != rows \
+            or Yb.shape[1] != y_columns(n) or q_mu.shape[0] != m or (per_latent and (tuple(q_sqrt.shape) != (n, m, m) or latents != n)):
+        raise ValueError("inconsistent shapes")
+    if not (q_mu.is_contiguous() and q_sqrt.is_contiguous() and (Z.is_contiguous() or not per_latent)):
+        raise ValueError(("Z / " if per_latent else "") + "q_mu / q_sqrt must be contiguous")
+    nbytes = int(workspace_bytes(m, rows, d, n))
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _ws(nbytes)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=Xb.device)
+    if info is None:
+        info = torch.zeros(n if per_latent else 1, dtype=torch.int32, device=Xb.device)
+    return m, d, rows, n, ws, out, info
+
+
+def _latent_hypers(variances, lengthscales, families, n: int, d: int):
+    """(family codes, (ls_host, ard, variances_host)) of the per-latent shards: variances [n], lengthscales [n] (isotropic) or
+    [n, d], families [n] names (leaf.latent_keywords makes them from leaves)"""
+    ls = np.asarray(lengthscales, dtype=np.float64)
+    var = np.asarray(variances, dtype=np.float64).reshape(-1)
+    if var.size != n or ls.shape[0] != n or (ls.ndim == 2 and ls.shape[1] != d) or ls.ndim > 2:
+        raise ValueError("variances / lengthscales: one entry (row) per latent")
+    fam = (_lib.C.c_int * n)(*[KERNEL_FAMILIES[f] for f in families])
+    return fam, (_lib.host_doubles(ls.reshape(-1).tolist()), int(ls.ndim == 2), _lib.host_doubles(var.tolist()))
+
+
 def svgp_elbo_sep_workspace(m: int, rows: int, d: int, P: int) -> torch.Tensor:
     lib = _lib.load()
     return _ws(int(lib.gpk_svgp_elbo_sep_workspace_bytes(m, rows, d, P)))
@@ -830,38 +846,14 @@ def svgp_elbo_shard_sep(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_m
     lengthscales [P] (isotropic) or [P, d], families [P] names; q_sqrt [P, m, m].  out[0] = sum_b var_exp_b, out[1] = KL;
     info [P].  Returns (out, info)."""
     lib = _lib.load()
-    for name, t in (("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)):
-        _chk(t, name, 2)
-    _chk(Z, "Z")
-    _chk(q_sqrt, "q_sqrt", 3)
-    P = q_mu.shape[1]
-    shared = Z.dim() == 2
-    m, d = Z.shape[-2], Z.shape[-1]
-    rows = Xb.shape[0]
-    if (not shared and (Z.dim() != 3 or Z.shape[0] != P)) or Xb.shape[1] != d or Yb.shape[0] != rows or Yb.shape[1] != P \
-            or q_mu.shape[0] != m or tuple(q_sqrt.shape) != (P, m, m) or len(families) != P:
-        raise ValueError("inconsistent shapes")
-    if not (Z.is_contiguous() and q_mu.is_contiguous() and q_sqrt.is_contiguous()):
-        raise ValueError("Z / q_mu / q_sqrt must be contiguous")
-    ls = np.asarray(lengthscales, dtype=np.float64)
-    var = np.asarray(variances, dtype=np.float64).reshape(-1)
-    if var.size != P or ls.shape[0] != P or (ls.ndim == 2 and ls.shape[1] != d) or ls.ndim > 2:
-        raise ValueError("variances / lengthscales: one entry (row) per latent")
-    ard = int(ls.ndim == 2)
-    nbytes = int(lib.gpk_svgp_elbo_sep_workspace_bytes(m, rows, d, P))
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = _ws(nbytes)
-    if out is None:
-        out = torch.empty(2, dtype=torch.float64, device=Xb.device)
-    if info is None:
-        info = torch.zeros(P, dtype=torch.int32, device=Xb.device)
-    fam = (_lib.C.c_int * P)(*[KERNEL_FAMILIES[f] for f in families])
+    m, d, rows, P, ws, out, info = _shard_setup(Z, Xb, Yb, q_mu, q_sqrt, ws, out, info, y_columns=lambda P: P, latents=len(families),
+                                                workspace_bytes=lib.gpk_svgp_elbo_sep_workspace_bytes)
+    fam, hypers = _latent_hypers(variances, lengthscales, families, P, d)
     nv, nv_rows, _keep = _noise_args(noise_variance, rows)
-    rc = lib.gpk_svgp_elbo_shard_sep(_stream(), fam, Z.data_ptr(), m, d, 0 if shared else m * d, Xb.data_ptr(), Yb.data_ptr(), rows,
-                                     _rowmajor(Xb, "Xb"), _rowmajor(Yb, "Yb"), d, P, _lib.host_doubles(ls.reshape(-1).tolist()), ard,
-                                     _lib.host_doubles(var.tolist()), nv, nv_rows, float(jitter), float(mean_const),
-                                     q_mu.data_ptr(), q_sqrt.data_ptr(), out.data_ptr(), info.data_ptr(), ws.data_ptr(),
-                                     ws.numel() * 8)
+    rc = lib.gpk_svgp_elbo_shard_sep(_stream(), fam, Z.data_ptr(), m, d, 0 if Z.dim() == 2 else m * d, Xb.data_ptr(), Yb.data_ptr(), rows,
+                                     _rowmajor(Xb, "Xb"), _rowmajor(Yb, "Yb"), d, P, *hypers, nv, nv_rows, float(jitter),
+                                     float(mean_const), q_mu.data_ptr(), q_sqrt.data_ptr(), out.data_ptr(), info.data_ptr(),
+                                     ws.data_ptr(), ws.numel() * 8)
     _lib.check(rc, "gpk_svgp_elbo_shard_sep")
     return out, info
 
@@ -880,41 +872,18 @@ def svgp_elbo_shard_lcm(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_m
     mixed into the P columns of Yb by W [P, L] (host or device): f = W g + mean_const.  out[0] = sum_b var_exp_b, out[1] = KL
     over the L latents; info [L].  Returns (out, info)."""
     lib = _lib.load()
-    for name, t in (("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)):
-        _chk(t, name, 2)
-    _chk(Z, "Z")
-    _chk(q_sqrt, "q_sqrt", 3)
-    L = q_mu.shape[1]
-    Wh = _mixing_weights(W, L)
+    _chk(q_mu, "q_mu", 2)
+    Wh = _mixing_weights(W, q_mu.shape[1])
     P = Wh.shape[0]
-    shared = Z.dim() == 2
-    m, d = Z.shape[-2], Z.shape[-1]
-    rows = Xb.shape[0]
-    if (not shared and (Z.dim() != 3 or Z.shape[0] != L)) or Xb.shape[1] != d or Yb.shape[0] != rows or Yb.shape[1] != P \
-            or q_mu.shape[0] != m or tuple(q_sqrt.shape) != (L, m, m) or len(families) != L:
-        raise ValueError("inconsistent shapes")
-    if not (Z.is_contiguous() and q_mu.is_contiguous() and q_sqrt.is_contiguous()):
-        raise ValueError("Z / q_mu / q_sqrt must be contiguous")
-    ls = np.asarray(lengthscales, dtype=np.float64)
-    var = np.asarray(variances, dtype=np.float64).reshape(-1)
-    if var.size != L or ls.shape[0] != L or (ls.ndim == 2 and ls.shape[1] != d) or ls.ndim > 2:
-        raise ValueError("variances / lengthscales: one entry (row) per latent")
+    m, d, rows, L, ws, out, info = _shard_setup(Z, Xb, Yb, q_mu, q_sqrt, ws, out, info, y_columns=lambda L: P, latents=len(families),
+                                                workspace_bytes=lambda m, rows, d, L: lib.gpk_svgp_elbo_lcm_workspace_bytes(m, rows, d, L, P))
+    fam, hypers = _latent_hypers(variances, lengthscales, families, L, d)
     if not float(noise_variance) > 0.0:
         raise ValueError("noise_variance must be positive")
-    ard = int(ls.ndim == 2)
-    nbytes = int(lib.gpk_svgp_elbo_lcm_workspace_bytes(m, rows, d, L, P))
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = _ws(nbytes)
-    if out is None:
-        out = torch.empty(2, dtype=torch.float64, device=Xb.device)
-    if info is None:
-        info = torch.zeros(L, dtype=torch.int32, device=Xb.device)
-    fam = (_lib.C.c_int * L)(*[KERNEL_FAMILIES[f] for f in families])
-    rc = lib.gpk_svgp_elbo_shard_lcm(_stream(), fam, Z.data_ptr(), m, d, 0 if shared else m * d, Xb.data_ptr(), Yb.data_ptr(), rows,
+    rc = lib.gpk_svgp_elbo_shard_lcm(_stream(), fam, Z.data_ptr(), m, d, 0 if Z.dim() == 2 else m * d, Xb.data_ptr(), Yb.data_ptr(), rows,
                                      _rowmajor(Xb, "Xb"), _rowmajor(Yb, "Yb"), d, L, P, _lib.host_doubles(Wh.reshape(-1).tolist()),
-                                     _lib.host_doubles(ls.reshape(-1).tolist()), ard, _lib.host_doubles(var.tolist()),
-                                     float(noise_variance), float(jitter), float(mean_const), q_mu.data_ptr(), q_sqrt.data_ptr(),
-                                     out.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+                                     *hypers, float(noise_variance), float(jitter), float(mean_const), q_mu.data_ptr(),
+                                     q_sqrt.data_ptr(), out.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel() * 8)
     _lib.check(rc, "gpk_svgp_elbo_shard_lcm")
     return out, info
 
@@ -932,31 +901,19 @@ def svgp_elbo_shard(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu: t
     """One shard of SVGP.elbo: out[0] = sum_b var_exp_b over this shard, out[1] = KL.  Returns (out, info).
     whiten=False: KL against N(0, Kuu) and the un-whitened conditional, on one factorisation (full or diagonal q_sqrt)."""
     lib = _lib.load()
-    for name, t in (("Z", Z), ("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)):
-        _chk(t, name, 2)
-    _chk(q_sqrt, "q_sqrt")
-    m, d = Z.shape
-    rows = Xb.shape[0]
-    P = q_mu.shape[1]
-    q_diag = q_sqrt.dim() == 2
-    if Xb.shape[1] != d or Yb.shape[0] != rows or Yb.shape[1] != P or q_mu.shape[0] != m:
-        raise ValueError("inconsistent shapes")
-    if not (q_mu.is_contiguous() and q_sqrt.is_contiguous()):
-        raise ValueError("q_mu / q_sqrt must be contiguous")
-    nbytes = int(lib.gpk_svgp_elbo_workspace_bytes(m, rows, d, P, int(q_diag), int(bool(whiten))))
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = _ws(nbytes)
-    if out is None:
-        out = torch.empty(2, dtype=torch.float64, device=Z.device)
-    if info is None:
-        info = torch.zeros(1, dtype=torch.int32, device=Z.device)
-    ls, ard = _ls_host(lengthscales, d, family, alpha)
+    whiten = int(bool(whiten))
+    m, d, rows, P, ws, out, info = _shard_setup(
+        Z, Xb, Yb, q_mu, q_sqrt, ws, out, info, y_columns=lambda P: P,
+        workspace_bytes=lambda m, rows, d, P: lib.gpk_svgp_elbo_workspace_bytes(m, rows, d, P, int(q_sqrt.dim() == 2), whiten))
+    q_diag = int(q_sqrt.dim() == 2)
+    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
+    ls, ard = leaf.host(d)
     nv, nv_rows, _keep = _noise_args(noise_variance, rows)
-    rc = lib.gpk_svgp_elbo_shard(_stream(), KERNEL_FAMILIES[family], Z.data_ptr(), m, _rowmajor(Z, "Z"),
+    rc = lib.gpk_svgp_elbo_shard(_stream(), leaf.code, Z.data_ptr(), m, _rowmajor(Z, "Z"),
                                  Xb.data_ptr(), Yb.data_ptr(), rows, _rowmajor(Xb, "Xb"),
-                                 _rowmajor(Yb, "Yb"), d, P, ls, ard, float(variance),
+                                 _rowmajor(Yb, "Yb"), d, P, ls, ard, leaf.variance,
                                  nv, nv_rows, float(jitter), float(mean_const),
-                                 q_mu.data_ptr(), q_sqrt.data_ptr(), int(q_diag), int(bool(whiten)), out.data_ptr(),
+                                 q_mu.data_ptr(), q_sqrt.data_ptr(), q_diag, whiten, out.data_ptr(),
                                  info.data_ptr(), ws.data_ptr(), ws.numel() * 8)
     _lib.check(rc, "gpk_svgp_elbo_shard")
     return out, info
@@ -971,30 +928,18 @@ def svgp_elbo_shard_lik(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_m
     out[0] = sum_b of the quadrature variational expectations over this shard, out[1] = KL.  Same forms, same workspace.
     "multiclass_robustmax": Yb is ONE column of labels."""
     lib = _lib.load()
-    for name, t in (("Z", Z), ("Xb", Xb), ("Yb", Yb), ("q_mu", q_mu)):
-        _chk(t, name, 2)
-    _chk(q_sqrt, "q_sqrt")
-    m, d = Z.shape
-    rows = Xb.shape[0]
-    P = q_mu.shape[1]
-    q_diag = q_sqrt.dim() == 2
-    if Xb.shape[1] != d or Yb.shape[0] != rows or Yb.shape[1] != _lik_y_columns(lik, P) or q_mu.shape[0] != m:
-        raise ValueError("inconsistent shapes")
-    if not (q_mu.is_contiguous() and q_sqrt.is_contiguous()):
-        raise ValueError("q_mu / q_sqrt must be contiguous")
+    whiten = int(bool(whiten))
+    m, d, rows, P, ws, out, info = _shard_setup(
+        Z, Xb, Yb, q_mu, q_sqrt, ws, out, info, y_columns=lambda P: _lik_y_columns(lik, P),
+        workspace_bytes=lambda m, rows, d, P: lib.gpk_svgp_elbo_workspace_bytes(m, rows, d, P, int(q_sqrt.dim() == 2), whiten))
+    q_diag = int(q_sqrt.dim() == 2)
     code, par = _lik_args(lik, params)
-    nbytes = int(lib.gpk_svgp_elbo_workspace_bytes(m, rows, d, P, int(q_diag), int(bool(whiten))))
-    if ws is None or ws.numel() * 8 < nbytes:
-        ws = _ws(nbytes)
-    if out is None:
-        out = torch.empty(2, dtype=torch.float64, device=Z.device)
-    if info is None:
-        info = torch.zeros(1, dtype=torch.int32, device=Z.device)
-    ls, ard = _ls_host(lengthscales, d, family, alpha)
-    rc = lib.gpk_svgp_elbo_shard_lik(_stream(), KERNEL_FAMILIES[family], Z.data_ptr(), m, _rowmajor(Z, "Z"), Xb.data_ptr(),
+    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
+    ls, ard = leaf.host(d)
+    rc = lib.gpk_svgp_elbo_shard_lik(_stream(), leaf.code, Z.data_ptr(), m, _rowmajor(Z, "Z"), Xb.data_ptr(),
                                      Yb.data_ptr(), rows, _rowmajor(Xb, "Xb"), _rowmajor(Yb, "Yb"), d, P, ls, ard,
-                                     float(variance), code, par, float(jitter), float(mean_const), q_mu.data_ptr(),
-                                     q_sqrt.data_ptr(), int(q_diag), int(bool(whiten)), out.data_ptr(), info.data_ptr(),
+                                     leaf.variance, code, par, float(jitter), float(mean_const), q_mu.data_ptr(),
+                                     q_sqrt.data_ptr(), q_diag, whiten, out.data_ptr(), info.data_ptr(),
                                      ws.data_ptr(), ws.numel() * 8)
     _lib.check(rc, "gpk_svgp_elbo_shard_lik")
     return out, info

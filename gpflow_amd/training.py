@@ -73,7 +73,7 @@ class SVGPTrainer:
         if isinstance(model.kernel, SeparateIndependent) and not isinstance(model.inducing_variable, SharedIndependentInducingVariables):
             raise NotImplementedError("the trainer with separate kernels per latent: shared inducing points")
         routes, c, self.separate = reverse.svgp_routes(model)
-        if any(len(pars) != 2 for r, _ in routes for pars in r.members):
+        if not all(leaf.is_plain for r, _ in routes for leaf in r.spec.members):
             raise NotImplementedError("the trainer keeps (variance, lengthscales) per kernel on the device side of its step: no "
                                       "RationalQuadratic (alpha), White or Constant (no lengthscales) members -- SVGP.elbo_and_grad "
                                       "with optimizers.Scipy covers them")

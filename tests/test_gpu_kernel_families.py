@@ -510,8 +510,8 @@ def test_combinations_with_static_and_rq_members_in_the_reverse_pass(gp, which):
     kern, pars, torch_kernel = _combination(gpflow.kernels, which)
     if which != "se+white":
         route = gpflow.models.reverse.CovarianceRoute(kern, D)
-        assert route.spec.tree == ("add", [("mul", [0, 1]), 2]) and route.spec.alphas[:2] == [None, None] \
-            and route.spec.alphas[2] == pytest.approx(1.7)
+        assert route.spec.tree == ("add", [("mul", [0, 1]), 2]) and [m.keywords().get("alpha") for m in route.spec.members[:2]] == [None, None] \
+            and route.spec.members[2].keywords()["alpha"] == pytest.approx(1.7)
         assert [len(m) for m in route.members] == [1, 2, 3]
 
     def leaves(extra):

@@ -60,10 +60,11 @@ def test_constructors_exports_and_parameters():
     assert float(w.variance.numpy()) == pytest.approx(2.5) and w.name == "w" and list(w.active_dims) == [1]
     assert w.trainable_parameters == (w.variance,) or list(w.trainable_parameters) == [w.variance]
     assert not hasattr(w, "lengthscales") and K.Constant().name == "Constant" and float(K.Constant().variance.numpy()) == pytest.approx(1.0)
-    # hyper(): the one notion of a device-built leaf
-    assert rq.hyper()[0] == "RationalQuadratic" and rq.hyper_alpha() == pytest.approx(0.25) and K.Exponential().hyper_alpha() is None
-    fam, var, ls = w.hyper()
-    assert (fam, var, float(ls)) == ("White", pytest.approx(2.5), 1.0) and w.hyper_alpha() is None
+    # leaf(): the one notion of a device-built leaf
+    assert rq.leaf().family == "RationalQuadratic" and rq.leaf().keywords()["alpha"] == pytest.approx(0.25) \
+        and K.Exponential().leaf().keywords().get("alpha") is None
+    kw = w.leaf().keywords()
+    assert (kw["family"], kw["variance"], float(kw["lengthscales"])) == ("White", pytest.approx(2.5), 1.0) and kw.get("alpha") is None
     from gpflow_amd.kernels.base import is_device_leaf
     assert all(is_device_leaf(k) for k in (rq, w, K.Constant(), K.Exponential(), K.Matern52()))
     assert not is_device_leaf(rq + w) and not is_device_leaf(K.SeparateIndependent([rq, w]))
@@ -106,7 +107,7 @@ def test_alpha_is_a_value_error_outside_the_rational_quadratic():
     with pytest.raises(ValueError, match="alpha"):
         gradients.KernelSpec.single(1.0, 1.0, "RationalQuadratic")
     spec = gradients.KernelSpec([("Constant", 2.0, 1.0), ("RationalQuadratic", 0.5, [1.0, 2.0], 0.7), ("White", 0.1, 1.0, None)], "add")
-    assert [spec.n_shape(i) for i in range(3)] == [0, 3, 0] and spec.kdiag() == pytest.approx(2.6) and not spec.packable
+    assert [m.n_shape for m in spec.members] == [0, 3, 0] and spec.kdiag() == pytest.approx(2.6) and not spec.packable
     assert gradients.KernelSpec.single(1.0, [1.0, 2.0], "Exponential").packable
 
 

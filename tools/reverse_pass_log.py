@@ -6,17 +6,21 @@
                                                                 SGPR.objective_and_grad, SVGPTrainer and NaturalGradient issue and return
     python tools/reverse_pass_log.py compare <a.pkl> <b.pkl>    compare two dumps case by case
 
-`gradients.ops` is tests/fake_ops.py + tests/fake_likelihood_ops.py (of the SAME tree) behind a logging proxy: one line per outermost
+`gradients.ops` is tests/fake_ops.py + tests/fake_likelihood_ops.py + tests/fake_kernel_ops.py (of the SAME tree, the last one winning,
+as in the `gp` fixture of tests/test_kernel_families_emulated.py) behind a logging proxy: one line per outermost
 `ops.*` call (name, shape and strides of every tensor argument, every scalar argument); a TorchDispatchMode adds one line per aten op
 issued OUTSIDE an `ops.*` call (the torch glue).  Each case runs twice and the second run is kept (`ls_device` caches).  Kept per
 case: the log and the bytes of F, every gradient and info.  Written for the refactor recorded in profiles/reverse_pass_refactor.txt.
 
-`dump-models` patches every `gpflow_amd.ops` name the three fakes define (as the `gp` fixture of tests/test_multiclass_emulated.py does)
-behind the same logging wrapper -- or, with `device`, patches nothing and logs nothing: the same matrix on the real library.  Kept per
+`dump-models` patches every `gpflow_amd.ops` name the fakes define -- fake_ops, fake_likelihood_ops, fake_multiclass_ops, then
+fake_kernel_ops and fake_lcm_ops last (the order of the `gp` fixtures of tests/test_multiclass_emulated.py,
+tests/test_kernel_families_emulated.py and tests/test_lcm_emulated.py) -- behind the same logging wrapper -- or, with `device`, patches nothing and logs nothing: the same matrix on the real library.  Kept per
 case: the `ops.*` log, the returned value, every gradient under a key that carries its position in the returned dict and the
 position of its Parameter in `model.parameters`; for the trainer F, every `u` / `dev` entry after two steps and the names of `host` in
-order (in the key).  A refusal is kept as its exception type.  The model functions run twice on one model: `<case>` is the second run
-(Parameter.device_value caches warm), `<case>#cold` the first.  Written for the refactor recorded in profiles/model_layer_refactor.txt.
+order (in the key); for a fused forward call (kind "value") the returned value alone.  A refusal is kept as its exception type.  The model functions run twice on one model: `<case>` is the second run
+(Parameter.device_value caches warm), `<case>#cold` the first.  Written for the refactor recorded in profiles/model_layer_refactor.txt;
+the RationalQuadratic / Exponential / White / Constant leaves and the LinearCoregionalization models were added for the one recorded
+in profiles/kernel_leaf_refactor.txt.
 """
 import itertools
 import pickle
@@ -59,13 +63,14 @@ def load(tree):
     sys.path[:0] = [tree, tree + "/tests"]
     import torch
     from torch.utils._python_dispatch import TorchDispatchMode
+    import fake_kernel_ops
     import fake_likelihood_ops
     import fake_ops
     from gpflow_amd import gradients
     log, depth, wrap = _logger()
 
     proxy = types.SimpleNamespace()
-    for mod in (fake_ops, fake_likelihood_ops):
+    for mod in (fake_ops, fake_likelihood_ops, fake_kernel_ops):
         for name in dir(mod):
             v = getattr(mod, name)
             if name.startswith("_") or isinstance(v, types.ModuleType):
@@ -91,6 +96,15 @@ def kernels(g, D=3):
         "sum2": lambda: dict(kernel_spec=g.KernelSpec([se, m32], "add")),
         "prod2_cols": lambda: dict(kernel_spec=g.KernelSpec([("SquaredExponential", 1.3, ard[:2]), m32], "mul", [[0, 1], [2]])),
         "nested": lambda: dict(kernel_spec=g.KernelSpec([se, m32, m52], ("mul", [("add", [0, 1]), 2]))),
+        # the families with an extra hyperparameter or without lengthscales: by keywords, and as members
+        "rq_iso": lambda: dict(variance=0.9, lengthscales=1.1, family="RationalQuadratic", alpha=0.7),
+        "rq_ard": lambda: dict(variance=0.9, lengthscales=ard, family="RationalQuadratic", alpha=1.7),
+        "exp_iso": lambda: dict(variance=1.1, lengthscales=1.4, family="Exponential"),
+        "const_rq_white": lambda: dict(kernel_spec=g.KernelSpec([("Constant", 2.0, 1.0), ("RationalQuadratic", 0.5, ard, 0.7),
+                                                                 ("White", 0.1, 1.0, None)], "add")),
+        "prod_static": lambda: dict(kernel_spec=g.KernelSpec([se, ("Constant", 2.0, 1.0)], "mul")),
+        "nested_rq_cols": lambda: dict(kernel_spec=g.KernelSpec([se, ("RationalQuadratic", 0.6, np.array(1.2), 1.3), m52],
+                                                                ("mul", [("add", [0, 1]), 2]), [None, [0, 2], None])),
     }
 
 
@@ -117,7 +131,7 @@ def cases(torch, g):
     liks = {"bernoulli_probit": (), "poisson_exp": (1.5,), "student_t": (0.7, 4.0)}
     kn = kernels(g)
     for qf, lik, (kname, kmk), P in itertools.product(("full", "diag"), ("scalar", "rows", *liks), kn.items(), (1, 2)):
-        if lik in liks and kname not in ("se_ard", "m32_iso"):
+        if lik in liks and kname not in ("se_ard", "m32_iso", "rq_iso"):
             continue   # (refused by SVGP.elbo_and_grad: a quadrature likelihood needs one stationary kernel)
         X, Y, Z, q_mu, q_full, q_diag, rows = data(64, 200, 3, P, lik)
         kw = dict(jitter=1e-6, scale=5.0, mean_const=0.1, kl_weight=0.5)
@@ -154,8 +168,8 @@ def dump(tree, path):
                     F, grads, info = getattr(g, fn)(*args, **kw, **kmk())
             vals = {"F": F, "info": info}
             for k, v in grads.items():
-                for i, vi in enumerate(v if isinstance(v, list) else [v]):
-                    vals[f"{k}[{i}]" if isinstance(v, list) else k] = vi
+                for i, vi in enumerate(v if isinstance(v, list) else [v]):   # (None: a member without that entry, kept as an empty one)
+                    vals[(f"{k}[{i}]" if isinstance(v, list) else k) + ("=None" if vi is None else "")] = torch.zeros(0) if vi is None else vi
             res[f"chunks{chunks}/{name}"] = (list(log), {k: (tuple(v.shape), v.detach().contiguous().numpy().tobytes()) for k, v in vals.items()})
     with open(path, "wb") as f:
         pickle.dump(res, f)
@@ -308,6 +322,52 @@ def model_cases(gp):
     for name, mk in nat.items():
         P = 2 if name in ("accepted_unwhite_shared", "separate") else 1
         out.append((f"natgrad/{name}", "natgrad", lambda mk=mk, P=P: (mk(), (X, Y2[:, :P]))))
+    # ---- leaves with an extra hyperparameter (RationalQuadratic) or without lengthscales (White, Constant), and LinearCoregionalization
+    rq = lambda **kw: K.RationalQuadratic(variance=1.1, lengthscales=0.9, alpha=0.7, **kw)  # noqa: E731
+    leaves = {"rq": rq, "rq_ard_active": lambda: K.RationalQuadratic(variance=1.1, lengthscales=[0.9, 1.2], alpha=1.7, active_dims=[0, 2]),
+              "se_white": lambda: se() + K.White(0.3), "const_times_rq": lambda: K.Constant(2.0) * rq()}
+
+    def model_over(cls, k, lik=None, P=1):
+        lik = lik or L.Gaussian(0.2)
+        if cls == "svgp":
+            return svgp_over(k, Z.copy(), lik, P)
+        return gp.models.GPR((X, Y2), k, likelihood=lik) if cls == "gpr" else gp.models.SGPR((X, Y2), k, Z.copy(), likelihood=lik)
+    for cls, (kname, mk) in itertools.product(("svgp", "gpr", "sgpr"), leaves.items()):
+        def make(cls=cls, mk=mk):
+            m = model_over(cls, mk())
+            return m, (lambda: m.elbo_and_grad((X, Y2[:, :1]))) if cls == "svgp" else m.objective_and_grad
+        out.append((f"leaf/{cls}/{kname}", "grad", make))
+
+    def value_case(mk, fn):
+        def make():
+            m = mk()
+            return m, lambda: fn(m)
+        return make
+    sep = lambda members: svgp_over(K.SeparateIndependent(members), shared_pts(), L.Gaussian(0.2), len(members))  # noqa: E731
+    forward = {"svgp/rq": (lambda: model_over("svgp", rq()), lambda m: m.elbo((X, Y2[:, :1]))),
+               "svgp/white": (lambda: model_over("svgp", K.White(0.3)), lambda m: m.elbo((X, Y2[:, :1]))),
+               "svgp/constant_bernoulli": (lambda: model_over("svgp", K.Constant(2.0), L.Bernoulli()), lambda m: m.elbo((X, liks["bernoulli"][2]))),
+               "svgp/rq_bernoulli": (lambda: model_over("svgp", rq(), L.Bernoulli()), lambda m: m.elbo((X, liks["bernoulli"][2]))),
+               "gpr/rq": (lambda: model_over("gpr", rq()), lambda m: m.log_marginal_likelihood()),
+               "gpr/constant": (lambda: model_over("gpr", K.Constant(2.0)), lambda m: m.log_marginal_likelihood()),
+               "sep/se_exponential_ard": (lambda: sep([se(), K.Exponential(variance=0.8, lengthscales=[1.1, 0.7, 1.3])]), lambda m: m.elbo((X, Y2))),
+               "sep/se_white": (lambda: sep([se(), K.White(0.3)]), lambda m: m.elbo((X, Y2))),
+               "sep/rq_member": (lambda: sep([se(), rq()]), lambda m: m.elbo((X, Y2)))}                 # (refused: no slot for alpha)
+    for name, (mk, fn) in forward.items():
+        out.append((f"forward/{name}", "value", value_case(mk, fn)))
+    Wmix = 0.5 * rng.normal(size=(2, 3))
+
+    def lcm(members=None, separate_z=False):
+        ks = members or [se(), m32(), K.Matern52(variance=0.8, lengthscales=[1.1, 0.7, 1.3])]   # (the fused shard's emulation: fake_ops' families)
+        iv = IV.SeparateIndependentInducingVariables([pts(0.1 * i) for i in range(3)]) if separate_z else shared_pts()
+        return svgp_over(K.LinearCoregionalization(ks, Wmix.copy()), iv, L.Gaussian(0.2), 3)
+    out.append(("lcm/elbo", "value", value_case(lcm, lambda m: m.elbo((X, Y2)))))
+    out.append(("lcm/elbo_separate_z", "value", value_case(lambda: lcm(separate_z=True), lambda m: m.elbo((X, Y2)))))
+    out.append(("lcm/elbo_rq_member", "value", value_case(lambda: lcm([se(), rq(), m32()]), lambda m: m.elbo((X, Y2)))))   # (refused)
+    out.append(("lcm/elbo_and_grad", "grad", elbo_case(lcm, Y2)))
+    out.append(("lcm/elbo_and_grad_rq_white", "grad", elbo_case(lambda: lcm([se(), rq(), K.White(0.3)], separate_z=True), Y2)))
+    for name, mk in (("rq", rq), ("se_white", leaves["se_white"]), ("constant", lambda: K.Constant(2.0))):                 # (refused)
+        out.append((f"trainer/leaf_{name}", "trainer", lambda mk=mk: (model_over("svgp", mk()), dict(learning_rate=1e-2), (X, Y2[:, :1]))))
     return out
 
 
@@ -318,10 +378,12 @@ def dump_models(tree, path, device=None):
     from gpflow_amd import ops, training
     log, depth, wrap = _logger()
     if device is None:
+        import fake_kernel_ops
+        import fake_lcm_ops
         import fake_likelihood_ops
         import fake_multiclass_ops
         import fake_ops
-        for mod in (fake_ops, fake_likelihood_ops, fake_multiclass_ops):
+        for mod in (fake_ops, fake_likelihood_ops, fake_multiclass_ops, fake_kernel_ops, fake_lcm_ops):
             for name in dir(mod):
                 v = getattr(mod, name)
                 if name.startswith("_") or not callable(v) or not hasattr(ops, name) or isinstance(v, types.ModuleType):
@@ -342,6 +404,13 @@ def dump_models(tree, path, device=None):
                     vals = {"F": value}
                     for j, (p, g) in enumerate(grads.items()):
                         vals[f"grad{j:02d}:parameter{pos[id(p)]}"] = g
+                    res[name + run] = (list(log), pack(vals))
+                continue
+            if kind == "value":
+                model, fn = make()
+                for run in ("#cold", ""):
+                    del log[:]
+                    vals = {"F": fn()}
                     res[name + run] = (list(log), pack(vals))
                 continue
             if kind == "trainer":
