@@ -89,6 +89,10 @@ _SIGS = {
     "gpk_moment_rows": (c_int, [c_void_p, _dp, c_long, c_int, c_int, _dp, c_long]),
     "gpk_stationary_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, c_int, _dp, c_double, c_int, _dp, _dp, c_long,
                                             _dp, c_int, c_double]),
+    "gpk_periodic_warp": (c_int, [c_void_p, _dp, c_long, c_int, c_int, C.POINTER(c_double), c_int, _dp, c_long]),
+    "gpk_periodic_moment_rows": (c_int, [c_void_p, _dp, c_long, c_int, c_int, C.POINTER(c_double), c_int, _dp, c_long]),
+    "gpk_periodic_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, _dp, c_long, _dp, c_long, c_int, c_int, _dp,
+                                          C.POINTER(c_double), c_int, _dp, c_long, _dp, c_int]),
     "gpk_adam_step": (c_int, [c_void_p, _dp, _dp, _dp, _dp, c_long, c_double, c_double, c_double, c_double, c_int]),
     "gpk_lowrank_axpy": (c_int, [c_void_p, c_double, _dp, c_long, _dp, c_long, _dp, c_long, c_int, c_int, c_int, _dp, c_long]),
     "gpk_symmetrize": (c_int, [c_void_p, _dp, c_int, c_long]),

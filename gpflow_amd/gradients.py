@@ -151,7 +151,7 @@ def ls_device(lengthscales, D: int, device) -> torch.Tensor:
 
 
 def stationary_kernel_adjoint(leaf: Leaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, symmetric: bool, packed_into=None,
-                              dvar_add: float = 0.0, return_packed: bool = False):
+                              dvar_add: float = 0.0, return_packed: bool = False, moments=None):
     """Adjoint of K = variance * f(r(A / ls, Bm / ls)) [n1, n2] given Kbar [n1, n2], `leaf` of one of the stationary families
     (stationaries.py:209-210 SquaredExponential, :254-313 Matern12 / 32 / 52; Exponential; RationalQuadratic with its `alpha`; the
     static families have no distance and never come here: KernelSpec._adjoint).
@@ -164,7 +164,11 @@ def stationary_kernel_adjoint(leaf: Leaf, A: torch.Tensor, Bm: torch.Tensor, Kba
     one elementwise pass that recomputes r2 from the inputs (`gpk_kernel_matrix_combine` op 3); for the
     SquaredExponential -2 dK/dr2 = K, so G also carries d/dvariance = sum(Kbar .* K) / variance; the Matern families
     take that sum from a second pass (op 1).  d/dvariance = sum(Kbar .* K) / variance holds for every family.  An extra `x` of
-    the family (the RationalQuadratic's alpha) adds d/dx = sum(Kbar .* dK/dx) (op "d" + x: "dalpha", into the same buffer)."""
+    the family (the RationalQuadratic's alpha) adds d/dx = sum(Kbar .* dK/dx) (op "d" + x: "dalpha", into the same buffer).
+
+    moments: a callable that builds the right-hand side Vt of the contraction R = G Vt^T in place of ops.moment_rows(Bm); its first
+    1 + 2 D rows must be those moment rows (an input-map kernel appends the rows its own tail needs: KernelSpec._adjoint), and R
+    is handed back as a fourth result."""
     n1, D = A.shape
     variance, lengthscales = leaf.variance, leaf.lengthscales
     ls = ls_device(lengthscales, D, A.device)
@@ -179,17 +183,20 @@ def stationary_kernel_adjoint(leaf: Leaf, A: torch.Tensor, Bm: torch.Tensor, Kba
         for name in leaf.row.extras:
             dextras.append(ops.kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="d" + name, out=G, **kw).sum().reshape(1))
         ops.kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="dr2", out=G, **kw)
-    Vt = ops.moment_rows(Bm)                         # [1, B, B^2]^T
+    Vt = ops.moment_rows(Bm) if moments is None else moments()   # [1, B, B^2]^T
     R = splitk_gemm_nt(G, Vt)                        # [n1, 1 + 2D] = G [1, B, B^2]: row sums rs, G B, G B^2
     # one launch for what follows (it was a dozen elementwise / reduction launches on [n1, D] arrays):  T = G B - A rs;
     # both arguments (symmetric):  A_bar = 2 T / ls^2,  d/dls = (2 sum A^2 rs - 2 sum A GB) / ls^3 = -sum(A A_bar) / ls
     # else:  A_bar = T / ls^2,  d/dls = sum(GB2 - 2 A GB + A^2 rs) / ls^3 = sum(GB2 - A (GB + T)) / ls^3;  d/dvariance = sum(rs) / variance
     # (packed_into = (small [1 + D], A_bar) of an earlier adjoint of the SAME kernel: the results are added to it in the same launch;
     #  return_packed: (small, A_bar) instead of the three views)
-    dvar, dls, Abar = ops.stationary_adjoint_tail(R, A if A.is_contiguous() else A.contiguous(), ls, variance=variance,
-                                                  symmetric=symmetric, sum_kbar_k=sum_kbar_k, into=packed_into, dvar_add=dvar_add)
+    dvar, dls, Abar = ops.stationary_adjoint_tail(R if moments is None else R[:, :1 + 2 * D],   # (a view: ldr stays R's width)
+                                                  A if A.is_contiguous() else A.contiguous(), ls, variance=variance, symmetric=symmetric,
+                                                  sum_kbar_k=sum_kbar_k, into=packed_into, dvar_add=dvar_add)
     if return_packed:
         return (packed_into[0] if packed_into is not None else dls._base), Abar
+    if moments is not None:
+        return dvar, torch.cat([_ls_grad(dls, leaf), *dextras]), Abar, R
     return dvar, torch.cat([_ls_grad(dls, leaf), *dextras]), Abar
 
 
@@ -213,10 +220,15 @@ class KernelSpec:
       adjoint  member i sees  Kbar (Sum)  or  Kbar .* prod_{j != i} k_j  (Product: formed by the same in-place combine pass)
                and goes through `stationary_kernel_adjoint`; the input gradients of the members add up."""
 
-    def __init__(self, members, op=None, cols=None):
+    def __init__(self, members, op=None, cols=None, periods=None):
         """members: leaves or tuples, see the class; cols[i]: the input columns member i sees (its `active_dims` as an index
         list, kernels/base.py:90-109) or None for all of them.  Members that see different columns are built and differentiated on
-        their own column slices; their input gradients are scattered back into the full columns and add up."""
+        their own column slices; their input gradients are scattered back into the full columns and add up.
+
+        periods[i]: None, or the period (0-d or [D_i]) of a Periodic member (kernels/periodic.py).  Its inputs go through the warp
+        Phi (ops.periodic_warp) after the column selection, and its leaf is in the DEVICE form -- the base family over the 2 D_i
+        warped columns with lengthscales 2 l, an ARD one repeated pairwise.  Its gradients come back in the user's form: d/dl (one,
+        or D_i), the extras, then d/dperiod last in the shape gradient, and an input gradient over the D_i columns."""
         self.members = [m if isinstance(m, Leaf) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
@@ -232,6 +244,13 @@ class KernelSpec:
         if len(cols) != len(self.members):
             raise ValueError("one column selection per member")
         self.cols = [None if c is None else np.asarray(c, dtype=np.int64).reshape(-1) for c in cols]
+        periods = [None] * len(self.members) if periods is None else list(periods)
+        if len(periods) != len(self.members):
+            raise ValueError("one period (or None) per member")
+        self.periods = [None if p is None else np.asarray(p, dtype=np.float64) for p in periods]
+        for leaf, p in zip(self.members, self.periods):
+            if p is not None and (leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
+                raise ValueError("a periodic member is a leaf with a distance over the warped columns, its period 0-d or [D]")
         self._idx = {}
 
     @staticmethod
@@ -241,7 +260,7 @@ class KernelSpec:
     @property
     def packable(self) -> bool:
         """one member whose two adjoints fit the packed tail of `_covariance_tail` ([variance, lengthscales] and A_bar in one launch)"""
-        return self.n == 1 and self.cols[0] is None and self.members[0].is_plain
+        return self.n == 1 and self.cols[0] is None and self.periods[0] is None and self.members[0].is_plain
 
     @staticmethod
     def _check_tree(node, n):
@@ -264,14 +283,21 @@ class KernelSpec:
     def n(self) -> int:
         return len(self.members)
 
-    def _sl(self, i: int, X):
-        """member i's view of the inputs: the columns of its active_dims as a contiguous copy (None stays None)"""
+    def _columns(self, i: int, X):
+        """the columns of member i's active_dims as a contiguous copy (None stays None)"""
         if X is None or self.cols[i] is None:
             return X
         key = (i, str(X.device))
         if key not in self._idx:
             self._idx[key] = torch.as_tensor(self.cols[i], device=X.device)
         return X.index_select(1, self._idx[key]).contiguous()
+
+    def _sl(self, i: int, X):
+        """member i's view of the inputs: its columns, then -- a periodic member -- the warp"""
+        X = self._columns(i, X)
+        if X is None or self.periods[i] is None:
+            return X
+        return ops.periodic_warp(X if X.is_contiguous() else X.contiguous(), self.periods[i])
 
     def build(self, X1, X2, out=None, diag_add: float = 0.0):
         return self._build(self.tree, X1, X2, out, diag_add)
@@ -325,8 +351,34 @@ class KernelSpec:
         """device copies of the members' lengthscales, made now (see `ls_device`)"""
         for i, leaf in enumerate(self.members):
             if not leaf.is_static:
-                ls_device(leaf.lengthscales, D if self.cols[i] is None else len(self.cols[i]), device)
+                Di = D if self.cols[i] is None else len(self.cols[i])
+                if self.periods[i] is not None:   # (the stationary tail at the warped width, the periodic tail at the base's)
+                    ls_device(self._base_lengthscales(i), Di, device)
+                    Di *= 2
+                ls_device(leaf.lengthscales, Di, device)
         return self
+
+    def _base_lengthscales(self, i: int):
+        """a periodic member's lengthscales as its user holds them: the device form halved (exact), an ARD one un-paired"""
+        ls = self.members[i].lengthscales
+        return (ls if ls.ndim == 0 or ls.size == 1 else ls.reshape(-1)[0::2]) / 2.0
+
+    def _periodic_adjoint(self, i: int, Ai, Bi, Kbar, symmetric):
+        """A periodic member's adjoint from its column-selected inputs: the stationary adjoint of the device-form leaf at the warped
+        inputs -- with the extra moment rows of the period gradient riding in its one contraction -- then ops.periodic_adjoint_tail.
+        (d/dvariance, [d/dl as the user holds them, extras, d/dperiod], A_bar [n1, D_i])."""
+        leaf, per = self.members[i], self.periods[i]
+        same = Bi is Ai
+        Ai = Ai if Ai.is_contiguous() else Ai.contiguous()
+        Bi = Ai if same else (Bi if Bi.is_contiguous() else Bi.contiguous())
+        PA = ops.periodic_warp(Ai, per)
+        PB = PA if Bi is Ai else ops.periodic_warp(Bi, per)
+        dv, dl, Pbar, R = stationary_kernel_adjoint(leaf, PA, PB, Kbar, symmetric=symmetric,
+                                                    moments=lambda: ops.periodic_moment_rows(Bi, per))
+        nls = leaf.n_lengthscales   # entries of dl in front of the extras: d/dl = 2 d/d(2 l), the two columns of a pair added
+        g_ls = 2.0 * dl[:1] if nls == 1 else 2.0 * (dl[0:nls:2] + dl[1:nls:2])
+        dper, Ab = ops.periodic_adjoint_tail(Ai, PA, Pbar, R, ls_device(self._base_lengthscales(i), Ai.shape[1], Ai.device), per)
+        return dv, torch.cat([g_ls, dl[nls:], dper]), Ab
 
     def adjoint(self, A, Bm, Kbar, symmetric: bool):
         """([d/dvariance_i [1]], [shape gradient_i: d/dlengthscales_i, then d/dalpha_i], A_bar [n1, D]) given Kbar, members in index
@@ -344,9 +396,13 @@ class KernelSpec:
                 dv = Kbar.sum() if leaf.family == "Constant" else torch.diagonal(Kbar).sum() if symmetric else Kbar.new_zeros(())
                 acc["dl"][node], acc["dv"][node] = Kbar.new_zeros(0), dv.reshape(1)
                 return
-            Ai = self._sl(node, A)
-            Bi = Ai if (symmetric and Bm is A) else self._sl(node, Bm)
-            dv, dl, Ab = stationary_kernel_adjoint(leaf, Ai, Bi, Kbar, symmetric=symmetric)
+            if self.periods[node] is not None:
+                Ai = self._columns(node, A)
+                dv, dl, Ab = self._periodic_adjoint(node, Ai, Ai if (symmetric and Bm is A) else self._columns(node, Bm), Kbar, symmetric)
+            else:
+                Ai = self._sl(node, A)
+                Bi = Ai if (symmetric and Bm is A) else self._sl(node, Bm)
+                dv, dl, Ab = stationary_kernel_adjoint(leaf, Ai, Bi, Kbar, symmetric=symmetric)
             acc["dl"][node], acc["dv"][node] = dl, dv.reshape(1)
             if all(c is None for c in self.cols):
                 acc["Abar"] = Ab if acc["Abar"] is None else acc["Abar"] + Ab
@@ -380,12 +436,34 @@ class KernelSpec:
             return dvs[0], dls[0]
         return torch.cat(dvs), list(dls)
 
+    def parameter_names(self, i: int) -> tuple:
+        """names of member i's hyperparameters in the order of its gradients: the leaf's, then a periodic member's "period" """
+        return self.members[i].row.parameters + (("period",) if self.periods[i] is not None else ())
+
+    def n_shape(self, i: int) -> int:
+        """entries of member i's shape gradient: Leaf.n_shape, and for a periodic member the user's lengthscales, the extras, the period"""
+        leaf = self.members[i]
+        if self.periods[i] is None:
+            return leaf.n_shape
+        return max(leaf.n_lengthscales // 2, 1) + len(leaf.extras) + int(self.periods[i].size)
+
+    def split_shape(self, i: int, g) -> dict:
+        """member i's shape gradient as {"lengthscales": ..., <extra>: [1], ..., "period": ...}: Leaf.split_shape, and for a periodic
+        member the user's form -- its lengthscale entries are what precedes the extras and the trailing period entries"""
+        leaf = self.members[i]
+        if self.periods[i] is None:
+            return leaf.split_shape(g)
+        nper, nex = int(self.periods[i].size), len(leaf.extras)
+        nls = g.shape[0] - nper - nex
+        return {"lengthscales": g[:nls], **{name: g[nls + j:nls + j + 1] for j, name in enumerate(leaf.row.extras)}, "period": g[nls + nex:]}
+
     def kernel_grads(self, g_var, g_shape) -> dict:
         """the kernel's entries of a `grads` dict from what `pack` returned: "variance", "lengthscales" (a static member's is empty)
-        and -- only when a member has one -- "alpha": [1] for one member, else a list with None for the members without"""
+        and -- only when a member has one -- "alpha" and "period": one tensor for one member, else a list with None for the members
+        without"""
         if self.n == 1:
-            return {"variance": g_var, **self.members[0].split_shape(g_shape)}
-        parts = [leaf.split_shape(g) for leaf, g in zip(self.members, g_shape)]
+            return {"variance": g_var, **self.split_shape(0, g_shape)}
+        parts = [self.split_shape(i, g) for i, g in enumerate(g_shape)]
         return {"variance": g_var, **{name: [p.get(name) for p in parts] for name in dict.fromkeys(k for p in parts for k in p)}}
 
 
@@ -839,7 +917,7 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
     kdiag = spec.kdiag()
     nmem = spec.n
-    nlsm = [leaf.n_shape for leaf in spec.members]             # shape-gradient entries per member (lengthscales: 1 = isotropic; + extras)
+    nlsm = [spec.n_shape(i) for i in range(nmem)]           # shape-gradient entries per member (lengthscales: 1 = isotropic; + extras)
 
     def all_reduce(t):
         if sharded:

@@ -93,9 +93,11 @@ class Kernel(Module, metaclass=abc.ABCMeta):
 class DeviceLeaf(Kernel):
     """A kernel that gpk_kernel_matrix builds from host hyperparameters (the stationary and the static families): `family` names its
     row of leaf.FAMILIES, `leaf()` is its current values and `leaf_params()` the Parameters behind them, in the same order;
-    K_diag = variance."""
+    K_diag = variance.  `maps_inputs`: `slice` does more than select columns (Periodic warps them), so `leaf()` goes with the output of
+    `slice` only -- whoever hands a builder inputs it did not get from `slice` must decline such a kernel."""
     family: Optional[str] = None
     device_leaf = True
+    maps_inputs = False
 
     def leaf_params(self) -> tuple:
         return tuple(getattr(self, name) for name in BY_NAME[self.family].parameters)
@@ -195,6 +197,7 @@ def gradient_spec(kernel, input_dim=None):
     carry their own `active_dims` (kernels/base.py:90-109): the spec then builds and differentiates each member on its own columns
     and scatters its input gradient back (round 5) -- `input_dim`, the number of input columns, resolves slices.  None if `kernel`
     is not such a combination."""
+    from .periodic import Periodic
     from .stationaries import IsotropicStationary
     from .statics import Static
     from .. import gradients
@@ -206,9 +209,9 @@ def gradient_spec(kernel, input_dim=None):
     def walk(k):
         if isinstance(k, Combination):
             return (k._op, [walk(c) for c in k.kernels])
-        if not (isinstance(k, (IsotropicStationary, Static)) and is_device_leaf(k)):
-            raise NotImplementedError("gradients of a kernel combination: Sums / Products (possibly nested) of isotropic-stationary "
-                                      "and static members (kernels/base.py:216-220, 305-315)")
+        if not (isinstance(k, (IsotropicStationary, Static, Periodic)) and is_device_leaf(k)):
+            raise NotImplementedError("gradients of a kernel combination: Sums / Products (possibly nested) of isotropic-stationary, "
+                                      "Periodic and static members (kernels/base.py:216-220, 305-315)")
         ks.append(k)
         return len(ks) - 1
     tree = walk(kernel)
@@ -222,7 +225,12 @@ def gradient_spec(kernel, input_dim=None):
             cols.append(np.arange(int(input_dim))[k.active_dims])
         else:
             cols.append(np.asarray(k.active_dims, dtype=np.int64))
-    return gradients.KernelSpec([k.leaf() for k in ks], tree, cols=cols), [k.leaf_params() for k in ks]
+    # (a Periodic member: the columns are its base's, the warp is the spec's -- `periods`)
+    for k, c in zip(ks, cols):
+        if isinstance(k, Periodic) and (c is not None or input_dim is not None):
+            k.check_width(len(c) if c is not None else int(input_dim))
+    periods = [k.period.numpy() if isinstance(k, Periodic) else None for k in ks]
+    return gradients.KernelSpec([k.leaf() for k in ks], tree, cols=cols, periods=periods), [k.leaf_params() for k in ks]
 
 
 class Sum(Combination):

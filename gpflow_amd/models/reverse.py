@@ -11,6 +11,7 @@ from ..base import FillTriangular
 from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
 from ..kernels.base import Combination, gradient_spec, is_device_leaf
+from ..kernels.periodic import Periodic
 from ..kernels.statics import Static
 from ..kernels.stationaries import IsotropicStationary
 from ..likelihoods import Gaussian
@@ -48,8 +49,8 @@ def minibatch_scale(num_data, rows) -> float:
 
 def _supported_stationary(k) -> bool:
     """a leaf of the reverse pass: an isotropic-stationary kernel (SquaredExponential, Matern, Exponential, RationalQuadratic) or a
-    static one (White, Constant) that the device builds"""
-    return isinstance(k, (IsotropicStationary, Static)) and is_device_leaf(k)
+    static one (White, Constant) that the device builds, or a Periodic kernel over a stationary base"""
+    return isinstance(k, (IsotropicStationary, Static, Periodic)) and is_device_leaf(k)
 
 
 class CovarianceRoute:
@@ -58,30 +59,38 @@ class CovarianceRoute:
     back to Z's columns.
       one SquaredExponential / Matern kernel: a one-member spec over ALL columns of inputs sliced by its `active_dims` out here
         (a spec with `cols` would leave the packed covariance tail of gradients.svgp_elbo_and_grad);
+      one Periodic kernel: the same, sliced by its BASE's `active_dims` -- the columns only; the warp is the spec's (`periods`);
       a Sum / Product of them, flat or nested: kernels.base.gradient_spec -- the spec slices for its members itself.
     Anything else raises NotImplementedError."""
 
     def __init__(self, kernel, input_dim=None):
         self.kernel = kernel
+        self._columns_of = kernel.base_kernel if isinstance(kernel, Periodic) else kernel   # whose `slice` selects columns and no more
         self.is_combination = isinstance(kernel, Combination)
         if self.is_combination:
             self.spec, self.members = gradient_spec(kernel, input_dim)
         elif _supported_stationary(kernel):
-            self.spec, self.members = gradients.KernelSpec([kernel.leaf()]), [kernel.leaf_params()]
+            period = kernel.period.numpy() if isinstance(kernel, Periodic) else None
+            if period is not None and (input_dim is not None or not isinstance(kernel.active_dims, slice)):   # before the device
+                kernel.check_width(len(np.arange(int(input_dim))[kernel.active_dims]) if isinstance(kernel.active_dims, slice)
+                                   else len(kernel.active_dims))
+            self.spec, self.members = gradients.KernelSpec([kernel.leaf()], periods=[period]), [kernel.leaf_params()]
         else:
-            raise NotImplementedError("gradients: a SquaredExponential / Matern / Exponential / RationalQuadratic / White / Constant "
-                                      "kernel, or a Sum / Product (possibly nested) of them")
+            raise NotImplementedError("gradients: a SquaredExponential / Matern / Exponential / RationalQuadratic / White / Constant / "
+                                      "Periodic kernel, or a Sum / Product (possibly nested) of them")
 
     def inputs(self, Z, X):
         """(Z, X, scatter) as passed to `gradients.*`; Z None (GPR): X alone is sliced"""
         if self.is_combination:
             return Z, X.contiguous(), (lambda gz: gz)
         if Z is None:
-            return None, self.kernel.slice(X, None)[0].contiguous(), None
-        return sliced(self.kernel, Z, X)
+            return None, self._columns_of.slice(X, None)[0].contiguous(), None
+        return sliced(self._columns_of, Z, X)
 
     def spec_at(self, values):
         """the spec with the members' values replaced, each laid out as its `members` entry (the trainer's current values)"""
+        if any(p is not None for p in self.spec.periods):
+            raise NotImplementedError("a Periodic member's leaf is not its Parameters' values (lengthscales 2 l over the warped columns)")
         return gradients.KernelSpec([leaf.replace(vals) for leaf, vals in zip(self.spec.members, values)], self.spec.tree, self.spec.cols)
 
     def member_grads(self, g):
@@ -90,8 +99,8 @@ class CovarianceRoute:
         several: "variance" [n] and one list per name)"""
         one = self.spec.n == 1
         gv = g["variance"].reshape(-1)
-        return [(gv[i:i + 1],) + tuple((g[name] if one else g[name][i]).reshape(-1) for name in leaf.row.parameters[1:])
-                for i, leaf in enumerate(self.spec.members)]
+        return [(gv[i:i + 1],) + tuple((g[name] if one else g[name][i]).reshape(-1) for name in self.spec.parameter_names(i)[1:])
+                for i in range(self.spec.n)]
 
     def kernel_pairs(self, g):
         """[(Parameter, dF/d constrained as NumPy)] of the members, in member order (the variances come back in one copy)"""

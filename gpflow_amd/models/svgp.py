@@ -112,7 +112,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         k, iv = self.kernel, self.inducing_variable
         if not isinstance(k, kernel_class or SeparateIndependent):
             return None
-        if not all(is_device_leaf(kk) and kk.has_default_active_dims for kk in k.kernels):
+        # (a kernel that maps its inputs -- Periodic -- is declined: these routes hand the builders RAW inputs; the composed path runs)
+        if not all(is_device_leaf(kk) and kk.has_default_active_dims and not kk.maps_inputs for kk in k.kernels):
             return None
         if isinstance(iv, SharedIndependentInducingVariables) and isinstance(iv.inducing_variable, InducingPoints):
             return k.kernels, iv.inducing_variable.Z.device_value().contiguous()
@@ -352,7 +353,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             ops.check_info(info)
             Fv += float(F.cpu()[0])
             kernel_pairs += route.kernel_pairs(g)
-            host = {n: g[n].cpu().numpy() for n in g if n not in ("variance", "lengthscales", "alpha", "Z")}
+            host = {n: g[n].cpu().numpy() for n in g if n not in ("variance", "lengthscales", "alpha", "period", "Z")}
             gz = scatter(g["Z"]).cpu().numpy()
             zgrads[id(iv.Z)] = (iv.Z, zgrads[id(iv.Z)][1] + gz if id(iv.Z) in zgrads else gz)   # shared Z: contributions add up
             hosts.append(host)

@@ -676,6 +676,80 @@ def stationary_adjoint_tail(R: torch.Tensor, A: torch.Tensor, ls: torch.Tensor, 
     return small[0:1], small[1:], Abar
 
 
+# ------------------------------------------------------------------------------------------------ the Periodic kernel's input warp
+def _period_host(period, d: int):
+    """(host array, ard_period) of the C-ABI: one period, or one per input column.  2 d columns must fit the builders."""
+    if d < 1 or 2 * d > MAX_D:
+        raise ValueError(f"periodic warp: input dimension {d} outside [1, {MAX_D // 2}] (the warped inputs have 2 D columns, at most {MAX_D})")
+    p = np.atleast_1d(np.asarray(period, dtype=np.float64))
+    if p.ndim != 1 or p.size not in (1, d):
+        raise ValueError(f"period has shape {p.shape}, input dimension is {d}")
+    return _lib.host_doubles(p.tolist()), int(p.size > 1)
+
+
+def periodic_warp(X: torch.Tensor, period, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Phi(X) [n, 2 D] for X [n, D]: Phi[:, 2 j] = cos(2 pi x_j / p_j), Phi[:, 2 j + 1] = sin(2 pi x_j / p_j) (include/gpk.h:
+    gpk_periodic_warp); `period` a scalar or [D], host values."""
+    lib = _lib.load()
+    _chk(X, "X", 2)
+    n, d = X.shape
+    per, ard = _period_host(period, d)
+    if out is None:
+        out = torch.empty((n, 2 * d), dtype=torch.float64, device=X.device)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (n, 2 * d):
+        raise ValueError("periodic_warp: out must be [n, 2 D]")
+    rc = lib.gpk_periodic_warp(_stream(), X.data_ptr(), _rowmajor(X, "X"), n, d, per, ard, out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_periodic_warp")
+    return out
+
+
+def periodic_moment_rows(B: torch.Tensor, period) -> torch.Tensor:
+    """[1; Phi(B)^T; (Phi(B)^2)^T; (b cos)^T, (b sin)^T interleaved] as [1 + 6 D, n2] for B [n2, D]: the right-hand side of the one
+    contraction behind a Periodic kernel's adjoint (gradients.KernelSpec._adjoint).  Its first 1 + 4 D rows are moment_rows(periodic_warp(B))."""
+    lib = _lib.load()
+    _chk(B, "B", 2)
+    n2, d = B.shape
+    per, ard = _period_host(period, d)
+    Vt = torch.empty((1 + 6 * d, n2), dtype=torch.float64, device=B.device)
+    rc = lib.gpk_periodic_moment_rows(_stream(), B.data_ptr(), _rowmajor(B, "B"), n2, d, per, ard, Vt.data_ptr(), max(n2, 1))
+    _lib.check(rc, "gpk_periodic_moment_rows")
+    return Vt
+
+
+def periodic_adjoint_tail(X: torch.Tensor, Phi: torch.Tensor, Phibar: torch.Tensor, R: torch.Tensor, ls: torch.Tensor, period, *,
+                          into: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d/dperiod [1] or [D], X_bar [n1, D]) of a Periodic kernel from its first argument X [n1, D], Phi = periodic_warp(X), Phibar
+    [n1, 2 D] (the A_bar of stationary_adjoint_tail at the warped inputs), R [n1, 1 + 6 D] = G periodic_moment_rows(B)^T and the BASE
+    lengthscales as a [D] device tensor (include/gpk.h: gpk_periodic_adjoint_tail) -- one launch.  d/dperiod covers both arguments of
+    K.  into = (d/dperiod, X_bar) of an earlier call: the results are ADDED to them."""
+    lib = _lib.load()
+    for t, name in ((X, "X"), (Phi, "Phi"), (Phibar, "Phibar"), (R, "R")):
+        _chk(t, name, 2)
+    _chk(ls, "ls", 1)
+    n1, d = X.shape
+    per, ard = _period_host(period, d)
+    if tuple(Phi.shape) != (n1, 2 * d) or tuple(Phibar.shape) != (n1, 2 * d) or tuple(R.shape) != (n1, 1 + 6 * d) or ls.shape[0] != d \
+            or not ls.is_contiguous():
+        raise ValueError("periodic_adjoint_tail: Phi and Phibar must be [n1, 2 D], R [n1, 1 + 6 D], ls a contiguous [D]")
+    np_ = d if ard else 1
+    if into is None:
+        dper = torch.empty(np_, dtype=torch.float64, device=X.device)
+        Xbar = torch.empty((n1, d), dtype=torch.float64, device=X.device)
+    else:
+        dper, Xbar = into
+        _chk(dper, "into[0]", 1)
+        _chk(Xbar, "into[1]", 2)
+        if dper.shape[0] != np_ or tuple(Xbar.shape) != (n1, d) or not dper.is_contiguous():
+            raise ValueError("periodic_adjoint_tail: into must be (d/dperiod [1 or D], X_bar [n1, D])")
+    rc = lib.gpk_periodic_adjoint_tail(_stream(), X.data_ptr(), _rowmajor(X, "X"), Phi.data_ptr(), _rowmajor(Phi, "Phi"),
+                                       Phibar.data_ptr(), _rowmajor(Phibar, "Phibar"), R.data_ptr(), _rowmajor(R, "R"), n1, d,
+                                       ls.data_ptr(), per, ard, Xbar.data_ptr(), _rowmajor(Xbar, "X_bar"), dper.data_ptr(),
+                                       int(into is not None))
+    _lib.check(rc, "gpk_periodic_adjoint_tail")
+    return dper, Xbar
+
+
 def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, *, beta1: float, beta2: float, epsilon: float,
                step: float, maximise: bool = False) -> torch.Tensor:
     """tf.keras Adam on one contiguous variable, in place (p, m, v): one launch instead of seven (include/gpk.h: gpk_adam_step).

@@ -73,6 +73,10 @@ class SVGPTrainer:
         if isinstance(model.kernel, SeparateIndependent) and not isinstance(model.inducing_variable, SharedIndependentInducingVariables):
             raise NotImplementedError("the trainer with separate kernels per latent: shared inducing points")
         routes, c, self.separate = reverse.svgp_routes(model)
+        if any(p is not None for r, _ in routes for p in r.spec.periods):
+            raise NotImplementedError("the trainer keeps (variance, lengthscales) per kernel on the device side of its step: no Periodic "
+                                      "member (its period, and a leaf that is not its Parameters' values) -- SVGP.elbo_and_grad with "
+                                      "optimizers.Scipy covers it")
         if not all(leaf.is_plain for r, _ in routes for leaf in r.spec.members):
             raise NotImplementedError("the trainer keeps (variance, lengthscales) per kernel on the device side of its step: no "
                                       "RationalQuadratic (alpha), White or Constant (no lengthscales) members -- SVGP.elbo_and_grad "

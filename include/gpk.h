@@ -383,6 +383,35 @@ int gpk_moment_rows(void* stream, const double* B, long ldb, int n2, int d, doub
 int gpk_stationary_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, int d,
                                 const double* ls_dev, double variance, int symmetric, const double* sum_kbar_k,
                                 double* Abar, long ldab, double* small, int accumulate, double dvar_add);
+/* ---- the Periodic kernel's input warp (periodic.hip) --------------------------------------------------------
+ * Periodic over a base kernel k evaluated on r^2 (gpflow/kernels/periodic.py):  k(r^2),  r^2 = sum_j sin^2(pi (x_j - x'_j) / p_j) / l_j^2.
+ * With a_j = 2 pi x_j / p_j and Phi(x) = (cos a_1, sin a_1, ..., cos a_d, sin a_d):  |Phi_j(x) - Phi_j(x')|^2 = 4 sin^2(pi (x_j - x'_j) / p_j),
+ * so it is the base kernel on Phi(X) [n, 2 d] with lengthscales 2 l_j for both columns of pair j: every builder and driver above
+ * takes it as a stationary leaf of width 2 d <= GPK_MAX_D.  period_host: HOST pointer, d entries if ard_period, else one (as ls_host).
+ * All three return GPK_E_ARG -- before any launch -- for d <= 0, 2 d > GPK_MAX_D, a leading dimension that is too small or a period
+ * that is not positive and finite.
+ *
+ * gpk_periodic_warp:  Phi[i, 2 j] = cos(2 pi x_ij / p_j),  Phi[i, 2 j + 1] = sin(2 pi x_ij / p_j)  as sincospi(2 x / p): x = k p gives
+ *   exactly (1, 0).  X [n, d] ldx, Phi [n, 2 d] ldphi (padding beyond 2 d is never written); n == 0 returns 0 without a launch.  A NaN
+ *   or Inf in x_ij makes Phi[i, 2 j] and Phi[i, 2 j + 1] NaN and nothing else. */
+int gpk_periodic_warp(void* stream, const double* X, long ldx, int n, int d, const double* period_host, int ard_period, double* Phi,
+                      long ldphi);
+/* gpk_periodic_moment_rows:  Vt [1 + 6 d, n2] ldv = [1 ; Phi(B)^T ; (Phi(B).^2)^T ; (b .* cos)^T, (b .* sin)^T interleaved as Phi is] for
+ *   B [n2, d].  The first 1 + 4 d rows are gpk_moment_rows of gpk_periodic_warp(B), bit for bit; R = G Vt^T [n1, 1 + 6 d] feeds
+ *   gpk_stationary_adjoint_tail (its first 1 + 4 d columns, ldr = 1 + 6 d) and gpk_periodic_adjoint_tail. */
+int gpk_periodic_moment_rows(void* stream, const double* B, long ldb, int n2, int d, const double* period_host, int ard_period, double* Vt,
+                             long ldv);
+/* gpk_periodic_adjoint_tail:  from the first argument X [n1, d], Phi = Phi(X) [n1, 2 d], Phibar [n1, 2 d] (the Abar of
+ *   gpk_stationary_adjoint_tail at the warped inputs), R [n1, 1 + 6 d] as above (G = Kbar .* (-2 dK/dr^2)), the BASE lengthscales
+ *   ls_dev [d] (device; an isotropic one repeated) and the periods:
+ *     Xbar[i, j] = (2 pi / p_j) (c_ij Phibar[i, 2 j + 1] - s_ij Phibar[i, 2 j])
+ *     dperiod_j  = pi / (2 p_j^2 l_j^2) sum_i [x_ij s_ij (G c')_ij - x_ij c_ij (G s')_ij - s_ij (G (b c'))_ij + c_ij (G (b s'))_ij]
+ *   the total derivative of sum(Kbar .* K) w.r.t. p_j: both arguments of K, so symmetric and non-symmetric calls are the same.
+ *   dperiod [d] if ard_period, else [1]: the sum over j.  accumulate != 0: Xbar and dperiod are ADDED to.  One workgroup, fixed
+ *   summation order, no atomics. */
+int gpk_periodic_adjoint_tail(void* stream, const double* X, long ldx, const double* Phi, long ldphi, const double* Phibar, long ldpb,
+                              const double* R, long ldr, int n1, int d, const double* ls_dev, const double* period_host, int ard_period,
+                              double* Xbar, long ldxb, double* dperiod, int accumulate);
 /* gpk_adam_step:  tf.keras Adam on one variable of n doubles, in place:  g' = maximise ? -g : g,
  *   m = beta1 m + (1 - beta1) g',  v = beta2 v + (1 - beta2) g'^2,  p -= step m / (sqrt(v) + epsilon),
  *   step = lr sqrt(1 - beta2^t) / (1 - beta1^t) computed by the caller. */
