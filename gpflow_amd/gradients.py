@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .leaf import Leaf
+from .leaf import DotLeaf, Leaf
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -205,6 +205,26 @@ def _ls_grad(dl: torch.Tensor, leaf: Leaf) -> torch.Tensor:
     return dl.sum().reshape(1) if leaf.n_lengthscales == 1 else dl
 
 
+def dot_kernel_adjoint(leaf: DotLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, symmetric: bool):
+    """Adjoint of a dot-product leaf K = k(s), s_ik = sum_j w_j a_ij b_kj (kernels/linears.py: Linear k = s, Polynomial k = (s + offset)^degree)
+    given Kbar [n1, n2].  Returns (d/dvariance [1], or [D] for an ARD variance; shape gradient: [d/doffset] for the Polynomial, empty for
+    Linear; A_bar [n1, D]); symmetric=True (Bm is A, Kbar symmetric): A_bar collects both arguments.
+
+    G = Kbar .* dk/ds is one pass that recomputes s (`gpk_dot_kernel_matrix_combine` op 3; Linear: dk/ds = 1, G is Kbar itself and nothing
+    is launched).  dF/dw_j = sum_i a_ij (G B)_ij, dF/da_ij = w_j (G B)_ij and dF/doffset = sum G all come from ONE contraction
+    R = G [1, B] and the one-launch tail ops.dot_adjoint_tail.  The right-hand side is ops.moment_rows(Bm), its B^2 rows unused: one
+    launch, where a narrower [1; B^T] is a fill, a transpose and a concatenation; the D extra columns of R cost a GEMM nothing
+    measurable at D <= 64 (chosen by the number of launches; neither has been timed)."""
+    D = A.shape[1]
+    if leaf.ard and leaf.n_variance != D:
+        raise ValueError(f"variance has {leaf.n_variance} entries, input dimension is {D}")
+    G = Kbar if leaf.family == "Linear" else ops.dot_kernel_matrix_combine(A, None if symmetric else Bm, Kbar, op="ds", **leaf.keywords())
+    R = splitk_gemm_nt(G if G.is_contiguous() else G.contiguous(), ops.moment_rows(Bm))   # [n1, 1 + 2 D]: row sums, G B, (G B^2 unused)
+    dw, doff, Abar = ops.dot_adjoint_tail(R, A if A.is_contiguous() else A.contiguous(), ls_device(leaf.variance, leaf.n_variance, A.device),
+                                          symmetric=symmetric)
+    return dw, (doff if leaf.row.extras else doff[:0]), Abar
+
+
 class KernelSpec:
     """What the reverse pass needs to know about the covariance function: ONE stationary kernel, or a Sum / Product of
     stationary / static kernels -- flat, or nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220 `Sum`, :305-315 `Product`; the reference
@@ -214,6 +234,11 @@ class KernelSpec:
     A member's SHAPE gradient -- the `dl` entry of `adjoint` -- is laid out like the leaf's `ls_host`: the lengthscale entries,
     then the extras; a static member's is empty (no lengthscale, no input gradient: A_bar is zero and no contraction is launched
     for it).  `kernel_grads` has the leaves split it into the "lengthscales" / "alpha" entries of a `grads` dict.
+
+    A member may also be a dot-product leaf (leaf.DotLeaf: Linear, Polynomial), built and folded by the `gpk_dot_*` entry points.  Its
+    K(x, x) depends on the row, so a spec with one has no `constant_diagonal`: `kdiag()` / `dkdiag()` raise, `kdiag_rows(X)` and
+    `diag_adjoint(X, kd_bar)` take their place; its variance gradient has D entries when the variance is ARD (`n_variance`), its shape
+    gradient is [d/doffset] or empty.
 
       build    the combined matrix, members folded in place by `gpk_kernel_matrix_combine` (no second matrix);
       kdiag    K(x, x): sum or product of the variances (stationary members), dkdiag[i] = d kdiag / d variance_i;
@@ -229,7 +254,7 @@ class KernelSpec:
         Phi (ops.periodic_warp) after the column selection, and its leaf is in the DEVICE form -- the base family over the 2 D_i
         warped columns with lengthscales 2 l, an ARD one repeated pairwise.  Its gradients come back in the user's form: d/dl (one,
         or D_i), the extras, then d/dperiod last in the shape gradient, and an input gradient over the D_i columns."""
-        self.members = [m if isinstance(m, Leaf) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
+        self.members = [m if isinstance(m, (Leaf, DotLeaf)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
         # (k0 + k1) * k2 (kernels/base.py:223-329: a Combination holds kernels, which may be Combinations of the other kind).
@@ -249,7 +274,7 @@ class KernelSpec:
             raise ValueError("one period (or None) per member")
         self.periods = [None if p is None else np.asarray(p, dtype=np.float64) for p in periods]
         for leaf, p in zip(self.members, self.periods):
-            if p is not None and (leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
+            if p is not None and (isinstance(leaf, DotLeaf) or leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
                 raise ValueError("a periodic member is a leaf with a distance over the warped columns, its period 0-d or [D]")
         self._idx = {}
 
@@ -299,13 +324,27 @@ class KernelSpec:
             return X
         return ops.periodic_warp(X if X.is_contiguous() else X.contiguous(), self.periods[i])
 
+    def is_dot(self, i: int) -> bool:
+        """member i is a dot-product leaf (leaf.DotLeaf: Linear, Polynomial): its own builders, and a diagonal that depends on the row"""
+        return isinstance(self.members[i], DotLeaf)
+
+    def n_variance(self, i: int) -> int:
+        """entries of member i's variance gradient: 1, or D for the ARD variance of a dot-product member"""
+        return self.members[i].n_variance if self.is_dot(i) else 1
+
+    def _fold(self, i: int, X1, X2, G, op: str, diag_add: float = 0.0):
+        """G <- G .* k_i(X1, X2) or G + k_i(X1, X2) in place (K recomputed in registers, no second matrix); X1, X2 as member i sees them"""
+        fold = ops.dot_kernel_matrix_combine if self.is_dot(i) else ops.kernel_matrix_combine
+        return fold(X1, X2, G, op=op, diag_add=diag_add, out=G, **self.members[i].keywords())
+
     def build(self, X1, X2, out=None, diag_add: float = 0.0):
         return self._build(self.tree, X1, X2, out, diag_add)
 
     def _build(self, node, X1, X2, out, diag_add=0.0):
         if isinstance(node, int):
-            return ops.kernel_matrix(self._sl(node, X1), self._sl(node, X2), diag_add=diag_add, lower_only=False, out=out,
-                                     **self.members[node].keywords())
+            build = ops.dot_kernel_matrix if self.is_dot(node) else ops.kernel_matrix
+            return build(self._sl(node, X1), self._sl(node, X2), diag_add=diag_add, lower_only=False, out=out,
+                         **self.members[node].keywords())
         op, ch = node
         if len(ch) == 1:
             return self._build(ch[0], X1, X2, out, diag_add)
@@ -313,8 +352,8 @@ class KernelSpec:
         out = self._build(ch[0], X1, X2, out)
         for j, c in enumerate(ch[1:], start=1):
             if isinstance(c, int):      # a leaf folds in place (K recomputed in registers, no second matrix);
-                ops.kernel_matrix_combine(self._sl(c, X1), self._sl(c, X2), out, op=op,   # diag_add rides in the LAST member's launch
-                                          diag_add=diag_add if j == last else 0.0, out=out, **self.members[c].keywords())
+                self._fold(c, self._sl(c, X1), self._sl(c, X2), out, op,                  # diag_add rides in the LAST member's launch
+                           diag_add=diag_add if j == last else 0.0)
             else:                        # a sub-combination needs its own matrix once
                 tmp = self._build(c, X1, X2, None)
                 out.add_(tmp) if op == "add" else out.mul_(tmp)
@@ -322,14 +361,87 @@ class KernelSpec:
             out.diagonal().add_(float(diag_add))
         return out
 
+    def _constant(self, node) -> bool:
+        """no dot-product member under `node`: its diagonal is one host value"""
+        return not self.is_dot(node) if isinstance(node, int) else all(self._constant(c) for c in node[1])
+
+    @property
+    def constant_diagonal(self) -> bool:
+        """K(x, x) is one host scalar, `kdiag()`: every member stationary, periodic or static.  A dot-product member makes it a function
+        of the row: `kdiag_rows(X)` and `diag_adjoint`."""
+        return self._constant(self.tree)
+
     def _kd(self, node) -> float:
         if isinstance(node, int):
+            if self.is_dot(node):
+                raise NotImplementedError("K(x, x) of a dot-product member (Linear, Polynomial) depends on the row: this caller takes the "
+                                          "diagonal for one scalar and has not been converted to KernelSpec.kdiag_rows")
             return self.members[node].variance
         vals = [self._kd(c) for c in node[1]]
         return float(np.prod(vals)) if node[0] == "mul" else float(np.sum(vals))
 
     def kdiag(self) -> float:
         return self._kd(self.tree)
+
+    def _kd_rows(self, node, X):
+        """K(x, x) under `node`: a host float (a constant subtree) or a fresh [rows] tensor"""
+        if self._constant(node):
+            return self._kd(node)
+        if isinstance(node, int):
+            return ops.dot_kernel_diag(self._sl(node, X), **self.members[node].keywords())
+        op, ch = node
+        rows = [c for c in ch if not self._constant(c)]
+        acc = self._kd_rows(rows[0], X)
+        for c in rows[1:]:
+            if isinstance(c, int):      # a leaf folds in place, as in `_build`
+                ops.dot_kernel_diag(self._sl(c, X), acc, op=op, out=acc, **self.members[c].keywords())
+            else:
+                sub = self._kd_rows(c, X)
+                acc.add_(sub) if op == "add" else acc.mul_(sub)
+        const = [self._kd(c) for c in ch if self._constant(c)]
+        if const:                       # the constant members enter as one scalar
+            acc.add_(float(np.sum(const))) if op == "add" else acc.mul_(float(np.prod(const)))
+        return acc
+
+    def kdiag_rows(self, X) -> torch.Tensor:
+        """K(x_b, x_b) for the rows of X [B, D] as a [B] device tensor: leaves through ops.dot_kernel_diag, combinations folded by its
+        ops "mul" / "add" and by scalars for the members with a constant diagonal"""
+        kd = self._kd_rows(self.tree, X)
+        return kd if torch.is_tensor(kd) else torch.full((X.shape[0],), float(kd), dtype=torch.float64, device=X.device)
+
+    def diag_adjoint(self, X, kd_bar):
+        """([d/dvariance_i], [shape gradient_i]) of sum_b kd_bar_b K(x_b, x_b), members in index order, laid out as `adjoint` lays
+        them out.  A member with a constant diagonal collects sum_b of what reaches it; a dot-product member g = (what reaches it)
+        .* dkd/ds and, from ONE thin product of g with ops.moment_rows(X), d/dw_j = sum_b g_b x_bj^2 and d/doffset = sum_b g_b.  For a
+        Product the other children's diagonals enter as in `_adjoint`."""
+        acc = {"dv": [None] * self.n, "dl": [None] * self.n}
+        self._diag_adjoint(self.tree, X, kd_bar if kd_bar.is_contiguous() else kd_bar.contiguous(), acc)
+        return acc["dv"], acc["dl"]
+
+    def _diag_adjoint(self, node, X, bar, acc):
+        if isinstance(node, int):
+            leaf = self.members[node]
+            if not self.is_dot(node):
+                acc["dv"][node], acc["dl"][node] = bar.sum().reshape(1), bar.new_zeros(self.n_shape(node))
+                return
+            Xi = self._sl(node, X)
+            Xi = Xi if Xi.is_contiguous() else Xi.contiguous()
+            D = Xi.shape[1]
+            g = bar if leaf.family == "Linear" else ops.dot_kernel_diag(Xi, bar, op="ds", **leaf.keywords())
+            m = ops.gemm_nt(g.reshape(1, -1), ops.moment_rows(Xi))[0]      # [1 + 2 D]: sum g, sum g x_j, sum g x_j^2
+            dw = m[1 + D:]
+            acc["dv"][node] = dw if leaf.ard else dw.sum().reshape(1)
+            acc["dl"][node] = m[0:1] if leaf.row.extras else m[:0]
+            return
+        op, ch = node
+        for jc, c in enumerate(ch):
+            b = bar
+            if op == "mul":
+                b = bar.clone()
+                for jo, o in enumerate(ch):
+                    if jo != jc:
+                        b.mul_(self._kd_rows(o, X))
+            self._diag_adjoint(c, X, b, acc)
 
     def _dkd(self, node) -> dict:
         if isinstance(node, int):
@@ -350,7 +462,9 @@ class KernelSpec:
     def warm(self, device, D: int) -> "KernelSpec":
         """device copies of the members' lengthscales, made now (see `ls_device`)"""
         for i, leaf in enumerate(self.members):
-            if not leaf.is_static:
+            if self.is_dot(i):              # (the weights of the dot-product tail)
+                ls_device(leaf.variance, leaf.n_variance, device)
+            elif not leaf.is_static:
                 Di = D if self.cols[i] is None else len(self.cols[i])
                 if self.periods[i] is not None:   # (the stationary tail at the warped width, the periodic tail at the base's)
                     ls_device(self._base_lengthscales(i), Di, device)
@@ -396,14 +510,17 @@ class KernelSpec:
                 dv = Kbar.sum() if leaf.family == "Constant" else torch.diagonal(Kbar).sum() if symmetric else Kbar.new_zeros(())
                 acc["dl"][node], acc["dv"][node] = Kbar.new_zeros(0), dv.reshape(1)
                 return
-            if self.periods[node] is not None:
+            if self.is_dot(node):
+                Ai = self._sl(node, A)
+                dv, dl, Ab = dot_kernel_adjoint(leaf, Ai, Ai if (symmetric and Bm is A) else self._sl(node, Bm), Kbar, symmetric=symmetric)
+            elif self.periods[node] is not None:
                 Ai = self._columns(node, A)
                 dv, dl, Ab = self._periodic_adjoint(node, Ai, Ai if (symmetric and Bm is A) else self._columns(node, Bm), Kbar, symmetric)
             else:
                 Ai = self._sl(node, A)
                 Bi = Ai if (symmetric and Bm is A) else self._sl(node, Bm)
                 dv, dl, Ab = stationary_kernel_adjoint(leaf, Ai, Bi, Kbar, symmetric=symmetric)
-            acc["dl"][node], acc["dv"][node] = dl, dv.reshape(1)
+            acc["dl"][node], acc["dv"][node] = dl, dv.reshape(-1)   # ([1]; an ARD dot-product member: [D])
             if all(c is None for c in self.cols):
                 acc["Abar"] = Ab if acc["Abar"] is None else acc["Abar"] + Ab
             else:   # scatter the member's input gradient back into the columns it read
@@ -423,8 +540,7 @@ class KernelSpec:
                     if jo == jc:
                         continue
                     if isinstance(o, int):
-                        ops.kernel_matrix_combine(self._sl(o, A), None if symmetric else self._sl(o, Bm), Kb, op="mul", out=Kb,
-                                                  **self.members[o].keywords())
+                        self._fold(o, self._sl(o, A), None if symmetric else self._sl(o, Bm), Kb, "mul")
                     else:
                         Kb.mul_(self._build(o, A, None if symmetric else Bm, None))
             self._adjoint(c, A, Bm, Kb, symmetric, acc)
@@ -549,9 +665,21 @@ class _Seed:
         """sum_bp c: what every fvar's Knn = kdiag collects"""
         return self.c.sum() if self.dim == 2 else self.c.sum() * self.P if self.dim == 1 else self.c * self.B * self.P
 
+    def crows(self):
+        """sum_p c_bp per row [B]: what the Knn = K(x_b, x_b) of row b's fvar collects when the diagonal depends on the row"""
+        if self.dim == 2:
+            return self.c.sum(1)
+        if self.dim == 1:
+            return self.c * self.P
+        return torch.full((self.B,), float(self.c) * self.P, dtype=self.fmean.dtype, device=self.fmean.device)
+
+    def kdiag_bar(self, spec: "KernelSpec"):
+        """the `knn_bar` of _covariance_tail: the scalar `csum` for a spec with a constant diagonal, else the rows `crows`"""
+        return self.csum() if spec.constant_diagonal else self.crows()
+
     def noise_grad(self, ve, s0, ssq, kdiag):
         """dF/d sigma^2 of the Gaussian likelihood: [1], or one entry per row (likelihood parameters are then reached through
-        Gaussian.noise_param_grads)"""
+        Gaussian.noise_param_grads).  kdiag: the host scalar, or the rows [B] of a diagonal that depends on the row."""
         B, P, scale, nv = self.B, self.P, self.scale, self.nv
         if self.dim == 1:
             # dF/d sigma_n^2 = scale sum_p (-1 / (2 s2_n) + ((y - f)^2 + fvar) / (2 s2_n^2))
@@ -562,6 +690,20 @@ class _Seed:
         #   d/ds2 = scale (-B P / (2 s2) + Q / (2 s2^2)) = (scale / s2) (B P (k0 - 1/2) - ve)          (two launches)
         k0 = -0.5 * LOG2PI - 0.5 * float(np.log(nv))
         return torch.mul(ve, -scale / nv).add_(scale / nv * B * P * (k0 - 0.5)).reshape(1)
+
+
+_ROW_DIAGONAL = "a dot-product member (Linear, Polynomial): K(x, x) depends on the row, which is not built into "
+
+
+def _knn_terms(spec: KernelSpec, Xb, s0):
+    """(knn, s0, K(x, x)) as the Gaussian data term takes the first two and _Seed.noise_grad the third.  A constant diagonal: the
+    host scalar, s0 untouched.  A diagonal that depends on the row (rows kd [B]): the C ABI keeps its host-scalar knn, so knn = 0
+    and s0 - kd go in; the kernel's (knn - s0) + ssq is then (kd - s0) + ssq in the reference's order, 0 - x being exact."""
+    if spec.constant_diagonal:
+        kd = spec.kdiag()
+        return [kd], s0, kd
+    kd = spec.kdiag_rows(Xb)
+    return [0.0], s0 - kd, kd
 
 
 def _factorise(spec: KernelSpec, Z, X, jitter):
@@ -594,8 +736,16 @@ def _project(At, q_mu, q_sqrt, **fmean_stats):
 def _covariance_tail(spec: KernelSpec, Z, Xb, Kuf_bar, LT, LinvT, Lbar, knn_bar, *, first=None, packed=False, before_products=None):
     """From Kuf_bar [M, B] and Lm_bar to (d/dvariance, d/dlengthscales, Z_bar):  Kuu_bar by the Cholesky adjoint (LT = Lm^T), the
     kernel adjoints of Kuf and of Kuu, and  knn_bar * d kdiag / d variance_i  for the Knn = kdiag in every fvar.
-    first: the Kuf adjoint where the caller already has it (SGPR sums it over the shards); before_products: see cholesky_adjoint."""
+    first: the Kuf adjoint where the caller already has it (SGPR sums it over the shards); before_products: see cholesky_adjoint.
+    A spec without a constant diagonal (a dot-product member): knn_bar is dF/dKnn per ROW of Xb [B] (_Seed.crows) and the members'
+    variance and offset gradients collect sum_b knn_bar_b d K(x_b, x_b) / d theta (KernelSpec.diag_adjoint); Z does not enter Knn."""
     Kuu_bar = cholesky_adjoint(LT, LinvT, Lbar, before_products=before_products)
+    if not spec.constant_diagonal:
+        dv1, dl1, Zb1 = first if first is not None else spec.adjoint(Z, Xb, Kuf_bar, symmetric=False)
+        dv2, dl2, Zb2 = spec.adjoint(Z, Z, Kuu_bar, symmetric=True)
+        dv3, dl3 = spec.diag_adjoint(Xb, knn_bar)
+        g_var, g_ls = spec.pack([a + b + c for a, b, c in zip(dv1, dv2, dv3)], [a + b + c for a, b, c in zip(dl1, dl2, dl3)])
+        return g_var, g_ls, Zb1 + Zb2
     dkd = spec.dkdiag()
     if packed:
         # one stationary kernel over all input columns: the second adjoint ADDS its variance / lengthscale / Z gradients to the
@@ -700,6 +850,8 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
 
     # ---------------------------------------------------------------- forward (intermediates kept)
+    if likelihood is not None and not spec.constant_diagonal:
+        raise NotImplementedError(_ROW_DIAGONAL + "the quadrature likelihoods' reverse pass")
     fwd = _svgp_forward(spec, Z, Xb, q_mu, q_sqrt, jitter)
     s0, fmean, ssq = fwd.s0, fwd.fmean, fwd.ssq
     if likelihood is not None:
@@ -707,7 +859,8 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
                                                              params=likelihood[1], mean_const=mean_const, want_grads=True)
         ve = lik_out[0:1]
     else:
-        ve, _ = ops.gaussian_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], noise_variance=noise_variance,
+        knn, s0_knn, kd = _knn_terms(spec, Xb, s0)
+        ve, _ = ops.gaussian_varexp_sum(Yb, fmean, s0=s0_knn, ssq=ssq, knn=knn, noise_variance=noise_variance,
                                         mean_const=mean_const)
     kl = ops.gauss_kl_white(q_mu, q_sqrt)
     F = torch.mul(ve, scale).sub_(kl, alpha=kl_weight)
@@ -718,7 +871,7 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     g_var, g_ls, Zbar, g_qmu, g_qs = _svgp_backward(spec, Z, Xb, q_mu, q_sqrt, fwd, seed, kl_weight)
     grads = spec.kernel_grads(g_var, g_ls)
     if likelihood is None:
-        grads["noise_variance"] = seed.noise_grad(ve, s0, ssq, spec.kdiag())
+        grads["noise_variance"] = seed.noise_grad(ve, s0, ssq, kd)
     grads.update({"Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": seed.r.sum().reshape(1)})
     if likelihood is not None and likelihood[0] == "student_t":
         grads["likelihood_scale"] = lik_out[1:2] * scale
@@ -781,7 +934,7 @@ def _svgp_backward(spec: KernelSpec, Z, Xb, q_mu, q_sqrt, fwd: _SvgpForward, see
     LT = ops.transpose(L, mode=1)
     with _SideBranch(Z, branch_q_prep, branch_q_products) as branch:
         Lbar = splitk_gemm_nt(Kuf_bar, A, c_lower=True, alpha=-1.0)                     # -tril(Kfu_bar^T At)
-        g_var, g_ls, Zbar = _covariance_tail(spec, Z, Xb, Kuf_bar, LT, LinvT, Lbar, seed.csum(), packed=one_kernel,
+        g_var, g_ls, Zbar = _covariance_tail(spec, Z, Xb, Kuf_bar, LT, LinvT, Lbar, seed.kdiag_bar(spec), packed=one_kernel,
                                              before_products=branch.release)
     g_qmu, g_qs = branch.results
     return g_var, g_ls, Zbar, g_qmu, g_qs
@@ -804,6 +957,8 @@ def svgp_elbo_and_grad_lcm(Zs, Xs, Yb: torch.Tensor, q_mu: torch.Tensor, q_sqrt:
     M = q_mu.shape[0]
     if W.ndim != 2 or W.shape[1] != Lnum or q_mu.shape[1] != Lnum or tuple(q_sqrt.shape) != (Lnum, M, M):
         raise ValueError("svgp_elbo_and_grad_lcm needs W [P, L], q_mu [M, L] and a full q_sqrt [L, M, M] for its L kernel_specs")
+    if not all(spec.constant_diagonal for spec in kernel_specs):
+        raise NotImplementedError(_ROW_DIAGONAL + "the mixing stage (one knn per latent)")
     for spec, Z in zip(kernel_specs, Zs):
         spec.warm(Z.device, Z.shape[1])
     # ---------------------------------------------------------------- phase 1: the latents' forwards
@@ -914,6 +1069,8 @@ def sgpr_elbo_and_grad(Z: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, *, var
         raise ValueError("num_data differs from the number of rows of a model that is not sharded")
     # (kernel_spec: a Sum / Product of stationary kernels, members possibly over different input columns -- round 5)
     spec = kernel_spec if kernel_spec is not None else KernelSpec.single(variance, lengthscales, family, alpha)
+    if not spec.constant_diagonal:
+        raise NotImplementedError(_ROW_DIAGONAL + "SGPR: its statistics take sum_n K(x_n, x_n) as N times one scalar")
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
     kdiag = spec.kdiag()
     nmem = spec.n
@@ -1054,7 +1211,8 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
             V = V.unsqueeze(0)
         kl = 0.5 * (ops.sumsq(alphat)[0] - M * P - torch.log(Lq.diagonal(dim1=1, dim2=2) ** 2).sum()
                     + sum(ops.sumsq(V[p])[0] for p in range(P))) + P * ops.sum_log_diag(L)[0]
-    ve, _ = ops.gaussian_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], noise_variance=noise_variance,
+    knn, s0_knn, kd = _knn_terms(spec, Xb, s0)
+    ve, _ = ops.gaussian_varexp_sum(Yb, fmean, s0=s0_knn, ssq=ssq, knn=knn, noise_variance=noise_variance,
                                     mean_const=mean_const)
     F = scale * ve - k * kl
     # ---- backward
@@ -1093,7 +1251,7 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
     X2 = ops.gemm_nt(X1, Linv, b_tri=2)                                                 # (.) Linv^T
     Lbar = splitk_gemm_nt(Kuf_bar, A, c_lower=True, alpha=-1.0) - torch.tril(X2)
     Lbar.diagonal().sub_(k * P / L.diagonal())
-    g_var, g_ls, Zbar = _covariance_tail(spec, Z, Xb, Kuf_bar, ops.transpose(L, mode=1), LinvT, Lbar, seed.csum())
-    grads = {**spec.kernel_grads(g_var, g_ls), "noise_variance": seed.noise_grad(ve, s0, ssq, spec.kdiag()),
+    g_var, g_ls, Zbar = _covariance_tail(spec, Z, Xb, Kuf_bar, ops.transpose(L, mode=1), LinvT, Lbar, seed.kdiag_bar(spec))
+    grads = {**spec.kernel_grads(g_var, g_ls), "noise_variance": seed.noise_grad(ve, s0, ssq, kd),
              "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)}
     return F, grads, info

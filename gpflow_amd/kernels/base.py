@@ -9,7 +9,7 @@ import torch
 
 from ..base import Module
 from .. import ops
-from ..leaf import BY_NAME, Leaf
+from ..leaf import BY_NAME, DOT_BY_NAME, Leaf
 
 ActiveDims = Union[slice, Sequence[int]]
 
@@ -119,6 +119,12 @@ def is_device_leaf(k) -> bool:
     return bool(getattr(k, "device_leaf", False)) and getattr(k, "family", None) in ops.KERNEL_FAMILIES
 
 
+def is_dot_leaf(k) -> bool:
+    """True for a dot-product kernel (kernels/linears.py: Linear, Polynomial), built by gpk_dot_kernel_matrix.  Never together with
+    `is_device_leaf`: its K_diag depends on the row, which the routes that ask `is_device_leaf` do not allow for."""
+    return getattr(k, "dot_family", None) in DOT_BY_NAME
+
+
 class Combination(Kernel):
     """A list of kernels reduced elementwise (gpflow/kernels/base.py:223-329); nested instances of the same class are
     flattened (:247-255).  Every member slices its own active_dims, so the combination itself never slices."""
@@ -148,7 +154,8 @@ class Combination(Kernel):
 
     def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
         """The first member is built into `out`; every further device-built member (stationary or static) is folded in by
-        gpk_kernel_matrix_combine (K recomputed in registers: one read + one write of `out`, no second matrix)."""
+        gpk_kernel_matrix_combine (K recomputed in registers: one read + one write of `out`, no second matrix), a dot-product member
+        (Linear, Polynomial) by gpk_dot_kernel_matrix_combine in the same way."""
         X = ops.to_device(X)
         X2 = ops.to_device(X2) if X2 is not None else None
         ks = list(self.kernels)
@@ -161,6 +168,8 @@ class Combination(Kernel):
             dadd = diag_add if i == last else 0.0
             if is_device_leaf(k):
                 ops.kernel_matrix_combine(Xs, X2s, out, op=self._op, diag_add=dadd, out=out, **k.leaf().keywords())
+            elif is_dot_leaf(k):
+                ops.dot_kernel_matrix_combine(Xs, X2s, out, op=self._op, diag_add=dadd, out=out, **k.leaf().keywords())
             else:
                 Ki = k.K_into(Xs, X2s, None)
                 out.add_(Ki) if self._op == "add" else out.mul_(Ki)
@@ -209,9 +218,9 @@ def gradient_spec(kernel, input_dim=None):
     def walk(k):
         if isinstance(k, Combination):
             return (k._op, [walk(c) for c in k.kernels])
-        if not (isinstance(k, (IsotropicStationary, Static, Periodic)) and is_device_leaf(k)):
+        if not ((isinstance(k, (IsotropicStationary, Static, Periodic)) and is_device_leaf(k)) or is_dot_leaf(k)):
             raise NotImplementedError("gradients of a kernel combination: Sums / Products (possibly nested) of isotropic-stationary, "
-                                      "Periodic and static members (kernels/base.py:216-220, 305-315)")
+                                      "Periodic, static and dot-product (Linear, Polynomial) members (kernels/base.py:216-220, 305-315)")
         ks.append(k)
         return len(ks) - 1
     tree = walk(kernel)

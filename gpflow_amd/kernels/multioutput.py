@@ -55,7 +55,7 @@ class SharedIndependent(MultioutputKernel):
         return K[None].expand(P, *K.shape).contiguous()  # [P, N, N2]
 
     def K_diag(self, X, full_output_cov: bool = True):
-        K = self.kernel.K_diag(X)  # [N]
+        K = self.kernel(X, full_cov=False)  # [N]  (through __call__: a diagonal that depends on the row reads the member's own columns)
         P = self.output_dim
         Ks = K[:, None].expand(-1, P)  # [N, P]
         return torch.diag_embed(Ks) if full_output_cov else Ks.contiguous()
@@ -83,7 +83,7 @@ class SeparateIndependent(MultioutputKernel):
         return Kxxs
 
     def K_diag(self, X, full_output_cov: bool = False):
-        stacked = torch.stack([k.K_diag(X) for k in self.kernels], dim=1)  # [N, P]
+        stacked = torch.stack([k(X, full_cov=False) for k in self.kernels], dim=1)  # [N, P]
         return torch.diag_embed(stacked) if full_output_cov else stacked
 
 
@@ -127,7 +127,7 @@ class LinearCoregionalization(MultioutputKernel):
         return torch.einsum("lnm,kl,kl->knm", Kxx, W, W)  # [P, N, N2]
 
     def K_diag(self, X, full_output_cov: bool = True):
-        Kd, W = torch.stack([k.K_diag(X) for k in self.kernels], dim=1), self.mixing()  # [N, L]
+        Kd, W = torch.stack([k(X, full_cov=False) for k in self.kernels], dim=1), self.mixing()  # [N, L]
         if full_output_cov:
             return torch.einsum("nl,kl,ql->nkq", Kd, W, W)  # [N, P, P]
         return Kd @ (W ** 2).t()  # [N, P]

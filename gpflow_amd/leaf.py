@@ -115,6 +115,102 @@ class Leaf(collections.namedtuple("_LeafFields", "row variance lengthscales extr
         return {"lengthscales": g[:cuts[0]], **{name: g[cuts[j]:cuts[j + 1]] for j, name in enumerate(self.row.extras)}}
 
 
+class DotFamily(NamedTuple):
+    name: str
+    code: int                          # GPK_DOT_* of include/gpk.h: NOT a GPK_KERN_* code, the stationary builders do not take it
+    extras: Tuple[str, ...] = ()       # hyperparameters with a gradient beyond the variance, in the order of the shape gradient
+
+    @property
+    def parameters(self) -> Tuple[str, ...]:
+        return ("variance",) + self.extras
+
+
+DOT_FAMILIES = (DotFamily("Linear", 0), DotFamily("Polynomial", 1, ("offset",)))
+DOT_BY_NAME = {f.name: f for f in DOT_FAMILIES}
+DOT_MAX_DEGREE = 16                    # GPK_DOT_MAX_DEGREE
+
+
+class DotLeaf(collections.namedtuple("_DotLeafFields", "row variance offset degree")):
+    """One dot-product leaf's host values (gpflow/kernels/linears.py), immutable: k = s for "Linear", (s + offset)^degree for
+    "Polynomial", s = sum_j variance_j x_j x'_j.  `variance` is 0-d (one weight) or [D] (ARD); `offset` a float; `degree` an int in
+    [1, DOT_MAX_DEGREE], a constant of the leaf without a gradient.  Its diagonal K(x, x) depends on the row: it is no row of FAMILIES,
+    gpk_kernel_matrix and the fused drivers do not take it -- the gpk_dot_* entry points do (ops.dot_kernel_matrix, ...)."""
+    __slots__ = ()
+    is_static = False
+    is_plain = False
+
+    def __new__(cls, family: str, variance, offset=None, degree=None):
+        if family not in DOT_BY_NAME:
+            raise ValueError(f"{family!r} is not a dot-product family: {sorted(DOT_BY_NAME)}")
+        row = DOT_BY_NAME[family]
+        variance = np.asarray(variance, dtype=np.float64)
+        if variance.ndim > 1:
+            raise ValueError(f"variance of shape {variance.shape}: one weight, or one per active input column")
+        if row.name == "Linear":
+            if offset is not None or degree is not None:
+                raise ValueError("offset and degree belong to the 'Polynomial' family, not to 'Linear'")
+            return tuple.__new__(cls, (row, variance, 0.0, 1))
+        if offset is None or degree is None:
+            raise ValueError("family 'Polynomial' needs offset and degree")
+        return tuple.__new__(cls, (row, variance, float(offset), check_degree(degree)))
+
+    @classmethod
+    def of(cls, family: str, values, degree=None) -> "DotLeaf":
+        """from the values in Parameter order (DotFamily.parameters) and the constant degree"""
+        return cls(family, **dict(zip(DOT_BY_NAME[family].parameters, values)), **({} if degree is None else {"degree": degree}))
+
+    def replace(self, values) -> "DotLeaf":
+        return DotLeaf.of(self.family, values, degree=self.degree if self.row.extras else None)
+
+    @property
+    def family(self) -> str:
+        return self.row.name
+
+    @property
+    def code(self) -> int:
+        return self.row.code
+
+    @property
+    def ard(self) -> bool:
+        return self.variance.ndim == 1
+
+    @property
+    def n_variance(self) -> int:
+        """entries of the variance gradient: 1, or D for an ARD variance"""
+        return int(self.variance.size) if self.ard else 1
+
+    @property
+    def n_shape(self) -> int:
+        """entries of the shape gradient: [d/doffset] for the Polynomial, none for Linear"""
+        return len(self.row.extras)
+
+    def keywords(self) -> dict:
+        """as the `ops.dot_*` builders take a leaf: family=, variance=, and offset= / degree= only where the family has them"""
+        return dict(family=self.family, variance=self.variance, **(dict(offset=self.offset, degree=self.degree) if self.row.extras else {}))
+
+    def host(self, d: int):
+        """(host array of the weights, ard) of the C-ABI"""
+        w = np.atleast_1d(self.variance)
+        if self.ard and w.size != d:
+            raise ValueError(f"variance has {w.size} entries, input dimension is {d}")
+        return _lib.host_doubles(w.tolist()), int(self.ard)
+
+    def split_shape(self, g) -> dict:
+        """a shape gradient as {"lengthscales": empty, "offset": [1]}: no lengthscales, by the static members' convention"""
+        return {"lengthscales": g[:0], **{name: g[j:j + 1] for j, name in enumerate(self.row.extras)}}
+
+
+def check_degree(degree) -> int:
+    """the Polynomial's degree as an int; NotImplementedError unless it is integral and in [1, DOT_MAX_DEGREE]"""
+    try:
+        ok = isinstance(degree, (int, float, np.integer, np.floating)) and float(degree) == int(degree) and 1 <= int(degree) <= DOT_MAX_DEGREE
+    except (ValueError, OverflowError):   # (int(nan), int(inf))
+        ok = False
+    if not ok:
+        raise NotImplementedError(f"Polynomial(degree={degree!r}): an integral degree 1 ... {DOT_MAX_DEGREE}: the power is a product, not pow")
+    return int(degree)
+
+
 def latent_keywords(leaves, d: int) -> dict:
     """variances=, lengthscales=, families= as the per-latent shards (ops.svgp_elbo_shard_sep / _lcm) take one leaf per latent:
     lengthscales [n] (all isotropic) or [n, d]"""

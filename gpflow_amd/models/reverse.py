@@ -10,7 +10,7 @@ from .. import gradients
 from ..base import FillTriangular
 from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
-from ..kernels.base import Combination, gradient_spec, is_device_leaf
+from ..kernels.base import Combination, gradient_spec, is_device_leaf, is_dot_leaf
 from ..kernels.periodic import Periodic
 from ..kernels.statics import Static
 from ..kernels.stationaries import IsotropicStationary
@@ -53,6 +53,17 @@ def _supported_stationary(k) -> bool:
     return isinstance(k, (IsotropicStationary, Static, Periodic)) and is_device_leaf(k)
 
 
+ROW_DIAGONAL = "a dot-product kernel or member (Linear, Polynomial), whose K(x, x) depends on the row,"
+
+
+def has_row_diagonal(k) -> bool:
+    """a dot-product kernel (kernels/linears.py) anywhere under k -- in a Sum / Product, or behind a multi-output wrapper"""
+    if is_dot_leaf(k):
+        return True
+    members = [k.kernel] if isinstance(k, SharedIndependent) else getattr(k, "kernels", [])
+    return any(has_row_diagonal(m) for m in members)
+
+
 class CovarianceRoute:
     """One covariance function as the reverse pass takes it: `spec` (gradients.KernelSpec), `members` [the Parameters of each leaf,
     in the leaf's order: DeviceLeaf.leaf_params] in the spec's order, the inputs as `gradients.*` gets them and the scatter of dF/dZ
@@ -75,9 +86,11 @@ class CovarianceRoute:
                 kernel.check_width(len(np.arange(int(input_dim))[kernel.active_dims]) if isinstance(kernel.active_dims, slice)
                                    else len(kernel.active_dims))
             self.spec, self.members = gradients.KernelSpec([kernel.leaf()], periods=[period]), [kernel.leaf_params()]
+        elif is_dot_leaf(kernel):
+            self.spec, self.members = gradients.KernelSpec([kernel.leaf()]), [kernel.leaf_params()]
         else:
             raise NotImplementedError("gradients: a SquaredExponential / Matern / Exponential / RationalQuadratic / White / Constant / "
-                                      "Periodic kernel, or a Sum / Product (possibly nested) of them")
+                                      "Periodic / Linear / Polynomial kernel, or a Sum / Product (possibly nested) of them")
 
     def inputs(self, Z, X):
         """(Z, X, scatter) as passed to `gradients.*`; Z None (GPR): X alone is sliced"""
@@ -99,13 +112,18 @@ class CovarianceRoute:
         several: "variance" [n] and one list per name)"""
         one = self.spec.n == 1
         gv = g["variance"].reshape(-1)
-        return [(gv[i:i + 1],) + tuple((g[name] if one else g[name][i]).reshape(-1) for name in self.spec.parameter_names(i)[1:])
+        cut = self._variance_cuts()
+        return [(gv[cut[i]:cut[i + 1]],) + tuple((g[name] if one else g[name][i]).reshape(-1) for name in self.spec.parameter_names(i)[1:])
                 for i in range(self.spec.n)]
+
+    def _variance_cuts(self):
+        """where member i's entries of grads["variance"] begin: one each, D for the ARD variance of a dot-product member"""
+        return np.concatenate([[0], np.cumsum([self.spec.n_variance(i) for i in range(self.spec.n)])]).astype(int)
 
     def kernel_pairs(self, g):
         """[(Parameter, dF/d constrained as NumPy)] of the members, in member order (the variances come back in one copy)"""
-        gv = g["variance"].reshape(-1).cpu().numpy()
-        return [(par, gv[i:i + 1] if j == 0 else gr.cpu().numpy())
+        gv, cut = g["variance"].reshape(-1).cpu().numpy(), self._variance_cuts()
+        return [(par, gv[cut[i]:cut[i + 1]] if j == 0 else gr.cpu().numpy())
                 for i, (pars, grs) in enumerate(zip(self.members, self.member_grads(g))) for j, (par, gr) in enumerate(zip(pars, grs))]
 
 
@@ -158,8 +176,17 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
         q_sqrt -- one route per latent, and `separate` is True (also for a single member: the callers name and slice by it).
     quadrature (a Bernoulli / Poisson / StudentT / MultiClass likelihood, `likelihood=` of gradients.svgp_elbo_and_grad): whitened,
     one kernel over all input columns, at most 16 latents.  narrow (natural gradients on q(u)): one kernel over all input columns,
-    full q_sqrt, constant noise.  A LinearCoregionalization kernel: `_lcm_routes` -- one route per latent, and its own refusals."""
+    full q_sqrt, constant noise.  A LinearCoregionalization kernel: `_lcm_routes` -- one route per latent, and its own refusals.
+    A dot-product kernel or member (Linear, Polynomial; `has_row_diagonal`): the plain routes of the first two lines only -- with
+    quadrature, narrow, SeparateIndependent or LinearCoregionalization it is refused here, by the limit it breaks."""
     k, iv = model.kernel, model.inducing_variable
+    if has_row_diagonal(k):   # Linear / Polynomial: covered by the plain route alone -- every other one takes K(x, x) for one scalar
+        limit = "the quadrature likelihoods' reverse pass: its variational expectations take K(x, x) as one value per latent" if quadrature \
+            else "natural gradients: their reverse pass is the packed one-kernel form with a scalar K(x, x)" if narrow \
+            else "the per-latent reverse passes (SeparateIndependent, LinearCoregionalization): one scalar K(x, x) per latent" \
+            if isinstance(k, (SeparateIndependent, LinearCoregionalization)) else None
+        if limit is not None:
+            raise NotImplementedError(f"gradients: {ROW_DIAGONAL} is not built into {limit}")
     if isinstance(k, LinearCoregionalization):
         return _lcm_routes(model, quadrature=quadrature, narrow=narrow)
     plain = not (quadrature or narrow)

@@ -167,7 +167,10 @@ class SGPR(GPModel, InternalDataTrainingLossMixin):
         k, iv, lik = self.kernel, self.inducing_variable, self.likelihood
         c = self.mean_function.constant_value()
         from ..kernels.base import Combination
-        from .reverse import CovarianceRoute
+        from .reverse import ROW_DIAGONAL, CovarianceRoute, has_row_diagonal
+        if has_row_diagonal(k):   # (forward included: elbo, upper_bound and predict_f all go through the statistics)
+            raise NotImplementedError(f"SGPR: {ROW_DIAGONAL} is not built into its statistics, which take sum_n K(x_n, x_n) as N times "
+                                      "one scalar")
         if not ((is_device_leaf(k) or isinstance(k, Combination)) and isinstance(iv, InducingPoints) and isinstance(lik, Gaussian)
                 and c is not None):
             raise NotImplementedError("SGPR here: stationary kernel (or a Sum / Product of them), InducingPoints, Gaussian "

@@ -353,7 +353,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             ops.check_info(info)
             Fv += float(F.cpu()[0])
             kernel_pairs += route.kernel_pairs(g)
-            host = {n: g[n].cpu().numpy() for n in g if n not in ("variance", "lengthscales", "alpha", "period", "Z")}
+            host = {n: g[n].cpu().numpy() for n in g if n not in ("variance", "lengthscales", "alpha", "period", "offset", "Z")}
             gz = scatter(g["Z"]).cpu().numpy()
             zgrads[id(iv.Z)] = (iv.Z, zgrads[id(iv.Z)][1] + gz if id(iv.Z) in zgrads else gz)   # shared Z: contributions add up
             hosts.append(host)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .leaf import FAMILIES, Leaf
+from .leaf import FAMILIES, DotLeaf, Leaf
 
 NB = 128
 KERNEL_FAMILIES = {f.name: f.code for f in FAMILIES}                      # name -> GPK_KERN_* (include/gpk.h)
@@ -168,6 +168,99 @@ def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch
                                        float(diag_add), G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
     _lib.check(rc, "gpk_kernel_matrix_combine")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ dot-product kernels (dot.hip)
+def _dot_leaf_args(family: str, variance, offset, degree, d: int):
+    """(code, host weights, ard, offset, degree) of the gpk_dot_* entry points for a leaf given by keywords: DotLeaf.host"""
+    leaf = DotLeaf(family, variance, offset=offset, degree=degree)
+    return (leaf.code, *leaf.host(d), float(leaf.offset), int(leaf.degree))
+
+
+def dot_kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, family: str = "Linear", variance, offset=None, degree=None,
+                      diag_add: float = 0.0, lower_only: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2] of a dot-product leaf: "Linear" (X1 * variance) X2^T, or
+    "Polynomial" (that + offset)^degree.  `variance` one weight or [D].  The symmetric build is exactly symmetric (include/gpk.h)."""
+    lib = _lib.load()
+    n1, n2, d, out = _kernel_operands(X1, X2, None, out, zero_new=lower_only)
+    if n1 == 0 or n2 == 0:
+        return out
+    code, w, ard, off, deg = _dot_leaf_args(family, variance, offset, degree, d)
+    rc = lib.gpk_dot_kernel_matrix(_stream(), code, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, w, ard, off, deg,
+                                   float(diag_add), int(lower_only), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_dot_kernel_matrix")
+    return out
+
+
+def dot_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, family: str = "Linear", variance,
+                              offset=None, degree=None, diag_add: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = G .* K(X1, X2) (op "mul"), G + K(X1, X2) (op "add") or G .* dK/ds (op "ds": s the weighted dot product; Polynomial
+    degree (s + offset)^(degree - 1), Linear 1), K recomputed on the fly; `out` may be G itself.  X2 None: K(X1, X1); `diag_add`
+    goes onto the diagonal of the combined result ("mul" / "add"); "ds" does NOT zero the diagonal."""
+    if op not in ("mul", "add", "ds"):
+        raise ValueError(f"dot_kernel_matrix_combine: op {op!r} is not 'mul', 'add' or 'ds'")
+    lib = _lib.load()
+    n1, n2, d, out = _kernel_operands(X1, X2, G, out)
+    if n1 == 0 or n2 == 0:
+        return out
+    code, w, ard, off, deg = _dot_leaf_args(family, variance, offset, degree, d)
+    rc = lib.gpk_dot_kernel_matrix_combine(_stream(), code, {"mul": 1, "add": 2, "ds": 3}[op], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
+                                           *_x2_args(X2, n2), d, w, ard, off, deg, float(diag_add), G.data_ptr(), _rowmajor(G, "G"),
+                                           out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_dot_kernel_matrix_combine")
+    return out
+
+
+def dot_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op: str = "k", family: str = "Linear", variance, offset=None,
+                    degree=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The row diagonal kd [n] of a dot-product leaf over the rows of X [n, D] (op "k"), or g .* kd ("mul"), g + kd ("add"),
+    g .* dkd/ds ("ds") with g [n]; `out` may be g.  kd is the diagonal of dot_kernel_matrix(X, None), bit for bit."""
+    lib = _lib.load()
+    _chk(X, "X", 2)
+    n, d = X.shape
+    if d < 1 or d > MAX_D:
+        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
+    if op not in ("k", "mul", "add", "ds"):
+        raise ValueError(f"dot_kernel_diag: op {op!r} is not 'k', 'mul', 'add' or 'ds'")
+    if (op == "k") != (g is None):
+        raise ValueError("dot_kernel_diag: g goes with the ops 'mul', 'add' and 'ds' and only with them")
+    if g is not None:
+        _chk(g, "g", 1)
+        if g.shape[0] != n or not g.is_contiguous():
+            raise ValueError("dot_kernel_diag: g must be a contiguous [n]")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=X.device)
+    _chk(out, "out", 1)
+    if out.shape[0] != n or not out.is_contiguous():
+        raise ValueError("dot_kernel_diag: out must be a contiguous [n]")
+    if n == 0:
+        return out
+    code, w, ard, off, deg = _dot_leaf_args(family, variance, offset, degree, d)
+    rc = lib.gpk_dot_kernel_diag(_stream(), code, {"k": 0, "mul": 1, "add": 2, "ds": 3}[op], X.data_ptr(), n, _rowmajor(X, "X"), d, w, ard,
+                                 off, deg, None if g is None else g.data_ptr(), out.data_ptr())
+    _lib.check(rc, "gpk_dot_kernel_diag")
+    return out
+
+
+def dot_adjoint_tail(R: torch.Tensor, A: torch.Tensor, w: torch.Tensor, *, symmetric: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(d/dvariance [1 or D], d/doffset [1], A_bar [n1, D]) of a dot-product leaf from R [n1, >= 1 + D] = G [1, B] (G = Kbar .* dK/ds),
+    the first kernel argument A [n1, D] and the weights as a device tensor, [1] or -- ARD -- [D] (include/gpk.h:
+    gpk_dot_adjoint_tail) -- one launch, bit-identical when repeated."""
+    lib = _lib.load()
+    _chk(R, "R", 2)
+    _chk(A, "A", 2)
+    _chk(w, "w", 1)
+    n1, d = A.shape
+    if R.shape[0] != n1 or R.shape[1] < 1 + d or w.shape[0] not in (1, d) or not w.is_contiguous() or d < 1 or d > MAX_D:
+        raise ValueError("dot_adjoint_tail: R must be [n1, >= 1 + D], w a contiguous [1] or [D], D in [1, 64]")
+    ard = int(w.shape[0] == d and d > 1)
+    nw = d if ard else 1
+    small = torch.empty(nw + 1, dtype=torch.float64, device=A.device)
+    Abar = torch.empty((n1, d), dtype=torch.float64, device=A.device)
+    rc = lib.gpk_dot_adjoint_tail(_stream(), R.data_ptr(), _rowmajor(R, "R"), A.data_ptr(), _rowmajor(A, "A"), n1, d, w.data_ptr(), ard,
+                                  int(bool(symmetric)), small.data_ptr(), Abar.data_ptr(), _rowmajor(Abar, "A_bar"))
+    _lib.check(rc, "gpk_dot_adjoint_tail")
+    return small[:nw], small[nw:], Abar
 
 
 def diag_add_(A: torch.Tensor, v: torch.Tensor) -> torch.Tensor:

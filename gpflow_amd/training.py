@@ -72,6 +72,9 @@ class SVGPTrainer:
                                       "(SVGP.elbo_and_grad with optimizers.Scipy does)")
         if isinstance(model.kernel, SeparateIndependent) and not isinstance(model.inducing_variable, SharedIndependentInducingVariables):
             raise NotImplementedError("the trainer with separate kernels per latent: shared inducing points")
+        if reverse.has_row_diagonal(model.kernel):
+            raise NotImplementedError(f"the trainer's device step takes K(x, x) for one scalar: {reverse.ROW_DIAGONAL} is not built into "
+                                      "it -- SVGP.elbo_and_grad with optimizers.Scipy covers it")
         routes, c, self.separate = reverse.svgp_routes(model)
         if any(p is not None for r, _ in routes for p in r.spec.periods):
             raise NotImplementedError("the trainer keeps (variance, lengthscales) per kernel on the device side of its step: no Periodic "

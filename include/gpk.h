@@ -412,6 +412,50 @@ int gpk_periodic_moment_rows(void* stream, const double* B, long ldb, int n2, in
 int gpk_periodic_adjoint_tail(void* stream, const double* X, long ldx, const double* Phi, long ldphi, const double* Phibar, long ldpb,
                               const double* R, long ldr, int n1, int d, const double* ls_dev, const double* period_host, int ard_period,
                               double* Xbar, long ldxb, double* dperiod, int accumulate);
+/* ---- dot-product kernels (dot.hip): Linear and Polynomial (gpflow/kernels/linears.py) ----------------------------------
+ * With s(x, y) = sum_j (x_j w_j) y_j and base = s + offset:
+ *     GPK_DOT_LINEAR      k = s                  dk/ds = 1
+ *     GPK_DOT_POLYNOMIAL  k = base^degree        dk/ds = dk/doffset = degree base^(degree - 1)
+ * These are NOT GPK_KERN_* families and no fused driver takes them: K(x, x) = k(s(x, x)) depends on the row.
+ * w_host: HOST pointer, d entries if ard, else one (as ls_host).  x_j w_j is formed first (X * variance of the reference: one
+ * rounding), the sum over j is an fma chain in ascending j.  degree in [1, GPK_DOT_MAX_DEGREE]; the power is the product
+ * base * base * ... taken left to right, never pow: a negative base behaves as the reference's integer power.  offset and degree are
+ * ignored by GPK_DOT_LINEAR (pass 0.0 and 1).
+ * Every entry point returns, before any launch: GPK_E_ARG for d <= 0, d > GPK_MAX_D, a negative size, a leading dimension that is
+ * too small, w_host == NULL, a weight or an offset that is not finite, a Polynomial degree outside [1, 16], an op out of range;
+ * GPK_E_UNSUPPORTED for a family other than the two.  Signs are not checked.  NaN / Inf propagate as through a matmul: a NaN in row
+ * i of X1 makes row i of K NaN (in the symmetric build column i as well) and nothing else.
+ *
+ * gpk_dot_kernel_matrix: the contract of gpk_kernel_matrix -- X2 == NULL: K(X1, X1) + diag_add I; lower_only; an operand without
+ *   elements may be NULL; nothing beyond n1 x n2 is written.  SYMMETRY: (x_i w) . x_j and (x_j w) . x_i differ in the last bit.  The
+ *   symmetric build computes the elements on or below the diagonal and writes each to its mirror position, so its output is exactly
+ *   symmetric (lower_only: bit for bit the lower triangle of the full build); with X2 given nothing is promised, as by a matmul. */
+#define GPK_DOT_LINEAR 0
+#define GPK_DOT_POLYNOMIAL 1
+#define GPK_DOT_MAX_DEGREE 16
+int gpk_dot_kernel_matrix(void* stream, int family, const double* X1, int n1, long ldx1, const double* X2, int n2, long ldx2, int d,
+                          const double* w_host, int ard, double offset, int degree, double diag_add, int lower_only, double* K,
+                          long ldk);
+/* gpk_dot_kernel_matrix_combine:  out = G .* k (op 1), G + k (op 2) or G .* dk/ds (op 3; Linear: a copy of G), k recomputed from the
+ *   inputs; out may alias G.  X2 == NULL: K(X1, X1) element by element (no mirror), diag_add onto the diagonal of the combined
+ *   result for ops 1 and 2.  Unlike op 3 of gpk_kernel_matrix_combine the diagonal is NOT zeroed: s_ii depends on the parameters. */
+int gpk_dot_kernel_matrix_combine(void* stream, int family, int op, const double* X1, int n1, long ldx1, const double* X2, int n2,
+                                  long ldx2, int d, const double* w_host, int ard, double offset, int degree, double diag_add,
+                                  const double* G, long ldg, double* out, long ldo);
+/* gpk_dot_kernel_diag:  the row diagonal kd_i = k(s(x_i, x_i)) over the rows of X [n, d] ldx, summed as the builder sums it (kd is the
+ *   diagonal of gpk_dot_kernel_matrix(X, NULL) without diag_add, bit for bit).  op 0: out = kd; 1: out = g .* kd; 2: out = g + kd;
+ *   3: out = g .* dkd/ds_i.  g [n] (DEVICE; not read by op 0), out [n]; out may alias g. */
+int gpk_dot_kernel_diag(void* stream, int family, int op, const double* X, int n, long ldx, int d, const double* w_host, int ard,
+                        double offset, int degree, const double* g, double* out);
+/* gpk_dot_adjoint_tail:  from R [n1, >= 1 + d] ldr = G [1, B] (column 0: the row sums of G = Kbar .* dk/ds, columns 1 .. d: G B), the
+ *   first kernel argument A [n1, d] and the weights w_dev (DEVICE; d entries if ard, else one):
+ *     d/dw_j     = sum_i A_ij R_i,1+j      (summed over j as well when !ard)
+ *     d/doffset  = sum_i R_i0
+ *     Abar_ij    = w_j R_i,1+j             (times 2 when symmetric: B is A and G symmetric, both arguments collected)
+ *   dsmall [(ard ? d : 1) + 1] = (d/dw, d/doffset).  From s_ik = sum_j w_j a_ij b_kj:  dF/dw_j = sum_ik G_ik a_ij b_kj,
+ *   dF/da_ij = w_j (G B)_ij.  One workgroup, fixed summation order: a second call is bit-identical. */
+int gpk_dot_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, int d, const double* w_dev, int ard,
+                         int symmetric, double* dsmall, double* Abar, long ldab);
 /* gpk_adam_step:  tf.keras Adam on one variable of n doubles, in place:  g' = maximise ? -g : g,
  *   m = beta1 m + (1 - beta1) g',  v = beta2 v + (1 - beta2) g'^2,  p -= step m / (sqrt(v) + epsilon),
  *   step = lr sqrt(1 - beta2^t) / (1 - beta1^t) computed by the caller. */
