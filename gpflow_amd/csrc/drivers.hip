@@ -20,7 +20,7 @@ int project_parts(hipStream_t s, const double* At, int rows, int m, long ldat, l
                   size_t ws_bytes, const double* V = nullptr, double* s0 = nullptr, double* fmean = nullptr) {
   if ((!At && rows > 0) || !LqT || rows < 0 || m <= 0 || P <= 0 || strideAt < 0) return GPK_E_ARG;
   if (V && ((rows > 0 && (!s0 || !fmean)) || strideAt != 0)) return GPK_E_ARG;
-  if (!ws || ws_bytes < gpk_project_workspace_bytes(rows, m, P)) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, gpk_project_workspace_bytes(rows, m, P)));
   if (rows == 0) return 0;
   const int nt = 2 * gpk_gemm_tiles_n(m);
   GemmArgs g = gemm_base(rows, m, m, 1.0, At, ldat, LqT, ldl, 0.0, nullptr, 0, P, strideAt, (long)m * ldl, 0);
@@ -111,7 +111,7 @@ extern "C" int gpk_gpr_lml(void* stream, int family, const double* X, int n, int
                            double* out, int* info, void* ws, size_t ws_bytes) {
   if (!X || !Y || !out || !info || n <= 0 || P <= 0) return GPK_E_ARG;
   const LmlWs w = lml_layout(ws, n, P);
-  if (!ws || ws_bytes < w.total) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, w.total));
   hipStream_t s = (hipStream_t)stream;
   int rc;
   // K(X,X) + noise I, lower tiles only (gpr.py:100-101); a heteroskedastic likelihood (noise_rows: one variance per data
@@ -424,7 +424,7 @@ int elbo_shard(void* stream, const ElboArgs& a, int whiten, void* ws, size_t ws_
     if (rc) return rc;
   }
   const ElboWs w = elbo_layout(ws, a.m, a.rows, a.P, a.q_diag, whiten);
-  if (!ws || ws_bytes < w.total) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, w.total));
   hipStream_t s = (hipStream_t)stream;
   if (whiten) return elbo_whitened(s, a, w);
   return a.q_diag ? elbo_unwhitened_diag(s, a, w) : elbo_unwhitened_full(s, a, w);
@@ -478,7 +478,7 @@ int elbo_shard_separate(void* stream, const ElboArgs& a, const int* family_host,
       !a.info || m <= 0 || rows < 0 || P <= 0 || P > 16 || d <= 0 || strideZ < 0)
     return GPK_E_ARG;
   const ElboWs w = elbo_sep_layout(ws, m, rows, P);
-  if (!ws || ws_bytes < w.total) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, w.total));
   hipStream_t s = (hipStream_t)stream;
   const int nls = a.k.ard ? d : 1;
   // (ls_host is strided by nls: there is no room for the trailing alpha of a RationalQuadratic member, gpk.h)

@@ -38,6 +38,14 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 static inline size_t gpk_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int gpk_cdiv(int a, int b) { return (a + b - 1) / b; }
+// The workspace contract of include/gpk.h (Conventions, "workspace"), points (c) and (d): what every entry point with a `ws`
+// parameter answers before anything is enqueued -- GPK_E_WORKSPACE for a null or short workspace, GPK_E_ARG for a base that is not
+// 16-byte aligned (the Carver keeps its pieces 256 bytes apart RELATIVE to the base, and the block inverses, the slot partials and
+// the trapezoid's rows are read and written 16 bytes at a time).
+static inline int gpk_check_workspace(const void* ws, size_t ws_bytes, size_t needed) {
+  if (!ws || ws_bytes < needed) return GPK_E_WORKSPACE;
+  return ((uintptr_t)ws & 15) ? GPK_E_ARG : 0;
+}
 
 // ---- GEMM (gemm.hip): GemmArgs, gemm_base and the selection as data (GemmPlan, make_gemm_plan) --------
 #include "gemm_plan.h"

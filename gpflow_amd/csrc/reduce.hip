@@ -228,7 +228,7 @@ int gpk_launch_kl_white_stage1(hipStream_t s, const double* q_mu, const double* 
 extern "C" int gpk_gauss_kl_white(void* stream, const double* q_mu, const double* q_sqrt, int m,
                                   int P, int q_diag, double* out, void* ws, size_t ws_bytes) {
   if (!q_mu || !q_sqrt || !out || m <= 0 || P <= 0) return GPK_E_ARG;
-  if (!ws || ws_bytes < gpk_reduce_workspace_bytes(m)) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, gpk_reduce_workspace_bytes(m)));
   int nb = 0;
   GPK_TRY(gpk_launch_kl_white_stage1((hipStream_t)stream, q_mu, q_sqrt, m, P, q_diag, (double*)ws, &nb, nullptr));
   return gpk_launch_final_one((hipStream_t)stream, (double*)ws, nb, 0.5, -0.5 * (double)m * (double)P, out);
@@ -237,7 +237,7 @@ extern "C" int gpk_gauss_kl_white(void* stream, const double* q_mu, const double
 extern "C" int gpk_sumsq(void* stream, const double* A, int rows, int cols, long lda, int upper_only,
                          double* out, void* ws, size_t ws_bytes) {
   if ((!A && rows > 0 && cols > 0) || !out || rows < 0 || cols < 0) return GPK_E_ARG;
-  if (!ws || ws_bytes < gpk_reduce_workspace_bytes(rows)) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, gpk_reduce_workspace_bytes(rows)));
   int nb = 0;
   GPK_TRY(gpk_launch_sumsq_stage1((hipStream_t)stream, A, rows, cols, lda, upper_only, (double*)ws, &nb));
   return gpk_launch_final_one((hipStream_t)stream, (double*)ws, nb, 1.0, 0.0, out);

@@ -453,7 +453,7 @@ extern "C" int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, 
                                        double noise_variance, const double* noise_rows, double mean_const, double* fvar_out,
                                        double* out, void* ws, size_t ws_bytes) {
   if ((rows > 0 && (!Y || !fmean)) || !knn_host || !out || P <= 0 || P > 16 || rows < 0) return GPK_E_ARG;
-  if (!ws || ws_bytes < gpk_reduce_workspace_bytes(rows)) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, gpk_reduce_workspace_bytes(rows)));
   const LatentMoments m = gpk_latent_moments(Y, ldy, fmean, rows, P, s0, s0_per_latent, ssq, knn_host, knn_per_latent, mean_const, fvar_out);
   int nb = 0;
   GPK_TRY(gpk_launch_varexp_stage1((hipStream_t)stream, m, noise_variance, noise_rows, (double*)ws, &nb));
@@ -488,7 +488,7 @@ extern "C" int gpk_mixed_gaussian_varexp_sum(void* stream, const double* Y, long
   if ((rows > 0 && (!Y || !gmean)) || !W_host || !knn_host || !out || L <= 0 || L > 16 || P <= 0 || P > 16 || rows < 0 ||
       !(noise_variance > 0.0))
     return GPK_E_ARG;
-  if (!ws || ws_bytes < gpk_mixed_varexp_workspace_bytes(rows, L, P)) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, gpk_mixed_varexp_workspace_bytes(rows, L, P)));
   hipStream_t s = (hipStream_t)stream;
   const LatentMoments g = gpk_latent_moments(Y, ldy, gmean, rows, L, s0, s0_per_latent, ssq, knn_host, knn_per_latent, mean_const, nullptr);
   double* part = (double*)ws;
@@ -566,7 +566,7 @@ extern "C" int gpk_likelihood_varexp_sum(void* stream, int lik, const double* li
                                          double* fvar_out, double* rows_out, double* dmu_out, double* dvar_out, double* out,
                                          void* ws, size_t ws_bytes) {
   if ((rows > 0 && (!Y || !fmean)) || !knn_host || !out || P <= 0 || P > 16 || rows < 0) return GPK_E_ARG;
-  if (!ws || ws_bytes < gpk_reduce_workspace_bytes(rows)) return GPK_E_WORKSPACE;
+  GPK_TRY(gpk_check_workspace(ws, ws_bytes, gpk_reduce_workspace_bytes(rows)));
   const LatentMoments m = gpk_latent_moments(Y, ldy, fmean, rows, P, s0, s0_per_latent, ssq, knn_host, knn_per_latent, mean_const, fvar_out);
   double* part = (double*)ws;
   int nb = 0;

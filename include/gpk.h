@@ -10,6 +10,21 @@
  *     config/__config__.py:99); leading dimensions are in elements;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls only enqueue work,
  *     they never synchronise; scratch comes from the caller's workspace;
+ *   - workspace: every entry point with a `void* ws, size_t ws_bytes` pair (gpk_project, _batched, _stats; gpk_gaussian_,
+ *     gpk_likelihood_, gpk_mixed_gaussian_varexp_sum; gpk_gauss_kl_white; gpk_sumsq; gpk_gpr_lml; gpk_svgp_elbo_shard, _lik, _sep,
+ *     _lcm) takes its scratch from the caller, sized by the *_workspace_bytes function named next to it, under one contract:
+ *       (a) contents: what `ws` holds at entry does not matter -- zeros, NaN bytes, or what another call (of another entry point,
+ *           shape or form) left there; the result is bit-identical whatever it is.  The library keeps counters and partial sums
+ *           in there between the launches of ONE call; each is written by a launch of that call before it is read, never
+ *           by a memset packet and never by the caller.  One workspace may therefore be reused across calls of any kind, as
+ *           long as two calls that share it are ordered on their streams;
+ *       (b) bounds: the call reads and writes only the first *_workspace_bytes(...) bytes of `ws`, whatever ws_bytes says;
+ *       (c) refusal: ws == NULL (even where the size is 0) or ws_bytes below that size returns GPK_E_WORKSPACE, and a refused
+ *           call enqueues and writes nothing: not `out`, not `info`, not `ws`;
+ *       (d) alignment: `ws` must be 16-byte aligned (any device allocator's blocks are; an odd element offset into an fp64 buffer
+ *           is not).  The pieces carved from it sit 256 bytes apart relative to the base and are read and written 16 bytes at a
+ *           time.  A base that is not 16-byte aligned returns GPK_E_ARG, with the same nothing-written rule.  No larger alignment
+ *           is required;
  *   - small hyper-parameter vectors (lengthscales) are HOST pointers, copied into kernel arguments;
  *   - empty operands: a pointer to an operand with no elements (0 rows or 0 columns) may be NULL -- a fresh empty tensor
  *     has no storage -- and the call then writes what the empty case defines: nothing for an empty output, the plain

@@ -8,7 +8,9 @@
 //     out fake addresses, the timing calls of the init-time self-check return constants;
 //   * every gpk_launch_* / gpk_* launcher as a stub that logs its stream, a name and the memory its kernel reads and writes.  The
 //     access list of a stub RESTATES its kernel; the kernel restated is named next to it (file:line at the time of writing).  A write
-//     set may be a superset of what the kernel touches, a read set is never a subset.
+//     set may be a superset of what the kernel touches, a read set is never a subset.  Where a kernel reads AND writes the same
+//     memory, the list is in the kernel's order: a read listed before the write is not served by it (the ticket of varexp_tail), a
+//     read listed behind it is (that kernel's block partials) -- assertion 9 of tests/test_potrf_schedule.py relies on this.
 //   * the two GEMM predicates, which are the library's own one-liners over make_gemm_plan (gemm_plan.h, plain C++).
 // Operands are fake addresses chosen here, so the alignment and parity that gpk_potrf_core reads from pointer bits are inputs.
 //

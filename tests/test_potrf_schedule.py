@@ -19,7 +19,9 @@ Edges of the relation
 
 Assertions (check_log): 1 no unordered conflict, 2 no lost hand-off, 3 no cycle, 4 the join is complete, 5 the status word is reset
 before anything may store INT_MAX there, 6 no cycle when the streams are mapped to hardware queues, 7 the workgroups that wait
-in-kernel leave compute units free.
+in-kernel leave compute units free, 8 the whole extent of every access (base + (batch - 1) stride + (rows - 1) ld + cols) lies inside
+its buffer, 9 within one call every read of the caller's workspace is covered by writes of that call that happen-before it
+(workspace_reads_are_written; include/gpk.h, the workspace contract -- necessary only: tests/test_gpu_workspace.py is the real check).
 
 Assertion 6 is a MODEL and is stated as one: streams are mapped to hardware queues by the rule written in aux_create's comment
 (potrf.hip: a pool of normal-priority queues, a new stream opens a queue while the pool is not full and then shares the queue with the
@@ -267,6 +269,7 @@ class Schedule:
     def _close(self):
         order, cyc = self._order()
         self.anc = None
+        self.order = order
         if order is None:
             self.problems.append((3, "cycle in stream order plus signal -> wait edges: " + cyc))
             return
@@ -450,7 +453,7 @@ def test_rectangle_overlap_against_enumeration():
 
 
 def check_log(log, expect=None, pools=(2, 4), **model):
-    """All six assertions on one log; returns the list of (assertion, message) that failed.  expect: launch name -> how often it
+    """All nine assertions on one log; returns the list of (assertion, message) that failed.  expect: launch name -> how often it
     must appear in EVERY call (the hooks: each non-empty one ran exactly once)."""
     sch = Schedule(log, **model)
     STATS["logs"] += 1
@@ -501,6 +504,70 @@ def check_log(log, expect=None, pools=(2, 4), **model):
         cyc = sch.queue_cycle(pool)
         if cyc:
             problems.append((6, "hardware-queue model, pool of %d: a wait that cannot be satisfied: %s" % (pool, cyc)))
+    # 8: the whole extent of every access lies inside its buffer (buffer_of only places the access's first byte)
+    inside = True
+    for n in sch.nodes:
+        for rw, base, rows, cols, ld, batch, stride in n.acc:
+            b = sch.buffer_of(base)
+            end = base + (batch - 1) * stride + (rows - 1) * ld + cols
+            if base < b["base"] or end > b["base"] + b["bytes"]:
+                inside = False
+                problems.append((8, "out of bounds: %s %s [%d, %d) of buffer '%s', which has %d bytes" %
+                                 (n, "writes" if rw == "W" else "reads", base - b["base"], end - b["base"], b["name"], b["bytes"])))
+    # 9: the workspace contract of include/gpk.h, point (a), in the recorded model
+    if inside:
+        problems.extend(workspace_reads_are_written(sch))
+    return problems
+
+
+def workspace_reads_are_written(sch):
+    """Assertion 9.  Within one call, every byte of the caller's workspace (the buffer the runner names 'ws') that a launch reads was
+    written by a launch of the SAME call that happens-before it, or earlier in the access list of the reading launch itself (a stub
+    lists its accesses in the kernel's own order: varexp_tail writes its block partials and then reads them, but reads the ticket before
+    it writes it).  What an earlier call or the caller left in the workspace never counts: its contents at entry do not matter.
+    The launches of a call are walked in one topological order of the happens-before relation.  Where assertion 1 holds, every write
+    that overlaps a read is ordered against it, so the writes met before the reader in that order are exactly the ones that
+    happen-before it.
+    This is NECESSARY, NOT SUFFICIENT: a stub's write set may be a superset of what its kernel touches (lower_only builds declare the
+    whole rectangle, padding rows and columns are never listed), so a kernel that reads what nobody wrote can pass here.
+    tests/test_gpu_workspace.py, which poisons the real workspace on the device, is the real check.  Granularity: 8-byte words."""
+    import numpy as np
+    ws = next((b for b in sch.bufs if b["name"] == "ws"), None)
+    if ws is None:
+        return []
+    lo, hi = ws["base"], ws["base"] + ws["bytes"]
+    written = np.zeros((ws["bytes"] + 7) // 8, dtype=np.bool_)
+
+    def words(base, rows, cols, ld, batch, stride):
+        for z in range(batch):
+            off = base + z * stride - lo
+            w0, w1 = off // 8, (off + cols + 7) // 8
+            if rows == 1:
+                yield written[w0:w1]
+            else:
+                assert ld % 8 == 0, "a pitch inside the workspace that is no multiple of 8 bytes"
+                yield np.lib.stride_tricks.as_strided(written[w0:], shape=(rows, w1 - w0), strides=(ld // 8, 1))
+
+    problems = []
+    for c in sch.calls:
+        written[:] = False
+        for i in sch.order:
+            n = sch.nodes[i]
+            if n.call != c or n.kind != "launch" or n.name.startswith("caller_"):
+                continue
+            for rw, base, rows, cols, ld, batch, stride in n.acc:
+                if not lo <= base < hi:
+                    continue
+                for z, v in enumerate(words(base, rows, cols, ld, batch, stride)):
+                    if rw == "W":
+                        v[...] = True
+                    elif not v.all():
+                        r, w = np.argwhere(~np.atleast_2d(v))[0]
+                        at = base + z * stride + int(r) * ld + 8 * int(w) - lo
+                        problems.append((9, "workspace read before it is written: %s reads byte %d of 'ws' (entry %d, row %d of an access of "
+                                            "%d rows x %d bytes at offset %d), which no launch of call %d that happens-before it has written"
+                                         % (n, at, z, int(r), rows, cols, base - lo, c)))
+                        break
     return problems
 
 
@@ -632,6 +699,38 @@ def test_sweep_drivers(runners):
     for n, P in itertools.product([100, 1024, 4096, 4500, 16384], [1, 4]):
         for mode in ALL_MODES:
             assert_clean(record(runners, "gpr_lml", mode, n=n, P=P, reps=2), ("gpr_lml", n, P, mode), expect={"kernel_matrix.sym": 1})
+
+
+# (M, rows): the shapes of tests/test_gpu_workspace.py, where the device runs on a poisoned workspace -- one leaf block with padding
+# columns (M % 8 = 4) and padding rows (rows % 32 != 0); two leaf blocks with the extra rows riding through the panels; the side
+# schedule with a fused group solve
+WORKSPACE_SHAPES = [(100, 300), (130, 40), (300, 333)]
+
+
+def test_sweep_drivers_workspace_shapes(runners):
+    """assertions 8 and 9 (and the rest) where the workspace layouts have padding: every driver the runner has, P = 1 and 3, two calls
+    on one workspace"""
+    for (m, rows), P, mode in itertools.product(WORKSPACE_SHAPES, (1, 3), ALL_MODES):
+        tag = (m, rows, P, mode)
+        for whiten, q_diag in ((1, 0), (1, 1), (0, 0), (0, 1)):
+            assert_clean(record(runners, "svgp", mode, n=m, rows=rows, P=P, whiten=whiten, q_diag=q_diag, reps=2), ("svgp", whiten, q_diag) + tag)
+            assert_clean(record(runners, "svgp_lik", mode, n=m, rows=rows, P=P, whiten=whiten, q_diag=q_diag, reps=2),
+                         ("svgp_lik", whiten, q_diag) + tag)
+        assert_clean(record(runners, "svgp_sep", mode, n=m, rows=rows, P=P, reps=2), ("svgp_sep",) + tag)
+        assert_clean(record(runners, "gpr_lml", mode, n=m, P=P, reps=2), ("gpr_lml",) + tag)
+
+
+def test_workspace_assertions_catch_what_they_are_for(runners):
+    """8 and 9 on a log that was tampered with: a workspace 256 bytes shorter than the driver's layout, and a whitened shard without
+    its kl_white_stage1 launch (whose kernel zeroes the ticket of the one-launch tail)"""
+    log = record(runners, "svgp", "gate", n=300, rows=333, P=3, reps=2)
+    assert not check_log(log)
+    short = Log(dict(o, bytes=o["bytes"] - 256) if o["k"] == "buf" and o["name"] == "ws" else o for o in log)
+    assert {a for a, _ in check_log(short)} == {8}
+    no_kl = Log(o for o in log if not (o["k"] == "launch" and o["name"] == "kl_white_stage1"))
+    found = [msg for a, msg in check_log(no_kl) if a == 9]
+    assert found and all("varexp_tail" in msg or "final" in msg for msg in found), found
+    assert any("varexp_tail" in msg for msg in found), found
 
 
 def test_unwhitened_full_prefilled_and_not(runners):

@@ -41,6 +41,11 @@ MUTATIONS = [
     ("rest_flag allowed on the masked stream; stream writes there modelled as unordered", "potrf_plan.h",
      [("q.rest_flag = pl.use_flags && p < kMaxFlagPanels && !masked;", "q.rest_flag = pl.use_flags && p < kMaxFlagPanels;")],
      [("potrf", "streamops", dict(n=5000, extra=1))], {"unordered_writes_on": ("masked",)}, 1),
+    ("the shard's layout asks for 256 bytes less than it carves (V, the last piece, sticks out)", "drivers.hip",
+     [("  w.V = c.take((size_t)m * P * sizeof(double));\n  w.total = c.used;", "  w.V = c.take((size_t)m * P * sizeof(double));\n  w.total = c.used - 256;")],
+     [("svgp", m, dict(n=300, rows=333, P=3, whiten=0)) for m in T.ALL_MODES], {}, 8),
+    ("drop the KL launches of the whitened shard (kl_white_kernel zeroes the tail's ticket)", "drivers.hip",
+     [("  return kl_white_to_out(s, a, w);\n}", "  return 0;\n}")], [("svgp", m, dict(n=300, rows=333, P=3)) for m in T.ALL_MODES], {}, 9),
     ("(control) the unmodified tree under the same runs and models", None, [], SHAPES_SMALL + SHAPES_5000, {"unordered_writes_on": ("masked",)}, None),
     ("(control) the unmodified tree, operands and shapes with events recorded on demand", None, [], SHAPES_EVR, {}, None),
 ]
