@@ -357,7 +357,7 @@ class KernelSpec:
             else:                        # a sub-combination needs its own matrix once
                 tmp = self._build(c, X1, X2, None)
                 out.add_(tmp) if op == "add" else out.mul_(tmp)
-        if diag_add != 0.0 and not isinstance(ch[last], int):
+        if X2 is None and diag_add != 0.0 and not isinstance(ch[last], int):    # (X2 given: ignored, as every leaf launch ignores it)
             out.diagonal().add_(float(diag_add))
         return out
 

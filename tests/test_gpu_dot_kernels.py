@@ -92,14 +92,14 @@ def _power(base, n):
     return p
 
 
-def _kref(family, degree, s, ds, what="k"):
+def _kref(family, degree, s, ds, what="k", offset=OFFSET):
     """(k or dk/ds in longdouble, bound) from s and its bound ds.  Linear: k = s, dk/ds = 1 exactly.  Polynomial: base = s + offset
     carries one more rounding, e = ds + u |base|; |base^n - (base + e')^n| <= (|base| + e)^n - |base|^n for |e'| <= e -- to first order
     the n |base|^(n-1) e of the derivation, the remainder being all there is where base is near 0 -- and the n - 1 products of the power
     add (n - 1) u |k|; dk/ds = degree base^(degree - 1): the same with n = degree - 1, and one more product for the factor `degree`."""
     if family == "Linear":
         return (s, ds) if what == "k" else (np.ones_like(s), np.zeros_like(s))
-    base = s + LD(OFFSET)
+    base = s + LD(offset)            # (offset=: the value a caller's Parameter holds, where that is not OFFSET to the bit)
     e = ds + U * np.abs(base)
     n = degree if what == "k" else degree - 1
     if n == 0:
