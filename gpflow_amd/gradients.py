@@ -154,7 +154,7 @@ def stationary_kernel_adjoint(leaf: Leaf, A: torch.Tensor, Bm: torch.Tensor, Kba
                               dvar_add: float = 0.0, return_packed: bool = False, moments=None):
     """Adjoint of K = variance * f(r(A / ls, Bm / ls)) [n1, n2] given Kbar [n1, n2], `leaf` of one of the stationary families
     (stationaries.py:209-210 SquaredExponential, :254-313 Matern12 / 32 / 52; Exponential; RationalQuadratic with its `alpha`; the
-    static families have no distance and never come here: KernelSpec._adjoint).
+    static families have no distance and never come here: StaticMember.adjoint).
 
     Returns (d/dvariance, shape gradient, A_bar [n1, D]); the shape gradient is laid out like the leaf's `ls_host` for every family:
     d/dlengthscales as the leaf holds them ([1] isotropic, else [D]), then one entry per extra.  With symmetric=True (Bm is A, Kbar
@@ -167,7 +167,7 @@ def stationary_kernel_adjoint(leaf: Leaf, A: torch.Tensor, Bm: torch.Tensor, Kba
     the family (the RationalQuadratic's alpha) adds d/dx = sum(Kbar .* dK/dx) (op "d" + x: "dalpha", into the same buffer).
 
     moments: a callable that builds the right-hand side Vt of the contraction R = G Vt^T in place of ops.moment_rows(Bm); its first
-    1 + 2 D rows must be those moment rows (an input-map kernel appends the rows its own tail needs: KernelSpec._adjoint), and R
+    1 + 2 D rows must be those moment rows (an input-map kernel appends the rows its own tail needs: PeriodicMember.adjoint), and R
     is handed back as a fourth result."""
     n1, D = A.shape
     variance, lengthscales = leaf.variance, leaf.lengthscales
@@ -225,35 +225,197 @@ def dot_kernel_adjoint(leaf: DotLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: t
     return dw, (doff if leaf.row.extras else doff[:0]), Abar
 
 
+class Member:
+    """One leaf of a KernelSpec as the tree walkers call it: its host values (`leaf`), the input columns it sees (`cols`: an index array,
+    or None for all), a Periodic leaf's `period`, and every answer that depends on the KIND of leaf.  This base class holds what the
+    kinds built by `gpk_kernel_matrix` share (stationary, static, periodic): the builders, and K(x, x) = variance as one host value.
+    `adjoint(A, Bm, Kbar, symmetric)` -> (d/dvariance [n_variance], shape gradient, A_bar over the member's columns, or None for no
+    input gradient) goes through the kind's `leaf_adjoint` function.  The four kinds follow; a further kind is one more class here."""
+    constant_diagonal, n_variance = True, 1
+    matrix, combine = "kernel_matrix", "kernel_matrix_combine"   # the kind's builders, by their names in `ops`
+
+    def __init__(self, leaf, cols=None, period=None):
+        self.leaf, self.cols, self.period, self._idx = leaf, cols, period, {}
+
+    def index(self, device) -> torch.Tensor:
+        """`cols` as a device tensor, made once per device"""
+        key = str(device)
+        if key not in self._idx:
+            self._idx[key] = torch.as_tensor(self.cols, device=device)
+        return self._idx[key]
+
+    def columns(self, X):
+        """the active columns as a contiguous copy (None stays None)"""
+        if X is None or self.cols is None:
+            return X
+        return X.index_select(1, self.index(X.device)).contiguous()
+
+    view = columns   # what the builders get
+
+    def build(self, X1, X2, out, diag_add: float = 0.0):
+        return getattr(ops, self.matrix)(self.view(X1), self.view(X2), diag_add=diag_add, lower_only=False, out=out, **self.leaf.keywords())
+
+    def fold(self, X1, X2, G, op: str, diag_add: float = 0.0):
+        """G <- G .* K(X1, X2) or G + K(X1, X2) in place (K recomputed in registers, no second matrix)"""
+        return getattr(ops, self.combine)(self.view(X1), self.view(X2), G, op=op, diag_add=diag_add, out=G, **self.leaf.keywords())
+
+    def kdiag(self) -> float:
+        return self.leaf.variance
+
+    def diag_adjoint(self, X, bar):
+        """(d/dvariance, shape gradient) of sum_b bar_b K(x_b, x_b): a constant diagonal collects the sum of what reaches it"""
+        return bar.sum().reshape(1), bar.new_zeros(self.n_shape())
+
+    def adjoint(self, A, Bm, Kbar, symmetric):
+        Ai = self.view(A)
+        Bi = Ai if (symmetric and Bm is A) else self.view(Bm)   # (the identity decides whether a second copy is launched)
+        dv, dl, Ab = self.leaf_adjoint(self.leaf, Ai, Bi, Kbar, symmetric=symmetric)
+        return dv.reshape(-1), dl, Ab
+
+    def warm(self, device, D: int) -> None:
+        """device copies of what the adjoint's tails read, made now (see `ls_device`); D: the width of the full inputs"""
+
+    def parameter_names(self) -> tuple:
+        return self.leaf.row.parameters
+
+    def n_shape(self) -> int:
+        return self.leaf.n_shape
+
+    def split_shape(self, g) -> dict:
+        return self.leaf.split_shape(g)
+
+
+class StationaryMember(Member):
+    """a leaf with a distance (leaf.FAMILIES, has_distance)"""
+    leaf_adjoint = staticmethod(stationary_kernel_adjoint)
+
+    def warm(self, device, D: int) -> None:
+        ls_device(self.leaf.lengthscales, D if self.cols is None else len(self.cols), device)
+
+
+class StaticMember(Member):
+    """White, Constant: no distance, so no lengthscale and no input gradient, and no contraction is launched"""
+
+    def adjoint(self, A, Bm, Kbar, symmetric):
+        # d/dvariance = sum(Kbar .* K) / variance read off directly: every entry (Constant), the diagonal of K(A, A) (White:
+        # NOT through the X2-given hadamard, which is zeros for it), nothing where White sees two sets of points
+        dv = Kbar.sum() if self.leaf.family == "Constant" else torch.diagonal(Kbar).sum() if symmetric else Kbar.new_zeros(())
+        dl = Kbar.new_zeros(0)
+        return dv.reshape(1), dl, None
+
+
+class DotMember(Member):
+    """a dot-product leaf (leaf.DotLeaf: Linear, Polynomial), built and folded by the `gpk_dot_*` entry points.  K(x, x) depends on the
+    row: `kdiag_rows` / `fold_kdiag`; the variance gradient has D entries when the variance is ARD, the shape gradient is [d/doffset] or
+    empty."""
+    constant_diagonal = False
+    matrix, combine = "dot_kernel_matrix", "dot_kernel_matrix_combine"
+    leaf_adjoint = staticmethod(dot_kernel_adjoint)
+    n_variance = property(lambda self: self.leaf.n_variance)
+
+    def kdiag(self) -> float:
+        raise NotImplementedError("K(x, x) of a dot-product member (Linear, Polynomial) depends on the row: this caller takes the "
+                                  "diagonal for one scalar and has not been converted to KernelSpec.kdiag_rows")
+
+    def kdiag_rows(self, X) -> torch.Tensor:
+        """K(x_b, x_b) as a fresh [rows] tensor"""
+        return ops.dot_kernel_diag(self.view(X), **self.leaf.keywords())
+
+    def fold_kdiag(self, X, acc, op: str) -> None:
+        """acc <- acc .* K(x_b, x_b) or acc + K(x_b, x_b) in place"""
+        ops.dot_kernel_diag(self.view(X), acc, op=op, out=acc, **self.leaf.keywords())
+
+    def diag_adjoint(self, X, bar):
+        """g = bar .* dkd/ds and, from ONE thin product of g with ops.moment_rows(X), d/dw_j = sum_b g_b x_bj^2 and d/doffset = sum_b g_b"""
+        leaf = self.leaf
+        Xi = self.view(X)
+        Xi = Xi if Xi.is_contiguous() else Xi.contiguous()
+        D = Xi.shape[1]
+        g = bar if leaf.family == "Linear" else ops.dot_kernel_diag(Xi, bar, op="ds", **leaf.keywords())
+        m = ops.gemm_nt(g.reshape(1, -1), ops.moment_rows(Xi))[0]      # [1 + 2 D]: sum g, sum g x_j, sum g x_j^2
+        dw = m[1 + D:]
+        return (dw if leaf.ard else dw.sum().reshape(1)), (m[0:1] if leaf.row.extras else m[:0])
+
+    def warm(self, device, D: int) -> None:
+        ls_device(self.leaf.variance, self.leaf.n_variance, device)   # (the weights of the dot-product tail)
+
+
+class PeriodicMember(StationaryMember):
+    """a Periodic leaf (kernels/periodic.py): a stationary member whose view of the inputs adds the warp Phi (ops.periodic_warp) after
+    the column selection.  `leaf` is in the DEVICE form -- the base family over the 2 D_i warped columns with lengthscales 2 l, an ARD
+    one repeated pairwise; `period` is 0-d or [D_i].  The gradients come back in the user's form: d/dl (one, or D_i), the extras, then
+    d/dperiod last in the shape gradient, and an input gradient over the D_i columns."""
+
+    def view(self, X):
+        X = self.columns(X)
+        return X if X is None else ops.periodic_warp(X if X.is_contiguous() else X.contiguous(), self.period)
+
+    def base_lengthscales(self):
+        """the lengthscales as the user holds them: the device form halved (exact), an ARD one un-paired"""
+        ls = self.leaf.lengthscales
+        return (ls if ls.ndim == 0 or ls.size == 1 else ls.reshape(-1)[0::2]) / 2.0
+
+    def adjoint(self, A, Bm, Kbar, symmetric):
+        """the stationary adjoint of the device-form leaf at the warped inputs -- with the extra moment rows of the period gradient
+        riding in its one contraction -- then ops.periodic_adjoint_tail"""
+        leaf, per = self.leaf, self.period
+        Ai = self.columns(A)
+        Bi = Ai if (symmetric and Bm is A) else self.columns(Bm)
+        same = Bi is Ai
+        Ai = Ai if Ai.is_contiguous() else Ai.contiguous()
+        Bi = Ai if same else (Bi if Bi.is_contiguous() else Bi.contiguous())
+        PA = ops.periodic_warp(Ai, per)
+        PB = PA if Bi is Ai else ops.periodic_warp(Bi, per)
+        dv, dl, Pbar, R = stationary_kernel_adjoint(leaf, PA, PB, Kbar, symmetric=symmetric,
+                                                    moments=lambda: ops.periodic_moment_rows(Bi, per))
+        nls = leaf.n_lengthscales   # entries of dl in front of the extras: d/dl = 2 d/d(2 l), the two columns of a pair added
+        g_ls = 2.0 * dl[:1] if nls == 1 else 2.0 * (dl[0:nls:2] + dl[1:nls:2])
+        dper, Ab = ops.periodic_adjoint_tail(Ai, PA, Pbar, R, ls_device(self.base_lengthscales(), Ai.shape[1], Ai.device), per)
+        dl = torch.cat([g_ls, dl[nls:], dper])
+        return dv.reshape(-1), dl, Ab
+
+    def warm(self, device, D: int) -> None:
+        Di = D if self.cols is None else len(self.cols)   # (the periodic tail at the base's width, the stationary tail at the warped one)
+        ls_device(self.base_lengthscales(), Di, device)
+        ls_device(self.leaf.lengthscales, 2 * Di, device)
+
+    def parameter_names(self) -> tuple:
+        return self.leaf.row.parameters + ("period",)
+
+    def n_shape(self) -> int:
+        return max(self.leaf.n_lengthscales // 2, 1) + len(self.leaf.extras) + int(self.period.size)
+
+    def split_shape(self, g) -> dict:
+        """the user's form: the lengthscale entries are what precedes the extras and the trailing period entries"""
+        nper, nex = int(self.period.size), len(self.leaf.extras)
+        nls = g.shape[0] - nper - nex
+        return {"lengthscales": g[:nls], **{name: g[nls + j:nls + j + 1] for j, name in enumerate(self.leaf.row.extras)}, "period": g[nls + nex:]}
+
+
 class KernelSpec:
-    """What the reverse pass needs to know about the covariance function: ONE stationary kernel, or a Sum / Product of
-    stationary / static kernels -- flat, or nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220 `Sum`, :305-315 `Product`; the reference
-    differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).  members: leaves (leaf.Leaf), given as such or as
-    tuples (family, variance, lengthscales[, alpha]); op: None | "add" | "mul" | tree.
+    """What the reverse pass needs to know about the covariance function: ONE kernel leaf, or a Sum / Product of leaves -- flat, or
+    nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220
+    `Sum`, :305-315 `Product`; the reference differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).
+    members: leaves (leaf.Leaf, leaf.DotLeaf), given as such or as tuples (family, variance, lengthscales[, alpha]); op: None | "add" |
+    "mul" | tree.
 
-    A member's SHAPE gradient -- the `dl` entry of `adjoint` -- is laid out like the leaf's `ls_host`: the lengthscale entries,
-    then the extras; a static member's is empty (no lengthscale, no input gradient: A_bar is zero and no contraction is launched
-    for it).  `kernel_grads` has the leaves split it into the "lengthscales" / "alpha" entries of a `grads` dict.
+    The constructor chooses ONE member object per leaf (`parts`: a StationaryMember, StaticMember, DotMember or PeriodicMember), the
+    only place where the kind of a leaf is asked.  Everything else here is about the TREE: `_build`, `_constant`, `_kd`, `_kd_rows`,
+    `_diag_adjoint`, `_dkd` and `_adjoint` are the only walkers, and at a leaf each is one call on the member object.
 
-    A member may also be a dot-product leaf (leaf.DotLeaf: Linear, Polynomial), built and folded by the `gpk_dot_*` entry points.  Its
-    K(x, x) depends on the row, so a spec with one has no `constant_diagonal`: `kdiag()` / `dkdiag()` raise, `kdiag_rows(X)` and
-    `diag_adjoint(X, kd_bar)` take their place; its variance gradient has D entries when the variance is ARD (`n_variance`), its shape
-    gradient is [d/doffset] or empty.
+    A member's SHAPE gradient -- the `dl` entry of `adjoint` -- is laid out like the leaf's `ls_host`: the lengthscale entries, then the
+    extras (a periodic member: then the period); a static member's is empty.  A spec with a dot-product member has no
+    `constant_diagonal`: `kdiag()` / `dkdiag()` raise, `kdiag_rows(X)` and `diag_adjoint(X, kd_bar)` take their place.
 
-      build    the combined matrix, members folded in place by `gpk_kernel_matrix_combine` (no second matrix);
-      kdiag    K(x, x): sum or product of the variances (stationary members), dkdiag[i] = d kdiag / d variance_i;
-      adjoint  member i sees  Kbar (Sum)  or  Kbar .* prod_{j != i} k_j  (Product: formed by the same in-place combine pass)
-               and goes through `stationary_kernel_adjoint`; the input gradients of the members add up."""
+      build    the combined matrix, members folded in place by the builders' combine pass (no second matrix);
+      kdiag    K(x, x): sum or product of the members' host values, dkdiag[i] = d kdiag / d variance_i;
+      adjoint  member i sees  Kbar (Sum)  or  Kbar .* prod_{j != i} k_j  (Product: formed by the same in-place combine pass);
+               the input gradients of the members are scattered back into the columns each read, and add up."""
 
     def __init__(self, members, op=None, cols=None, periods=None):
         """members: leaves or tuples, see the class; cols[i]: the input columns member i sees (its `active_dims` as an index
-        list, kernels/base.py:90-109) or None for all of them.  Members that see different columns are built and differentiated on
-        their own column slices; their input gradients are scattered back into the full columns and add up.
-
-        periods[i]: None, or the period (0-d or [D_i]) of a Periodic member (kernels/periodic.py).  Its inputs go through the warp
-        Phi (ops.periodic_warp) after the column selection, and its leaf is in the DEVICE form -- the base family over the 2 D_i
-        warped columns with lengthscales 2 l, an ARD one repeated pairwise.  Its gradients come back in the user's form: d/dl (one,
-        or D_i), the extras, then d/dperiod last in the shape gradient, and an input gradient over the D_i columns."""
+        list, kernels/base.py:90-109) or None for all of them; periods[i]: None, or the period (0-d or [D_i]) of a Periodic member,
+        whose leaf is then in the device form (PeriodicMember)."""
         self.members = [m if isinstance(m, (Leaf, DotLeaf)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
@@ -276,7 +438,9 @@ class KernelSpec:
         for leaf, p in zip(self.members, self.periods):
             if p is not None and (isinstance(leaf, DotLeaf) or leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
                 raise ValueError("a periodic member is a leaf with a distance over the warped columns, its period 0-d or [D]")
-        self._idx = {}
+        self.parts = [PeriodicMember(leaf, c, p) if p is not None else DotMember(leaf, c) if isinstance(leaf, DotLeaf)
+                      else StaticMember(leaf, c) if leaf.is_static else StationaryMember(leaf, c)
+                      for leaf, c, p in zip(self.members, self.cols, self.periods)]
 
     @staticmethod
     def single(variance, lengthscales, family="SquaredExponential", alpha=None):
@@ -308,52 +472,28 @@ class KernelSpec:
     def n(self) -> int:
         return len(self.members)
 
-    def _columns(self, i: int, X):
-        """the columns of member i's active_dims as a contiguous copy (None stays None)"""
-        if X is None or self.cols[i] is None:
-            return X
-        key = (i, str(X.device))
-        if key not in self._idx:
-            self._idx[key] = torch.as_tensor(self.cols[i], device=X.device)
-        return X.index_select(1, self._idx[key]).contiguous()
-
-    def _sl(self, i: int, X):
-        """member i's view of the inputs: its columns, then -- a periodic member -- the warp"""
-        X = self._columns(i, X)
-        if X is None or self.periods[i] is None:
-            return X
-        return ops.periodic_warp(X if X.is_contiguous() else X.contiguous(), self.periods[i])
-
     def is_dot(self, i: int) -> bool:
         """member i is a dot-product leaf (leaf.DotLeaf: Linear, Polynomial): its own builders, and a diagonal that depends on the row"""
         return isinstance(self.members[i], DotLeaf)
 
     def n_variance(self, i: int) -> int:
         """entries of member i's variance gradient: 1, or D for the ARD variance of a dot-product member"""
-        return self.members[i].n_variance if self.is_dot(i) else 1
-
-    def _fold(self, i: int, X1, X2, G, op: str, diag_add: float = 0.0):
-        """G <- G .* k_i(X1, X2) or G + k_i(X1, X2) in place (K recomputed in registers, no second matrix); X1, X2 as member i sees them"""
-        fold = ops.dot_kernel_matrix_combine if self.is_dot(i) else ops.kernel_matrix_combine
-        return fold(X1, X2, G, op=op, diag_add=diag_add, out=G, **self.members[i].keywords())
+        return self.parts[i].n_variance
 
     def build(self, X1, X2, out=None, diag_add: float = 0.0):
         return self._build(self.tree, X1, X2, out, diag_add)
 
     def _build(self, node, X1, X2, out, diag_add=0.0):
         if isinstance(node, int):
-            build = ops.dot_kernel_matrix if self.is_dot(node) else ops.kernel_matrix
-            return build(self._sl(node, X1), self._sl(node, X2), diag_add=diag_add, lower_only=False, out=out,
-                         **self.members[node].keywords())
+            return self.parts[node].build(X1, X2, out, diag_add)
         op, ch = node
         if len(ch) == 1:
             return self._build(ch[0], X1, X2, out, diag_add)
         last = len(ch) - 1
         out = self._build(ch[0], X1, X2, out)
         for j, c in enumerate(ch[1:], start=1):
-            if isinstance(c, int):      # a leaf folds in place (K recomputed in registers, no second matrix);
-                self._fold(c, self._sl(c, X1), self._sl(c, X2), out, op,                  # diag_add rides in the LAST member's launch
-                           diag_add=diag_add if j == last else 0.0)
+            if isinstance(c, int):      # a leaf folds in place; diag_add rides in the LAST member's launch
+                self.parts[c].fold(X1, X2, out, op, diag_add=diag_add if j == last else 0.0)
             else:                        # a sub-combination needs its own matrix once
                 tmp = self._build(c, X1, X2, None)
                 out.add_(tmp) if op == "add" else out.mul_(tmp)
@@ -362,8 +502,8 @@ class KernelSpec:
         return out
 
     def _constant(self, node) -> bool:
-        """no dot-product member under `node`: its diagonal is one host value"""
-        return not self.is_dot(node) if isinstance(node, int) else all(self._constant(c) for c in node[1])
+        """every member under `node` has a constant diagonal: the node's diagonal is one host value"""
+        return self.parts[node].constant_diagonal if isinstance(node, int) else all(self._constant(c) for c in node[1])
 
     @property
     def constant_diagonal(self) -> bool:
@@ -373,10 +513,7 @@ class KernelSpec:
 
     def _kd(self, node) -> float:
         if isinstance(node, int):
-            if self.is_dot(node):
-                raise NotImplementedError("K(x, x) of a dot-product member (Linear, Polynomial) depends on the row: this caller takes the "
-                                          "diagonal for one scalar and has not been converted to KernelSpec.kdiag_rows")
-            return self.members[node].variance
+            return self.parts[node].kdiag()
         vals = [self._kd(c) for c in node[1]]
         return float(np.prod(vals)) if node[0] == "mul" else float(np.sum(vals))
 
@@ -388,13 +525,13 @@ class KernelSpec:
         if self._constant(node):
             return self._kd(node)
         if isinstance(node, int):
-            return ops.dot_kernel_diag(self._sl(node, X), **self.members[node].keywords())
+            return self.parts[node].kdiag_rows(X)
         op, ch = node
         rows = [c for c in ch if not self._constant(c)]
         acc = self._kd_rows(rows[0], X)
         for c in rows[1:]:
             if isinstance(c, int):      # a leaf folds in place, as in `_build`
-                ops.dot_kernel_diag(self._sl(c, X), acc, op=op, out=acc, **self.members[c].keywords())
+                self.parts[c].fold_kdiag(X, acc, op)
             else:
                 sub = self._kd_rows(c, X)
                 acc.add_(sub) if op == "add" else acc.mul_(sub)
@@ -411,27 +548,14 @@ class KernelSpec:
 
     def diag_adjoint(self, X, kd_bar):
         """([d/dvariance_i], [shape gradient_i]) of sum_b kd_bar_b K(x_b, x_b), members in index order, laid out as `adjoint` lays
-        them out.  A member with a constant diagonal collects sum_b of what reaches it; a dot-product member g = (what reaches it)
-        .* dkd/ds and, from ONE thin product of g with ops.moment_rows(X), d/dw_j = sum_b g_b x_bj^2 and d/doffset = sum_b g_b.  For a
-        Product the other children's diagonals enter as in `_adjoint`."""
+        them out (Member.diag_adjoint, DotMember.diag_adjoint).  For a Product the other children's diagonals enter as in `_adjoint`."""
         acc = {"dv": [None] * self.n, "dl": [None] * self.n}
         self._diag_adjoint(self.tree, X, kd_bar if kd_bar.is_contiguous() else kd_bar.contiguous(), acc)
         return acc["dv"], acc["dl"]
 
     def _diag_adjoint(self, node, X, bar, acc):
         if isinstance(node, int):
-            leaf = self.members[node]
-            if not self.is_dot(node):
-                acc["dv"][node], acc["dl"][node] = bar.sum().reshape(1), bar.new_zeros(self.n_shape(node))
-                return
-            Xi = self._sl(node, X)
-            Xi = Xi if Xi.is_contiguous() else Xi.contiguous()
-            D = Xi.shape[1]
-            g = bar if leaf.family == "Linear" else ops.dot_kernel_diag(Xi, bar, op="ds", **leaf.keywords())
-            m = ops.gemm_nt(g.reshape(1, -1), ops.moment_rows(Xi))[0]      # [1 + 2 D]: sum g, sum g x_j, sum g x_j^2
-            dw = m[1 + D:]
-            acc["dv"][node] = dw if leaf.ard else dw.sum().reshape(1)
-            acc["dl"][node] = m[0:1] if leaf.row.extras else m[:0]
+            acc["dv"][node], acc["dl"][node] = self.parts[node].diag_adjoint(X, bar)
             return
         op, ch = node
         for jc, c in enumerate(ch):
@@ -461,38 +585,9 @@ class KernelSpec:
 
     def warm(self, device, D: int) -> "KernelSpec":
         """device copies of the members' lengthscales, made now (see `ls_device`)"""
-        for i, leaf in enumerate(self.members):
-            if self.is_dot(i):              # (the weights of the dot-product tail)
-                ls_device(leaf.variance, leaf.n_variance, device)
-            elif not leaf.is_static:
-                Di = D if self.cols[i] is None else len(self.cols[i])
-                if self.periods[i] is not None:   # (the stationary tail at the warped width, the periodic tail at the base's)
-                    ls_device(self._base_lengthscales(i), Di, device)
-                    Di *= 2
-                ls_device(leaf.lengthscales, Di, device)
+        for m in self.parts:
+            m.warm(device, D)
         return self
-
-    def _base_lengthscales(self, i: int):
-        """a periodic member's lengthscales as its user holds them: the device form halved (exact), an ARD one un-paired"""
-        ls = self.members[i].lengthscales
-        return (ls if ls.ndim == 0 or ls.size == 1 else ls.reshape(-1)[0::2]) / 2.0
-
-    def _periodic_adjoint(self, i: int, Ai, Bi, Kbar, symmetric):
-        """A periodic member's adjoint from its column-selected inputs: the stationary adjoint of the device-form leaf at the warped
-        inputs -- with the extra moment rows of the period gradient riding in its one contraction -- then ops.periodic_adjoint_tail.
-        (d/dvariance, [d/dl as the user holds them, extras, d/dperiod], A_bar [n1, D_i])."""
-        leaf, per = self.members[i], self.periods[i]
-        same = Bi is Ai
-        Ai = Ai if Ai.is_contiguous() else Ai.contiguous()
-        Bi = Ai if same else (Bi if Bi.is_contiguous() else Bi.contiguous())
-        PA = ops.periodic_warp(Ai, per)
-        PB = PA if Bi is Ai else ops.periodic_warp(Bi, per)
-        dv, dl, Pbar, R = stationary_kernel_adjoint(leaf, PA, PB, Kbar, symmetric=symmetric,
-                                                    moments=lambda: ops.periodic_moment_rows(Bi, per))
-        nls = leaf.n_lengthscales   # entries of dl in front of the extras: d/dl = 2 d/d(2 l), the two columns of a pair added
-        g_ls = 2.0 * dl[:1] if nls == 1 else 2.0 * (dl[0:nls:2] + dl[1:nls:2])
-        dper, Ab = ops.periodic_adjoint_tail(Ai, PA, Pbar, R, ls_device(self._base_lengthscales(i), Ai.shape[1], Ai.device), per)
-        return dv, torch.cat([g_ls, dl[nls:], dper]), Ab
 
     def adjoint(self, A, Bm, Kbar, symmetric: bool):
         """([d/dvariance_i [1]], [shape gradient_i: d/dlengthscales_i, then d/dalpha_i], A_bar [n1, D]) given Kbar, members in index
@@ -503,33 +598,19 @@ class KernelSpec:
 
     def _adjoint(self, node, A, Bm, Kbar, symmetric, acc):
         if isinstance(node, int):
-            leaf = self.members[node]
-            if leaf.is_static:
-                # d/dvariance = sum(Kbar .* K) / variance read off directly: every entry (Constant), the diagonal of K(A, A) (White:
-                # NOT through the X2-given hadamard, which is zeros for it), nothing where White sees two sets of points
-                dv = Kbar.sum() if leaf.family == "Constant" else torch.diagonal(Kbar).sum() if symmetric else Kbar.new_zeros(())
-                acc["dl"][node], acc["dv"][node] = Kbar.new_zeros(0), dv.reshape(1)
+            m = self.parts[node]
+            acc["dv"][node], acc["dl"][node], Ab = m.adjoint(A, Bm, Kbar, symmetric)   # (dv [1]; an ARD dot-product member: [D])
+            if Ab is None:          # no input gradient
                 return
-            if self.is_dot(node):
-                Ai = self._sl(node, A)
-                dv, dl, Ab = dot_kernel_adjoint(leaf, Ai, Ai if (symmetric and Bm is A) else self._sl(node, Bm), Kbar, symmetric=symmetric)
-            elif self.periods[node] is not None:
-                Ai = self._columns(node, A)
-                dv, dl, Ab = self._periodic_adjoint(node, Ai, Ai if (symmetric and Bm is A) else self._columns(node, Bm), Kbar, symmetric)
-            else:
-                Ai = self._sl(node, A)
-                Bi = Ai if (symmetric and Bm is A) else self._sl(node, Bm)
-                dv, dl, Ab = stationary_kernel_adjoint(leaf, Ai, Bi, Kbar, symmetric=symmetric)
-            acc["dl"][node], acc["dv"][node] = dl, dv.reshape(-1)   # ([1]; an ARD dot-product member: [D])
             if all(c is None for c in self.cols):
                 acc["Abar"] = Ab if acc["Abar"] is None else acc["Abar"] + Ab
             else:   # scatter the member's input gradient back into the columns it read
                 if acc["Abar"] is None:
                     acc["Abar"] = torch.zeros_like(A)
-                if self.cols[node] is None:
+                if m.cols is None:
                     acc["Abar"] += Ab
                 else:
-                    acc["Abar"].index_add_(1, self._idx[(node, str(A.device))], Ab)
+                    acc["Abar"].index_add_(1, m.index(A.device), Ab)
             return
         op, ch = node
         for jc, c in enumerate(ch):
@@ -540,7 +621,7 @@ class KernelSpec:
                     if jo == jc:
                         continue
                     if isinstance(o, int):
-                        self._fold(o, self._sl(o, A), None if symmetric else self._sl(o, Bm), Kb, "mul")
+                        self.parts[o].fold(A, None if symmetric else Bm, Kb, "mul")
                     else:
                         Kb.mul_(self._build(o, A, None if symmetric else Bm, None))
             self._adjoint(c, A, Bm, Kb, symmetric, acc)
@@ -554,24 +635,15 @@ class KernelSpec:
 
     def parameter_names(self, i: int) -> tuple:
         """names of member i's hyperparameters in the order of its gradients: the leaf's, then a periodic member's "period" """
-        return self.members[i].row.parameters + (("period",) if self.periods[i] is not None else ())
+        return self.parts[i].parameter_names()
 
     def n_shape(self, i: int) -> int:
         """entries of member i's shape gradient: Leaf.n_shape, and for a periodic member the user's lengthscales, the extras, the period"""
-        leaf = self.members[i]
-        if self.periods[i] is None:
-            return leaf.n_shape
-        return max(leaf.n_lengthscales // 2, 1) + len(leaf.extras) + int(self.periods[i].size)
+        return self.parts[i].n_shape()
 
     def split_shape(self, i: int, g) -> dict:
-        """member i's shape gradient as {"lengthscales": ..., <extra>: [1], ..., "period": ...}: Leaf.split_shape, and for a periodic
-        member the user's form -- its lengthscale entries are what precedes the extras and the trailing period entries"""
-        leaf = self.members[i]
-        if self.periods[i] is None:
-            return leaf.split_shape(g)
-        nper, nex = int(self.periods[i].size), len(leaf.extras)
-        nls = g.shape[0] - nper - nex
-        return {"lengthscales": g[:nls], **{name: g[nls + j:nls + j + 1] for j, name in enumerate(leaf.row.extras)}, "period": g[nls + nex:]}
+        """member i's shape gradient as {"lengthscales": ..., <extra>: [1], ..., "period": ...}"""
+        return self.parts[i].split_shape(g)
 
     def kernel_grads(self, g_var, g_shape) -> dict:
         """the kernel's entries of a `grads` dict from what `pack` returned: "variance", "lengthscales" (a static member's is empty)
@@ -579,8 +651,8 @@ class KernelSpec:
         without"""
         if self.n == 1:
             return {"variance": g_var, **self.split_shape(0, g_shape)}
-        parts = [self.split_shape(i, g) for i, g in enumerate(g_shape)]
-        return {"variance": g_var, **{name: [p.get(name) for p in parts] for name in dict.fromkeys(k for p in parts for k in p)}}
+        split = [self.split_shape(i, g) for i, g in enumerate(g_shape)]
+        return {"variance": g_var, **{name: [p.get(name) for p in split] for name in dict.fromkeys(k for p in split for k in p)}}
 
 
 class _Seed:

@@ -113,9 +113,14 @@ class DeviceLeaf(Kernel):
     def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
         return ops.kernel_matrix(X, X2, diag_add=diag_add, lower_only=lower_only, out=out, **self.leaf().keywords())
 
+    def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
+        """out <- out .* K or out + K in place (K recomputed in registers: one read + one write of `out`, no second matrix); the
+        dot-product kernels answer it too (kernels/linears.py), and Combination.K_into asks nothing else of a member"""
+        return ops.kernel_matrix_combine(X, X2, out, op=op, diag_add=diag_add, out=out, **self.leaf().keywords())
+
 
 def is_device_leaf(k) -> bool:
-    """True for a DeviceLeaf of a known family.  The one notion Combination.K_into, gradient_spec and the model routes share."""
+    """True for a DeviceLeaf of a known family.  The one notion reverse_leaf and the model routes share."""
     return bool(getattr(k, "device_leaf", False)) and getattr(k, "family", None) in ops.KERNEL_FAMILIES
 
 
@@ -153,9 +158,8 @@ class Combination(Kernel):
         return True
 
     def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
-        """The first member is built into `out`; every further device-built member (stationary or static) is folded in by
-        gpk_kernel_matrix_combine (K recomputed in registers: one read + one write of `out`, no second matrix), a dot-product member
-        (Linear, Polynomial) by gpk_dot_kernel_matrix_combine in the same way."""
+        """The first member is built into `out`; every further member that can (`K_fold`: the device-built and the dot-product
+        leaves) folds itself in place, any other is built into a matrix of its own once."""
         X = ops.to_device(X)
         X2 = ops.to_device(X2) if X2 is not None else None
         ks = list(self.kernels)
@@ -166,10 +170,8 @@ class Combination(Kernel):
         for i, k in enumerate(ks[1:], start=1):
             Xs, X2s = k.slice(X, X2)
             dadd = diag_add if i == last else 0.0
-            if is_device_leaf(k):
-                ops.kernel_matrix_combine(Xs, X2s, out, op=self._op, diag_add=dadd, out=out, **k.leaf().keywords())
-            elif is_dot_leaf(k):
-                ops.dot_kernel_matrix_combine(Xs, X2s, out, op=self._op, diag_add=dadd, out=out, **k.leaf().keywords())
+            if hasattr(k, "K_fold"):
+                k.K_fold(Xs, X2s, out, self._op, diag_add=dadd)
             else:
                 Ki = k.K_into(Xs, X2s, None)
                 out.add_(Ki) if self._op == "add" else out.mul_(Ki)
@@ -199,6 +201,24 @@ class Combination(Kernel):
         return self.K_diag(X) if not full_cov else self.K(X, X2)
 
 
+def reverse_leaf(k, input_dim=None):
+    """(leaf, period or None, leaf_params) of a kernel that is ONE leaf the reverse pass covers, else None: an isotropic-stationary or a
+    static kernel that the device builds, a Periodic one over such a base (`leaf` in the device form, the warp left to the spec: its
+    `periods`), or a dot-product one.  A Periodic kernel's width is checked here, before anything touches the device, wherever its
+    active columns can be counted: an index list, or a slice of `input_dim` columns."""
+    from .periodic import Periodic
+    from .stationaries import IsotropicStationary
+    from .statics import Static
+    periodic = isinstance(k, Periodic)
+    if not (((periodic or isinstance(k, (IsotropicStationary, Static))) and is_device_leaf(k)) or is_dot_leaf(k)):
+        return None
+    if periodic and not isinstance(k.active_dims, slice):
+        k.check_width(len(k.active_dims))
+    elif periodic and input_dim is not None:
+        k.check_width(len(np.arange(int(input_dim))[k.active_dims]))
+    return k.leaf(), (k.period.numpy() if periodic else None), k.leaf_params()
+
+
 def gradient_spec(kernel, input_dim=None):
     """gradients.KernelSpec + [(variance Parameter, lengthscales Parameter)] for the kernels the reverse pass covers beyond a
     single stationary one: a Sum / Product of isotropic-stationary members, flat or nested (kernels/base.py:216-220, 305-315; the
@@ -206,19 +226,17 @@ def gradient_spec(kernel, input_dim=None):
     carry their own `active_dims` (kernels/base.py:90-109): the spec then builds and differentiates each member on its own columns
     and scatters its input gradient back (round 5) -- `input_dim`, the number of input columns, resolves slices.  None if `kernel`
     is not such a combination."""
-    from .periodic import Periodic
-    from .stationaries import IsotropicStationary
-    from .statics import Static
     from .. import gradients
     if not isinstance(kernel, Combination):
         return None
-    # leaves in traversal order + the tree over their indices (a flat combination: one node)
-    ks = []
+    # leaves in traversal order (with what reverse_leaf says of each) + the tree over their indices (a flat combination: one node)
+    ks, found = [], []
 
     def walk(k):
         if isinstance(k, Combination):
             return (k._op, [walk(c) for c in k.kernels])
-        if not ((isinstance(k, (IsotropicStationary, Static, Periodic)) and is_device_leaf(k)) or is_dot_leaf(k)):
+        found.append(reverse_leaf(k, input_dim))
+        if found[-1] is None:      # (not one of its leaves)
             raise NotImplementedError("gradients of a kernel combination: Sums / Products (possibly nested) of isotropic-stationary, "
                                       "Periodic, static and dot-product (Linear, Polynomial) members (kernels/base.py:216-220, 305-315)")
         ks.append(k)
@@ -234,12 +252,8 @@ def gradient_spec(kernel, input_dim=None):
             cols.append(np.arange(int(input_dim))[k.active_dims])
         else:
             cols.append(np.asarray(k.active_dims, dtype=np.int64))
-    # (a Periodic member: the columns are its base's, the warp is the spec's -- `periods`)
-    for k, c in zip(ks, cols):
-        if isinstance(k, Periodic) and (c is not None or input_dim is not None):
-            k.check_width(len(c) if c is not None else int(input_dim))
-    periods = [k.period.numpy() if isinstance(k, Periodic) else None for k in ks]
-    return gradients.KernelSpec([k.leaf() for k in ks], tree, cols=cols, periods=periods), [k.leaf_params() for k in ks]
+    leaves, periods, params = zip(*found)     # (a Periodic member: the columns are its base's, the warp is the spec's -- `periods`)
+    return gradients.KernelSpec(leaves, tree, cols=cols, periods=periods), list(params)
 
 
 class Sum(Combination):

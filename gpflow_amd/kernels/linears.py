@@ -51,6 +51,10 @@ class Linear(Kernel):
         self.check_width(X.shape[-1])
         return ops.dot_kernel_matrix(X, X2, diag_add=diag_add, lower_only=lower_only, out=out, **self.leaf().keywords())
 
+    def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
+        """out <- out .* K or out + K in place, as DeviceLeaf.K_fold"""
+        return ops.dot_kernel_matrix_combine(X, X2, out, op=op, diag_add=diag_add, out=out, **self.leaf().keywords())
+
     def K(self, X, X2=None) -> torch.Tensor:
         """leading batch dimensions as IsotropicStationary.K: flattened to rows and restored"""
         X = ops.to_device(X)

@@ -136,7 +136,6 @@ class DotLeaf(collections.namedtuple("_DotLeafFields", "row variance offset degr
     [1, DOT_MAX_DEGREE], a constant of the leaf without a gradient.  Its diagonal K(x, x) depends on the row: it is no row of FAMILIES,
     gpk_kernel_matrix and the fused drivers do not take it -- the gpk_dot_* entry points do (ops.dot_kernel_matrix, ...)."""
     __slots__ = ()
-    is_static = False
     is_plain = False
 
     def __new__(cls, family: str, variance, offset=None, degree=None):

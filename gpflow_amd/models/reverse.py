@@ -10,10 +10,8 @@ from .. import gradients
 from ..base import FillTriangular
 from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
-from ..kernels.base import Combination, gradient_spec, is_device_leaf, is_dot_leaf
+from ..kernels.base import Combination, gradient_spec, is_dot_leaf, reverse_leaf
 from ..kernels.periodic import Periodic
-from ..kernels.statics import Static
-from ..kernels.stationaries import IsotropicStationary
 from ..likelihoods import Gaussian
 from ..mean_functions import Constant
 
@@ -48,9 +46,9 @@ def minibatch_scale(num_data, rows) -> float:
 
 
 def _supported_stationary(k) -> bool:
-    """a leaf of the reverse pass: an isotropic-stationary kernel (SquaredExponential, Matern, Exponential, RationalQuadratic) or a
-    static one (White, Constant) that the device builds, or a Periodic kernel over a stationary base"""
-    return isinstance(k, (IsotropicStationary, Static, Periodic)) and is_device_leaf(k)
+    """a leaf of the reverse pass (kernels.base.reverse_leaf) with a constant diagonal: an isotropic-stationary kernel, a static one, or
+    a Periodic kernel over a stationary base"""
+    return reverse_leaf(k) is not None and not is_dot_leaf(k)
 
 
 ROW_DIAGONAL = "a dot-product kernel or member (Linear, Polynomial), whose K(x, x) depends on the row,"
@@ -80,17 +78,13 @@ class CovarianceRoute:
         self.is_combination = isinstance(kernel, Combination)
         if self.is_combination:
             self.spec, self.members = gradient_spec(kernel, input_dim)
-        elif _supported_stationary(kernel):
-            period = kernel.period.numpy() if isinstance(kernel, Periodic) else None
-            if period is not None and (input_dim is not None or not isinstance(kernel.active_dims, slice)):   # before the device
-                kernel.check_width(len(np.arange(int(input_dim))[kernel.active_dims]) if isinstance(kernel.active_dims, slice)
-                                   else len(kernel.active_dims))
-            self.spec, self.members = gradients.KernelSpec([kernel.leaf()], periods=[period]), [kernel.leaf_params()]
-        elif is_dot_leaf(kernel):
-            self.spec, self.members = gradients.KernelSpec([kernel.leaf()]), [kernel.leaf_params()]
-        else:
+            return
+        found = reverse_leaf(kernel, input_dim)
+        if found is None:
             raise NotImplementedError("gradients: a SquaredExponential / Matern / Exponential / RationalQuadratic / White / Constant / "
                                       "Periodic / Linear / Polynomial kernel, or a Sum / Product (possibly nested) of them")
+        leaf, period, params = found
+        self.spec, self.members = gradients.KernelSpec([leaf], periods=[period]), [params]
 
     def inputs(self, Z, X):
         """(Z, X, scatter) as passed to `gradients.*`; Z None (GPR): X alone is sliced"""

@@ -64,11 +64,11 @@ def test_spec_bookkeeping_for_a_periodic_member():
     spec = gradients.KernelSpec([Leaf("SquaredExponential", 1.0, 2.0)], periods=[1.5])
     assert not spec.packable and gradients.KernelSpec([Leaf("SquaredExponential", 1.0, 2.0)]).packable
     assert spec.parameter_names(0) == ("variance", "lengthscales", "period") and spec.n_shape(0) == 2
-    assert float(spec._base_lengthscales(0)) == 1.0
+    assert float(spec.parts[0].base_lengthscales()) == 1.0
     ard = gradients.KernelSpec([Leaf("RationalQuadratic", 1.0, [2.0, 2.0, 3.0, 3.0], alpha=0.5), Leaf("White", 0.1)], "add",
                                periods=[[1.0, 2.0], None])
     assert ard.parameter_names(0) == ("variance", "lengthscales", "alpha", "period") and ard.parameter_names(1) == ("variance",)
-    assert ard.n_shape(0) == 5 and ard.n_shape(1) == 0 and list(ard._base_lengthscales(0)) == [1.0, 1.5]
+    assert ard.n_shape(0) == 5 and ard.n_shape(1) == 0 and list(ard.parts[0].base_lengthscales()) == [1.0, 1.5]
     g = np.arange(5.0)
     parts = ard.split_shape(0, g)
     assert list(parts) == ["lengthscales", "alpha", "period"] and list(parts["lengthscales"]) == [0.0, 1.0] \

@@ -6,21 +6,24 @@
                                                                 SGPR.objective_and_grad, SVGPTrainer and NaturalGradient issue and return
     python tools/reverse_pass_log.py compare <a.pkl> <b.pkl>    compare two dumps case by case
 
-`gradients.ops` is tests/fake_ops.py + tests/fake_likelihood_ops.py + tests/fake_kernel_ops.py (of the SAME tree, the last one winning,
-as in the `gp` fixture of tests/test_kernel_families_emulated.py) behind a logging proxy: one line per outermost
+`gradients.ops` is tests/fake_ops.py + fake_likelihood_ops.py + fake_kernel_ops.py + fake_periodic_ops.py + fake_lcm_ops.py +
+fake_dot_ops.py (of the SAME tree, the last one winning: `FAKES` of tests/test_kernel_trees_emulated.py) behind a logging proxy: one line per outermost
 `ops.*` call (name, shape and strides of every tensor argument, every scalar argument); a TorchDispatchMode adds one line per aten op
 issued OUTSIDE an `ops.*` call (the torch glue).  Each case runs twice and the second run is kept (`ls_device` caches).  Kept per
-case: the log and the bytes of F, every gradient and info.  Written for the refactor recorded in profiles/reverse_pass_refactor.txt.
+case: the log and the bytes of F, every gradient and info; a refusal is kept as its exception type and message (a spec without a
+constant diagonal under a quadrature likelihood or in sgpr_elbo_and_grad).  Written for the refactor recorded in
+profiles/reverse_pass_refactor.txt.
 
 `dump-models` patches every `gpflow_amd.ops` name the fakes define -- fake_ops, fake_likelihood_ops, fake_multiclass_ops, then
-fake_kernel_ops and fake_lcm_ops last (the order of the `gp` fixtures of tests/test_multiclass_emulated.py,
-tests/test_kernel_families_emulated.py and tests/test_lcm_emulated.py) -- behind the same logging wrapper -- or, with `device`, patches nothing and logs nothing: the same matrix on the real library.  Kept per
+fake_kernel_ops, fake_periodic_ops, fake_lcm_ops and fake_dot_ops last (the order of the `gp` fixture of
+tests/test_multiclass_emulated.py, then of `FAKES` of tests/test_kernel_trees_emulated.py) -- behind the same logging wrapper -- or, with `device`, patches nothing and logs nothing: the same matrix on the real library.  Kept per
 case: the `ops.*` log, the returned value, every gradient under a key that carries its position in the returned dict and the
 position of its Parameter in `model.parameters`; for the trainer F, every `u` / `dev` entry after two steps and the names of `host` in
-order (in the key); for a fused forward call (kind "value") the returned value alone.  A refusal is kept as its exception type.  The model functions run twice on one model: `<case>` is the second run
+order (in the key); for a fused forward call (kind "value") the returned value alone.  A refusal is kept as its exception type and message.  The model functions run twice on one model: `<case>` is the second run
 (Parameter.device_value caches warm), `<case>#cold` the first.  Written for the refactor recorded in profiles/model_layer_refactor.txt;
 the RationalQuadratic / Exponential / White / Constant leaves and the LinearCoregionalization models were added for the one recorded
-in profiles/kernel_leaf_refactor.txt.
+in profiles/kernel_leaf_refactor.txt; the Periodic and dot-product (Linear, Polynomial) leaves and their trees for the one recorded in
+profiles/kernel_members_refactor.txt.
 """
 import itertools
 import pickle
@@ -63,14 +66,17 @@ def load(tree):
     sys.path[:0] = [tree, tree + "/tests"]
     import torch
     from torch.utils._python_dispatch import TorchDispatchMode
+    import fake_dot_ops
     import fake_kernel_ops
+    import fake_lcm_ops
     import fake_likelihood_ops
     import fake_ops
+    import fake_periodic_ops
     from gpflow_amd import gradients
     log, depth, wrap = _logger()
 
     proxy = types.SimpleNamespace()
-    for mod in (fake_ops, fake_likelihood_ops, fake_kernel_ops):
+    for mod in (fake_ops, fake_likelihood_ops, fake_kernel_ops, fake_periodic_ops, fake_lcm_ops, fake_dot_ops):
         for name in dir(mod):
             v = getattr(mod, name)
             if name.startswith("_") or isinstance(v, types.ModuleType):
@@ -88,7 +94,14 @@ def load(tree):
 
 
 def kernels(g, D=3):
+    from gpflow_amd.leaf import DotLeaf, Leaf
     ard = np.sqrt(D) * (0.8 + 0.05 * np.arange(D))
+    lin, lin_ard = DotLeaf("Linear", 0.8), DotLeaf("Linear", [0.5, 2.0, 1.25])
+    poly2, poly1 = DotLeaf("Polynomial", 0.7, offset=0.3, degree=2), DotLeaf("Polynomial", [0.4, 0.9, 0.6], offset=0.5, degree=1)
+    # a periodic member's leaf is in the device form: lengthscales 2 l over the warped columns, an ARD one repeated pairwise
+    per_se = Leaf("SquaredExponential", 1.3, 2 * 0.9)
+    per_se_ard = Leaf("SquaredExponential", 1.3, [1.2, 1.2, 1.8, 1.8, 2.6, 2.6])
+    per_rq = Leaf("RationalQuadratic", 0.9, [1.0, 1.0, 4.0, 4.0], alpha=0.7)
     se, m32, m52 = ("SquaredExponential", 1.3, ard), ("Matern32", 0.7, np.array(1.3)), ("Matern52", 0.9, np.array(0.8))
     return {
         "se_ard": lambda: dict(variance=1.3, lengthscales=ard),
@@ -105,6 +118,19 @@ def kernels(g, D=3):
         "prod_static": lambda: dict(kernel_spec=g.KernelSpec([se, ("Constant", 2.0, 1.0)], "mul")),
         "nested_rq_cols": lambda: dict(kernel_spec=g.KernelSpec([se, ("RationalQuadratic", 0.6, np.array(1.2), 1.3), m52],
                                                                 ("mul", [("add", [0, 1]), 2]), [None, [0, 2], None])),
+        # dot-product leaves (a diagonal that depends on the row), periodic members (warped inputs, a period gradient), and their trees
+        "lin_iso": lambda: dict(kernel_spec=g.KernelSpec([lin])),
+        "lin_ard": lambda: dict(kernel_spec=g.KernelSpec([lin_ard])),
+        "poly2": lambda: dict(kernel_spec=g.KernelSpec([poly2])),
+        "poly1_ard": lambda: dict(kernel_spec=g.KernelSpec([poly1])),
+        "per_se": lambda: dict(kernel_spec=g.KernelSpec([per_se], periods=[1.5])),
+        "per_rq_cols": lambda: dict(kernel_spec=g.KernelSpec([per_rq], cols=[[0, 2]], periods=[[1.5, 3.0]])),
+        "sum_lin_se": lambda: dict(kernel_spec=g.KernelSpec([lin_ard, se], "add")),
+        "prod_m32_poly": lambda: dict(kernel_spec=g.KernelSpec([m32, poly2], "mul")),
+        "three_level": lambda: dict(kernel_spec=g.KernelSpec(
+            [lin_ard, per_se_ard, poly2, Leaf("White", 0.3), Leaf("RationalQuadratic", 0.6, 0.5, alpha=0.7)],
+            ("add", [("mul", [("add", [0, 1]), ("add", [2, 3])]), 4]), [None, None, None, None, [0, 2]],
+            [None, [2.5, 3.0, 3.5], None, None, None])),
     }
 
 
@@ -131,8 +157,8 @@ def cases(torch, g):
     liks = {"bernoulli_probit": (), "poisson_exp": (1.5,), "student_t": (0.7, 4.0)}
     kn = kernels(g)
     for qf, lik, (kname, kmk), P in itertools.product(("full", "diag"), ("scalar", "rows", *liks), kn.items(), (1, 2)):
-        if lik in liks and kname not in ("se_ard", "m32_iso", "rq_iso"):
-            continue   # (refused by SVGP.elbo_and_grad: a quadrature likelihood needs one stationary kernel)
+        if lik in liks and kname not in ("se_ard", "m32_iso", "rq_iso", "lin_ard", "per_se", "sum_lin_se"):
+            continue   # (refused by SVGP.elbo_and_grad: a quadrature likelihood needs one stationary kernel; here a row diagonal is refused)
         X, Y, Z, q_mu, q_full, q_diag, rows = data(64, 200, 3, P, lik)
         kw = dict(jitter=1e-6, scale=5.0, mean_const=0.1, kl_weight=0.5)
         kw["noise_variance"] = t(rows) if lik == "rows" else 0.2
@@ -162,10 +188,14 @@ def dump(tree, path):
     for chunks, min_n in ((1, 1024), (4, 64)):
         g.TRI_PRODUCT_CHUNKS, g.TRI_PRODUCT_MIN_N = chunks, min_n
         for name, fn, args, kw, kmk in cases(torch, g):
-            for _ in range(2):
-                del log[:]
-                with Glue():
-                    F, grads, info = getattr(g, fn)(*args, **kw, **kmk())
+            try:
+                for _ in range(2):
+                    del log[:]
+                    with Glue():
+                        F, grads, info = getattr(g, fn)(*args, **kw, **kmk())
+            except (NotImplementedError, ValueError) as e:
+                res[f"chunks{chunks}/{name}"] = (list(log), {f"refused:{type(e).__name__}:{e}": ((), b"")})
+                continue
             vals = {"F": F, "info": info}
             for k, v in grads.items():
                 for i, vi in enumerate(v if isinstance(v, list) else [v]):   # (None: a member without that entry, kept as an empty one)
@@ -177,6 +207,8 @@ def dump(tree, path):
     print(len(res), "cases; benchmark form (M = 64, P = 2):", n_ops, "ops.* calls,",
           len(res["chunks1/white/full/scalar/se_ard/P2"][0]) - n_ops, "aten ops")
     print([e[0][4:] for e in res["chunks1/white/full/scalar/se_ard/P2"][0] if e[0].startswith("ops.")])
+    refused = [n for n, (_, v) in res.items() if any(k.startswith("refused:") for k in v)]
+    print(len(refused), "refusals:", sorted({next(iter(res[n][1])) for n in refused}))
 
 
 def model_cases(gp):
@@ -368,6 +400,45 @@ def model_cases(gp):
     out.append(("lcm/elbo_and_grad_rq_white", "grad", elbo_case(lambda: lcm([se(), rq(), K.White(0.3)], separate_z=True), Y2)))
     for name, mk in (("rq", rq), ("se_white", leaves["se_white"]), ("constant", lambda: K.Constant(2.0))):                 # (refused)
         out.append((f"trainer/leaf_{name}", "trainer", lambda mk=mk: (model_over("svgp", mk()), dict(learning_rate=1e-2), (X, Y2[:, :1]))))
+    # ---- dot-product leaves (Linear, Polynomial: K(x, x) depends on the row), Periodic (warped inputs, a period), and trees of them
+    lin = lambda **kw: K.Linear(variance=0.8, **kw)  # noqa: E731
+    lin_ard = lambda: K.Linear(variance=[0.5, 2.0, 1.25])  # noqa: E731
+    poly2 = lambda: K.Polynomial(2, variance=0.7, offset=0.3)  # noqa: E731
+    per_se = lambda: K.Periodic(se(), period=1.5)  # noqa: E731
+
+    def three_level():
+        per = K.Periodic(K.SquaredExponential(variance=1.3, lengthscales=[0.6, 0.9, 1.3]), period=[2.5, 3.0, 3.5])
+        return (lin_ard() + per) * (poly2() + K.White(variance=0.3)) + K.RationalQuadratic(variance=0.6, lengthscales=0.5, alpha=0.7,
+                                                                                             active_dims=[0, 2])
+    members = {"lin_iso": lin, "lin_ard": lin_ard, "poly2": poly2,
+               "poly1_ard_active": lambda: K.Polynomial(1, variance=[0.4, 0.9], offset=0.5, active_dims=[2, 0]),
+               "per_se": per_se,
+               "per_rq_cols": lambda: K.Periodic(K.RationalQuadratic(variance=1.1, lengthscales=[0.9, 1.2], alpha=1.7, active_dims=[0, 2]),
+                                                 period=[1.5, 3.0]),
+               "sum_lin_se": lambda: lin_ard() + se(), "prod_m32_poly": lambda: m32() * poly2(), "three_level": three_level}
+    for (kname, mk), wh, diag in itertools.product(members.items(), (True, False), (False, True)):
+        def make(mk=mk, wh=wh, diag=diag):
+            m = gp.models.SVGP(mk(), L.Gaussian(0.2), Z.copy(), q_mu=q_mu[:, :1].copy(), q_sqrt=(q_diag[:, :1] if diag else q_full[:1]).copy(),
+                               q_diag=diag, whiten=wh, num_latent_gps=1, num_data=5 * N)
+            return m, lambda: m.elbo_and_grad((X, Y2[:, :1]))
+        out.append((f"member/svgp/{'white' if wh else 'unwhite'}/{'diag' if diag else 'full'}/{kname}", "grad", make))
+    for cls, (kname, mk) in itertools.product(("gpr", "sgpr"), members.items()):     # (SGPR refuses a row diagonal)
+        def make(cls=cls, mk=mk):
+            m = model_over(cls, mk())
+            return m, m.objective_and_grad
+        out.append((f"member/{cls}/{kname}", "grad", make))
+    # refused: a row diagonal outside the plain routes, a Periodic member in the trainer
+    for kname in ("lin_iso", "sum_lin_se"):
+        out.append((f"member/quadrature/{kname}", "grad",
+                    elbo_case(lambda kname=kname: model_over("svgp", members[kname](), L.Bernoulli()), liks["bernoulli"][2])))
+        out.append((f"natgrad/member_{kname}", "natgrad", lambda kname=kname: (model_over("svgp", members[kname]()), (X, Y2[:, :1]))))
+    for kname in ("per_se", "three_level", "lin_iso"):
+        out.append((f"trainer/member_{kname}", "trainer",
+                    lambda kname=kname: (model_over("svgp", members[kname]()), dict(learning_rate=1e-2), (X, Y2[:, :1]))))
+    out.append(("member/sep_dot", "grad", elbo_case(lambda: sep([se(), lin()]), Y2)))
+    out.append(("member/sep_per", "grad", elbo_case(lambda: sep([se(), per_se()]), Y2)))
+    out.append(("member/lcm_dot", "grad", elbo_case(lambda: lcm([se(), poly2(), m32()]), Y2)))
+    out.append(("member/lcm_sum_dot", "grad", elbo_case(lambda: lcm([se(), lin() + se(), m32()]), Y2)))
     return out
 
 
@@ -378,12 +449,14 @@ def dump_models(tree, path, device=None):
     from gpflow_amd import ops, training
     log, depth, wrap = _logger()
     if device is None:
+        import fake_dot_ops
         import fake_kernel_ops
         import fake_lcm_ops
         import fake_likelihood_ops
         import fake_multiclass_ops
         import fake_ops
-        for mod in (fake_ops, fake_likelihood_ops, fake_multiclass_ops, fake_kernel_ops, fake_lcm_ops):
+        import fake_periodic_ops
+        for mod in (fake_ops, fake_likelihood_ops, fake_multiclass_ops, fake_kernel_ops, fake_periodic_ops, fake_lcm_ops, fake_dot_ops):
             for name in dir(mod):
                 v = getattr(mod, name)
                 if name.startswith("_") or not callable(v) or not hasattr(ops, name) or isinstance(v, types.ModuleType):
@@ -427,13 +500,13 @@ def dump_models(tree, path, device=None):
                 vals = {"q_mu": model.q_mu.numpy(), "q_sqrt": model.q_sqrt.numpy()}
             res[name] = (list(log), pack(vals))
         except (NotImplementedError, ValueError) as e:
-            res[name] = (list(log), {"refused:" + type(e).__name__: ((), b"")})
+            res[name] = (list(log), {f"refused:{type(e).__name__}:{e}": ((), b"")})
     with open(path, "wb") as f:
         pickle.dump(res, f)
     refused = [n for n, (_, v) in res.items() if any(k.startswith("refused:") for k in v)]
     print(len(res), "entries;", len(refused), "refusals:")
     for n in refused:
-        print("   ", n, next(iter(res[n][1])), "after", len(res[n][0]), "ops.* calls")
+        print("   ", n, next(iter(res[n][1]))[:60], "after", len(res[n][0]), "ops.* calls")
 
 
 def compare(pa, pb):
