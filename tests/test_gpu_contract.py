@@ -9,7 +9,9 @@ Each case runs the device call and the `fake_ops` call on the same NumPy inputs 
   4. a second identical device call is bit-identical (no floating-point atomics in the library);
   5. inputs outside the contract are refused on both sides.
 Every case carries a comment naming the boundary or branch it targets; for GEMM_CASES and PROJECT_CASES the branch is pinned, on the
-CPU, by tests/test_gpu_gemm_launch.py (test_contract_tables_are_on_their_branches): a row added here gets its pin there.  The
+CPU, by tests/test_gpu_gemm_launch.py (test_contract_tables_are_on_their_branches): a row added here gets its pin there.  The rows on
+the two sides of a grid clamp, a gridDim-stride loop or a count-selected instantiation are named, per launch, by LAUNCHES in
+tests/test_launch_geometry.py, whose CPU guard fails when such a row leaves its table.  The
 CPU-tier guard at the end fails when a primitive shared by `fake_ops` and `ops` has no case table here.
 """
 import contextlib
@@ -84,9 +86,16 @@ def _on(x, layout="c", dev="cuda", base=False):
     pad: the first cols columns of a wider buffer whose leading dimension is even (the smallest even value >= cols + 2): base and
          every row 16-byte aligned, as in c, but ld != cols;
     bpad / bodd (3-D input only; any other layout of a 3-D input is c): contiguous entries carved from one 1-D buffer at batch stride
-         rows * cols + 2 (even) / rows * cols + 1 (odd: every second entry is 8-byte aligned only).
+         rows * cols + 2 (even) / rows * cols + 1 (odd: every second entry is 8-byte aligned only);
+    bld (3-D input only): every entry a row-major view with the odd leading dimension of ld, entries rows * ld apart.
     Padding around a view is NaN, inside the allocation.  base=True: returns (view, allocation), for _outside_view."""
     x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 3 and layout == "bld":
+        b, r, c = x.shape
+        buf = torch.full((b, r, c + 1 if (c + 1) % 2 else c + 2), NAN, dtype=torch.float64, device=dev)
+        v = buf[:, :, :c]
+        v.copy_(torch.from_numpy(x))
+        return (v, buf) if base else v
     if x.ndim == 3 and layout in ("bpad", "bodd"):
         b, r, c = x.shape
         stride = r * c + (2 if layout == "bpad" else 1)
@@ -190,6 +199,13 @@ GEMM_CASES = [
     (9, 11, 0, 1.0, 0.0, 0, False, "c", 0),         # k = 0, fresh empty operands (null A / B): C = 0, NaN C not read
     (9, 11, 0, 2.0, -0.5, 0, False, "c", 0),        # k = 0 with beta != 0: C = beta C
     (130, 140, 0, 1.0, 0.0, 0, True, "c", 0),       # k = 0 with c_lower: the tile above the diagonal keeps its sentinel
+    # gemm_nt_empty_k_kernel's launch: min(ceil(n / 256), 64) column blocks with a grid-stride loop, at most 65535 rows per launch
+    # with a host loop over the first row, blockIdx.z over the batch (tests/test_launch_geometry.py: LAUNCHES)
+    (2, 16384, 0, 1.0, 0.0, 0, False, "c", 0),      # k = 0, 64 column blocks, exactly the clamp: no second trip; NaN C not read
+    (2, 16385, 0, 2.0, -0.5, 0, False, "ld", 0),    # k = 0, one column past the clamp: thread 0 of block 0 loops; beta C, odd ld
+    (65535, 3, 0, 2.0, -0.5, 0, False, "c", 0),     # k = 0, 65535 rows: one launch, grid.y at its limit; beta C
+    (65536, 3, 0, 1.0, 0.0, 0, False, "c", 0),      # k = 0, 65536 rows: a second launch of one row (row0 = 65535); NaN C not read
+    (9, 300, 0, 2.0, -0.5, 0, False, "c", 3),       # k = 0, batch 3 (3-D operands without a last dimension are accepted): blockIdx.z
     (33, 35, 15, 1.0, 0.0, 0, False, "c", 0),       # K slab - 1: generic kernel
     (33, 35, 16, 1.0, 0.0, 0, False, "c", 0),       # one whole K slab: small latency kernel (kind 1)
     (33, 35, 17, 1.0, 0.0, 0, False, "c", 0),       # K slab + 1: generic kernel, partial slab
@@ -254,10 +270,13 @@ def test_gemm_nt_contract(gpu, case):
     skipped = (C0 == -777.0) if c_lower else np.zeros(C0.shape, dtype=bool)
     for who, impl, dev in _impls():
         lay = layout if batch == 0 else "c"
-        tA, tB, tC = _on(A, lay, dev), _on(Bdev, lay, dev), _on(C0, lay, dev)
+        tA, tB, (tC, bufC) = _on(A, lay, dev), _on(Bdev, lay, dev), _on(C0, lay, dev, base=True)
         got = _np(impl.gemm_nt(tA, tB, alpha=alpha, beta=beta, C=tC, b_tri=b_tri, c_lower=c_lower))
         _within(f"gemm_nt {who}", np.where(skipped, 0, got), np.where(skipped, 0, ref), np.where(skipped, 0, bnd))
         assert _same_bits(got[skipped], C0[skipped]), f"gemm_nt {who}: a skipped c_lower tile was written"
+        if k == 0:   # no product: exact zeros, or the one rounding of beta C -- NumPy's bits
+            assert _same_bits(got[~skipped], (beta * C0 if beta != 0 else np.zeros(C0.shape))[~skipped]), f"gemm_nt {who}: k = 0"
+        assert _padding_untouched(tC, bufC), f"gemm_nt {who}: wrote outside the view of C"
         _check_unchanged(f"gemm_nt {who}", (tA, tB), (A, Bdev))
         if who == "device":   # determinism: the same call again is bit-identical
             tC2 = _on(C0, lay, dev)
@@ -805,8 +824,10 @@ def test_gaussian_varexp_sum_refuses_17_latents(gpu):
 
 
 # (m, P, q_diag)
-KL_CASES = [(1, 1, False), (17, 5, True), (129, 4, False), (1100, 1, True)]
-# size 1; P = 5 diagonal; a tile edge over 4 latents; more rows than MAXPART stage-1 blocks
+KL_CASES = [(1, 1, False), (17, 5, True), (129, 4, False), (1100, 1, True), (1100, 1, False)]
+# size 1; P = 5 diagonal; a tile edge over 4 latents; more rows than MAXPART stage-1 blocks;
+# kl_white_kernel's grid is one block per 1024 elements, clamped to MAXPART = 1024 blocks: a full q_sqrt of 1100 x 1100 asks for 1182
+# (the diagonal form counts M P elements: its 1100 rows are two blocks), so the grid-stride loop runs past its usual four trips
 CASE_TABLES["gauss_kl_white"] = KL_CASES
 
 
@@ -839,6 +860,13 @@ COMBINE_CASES = [
     (1, 129, 64, 1.0, True, 0.5, "off"),      # one part, misaligned, lower
     (2, 65537, 3, 1.0, False, 1.0, "c"),      # more than 65535 rows: grid.y capped, the kernel loops over rows
 ]
+# combine_parts_kernel<NP> is picked by the count: 8, 16 (splitk_gemm_nt's 8 chunks) and 32 (the [M, 17] product at K = 8192) have an
+# instantiation of their own, 33 takes the run-time loop of NP = 0.  Per count: (130, 66) contiguous -- the 16-byte loads, all NP
+# issued before the first add; (65, 63) with an odd leading dimension and part stride -- the element loop inside the same
+# instantiation; lower with NaN above the diagonal -- never read, zeros written, Phi's diagonal 0.5
+for _np_count in (8, 16, 32, 33):
+    COMBINE_CASES += [(_np_count, 130, 66, -0.5, False, 1.0, "c"), (_np_count, 65, 63, 2.0, False, 1.0, "ld"),
+                      (_np_count, 130, 130, 1.0, True, 0.5, "c")]
 CASE_TABLES["combine_parts"] = COMBINE_CASES
 
 
@@ -860,12 +888,15 @@ def test_combine_parts_contract(gpu, case):
         bnd = np.where(keep, bnd, 0)
     src = pin if npart > 1 else pin[0]
     for who, impl, dev in _impls():
-        tp = _on(src, layout if npart == 1 else "c", dev)
+        tp, buf = _on(src, layout if npart == 1 else {"ld": "bld"}.get(layout, "c"), dev, base=True)
         R = _np(impl.combine_parts(tp, alpha=alpha, lower=lower, diag_scale=dscale))
         _within(f"combine_parts {who}", R, ref, bnd)
         if lower:
             assert np.all(R[~keep] == 0), who
         _check_unchanged(f"combine_parts {who}", [tp], [src])
+        assert _padding_untouched(tp, buf), f"combine_parts {who}: wrote outside the view of parts"
+        if who == "device":   # determinism: the same call again is bit-identical
+            assert _same_bits(_np(impl.combine_parts(tp, alpha=alpha, lower=lower, diag_scale=dscale)), R), "combine_parts: a second call differs"
 
 
 # ------------------------------------------------------------------------------------------------ projection
@@ -991,6 +1022,14 @@ SVGP_CASES = [
     (640, 300, 8, 1, False, False, "c"),    # P = 1: the prefilled triangular rows (tril(q_sqrt)^T) skipped across two extra-row groups
     (1152, 1040, 8, 1, False, False, "c"),  # ... across three groups and in the tail zone (shrinking groups at the end)
     (640, 300, 8, 2, False, False, "off"),  # P = 2: the same form without the skip; misaligned rows
+    # varexp_kernel<true>, the one-launch tail of the whitened Gaussian shard: min(ceil(rows P / 256), 1024) blocks with a grid-stride
+    # loop over the elements; the block that draws the last ticket sums gridDim.x block partials with a loop i += 256
+    (16, 65537, 2, 1, False, True, "c"),    # 257 blocks: the ticket holder's loop takes a second trip, of one partial
+    (16, 131072, 2, 2, False, True, "c"),   # rows P = 262144, exactly 1024 blocks: one element per thread, four trips of the ticket sum
+    (16, 131073, 2, 2, False, True, "c"),   # rows P = 262146: two threads take a second element trip; P = 2, so b = e / P matters
+    # kl_unwhite_diag_kernel: min(M, 1024) blocks, the inducing points strided by gridDim.x, a block_sum (shared scratch) per trip
+    (1024, 64, 8, 2, True, False, "c"),     # un-whitened diagonal q_sqrt at exactly the clamp: one trip per block
+    (1100, 64, 8, 2, True, False, "c"),     # 76 blocks take a second trip and reuse the scratch of block_sum
 ]
 CASE_TABLES["svgp_elbo_shard"] = SVGP_CASES
 
@@ -1004,18 +1043,26 @@ def test_svgp_elbo_shard_contract(gpu, case):
     kw = dict(variance=1.1, lengthscales=0.9, noise_variance=0.2, jitter=1e-6, mean_const=0.05)
     res = {}
     for who, impl, dev in _impls():
-        tX, tY = _on(X, layout, dev), _on(Y, layout, dev)
-        out, info = impl.svgp_elbo_shard(_on(Z, "c", dev), tX, tY, _on(q_mu, "c", dev), _on(qs, "c", dev), whiten=whiten, **kw)
+        (tX, bX), (tY, bY) = _on(X, layout, dev, base=True), _on(Y, layout, dev, base=True)
+        args = (_on(Z, "c", dev), tX, tY, _on(q_mu, "c", dev), _on(qs, "c", dev))
+        out, info = impl.svgp_elbo_shard(*args, whiten=whiten, **kw)
         assert int(_np(info)[0]) == 0
         res[who] = _np(out)
         _check_unchanged(f"svgp_elbo_shard {who}", [tX, tY], [X, Y])
+        assert _padding_untouched(tX, bX) and _padding_untouched(tY, bY), f"svgp_elbo_shard {who}: wrote outside a view"
+        if who == "device":   # determinism: the same call again (a fresh workspace) is bit-identical
+            assert _same_bits(_np(impl.svgp_elbo_shard(*args, whiten=whiten, **kw)[0]), res[who]), "svgp_elbo_shard: a second call differs"
     dv, fv = res["device"], res["fake_ops"]
     if rows == 0:
         assert dv[0] == 0.0 and fv[0] == 0.0, (dv, fv)
     kap = _kappa(Z, "SquaredExponential", 1.1, 0.9, 1e-6)
     cond = math.sqrt(kap) if whiten else kap
-    assert abs(dv[0] - fv[0]) <= _fused_bound(M, fv[0], abs(fv[0]) + 10 * rows * P, cond), (dv, fv)
-    assert abs(dv[1] - fv[1]) <= _fused_bound(M, fv[1], abs(fv[1]) + 10 * M * P, cond), (dv, fv)
+    bounds = (_fused_bound(M, fv[0], abs(fv[0]) + 10 * rows * P, cond), _fused_bound(M, fv[1], abs(fv[1]) + 10 * M * P, cond))
+    if rows:
+        print(f"svgp_elbo_shard {case}: |device - fake_ops| / bound = {abs(dv[0] - fv[0]) / bounds[0]:.3e} (out[0]), "
+              f"{abs(dv[1] - fv[1]) / bounds[1]:.3e} (out[1]); kappa(Kuu) = {kap:.3e}")
+    assert abs(dv[0] - fv[0]) <= bounds[0], (dv, fv)
+    assert abs(dv[1] - fv[1]) <= bounds[1], (dv, fv)
     if whiten:   # the whitened KL does not involve Kuu: the reduction bound alone
         kl = float(fake_ops.gauss_kl_white(torch.from_numpy(q_mu), torch.from_numpy(qs))[0])
         assert abs(dv[1] - kl) <= (2 * (M * M * P + 2) + 4) * U * (abs(kl) + M * M * P), (dv[1], kl)
@@ -1125,13 +1172,21 @@ def test_stationary_adjoint_tail_contract(gpu, n1, d, sym):
         _within(f"adjoint dls {who}", _np(sl), dls, (2 * (n1 + 2) + 10) * U * terms.sum(0) / (l ** 3) + LD(1e-300))
 
 
-CASE_TABLES["adam_step_"] = [(1, False), (257, True), (5000, False)]   # size 1; maximise; several blocks
+CASE_TABLES["adam_step_"] = [
+    (1, False), (257, True), (5000, False),   # size 1; maximise; several blocks
+    # adam_kernel's grid is clamped to 4096 blocks of 256 threads, then a grid-stride loop (q_sqrt at M = 2048 is 4 194 304 elements)
+    (1048576, False),      # 4096 x 256, exactly the clamp: every thread one trip
+    (1048577, True),       # one element past it: thread 0 of block 0 takes a second trip; maximise
+    (2097153 + 257, False),   # every thread a second trip, 258 of them a third; the last block of the last trip partial
+]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,maxi", CASE_TABLES["adam_step_"])
 def test_adam_step_contract(gpu, n, maxi):
-    """A handful of correctly rounded operations per element: a few ulp of each term of the longdouble update."""
+    """A handful of correctly rounded operations per element: a few ulp of each term of the longdouble update.  (One flat
+    contiguous variable each: the three that are written sit one element inside a NaN-filled allocation, which must stay NaN on
+    both sides.)"""
     rng = np.random.default_rng(n)
     p, g, m, v = rng.normal(size=n), rng.normal(size=n), rng.normal(size=n), rng.uniform(0.1, 1, size=n)
     b1, b2, eps, step = 0.9, 0.999, 1e-7, 0.01
@@ -1140,16 +1195,35 @@ def test_adam_step_contract(gpu, n, maxi):
     vr = b2 * v.astype(LD) + (1 - LD(b2)) * gg * gg
     upd = step * mr / (np.sqrt(vr) + eps)
     pr = p - upd
+
+    def inside(x, dev):   # x as the elements 1 .. n of a NaN-filled allocation of n + 2
+        buf = torch.full((n + 2,), NAN, dtype=torch.float64, device=dev)
+        buf[1:n + 1].copy_(torch.from_numpy(x))
+        return buf[1:n + 1], buf
+
     for who, impl, dev in _impls():
-        tp, tg, tm, tv = (_on(x, "c", dev) for x in (p, g, m, v))
-        impl.adam_step_(tp, tg, tm, tv, beta1=b1, beta2=b2, epsilon=eps, step=step, maximise=maxi)
-        _within(f"adam m {who}", _np(tm), mr, 4 * U * (np.abs(m) + np.abs(g)))
-        _within(f"adam v {who}", _np(tv), vr, 4 * U * (v + g * g))
-        _within(f"adam p {who}", _np(tp), pr, 2 * U * np.abs(p) + 8 * U * (np.abs(upd) + step * (np.abs(m) + np.abs(g)) / np.sqrt(vr)))
-        _check_unchanged(f"adam {who}", [tg], [g])
+        def run():
+            (tp, bp), (tm, bm), (tv, bv), tg = inside(p, dev), inside(m, dev), inside(v, dev), _on(g, "c", dev)
+            impl.adam_step_(tp, tg, tm, tv, beta1=b1, beta2=b2, epsilon=eps, step=step, maximise=maxi)
+            for t, b in ((tp, bp), (tm, bm), (tv, bv)):
+                assert _padding_untouched(t, b), f"adam {who}: wrote outside the variable"
+            _check_unchanged(f"adam {who}", [tg], [g])
+            return _np(tp), _np(tm), _np(tv)
+        gp, gm, gv = run()
+        _within(f"adam m {who}", gm, mr, 4 * U * (np.abs(m) + np.abs(g)))
+        _within(f"adam v {who}", gv, vr, 4 * U * (v + g * g))
+        _within(f"adam p {who}", gp, pr, 2 * U * np.abs(p) + 8 * U * (np.abs(upd) + step * (np.abs(m) + np.abs(g)) / np.sqrt(vr)))
+        if who == "device":   # determinism: the same update again, from the same state, is bit-identical
+            assert all(_same_bits(a, b) for a, b in zip(run(), (gp, gm, gv))), "adam: a second call differs"
 
 
-CASE_TABLES["lowrank_axpy"] = [(1, 1, 1, "c"), (65, 130, 16, "ld"), (300, 63, 5, "off")]   # size 1; k = 16 maximum; misaligned
+CASE_TABLES["lowrank_axpy"] = [
+    (1, 1, 1, "c"), (65, 130, 16, "ld"), (300, 63, 5, "off"),   # size 1; k = 16 maximum; misaligned
+    # lowrank_axpy_kernel's gridDim.y is clamped to 2048, the rows strided by it (8192 rows in the reverse pass of the training step)
+    (2048, 130, 16, "c"),     # exactly the clamp: one row per block; aligned, even n: the 16-byte path; k = 16
+    (2049, 63, 5, "off"),     # one row past it: blockIdx.y = 0 takes a second trip; odd n, misaligned: the element path; k = 5
+    (4097, 66, 16, "c"),      # every blockIdx.y a second trip, the first a third; the 16-byte path in the strided rows
+]
 
 
 @pytest.mark.gpu
@@ -1161,9 +1235,13 @@ def test_lowrank_axpy_contract(gpu, m, n, k, layout):
     ref = -0.7 * X.astype(LD) + Uu.astype(LD) @ V.T.astype(LD)
     bnd = 2 * (k + 3) * U * (0.7 * np.abs(X) + np.abs(Uu) @ np.abs(V).T)
     for who, impl, dev in _impls():
-        tX, tU, tV = _on(X, layout, dev), _on(Uu, layout, dev), _on(V, layout, dev)
-        _within(f"lowrank_axpy {who}", _np(impl.lowrank_axpy(-0.7, tX, tU, tV)), ref, bnd)
+        (tX, bX), (tU, bU), (tV, bV) = (_on(x, layout, dev, base=True) for x in (X, Uu, V))
+        got = _np(impl.lowrank_axpy(-0.7, tX, tU, tV))
+        _within(f"lowrank_axpy {who}", got, ref, bnd)
         _check_unchanged(f"lowrank_axpy {who}", [tX, tU, tV], [X, Uu, V])
+        assert all(_padding_untouched(t, b) for t, b in ((tX, bX), (tU, bU), (tV, bV))), f"lowrank_axpy {who}: wrote outside a view"
+        if who == "device":   # determinism: the same call again is bit-identical
+            assert _same_bits(_np(impl.lowrank_axpy(-0.7, tX, tU, tV)), got), "lowrank_axpy: a second call differs"
     with pytest.raises(ValueError):       # k = 17 is refused on both sides
         ops.lowrank_axpy(1.0, _on(X), _on(np.zeros((m, 17))), _on(np.zeros((n, 17))))
     with pytest.raises(AssertionError):

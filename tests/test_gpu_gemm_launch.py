@@ -278,10 +278,38 @@ PROJECT_CASE_PINS = {
 }
 
 
+# The k = 0 rows make no plan: gpk_gemm_nt launches gemm_nt_empty_k_kernel itself, i0 = 0, 65535, ... < m, each launch on a grid of
+# (min(ceil(n / 256), 64), min(m - i0, 65535), batch) with a grid-stride loop over the columns (tests/test_launch_geometry.py holds the
+# two expressions to the source).  What each row's comment claims about that geometry:
+# (column blocks, trips of the column loop, launches, rows of the last launch, grid.z)
+GEMM_EMPTY_K_PINS = {
+    (9, 11, 0, 1.0, 0.0, 0, False, "c", 0): (1, 1, 1, 9, 1),
+    (9, 11, 0, 2.0, -0.5, 0, False, "c", 0): (1, 1, 1, 9, 1),
+    (130, 140, 0, 1.0, 0.0, 0, True, "c", 0): (1, 1, 1, 130, 1),
+    (2, 16384, 0, 1.0, 0.0, 0, False, "c", 0): (64, 1, 1, 2, 1),
+    (2, 16385, 0, 2.0, -0.5, 0, False, "ld", 0): (64, 2, 1, 2, 1),
+    (65535, 3, 0, 2.0, -0.5, 0, False, "c", 0): (1, 1, 1, 65535, 1),
+    (65536, 3, 0, 1.0, 0.0, 0, False, "c", 0): (1, 1, 2, 1, 1),
+    (9, 300, 0, 2.0, -0.5, 0, False, "c", 3): (2, 1, 1, 9, 3),
+}
+
+
+def _empty_k_geometry(case):
+    m, n, batch = case[0], case[1], abs(case[8]) or 1
+    gx = min(-(-n // 256), 64)
+    launches = -(-m // 65535)
+    return gx, -(-n // (gx * 256)), launches, m - (launches - 1) * 65535, batch
+
+
 def test_contract_tables_are_on_their_branches(dumper, tmp_path):
     """Every row of the public-path tables of test_gpu_contract.py that reaches make_gemm_plan has a pin here, and takes the branch
-    its comment names."""
+    its comment names; every k = 0 row has its launch geometry pinned."""
     import test_gpu_contract as contract
+    empty_k = [c for c in contract.GEMM_CASES if c[2] == 0 and c[0] > 0 and c[1] > 0]
+    assert not [c for c in empty_k if c not in GEMM_EMPTY_K_PINS], "k = 0 rows without a pinned launch geometry"
+    assert not [c for c in GEMM_EMPTY_K_PINS if c not in empty_k], "pins of k = 0 rows that are gone"
+    for c in empty_k:
+        assert _empty_k_geometry(c) == GEMM_EMPTY_K_PINS[c], (c, _empty_k_geometry(c))
     rows = [("gemm_nt", case, _gemm_case_call(case), GEMM_CASE_PINS) for case in contract.GEMM_CASES]
     rows += [("project", case, _project_case_call(case), PROJECT_CASE_PINS) for case in contract.PROJECT_CASES]
     rows = [r for r in rows if r[2] is not None]

@@ -707,7 +707,10 @@ def test_moment_rows_nonfinite(impl, n2, d, layout):
 
 
 # (nparts, m, n, alpha, lower, diag_scale)
-NF_TABLES["combine_parts"] = [(4, 70, 66, -0.5, False, 1.0), (3, 130, 130, 1.0, True, 0.5)]
+NF_TABLES["combine_parts"] = [(4, 70, 66, -0.5, False, 1.0), (3, 130, 130, 1.0, True, 0.5),
+                              # the count-selected instantiations combine_parts_kernel<8 / 16 / 32> and, at 33, the run-time loop
+                              (8, 70, 66, -0.5, False, 1.0), (16, 130, 130, 1.0, True, 0.5), (32, 70, 66, -0.5, False, 1.0),
+                              (33, 130, 130, 1.0, True, 0.5)]
 
 
 @pytest.mark.parametrize("case", NF_TABLES["combine_parts"], ids=str)
@@ -739,7 +742,8 @@ def test_combine_parts_nonfinite(impl, case):
         _footprint("combine_parts", who, run, {"parts": parts}, "parts", (1, 0, n - 1), NAN, {}, clean)
 
 
-NF_TABLES["lowrank_axpy"] = [(65, 130, 16, "ld"), (300, 63, 5, "off")]
+NF_TABLES["lowrank_axpy"] = [(65, 130, 16, "ld"), (300, 63, 5, "off"),
+                             (2049, 66, 16, "c")]   # one row past the clamp of gridDim.y: row 2048 is blockIdx.y = 0's second trip
 
 
 @pytest.mark.parametrize("m,n,k,layout", NF_TABLES["lowrank_axpy"])
@@ -759,13 +763,14 @@ def test_lowrank_axpy_nonfinite(impl, m, n, k, layout):
     for val in (NAN, PINF, NINF):
         for i, j in ((0, 0), (m - 1, n - 1), (64, 62)):
             _footprint("lowrank_axpy", who, run, arrs, "X", (i, j), val, {"out": [(i, j)]}, clean, ref)
-        for i, kk in ((0, 0), (m - 1, k - 1)):
+        for i, kk in ((0, 0), (m - 1, k - 1)):   # (m - 1: past the clamp, the row of a second trip)
             _footprint("lowrank_axpy", who, run, arrs, "U", (i, kk), val, {"out": [(i,)]}, clean, ref)
         for j, kk in ((0, k - 1), (n - 1, 0)):
             _footprint("lowrank_axpy", who, run, arrs, "V", (j, kk), val, {"out": [(slice(None), j)]}, clean, ref)
 
 
-NF_TABLES["adam_step_"] = [(257, True), (5000, False)]
+NF_TABLES["adam_step_"] = [(257, True), (5000, False),
+                           (1048577, False)]   # one element past the grid clamp of 4096 x 256: the last element is a second trip
 
 
 @pytest.mark.parametrize("n,maxi", NF_TABLES["adam_step_"])
@@ -781,7 +786,7 @@ def test_adam_step_nonfinite(impl, n, maxi):
         _unchanged("adam_step_", [(tg, a["g"])])
         return {"p": _np(tp), "m": _np(tm), "v": _np(tv)}
     clean = run(arrs)
-    for i in (0, n - 1, 255, 256):
+    for i in _pick((0, 255, 256, 1048575), n):   # (and n - 1)
         _footprint("adam_step_", who, run, arrs, "g", (i,), NAN, {"p": [(i,)], "m": [(i,)], "v": [(i,)]}, clean)
         _footprint("adam_step_", who, run, arrs, "p", (i,), NAN, {"p": [(i,)]}, clean)
 

@@ -95,6 +95,10 @@ def test_fused_statistics_against_numpy(gpu, rows, m, P):
     assert np.array_equal(ops.project(tA, tL).cpu().numpy().view(np.int64), got["ssq"].view(np.int64))
 
 
+# shapes of test_shard_against_oracle that take one noise variance per row (varexp_kernel's noise_rows branch) instead of a constant
+PER_ROW_NOISE = {(16, 65537, 2, 1)}
+
+
 def _shard_inputs(m, rows, d, P, seed=13):
     rng = np.random.default_rng(seed)
     X = rng.normal(size=(rows, d))
@@ -116,11 +120,14 @@ def _shard(X, Y, Z, q_mu, q_sqrt, kw, ws=None):
 @pytest.mark.parametrize("m,rows,d,P", [(256, 300, 3, 1), (256, 300, 3, 2),   # side schedule, one-launch tail
                                         (256, 200, 3, 1),                      # the extra rows ride through the panels
                                         (256, 64, 3, 1),                       # statistics out of the GEMM (unpaired fast tile)
-                                        (512, 16507, 3, 1)])                   # side schedule AND the paired walk with statistics
+                                        (512, 16507, 3, 1),                    # side schedule AND the paired walk with statistics
+                                        (16, 65537, 2, 1)])                    # 257 tail blocks (PER_ROW_NOISE): the ticket sum's second trip
 def test_shard_against_oracle(gpu, m, rows, d, P):
     """2. Both terms of the whitened shard against the oracle at rtol = 1e-9, the tolerance of the model-level ELBO comparisons
     (tests/test_gpu_models.py:284; the shard tests of tests/test_gpu_primitives.py:425 use the same for out[0])."""
     X, Y, Z, q_mu, q_sqrt, kw = _shard_inputs(m, rows, d, P)
+    if (m, rows, d, P) in PER_ROW_NOISE:
+        kw["noise_variance"] = np.random.default_rng(rows).uniform(0.05, 0.2, size=rows)
     out, info = _shard(X, Y, Z, q_mu, q_sqrt, kw)
     assert np.all(info == 0), info
     s_ref, kl_ref = orc.svgp_elbo_terms(X, Y, Z, q_mu, q_sqrt, whiten=True, **kw)
@@ -155,6 +162,33 @@ def test_ticket_and_workspace_reuse(gpu, q_diag):
     out, info = _shard(*small, ws=ws)
     assert np.all(info == 0)
     assert np.array_equal(out.view(np.int64), fresh_small[0].view(np.int64)), f"smaller shape on the reused workspace: {out!r} vs {fresh_small[0]!r}"
+
+
+@pytest.mark.gpu
+def test_ticket_and_workspace_reuse_past_the_block_clamp(gpu):
+    """3b. The same at rows P = 262146 (tests/test_gpu_contract.py: SVGP_CASES), where the tail's grid is clamped to 1024 blocks and
+    its elements are strided: the ticket stands at 1024 after a call, and kl_white_kernel of the next call must zero it -- else no
+    block draws the last ticket and out[0] is never written.  The workspace starts with 0xFF bytes; out is NaN before every call;
+    each result equals the call on a fresh workspace bit for bit."""
+    import torch
+    from gpflow_amd import ops
+    m, rows, d, P = 16, 131073, 2, 2
+    X, Y, Z, q_mu, q_sqrt, kw = _shard_inputs(m, rows, d, P)
+    tensors = [_t(x) for x in (Z, X, Y, q_mu, q_sqrt)]
+    nbytes = int(ops._lib.load().gpk_svgp_elbo_workspace_bytes(m, rows, d, P, 0, 1))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=ops.device())
+    ws.view(torch.uint8).fill_(0xFF)
+
+    def call(w):
+        out = torch.full((2,), float("nan"), dtype=torch.float64, device=ops.device())
+        _, info = ops.svgp_elbo_shard(*tensors, jitter=1e-6, ws=w, out=out, **kw)
+        assert np.all(info.cpu().numpy() == 0)
+        return out.cpu().numpy()
+    fresh = call(torch.zeros_like(ws))
+    assert np.all(np.isfinite(fresh)), fresh
+    for i in range(2):
+        out = call(ws)
+        assert np.array_equal(out.view(np.int64), fresh.view(np.int64)), f"call {i} on the reused workspace: {out!r} vs {fresh!r}"
 
 
 @pytest.mark.gpu
