@@ -2,6 +2,7 @@
 // quadrature (lik_varexp_kernel), MultiClass / RobustMax (lik_multiclass_kernel), Gaussian on linearly mixed latents
 // (mixed_varexp_kernel: LinearCoregionalization).  Stage 1 of the two-stage reductions of reduce.hip.
 #include "reduce_device.h"
+#include "digamma.h"
 
 namespace {
 
@@ -85,7 +86,8 @@ __global__ __launch_bounds__(RB) void varexp_kernel(VarexpArgs a) {
 }
 
 // ---- non-Gaussian variational expectations, stage 1 (likelihoods/base.py: ScalarLikelihood through NDiagGHQuadrature,
-// quadrature/gauss_hermite.py; scalar_discrete.py Bernoulli / Poisson; scalar_continuous.py StudentT) -----------------------
+// quadrature/gauss_hermite.py; scalar_discrete.py Bernoulli / Poisson / Ordinal; scalar_continuous.py StudentT / Exponential /
+// Gamma / Beta; the formulas of every code: include/gpk.h) -----------------------------------------------------------------
 //   VE[b,p] = sum_h (w_h / sqrt(pi)) g(mu + sqrt(2 v) x_h),  g = log p(y | f),  with d/dmu and d/dv of that same sum.
 // numpy.polynomial.hermite.hermgauss(20), the reference's DEFAULT_NUM_GAUSS_HERMITE_POINTS (gpk_gauss_hermite returns this table)
 #define GPK_GH20_X                                                                                                          \
@@ -99,6 +101,7 @@ __global__ __launch_bounds__(RB) void varexp_kernel(VarexpArgs a) {
       0.4622436696006101, 0.28667550536283415, 0.1090172060200233, 0.024810520887463643, 0.0032437733422378567,              \
       0.00022833863601635365, 7.80255647853206e-06, 1.0860693707692782e-07, 4.3993409922731747e-10, 2.2293936455341447e-13
 constexpr int GH_N = 20;
+constexpr int GPK_ORDINAL_MAXEDGE = 15;
 __constant__ const double gh_x_dev[GH_N] = {GPK_GH20_X};
 __constant__ const double gh_w_dev[GH_N] = {GPK_GH20_W};
 const double gh_x_host[GH_N] = {GPK_GH20_X};
@@ -109,15 +112,20 @@ struct LikVarexpArgs {
   double par0, par1, c0;   // Poisson: binsize, -, log(binsize);  StudentT: scale, df, the f-independent part of log p;
                            // MultiClass: log(1 - eps), log(eps / (C - 1)), their difference
   double *rows_out, *dmu_out, *dvar_out;
-  double *part, *part1;    // stage-1 partials of sum VE and (part1 may be null) of sum dVE/dscale
+  double *part, *part1;    // stage-1 partials of sum VE and (part1 may be null) of sum dVE/dtheta (the code's one trainable parameter)
+  // Exponential: nothing;  Gamma: par0 = shape, par1 = psi(shape), c0 = lgamma(shape);  Beta: par0 = scale, par1 = psi(scale),
+  // c0 = lgamma(scale);  Ordinal: par0 = sigma and the bin edges, by value:
+  int nedge; double edge[GPK_ORDINAL_MAXEDGE];
 };
 
 // One element (b, p) is shared by LPE = 4 adjacent lanes, five nodes each (8192 x P elements with a serial 20-node loop of fp64
 // erfc + log + exp per thread would leave most of the chip idle); the four partial sums meet through two xor shuffles, so all
-// four lanes hold the same bits.  The closed-form Poisson branch has no nodes: one lane per element.  A wave pass covers
+// four lanes hold the same bits.  The closed-form branches (Poisson, Exponential, Gamma) have no nodes: one lane per element.  A wave pass covers
 // floor((64 / LPE) / P) WHOLE rows, so that the row sums of rows_out are a fixed-order shuffle loop inside one wave.
 // This layout is written down once, for both kernels and for the launcher's grid:
-__host__ __device__ constexpr int quad_lpe(int lik) { return lik == GPK_LIK_POISSON_EXP ? 1 : 4; }   // lanes per element
+__host__ __device__ constexpr int quad_lpe(int lik) {   // lanes per element
+  return lik == GPK_LIK_POISSON_EXP || lik == GPK_LIK_EXPONENTIAL_EXP || lik == GPK_LIK_GAMMA_EXP ? 1 : 4;
+}
 __host__ __device__ constexpr int quad_rows_per_pass(int lpe, int P) { return (64 / lpe) / P; }      // (P <= 16 <= 64 / lpe)
 template <int LPE>
 struct QuadLanes {
@@ -148,11 +156,15 @@ struct QuadLanes {
 };
 
 // Non-finite inputs: NaN / Inf in fmean or fvar travel through the arithmetic; a non-finite label adds y - y = NaN to every output
-// of its element (the comparison y == 1 of the Bernoulli density would otherwise read a NaN label as class 0).
+// of its element (the comparison y == 1 of the Bernoulli density would otherwise read a NaN label as class 0).  Ordinal: a label that
+// is no integer in [0, nedge] adds NaN instead (the MultiClass rule), to the parameter derivative as well.
+// The node loop of the Beta branch is NOT unrolled: each node holds two lgamma and two gpk_digamma, and five inlined copies of
+// them buy nothing but registers (DESIGN.md section 6 has the compiler's figures for every instantiation).
 template <int LIK>
 __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
   constexpr int LPE = quad_lpe(LIK);
   constexpr int NPL = GH_N / 4;      // nodes per lane (quadrature branches)
+  constexpr int NODE_UNROLL = LIK == GPK_LIK_BETA_PROBIT ? 1 : NPL;
   __shared__ double sh[4];
   const LatentMoments& m = a.m;
   const QuadLanes<LPE> L(m);
@@ -161,7 +173,7 @@ __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
   for (long u = (long)blockIdx.x * (RB / 64) + w; u < L.npass; u += (long)gridDim.x * (RB / 64)) {
     long b; double y, mu, fv;
     const bool act = L.load(m, u, p, b, y, mu, fv);
-    const double ynan = y - y;
+    double ynan = y - y;
     double ve, dmu, dvar, dsc = 0.0;
     if (LIK == GPK_LIK_POISSON_EXP) {
       // scalar_discrete.py: Poisson.variational_expectations with the exp link, closed form
@@ -169,11 +181,43 @@ __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
       ve = y * mu - e - lgamma(y + 1.0) + y * a.c0;
       dmu = y - e;
       dvar = -0.5 * e;
+    } else if (LIK == GPK_LIK_EXPONENTIAL_EXP) {
+      // scalar_continuous.py: Exponential.variational_expectations with the exp link, closed form
+      const double ye = y * exp(0.5 * fv - mu);
+      ve = -mu - ye;
+      dmu = ye - 1.0;
+      dvar = -0.5 * ye;
+    } else if (LIK == GPK_LIK_GAMMA_EXP) {
+      // scalar_continuous.py: Gamma.variational_expectations with the exp link, closed form; log y as it comes (no clamp)
+      const double ye = y * exp(0.5 * fv - mu);
+      const double ly = log(y);
+      ve = -a.par0 * mu - a.c0 + (a.par0 - 1.0) * ly - ye;
+      dmu = ye - a.par0;
+      dvar = -0.5 * ye;
+      dsc = ly - mu - a.par1;
     } else {
       const double sd = sqrt(2.0 * fv);
       const double sgn = (y == 1.0) ? 1.0 : -1.0;
-      double sv = 0.0, sm = 0.0, sx = 0.0, ss = 0.0;
+      // Beta: the clipped label's two logarithms, once per element (comparisons: a NaN label stays NaN)
+      const double yc = y < 1e-6 ? 1e-6 : (y > 1.0 - 1e-6 ? 1.0 - 1e-6 : y);
+      const double ly = LIK == GPK_LIK_BETA_PROBIT ? log(yc) : 0.0, l1y = LIK == GPK_LIK_BETA_PROBIT ? log(1.0 - yc) : 0.0;
+      // Ordinal: the two edges of the label's bin, picked by comparison (the table is a kernel argument: no indexed copy of it);
+      // has_l / has_r: the edge is finite, i.e. not the open end of the first or last bin
+      double el = 0.0, er = 0.0;
+      bool has_l = false, has_r = false;
+      if (LIK == GPK_LIK_ORDINAL) {
+        const bool lab_ok = y >= 0.0 && y <= (double)a.nedge && y == floor(y);   // (false for NaN and +-Inf)
+        const int yi = lab_ok ? (int)y : 0;
+        ynan = lab_ok ? 0.0 : __builtin_nan("");
+        has_l = yi < a.nedge; has_r = yi > 0;
 #pragma unroll
+        for (int i = 0; i < GPK_ORDINAL_MAXEDGE; ++i) {
+          el = i == yi ? a.edge[i] : el;
+          er = i == yi - 1 ? a.edge[i] : er;
+        }
+      }
+      double sv = 0.0, sm = 0.0, sx = 0.0, ss = 0.0;
+#pragma unroll NODE_UNROLL
       for (int j = 0; j < NPL; ++j) {
         const double x = gh_x_dev[k * NPL + j];
         const double wn = gh_w_dev[k * NPL + j] * 0.5641895835477563;   // w_h / sqrt(pi)
@@ -185,6 +229,28 @@ __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
           const double q = 0.5 * erfc(-sgn * f * 0.7071067811865476) * (1.0 - 2e-3) + 1e-3;
           gv = log(q);
           gp = sgn * ((1.0 - 2e-3) * 0.3989422804014327) * exp(-0.5 * f * f) / q;
+        } else if (LIK == GPK_LIK_BETA_PROBIT) {
+          // logdensities.py beta with alpha = m scale, beta = scale - alpha, m = inv_probit(f)
+          const double mm = 0.5 * erfc(-f * 0.7071067811865476) * (1.0 - 2e-3) + 1e-3;
+          const double al = mm * a.par0, be = a.par0 - al;
+          const double pa = gpk_digamma(al), pb = gpk_digamma(be);
+          gv = (al - 1.0) * ly + (be - 1.0) * l1y + a.c0 - lgamma(al) - lgamma(be);
+          gp = a.par0 * ((1.0 - 2e-3) * 0.3989422804014327) * exp(-0.5 * f * f) * (ly - l1y - pa + pb);
+          ss += wn * (mm * ly + (1.0 - mm) * l1y + a.par1 - mm * pa - (1.0 - mm) * pb);
+        } else if (LIK == GPK_LIK_ORDINAL) {
+          // scalar_discrete.py Ordinal: log(inv_probit(zl) - inv_probit(zr) + 1e-6); the open end of a bin is +-Inf in z (erfc gives
+          // exactly 0 or 2 there) and has no density term.  The difference of the two Phi through erfc on the side where both are small.
+          const double zl = has_l ? (el - f) / a.par0 : __builtin_inf();
+          const double zr = has_r ? (er - f) / a.par0 : -__builtin_inf();
+          const bool right = zr >= 0.0;
+          const double za = right ? zr : -zl, zb = right ? zl : -zr;
+          const double D = (1.0 - 2e-3) * (0.5 * (erfc(za * 0.7071067811865476) - erfc(zb * 0.7071067811865476)));
+          const double pl = has_l ? 0.3989422804014327 * exp(-0.5 * zl * zl) : 0.0;
+          const double pr = has_r ? 0.3989422804014327 * exp(-0.5 * zr * zr) : 0.0;
+          const double den = a.par0 * (D + 1e-6);
+          gv = log(D + 1e-6);
+          gp = -(1.0 - 2e-3) * (pl - pr) / den;
+          ss += wn * (-(1.0 - 2e-3) * ((has_l ? zl * pl : 0.0) - (has_r ? zr * pr : 0.0)) / den);
         } else {
           // logdensities.py student_t:  c0 - (df + 1) / 2 log(1 + ((y - f) / scale)^2 / df)
           const double r = (y - f) / a.par0;
@@ -205,6 +271,7 @@ __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
       dsc = ss;
     }
     ve += ynan; dmu += ynan; dvar += ynan;
+    if (LIK == GPK_LIK_ORDINAL) dsc += ynan;
     double rs = 0.0;   // the row's P elements sit in adjacent groups of this wave: summed in the order p = 0, 1, ...
     for (int q = 0; q < m.P; ++q) rs += __shfl(ve, (L.row_lane0 + q * LPE) & 63);
     if (act && k == 0) {
@@ -513,7 +580,7 @@ extern "C" int gpk_gauss_hermite(int n, double* x_host, double* w_host) {
 // The one host-side description of a likelihood code: which (params, P) it accepts, its kernel, and the three constants the kernel
 // reads.  0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters, classes).
 namespace {
-struct LikPlan { void (*kernel)(LikVarexpArgs); double par0, par1, c0; };
+struct LikPlan { void (*kernel)(LikVarexpArgs); double par0, par1, c0; int nedge; const double* edge; };
 int lik_plan(int lik, const double* q, int P, LikPlan* o) {
   *o = LikPlan{};
   switch (lik) {
@@ -534,6 +601,26 @@ int lik_plan(int lik, const double* q, int P, LikPlan* o) {
       o->kernel = lik_multiclass_kernel;
       o->par0 = log1p(-q[0]); o->par1 = log(q[0] / (double)(P - 1)); o->c0 = o->par0 - o->par1;
       return 0;
+    case GPK_LIK_EXPONENTIAL_EXP: o->kernel = lik_varexp_kernel<GPK_LIK_EXPONENTIAL_EXP>; return 0;
+    case GPK_LIK_GAMMA_EXP:   // params = {shape}
+      if (!(q && q[0] > 0.0)) return GPK_E_ARG;
+      o->kernel = lik_varexp_kernel<GPK_LIK_GAMMA_EXP>;
+      o->par0 = q[0]; o->par1 = gpk_digamma(q[0]); o->c0 = lgamma(q[0]);
+      return 0;
+    case GPK_LIK_BETA_PROBIT:   // params = {scale}
+      if (!(q && q[0] > 0.0)) return GPK_E_ARG;
+      o->kernel = lik_varexp_kernel<GPK_LIK_BETA_PROBIT>;
+      o->par0 = q[0]; o->par1 = gpk_digamma(q[0]); o->c0 = lgamma(q[0]);
+      return 0;
+    case GPK_LIK_ORDINAL: {   // params = {sigma, n, e_0 .. e_{n-1}}: n is read before any edge
+      if (!(q && q[0] > 0.0 && q[1] >= 1.0 && q[1] <= (double)GPK_ORDINAL_MAXEDGE && q[1] == floor(q[1]))) return GPK_E_ARG;
+      const int n = (int)q[1];
+      for (int i = 0; i < n; ++i)
+        if (!(isfinite(q[2 + i]) && (i == 0 || q[2 + i] > q[1 + i]))) return GPK_E_ARG;
+      o->kernel = lik_varexp_kernel<GPK_LIK_ORDINAL>;
+      o->par0 = q[0]; o->nedge = n; o->edge = q + 2;
+      return 0;
+    }
     default: return GPK_E_UNSUPPORTED;
   }
 }
@@ -549,6 +636,8 @@ int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* pa
   GPK_TRY(lik_plan(lik, params, m.P, &plan));
   LikVarexpArgs a{};
   a.m = m; a.par0 = plan.par0; a.par1 = plan.par1; a.c0 = plan.c0;
+  a.nedge = plan.nedge;
+  for (int i = 0; i < plan.nedge; ++i) a.edge[i] = plan.edge[i];
   a.rows_out = rows_out; a.dmu_out = dmu_out; a.dvar_out = dvar_out; a.part = part; a.part1 = part1;
   const int per_wave = quad_rows_per_pass(quad_lpe(lik), m.P);   // (MultiClass: per row, not per element)
   long nb = (((long)m.rows + per_wave - 1) / per_wave + RB / 64 - 1) / (RB / 64);
@@ -572,7 +661,7 @@ extern "C" int gpk_likelihood_varexp_sum(void* stream, int lik, const double* li
   int nb = 0;
   GPK_TRY(gpk_launch_likelihood_varexp_stage1((hipStream_t)stream, lik, lik_params_host, m, rows_out, dmu_out, dvar_out, part,
                                               part + GPK_REDUCE_MAXPART, &nb));
-  // out[0] = sum VE, out[1] = sum dVE/dscale (StudentT; the others' partials are zeros)
+  // out[0] = sum VE, out[1] = sum dVE/dtheta of the code's one trainable parameter (the partials of a code without one are zeros)
   GPK_TRY(gpk_launch_final_one((hipStream_t)stream, part, nb, 1.0, 0.0, out));
   return gpk_launch_final_one((hipStream_t)stream, part + GPK_REDUCE_MAXPART, nb, 1.0, 0.0, out + 1);
 }

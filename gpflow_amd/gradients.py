@@ -911,7 +911,8 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
 
     likelihood = (name, params) of ops.likelihood_varexp_sum (Bernoulli, Poisson, StudentT) replaces the Gaussian: the variational
     expectations and the seeds r = dF/dfmean, c = dF/dfvar -- now one value per (row, latent) -- come from the quadrature kernel;
-    `noise_variance` is ignored, grads has no "noise_variance" and, for "student_t", a "likelihood_scale"."""
+    `noise_variance` is ignored, grads has no "noise_variance" and, where the likelihood class names a `device_grad_param`, a
+    "likelihood_<that name>" (StudentT and Beta: "likelihood_scale", Gamma: "likelihood_shape", Ordinal: "likelihood_sigma")."""
     M, D = Z.shape
     P = q_mu.shape[1]
     q_diag = q_sqrt.dim() == 2
@@ -945,8 +946,11 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     if likelihood is None:
         grads["noise_variance"] = seed.noise_grad(ve, s0, ssq, kd)
     grads.update({"Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": seed.r.sum().reshape(1)})
-    if likelihood is not None and likelihood[0] == "student_t":
-        grads["likelihood_scale"] = lik_out[1:2] * scale
+    if likelihood is not None:
+        from .likelihoods import device_grad_param
+        name = device_grad_param(likelihood[0])   # (the one Parameter whose derivative the kernel returns as out[1])
+        if name is not None:
+            grads["likelihood_" + name] = lik_out[1:2] * scale
     return F, grads, fwd.info
 
 

@@ -1,6 +1,7 @@
 """Likelihoods: Gaussian (gpflow/likelihoods/scalar_continuous.py:41-148) -- the conjugate case that keeps the whole ELBO on
 the dense path -- and the scalar non-conjugate ones whose variational expectations are Gauss-Hermite quadrature on the device
-(Bernoulli, Poisson: scalar_discrete.py; StudentT: scalar_continuous.py; ScalarLikelihood: base.py), and MultiClass with the
+(Bernoulli, Poisson, Ordinal: scalar_discrete.py; StudentT, Exponential, Gamma, Beta: scalar_continuous.py; ScalarLikelihood:
+base.py; Poisson, Exponential and Gamma under the exp link in the reference's closed forms), and MultiClass with the
 RobustMax link (multiclass.py), whose latents are coupled under one quadrature sum per row."""
 from __future__ import annotations
 
@@ -151,6 +152,9 @@ class ScalarLikelihood(Likelihood):
     through the square root, as in the reference."""
 
     device_lik: str = ""   # the likelihood's name in ops.LIKELIHOOD_CODES
+    # the attribute name of the ONE trainable Parameter whose derivative the kernel returns as out[1] (include/gpk.h), or None:
+    # the reverse pass reports it as grads["likelihood_" + device_grad_param]
+    device_grad_param: Optional[str] = None
 
     def device_params(self) -> tuple:
         """the lik_params_host of the C-ABI at the current parameter values"""
@@ -282,6 +286,7 @@ class StudentT(ScalarLikelihood):
     """StudentT(scale=1.0, df=3.0), scalar_continuous.py: `scale` a positive Parameter, `df` a plain float."""
 
     device_lik = "student_t"
+    device_grad_param = "scale"
 
     def __init__(self, scale=1.0, df: float = 3.0):
         self.df = float(df)
@@ -302,6 +307,155 @@ class StudentT(ScalarLikelihood):
     def _conditional_variance(self, F):
         scale = float(self.scale.numpy())
         return torch.full_like(F, scale * scale * self.df / (self.df - 2.0))
+
+
+def _exp_link_only(name: str, invlink):
+    if invlink not in (exp, np.exp):
+        raise NotImplementedError(f"{name}: only the exp link is implemented")
+    return exp
+
+
+class Exponential(ScalarLikelihood):
+    """Exponential(invlink=exp), scalar_continuous.py: log p = -log(lambda) - y / lambda, lambda = exp(f) (logdensities.py exponential).
+    Only the exp link is built; its variational expectations are the reference's closed form."""
+
+    device_lik = "exponential_exp"
+
+    def __init__(self, invlink=exp):
+        self.invlink = _exp_link_only("Exponential", invlink)
+
+    def _log_density(self, F, Y):
+        return -F - Y * torch.exp(-F)
+
+    def _conditional_mean(self, F):
+        return torch.exp(F)
+
+    def _conditional_variance(self, F):
+        return torch.exp(2.0 * F)
+
+
+class Gamma(ScalarLikelihood):
+    """Gamma(invlink=exp, shape=1.0), scalar_continuous.py: `shape` a positive Parameter, the latent sets the scale exp(f):
+    log p = -shape f - lgamma(shape) + (shape - 1) log y - y exp(-f) (logdensities.py gamma).  Only the exp link is built; its
+    variational expectations are the reference's closed form."""
+
+    device_lik = "gamma_exp"
+    device_grad_param = "shape"
+
+    def __init__(self, invlink=exp, shape=1.0):
+        self.invlink = _exp_link_only("Gamma", invlink)
+        self.shape = Parameter(shape, transform=positive())
+
+    def device_params(self) -> tuple:
+        return (float(self.shape.numpy()),)
+
+    def _log_density(self, F, Y):
+        shape = float(self.shape.numpy())
+        return -shape * F - lgamma(shape) + (shape - 1.0) * torch.log(Y) - Y * torch.exp(-F)
+
+    def _conditional_mean(self, F):
+        return float(self.shape.numpy()) * torch.exp(F)
+
+    def _conditional_variance(self, F):
+        return float(self.shape.numpy()) * torch.exp(2.0 * F)
+
+
+class Beta(ScalarLikelihood):
+    """Beta(invlink=inv_probit, scale=1.0), scalar_continuous.py: the latent sets the mean m = inv_probit(f) of a Beta density with
+    alpha = m scale, beta = scale - alpha; `scale` a positive Parameter.  The label is clipped into [1e-6, 1 - 1e-6]
+    (logdensities.py beta).  Only the probit link is built."""
+
+    device_lik = "beta_probit"
+    device_grad_param = "scale"
+
+    def __init__(self, invlink=inv_probit, scale=1.0):
+        if invlink is not inv_probit:
+            raise NotImplementedError("Beta: only the inv_probit link is implemented")
+        self.invlink = invlink
+        self.scale = Parameter(scale, transform=positive())
+
+    def device_params(self) -> tuple:
+        return (float(self.scale.numpy()),)
+
+    def _log_density(self, F, Y):
+        scale = float(self.scale.numpy())
+        alpha = inv_probit(F) * scale
+        beta = scale - alpha
+        yc = torch.clamp(Y, 1e-6, 1.0 - 1e-6)
+        return (alpha - 1.0) * torch.log(yc) + (beta - 1.0) * torch.log(1.0 - yc) + lgamma(scale) - torch.lgamma(alpha) \
+            - torch.lgamma(beta)
+
+    def _conditional_mean(self, F):
+        return inv_probit(F)
+
+    def _conditional_variance(self, F):
+        m = inv_probit(F)
+        return (m - m * m) / (float(self.scale.numpy()) + 1.0)
+
+
+class Ordinal(ScalarLikelihood):
+    """Ordinal(bin_edges), scalar_discrete.py: labels are the integers 0 .. K - 1 of K = len(bin_edges) + 1 ordered bins of the real
+    line; p(y = k | f) = inv_probit((e_k - f) / sigma) - inv_probit((e_{k-1} - f) / sigma) with e_{-1} = -inf, e_{K-1} = +inf, and
+    log p has 1e-6 added inside the logarithm.  `bin_edges` are fixed (1-D, strictly increasing, at most ops.ORDINAL_MAX_EDGES of
+    them: the kernel takes the table by value); `sigma` is a positive Parameter.  A label that is no integer in [0, K) gives NaN
+    (the choice the kernel makes, include/gpk.h: the reference would index garbage)."""
+
+    device_lik = "ordinal"
+    device_grad_param = "sigma"
+
+    def __init__(self, bin_edges):
+        edges = np.array(bin_edges, dtype=np.float64)
+        if edges.ndim != 1 or edges.size < 1:
+            raise ValueError("Ordinal: bin_edges must be a 1-D sequence of at least one edge")
+        if edges.size > ops.ORDINAL_MAX_EDGES:
+            raise ValueError(f"Ordinal: at most {ops.ORDINAL_MAX_EDGES} bin edges, got {edges.size}")
+        if not (np.isfinite(edges).all() and (np.diff(edges) > 0).all()):
+            raise ValueError("Ordinal: bin_edges must be finite and strictly increasing")
+        self.bin_edges = edges
+        self.num_bins = edges.size + 1
+        self.sigma = Parameter(1.0, transform=positive())
+
+    def device_params(self) -> tuple:
+        return (float(self.sigma.numpy()), float(self.bin_edges.size)) + tuple(float(e) for e in self.bin_edges)
+
+    def _scaled_edges(self, like: torch.Tensor):
+        """(e_k / sigma with +inf appended, the same with -inf in front), each [K]"""
+        e = torch.as_tensor(self.bin_edges / float(self.sigma.numpy()), dtype=torch.float64, device=like.device)
+        inf = torch.full((1,), float("inf"), dtype=torch.float64, device=like.device)
+        return torch.cat([e, inf]), torch.cat([-inf, e])
+
+    def _make_phi(self, F):
+        """p(y = k | f) for every bin as a last axis [..., K]; every row sums to 1 - 2e-3 (the two outermost jitters)"""
+        F = ops.to_device(F)
+        left, right = self._scaled_edges(F)
+        fs = (F / float(self.sigma.numpy()))[..., None]
+        return inv_probit(left - fs) - inv_probit(right - fs)
+
+    def _log_density(self, F, Y):
+        left, right = self._scaled_edges(F)
+        ok = (Y >= 0) & (Y <= self.bin_edges.size) & (Y == torch.floor(Y))
+        idx = torch.where(ok, Y, torch.zeros_like(Y)).long()
+        fs = F / float(self.sigma.numpy())
+        lp = torch.log(inv_probit(left[idx] - fs) - inv_probit(right[idx] - fs) + 1e-6)
+        return lp + torch.where(ok, torch.zeros_like(Y), torch.full_like(Y, float("nan")))
+
+    def _conditional_mean(self, F):
+        phi = self._make_phi(F)
+        return phi @ torch.arange(self.num_bins, dtype=phi.dtype, device=phi.device)
+
+    def _conditional_variance(self, F):
+        phi = self._make_phi(F)
+        k = torch.arange(self.num_bins, dtype=phi.dtype, device=phi.device)
+        mean = phi @ k
+        return phi @ (k * k) - mean * mean
+
+
+def device_grad_param(device_lik: str) -> Optional[str]:
+    """the `device_grad_param` of the ScalarLikelihood class that runs as `device_lik` (None: no such class, or no such Parameter)"""
+    for cls in ScalarLikelihood.__subclasses__():
+        if cls.device_lik == device_lik:
+            return cls.device_grad_param
+    return None
 
 
 class RobustMax:

@@ -325,7 +325,6 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         touches the device.
         For minibatch training keep the variables on the device instead: training.SVGPTrainer."""
         from .. import gradients
-        from ..likelihoods import StudentT
         from . import reverse
         lik = self.likelihood
         quad = isinstance(lik, (ScalarLikelihood, MultiClass))
@@ -362,7 +361,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         q_pairs = [(self.q_mu, np.concatenate([h["q_mu"] for h in hosts], axis=1)),
                    (self.q_sqrt, np.concatenate([h["q_sqrt"] for h in hosts], axis=0))]
         if quad:
-            lik_pairs = [(lik.scale, hosts[0]["likelihood_scale"])] if isinstance(lik, StudentT) else []
+            name = getattr(lik, "device_grad_param", None)   # (the Parameter the kernel's out[1] differentiates, if the class has one)
+            lik_pairs = [(getattr(lik, name), hosts[0]["likelihood_" + name])] if name else []
         else:
             # (the latents share the likelihood: their per-row dF/d sigma_n^2 add up before the noise Function's reverse pass)
             g_noise = total("noise_variance")

@@ -533,18 +533,34 @@ def gaussian_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[to
     return out, fvar
 
 
-LIKELIHOOD_CODES = {"bernoulli_probit": 1, "poisson_exp": 2, "student_t": 3, "multiclass_robustmax": 4}   # include/gpk.h: GPK_LIK_*
-_LIKELIHOOD_NPAR = {"bernoulli_probit": 0, "poisson_exp": 1, "student_t": 2, "multiclass_robustmax": 1}
+LIKELIHOOD_CODES = {"bernoulli_probit": 1, "poisson_exp": 2, "student_t": 3, "multiclass_robustmax": 4,   # include/gpk.h: GPK_LIK_*
+                    "exponential_exp": 8, "gamma_exp": 9, "beta_probit": 10, "ordinal": 11}               # (5 - 7: unassigned)
+_LIKELIHOOD_NPAR = {"bernoulli_probit": 0, "poisson_exp": 1, "student_t": 2, "multiclass_robustmax": 1,
+                    "exponential_exp": 0, "gamma_exp": 1, "beta_probit": 1}   # ("ordinal": see _lik_npar)
 ROW_LIKELIHOODS = ("multiclass_robustmax",)   # the latents of a row are coupled: Y is ONE column of labels, P >= 2 classes
+ORDINAL_MAX_EDGES = 15
+
+
+def _lik_npar(lik: str, params) -> int:
+    """how many parameters the code takes: a fixed count, or for "ordinal" (sigma, n, e_0 .. e_{n-1}) the 2 + n its own second
+    entry announces (n an integer in 1 .. ORDINAL_MAX_EDGES; -1, which no length equals, when it is not)"""
+    if lik != "ordinal":
+        return _LIKELIHOOD_NPAR[lik]
+    if len(params) < 2 or not (params[1] == int(params[1]) if np.isfinite(params[1]) else False) \
+            or not 1 <= int(params[1]) <= ORDINAL_MAX_EDGES:
+        return -1
+    return 2 + int(params[1])
 
 
 def _lik_args(lik: str, params):
-    """(code, host array | None) of the (lik, lik_params_host) pair of the C-ABI: params is () for "bernoulli_probit", (binsize,)
-    for "poisson_exp", (scale, df) for "student_t", (epsilon,) for "multiclass_robustmax"."""
+    """(code, host array | None) of the (lik, lik_params_host) pair of the C-ABI: params is () for "bernoulli_probit" and
+    "exponential_exp", (binsize,) for "poisson_exp", (scale, df) for "student_t", (epsilon,) for "multiclass_robustmax", (shape,) for
+    "gamma_exp", (scale,) for "beta_probit", (sigma, n, e_0, ..., e_{n-1}) for "ordinal" (n <= 15 bin edges).  The VALUES are the
+    library's to judge (GPK_E_ARG)."""
     if lik not in LIKELIHOOD_CODES:
         raise ValueError(f"unknown likelihood {lik!r}: one of {sorted(LIKELIHOOD_CODES)}")
     params = [float(v) for v in params]
-    if len(params) != _LIKELIHOOD_NPAR[lik]:
+    if len(params) != _lik_npar(lik, params):
         raise ValueError(f"likelihood {lik!r}: wrong number of parameters ({len(params)})")
     return LIKELIHOOD_CODES[lik], (_lib.host_doubles(params) if params else None)
 
@@ -626,7 +642,7 @@ def likelihood_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[
                           want_fvar: bool = False, want_rows: bool = False, want_grads: bool = False):
     """Gauss-Hermite variational expectations of a non-Gaussian scalar likelihood (gpk_likelihood_varexp_sum), fvar = knn - s0 + ssq.
     Returns (out [2], rows | None, dmu | None, dvar | None, fvar | None): out[0] = sum over rows and outputs, out[1] = its
-    derivative w.r.t. the StudentT scale (0 otherwise); rows [rows] = sums over the outputs; dmu, dvar [rows, P] = d/dfmean,
+    derivative w.r.t. the code's one trainable parameter (StudentT scale, Gamma shape, Beta scale, Ordinal sigma; 0 otherwise); rows [rows] = sums over the outputs; dmu, dvar [rows, P] = d/dfmean,
     d/dfvar of every term.  "multiclass_robustmax" (params = (epsilon,)): Y is ONE column of class labels, the P >= 2 latents of a
     row are its classes, rows [rows] is the row's value and dmu, dvar its derivatives w.r.t. all P means and variances."""
     lib = _lib.load()

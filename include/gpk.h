@@ -280,7 +280,8 @@ int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, const doubl
  * likelihoods/base.py, through quadrature/gauss_hermite.py with DEFAULT_NUM_GAUSS_HERMITE_POINTS = 20):
  *   fvar[b,p] = knn - s0[b | p,b] + ssq[p,b],   mu = fmean[b,p] + mean_const,   sum_h (w_h / sqrt pi) g(mu + sqrt(2 fvar) x_h)
  *   VE[b,p]   = that sum with g(f) = log p(Y[b,p] | f)
- *   out[0] = sum_b sum_p VE[b,p];   out[1] = sum_b sum_p dVE/dscale (GPK_LIK_STUDENT_T; 0 for the others)
+ *   out[0] = sum_b sum_p VE[b,p];   out[1] = sum_b sum_p dVE/dtheta, theta the code's one trainable parameter
+ *                                     (GPK_LIK_STUDENT_T: scale; exactly 0 for a code without one; the later codes: see below)
  *   rows_out [rows]   = sum_p VE[b,p]                      (what variational_expectations returns)
  *   dmu_out, dvar_out [rows,P] = dVE/dfmean, dVE/dfvar: the exact derivatives of the quadrature sum,
  *                       sum_h (w_h / sqrt pi) g'(f_h)  and  sum_h (w_h / sqrt pi) g'(f_h) x_h / sqrt(2 fvar)
@@ -314,11 +315,52 @@ int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, const doubl
  *   Non-finite inputs: a NaN in fmean[b,:] or fvar[b,:] reaches row b's outputs and out[0], and no other row: the row is the
  *   unit here, not the element.
  *   Deterministic: four lanes per (row, class) group, the product over the row's classes and the sums over them are fixed-order
- *   shuffle loops inside one wave, then the two-stage reduction; no floating-point atomics. */
+ *   shuffle loops inside one wave, then the two-stage reduction; no floating-point atomics.
+ *
+ * Four more SCALAR codes (likelihoods/scalar_continuous.py Exponential, Gamma, Beta; scalar_discrete.py Ordinal; logdensities.py).
+ * Operands, optional outputs, rows = 0, P <= 16, the unclamped fvar = knn - s0 + ssq and the y - y rule for a non-finite label are
+ * those of the scalar codes above.  For every code out[1] is "the sum of dVE/dtheta for the code's ONE trainable parameter"
+ * (StudentT: scale, Gamma: shape, Beta: scale, Ordinal: sigma) and exactly 0 where there is none.
+ * Notation: mu = fmean + mean_const, v = fvar, e = exp(-mu + v / 2).
+ *   GPK_LIK_EXPONENTIAL_EXP   no parameters (NULL); closed form (no quadrature), one lane per element as Poisson:
+ *                             VE = -mu - y e,  dmu = -1 + y e,  dvar = -y e / 2,  out[1] = 0
+ *   GPK_LIK_GAMMA_EXP         params = {shape}, shape > 0; closed form:
+ *                             VE = -shape mu - lgamma(shape) + (shape - 1) log y - y e,  dmu = -shape + y e,  dvar = -y e / 2,
+ *                             dVE/dshape = -mu - psi(shape) + log y.  The host computes lgamma(shape) and psi(shape) once.
+ *                             y <= 0 goes through log as it comes (-Inf or NaN, as the reference): no clamp.
+ *   GPK_LIK_BETA_PROBIT       params = {scale}, scale > 0; 20-node quadrature, four lanes per element:
+ *                             m = 0.5 erfc(-f / sqrt 2) (1 - 2e-3) + 1e-3,  alpha = m scale,  beta = scale - alpha,
+ *                             yc = min(max(y, 1e-6), 1 - 1e-6)  (comparisons: a NaN label stays NaN),
+ *                             g = (alpha - 1) log yc + (beta - 1) log(1 - yc) + lgamma(scale) - lgamma(alpha) - lgamma(beta)
+ *                             g'(f) = scale 0.998 phi(f) (log yc - log(1 - yc) - psi(alpha) + psi(beta))
+ *                             dg/dscale = m log yc + (1 - m) log(1 - yc) + psi(scale) - m psi(alpha) - (1 - m) psi(beta)
+ *   GPK_LIK_ORDINAL           params = {sigma, n, e_0 ... e_{n-1}}: sigma > 0, 1 <= n <= 15 (n an integer held in a double), the n
+ *                             edges finite and strictly increasing; anything else, or NULL, is GPK_E_ARG.  The label y is an
+ *                             integer in [0, n]; with e_{-1} = -Inf and e_n = +Inf:
+ *                             zl = (e_y - f) / sigma,  zr = (e_{y-1} - f) / sigma,  D = 0.998 (Phi(zl) - Phi(zr)),  g = log(D + 1e-6)
+ *                             (the jitters of the two inv_probit cancel).  Phi(zl) - Phi(zr) is taken through erfc on the side
+ *                             where both terms are small -- (erfc(zr / sqrt 2) - erfc(zl / sqrt 2)) / 2 when zr >= 0, else
+ *                             (erfc(-zl / sqrt 2) - erfc(-zr / sqrt 2)) / 2 -- so that a far tail keeps its relative accuracy.  An
+ *                             infinite edge contributes Phi = 0 or 1 and a zero density term (0 * Inf is never formed).
+ *                             g'(f) = -0.998 (phi(zl) - phi(zr)) / (sigma (D + 1e-6))
+ *                             dg/dsigma = -0.998 (zl phi(zl) - zr phi(zr)) / (sigma (D + 1e-6))
+ *                             A label that is not an integer in [0, n] -- NaN and +-Inf included -- makes that ELEMENT's outputs
+ *                             NaN (its entries of dmu_out / dvar_out, its row of rows_out, out[0] and out[1]) and affects nothing
+ *                             else.  This is the MultiClass choice: the reference would index garbage.
+ *   Codes 10 and 11: dmu = sum_h (w_h / sqrt pi) g'(f_h), dvar = sum_h (w_h / sqrt pi) g'(f_h) x_h / sqrt(2 v), the exact derivatives
+ *   of the sum, as for Bernoulli and StudentT.  psi is gpk_digamma (csrc/digamma.h: its absolute error bound is derived there).
+ *
+ * Codes: 0 is the Gaussian stage of gpk_svgp_elbo_shard and no likelihood code.  5, 6 and 7 are unassigned and answer
+ * GPK_E_UNSUPPORTED: they are kept for links of the codes 1 .. 4 should those be built (Bernoulli with the logistic link, Poisson
+ * with softplus, MultiClass with Softmax), so that a family's links stay next to each other; callers and tests rely on 5 being unknown. */
 #define GPK_LIK_BERNOULLI_PROBIT 1
 #define GPK_LIK_POISSON_EXP 2
 #define GPK_LIK_STUDENT_T 3
 #define GPK_LIK_MULTICLASS_ROBUSTMAX 4
+#define GPK_LIK_EXPONENTIAL_EXP 8
+#define GPK_LIK_GAMMA_EXP 9
+#define GPK_LIK_BETA_PROBIT 10
+#define GPK_LIK_ORDINAL 11
 int gpk_likelihood_varexp_sum(void* stream, int lik, const double* lik_params_host, const double* Y, long ldy,
                               const double* fmean, int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
                               const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
