@@ -10,8 +10,7 @@ include/gpk.h ("dot-product kernels"):
   * the row diagonal sums the same chain: bit for bit the diagonal of the symmetric build;
   * the tail is the three formulas of the header.
 What the device refuses (GPK_E_ARG / GPK_E_UNSUPPORTED, or the ValueError / NotImplementedError ops raises before it) is an
-AssertionError here.  Patched after fake_ops, fake_likelihood_ops, fake_kernel_ops and fake_periodic_ops.  The product never imports
-this file.
+AssertionError here.  The product never imports this file.
 """
 from __future__ import annotations
 

@@ -7,8 +7,8 @@
   * out = [sum VE, d sum VE / d s2]; dgmu = ((Y - f) W) / s2; dW = ((Y - f)^T gmean - W .* colsum(gvar)) / s2;
   * rows = 0 gives out = [0, 0] and dW = 0;
   * what the device refuses (GPK_E_ARG) is an AssertionError here.
-The fused shard sits on the pieces of fake_ops.svgp_elbo_shard_sep: that function runs with its `gaussian_varexp_sum` stage replaced
-by the mixing stage for the duration of the call.  The names are NOT added to fake_ops.  The product never imports this file.
+The fused shard is fake_ops' per-latent chain ending in the mixing stage: the stage is an argument of `fake_ops._shard_sep`.  The
+names are NOT added to fake_ops.  The product never imports this file.
 """
 from __future__ import annotations
 
@@ -74,21 +74,13 @@ def svgp_elbo_lcm_workspace(m, rows, d, L, P):
 
 def svgp_elbo_shard_lcm(Z, Xb, Yb, q_mu, q_sqrt, W, *, variances, lengthscales, families, noise_variance, jitter, mean_const=0.0,
                         ws=None, out=None, info=None):
-    """fake_ops.svgp_elbo_shard_sep over the L latents with the mixing stage in the place of its Gaussian stage"""
+    """fake_ops' per-latent chain over the L latents, ending in the mixing stage"""
     W = _weights(W, q_mu.shape[1])
     assert Yb.shape[1] == W.shape[0], (Yb.shape, W.shape)
     assert float(noise_variance) > 0.0
 
-    def stage(Y, fmean, *, s0, ssq, knn, noise_variance, mean_const=0.0, s0_per_latent=False, want_fvar=False):
-        res = mixed_gaussian_varexp_sum(Y, fmean, W, s0=s0, ssq=ssq, knn=knn, noise_variance=noise_variance, mean_const=mean_const,
-                                        s0_per_latent=s0_per_latent)
-        return res[0][0:1], None
+    def stage(Y, fmean, **kw):
+        return mixed_gaussian_varexp_sum(Y, fmean, W, noise_variance=noise_variance, **kw)[0][0:1], None
 
-    saved = fake_ops.gaussian_varexp_sum
-    fake_ops.gaussian_varexp_sum = stage
-    try:
-        return fake_ops.svgp_elbo_shard_sep(Z, Xb, Yb, q_mu, q_sqrt, variances=variances, lengthscales=lengthscales, families=families,
-                                            noise_variance=noise_variance, jitter=jitter, mean_const=mean_const, ws=ws, out=out,
-                                            info=info)
-    finally:
-        fake_ops.gaussian_varexp_sum = saved
+    return fake_ops._shard_sep(Z, Xb, Yb, q_mu, q_sqrt, stage, variances=variances, lengthscales=lengthscales, families=families,
+                               jitter=jitter, mean_const=mean_const, out=out)

@@ -1,12 +1,24 @@
 """CPU emulation of the likelihood primitives of `gpflow_amd.ops` -- TEST INFRASTRUCTURE ONLY, the companion of tests/fake_ops.py
 for `gauss_hermite`, `likelihood_varexp_sum` and `svgp_elbo_shard_lik` (include/gpk.h: gpk_gauss_hermite,
-gpk_likelihood_varexp_sum, gpk_svgp_elbo_shard_lik).  NumPy fp64, written from the stated contract:
+gpk_likelihood_varexp_sum, gpk_svgp_elbo_shard_lik) and all eight codes of `ops.LIKELIHOOD_CODES`: one row of `LIKELIHOODS` each.
+NumPy fp64 with scipy's erfc / gammaln / digamma, written from the stated contract:
 
-  * fvar = knn - s0 + ssq, mu = fmean + mean_const; no clamp of fvar (a negative value gives NaN through the square root);
-  * "bernoulli_probit" and "student_t": sum_h (w_h / sqrt pi) g(mu + sqrt(2 fvar) x_h) over hermgauss(20), with the exact
-    derivatives of that sum w.r.t. mu and fvar; "poisson_exp": the closed form;
-  * a non-finite label adds y - y to every output of its element; NaN / Inf in fmean / fvar travel through the arithmetic;
+  * fvar = knn - s0 + ssq, mu = fmean + mean_const; no clamp of fvar (a negative value gives NaN through the square root); fvar is
+    returned unclamped;
+  * "bernoulli_probit", "student_t", "beta_probit", "ordinal": sum_h (w_h / sqrt pi) g(mu + sqrt(2 fvar) x_h) over hermgauss(20), with
+    the exact derivatives of that sum w.r.t. mu and fvar; "poisson_exp", "exponential_exp", "gamma_exp": the closed forms, the last
+    two with e = exp(-mu + fvar / 2);
+  * out[1] = the sum of dVE/dtheta of the code's one trainable parameter (scale of "student_t", shape, scale, sigma), 0.0 for the
+    codes without one;
+  * a non-finite label adds y - y to every output of its element; NaN / Inf in fmean / fvar travel through the arithmetic; an Ordinal
+    label that is no integer in [0, n] makes its element's outputs NaN (out[1] included);
+  * "multiclass_robustmax" is the one row-coupled code: P = number of classes, 2 <= P <= 16; params = (epsilon,), 0 < epsilon < 1; Y
+    has ONE column, the label of the row.  The value clamps 2 fvar_y and fvar_k at 1e-10 by COMPARISON (a NaN stays NaN), and where a
+    clamp is active the derivative w.r.t. that variance is exactly 0.  VE_b = p log(1 - eps) + (1 - p) log(eps / (P - 1)),
+    p = sum_h (w_h / sqrt pi) prod_{k != y} c_kh, with the exact derivatives of that sum w.r.t. all P means and variances of the row;
+    out = [sum_b VE_b, 0]; a label that is no integer in [0, P) makes every output of its row NaN, and nothing else;
   * what the device refuses (GPK_E_ARG / GPK_E_UNSUPPORTED) is an AssertionError here.
+The fused shard is fake_ops' shared-kernel chain ending in the quadrature stage: the stage is an argument of `fake_ops._shard`.
 The product never imports this file.
 """
 from __future__ import annotations
@@ -17,12 +29,7 @@ import torch
 
 import fake_ops
 
-LIKELIHOOD_CODES = {"bernoulli_probit": 1, "poisson_exp": 2, "student_t": 3}
-_NPAR = {"bernoulli_probit": 0, "poisson_exp": 1, "student_t": 2}
-
-
-def _np(t):
-    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
+_np = fake_ops._np
 
 
 def gauss_hermite(n=20):
@@ -30,19 +37,190 @@ def gauss_hermite(n=20):
     return np.polynomial.hermite.hermgauss(20)
 
 
-def _check_lik(lik, params):
-    assert lik in LIKELIHOOD_CODES, lik
-    params = [float(v) for v in params]
-    assert len(params) == _NPAR[lik], (lik, params)
-    assert all(v > 0.0 for v in params), params    # binsize / scale / df: GPK_E_ARG
+# ---- parameter checks: check(params, P) -> params
+def _positive(n):
+    def check(params, P):
+        assert len(params) == n, params                # a missing binsize / scale / df / shape: GPK_E_ARG
+        assert all(v > 0.0 for v in params), params    # GPK_E_ARG
+        return params
+    return check
+
+
+def _check_ordinal(params, P):
+    assert len(params) >= 2 and params[0] > 0.0, params            # sigma
+    n = params[1]
+    assert n == np.floor(n) and 1 <= n <= 15, params               # 1 .. 15 edges
+    assert len(params) == 2 + int(n), params
+    e = np.asarray(params[2:])
+    assert np.isfinite(e).all() and (np.diff(e) > 0).all(), params  # finite, strictly increasing
     return params
+
+
+def _check_multiclass(params, P):
+    assert len(params) == 1, params                # a missing epsilon: GPK_E_ARG
+    assert 0.0 < params[0] < 1.0, params           # GPK_E_ARG
+    assert 2 <= P <= 16, P                         # GPK_E_ARG
+    return params
+
+
+# ---- evaluations: evaluate(par, y, mu, fv) -> (VE, dVE/dmu, dVE/dfvar, dVE/dtheta), element by element
+def _poisson_exp(par, y, mu, fv):
+    ynan = y - y
+    e = np.exp(mu + 0.5 * fv) * par[0]
+    ve = y * mu - e - sps.gammaln(y + 1.0) + y * np.log(par[0])
+    return ve + ynan, y - e + ynan, -0.5 * e + ynan, np.zeros_like(mu)
+
+
+def _exponential_exp(par, y, mu, fv):
+    ynan = y - y
+    ye = y * np.exp(-mu + 0.5 * fv)
+    return -mu - ye + ynan, ye - 1.0 + ynan, -0.5 * ye + ynan, np.zeros_like(mu)
+
+
+def _gamma_exp(par, y, mu, fv):
+    ynan = y - y
+    ye = y * np.exp(-mu + 0.5 * fv)
+    shape = par[0]
+    ve = -shape * mu - sps.gammaln(shape) + (shape - 1.0) * np.log(y) - ye
+    return ve + ynan, ye - shape + ynan, -0.5 * ye + ynan, np.log(y) - mu - sps.digamma(shape)
+
+
+def _phi(z):
+    return np.exp(-0.5 * z * z) / np.sqrt(2.0 * np.pi)
+
+
+def _quadrature(point):
+    """a code given at the 20 nodes: point(par, y, f) -> (g, dg/df, dg/dtheta or None, the NaN mask of its invalid labels or None)"""
+    def evaluate(par, y, mu, fv):
+        x, w = gauss_hermite(20)
+        wn = w / np.sqrt(np.pi)
+        sd = np.sqrt(2.0 * fv)
+        f = mu[..., None] + sd[..., None] * x
+        g, gp, gt, invalid = point(par, y, f)
+        ynan = y - y if invalid is None else invalid
+        ve = (g * wn).sum(-1)
+        dmu = (gp * wn).sum(-1)
+        dvar = (gp * x * wn).sum(-1) / sd
+        dth = np.zeros_like(mu) if gt is None else (gt * wn).sum(-1)
+        if invalid is not None:
+            dth = dth + invalid
+        return ve + ynan, dmu + ynan, dvar + ynan, dth
+    return evaluate
+
+
+def _bernoulli_probit(par, y, f):
+    sgn = np.where(y == 1.0, 1.0, -1.0)[..., None]
+    q = 0.5 * sps.erfc(-sgn * f / np.sqrt(2.0)) * (1.0 - 2e-3) + 1e-3
+    return np.log(q), sgn * (1.0 - 2e-3) * np.exp(-0.5 * f * f) / np.sqrt(2.0 * np.pi) / q, None, None
+
+
+def _student_t(par, y, f):
+    scale, df = par
+    r = (y[..., None] - f) / scale
+    c0 = sps.gammaln(0.5 * (df + 1.0)) - sps.gammaln(0.5 * df) - 0.5 * (np.log(scale * scale) + np.log(df) + np.log(np.pi))
+    g = c0 - 0.5 * (df + 1.0) * np.log1p(r * r / df)
+    gp = (df + 1.0) * r / (scale * (df + r * r))
+    return g, gp, ((df + 1.0) * r * r / (df + r * r) - 1.0) / scale, None
+
+
+def _beta_probit(par, y, f):
+    scale = par[0]
+    m = 0.5 * sps.erfc(-f / np.sqrt(2.0)) * (1.0 - 2e-3) + 1e-3
+    al = m * scale
+    be = scale - al
+    yc = np.where(y < 1e-6, 1e-6, np.where(y > 1.0 - 1e-6, 1.0 - 1e-6, y))[..., None]
+    ly, l1 = np.log(yc), np.log(1.0 - yc)
+    pa, pb = sps.digamma(al), sps.digamma(be)
+    g = (al - 1.0) * ly + (be - 1.0) * l1 + sps.gammaln(scale) - sps.gammaln(al) - sps.gammaln(be)
+    gp = scale * (1.0 - 2e-3) * _phi(f) * (ly - l1 - pa + pb)
+    gt = m * ly + (1.0 - m) * l1 + sps.digamma(scale) - m * pa - (1.0 - m) * pb
+    return g, gp, gt, None
+
+
+def _ordinal(par, y, f):
+    sigma, n = par[0], int(par[1])
+    ok = (y >= 0) & (y <= n) & (y == np.floor(y))
+    yi = np.where(ok, y, 0).astype(np.int64)
+    left = np.concatenate([par[2:], [np.inf]])[yi][..., None]
+    right = np.concatenate([[-np.inf], par[2:]])[yi][..., None]
+    zl, zr = (left - f) / sigma, (right - f) / sigma
+    up = zr >= 0
+    za, zb = np.where(up, zr, -zl), np.where(up, zl, -zr)
+    D = (1.0 - 2e-3) * 0.5 * (sps.erfc(za / np.sqrt(2.0)) - sps.erfc(zb / np.sqrt(2.0)))
+    pl = np.where(np.isfinite(left), _phi(zl), 0.0)
+    pr = np.where(np.isfinite(right), _phi(zr), 0.0)
+    tl = np.where(np.isfinite(left), zl * pl, 0.0)
+    tr = np.where(np.isfinite(right), zr * pr, 0.0)
+    den = sigma * (D + 1e-6)
+    return np.log(D + 1e-6), -(1.0 - 2e-3) * (pl - pr) / den, -(1.0 - 2e-3) * (tl - tr) / den, np.where(ok, 0.0, np.nan)
+
+
+def _clamp(v, lo):
+    """max(v, lo) as a comparison: NaN stays NaN.  Returns (clamped, clamp active)"""
+    active = v < lo
+    return np.where(active, lo, v), active
+
+
+def _multiclass_robustmax(par, y, mu, fv):
+    """row by row: VE [rows], the derivatives [rows, P]"""
+    eps = par[0]
+    rows, P = mu.shape
+    y = y[:, 0] if rows else np.zeros(0)
+    ok = (y >= 0) & (y < P) & (y == np.floor(y))
+    yi = np.where(ok, y, 0).astype(np.int64)
+    ynan = np.where(ok, 0.0, np.nan)
+    on = np.zeros((rows, P), dtype=bool)
+    on[np.arange(rows), yi] = True
+    x, w = gauss_hermite(20)
+    wn = w / np.sqrt(np.pi)
+    mu_y, fv_y = mu[on], fv[on]
+    tv, cy = _clamp(2.0 * fv_y, 1e-10)
+    vk, ck = _clamp(fv, 1e-10)
+    s, sdk = np.sqrt(tv), np.sqrt(vk)
+    X = mu_y[:, None] + s[:, None] * x                                             # [rows, H]
+    d = (X[:, None, :] - mu[:, :, None]) / sdk[:, :, None]                         # [rows, P, H]
+    c = 0.5 * sps.erfc(-d / np.sqrt(2.0)) * (1.0 - 2e-4) + 1e-4
+    t = (1.0 - 2e-4) * np.exp(-0.5 * d * d) / np.sqrt(2.0 * np.pi) / (sdk[:, :, None] * c)
+    c = np.where(on[:, :, None], 1.0, c)
+    t = np.where(on[:, :, None], 0.0, t)
+    wp = np.prod(c, axis=1) * wn                                                   # [rows, H]
+    p = wp.sum(-1)
+    l1, l0 = np.log1p(-eps), np.log(eps / (P - 1))
+    kap = l1 - l0
+    ve = p * l1 + (1.0 - p) * l0 + ynan
+    a1 = (wp[:, None, :] * t).sum(-1)                                              # [rows, P]
+    a2 = (wp[:, None, :] * t * d).sum(-1)
+    a3 = (wp[:, None, :] * t * x).sum(-1)
+    dmu = np.where(on, kap * a1.sum(1, keepdims=True), -kap * a1)
+    dvar_y = np.where(cy, 0.0, kap * a3.sum(1) / s)
+    dvar_k = np.where(ck, 0.0, -kap * a2 / (2.0 * sdk))
+    dvar = np.where(on, dvar_y[:, None], dvar_k)
+    return ve, dmu + ynan[:, None], dvar + ynan[:, None], 0.0
+
+
+# name of ops.LIKELIHOOD_CODES -> (the check of params, the evaluation); include/gpk.h: GPK_LIK_BERNOULLI_PROBIT .. GPK_LIK_ORDINAL
+LIKELIHOODS = {
+    "bernoulli_probit": (_positive(0), _quadrature(_bernoulli_probit)),
+    "poisson_exp": (_positive(1), _poisson_exp),                              # binsize
+    "student_t": (_positive(2), _quadrature(_student_t)),                     # scale, df
+    "multiclass_robustmax": (_check_multiclass, _multiclass_robustmax),       # epsilon; the one row-coupled code
+    "exponential_exp": (_positive(0), _exponential_exp),
+    "gamma_exp": (_positive(1), _gamma_exp),                                  # shape
+    "beta_probit": (_positive(1), _quadrature(_beta_probit)),                 # scale
+    "ordinal": (_check_ordinal, _quadrature(_ordinal)),                       # sigma, n, n edges
+}
+
+
+def _check_lik(lik, params, P):
+    assert lik in LIKELIHOODS, lik
+    return LIKELIHOODS[lik][0]([float(v) for v in params], P)
 
 
 def likelihood_varexp_sum(Y, fmean, *, s0, ssq, knn, lik, params=(), mean_const=0.0, s0_per_latent=False, want_fvar=False,
                           want_rows=False, want_grads=False):
     rows, P = fmean.shape
     assert 1 <= P <= 16, P    # gpk_likelihood_varexp_sum: GPK_E_ARG outside 1 .. 16 latents
-    par = _check_lik(lik, params)
+    par = _check_lik(lik, params, P)
     knn = np.broadcast_to(np.atleast_1d(np.asarray(knn, dtype=np.float64)), (P,))
     fv = np.tile(knn[None, :], (rows, 1)).astype(np.float64)
     if s0 is not None:
@@ -52,54 +230,22 @@ def likelihood_varexp_sum(Y, fmean, *, s0, ssq, knn, lik, params=(), mean_const=
     mu = _np(fmean) + mean_const
     y = _np(Y)[:, :P]
     with np.errstate(all="ignore"):
-        ynan = y - y
-        dsc = np.zeros_like(mu)
-        if lik == "poisson_exp":
-            e = np.exp(mu + 0.5 * fv) * par[0]
-            ve = y * mu - e - sps.gammaln(y + 1.0) + y * np.log(par[0])
-            dmu, dvar = y - e, -0.5 * e
-        else:
-            x, w = gauss_hermite(20)
-            wn = w / np.sqrt(np.pi)
-            sd = np.sqrt(2.0 * fv)
-            f = mu[..., None] + sd[..., None] * x
-            if lik == "bernoulli_probit":
-                sgn = np.where(y == 1.0, 1.0, -1.0)[..., None]
-                q = 0.5 * sps.erfc(-sgn * f / np.sqrt(2.0)) * (1.0 - 2e-3) + 1e-3
-                g = np.log(q)
-                gp = sgn * (1.0 - 2e-3) * np.exp(-0.5 * f * f) / np.sqrt(2.0 * np.pi) / q
-            else:
-                scale, df = par
-                r = (y[..., None] - f) / scale
-                c0 = sps.gammaln(0.5 * (df + 1.0)) - sps.gammaln(0.5 * df) - 0.5 * (np.log(scale * scale) + np.log(df) + np.log(np.pi))
-                g = c0 - 0.5 * (df + 1.0) * np.log1p(r * r / df)
-                gp = (df + 1.0) * r / (scale * (df + r * r))
-                dsc = ((((df + 1.0) * r * r / (df + r * r) - 1.0) / scale) * wn).sum(-1)
-            ve = (g * wn).sum(-1)
-            dmu = (gp * wn).sum(-1)
-            dvar = (gp * x * wn).sum(-1) / sd
-        ve, dmu, dvar = ve + ynan, dmu + ynan, dvar + ynan
-        out = torch.tensor([ve.sum(), dsc.sum()], dtype=torch.float64)
+        ve, dmu, dvar, dth = LIKELIHOODS[lik][1](par, y, mu, fv)
+        out = torch.tensor([ve.sum(), np.sum(dth)], dtype=torch.float64)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))   # noqa: E731
-    return (out, t(ve.sum(1)) if want_rows else None, t(dmu) if want_grads else None, t(dvar) if want_grads else None,
-            t(fv) if want_fvar else None)
+    return (out, t(ve.sum(1) if ve.ndim == 2 else ve) if want_rows else None, t(dmu) if want_grads else None,
+            t(dvar) if want_grads else None, t(fv) if want_fvar else None)
 
 
 def svgp_elbo_shard_lik(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, lik, params=(), jitter, mean_const=0.0,
-                        family="SquaredExponential", ws=None, out=None, info=None, whiten=True):
-    """gpk_svgp_elbo_shard_lik is gpk_svgp_elbo_shard with another last stage; so is its emulation: fake_ops.svgp_elbo_shard
-    runs with its `gaussian_varexp_sum` replaced by the quadrature stage for the duration of the call."""
-    _check_lik(lik, params)
+                        family="SquaredExponential", alpha=None, ws=None, out=None, info=None, whiten=True):
+    """gpk_svgp_elbo_shard_lik is gpk_svgp_elbo_shard with another last stage; so is its emulation"""
+    _check_lik(lik, params, q_mu.shape[1])
+    assert lik != "multiclass_robustmax" or Yb.shape[1] == 1, Yb.shape
 
-    def stage(Y, fmean, *, s0, ssq, knn, noise_variance, mean_const=0.0, s0_per_latent=False, want_fvar=False):
-        res = likelihood_varexp_sum(Y, fmean, s0=s0, ssq=ssq, knn=knn, lik=lik, params=params, mean_const=mean_const,
-                                    s0_per_latent=s0_per_latent, want_fvar=want_fvar)
+    def stage(Y, fmean, **kw):
+        res = likelihood_varexp_sum(Y, fmean, lik=lik, params=params, **kw)
         return res[0][0:1], res[4]
 
-    saved = fake_ops.gaussian_varexp_sum
-    fake_ops.gaussian_varexp_sum = stage
-    try:
-        return fake_ops.svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, variance=variance, lengthscales=lengthscales, noise_variance=1.0,
-                                        jitter=jitter, mean_const=mean_const, family=family, ws=ws, out=out, info=info, whiten=whiten)
-    finally:
-        fake_ops.gaussian_varexp_sum = saved
+    return fake_ops._shard(Z, Xb, Yb, q_mu, q_sqrt, stage, variance=variance, lengthscales=lengthscales, jitter=jitter,
+                           mean_const=mean_const, family=family, alpha=alpha, out=out, whiten=whiten)

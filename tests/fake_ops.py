@@ -9,6 +9,19 @@ reproduces the CONTRACT of each primitive, including what the HIP kernels do NOT
   * gemm_nt(c_lower): 128 x 128 tiles strictly above the diagonal are skipped (left at their initial value);
   * potrf_ reads only the lower triangle of the square block and leaves / zeroes the upper one;
   * transpose(mode=1) keeps only the lower triangle of its input.
+The covariance builders (`kernel_matrix`, `kernel_matrix_hadamard`, `kernel_matrix_combine`) and the fused wrappers that take
+`family` know the eight families of include/gpk.h (next to the family codes) and the keyword `alpha`:
+  * the Materns: r = sqrt(max(r2, 1e-36)); -2 dk/dr2 is 0 where r2 <= 1e-36 (a NaN r2 is not clamped);
+  * Exponential: variance exp(-r / 2), r = sqrt(max(r2, 1e-36)); -2 dk/dr2 = variance exp(-r / 2) / (2 r), 0 where r2 <= 1e-36;
+  * RationalQuadratic: u = r2 / (2 alpha), k = variance exp(-alpha log1p(u)), -2 dk/dr2 = variance exp(-(alpha + 1) log1p(u)),
+    dk/dalpha = k (u / (1 + u) - log1p(u)) (op "dalpha": exact zeros on the diagonal of the symmetric form, as "dr2");
+  * White: variance on the diagonal when X2 is None, zeros for ANY X2 given (never by comparing values); Constant: variance
+    everywhere; both without reading X (a NaN there does not reach the output), -2 dk/dr2 = 0;
+  * what the device refuses (GPK_E_ARG / GPK_E_UNSUPPORTED) is an AssertionError here: "dalpha" for another family, alpha missing,
+    <= 0 or not finite, alpha given to another family, a RationalQuadratic member in the per-latent shard.
+The fused chains end in a stage they are GIVEN: `_shard` (shared kernel) and `_shard_sep` (one kernel per latent) take it as an
+argument; the public functions pass the Gaussian stage, tests/fake_likelihood_ops.py and tests/fake_lcm_ops.py pass theirs.  Every
+emulated name is defined in one module only (tests/emulation.py checks it and installs them all).
 The product never imports this file.
 """
 from __future__ import annotations
@@ -24,7 +37,8 @@ def _np(t):
     return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
 
 
-KERNEL_FAMILIES = {"SquaredExponential": 0, "Matern12": 1, "Matern32": 2, "Matern52": 3}
+KERNEL_FAMILIES = {"SquaredExponential": 0, "Matern12": 1, "Matern32": 2, "Matern52": 3, "Exponential": 4, "RationalQuadratic": 5,
+                   "White": 6, "Constant": 7}    # include/gpk.h: GPK_KERN_SE .. GPK_KERN_CONSTANT
 
 
 def device():
@@ -57,20 +71,6 @@ def _k(X1, X2, variance, lengthscales, family="SquaredExponential"):
     raise KeyError(family)
 
 
-def kernel_matrix(X1, X2, *, variance, lengthscales, family="SquaredExponential", diag_add=0.0, lower_only=False,
-                  out=None):
-    K = _k(X1, X1 if X2 is None else X2, variance, lengthscales, family)
-    if X2 is None:
-        K = K + diag_add * np.eye(K.shape[0])
-        if lower_only:   # tiles strictly above the diagonal are not written
-            K = np.where(np.triu(np.ones_like(K), 1) > 0, np.nan, K)
-    Kt = torch.from_numpy(K)
-    if out is None:
-        return Kt
-    out.copy_(Kt)
-    return out
-
-
 def _dr2(X1, X2, variance, lengthscales, family):
     """-2 dk/dr2 at the scaled squared distance (zero where the 1e-36 clamp is active)."""
     a, b = _np(X1) / _ls(lengthscales, X1.shape[1]), _np(X2) / _ls(lengthscales, X1.shape[1])
@@ -90,30 +90,86 @@ def _dr2(X1, X2, variance, lengthscales, family):
     return np.where(ok, f, 0.0)
 
 
-def kernel_matrix_hadamard(X1, X2, G, *, variance, lengthscales, family="SquaredExponential", out=None):
-    assert tuple(G.shape) == (X1.shape[0], X2.shape[0])
-    R = torch.from_numpy(_k(X1, X2, variance, lengthscales, family) * _np(G))
-    if out is None:
-        return R
-    out.copy_(R)
-    return out
+def _alpha(family, alpha):
+    if family == "RationalQuadratic":
+        assert alpha is not None, "RationalQuadratic needs alpha"                         # (ops: ValueError)
+        assert np.isfinite(float(alpha)) and float(alpha) > 0.0, alpha                     # GPK_E_ARG
+        return float(alpha)
+    assert alpha is None, f"alpha given to {family}"                                      # (ops: ValueError)
+    assert family in KERNEL_FAMILIES, family
+    return None
 
 
-def kernel_matrix_combine(X1, X2, G, *, op, variance, lengthscales, family="SquaredExponential", diag_add=0.0, out=None):
-    if op == "dr2":
-        R = _dr2(X1, X1 if X2 is None else X2, variance, lengthscales, family) * _np(G)
-        if X2 is None:
-            np.fill_diagonal(R, 0.0)
-    else:
-        K = _k(X1, X1 if X2 is None else X2, variance, lengthscales, family)
-        R = K * _np(G) if op == "mul" else K + _np(G)
-        if X2 is None:
-            R = R + diag_add * np.eye(R.shape[0])
-    Rt = torch.from_numpy(R)
+def _profile(X1, X2, variance, lengthscales, family, alpha, what="k"):
+    """k, -2 dk/dr2 ("dr2") or dk/dalpha ("dalpha") for [n1, n2]; X2 None = K(X1, X1)"""
+    n1, n2 = X1.shape[0], (X1 if X2 is None else X2).shape[0]
+    if family in ("White", "Constant"):
+        if what != "k":
+            return np.zeros((n1, n2))
+        if family == "Constant":
+            return np.full((n1, n2), float(variance))
+        return float(variance) * np.eye(n1) if X2 is None else np.zeros((n1, n2))
+    if family not in ("Exponential", "RationalQuadratic"):   # the four first families: the formulas the contract tables compare bits with
+        return (_k if what == "k" else _dr2)(X1, X1 if X2 is None else X2, variance, lengthscales, family)
+    a, b = _np(X1) / _ls(lengthscales, X1.shape[1]), _np(X1 if X2 is None else X2) / _ls(lengthscales, X1.shape[1])
+    r2 = -2.0 * a @ b.T + (a * a).sum(1)[:, None] + (b * b).sum(1)[None, :]
+    if family == "Exponential":
+        if what == "k":
+            return variance * np.exp(-0.5 * np.sqrt(np.where(r2 < 1e-36, 1e-36, r2)))
+        ok = ~(r2 <= 1e-36)
+        r = np.sqrt(np.where(ok, r2, 1.0))
+        return np.where(ok, variance * np.exp(-0.5 * r) / (2.0 * r), 0.0)
+    u = r2 / (2.0 * alpha)
+    l1p = np.log1p(u)
+    if what == "k":
+        return variance * np.exp(-alpha * l1p)
+    if what == "dr2":
+        return variance * np.exp(-(alpha + 1.0) * l1p)
+    return variance * np.exp(-alpha * l1p) * (u / (1.0 + u) - l1p)
+
+
+def _ret(R, out):
+    Rt = torch.from_numpy(np.ascontiguousarray(R, dtype=np.float64))
     if out is None:
         return Rt
     out.copy_(Rt)
     return out
+
+
+def kernel_matrix(X1, X2, *, variance, lengthscales, family="SquaredExponential", diag_add=0.0, lower_only=False, alpha=None,
+                  out=None):
+    alpha = _alpha(family, alpha)
+    with np.errstate(all="ignore"):
+        K = _profile(X1, X2, variance, lengthscales, family, alpha)
+        if X2 is None:
+            K = K + diag_add * np.eye(K.shape[0])
+            if lower_only:   # tiles strictly above the diagonal are not written
+                K = np.where(np.triu(np.ones_like(K), 1) > 0, np.nan, K)
+    return _ret(K, out)
+
+
+def kernel_matrix_hadamard(X1, X2, G, *, variance, lengthscales, family="SquaredExponential", alpha=None, out=None):
+    assert X2 is not None and tuple(G.shape) == (X1.shape[0], X2.shape[0])
+    alpha = _alpha(family, alpha)
+    with np.errstate(all="ignore"):
+        return _ret(_profile(X1, X2, variance, lengthscales, family, alpha) * _np(G), out)
+
+
+def kernel_matrix_combine(X1, X2, G, *, op, variance, lengthscales, family="SquaredExponential", diag_add=0.0, alpha=None, out=None):
+    assert op in ("mul", "add", "dr2", "dalpha"), op                                       # GPK_E_ARG
+    assert op != "dalpha" or family == "RationalQuadratic", (op, family)                   # GPK_E_UNSUPPORTED
+    alpha = _alpha(family, alpha)
+    with np.errstate(all="ignore"):
+        if op in ("dr2", "dalpha"):
+            R = _profile(X1, X2, variance, lengthscales, family, alpha, op) * _np(G)
+            if X2 is None:
+                np.fill_diagonal(R, 0.0)
+        else:
+            K = _profile(X1, X2, variance, lengthscales, family, alpha)
+            R = K * _np(G) if op == "mul" else K + _np(G)
+            if X2 is None:
+                R = R + diag_add * np.eye(R.shape[0])
+    return _ret(R, out)
 
 
 def _invd(n, batch, mark):
@@ -353,14 +409,15 @@ def project(At, LqT):
                                       for p in range(LqT.shape[0])]))
 
 
-def gpr_lml(X, Y, *, variance, lengthscales, noise_variance, mean_const=0.0, family="SquaredExponential", ws=None):
+def gpr_lml(X, Y, *, variance, lengthscales, noise_variance, mean_const=0.0, family="SquaredExponential", alpha=None, ws=None):
     """The fused driver, emulated by the same chain of primitives it runs (drivers.hip: gpk_gpr_lml)."""
+    _alpha(family, alpha)
     n, P = Y.shape
     assert n >= 1 and P >= 1, (n, P)    # gpk_gpr_lml: GPK_E_ARG
     T = torch.empty((n + P, n), dtype=torch.float64)
     nv = _noise(noise_variance, n)
-    kernel_matrix(X, None, variance=variance, lengthscales=lengthscales, family=family, diag_add=0.0 if isinstance(nv, np.ndarray) else nv,
-                  lower_only=True, out=T[:n])
+    kernel_matrix(X, None, variance=variance, lengthscales=lengthscales, family=family, alpha=alpha,
+                  diag_add=0.0 if isinstance(nv, np.ndarray) else nv, lower_only=True, out=T[:n])
     if isinstance(nv, np.ndarray):
         diag_add_(T[:n], torch.from_numpy(nv[:, 0].copy()))
     T[n:] = (Y - mean_const).t()
@@ -375,9 +432,18 @@ def svgp_elbo_sep_workspace(m, rows, d, P):
     return torch.empty(1, dtype=torch.float64)
 
 
-def svgp_elbo_shard_sep(Z, Xb, Yb, q_mu, q_sqrt, *, variances, lengthscales, families, noise_variance, jitter, mean_const=0.0,
-                        ws=None, out=None, info=None):
-    """gpk_svgp_elbo_shard_sep emulated by its chain of primitives (whitened; one kernel per latent; full q_sqrt)."""
+def _gaussian_stage(noise_variance):
+    """the last stage of the fused chains as their public forms run it (the workers below take theirs as an argument)"""
+    def stage(Y, fmean, **kw):
+        return gaussian_varexp_sum(Y, fmean, noise_variance=noise_variance, **kw)
+    return stage
+
+
+def _shard_sep(Z, Xb, Yb, q_mu, q_sqrt, stage, *, variances, lengthscales, families, jitter, mean_const=0.0, out=None):
+    """The per-latent chain (whitened; one kernel per latent; full q_sqrt) up to its last stage: `stage` takes the operands of
+    gaussian_varexp_sum but the noise and returns its pair -- the Gaussian stage for gpk_svgp_elbo_shard_sep, the mixing stage for
+    gpk_svgp_elbo_shard_lcm."""
+    assert "RationalQuadratic" not in list(families), "no slot for alpha in the per-latent shard"   # GPK_E_UNSUPPORTED
     P = q_mu.shape[1]
     M, rows = Z.shape[-2], Xb.shape[0]
     assert 1 <= P <= 16 and M >= 1, (P, M)    # gpk_svgp_elbo_shard_sep: GPK_E_ARG
@@ -396,8 +462,8 @@ def svgp_elbo_shard_sep(Z, Xb, Yb, q_mu, q_sqrt, *, variances, lengthscales, fam
         s0 = torch.stack([row_stats(T[p, M:].contiguous(), V=q_mu[:, p:p + 1].contiguous())[0] for p in range(P)])
         fmean = torch.stack([row_stats(T[p, M:].contiguous(), V=q_mu[:, p:p + 1].contiguous())[1][:, 0] for p in range(P)], dim=1)
         ssq = project(T[:, M:], transpose(q_sqrt, mode=1))
-        ve, _ = gaussian_varexp_sum(Yb, fmean.contiguous(), s0=s0, ssq=ssq, knn=[float(v) for v in variances],
-                                    noise_variance=noise_variance, mean_const=mean_const, s0_per_latent=True)
+        ve, _ = stage(Yb, fmean.contiguous(), s0=s0, ssq=ssq, knn=[float(v) for v in variances], mean_const=mean_const,
+                      s0_per_latent=True)
         res[0] = ve[0]
         res[1] = gauss_kl_white(q_mu, q_sqrt)[0]
     if out is not None:
@@ -406,16 +472,33 @@ def svgp_elbo_shard_sep(Z, Xb, Yb, q_mu, q_sqrt, *, variances, lengthscales, fam
     return res, inf
 
 
+def svgp_elbo_shard_sep(Z, Xb, Yb, q_mu, q_sqrt, *, variances, lengthscales, families, noise_variance, jitter, mean_const=0.0,
+                        ws=None, out=None, info=None):
+    """gpk_svgp_elbo_shard_sep emulated by its chain of primitives, ending in the Gaussian stage"""
+    return _shard_sep(Z, Xb, Yb, q_mu, q_sqrt, _gaussian_stage(noise_variance), variances=variances, lengthscales=lengthscales,
+                      families=families, jitter=jitter, mean_const=mean_const, out=out)
+
+
 def svgp_elbo_workspace(m, rows, d, P, q_diag, whiten=True):
     return torch.empty(1, dtype=torch.float64)
 
 
 def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_variance, jitter, mean_const=0.0,
-                    family="SquaredExponential", ws=None, out=None, info=None, whiten=True):
-    """gpk_svgp_elbo_shard emulated by its own chain of primitives (shared kernel; whitened, or un-whitened on one trapezoid)."""
+                    family="SquaredExponential", alpha=None, ws=None, out=None, info=None, whiten=True):
+    """gpk_svgp_elbo_shard emulated by its own chain of primitives, ending in the Gaussian stage"""
+    return _shard(Z, Xb, Yb, q_mu, q_sqrt, _gaussian_stage(noise_variance), variance=variance, lengthscales=lengthscales, jitter=jitter,
+                  mean_const=mean_const, family=family, alpha=alpha, out=out, whiten=whiten)
+
+
+def _shard(Z, Xb, Yb, q_mu, q_sqrt, stage, *, variance, lengthscales, jitter, mean_const=0.0, family="SquaredExponential", alpha=None,
+           out=None, whiten=True):
+    """The shared-kernel chain (whitened, or un-whitened on one trapezoid) up to its last stage: `stage` takes the operands of
+    gaussian_varexp_sum but the noise and returns its pair -- the Gaussian stage for gpk_svgp_elbo_shard, a quadrature stage for
+    gpk_svgp_elbo_shard_lik (fake_likelihood_ops)."""
+    _alpha(family, alpha)
     M, rows, P = Z.shape[0], Xb.shape[0], q_mu.shape[1]
     assert 1 <= P <= 16 and M >= 1, (P, M)    # gpk_svgp_elbo_shard: GPK_E_ARG
-    kw = dict(variance=variance, lengthscales=lengthscales, family=family)
+    kw = dict(variance=variance, lengthscales=lengthscales, family=family, alpha=alpha)
     if not whiten and q_sqrt.dim() == 2:
         # un-whitened, diagonal q_sqrt: [Kuu ; Kfu ; q_mu^T ; I] -> A^T, (Lm^-1 q_mu)^T, Lm^-T (drivers.hip, round 5)
         T = torch.empty((M + rows + P + M, M), dtype=torch.float64)
@@ -432,8 +515,7 @@ def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_va
             A2 = gemm_nt(At, LinvT, b_tri=1) if rows else At
             s0 = row_stats(At)[0] if rows else torch.zeros(0, dtype=torch.float64)
             _, fmean, ssq = row_stats(A2, V=q_mu, W=q_sqrt, want_sumsq=False) if rows else (None, torch.zeros((0, P), dtype=torch.float64), torch.zeros((P, 0), dtype=torch.float64))
-            ve, _ = gaussian_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[variance], noise_variance=noise_variance,
-                                        mean_const=mean_const)
+            ve, _ = stage(Yb, fmean, s0=s0, ssq=ssq, knn=[variance], mean_const=mean_const)
             res[0] = ve[0]
             kinv = (np.triu(_np(LinvT)) ** 2).sum(1)
             w = _np(q_sqrt)
@@ -459,8 +541,7 @@ def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_va
             GT = T[M + rows + P:].reshape(P, M, M).contiguous()
             s0, fmean, _ = row_stats(At, V=V)
             ssq = project(At, GT)
-            ve, _ = gaussian_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[variance], noise_variance=noise_variance,
-                                        mean_const=mean_const)
+            ve, _ = stage(Yb, fmean, s0=s0, ssq=ssq, knn=[variance], mean_const=mean_const)
             res[0] = ve[0]
             Lq = np.tril(_np(q_sqrt))
             res[1] = 0.5 * float((_np(T[M + rows:M + rows + P]) ** 2).sum()) + 0.5 * float((_np(GT) ** 2).sum()) - 0.5 * M * P \
@@ -485,8 +566,7 @@ def svgp_elbo_shard(Z, Xb, Yb, q_mu, q_sqrt, *, variance, lengthscales, noise_va
         else:
             s0, fmean, _ = row_stats(At, V=q_mu)
             ssq = project(At.contiguous(), transpose(q_sqrt, mode=1))
-        ve, _ = gaussian_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[variance], noise_variance=noise_variance,
-                                    mean_const=mean_const)
+        ve, _ = stage(Yb, fmean, s0=s0, ssq=ssq, knn=[variance], mean_const=mean_const)
         res[0] = ve[0]
         res[1] = gauss_kl_white(q_mu, q_sqrt)[0]
     if out is not None:

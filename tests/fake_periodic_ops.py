@@ -8,8 +8,7 @@ warp"):
     fake_ops.moment_rows at the warped inputs;
   * the tail is the two formulas of the header, `into` = accumulate.
 What the device refuses (GPK_E_ARG, or the ValueError ops raises before it) is an AssertionError here: D outside [1, 32], a period
-of the wrong length or one that is not positive and finite.  Patched after fake_ops, fake_likelihood_ops and fake_kernel_ops.  The
-product never imports this file.
+of the wrong length or one that is not positive and finite.  The product never imports this file.
 """
 from __future__ import annotations
 

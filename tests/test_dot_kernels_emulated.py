@@ -1,7 +1,6 @@
 """CPU: the dot-product kernels (primitives, the classes on every forward route, the reverse pass of GPR and SVGP with a row diagonal)
-driven by the test bodies of tests/test_gpu_dot_kernels.py with the device primitives replaced by their NumPy emulation --
-tests/fake_ops.py, then fake_likelihood_ops.py, fake_kernel_ops.py, fake_periodic_ops.py, fake_lcm_ops.py and fake_dot_ops.py patched
-last -- as tests/test_periodic_emulated.py drives tests/test_gpu_periodic.py.  What this does NOT test is the HIP kernel: that is what
+driven by the test bodies of tests/test_gpu_dot_kernels.py with the device primitives replaced by their NumPy emulation
+(tests/emulation.py: every tests/fake_*.py) -- as tests/test_periodic_emulated.py drives tests/test_gpu_periodic.py.  What this does NOT test is the HIP kernel: that is what
 the same bodies do under `-m gpu`.  The CPU-only checks of the feature (what the library answers before it touches a device, the
 leaf and the spec's bookkeeping, the launch list of a constant-diagonal spec) are at the end; they need no device.
 """
@@ -12,27 +11,13 @@ import re
 import numpy as np
 import pytest
 
-import fake_dot_ops
-import fake_kernel_ops
-import fake_lcm_ops
-import fake_likelihood_ops
-import fake_ops
-import fake_periodic_ops
+import emulation
 import test_gpu_dot_kernels as T
 
 
 @pytest.fixture
 def gp(monkeypatch):
-    import gpflow_amd
-    from gpflow_amd import ops
-    for mod in (fake_ops, fake_likelihood_ops, fake_kernel_ops, fake_periodic_ops, fake_lcm_ops, fake_dot_ops):
-        for name in dir(mod):
-            if name.startswith("_") or not callable(getattr(mod, name)) or not hasattr(ops, name):
-                continue
-            if name in ("torch", "np", "sla", "sps", "fake_ops", "fake_likelihood_ops"):
-                continue
-            monkeypatch.setattr(ops, name, getattr(mod, name))
-    return gpflow_amd
+    return emulation.install(monkeypatch)
 
 
 for _n in [n for n in dir(T) if n.startswith("test_")]:
@@ -120,8 +105,7 @@ def test_a_constant_diagonal_spec_issues_the_calls_it_issued(monkeypatch):
             calls.append(name)
             return fn(*a, **kw)
         return call
-    mods = (fake_ops, fake_kernel_ops)
-    proxy = types.SimpleNamespace(**{n: logged(n, getattr(m, n)) for m in mods for n in dir(m) if not n.startswith("_") and callable(getattr(m, n))})
+    proxy = types.SimpleNamespace(**{n: logged(n, fn) for n, fn in emulation.primitives().items()})
     monkeypatch.setattr(gradients, "ops", proxy)
     rng = np.random.default_rng(0)
     t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64))  # noqa: E731

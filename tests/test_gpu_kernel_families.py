@@ -3,9 +3,8 @@ primitives (`ops.kernel_matrix`, `kernel_matrix_combine` with its fourth op "dal
 drivers that forward a family, the reverse pass (`gradients.*`, `KernelSpec` with `alpha` and static members) and the model surface.
 
 The same bodies run in the CPU tier against the NumPy emulation (tests/test_kernel_families_emulated.py imports them without this
-module's `gpu` mark and gives them an emulated `gp` fixture: tests/fake_ops.py + tests/fake_likelihood_ops.py +
-tests/fake_kernel_ops.py).  On the device every primitive case also runs the emulation beside it (`_impls`: test_gpu_contract's
-pair with fake_kernel_ops in the place of fake_ops, which does not know the new families).
+module's `gpu` mark and gives them an emulated `gp` fixture: tests/emulation.py).  On the device every primitive case also runs the
+emulation beside it (`_impls`: test_gpu_contract's pair, tests/fake_ops.py, which knows the eight families).
 
 References.  Primitives: the method of test_gpu_contract._kref -- the same expansion formula in np.longdouble and a bound derived
 from it (`_kref_new`, u = 2^-53).  Fused paths and gradients: torch autograd through the unchanged oracle
@@ -23,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import gp_oracle_grad as orcg  # noqa: E402  (checker only)
-import fake_kernel_ops  # noqa: E402
+import fake_ops  # noqa: E402
 from test_gpu_contract import LD, U, _check_unchanged, _kdata, _np, _on, _within  # noqa: E402
 from test_gpu_likelihoods import _refused  # noqa: E402
 
@@ -48,7 +47,7 @@ def _dev(gp):
 def _impls(gp):
     """test_gpu_contract._impls for the extended primitives: gp.ops, and beside a real device the emulation on the same inputs"""
     dev = _dev(gp)
-    return [("ops", gp.ops, dev)] + ([("fake_kernel_ops", fake_kernel_ops, "cpu")] if dev != "cpu" else [])
+    return [("ops", gp.ops, dev)] + ([("fake_ops", fake_ops, "cpu")] if dev != "cpu" else [])
 
 
 def _akw(alpha):

@@ -3,7 +3,7 @@
 `SVGP.elbo` / `predict_f` and the reverse pass `SVGP.elbo_and_grad` of the model.
 
 The same bodies run in the CPU tier against the NumPy emulation (tests/test_lcm_emulated.py imports them without this module's
-`gpu` mark and gives them an emulated `gp` fixture: tests/fake_ops.py + tests/fake_likelihood_ops.py + tests/fake_lcm_ops.py).
+`gpu` mark and gives them an emulated `gp` fixture: tests/emulation.py, with tests/fake_lcm_ops.py for the primitives here).
 
 References.  The primitive: its contract (include/gpk.h) restated in np.longdouble (`_mixed_reference`), every bound derived next
 to its check with u = 2^-53.  The fused shard: the emulation, within test_gpu_contract._fused_bound.  The model: per-latent
@@ -307,7 +307,7 @@ def _lcm_cond(Z, kw):
 
 @pytest.mark.parametrize("case", LCM_SHARD_CASES, ids=[str(c) for c in LCM_SHARD_CASES])
 def test_svgp_elbo_shard_lcm_contract(gp, case):
-    """The fused shard against its emulation (fake_lcm_ops on fake_ops.svgp_elbo_shard_sep's pieces) within _fused_bound, as
+    """The fused shard against its emulation (fake_lcm_ops on fake_ops' per-latent chain) within _fused_bound, as
     test_svgp_elbo_shard_sep_contract holds the separate shard; the KL to that test's reduction bound."""
     ops, dev = gp.ops, _dev(gp)
     M, rows, L, P, layout, _, _ = case

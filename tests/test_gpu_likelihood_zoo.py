@@ -2,8 +2,8 @@
 `ops.svgp_elbo_shard_lik`, the classes, `SVGP.elbo` / `predict_y` / `predict_log_density` and the reverse pass with them.  The layout
 follows tests/test_gpu_likelihoods.py, whose helpers (`_within`, `_mp_map`, `_svgp_problem`, the case table) are reused.
 
-The same bodies run in the CPU tier against the NumPy emulation (tests/test_likelihood_zoo_emulated.py: tests/fake_ops.py,
-fake_likelihood_ops.py, fake_multiclass_ops.py and fake_likelihood_zoo_ops.py, patched in that order).
+The same bodies run in the CPU tier against the NumPy emulation (tests/test_likelihood_zoo_emulated.py: tests/emulation.py,
+the four codes being rows of the table of tests/fake_likelihood_ops.py).
 
 References.  Values: the contract of include/gpk.h restated in np.longdouble (`_reference`) with erfc / loggamma / digamma from mpmath
 (40 digits); the model-level 1e-8 comparisons take the same restatement over scipy's fp64 functions (their 1e-15 is far inside that

@@ -3,7 +3,7 @@
 `predict_log_density` and the reverse pass `SVGP.elbo_and_grad` with these likelihoods.
 
 The same bodies run in the CPU tier against the NumPy emulation (tests/test_likelihoods_emulated.py imports them without this
-module's `gpu` mark and gives them an emulated `gp` fixture: tests/fake_ops.py + tests/fake_likelihood_ops.py).
+module's `gpu` mark and gives them an emulated `gp` fixture: tests/emulation.py, with tests/fake_likelihood_ops.py).
 
 References.  Values: oracle/gp_oracle.py gives q(f) (`svgp_predict_f`) and the KL (`gauss_kl`); the Gauss-Hermite sum over
 numpy.polynomial.hermite.hermgauss(20) is written here (`_reference`), in np.longdouble with erfc / lgamma from mpmath (40

@@ -3,8 +3,8 @@
 `MultiClass`, `SVGP.elbo` / `predict_y` / `predict_log_density` and the reverse pass `SVGP.elbo_and_grad` with this likelihood.
 
 The same bodies run in the CPU tier against the NumPy emulation (tests/test_multiclass_emulated.py imports them without this
-module's `gpu` mark and gives them an emulated `gp` fixture: tests/fake_ops.py + tests/fake_likelihood_ops.py +
-tests/fake_multiclass_ops.py).
+module's `gpu` mark and gives them an emulated `gp` fixture: tests/emulation.py, the code being a row of the table of
+tests/fake_likelihood_ops.py).
 
 References.  Values: oracle/gp_oracle.py gives q(f) (`svgp_predict_f`) and the KL (`gauss_kl`); the definition of the likelihood
 (GPflow 2.9.2 likelihoods/multiclass.py) is restated here in np.longdouble with erfc from mpmath at 40 digits (`_mc_reference`).

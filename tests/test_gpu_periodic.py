@@ -2,8 +2,8 @@
 `periodic_adjoint_tail`), the kernel matrix through the warp, and `kernels.Periodic` on every model route of the reverse pass.
 
 The same bodies run in the CPU tier against the NumPy emulation (tests/test_periodic_emulated.py imports them without this module's
-`gpu` mark and gives them an emulated `gp` fixture: tests/fake_ops.py + fake_likelihood_ops.py + fake_kernel_ops.py +
-fake_periodic_ops.py).  On the device every primitive case also runs the emulation beside it (`_impls`).
+`gpu` mark and gives them an emulated `gp` fixture: tests/emulation.py, with tests/fake_periodic_ops.py for the three primitives
+here).  On the device every primitive case also runs the emulation beside it (`_impls`).
 
 References.  Primitives: np.longdouble restatements with bounds derived next to them (u = 2^-53).  The kernel matrix and the models
 are compared with the DIRECT formula  k(sum_j sin^2(pi (x_j - x'_j) / p_j) / l_j^2) -- never with the warp: in longdouble for the
@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import gp_oracle_grad as orcg  # noqa: E402  (checker only)
-import fake_kernel_ops  # noqa: E402
+import fake_ops  # noqa: E402
 import fake_periodic_ops  # noqa: E402
 from test_gpu_contract import LD, U, _check_unchanged, _np, _on, _padding_untouched, _within  # noqa: E402
 from test_gpu_kernel_families import _check_model_grads, _close, _kfun, _leaf, _svgp_problem, _t, _torch_kernel  # noqa: E402
@@ -42,9 +42,9 @@ def _dev(gp):
 
 
 class _Emulation:
-    """the emulated primitives under one roof: the builders of fake_kernel_ops, the three of fake_periodic_ops"""
-    kernel_matrix = staticmethod(fake_kernel_ops.kernel_matrix)
-    moment_rows = staticmethod(fake_kernel_ops.fake_ops.moment_rows)
+    """the emulated primitives under one roof: the builders of fake_ops, the three of fake_periodic_ops"""
+    kernel_matrix = staticmethod(fake_ops.kernel_matrix)
+    moment_rows = staticmethod(fake_ops.moment_rows)
     periodic_warp = staticmethod(fake_periodic_ops.periodic_warp)
     periodic_moment_rows = staticmethod(fake_periodic_ops.periodic_moment_rows)
     periodic_adjoint_tail = staticmethod(fake_periodic_ops.periodic_adjoint_tail)

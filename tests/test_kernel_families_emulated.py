@@ -1,6 +1,6 @@
 """CPU: the kernel families Exponential, RationalQuadratic, White and Constant (primitives, fused drivers, reverse pass, model
 surface) driven by the test bodies of tests/test_gpu_kernel_families.py with the device primitives replaced by their NumPy
-emulation -- tests/fake_ops.py, then tests/fake_likelihood_ops.py, then tests/fake_kernel_ops.py patched last -- exactly as
+emulation (tests/emulation.py: every tests/fake_*.py; the eight families are in tests/fake_ops.py) -- exactly as
 tests/test_lcm_emulated.py drives tests/test_gpu_lcm.py.  What this does NOT test is the HIP kernel: that is what the same bodies do
 under `-m gpu`.  The CPU-only checks of the feature (constructors, what the library answers before it touches a device, the
 exported functions) are at the end; they need no device.
@@ -12,24 +12,13 @@ import re
 import numpy as np
 import pytest
 
-import fake_kernel_ops
-import fake_likelihood_ops
-import fake_ops
+import emulation
 import test_gpu_kernel_families as T
 
 
 @pytest.fixture
 def gp(monkeypatch):
-    import gpflow_amd
-    from gpflow_amd import ops
-    for mod in (fake_ops, fake_likelihood_ops, fake_kernel_ops):
-        for name in dir(mod):
-            if name.startswith("_") or not callable(getattr(mod, name)) or not hasattr(ops, name):
-                continue
-            if name in ("torch", "np", "sla", "sps", "fake_ops", "fake_likelihood_ops"):
-                continue
-            monkeypatch.setattr(ops, name, getattr(mod, name))
-    return gpflow_amd
+    return emulation.install(monkeypatch)
 
 
 for _n in [n for n in dir(T) if n.startswith("test_")]:

@@ -1,7 +1,6 @@
 """CPU: kernel trees of mixed leaf kinds (every ordered pair of kinds in a Sum and a Product, nested trees on every model route)
-driven by the test bodies of tests/test_gpu_kernel_trees.py with the device primitives replaced by their NumPy emulation --
-tests/fake_ops.py, then fake_likelihood_ops.py, fake_kernel_ops.py, fake_periodic_ops.py, fake_lcm_ops.py and fake_dot_ops.py patched
-last -- as tests/test_dot_kernels_emulated.py drives tests/test_gpu_dot_kernels.py.  What this does NOT test is the HIP kernels: that
+driven by the test bodies of tests/test_gpu_kernel_trees.py with the device primitives replaced by their NumPy emulation
+(tests/emulation.py: every tests/fake_*.py) -- as tests/test_dot_kernels_emulated.py drives tests/test_gpu_dot_kernels.py.  What this does NOT test is the HIP kernels: that
 is what the same bodies do under `-m gpu`.  The CPU-only checks are at the end: the guard that holds `KINDS` to the leaf tables, the
 conditioning of the oracle for every model tree, the bookkeeping of one three-level tree and the launch list of a constant-diagonal
 mixed tree; they need no device.
@@ -11,29 +10,13 @@ import types
 import numpy as np
 import pytest
 
-import fake_dot_ops
-import fake_kernel_ops
-import fake_lcm_ops
-import fake_likelihood_ops
-import fake_ops
-import fake_periodic_ops
+import emulation
 import test_gpu_kernel_trees as T
-
-FAKES = (fake_ops, fake_likelihood_ops, fake_kernel_ops, fake_periodic_ops, fake_lcm_ops, fake_dot_ops)
 
 
 @pytest.fixture
 def gp(monkeypatch):
-    import gpflow_amd
-    from gpflow_amd import ops
-    for mod in FAKES:
-        for name in dir(mod):
-            if name.startswith("_") or not callable(getattr(mod, name)) or not hasattr(ops, name):
-                continue
-            if name in ("torch", "np", "sla", "sps", "fake_ops", "fake_likelihood_ops"):
-                continue
-            monkeypatch.setattr(ops, name, getattr(mod, name))
-    return gpflow_amd
+    return emulation.install(monkeypatch)
 
 
 for _n in [n for n in dir(T) if n.startswith("test_")]:
@@ -154,7 +137,7 @@ def test_a_constant_diagonal_mixed_tree_issues_no_row_diagonal_call(monkeypatch)
             calls.append(name)
             return fn(*a, **kw)
         return call
-    proxy = types.SimpleNamespace(**{n: logged(n, getattr(m, n)) for m in FAKES for n in dir(m) if not n.startswith("_") and callable(getattr(m, n))})
+    proxy = types.SimpleNamespace(**{n: logged(n, fn) for n, fn in emulation.primitives().items()})
     monkeypatch.setattr(gradients, "ops", proxy)
     for meth in ("kdiag_rows", "diag_adjoint"):
         monkeypatch.setattr(gradients.KernelSpec, meth, logged(meth, getattr(gradients.KernelSpec, meth)))

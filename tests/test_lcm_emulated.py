@@ -1,6 +1,6 @@
 """CPU: the LinearCoregionalization layer (kernel class, mixing, posterior, SVGP routing, reverse pass) driven by the test bodies of
-tests/test_gpu_lcm.py with the device primitives replaced by their NumPy emulation -- tests/fake_ops.py, then
-tests/fake_likelihood_ops.py, then tests/fake_lcm_ops.py patched last -- exactly as tests/test_multiclass_emulated.py drives
+tests/test_gpu_lcm.py with the device primitives replaced by their NumPy emulation (tests/emulation.py: every
+tests/fake_*.py) -- exactly as tests/test_multiclass_emulated.py drives
 tests/test_gpu_multiclass.py.  What this does NOT test is the HIP kernel: that is what the same bodies do under `-m gpu`.  The
 CPU-only checks of the feature (constructors, the posterior table, what the library answers before it touches a device, the call
 log of the reverse pass, the build) are at the end; they need no device.
@@ -14,24 +14,13 @@ import numpy as np
 import pytest
 import torch
 
-import fake_lcm_ops
-import fake_likelihood_ops
-import fake_ops
+import emulation
 import test_gpu_lcm as T
 
 
 @pytest.fixture
 def gp(monkeypatch):
-    import gpflow_amd
-    from gpflow_amd import ops
-    for mod in (fake_ops, fake_likelihood_ops, fake_lcm_ops):
-        for name in dir(mod):
-            if name.startswith("_") or not callable(getattr(mod, name)) or not hasattr(ops, name):
-                continue
-            if name in ("torch", "np", "sla", "sps", "fake_ops", "fake_likelihood_ops"):
-                continue
-            monkeypatch.setattr(ops, name, getattr(mod, name))
-    return gpflow_amd
+    return emulation.install(monkeypatch)
 
 
 for _n in [n for n in dir(T) if n.startswith("test_")]:
@@ -173,10 +162,7 @@ def test_lcm_reverse_pass_call_log(monkeypatch):
             finally:
                 depth[0] -= 1
         return call
-    names = {}
-    for mod in (fake_ops, fake_lcm_ops):
-        names.update({n: logged(n, getattr(mod, n)) for n in dir(mod) if not n.startswith("_") and callable(getattr(mod, n))})
-    monkeypatch.setattr(gradients, "ops", types.SimpleNamespace(**names))
+    monkeypatch.setattr(gradients, "ops", types.SimpleNamespace(**{n: logged(n, fn) for n, fn in emulation.primitives().items()}))
     rng = np.random.default_rng(4)
     M, B, D, L, P = 24, 50, 2, 3, 4
     t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64))  # noqa: E731

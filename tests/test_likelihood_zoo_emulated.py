@@ -1,6 +1,6 @@
 """CPU: the Exponential / Gamma / Beta / Ordinal layer (classes, SVGP routing, reverse pass) driven by the test bodies of
-tests/test_gpu_likelihood_zoo.py with the device primitives replaced by their NumPy emulation -- tests/fake_ops.py,
-fake_likelihood_ops.py, fake_multiclass_ops.py and fake_likelihood_zoo_ops.py, patched in that order -- following
+tests/test_gpu_likelihood_zoo.py with the device primitives replaced by their NumPy emulation (tests/emulation.py: every
+tests/fake_*.py; the eight likelihood codes are the table of tests/fake_likelihood_ops.py) -- following
 tests/test_likelihoods_emulated.py.  What this does NOT test is the HIP kernel: that is what the same bodies do under `-m gpu`.  The
 CPU-only checks (the library's answers to bad parameters and unknown codes, the psi routine against mpmath, constructors, refusals)
 are at the end; they need no device.
@@ -13,25 +13,13 @@ import sys
 import numpy as np
 import pytest
 
-import fake_likelihood_ops
-import fake_likelihood_zoo_ops
-import fake_multiclass_ops
-import fake_ops
+import emulation
 import test_gpu_likelihood_zoo as T
 
 
 @pytest.fixture
 def gp(monkeypatch):
-    import gpflow_amd
-    from gpflow_amd import ops
-    for mod in (fake_ops, fake_likelihood_ops, fake_multiclass_ops, fake_likelihood_zoo_ops):
-        for name in dir(mod):
-            if name.startswith("_") or not callable(getattr(mod, name)) or not hasattr(ops, name):
-                continue
-            if name in ("torch", "np", "sla", "sps", "fake_ops", "fake_likelihood_ops", "fake_multiclass_ops"):
-                continue
-            monkeypatch.setattr(ops, name, getattr(mod, name))
-    return gpflow_amd
+    return emulation.install(monkeypatch)
 
 
 for _n in [n for n in dir(T) if n.startswith("test_")]:

@@ -1,29 +1,19 @@
 """CPU: the likelihood layer (classes, SVGP routing, reverse pass) driven by the test bodies of tests/test_gpu_likelihoods.py
-with the device primitives replaced by their NumPy emulation -- tests/fake_ops.py plus tests/fake_likelihood_ops.py for the three
-likelihood primitives -- following tests/test_host_emulated.py.  What this does NOT test is the HIP kernel: that is what the same
+with the device primitives replaced by their NumPy emulation (tests/emulation.py: every tests/fake_*.py, with
+tests/fake_likelihood_ops.py for the three likelihood primitives) -- following tests/test_host_emulated.py.  What this does NOT test is the HIP kernel: that is what the same
 bodies do under `-m gpu`.  The CPU-only checks of the feature (the quadrature table the library holds, constructors, refusals)
 are at the end; they need no device.
 """
 import numpy as np
 import pytest
 
-import fake_likelihood_ops
-import fake_ops
+import emulation
 import test_gpu_likelihoods as T
 
 
 @pytest.fixture
 def gp(monkeypatch):
-    import gpflow_amd
-    from gpflow_amd import ops
-    for mod in (fake_ops, fake_likelihood_ops):
-        for name in dir(mod):
-            if name.startswith("_") or not callable(getattr(mod, name)) or not hasattr(ops, name):
-                continue
-            if name in ("torch", "np", "sla", "sps", "fake_ops"):
-                continue
-            monkeypatch.setattr(ops, name, getattr(mod, name))
-    return gpflow_amd
+    return emulation.install(monkeypatch)
 
 
 for _n in [n for n in dir(T) if n.startswith("test_")]:

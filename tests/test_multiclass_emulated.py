@@ -1,6 +1,6 @@
 """CPU: the MultiClass layer (classes, SVGP routing, reverse pass) driven by the test bodies of tests/test_gpu_multiclass.py with
-the device primitives replaced by their NumPy emulation -- tests/fake_ops.py, then tests/fake_likelihood_ops.py, then
-tests/fake_multiclass_ops.py patched last -- exactly as tests/test_likelihoods_emulated.py drives tests/test_gpu_likelihoods.py.
+the device primitives replaced by their NumPy emulation (tests/emulation.py: every tests/fake_*.py; the MultiClass code is a
+row of the table of tests/fake_likelihood_ops.py) -- exactly as tests/test_likelihoods_emulated.py drives tests/test_gpu_likelihoods.py.
 What this does NOT test is the HIP kernel: that is what the same bodies do under `-m gpu`.  The CPU-only checks of the feature
 (constructors, refusals, what the library answers before it touches a device) are at the end; they need no device.
 """
@@ -9,24 +9,13 @@ import ctypes
 import numpy as np
 import pytest
 
-import fake_likelihood_ops
-import fake_multiclass_ops
-import fake_ops
+import emulation
 import test_gpu_multiclass as T
 
 
 @pytest.fixture
 def gp(monkeypatch):
-    import gpflow_amd
-    from gpflow_amd import ops
-    for mod in (fake_ops, fake_likelihood_ops, fake_multiclass_ops):
-        for name in dir(mod):
-            if name.startswith("_") or not callable(getattr(mod, name)) or not hasattr(ops, name):
-                continue
-            if name in ("torch", "np", "sla", "sps", "fake_ops", "fake_likelihood_ops"):
-                continue
-            monkeypatch.setattr(ops, name, getattr(mod, name))
-    return gpflow_amd
+    return emulation.install(monkeypatch)
 
 
 for _n in [n for n in dir(T) if n.startswith("test_")]:

@@ -1,6 +1,6 @@
 """CPU: the Periodic kernel (primitives, the matrix through the warp, every model route of the reverse pass) driven by the test
-bodies of tests/test_gpu_periodic.py with the device primitives replaced by their NumPy emulation -- tests/fake_ops.py, then
-fake_likelihood_ops.py, fake_kernel_ops.py and fake_periodic_ops.py patched last -- as tests/test_kernel_families_emulated.py drives
+bodies of tests/test_gpu_periodic.py with the device primitives replaced by their NumPy emulation (tests/emulation.py: every
+tests/fake_*.py, tests/fake_periodic_ops.py among them) -- as tests/test_kernel_families_emulated.py drives
 tests/test_gpu_kernel_families.py.  What this does NOT test is the HIP kernel: that is what the same bodies do under `-m gpu`.  The
 CPU-only checks of the feature (the constructor, what the library answers before it touches a device, the spec's bookkeeping) are at
 the end; they need no device.
@@ -10,25 +10,13 @@ import ctypes
 import numpy as np
 import pytest
 
-import fake_kernel_ops
-import fake_likelihood_ops
-import fake_ops
-import fake_periodic_ops
+import emulation
 import test_gpu_periodic as T
 
 
 @pytest.fixture
 def gp(monkeypatch):
-    import gpflow_amd
-    from gpflow_amd import ops
-    for mod in (fake_ops, fake_likelihood_ops, fake_kernel_ops, fake_periodic_ops):
-        for name in dir(mod):
-            if name.startswith("_") or not callable(getattr(mod, name)) or not hasattr(ops, name):
-                continue
-            if name in ("torch", "np", "sla", "sps", "fake_ops", "fake_likelihood_ops"):
-                continue
-            monkeypatch.setattr(ops, name, getattr(mod, name))
-    return gpflow_amd
+    return emulation.install(monkeypatch)
 
 
 for _n in [n for n in dir(T) if n.startswith("test_")]:

@@ -6,17 +6,17 @@
                                                                 SGPR.objective_and_grad, SVGPTrainer and NaturalGradient issue and return
     python tools/reverse_pass_log.py compare <a.pkl> <b.pkl>    compare two dumps case by case
 
-`gradients.ops` is tests/fake_ops.py + fake_likelihood_ops.py + fake_kernel_ops.py + fake_periodic_ops.py + fake_lcm_ops.py +
-fake_dot_ops.py (of the SAME tree, the last one winning: `FAKES` of tests/test_kernel_trees_emulated.py) behind a logging proxy: one line per outermost
+`gradients.ops` is the whole emulation of the SAME tree (`primitives()` of its tests/emulation.py: every name of every tests/fake_*.py,
+each defined once) behind a logging proxy: one line per outermost
 `ops.*` call (name, shape and strides of every tensor argument, every scalar argument); a TorchDispatchMode adds one line per aten op
 issued OUTSIDE an `ops.*` call (the torch glue).  Each case runs twice and the second run is kept (`ls_device` caches).  Kept per
 case: the log and the bytes of F, every gradient and info; a refusal is kept as its exception type and message (a spec without a
 constant diagonal under a quadrature likelihood or in sgpr_elbo_and_grad).  Written for the refactor recorded in
 profiles/reverse_pass_refactor.txt.
 
-`dump-models` patches every `gpflow_amd.ops` name the fakes define -- fake_ops, fake_likelihood_ops, fake_multiclass_ops, then
-fake_kernel_ops, fake_periodic_ops, fake_lcm_ops and fake_dot_ops last (the order of the `gp` fixture of
-tests/test_multiclass_emulated.py, then of `FAKES` of tests/test_kernel_trees_emulated.py) -- behind the same logging wrapper -- or, with `device`, patches nothing and logs nothing: the same matrix on the real library.  Kept per
+`dump-models` patches every `gpflow_amd.ops` name the emulation defines (the same `primitives()`, what `emulation.install` patches
+in the tests) behind the same logging wrapper -- or, with `device`, patches nothing and logs nothing: the same matrix on the real library.
+A tree from before tests/emulation.py existed is dumped with ITS OWN copy of this tool (profiles/emulation_refactor.txt).  Kept per
 case: the `ops.*` log, the returned value, every gradient under a key that carries its position in the returned dict and the
 position of its Parameter in `model.parameters`; for the trainer F, every `u` / `dev` entry after two steps and the names of `host` in
 order (in the key); for a fused forward call (kind "value") the returned value alone.  A refusal is kept as its exception type and message.  The model functions run twice on one model: `<case>` is the second run
@@ -66,23 +66,10 @@ def load(tree):
     sys.path[:0] = [tree, tree + "/tests"]
     import torch
     from torch.utils._python_dispatch import TorchDispatchMode
-    import fake_dot_ops
-    import fake_kernel_ops
-    import fake_lcm_ops
-    import fake_likelihood_ops
-    import fake_ops
-    import fake_periodic_ops
+    import emulation
     from gpflow_amd import gradients
     log, depth, wrap = _logger()
-
-    proxy = types.SimpleNamespace()
-    for mod in (fake_ops, fake_likelihood_ops, fake_kernel_ops, fake_periodic_ops, fake_lcm_ops, fake_dot_ops):
-        for name in dir(mod):
-            v = getattr(mod, name)
-            if name.startswith("_") or isinstance(v, types.ModuleType):
-                continue
-            setattr(proxy, name, wrap(name, v) if callable(v) else v)
-    gradients.ops = proxy
+    gradients.ops = types.SimpleNamespace(**{name: wrap(name, fn) for name, fn in emulation.primitives().items()})
 
     class Glue(TorchDispatchMode):
         def __torch_dispatch__(self, func, types_, args=(), kwargs=None):
@@ -449,19 +436,10 @@ def dump_models(tree, path, device=None):
     from gpflow_amd import ops, training
     log, depth, wrap = _logger()
     if device is None:
-        import fake_dot_ops
-        import fake_kernel_ops
-        import fake_lcm_ops
-        import fake_likelihood_ops
-        import fake_multiclass_ops
-        import fake_ops
-        import fake_periodic_ops
-        for mod in (fake_ops, fake_likelihood_ops, fake_multiclass_ops, fake_kernel_ops, fake_periodic_ops, fake_lcm_ops, fake_dot_ops):
-            for name in dir(mod):
-                v = getattr(mod, name)
-                if name.startswith("_") or not callable(v) or not hasattr(ops, name) or isinstance(v, types.ModuleType):
-                    continue
-                setattr(ops, name, wrap(name, v))
+        import emulation
+        for name, fn in emulation.primitives().items():
+            if hasattr(ops, name):
+                setattr(ops, name, wrap(name, fn))
     arr = lambda v: np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64))  # noqa: E731
     pack = lambda vals: {k: (tuple(arr(v).shape), arr(v).tobytes()) for k, v in vals.items()}  # noqa: E731
     res = {}
