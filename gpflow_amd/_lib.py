@@ -100,6 +100,8 @@ _SIGS = {
     "gpk_dot_kernel_diag": (c_int, [c_void_p, c_int, c_int, _dp, c_int, c_long, c_int, C.POINTER(c_double), c_int, c_double, c_int,
                                     _dp, _dp]),
     "gpk_dot_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, c_int, _dp, c_int, c_int, _dp, _dp, c_long]),
+    "gpk_tril_product_tiles": (c_int, [c_int]),
+    "gpk_tril_product": (c_int, [c_void_p, _dp, c_int, c_long, _dp, c_long, c_long, c_int, _dp, _dp, _dp, _dp, c_long, c_long]),
     "gpk_adam_step": (c_int, [c_void_p, _dp, _dp, _dp, _dp, c_long, c_double, c_double, c_double, c_double, c_int]),
     "gpk_lowrank_axpy": (c_int, [c_void_p, c_double, _dp, c_long, _dp, c_long, _dp, c_long, c_int, c_int, c_int, _dp, c_long]),
     "gpk_symmetrize": (c_int, [c_void_p, _dp, c_int, c_long]),

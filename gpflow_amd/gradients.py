@@ -1331,3 +1331,80 @@ def svgp_elbo_and_grad_unwhitened(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.T
     grads = {**spec.kernel_grads(g_var, g_ls), "noise_variance": seed.noise_grad(ve, s0, ssq, kd),
              "Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)}
     return F, grads, info
+
+
+def vgp_elbo_and_grad(X: torch.Tensor, Y: torch.Tensor, q_mu: torch.Tensor, q_sqrt: torch.Tensor, *, kernel_spec: "KernelSpec",
+                      jitter: float, mean_const: float = 0.0, noise_variance: Optional[float] = None, likelihood=None
+                      ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor]:
+    """VGP.elbo (gpflow/models/vgp.py:131-155) and its gradient: the full variational GP, q(f) = N(L q_mu + m, L S S^T L^T) with
+    L = chol(K(X, X) + jitter I) and S_r = tril(q_sqrt[r]) -- the whitened conditional at the data, both factors N x N lower triangular.
+
+        forward   fmean = L q_mu + m,   fvar[n, r] = sum_j (L S_r)[n, j]^2      (ops.tril_product: the product is not stored)
+                  F = sum var_exp(fmean, fvar) - KL[q(v) || N(0, I)]
+        backward  r = dF/dfmean, c = dF/dfvar [N, R];   T_bar_r = 2 diag(c_r) L S_r  (ops.tril_product in store mode)
+                  L_bar = tril(r q_mu^T) + sum_r tril(T_bar_r S_r^T),   S_bar_r = tril(L^T T_bar_r) - S_r + diag(1 / S_r),
+                  q_mu_bar = L^T r - q_mu,   K_bar = cholesky_adjoint(L_bar),  kernel parameters from K_bar (symmetric adjoint)
+
+    Gaussian likelihood with one `noise_variance`, or likelihood = (name, params) of ops.likelihood_varexp_sum (then `noise_variance` is
+    ignored and the seeds are the quadrature kernel's own dmu, dvar; "multiclass_robustmax": Y is one column of labels, R classes).
+    The trapezoid is [K + jitter I ; I], as in gpr_lml_and_grad: the identity rows come back as L^-T, which the Cholesky adjoint needs.
+    Returns (F [1], grads, info): grads as svgp_elbo_and_grad names them, without "Z"."""
+    N, D = X.shape
+    R = q_mu.shape[1]
+    if tuple(q_mu.shape) != (N, R) or tuple(q_sqrt.shape) != (R, N, N):
+        raise ValueError("vgp_elbo_and_grad needs q_mu [N, R] and a full q_sqrt [R, N, N] for the N rows of X")
+    if (noise_variance is None) == (likelihood is None):
+        raise ValueError("vgp_elbo_and_grad: one of noise_variance (Gaussian) and likelihood = (name, params)")
+    if noise_variance is not None and torch.is_tensor(noise_variance) and noise_variance.dim() >= 1:
+        raise NotImplementedError("vgp_elbo_and_grad: one noise variance (a heteroskedastic Gaussian likelihood is outside the VGP's reverse pass)")
+    dev = X.device
+    spec = kernel_spec
+    spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
+    q_mu, q_sqrt = q_mu.contiguous(), q_sqrt.contiguous()
+    # ---------------------------------------------------------------- forward
+    T = torch.empty((2 * N, N), dtype=torch.float64, device=dev)
+    spec.build(X, None, T[:N], diag_add=jitter)                                         # K + jitter I
+    _, info = ops.potrf_(T, N, zero_upper=True, identity_rows=True)                     # (the last N rows: I -> L^-T)
+    L, LinvT = T[:N], T[N:]
+    ssq, _ = ops.tril_product(L, q_sqrt)                                                # [R, N]
+    fmean = ops.row_stats(L, V=q_mu, want_sumsq=False)[1]                               # L q_mu  [N, R] (one pass over L)
+    if likelihood is not None:
+        lik_out, _, dmu, dvar, _ = ops.likelihood_varexp_sum(Y, fmean, s0=None, ssq=ssq, knn=[0.0], lik=likelihood[0],
+                                                             params=likelihood[1], mean_const=mean_const, want_grads=True)
+        ve = lik_out[0:1]
+    else:
+        ve, _ = ops.gaussian_varexp_sum(Y, fmean, s0=None, ssq=ssq, knn=[0.0], noise_variance=noise_variance, mean_const=mean_const)
+    kl = ops.gauss_kl_white(q_mu, q_sqrt)
+    F = torch.sub(ve, kl)
+    # ---------------------------------------------------------------- backward
+    seed = _Seed(Y, fmean, scale=1.0, mean_const=mean_const, noise_variance=noise_variance,
+                 lik_grads=(dmu, dvar) if likelihood is not None else None)
+    r = seed.r
+    if seed.scalar:
+        rowscale = torch.full((R, N), 2.0 * seed.c, dtype=torch.float64, device=dev)
+    else:
+        rowscale = seed.c.t().mul(2.0).contiguous()
+    _, Tb = ops.tril_product(L, q_sqrt, rowscale=rowscale, want_ssq=False, want_product=True)   # T_bar_r (zeros above the diagonal)
+    Lq = _tril(q_sqrt)                                                                  # band_part(q_sqrt, -1, 0): the GEMMs read stored zeros
+    LT = ops.transpose(L, mode=1)
+    Lbar = ops.gemm_nt(r, q_mu, c_lower=True)                                           # r q_mu^T (the lower tiles)
+    for p in range(R):
+        ops.gemm_nt(Tb[p], Lq[p], beta=1.0, C=Lbar, a_tri=2, b_tri=2, c_lower=True)     # + T_bar_p S_p^T
+    Lbar = _tril(Lbar)
+    g_qs = torch.stack([_tril(ops.gemm_nt(LT, ops.transpose(Tb[p]), a_tri=1, b_tri=1, c_lower=True)) for p in range(R)])   # tril(L^T T_bar_p)
+    g_qs.sub_(Lq)
+    g_qs.diagonal(dim1=1, dim2=2).add_(1.0 / Lq.diagonal(dim1=1, dim2=2))
+    g_qmu = ops.row_stats(LT, V=r.contiguous(), want_sumsq=False)[1].sub_(q_mu)         # L^T r - q_mu
+    Kbar = cholesky_adjoint(LT, LinvT, Lbar)
+    dvs, dlss, _ = spec.adjoint(X, X, Kbar, symmetric=True)
+    g_var, g_ls = spec.pack(dvs, dlss)
+    grads = spec.kernel_grads(g_var, g_ls)
+    if likelihood is None:
+        grads["noise_variance"] = seed.noise_grad(ve, None, ssq, 0.0)
+    grads.update({"q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)})
+    if likelihood is not None:
+        from .likelihoods import device_grad_param
+        name = device_grad_param(likelihood[0])   # (the one Parameter whose derivative the kernel returns as out[1])
+        if name is not None:
+            grads["likelihood_" + name] = lik_out[1:2].clone()
+    return F, grads, info

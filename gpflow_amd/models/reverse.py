@@ -243,6 +243,44 @@ def _lcm_routes(model, *, quadrature, narrow):
     return [(CovarianceRoute(kk, int(v.Z.shape[1])), v) for kk, v in zip(k.kernels, ivs)], float(c), True
 
 
+def vgp_scope(model):
+    """The mean constant of a VGP inside its device paths, else NotImplementedError -- checked when the model is BUILT and again by
+    every route, before anything touches the device: a single-output kernel, a zero or constant mean, and a Gaussian likelihood with
+    one noise variance or a likelihood whose variational expectations the library computes (`device_lik`; at most 16 latents, which
+    for MultiClass are its classes)."""
+    from ..kernels import MultioutputKernel
+    from .. import ops
+    lik, R = model.likelihood, model.q_mu.shape[1]
+    no = lambda what: NotImplementedError(f"VGP: {what}")   # noqa: E731
+    if isinstance(model.kernel, MultioutputKernel):
+        raise no("a multi-output kernel is not built into the full variational model (one kernel shared by the latents)")
+    if isinstance(lik, Gaussian):
+        if lik.is_heteroskedastic:
+            raise no("a heteroskedastic Gaussian likelihood is not built into the full variational model (one noise variance)")
+    elif getattr(lik, "device_lik", "") not in ops.LIKELIHOOD_CODES:
+        raise no(f"the likelihood {type(lik).__name__} has no variational-expectation kernel on the device (`device_lik`)")
+    elif hasattr(lik, "check_device_classes"):
+        lik.check_device_classes(R)   # (ValueError: latents != classes; NotImplementedError: more than 16)
+    c = model.mean_function.constant_value()
+    if c is None:
+        raise no("a zero or constant mean function")
+    return float(c)
+
+
+def vgp_route(model):
+    """(CovarianceRoute, mean constant) for a VGP inside the reverse pass (gradients.vgp_elbo_and_grad), else NotImplementedError:
+    `vgp_scope`, any kernel tree the route takes, a trainable Gaussian noise held as a `variance` Parameter, at most 16 latents for a
+    quadrature likelihood (its kernel's columns per call)."""
+    c = vgp_scope(model)
+    lik = model.likelihood
+    if isinstance(lik, Gaussian):
+        if not lik.has_variance_parameter:
+            raise NotImplementedError("VGP gradients: a Gaussian likelihood with its noise held as a `variance` Parameter")
+    elif model.q_mu.shape[1] > 16:
+        raise NotImplementedError("VGP gradients: at most 16 latents with a quadrature likelihood")
+    return CovarianceRoute(model.kernel, model.data[0].shape[1]), c
+
+
 def regression_route(model):
     """(CovarianceRoute, mean constant) for a GPR / SGPR inside the reverse pass, else NotImplementedError"""
     c = model.mean_function.constant_value()

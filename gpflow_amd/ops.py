@@ -506,6 +506,61 @@ def project_stats(At: torch.Tensor, LqT: torch.Tensor, V: torch.Tensor):
     return s0, fmean, ssq
 
 
+TRIL_TILE = 128   # include/gpk.h: GPK_TRIL_TILE
+
+
+def tril_product_parts(n: int, R: int, device_=None) -> torch.Tensor:
+    """the scratch operand `parts` [R, tiles, n] of tril_product (include/gpk.h: gpk_tril_product; contents at entry do not matter)"""
+    lib = _lib.load()
+    return torch.empty((R, int(lib.gpk_tril_product_tiles(int(n))), n), dtype=torch.float64, device=device_ or device())
+
+
+def tril_product(L: torch.Tensor, S: torch.Tensor, *, rowscale: Optional[torch.Tensor] = None, want_ssq: bool = True,
+                 want_product: bool = False, parts: Optional[torch.Tensor] = None, product_out: Optional[torch.Tensor] = None):
+    """(ssq [R, n] | None, T [R, n, n] | None) of the product of lower-triangular matrices P_r = tril(L) tril(S_r), L [n, n], S [R, n, n]
+    (any leading dimension and batch stride, unit column stride; nothing above either diagonal is read): ssq[r, i] = sum_j P_r[i, j]^2
+    without storing the product -- the marginal variances of the VGP's q(f) -- and / or T_r = diag(rowscale[r]) P_r (rowscale [R, n],
+    None: ones) below the diagonal: the seed of its reverse pass.  A fresh T is zero above the diagonal; `product_out` [R, n, >= n] is
+    written on and below the diagonal only.  parts: the scratch [R, tiles, n] (tril_product_parts), allocated when None."""
+    lib = _lib.load()
+    _chk(L, "L", 2)
+    _chk(S, "S", 3)
+    n = L.shape[0]
+    R = S.shape[0]
+    if L.shape[1] < n or S.shape[1] != n or S.shape[2] < n:
+        raise ValueError(f"tril_product: L must be [n, n] and S [R, n, n], got {tuple(L.shape)} and {tuple(S.shape)}")
+    if S.numel() and n > 1 and S.stride(2) != 1:
+        raise _lib.GpkError("S: last dimension must be contiguous")
+    want_product = want_product or product_out is not None
+    if not (want_ssq or want_product):
+        raise ValueError("tril_product: neither the row sums nor the product was asked for")
+    if rowscale is not None:
+        _chk(rowscale, "rowscale", 2)
+        if not want_product or tuple(rowscale.shape) != (R, n) or not rowscale.is_contiguous():
+            raise ValueError("tril_product: rowscale is a contiguous [R, n] and goes with the stored product")
+    ssq = torch.empty((R, n), dtype=torch.float64, device=L.device) if want_ssq else None
+    if want_ssq:
+        if parts is None:
+            parts = tril_product_parts(n, R, L.device)
+        _chk(parts, "parts", 3)
+        if tuple(parts.shape) != (R, int(lib.gpk_tril_product_tiles(n)), n) or not parts.is_contiguous():
+            raise ValueError("tril_product: parts must be a contiguous [R, tiles, n]")
+    T = None
+    if want_product:
+        T = product_out if product_out is not None else torch.zeros((R, n, n), dtype=torch.float64, device=L.device)
+        _chk(T, "product_out", 3)
+        if T.shape[0] != R or T.shape[1] != n or T.shape[2] < n or (T.numel() and n > 1 and T.stride(2) != 1):
+            raise ValueError("tril_product: product_out must be [R, n, >= n] with unit column stride")
+    if n == 0 or R == 0:
+        return ssq, T
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    rc = lib.gpk_tril_product(_stream(), L.data_ptr(), n, _rowmajor(L, "L"), S.data_ptr(), _rowmajor(S[0], "S"),
+                              int(S.stride(0)) if R > 1 else 0, R, ptr(ssq), ptr(parts) if want_ssq else None, ptr(rowscale), ptr(T),
+                              _rowmajor(T[0], "product_out") if T is not None else 0, int(T.stride(0)) if T is not None and R > 1 else 0)
+    _lib.check(rc, "gpk_tril_product")
+    return ssq, T
+
+
 def gaussian_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[torch.Tensor],
                         ssq: Optional[torch.Tensor], knn: Sequence[float], noise_variance,
                         mean_const: float = 0.0, s0_per_latent: bool = False, want_fvar: bool = False):

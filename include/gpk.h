@@ -599,6 +599,35 @@ int gpk_svgp_elbo_shard_lcm(void* stream, const int* family_host, const double* 
  * n <= 16.  One tiny kernel on `stream`; never synchronises. */
 int gpk_publish_host(void* stream, const double* src, int n, const int* info, void* host_dst, int seq);
 
+/* ---- the full variational GP (gpflow/models/vgp.py:36-180): product of two lower-triangular matrices ------------------------
+ * With L [n, ldl] (the Cholesky factor of K(X, X) + jitter I) and S_r = S + r * stride_s [n, lds], r < R (the q_sqrt of the model),
+ * both row-major and LOWER triangular, the product  P_r = L S_r  is lower triangular again,
+ *     P_r[i, j] = sum_{k = j .. i} L[i, k] S_r[k, j]        (j <= i),
+ * and the marginal variance of the model's q(f) is its row sum of squares (vgp.py:149-152 through conditionals/util.py:151-164 with
+ * white = True and Lm = L):
+ *     ssq[r, i] = sum_{j <= i} P_r[i, j]^2                   ssq [R, n], the `ssq` operand of gpk_*_varexp_sum.
+ * Triangle: only entries with column <= row are READ, of L and of every S_r; what is stored above either diagonal (NaN, Inf,
+ * garbage) never reaches a result -- the band_part(q_sqrt, -1, 0) of the reference, by construction.  A term of the sum above is
+ * formed exactly when j <= k <= i: a NaN at L[i0, k0] reaches P_r[i0, j] for j <= k0 (and so ssq[r, i0] for every r) and nothing
+ * else; a NaN at S_r[k0, j0] reaches P_r[i, j0] for i >= k0 (and so ssq[r, i] for i >= k0) and nothing else.
+ * Outputs, each optional, at least one:
+ *   ssq   [R, n] (with `parts`): the product is not stored;
+ *   T     [R, n, ldt] (batch stride stride_t): T_r[i, j] = rowscale[r, i] * P_r[i, j] for j <= i (rowscale [R, n], may be NULL: 1);
+ *         nothing is written above the diagonal or into the padding (ldt > n).  This is the seed of the reverse pass,
+ *         T_bar = 2 diag(dF/dfvar) L S.
+ * parts [R, gpk_tril_product_tiles(n), n]: scratch of the row sums -- entry [r, t, i] is the sum over the columns of tile column t
+ *   (GPK_TRIL_TILE columns each) for t <= i / GPK_TRIL_TILE; the call writes every entry it later reads (its contents at entry do not
+ *   matter), touches nothing outside that extent, and sums the tile columns in the order t = 0, 1, ...: no floating-point atomics,
+ *   two calls on the same inputs give the same bits.  Needed with ssq, ignored (may be NULL) without.
+ * One 128 x 128 output tile per workgroup, fp64 MFMA over the tile-block range j .. i only (n^3 / 3 multiply-adds per r; the
+ * 16 x 16 blocks on the two diagonals by VALU under the exact predicate), the tiles with the longest K range first.
+ * GPK_E_ARG before anything is enqueued: n < 0, R < 0, ldl / lds / ldt < n, L or S NULL, neither ssq nor T, ssq without parts,
+ * rowscale without T.  n == 0 or R == 0: returns 0, nothing is enqueued or written. */
+#define GPK_TRIL_TILE 128
+int gpk_tril_product_tiles(int n);   /* ceil(n / GPK_TRIL_TILE) */
+int gpk_tril_product(void* stream, const double* L, int n, long ldl, const double* S, long lds, long stride_s, int R,
+                     double* ssq, double* parts, const double* rowscale, double* T, long ldt, long stride_t);
+
 /* Optional per-launch timing of the GEMM kernel (HIP events on the launch stream) for the roofline
  * leg of bench.py: enable(1) starts recording, collect() synchronises and returns the summed kernel
  * time, launch count and ALGORITHMIC flops (useful multiply-adds only) since enable. */
