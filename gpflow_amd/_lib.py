@@ -100,6 +100,16 @@ _SIGS = {
     "gpk_dot_kernel_diag": (c_int, [c_void_p, c_int, c_int, _dp, c_int, c_long, c_int, C.POINTER(c_double), c_int, c_double, c_int,
                                     _dp, _dp]),
     "gpk_dot_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, c_int, _dp, c_int, c_int, _dp, _dp, c_long]),
+    "gpk_arccos_kernel_matrix": (c_int, [c_void_p, c_int, _dp, c_int, c_long, _dp, c_int, c_long, c_int, C.POINTER(c_double), c_int,
+                                         c_double, c_double, c_double, c_int, _dp, c_long]),
+    "gpk_arccos_kernel_matrix_combine": (c_int, [c_void_p, c_int, c_int, _dp, c_int, c_long, _dp, c_int, c_long, c_int,
+                                                 C.POINTER(c_double), c_int, c_double, c_double, c_double, _dp, c_long, _dp, c_long]),
+    "gpk_arccos_kernel_diag": (c_int, [c_void_p, c_int, c_int, _dp, c_int, c_long, c_int, C.POINTER(c_double), c_int, c_double, c_double,
+                                       _dp, _dp]),
+    "gpk_arccos_adjoint_stage": (c_int, [c_void_p, c_int, _dp, c_int, c_long, _dp, c_int, c_long, c_int, C.POINTER(c_double), c_int,
+                                         c_double, c_double, _dp, c_long, _dp, c_long, _dp]),
+    "gpk_arccos_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, _dp, c_long, c_int, c_int, C.POINTER(c_double), c_int,
+                                        _dp, _dp, _dp, _dp, c_long]),
     "gpk_tril_product_tiles": (c_int, [c_int]),
     "gpk_tril_product": (c_int, [c_void_p, _dp, c_int, c_long, _dp, c_long, c_long, c_int, _dp, _dp, _dp, _dp, c_long, c_long]),
     "gpk_adam_step": (c_int, [c_void_p, _dp, _dp, _dp, _dp, c_long, c_double, c_double, c_double, c_double, c_int]),

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .leaf import DotLeaf, Leaf
+from .leaf import ArcLeaf, DotLeaf, Leaf
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -225,6 +225,27 @@ def dot_kernel_adjoint(leaf: DotLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: t
     return dw, (doff if leaf.row.extras else doff[:0]), Abar
 
 
+def arccos_kernel_adjoint(leaf: ArcLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, symmetric: bool):
+    """Adjoint of an ArcCosine leaf (kernels/misc.py) given Kbar [n1, n2].  Returns (d/dvariance [1]; shape gradient:
+    d/dweight_variances [1 or D], then d/dbias_variance [1]; A_bar [n1, D]); symmetric=True (Bm is A, Kbar symmetric): A_bar collects
+    both arguments and the diagonal of K(A, A) is the by-index one (include/gpk.h).
+
+    K depends on the inputs and on (w, b) through s_ik, p_i and q_k.  ONE stage (ops.arccos_adjoint_stage) recomputes them per tile and
+    leaves G = Kbar .* dk/ds and the per-tile partials of rho_i = sum_k Kbar_ik dk/dp_i, gamma_k = sum_i Kbar_ik dk/dq_k and
+    sum Kbar .* k / variance; ONE contraction R = G [1, B] (the right-hand side is ops.moment_rows(Bm), as in dot_kernel_adjoint);
+    ONE one-workgroup tail (ops.arccos_adjoint_tail) that adds the norm terms 2 w_j a_ij rho_i, sum_i rho_i a_ij^2, sum_k gamma_k b_kj^2."""
+    D = A.shape[1]
+    if leaf.ard and leaf.n_weights != D:
+        raise ValueError(f"weight_variances has {leaf.n_weights} entries, input dimension is {D}")
+    A = A if A.is_contiguous() else A.contiguous()
+    Bm = A if symmetric else (Bm if Bm.is_contiguous() else Bm.contiguous())
+    parts = ops.arccos_adjoint_parts(A.shape[0], Bm.shape[0], A.device)
+    G = ops.arccos_adjoint_stage(A, None if symmetric else Bm, Kbar if Kbar.is_contiguous() else Kbar.contiguous(), parts, **leaf.keywords())
+    R = splitk_gemm_nt(G, ops.moment_rows(Bm))   # [n1, 1 + 2 D]: row sums, G B, (G B^2 unused)
+    dv, dw, db, Abar = ops.arccos_adjoint_tail(R, A, None if symmetric else Bm, parts, weight_variances=leaf.weight_variances)
+    return dv, torch.cat([dw, db]), Abar
+
+
 class Member:
     """One leaf of a KernelSpec as the tree walkers call it: its host values (`leaf`), the input columns it sees (`cols`: an index array,
     or None for all), a Periodic leaf's `period`, and every answer that depends on the KIND of leaf.  This base class holds what the
@@ -340,6 +361,44 @@ class DotMember(Member):
         ls_device(self.leaf.variance, self.leaf.n_variance, device)   # (the weights of the dot-product tail)
 
 
+class ArcMember(Member):
+    """an ArcCosine leaf (leaf.ArcLeaf), built and folded by the `gpk_arccos_*` entry points.  K(x, x) = variance jf p(x)^order depends
+    on the row: `kdiag_rows` / `fold_kdiag`; one variance entry, the shape gradient is d/dweight_variances [1 or D], then
+    d/dbias_variance."""
+    constant_diagonal = False
+    matrix, combine = "arccos_kernel_matrix", "arccos_kernel_matrix_combine"
+    leaf_adjoint = staticmethod(arccos_kernel_adjoint)
+
+    def kdiag(self) -> float:
+        raise NotImplementedError("K(x, x) of an ArcCosine member depends on the row: this caller takes the diagonal for one scalar and "
+                                  "has not been converted to KernelSpec.kdiag_rows")
+
+    def kdiag_rows(self, X) -> torch.Tensor:
+        """K(x_b, x_b) as a fresh [rows] tensor"""
+        return ops.arccos_kernel_diag(self.view(X), **self.leaf.keywords())
+
+    def fold_kdiag(self, X, acc, op: str) -> None:
+        """acc <- acc .* K(x_b, x_b) or acc + K(x_b, x_b) in place"""
+        ops.arccos_kernel_diag(self.view(X), acc, op=op, out=acc, **self.leaf.keywords())
+
+    def diag_adjoint(self, X, bar):
+        """d/dvariance = sum_b bar_b kd_b / variance (the diagonal at variance 1); g = bar .* dkd/dp and, from ONE thin product of g with
+        ops.moment_rows(X), d/dw_j = sum_b g_b x_bj^2 and d/dbias = sum_b g_b"""
+        leaf = self.leaf
+        Xi = self.view(X)
+        Xi = Xi if Xi.is_contiguous() else Xi.contiguous()
+        D = Xi.shape[1]
+        kw = leaf.keywords()
+        dv = ops.arccos_kernel_diag(Xi, bar, op="mul", **dict(kw, variance=1.0)).sum().reshape(1)
+        g = ops.arccos_kernel_diag(Xi, bar, op="dp", **kw)
+        m = ops.gemm_nt(g.reshape(1, -1), ops.moment_rows(Xi))[0]      # [1 + 2 D]: sum g, sum g x_j, sum g x_j^2
+        dw = m[1 + D:]
+        return dv, torch.cat([dw if leaf.ard else dw.sum().reshape(1), m[0:1]])
+
+    def parameter_names(self) -> tuple:
+        return self.leaf.parameters
+
+
 class PeriodicMember(StationaryMember):
     """a Periodic leaf (kernels/periodic.py): a stationary member whose view of the inputs adds the warp Phi (ops.periodic_warp) after
     the column selection.  `leaf` is in the DEVICE form -- the base family over the 2 D_i warped columns with lengthscales 2 l, an ARD
@@ -396,10 +455,10 @@ class KernelSpec:
     """What the reverse pass needs to know about the covariance function: ONE kernel leaf, or a Sum / Product of leaves -- flat, or
     nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220
     `Sum`, :305-315 `Product`; the reference differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).
-    members: leaves (leaf.Leaf, leaf.DotLeaf), given as such or as tuples (family, variance, lengthscales[, alpha]); op: None | "add" |
+    members: leaves (leaf.Leaf, leaf.DotLeaf, leaf.ArcLeaf), given as such or as tuples (family, variance, lengthscales[, alpha]); op: None | "add" |
     "mul" | tree.
 
-    The constructor chooses ONE member object per leaf (`parts`: a StationaryMember, StaticMember, DotMember or PeriodicMember), the
+    The constructor chooses ONE member object per leaf (`parts`: a StationaryMember, StaticMember, DotMember, ArcMember or PeriodicMember), the
     only place where the kind of a leaf is asked.  Everything else here is about the TREE: `_build`, `_constant`, `_kd`, `_kd_rows`,
     `_diag_adjoint`, `_dkd` and `_adjoint` are the only walkers, and at a leaf each is one call on the member object.
 
@@ -416,7 +475,7 @@ class KernelSpec:
         """members: leaves or tuples, see the class; cols[i]: the input columns member i sees (its `active_dims` as an index
         list, kernels/base.py:90-109) or None for all of them; periods[i]: None, or the period (0-d or [D_i]) of a Periodic member,
         whose leaf is then in the device form (PeriodicMember)."""
-        self.members = [m if isinstance(m, (Leaf, DotLeaf)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
+        self.members = [m if isinstance(m, (Leaf, DotLeaf, ArcLeaf)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
         # (k0 + k1) * k2 (kernels/base.py:223-329: a Combination holds kernels, which may be Combinations of the other kind).
@@ -436,9 +495,10 @@ class KernelSpec:
             raise ValueError("one period (or None) per member")
         self.periods = [None if p is None else np.asarray(p, dtype=np.float64) for p in periods]
         for leaf, p in zip(self.members, self.periods):
-            if p is not None and (isinstance(leaf, DotLeaf) or leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
+            if p is not None and (isinstance(leaf, (DotLeaf, ArcLeaf)) or leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
                 raise ValueError("a periodic member is a leaf with a distance over the warped columns, its period 0-d or [D]")
         self.parts = [PeriodicMember(leaf, c, p) if p is not None else DotMember(leaf, c) if isinstance(leaf, DotLeaf)
+                      else ArcMember(leaf, c) if isinstance(leaf, ArcLeaf)
                       else StaticMember(leaf, c) if leaf.is_static else StationaryMember(leaf, c)
                       for leaf, c, p in zip(self.members, self.cols, self.periods)]
 
@@ -764,7 +824,7 @@ class _Seed:
         return torch.mul(ve, -scale / nv).add_(scale / nv * B * P * (k0 - 0.5)).reshape(1)
 
 
-_ROW_DIAGONAL = "a dot-product member (Linear, Polynomial): K(x, x) depends on the row, which is not built into "
+_ROW_DIAGONAL = "a dot-product or ArcCosine member (Linear, Polynomial, ArcCosine): K(x, x) depends on the row, which is not built into "
 
 
 def _knn_terms(spec: KernelSpec, Xb, s0):

@@ -1,0 +1,87 @@
+"""The ArcCosine kernel (gpflow/kernels/misc.py): the covariance of an infinitely wide one-layer network (Cho & Saul, 2009).
+
+    s(x, y) = sum_j weight_variances_j x_j y_j + bias_variance          p(x) = s(x, x)
+    theta   = acos(eps + (1 - 2 eps) s / (sqrt p(x) sqrt p(y)))
+    K       = (variance / pi) J_order(theta) p(x)^(order/2) p(y)^(order/2)         K_diag = variance (J_order(0) / pi) p(x)^order
+
+Built in one pass by gpk_arccos_kernel_matrix (csrc/arccosine/arccosine.hip), folded into a Sum / Product in place by
+gpk_arccos_kernel_matrix_combine.  Like the dot-product kernels it is NOT a DeviceLeaf -- its diagonal depends on the row, so every
+fused route that takes K_diag for the variance (`kernels.base.is_device_leaf`) declines it and the composed routes run -- and it is not
+a dot-product leaf either: each element needs both row norms and an acos.  `is_arc_leaf` is its predicate, `leaf()` a leaf.ArcLeaf.
+K(X, X) takes its diagonal by index (include/gpk.h); K_diag is the closed form, a relative 1.4e-8 from it at order 0, as in the reference."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from ..base import Parameter, positive
+from .. import ops
+from ..leaf import ARC_PARAMETERS, ArcLeaf, check_order
+from .base import ActiveDims, Kernel
+
+
+class ArcCosine(Kernel):
+    """misc.py `ArcCosine`: `order` 0, 1 or 2 (a constant; anything else raises ValueError, as the reference does);
+    `weight_variances` one weight, or one per active input column (ARD)"""
+    arc_leaf = True
+    implemented_orders = {0, 1, 2}
+
+    def __init__(self, order: int = 0, variance=1.0, weight_variances=1.0, bias_variance=1.0, active_dims: Optional[ActiveDims] = None,
+                 name: Optional[str] = None):
+        self.order = check_order(order)     # ValueError before anything else
+        super().__init__(active_dims=active_dims, name=name)
+        self.variance = Parameter(variance, transform=positive())
+        self.weight_variances = Parameter(weight_variances, transform=positive())
+        self.bias_variance = Parameter(bias_variance, transform=positive())
+        if self.variance.numpy().ndim > 0 or self.bias_variance.numpy().ndim > 0:
+            raise ValueError("variance and bias_variance are scalars")
+        w = self.weight_variances.numpy()
+        if w.ndim > 1:
+            raise ValueError(f"weight_variances of shape {w.shape}: one weight, or one per active input column")
+        if w.ndim == 1 and not isinstance(self._active_dims, slice) and w.shape[0] != len(self._active_dims):   # gpflow/kernels/base.py:158-178
+            raise ValueError(f"Size of `active_dims` {self._active_dims} does not match size of ard parameter ({w.shape[0]})")
+
+    @property
+    def ard(self) -> bool:
+        return self.weight_variances.numpy().ndim > 0
+
+    def leaf_params(self) -> tuple:
+        return tuple(getattr(self, name) for name in ARC_PARAMETERS)
+
+    def leaf(self) -> ArcLeaf:
+        return ArcLeaf.of(self.order, [p.numpy() for p in self.leaf_params()])
+
+    def check_width(self, d: int) -> None:
+        """ValueError, before the device, for ARD weights that do not fit the d input columns the kernel sees"""
+        w = self.weight_variances.numpy()
+        if w.ndim == 1 and w.shape[0] != d:
+            raise ValueError(f"weight_variances has {w.shape[0]} entries, the kernel sees {d} input columns")
+
+    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
+        self.check_width(X.shape[-1])
+        return ops.arccos_kernel_matrix(X, X2, diag_add=diag_add, lower_only=lower_only, out=out, **self.leaf().keywords())
+
+    def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
+        """out <- out .* K or out + K in place, as DeviceLeaf.K_fold"""
+        self.check_width(X.shape[-1])
+        return ops.arccos_kernel_matrix_combine(X, X2, out, op=op, diag_add=diag_add, out=out, **self.leaf().keywords())
+
+    def K(self, X, X2=None) -> torch.Tensor:
+        """leading batch dimensions as Linear.K: flattened to rows and restored"""
+        X = ops.to_device(X)
+        D = X.shape[-1]
+        if X2 is None:
+            if X.dim() == 2:
+                return self.K_into(X, None, None)
+            lead, n = X.shape[:-2], X.shape[-2]
+            return torch.stack([self.K_into(x.contiguous(), None, None) for x in X.reshape(-1, n, D)]).reshape(*lead, n, n)
+        X2 = ops.to_device(X2)
+        Kf = self.K_into(X.reshape(-1, D).contiguous(), X2.reshape(-1, D).contiguous(), None)
+        return Kf.reshape(*X.shape[:-1], *X2.shape[:-1])
+
+    def K_diag(self, X) -> torch.Tensor:
+        """the row diagonal on the device (gpk_arccos_kernel_diag), the closed form; leading batch dimensions allowed"""
+        X = ops.to_device(X)
+        self.check_width(X.shape[-1])
+        return ops.arccos_kernel_diag(X.reshape(-1, X.shape[-1]).contiguous(), **self.leaf().keywords()).reshape(X.shape[:-1])

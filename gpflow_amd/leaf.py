@@ -199,6 +199,72 @@ class DotLeaf(collections.namedtuple("_DotLeafFields", "row variance offset degr
         return {"lengthscales": g[:0], **{name: g[j:j + 1] for j, name in enumerate(self.row.extras)}}
 
 
+ARC_ORDERS = (0, 1, 2)
+ARC_PARAMETERS = ("variance", "weight_variances", "bias_variance")
+
+
+def check_order(order) -> int:
+    """the ArcCosine's order as an int; ValueError unless it is 0, 1 or 2 (gpflow/kernels/misc.py: `implemented_orders`)"""
+    if isinstance(order, bool) or not isinstance(order, (int, float, np.integer, np.floating)) or order not in ARC_ORDERS:
+        raise ValueError(f"ArcCosine(order={order!r}): requested kernel order is not implemented, it is one of {ARC_ORDERS}")
+    return int(order)
+
+
+class ArcLeaf(collections.namedtuple("_ArcLeafFields", "order variance weight_variances bias_variance")):
+    """One ArcCosine leaf's host values (gpflow/kernels/misc.py), immutable: `order` 0, 1 or 2, a constant of the leaf without a
+    gradient; `variance` a float; `weight_variances` 0-d (one weight) or [D] (ARD); `bias_variance` a float.  Its diagonal K(x, x)
+    depends on the row and each element needs both row norms and an acos: it is no row of FAMILIES and none of DOT_FAMILIES -- the
+    gpk_arccos_* entry points take it (ops.arccos_kernel_matrix, ...)."""
+    __slots__ = ()
+    is_plain = False
+    family = "ArcCosine"
+    parameters = ARC_PARAMETERS
+
+    def __new__(cls, order, variance, weight_variances=1.0, bias_variance=1.0):
+        w = np.asarray(weight_variances, dtype=np.float64)
+        if w.ndim > 1:
+            raise ValueError(f"weight_variances of shape {w.shape}: one weight, or one per active input column")
+        return tuple.__new__(cls, (check_order(order), float(variance), w, float(bias_variance)))
+
+    @classmethod
+    def of(cls, order, values) -> "ArcLeaf":
+        """from the values in Parameter order (ARC_PARAMETERS) and the constant order"""
+        return cls(order, **dict(zip(ARC_PARAMETERS, values)))
+
+    def replace(self, values) -> "ArcLeaf":
+        return ArcLeaf.of(self.order, values)
+
+    @property
+    def ard(self) -> bool:
+        return self.weight_variances.ndim == 1
+
+    @property
+    def n_weights(self) -> int:
+        """entries of the weight gradient: 1, or D for ARD weights"""
+        return int(self.weight_variances.size) if self.ard else 1
+
+    @property
+    def n_shape(self) -> int:
+        """entries of the shape gradient: d/dweight_variances, then d/dbias_variance"""
+        return self.n_weights + 1
+
+    def keywords(self) -> dict:
+        """as the `ops.arccos_*` builders take a leaf"""
+        return dict(order=self.order, variance=self.variance, weight_variances=self.weight_variances, bias_variance=self.bias_variance)
+
+    def host(self, d: int):
+        """(host array of the weights, ard) of the C-ABI"""
+        w = np.atleast_1d(self.weight_variances)
+        if self.ard and w.size != d:
+            raise ValueError(f"weight_variances has {w.size} entries, input dimension is {d}")
+        return _lib.host_doubles(w.tolist()), int(self.ard)
+
+    def split_shape(self, g) -> dict:
+        """a shape gradient as {"lengthscales": empty, "weight_variances": [1 or D], "bias_variance": [1]}"""
+        nw = self.n_weights
+        return {"lengthscales": g[:0], "weight_variances": g[:nw], "bias_variance": g[nw:nw + 1]}
+
+
 def check_degree(degree) -> int:
     """the Polynomial's degree as an int; NotImplementedError unless it is integral and in [1, DOT_MAX_DEGREE]"""
     try:

@@ -10,7 +10,7 @@ from .. import gradients
 from ..base import FillTriangular
 from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
-from ..kernels.base import Combination, gradient_spec, is_dot_leaf, reverse_leaf
+from ..kernels.base import Combination, gradient_spec, has_row_diagonal_leaf, reverse_leaf
 from ..kernels.periodic import Periodic
 from ..likelihoods import Gaussian
 from ..mean_functions import Constant
@@ -48,15 +48,16 @@ def minibatch_scale(num_data, rows) -> float:
 def _supported_stationary(k) -> bool:
     """a leaf of the reverse pass (kernels.base.reverse_leaf) with a constant diagonal: an isotropic-stationary kernel, a static one, or
     a Periodic kernel over a stationary base"""
-    return reverse_leaf(k) is not None and not is_dot_leaf(k)
+    return reverse_leaf(k) is not None and not has_row_diagonal_leaf(k)
 
 
-ROW_DIAGONAL = "a dot-product kernel or member (Linear, Polynomial), whose K(x, x) depends on the row,"
+ROW_DIAGONAL = "a dot-product or ArcCosine kernel or member (Linear, Polynomial, ArcCosine), whose K(x, x) depends on the row,"
 
 
 def has_row_diagonal(k) -> bool:
-    """a dot-product kernel (kernels/linears.py) anywhere under k -- in a Sum / Product, or behind a multi-output wrapper"""
-    if is_dot_leaf(k):
+    """a dot-product kernel (kernels/linears.py) or an ArcCosine kernel (kernels/misc.py) anywhere under k -- in a Sum / Product, or
+    behind a multi-output wrapper"""
+    if has_row_diagonal_leaf(k):
         return True
     members = [k.kernel] if isinstance(k, SharedIndependent) else getattr(k, "kernels", [])
     return any(has_row_diagonal(m) for m in members)
@@ -82,7 +83,7 @@ class CovarianceRoute:
         found = reverse_leaf(kernel, input_dim)
         if found is None:
             raise NotImplementedError("gradients: a SquaredExponential / Matern / Exponential / RationalQuadratic / White / Constant / "
-                                      "Periodic / Linear / Polynomial kernel, or a Sum / Product (possibly nested) of them")
+                                      "Periodic / Linear / Polynomial / ArcCosine kernel, or a Sum / Product (possibly nested) of them")
         leaf, period, params = found
         self.spec, self.members = gradients.KernelSpec([leaf], periods=[period]), [params]
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .leaf import FAMILIES, DotLeaf, Leaf
+from .leaf import FAMILIES, ArcLeaf, DotLeaf, Leaf
 
 NB = 128
 KERNEL_FAMILIES = {f.name: f.code for f in FAMILIES}                      # name -> GPK_KERN_* (include/gpk.h)
@@ -261,6 +261,144 @@ def dot_adjoint_tail(R: torch.Tensor, A: torch.Tensor, w: torch.Tensor, *, symme
                                   int(bool(symmetric)), small.data_ptr(), Abar.data_ptr(), _rowmajor(Abar, "A_bar"))
     _lib.check(rc, "gpk_dot_adjoint_tail")
     return small[:nw], small[nw:], Abar
+
+
+# ------------------------------------------------------------------------------------------------ ArcCosine kernel (arccosine/arccosine.hip)
+ARC_TILE = 64   # include/gpk.h: GPK_ARC_TILE
+
+
+def _arc_leaf_args(order, variance, weight_variances, bias_variance, d: int):
+    """(order, host weights, ard, variance, bias) of the gpk_arccos_* entry points for a leaf given by keywords: ArcLeaf.host"""
+    leaf = ArcLeaf(order, variance, weight_variances, bias_variance)
+    return (leaf.order, *leaf.host(d), leaf.variance, leaf.bias_variance)
+
+
+def arccos_kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, order: int = 0, variance=1.0, weight_variances=1.0,
+                         bias_variance=1.0, diag_add: float = 0.0, lower_only: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2] of an ArcCosine leaf of order 0, 1 or 2.  `weight_variances`
+    one weight or [D].  The symmetric build is exactly symmetric and takes its diagonal by index (include/gpk.h)."""
+    lib = _lib.load()
+    n1, n2, d, out = _kernel_operands(X1, X2, None, out, zero_new=lower_only)
+    if n1 == 0 or n2 == 0:
+        return out
+    order, w, ard, v, b = _arc_leaf_args(order, variance, weight_variances, bias_variance, d)
+    rc = lib.gpk_arccos_kernel_matrix(_stream(), order, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, w, ard, v, b,
+                                      float(diag_add), int(lower_only), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_arccos_kernel_matrix")
+    return out
+
+
+def arccos_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, order: int = 0, variance=1.0,
+                                 weight_variances=1.0, bias_variance=1.0, diag_add: float = 0.0,
+                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = G .* K(X1, X2) (op "mul") or G + K(X1, X2) (op "add"), K recomputed on the fly; `out` may be G itself.  X2 None: K(X1, X1)
+    with the diagonal by index; `diag_add` goes onto the diagonal of the combined result."""
+    if op not in ("mul", "add"):
+        raise ValueError(f"arccos_kernel_matrix_combine: op {op!r} is not 'mul' or 'add'")
+    lib = _lib.load()
+    n1, n2, d, out = _kernel_operands(X1, X2, G, out)
+    if n1 == 0 or n2 == 0:
+        return out
+    order, w, ard, v, b = _arc_leaf_args(order, variance, weight_variances, bias_variance, d)
+    rc = lib.gpk_arccos_kernel_matrix_combine(_stream(), order, {"mul": 1, "add": 2}[op], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
+                                              *_x2_args(X2, n2), d, w, ard, v, b, float(diag_add), G.data_ptr(), _rowmajor(G, "G"),
+                                              out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_arccos_kernel_matrix_combine")
+    return out
+
+
+def arccos_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op: str = "k", order: int = 0, variance=1.0,
+                       weight_variances=1.0, bias_variance=1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The row diagonal kd [n] = variance jf p^order (jf = 1, 1, 3) of an ArcCosine leaf over the rows of X [n, D] (op "k"), or
+    g .* kd ("mul"), g + kd ("add"), g .* dkd/dp ("dp") with g [n]; `out` may be g.  The closed form: NOT the diagonal of
+    arccos_kernel_matrix(X, None) bit for bit (include/gpk.h)."""
+    lib = _lib.load()
+    _chk(X, "X", 2)
+    n, d = X.shape
+    if d < 1 or d > MAX_D:
+        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
+    if op not in ("k", "mul", "add", "dp"):
+        raise ValueError(f"arccos_kernel_diag: op {op!r} is not 'k', 'mul', 'add' or 'dp'")
+    if (op == "k") != (g is None):
+        raise ValueError("arccos_kernel_diag: g goes with the ops 'mul', 'add' and 'dp' and only with them")
+    if g is not None:
+        _chk(g, "g", 1)
+        if g.shape[0] != n or not g.is_contiguous():
+            raise ValueError("arccos_kernel_diag: g must be a contiguous [n]")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=X.device)
+    _chk(out, "out", 1)
+    if out.shape[0] != n or not out.is_contiguous():
+        raise ValueError("arccos_kernel_diag: out must be a contiguous [n]")
+    if n == 0:
+        return out
+    order, w, ard, v, b = _arc_leaf_args(order, variance, weight_variances, bias_variance, d)
+    rc = lib.gpk_arccos_kernel_diag(_stream(), order, {"k": 0, "mul": 1, "add": 2, "dp": 3}[op], X.data_ptr(), n, _rowmajor(X, "X"), d, w,
+                                    ard, v, b, None if g is None else g.data_ptr(), out.data_ptr())
+    _lib.check(rc, "gpk_arccos_kernel_diag")
+    return out
+
+
+def arccos_adjoint_parts(n1: int, n2: int, device_=None) -> torch.Tensor:
+    """the scratch operand `parts` of arccos_adjoint_stage / _tail: tc n1 + tr n2 + tr tc doubles, tr / tc the tile rows / columns of
+    ARC_TILE (include/gpk.h: its documented extent); its contents at entry do not matter"""
+    tr, tc = -(-int(n1) // ARC_TILE), -(-int(n2) // ARC_TILE)
+    return torch.empty(tc * int(n1) + tr * int(n2) + tr * tc, dtype=torch.float64, device=device_ or device())
+
+
+def arccos_adjoint_stage(X1: torch.Tensor, X2: Optional[torch.Tensor], Kbar: torch.Tensor, parts: torch.Tensor, *, order: int = 0,
+                         variance=1.0, weight_variances=1.0, bias_variance=1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pass over Kbar [n1, n2]: returns G = Kbar .* dK/ds (`out` may be Kbar itself) and fills `parts` (arccos_adjoint_parts) with
+    the per-tile sums of Kbar .* dK/dp (by row), Kbar .* dK/dq (by column) and Kbar .* K / variance.  X2 None: K(X1, X1), the diagonal
+    by index.  Deterministic: a second call gives the same bits."""
+    lib = _lib.load()
+    n1, n2, d, out = _kernel_operands(X1, X2, Kbar, out)
+    _chk(parts, "parts", 1)
+    tr, tc = -(-n1 // ARC_TILE), -(-n2 // ARC_TILE)
+    if not parts.is_contiguous() or parts.numel() < tc * n1 + tr * n2 + tr * tc:
+        raise ValueError(f"arccos_adjoint_stage: parts must be a contiguous [>= {tc * n1 + tr * n2 + tr * tc}] (ops.arccos_adjoint_parts)")
+    if n1 == 0 or n2 == 0:
+        return out
+    order, w, ard, v, b = _arc_leaf_args(order, variance, weight_variances, bias_variance, d)
+    rc = lib.gpk_arccos_adjoint_stage(_stream(), order, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, w, ard, v, b,
+                                      Kbar.data_ptr(), _rowmajor(Kbar, "Kbar"), out.data_ptr(), _rowmajor(out, "out"), parts.data_ptr())
+    _lib.check(rc, "gpk_arccos_adjoint_stage")
+    return out
+
+
+def arccos_adjoint_tail(R: torch.Tensor, A: torch.Tensor, Bm: Optional[torch.Tensor], parts: torch.Tensor, *,
+                        weight_variances) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(d/dvariance [1], d/dweight_variances [1 or D], d/dbias_variance [1], A_bar [n1, D]) of an ArcCosine leaf from R [n1, >= 1 + D]
+    = G [1, B], the `parts` of arccos_adjoint_stage, the first kernel argument A [n1, D] and the second Bm [n2, D] (None: symmetric --
+    Bm is A, Kbar symmetric, A_bar collects both arguments); include/gpk.h: gpk_arccos_adjoint_tail -- one launch, bit-identical
+    when repeated."""
+    lib = _lib.load()
+    _chk(R, "R", 2)
+    _chk(A, "A", 2)
+    _chk(parts, "parts", 1)
+    n1, d = A.shape
+    if Bm is not None:
+        _chk(Bm, "Bm", 2)
+    n2 = n1 if Bm is None else Bm.shape[0]
+    w = np.asarray(weight_variances, dtype=np.float64)
+    tr, tc = -(-n1 // ARC_TILE), -(-n2 // ARC_TILE)
+    if R.shape[0] != n1 or R.shape[1] < 1 + d or d < 1 or d > MAX_D or (Bm is not None and Bm.shape[1] != d) or w.ndim > 1 \
+            or (w.ndim == 1 and w.size != d) or not parts.is_contiguous() or parts.numel() < tc * n1 + tr * n2 + tr * tc:
+        raise ValueError("arccos_adjoint_tail: R must be [n1, >= 1 + D], Bm [n2, D], weight_variances one weight or [D], D in [1, 64], "
+                         "parts the stage's (ops.arccos_adjoint_parts)")
+    ard = int(w.ndim == 1)
+    nw = d if ard else 1
+    small = torch.zeros(nw + 2, dtype=torch.float64, device=A.device)
+    Abar = torch.zeros((n1, d), dtype=torch.float64, device=A.device) if n2 == 0 else torch.empty((n1, d), dtype=torch.float64, device=A.device)
+    if n1 == 0 or n2 == 0:
+        return small[:1], small[1:1 + nw], small[1 + nw:], Abar
+    rg = torch.empty(n1 + n2, dtype=torch.float64, device=A.device)
+    rc = lib.gpk_arccos_adjoint_tail(_stream(), R.data_ptr(), _rowmajor(R, "R"), A.data_ptr(), _rowmajor(A, "A"), n1,
+                                     None if Bm is None else Bm.data_ptr(), 0 if Bm is None else _rowmajor(Bm, "Bm"), n2, d,
+                                     _lib.host_doubles(np.atleast_1d(w).tolist()), ard, parts.data_ptr(), rg.data_ptr(), small.data_ptr(),
+                                     Abar.data_ptr(), _rowmajor(Abar, "A_bar"))
+    _lib.check(rc, "gpk_arccos_adjoint_tail")
+    return small[:1], small[1:1 + nw], small[1 + nw:], Abar
 
 
 def diag_add_(A: torch.Tensor, v: torch.Tensor) -> torch.Tensor:

@@ -513,6 +513,67 @@ int gpk_dot_kernel_diag(void* stream, int family, int op, const double* X, int n
  *   dF/da_ij = w_j (G B)_ij.  One workgroup, fixed summation order: a second call is bit-identical. */
 int gpk_dot_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, int d, const double* w_dev, int ard,
                          int symmetric, double* dsmall, double* Abar, long ldab);
+/* ---- ArcCosine kernel (arccosine/arccosine.hip; gpflow/kernels/misc.py) -------------------------------------------------------
+ * With w (weight_variances: w_host, HOST pointer, d entries if ard, else one), b (bias_variance), v (variance), eps = 1e-15:
+ *     s(x, y) = sum_j (x_j w_j) y_j + b        p(x) = s(x, x)        c = s / (sqrt p(x) sqrt p(y))
+ *     theta = acos(clamp(eps + (1 - 2 eps) c))
+ *     J_0 = pi - theta   J_1 = sin theta + (pi - theta) cos theta   J_2 = 3 sin theta cos theta + (pi - theta)(1 + 2 cos^2 theta)
+ *     K(x, y) = (v / pi) J_order(theta) p(x)^(order/2) p(y)^(order/2)        K_diag(x) = v jf p(x)^order,  jf = 1, 1, 3
+ * order in {0, 1, 2}.  x_j w_j is formed first (one rounding), the sum over j is an fma chain over ascending j from 0.0, b is added
+ * last; p comes from the same chain, so p of a row as first and as second argument has the same bits.  Not a GPK_KERN_* family, not a
+ * GPK_DOT_* code; no fused driver takes it (K(x, x) depends on the row).
+ *  1. DIAGONAL BY INDEX: with X2 == NULL the element (i, i) takes c = 1 because row index == column index, never by comparing
+ *     values: its acos argument is the double 1.0 - 1e-15, its value (v / pi) J(acos(1 - eps)) p_i^order; in the adjoint stage its
+ *     angular derivative is zero and only p_i^order differentiates.  K_diag (gpk_arccos_kernel_diag) is the closed form and is NOT
+ *     the diagonal of K(X, X) bit for bit (a relative 1.4e-8 apart at order 0, as in the reference).
+ *     (A row that holds a NaN or an Inf makes its own diagonal element NaN as well: the constant enters as fma(sqrt p sqrt q, 0, 1 - eps).)
+ *  2. RANGE: the acos argument is clamped to [-1, 1] by comparisons that a NaN fails, so a NaN / Inf in a row of X1 (X2) makes
+ *     exactly that row (column) of K NaN.
+ *  3. (dJ/dtheta)(dtheta/d arg) = 1 / sin theta, pi - theta, 4 J_1 for orders 0, 1, 2, with cos theta = the clamped argument and
+ *     sin theta = sqrt((1 - cos)(1 + cos)): acos and sqrt only.  Order 0 is infinite where the argument is +-1 off the diagonal.
+ * Every entry point returns, before any launch: GPK_E_ARG for d outside 1 .. GPK_MAX_D, w_host == NULL, a weight that is negative or
+ * not finite, b <= 0 or not finite, v not finite, a negative size, a leading dimension that is too small, an op out of range, a NULL
+ * operand that has elements; GPK_E_UNSUPPORTED for an order outside 0 .. 2; 0 without a launch for an operand without elements.
+ *
+ * gpk_arccos_kernel_matrix: the contract of gpk_dot_kernel_matrix -- X2 == NULL: K(X1, X1) + diag_add I, computed on or below the
+ *   diagonal and mirrored (exactly symmetric; lower_only: bit for bit the lower triangle of the full build); nothing beyond n1 x n2 is
+ *   written.
+ * gpk_arccos_kernel_matrix_combine: out = G .* k (op 1) or G + k (op 2), k recomputed; out may alias G; X2 == NULL: K(X1, X1) element by
+ *   element with the diagonal by index, diag_add onto the diagonal of the combined result.
+ * gpk_arccos_kernel_diag: over the rows of X [n, d] ldx.  op 0: out = kd; 1: g .* kd; 2: g + kd; 3: g .* dkd/dp (0, v, 6 v p).  g [n]
+ *   (DEVICE; not read by op 0), out [n]; out may alias g.  A NaN / Inf in row i reaches out[i] at every order.
+ * gpk_arccos_adjoint_stage: ONE pass over Kbar [n1, n2] ldkb that recomputes s, p, q, theta per 64 x 64 tile and writes
+ *     G = Kbar .* dk/ds  [n1, n2] ldg (G may alias Kbar), and into parts, with tr = ceil(n1 / 64), tc = ceil(n2 / 64):
+ *     parts[t * n1 + i],  t < tc                   the sum over the columns k of column tile t of Kbar_ik dk/dp_i
+ *     parts[tc * n1 + t * n2 + k],  t < tr         the sum over the rows i of row tile t of Kbar_ik dk/dq_k
+ *     parts[tc * n1 + tr * n2 + tY * tc + tX]      the sum over tile (tY, tX) of Kbar_ik J_ik p_i^(order/2) q_k^(order/2)
+ *   parts is scratch of tc n1 + tr n2 + tr tc doubles (GPK_ARC_TILE = 64): the call writes every slot, each by exactly one workgroup in
+ *   a fixed order, reads none and touches nothing beyond that extent; no atomics, a second call gives the same bits.  X2 == NULL:
+ *   K(X1, X1), every element computed (no mirror), the diagonal by index.
+ * gpk_arccos_adjoint_tail: one workgroup.  From R [n1, >= 1 + d] ldr = G [1, B] (column 0: row sums of G, columns 1 .. d: G B), the
+ *   parts of the stage, A [n1, d] and B [n2, d] (NULL: symmetric -- B is A, Kbar symmetric, both arguments collected), with
+ *   rho_i = sum_t parts[t n1 + i], gamma_k = sum_t parts[tc n1 + t n2 + k]:
+ *     dsmall[0]              d/dv  = (1 / pi) sum of the tile sums
+ *     dsmall[1 ..]           d/dw_j = sum_i A_ij R_i,1+j + sum_i rho_i A_ij^2 + sum_k gamma_k B_kj^2     (summed over j when !ard)
+ *     dsmall[last]           d/db  = sum_i R_i0 + sum_i rho_i + sum_k gamma_k
+ *     Abar_ij = w_j R_i,1+j + 2 w_j A_ij rho_i        (symmetric: 2 w_j R_i,1+j + 2 w_j A_ij (rho_i + gamma_i))
+ *   dsmall [1 + (ard ? d : 1) + 1]; rg: scratch of n1 + n2 doubles (the summed rho, gamma).  Fixed summation order: a second call is
+ *   bit-identical.  n1 == 0 or n2 == 0: dsmall is zeros, Abar is not written. */
+#define GPK_ARC_TILE 64
+int gpk_arccos_kernel_matrix(void* stream, int order, const double* X1, int n1, long ldx1, const double* X2, int n2, long ldx2, int d,
+                             const double* w_host, int ard, double variance, double bias, double diag_add, int lower_only, double* K,
+                             long ldk);
+int gpk_arccos_kernel_matrix_combine(void* stream, int order, int op, const double* X1, int n1, long ldx1, const double* X2, int n2,
+                                     long ldx2, int d, const double* w_host, int ard, double variance, double bias, double diag_add,
+                                     const double* G, long ldg, double* out, long ldo);
+int gpk_arccos_kernel_diag(void* stream, int order, int op, const double* X, int n, long ldx, int d, const double* w_host, int ard,
+                           double variance, double bias, const double* g, double* out);
+int gpk_arccos_adjoint_stage(void* stream, int order, const double* X1, int n1, long ldx1, const double* X2, int n2, long ldx2, int d,
+                             const double* w_host, int ard, double variance, double bias, const double* Kbar, long ldkb, double* G,
+                             long ldg, double* parts);
+int gpk_arccos_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, const double* B, long ldb, int n2,
+                            int d, const double* w_host, int ard, const double* parts, double* rg, double* dsmall, double* Abar,
+                            long ldab);
 /* gpk_adam_step:  tf.keras Adam on one variable of n doubles, in place:  g' = maximise ? -g : g,
  *   m = beta1 m + (1 - beta1) g',  v = beta2 v + (1 - beta2) g'^2,  p -= step m / (sqrt(v) + epsilon),
  *   step = lr sqrt(1 - beta2^t) / (1 - beta1^t) computed by the caller. */
