@@ -24,12 +24,13 @@
 // fma(x_j w_j, x_j, .): no second pass over X, no norm vectors in global memory, and p of row i as a row equals p of row i as a column
 // bit for bit.  The symmetric build computes the elements on or below the diagonal and mirrors them (exactly symmetric; lower_only is bit
 // for bit the lower triangle of the full build).
-#include "../gpk_internal.h"
+#include "../pair_tile.h"
 #include <cmath>
 
 namespace {
 
-constexpr int T = GPK_ARC_TILE;
+using namespace pair_tile;
+static_assert(T == GPK_ARC_TILE, "include/gpk.h states the tile of the adjoint stage's partials");
 constexpr double ARC_EPS = 1e-15;
 constexpr double ARC_SCALE = 1.0 - 2.0 * ARC_EPS;
 constexpr double ARC_CT_DIAG = 1.0 - ARC_EPS;   // the acos argument of a diagonal element taken by index
@@ -262,8 +263,8 @@ __global__ __launch_bounds__(256) void arccos_kernel(ArcArgs p) {
   }
 }
 
-// The row diagonal, the closed form: kd_i = v jf p_i^order with jf = J_order(0) / pi = 1, 1, 3; 64 rows per workgroup staged as in
-// dot_diag_kernel, p_i by the builder's chain.  op 0: out = kd; 1: g .* kd; 2: g + kd; 3: g .* dkd/dp.  Order 0 does not depend on p:
+// The row diagonal, the closed form: kd_i = v jf p_i^order with jf = J_order(0) / pi = 1, 1, 3; pair_tile.h's row_diag, p_i by the
+// builder's chain.  op 0: out = kd; 1: g .* kd; 2: g + kd; 3: g .* dkd/dp.  Order 0 does not depend on p:
 // p enters as fma(p, 0, 1), so a NaN or Inf in the row still reaches kd.
 struct ArcDiagArgs {
   const double* X; long ldx; int n, d;
@@ -275,27 +276,11 @@ struct ArcDiagArgs {
 template <int ORDER>
 __global__ __launch_bounds__(256) void arccos_diag_kernel(ArcDiagArgs p) {
   extern __shared__ __attribute__((aligned(16))) double sm[];   // [d][T]
-  const int d = p.d, r0 = blockIdx.x * T, tid = threadIdx.x;
-  for (int e = tid; e < T * d; e += 256) {
-    const int row = e / d, dd = e - row * d;
-    const int gi = r0 + row;
-    sm[dd * T + row] = (gi < p.n) ? p.X[(long)gi * p.ldx + dd] : 0.0;
-  }
-  __syncthreads();
-  const int gi = r0 + tid;
-  if (tid >= T || gi >= p.n) return;
-  double acc = 0.0;
-  for (int dd = 0; dd < d; ++dd) {
-    const double x = sm[dd * T + tid];
-    acc = fma(x * p.w[dd], x, acc);
-  }
-  const double pv = acc + p.bias;
-  double k;
-  if (p.op == 3)
-    k = ORDER == 0 ? 0.0 * pv : ORDER == 1 ? fma(pv, 0.0, p.variance) : 6.0 * p.variance * pv;
-  else
-    k = ORDER == 0 ? p.variance * fma(pv, 0.0, 1.0) : ORDER == 1 ? p.variance * pv : 3.0 * p.variance * pv * pv;
-  p.out[gi] = (p.op == 0) ? k : (p.op == 2) ? p.g[gi] + k : p.g[gi] * k;
+  row_diag(p, sm, [&](double acc) {
+    const double pv = acc + p.bias;
+    if (p.op == 3) return ORDER == 0 ? 0.0 * pv : ORDER == 1 ? fma(pv, 0.0, p.variance) : 6.0 * p.variance * pv;
+    return ORDER == 0 ? p.variance * fma(pv, 0.0, 1.0) : ORDER == 1 ? p.variance * pv : 3.0 * p.variance * pv * pv;
+  });
 }
 
 // The adjoint tail: one workgroup, as dot_adjoint_tail_kernel.  Phase 1 sums the stage's partials in slot order into rg:
@@ -403,35 +388,23 @@ __global__ __launch_bounds__(AT_THREADS) void arccos_adjoint_tail_kernel(ArcTail
 }
 
 template <int ORDER, int MODE>
-int launch_arc(hipStream_t st, const ArcArgs& a, dim3 grid, size_t lds) {
-  static const int max_lds = (int)((size_t)2 * GPK_MAX_D * T * sizeof(double));   // 64 KB at d = GPK_MAX_D
-  static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(arccos_kernel<ORDER, MODE>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  GPK_HIP(at);
+int launch_arc(hipStream_t st, const ArcArgs& a, size_t lds) {
+  GPK_HIP((allow_tile_lds<arccos_kernel<ORDER, MODE>>()));
+  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
   hipLaunchKernelGGL((arccos_kernel<ORDER, MODE>), grid, dim3(256), lds, st, a);
   GPK_LAUNCH_CHECK();
   return 0;
 }
 
 template <int MODE>
-int launch_arc_order(hipStream_t st, int order, const ArcArgs& a) {
-  const size_t lds = (size_t)2 * a.d * T * sizeof(double);
-  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
-  return order == 0 ? launch_arc<0, MODE>(st, a, grid, lds)
-         : order == 1 ? launch_arc<1, MODE>(st, a, grid, lds)
-                      : launch_arc<2, MODE>(st, a, grid, lds);
+int launch_arc_order(hipStream_t st, int order, const ArcArgs& a, size_t lds) {
+  return order == 0 ? launch_arc<0, MODE>(st, a, lds) : order == 1 ? launch_arc<1, MODE>(st, a, lds) : launch_arc<2, MODE>(st, a, lds);
 }
 
 // what every entry point checks of a leaf before it looks at the operands; the weights spread over the d columns into `w`
 int read_arc_weights(double* w, int d, const double* w_host, int ard) {
   if (d <= 0 || d > GPK_MAX_D || !w_host) return GPK_E_ARG;
-  for (int j = 0; j < d; ++j) {
-    const double v = w_host[ard ? j : 0];
-    if (!std::isfinite(v) || v < 0.0) return GPK_E_ARG;
-    w[j] = v;
-  }
-  for (int j = d; j < GPK_MAX_D; ++j) w[j] = 0.0;
-  return 0;
+  return spread_weights(w, d, w_host, ard, /*allow_negative=*/false);
 }
 
 int read_arc_leaf(double* w, int order, int d, const double* w_host, int ard, double variance, double bias) {
@@ -448,15 +421,14 @@ extern "C" int gpk_arccos_kernel_matrix(void* stream, int order, const double* X
   if (n1 < 0 || (X2 && n2 < 0)) return GPK_E_ARG;
   ArcArgs a{};
   GPK_TRY(read_arc_leaf(a.w, order, d, w_host, ard, variance, bias));
-  a.sym = a.same = (X2 == nullptr);
-  a.n1 = n1; a.n2 = a.sym ? n1 : n2;
-  if (ldx1 < d || (X2 && ldx2 < d) || ldk < a.n2) return GPK_E_ARG;
-  if (a.n1 == 0 || a.n2 == 0) return 0;   // (gpk.h: an operand without elements may be NULL)
+  const int m2 = X2 ? n2 : n1;
+  if (ldx1 < d || (X2 && ldx2 < d) || ldk < m2) return GPK_E_ARG;
+  if (n1 == 0 || m2 == 0) return 0;   // (gpk.h: an operand without elements may be NULL)
   if (!X1 || !K) return GPK_E_ARG;
-  a.X1 = X1; a.ldx1 = ldx1;
-  a.X2 = a.sym ? X1 : X2; a.ldx2 = a.sym ? ldx1 : ldx2;
-  a.d = d; a.K = K; a.ldk = ldk; a.vpi = variance * ARC_INV_PI; a.bias = bias; a.diag_add = diag_add; a.lower_only = lower_only;
-  return launch_arc_order<0>((hipStream_t)stream, order, a);
+  const size_t lds = set_operands(a, X1, n1, ldx1, X2, n2, ldx2, d, K, ldk, nullptr, 0);
+  a.sym = a.same = (X2 == nullptr);
+  a.vpi = variance * ARC_INV_PI; a.bias = bias; a.diag_add = diag_add; a.lower_only = lower_only;
+  return launch_arc_order<0>((hipStream_t)stream, order, a, lds);
 }
 
 extern "C" int gpk_arccos_kernel_matrix_combine(void* stream, int order, int op, const double* X1, int n1, long ldx1, const double* X2,
@@ -466,17 +438,15 @@ extern "C" int gpk_arccos_kernel_matrix_combine(void* stream, int order, int op,
   ArcArgs a{};
   GPK_TRY(read_arc_leaf(a.w, order, d, w_host, ard, variance, bias));
   if (op < 1 || op > 2) return GPK_E_ARG;
-  a.comb_diag = a.same = (X2 == nullptr);
-  a.n1 = n1; a.n2 = X2 ? n2 : n1;
-  if (ldx1 < d || (X2 && ldx2 < d) || ldg < a.n2 || ldo < a.n2) return GPK_E_ARG;
-  if (a.n1 == 0 || a.n2 == 0) return 0;
+  const int m2 = X2 ? n2 : n1;
+  if (ldx1 < d || (X2 && ldx2 < d) || ldg < m2 || ldo < m2) return GPK_E_ARG;
+  if (n1 == 0 || m2 == 0) return 0;
   if (!X1 || !G || !out) return GPK_E_ARG;
-  a.X1 = X1; a.ldx1 = ldx1;
-  a.X2 = X2 ? X2 : X1; a.ldx2 = X2 ? ldx2 : ldx1;
-  a.d = d; a.K = out; a.ldk = ldo; a.vpi = variance * ARC_INV_PI; a.bias = bias; a.diag_add = a.comb_diag ? diag_add : 0.0;
-  a.G = G; a.ldg = ldg;
+  const size_t lds = set_operands(a, X1, n1, ldx1, X2, n2, ldx2, d, out, ldo, G, ldg);
+  a.comb_diag = a.same = (X2 == nullptr);
+  a.vpi = variance * ARC_INV_PI; a.bias = bias; a.diag_add = a.comb_diag ? diag_add : 0.0;
   const hipStream_t st = (hipStream_t)stream;
-  return op == 1 ? launch_arc_order<1>(st, order, a) : launch_arc_order<2>(st, order, a);
+  return op == 1 ? launch_arc_order<1>(st, order, a, lds) : launch_arc_order<2>(st, order, a, lds);
 }
 
 extern "C" int gpk_arccos_kernel_diag(void* stream, int order, int op, const double* X, int n, long ldx, int d, const double* w_host, int ard,
@@ -507,17 +477,15 @@ extern "C" int gpk_arccos_adjoint_stage(void* stream, int order, const double* X
   if (n1 < 0 || (X2 && n2 < 0)) return GPK_E_ARG;
   ArcArgs a{};
   GPK_TRY(read_arc_leaf(a.w, order, d, w_host, ard, variance, bias));
-  a.same = (X2 == nullptr);
-  a.n1 = n1; a.n2 = X2 ? n2 : n1;
-  if (ldx1 < d || (X2 && ldx2 < d) || ldkb < a.n2 || ldg < a.n2) return GPK_E_ARG;
-  if (a.n1 == 0 || a.n2 == 0) return 0;
+  const int m2 = X2 ? n2 : n1;
+  if (ldx1 < d || (X2 && ldx2 < d) || ldkb < m2 || ldg < m2) return GPK_E_ARG;
+  if (n1 == 0 || m2 == 0) return 0;
   if (!X1 || !Kbar || !G || !parts) return GPK_E_ARG;
-  a.X1 = X1; a.ldx1 = ldx1;
-  a.X2 = X2 ? X2 : X1; a.ldx2 = X2 ? ldx2 : ldx1;
-  a.d = d; a.K = G; a.ldk = ldg; a.vpi = variance * ARC_INV_PI; a.bias = bias;
-  a.G = Kbar; a.ldg = ldkb;
+  const size_t lds = set_operands(a, X1, n1, ldx1, X2, n2, ldx2, d, G, ldg, Kbar, ldkb);
+  a.same = (X2 == nullptr);
+  a.vpi = variance * ARC_INV_PI; a.bias = bias;
   a.parts = parts; a.tr = gpk_cdiv(a.n1, T); a.tc = gpk_cdiv(a.n2, T);
-  return launch_arc_order<3>((hipStream_t)stream, order, a);
+  return launch_arc_order<3>((hipStream_t)stream, order, a, lds);
 }
 
 extern "C" int gpk_arccos_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, const double* B, long ldb,

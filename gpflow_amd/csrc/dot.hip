@@ -13,7 +13,7 @@
 // (X2 == NULL) computes the elements on or below the diagonal only and writes each of them to its mirror position as well: its
 // output is exactly symmetric, and the lower triangle of a lower_only build is bit for bit that of the full one.  A build with X2
 // given promises no symmetry, whatever X2 holds (as the reference's matmul does not).
-#include "gpk_internal.h"
+#include "pair_tile.h"
 #include <cmath>
 
 namespace {
@@ -30,7 +30,7 @@ struct DotArgs {
   double w[GPK_MAX_D];        // one weight per input column (a single one repeated)
 };
 
-constexpr int T = 64;
+using namespace pair_tile;
 
 // base^degree as base * base * ... * base, left to right
 __device__ __forceinline__ double dot_power(double base, int degree) {
@@ -171,22 +171,7 @@ struct DotDiagArgs {
 template <int FAMILY>
 __global__ __launch_bounds__(256) void dot_diag_kernel(DotDiagArgs p) {
   extern __shared__ __attribute__((aligned(16))) double sm[];   // [d][T]
-  const int d = p.d, r0 = blockIdx.x * T, tid = threadIdx.x;
-  for (int e = tid; e < T * d; e += 256) {
-    const int row = e / d, dd = e - row * d;
-    const int gi = r0 + row;
-    sm[dd * T + row] = (gi < p.n) ? p.X[(long)gi * p.ldx + dd] : 0.0;
-  }
-  __syncthreads();
-  const int gi = r0 + tid;
-  if (tid >= T || gi >= p.n) return;
-  double s = 0.0;
-  for (int dd = 0; dd < d; ++dd) {
-    const double x = sm[dd * T + tid];
-    s = fma(x * p.w[dd], x, s);
-  }
-  const double k = (p.op == 3) ? dot_ds<FAMILY>(s, p.offset, p.degree) : dot_eval<FAMILY>(s, p.offset, p.degree);
-  p.out[gi] = (p.op == 0) ? k : (p.op == 2) ? p.g[gi] + k : p.g[gi] * k;
+  row_diag(p, sm, [&](double s) { return (p.op == 3) ? dot_ds<FAMILY>(s, p.offset, p.degree) : dot_eval<FAMILY>(s, p.offset, p.degree); });
 }
 
 constexpr int DT_THREADS = 1024;
@@ -238,20 +223,17 @@ __global__ __launch_bounds__(DT_THREADS) void dot_adjoint_tail_kernel(const doub
 }
 
 template <int FAMILY, int COMB>
-int launch_dot(hipStream_t st, const DotArgs& a, dim3 grid, size_t lds) {
-  static const int max_lds = (int)((size_t)2 * GPK_MAX_D * T * sizeof(double));   // 64 KB at d = GPK_MAX_D
-  static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(dot_kernel<FAMILY, COMB>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  GPK_HIP(at);
+int launch_dot(hipStream_t st, const DotArgs& a, size_t lds) {
+  GPK_HIP((allow_tile_lds<dot_kernel<FAMILY, COMB>>()));
+  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
   hipLaunchKernelGGL((dot_kernel<FAMILY, COMB>), grid, dim3(256), lds, st, a);
   GPK_LAUNCH_CHECK();
   return 0;
 }
 
 template <int COMB>
-int launch_dot_family(hipStream_t st, int family, const DotArgs& a, dim3 grid, size_t lds) {
-  return family == GPK_DOT_LINEAR ? launch_dot<GPK_DOT_LINEAR, COMB>(st, a, grid, lds)
-                                  : launch_dot<GPK_DOT_POLYNOMIAL, COMB>(st, a, grid, lds);
+int launch_dot_family(hipStream_t st, int family, const DotArgs& a, size_t lds) {
+  return family == GPK_DOT_LINEAR ? launch_dot<GPK_DOT_LINEAR, COMB>(st, a, lds) : launch_dot<GPK_DOT_POLYNOMIAL, COMB>(st, a, lds);
 }
 
 // what every entry point checks of a leaf before it looks at the operands; the weights spread over the d columns into `w`
@@ -260,13 +242,7 @@ int read_dot_leaf(double* w, int family, int d, const double* w_host, int ard, d
   if (family != GPK_DOT_LINEAR && family != GPK_DOT_POLYNOMIAL) return GPK_E_UNSUPPORTED;
   if (!std::isfinite(offset)) return GPK_E_ARG;
   if (family == GPK_DOT_POLYNOMIAL && (degree < 1 || degree > GPK_DOT_MAX_DEGREE)) return GPK_E_ARG;
-  for (int j = 0; j < d; ++j) {
-    const double v = w_host[ard ? j : 0];
-    if (!std::isfinite(v)) return GPK_E_ARG;
-    w[j] = v;
-  }
-  for (int j = d; j < GPK_MAX_D; ++j) w[j] = 0.0;
-  return 0;
+  return spread_weights(w, d, w_host, ard, /*allow_negative=*/true);
 }
 }  // namespace
 
@@ -276,17 +252,14 @@ extern "C" int gpk_dot_kernel_matrix(void* stream, int family, const double* X1,
   if (n1 < 0 || (X2 && n2 < 0)) return GPK_E_ARG;
   DotArgs a{};
   GPK_TRY(read_dot_leaf(a.w, family, d, w_host, ard, offset, degree));
-  a.sym = (X2 == nullptr);
-  a.n1 = n1; a.n2 = a.sym ? n1 : n2;
-  if (ldx1 < d || (X2 && ldx2 < d) || ldk < a.n2) return GPK_E_ARG;
-  if (a.n1 == 0 || a.n2 == 0) return 0;   // (gpk.h: an operand without elements may be NULL)
+  const int m2 = X2 ? n2 : n1;
+  if (ldx1 < d || (X2 && ldx2 < d) || ldk < m2) return GPK_E_ARG;
+  if (n1 == 0 || m2 == 0) return 0;   // (gpk.h: an operand without elements may be NULL)
   if (!X1 || !K) return GPK_E_ARG;
-  a.X1 = X1; a.ldx1 = ldx1;
-  a.X2 = a.sym ? X1 : X2; a.ldx2 = a.sym ? ldx1 : ldx2;
-  a.d = d; a.K = K; a.ldk = ldk; a.offset = offset; a.degree = degree; a.diag_add = diag_add; a.lower_only = lower_only;
-  const size_t lds = (size_t)2 * d * T * sizeof(double);
-  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
-  return launch_dot_family<0>((hipStream_t)stream, family, a, grid, lds);
+  const size_t lds = set_operands(a, X1, n1, ldx1, X2, n2, ldx2, d, K, ldk, nullptr, 0);
+  a.sym = (X2 == nullptr);
+  a.offset = offset; a.degree = degree; a.diag_add = diag_add; a.lower_only = lower_only;
+  return launch_dot_family<0>((hipStream_t)stream, family, a, lds);
 }
 
 extern "C" int gpk_dot_kernel_matrix_combine(void* stream, int family, int op, const double* X1, int n1, long ldx1, const double* X2,
@@ -296,22 +269,17 @@ extern "C" int gpk_dot_kernel_matrix_combine(void* stream, int family, int op, c
   DotArgs a{};
   GPK_TRY(read_dot_leaf(a.w, family, d, w_host, ard, offset, degree));
   if (op < 1 || op > 3) return GPK_E_ARG;
-  a.comb_diag = (X2 == nullptr);
-  a.n1 = n1; a.n2 = X2 ? n2 : n1;
-  if (ldx1 < d || (X2 && ldx2 < d) || ldg < a.n2 || ldo < a.n2) return GPK_E_ARG;
-  if (a.n1 == 0 || a.n2 == 0) return 0;
+  const int m2 = X2 ? n2 : n1;
+  if (ldx1 < d || (X2 && ldx2 < d) || ldg < m2 || ldo < m2) return GPK_E_ARG;
+  if (n1 == 0 || m2 == 0) return 0;
   if (!X1 || !G || !out) return GPK_E_ARG;
-  a.X1 = X1; a.ldx1 = ldx1;
-  a.X2 = X2 ? X2 : X1; a.ldx2 = X2 ? ldx2 : ldx1;
-  a.d = d; a.K = out; a.ldk = ldo; a.offset = offset; a.degree = degree; a.diag_add = a.comb_diag ? diag_add : 0.0;
-  a.sym = 0; a.lower_only = 0;
-  a.G = G; a.ldg = ldg;
-  const size_t lds = (size_t)2 * d * T * sizeof(double);
-  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
+  const size_t lds = set_operands(a, X1, n1, ldx1, X2, n2, ldx2, d, out, ldo, G, ldg);
+  a.comb_diag = (X2 == nullptr);
+  a.offset = offset; a.degree = degree; a.diag_add = a.comb_diag ? diag_add : 0.0;
   const hipStream_t st = (hipStream_t)stream;
-  return op == 1 ? launch_dot_family<1>(st, family, a, grid, lds)
-         : op == 2 ? launch_dot_family<2>(st, family, a, grid, lds)
-                   : launch_dot_family<3>(st, family, a, grid, lds);
+  return op == 1 ? launch_dot_family<1>(st, family, a, lds)
+         : op == 2 ? launch_dot_family<2>(st, family, a, lds)
+                   : launch_dot_family<3>(st, family, a, lds);
 }
 
 extern "C" int gpk_dot_kernel_diag(void* stream, int family, int op, const double* X, int n, long ldx, int d, const double* w_host, int ard,

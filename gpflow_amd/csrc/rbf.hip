@@ -13,7 +13,7 @@
 // 4 x 4 patch and stores 32 contiguous bytes per row (16 threads -> 512 B contiguous per row).
 // The expansion formula and the association (-2 x.y) + (|x|^2 + |y|^2) of the reference are kept
 // so rounding has the same structure (the diagonal is exp(-0.5 * ~1e-16), not exactly sigma^2).
-#include "gpk_internal.h"
+#include "pair_tile.h"
 #include <algorithm>
 #include <cmath>
 
@@ -32,7 +32,8 @@ struct RbfArgs {
   double alpha;               // GPK_KERN_RQ only: the trailing entry of ls_host (gpk.h)
 };
 
-constexpr int T = 64;
+using namespace pair_tile;
+constexpr int NORMS = 2 * T;   // doubles of LDS behind the slabs: the squared norms of the tile's rows and columns
 
 // Static families (statics.py): no distance -- White is variance on the diagonal of K(X, X) (X2 == NULL) and 0 elsewhere, whatever the
 // values of X2; Constant is variance everywhere.  Their tiles never stage or read X.
@@ -208,31 +209,26 @@ __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
   }
 }
 
-}  // namespace
-
-namespace {
 template <int FAMILY, int COMB>
-int launch_family(hipStream_t st, const RbfArgs& a, dim3 grid, size_t lds) {
-  static const int max_lds = (int)(((size_t)2 * GPK_MAX_D * T + 2 * T) * sizeof(double));
-  static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(rbf_kernel<FAMILY, COMB>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  GPK_HIP(at);
+int launch_family(hipStream_t st, const RbfArgs& a, size_t lds) {
+  GPK_HIP((allow_tile_lds<rbf_kernel<FAMILY, COMB>, NORMS>()));
+  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
   hipLaunchKernelGGL((rbf_kernel<FAMILY, COMB>), grid, dim3(256), lds, st, a);
   GPK_LAUNCH_CHECK();
   return 0;
 }
 
 template <int COMB>
-int launch_combine(hipStream_t st, int family, const RbfArgs& a, dim3 grid, size_t lds) {
+int launch_combine(hipStream_t st, int family, const RbfArgs& a, size_t lds) {
   switch (family) {
-    case GPK_KERN_SE: return launch_family<GPK_KERN_SE, COMB>(st, a, grid, lds);
-    case GPK_KERN_MATERN12: return launch_family<GPK_KERN_MATERN12, COMB>(st, a, grid, lds);
-    case GPK_KERN_MATERN32: return launch_family<GPK_KERN_MATERN32, COMB>(st, a, grid, lds);
-    case GPK_KERN_MATERN52: return launch_family<GPK_KERN_MATERN52, COMB>(st, a, grid, lds);
-    case GPK_KERN_EXPONENTIAL: return launch_family<GPK_KERN_EXPONENTIAL, COMB>(st, a, grid, lds);
-    case GPK_KERN_RQ: return launch_family<GPK_KERN_RQ, COMB>(st, a, grid, lds);
-    case GPK_KERN_WHITE: return launch_family<GPK_KERN_WHITE, COMB>(st, a, grid, lds);
-    case GPK_KERN_CONSTANT: return launch_family<GPK_KERN_CONSTANT, COMB>(st, a, grid, lds);
+    case GPK_KERN_SE: return launch_family<GPK_KERN_SE, COMB>(st, a, lds);
+    case GPK_KERN_MATERN12: return launch_family<GPK_KERN_MATERN12, COMB>(st, a, lds);
+    case GPK_KERN_MATERN32: return launch_family<GPK_KERN_MATERN32, COMB>(st, a, lds);
+    case GPK_KERN_MATERN52: return launch_family<GPK_KERN_MATERN52, COMB>(st, a, lds);
+    case GPK_KERN_EXPONENTIAL: return launch_family<GPK_KERN_EXPONENTIAL, COMB>(st, a, lds);
+    case GPK_KERN_RQ: return launch_family<GPK_KERN_RQ, COMB>(st, a, lds);
+    case GPK_KERN_WHITE: return launch_family<GPK_KERN_WHITE, COMB>(st, a, lds);
+    case GPK_KERN_CONSTANT: return launch_family<GPK_KERN_CONSTANT, COMB>(st, a, lds);
   }
   return GPK_E_UNSUPPORTED;
 }
@@ -260,16 +256,13 @@ extern "C" int gpk_kernel_matrix(void* stream, int family, const double* X1, int
   if (n1 == 0 || (X2 && n2 == 0)) return 0;
   if (!X1 || !K) return GPK_E_ARG;
   RbfArgs a{};
-  a.X1 = X1; a.ldx1 = ldx1; a.n1 = n1;
+  const size_t lds = set_operands<NORMS>(a, X1, n1, ldx1, X2, n2, ldx2, d, K, ldk, nullptr, 0);
   a.sym = (X2 == nullptr);
-  a.X2 = a.sym ? X1 : X2; a.ldx2 = a.sym ? ldx1 : ldx2; a.n2 = a.sym ? n1 : n2;
-  a.d = d; a.K = K; a.ldk = ldk; a.variance = variance; a.diag_add = diag_add;
+  a.variance = variance; a.diag_add = diag_add;
   a.family = family; a.lower_only = lower_only; a.ard = ard;
   if (const int rc = read_hypers(a, family, ls_host, ard, d)) return rc;
   if (a.n1 == 0 || a.n2 == 0) return 0;
-  const size_t lds = ((size_t)2 * d * T + 2 * T) * sizeof(double);
-  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
-  return launch_combine<0>((hipStream_t)stream, family, a, grid, lds);
+  return launch_combine<0>((hipStream_t)stream, family, a, lds);
 }
 
 // out = G .* k(X1, X2) (op 1) or G + k(X1, X2) (op 2), k recomputed from the inputs, not read: one read of G and one
@@ -289,23 +282,18 @@ extern "C" int gpk_kernel_matrix_combine(void* stream, int family, int op, const
   if (n1 == 0 || (X2 && n2 == 0)) return 0;
   if (!X1 || !G || !out) return GPK_E_ARG;
   RbfArgs a{};
-  a.X1 = X1; a.ldx1 = ldx1; a.n1 = n1;
-  a.sym = 0;
+  const size_t lds = set_operands<NORMS>(a, X1, n1, ldx1, X2, n2, ldx2, d, out, ldo, G, ldg);
   a.comb_diag = (X2 == nullptr);
-  a.X2 = X2 ? X2 : X1; a.ldx2 = X2 ? ldx2 : ldx1; a.n2 = X2 ? n2 : n1;
-  a.d = d; a.K = out; a.ldk = ldo; a.variance = variance; a.diag_add = a.comb_diag ? diag_add : 0.0;
-  a.family = family; a.lower_only = 0; a.ard = ard;
-  a.G = G; a.ldg = ldg;
+  a.variance = variance; a.diag_add = a.comb_diag ? diag_add : 0.0;
+  a.family = family; a.ard = ard;
   if (const int rc = read_hypers(a, family, ls_host, ard, d)) return rc;
   if (a.n1 == 0 || a.n2 == 0) return 0;
   // White against a second set of points is zero: G + 0 in place is G
   if (family == GPK_KERN_WHITE && op == 2 && X2 && out == G && ldo == ldg) return 0;
-  const size_t lds = ((size_t)2 * d * T + 2 * T) * sizeof(double);
-  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
-  if (op == 4) return launch_family<GPK_KERN_RQ, 4>((hipStream_t)stream, a, grid, lds);
-  if (op == 3) return launch_combine<3>((hipStream_t)stream, family, a, grid, lds);
-  return op == 1 ? launch_combine<1>((hipStream_t)stream, family, a, grid, lds)
-                 : launch_combine<2>((hipStream_t)stream, family, a, grid, lds);
+  if (op == 4) return launch_family<GPK_KERN_RQ, 4>((hipStream_t)stream, a, lds);
+  if (op == 3) return launch_combine<3>((hipStream_t)stream, family, a, lds);
+  return op == 1 ? launch_combine<1>((hipStream_t)stream, family, a, lds)
+                 : launch_combine<2>((hipStream_t)stream, family, a, lds);
 }
 
 extern "C" int gpk_kernel_matrix_hadamard(void* stream, int family, const double* X1, int n1, long ldx1,
