@@ -350,6 +350,20 @@ int gpk_gaussian_varexp_sum(void* stream, const double* Y, long ldy, const doubl
  *   Codes 10 and 11: dmu = sum_h (w_h / sqrt pi) g'(f_h), dvar = sum_h (w_h / sqrt pi) g'(f_h) x_h / sqrt(2 v), the exact derivatives
  *   of the sum, as for Bernoulli and StudentT.  psi is gpk_digamma (csrc/digamma.h: its absolute error bound is derived there).
  *
+ * Edges of the SCALAR codes, where the formulas above are taken as they stand (held by tests/test_gpu_likelihood_edges.py):
+ *   fvar == 0 exactly.  Quadrature codes (1, 3, 10, 11): sqrt(2 fvar) = 0 and every node is mu, so VE and dmu are the one-point
+ *   values g(mu) and g'(mu), to the rounding of the 20-term sums.  dvar = (sum_h (w_h / sqrt pi) g'(mu) x_h) / 0 is NOT finite: NaN
+ *   or +-Inf, the numerator being 0 or a rounding residue.  The limit g''(mu) / 2 is not substituted and no epsilon is added under
+ *   the root; a caller that differentiates w.r.t. a variance must not pass an exact 0.  Closed forms (2, 8, 9): every output is
+ *   finite.  Every other element has the bits it has when this element's fvar is 1.
+ *   Overflow inside a closed form: exp(mu + fvar / 2) (Poisson) or e = exp(-mu + fvar / 2) (Exponential, Gamma) is +Inf from an
+ *   argument of 709.79 on.  The element's outputs are the IEEE results of the formulas in the order written: VE = -Inf, dvar = -Inf,
+ *   dmu = -Inf (Poisson) or +Inf (Exponential, Gamma); with y = 0, y e = 0 * Inf = NaN in all three.  out[0] follows (-Inf, or NaN),
+ *   the element's row of rows_out too, and no other element changes.
+ *   GPK_LIK_GAMMA_EXP with y = 0: log y = -Inf as it comes.  VE = (shape - 1) (-Inf) + finite terms: -Inf for shape > 1, +Inf for
+ *   shape < 1, NaN for shape == 1 (0 * Inf); dmu = -shape and dvar = 0 (y e = 0 exactly); dVE/dshape = -Inf, so out[1] = -Inf for
+ *   every shape.
+ *
  * Codes: 0 is the Gaussian stage of gpk_svgp_elbo_shard and no likelihood code.  5, 6 and 7 are unassigned and answer
  * GPK_E_UNSUPPORTED: they are kept for links of the codes 1 .. 4 should those be built (Bernoulli with the logistic link, Poisson
  * with softplus, MultiClass with Softmax), so that a family's links stay next to each other; callers and tests rely on 5 being unknown. */
