@@ -110,6 +110,14 @@ _SIGS = {
                                          c_double, c_double, _dp, c_long, _dp, c_long, _dp]),
     "gpk_arccos_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, _dp, c_long, c_int, c_int, C.POINTER(c_double), c_int,
                                         _dp, _dp, _dp, _dp, c_long]),
+    "gpk_coregion_output_covariance": (c_int, [c_void_p, _dp, c_long, _dp, c_int, c_int, _dp, c_long]),
+    "gpk_coregion_kernel_matrix": (c_int, [c_void_p, _dp, c_int, c_long, _dp, c_int, c_long, _dp, c_long, c_int, c_double, c_int, _dp,
+                                           c_long]),
+    "gpk_coregion_kernel_matrix_combine": (c_int, [c_void_p, c_int, _dp, c_int, c_long, _dp, c_int, c_long, _dp, c_long, c_int, c_double,
+                                                   _dp, c_long, _dp, c_long]),
+    "gpk_coregion_kernel_diag": (c_int, [c_void_p, c_int, _dp, c_int, c_long, _dp, c_long, c_int, _dp, _dp]),
+    "gpk_coregion_onehot_rows": (c_int, [c_void_p, _dp, c_int, c_long, c_int, _dp, c_long]),
+    "gpk_coregion_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, c_int, _dp, c_long, _dp]),
     "gpk_tril_product_tiles": (c_int, [c_int]),
     "gpk_tril_product": (c_int, [c_void_p, _dp, c_int, c_long, _dp, c_long, c_long, c_int, _dp, _dp, _dp, _dp, c_long, c_long]),
     "gpk_adam_step": (c_int, [c_void_p, _dp, _dp, _dp, _dp, c_long, c_double, c_double, c_double, c_double, c_int]),

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .leaf import ArcLeaf, DotLeaf, Leaf
+from .leaf import ArcLeaf, CoregionLeaf, DotLeaf, Leaf
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -399,6 +399,70 @@ class ArcMember(Member):
         return self.leaf.parameters
 
 
+def coregion_kernel_adjoint(leaf: CoregionLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, symmetric: bool):
+    """Adjoint of a Coregion leaf K[i, k] = B[l_i, l'_k], B = W W^T + diag(kappa) (kernels/misc.py), given Kbar [n1, n2]; A [n1, 1] and
+    Bm [n2, 1] are the label columns.  Returns (d/dkappa [P], d/dW [P R] flattened row-major, None: labels have no gradient).
+
+    Bbar[a, b] = sum_{i: l_i = a} sum_{k: l'_k = b} Kbar[i, k] = (E1 Kbar E2^T)[a, b] with the one-hot rows E = ops.coregion_onehot_rows.
+    Kbar is read ONCE, by the long contraction T = Kbar E2^T [n1, P] -- `splitk_gemm_nt(Kbar, E2)`, Kbar the GEMM's first operand as G
+    is in the other adjoints; the second, thin contraction Bbar = E1 T = gemm_nt(E1, T^T) [P, P] takes T transposed (one small launch
+    over n1 x P).  The other orientation, splitk_gemm_nt(E2, Kbar) [P, n1], needs no transpose and was measured 9 - 11 % slower at
+    8192 x 8192 ("Coregion kernel").  Then the one-workgroup tail: d/dW = (Bbar + Bbar^T) W, d/dkappa = diag(Bbar).
+    The same formulas serve K(A, A) with a symmetric Kbar: Bbar collects both arguments."""
+    P = leaf.n_outputs
+    A = A if A.is_contiguous() else A.contiguous()
+    E1 = ops.coregion_onehot_rows(A, P)
+    E2 = E1 if (symmetric or Bm is A) else ops.coregion_onehot_rows(Bm if Bm.is_contiguous() else Bm.contiguous(), P)
+    T = splitk_gemm_nt(Kbar if Kbar.is_contiguous() else Kbar.contiguous(), E2)    # [n1, P]: the one pass over Kbar
+    Bbar = ops.gemm_nt(E1, ops.transpose(T))                                       # [P, P]
+    dk, dW = ops.coregion_adjoint_tail(Bbar, W=leaf.W)
+    return dk, dW.reshape(-1), None
+
+
+class CoregionMember(Member):
+    """a Coregion leaf (leaf.CoregionLeaf), built and folded by the `gpk_coregion_*` entry points over its ONE label column.
+    K(x, x) = B[l, l] depends on the row: `kdiag_rows` / `fold_kdiag`.  The gradient slot the spec calls "variance" holds d/dkappa [P]
+    (as the ARD variance of a DotMember has D entries); the shape gradient is d/dW [P R]; there is no input gradient."""
+    constant_diagonal = False
+    matrix, combine = "coregion_kernel_matrix", "coregion_kernel_matrix_combine"
+    leaf_adjoint = staticmethod(coregion_kernel_adjoint)
+    n_variance = property(lambda self: self.leaf.n_variance)
+
+    def kdiag(self) -> float:
+        raise NotImplementedError("K(x, x) of a Coregion member depends on the row: this caller takes the diagonal for one scalar and "
+                                  "has not been converted to KernelSpec.kdiag_rows")
+
+    def kdiag_rows(self, X) -> torch.Tensor:
+        """K(x_b, x_b) as a fresh [rows] tensor"""
+        return ops.coregion_kernel_diag(self.view(X), **self.leaf.keywords())
+
+    def fold_kdiag(self, X, acc, op: str) -> None:
+        """acc <- acc .* K(x_b, x_b) or acc + K(x_b, x_b) in place"""
+        ops.coregion_kernel_diag(self.view(X), acc, op=op, out=acc, **self.leaf.keywords())
+
+    def diag_adjoint(self, X, bar):
+        """dbar_a = sum_{b: l_b = a} bar_b from ONE thin product of bar with the one-hot rows; kd = sum_r W[l, r]^2 + kappa[l], so
+        d/dkappa = dbar and d/dW[a, :] = 2 dbar_a W[a, :]"""
+        leaf = self.leaf
+        Xi = self.view(X)
+        Xi = Xi if Xi.is_contiguous() else Xi.contiguous()
+        dbar = ops.gemm_nt(bar.reshape(1, -1), ops.coregion_onehot_rows(Xi, leaf.n_outputs))[0]      # [P]
+        Wd = ls_device(leaf.W.reshape(-1), leaf.n_shape, bar.device).reshape(leaf.n_outputs, leaf.rank)
+        return dbar, (2.0 * dbar[:, None] * Wd).reshape(-1)
+
+    def adjoint(self, A, Bm, Kbar, symmetric):
+        Ai = self.view(A)
+        Bi = Ai if (symmetric and Bm is A) else self.view(Bm)
+        dk, dW, _ = self.leaf_adjoint(self.leaf, Ai, Bi, Kbar, symmetric=symmetric)
+        return dk.reshape(-1), dW, None
+
+    def warm(self, device, D: int) -> None:
+        ls_device(self.leaf.W.reshape(-1), self.leaf.n_shape, device)   # (the W of diag_adjoint)
+
+    def parameter_names(self) -> tuple:
+        return self.leaf.parameters
+
+
 class PeriodicMember(StationaryMember):
     """a Periodic leaf (kernels/periodic.py): a stationary member whose view of the inputs adds the warp Phi (ops.periodic_warp) after
     the column selection.  `leaf` is in the DEVICE form -- the base family over the 2 D_i warped columns with lengthscales 2 l, an ARD
@@ -455,10 +519,10 @@ class KernelSpec:
     """What the reverse pass needs to know about the covariance function: ONE kernel leaf, or a Sum / Product of leaves -- flat, or
     nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220
     `Sum`, :305-315 `Product`; the reference differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).
-    members: leaves (leaf.Leaf, leaf.DotLeaf, leaf.ArcLeaf), given as such or as tuples (family, variance, lengthscales[, alpha]); op: None | "add" |
+    members: leaves (leaf.Leaf, leaf.DotLeaf, leaf.ArcLeaf, leaf.CoregionLeaf), given as such or as tuples (family, variance, lengthscales[, alpha]); op: None | "add" |
     "mul" | tree.
 
-    The constructor chooses ONE member object per leaf (`parts`: a StationaryMember, StaticMember, DotMember, ArcMember or PeriodicMember), the
+    The constructor chooses ONE member object per leaf (`parts`: a StationaryMember, StaticMember, DotMember, ArcMember, CoregionMember or PeriodicMember), the
     only place where the kind of a leaf is asked.  Everything else here is about the TREE: `_build`, `_constant`, `_kd`, `_kd_rows`,
     `_diag_adjoint`, `_dkd` and `_adjoint` are the only walkers, and at a leaf each is one call on the member object.
 
@@ -475,7 +539,7 @@ class KernelSpec:
         """members: leaves or tuples, see the class; cols[i]: the input columns member i sees (its `active_dims` as an index
         list, kernels/base.py:90-109) or None for all of them; periods[i]: None, or the period (0-d or [D_i]) of a Periodic member,
         whose leaf is then in the device form (PeriodicMember)."""
-        self.members = [m if isinstance(m, (Leaf, DotLeaf, ArcLeaf)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
+        self.members = [m if isinstance(m, (Leaf, DotLeaf, ArcLeaf, CoregionLeaf)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
         # (k0 + k1) * k2 (kernels/base.py:223-329: a Combination holds kernels, which may be Combinations of the other kind).
@@ -495,10 +559,11 @@ class KernelSpec:
             raise ValueError("one period (or None) per member")
         self.periods = [None if p is None else np.asarray(p, dtype=np.float64) for p in periods]
         for leaf, p in zip(self.members, self.periods):
-            if p is not None and (isinstance(leaf, (DotLeaf, ArcLeaf)) or leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
+            if p is not None and (isinstance(leaf, (DotLeaf, ArcLeaf, CoregionLeaf)) or leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
                 raise ValueError("a periodic member is a leaf with a distance over the warped columns, its period 0-d or [D]")
         self.parts = [PeriodicMember(leaf, c, p) if p is not None else DotMember(leaf, c) if isinstance(leaf, DotLeaf)
                       else ArcMember(leaf, c) if isinstance(leaf, ArcLeaf)
+                      else CoregionMember(leaf, c) if isinstance(leaf, CoregionLeaf)
                       else StaticMember(leaf, c) if leaf.is_static else StationaryMember(leaf, c)
                       for leaf, c, p in zip(self.members, self.cols, self.periods)]
 
@@ -824,7 +889,7 @@ class _Seed:
         return torch.mul(ve, -scale / nv).add_(scale / nv * B * P * (k0 - 0.5)).reshape(1)
 
 
-_ROW_DIAGONAL = "a dot-product or ArcCosine member (Linear, Polynomial, ArcCosine): K(x, x) depends on the row, which is not built into "
+_ROW_DIAGONAL = "a dot-product, ArcCosine or Coregion member (Linear, Polynomial, ArcCosine, Coregion): K(x, x) depends on the row, which is not built into "
 
 
 def _knn_terms(spec: KernelSpec, Xb, s0):

@@ -136,9 +136,15 @@ def is_arc_leaf(k) -> bool:
     return bool(getattr(k, "arc_leaf", False)) and not is_device_leaf(k) and not is_dot_leaf(k)
 
 
+def is_coregion_leaf(k) -> bool:
+    """True for a Coregion kernel (kernels/misc.py), built by gpk_coregion_kernel_matrix.  Never together with `is_device_leaf`,
+    `is_dot_leaf` or `is_arc_leaf`: its K_diag depends on the row's task label, and an element is a gather from the output covariance."""
+    return bool(getattr(k, "coregion_leaf", False)) and not is_device_leaf(k) and not is_dot_leaf(k) and not is_arc_leaf(k)
+
+
 def has_row_diagonal_leaf(k) -> bool:
-    """a leaf whose K(x, x) depends on the row: the dot-product kernels and ArcCosine"""
-    return is_dot_leaf(k) or is_arc_leaf(k)
+    """a leaf whose K(x, x) depends on the row: the dot-product kernels, ArcCosine and Coregion"""
+    return is_dot_leaf(k) or is_arc_leaf(k) or is_coregion_leaf(k)
 
 
 class Combination(Kernel):
@@ -215,13 +221,13 @@ class Combination(Kernel):
 def reverse_leaf(k, input_dim=None):
     """(leaf, period or None, leaf_params) of a kernel that is ONE leaf the reverse pass covers, else None: an isotropic-stationary or a
     static kernel that the device builds, a Periodic one over such a base (`leaf` in the device form, the warp left to the spec: its
-    `periods`), a dot-product one, or an ArcCosine one.  A Periodic kernel's width is checked here, before anything touches the device, wherever its
+    `periods`), a dot-product one, an ArcCosine one, or a Coregion one.  A Periodic kernel's width is checked here, before anything touches the device, wherever its
     active columns can be counted: an index list, or a slice of `input_dim` columns."""
     from .periodic import Periodic
     from .stationaries import IsotropicStationary
     from .statics import Static
     periodic = isinstance(k, Periodic)
-    if not (((periodic or isinstance(k, (IsotropicStationary, Static))) and is_device_leaf(k)) or is_dot_leaf(k) or is_arc_leaf(k)):
+    if not (((periodic or isinstance(k, (IsotropicStationary, Static))) and is_device_leaf(k)) or has_row_diagonal_leaf(k)):
         return None
     if periodic and not isinstance(k.active_dims, slice):
         k.check_width(len(k.active_dims))
@@ -249,7 +255,7 @@ def gradient_spec(kernel, input_dim=None):
         found.append(reverse_leaf(k, input_dim))
         if found[-1] is None:      # (not one of its leaves)
             raise NotImplementedError("gradients of a kernel combination: Sums / Products (possibly nested) of isotropic-stationary, "
-                                      "Periodic, static, dot-product (Linear, Polynomial) and ArcCosine members (kernels/base.py:216-220, 305-315)")
+                                      "Periodic, static, dot-product (Linear, Polynomial), ArcCosine and Coregion members (kernels/base.py:216-220, 305-315)")
         ks.append(k)
         return len(ks) - 1
     tree = walk(kernel)

@@ -8,16 +8,27 @@ Built in one pass by gpk_arccos_kernel_matrix (csrc/arccosine/arccosine.hip), fo
 gpk_arccos_kernel_matrix_combine.  Like the dot-product kernels it is NOT a DeviceLeaf -- its diagonal depends on the row, so every
 fused route that takes K_diag for the variance (`kernels.base.is_device_leaf`) declines it and the composed routes run -- and it is not
 a dot-product leaf either: each element needs both row norms and an acos.  `is_arc_leaf` is its predicate, `leaf()` a leaf.ArcLeaf.
-K(X, X) takes its diagonal by index (include/gpk.h); K_diag is the closed form, a relative 1.4e-8 from it at order 0, as in the reference."""
+K(X, X) takes its diagonal by index (include/gpk.h); K_diag is the closed form, a relative 1.4e-8 from it at order 0, as in the reference.
+
+The Coregion kernel (gpflow/kernels/misc.py), the intrinsic-coregionalisation (multi-task) kernel over ONE column of task labels:
+
+    B = W W^T + diag(kappa)  [output_dim, output_dim]          K(x, y) = B[l(x), l(y)]          K_diag(x) = B[l(x), l(x)]
+
+the usual recipe being `k_data(active_dims=[0 .. D-1]) * Coregion(output_dim=P, rank=R, active_dims=[D])`.  Built by
+gpk_coregion_kernel_matrix (csrc/coregion/coregion.hip: a gather from B staged in LDS), folded into a Sum / Product in place by
+gpk_coregion_kernel_matrix_combine -- the launch the recipe's Product makes.  Not a DeviceLeaf, not a dot-product leaf, not an ArcCosine
+one: `is_coregion_leaf` is its predicate, `leaf()` a leaf.CoregionLeaf.  A label is the column truncated toward zero, valid inside
+(-1, output_dim); an invalid one makes its row / column of K NaN (include/gpk.h)."""
 from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
 from ..base import Parameter, positive
 from .. import ops
-from ..leaf import ARC_PARAMETERS, ArcLeaf, check_order
+from ..leaf import ARC_PARAMETERS, COREGION_PARAMETERS, ArcLeaf, CoregionLeaf, check_coregion_sizes, check_order
 from .base import ActiveDims, Kernel
 
 
@@ -85,3 +96,71 @@ class ArcCosine(Kernel):
         X = ops.to_device(X)
         self.check_width(X.shape[-1])
         return ops.arccos_kernel_diag(X.reshape(-1, X.shape[-1]).contiguous(), **self.leaf().keywords()).reshape(X.shape[:-1])
+
+
+class Coregion(Kernel):
+    """misc.py `Coregion`: `W` [output_dim, rank] unconstrained, initial 0.1 * ones; `kappa` [output_dim] positive, initial ones;
+    `output_dim` in 1 ... 64 and `rank` in 1 ... 64 (anything else raises ValueError); exactly ONE active input column, the task label"""
+    coregion_leaf = True
+
+    def __init__(self, output_dim: int, rank: int, *, active_dims: Optional[ActiveDims] = None, name: Optional[str] = None):
+        self.output_dim, self.rank = check_coregion_sizes(output_dim, rank)     # ValueError before anything else
+        super().__init__(active_dims=active_dims, name=name)
+        if not isinstance(self._active_dims, slice) and len(self._active_dims) != 1:
+            raise ValueError(f"Coregion(active_dims={list(self._active_dims)}): exactly one active input column, the task label")
+        self.W = Parameter(0.1 * np.ones((self.output_dim, self.rank)))
+        self.kappa = Parameter(np.ones(self.output_dim), transform=positive())
+
+    def leaf_params(self) -> tuple:
+        """(kappa, W): the order of the gradients (leaf.COREGION_PARAMETERS); the Parameters themselves are W, then kappa"""
+        return tuple(getattr(self, name) for name in COREGION_PARAMETERS)
+
+    def leaf(self) -> CoregionLeaf:
+        W, kappa = self.W.numpy(), self.kappa.numpy()
+        if W.shape != (self.output_dim, self.rank) or kappa.shape != (self.output_dim,):
+            raise ValueError(f"W of shape {W.shape} and kappa of shape {kappa.shape}: [{self.output_dim}, {self.rank}] and [{self.output_dim}]")
+        return CoregionLeaf(W, kappa)
+
+    @staticmethod
+    def check_width(d: int) -> None:
+        """ValueError, before the device, unless the kernel sees exactly one input column"""
+        if d != 1:
+            raise ValueError(f"Coregion: the kernel sees {d} input columns; exactly one active column (the task label) is needed: "
+                             "set active_dims=[column]")
+
+    def output_covariance(self) -> torch.Tensor:
+        """B = W W^T + diag(kappa) [output_dim, output_dim], on the device (a fresh tensor)"""
+        return ops.coregion_output_covariance(**self.leaf().keywords()).clone()
+
+    def output_variance(self) -> torch.Tensor:
+        """diag(B) = sum_r W[:, r]^2 + kappa [output_dim], on the device"""
+        return torch.diagonal(ops.coregion_output_covariance(**self.leaf().keywords())).clone()
+
+    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
+        self.check_width(X.shape[-1])
+        return ops.coregion_kernel_matrix(X, X2, diag_add=diag_add, lower_only=lower_only, out=out, **self.leaf().keywords())
+
+    def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
+        """out <- out .* K or out + K in place, as DeviceLeaf.K_fold"""
+        self.check_width(X.shape[-1])
+        return ops.coregion_kernel_matrix_combine(X, X2, out, op=op, diag_add=diag_add, out=out, **self.leaf().keywords())
+
+    def K(self, X, X2=None) -> torch.Tensor:
+        """leading batch dimensions as Linear.K: flattened to rows and restored"""
+        X = ops.to_device(X)
+        D = X.shape[-1]
+        self.check_width(D)
+        if X2 is None:
+            if X.dim() == 2:
+                return self.K_into(X, None, None)
+            lead, n = X.shape[:-2], X.shape[-2]
+            return torch.stack([self.K_into(x.contiguous(), None, None) for x in X.reshape(-1, n, D)]).reshape(*lead, n, n)
+        X2 = ops.to_device(X2)
+        Kf = self.K_into(X.reshape(-1, D).contiguous(), X2.reshape(-1, D).contiguous(), None)
+        return Kf.reshape(*X.shape[:-1], *X2.shape[:-1])
+
+    def K_diag(self, X) -> torch.Tensor:
+        """the row diagonal on the device (gpk_coregion_kernel_diag), read from B; leading batch dimensions allowed"""
+        X = ops.to_device(X)
+        self.check_width(X.shape[-1])
+        return ops.coregion_kernel_diag(X.reshape(-1, 1).contiguous(), **self.leaf().keywords()).reshape(X.shape[:-1])

@@ -265,6 +265,75 @@ class ArcLeaf(collections.namedtuple("_ArcLeafFields", "order variance weight_va
         return {"lengthscales": g[:0], "weight_variances": g[:nw], "bias_variance": g[nw:nw + 1]}
 
 
+COREGION_MAX_OUTPUTS = 64             # GPK_COREGION_MAX_OUTPUTS
+COREGION_MAX_RANK = 64                # GPK_COREGION_MAX_RANK
+COREGION_PARAMETERS = ("kappa", "W")  # in the order of the gradients: the "variance" slot holds d/dkappa, the shape gradient d/dW
+
+
+def check_coregion_sizes(output_dim, rank) -> tuple:
+    """(output_dim, rank) as ints; ValueError unless both are integral, output_dim in 1 ... COREGION_MAX_OUTPUTS and rank in
+    1 ... COREGION_MAX_RANK"""
+    for name, v, top in (("output_dim", output_dim, COREGION_MAX_OUTPUTS), ("rank", rank, COREGION_MAX_RANK)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
+            raise ValueError(f"Coregion({name}={v!r}): an integer in 1 ... {top}")
+    return int(output_dim), int(rank)
+
+
+class CoregionLeaf(collections.namedtuple("_CoregionLeafFields", "W kappa")):
+    """One Coregion leaf's host values (gpflow/kernels/misc.py `Coregion`), immutable: `W` [P, R] unconstrained, `kappa` [P] positive;
+    B = W W^T + diag(kappa), K(x, y) = B[l(x), l(y)] over ONE column of task labels.  Its diagonal depends on the row; it is no row of
+    FAMILIES and none of DOT_FAMILIES -- the gpk_coregion_* entry points take it (ops.coregion_kernel_matrix, ...).  In the gradient
+    layout of a KernelSpec the slot called "variance" holds d/dkappa [P] (as the ARD variance of a DotLeaf has D entries) and the shape
+    gradient is d/dW flattened row-major [P R]."""
+    __slots__ = ()
+    is_plain = False
+    family = "Coregion"
+    parameters = COREGION_PARAMETERS
+
+    def __new__(cls, W, kappa):
+        W, kappa = np.array(W, dtype=np.float64), np.array(kappa, dtype=np.float64)
+        if W.ndim != 2 or kappa.ndim != 1 or kappa.shape[0] != W.shape[0]:
+            raise ValueError(f"W of shape {W.shape} and kappa of shape {kappa.shape}: W is [output_dim, rank], kappa [output_dim]")
+        check_coregion_sizes(*W.shape)
+        W.setflags(write=False)
+        kappa.setflags(write=False)
+        return tuple.__new__(cls, (W, kappa))
+
+    @classmethod
+    def of(cls, values) -> "CoregionLeaf":
+        """from the values in gradient order (COREGION_PARAMETERS: kappa, then W)"""
+        return cls(**dict(zip(COREGION_PARAMETERS, values)))
+
+    def replace(self, values) -> "CoregionLeaf":
+        return CoregionLeaf.of(values)
+
+    @property
+    def n_outputs(self) -> int:
+        return int(self.W.shape[0])
+
+    @property
+    def rank(self) -> int:
+        return int(self.W.shape[1])
+
+    @property
+    def n_variance(self) -> int:
+        """entries of the gradient slot the spec calls "variance": d/dkappa [P]"""
+        return self.n_outputs
+
+    @property
+    def n_shape(self) -> int:
+        """entries of the shape gradient: d/dW flattened row-major"""
+        return self.n_outputs * self.rank
+
+    def keywords(self) -> dict:
+        """as the `ops.coregion_*` builders take a leaf"""
+        return dict(W=self.W, kappa=self.kappa)
+
+    def split_shape(self, g) -> dict:
+        """a shape gradient as {"lengthscales": empty, "W": [P R]}"""
+        return {"lengthscales": g[:0], "W": g}
+
+
 def check_degree(degree) -> int:
     """the Polynomial's degree as an int; NotImplementedError unless it is integral and in [1, DOT_MAX_DEGREE]"""
     try:

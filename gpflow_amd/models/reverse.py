@@ -51,11 +51,11 @@ def _supported_stationary(k) -> bool:
     return reverse_leaf(k) is not None and not has_row_diagonal_leaf(k)
 
 
-ROW_DIAGONAL = "a dot-product or ArcCosine kernel or member (Linear, Polynomial, ArcCosine), whose K(x, x) depends on the row,"
+ROW_DIAGONAL = "a dot-product, ArcCosine or Coregion kernel or member (Linear, Polynomial, ArcCosine, Coregion), whose K(x, x) depends on the row,"
 
 
 def has_row_diagonal(k) -> bool:
-    """a dot-product kernel (kernels/linears.py) or an ArcCosine kernel (kernels/misc.py) anywhere under k -- in a Sum / Product, or
+    """a dot-product kernel (kernels/linears.py) or an ArcCosine or Coregion kernel (kernels/misc.py) anywhere under k -- in a Sum / Product, or
     behind a multi-output wrapper"""
     if has_row_diagonal_leaf(k):
         return True
@@ -83,7 +83,7 @@ class CovarianceRoute:
         found = reverse_leaf(kernel, input_dim)
         if found is None:
             raise NotImplementedError("gradients: a SquaredExponential / Matern / Exponential / RationalQuadratic / White / Constant / "
-                                      "Periodic / Linear / Polynomial / ArcCosine kernel, or a Sum / Product (possibly nested) of them")
+                                      "Periodic / Linear / Polynomial / ArcCosine / Coregion kernel, or a Sum / Product (possibly nested) of them")
         leaf, period, params = found
         self.spec, self.members = gradients.KernelSpec([leaf], periods=[period]), [params]
 

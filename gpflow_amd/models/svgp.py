@@ -352,7 +352,10 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             ops.check_info(info)
             Fv += float(F.cpu()[0])
             kernel_pairs += route.kernel_pairs(g)
-            host = {n: g[n].cpu().numpy() for n in g if n not in ("variance", "lengthscales", "alpha", "period", "offset", "Z")}
+            # (the kernel's entries went through route.kernel_pairs; in a combination each is a list with one entry per member)
+            kernel_names = {"variance", "lengthscales", "alpha", "period", "offset", "Z"} \
+                | {n for i in range(route.spec.n) for n in route.spec.parameter_names(i)}
+            host = {n: g[n].cpu().numpy() for n in g if n not in kernel_names}
             gz = scatter(g["Z"]).cpu().numpy()
             zgrads[id(iv.Z)] = (iv.Z, zgrads[id(iv.Z)][1] + gz if id(iv.Z) in zgrads else gz)   # shared Z: contributions add up
             hosts.append(host)

@@ -6,13 +6,14 @@ nothing silently falls back to torch math or to the CPU.
 """
 from __future__ import annotations
 
+import collections
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .leaf import FAMILIES, ArcLeaf, DotLeaf, Leaf
+from .leaf import FAMILIES, ArcLeaf, CoregionLeaf, DotLeaf, Leaf
 
 NB = 128
 KERNEL_FAMILIES = {f.name: f.code for f in FAMILIES}                      # name -> GPK_KERN_* (include/gpk.h)
@@ -399,6 +400,164 @@ def arccos_adjoint_tail(R: torch.Tensor, A: torch.Tensor, Bm: Optional[torch.Ten
                                      Abar.data_ptr(), _rowmajor(Abar, "A_bar"))
     _lib.check(rc, "gpk_arccos_adjoint_tail")
     return small[:1], small[1:1 + nw], small[1 + nw:], Abar
+
+
+# ------------------------------------------------------------------------------------------------ Coregion kernel (coregion/coregion.hip)
+COREGION_MAX_OUTPUTS, COREGION_MAX_RANK = 64, 64   # include/gpk.h: GPK_COREGION_MAX_OUTPUTS, GPK_COREGION_MAX_RANK
+_coregion_cache: "collections.OrderedDict" = collections.OrderedDict()
+
+
+def _cached(key, make):
+    """a small device tensor found by the VALUES it was made from (as gradients.ls_device finds lengthscales): a host -> device copy
+    from pageable memory blocks the host, so each set of values is uploaded, and B built, once"""
+    t = _coregion_cache.get(key)
+    if t is None:
+        t = _coregion_cache[key] = make()
+        while len(_coregion_cache) > 64:
+            _coregion_cache.popitem(last=False)
+    return t
+
+
+def _coregion_host(W, kappa):
+    """(W [P, R], kappa [P]) as contiguous host arrays, checked as CoregionLeaf checks them"""
+    leaf = CoregionLeaf(W, kappa)
+    return np.ascontiguousarray(leaf.W), np.ascontiguousarray(leaf.kappa)
+
+
+def _coregion_on_device(a: np.ndarray, dev) -> torch.Tensor:
+    return _cached(("host", a.shape, a.tobytes(), str(dev)), lambda: torch.as_tensor(a.copy(), device=dev))
+
+
+def coregion_output_covariance(W, kappa, *, device_=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """B = W W^T + diag(kappa) [P, P] on the device from the HOST arrays W [P, R] and kappa [P], as a CoregionLeaf holds them
+    (gpk_coregion_output_covariance: one workgroup, exactly symmetric, bit-identical when repeated).  Without `out` the result is
+    cached by the values of (W, kappa): the first call costs two small uploads and the launch, a second call with the same values
+    neither -- the caller must not write to it.  With `out` ([P, P], any leading dimension) the launch is made into it."""
+    lib = _lib.load()
+    Wh, kh = _coregion_host(W, kappa)
+    P, R = Wh.shape
+    dev = torch.device(device_) if device_ is not None else (out.device if out is not None else device())
+
+    def build(B):
+        Wd, kd = _coregion_on_device(Wh, dev), _coregion_on_device(kh, dev)
+        rc = lib.gpk_coregion_output_covariance(_stream(), Wd.data_ptr(), R, kd.data_ptr(), P, R, B.data_ptr(), _rowmajor(B, "B"))
+        _lib.check(rc, "gpk_coregion_output_covariance")
+        return B
+    if out is not None:
+        _chk(out, "out", 2)
+        if tuple(out.shape) != (P, P):
+            raise ValueError(f"coregion_output_covariance: out must be [{P}, {P}]")
+        return build(out)
+    return _cached(("B", Wh.shape, Wh.tobytes(), kh.tobytes(), str(dev)),
+                   lambda: build(torch.empty((P, P), dtype=torch.float64, device=dev)))
+
+
+def _label_columns(X1, X2, G, out, what: str, zero_new: bool = False):
+    n1, n2, d, out = _kernel_operands(X1, X2, G, out, zero_new=zero_new)
+    if d != 1:
+        raise ValueError(f"{what}: the Coregion kernel reads ONE column of task labels, got {d}")
+    return n1, n2, out
+
+
+def coregion_kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, W, kappa, diag_add: float = 0.0, lower_only: bool = False,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K(X1, X2)[i, k] = B[l_i, l'_k] (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2] over the label columns X1 [n1, 1],
+    X2 [n2, 1]; W [P, R], kappa [P] host arrays.  Exact: the bits of B; exactly symmetric; an invalid label (include/gpk.h) makes its row /
+    column NaN."""
+    lib = _lib.load()
+    n1, n2, out = _label_columns(X1, X2, None, out, "coregion_kernel_matrix", zero_new=lower_only)
+    B = coregion_output_covariance(W, kappa, device_=X1.device)
+    if n1 == 0 or n2 == 0:
+        return out
+    rc = lib.gpk_coregion_kernel_matrix(_stream(), X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), B.data_ptr(), B.shape[1],
+                                        B.shape[0], float(diag_add), int(lower_only), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_coregion_kernel_matrix")
+    return out
+
+
+def coregion_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, W, kappa,
+                                   diag_add: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = G .* K(X1, X2) (op "mul") or G + K(X1, X2) (op "add"), K gathered on the fly; `out` may be G itself.  X2 None: K(X1, X1),
+    `diag_add` goes onto the diagonal of the combined result."""
+    if op not in ("mul", "add"):
+        raise ValueError(f"coregion_kernel_matrix_combine: op {op!r} is not 'mul' or 'add'")
+    lib = _lib.load()
+    n1, n2, out = _label_columns(X1, X2, G, out, "coregion_kernel_matrix_combine")
+    B = coregion_output_covariance(W, kappa, device_=X1.device)
+    if n1 == 0 or n2 == 0:
+        return out
+    rc = lib.gpk_coregion_kernel_matrix_combine(_stream(), {"mul": 1, "add": 2}[op], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
+                                                *_x2_args(X2, n2), B.data_ptr(), B.shape[1], B.shape[0], float(diag_add), G.data_ptr(),
+                                                _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_coregion_kernel_matrix_combine")
+    return out
+
+
+def coregion_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op: str = "k", W, kappa,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The row diagonal kd [n] = B[l_i, l_i] over the label column X [n, 1] (op "k"), or g .* kd ("mul"), g + kd ("add") with g [n];
+    `out` may be g.  Read from B: bit for bit the diagonal of coregion_kernel_matrix(X, None)."""
+    lib = _lib.load()
+    _chk(X, "X", 2)
+    n, d = X.shape
+    if d != 1:
+        raise ValueError(f"coregion_kernel_diag: the Coregion kernel reads ONE column of task labels, got {d}")
+    if op not in ("k", "mul", "add"):
+        raise ValueError(f"coregion_kernel_diag: op {op!r} is not 'k', 'mul' or 'add'")
+    if (op == "k") != (g is None):
+        raise ValueError("coregion_kernel_diag: g goes with the ops 'mul' and 'add' and only with them")
+    if g is not None:
+        _chk(g, "g", 1)
+        if g.shape[0] != n or not g.is_contiguous():
+            raise ValueError("coregion_kernel_diag: g must be a contiguous [n]")
+    B = coregion_output_covariance(W, kappa, device_=X.device)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=X.device)
+    _chk(out, "out", 1)
+    if out.shape[0] != n or not out.is_contiguous():
+        raise ValueError("coregion_kernel_diag: out must be a contiguous [n]")
+    if n == 0:
+        return out
+    rc = lib.gpk_coregion_kernel_diag(_stream(), {"k": 0, "mul": 1, "add": 2}[op], X.data_ptr(), n, _rowmajor(X, "X"), B.data_ptr(),
+                                      B.shape[1], B.shape[0], None if g is None else g.data_ptr(), out.data_ptr())
+    _lib.check(rc, "gpk_coregion_kernel_diag")
+    return out
+
+
+def coregion_onehot_rows(X: torch.Tensor, n_outputs: int) -> torch.Tensor:
+    """E [P, n] with E[a, i] = 1 where the label of row i of X [n, 1] is a, else 0 (column i NaN for an invalid label): the right-hand
+    side of the Coregion adjoint's contractions (gradients.coregion_kernel_adjoint), as moment_rows is for the dot-product kernels."""
+    lib = _lib.load()
+    _chk(X, "X", 2)
+    n, d = X.shape
+    P = int(n_outputs)
+    if d != 1 or not 1 <= P <= COREGION_MAX_OUTPUTS:
+        raise ValueError(f"coregion_onehot_rows: X must be one column of labels and n_outputs in 1 ... {COREGION_MAX_OUTPUTS}")
+    E = torch.empty((P, n), dtype=torch.float64, device=X.device)
+    if n == 0:
+        return E
+    rc = lib.gpk_coregion_onehot_rows(_stream(), X.data_ptr(), n, _rowmajor(X, "X"), P, E.data_ptr(), n)
+    _lib.check(rc, "gpk_coregion_onehot_rows")
+    return E
+
+
+def coregion_adjoint_tail(Bbar: torch.Tensor, *, W) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d/dkappa [P] = diag(Bbar), d/dW [P, R] = (Bbar + Bbar^T) W) from Bbar [P, P] on the device and the host array W [P, R]
+    (gpk_coregion_adjoint_tail: one workgroup, bit-identical when repeated)."""
+    lib = _lib.load()
+    _chk(Bbar, "Bbar", 2)
+    Wh = np.ascontiguousarray(np.asarray(W, dtype=np.float64))
+    if Wh.ndim != 2 or tuple(Bbar.shape) != (Wh.shape[0], Wh.shape[0]) or not 1 <= Wh.shape[0] <= COREGION_MAX_OUTPUTS \
+            or not 1 <= Wh.shape[1] <= COREGION_MAX_RANK:
+        raise ValueError("coregion_adjoint_tail: W must be [P, R] with P, R in 1 ... 64 and Bbar [P, P]")
+    P, R = Wh.shape
+    Wd = _coregion_on_device(Wh, Bbar.device)
+    dW = torch.empty((P, R), dtype=torch.float64, device=Bbar.device)
+    dk = torch.empty(P, dtype=torch.float64, device=Bbar.device)
+    rc = lib.gpk_coregion_adjoint_tail(_stream(), Bbar.data_ptr(), _rowmajor(Bbar, "Bbar"), Wd.data_ptr(), R, P, R, dW.data_ptr(), R,
+                                       dk.data_ptr())
+    _lib.check(rc, "gpk_coregion_adjoint_tail")
+    return dk, dW
 
 
 def diag_add_(A: torch.Tensor, v: torch.Tensor) -> torch.Tensor:

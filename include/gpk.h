@@ -588,6 +588,54 @@ int gpk_arccos_adjoint_stage(void* stream, int order, const double* X1, int n1, 
 int gpk_arccos_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, const double* B, long ldb, int n2,
                             int d, const double* w_host, int ard, const double* parts, double* rg, double* dsmall, double* Abar,
                             long ldab);
+/* ---- Coregion kernel (coregion/coregion.hip; gpflow/kernels/misc.py `Coregion`) --------------------------------------------------
+ * The intrinsic-coregionalisation (multi-task) kernel over ONE input column that carries the row's task label.  With W [P, R]
+ * (unconstrained) and kappa [P] (positive), P = output_dim <= GPK_COREGION_MAX_OUTPUTS, R = rank <= GPK_COREGION_MAX_RANK:
+ *     B = W W^T + diag(kappa)  [P, P]        K(x, y) = B[l(x), l(y)]        K_diag(x) = B[l(x), l(x)]
+ * LABELS.  The label l of a row is its one column converted as the reference's tf.cast(., int32) converts it: truncation toward zero
+ * (2.7 -> 2, -0.5 -> 0).  A label is VALID when the DOUBLE satisfies -1 < x < P; the test is made on the double, before any
+ * conversion to an integer.  Anything else (NaN, +-Inf, x <= -1, x >= P) is an invalid label: it never forms an address, and it follows
+ * the library's NaN rule -- a NaN in row i of X1 makes row i of K NaN and nothing else: an invalid label in row i of X1 makes row i of
+ * K NaN (in the symmetric build, and for X2, the column as well), kd_i NaN and column i of E NaN, and touches nothing else.
+ * B is a TYPED operand (DEVICE, [P, P] row-major, ldb >= P; exactly the P x P elements are read or written), not a workspace.
+ * No entry point uses atomics or reads the environment.  Not a GPK_KERN_* family, not a GPK_DOT_* code; no fused driver takes it.
+ * Every entry point returns, before any launch and with nothing written: GPK_E_ARG for P <= 0, P > GPK_COREGION_MAX_OUTPUTS, R <= 0,
+ * R > GPK_COREGION_MAX_RANK, a negative size, a leading dimension that is too small (ldx < 1), an op out of range, a NULL operand
+ * that has elements; 0 without a launch where there is nothing to do.
+ *
+ * gpk_coregion_output_covariance: one workgroup.  W (DEVICE, [P, R] ldw), kappa (DEVICE, [P]) -> B [P, P] ldb.  B[a, b] is an fma
+ *   chain over r ascending from 0.0 of W[a, r] * W[b, r]; on the diagonal kappa[a] is added last.  Products commute, so B is EXACTLY
+ *   symmetric; a second call gives the same bits.
+ * gpk_coregion_kernel_matrix: the contract of gpk_dot_kernel_matrix over the label columns X1 [n1, 1] ldx1, X2 [n2, 1] ldx2 and B --
+ *   X2 == NULL: K(X1, X1) + diag_add I; lower_only: only the elements on or below the diagonal are written; an operand without
+ *   elements may be NULL; nothing beyond n1 x n2 is written; any ldk and alignment (K misaligned or ldk odd: scalar stores).  One
+ *   64 x 64 tile per workgroup, which stages B and the tile's 64 + 64 labels in LDS; an element is one LDS gather and one global store
+ *   and has the BITS of B[l_i, l_k], so the symmetric build is exactly symmetric without a mirror pass and lower_only is bit for bit
+ *   the lower triangle of the full build.  diag_add is ignored when X2 is given.
+ * gpk_coregion_kernel_matrix_combine: out = G .* k (op 1) or G + k (op 2); out may alias G; X2 == NULL: diag_add goes onto the
+ *   diagonal of the combined result.  No derivative op: no parameter enters through a scalar argument.
+ * gpk_coregion_kernel_diag: kd_i = B[l_i, l_i], read from B: bit for bit the diagonal of gpk_coregion_kernel_matrix(X, NULL) with
+ *   diag_add = 0.  op 0: out = kd; 1: g .* kd; 2: g + kd.  g [n] (DEVICE; not read by op 0), out [n]; out may alias g.
+ * gpk_coregion_onehot_rows: E [P, n] lde, E[a, i] = 1 where l_i == a, else 0 (column i all NaN for an invalid label): the right-hand
+ *   side of the adjoint's contractions, as gpk_moment_rows is for the dot-product kernels.
+ * gpk_coregion_adjoint_tail: one workgroup.  With Bbar[a, b] = sum_{i: l_i = a} sum_{k: l'_k = b} Kbar[i, k] ([P, P] ldbb, DEVICE) and W:
+ *     dW [P, R] lddw = (Bbar + Bbar^T) W  -- dW[a, r] is an fma chain over b ascending of (Bbar[a, b] + Bbar[b, a]) * W[b, r]
+ *     dkappa [P]     = diag(Bbar)
+ *   The same formulas serve K(X, X) with a symmetric Kbar: Bbar already collects both arguments.  Fixed summation order: a second call
+ *   is bit-identical. */
+#define GPK_COREGION_MAX_OUTPUTS 64
+#define GPK_COREGION_MAX_RANK 64
+int gpk_coregion_output_covariance(void* stream, const double* W, long ldw, const double* kappa, int P, int R, double* B, long ldb);
+int gpk_coregion_kernel_matrix(void* stream, const double* X1, int n1, long ldx1, const double* X2, int n2, long ldx2, const double* B,
+                               long ldb, int P, double diag_add, int lower_only, double* K, long ldk);
+int gpk_coregion_kernel_matrix_combine(void* stream, int op, const double* X1, int n1, long ldx1, const double* X2, int n2, long ldx2,
+                                       const double* B, long ldb, int P, double diag_add, const double* G, long ldg, double* out,
+                                       long ldo);
+int gpk_coregion_kernel_diag(void* stream, int op, const double* X, int n, long ldx, const double* B, long ldb, int P, const double* g,
+                             double* out);
+int gpk_coregion_onehot_rows(void* stream, const double* X, int n, long ldx, int P, double* E, long lde);
+int gpk_coregion_adjoint_tail(void* stream, const double* Bbar, long ldbb, const double* W, long ldw, int P, int R, double* dW, long lddw,
+                              double* dkappa);
 /* gpk_adam_step:  tf.keras Adam on one variable of n doubles, in place:  g' = maximise ? -g : g,
  *   m = beta1 m + (1 - beta1) g',  v = beta2 v + (1 - beta2) g'^2,  p -= step m / (sqrt(v) + epsilon),
  *   step = lr sqrt(1 - beta2^t) / (1 - beta1^t) computed by the caller. */
