@@ -60,6 +60,9 @@ _SIGS = {
                                         c_size_t]),
     "gpk_likelihood_varexp_sum": (c_int, [c_void_p, c_int, C.POINTER(c_double), _dp, c_long, _dp, c_int, c_int, _dp, c_int, _dp,
                                           C.POINTER(c_double), c_int, c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_size_t]),
+    "gpk_switched_varexp_blocks": (c_int, [c_int, c_int]),
+    "gpk_switched_varexp_sum": (c_int, [c_void_p, c_int, C.POINTER(c_int), C.POINTER(c_double), _dp, c_long, c_int, _dp, c_int, c_int,
+                                        _dp, c_int, _dp, C.POINTER(c_double), c_int, c_double, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpk_mixed_varexp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gpk_mixed_gaussian_varexp_sum": (c_int, [c_void_p, _dp, c_long, _dp, c_int, c_int, c_int, C.POINTER(c_double), _dp, c_int, _dp,
                                               C.POINTER(c_double), c_int, c_double, c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_size_t]),

@@ -16,6 +16,7 @@
 // stages B ([P][P], 32 KB at P = 64) and the labels of its 64 rows and 64 columns in LDS; an element is one LDS gather and one global
 // store.  No atomics, no environment reads, vector or plain C++ stores only.
 #include "../pair_tile.h"
+#include "../label.h"   // label_of
 #include <cmath>
 
 namespace {
@@ -23,10 +24,6 @@ namespace {
 using namespace pair_tile;
 constexpr int MAXP = GPK_COREGION_MAX_OUTPUTS;
 constexpr int MAXR = GPK_COREGION_MAX_RANK;
-
-// the label of a row, or -1 for an invalid one.  The DOUBLE is tested (both comparisons are false for a NaN); only a value inside
-// (-1, P) is converted, and the conversion truncates toward zero.
-__device__ __forceinline__ int label_of(double x, int P) { return (x > -1.0 && x < (double)P) ? (int)x : -1; }
 
 struct CoArgs {
   const double* X1; long ldx1; int n1;

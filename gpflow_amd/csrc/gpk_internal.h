@@ -148,5 +148,7 @@ __attribute__((weak)) int gpk_launch_mixed_varexp_stage1(hipStream_t s, const La
                                    double* fvar_out, double* dgmu_out, double* part0, double* part1, double* partW, int* count);
 // the quadrature stage of gpk_likelihood_varexp_sum; part1 (partials of sum dVE/dscale) may be null
 int gpk_likelihood_check(int lik, const double* params, int P);   // 0, GPK_E_UNSUPPORTED (unknown code) or GPK_E_ARG (parameters, classes)
+// the same answer, and the three constants the code's element body reads (lik_element.h: LikConsts), computed once on the host
+int gpk_likelihood_constants(int lik, const double* params, int P, double* par0, double* par1, double* c0);
 int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const LatentMoments& m, double* rows_out,
                                         double* dmu_out, double* dvar_out, double* part, double* part1, int* count);

@@ -1,20 +1,9 @@
 // The variational-expectation stage of an ELBO shard: Gaussian in closed form (varexp_kernel), scalar likelihoods by Gauss-Hermite
 // quadrature (lik_varexp_kernel), MultiClass / RobustMax (lik_multiclass_kernel), Gaussian on linearly mixed latents
 // (mixed_varexp_kernel: LinearCoregionalization).  Stage 1 of the two-stage reductions of reduce.hip.
-#include "reduce_device.h"
-#include "digamma.h"
+#include "lik_element.h"   // latent_var, the quadrature table, QuadLanes, lik_element<LIK>
 
 namespace {
-
-// fvar[b,p] = knn - s0 + ssq, in this order and each step a statement of its own: with -ffp-contract=on the bits depend on it.
-// slot_sum (varexp_kernel<true>): the last term, already summed from the slot partials in slot order, in place of m.ssq.
-__device__ __forceinline__ double latent_var(const LatentMoments& m, long b, int p, const double* slot_sum = nullptr) {
-  double fv = m.knn[m.knn_per_latent ? p : 0];
-  if (m.s0) fv -= m.s0_per_latent ? m.s0[(long)p * m.rows + b] : m.s0[b];
-  if (slot_sum) fv += *slot_sum;
-  else if (m.ssq) fv += m.ssq[(long)p * m.rows + b];
-  return fv;
-}
 
 // ---- Gaussian variational expectations, stage 1 -----------------------------------------------------
 struct VarexpArgs {
@@ -89,21 +78,7 @@ __global__ __launch_bounds__(RB) void varexp_kernel(VarexpArgs a) {
 // quadrature/gauss_hermite.py; scalar_discrete.py Bernoulli / Poisson / Ordinal; scalar_continuous.py StudentT / Exponential /
 // Gamma / Beta; the formulas of every code: include/gpk.h) -----------------------------------------------------------------
 //   VE[b,p] = sum_h (w_h / sqrt(pi)) g(mu + sqrt(2 v) x_h),  g = log p(y | f),  with d/dmu and d/dv of that same sum.
-// numpy.polynomial.hermite.hermgauss(20), the reference's DEFAULT_NUM_GAUSS_HERMITE_POINTS (gpk_gauss_hermite returns this table)
-#define GPK_GH20_X                                                                                                          \
-  -5.387480890011233, -4.603682449550744, -3.944764040115625, -3.3478545673832163, -2.7888060584281305, -2.2549740020892757, \
-      -1.7385377121165861, -1.234076215395323, -0.7374737285453944, -0.24534070830090124, 0.24534070830090124,              \
-      0.7374737285453944, 1.234076215395323, 1.7385377121165861, 2.2549740020892757, 2.7888060584281305, 3.3478545673832163, \
-      3.944764040115625, 4.603682449550744, 5.387480890011233
-#define GPK_GH20_W                                                                                                          \
-  2.2293936455341447e-13, 4.3993409922731747e-10, 1.0860693707692782e-07, 7.80255647853206e-06, 0.00022833863601635365,     \
-      0.0032437733422378567, 0.024810520887463643, 0.1090172060200233, 0.28667550536283415, 0.4622436696006101,              \
-      0.4622436696006101, 0.28667550536283415, 0.1090172060200233, 0.024810520887463643, 0.0032437733422378567,              \
-      0.00022833863601635365, 7.80255647853206e-06, 1.0860693707692782e-07, 4.3993409922731747e-10, 2.2293936455341447e-13
-constexpr int GH_N = 20;
-constexpr int GPK_ORDINAL_MAXEDGE = 15;
-__constant__ const double gh_x_dev[GH_N] = {GPK_GH20_X};
-__constant__ const double gh_w_dev[GH_N] = {GPK_GH20_W};
+// the node table: lik_element.h (gpk_gauss_hermite returns the host copy)
 const double gh_x_host[GH_N] = {GPK_GH20_X};
 const double gh_w_host[GH_N] = {GPK_GH20_W};
 
@@ -118,53 +93,11 @@ struct LikVarexpArgs {
   int nedge; double edge[GPK_ORDINAL_MAXEDGE];
 };
 
-// One element (b, p) is shared by LPE = 4 adjacent lanes, five nodes each (8192 x P elements with a serial 20-node loop of fp64
-// erfc + log + exp per thread would leave most of the chip idle); the four partial sums meet through two xor shuffles, so all
-// four lanes hold the same bits.  The closed-form branches (Poisson, Exponential, Gamma) have no nodes: one lane per element.  A wave pass covers
-// floor((64 / LPE) / P) WHOLE rows, so that the row sums of rows_out are a fixed-order shuffle loop inside one wave.
-// This layout is written down once, for both kernels and for the launcher's grid:
-__host__ __device__ constexpr int quad_lpe(int lik) {   // lanes per element
-  return lik == GPK_LIK_POISSON_EXP || lik == GPK_LIK_EXPONENTIAL_EXP || lik == GPK_LIK_GAMMA_EXP ? 1 : 4;
-}
-__host__ __device__ constexpr int quad_rows_per_pass(int lpe, int P) { return (64 / lpe) / P; }      // (P <= 16 <= 64 / lpe)
-template <int LPE>
-struct QuadLanes {
-  int k, p;        // this lane's node quarter and latent
-  int jr, rpw;     // its group's row within a pass, whole rows per pass
-  int row_lane0;   // lane of the row's first group
-  long npass;
-  __device__ explicit QuadLanes(const LatentMoments& m) {
-    const int lane = threadIdx.x & 63, g = lane / LPE;
-    k = lane % LPE; rpw = quad_rows_per_pass(LPE, m.P);
-    jr = g / m.P; p = g - jr * m.P;
-    row_lane0 = (jr * m.P * LPE) & 63;
-    npass = ((long)m.rows + rpw - 1) / rpw;
-  }
-  // row b, label (column ycol of Y), mean and variance of this lane's element in pass u; false: an idle lane, which runs on
-  // harmless values and is masked by the caller
-  __device__ bool load(const LatentMoments& m, long u, int ycol, long& b, double& y, double& mu, double& fv) const {
-    b = u * rpw + jr;
-    const bool act = jr < rpw && b < m.rows;
-    y = 0.0; mu = 0.0; fv = 1.0;
-    if (act) {
-      fv = latent_var(m, b, p);
-      mu = m.fmean[b * m.P + p] + m.mean_const;
-      y = m.Y[b * m.ldy + ycol];
-    }
-    return act;
-  }
-};
-
-// Non-finite inputs: NaN / Inf in fmean or fvar travel through the arithmetic; a non-finite label adds y - y = NaN to every output
-// of its element (the comparison y == 1 of the Bernoulli density would otherwise read a NaN label as class 0).  Ordinal: a label that
-// is no integer in [0, nedge] adds NaN instead (the MultiClass rule), to the parameter derivative as well.
-// The node loop of the Beta branch is NOT unrolled: each node holds two lgamma and two gpk_digamma, and five inlined copies of
-// them buy nothing but registers (DESIGN.md section 6 has the compiler's figures for every instantiation).
+// The lane layout (QuadLanes): lik_element.h; the element body of every code: lik_element_body.inc, included in place.  The P elements of a row sit in adjacent groups of
+// one wave, so rows_out is a fixed-order shuffle loop; one partial of sum VE and one of sum dVE/dtheta per block.
 template <int LIK>
 __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
   constexpr int LPE = quad_lpe(LIK);
-  constexpr int NPL = GH_N / 4;      // nodes per lane (quadrature branches)
-  constexpr int NODE_UNROLL = LIK == GPK_LIK_BETA_PROBIT ? 1 : NPL;
   __shared__ double sh[4];
   const LatentMoments& m = a.m;
   const QuadLanes<LPE> L(m);
@@ -175,103 +108,7 @@ __global__ __launch_bounds__(RB) void lik_varexp_kernel(LikVarexpArgs a) {
     const bool act = L.load(m, u, p, b, y, mu, fv);
     double ynan = y - y;
     double ve, dmu, dvar, dsc = 0.0;
-    if (LIK == GPK_LIK_POISSON_EXP) {
-      // scalar_discrete.py: Poisson.variational_expectations with the exp link, closed form
-      const double e = exp(mu + 0.5 * fv) * a.par0;
-      ve = y * mu - e - lgamma(y + 1.0) + y * a.c0;
-      dmu = y - e;
-      dvar = -0.5 * e;
-    } else if (LIK == GPK_LIK_EXPONENTIAL_EXP) {
-      // scalar_continuous.py: Exponential.variational_expectations with the exp link, closed form
-      const double ye = y * exp(0.5 * fv - mu);
-      ve = -mu - ye;
-      dmu = ye - 1.0;
-      dvar = -0.5 * ye;
-    } else if (LIK == GPK_LIK_GAMMA_EXP) {
-      // scalar_continuous.py: Gamma.variational_expectations with the exp link, closed form; log y as it comes (no clamp)
-      const double ye = y * exp(0.5 * fv - mu);
-      const double ly = log(y);
-      ve = -a.par0 * mu - a.c0 + (a.par0 - 1.0) * ly - ye;
-      dmu = ye - a.par0;
-      dvar = -0.5 * ye;
-      dsc = ly - mu - a.par1;
-    } else {
-      const double sd = sqrt(2.0 * fv);
-      const double sgn = (y == 1.0) ? 1.0 : -1.0;
-      // Beta: the clipped label's two logarithms, once per element (comparisons: a NaN label stays NaN)
-      const double yc = y < 1e-6 ? 1e-6 : (y > 1.0 - 1e-6 ? 1.0 - 1e-6 : y);
-      const double ly = LIK == GPK_LIK_BETA_PROBIT ? log(yc) : 0.0, l1y = LIK == GPK_LIK_BETA_PROBIT ? log(1.0 - yc) : 0.0;
-      // Ordinal: the two edges of the label's bin, picked by comparison (the table is a kernel argument: no indexed copy of it);
-      // has_l / has_r: the edge is finite, i.e. not the open end of the first or last bin
-      double el = 0.0, er = 0.0;
-      bool has_l = false, has_r = false;
-      if (LIK == GPK_LIK_ORDINAL) {
-        const bool lab_ok = y >= 0.0 && y <= (double)a.nedge && y == floor(y);   // (false for NaN and +-Inf)
-        const int yi = lab_ok ? (int)y : 0;
-        ynan = lab_ok ? 0.0 : __builtin_nan("");
-        has_l = yi < a.nedge; has_r = yi > 0;
-#pragma unroll
-        for (int i = 0; i < GPK_ORDINAL_MAXEDGE; ++i) {
-          el = i == yi ? a.edge[i] : el;
-          er = i == yi - 1 ? a.edge[i] : er;
-        }
-      }
-      double sv = 0.0, sm = 0.0, sx = 0.0, ss = 0.0;
-#pragma unroll NODE_UNROLL
-      for (int j = 0; j < NPL; ++j) {
-        const double x = gh_x_dev[k * NPL + j];
-        const double wn = gh_w_dev[k * NPL + j] * 0.5641895835477563;   // w_h / sqrt(pi)
-        const double f = fma(sd, x, mu);
-        double gv, gp;
-        if (LIK == GPK_LIK_BERNOULLI_PROBIT) {
-          // log(y == 1 ? p : 1 - p), p = inv_probit(f) = 0.5 (1 + erf(f / sqrt 2)) (1 - 2e-3) + 1e-3;  1 - p = inv_probit(-f), taken
-          // through erfc so that the small side keeps its relative accuracy
-          const double q = 0.5 * erfc(-sgn * f * 0.7071067811865476) * (1.0 - 2e-3) + 1e-3;
-          gv = log(q);
-          gp = sgn * ((1.0 - 2e-3) * 0.3989422804014327) * exp(-0.5 * f * f) / q;
-        } else if (LIK == GPK_LIK_BETA_PROBIT) {
-          // logdensities.py beta with alpha = m scale, beta = scale - alpha, m = inv_probit(f)
-          const double mm = 0.5 * erfc(-f * 0.7071067811865476) * (1.0 - 2e-3) + 1e-3;
-          const double al = mm * a.par0, be = a.par0 - al;
-          const double pa = gpk_digamma(al), pb = gpk_digamma(be);
-          gv = (al - 1.0) * ly + (be - 1.0) * l1y + a.c0 - lgamma(al) - lgamma(be);
-          gp = a.par0 * ((1.0 - 2e-3) * 0.3989422804014327) * exp(-0.5 * f * f) * (ly - l1y - pa + pb);
-          ss += wn * (mm * ly + (1.0 - mm) * l1y + a.par1 - mm * pa - (1.0 - mm) * pb);
-        } else if (LIK == GPK_LIK_ORDINAL) {
-          // scalar_discrete.py Ordinal: log(inv_probit(zl) - inv_probit(zr) + 1e-6); the open end of a bin is +-Inf in z (erfc gives
-          // exactly 0 or 2 there) and has no density term.  The difference of the two Phi through erfc on the side where both are small.
-          const double zl = has_l ? (el - f) / a.par0 : __builtin_inf();
-          const double zr = has_r ? (er - f) / a.par0 : -__builtin_inf();
-          const bool right = zr >= 0.0;
-          const double za = right ? zr : -zl, zb = right ? zl : -zr;
-          const double D = (1.0 - 2e-3) * (0.5 * (erfc(za * 0.7071067811865476) - erfc(zb * 0.7071067811865476)));
-          const double pl = has_l ? 0.3989422804014327 * exp(-0.5 * zl * zl) : 0.0;
-          const double pr = has_r ? 0.3989422804014327 * exp(-0.5 * zr * zr) : 0.0;
-          const double den = a.par0 * (D + 1e-6);
-          gv = log(D + 1e-6);
-          gp = -(1.0 - 2e-3) * (pl - pr) / den;
-          ss += wn * (-(1.0 - 2e-3) * ((has_l ? zl * pl : 0.0) - (has_r ? zr * pr : 0.0)) / den);
-        } else {
-          // logdensities.py student_t:  c0 - (df + 1) / 2 log(1 + ((y - f) / scale)^2 / df)
-          const double r = (y - f) / a.par0;
-          const double den = a.par1 + r * r;
-          gv = a.c0 - 0.5 * (a.par1 + 1.0) * log1p(r * r / a.par1);
-          gp = (a.par1 + 1.0) * r / (a.par0 * den);
-          ss += wn * (((a.par1 + 1.0) * r * r / den - 1.0) / a.par0);
-        }
-        sv += wn * gv;
-        sm += wn * gp;
-        sx += wn * gp * x;
-      }
-      sv += __shfl_xor(sv, 1); sm += __shfl_xor(sm, 1); sx += __shfl_xor(sx, 1); ss += __shfl_xor(ss, 1);
-      sv += __shfl_xor(sv, 2); sm += __shfl_xor(sm, 2); sx += __shfl_xor(sx, 2); ss += __shfl_xor(ss, 2);
-      ve = sv;
-      dmu = sm;
-      dvar = sx / sd;
-      dsc = ss;
-    }
-    ve += ynan; dmu += ynan; dvar += ynan;
-    if (LIK == GPK_LIK_ORDINAL) dsc += ynan;
+#include "lik_element_body.inc"
     double rs = 0.0;   // the row's P elements sit in adjacent groups of this wave: summed in the order p = 0, 1, ...
     for (int q = 0; q < m.P; ++q) rs += __shfl(ve, (L.row_lane0 + q * LPE) & 63);
     if (act && k == 0) {
@@ -628,6 +465,12 @@ int lik_plan(int lik, const double* q, int P, LikPlan* o) {
 int gpk_likelihood_check(int lik, const double* params, int P) {
   LikPlan plan;
   return lik_plan(lik, params, P, &plan);
+}
+int gpk_likelihood_constants(int lik, const double* params, int P, double* par0, double* par1, double* c0) {
+  LikPlan plan;
+  GPK_TRY(lik_plan(lik, params, P, &plan));
+  *par0 = plan.par0; *par1 = plan.par1; *c0 = plan.c0;
+  return 0;
 }
 
 int gpk_launch_likelihood_varexp_stage1(hipStream_t s, int lik, const double* params, const LatentMoments& m, double* rows_out,

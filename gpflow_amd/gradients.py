@@ -1053,9 +1053,7 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     fwd = _svgp_forward(spec, Z, Xb, q_mu, q_sqrt, jitter)
     s0, fmean, ssq = fwd.s0, fwd.fmean, fwd.ssq
     if likelihood is not None:
-        lik_out, _, dmu, dvar, _ = ops.likelihood_varexp_sum(Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], lik=likelihood[0],
-                                                             params=likelihood[1], mean_const=mean_const, want_grads=True)
-        ve = lik_out[0:1]
+        ve, dmu, dvar, lik_grads = _likelihood_stage(likelihood, Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], mean_const=mean_const)
     else:
         knn, s0_knn, kd = _knn_terms(spec, Xb, s0)
         ve, _ = ops.gaussian_varexp_sum(Yb, fmean, s0=s0_knn, ssq=ssq, knn=knn, noise_variance=noise_variance,
@@ -1072,11 +1070,24 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
         grads["noise_variance"] = seed.noise_grad(ve, s0, ssq, kd)
     grads.update({"Z": Zbar, "q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": seed.r.sum().reshape(1)})
     if likelihood is not None:
-        from .likelihoods import device_grad_param
-        name = device_grad_param(likelihood[0])   # (the one Parameter whose derivative the kernel returns as out[1])
-        if name is not None:
-            grads["likelihood_" + name] = lik_out[1:2] * scale
+        grads.update({name: g * scale for name, g in lik_grads.items()})
     return F, grads, fwd.info
+
+
+def _likelihood_stage(likelihood, Y, fmean, *, s0, ssq, knn, mean_const):
+    """The variational-expectation stage of a reverse pass for likelihood = (name, params): (sum VE [1], dmu, dvar [rows, P], {grad
+    name: dVE/dparameter [1]}).  A name of ops.LIKELIHOOD_CODES is one ops.likelihood_varexp_sum call, and its gradient -- where the
+    likelihood class names a `device_grad_param` -- is "likelihood_<that name>".  "switched": params is the member table of
+    ops.switched_varexp_sum, the task label is the last column of Y, and the gradients are "likelihood_<t>", one per task."""
+    if likelihood[0] == "switched":
+        out, _, dmu, dvar, _ = ops.switched_varexp_sum(Y, fmean, s0=s0, ssq=ssq, knn=knn, members=likelihood[1], mean_const=mean_const,
+                                                       want_grads=True)
+        return out[0:1], dmu, dvar, {f"likelihood_{t}": out[1 + t:2 + t] for t in range(len(likelihood[1]))}
+    out, _, dmu, dvar, _ = ops.likelihood_varexp_sum(Y, fmean, s0=s0, ssq=ssq, knn=knn, lik=likelihood[0], params=likelihood[1],
+                                                     mean_const=mean_const, want_grads=True)
+    from .likelihoods import device_grad_param
+    name = device_grad_param(likelihood[0])   # (the one Parameter whose derivative the kernel returns as out[1])
+    return out[0:1], dmu, dvar, ({} if name is None else {"likelihood_" + name: out[1:2]})
 
 
 class _SvgpForward:
@@ -1494,9 +1505,7 @@ def vgp_elbo_and_grad(X: torch.Tensor, Y: torch.Tensor, q_mu: torch.Tensor, q_sq
     ssq, _ = ops.tril_product(L, q_sqrt)                                                # [R, N]
     fmean = ops.row_stats(L, V=q_mu, want_sumsq=False)[1]                               # L q_mu  [N, R] (one pass over L)
     if likelihood is not None:
-        lik_out, _, dmu, dvar, _ = ops.likelihood_varexp_sum(Y, fmean, s0=None, ssq=ssq, knn=[0.0], lik=likelihood[0],
-                                                             params=likelihood[1], mean_const=mean_const, want_grads=True)
-        ve = lik_out[0:1]
+        ve, dmu, dvar, lik_grads = _likelihood_stage(likelihood, Y, fmean, s0=None, ssq=ssq, knn=[0.0], mean_const=mean_const)
     else:
         ve, _ = ops.gaussian_varexp_sum(Y, fmean, s0=None, ssq=ssq, knn=[0.0], noise_variance=noise_variance, mean_const=mean_const)
     kl = ops.gauss_kl_white(q_mu, q_sqrt)
@@ -1528,8 +1537,5 @@ def vgp_elbo_and_grad(X: torch.Tensor, Y: torch.Tensor, q_mu: torch.Tensor, q_sq
         grads["noise_variance"] = seed.noise_grad(ve, None, ssq, 0.0)
     grads.update({"q_mu": g_qmu, "q_sqrt": g_qs, "mean_const": r.sum().reshape(1)})
     if likelihood is not None:
-        from .likelihoods import device_grad_param
-        name = device_grad_param(likelihood[0])   # (the one Parameter whose derivative the kernel returns as out[1])
-        if name is not None:
-            grads["likelihood_" + name] = lik_out[1:2].clone()
+        grads.update({name: g.clone() for name, g in lik_grads.items()})
     return F, grads, info

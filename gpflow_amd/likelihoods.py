@@ -584,3 +584,126 @@ class MultiClass(Likelihood):
         Fmu = ops.to_device(Fmu)
         Fm, Fv, Yd = self._flat(Fmu, Fvar, Y)
         return torch.log(self._density(Fm, Fv, Yd[:, :1])).reshape(Fmu.shape[:-1])
+
+
+class SwitchedLikelihood(Likelihood):
+    """SwitchedLikelihood(likelihood_list), likelihoods/misc.py: the last column of Y is a task label and each row is scored by its own
+    task's likelihood; Y[..., :-1] are the values.  The label is read as the Coregion kernel reads one (truncation toward zero, valid
+    inside (-1, T)); a row with an invalid label gives NaN.  Members: `Gaussian` with one `variance` Parameter, or a ScalarLikelihood
+    whose `device_lik` is in ops.SWITCHED_MEMBERS (Bernoulli, Poisson, StudentT, Exponential, Gamma, Beta) -- anything else is refused
+    when the likelihood is built.  `variational_expectations`, the hot one, is ONE launch for all tasks (gpk_switched_varexp_sum); the
+    densities are elementwise device glue over the members' own.  Without Y there is no task: the conditional moments and
+    predict_mean_and_var raise, as in the reference."""
+
+    def __init__(self, likelihood_list):
+        members = list(likelihood_list)
+        if not 1 <= len(members) <= ops.SWITCHED_MAX_TASKS:
+            raise ValueError(f"SwitchedLikelihood: 1 .. {ops.SWITCHED_MAX_TASKS} members, got {len(members)}")
+        for t, lik in enumerate(members):
+            why = self._refusal(lik)
+            if why is not None:
+                raise NotImplementedError(f"SwitchedLikelihood: member {t} ({type(lik).__name__}) {why}")
+        self.likelihoods = members
+
+    @staticmethod
+    def _refusal(lik) -> Optional[str]:
+        """why `lik` cannot be a member, or None"""
+        if isinstance(lik, Gaussian):
+            if lik.is_heteroskedastic:
+                return "has a noise Function: a member's noise is one `variance` Parameter"
+            return None if lik.has_variance_parameter else "holds its noise as `scale=`: a member's noise is one `variance` Parameter"
+        if isinstance(lik, SwitchedLikelihood):
+            return "is itself switched: a row has one task label"
+        if isinstance(lik, MultiClass):
+            return "couples the latents of a row: the per-row choice is between scalar likelihoods"
+        if isinstance(lik, Ordinal):
+            return "needs an edge table per task, which the switched stage's table of three constants per task does not hold"
+        if isinstance(lik, ScalarLikelihood) and lik.device_lik in ops.SWITCHED_MEMBERS:
+            return None
+        return "has no body in the switched variational-expectation stage (ops.SWITCHED_MEMBERS)"
+
+    @property
+    def num_tasks(self) -> int:
+        return len(self.likelihoods)
+
+    def device_members(self) -> tuple:
+        """the (name, params) table of ops.switched_varexp_sum at the current parameter values"""
+        return tuple(("gaussian", (lik.noise_variance(),)) if isinstance(lik, Gaussian) else (lik.device_lik, lik.device_params())
+                     for lik in self.likelihoods)
+
+    def device_grad_params(self) -> list:
+        """per task, the member's Parameter that out[1 + t] of the stage differentiates, or None"""
+        return [lik.variance if isinstance(lik, Gaussian) else
+                (getattr(lik, lik.device_grad_param) if lik.device_grad_param else None) for lik in self.likelihoods]
+
+    def _tasks(self, Y):
+        """(values [..., P], task index [..., 1] with 0 in place of an invalid one, 0 | NaN [..., 1]) of Y [..., P + 1]"""
+        Y = ops.to_device(Y)
+        lab = Y[..., -1:]
+        ok = (lab > -1.0) & (lab < float(self.num_tasks))
+        task = torch.where(ok, torch.trunc(lab), torch.zeros_like(lab)).long()
+        return Y[..., :-1], task, torch.where(ok, torch.zeros_like(lab), torch.full_like(lab, float("nan")))
+
+    def _select(self, per_member, task, nan):
+        """per_member[t] where task == t, plus the NaN of an invalid label"""
+        out = per_member[0]
+        for t in range(1, self.num_tasks):
+            out = torch.where(task == t, per_member[t], out)
+        return out + nan
+
+    @staticmethod
+    def _member_log_density(lik, F, Yv, extra_var=None):
+        if isinstance(lik, Gaussian):
+            v = lik.noise_variance()
+            return gaussian(Yv, F, v if extra_var is None else extra_var + v)
+        return lik._log_density(F, Yv)
+
+    def log_prob(self, X, F, Y):
+        F = ops.to_device(F)
+        Yv, task, nan = self._tasks(Y)
+        return self._select([self._member_log_density(lik, F, Yv) for lik in self.likelihoods], task, nan).sum(-1)
+
+    def predict_log_density(self, X, Fmu, Fvar, Y):
+        """log int p(y | f) N(f | mu, v) df per element by the row's own member (Gaussian: closed form; Bernoulli: its closed form;
+        the others: the 20-node log-sum-exp of ScalarLikelihood), summed over the outputs -> [N]"""
+        Fmu, Fvar = ops.to_device(Fmu), ops.to_device(Fvar)
+        Yv, task, nan = self._tasks(Y)
+        per = []
+        for lik in self.likelihoods:
+            if isinstance(lik, Gaussian):
+                per.append(self._member_log_density(lik, Fmu, Yv, extra_var=Fvar))
+            elif isinstance(lik, Bernoulli):
+                per.append(lik._log_density_of_p(lik.predict_mean_and_var(X, Fmu, Fvar)[0], Yv))
+            else:
+                f, wn = lik._points(Fmu, Fvar)
+                per.append(torch.logsumexp(torch.log(wn) + lik._log_density(f, Yv[..., None]), dim=-1))
+        return self._select(per, task, nan).sum(-1)
+
+    def variational_expectations(self, X, Fmu, Fvar, Y) -> torch.Tensor:
+        """misc.py SwitchedLikelihood.variational_expectations -- per-row values [N], summed over the P outputs; the kernel takes at
+        most 16 output columns per call"""
+        Fmu, Fvar, Y = ops.to_device(Fmu), ops.to_device(Fvar), ops.to_device(Y)
+        lead, P = Fmu.shape[:-1], Fmu.shape[-1]
+        if Y.shape[-1] != P + 1:
+            raise ValueError(f"SwitchedLikelihood: Y needs {P} value columns and the task label behind them, got {Y.shape[-1]} columns")
+        Fm, Fv, Yd = Fmu.reshape(-1, P), Fvar.reshape(-1, P), Y.reshape(-1, P + 1)
+        members = self.device_members()
+        total = None
+        for c0 in range(0, P, 16):
+            c1 = min(c0 + 16, P)
+            rows = ops.switched_varexp_sum(Yd[:, c0:], Fm[:, c0:c1].contiguous(), s0=None, ssq=Fv[:, c0:c1].t().contiguous(), knn=[0.0],
+                                           members=members, ylab=P - c0, want_rows=True)[1]
+            total = rows if total is None else total + rows
+        return total.reshape(lead)
+
+    def _needs_task(self, what):
+        raise NotImplementedError(f"SwitchedLikelihood.{what}: without Y there is no task label to choose a member by")
+
+    def predict_mean_and_var(self, X, Fmu, Fvar):
+        self._needs_task("predict_mean_and_var")
+
+    def conditional_mean(self, X, F):
+        self._needs_task("conditional_mean")
+
+    def conditional_variance(self, X, F):
+        self._needs_task("conditional_variance")

@@ -10,7 +10,7 @@ from .. import ops
 from ..base import Module
 from ..config import default_jitter
 from ..kernels import Kernel, MultioutputKernel
-from ..likelihoods import Likelihood
+from ..likelihoods import Likelihood, SwitchedLikelihood
 from ..mean_functions import MeanFunction, Zero
 from ..posteriors import assert_params_false
 
@@ -64,6 +64,8 @@ class GPModel(BayesianModel):
         output_dim = Y.shape[-1]
         if isinstance(kernel, MultioutputKernel):
             return kernel.num_latent_gps
+        if isinstance(likelihood, SwitchedLikelihood):   # (calc_num_latent_gps, model.py:153-170: the last column of Y is the task label)
+            return output_dim - 1
         return output_dim
 
     @abc.abstractmethod

@@ -12,7 +12,7 @@ from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVar
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
 from ..kernels.base import Combination, gradient_spec, has_row_diagonal_leaf, reverse_leaf
 from ..kernels.periodic import Periodic
-from ..likelihoods import Gaussian
+from ..likelihoods import Gaussian, SwitchedLikelihood
 from ..mean_functions import Constant
 
 
@@ -185,7 +185,8 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
     if isinstance(k, LinearCoregionalization):
         return _lcm_routes(model, quadrature=quadrature, narrow=narrow)
     plain = not (quadrature or narrow)
-    lik_ok = (model.whiten and model._device_likelihood()) if quadrature else _gaussian_noise(model.likelihood, not narrow)
+    lik_ok = (model.whiten and (model._device_likelihood() or model._switched_likelihood())) if quadrature \
+        else _gaussian_noise(model.likelihood, not narrow)
     q_full = model.q_sqrt.numpy().ndim == 3
     separate = isinstance(k, SeparateIndependent)
     if separate and plain:
@@ -248,7 +249,7 @@ def vgp_scope(model):
     """The mean constant of a VGP inside its device paths, else NotImplementedError -- checked when the model is BUILT and again by
     every route, before anything touches the device: a single-output kernel, a zero or constant mean, and a Gaussian likelihood with
     one noise variance or a likelihood whose variational expectations the library computes (`device_lik`; at most 16 latents, which
-    for MultiClass are its classes)."""
+    for MultiClass are its classes), or a SwitchedLikelihood with at most 16 latents."""
     from ..kernels import MultioutputKernel
     from .. import ops
     lik, R = model.likelihood, model.q_mu.shape[1]
@@ -258,6 +259,9 @@ def vgp_scope(model):
     if isinstance(lik, Gaussian):
         if lik.is_heteroskedastic:
             raise no("a heteroskedastic Gaussian likelihood is not built into the full variational model (one noise variance)")
+    elif isinstance(lik, SwitchedLikelihood):
+        if R > 16:
+            raise no("a SwitchedLikelihood with more than 16 latents (the columns of one call of its stage)")
     elif getattr(lik, "device_lik", "") not in ops.LIKELIHOOD_CODES:
         raise no(f"the likelihood {type(lik).__name__} has no variational-expectation kernel on the device (`device_lik`)")
     elif hasattr(lik, "check_device_classes"):

@@ -14,7 +14,7 @@ from ..inducing_variables import (InducingPoints, SharedIndependentInducingVaria
 from ..kernels import Kernel
 from ..kernels.base import is_device_leaf
 from ..leaf import latent_keywords
-from ..likelihoods import Gaussian, Likelihood, MultiClass, ScalarLikelihood
+from ..likelihoods import Gaussian, Likelihood, MultiClass, ScalarLikelihood, SwitchedLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
 from .reverse import shared_pair
@@ -86,6 +86,11 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             lik.check_device_classes(self.q_mu.shape[1])   # (ValueError: latents != classes; NotImplementedError: more than 16)
             return True
         return isinstance(lik, ScalarLikelihood) and lik.device_lik in ops.LIKELIHOOD_CODES and self.q_mu.shape[1] <= 16
+
+    def _switched_likelihood(self) -> bool:
+        """a SwitchedLikelihood with at most 16 latents: the composed ELBO and the quadrature reverse pass take it; the fused shard
+        (gpk_svgp_elbo_shard_lik: one code per launch) does not, so `_device_likelihood` stays false for it"""
+        return isinstance(self.likelihood, SwitchedLikelihood) and self.q_mu.shape[1] <= 16
 
     def _fused_separate_config(self):
         """(member kernels, Z [m, d] | [P, m, d], mean constant) when the ELBO shard of a SeparateIndependent model is one
@@ -327,7 +332,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         from .. import gradients
         from . import reverse
         lik = self.likelihood
-        quad = isinstance(lik, (ScalarLikelihood, MultiClass))
+        quad, switched = isinstance(lik, (ScalarLikelihood, MultiClass, SwitchedLikelihood)), isinstance(lik, SwitchedLikelihood)
         routes, c, separate = reverse.svgp_routes(self, quadrature=quad)
         self._check_mixing_widths(data[1])
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])
@@ -336,7 +341,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             return self._elbo_and_grad_lcm(routes, c, X, Y)
         kw = dict(jitter=config.default_jitter(), scale=reverse.minibatch_scale(self.num_data, X.shape[0]), mean_const=c)
         if quad:
-            kw.update(noise_variance=None, likelihood=(lik.device_lik, lik.device_params()))
+            kw.update(noise_variance=None,
+                      likelihood=("switched", lik.device_members()) if switched else (lik.device_lik, lik.device_params()))
         else:
             kw["noise_variance"] = lik.noise_for(X)
         fn = gradients.svgp_elbo_and_grad if self.whiten else gradients.svgp_elbo_and_grad_unwhitened
@@ -363,7 +369,9 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         total = lambda n: sum((h[n] for h in hosts[1:]), hosts[0][n])  # noqa: E731
         q_pairs = [(self.q_mu, np.concatenate([h["q_mu"] for h in hosts], axis=1)),
                    (self.q_sqrt, np.concatenate([h["q_sqrt"] for h in hosts], axis=0))]
-        if quad:
+        if switched:   # (out[1 + t] of the stage: task t's Parameter, a Gaussian member's variance included)
+            lik_pairs = [(par, hosts[0][f"likelihood_{t}"]) for t, par in enumerate(lik.device_grad_params()) if par is not None]
+        elif quad:
             name = getattr(lik, "device_grad_param", None)   # (the Parameter the kernel's out[1] differentiates, if the class has one)
             lik_pairs = [(getattr(lik, name), hosts[0]["likelihood_" + name])] if name else []
         else:

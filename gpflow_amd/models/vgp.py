@@ -10,7 +10,7 @@ from .. import config, ops
 from ..base import Parameter, triangular
 from ..conditionals import conditional
 from ..kernels import Kernel
-from ..likelihoods import Gaussian, Likelihood
+from ..likelihoods import Gaussian, Likelihood, SwitchedLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
 from .training_mixins import InternalDataTrainingLossMixin
@@ -23,7 +23,8 @@ class VGP(GPModel, InternalDataTrainingLossMixin):
     (ops.tril_product).
 
     Scope (reverse.vgp_scope, refused when the model is built): a single-output kernel, a zero or constant mean, a Gaussian likelihood
-    with one noise variance or any likelihood with a `device_lik` (MultiClass: one latent per class, Y one column of labels)."""
+    with one noise variance or any likelihood with a `device_lik` (MultiClass: one latent per class, Y one column of labels), or a
+    SwitchedLikelihood (the last column of Y is the task label; at most 16 latents)."""
 
     def __init__(self, data, kernel: Kernel, likelihood: Likelihood, mean_function: Optional[MeanFunction] = None,
                  num_latent_gps: Optional[int] = None):
@@ -43,8 +44,8 @@ class VGP(GPModel, InternalDataTrainingLossMixin):
 
     @staticmethod
     def calc_num_latent_gps_from_data(data, kernel, likelihood) -> int:
-        """model.py:142-151, with the one case the reference handles in calc_num_latent_gps: a MultiClass likelihood has one latent per
-        class, not per column of Y"""
+        """model.py:142-151, with the cases the reference handles in calc_num_latent_gps: a MultiClass likelihood has one latent per
+        class, not per column of Y; a SwitchedLikelihood one per VALUE column of Y (GPModel's rule: the last column is the task label)"""
         if hasattr(likelihood, "num_classes"):
             return int(likelihood.num_classes)
         return GPModel.calc_num_latent_gps_from_data(data, kernel, likelihood)
@@ -78,13 +79,16 @@ class VGP(GPModel, InternalDataTrainingLossMixin):
         route, c = reverse.vgp_route(self)   # (refused before anything touches the device)
         X, Y = self.data
         _, Xs, _ = route.inputs(None, X)     # active_dims (kernels/base.py:90-109); nothing is differentiated w.r.t. X
-        gaussian = isinstance(lik, Gaussian)
-        kw = dict(noise_variance=lik.noise_variance()) if gaussian else dict(likelihood=(lik.device_lik, lik.device_params()))
+        gaussian, switched = isinstance(lik, Gaussian), isinstance(lik, SwitchedLikelihood)
+        kw = dict(noise_variance=lik.noise_variance()) if gaussian else \
+            dict(likelihood=("switched", lik.device_members()) if switched else (lik.device_lik, lik.device_params()))
         F, g, info = gradients.vgp_elbo_and_grad(Xs, Y, self.q_mu.device_value(), self.q_sqrt.device_value(), kernel_spec=route.spec,
                                                  jitter=config.default_jitter(), mean_const=c, **kw)
         ops.check_info(info)
         if gaussian:
             lik_pairs = reverse.noise_pairs(lik, X, g["noise_variance"])
+        elif switched:   # (out[1 + t] of the stage: task t's Parameter, a Gaussian member's variance included)
+            lik_pairs = [(par, g[f"likelihood_{t}"].cpu().numpy()) for t, par in enumerate(lik.device_grad_params()) if par is not None]
         else:
             name = getattr(lik, "device_grad_param", None)   # (the Parameter the kernel's out[1] differentiates, if the class has one)
             lik_pairs = [(getattr(lik, name), g["likelihood_" + name].cpu().numpy())] if name else []

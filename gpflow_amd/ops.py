@@ -1029,6 +1029,71 @@ def likelihood_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[
     return out, rws, dmu, dvar, fvar
 
 
+# the members of a switched likelihood's table (gpk_switched_varexp_sum): there, and only there, code 0 is a Gaussian with params =
+# (variance,); the others are the scalar codes of LIKELIHOOD_CODES without "ordinal" (an edge table per task)
+SWITCHED_MEMBERS = {"gaussian": 0, **{name: LIKELIHOOD_CODES[name] for name in
+                                      ("bernoulli_probit", "poisson_exp", "student_t", "exponential_exp", "gamma_exp", "beta_probit")}}
+SWITCHED_MAX_TASKS = 16
+
+
+def _switched_table(members):
+    """(T, codes, params [T][2]) as host arrays from a sequence of (name, params): the VALUES are the library's to judge"""
+    members = list(members)
+    if not 1 <= len(members) <= SWITCHED_MAX_TASKS:
+        raise ValueError(f"a switched likelihood takes 1 .. {SWITCHED_MAX_TASKS} members, got {len(members)}")
+    codes, flat = [], []
+    for name, params in members:
+        if name not in SWITCHED_MEMBERS:
+            raise ValueError(f"unknown member {name!r} of a switched likelihood: one of {sorted(SWITCHED_MEMBERS)}")
+        params = [float(v) for v in params]
+        if len(params) != (1 if name == "gaussian" else _LIKELIHOOD_NPAR[name]):
+            raise ValueError(f"switched likelihood member {name!r}: wrong number of parameters ({len(params)})")
+        codes.append(SWITCHED_MEMBERS[name])
+        flat += (params + [0.0, 0.0])[:2]
+    return len(members), (_lib.c_int * len(codes))(*codes), _lib.host_doubles(flat)
+
+
+def switched_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[torch.Tensor], ssq: Optional[torch.Tensor],
+                        knn: Sequence[float], members, ylab: Optional[int] = None, mean_const: float = 0.0,
+                        s0_per_latent: bool = False, want_fvar: bool = False, want_rows: bool = False, want_grads: bool = False):
+    """Variational expectations of a switched likelihood (gpk_switched_varexp_sum): row b is scored by members[t], t the task label in
+    column `ylab` of Y (default: the last), read as the Coregion kernel reads a label; the values are Y[:, :P].  members: a sequence
+    of (name, params), name in SWITCHED_MEMBERS ("gaussian": params = (variance,)).  Returns (out [1 + T], rows | None, dmu | None,
+    dvar | None, fvar | None): out[0] = the sum over rows and outputs, out[1 + t] = its derivative w.r.t. member t's one trainable
+    parameter (Gaussian variance, StudentT scale, Gamma shape, Beta scale; 0 otherwise, and for a task without rows); a row with an
+    invalid label is NaN in rows, dmu, dvar and out[0]."""
+    lib = _lib.load()
+    _chk(Y, "Y", 2)
+    _chk(fmean, "fmean", 2)
+    rows, P = fmean.shape
+    if not fmean.is_contiguous():
+        raise ValueError("fmean must be contiguous")
+    ylab = Y.shape[1] - 1 if ylab is None else int(ylab)
+    if Y.shape[0] != rows or not P <= ylab < Y.shape[1]:
+        raise ValueError("Y must have one row per row of fmean, P value columns and the label column `ylab` behind them")
+    for name, t, shape in (("s0", s0, (P, rows) if s0_per_latent else (rows,)), ("ssq", ssq, (P, rows))):
+        if t is not None:
+            _chk(t, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous {shape}")
+    T, codes, par = _switched_table(members)
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=Y.device)
+    out = new(1 + T)
+    fvar = new(rows, P) if want_fvar else None
+    rws = new(rows) if want_rows else None
+    dmu, dvar = (new(rows, P), new(rows, P)) if want_grads else (None, None)
+    parts = new((1 + T) * int(lib.gpk_switched_varexp_blocks(rows, P)))
+    knn = list(np.atleast_1d(np.asarray(knn, dtype=np.float64)))
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    rc = lib.gpk_switched_varexp_sum(_stream(), T, codes, par, Y.data_ptr(), _rowmajor(Y, "Y"), ylab, fmean.data_ptr(), rows, P,
+                                     ptr(s0), int(s0_per_latent), ptr(ssq), _lib.host_doubles(knn), int(len(knn) > 1),
+                                     float(mean_const), ptr(fvar), ptr(rws), ptr(dmu), ptr(dvar), out.data_ptr(), parts.data_ptr())
+    _lib.check(rc, "gpk_switched_varexp_sum")
+    return out, rws, dmu, dvar, fvar
+
+
 def gauss_kl_white(q_mu: torch.Tensor, q_sqrt: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     _chk(q_mu, "q_mu", 2)

@@ -379,6 +379,39 @@ int gpk_likelihood_varexp_sum(void* stream, int lik, const double* lik_params_ho
                               const double* fmean, int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
                               const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out,
                               double* rows_out, double* dmu_out, double* dvar_out, double* out, void* ws, size_t ws_bytes);
+/* Variational expectations of a SWITCHED likelihood (likelihoods/misc.py SwitchedLikelihood): every row is scored by the likelihood of
+ * its own task, in one launch (csrc/switched/switched_varexp.hip).  Operands not named here behave exactly as they do in
+ * gpk_likelihood_varexp_sum (fmean contiguous [rows,P], s0 / ssq / fvar_out / rows_out / dmu_out / dvar_out optional, knn a HOST pointer).
+ *   Tasks: 1 <= T <= 16 and 1 <= P <= 16, else GPK_E_ARG.  Row b's task is t = label_of(Y[b * ldy + ylab], T), the rule of the
+ *   Coregion kernel (csrc/label.h): truncation toward zero, the test -1 < x < T made on the DOUBLE before any conversion to an integer;
+ *   an invalid label is -1 and never forms an address.  The value columns are Y[b * ldy + p], p < P, so ylab >= P is required, and
+ *   ylab < ldy (GPK_E_ARG otherwise).
+ *   Codes: codes_host[t] is a GPK_LIK_* value of a SCALAR code, or 0.  In this table, and only here, 0 means a Gaussian with
+ *   params = {variance}, variance > 0 (the remark below, "0 is ... no likelihood code", stays true for every other entry point).
+ *   Accepted: 0, 1 (Bernoulli), 2 (Poisson), 3 (StudentT), 8 (Exponential), 9 (Gamma), 10 (Beta).  4 (MultiClass couples a row's
+ *   latents), 11 (Ordinal: an edge table per task) and 5 - 7 answer GPK_E_UNSUPPORTED.  params_host is [T][2] row-major; each member's
+ *   parameters are checked by the code's own rule above (GPK_E_ARG); entries a code does not use are ignored.  A refused call writes
+ *   nothing.
+ *   Elements: the formulas of each code, above.  The Gaussian member, with mu = fmean + mean_const, v = fvar, s2 = its variance:
+ *     VE = -0.5 log 2pi - 0.5 log s2 - 0.5 ((y - mu)^2 + v) / s2,  dmu = (y - mu) / s2,  dvar = -0.5 / s2,
+ *     dVE/ds2 = -0.5 / s2 + 0.5 ((y - mu)^2 + v) / s2^2;  a non-finite label adds y - y to VE, dmu and dvar, as for the scalar codes.
+ *   Outputs: out[0] = sum_b sum_p VE;  out[1 + t] = the sum over the elements of task t's rows of dVE/dtheta_t, theta_t that code's one
+ *   trainable parameter (Gaussian: variance, StudentT: scale, Gamma: shape, Beta: scale), exactly 0 for a code without one and for a
+ *   task with no rows.  rows_out, dmu_out, dvar_out, fvar_out keep their meaning.  rows = 0 writes out = 0 (all 1 + T entries) and
+ *   nothing else.
+ *   An invalid task label (NaN, +-Inf, <= -1, >= T) makes that ROW's outputs NaN -- rows_out[b], its P entries of dmu_out / dvar_out,
+ *   its term of out[0] -- and touches no other row and no out[1 + t] (the row belongs to no task); fvar_out is still the unclamped
+ *   knn - s0 + ssq there.  Non-finite values in Y's value columns, fmean or fvar follow the member code's rule and reach that task's
+ *   out[1 + t] exactly where the rule reaches out[1] of gpk_likelihood_varexp_sum.
+ *   Deterministic: no floating-point atomics, bit-identical on a rerun; each element's dmu, dvar, fvar and each row's rows_out do not
+ *   depend on where the row sits or on which tasks share its wave (the sums out[] depend on the order of the rows).
+ *   Scratch: parts, (1 + T) * gpk_switched_varexp_blocks(rows, P) doubles; its contents at entry do not matter and nothing past that
+ *   extent is touched. */
+int gpk_switched_varexp_blocks(int rows, int P);
+int gpk_switched_varexp_sum(void* stream, int T, const int* codes_host, const double* params_host, const double* Y, long ldy, int ylab,
+                            const double* fmean, int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
+                            const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out, double* rows_out,
+                            double* dmu_out, double* dvar_out, double* out, double* parts);
 /* Gaussian variational expectations of LINEARLY MIXED latents -- the stage between the latent moments and the likelihood of a
  * LinearCoregionalization model (kernels/multioutput/kernels.py LinearCoregionalization, conditionals/util.py mix_latent_gp):
  * L latent GPs g, P outputs f = W g, W [P, L] row-major on the HOST, 1 <= L, P <= 16.  The latent operands are those of
