@@ -113,6 +113,11 @@ _SIGS = {
                                          c_double, c_double, _dp, c_long, _dp, c_long, _dp]),
     "gpk_arccos_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, _dp, c_long, c_int, c_int, C.POINTER(c_double), c_int,
                                         _dp, _dp, _dp, _dp, c_long]),
+    "gpk_changepoint_weights": (c_int, [c_void_p, _dp, c_int, c_long, c_int, C.POINTER(c_double), C.POINTER(c_double), _dp, c_long]),
+    "gpk_changepoint_fold": (c_int, [c_void_p, c_int, _dp, _dp, c_int, c_int, _dp, c_long, _dp, c_long, c_double, _dp, c_long]),
+    "gpk_changepoint_adjoint_stage": (c_int, [c_void_p, _dp, _dp, c_int, c_int, _dp, c_long, _dp, c_long, _dp, c_long, _dp]),
+    "gpk_changepoint_adjoint_tail": (c_int, [c_void_p, _dp, c_int, c_long, c_int, C.POINTER(c_double), C.POINTER(c_double), _dp, c_long,
+                                             c_int, _dp, c_long, _dp, _dp, _dp]),
     "gpk_coregion_output_covariance": (c_int, [c_void_p, _dp, c_long, _dp, c_int, c_int, _dp, c_long]),
     "gpk_coregion_kernel_matrix": (c_int, [c_void_p, _dp, c_int, c_long, _dp, c_int, c_long, _dp, c_long, c_int, c_double, c_int, _dp,
                                            c_long]),

@@ -515,6 +515,31 @@ class PeriodicMember(StationaryMember):
         return {"lengthscales": g[:nls], **{name: g[nls + j:nls + j + 1] for j, name in enumerate(self.leaf.row.extras)}, "period": g[nls + nex:]}
 
 
+class ChangePointsNode:
+    """The host values of one ChangePoints node of a KernelSpec tree (kernels/changepoints.py): `locations` [C] SORTED (a stable
+    argsort of the given ones, `permutation`: sorted[j] = given[permutation[j]]), `steepness` [C] paired with the sorted locations as
+    the reference pairs them (`scalar_steepness`: one value stands for all C), and `switch_dim`, a column of the UNSLICED inputs."""
+
+    def __init__(self, locations, steepness, switch_dim: int = 0):
+        loc = np.asarray(locations, dtype=np.float64).reshape(-1)
+        st = np.asarray(steepness, dtype=np.float64)
+        self.scalar_steepness = st.ndim == 0
+        if not self.scalar_steepness and st.reshape(-1).size != loc.size:
+            raise ValueError(f"ChangePoints: {st.reshape(-1).size} steepness entries for {loc.size} locations")
+        if int(switch_dim) < 0:
+            raise ValueError("ChangePoints: switch_dim must not be negative")
+        if loc.size + 1 > ops.CP_MAX_MEMBERS:
+            raise NotImplementedError(f"ChangePoints: more than {ops.CP_MAX_MEMBERS} member kernels")
+        self.permutation = np.argsort(loc, kind="stable")
+        self.locations = loc[self.permutation]
+        self.steepness = np.broadcast_to(st.reshape(-1) if not self.scalar_steepness else st, (loc.size,)).copy()
+        self.switch_dim = int(switch_dim)
+
+    @property
+    def n_members(self) -> int:
+        return self.locations.size + 1
+
+
 class KernelSpec:
     """What the reverse pass needs to know about the covariance function: ONE kernel leaf, or a Sum / Product of leaves -- flat, or
     nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220
@@ -526,6 +551,12 @@ class KernelSpec:
     only place where the kind of a leaf is asked.  Everything else here is about the TREE: `_build`, `_constant`, `_kd`, `_kd_rows`,
     `_diag_adjoint`, `_dkd` and `_adjoint` are the only walkers, and at a leaf each is one call on the member object.
 
+    A third kind of node, ("cp", [children], k), is a ChangePoints combination (kernels/changepoints.py): K = sum_i (a_i b_i^T) .* K_i
+    with weights from the node's own values `nodes[k]` (a ChangePointsNode).  Every walker dispatches on it first (`_build_cp`,
+    `_adjoint_cp`, the "cp" branches of `_kd_rows` and `_diag_adjoint`; `_constant` is False, `_kd` and `_dkd` raise).  Its gradients
+    (d/dlocations, d/dsteepness) do not fit the per-member lists: `adjoint` / `diag_adjoint` add them up on the spec from `warm()` on,
+    and `kernel_grads` hands them out under "changepoints" and empties the sums.  A spec without such a node issues the calls it issued.
+
     A member's SHAPE gradient -- the `dl` entry of `adjoint` -- is laid out like the leaf's `ls_host`: the lengthscale entries, then the
     extras (a periodic member: then the period); a static member's is empty.  A spec with a dot-product member has no
     `constant_diagonal`: `kdiag()` / `dkdiag()` raise, `kdiag_rows(X)` and `diag_adjoint(X, kd_bar)` take their place.
@@ -535,10 +566,13 @@ class KernelSpec:
       adjoint  member i sees  Kbar (Sum)  or  Kbar .* prod_{j != i} k_j  (Product: formed by the same in-place combine pass);
                the input gradients of the members are scattered back into the columns each read, and add up."""
 
-    def __init__(self, members, op=None, cols=None, periods=None):
+    def __init__(self, members, op=None, cols=None, periods=None, nodes=None):
         """members: leaves or tuples, see the class; cols[i]: the input columns member i sees (its `active_dims` as an index
         list, kernels/base.py:90-109) or None for all of them; periods[i]: None, or the period (0-d or [D_i]) of a Periodic member,
-        whose leaf is then in the device form (PeriodicMember)."""
+        whose leaf is then in the device form (PeriodicMember); nodes[k]: the values of the tree's ChangePoints node
+        ("cp", [children], k) -- a ChangePointsNode, the one kind of node with parameters of its own."""
+        self.nodes = list(nodes or [])
+        self._node_grads = None
         self.members = [m if isinstance(m, (Leaf, DotLeaf, ArcLeaf, CoregionLeaf)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
@@ -547,9 +581,12 @@ class KernelSpec:
         n = len(self.members)
         if op in ("add", "mul"):
             op = (op, list(range(n)))
-        elif n > 1 and not isinstance(op, (tuple, list)):
+        elif (n > 1 or nodes) and not isinstance(op, (tuple, list)):
             raise ValueError("a kernel combination needs op 'add' or 'mul'")
-        self.tree = 0 if n == 1 else self._check_tree(op, n)
+        self.tree = 0 if n == 1 and not self.nodes else self._check_tree(op, n)
+        for nd in self._cp_nodes(self.tree):
+            if nd[2] >= len(self.nodes) or len(nd[1]) != self.nodes[nd[2]].n_members:
+                raise ValueError("a ChangePoints node has one child per regime: len(locations) + 1")
         cols = [None] * len(self.members) if cols is None else list(cols)
         if len(cols) != len(self.members):
             raise ValueError("one column selection per member")
@@ -574,7 +611,7 @@ class KernelSpec:
     @property
     def packable(self) -> bool:
         """one member whose two adjoints fit the packed tail of `_covariance_tail` ([variance, lengthscales] and A_bar in one launch)"""
-        return self.n == 1 and self.cols[0] is None and self.periods[0] is None and self.members[0].is_plain
+        return self.n == 1 and not self.nodes and self.cols[0] is None and self.periods[0] is None and self.members[0].is_plain
 
     @staticmethod
     def _check_tree(node, n):
@@ -584,13 +621,22 @@ class KernelSpec:
             if isinstance(nd, (int, np.integer)):
                 seen.append(int(nd))
                 return int(nd)
+            if len(nd) == 3 and nd[0] == "cp":     # ("cp", [children], node index): one child per regime
+                _, ch, k = nd
+                if not isinstance(k, (int, np.integer)) or k in seen_nodes or len(ch) < 1:
+                    raise ValueError("a ChangePoints node is ('cp', [children], index of its values in `nodes`)")
+                seen_nodes.append(int(k))
+                return ("cp", [walk(c) for c in ch], int(k))
             op, ch = nd
             if op not in ("add", "mul") or len(ch) < 1:
                 raise ValueError("a combination node is ('add' | 'mul', [children])")
             return (op, [walk(c) for c in ch])
+        seen_nodes = []
         out = walk(node)
         if sorted(seen) != list(range(n)):
             raise ValueError("every member must appear exactly once in the combination tree")
+        if sorted(seen_nodes) != list(range(len(seen_nodes))):
+            raise ValueError("the ChangePoints nodes of the tree are numbered 0 .. in `nodes`")
         return out
 
     @property
@@ -611,6 +657,8 @@ class KernelSpec:
     def _build(self, node, X1, X2, out, diag_add=0.0):
         if isinstance(node, int):
             return self.parts[node].build(X1, X2, out, diag_add)
+        if node[0] == "cp":
+            return self._build_cp(node, X1, X2, out, diag_add)
         op, ch = node
         if len(ch) == 1:
             return self._build(ch[0], X1, X2, out, diag_add)
@@ -626,9 +674,41 @@ class KernelSpec:
             out.diagonal().add_(float(diag_add))
         return out
 
+    @classmethod
+    def _cp_nodes(cls, node):
+        """the ChangePoints nodes under `node`, in traversal order"""
+        if isinstance(node, int):
+            return []
+        return ([node] if node[0] == "cp" else []) + [nd for c in node[1] for nd in cls._cp_nodes(c)]
+
+    def _cp_weights(self, k: int, X):
+        """A [T, rows] of node k over the switch column of the UNSLICED inputs"""
+        nd = self.nodes[k]
+        if nd.switch_dim >= X.shape[1]:
+            raise ValueError(f"ChangePoints: switch_dim {nd.switch_dim} is outside the {X.shape[1]} input columns")
+        return ops.changepoint_weights(X[:, nd.switch_dim], locations=nd.locations, steepness=nd.steepness)
+
+    def _build_cp(self, node, X1, X2, out, diag_add=0.0):
+        """the first child is built into `out` and weighted in place (op 0); every further child is built once into ONE reused
+        temporary and folded in (op 1: one read of each, one write of `out`); diag_add rides in the LAST fold"""
+        _, ch, k = node
+        A = self._cp_weights(k, X1)
+        B = None if X2 is None else self._cp_weights(k, X2)
+        last = len(ch) - 1
+        out = self._build(ch[0], X1, X2, out)
+        ops.changepoint_fold(A[0], None if B is None else B[0], out, diag_add=diag_add if last == 0 else 0.0, out=out)
+        tmp = None
+        for j, c in enumerate(ch[1:], start=1):
+            tmp = self._build(c, X1, X2, tmp)
+            ops.changepoint_fold(A[j], None if B is None else B[j], tmp, out, diag_add=diag_add if j == last else 0.0, out=out)
+        return out
+
     def _constant(self, node) -> bool:
-        """every member under `node` has a constant diagonal: the node's diagonal is one host value"""
-        return self.parts[node].constant_diagonal if isinstance(node, int) else all(self._constant(c) for c in node[1])
+        """every member under `node` has a constant diagonal: the node's diagonal is one host value (never under a ChangePoints node:
+        its weights depend on the row)"""
+        if isinstance(node, int):
+            return self.parts[node].constant_diagonal
+        return node[0] != "cp" and all(self._constant(c) for c in node[1])
 
     @property
     def constant_diagonal(self) -> bool:
@@ -639,6 +719,9 @@ class KernelSpec:
     def _kd(self, node) -> float:
         if isinstance(node, int):
             return self.parts[node].kdiag()
+        if node[0] == "cp":
+            raise NotImplementedError("K(x, x) of a ChangePoints node depends on the row: this caller takes the diagonal for one scalar "
+                                      "and has not been converted to KernelSpec.kdiag_rows")
         vals = [self._kd(c) for c in node[1]]
         return float(np.prod(vals)) if node[0] == "mul" else float(np.sum(vals))
 
@@ -651,6 +734,12 @@ class KernelSpec:
             return self._kd(node)
         if isinstance(node, int):
             return self.parts[node].kdiag_rows(X)
+        if node[0] == "cp":     # sum_i a_i^2 kd_i, the weight formed first as the fold forms it: the diagonal of the built matrix
+            A, acc = self._cp_weights(node[2], X), None
+            for i, c in enumerate(node[1]):
+                term = (A[i] * A[i]) * self._kd_rows(c, X)
+                acc = term if acc is None else acc + term
+            return acc
         op, ch = node
         rows = [c for c in ch if not self._constant(c)]
         acc = self._kd_rows(rows[0], X)
@@ -682,6 +771,17 @@ class KernelSpec:
         if isinstance(node, int):
             acc["dv"][node], acc["dl"][node] = self.parts[node].diag_adjoint(X, bar)
             return
+        if node[0] == "cp":     # child i sees bar .* a_i^2; the weights see 2 a_i kd_i bar, and one tail turns them into the node's gradients
+            _, ch, k = node
+            A = self._cp_weights(k, X)
+            init = torch.empty_like(A)
+            for i, c in enumerate(ch):
+                init[i] = (2.0 * A[i]) * self._kd_rows(c, X) * bar
+                self._diag_adjoint(c, X, bar * (A[i] * A[i]), acc)
+            nd = self.nodes[k]
+            dl, ds, _ = ops.changepoint_adjoint_tail(X[:, nd.switch_dim], locations=nd.locations, steepness=nd.steepness, init=init)
+            self._add_node_grads(k, dl, ds)
+            return
         op, ch = node
         for jc, c in enumerate(ch):
             b = bar
@@ -695,6 +795,8 @@ class KernelSpec:
     def _dkd(self, node) -> dict:
         if isinstance(node, int):
             return {node: 1.0}
+        if node[0] == "cp":
+            raise NotImplementedError("K(x, x) of a ChangePoints node depends on the row: KernelSpec.diag_adjoint takes the place of dkdiag")
         op, ch = node
         kd = self._kd(node)
         out = {}
@@ -712,7 +814,15 @@ class KernelSpec:
         """device copies of the members' lengthscales, made now (see `ls_device`)"""
         for m in self.parts:
             m.warm(device, D)
+        self._node_grads = None     # a gradient evaluation begins: what `adjoint` / `diag_adjoint` add up for the nodes starts empty
         return self
+
+    def _add_node_grads(self, k: int, dl, ds) -> None:
+        """d/dlocations (sorted order) and d/dsteepness (per change point) of node k from one tail, added to what this evaluation has"""
+        if self._node_grads is None:
+            self._node_grads = [None] * len(self.nodes)
+        have = self._node_grads[k]
+        self._node_grads[k] = (dl, ds) if have is None else (have[0] + dl, have[1] + ds)
 
     def adjoint(self, A, Bm, Kbar, symmetric: bool):
         """([d/dvariance_i [1]], [shape gradient_i: d/dlengthscales_i, then d/dalpha_i], A_bar [n1, D]) given Kbar, members in index
@@ -737,6 +847,8 @@ class KernelSpec:
                 else:
                     acc["Abar"].index_add_(1, m.index(A.device), Ab)
             return
+        if node[0] == "cp":
+            return self._adjoint_cp(node, A, Bm, Kbar, symmetric, acc)
         op, ch = node
         for jc, c in enumerate(ch):
             Kb = Kbar
@@ -750,6 +862,32 @@ class KernelSpec:
                     else:
                         Kb.mul_(self._build(o, A, None if symmetric else Bm, None))
             self._adjoint(c, A, Bm, Kb, symmetric, acc)
+
+    def _adjoint_cp(self, node, A, Bm, Kbar, symmetric, acc):
+        """K = sum_i (a_i b_i^T) .* K_i.  Per child: K_i built into ONE reused temporary, ONE stage call that overwrites it with the
+        child's seed G = Kbar .* (a_i b_i^T) and leaves the tile partials of the weight adjoints, the child's own adjoint with G.  After
+        the last child one tail per argument: the node's d/dlocations, d/dsteepness, and the gradient of the switch column, which is
+        added into A_bar (symmetric: both arguments)."""
+        _, ch, k = node
+        nd = self.nodes[k]
+        B2 = None if symmetric else Bm
+        Kbar = Kbar if Kbar.is_contiguous() else Kbar.contiguous()
+        W1 = self._cp_weights(k, A)
+        W2 = None if symmetric else self._cp_weights(k, Bm)
+        n1, n2 = Kbar.shape
+        parts = ops.changepoint_adjoint_parts(len(ch), n1, n2, A.device)
+        tmp = None
+        for i, c in enumerate(ch):
+            tmp = self._build(c, A, B2, tmp)
+            G = ops.changepoint_adjoint_stage(W1[i], None if symmetric else W2[i], Kbar, tmp, parts[i], out=tmp)
+            self._adjoint(c, A, Bm, G, symmetric, acc)
+        kw = dict(locations=nd.locations, steepness=nd.steepness, parts=parts)
+        dl, ds, xbar = ops.changepoint_adjoint_tail(A[:, nd.switch_dim], n_other=n2, columns=False, **kw)
+        dl2, ds2, xbar2 = ops.changepoint_adjoint_tail((A if symmetric else Bm)[:, nd.switch_dim], n_other=n1, columns=True, **kw)
+        self._add_node_grads(k, dl + dl2, ds + ds2)
+        if acc["Abar"] is None:
+            acc["Abar"] = torch.zeros_like(A)
+        acc["Abar"][:, nd.switch_dim] += (xbar + xbar2) if symmetric else xbar
 
     def pack(self, dvs, dls):
         """gradient entries: one member -> ("variance" [1], "lengthscales" [D or 1]) as before; several -> "variance" [n] and
@@ -775,9 +913,29 @@ class KernelSpec:
         and -- only when a member has one -- "alpha" and "period": one tensor for one member, else a list with None for the members
         without"""
         if self.n == 1:
-            return {"variance": g_var, **self.split_shape(0, g_shape)}
+            return {"variance": g_var, **self.split_shape(0, g_shape), **self._changepoint_grads()}
         split = [self.split_shape(i, g) for i, g in enumerate(g_shape)]
-        return {"variance": g_var, **{name: [p.get(name) for p in split] for name in dict.fromkeys(k for p in split for k in p)}}
+        return {"variance": g_var, **{name: [p.get(name) for p in split] for name in dict.fromkeys(k for p in split for k in p)},
+                **self._changepoint_grads()}
+
+    def _changepoint_grads(self) -> dict:
+        """{"changepoints": [{"locations": [C], "steepness": [C or 1]}, ...]}, one entry per ChangePoints node in node order -- the
+        locations' gradient back in the GIVEN order (through the sort's permutation), a scalar steepness collecting the sum; what the
+        `adjoint` / `diag_adjoint` calls since `warm` added up.  No node: no key."""
+        if not self.nodes:
+            return {}
+        out = []
+        for k, nd in enumerate(self.nodes):
+            have = None if self._node_grads is None else self._node_grads[k]
+            C = nd.locations.size
+            dl = have[0] if have is not None else torch.zeros(C, dtype=torch.float64)
+            ds = have[1] if have is not None else torch.zeros(C, dtype=torch.float64)
+            given = torch.zeros_like(dl)
+            if C:
+                given[torch.as_tensor(nd.permutation, device=dl.device)] = dl
+            out.append({"locations": given, "steepness": ds.sum().reshape(1) if nd.scalar_steepness else ds})
+        self._node_grads = None
+        return {"changepoints": out}
 
 
 class _Seed:

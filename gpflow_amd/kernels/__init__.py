@@ -8,10 +8,11 @@ from .statics import Static, White, Constant, Bias
 from .periodic import Periodic
 from .linears import Linear, Polynomial
 from .misc import ArcCosine, Coregion
+from .changepoints import ChangePoints
 from .multioutput import MultioutputKernel, SharedIndependent, SeparateIndependent, LinearCoregionalization
 
 RBF = SquaredExponential  # gpflow/kernels/__init__.py:50
 
 __all__ = ["Kernel", "Combination", "Sum", "Product", "Stationary", "IsotropicStationary", "SquaredExponential", "RBF", "Matern12",
-           "Matern32", "Matern52", "Exponential", "RationalQuadratic", "Static", "White", "Constant", "Bias", "Periodic", "Linear", "Polynomial", "ArcCosine", "Coregion", "MultioutputKernel", "SharedIndependent", "SeparateIndependent",
+           "Matern32", "Matern52", "Exponential", "RationalQuadratic", "Static", "White", "Constant", "Bias", "Periodic", "Linear", "Polynomial", "ArcCosine", "Coregion", "ChangePoints", "MultioutputKernel", "SharedIndependent", "SeparateIndependent",
            "LinearCoregionalization"]

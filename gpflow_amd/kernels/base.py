@@ -151,7 +151,7 @@ class Combination(Kernel):
     """A list of kernels reduced elementwise (gpflow/kernels/base.py:223-329); nested instances of the same class are
     flattened (:247-255).  Every member slices its own active_dims, so the combination itself never slices."""
 
-    _op = None  # "add" | "mul"
+    _op = None  # "add" | "mul"; "cp": kernels/changepoints.py, which overrides every method here that reads it
 
     def __init__(self, kernels: Sequence[Kernel], name: Optional[str] = None):
         super().__init__(name=name)
@@ -247,9 +247,13 @@ def gradient_spec(kernel, input_dim=None):
     if not isinstance(kernel, Combination):
         return None
     # leaves in traversal order (with what reverse_leaf says of each) + the tree over their indices (a flat combination: one node)
-    ks, found = [], []
+    ks, found, nodes = [], [], []
 
     def walk(k):
+        if isinstance(k, Combination) and k._op == "cp":   # ChangePoints: a node with values of its own, numbered as it is met
+            nodes.append(k.node())
+            index = len(nodes) - 1
+            return ("cp", [walk(c) for c in k.kernels], index)
         if isinstance(k, Combination):
             return (k._op, [walk(c) for c in k.kernels])
         found.append(reverse_leaf(k, input_dim))
@@ -270,7 +274,14 @@ def gradient_spec(kernel, input_dim=None):
         else:
             cols.append(np.asarray(k.active_dims, dtype=np.int64))
     leaves, periods, params = zip(*found)     # (a Periodic member: the columns are its base's, the warp is the spec's -- `periods`)
-    return gradients.KernelSpec(leaves, tree, cols=cols, periods=periods), list(params)
+    return gradients.KernelSpec(leaves, tree, cols=cols, periods=periods, nodes=nodes), list(params)
+
+
+def changepoint_nodes(kernel) -> list:
+    """the ChangePoints kernels under `kernel` in the order `gradient_spec` numbers their nodes (each as it is met, before its members)"""
+    if not isinstance(kernel, Combination):
+        return []
+    return ([kernel] if kernel._op == "cp" else []) + [n for c in kernel.kernels for n in changepoint_nodes(c)]
 
 
 class Sum(Combination):

@@ -10,7 +10,7 @@ from .. import gradients
 from ..base import FillTriangular
 from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
-from ..kernels.base import Combination, gradient_spec, has_row_diagonal_leaf, reverse_leaf
+from ..kernels.base import Combination, changepoint_nodes, gradient_spec, has_row_diagonal_leaf, reverse_leaf
 from ..kernels.periodic import Periodic
 from ..likelihoods import Gaussian, SwitchedLikelihood
 from ..mean_functions import Constant
@@ -57,7 +57,7 @@ ROW_DIAGONAL = "a dot-product, ArcCosine or Coregion kernel or member (Linear, P
 def has_row_diagonal(k) -> bool:
     """a dot-product kernel (kernels/linears.py) or an ArcCosine or Coregion kernel (kernels/misc.py) anywhere under k -- in a Sum / Product, or
     behind a multi-output wrapper"""
-    if has_row_diagonal_leaf(k):
+    if has_row_diagonal_leaf(k) or getattr(k, "_op", None) == "cp":   # (a ChangePoints: its weights depend on the row)
         return True
     members = [k.kernel] if isinstance(k, SharedIndependent) else getattr(k, "kernels", [])
     return any(has_row_diagonal(m) for m in members)
@@ -77,6 +77,7 @@ class CovarianceRoute:
         self.kernel = kernel
         self._columns_of = kernel.base_kernel if isinstance(kernel, Periodic) else kernel   # whose `slice` selects columns and no more
         self.is_combination = isinstance(kernel, Combination)
+        self.nodes = [k.node_params() for k in changepoint_nodes(kernel)]   # (locations, steepness) per ChangePoints node, in node order
         if self.is_combination:
             self.spec, self.members = gradient_spec(kernel, input_dim)
             return
@@ -118,8 +119,11 @@ class CovarianceRoute:
     def kernel_pairs(self, g):
         """[(Parameter, dF/d constrained as NumPy)] of the members, in member order (the variances come back in one copy)"""
         gv, cut = g["variance"].reshape(-1).cpu().numpy(), self._variance_cuts()
-        return [(par, gv[cut[i]:cut[i + 1]] if j == 0 else gr.cpu().numpy())
-                for i, (pars, grs) in enumerate(zip(self.members, self.member_grads(g))) for j, (par, gr) in enumerate(zip(pars, grs))]
+        pairs = [(par, gv[cut[i]:cut[i + 1]] if j == 0 else gr.cpu().numpy())
+                 for i, (pars, grs) in enumerate(zip(self.members, self.member_grads(g))) for j, (par, gr) in enumerate(zip(pars, grs))]
+        for (loc, steep), gn in zip(self.nodes, g.get("changepoints", [])):   # a ChangePoints node's own Parameters, in node order
+            pairs += [(loc, gn["locations"].cpu().numpy()), (steep, gn["steepness"].cpu().numpy().reshape(steep.numpy().shape))]
+        return pairs
 
 
 def noise_pairs(lik, X, g_noise, reduce=None):

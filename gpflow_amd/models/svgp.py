@@ -359,7 +359,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             Fv += float(F.cpu()[0])
             kernel_pairs += route.kernel_pairs(g)
             # (the kernel's entries went through route.kernel_pairs; in a combination each is a list with one entry per member)
-            kernel_names = {"variance", "lengthscales", "alpha", "period", "offset", "Z"} \
+            kernel_names = {"variance", "lengthscales", "alpha", "period", "offset", "changepoints", "Z"} \
                 | {n for i in range(route.spec.n) for n in route.spec.parameter_names(i)}
             host = {n: g[n].cpu().numpy() for n in g if n not in kernel_names}
             gz = scatter(g["Z"]).cpu().numpy()

@@ -402,6 +402,162 @@ def arccos_adjoint_tail(R: torch.Tensor, A: torch.Tensor, Bm: Optional[torch.Ten
     return small[:1], small[1:1 + nw], small[1 + nw:], Abar
 
 
+# ------------------------------------------------------------------------------------------------ ChangePoints kernel (changepoints/changepoints.hip)
+CP_TILE, CP_MAX_MEMBERS, CP_TAIL_ROWS = 64, 16, 256   # include/gpk.h: GPK_CP_TILE, GPK_CP_MAX_MEMBERS; rows per workgroup of the tail
+
+
+def _cp_points(locations, steepness):
+    """(C, host locations, host steepness) of the gpk_changepoint_* entry points: `locations` [C] SORTED, `steepness` [C] positive"""
+    loc = np.asarray(locations, dtype=np.float64).reshape(-1)
+    st = np.asarray(steepness, dtype=np.float64).reshape(-1)
+    if st.size != loc.size:
+        raise ValueError(f"changepoints: {loc.size} locations and {st.size} steepness entries")
+    if loc.size + 1 > CP_MAX_MEMBERS:
+        raise NotImplementedError(f"changepoints: more than {CP_MAX_MEMBERS} member kernels")
+    return int(loc.size), _lib.host_doubles(loc.tolist() or [0.0]), _lib.host_doubles(st.tolist() or [1.0])
+
+
+def _cp_column(x, name: str):
+    """(pointer, rows, stride) of a switch column: an [n] or [n, 1] view, e.g. X[:, switch_dim] of a row-major X"""
+    _chk(x, name)
+    if x.dim() == 2 and x.shape[1] == 1:
+        x = x[:, 0]
+    if x.dim() != 1:
+        raise ValueError(f"{name}: the switch column is [n] (a view such as X[:, switch_dim])")
+    n = x.shape[0]
+    ld = int(x.stride(0)) if n > 1 else 1
+    if ld < 1:
+        raise ValueError(f"{name}: the switch column needs a positive stride")
+    return x.data_ptr(), n, ld
+
+
+def _cp_vector(v, n: int, name: str):
+    _chk(v, name, 1)
+    if v.shape[0] != n or not v.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [{n}]")
+    return v.data_ptr()
+
+
+def changepoint_weights(x: torch.Tensor, *, locations, steepness, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A [T, n], T = len(locations) + 1: row i holds a_i(x_r) = sig_{i-1}(x_r) (1 - sig_i(x_r)) over the switch column x (include/gpk.h,
+    "ChangePoints kernel"): saturated sigmoids are exactly 0 or 1, a NaN / Inf in x makes that row's weights NaN."""
+    lib = _lib.load()
+    C, loc, st = _cp_points(locations, steepness)
+    px, n, ldx = _cp_column(x, "x")
+    if out is None:
+        out = torch.empty((C + 1, n), dtype=torch.float64, device=x.device)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (C + 1, n):
+        raise ValueError(f"changepoint_weights: out must be [{C + 1}, {n}]")
+    if n == 0:
+        return out
+    _lib.check(lib.gpk_changepoint_weights(_stream(), px, n, ldx, C, loc, st, out.data_ptr(), _rowmajor(out, "out")), "gpk_changepoint_weights")
+    return out
+
+
+def changepoint_fold(a: torch.Tensor, b: Optional[torch.Tensor], Ki: torch.Tensor, acc: Optional[torch.Tensor] = None, *,
+                     diag_add: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = (a b^T) .* Ki (acc None) or acc + (a b^T) .* Ki in ONE pass; b None: b is a (Ki square; an exactly symmetric Ki stays
+    exactly symmetric) and diag_add goes onto the diagonal.  `out` may be Ki (acc None) or acc; allocated when None."""
+    lib = _lib.load()
+    _chk(Ki, "Ki", 2)
+    n1, n2 = Ki.shape
+    if b is None and n1 != n2:
+        raise ValueError("changepoint_fold: b None needs a square Ki")
+    pa = _cp_vector(a, n1, "a")
+    pb = None if b is None else _cp_vector(b, n2, "b")
+    if acc is not None:
+        _chk(acc, "acc", 2)
+        if tuple(acc.shape) != (n1, n2):
+            raise ValueError("inconsistent shapes")
+    if out is None:
+        out = torch.empty((n1, n2), dtype=torch.float64, device=Ki.device)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (n1, n2):
+        raise ValueError("inconsistent shapes")
+    if n1 == 0 or n2 == 0:
+        return out
+    rc = lib.gpk_changepoint_fold(_stream(), 0 if acc is None else 1, pa, pb, n1, n2, Ki.data_ptr(), _rowmajor(Ki, "Ki"),
+                                  None if acc is None else acc.data_ptr(), 0 if acc is None else _rowmajor(acc, "acc"), float(diag_add),
+                                  out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_changepoint_fold")
+    return out
+
+
+def changepoint_adjoint_parts(T: int, n1: int, n2: int, device_=None) -> torch.Tensor:
+    """the scratch operand `parts` of changepoint_adjoint_stage / _tail for T members: [T, tc n1 + tr n2] doubles, tr / tc the tile
+    rows / columns of CP_TILE (include/gpk.h: the documented extent per member); its contents at entry do not matter"""
+    tr, tc = -(-int(n1) // CP_TILE), -(-int(n2) // CP_TILE)
+    return torch.empty((int(T), tc * int(n1) + tr * int(n2)), dtype=torch.float64, device=device_ or device())
+
+
+def changepoint_adjoint_stage(a: torch.Tensor, b: Optional[torch.Tensor], Kbar: torch.Tensor, Ki: torch.Tensor, parts: torch.Tensor, *,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pass over Kbar and Ki [n1, n2]: returns G = Kbar .* (a b^T) (`out` may be Ki itself; Kbar is never written) and fills
+    `parts` (ONE member's row of changepoint_adjoint_parts) with the per-tile sums of Kbar Ki b_c (by row) and Kbar Ki a_r (by
+    column).  b None: b is a, every element computed.  Deterministic: a second call gives the same bits."""
+    lib = _lib.load()
+    _chk(Kbar, "Kbar", 2)
+    _chk(Ki, "Ki", 2)
+    n1, n2 = Kbar.shape
+    if tuple(Ki.shape) != (n1, n2) or (b is None and n1 != n2):
+        raise ValueError("inconsistent shapes")
+    pa = _cp_vector(a, n1, "a")
+    pb = None if b is None else _cp_vector(b, n2, "b")
+    _chk(parts, "parts", 1)
+    tr, tc = -(-n1 // CP_TILE), -(-n2 // CP_TILE)
+    if not parts.is_contiguous() or parts.numel() < tc * n1 + tr * n2:
+        raise ValueError(f"changepoint_adjoint_stage: parts must be a contiguous [>= {tc * n1 + tr * n2}] (ops.changepoint_adjoint_parts)")
+    if out is None:
+        out = torch.empty((n1, n2), dtype=torch.float64, device=Kbar.device)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (n1, n2):
+        raise ValueError("inconsistent shapes")
+    if n1 == 0 or n2 == 0:
+        return out
+    rc = lib.gpk_changepoint_adjoint_stage(_stream(), pa, pb, n1, n2, Kbar.data_ptr(), _rowmajor(Kbar, "Kbar"), Ki.data_ptr(),
+                                           _rowmajor(Ki, "Ki"), out.data_ptr(), _rowmajor(out, "out"), parts.data_ptr())
+    _lib.check(rc, "gpk_changepoint_adjoint_stage")
+    return out
+
+
+def changepoint_adjoint_tail(x: torch.Tensor, *, locations, steepness, parts: Optional[torch.Tensor] = None, n_other: int = 0,
+                             columns: bool = False, init: Optional[torch.Tensor] = None
+                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(d/dlocations [C] (sorted order), d/dsteepness [C], xbar [n]) for ONE argument of the kernel with its switch column x [n].
+    The weight adjoints are `init` [T, n] (None: zeros) plus the sums of the stage's partials: `parts` [T, tc n1 + tr n2]
+    (ops.changepoint_adjoint_parts, every member's row filled by its stage call); columns False: x is the first argument (n = n1,
+    n_other = n2), True: the second (n = n2, n_other = n1).  parts None: `init` alone (the diagonal path).  Fixed summation order: a
+    second call is bit-identical."""
+    lib = _lib.load()
+    C, loc, st = _cp_points(locations, steepness)
+    px, n, ldx = _cp_column(x, "x")
+    dev = x.device
+    small = torch.zeros(2 * C, dtype=torch.float64, device=dev)
+    xbar = torch.zeros(n, dtype=torch.float64, device=dev)
+    pp, stride, ntiles = None, 0, 0
+    if parts is not None:
+        _chk(parts, "parts", 2)
+        n1, n2 = (int(n_other), n) if columns else (n, int(n_other))
+        tr, tc = -(-n1 // CP_TILE), -(-n2 // CP_TILE)
+        if not parts.is_contiguous() or parts.shape[0] != C + 1 or parts.shape[1] < tc * n1 + tr * n2:
+            raise ValueError(f"changepoint_adjoint_tail: parts must be a contiguous [{C + 1}, >= {tc * n1 + tr * n2}]")
+        stride, ntiles = int(parts.shape[1]), (tr if columns else tc)
+        pp = parts.data_ptr() + (8 * tc * n1 if columns else 0)
+    if init is not None:
+        _chk(init, "init", 2)
+        if tuple(init.shape) != (C + 1, n):
+            raise ValueError(f"changepoint_adjoint_tail: init must be [{C + 1}, {n}]")
+    if n == 0 or C == 0:
+        return small[:C], small[C:], xbar
+    red = torch.empty(-(-n // CP_TAIL_ROWS) * 2 * C, dtype=torch.float64, device=dev)
+    rc = lib.gpk_changepoint_adjoint_tail(_stream(), px, n, ldx, C, loc, st, pp if ntiles else None, stride, ntiles,
+                                          None if init is None else init.data_ptr(), 0 if init is None else _rowmajor(init, "init"),
+                                          red.data_ptr(), small.data_ptr(), xbar.data_ptr())
+    _lib.check(rc, "gpk_changepoint_adjoint_tail")
+    return small[:C], small[C:], xbar
+
+
 # ------------------------------------------------------------------------------------------------ Coregion kernel (coregion/coregion.hip)
 COREGION_MAX_OUTPUTS, COREGION_MAX_RANK = 64, 64   # include/gpk.h: GPK_COREGION_MAX_OUTPUTS, GPK_COREGION_MAX_RANK
 _coregion_cache: "collections.OrderedDict" = collections.OrderedDict()

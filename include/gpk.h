@@ -621,6 +621,55 @@ int gpk_arccos_adjoint_stage(void* stream, int order, const double* X1, int n1, 
 int gpk_arccos_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, const double* B, long ldb, int n2,
                             int d, const double* w_host, int ard, const double* parts, double* rg, double* dsmall, double* Abar,
                             long ldab);
+/* ---- ChangePoints kernel (changepoints/changepoints.hip; gpflow/kernels/changepoints.py) ---------------------------------------
+ * A combination that switches between T = C + 1 member kernels along ONE input column x.  With the locations l_0 <= ... <= l_{C-1}
+ * (loc_host) and the steepness s_j > 0 (steep_host), both HOST pointers with C entries, C <= GPK_CP_MAX_MEMBERS - 1:
+ *     sig_j(x) = 1 / (1 + exp(-s_j (x - l_j)))          1 - sig_j(x) = 1 / (1 + exp(+s_j (x - l_j)))
+ *     a_i(x) = sig_{i-1}(x) (1 - sig_i(x)),  i = 0 .. C  (sig_{-1} = 1, 1 - sig_C = 1)
+ *     K(x, y) = sum_i a_i(x) k_i(x, y) a_i(y)            K_diag(x) = sum_i a_i(x)^2 k_i(x, x)
+ *  1. 1 - sig_j is its own reciprocal, never a subtraction.
+ *  2. A saturated sigmoid is exactly 0 or 1 (exp overflows to Inf, underflows to 0): its member contributes exactly 0, or its full value.
+ *  3. The exponent is s (x - l) + (x - x): a NaN or an Inf in x makes every weight of that row NaN, hence exactly that row (column)
+ *     of K, and nothing else.
+ *  4. The tile passes form w = a_r b_c FIRST, then w * Ki: with b == NULL (b is a) an exactly symmetric Ki stays exactly symmetric.
+ * Every entry point returns, before any launch: GPK_E_UNSUPPORTED for C > GPK_CP_MAX_MEMBERS - 1; GPK_E_ARG for C < 0, a NULL
+ * loc_host / steep_host with C > 0, a location or steepness that is not finite, a steepness <= 0, locations that are not sorted, a
+ * negative size, a leading dimension that is too small, an op out of range, a NULL operand that has elements; 0 without a launch for
+ * an operand without elements.  No atomics; a second call gives the same bits; nothing beyond the stated extents is written.
+ *
+ * gpk_changepoint_weights: A [T, n] lda (>= n), row i = a_i(x_r), from the switch column x_r = x[r ldx] (pass the column's address).
+ * gpk_changepoint_fold: over Ki [n1, n2] ldki with a [n1], b [n2] (DEVICE; b == NULL: b is a, n2 is n1, and diag_add goes onto the
+ *   diagonal).  op 0: out = (a b^T) .* Ki;  op 1: out = acc + (a b^T) .* Ki.  out may alias Ki (op 0) or acc (op 1).  One pass: Ki and
+ *   acc are read once, out is written once.  acc is not read by op 0.
+ * gpk_changepoint_adjoint_stage: ONE pass over Kbar [n1, n2] ldkb and Ki [n1, n2] ldki that writes G = Kbar .* (a b^T) [n1, n2] ldg
+ *   (the seed of the member's own adjoint; G may alias Ki; Kbar is never written) and into parts, with tr = ceil(n1 / 64),
+ *   tc = ceil(n2 / 64):
+ *     parts[t * n1 + r],  t < tc               the sum over the columns c of column tile t of Kbar_rc Ki_rc b_c
+ *     parts[tc * n1 + t * n2 + c],  t < tr     the sum over the rows r of row tile t of Kbar_rc Ki_rc a_r
+ *   parts is scratch of tc n1 + tr n2 doubles (GPK_CP_TILE = 64): the call writes every slot, each by exactly one workgroup in a
+ *   fixed order, reads none and touches nothing beyond that extent.  b == NULL: every element is computed (no mirror) and both sets
+ *   are filled.
+ * gpk_changepoint_adjoint_tail: for ONE argument (the rows, or the columns) with its switch column x [n] ldx.  The weight adjoints are
+ *     abar_i[r] = init[i ldinit + r] + sum_{t < ntiles} parts[i member_stride + t n + r]        i = 0 .. C, t ascending
+ *   (init [T, n] ldinit may be NULL: zeros; ntiles == 0: parts is not read and may be NULL; for the rows pass the stage's parts and
+ *   ntiles = tc, for the columns parts + tc n1 and ntiles = tr; member_stride: from member i's parts to member i + 1's).  With
+ *   tbar_j = abar_{j+1} a_{j+1} (1 - sig_j) - abar_j a_j sig_j:
+ *     dsmall[j]     = d/dl_j = -s_j sum_r tbar_j          dsmall[C + j] = d/ds_j = sum_r tbar_j (x_r - l_j)          j = 0 .. C-1
+ *     xbar[r]       = sum_j s_j tbar_j
+ *   Two launches: one thread per row, each workgroup of 256 rows leaving its 2 C sums in red (scratch of ceil(n / 256) 2 C doubles,
+ *   every slot written by one workgroup in a fixed order); then ONE workgroup adds them in block order.  C == 0 or n == 0: 0,
+ *   nothing is written. */
+#define GPK_CP_TILE 64
+#define GPK_CP_MAX_MEMBERS 16
+int gpk_changepoint_weights(void* stream, const double* x, int n, long ldx, int C, const double* loc_host, const double* steep_host,
+                            double* A, long lda);
+int gpk_changepoint_fold(void* stream, int op, const double* a, const double* b, int n1, int n2, const double* Ki, long ldki,
+                         const double* acc, long ldacc, double diag_add, double* out, long ldo);
+int gpk_changepoint_adjoint_stage(void* stream, const double* a, const double* b, int n1, int n2, const double* Kbar, long ldkb,
+                                  const double* Ki, long ldki, double* G, long ldg, double* parts);
+int gpk_changepoint_adjoint_tail(void* stream, const double* x, int n, long ldx, int C, const double* loc_host, const double* steep_host,
+                                 const double* parts, long member_stride, int ntiles, const double* init, long ldinit, double* red,
+                                 double* dsmall, double* xbar);
 /* ---- Coregion kernel (coregion/coregion.hip; gpflow/kernels/misc.py `Coregion`) --------------------------------------------------
  * The intrinsic-coregionalisation (multi-task) kernel over ONE input column that carries the row's task label.  With W [P, R]
  * (unconstrained) and kappa [P] (positive), P = output_dim <= GPK_COREGION_MAX_OUTPUTS, R = rank <= GPK_COREGION_MAX_RANK:
