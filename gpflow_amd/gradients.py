@@ -247,13 +247,21 @@ def arccos_kernel_adjoint(leaf: ArcLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar
 
 
 class Member:
-    """One leaf of a KernelSpec as the tree walkers call it: its host values (`leaf`), the input columns it sees (`cols`: an index array,
-    or None for all), a Periodic leaf's `period`, and every answer that depends on the KIND of leaf.  This base class holds what the
-    kinds built by `gpk_kernel_matrix` share (stationary, static, periodic): the builders, and K(x, x) = variance as one host value.
-    `adjoint(A, Bm, Kbar, symmetric)` -> (d/dvariance [n_variance], shape gradient, A_bar over the member's columns, or None for no
-    input gradient) goes through the kind's `leaf_adjoint` function.  The four kinds follow; a further kind is one more class here."""
-    constant_diagonal, n_variance = True, 1
-    matrix, combine = "kernel_matrix", "kernel_matrix_combine"   # the kind's builders, by their names in `ops`
+    """One leaf of a KernelSpec as the tree walkers call it: its host values (`leaf`: a value of leaf.py that answers its protocol),
+    the input columns it sees (`cols`: an index array, or None for all), a Periodic leaf's `period`, and every answer that depends on
+    the KIND of leaf.  This base class holds what every kind shares: the builders (the leaf's `builders`, looked up on `ops` by name at
+    the call), `n_variance`, `parameter_names`, `n_shape` and `split_shape` as the leaf answers them, `adjoint(A, Bm, Kbar, symmetric)`
+    -> (d/dvariance [n_variance], shape gradient, A_bar over the member's columns, or None for no input gradient) through the kind's
+    `leaf_adjoint` function; and what the kinds built by `gpk_kernel_matrix` share (stationary, static, periodic): K(x, x) = variance
+    as one host value.  RowDiagonalMember holds what the kinds with a diagonal that depends on the row share.
+
+    Where the next kind plugs in: one value type in leaf.py that answers the protocol, three thin `ops` wrappers (matrix, combine,
+    row diagonal) over `ops._pair_builder` / `ops._row_diagonal`, one kernel class on kernels.base.RowDiagonalLeaf, and here one
+    subclass of RowDiagonalMember with its `leaf_adjoint`, `diag_adjoint` and `warm`, entered in MEMBER_OF_LEAF."""
+    constant_diagonal = True
+    n_variance = property(lambda self: self.leaf.n_variance)
+    matrix = property(lambda self: self.leaf.builders[0])     # the kind's builders, by their names in `ops`
+    combine = property(lambda self: self.leaf.builders[1])
 
     def __init__(self, leaf, cols=None, period=None):
         self.leaf, self.cols, self.period, self._idx = leaf, cols, period, {}
@@ -297,7 +305,7 @@ class Member:
         """device copies of what the adjoint's tails read, made now (see `ls_device`); D: the width of the full inputs"""
 
     def parameter_names(self) -> tuple:
-        return self.leaf.row.parameters
+        return self.leaf.parameters
 
     def n_shape(self) -> int:
         return self.leaf.n_shape
@@ -325,78 +333,64 @@ class StaticMember(Member):
         return dv.reshape(1), dl, None
 
 
-class DotMember(Member):
-    """a dot-product leaf (leaf.DotLeaf: Linear, Polynomial), built and folded by the `gpk_dot_*` entry points.  K(x, x) depends on the
-    row: `kdiag_rows` / `fold_kdiag`; the variance gradient has D entries when the variance is ARD, the shape gradient is [d/doffset] or
-    empty."""
+class RowDiagonalMember(Member):
+    """a leaf whose K(x, x) depends on the row (leaf.py: `constant_diagonal` False): `kdiag_rows` / `fold_kdiag` through the leaf's row
+    diagonal builder take the place of the one host value, and `diag_adjoint` is the kind's own"""
     constant_diagonal = False
-    matrix, combine = "dot_kernel_matrix", "dot_kernel_matrix_combine"
-    leaf_adjoint = staticmethod(dot_kernel_adjoint)
-    n_variance = property(lambda self: self.leaf.n_variance)
 
     def kdiag(self) -> float:
-        raise NotImplementedError("K(x, x) of a dot-product member (Linear, Polynomial) depends on the row: this caller takes the "
-                                  "diagonal for one scalar and has not been converted to KernelSpec.kdiag_rows")
+        raise NotImplementedError(f"K(x, x) of a {self.leaf.family} member depends on the row: this caller takes the diagonal for one "
+                                  "scalar and has not been converted to KernelSpec.kdiag_rows")
 
     def kdiag_rows(self, X) -> torch.Tensor:
         """K(x_b, x_b) as a fresh [rows] tensor"""
-        return ops.dot_kernel_diag(self.view(X), **self.leaf.keywords())
+        return getattr(ops, self.leaf.builders[2])(self.view(X), **self.leaf.keywords())
 
     def fold_kdiag(self, X, acc, op: str) -> None:
         """acc <- acc .* K(x_b, x_b) or acc + K(x_b, x_b) in place"""
-        ops.dot_kernel_diag(self.view(X), acc, op=op, out=acc, **self.leaf.keywords())
+        getattr(ops, self.leaf.builders[2])(self.view(X), acc, op=op, out=acc, **self.leaf.keywords())
+
+    def rows(self, X):
+        """the member's view of X, contiguous: what a `diag_adjoint` contracts with"""
+        Xi = self.view(X)
+        return Xi if Xi.is_contiguous() else Xi.contiguous()
+
+
+def _moment_sums(g: torch.Tensor, Xi: torch.Tensor) -> torch.Tensor:
+    """m [1 + 2 D] = (sum_b g_b, sum_b g_b x_bj, sum_b g_b x_bj^2) from ONE thin product of g [rows] with ops.moment_rows(Xi)"""
+    return ops.gemm_nt(g.reshape(1, -1), ops.moment_rows(Xi))[0]
+
+
+class DotMember(RowDiagonalMember):
+    """a dot-product leaf (leaf.DotLeaf: Linear, Polynomial), built and folded by the `gpk_dot_*` entry points.  The variance gradient
+    has D entries when the variance is ARD, the shape gradient is [d/doffset] or empty."""
+    leaf_adjoint = staticmethod(dot_kernel_adjoint)
 
     def diag_adjoint(self, X, bar):
-        """g = bar .* dkd/ds and, from ONE thin product of g with ops.moment_rows(X), d/dw_j = sum_b g_b x_bj^2 and d/doffset = sum_b g_b"""
-        leaf = self.leaf
-        Xi = self.view(X)
-        Xi = Xi if Xi.is_contiguous() else Xi.contiguous()
-        D = Xi.shape[1]
-        g = bar if leaf.family == "Linear" else ops.dot_kernel_diag(Xi, bar, op="ds", **leaf.keywords())
-        m = ops.gemm_nt(g.reshape(1, -1), ops.moment_rows(Xi))[0]      # [1 + 2 D]: sum g, sum g x_j, sum g x_j^2
-        dw = m[1 + D:]
+        """g = bar .* dkd/ds and, from `_moment_sums`, d/dw_j = sum_b g_b x_bj^2 and d/doffset = sum_b g_b"""
+        leaf, Xi = self.leaf, self.rows(X)
+        m = _moment_sums(bar if leaf.family == "Linear" else ops.dot_kernel_diag(Xi, bar, op="ds", **leaf.keywords()), Xi)
+        dw = m[1 + Xi.shape[1]:]
         return (dw if leaf.ard else dw.sum().reshape(1)), (m[0:1] if leaf.row.extras else m[:0])
 
     def warm(self, device, D: int) -> None:
         ls_device(self.leaf.variance, self.leaf.n_variance, device)   # (the weights of the dot-product tail)
 
 
-class ArcMember(Member):
-    """an ArcCosine leaf (leaf.ArcLeaf), built and folded by the `gpk_arccos_*` entry points.  K(x, x) = variance jf p(x)^order depends
-    on the row: `kdiag_rows` / `fold_kdiag`; one variance entry, the shape gradient is d/dweight_variances [1 or D], then
-    d/dbias_variance."""
-    constant_diagonal = False
-    matrix, combine = "arccos_kernel_matrix", "arccos_kernel_matrix_combine"
+class ArcMember(RowDiagonalMember):
+    """an ArcCosine leaf (leaf.ArcLeaf), built and folded by the `gpk_arccos_*` entry points: K(x, x) = variance jf p(x)^order.  One
+    variance entry, the shape gradient is d/dweight_variances [1 or D], then d/dbias_variance."""
     leaf_adjoint = staticmethod(arccos_kernel_adjoint)
 
-    def kdiag(self) -> float:
-        raise NotImplementedError("K(x, x) of an ArcCosine member depends on the row: this caller takes the diagonal for one scalar and "
-                                  "has not been converted to KernelSpec.kdiag_rows")
-
-    def kdiag_rows(self, X) -> torch.Tensor:
-        """K(x_b, x_b) as a fresh [rows] tensor"""
-        return ops.arccos_kernel_diag(self.view(X), **self.leaf.keywords())
-
-    def fold_kdiag(self, X, acc, op: str) -> None:
-        """acc <- acc .* K(x_b, x_b) or acc + K(x_b, x_b) in place"""
-        ops.arccos_kernel_diag(self.view(X), acc, op=op, out=acc, **self.leaf.keywords())
-
     def diag_adjoint(self, X, bar):
-        """d/dvariance = sum_b bar_b kd_b / variance (the diagonal at variance 1); g = bar .* dkd/dp and, from ONE thin product of g with
-        ops.moment_rows(X), d/dw_j = sum_b g_b x_bj^2 and d/dbias = sum_b g_b"""
-        leaf = self.leaf
-        Xi = self.view(X)
-        Xi = Xi if Xi.is_contiguous() else Xi.contiguous()
-        D = Xi.shape[1]
+        """d/dvariance = sum_b bar_b kd_b / variance (the diagonal at variance 1); g = bar .* dkd/dp and, from `_moment_sums`,
+        d/dw_j = sum_b g_b x_bj^2 and d/dbias = sum_b g_b"""
+        leaf, Xi = self.leaf, self.rows(X)
         kw = leaf.keywords()
         dv = ops.arccos_kernel_diag(Xi, bar, op="mul", **dict(kw, variance=1.0)).sum().reshape(1)
-        g = ops.arccos_kernel_diag(Xi, bar, op="dp", **kw)
-        m = ops.gemm_nt(g.reshape(1, -1), ops.moment_rows(Xi))[0]      # [1 + 2 D]: sum g, sum g x_j, sum g x_j^2
-        dw = m[1 + D:]
+        m = _moment_sums(ops.arccos_kernel_diag(Xi, bar, op="dp", **kw), Xi)
+        dw = m[1 + Xi.shape[1]:]
         return dv, torch.cat([dw if leaf.ard else dw.sum().reshape(1), m[0:1]])
-
-    def parameter_names(self) -> tuple:
-        return self.leaf.parameters
 
 
 def coregion_kernel_adjoint(leaf: CoregionLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, symmetric: bool):
@@ -419,48 +413,22 @@ def coregion_kernel_adjoint(leaf: CoregionLeaf, A: torch.Tensor, Bm: torch.Tenso
     return dk, dW.reshape(-1), None
 
 
-class CoregionMember(Member):
-    """a Coregion leaf (leaf.CoregionLeaf), built and folded by the `gpk_coregion_*` entry points over its ONE label column.
-    K(x, x) = B[l, l] depends on the row: `kdiag_rows` / `fold_kdiag`.  The gradient slot the spec calls "variance" holds d/dkappa [P]
-    (as the ARD variance of a DotMember has D entries); the shape gradient is d/dW [P R]; there is no input gradient."""
-    constant_diagonal = False
-    matrix, combine = "coregion_kernel_matrix", "coregion_kernel_matrix_combine"
+class CoregionMember(RowDiagonalMember):
+    """a Coregion leaf (leaf.CoregionLeaf), built and folded by the `gpk_coregion_*` entry points over its ONE label column:
+    K(x, x) = B[l, l].  The gradient slot the spec calls "variance" holds d/dkappa [P] (as the ARD variance of a DotMember has D
+    entries); the shape gradient is d/dW [P R]; there is no input gradient."""
     leaf_adjoint = staticmethod(coregion_kernel_adjoint)
-    n_variance = property(lambda self: self.leaf.n_variance)
-
-    def kdiag(self) -> float:
-        raise NotImplementedError("K(x, x) of a Coregion member depends on the row: this caller takes the diagonal for one scalar and "
-                                  "has not been converted to KernelSpec.kdiag_rows")
-
-    def kdiag_rows(self, X) -> torch.Tensor:
-        """K(x_b, x_b) as a fresh [rows] tensor"""
-        return ops.coregion_kernel_diag(self.view(X), **self.leaf.keywords())
-
-    def fold_kdiag(self, X, acc, op: str) -> None:
-        """acc <- acc .* K(x_b, x_b) or acc + K(x_b, x_b) in place"""
-        ops.coregion_kernel_diag(self.view(X), acc, op=op, out=acc, **self.leaf.keywords())
 
     def diag_adjoint(self, X, bar):
         """dbar_a = sum_{b: l_b = a} bar_b from ONE thin product of bar with the one-hot rows; kd = sum_r W[l, r]^2 + kappa[l], so
         d/dkappa = dbar and d/dW[a, :] = 2 dbar_a W[a, :]"""
-        leaf = self.leaf
-        Xi = self.view(X)
-        Xi = Xi if Xi.is_contiguous() else Xi.contiguous()
+        leaf, Xi = self.leaf, self.rows(X)
         dbar = ops.gemm_nt(bar.reshape(1, -1), ops.coregion_onehot_rows(Xi, leaf.n_outputs))[0]      # [P]
         Wd = ls_device(leaf.W.reshape(-1), leaf.n_shape, bar.device).reshape(leaf.n_outputs, leaf.rank)
         return dbar, (2.0 * dbar[:, None] * Wd).reshape(-1)
 
-    def adjoint(self, A, Bm, Kbar, symmetric):
-        Ai = self.view(A)
-        Bi = Ai if (symmetric and Bm is A) else self.view(Bm)
-        dk, dW, _ = self.leaf_adjoint(self.leaf, Ai, Bi, Kbar, symmetric=symmetric)
-        return dk.reshape(-1), dW, None
-
     def warm(self, device, D: int) -> None:
         ls_device(self.leaf.W.reshape(-1), self.leaf.n_shape, device)   # (the W of diag_adjoint)
-
-    def parameter_names(self) -> tuple:
-        return self.leaf.parameters
 
 
 class PeriodicMember(StationaryMember):
@@ -503,7 +471,7 @@ class PeriodicMember(StationaryMember):
         ls_device(self.leaf.lengthscales, 2 * Di, device)
 
     def parameter_names(self) -> tuple:
-        return self.leaf.row.parameters + ("period",)
+        return self.leaf.parameters + ("period",)
 
     def n_shape(self) -> int:
         return max(self.leaf.n_lengthscales // 2, 1) + len(self.leaf.extras) + int(self.period.size)
@@ -513,6 +481,11 @@ class PeriodicMember(StationaryMember):
         nper, nex = int(self.period.size), len(self.leaf.extras)
         nls = g.shape[0] - nper - nex
         return {"lengthscales": g[:nls], **{name: g[nls + j:nls + j + 1] for j, name in enumerate(self.leaf.row.extras)}, "period": g[nls + nex:]}
+
+
+# leaf type -> member class: the one place where the four kinds of leaf are listed (a Leaf: StaticMember / PeriodicMember are chosen
+# by its values, in the constructor of KernelSpec)
+MEMBER_OF_LEAF = {Leaf: StationaryMember, DotLeaf: DotMember, ArcLeaf: ArcMember, CoregionLeaf: CoregionMember}
 
 
 class ChangePointsNode:
@@ -544,11 +517,13 @@ class KernelSpec:
     """What the reverse pass needs to know about the covariance function: ONE kernel leaf, or a Sum / Product of leaves -- flat, or
     nested (a Product of Sums, ...: `op` a tree, see __init__) -- over the same or different input columns (gpflow/kernels/base.py:216-220
     `Sum`, :305-315 `Product`; the reference differentiates `tf.add_n` / `tf.multiply` of the member matrices with autodiff).
-    members: leaves (leaf.Leaf, leaf.DotLeaf, leaf.ArcLeaf, leaf.CoregionLeaf), given as such or as tuples (family, variance, lengthscales[, alpha]); op: None | "add" |
+    members: leaves (the value types of leaf.py), given as such or as tuples (family, variance, lengthscales[, alpha]); op: None | "add" |
     "mul" | tree.
 
-    The constructor chooses ONE member object per leaf (`parts`: a StationaryMember, StaticMember, DotMember, ArcMember, CoregionMember or PeriodicMember), the
-    only place where the kind of a leaf is asked.  Everything else here is about the TREE: `_build`, `_constant`, `_kd`, `_kd_rows`,
+    The constructor chooses ONE member object per leaf (`parts`) from the one mapping MEMBER_OF_LEAF, leaf type -> member class (a Leaf
+    with a period: a PeriodicMember; a static one: a StaticMember), the only place where the kind of a leaf is asked.  The next kind
+    plugs in there: one leaf type that answers the protocol of leaf.py, three thin `ops` wrappers, one kernel class on
+    kernels.base.RowDiagonalLeaf, one member class with its `diag_adjoint` and `leaf_adjoint`.  Everything else here is about the TREE: `_build`, `_constant`, `_kd`, `_kd_rows`,
     `_diag_adjoint`, `_dkd` and `_adjoint` are the only walkers, and at a leaf each is one call on the member object.
 
     A third kind of node, ("cp", [children], k), is a ChangePoints combination (kernels/changepoints.py): K = sum_i (a_i b_i^T) .* K_i
@@ -573,7 +548,7 @@ class KernelSpec:
         ("cp", [children], k) -- a ChangePointsNode, the one kind of node with parameters of its own."""
         self.nodes = list(nodes or [])
         self._node_grads = None
-        self.members = [m if isinstance(m, (Leaf, DotLeaf, ArcLeaf, CoregionLeaf)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
+        self.members = [m if isinstance(m, tuple(MEMBER_OF_LEAF)) else Leaf(*m[:3], alpha=m[3] if len(m) > 3 else None) for m in members]
         # op: "add" | "mul" for a flat combination of all members, or a TREE for nested ones (a Product of Sums, ...):
         # (op, [children]) with a child either a member index or another such pair -- e.g. ("mul", [("add", [0, 1]), 2]) is
         # (k0 + k1) * k2 (kernels/base.py:223-329: a Combination holds kernels, which may be Combinations of the other kind).
@@ -596,13 +571,10 @@ class KernelSpec:
             raise ValueError("one period (or None) per member")
         self.periods = [None if p is None else np.asarray(p, dtype=np.float64) for p in periods]
         for leaf, p in zip(self.members, self.periods):
-            if p is not None and (isinstance(leaf, (DotLeaf, ArcLeaf, CoregionLeaf)) or leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
+            if p is not None and (not isinstance(leaf, Leaf) or leaf.is_static or p.ndim > 1 or (leaf.n_lengthscales > 1 and leaf.n_lengthscales % 2)):
                 raise ValueError("a periodic member is a leaf with a distance over the warped columns, its period 0-d or [D]")
-        self.parts = [PeriodicMember(leaf, c, p) if p is not None else DotMember(leaf, c) if isinstance(leaf, DotLeaf)
-                      else ArcMember(leaf, c) if isinstance(leaf, ArcLeaf)
-                      else CoregionMember(leaf, c) if isinstance(leaf, CoregionLeaf)
-                      else StaticMember(leaf, c) if leaf.is_static else StationaryMember(leaf, c)
-                      for leaf, c, p in zip(self.members, self.cols, self.periods)]
+        self.parts = [PeriodicMember(leaf, c, p) if p is not None else StaticMember(leaf, c) if isinstance(leaf, Leaf) and leaf.is_static
+                      else MEMBER_OF_LEAF[type(leaf)](leaf, c) for leaf, c, p in zip(self.members, self.cols, self.periods)]
 
     @staticmethod
     def single(variance, lengthscales, family="SquaredExponential", alpha=None):
@@ -831,6 +803,13 @@ class KernelSpec:
         self._adjoint(self.tree, A, Bm, Kbar, symmetric, acc)
         return acc["dv"], acc["dl"], (acc["Abar"] if acc["Abar"] is not None else torch.zeros_like(A))   # (static members only: zero)
 
+    @staticmethod
+    def _abar(acc, A):
+        """acc["Abar"] to add into in place: begun as zeros like A where no input gradient has reached it yet"""
+        if acc["Abar"] is None:
+            acc["Abar"] = torch.zeros_like(A)
+        return acc["Abar"]
+
     def _adjoint(self, node, A, Bm, Kbar, symmetric, acc):
         if isinstance(node, int):
             m = self.parts[node]
@@ -839,13 +818,10 @@ class KernelSpec:
                 return
             if all(c is None for c in self.cols):
                 acc["Abar"] = Ab if acc["Abar"] is None else acc["Abar"] + Ab
+            elif m.cols is None:
+                self._abar(acc, A).add_(Ab)
             else:   # scatter the member's input gradient back into the columns it read
-                if acc["Abar"] is None:
-                    acc["Abar"] = torch.zeros_like(A)
-                if m.cols is None:
-                    acc["Abar"] += Ab
-                else:
-                    acc["Abar"].index_add_(1, m.index(A.device), Ab)
+                self._abar(acc, A).index_add_(1, m.index(A.device), Ab)
             return
         if node[0] == "cp":
             return self._adjoint_cp(node, A, Bm, Kbar, symmetric, acc)
@@ -885,9 +861,7 @@ class KernelSpec:
         dl, ds, xbar = ops.changepoint_adjoint_tail(A[:, nd.switch_dim], n_other=n2, columns=False, **kw)
         dl2, ds2, xbar2 = ops.changepoint_adjoint_tail((A if symmetric else Bm)[:, nd.switch_dim], n_other=n1, columns=True, **kw)
         self._add_node_grads(k, dl + dl2, ds + ds2)
-        if acc["Abar"] is None:
-            acc["Abar"] = torch.zeros_like(A)
-        acc["Abar"][:, nd.switch_dim] += (xbar + xbar2) if symmetric else xbar
+        self._abar(acc, A)[:, nd.switch_dim] += (xbar + xbar2) if symmetric else xbar
 
     def pack(self, dvs, dls):
         """gradient entries: one member -> ("variance" [1], "lengthscales" [D or 1]) as before; several -> "variance" [n] and

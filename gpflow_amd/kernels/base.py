@@ -9,7 +9,7 @@ import torch
 
 from ..base import Module
 from .. import ops
-from ..leaf import BY_NAME, DOT_BY_NAME, Leaf
+from ..leaf import BY_NAME, Leaf
 
 ActiveDims = Union[slice, Sequence[int]]
 
@@ -115,7 +115,7 @@ class DeviceLeaf(Kernel):
 
     def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
         """out <- out .* K or out + K in place (K recomputed in registers: one read + one write of `out`, no second matrix); the
-        dot-product kernels answer it too (kernels/linears.py), and Combination.K_into asks nothing else of a member"""
+        row-diagonal leaves answer it too (RowDiagonalLeaf), and Combination.K_into asks nothing else of a member"""
         return ops.kernel_matrix_combine(X, X2, out, op=op, diag_add=diag_add, out=out, **self.leaf().keywords())
 
 
@@ -124,27 +124,69 @@ def is_device_leaf(k) -> bool:
     return bool(getattr(k, "device_leaf", False)) and getattr(k, "family", None) in ops.KERNEL_FAMILIES
 
 
+class RowDiagonalLeaf(Kernel):
+    """A kernel leaf whose K(x, x) depends on the row, built by the entry points of its own kind (`leaf_kind`: "dot" kernels/linears.py,
+    "arc" and "coregion" kernels/misc.py): never a DeviceLeaf, so every fused route that takes K_diag for the variance declines it and
+    the composed routes run.  Written once here, over `leaf()` (a value of leaf.py that answers its protocol), the leaf's `builders` --
+    looked up on `ops` by name at the call -- and `check_width(d)`, the ValueError before the device for a width the kernel cannot see:
+    K, K_into, K_fold, K_diag.  A class gives `leaf_kind`, its constructor, `leaf_params()`, `leaf()` and `check_width`."""
+    leaf_kind: Optional[str] = None
+
+    def _builder(self, which: int, X, *args, **kw):
+        self.check_width(X.shape[-1])
+        leaf = self.leaf()
+        return getattr(ops, leaf.builders[which])(X, *args, **kw, **leaf.keywords())
+
+    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
+        return self._builder(0, X, X2, diag_add=diag_add, lower_only=lower_only, out=out)
+
+    def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
+        """out <- out .* K or out + K in place, as DeviceLeaf.K_fold"""
+        return self._builder(1, X, X2, out, op=op, diag_add=diag_add, out=out)
+
+    def K(self, X, X2=None) -> torch.Tensor:
+        """leading batch dimensions as IsotropicStationary.K: flattened to rows and restored"""
+        X = ops.to_device(X)
+        D = X.shape[-1]
+        if X2 is None:
+            if X.dim() == 2:
+                return self.K_into(X, None, None)
+            lead, n = X.shape[:-2], X.shape[-2]
+            return torch.stack([self.K_into(x.contiguous(), None, None) for x in X.reshape(-1, n, D)]).reshape(*lead, n, n)
+        X2 = ops.to_device(X2)
+        Kf = self.K_into(X.reshape(-1, D).contiguous(), X2.reshape(-1, D).contiguous(), None)
+        return Kf.reshape(*X.shape[:-1], *X2.shape[:-1])
+
+    def K_diag(self, X) -> torch.Tensor:
+        """the row diagonal on the device (the kind's *_kernel_diag entry point); leading batch dimensions allowed"""
+        X = ops.to_device(X)
+        return self._builder(2, X.reshape(-1, X.shape[-1]).contiguous()).reshape(X.shape[:-1])
+
+
+def _leaf_kind(k):
+    return getattr(k, "leaf_kind", None)
+
+
 def is_dot_leaf(k) -> bool:
-    """True for a dot-product kernel (kernels/linears.py: Linear, Polynomial), built by gpk_dot_kernel_matrix.  Never together with
-    `is_device_leaf`: its K_diag depends on the row, which the routes that ask `is_device_leaf` do not allow for."""
-    return getattr(k, "dot_family", None) in DOT_BY_NAME
+    """True for a dot-product kernel (kernels/linears.py: Linear, Polynomial), built by gpk_dot_kernel_matrix.  A kernel has ONE
+    `leaf_kind`, and a DeviceLeaf none: this, `is_arc_leaf`, `is_coregion_leaf` and `is_device_leaf` never hold together."""
+    return _leaf_kind(k) == "dot"
 
 
 def is_arc_leaf(k) -> bool:
-    """True for an ArcCosine kernel (kernels/misc.py), built by gpk_arccos_kernel_matrix.  Never together with `is_device_leaf` or
-    `is_dot_leaf`: its K_diag depends on the row, and each element needs both row norms and an acos."""
-    return bool(getattr(k, "arc_leaf", False)) and not is_device_leaf(k) and not is_dot_leaf(k)
+    """True for an ArcCosine kernel (kernels/misc.py), built by gpk_arccos_kernel_matrix: each element needs both row norms and an acos."""
+    return _leaf_kind(k) == "arc"
 
 
 def is_coregion_leaf(k) -> bool:
-    """True for a Coregion kernel (kernels/misc.py), built by gpk_coregion_kernel_matrix.  Never together with `is_device_leaf`,
-    `is_dot_leaf` or `is_arc_leaf`: its K_diag depends on the row's task label, and an element is a gather from the output covariance."""
-    return bool(getattr(k, "coregion_leaf", False)) and not is_device_leaf(k) and not is_dot_leaf(k) and not is_arc_leaf(k)
+    """True for a Coregion kernel (kernels/misc.py), built by gpk_coregion_kernel_matrix: an element is a gather from the output
+    covariance, the diagonal depends on the row's task label."""
+    return _leaf_kind(k) == "coregion"
 
 
 def has_row_diagonal_leaf(k) -> bool:
-    """a leaf whose K(x, x) depends on the row: the dot-product kernels, ArcCosine and Coregion"""
-    return is_dot_leaf(k) or is_arc_leaf(k) or is_coregion_leaf(k)
+    """a leaf whose K(x, x) depends on the row: one with a `leaf_kind` (the dot-product kernels, ArcCosine, Coregion)"""
+    return _leaf_kind(k) is not None
 
 
 class Combination(Kernel):

@@ -10,17 +10,14 @@ from __future__ import annotations
 
 from typing import Optional
 
-import torch
-
 from ..base import Parameter, positive
-from .. import ops
 from ..leaf import DOT_BY_NAME, DotLeaf, check_degree
-from .base import ActiveDims, Kernel
+from .base import ActiveDims, RowDiagonalLeaf
 
 
-class Linear(Kernel):
+class Linear(RowDiagonalLeaf):
     """linears.py `Linear`: `variance` one weight, or one per active input column (ARD)"""
-    dot_family = "Linear"
+    leaf_kind, dot_family = "dot", "Linear"
 
     def __init__(self, variance=1.0, active_dims: Optional[ActiveDims] = None, name: Optional[str] = None):
         super().__init__(active_dims=active_dims, name=name)
@@ -46,33 +43,6 @@ class Linear(Kernel):
         v = self.variance.numpy()
         if v.ndim == 1 and v.shape[0] != d:
             raise ValueError(f"variance has {v.shape[0]} entries, the kernel sees {d} input columns")
-
-    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
-        self.check_width(X.shape[-1])
-        return ops.dot_kernel_matrix(X, X2, diag_add=diag_add, lower_only=lower_only, out=out, **self.leaf().keywords())
-
-    def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
-        """out <- out .* K or out + K in place, as DeviceLeaf.K_fold"""
-        return ops.dot_kernel_matrix_combine(X, X2, out, op=op, diag_add=diag_add, out=out, **self.leaf().keywords())
-
-    def K(self, X, X2=None) -> torch.Tensor:
-        """leading batch dimensions as IsotropicStationary.K: flattened to rows and restored"""
-        X = ops.to_device(X)
-        D = X.shape[-1]
-        if X2 is None:
-            if X.dim() == 2:
-                return self.K_into(X, None, None)
-            lead, n = X.shape[:-2], X.shape[-2]
-            return torch.stack([self.K_into(x.contiguous(), None, None) for x in X.reshape(-1, n, D)]).reshape(*lead, n, n)
-        X2 = ops.to_device(X2)
-        Kf = self.K_into(X.reshape(-1, D).contiguous(), X2.reshape(-1, D).contiguous(), None)
-        return Kf.reshape(*X.shape[:-1], *X2.shape[:-1])
-
-    def K_diag(self, X) -> torch.Tensor:
-        """the row diagonal on the device (gpk_dot_kernel_diag): the diagonal of K(X, X) bit for bit; leading batch dimensions allowed"""
-        X = ops.to_device(X)
-        self.check_width(X.shape[-1])
-        return ops.dot_kernel_diag(X.reshape(-1, X.shape[-1]).contiguous(), **self.leaf().keywords()).reshape(X.shape[:-1])
 
 
 class Polynomial(Linear):

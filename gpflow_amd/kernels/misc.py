@@ -29,13 +29,13 @@ import torch
 from ..base import Parameter, positive
 from .. import ops
 from ..leaf import ARC_PARAMETERS, COREGION_PARAMETERS, ArcLeaf, CoregionLeaf, check_coregion_sizes, check_order
-from .base import ActiveDims, Kernel
+from .base import ActiveDims, RowDiagonalLeaf
 
 
-class ArcCosine(Kernel):
+class ArcCosine(RowDiagonalLeaf):
     """misc.py `ArcCosine`: `order` 0, 1 or 2 (a constant; anything else raises ValueError, as the reference does);
     `weight_variances` one weight, or one per active input column (ARD)"""
-    arc_leaf = True
+    leaf_kind = "arc"
     implemented_orders = {0, 1, 2}
 
     def __init__(self, order: int = 0, variance=1.0, weight_variances=1.0, bias_variance=1.0, active_dims: Optional[ActiveDims] = None,
@@ -69,39 +69,11 @@ class ArcCosine(Kernel):
         if w.ndim == 1 and w.shape[0] != d:
             raise ValueError(f"weight_variances has {w.shape[0]} entries, the kernel sees {d} input columns")
 
-    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
-        self.check_width(X.shape[-1])
-        return ops.arccos_kernel_matrix(X, X2, diag_add=diag_add, lower_only=lower_only, out=out, **self.leaf().keywords())
 
-    def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
-        """out <- out .* K or out + K in place, as DeviceLeaf.K_fold"""
-        self.check_width(X.shape[-1])
-        return ops.arccos_kernel_matrix_combine(X, X2, out, op=op, diag_add=diag_add, out=out, **self.leaf().keywords())
-
-    def K(self, X, X2=None) -> torch.Tensor:
-        """leading batch dimensions as Linear.K: flattened to rows and restored"""
-        X = ops.to_device(X)
-        D = X.shape[-1]
-        if X2 is None:
-            if X.dim() == 2:
-                return self.K_into(X, None, None)
-            lead, n = X.shape[:-2], X.shape[-2]
-            return torch.stack([self.K_into(x.contiguous(), None, None) for x in X.reshape(-1, n, D)]).reshape(*lead, n, n)
-        X2 = ops.to_device(X2)
-        Kf = self.K_into(X.reshape(-1, D).contiguous(), X2.reshape(-1, D).contiguous(), None)
-        return Kf.reshape(*X.shape[:-1], *X2.shape[:-1])
-
-    def K_diag(self, X) -> torch.Tensor:
-        """the row diagonal on the device (gpk_arccos_kernel_diag), the closed form; leading batch dimensions allowed"""
-        X = ops.to_device(X)
-        self.check_width(X.shape[-1])
-        return ops.arccos_kernel_diag(X.reshape(-1, X.shape[-1]).contiguous(), **self.leaf().keywords()).reshape(X.shape[:-1])
-
-
-class Coregion(Kernel):
+class Coregion(RowDiagonalLeaf):
     """misc.py `Coregion`: `W` [output_dim, rank] unconstrained, initial 0.1 * ones; `kappa` [output_dim] positive, initial ones;
     `output_dim` in 1 ... 64 and `rank` in 1 ... 64 (anything else raises ValueError); exactly ONE active input column, the task label"""
-    coregion_leaf = True
+    leaf_kind = "coregion"
 
     def __init__(self, output_dim: int, rank: int, *, active_dims: Optional[ActiveDims] = None, name: Optional[str] = None):
         self.output_dim, self.rank = check_coregion_sizes(output_dim, rank)     # ValueError before anything else
@@ -135,32 +107,3 @@ class Coregion(Kernel):
     def output_variance(self) -> torch.Tensor:
         """diag(B) = sum_r W[:, r]^2 + kappa [output_dim], on the device"""
         return torch.diagonal(ops.coregion_output_covariance(**self.leaf().keywords())).clone()
-
-    def K_into(self, X, X2, out, *, diag_add: float = 0.0, lower_only: bool = False):
-        self.check_width(X.shape[-1])
-        return ops.coregion_kernel_matrix(X, X2, diag_add=diag_add, lower_only=lower_only, out=out, **self.leaf().keywords())
-
-    def K_fold(self, X, X2, out, op: str, diag_add: float = 0.0):
-        """out <- out .* K or out + K in place, as DeviceLeaf.K_fold"""
-        self.check_width(X.shape[-1])
-        return ops.coregion_kernel_matrix_combine(X, X2, out, op=op, diag_add=diag_add, out=out, **self.leaf().keywords())
-
-    def K(self, X, X2=None) -> torch.Tensor:
-        """leading batch dimensions as Linear.K: flattened to rows and restored"""
-        X = ops.to_device(X)
-        D = X.shape[-1]
-        self.check_width(D)
-        if X2 is None:
-            if X.dim() == 2:
-                return self.K_into(X, None, None)
-            lead, n = X.shape[:-2], X.shape[-2]
-            return torch.stack([self.K_into(x.contiguous(), None, None) for x in X.reshape(-1, n, D)]).reshape(*lead, n, n)
-        X2 = ops.to_device(X2)
-        Kf = self.K_into(X.reshape(-1, D).contiguous(), X2.reshape(-1, D).contiguous(), None)
-        return Kf.reshape(*X.shape[:-1], *X2.shape[:-1])
-
-    def K_diag(self, X) -> torch.Tensor:
-        """the row diagonal on the device (gpk_coregion_kernel_diag), read from B; leading batch dimensions allowed"""
-        X = ops.to_device(X)
-        self.check_width(X.shape[-1])
-        return ops.coregion_kernel_diag(X.reshape(-1, 1).contiguous(), **self.leaf().keywords()).reshape(X.shape[:-1])

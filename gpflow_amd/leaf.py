@@ -1,12 +1,35 @@
-"""What a device-built kernel leaf consists of, written once: the table of families and the value type `Leaf`.
+"""What a device-built kernel leaf consists of, written once: the tables of families and the four value types of a leaf.
 
-A leaf is one kernel that `gpk_kernel_matrix` builds from host hyperparameters.  Its pieces travel in one order everywhere -- as the
-Parameters of the kernel class, as the `ls_host` array of the C-ABI, as a shape gradient of the reverse pass:
+A leaf is one kernel that the device builds from host hyperparameters.  There are four kinds, one immutable value type each:
 
-    variance, lengthscales (a family with a distance), then the family's extras in the order of its table row
+    Leaf          a row of FAMILIES (stationary, static; a Periodic kernel's base), built by `gpk_kernel_matrix`; K(x, x) = variance
+    DotLeaf       a row of DOT_FAMILIES (Linear, Polynomial), built by the `gpk_dot_*` entry points
+    ArcLeaf       ArcCosine of order 0, 1 or 2, built by the `gpk_arccos_*` entry points
+    CoregionLeaf  Coregion over one column of task labels, built by the `gpk_coregion_*` entry points
 
-`ops` (the C-ABI form), `kernels` (the classes answer `leaf()`) and `gradients.KernelSpec` (its members are leaves) import this
-module; it imports none of them.  A new family is a row of FAMILIES; a new extra hyperparameter is a name in that row.
+THE PROTOCOL.  Every kind answers the same names with the same meaning; `ops` (the C-ABI form), `kernels` (the classes answer
+`leaf()`) and `gradients.KernelSpec` (its members are leaves) ask nothing else of a leaf, and none of them asks which kind it is:
+
+    family              the name of the leaf's family
+    parameters          the names of its hyperparameters (and of its kernel class's Parameters) in the ONE order they travel in: as
+                        the values `replace` takes, as the gradients of the reverse pass (the variance slot, then the shape gradient)
+    n_variance          entries of the gradient slot a KernelSpec calls "variance": 1; D for an ARD DotLeaf; P (d/dkappa) for Coregion
+    n_shape             entries of the shape gradient, everything after that slot
+    split_shape(g)      a shape gradient as {"lengthscales": ..., <name>: ..., ...} ("lengthscales" empty where the kind has none)
+    keywords()          the leaf as the keywords of its `ops` builders
+    replace(values)     the same family (and constants: degree, order) with other values, given in `parameters` order
+    is_plain            (variance, lengthscales) and nothing else: what the packed covariance tail and the trainer's device step keep
+    constant_diagonal   K(x, x) is one host value, the variance (Leaf); False: it depends on the row and the kind has a diag builder
+    builders            the names of the kind's `ops` functions: (matrix, combine, row diagonal or None)
+    abi(d)              what stands between the operands and `diag_add` in the kind's C entry points for inputs of d columns, the
+                        code that goes in front of the operands first: (code, *host(d), variance) for a Leaf -- `host` is the
+                        lengthscales, then the family's extras in the order of its table row --, (code, w, ard, offset, degree) for a
+                        DotLeaf, (order, w, ard, variance, bias) for an ArcLeaf.  A CoregionLeaf has no host-only form -- its table
+                        B = W W^T + diag(kappa) lives on the device -- and so no `abi`: it keeps W / kappa, and `ops` resolves B.
+
+This module imports none of its users.  A new family is a row of FAMILIES or DOT_FAMILIES, a new extra hyperparameter a name in that
+row; a new KIND is one more value type here that answers the protocol (then: three thin `ops` wrappers, a kernel class on
+kernels.base.RowDiagonalLeaf, a member class in `gradients`).
 """
 from __future__ import annotations
 
@@ -44,6 +67,8 @@ class Leaf(collections.namedtuple("_LeafFields", "row variance lengthscales extr
     order.  Made from keywords -- Leaf(family, variance, lengthscales, alpha=...) -- or, `of` / `replace`, from values in Parameter
     order."""
     __slots__ = ()
+    n_variance, constant_diagonal = 1, True
+    builders = ("kernel_matrix", "kernel_matrix_combine", None)
 
     def __new__(cls, family: str, variance, lengthscales=None, **extras):
         row = BY_NAME[family]
@@ -71,6 +96,10 @@ class Leaf(collections.namedtuple("_LeafFields", "row variance lengthscales extr
     @property
     def family(self) -> str:
         return self.row.name
+
+    @property
+    def parameters(self) -> Tuple[str, ...]:
+        return self.row.parameters
 
     @property
     def code(self) -> int:
@@ -101,11 +130,14 @@ class Leaf(collections.namedtuple("_LeafFields", "row variance lengthscales extr
 
     def host(self, d: int):
         """(host array, ard) of the C-ABI: the lengthscales, then the extras (include/gpk.h, next to the family codes)"""
-        ls = np.atleast_1d(self.lengthscales)
+        ls = self.lengthscales if self.lengthscales.ndim else self.lengthscales.reshape(1)
         ard = ls.size > 1
         if ard and ls.size != d:
             raise ValueError(f"lengthscales has {ls.size} entries, input dimension is {d}")
         return _lib.host_doubles(ls.tolist() + list(self.extras)), int(ard)
+
+    def abi(self, d: int) -> tuple:
+        return (self.code, *self.host(d), self.variance)
 
     def split_shape(self, g) -> dict:
         """a shape gradient, laid out like `host`, as {"lengthscales": ..., <extra>: [1], ...}"""
@@ -136,7 +168,8 @@ class DotLeaf(collections.namedtuple("_DotLeafFields", "row variance offset degr
     [1, DOT_MAX_DEGREE], a constant of the leaf without a gradient.  Its diagonal K(x, x) depends on the row: it is no row of FAMILIES,
     gpk_kernel_matrix and the fused drivers do not take it -- the gpk_dot_* entry points do (ops.dot_kernel_matrix, ...)."""
     __slots__ = ()
-    is_plain = False
+    is_plain = constant_diagonal = False
+    builders = ("dot_kernel_matrix", "dot_kernel_matrix_combine", "dot_kernel_diag")
 
     def __new__(cls, family: str, variance, offset=None, degree=None):
         if family not in DOT_BY_NAME:
@@ -166,6 +199,10 @@ class DotLeaf(collections.namedtuple("_DotLeafFields", "row variance offset degr
         return self.row.name
 
     @property
+    def parameters(self) -> Tuple[str, ...]:
+        return self.row.parameters
+
+    @property
     def code(self) -> int:
         return self.row.code
 
@@ -189,10 +226,13 @@ class DotLeaf(collections.namedtuple("_DotLeafFields", "row variance offset degr
 
     def host(self, d: int):
         """(host array of the weights, ard) of the C-ABI"""
-        w = np.atleast_1d(self.variance)
+        w = self.variance if self.variance.ndim else self.variance.reshape(1)
         if self.ard and w.size != d:
             raise ValueError(f"variance has {w.size} entries, input dimension is {d}")
         return _lib.host_doubles(w.tolist()), int(self.ard)
+
+    def abi(self, d: int) -> tuple:
+        return (self.code, *self.host(d), float(self.offset), int(self.degree))
 
     def split_shape(self, g) -> dict:
         """a shape gradient as {"lengthscales": empty, "offset": [1]}: no lengthscales, by the static members' convention"""
@@ -216,9 +256,9 @@ class ArcLeaf(collections.namedtuple("_ArcLeafFields", "order variance weight_va
     depends on the row and each element needs both row norms and an acos: it is no row of FAMILIES and none of DOT_FAMILIES -- the
     gpk_arccos_* entry points take it (ops.arccos_kernel_matrix, ...)."""
     __slots__ = ()
-    is_plain = False
-    family = "ArcCosine"
-    parameters = ARC_PARAMETERS
+    is_plain = constant_diagonal = False
+    family, parameters, n_variance = "ArcCosine", ARC_PARAMETERS, 1
+    builders = ("arccos_kernel_matrix", "arccos_kernel_matrix_combine", "arccos_kernel_diag")
 
     def __new__(cls, order, variance, weight_variances=1.0, bias_variance=1.0):
         w = np.asarray(weight_variances, dtype=np.float64)
@@ -254,10 +294,13 @@ class ArcLeaf(collections.namedtuple("_ArcLeafFields", "order variance weight_va
 
     def host(self, d: int):
         """(host array of the weights, ard) of the C-ABI"""
-        w = np.atleast_1d(self.weight_variances)
+        w = self.weight_variances if self.weight_variances.ndim else self.weight_variances.reshape(1)
         if self.ard and w.size != d:
             raise ValueError(f"weight_variances has {w.size} entries, input dimension is {d}")
         return _lib.host_doubles(w.tolist()), int(self.ard)
+
+    def abi(self, d: int) -> tuple:
+        return (self.order, *self.host(d), self.variance, self.bias_variance)
 
     def split_shape(self, g) -> dict:
         """a shape gradient as {"lengthscales": empty, "weight_variances": [1 or D], "bias_variance": [1]}"""
@@ -286,9 +329,9 @@ class CoregionLeaf(collections.namedtuple("_CoregionLeafFields", "W kappa")):
     layout of a KernelSpec the slot called "variance" holds d/dkappa [P] (as the ARD variance of a DotLeaf has D entries) and the shape
     gradient is d/dW flattened row-major [P R]."""
     __slots__ = ()
-    is_plain = False
-    family = "Coregion"
-    parameters = COREGION_PARAMETERS
+    is_plain = constant_diagonal = False
+    family, parameters = "Coregion", COREGION_PARAMETERS
+    builders = ("coregion_kernel_matrix", "coregion_kernel_matrix_combine", "coregion_kernel_diag")
 
     def __new__(cls, W, kappa):
         W, kappa = np.array(W, dtype=np.float64), np.array(kappa, dtype=np.float64)

@@ -7,6 +7,7 @@ nothing silently falls back to torch math or to the CPU.
 from __future__ import annotations
 
 import collections
+from functools import partial
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -56,13 +57,12 @@ def _rowmajor(t: torch.Tensor, name: str) -> int:
     """Leading dimension of a 2-D row-major view (last stride 1)."""
     if t.dim() != 2:
         raise ValueError(f"{name}: expected a matrix, got shape {tuple(t.shape)}")
-    if t.numel() == 0:   # no elements: the strides of an empty tensor mean nothing (include/gpk.h, empty operands)
-        return int(max(t.shape[1], 1))
-    if t.shape[1] > 1 and t.stride(1) != 1:
+    rows, cols = t.shape
+    if rows == 0 or cols == 0:   # no elements: the strides of an empty tensor mean nothing (include/gpk.h, empty operands)
+        return max(cols, 1)
+    if cols > 1 and t.stride(1) != 1:
         raise _lib.GpkError(f"{name}: last dimension must be contiguous")
-    if t.shape[0] > 1:
-        return int(t.stride(0))
-    return int(max(t.shape[1], 1))
+    return t.stride(0) if rows > 1 else cols
 
 
 INFO_HANDOFF_TIMEOUT = 2 ** 31 - 1   # include/gpk.h: status of a factorisation whose internal hand-off never arrived
@@ -90,8 +90,10 @@ def _noise_args(noise_variance, rows: int):
 
 
 # ------------------------------------------------------------------------------------------------
-def _kernel_operands(X1, X2, G, out, *, x2_optional: bool = True, zero_new: bool = False,
-                     columns_differ: str = "X1 and X2 must have the same number of columns"):
+_COLUMNS_DIFFER = "X1 and X2 must have the same number of columns"
+
+
+def _kernel_operands(X1, X2, G, out, *, x2_optional: bool = True, zero_new: bool = False, columns_differ: str = _COLUMNS_DIFFER):
     """What the kernel_matrix* wrappers check before they look at the leaf: devices and dtypes, the shapes of X2 (None: K(X1, X1),
     where the wrapper allows it) / G (None: no second factor) / out (allocated when None, zero-filled if `zero_new`), d in
     [1, MAX_D].  Returns (n1, n2, d, out); n1 == 0 or n2 == 0: nothing to compute, the wrapper returns `out` (and X2 = NULL would
@@ -122,34 +124,100 @@ def _x2_args(X2, n2):
     return (X2.data_ptr(), n2, _rowmajor(X2, "X2")) if X2 is not None else (None, n2, 0)
 
 
+# the op names of each kind of leaf and their codes at the C-ABI (include/gpk.h); "k", the row diagonal itself, only in the *_diag entry points
+_STATIONARY_OPS = {"mul": 1, "add": 2, "dr2": 3, "dalpha": 4}
+_DOT_OPS = {"k": 0, "mul": 1, "add": 2, "ds": 3}
+_ARC_OPS = {"k": 0, "mul": 1, "add": 2, "dp": 3}
+_COREGION_OPS = {"k": 0, "mul": 1, "add": 2}
+_LABELS = (1, "the Coregion kernel reads ONE column of task labels")   # a required width and what a message says of it
+
+
+def _check_op(name: str, op: str, allowed) -> None:
+    if op not in allowed:
+        quoted = [repr(o) for o in allowed]
+        raise ValueError(f"{name}: op {op!r} is not {', '.join(quoted[:-1])} or {quoted[-1]}")
+
+
+def _pair_builder(entry: str, X1, X2, G, out, op, codes, leaf, diag_add, lower_only, width=None, x2_optional=True,
+                  columns_differ=_COLUMNS_DIFFER):
+    """The one body of the kernel_matrix* wrappers of every kind of leaf: `_kernel_operands`, the empty-result return, the leaf's
+    C-ABI arguments, the call of `entry` and `_lib.check`.  `op` (None: the entry point takes none) is looked up in `codes`; `leaf()`
+    makes the leaf, whose `abi(d)` gives its arguments, the code in front (leaf.py, the protocol); `diag_add` / `lower_only` None: the
+    entry point has no such argument; G None: no second factor; `x2_optional`, `columns_differ`: as `_kernel_operands` takes them.
+    `width` (`_LABELS`): the kind reads exactly that many columns, its entry points take no `d` and no code, and `leaf()` gives the
+    arguments themselves -- the kind's table on the device, a launch of its own -- whatever the sizes."""
+    lib = _lib.load()
+    n1, n2, d, out = _kernel_operands(X1, X2, G, out, x2_optional=x2_optional, zero_new=lower_only, columns_differ=columns_differ)
+    if width is not None:
+        if d != width[0]:
+            raise ValueError(f"{entry[4:]}: {width[1]}, got {d}")
+        args = leaf()
+    if n1 == 0 or n2 == 0:
+        return out
+    head, dims = (), ()
+    if width is None:
+        args = leaf().abi(d)
+        head, dims, args = args[:1], (d,), args[1:]
+    rc = getattr(lib, entry)(_stream(), *head, *(() if op is None else (codes[op],)), X1.data_ptr(), n1,
+                             _rowmajor(X1, "X1"), *_x2_args(X2, n2), *dims, *args,
+                             *(() if diag_add is None else (float(diag_add),)), *(() if lower_only is None else (int(lower_only),)),
+                             *(() if G is None else (G.data_ptr(), _rowmajor(G, "G"))), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, entry)
+    return out
+
+
+def _row_diagonal(entry: str, name: str, codes, X, g, out, op, leaf, width=None):
+    """The one body of the *_kernel_diag wrappers: the operand checks of a row diagonal over X [n, D] -- the width, the op (the keys
+    of `codes`, "k" first), g given exactly when the op is not "k", g and `out` contiguous [n] -- the empty-result return, the leaf's
+    C-ABI arguments (`leaf`, `width`: as `_pair_builder`), the call of `entry` and `_lib.check`.  `name`: the wrapper's, for the messages."""
+    lib = _lib.load()
+    _chk(X, "X", 2)
+    n, d = X.shape
+    if width is not None and d != width[0]:
+        raise ValueError(f"{name}: {width[1]}, got {d}")
+    if width is None and (d < 1 or d > MAX_D):
+        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
+    _check_op(name, op, codes)
+    if (op == "k") != (g is None):
+        with_g = [repr(o) for o in codes if o != "k"]
+        raise ValueError(f"{name}: g goes with the ops {', '.join(with_g[:-1])} and {with_g[-1]} and only with them")
+    if g is not None:
+        _chk(g, "g", 1)
+        if g.shape[0] != n or not g.is_contiguous():
+            raise ValueError(f"{name}: g must be a contiguous [n]")
+    if width is not None:
+        args = leaf()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=X.device)
+    _chk(out, "out", 1)
+    if out.shape[0] != n or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous [n]")
+    if n == 0:
+        return out
+    head, dims = (), ()
+    if width is None:
+        args = leaf().abi(d)
+        head, dims, args = args[:1], (d,), args[1:]
+    rc = getattr(lib, entry)(_stream(), *head, codes[op], X.data_ptr(), n, _rowmajor(X, "X"), *dims, *args,
+                             None if g is None else g.data_ptr(), out.data_ptr())
+    _lib.check(rc, entry)
+    return out
+
+
 def kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, variance: float, lengthscales,
                   family: str = "SquaredExponential", diag_add: float = 0.0, lower_only: bool = False,
                   alpha=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2]."""
-    lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, None, out, zero_new=lower_only)
-    if n1 == 0 or n2 == 0:
-        return out
-    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
-    rc = lib.gpk_kernel_matrix(_stream(), leaf.code, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, *leaf.host(d),
-                               leaf.variance, float(diag_add), int(lower_only), out.data_ptr(), _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_kernel_matrix")
-    return out
+    return _pair_builder("gpk_kernel_matrix", X1, X2, None, out, None, None,
+                         partial(Leaf, family, variance, lengthscales, alpha=alpha), diag_add, lower_only)
 
 
 def kernel_matrix_hadamard(X1: torch.Tensor, X2: torch.Tensor, G: torch.Tensor, *, variance: float, lengthscales,
                            family: str = "SquaredExponential", alpha=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """G .* K(X1, X2) with K recomputed on the fly -> [n1, n2] (the elementwise factor of the kernel backward)."""
-    lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, G, out, x2_optional=False, columns_differ="inconsistent shapes")
-    if n1 == 0 or n2 == 0:
-        return out
-    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
-    rc = lib.gpk_kernel_matrix_hadamard(_stream(), leaf.code, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d,
-                                        *leaf.host(d), leaf.variance, G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(),
-                                        _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_kernel_matrix_hadamard")
-    return out
+    return _pair_builder("gpk_kernel_matrix_hadamard", X1, X2, G, out, None, None,
+                         partial(Leaf, family, variance, lengthscales, alpha=alpha), None, None,
+                         x2_optional=False, columns_differ="inconsistent shapes")
 
 
 def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, variance: float,
@@ -159,38 +227,17 @@ def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch
     lengthscale / input gradients of a stationary kernel; r2 = scaled squared distance), K recomputed on the fly; `out`
     may be G itself.  X2 None: K(X1, X1); `diag_add` goes onto the diagonal of the combined result ("mul" / "add"), and
     "dr2" writes exact zeros on the diagonal.  op "dalpha" ("RationalQuadratic" only): G .* dK/dalpha, diagonal as "dr2"."""
-    lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, G, out)
-    if n1 == 0 or n2 == 0:
-        return out
-    leaf = Leaf(family, variance, lengthscales, alpha=alpha)
-    rc = lib.gpk_kernel_matrix_combine(_stream(), leaf.code, {"mul": 1, "add": 2, "dr2": 3, "dalpha": 4}[op], X1.data_ptr(), n1,
-                                       _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, *leaf.host(d), leaf.variance,
-                                       float(diag_add), G.data_ptr(), _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_kernel_matrix_combine")
-    return out
+    return _pair_builder("gpk_kernel_matrix_combine", X1, X2, G, out, op, _STATIONARY_OPS,
+                         partial(Leaf, family, variance, lengthscales, alpha=alpha), diag_add, None)
 
 
 # ------------------------------------------------------------------------------------------------ dot-product kernels (dot.hip)
-def _dot_leaf_args(family: str, variance, offset, degree, d: int):
-    """(code, host weights, ard, offset, degree) of the gpk_dot_* entry points for a leaf given by keywords: DotLeaf.host"""
-    leaf = DotLeaf(family, variance, offset=offset, degree=degree)
-    return (leaf.code, *leaf.host(d), float(leaf.offset), int(leaf.degree))
-
-
 def dot_kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, family: str = "Linear", variance, offset=None, degree=None,
                       diag_add: float = 0.0, lower_only: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2] of a dot-product leaf: "Linear" (X1 * variance) X2^T, or
     "Polynomial" (that + offset)^degree.  `variance` one weight or [D].  The symmetric build is exactly symmetric (include/gpk.h)."""
-    lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, None, out, zero_new=lower_only)
-    if n1 == 0 or n2 == 0:
-        return out
-    code, w, ard, off, deg = _dot_leaf_args(family, variance, offset, degree, d)
-    rc = lib.gpk_dot_kernel_matrix(_stream(), code, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, w, ard, off, deg,
-                                   float(diag_add), int(lower_only), out.data_ptr(), _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_dot_kernel_matrix")
-    return out
+    return _pair_builder("gpk_dot_kernel_matrix", X1, X2, None, out, None, None,
+                         partial(DotLeaf, family, variance, offset, degree), diag_add, lower_only)
 
 
 def dot_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, family: str = "Linear", variance,
@@ -198,49 +245,17 @@ def dot_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: t
     """out = G .* K(X1, X2) (op "mul"), G + K(X1, X2) (op "add") or G .* dK/ds (op "ds": s the weighted dot product; Polynomial
     degree (s + offset)^(degree - 1), Linear 1), K recomputed on the fly; `out` may be G itself.  X2 None: K(X1, X1); `diag_add`
     goes onto the diagonal of the combined result ("mul" / "add"); "ds" does NOT zero the diagonal."""
-    if op not in ("mul", "add", "ds"):
-        raise ValueError(f"dot_kernel_matrix_combine: op {op!r} is not 'mul', 'add' or 'ds'")
-    lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, G, out)
-    if n1 == 0 or n2 == 0:
-        return out
-    code, w, ard, off, deg = _dot_leaf_args(family, variance, offset, degree, d)
-    rc = lib.gpk_dot_kernel_matrix_combine(_stream(), code, {"mul": 1, "add": 2, "ds": 3}[op], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
-                                           *_x2_args(X2, n2), d, w, ard, off, deg, float(diag_add), G.data_ptr(), _rowmajor(G, "G"),
-                                           out.data_ptr(), _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_dot_kernel_matrix_combine")
-    return out
+    _check_op("dot_kernel_matrix_combine", op, ("mul", "add", "ds"))
+    return _pair_builder("gpk_dot_kernel_matrix_combine", X1, X2, G, out, op, _DOT_OPS,
+                         partial(DotLeaf, family, variance, offset, degree), diag_add, None)
 
 
 def dot_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op: str = "k", family: str = "Linear", variance, offset=None,
                     degree=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The row diagonal kd [n] of a dot-product leaf over the rows of X [n, D] (op "k"), or g .* kd ("mul"), g + kd ("add"),
     g .* dkd/ds ("ds") with g [n]; `out` may be g.  kd is the diagonal of dot_kernel_matrix(X, None), bit for bit."""
-    lib = _lib.load()
-    _chk(X, "X", 2)
-    n, d = X.shape
-    if d < 1 or d > MAX_D:
-        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
-    if op not in ("k", "mul", "add", "ds"):
-        raise ValueError(f"dot_kernel_diag: op {op!r} is not 'k', 'mul', 'add' or 'ds'")
-    if (op == "k") != (g is None):
-        raise ValueError("dot_kernel_diag: g goes with the ops 'mul', 'add' and 'ds' and only with them")
-    if g is not None:
-        _chk(g, "g", 1)
-        if g.shape[0] != n or not g.is_contiguous():
-            raise ValueError("dot_kernel_diag: g must be a contiguous [n]")
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=X.device)
-    _chk(out, "out", 1)
-    if out.shape[0] != n or not out.is_contiguous():
-        raise ValueError("dot_kernel_diag: out must be a contiguous [n]")
-    if n == 0:
-        return out
-    code, w, ard, off, deg = _dot_leaf_args(family, variance, offset, degree, d)
-    rc = lib.gpk_dot_kernel_diag(_stream(), code, {"k": 0, "mul": 1, "add": 2, "ds": 3}[op], X.data_ptr(), n, _rowmajor(X, "X"), d, w, ard,
-                                 off, deg, None if g is None else g.data_ptr(), out.data_ptr())
-    _lib.check(rc, "gpk_dot_kernel_diag")
-    return out
+    return _row_diagonal("gpk_dot_kernel_diag", "dot_kernel_diag", _DOT_OPS, X, g, out, op,
+                         partial(DotLeaf, family, variance, offset, degree))
 
 
 def dot_adjoint_tail(R: torch.Tensor, A: torch.Tensor, w: torch.Tensor, *, symmetric: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -268,25 +283,12 @@ def dot_adjoint_tail(R: torch.Tensor, A: torch.Tensor, w: torch.Tensor, *, symme
 ARC_TILE = 64   # include/gpk.h: GPK_ARC_TILE
 
 
-def _arc_leaf_args(order, variance, weight_variances, bias_variance, d: int):
-    """(order, host weights, ard, variance, bias) of the gpk_arccos_* entry points for a leaf given by keywords: ArcLeaf.host"""
-    leaf = ArcLeaf(order, variance, weight_variances, bias_variance)
-    return (leaf.order, *leaf.host(d), leaf.variance, leaf.bias_variance)
-
-
 def arccos_kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, order: int = 0, variance=1.0, weight_variances=1.0,
                          bias_variance=1.0, diag_add: float = 0.0, lower_only: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2] of an ArcCosine leaf of order 0, 1 or 2.  `weight_variances`
     one weight or [D].  The symmetric build is exactly symmetric and takes its diagonal by index (include/gpk.h)."""
-    lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, None, out, zero_new=lower_only)
-    if n1 == 0 or n2 == 0:
-        return out
-    order, w, ard, v, b = _arc_leaf_args(order, variance, weight_variances, bias_variance, d)
-    rc = lib.gpk_arccos_kernel_matrix(_stream(), order, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, w, ard, v, b,
-                                      float(diag_add), int(lower_only), out.data_ptr(), _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_arccos_kernel_matrix")
-    return out
+    return _pair_builder("gpk_arccos_kernel_matrix", X1, X2, None, out, None, None,
+                         partial(ArcLeaf, order, variance, weight_variances, bias_variance), diag_add, lower_only)
 
 
 def arccos_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, order: int = 0, variance=1.0,
@@ -294,18 +296,9 @@ def arccos_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G
                                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = G .* K(X1, X2) (op "mul") or G + K(X1, X2) (op "add"), K recomputed on the fly; `out` may be G itself.  X2 None: K(X1, X1)
     with the diagonal by index; `diag_add` goes onto the diagonal of the combined result."""
-    if op not in ("mul", "add"):
-        raise ValueError(f"arccos_kernel_matrix_combine: op {op!r} is not 'mul' or 'add'")
-    lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, G, out)
-    if n1 == 0 or n2 == 0:
-        return out
-    order, w, ard, v, b = _arc_leaf_args(order, variance, weight_variances, bias_variance, d)
-    rc = lib.gpk_arccos_kernel_matrix_combine(_stream(), order, {"mul": 1, "add": 2}[op], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
-                                              *_x2_args(X2, n2), d, w, ard, v, b, float(diag_add), G.data_ptr(), _rowmajor(G, "G"),
-                                              out.data_ptr(), _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_arccos_kernel_matrix_combine")
-    return out
+    _check_op("arccos_kernel_matrix_combine", op, ("mul", "add"))
+    return _pair_builder("gpk_arccos_kernel_matrix_combine", X1, X2, G, out, op, _ARC_OPS,
+                         partial(ArcLeaf, order, variance, weight_variances, bias_variance), diag_add, None)
 
 
 def arccos_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op: str = "k", order: int = 0, variance=1.0,
@@ -313,31 +306,8 @@ def arccos_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op:
     """The row diagonal kd [n] = variance jf p^order (jf = 1, 1, 3) of an ArcCosine leaf over the rows of X [n, D] (op "k"), or
     g .* kd ("mul"), g + kd ("add"), g .* dkd/dp ("dp") with g [n]; `out` may be g.  The closed form: NOT the diagonal of
     arccos_kernel_matrix(X, None) bit for bit (include/gpk.h)."""
-    lib = _lib.load()
-    _chk(X, "X", 2)
-    n, d = X.shape
-    if d < 1 or d > MAX_D:
-        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
-    if op not in ("k", "mul", "add", "dp"):
-        raise ValueError(f"arccos_kernel_diag: op {op!r} is not 'k', 'mul', 'add' or 'dp'")
-    if (op == "k") != (g is None):
-        raise ValueError("arccos_kernel_diag: g goes with the ops 'mul', 'add' and 'dp' and only with them")
-    if g is not None:
-        _chk(g, "g", 1)
-        if g.shape[0] != n or not g.is_contiguous():
-            raise ValueError("arccos_kernel_diag: g must be a contiguous [n]")
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=X.device)
-    _chk(out, "out", 1)
-    if out.shape[0] != n or not out.is_contiguous():
-        raise ValueError("arccos_kernel_diag: out must be a contiguous [n]")
-    if n == 0:
-        return out
-    order, w, ard, v, b = _arc_leaf_args(order, variance, weight_variances, bias_variance, d)
-    rc = lib.gpk_arccos_kernel_diag(_stream(), order, {"k": 0, "mul": 1, "add": 2, "dp": 3}[op], X.data_ptr(), n, _rowmajor(X, "X"), d, w,
-                                    ard, v, b, None if g is None else g.data_ptr(), out.data_ptr())
-    _lib.check(rc, "gpk_arccos_kernel_diag")
-    return out
+    return _row_diagonal("gpk_arccos_kernel_diag", "arccos_kernel_diag", _ARC_OPS, X, g, out, op,
+                         partial(ArcLeaf, order, variance, weight_variances, bias_variance))
 
 
 def arccos_adjoint_parts(n1: int, n2: int, device_=None) -> torch.Tensor:
@@ -360,7 +330,7 @@ def arccos_adjoint_stage(X1: torch.Tensor, X2: Optional[torch.Tensor], Kbar: tor
         raise ValueError(f"arccos_adjoint_stage: parts must be a contiguous [>= {tc * n1 + tr * n2 + tr * tc}] (ops.arccos_adjoint_parts)")
     if n1 == 0 or n2 == 0:
         return out
-    order, w, ard, v, b = _arc_leaf_args(order, variance, weight_variances, bias_variance, d)
+    order, w, ard, v, b = ArcLeaf(order, variance, weight_variances, bias_variance).abi(d)
     rc = lib.gpk_arccos_adjoint_stage(_stream(), order, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, w, ard, v, b,
                                       Kbar.data_ptr(), _rowmajor(Kbar, "Kbar"), out.data_ptr(), _rowmajor(out, "out"), parts.data_ptr())
     _lib.check(rc, "gpk_arccos_adjoint_stage")
@@ -608,11 +578,10 @@ def coregion_output_covariance(W, kappa, *, device_=None, out: Optional[torch.Te
                    lambda: build(torch.empty((P, P), dtype=torch.float64, device=dev)))
 
 
-def _label_columns(X1, X2, G, out, what: str, zero_new: bool = False):
-    n1, n2, d, out = _kernel_operands(X1, X2, G, out, zero_new=zero_new)
-    if d != 1:
-        raise ValueError(f"{what}: the Coregion kernel reads ONE column of task labels, got {d}")
-    return n1, n2, out
+def _coregion_table(W, kappa, X):
+    """what a Coregion leaf hands `_pair_builder` / `_row_diagonal` for `leaf()`: (pointer, leading dimension, P) of B on X's device"""
+    B = coregion_output_covariance(W, kappa, device_=X.device)
+    return B.data_ptr(), B.shape[1], B.shape[0]
 
 
 def coregion_kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, W, kappa, diag_add: float = 0.0, lower_only: bool = False,
@@ -620,64 +589,25 @@ def coregion_kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, W, k
     """K(X1, X2)[i, k] = B[l_i, l'_k] (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2] over the label columns X1 [n1, 1],
     X2 [n2, 1]; W [P, R], kappa [P] host arrays.  Exact: the bits of B; exactly symmetric; an invalid label (include/gpk.h) makes its row /
     column NaN."""
-    lib = _lib.load()
-    n1, n2, out = _label_columns(X1, X2, None, out, "coregion_kernel_matrix", zero_new=lower_only)
-    B = coregion_output_covariance(W, kappa, device_=X1.device)
-    if n1 == 0 or n2 == 0:
-        return out
-    rc = lib.gpk_coregion_kernel_matrix(_stream(), X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), B.data_ptr(), B.shape[1],
-                                        B.shape[0], float(diag_add), int(lower_only), out.data_ptr(), _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_coregion_kernel_matrix")
-    return out
+    return _pair_builder("gpk_coregion_kernel_matrix", X1, X2, None, out, None, None, partial(_coregion_table, W, kappa, X1),
+                         diag_add, lower_only, _LABELS)
 
 
 def coregion_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, W, kappa,
                                    diag_add: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = G .* K(X1, X2) (op "mul") or G + K(X1, X2) (op "add"), K gathered on the fly; `out` may be G itself.  X2 None: K(X1, X1),
     `diag_add` goes onto the diagonal of the combined result."""
-    if op not in ("mul", "add"):
-        raise ValueError(f"coregion_kernel_matrix_combine: op {op!r} is not 'mul' or 'add'")
-    lib = _lib.load()
-    n1, n2, out = _label_columns(X1, X2, G, out, "coregion_kernel_matrix_combine")
-    B = coregion_output_covariance(W, kappa, device_=X1.device)
-    if n1 == 0 or n2 == 0:
-        return out
-    rc = lib.gpk_coregion_kernel_matrix_combine(_stream(), {"mul": 1, "add": 2}[op], X1.data_ptr(), n1, _rowmajor(X1, "X1"),
-                                                *_x2_args(X2, n2), B.data_ptr(), B.shape[1], B.shape[0], float(diag_add), G.data_ptr(),
-                                                _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
-    _lib.check(rc, "gpk_coregion_kernel_matrix_combine")
-    return out
+    _check_op("coregion_kernel_matrix_combine", op, ("mul", "add"))
+    return _pair_builder("gpk_coregion_kernel_matrix_combine", X1, X2, G, out, op, _COREGION_OPS, partial(_coregion_table, W, kappa, X1),
+                         diag_add, None, _LABELS)
 
 
 def coregion_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op: str = "k", W, kappa,
                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The row diagonal kd [n] = B[l_i, l_i] over the label column X [n, 1] (op "k"), or g .* kd ("mul"), g + kd ("add") with g [n];
     `out` may be g.  Read from B: bit for bit the diagonal of coregion_kernel_matrix(X, None)."""
-    lib = _lib.load()
-    _chk(X, "X", 2)
-    n, d = X.shape
-    if d != 1:
-        raise ValueError(f"coregion_kernel_diag: the Coregion kernel reads ONE column of task labels, got {d}")
-    if op not in ("k", "mul", "add"):
-        raise ValueError(f"coregion_kernel_diag: op {op!r} is not 'k', 'mul' or 'add'")
-    if (op == "k") != (g is None):
-        raise ValueError("coregion_kernel_diag: g goes with the ops 'mul' and 'add' and only with them")
-    if g is not None:
-        _chk(g, "g", 1)
-        if g.shape[0] != n or not g.is_contiguous():
-            raise ValueError("coregion_kernel_diag: g must be a contiguous [n]")
-    B = coregion_output_covariance(W, kappa, device_=X.device)
-    if out is None:
-        out = torch.empty(n, dtype=torch.float64, device=X.device)
-    _chk(out, "out", 1)
-    if out.shape[0] != n or not out.is_contiguous():
-        raise ValueError("coregion_kernel_diag: out must be a contiguous [n]")
-    if n == 0:
-        return out
-    rc = lib.gpk_coregion_kernel_diag(_stream(), {"k": 0, "mul": 1, "add": 2}[op], X.data_ptr(), n, _rowmajor(X, "X"), B.data_ptr(),
-                                      B.shape[1], B.shape[0], None if g is None else g.data_ptr(), out.data_ptr())
-    _lib.check(rc, "gpk_coregion_kernel_diag")
-    return out
+    return _row_diagonal("gpk_coregion_kernel_diag", "coregion_kernel_diag", _COREGION_OPS, X, g, out, op,
+                         partial(_coregion_table, W, kappa, X), _LABELS)
 
 
 def coregion_onehot_rows(X: torch.Tensor, n_outputs: int) -> torch.Tensor:
