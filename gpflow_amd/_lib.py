@@ -126,6 +126,15 @@ _SIGS = {
     "gpk_coregion_kernel_diag": (c_int, [c_void_p, c_int, _dp, c_int, c_long, _dp, c_long, c_int, _dp, _dp]),
     "gpk_coregion_onehot_rows": (c_int, [c_void_p, _dp, c_int, c_long, c_int, _dp, c_long]),
     "gpk_coregion_adjoint_tail": (c_int, [c_void_p, _dp, c_long, _dp, c_long, c_int, c_int, _dp, c_long, _dp]),
+    "gpk_conv_kfu": (c_int, [c_void_p, _dp, c_int, c_long, c_int, c_int, c_int, c_int, c_int, _dp, c_int, c_long, _dp, c_double, c_double,
+                             _dp, c_long]),
+    "gpk_conv_kdiag": (c_int, [c_void_p, _dp, c_int, c_long, c_int, c_int, c_int, c_int, c_int, _dp, c_double, c_double, _dp]),
+    "gpk_conv_kfu_partials_len": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gpk_conv_kfu_adjoint": (c_int, [c_void_p, _dp, c_int, c_long, c_int, c_int, c_int, c_int, c_int, _dp, c_int, c_long, _dp, c_double,
+                                     c_double, _dp, c_long, _dp, _dp, _dp, c_long, _dp]),
+    "gpk_conv_kdiag_partials_len": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gpk_conv_kdiag_adjoint": (c_int, [c_void_p, _dp, c_int, c_long, c_int, c_int, c_int, c_int, c_int, _dp, c_double, c_double, _dp, _dp,
+                                       _dp, _dp]),
     "gpk_tril_product_tiles": (c_int, [c_int]),
     "gpk_tril_product": (c_int, [c_void_p, _dp, c_int, c_long, _dp, c_long, c_long, c_int, _dp, _dp, _dp, _dp, c_long, c_long]),
     "gpk_adam_step": (c_int, [c_void_p, _dp, _dp, _dp, _dp, c_long, c_double, c_double, c_double, c_double, c_int]),

@@ -6,7 +6,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from .inducing_variables import (InducingPoints, SeparateIndependentInducingVariables,
+from .inducing_variables import (InducingPatches, InducingPoints, SeparateIndependentInducingVariables,
                                  SharedIndependentInducingVariables)
 from .kernels import Kernel, LinearCoregionalization, MultioutputKernel, SeparateIndependent, SharedIndependent
 
@@ -36,9 +36,21 @@ def _pairs(inducing_variable, kernel):
     return list(zip(zs, ks))
 
 
+def patch_pair(inducing_variable, kernel) -> bool:
+    """True for (InducingPatches, Convolutional) -- kuus.py / kufs.py register exactly this pair -- and NotImplementedError for either
+    half with anything else, before the device is touched"""
+    patches, conv = isinstance(inducing_variable, InducingPatches), bool(getattr(kernel, "patch_kernel", False))
+    if patches != conv:
+        raise NotImplementedError(f"Kuu/Kuf: ({type(inducing_variable).__name__}, {type(kernel).__name__}) -- a Convolutional kernel "
+                                  "goes with InducingPatches, and InducingPatches with no other kernel")
+    return patches
+
+
 def Kuu(inducing_variable, kernel, *, jitter: float = 0.0) -> torch.Tensor:
     """[M,M] (InducingPoints x Kernel: kuus.py:24-34; Shared x Shared: multioutput/kuus.py:49-62)
     or [L,M,M] (any Separate combination: multioutput/kuus.py:65-121)."""
+    if patch_pair(inducing_variable, kernel):
+        return kernel.Kuu_into(inducing_variable.Z.device_value(), None, diag_add=jitter)
     if isinstance(inducing_variable, InducingPoints) and not isinstance(kernel, MultioutputKernel):
         Z = inducing_variable.Z.device_value()
         Zs, _ = kernel.slice(Z, None)
@@ -51,6 +63,8 @@ def Kuu(inducing_variable, kernel, *, jitter: float = 0.0) -> torch.Tensor:
 
 def Kfu(inducing_variable, kernel, Xnew) -> torch.Tensor:
     """K(Xnew, Z): the row-major [N,M] (or [L,N,M]) layout the device solves consume."""
+    if patch_pair(inducing_variable, kernel):   # (a half pair is refused here, before Xnew is copied to the device)
+        return kernel.Kfu_into(ops.to_device(Xnew), inducing_variable.Z.device_value(), None)
     Xnew = ops.to_device(Xnew)
     if isinstance(inducing_variable, InducingPoints) and not isinstance(kernel, MultioutputKernel):
         Z = inducing_variable.Z.device_value()

@@ -912,6 +912,71 @@ class KernelSpec:
         return {"changepoints": out}
 
 
+class PatchSpec:
+    """kernels.Convolutional over InducingPatches as the reverse pass sees it: the calls `_factorise`, `_knn_terms`, `_covariance_tail`
+    and `kernel_grads` make, answered from three places.  Kuu = k(Z, Z) and its adjoint are the base leaf's -- a one-member KernelSpec,
+    `base` --; Kfu, its adjoint and the row diagonal are the patch-response kernels (ops.conv_*).  The calls are told apart by ROLE:
+    `build(Z, None)` / `adjoint(.., symmetric=True)` is Kuu, `build(X, Z)` / `adjoint(Z, X, Kuf_bar, symmetric=False)` is Kfu; no
+    shape is compared (patch_len may equal the image width).  d/dweights does not fit the per-member lists: the two conv adjoints add
+    it up on the spec from `warm()` on, and `kernel_grads` hands it out under "weights"."""
+    constant_diagonal = False
+    packable = False
+    n = 1
+
+    def __init__(self, leaf: Leaf, geometry, weights):
+        self.base = KernelSpec([leaf])
+        self.geometry, self.weights = tuple(geometry), np.asarray(weights, dtype=np.float64).reshape(-1)
+        self.members, self.tree, self.cols, self.periods, self.nodes = self.base.members, 0, [None], [None], []
+        self._dw = None
+
+    def _kw(self) -> dict:
+        leaf = self.members[0]
+        return dict(geometry=self.geometry, weights=self.weights, variance=leaf.variance, lengthscales=float(np.asarray(leaf.lengthscales).reshape(-1)[0]))
+
+    def warm(self, device, D: int) -> "PatchSpec":
+        self.base.warm(device, D)                      # (D: the width of Z, patch_len)
+        ops.conv_weights_device(self.weights, device)
+        self._dw = None
+        return self
+
+    def build(self, X1, X2, out=None, diag_add: float = 0.0):
+        if X2 is None:
+            return self.base.build(X1, None, out, diag_add)
+        return ops.conv_kfu(X1, X2, out=out, **self._kw())
+
+    def kdiag_rows(self, X) -> torch.Tensor:
+        return ops.conv_kdiag(X, **self._kw())
+
+    def _add_dw(self, dw) -> None:
+        self._dw = dw if self._dw is None else self._dw + dw
+
+    def adjoint(self, A, Bm, Kbar, symmetric: bool):
+        if symmetric:
+            return self.base.adjoint(A, Bm, Kbar, True)
+        dv, dl, dZ, dw = ops.conv_kfu_adjoint(Bm, A, ops.transpose(Kbar if Kbar.is_contiguous() else Kbar.contiguous()), **self._kw())
+        self._add_dw(dw)
+        return [dv], [dl], dZ
+
+    def diag_adjoint(self, X, kd_bar):
+        dv, dl, dw = ops.conv_kdiag_adjoint(X, kd_bar.contiguous(), **self._kw())
+        self._add_dw(dw)
+        return [dv], [dl]
+
+    def kdiag(self):
+        raise NotImplementedError("a Convolutional kernel's K(x, x) depends on the image: kdiag_rows")
+
+    dkdiag = kdiag
+    pack = KernelSpec.pack
+    n_variance = property(lambda self: self.base.n_variance)
+    parameter_names = property(lambda self: self.base.parameter_names)
+    n_shape = property(lambda self: self.base.n_shape)
+    split_shape = property(lambda self: self.base.split_shape)
+
+    def kernel_grads(self, g_var, g_shape) -> dict:
+        dw, self._dw = self._dw, None
+        return {**self.base.kernel_grads(g_var, g_shape), "weights": dw if dw is not None else torch.zeros(self.weights.size, dtype=torch.float64)}
+
+
 class _Seed:
     """The seeds of the data term  scale * sum_bp var_exp(fmean_bp, fvar_bp):  r = dF/dfmean [B, P]  and  c = dF/dfvar  in the form
     the likelihood gives it:
@@ -1180,12 +1245,14 @@ def svgp_elbo_and_grad(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_mu
     spec.warm(dev, D)   # (device copies of the lengthscales BEFORE the first kernel is enqueued: see ls_device)
 
     # ---------------------------------------------------------------- forward (intermediates kept)
-    if likelihood is not None and not spec.constant_diagonal:
+    patch = isinstance(spec, PatchSpec)   # (its row diagonal enters the likelihood stage as _knn_terms puts it into the Gaussian one)
+    if likelihood is not None and not spec.constant_diagonal and not patch:
         raise NotImplementedError(_ROW_DIAGONAL + "the quadrature likelihoods' reverse pass")
     fwd = _svgp_forward(spec, Z, Xb, q_mu, q_sqrt, jitter)
     s0, fmean, ssq = fwd.s0, fwd.fmean, fwd.ssq
     if likelihood is not None:
-        ve, dmu, dvar, lik_grads = _likelihood_stage(likelihood, Yb, fmean, s0=s0, ssq=ssq, knn=[spec.kdiag()], mean_const=mean_const)
+        knn, s0_knn = _knn_terms(spec, Xb, s0)[:2] if patch else ([spec.kdiag()], s0)
+        ve, dmu, dvar, lik_grads = _likelihood_stage(likelihood, Yb, fmean, s0=s0_knn, ssq=ssq, knn=knn, mean_const=mean_const)
     else:
         knn, s0_knn, kd = _knn_terms(spec, Xb, s0)
         ve, _ = ops.gaussian_varexp_sum(Yb, fmean, s0=s0_knn, ssq=ssq, knn=knn, noise_variance=noise_variance,

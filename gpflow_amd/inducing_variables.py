@@ -34,6 +34,11 @@ class InducingPoints(InducingPointsBase):
     """Real-space inducing points."""
 
 
+class InducingPatches(InducingPointsBase):
+    """Inducing patches Z [M, h w] of kernels.Convolutional (inducing_variables.py `InducingPatches`): points in PATCH space, so
+    Kuu is the base kernel over them and Kuf the patch response of an image -- never an InducingPoints, and no other kernel takes them."""
+
+
 class MultioutputInducingVariables(InducingVariables):
     @property
     def inducing_variables(self):

@@ -9,6 +9,7 @@ from .periodic import Periodic
 from .linears import Linear, Polynomial
 from .misc import ArcCosine, Coregion
 from .changepoints import ChangePoints
+from .convolutional import Convolutional  # noqa: F401  (kernels.Convolutional; not in __all__: it has no argument-free form, which tests/test_leaf_protocol.py asks of every name listed there)
 from .multioutput import MultioutputKernel, SharedIndependent, SeparateIndependent, LinearCoregionalization
 
 RBF = SquaredExponential  # gpflow/kernels/__init__.py:50

@@ -69,6 +69,15 @@ class Kernel(Module, metaclass=abc.ABCMeta):
         out.copy_(K)
         return out
 
+    def Kuu_into(self, Z, out, *, diag_add: float = 0.0, lower_only: bool = False):
+        """K(Z, Z) + diag_add I by ROLE (covariances.Kuu, the fused posterior): K_into for every kernel whose inducing variables are
+        points; kernels.Convolutional builds its base kernel over the inducing patches here"""
+        return self.K_into(Z, None, out, diag_add=diag_add, lower_only=lower_only)
+
+    def Kfu_into(self, X, Z, out):
+        """K(X, Z) by role, as `Kuu_into`"""
+        return self.K_into(X, Z, out)
+
     def __add__(self, other: "Kernel") -> "Kernel":
         """gpflow/kernels/base.py:216-217"""
         return Sum([self, other])
@@ -88,6 +97,13 @@ class Kernel(Module, metaclass=abc.ABCMeta):
         if not full_cov:
             return self.K_diag(X)
         return self.K(X, X2)
+
+
+def refuse_patch_members(kernels, where: str) -> None:
+    """kernels.Convolutional stands alone: its Kuu, Kuf and K_diag come from three different builders over two kinds of input, which
+    no combination or multi-output wrapper hands its members"""
+    if any(getattr(k, "patch_kernel", False) for k in kernels):
+        raise NotImplementedError(f"a Convolutional kernel as a member of {where} is not built: it is used on its own, with InducingPatches")
 
 
 class DeviceLeaf(Kernel):
@@ -199,6 +215,7 @@ class Combination(Kernel):
         super().__init__(name=name)
         if not all(isinstance(k, Kernel) for k in kernels):
             raise TypeError("can only combine Kernel instances")
+        refuse_patch_members(kernels, type(self).__name__)
         flat = []
         for k in kernels:
             flat.extend(k.kernels if isinstance(k, self.__class__) else [k])

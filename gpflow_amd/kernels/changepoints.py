@@ -20,7 +20,7 @@ import torch
 
 from ..base import Parameter, positive
 from .. import ops
-from .base import Combination, Kernel
+from .base import Combination, Kernel, refuse_patch_members
 
 
 class ChangePoints(Combination):
@@ -37,6 +37,7 @@ class ChangePoints(Combination):
         kernels = list(kernels)
         if not all(isinstance(k, Kernel) for k in kernels):
             raise TypeError("can only combine Kernel instances")
+        refuse_patch_members(kernels, "ChangePoints")
         loc = np.asarray(locations, dtype=np.float64)
         if loc.ndim > 1 or len(kernels) != loc.size + 1:
             raise ValueError(f"ChangePoints: {len(kernels)} kernels need {len(kernels) - 1} locations, got {loc.size}")

@@ -7,7 +7,7 @@ import torch
 
 from .. import ops
 from ..base import Parameter
-from .base import Kernel
+from .base import Kernel, refuse_patch_members
 
 
 class MultioutputKernel(Kernel):
@@ -35,6 +35,7 @@ class SharedIndependent(MultioutputKernel):
 
     def __init__(self, kernel: Kernel, output_dim: int):
         super().__init__()
+        refuse_patch_members([kernel], type(self).__name__)
         self.kernel = kernel
         self.output_dim = int(output_dim)
 
@@ -66,6 +67,7 @@ class SeparateIndependent(MultioutputKernel):
 
     def __init__(self, kernels: Sequence[Kernel], name: Optional[str] = None):
         super().__init__(name=name)
+        refuse_patch_members(kernels, type(self).__name__)
         self.kernels = list(kernels)
 
     @property
@@ -93,6 +95,7 @@ class LinearCoregionalization(MultioutputKernel):
 
     def __init__(self, kernels: Sequence[Kernel], W, name: Optional[str] = None):
         super().__init__(name=name)
+        refuse_patch_members(kernels, type(self).__name__)
         self.kernels = list(kernels)
         self.W = Parameter(W)  # [P, L]
 

@@ -8,7 +8,7 @@ import torch
 
 from .. import gradients
 from ..base import FillTriangular
-from ..inducing_variables import (InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
+from ..inducing_variables import (InducingPatches, InducingPoints, SeparateIndependentInducingVariables, SharedIndependentInducingVariables)
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
 from ..kernels.base import Combination, changepoint_nodes, gradient_spec, has_row_diagonal_leaf, reverse_leaf
 from ..kernels.periodic import Periodic
@@ -73,13 +73,21 @@ class CovarianceRoute:
       a Sum / Product of them, flat or nested: kernels.base.gradient_spec -- the spec slices for its members itself.
     Anything else raises NotImplementedError."""
 
-    def __init__(self, kernel, input_dim=None):
+    def __init__(self, kernel, input_dim=None, patches: bool = False):
         self.kernel = kernel
+        self.patch = bool(getattr(kernel, "patch_kernel", False))
+        if self.patch and not patches:   # (every caller but svgp_routes: a route over K(X, X) or over InducingPoints)
+            raise NotImplementedError("gradients: a Convolutional kernel is built into SVGP.elbo_and_grad over InducingPatches only -- GPR, "
+                                      "SGPR and VGP need the full K(X, X2), SVGPTrainer and the natural gradients the packed one-kernel form")
         self._columns_of = kernel.base_kernel if isinstance(kernel, Periodic) else kernel   # whose `slice` selects columns and no more
         self.is_combination = isinstance(kernel, Combination)
         self.nodes = [k.node_params() for k in changepoint_nodes(kernel)]   # (locations, steepness) per ChangePoints node, in node order
         if self.is_combination:
             self.spec, self.members = gradient_spec(kernel, input_dim)
+            return
+        if self.patch:   # Kuu from the base leaf, Kfu and the row diagonal from the patch-response kernels (gradients.PatchSpec)
+            base = kernel.base_kernel
+            self.spec, self.members = gradients.PatchSpec(base.leaf(), kernel.geometry, kernel.weights.numpy()), [base.leaf_params()]
             return
         found = reverse_leaf(kernel, input_dim)
         if found is None:
@@ -123,6 +131,8 @@ class CovarianceRoute:
                  for i, (pars, grs) in enumerate(zip(self.members, self.member_grads(g))) for j, (par, gr) in enumerate(zip(pars, grs))]
         for (loc, steep), gn in zip(self.nodes, g.get("changepoints", [])):   # a ChangePoints node's own Parameters, in node order
             pairs += [(loc, gn["locations"].cpu().numpy()), (steep, gn["steepness"].cpu().numpy().reshape(steep.numpy().shape))]
+        if self.patch:
+            pairs.append((self.kernel.weights, g["weights"].cpu().numpy()))
         return pairs
 
 
@@ -188,6 +198,10 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
             raise NotImplementedError(f"gradients: {ROW_DIAGONAL} is not built into {limit}")
     if isinstance(k, LinearCoregionalization):
         return _lcm_routes(model, quadrature=quadrature, narrow=narrow)
+    patch = bool(getattr(k, "patch_kernel", False))
+    if patch and narrow:
+        raise NotImplementedError("gradients: a Convolutional kernel is not built into the natural gradients (the packed one-kernel "
+                                  "reverse pass with a scalar K(x, x))")
     plain = not (quadrature or narrow)
     lik_ok = (model.whiten and (model._device_likelihood() or model._switched_likelihood())) if quadrature \
         else _gaussian_noise(model.likelihood, not narrow)
@@ -204,13 +218,15 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
         elif not plain:
             ok = ok and pairs[0][0].has_default_active_dims
     c = model.mean_function.constant_value()
-    if not (ok and lik_ok and c is not None and all(isinstance(v, InducingPoints) for _, v in pairs)):
+    # (a Convolutional kernel goes with InducingPatches, every other kernel with InducingPoints: covariances.patch_pair)
+    iv_ok = all(isinstance(v, InducingPatches if getattr(kk, "patch_kernel", False) else InducingPoints) for kk, v in pairs)
+    if not (ok and lik_ok and c is not None and iv_ok):
         raise NotImplementedError(
             "gradients: SVGP over InducingPoints with a constant mean and a SquaredExponential / Matern kernel (shared by independent "
             "latents, or one per latent with a full q_sqrt) or a Sum / Product of them, and a Gaussian likelihood -- or, whitened with one "
             "kernel over all input columns and at most 16 latents, a Bernoulli / Poisson / StudentT / MultiClass likelihood; natural "
             "gradients: one kernel over all input columns, full q_sqrt, constant noise")
-    return [(CovarianceRoute(kk, int(v.Z.shape[1])), v) for kk, v in pairs], float(c), separate
+    return [(CovarianceRoute(kk, int(v.Z.shape[1]), patches=True), v) for kk, v in pairs], float(c), separate
 
 
 def _latent_inducing_points(iv, n):

@@ -1629,3 +1629,121 @@ def svgp_elbo_shard_lik(Z: torch.Tensor, Xb: torch.Tensor, Yb: torch.Tensor, q_m
                                      ws.data_ptr(), ws.numel() * 8)
     _lib.check(rc, "gpk_svgp_elbo_shard_lik")
     return out, info
+
+
+# ------------------------------------------------------------------------------------------------ Convolutional kernel (conv/conv.hip)
+CONV_MAX_PIXELS, CONV_MBLOCK = 4096, 64   # include/gpk.h: GPK_CONV_MAX_PIXELS, GPK_CONV_MBLOCK
+
+
+def conv_geometry(image_shape, patch_shape, colour_channels: int = 1) -> Tuple[int, int, int, int, int]:
+    """(H, W, C, h, w) checked against the limits of include/gpk.h -- a ValueError before anything touches the device"""
+    if len(tuple(image_shape)) != 2 or len(tuple(patch_shape)) != 2:
+        raise ValueError("Convolutional: image_shape is [H, W] and patch_shape [h, w]")
+    (H, W), (h, w), C = (int(s) for s in image_shape), (int(s) for s in patch_shape), int(colour_channels)
+    if min(H, W, C) < 1 or not (1 <= h <= H and 1 <= w <= W):
+        raise ValueError(f"Convolutional: a patch [{h}, {w}] must fit the image [{H}, {W}] (1 <= h <= H, 1 <= w <= W), colour_channels >= 1")
+    if H * W * C > CONV_MAX_PIXELS:
+        raise ValueError(f"Convolutional: an image of {H * W * C} values does not fit the staged image (H W C <= {CONV_MAX_PIXELS})")
+    if h * w > MAX_D:
+        raise ValueError(f"Convolutional: a patch of {h * w} values exceeds the builder's width (h w <= {MAX_D})")
+    return H, W, C, h, w
+
+
+def conv_num_patches(geometry) -> int:
+    H, W, C, h, w = geometry
+    return C * (H - h + 1) * (W - w + 1)
+
+
+def conv_weights_device(weights, dev) -> torch.Tensor:
+    """the patch weights [P] on the device, found by value (see `_cached`)"""
+    a = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    return _cached(("conv_w", a.shape, a.tobytes(), str(dev)), lambda: torch.as_tensor(a.copy(), device=dev))
+
+
+def _conv_operands(name, X, geometry, weights, lengthscale):
+    _chk(X, "X", 2)
+    H, W, C, h, w = geometry
+    P = conv_num_patches(geometry)
+    if X.shape[1] != H * W * C:
+        raise ValueError(f"{name}: X must be [N, {H * W * C}] (images [{H}, {W}, {C}] flattened), got {tuple(X.shape)}")
+    if np.size(weights) != P:
+        raise ValueError(f"{name}: weights must be [{P}], one per patch")
+    if np.ndim(lengthscale) != 0:
+        raise ValueError(f"{name}: one scalar lengthscale")
+    return conv_weights_device(weights, X.device), P
+
+
+def _conv_z(name, Z, geometry):
+    _chk(Z, "Z", 2)
+    if Z.shape[1] != geometry[3] * geometry[4]:
+        raise ValueError(f"{name}: Z must be [M, {geometry[3] * geometry[4]}] (inducing patches), got {tuple(Z.shape)}")
+
+
+def conv_kfu(X: torch.Tensor, Z: torch.Tensor, *, geometry, weights, variance, lengthscales, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Kfu [N, M] = (1 / P) sum_p w_p k(z_m, x_n^[p]) of the images X [N, H W C] and the inducing patches Z [M, h w]
+    (include/gpk.h: gpk_conv_kfu); `out` [N, M] with any leading dimension."""
+    lib = _lib.load()
+    wd, _ = _conv_operands("conv_kfu", X, geometry, weights, lengthscales)
+    _conv_z("conv_kfu", Z, geometry)
+    N, M = X.shape[0], Z.shape[0]
+    if out is None:
+        out = torch.empty((N, M), dtype=torch.float64, device=X.device)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (N, M):
+        raise ValueError(f"conv_kfu: out must be [{N}, {M}]")
+    if N == 0 or M == 0:
+        return out
+    rc = lib.gpk_conv_kfu(_stream(), X.data_ptr(), N, _rowmajor(X, "X"), *geometry, Z.data_ptr(), M, _rowmajor(Z, "Z"), wd.data_ptr(),
+                          float(variance), float(lengthscales), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_conv_kfu")
+    return out
+
+
+def conv_kdiag(X: torch.Tensor, *, geometry, weights, variance, lengthscales) -> torch.Tensor:
+    """K_diag [N] = (1 / P^2) sum_{p,q} w_p w_q k(x_n^[p], x_n^[q]) (gpk_conv_kdiag)"""
+    lib = _lib.load()
+    wd, _ = _conv_operands("conv_kdiag", X, geometry, weights, lengthscales)
+    out = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+    if X.shape[0]:
+        rc = lib.gpk_conv_kdiag(_stream(), X.data_ptr(), X.shape[0], _rowmajor(X, "X"), *geometry, wd.data_ptr(), float(variance),
+                                float(lengthscales), out.data_ptr())
+        _lib.check(rc, "gpk_conv_kdiag")
+    return out
+
+
+def conv_kfu_adjoint(X: torch.Tensor, Z: torch.Tensor, G: torch.Tensor, *, geometry, weights, variance, lengthscales):
+    """(d/dvariance [1], d/dlengthscales [1], dZ [M, h w], d/dweights [P]) from G = dF/dKfu [N, M] (gpk_conv_kfu_adjoint: a recompute
+    stage with typed partials sized by gpk_conv_kfu_partials_len, and one tail launch; bit-identical when repeated)"""
+    lib = _lib.load()
+    wd, P = _conv_operands("conv_kfu_adjoint", X, geometry, weights, lengthscales)
+    _conv_z("conv_kfu_adjoint", Z, geometry)
+    _chk(G, "G", 2)
+    N, M = X.shape[0], Z.shape[0]
+    if tuple(G.shape) != (N, M):
+        raise ValueError(f"conv_kfu_adjoint: G must be [{N}, {M}]")
+    parts = torch.empty(max(int(lib.gpk_conv_kfu_partials_len(N, M, *geometry)), 1), dtype=torch.float64, device=X.device)
+    small = torch.empty(2, dtype=torch.float64, device=X.device)
+    dZ = torch.empty((M, Z.shape[1]), dtype=torch.float64, device=X.device)
+    dw = torch.empty(P, dtype=torch.float64, device=X.device)
+    rc = lib.gpk_conv_kfu_adjoint(_stream(), X.data_ptr(), N, _rowmajor(X, "X"), *geometry, Z.data_ptr(), M, _rowmajor(Z, "Z"),
+                                  wd.data_ptr(), float(variance), float(lengthscales), G.data_ptr(), _rowmajor(G, "G"), parts.data_ptr(),
+                                  small.data_ptr(), dZ.data_ptr(), _rowmajor(dZ, "dZ"), dw.data_ptr())
+    _lib.check(rc, "gpk_conv_kfu_adjoint")
+    return small[:1], small[1:], dZ, dw
+
+
+def conv_kdiag_adjoint(X: torch.Tensor, c: torch.Tensor, *, geometry, weights, variance, lengthscales):
+    """(d/dvariance [1], d/dlengthscales [1], d/dweights [P]) from c = dF/dK_diag [N] (gpk_conv_kdiag_adjoint)"""
+    lib = _lib.load()
+    wd, P = _conv_operands("conv_kdiag_adjoint", X, geometry, weights, lengthscales)
+    _chk(c, "c", 1)
+    N = X.shape[0]
+    if c.numel() != N or not c.is_contiguous():
+        raise ValueError(f"conv_kdiag_adjoint: c must be a contiguous [{N}]")
+    parts = torch.empty(max(int(lib.gpk_conv_kdiag_partials_len(N, *geometry)), 1), dtype=torch.float64, device=X.device)
+    small = torch.empty(2, dtype=torch.float64, device=X.device)
+    dw = torch.empty(P, dtype=torch.float64, device=X.device)
+    rc = lib.gpk_conv_kdiag_adjoint(_stream(), X.data_ptr(), N, _rowmajor(X, "X"), *geometry, wd.data_ptr(), float(variance),
+                                    float(lengthscales), c.data_ptr(), parts.data_ptr(), small.data_ptr(), dw.data_ptr())
+    _lib.check(rc, "gpk_conv_kdiag_adjoint")
+    return small[:1], small[1:], dw

@@ -371,8 +371,8 @@ class IndependentPosterior(BasePosterior):
         Xs, Zs = kernel.slice(Xf, Z)
         M, N = Zs.shape[0], Xs.shape[0]
         T = torch.empty((M + N, M), dtype=torch.float64, device=Zs.device)
-        kernel.K_into(Zs, None, T[:M], diag_add=config.default_jitter(), lower_only=True)
-        kernel.K_into(Xs, Zs, T[M:])
+        kernel.Kuu_into(Zs, T[:M], diag_add=config.default_jitter(), lower_only=True)
+        kernel.Kfu_into(Xs, Zs, T[M:])
         invd, info = ops.potrf_(T, M, zero_upper=True)
         ops.check_info(info)
         fac, q_mu, q_sqrt = Factor(T[:M], invd), self.q_mu, self.q_sqrt
@@ -385,6 +385,7 @@ class IndependentPosteriorSingleOutput(IndependentPosterior):
     """posteriors.py:825-841"""
 
     def _conditional_fused(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        covariances.patch_pair(self.X_data, self.kernel)   # (a Convolutional kernel without InducingPatches, or the reverse: refused)
         fmean, fvar = self._fused_single_kernel(self.kernel, self.X_data.Z.device_value(), Xnew, full_cov)
         return self._post_process_mean_and_cov(fmean, fvar, full_cov, full_output_cov)
 

@@ -75,6 +75,9 @@ class SVGPTrainer:
         if reverse.has_row_diagonal(model.kernel):
             raise NotImplementedError(f"the trainer's device step takes K(x, x) for one scalar: {reverse.ROW_DIAGONAL} is not built into "
                                       "it -- SVGP.elbo_and_grad with optimizers.Scipy covers it")
+        if getattr(model.kernel, "patch_kernel", False):
+            raise NotImplementedError("SVGPTrainer: a Convolutional kernel is not built into the device-resident training step (its "
+                                      "weights are not among the packed variables); train it with optimizers.Scipy")
         routes, c, self.separate = reverse.svgp_routes(model)
         if any(p is not None for r, _ in routes for p in r.spec.periods):
             raise NotImplementedError("the trainer keeps (variance, lengthscales) per kernel on the device side of its step: no Periodic "

@@ -849,6 +849,47 @@ int gpk_profile_gemm_collect_kind(int kind, double min_flops, double* total_ms, 
 int gpk_profile_gemm_window(double min_flops, double* window_ms, double* flops_all, double* flops_matching,
                             long* launches_all);
 
+/* ---- Convolutional kernel over inducing patches (conv/conv.hip; gpflow/kernels/convolutional.py, covariances/kufs.py) -------------
+ * A row of X [N, H W C] ldx is an image [H, W, C] flattened row-major, channel fastest: pixel (i, j, c) at column (i W + j) C + c.  A
+ * patch is an h x w window of ONE channel, stride 1, no padding, flattened row-major (patch_len = h w); the P = C (H-h+1) (W-w+1)
+ * patches of an image are ordered by channel, window row, window column.  Z [M, patch_len] ldz: inducing patches; weights [P]: DEVICE
+ * pointer; the base kernel is the SquaredExponential k(a, b) = variance exp(-|a - b|^2 / (2 lengthscale^2)), both host scalars.
+ *     Kfu[n, m] = (1 / P) sum_p w_p k(z_m, x_n^[p])        K_diag[n] = (1 / P^2) sum_{p,q} w_p w_q k(x_n^[p], x_n^[q])
+ * Patches are never materialised: a workgroup stages one image in LDS and gathers patch elements from it.  The squared distance is
+ * (|z|^2 + |x|^2) - 2 z.x on inputs divided by the lengthscale, not clamped; in K_diag the terms p == q are taken BY INDEX (k = variance,
+ * no distance formed).  A NaN or Inf pixel makes exactly the row of Kfu and the entry of K_diag of its own image non-finite.
+ * Every entry point returns GPK_E_ARG, before any launch: H W C > GPK_CONV_MAX_PIXELS, h w > GPK_MAX_D, h outside 1 .. H, w outside
+ * 1 .. W, C < 1, a negative size, a leading dimension that is too small, a lengthscale that is not > 0, a variance or lengthscale that is
+ * not finite, a NULL operand that has elements.  No limit on N, M or P beyond these.  No atomics: a second call gives the same bits.
+ *
+ * gpk_conv_kfu: Kfu [N, M] ldk; one workgroup per (image, block of GPK_CONV_MBLOCK inducing patches); every element is stored once and
+ *   nothing beyond N x M is written.
+ * gpk_conv_kdiag: out [N]; one workgroup per image over the tiles q <= p of the patch Gram, off-diagonal pairs doubled.
+ * gpk_conv_kfu_adjoint: from G = dF/dKfu [N, M] ldg, with g_nmp = G[n, m] w_p k(z_m, x_n^[p]) / P and r2 the scaled squared distance:
+ *     dsmall[0] = d/dvariance = sum g / variance        dsmall[1] = d/dlengthscale = sum g r2 / lengthscale
+ *     dZ[m, :] = (1 / lengthscale^2) sum_{n,p} g (x_n^[p] - z_m)   [M, patch_len] lddz        dw[p] = (1 / P) sum_{n,m} G[n, m] k(z_m, x_n^[p])
+ *   A recompute stage (workgroup = block of inducing patches x chunk of images, dZ accumulated on chip over the chunk) writes typed
+ *   partials into `parts` -- gpk_conv_kfu_partials_len(N, M, H, W, C, h, w) doubles, at most 32 M (patch_len + 4) + 32 ceil(M / 64) (P + 2):
+ *   it does not grow with N -- and ONE tail launch adds them in index order.  Every slot of `parts` that is read was written by the
+ *   same call; its contents at entry do not matter.  N == 0: zeros.  No gradient with respect to X is formed.
+ * gpk_conv_kdiag_adjoint: from c = dF/dK_diag [N]:
+ *     dsmall[0] = sum_n c_n K_diag[n] / variance        dsmall[1] = sum_n c_n (1 / P^2) sum_{p != q} w_p w_q k r2 / lengthscale
+ *     dw[p] = (2 / P^2) sum_n c_n sum_q w_q k(x_n^[p], x_n^[q])
+ *   `parts`: gpk_conv_kdiag_partials_len(N, H, W, C, h, w) doubles (at most 128 (P + 2)), same rules. */
+#define GPK_CONV_MAX_PIXELS 4096
+#define GPK_CONV_MBLOCK 64
+int gpk_conv_kfu(void* stream, const double* X, int N, long ldx, int H, int W, int C, int h, int w, const double* Z, int M, long ldz,
+                 const double* weights, double variance, double lengthscale, double* Kfu, long ldk);
+int gpk_conv_kdiag(void* stream, const double* X, int N, long ldx, int H, int W, int C, int h, int w, const double* weights,
+                   double variance, double lengthscale, double* out);
+size_t gpk_conv_kfu_partials_len(int N, int M, int H, int W, int C, int h, int w);
+int gpk_conv_kfu_adjoint(void* stream, const double* X, int N, long ldx, int H, int W, int C, int h, int w, const double* Z, int M,
+                         long ldz, const double* weights, double variance, double lengthscale, const double* G, long ldg, double* parts,
+                         double* dsmall, double* dZ, long lddz, double* dw);
+size_t gpk_conv_kdiag_partials_len(int N, int H, int W, int C, int h, int w);
+int gpk_conv_kdiag_adjoint(void* stream, const double* X, int N, long ldx, int H, int W, int C, int h, int w, const double* weights,
+                           double variance, double lengthscale, const double* c, double* parts, double* dsmall, double* dw);
+
 /* micro-benchmarks used by bench.py / profiles (fp64 MFMA issue rate, HBM write stream) */
 int gpk_bench_mfma_f64(void* stream, int blocks, int iters, double* sink);
 int gpk_bench_stream_store(void* stream, double* out, long n_doubles);
