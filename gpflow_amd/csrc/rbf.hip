@@ -14,6 +14,7 @@
 // The expansion formula and the association (-2 x.y) + (|x|^2 + |y|^2) of the reference are kept
 // so rounding has the same structure (the diagonal is exp(-0.5 * ~1e-16), not exactly sigma^2).
 #include "pair_tile.h"
+#include "kern_profile.h"
 #include <algorithm>
 #include <cmath>
 
@@ -40,46 +41,7 @@ constexpr int NORMS = 2 * T;   // doubles of LDS behind the slabs: the squared n
 template <int family>
 constexpr bool kern_static = (family == GPK_KERN_WHITE || family == GPK_KERN_CONSTANT);
 
-template <int family>
-__device__ __forceinline__ double kern_eval(double r2, double variance, double alpha) {
-  if (family == GPK_KERN_SE) return variance * exp(-0.5 * r2);
-  if (family == GPK_KERN_RQ) return variance * exp(-alpha * log1p(r2 / (2.0 * alpha)));   // (1 + r2 / (2 alpha))^-alpha, on r2: no clamp
-  const double r = sqrt(r2 < 1e-36 ? 1e-36 : r2);   // (not fmax: a NaN r2 has to come out as NaN, as tf.maximum gives)
-  if (family == GPK_KERN_MATERN12) return variance * exp(-r);
-  if (family == GPK_KERN_EXPONENTIAL) return variance * exp(-0.5 * r);
-  if (family == GPK_KERN_MATERN32) {
-    const double sqrt3 = 1.7320508075688772;
-    return variance * (1.0 + sqrt3 * r) * exp(-sqrt3 * r);
-  }
-  const double sqrt5 = 2.23606797749979;
-  return variance * (1.0 + sqrt5 * r + 5.0 / 3.0 * (r * r)) * exp(-sqrt5 * r);
-}
-
-// -2 dk/dr2 at the SCALED squared distance: the factor every lengthscale / input gradient of a stationary kernel starts
-// from (for the SquaredExponential it is k itself).  r = sqrt(max(r2, 1e-36)) has derivative 0 where the clamp is
-// active (stationaries.py:103-116 under TF autodiff: tf.maximum passes nothing to the clamped argument).
-template <int family>
-__device__ __forceinline__ double kern_dr2(double r2, double variance, double alpha) {
-  if (family == GPK_KERN_SE) return variance * exp(-0.5 * r2);
-  if (family == GPK_KERN_RQ) return variance * exp(-(alpha + 1.0) * log1p(r2 / (2.0 * alpha)));
-  if (r2 <= 1e-36) return 0.0;   // (a NaN r2 is not clamped: it reaches sqrt and comes out as NaN)
-  const double r = sqrt(r2);
-  if (family == GPK_KERN_MATERN12) return variance * exp(-r) / r;
-  if (family == GPK_KERN_EXPONENTIAL) return variance * exp(-0.5 * r) / (2.0 * r);
-  if (family == GPK_KERN_MATERN32) {
-    const double sqrt3 = 1.7320508075688772;
-    return 3.0 * variance * exp(-sqrt3 * r);
-  }
-  const double sqrt5 = 2.23606797749979;
-  return (5.0 / 3.0) * variance * (1.0 + sqrt5 * r) * exp(-sqrt5 * r);
-}
-
-// dk/dalpha of the RationalQuadratic: with u = r2 / (2 alpha) and k = variance exp(-alpha log1p(u)), du/dalpha = -u / alpha gives
-// k (u / (1 + u) - log1p(u)); the logarithm is the one k itself needs.
-__device__ __forceinline__ double kern_dalpha_rq(double r2, double variance, double alpha) {
-  const double u = r2 / (2.0 * alpha), l = log1p(u);
-  return variance * exp(-alpha * l) * (u / (1.0 + u) - l);
-}
+// (kern_eval, kern_dr2, kern_dalpha_rq: kern_profile.h, shared with wide/wide_stationary.hip)
 
 // MIRROR (symmetric full build): only tiles on or below the diagonal are computed; each is also written
 // transposed to its mirror position (K(X,X) from the expansion formula is bitwise symmetric: products and the

@@ -25,7 +25,6 @@ from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
 
-import collections
 import os
 
 import numpy as np
@@ -131,23 +130,7 @@ def cholesky_adjoint(LT: torch.Tensor, LinvT: torch.Tensor, Lbar: torch.Tensor, 
     return ops.symmetrize_(S)
 
 
-_ls_cache: "collections.OrderedDict" = collections.OrderedDict()
-
-
-def ls_device(lengthscales, D: int, device) -> torch.Tensor:
-    """Lengthscales as a [D] device tensor.  A host array -> device copy from pageable memory BLOCKS the host until the stream
-    has drained; in the tail of a reverse pass that serialised ~80 short launches behind an idle GPU (1 ms of a 6.5-ms training
-    step, profiles/r04_train_timeline_before.txt).  The tensors are therefore made once per set of values -- the gradient entry
-    points ask for them BEFORE they enqueue their first kernel -- and found here by the adjoints."""
-    a = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscales, dtype=np.float64), (D,)))
-    key = (a.tobytes(), str(device))
-    t = _ls_cache.get(key)
-    if t is None:
-        t = torch.as_tensor(a.copy(), device=device)
-        _ls_cache[key] = t
-        while len(_ls_cache) > 32:
-            _ls_cache.popitem(last=False)
-    return t
+ls_device = ops.ls_device   # (it lives in `ops` since the wide builder reads its lengthscales from the device; the name stays importable from here)
 
 
 def stationary_kernel_adjoint(leaf: Leaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, symmetric: bool, packed_into=None,

@@ -9,7 +9,7 @@ import torch
 
 from ..base import Module
 from .. import ops
-from ..leaf import BY_NAME, Leaf
+from ..leaf import BY_NAME, MAX_D, Leaf
 
 ActiveDims = Union[slice, Sequence[int]]
 
@@ -138,6 +138,16 @@ class DeviceLeaf(Kernel):
 def is_device_leaf(k) -> bool:
     """True for a DeviceLeaf of a known family.  The one notion reverse_leaf and the model routes share."""
     return bool(getattr(k, "device_leaf", False)) and getattr(k, "family", None) in ops.KERNEL_FAMILIES
+
+
+def fits_fused_drivers(k, D: int) -> bool:
+    """Whether the active width of leaf kernel `k` over inputs of D columns fits the fused model drivers (gpk_gpr_lml,
+    gpk_svgp_elbo_shard / _lik / _sep / _lcm): they take the lengthscales from the host and call the narrow builder themselves, so
+    they stop at MAX_D columns.  The width is an index list's length, or what a slice keeps of the D columns.  A wider leaf
+    takes the composed route next to every fused one: its builds go through `ops`, which sends them to the wide builder."""
+    dims = k.active_dims
+    width = len(range(*dims.indices(int(D)))) if isinstance(dims, slice) else len(dims)
+    return width <= MAX_D
 
 
 class RowDiagonalLeaf(Kernel):

@@ -7,7 +7,7 @@ import torch
 
 from .. import ops, posteriors
 from ..kernels import Kernel
-from ..kernels.base import is_device_leaf
+from ..kernels.base import fits_fused_drivers, is_device_leaf
 from ..likelihoods import Gaussian
 from ..logdensities import multivariate_normal
 from ..mean_functions import MeanFunction
@@ -40,7 +40,7 @@ class GPR(GPModel, InternalDataTrainingLossMixin):
         otherwise it is composed from the same primitives."""
         X, Y = self.data
         c = self.mean_function.constant_value()
-        if is_device_leaf(self.kernel) and c is not None:
+        if is_device_leaf(self.kernel) and c is not None and fits_fused_drivers(self.kernel, X.shape[1]):
             Xs, _ = self.kernel.slice(X, None)
             out, info = ops.gpr_lml(Xs, Y, noise_variance=self.likelihood.noise_for(X), mean_const=c, ws=self._ws,
                                     **self.kernel.leaf().keywords())

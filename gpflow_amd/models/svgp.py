@@ -12,7 +12,7 @@ from ..conditionals import conditional
 from ..inducing_variables import (InducingPoints, SharedIndependentInducingVariables,
                                   inducingpoint_wrapper)
 from ..kernels import Kernel
-from ..kernels.base import is_device_leaf
+from ..kernels.base import fits_fused_drivers, is_device_leaf
 from ..leaf import latent_keywords
 from ..likelihoods import Gaussian, Likelihood, MultiClass, ScalarLikelihood, SwitchedLikelihood
 from ..mean_functions import MeanFunction
@@ -74,8 +74,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         if c is None:
             return None
         k, iv = shared_pair(self.kernel, self.inducing_variable)
-        if not (is_device_leaf(k) and isinstance(iv, InducingPoints)):
-            return None
+        if not (is_device_leaf(k) and isinstance(iv, InducingPoints) and fits_fused_drivers(k, iv.Z.shape[-1])):
+            return None   # (a leaf wider than the fused drivers take: the composed route)
         return k, iv.Z.device_value(), c
 
     def _device_likelihood(self) -> bool:
@@ -121,11 +121,13 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         if not all(is_device_leaf(kk) and kk.has_default_active_dims and not kk.maps_inputs for kk in k.kernels):
             return None
         if isinstance(iv, SharedIndependentInducingVariables) and isinstance(iv.inducing_variable, InducingPoints):
+            if not fits_fused_drivers(k.kernels[0], iv.inducing_variable.Z.shape[-1]):
+                return None   # (members over all columns, wider than the per-latent shards take: the composed route)
             return k.kernels, iv.inducing_variable.Z.device_value().contiguous()
         if isinstance(iv, SeparateIndependentInducingVariables) and len(iv.inducing_variable_list) == len(k.kernels) \
                 and all(isinstance(v, InducingPoints) for v in iv.inducing_variable_list):
             Zs = [v.Z.device_value() for v in iv.inducing_variable_list]
-            if len({tuple(z.shape) for z in Zs}) == 1:
+            if len({tuple(z.shape) for z in Zs}) == 1 and fits_fused_drivers(k.kernels[0], Zs[0].shape[-1]):
                 return k.kernels, torch.stack(Zs).contiguous()
         return None
 

@@ -14,12 +14,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .leaf import FAMILIES, ArcLeaf, CoregionLeaf, DotLeaf, Leaf
+from .leaf import FAMILIES, MAX_D, WIDE_MAX_D, ArcLeaf, CoregionLeaf, DotLeaf, Leaf
 
 NB = 128
 KERNEL_FAMILIES = {f.name: f.code for f in FAMILIES}                      # name -> GPK_KERN_* (include/gpk.h)
 STATIC_FAMILIES = tuple(f.name for f in FAMILIES if not f.has_distance)   # the inputs are never read, no lengthscale or input gradient
-MAX_D = 64
 
 
 def device() -> torch.device:
@@ -93,10 +92,11 @@ def _noise_args(noise_variance, rows: int):
 _COLUMNS_DIFFER = "X1 and X2 must have the same number of columns"
 
 
-def _kernel_operands(X1, X2, G, out, *, x2_optional: bool = True, zero_new: bool = False, columns_differ: str = _COLUMNS_DIFFER):
+def _kernel_operands(X1, X2, G, out, *, x2_optional: bool = True, zero_new: bool = False, columns_differ: str = _COLUMNS_DIFFER,
+                     max_d: int = MAX_D):
     """What the kernel_matrix* wrappers check before they look at the leaf: devices and dtypes, the shapes of X2 (None: K(X1, X1),
     where the wrapper allows it) / G (None: no second factor) / out (allocated when None, zero-filled if `zero_new`), d in
-    [1, MAX_D].  Returns (n1, n2, d, out); n1 == 0 or n2 == 0: nothing to compute, the wrapper returns `out` (and X2 = NULL would
+    [1, max_d].  Returns (n1, n2, d, out); n1 == 0 or n2 == 0: nothing to compute, the wrapper returns `out` (and X2 = NULL would
     mean K(X1, X1) at the C-ABI)."""
     _chk(X1, "X1", 2)
     n1, d = X1.shape
@@ -109,8 +109,8 @@ def _kernel_operands(X1, X2, G, out, *, x2_optional: bool = True, zero_new: bool
     n2 = X2.shape[0] if X2 is not None else n1
     if G is not None and tuple(G.shape) != (n1, n2):
         raise ValueError("inconsistent shapes")
-    if d < 1 or d > MAX_D:
-        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
+    if d < 1 or d > max_d:
+        raise ValueError(f"input dimension {d} outside [1, {max_d}]")
     if out is None:
         out = torch.empty((n1, n2), dtype=torch.float64, device=X1.device)
         if zero_new:
@@ -204,20 +204,73 @@ def _row_diagonal(entry: str, name: str, codes, X, g, out, op, leaf, width=None)
     return out
 
 
+_ls_cache: "collections.OrderedDict" = collections.OrderedDict()
+
+
+def ls_device(lengthscales, D: int, device) -> torch.Tensor:
+    """Lengthscales as a [D] device tensor.  A host array -> device copy from pageable memory BLOCKS the host until the stream
+    has drained; in the tail of a reverse pass that serialised ~80 short launches behind an idle GPU (1 ms of a 6.5-ms training
+    step, profiles/r04_train_timeline_before.txt).  The tensors are therefore made once per set of values -- the gradient entry
+    points ask for them BEFORE they enqueue their first kernel -- and found here by the adjoints and by the wide builder."""
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscales, dtype=np.float64), (D,)))
+    key = (a.tobytes(), str(device))
+    t = _ls_cache.get(key)
+    if t is None:
+        t = torch.as_tensor(a.copy(), device=device)
+        _ls_cache[key] = t
+        while len(_ls_cache) > 32:
+            _ls_cache.popitem(last=False)
+    return t
+
+
+def _stationary_builder(entry: str, X1, X2, G, out, op, leaf, diag_add, lower_only, **checks):
+    """`_pair_builder` for a row of FAMILIES, by the width of the inputs.  d <= MAX_D: the narrow entry point `entry`, the call it
+    always was.  MAX_D < d <= WIDE_MAX_D: a stationary family goes to the wide entry points (gpk_wide_kernel_matrix / _combine:
+    lengthscales from the by-value device cache, alpha an argument; the hadamard is combine "mul"); a static family never reads X
+    and goes to `entry` with the width replaced by 1.  Above WIDE_MAX_D: ValueError."""
+    d = X1.shape[1] if isinstance(X1, torch.Tensor) and X1.dim() == 2 else 0
+    if d <= MAX_D:
+        return _pair_builder(entry, X1, X2, G, out, op, _STATIONARY_OPS, leaf, diag_add, lower_only, **checks)
+    if d > WIDE_MAX_D:
+        raise ValueError(f"input dimension {d} outside [1, {WIDE_MAX_D}]: the builder of the stationary kernels takes up to {MAX_D} "
+                         f"columns on its 64 x 64 tile and up to {WIDE_MAX_D} on its matrix-instruction tile")
+    lf = leaf()
+    if lf.is_static:
+        if X2 is not None and isinstance(X2, torch.Tensor) and X2.dim() == 2 and X2.shape[1] != d:
+            raise ValueError(checks.get("columns_differ", _COLUMNS_DIFFER))
+        return _pair_builder(entry, X1[:, :1], None if X2 is None else X2[:, :1], G, out, op, _STATIONARY_OPS, lambda: lf, diag_add,
+                             lower_only, **checks)
+    lib = _lib.load()
+    n1, n2, d, out = _kernel_operands(X1, X2, G, out, zero_new=bool(lower_only), max_d=WIDE_MAX_D, **checks)
+    hadamard = entry == "gpk_kernel_matrix_hadamard"
+    code = () if G is None else (1,) if hadamard else (_STATIONARY_OPS[op],)
+    if n1 == 0 or n2 == 0:
+        return out
+    _, ard = lf.host(d)   # (the check that an ARD leaf has d lengthscales)
+    ls = ls_device(lf.lengthscales, d if ard else 1, X1.device)
+    wide = "gpk_wide_kernel_matrix" if G is None else "gpk_wide_kernel_matrix_combine"
+    rc = getattr(lib, wide)(_stream(), lf.code, *code, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, ls.data_ptr(), ard,
+                            lf.extras[0] if lf.extras else 1.0, lf.variance, 0.0 if diag_add is None else float(diag_add),
+                            *(() if G is not None else (int(bool(lower_only)),)),
+                            *(() if G is None else (G.data_ptr(), _rowmajor(G, "G"))), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, wide)
+    return out
+
+
 def kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, variance: float, lengthscales,
                   family: str = "SquaredExponential", diag_add: float = 0.0, lower_only: bool = False,
                   alpha=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2]."""
-    return _pair_builder("gpk_kernel_matrix", X1, X2, None, out, None, None,
-                         partial(Leaf, family, variance, lengthscales, alpha=alpha), diag_add, lower_only)
+    """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2].  Up to WIDE_MAX_D columns (`_stationary_builder`)."""
+    return _stationary_builder("gpk_kernel_matrix", X1, X2, None, out, None,
+                               partial(Leaf, family, variance, lengthscales, alpha=alpha), diag_add, lower_only)
 
 
 def kernel_matrix_hadamard(X1: torch.Tensor, X2: torch.Tensor, G: torch.Tensor, *, variance: float, lengthscales,
                            family: str = "SquaredExponential", alpha=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """G .* K(X1, X2) with K recomputed on the fly -> [n1, n2] (the elementwise factor of the kernel backward)."""
-    return _pair_builder("gpk_kernel_matrix_hadamard", X1, X2, G, out, None, None,
-                         partial(Leaf, family, variance, lengthscales, alpha=alpha), None, None,
-                         x2_optional=False, columns_differ="inconsistent shapes")
+    return _stationary_builder("gpk_kernel_matrix_hadamard", X1, X2, G, out, None,
+                               partial(Leaf, family, variance, lengthscales, alpha=alpha), None, None,
+                               x2_optional=False, columns_differ="inconsistent shapes")
 
 
 def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, variance: float,
@@ -227,8 +280,8 @@ def kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch
     lengthscale / input gradients of a stationary kernel; r2 = scaled squared distance), K recomputed on the fly; `out`
     may be G itself.  X2 None: K(X1, X1); `diag_add` goes onto the diagonal of the combined result ("mul" / "add"), and
     "dr2" writes exact zeros on the diagonal.  op "dalpha" ("RationalQuadratic" only): G .* dK/dalpha, diagonal as "dr2"."""
-    return _pair_builder("gpk_kernel_matrix_combine", X1, X2, G, out, op, _STATIONARY_OPS,
-                         partial(Leaf, family, variance, lengthscales, alpha=alpha), diag_add, None)
+    return _stationary_builder("gpk_kernel_matrix_combine", X1, X2, G, out, op,
+                               partial(Leaf, family, variance, lengthscales, alpha=alpha), diag_add, None)
 
 
 # ------------------------------------------------------------------------------------------------ dot-product kernels (dot.hip)
@@ -1511,6 +1564,9 @@ def _shard_setup(Z, Xb, Yb, q_mu, q_sqrt, ws, out, info, *, y_columns, workspace
 def _latent_hypers(variances, lengthscales, families, n: int, d: int):
     """(family codes, (ls_host, ard, variances_host)) of the per-latent shards: variances [n], lengthscales [n] (isotropic) or
     [n, d], families [n] names (leaf.latent_keywords makes them from leaves)"""
+    if d > MAX_D:
+        raise NotImplementedError(f"the per-latent fused shards build through the narrow builder: input dimension {d} > {MAX_D} "
+                                  "(the composed ELBO takes wide inputs)")
     ls = np.asarray(lengthscales, dtype=np.float64)
     var = np.asarray(variances, dtype=np.float64).reshape(-1)
     if var.size != n or ls.shape[0] != n or (ls.ndim == 2 and ls.shape[1] != d) or ls.ndim > 2:

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import config, distributed, gradients, ops
+from .leaf import MAX_D, WIDE_MAX_D
 
 
 class _Adam:
@@ -88,6 +89,11 @@ class SVGPTrainer:
                                       "RationalQuadratic (alpha), White or Constant (no lengthscales) members -- SVGP.elbo_and_grad "
                                       "with optimizers.Scipy covers them")
         iv = routes[0][1]
+        D = int(iv.Z.shape[-1])
+        if any((D if part.cols is None else len(part.cols)) > MAX_D for r, _ in routes for part in r.spec.parts):
+            raise NotImplementedError(f"the trainer's device step keeps the lengthscales in kernel arguments: a kernel over more than "
+                                      f"{MAX_D} input columns is not built into it -- SVGP.elbo_and_grad with optimizers.Scipy "
+                                      f"covers up to {WIDE_MAX_D}")
         self.routes = [r for r, _ in routes]
         lik = model.likelihood
         self.q_diag = model.q_sqrt.numpy().ndim == 2

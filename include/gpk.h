@@ -141,6 +141,37 @@ int gpk_kernel_matrix_hadamard(void* stream, int family, const double* X1, int n
                                const double* X2, int n2, long ldx2, int d, const double* ls_host, int ard,
                                double variance, const double* G, long ldg, double* out, long ldo);
 
+/* ---- covariance builder, wide inputs (csrc/wide/wide_stationary.hip) ---------------------------
+ * The six stationary families for 1 <= d <= GPK_WIDE_MAX_D columns: an MFMA tile kernel with a K loop over 16-column slabs, where
+ * gpk_kernel_matrix (d <= GPK_MAX_D) stages whole rows.  The contract is that of gpk_kernel_matrix / gpk_kernel_matrix_combine:
+ *   K[i,j] = variance * k(r2(X1_i / ls, X2_j / ls)) (+ diag_add if i == j and X2 == NULL);
+ *   X1 [n1,d] ldx1; X2 [n2,d] ldx2 or NULL (symmetric: X2 = X1);  K [n1,n2] ldk;  lower_only: with X2 == NULL write only tiles
+ *   that touch the lower triangle (what the Cholesky reads), strictly-upper tiles are left untouched;
+ *   combine: out = G .* k(X1, X2) (op 1), G + k(X1, X2) (op 2), G .* (-2 dk/dr2)(X1, X2) (op 3) or G .* (dk/dalpha)(X1, X2) (op 4),
+ *   k recomputed from the inputs (one read of G, one write; G may alias out); X2 == NULL: K(X1, X1), and diag_add goes onto the
+ *   diagonal of the COMBINED result; ops 3 and 4 with X2 == NULL write exact zeros on the diagonal; op 4: GPK_KERN_RQ only (any
+ *   other family: GPK_E_UNSUPPORTED);
+ *   an operand without elements may be NULL, and empty operands return 0 without a launch;
+ *   GPK_E_ARG, before any launch: a negative size, d outside 1 .. GPK_WIDE_MAX_D, a leading dimension smaller than the operand's
+ *   columns, an op outside 1 .. 4, a NULL operand that has elements, GPK_KERN_RQ with an alpha that is not positive and finite,
+ *   more than 65535 tiles of rows (n1 > 65535 x 128, or x 64 where the 64-tile is taken: the tile rows are the grid's y dimension).
+ * with three differences:
+ *   1. d may be anything in 1 .. GPK_WIDE_MAX_D (the limit of gpk_stationary_adjoint_tail);
+ *   2. ls_dev is a DEVICE pointer (d doubles if ard, else one), as gpk_stationary_adjoint_tail takes it -- 1024 doubles do not fit
+ *      in kernel arguments -- and alpha is an argument of its own, read for GPK_KERN_RQ only;
+ *   3. GPK_KERN_WHITE and GPK_KERN_CONSTANT are GPK_E_UNSUPPORTED: they never read X, gpk_kernel_matrix builds them at any width.
+ * The symmetric build is exactly symmetric; a row's squared norm has the same bits as a row and as a column; no atomics: a second
+ * call gives the same bits.  A NaN in one row of X makes exactly that row and column NaN.  Results are NOT bit-identical to
+ * gpk_kernel_matrix at d <= GPK_MAX_D (another summation order). */
+#define GPK_WIDE_MAX_D 1024
+int gpk_wide_kernel_matrix(void* stream, int family, const double* X1, int n1, long ldx1,
+                           const double* X2, int n2, long ldx2, int d, const double* ls_dev, int ard,
+                           double alpha, double variance, double diag_add, int lower_only, double* K, long ldk);
+int gpk_wide_kernel_matrix_combine(void* stream, int family, int op, const double* X1, int n1, long ldx1,
+                                   const double* X2, int n2, long ldx2, int d, const double* ls_dev, int ard,
+                                   double alpha, double variance, double diag_add, const double* G, long ldg,
+                                   double* out, long ldo);
+
 /* ---- trapezoidal Cholesky ---------------------------------------------------------------------
  * A is [(n + extra) x n] row-major.  Top n x n block (lower triangle read): K -> L in place,
  * K = L L^T (tf.linalg.cholesky call sites: gpr.py:102, posteriors.py:422,703, conditionals/util.py:67,
