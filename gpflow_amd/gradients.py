@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .leaf import ArcLeaf, CoregionLeaf, DotLeaf, Leaf
+from .leaf import MAX_D, ArcLeaf, CoregionLeaf, DotLeaf, Leaf
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -216,7 +216,8 @@ def arccos_kernel_adjoint(leaf: ArcLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar
     K depends on the inputs and on (w, b) through s_ik, p_i and q_k.  ONE stage (ops.arccos_adjoint_stage) recomputes them per tile and
     leaves G = Kbar .* dk/ds and the per-tile partials of rho_i = sum_k Kbar_ik dk/dp_i, gamma_k = sum_i Kbar_ik dk/dq_k and
     sum Kbar .* k / variance; ONE contraction R = G [1, B] (the right-hand side is ops.moment_rows(Bm), as in dot_kernel_adjoint);
-    ONE one-workgroup tail (ops.arccos_adjoint_tail) that adds the norm terms 2 w_j a_ij rho_i, sum_i rho_i a_ij^2, sum_k gamma_k b_kj^2."""
+    ONE one-workgroup tail (ops.arccos_adjoint_tail) that adds the norm terms 2 w_j a_ij rho_i, sum_i rho_i a_ij^2, sum_k gamma_k b_kj^2.
+    Past MAX_D columns the same three calls reach the wide entry points (csrc/wide/wide_arccosine.hip; the tail is two launches)."""
     D = A.shape[1]
     if leaf.ard and leaf.n_weights != D:
         raise ValueError(f"weight_variances has {leaf.n_weights} entries, input dimension is {D}")
@@ -224,7 +225,10 @@ def arccos_kernel_adjoint(leaf: ArcLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar
     Bm = A if symmetric else (Bm if Bm.is_contiguous() else Bm.contiguous())
     parts = ops.arccos_adjoint_parts(A.shape[0], Bm.shape[0], A.device)
     G = ops.arccos_adjoint_stage(A, None if symmetric else Bm, Kbar if Kbar.is_contiguous() else Kbar.contiguous(), parts, **leaf.keywords())
-    R = splitk_gemm_nt(G, ops.moment_rows(Bm))   # [n1, 1 + 2 D]: row sums, G B, (G B^2 unused)
+    Vt = ops.moment_rows(Bm)
+    if D > MAX_D:   # (wide inputs: the B^2 rows, which no one reads, would double the contraction)
+        Vt = Vt[:1 + D]
+    R = splitk_gemm_nt(G, Vt)   # [n1, 1 + 2 D]: row sums, G B, (G B^2 unused); wide: [n1, 1 + D]
     dv, dw, db, Abar = ops.arccos_adjoint_tail(R, A, None if symmetric else Bm, parts, weight_variances=leaf.weight_variances)
     return dv, torch.cat([dw, db]), Abar
 
@@ -374,6 +378,10 @@ class ArcMember(RowDiagonalMember):
         m = _moment_sums(ops.arccos_kernel_diag(Xi, bar, op="dp", **kw), Xi)
         dw = m[1 + Xi.shape[1]:]
         return dv, torch.cat([dw if leaf.ard else dw.sum().reshape(1), m[0:1]])
+
+    def warm(self, device, D: int) -> None:
+        if (D if self.cols is None else len(self.cols)) > MAX_D:   # (the weights the wide entry points read on the device)
+            ls_device(self.leaf.weight_variances, self.leaf.n_weights, device)
 
 
 def coregion_kernel_adjoint(leaf: CoregionLeaf, A: torch.Tensor, Bm: torch.Tensor, Kbar: torch.Tensor, *, symmetric: bool):

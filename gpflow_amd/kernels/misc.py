@@ -64,7 +64,11 @@ class ArcCosine(RowDiagonalLeaf):
         return ArcLeaf.of(self.order, [p.numpy() for p in self.leaf_params()])
 
     def check_width(self, d: int) -> None:
-        """ValueError, before the device, for ARD weights that do not fit the d input columns the kernel sees"""
+        """ValueError, before the device, for ARD weights that do not fit the d input columns the kernel sees, or for more columns
+        than the wide builder takes"""
+        if d > ops.WIDE_MAX_D:
+            raise ValueError(f"ArcCosine sees {d} input columns: the builder takes up to {ops.MAX_D} on its 64 x 64 tile and up to "
+                             f"{ops.WIDE_MAX_D} on its matrix-instruction tile")
         w = self.weight_variances.numpy()
         if w.ndim == 1 and w.shape[0] != d:
             raise ValueError(f"weight_variances has {w.shape[0]} entries, the kernel sees {d} input columns")

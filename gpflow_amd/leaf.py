@@ -41,8 +41,8 @@ import numpy as np
 from . import _lib
 
 
-MAX_D = 64            # GPK_MAX_D: the widest input of every builder but the stationary one, and of the fused model drivers
-WIDE_MAX_D = 1024     # GPK_WIDE_MAX_D: the widest input of the stationary builder (csrc/wide/wide_stationary.hip)
+MAX_D = 64            # GPK_MAX_D: the widest input of every builder but the stationary and the ArcCosine one, and of the fused model drivers
+WIDE_MAX_D = 1024     # GPK_WIDE_MAX_D: the widest input of the stationary and ArcCosine builders (csrc/wide/)
 
 
 class Family(NamedTuple):

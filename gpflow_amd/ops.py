@@ -139,15 +139,17 @@ def _check_op(name: str, op: str, allowed) -> None:
 
 
 def _pair_builder(entry: str, X1, X2, G, out, op, codes, leaf, diag_add, lower_only, width=None, x2_optional=True,
-                  columns_differ=_COLUMNS_DIFFER):
+                  columns_differ=_COLUMNS_DIFFER, max_d: int = MAX_D):
     """The one body of the kernel_matrix* wrappers of every kind of leaf: `_kernel_operands`, the empty-result return, the leaf's
     C-ABI arguments, the call of `entry` and `_lib.check`.  `op` (None: the entry point takes none) is looked up in `codes`; `leaf()`
     makes the leaf, whose `abi(d)` gives its arguments, the code in front (leaf.py, the protocol); `diag_add` / `lower_only` None: the
     entry point has no such argument; G None: no second factor; `x2_optional`, `columns_differ`: as `_kernel_operands` takes them.
     `width` (`_LABELS`): the kind reads exactly that many columns, its entry points take no `d` and no code, and `leaf()` gives the
-    arguments themselves -- the kind's table on the device, a launch of its own -- whatever the sizes."""
+    arguments themselves -- the kind's table on the device, a launch of its own -- whatever the sizes.  `max_d`: the widest input
+    `entry` takes."""
     lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, G, out, x2_optional=x2_optional, zero_new=lower_only, columns_differ=columns_differ)
+    n1, n2, d, out = _kernel_operands(X1, X2, G, out, x2_optional=x2_optional, zero_new=lower_only, columns_differ=columns_differ,
+                                      max_d=max_d)
     if width is not None:
         if d != width[0]:
             raise ValueError(f"{entry[4:]}: {width[1]}, got {d}")
@@ -166,7 +168,7 @@ def _pair_builder(entry: str, X1, X2, G, out, op, codes, leaf, diag_add, lower_o
     return out
 
 
-def _row_diagonal(entry: str, name: str, codes, X, g, out, op, leaf, width=None):
+def _row_diagonal(entry: str, name: str, codes, X, g, out, op, leaf, width=None, max_d: int = MAX_D):
     """The one body of the *_kernel_diag wrappers: the operand checks of a row diagonal over X [n, D] -- the width, the op (the keys
     of `codes`, "k" first), g given exactly when the op is not "k", g and `out` contiguous [n] -- the empty-result return, the leaf's
     C-ABI arguments (`leaf`, `width`: as `_pair_builder`), the call of `entry` and `_lib.check`.  `name`: the wrapper's, for the messages."""
@@ -175,8 +177,8 @@ def _row_diagonal(entry: str, name: str, codes, X, g, out, op, leaf, width=None)
     n, d = X.shape
     if width is not None and d != width[0]:
         raise ValueError(f"{name}: {width[1]}, got {d}")
-    if width is None and (d < 1 or d > MAX_D):
-        raise ValueError(f"input dimension {d} outside [1, {MAX_D}]")
+    if width is None and (d < 1 or d > max_d):
+        raise ValueError(f"input dimension {d} outside [1, {max_d}]")
     _check_op(name, op, codes)
     if (op == "k") != (g is None):
         with_g = [repr(o) for o in codes if o != "k"]
@@ -334,14 +336,47 @@ def dot_adjoint_tail(R: torch.Tensor, A: torch.Tensor, w: torch.Tensor, *, symme
 
 # ------------------------------------------------------------------------------------------------ ArcCosine kernel (arccosine/arccosine.hip)
 ARC_TILE = 64   # include/gpk.h: GPK_ARC_TILE
+_WIDE_ARC_TAIL_ROWS = 256   # include/gpk.h: GPK_WIDE_ARC_TAIL_ROWS
+
+
+class _ArcOnDevice:
+    """An ArcLeaf as the gpk_wide_arc_* entry points take it (csrc/wide/wide_arccosine.hip): `abi(d)` is ArcLeaf.abi with the weights'
+    DEVICE pointer -- from the by-value cache `ls_device` -- in place of the host array.  The library cannot look at device weights,
+    so what gpk_arccos_* refuse of them is refused here."""
+
+    def __init__(self, leaf: ArcLeaf, device_):
+        self.leaf, self.device = leaf, device_
+
+    def abi(self, d: int) -> tuple:
+        lf = self.leaf
+        _, ard = lf.host(d)   # (the check that ARD weights have d entries)
+        w = np.atleast_1d(lf.weight_variances)
+        if not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+            raise ValueError("weight_variances must be finite and not negative")
+        self.w = ls_device(lf.weight_variances, d if ard else 1, self.device)
+        return (lf.order, self.w.data_ptr(), ard, lf.variance, lf.bias_variance)
+
+
+def _arc_route(entry: str, X, leaf):
+    """(entry point, leaf maker, widest input) of an ArcCosine wrapper by the width of X.  d <= MAX_D: `entry` and `leaf`, the call it
+    always was.  MAX_D < d <= WIDE_MAX_D: the wide entry point of the same name and the leaf with its weights on the device.  Above
+    WIDE_MAX_D: ValueError."""
+    d = X.shape[1] if isinstance(X, torch.Tensor) and X.dim() == 2 else 0
+    if d <= MAX_D:
+        return entry, leaf, MAX_D
+    if d > WIDE_MAX_D:
+        raise ValueError(f"input dimension {d} outside [1, {WIDE_MAX_D}]: the ArcCosine builder takes up to {MAX_D} columns on its "
+                         f"64 x 64 tile and up to {WIDE_MAX_D} on its matrix-instruction tile")
+    return entry.replace("gpk_arccos_", "gpk_wide_arc_"), (lambda: _ArcOnDevice(leaf(), X.device)), WIDE_MAX_D
 
 
 def arccos_kernel_matrix(X1: torch.Tensor, X2: Optional[torch.Tensor], *, order: int = 0, variance=1.0, weight_variances=1.0,
                          bias_variance=1.0, diag_add: float = 0.0, lower_only: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K(X1, X2) (or K(X1, X1) + diag_add I when X2 is None) -> [n1, n2] of an ArcCosine leaf of order 0, 1 or 2.  `weight_variances`
-    one weight or [D].  The symmetric build is exactly symmetric and takes its diagonal by index (include/gpk.h)."""
-    return _pair_builder("gpk_arccos_kernel_matrix", X1, X2, None, out, None, None,
-                         partial(ArcLeaf, order, variance, weight_variances, bias_variance), diag_add, lower_only)
+    one weight or [D].  The symmetric build is exactly symmetric and takes its diagonal by index (include/gpk.h).  Up to WIDE_MAX_D
+    columns (`_arc_route`)."""
+    entry, leaf, max_d = _arc_route("gpk_arccos_kernel_matrix", X1, partial(ArcLeaf, order, variance, weight_variances, bias_variance))
+    return _pair_builder(entry, X1, X2, None, out, None, None, leaf, diag_add, lower_only, max_d=max_d)
 
 
 def arccos_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G: torch.Tensor, *, op: str, order: int = 0, variance=1.0,
@@ -350,8 +385,8 @@ def arccos_kernel_matrix_combine(X1: torch.Tensor, X2: Optional[torch.Tensor], G
     """out = G .* K(X1, X2) (op "mul") or G + K(X1, X2) (op "add"), K recomputed on the fly; `out` may be G itself.  X2 None: K(X1, X1)
     with the diagonal by index; `diag_add` goes onto the diagonal of the combined result."""
     _check_op("arccos_kernel_matrix_combine", op, ("mul", "add"))
-    return _pair_builder("gpk_arccos_kernel_matrix_combine", X1, X2, G, out, op, _ARC_OPS,
-                         partial(ArcLeaf, order, variance, weight_variances, bias_variance), diag_add, None)
+    entry, leaf, max_d = _arc_route("gpk_arccos_kernel_matrix_combine", X1, partial(ArcLeaf, order, variance, weight_variances, bias_variance))
+    return _pair_builder(entry, X1, X2, G, out, op, _ARC_OPS, leaf, diag_add, None, max_d=max_d)
 
 
 def arccos_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op: str = "k", order: int = 0, variance=1.0,
@@ -359,8 +394,8 @@ def arccos_kernel_diag(X: torch.Tensor, g: Optional[torch.Tensor] = None, *, op:
     """The row diagonal kd [n] = variance jf p^order (jf = 1, 1, 3) of an ArcCosine leaf over the rows of X [n, D] (op "k"), or
     g .* kd ("mul"), g + kd ("add"), g .* dkd/dp ("dp") with g [n]; `out` may be g.  The closed form: NOT the diagonal of
     arccos_kernel_matrix(X, None) bit for bit (include/gpk.h)."""
-    return _row_diagonal("gpk_arccos_kernel_diag", "arccos_kernel_diag", _ARC_OPS, X, g, out, op,
-                         partial(ArcLeaf, order, variance, weight_variances, bias_variance))
+    entry, leaf, max_d = _arc_route("gpk_arccos_kernel_diag", X, partial(ArcLeaf, order, variance, weight_variances, bias_variance))
+    return _row_diagonal(entry, "arccos_kernel_diag", _ARC_OPS, X, g, out, op, leaf, max_d=max_d)
 
 
 def arccos_adjoint_parts(n1: int, n2: int, device_=None) -> torch.Tensor:
@@ -376,17 +411,19 @@ def arccos_adjoint_stage(X1: torch.Tensor, X2: Optional[torch.Tensor], Kbar: tor
     the per-tile sums of Kbar .* dK/dp (by row), Kbar .* dK/dq (by column) and Kbar .* K / variance.  X2 None: K(X1, X1), the diagonal
     by index.  Deterministic: a second call gives the same bits."""
     lib = _lib.load()
-    n1, n2, d, out = _kernel_operands(X1, X2, Kbar, out)
+    entry, leaf, max_d = _arc_route("gpk_arccos_adjoint_stage", X1, partial(ArcLeaf, order, variance, weight_variances, bias_variance))
+    n1, n2, d, out = _kernel_operands(X1, X2, Kbar, out, max_d=max_d)
     _chk(parts, "parts", 1)
     tr, tc = -(-n1 // ARC_TILE), -(-n2 // ARC_TILE)
     if not parts.is_contiguous() or parts.numel() < tc * n1 + tr * n2 + tr * tc:
         raise ValueError(f"arccos_adjoint_stage: parts must be a contiguous [>= {tc * n1 + tr * n2 + tr * tc}] (ops.arccos_adjoint_parts)")
     if n1 == 0 or n2 == 0:
         return out
-    order, w, ard, v, b = ArcLeaf(order, variance, weight_variances, bias_variance).abi(d)
-    rc = lib.gpk_arccos_adjoint_stage(_stream(), order, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, w, ard, v, b,
-                                      Kbar.data_ptr(), _rowmajor(Kbar, "Kbar"), out.data_ptr(), _rowmajor(out, "out"), parts.data_ptr())
-    _lib.check(rc, "gpk_arccos_adjoint_stage")
+    order, w, ard, v, b = leaf().abi(d)
+    rc = getattr(lib, entry)(_stream(), order, X1.data_ptr(), n1, _rowmajor(X1, "X1"), *_x2_args(X2, n2), d, w, ard, v, b,
+                             Kbar.data_ptr(), _rowmajor(Kbar, "Kbar"), out.data_ptr(), _rowmajor(out, "out"), parts.data_ptr(),
+                             *((parts.numel(),) if max_d > MAX_D else ()))   # (the wide entry point takes the length of parts)
+    _lib.check(rc, entry)
     return out
 
 
@@ -406,10 +443,10 @@ def arccos_adjoint_tail(R: torch.Tensor, A: torch.Tensor, Bm: Optional[torch.Ten
     n2 = n1 if Bm is None else Bm.shape[0]
     w = np.asarray(weight_variances, dtype=np.float64)
     tr, tc = -(-n1 // ARC_TILE), -(-n2 // ARC_TILE)
-    if R.shape[0] != n1 or R.shape[1] < 1 + d or d < 1 or d > MAX_D or (Bm is not None and Bm.shape[1] != d) or w.ndim > 1 \
+    if R.shape[0] != n1 or R.shape[1] < 1 + d or d < 1 or d > WIDE_MAX_D or (Bm is not None and Bm.shape[1] != d) or w.ndim > 1 \
             or (w.ndim == 1 and w.size != d) or not parts.is_contiguous() or parts.numel() < tc * n1 + tr * n2 + tr * tc:
-        raise ValueError("arccos_adjoint_tail: R must be [n1, >= 1 + D], Bm [n2, D], weight_variances one weight or [D], D in [1, 64], "
-                         "parts the stage's (ops.arccos_adjoint_parts)")
+        raise ValueError(f"arccos_adjoint_tail: R must be [n1, >= 1 + D], Bm [n2, D], weight_variances one weight or [D], D in [1, 64] "
+                         f"(one launch) or up to {WIDE_MAX_D} (two), parts the stage's (ops.arccos_adjoint_parts)")
     ard = int(w.ndim == 1)
     nw = d if ard else 1
     small = torch.zeros(nw + 2, dtype=torch.float64, device=A.device)
@@ -417,6 +454,18 @@ def arccos_adjoint_tail(R: torch.Tensor, A: torch.Tensor, Bm: Optional[torch.Ten
     if n1 == 0 or n2 == 0:
         return small[:1], small[1:1 + nw], small[1 + nw:], Abar
     rg = torch.empty(n1 + n2, dtype=torch.float64, device=A.device)
+    if d > MAX_D:   # gpk_wide_arc_adjoint_tail: the weights on the device, the blocks' partial column sums in `scratch`
+        if not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+            raise ValueError("arccos_adjoint_tail: weight_variances must be finite and not negative")
+        wd = ls_device(w, nw, A.device)
+        nblk = -(-n1 // _WIDE_ARC_TAIL_ROWS) + (0 if Bm is None else -(-n2 // _WIDE_ARC_TAIL_ROWS))
+        scratch = torch.empty(nblk * (d + 1), dtype=torch.float64, device=A.device)
+        rc = lib.gpk_wide_arc_adjoint_tail(_stream(), R.data_ptr(), _rowmajor(R, "R"), A.data_ptr(), _rowmajor(A, "A"), n1,
+                                           None if Bm is None else Bm.data_ptr(), 0 if Bm is None else _rowmajor(Bm, "Bm"), n2, d,
+                                           wd.data_ptr(), ard, parts.data_ptr(), parts.numel(), rg.data_ptr(), scratch.data_ptr(),
+                                           scratch.numel(), small.data_ptr(), Abar.data_ptr(), _rowmajor(Abar, "A_bar"))
+        _lib.check(rc, "gpk_wide_arc_adjoint_tail")
+        return small[:1], small[1:1 + nw], small[1 + nw:], Abar
     rc = lib.gpk_arccos_adjoint_tail(_stream(), R.data_ptr(), _rowmajor(R, "R"), A.data_ptr(), _rowmajor(A, "A"), n1,
                                      None if Bm is None else Bm.data_ptr(), 0 if Bm is None else _rowmajor(Bm, "Bm"), n2, d,
                                      _lib.host_doubles(np.atleast_1d(w).tolist()), ard, parts.data_ptr(), rg.data_ptr(), small.data_ptr(),

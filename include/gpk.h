@@ -652,6 +652,42 @@ int gpk_arccos_adjoint_stage(void* stream, int order, const double* X1, int n1, 
 int gpk_arccos_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, const double* B, long ldb, int n2,
                             int d, const double* w_host, int ard, const double* parts, double* rg, double* dsmall, double* Abar,
                             long ldab);
+/* ---- ArcCosine kernel, wide inputs (csrc/wide/wide_arccosine.hip) ----------------------------------------------------------------
+ * The kernel above for 1 <= d <= GPK_WIDE_MAX_D columns: an MFMA tile kernel with a K loop over 16-column slabs (128 x 128 tiles, or
+ * 64 x 64 where the larger grid would not fill the device: a function of n1, n2 and X2 == NULL alone), where gpk_arccos_* stage whole
+ * rows.  Formulas, the three contract items (diagonal by index, range, no singular forms), ops, aliasing and the layout of `parts`
+ * (one slot per 64-wide tile row / column / tile: GPK_ARC_TILE at either tile size) are those of gpk_arccos_*, with these differences:
+ *   1. w_dev is a DEVICE pointer (d doubles if ard, else one) -- 1024 doubles do not fit in kernel arguments.  It cannot be checked
+ *      on the host: the caller answers for weights that are finite and not negative.
+ *   2. x_j w_j is formed first (one rounding), as above, but the sums over j leave the fp64 matrix pipe: results are NOT bit-identical
+ *      to gpk_arccos_* at d <= GPK_MAX_D.  p(x) is four fma chains fma(x_j w_j, x_j, .), chain f over the ascending columns j with
+ *      (j % 16) / 4 == f, added in the order f = 0 .. 3, then + b: the same bits for a row as first and as second argument, at either
+ *      tile size, in the builder, the combine ops, the adjoint stage and gpk_wide_arc_kernel_diag.  No atomics anywhere: a second call
+ *      of any entry point gives the same bits.
+ *   3. `parts` and `scratch` come with their lengths in doubles; one that is shorter than the extent is GPK_E_ARG.
+ *   4. gpk_wide_arc_adjoint_tail is TWO launches.  The first runs one workgroup per GPK_WIDE_ARC_TAIL_ROWS rows of A and then (B given)
+ *      of B: it writes rg and its rows of Abar and leaves, in scratch [nblk (d + 1)], nblk = ceil(n1 / 256) + (B ? ceil(n2 / 256) : 0),
+ *      block q's partial of d/dw_j at [q (d + 1) + j] and of d/db at [q (d + 1) + d].  The second adds the blocks in block order and
+ *      the tile sums of `parts`.  n1 == 0 or n2 == 0: nothing is launched and nothing written.
+ * GPK_E_UNSUPPORTED for an order outside 0 .. 2; GPK_E_ARG, before any launch and with nothing written: d outside
+ * 1 .. GPK_WIDE_MAX_D, w_dev == NULL, b <= 0 or not finite, v not finite, a negative size, a leading dimension that is too small, an op
+ * out of range, a NULL operand that has elements, a short parts / scratch, more than 65535 tiles of rows; 0 without a launch for an
+ * operand without elements. */
+#define GPK_WIDE_ARC_TAIL_ROWS 256
+int gpk_wide_arc_kernel_matrix(void* stream, int order, const double* X1, int n1, long ldx1, const double* X2, int n2, long ldx2, int d,
+                               const double* w_dev, int ard, double variance, double bias, double diag_add, int lower_only, double* K,
+                               long ldk);
+int gpk_wide_arc_kernel_matrix_combine(void* stream, int order, int op, const double* X1, int n1, long ldx1, const double* X2, int n2,
+                                       long ldx2, int d, const double* w_dev, int ard, double variance, double bias, double diag_add,
+                                       const double* G, long ldg, double* out, long ldo);
+int gpk_wide_arc_kernel_diag(void* stream, int order, int op, const double* X, int n, long ldx, int d, const double* w_dev, int ard,
+                             double variance, double bias, const double* g, double* out);
+int gpk_wide_arc_adjoint_stage(void* stream, int order, const double* X1, int n1, long ldx1, const double* X2, int n2, long ldx2, int d,
+                               const double* w_dev, int ard, double variance, double bias, const double* Kbar, long ldkb, double* G,
+                               long ldg, double* parts, long parts_len);
+int gpk_wide_arc_adjoint_tail(void* stream, const double* R, long ldr, const double* A, long lda, int n1, const double* B, long ldb,
+                              int n2, int d, const double* w_dev, int ard, const double* parts, long parts_len, double* rg,
+                              double* scratch, long scratch_len, double* dsmall, double* Abar, long ldab);
 /* ---- ChangePoints kernel (changepoints/changepoints.hip; gpflow/kernels/changepoints.py) ---------------------------------------
  * A combination that switches between T = C + 1 member kernels along ONE input column x.  With the locations l_0 <= ... <= l_{C-1}
  * (loc_host) and the steepness s_j > 0 (steep_host), both HOST pointers with C entries, C <= GPK_CP_MAX_MEMBERS - 1:
