@@ -1268,7 +1268,12 @@ def _likelihood_stage(likelihood, Y, fmean, *, s0, ssq, knn, mean_const):
     """The variational-expectation stage of a reverse pass for likelihood = (name, params): (sum VE [1], dmu, dvar [rows, P], {grad
     name: dVE/dparameter [1]}).  A name of ops.LIKELIHOOD_CODES is one ops.likelihood_varexp_sum call, and its gradient -- where the
     likelihood class names a `device_grad_param` -- is "likelihood_<that name>".  "switched": params is the member table of
-    ops.switched_varexp_sum, the task label is the last column of Y, and the gradients are "likelihood_<t>", one per task."""
+    ops.switched_varexp_sum, the task label is the last column of Y, and the gradients are "likelihood_<t>", one per task.  "hetero":
+    params is the scale link of ops.hetero_varexp_sum, fmean is [rows, 2] (location, scale) and Y one column; no likelihood gradients."""
+    if likelihood[0] == "hetero":
+        out, _, dmu, dvar, _ = ops.hetero_varexp_sum(Y, fmean, s0=s0, ssq=ssq, knn=knn, link=likelihood[1], mean_const=mean_const,
+                                                     want_grads=True)
+        return out[0:1], dmu, dvar, {}
     if likelihood[0] == "switched":
         out, _, dmu, dvar, _ = ops.switched_varexp_sum(Y, fmean, s0=s0, ssq=ssq, knn=knn, members=likelihood[1], mean_const=mean_const,
                                                        want_grads=True)

@@ -614,7 +614,7 @@ class SwitchedLikelihood(Likelihood):
             return None if lik.has_variance_parameter else "holds its noise as `scale=`: a member's noise is one `variance` Parameter"
         if isinstance(lik, SwitchedLikelihood):
             return "is itself switched: a row has one task label"
-        if isinstance(lik, MultiClass):
+        if isinstance(lik, (MultiClass, HeteroskedasticTFPConditional)):
             return "couples the latents of a row: the per-row choice is between scalar likelihoods"
         if isinstance(lik, Ordinal):
             return "needs an edge table per task, which the switched stage's table of three constants per task does not hold"
@@ -707,3 +707,70 @@ class SwitchedLikelihood(Likelihood):
 
     def conditional_variance(self, X, F):
         self._needs_task("conditional_variance")
+
+
+class HeteroskedasticTFPConditional(Likelihood):
+    """HeteroskedasticTFPConditional(distribution_class=None, scale_transform="exp"), likelihoods/multilatent.py: TWO latent GPs per row,
+    y | f, g ~ Normal(f, s(g)^2) -- column 0 of F is the location, column 1 the unconstrained scale, s = "exp" (the reference's
+    default) or "softplus".  Only the Normal conditional is built (`distribution_class` None or "Normal"): its location integrates out
+    in closed form, so the reference's 20 x 20 quadrature grid per row becomes a closed form (exp) or a 20-node rule over the scale
+    latent alone (softplus), in one kernel (gpk_hetero_varexp_sum; the predictions: gpk_hetero_predict).  No trainable Parameter.
+    It cannot be a member of a SwitchedLikelihood (a member has one latent per column)."""
+
+    latent_dim = 2
+    observation_dim = 1
+
+    def __init__(self, distribution_class=None, scale_transform="exp"):
+        if distribution_class not in (None, "Normal"):
+            raise NotImplementedError(f"HeteroskedasticTFPConditional: only the Normal conditional is built (its location latent "
+                                      f"integrates out in closed form), got distribution_class = {distribution_class!r}")
+        if not isinstance(scale_transform, str) or scale_transform not in ops.HETERO_LINKS:
+            raise NotImplementedError(f"HeteroskedasticTFPConditional: scale_transform is one of {sorted(ops.HETERO_LINKS)}, "
+                                      f"got {scale_transform!r}")
+        self.distribution_class = "Normal"
+        self.scale_transform = scale_transform
+
+    def check_latents(self, num_latents, y_columns=None):
+        """ValueError unless the latents are the two of a row and Y has its one column"""
+        if int(num_latents) != self.latent_dim:
+            raise ValueError(f"HeteroskedasticTFPConditional needs {self.latent_dim} latent GPs (location, scale), got {int(num_latents)}")
+        if y_columns is not None and int(y_columns) != self.observation_dim:
+            raise ValueError(f"HeteroskedasticTFPConditional: Y has one column, got {int(y_columns)}")
+
+    def _flat(self, Fmu, Fvar, Y=None):
+        """(fmean [N, 2], fvar [N, 2], Y [N, 1] | None, leading shape), refusing other widths before the device is touched"""
+        self.check_latents(tuple(Fmu.shape)[-1], None if Y is None else tuple(Y.shape)[-1])
+        Fmu, Fvar = ops.to_device(Fmu), ops.to_device(Fvar)
+        Yd = None if Y is None else ops.to_device(Y).reshape(-1, 1)
+        return Fmu.reshape(-1, 2).contiguous(), Fvar.reshape(-1, 2).contiguous(), Yd, Fmu.shape[:-1]
+
+    def _scale(self, G):
+        return torch.exp(G) if self.scale_transform == "exp" else torch.nn.functional.softplus(G)
+
+    def conditional_mean(self, X, F):
+        return ops.to_device(F)[..., :1]
+
+    def conditional_variance(self, X, F):
+        return self._scale(ops.to_device(F)[..., 1:]) ** 2
+
+    def variational_expectations(self, X, Fmu, Fvar, Y) -> torch.Tensor:
+        """per-row values [N] (the reference: a 20 x 20 grid; here gpk_hetero_varexp_sum)"""
+        Fm, Fv, Yd, lead = self._flat(Fmu, Fvar, Y)
+        rows = ops.hetero_varexp_sum(Yd, Fm, s0=None, ssq=Fv.t().contiguous(), knn=[0.0], link=self.scale_transform, want_rows=True)[1]
+        return rows.reshape(lead)
+
+    def log_prob(self, X, F, Y):
+        """log N(y | f, s(g)^2) [N]: the predictive density of a point mass at F (zero variances: every node of the rule is g)"""
+        F = ops.to_device(F)
+        return self.predict_log_density(X, F, torch.zeros_like(F), Y)
+
+    def predict_mean_and_var(self, X, Fmu, Fvar):
+        """([N, 1], [N, 1]): the location mean, and Fvar[:, 0] + E[s(g)^2]"""
+        Fm, Fv, _, lead = self._flat(Fmu, Fvar)
+        mean, var, _ = ops.hetero_predict(Fm, Fv, link=self.scale_transform)
+        return mean.reshape(lead + (1,)), var.reshape(lead + (1,))
+
+    def predict_log_density(self, X, Fmu, Fvar, Y):
+        """log int N(y | m1, v1 + s(g)^2) N(g | m2, v2) dg by the 20-node rule, [N]"""
+        Fm, Fv, Yd, lead = self._flat(Fmu, Fvar, Y)
+        return ops.hetero_predict(Fm, Fv, Yd, link=self.scale_transform)[2].reshape(lead)

@@ -10,7 +10,7 @@ from .. import ops
 from ..base import Module
 from ..config import default_jitter
 from ..kernels import Kernel, MultioutputKernel
-from ..likelihoods import Likelihood, SwitchedLikelihood
+from ..likelihoods import HeteroskedasticTFPConditional, Likelihood, SwitchedLikelihood
 from ..mean_functions import MeanFunction, Zero
 from ..posteriors import assert_params_false
 
@@ -50,6 +50,8 @@ class GPModel(BayesianModel):
     def __init__(self, kernel: Kernel, likelihood: Likelihood, mean_function: Optional[MeanFunction] = None,
                  num_latent_gps: Optional[int] = None):
         assert num_latent_gps is not None, "GPModel requires specification of num_latent_gps"
+        if isinstance(likelihood, HeteroskedasticTFPConditional):   # (its two latents are the location and the scale of a row)
+            likelihood.check_latents(num_latent_gps)
         self.num_latent_gps = num_latent_gps
         if mean_function is None:
             mean_function = Zero()
@@ -66,6 +68,9 @@ class GPModel(BayesianModel):
             return kernel.num_latent_gps
         if isinstance(likelihood, SwitchedLikelihood):   # (calc_num_latent_gps, model.py:153-170: the last column of Y is the task label)
             return output_dim - 1
+        if isinstance(likelihood, HeteroskedasticTFPConditional):   # (likelihood.latent_dim: location and scale; Y is one column)
+            likelihood.check_latents(likelihood.latent_dim, output_dim)
+            return likelihood.latent_dim
         return output_dim
 
     @abc.abstractmethod

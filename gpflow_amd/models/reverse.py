@@ -12,7 +12,7 @@ from ..inducing_variables import (InducingPatches, InducingPoints, SeparateIndep
 from ..kernels import LinearCoregionalization, SeparateIndependent, SharedIndependent
 from ..kernels.base import Combination, changepoint_nodes, gradient_spec, has_row_diagonal_leaf, reverse_leaf
 from ..kernels.periodic import Periodic
-from ..likelihoods import Gaussian, SwitchedLikelihood
+from ..likelihoods import Gaussian, HeteroskedasticTFPConditional, SwitchedLikelihood
 from ..mean_functions import Constant
 
 
@@ -189,6 +189,17 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
     A dot-product kernel or member (Linear, Polynomial; `has_row_diagonal`): the plain routes of the first two lines only -- with
     quadrature, narrow, SeparateIndependent or LinearCoregionalization it is refused here, by the limit it breaks."""
     k, iv = model.kernel, model.inducing_variable
+    if isinstance(model.likelihood, HeteroskedasticTFPConditional):   # the scope of the quadrature reverse pass, each limit by name
+        no = lambda what: NotImplementedError(f"gradients: HeteroskedasticTFPConditional {what}")   # noqa: E731
+        if narrow:
+            raise no("is outside the natural gradients (a Gaussian likelihood with a constant noise)")
+        if not quadrature:
+            raise no("is outside training.SVGPTrainer's device step (a Gaussian likelihood); use SVGP.elbo_and_grad / optimizers.Scipy")
+        if isinstance(k, (SeparateIndependent, LinearCoregionalization)):
+            raise no("with one kernel per latent runs forward only (SVGP.elbo): the quadrature reverse pass takes ONE kernel shared by "
+                     "the latents")
+        if not model.whiten:
+            raise no("un-whitened runs forward only (SVGP.elbo): the quadrature reverse pass is whitened")
     if has_row_diagonal(k):   # Linear / Polynomial: covered by the plain route alone -- every other one takes K(x, x) for one scalar
         limit = "the quadrature likelihoods' reverse pass: its variational expectations take K(x, x) as one value per latent" if quadrature \
             else "natural gradients: their reverse pass is the packed one-kernel form with a scalar K(x, x)" if narrow \
@@ -203,7 +214,7 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
         raise NotImplementedError("gradients: a Convolutional kernel is not built into the natural gradients (the packed one-kernel "
                                   "reverse pass with a scalar K(x, x))")
     plain = not (quadrature or narrow)
-    lik_ok = (model.whiten and (model._device_likelihood() or model._switched_likelihood())) if quadrature \
+    lik_ok = (model.whiten and (model._device_likelihood() or model._switched_likelihood() or model._hetero_likelihood())) if quadrature \
         else _gaussian_noise(model.likelihood, not narrow)
     q_full = model.q_sqrt.numpy().ndim == 3
     separate = isinstance(k, SeparateIndependent)
@@ -269,7 +280,7 @@ def vgp_scope(model):
     """The mean constant of a VGP inside its device paths, else NotImplementedError -- checked when the model is BUILT and again by
     every route, before anything touches the device: a single-output kernel, a zero or constant mean, and a Gaussian likelihood with
     one noise variance or a likelihood whose variational expectations the library computes (`device_lik`; at most 16 latents, which
-    for MultiClass are its classes), or a SwitchedLikelihood with at most 16 latents."""
+    for MultiClass are its classes), or a SwitchedLikelihood with at most 16 latents, or a HeteroskedasticTFPConditional (two latents)."""
     from ..kernels import MultioutputKernel
     from .. import ops
     lik, R = model.likelihood, model.q_mu.shape[1]
@@ -282,6 +293,8 @@ def vgp_scope(model):
     elif isinstance(lik, SwitchedLikelihood):
         if R > 16:
             raise no("a SwitchedLikelihood with more than 16 latents (the columns of one call of its stage)")
+    elif isinstance(lik, HeteroskedasticTFPConditional):
+        lik.check_latents(R)   # (ValueError: its latents are the location and the scale of a row)
     elif getattr(lik, "device_lik", "") not in ops.LIKELIHOOD_CODES:
         raise no(f"the likelihood {type(lik).__name__} has no variational-expectation kernel on the device (`device_lik`)")
     elif hasattr(lik, "check_device_classes"):

@@ -14,7 +14,7 @@ from ..inducing_variables import (InducingPoints, SharedIndependentInducingVaria
 from ..kernels import Kernel
 from ..kernels.base import fits_fused_drivers, is_device_leaf
 from ..leaf import latent_keywords
-from ..likelihoods import Gaussian, Likelihood, MultiClass, ScalarLikelihood, SwitchedLikelihood
+from ..likelihoods import Gaussian, HeteroskedasticTFPConditional, Likelihood, MultiClass, ScalarLikelihood, SwitchedLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
 from .reverse import shared_pair
@@ -23,14 +23,19 @@ from .training_mixins import ExternalDataTrainingLossMixin
 
 class SVGP(GPModel, ExternalDataTrainingLossMixin):
     def __init__(self, kernel: Kernel, likelihood: Likelihood, inducing_variable, *,
-                 mean_function: Optional[MeanFunction] = None, num_latent_gps: int = 1,
+                 mean_function: Optional[MeanFunction] = None, num_latent_gps: Optional[int] = None,
                  q_diag: bool = False, q_mu=None, q_sqrt=None, whiten: bool = True, num_data=None):
+        hetero = isinstance(likelihood, HeteroskedasticTFPConditional)
+        if num_latent_gps is None:   # (1, as in the reference; the two latents of a row for the heteroskedastic likelihood)
+            num_latent_gps = likelihood.latent_dim if hetero else 1
         super().__init__(kernel, likelihood, mean_function, num_latent_gps)
         self.num_data = num_data
         self.whiten = whiten
         self.inducing_variable = inducingpoint_wrapper(inducing_variable)
         num_inducing = self.inducing_variable.num_inducing
         self._init_variational_parameters(num_inducing, q_mu, q_sqrt, q_diag)
+        if hetero:   # (q_mu / q_sqrt handed in set the count too)
+            likelihood.check_latents(self.q_mu.shape[1])
         self._ws = None
 
     def _init_variational_parameters(self, num_inducing, q_mu, q_sqrt, q_diag) -> None:
@@ -91,6 +96,11 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         """a SwitchedLikelihood with at most 16 latents: the composed ELBO and the quadrature reverse pass take it; the fused shard
         (gpk_svgp_elbo_shard_lik: one code per launch) does not, so `_device_likelihood` stays false for it"""
         return isinstance(self.likelihood, SwitchedLikelihood) and self.q_mu.shape[1] <= 16
+
+    def _hetero_likelihood(self) -> bool:
+        """the heteroskedastic two-latent likelihood: as the switched one, the composed ELBO and the quadrature reverse pass take it and
+        the fused shards decline it"""
+        return isinstance(self.likelihood, HeteroskedasticTFPConditional)
 
     def _fused_separate_config(self):
         """(member kernels, Z [m, d] | [P, m, d], mean constant) when the ELBO shard of a SeparateIndependent model is one
@@ -252,6 +262,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         if isinstance(self.likelihood, MultiClass):   # (refused before anything touches the device)
             self.likelihood.check_device_classes(self.q_mu.shape[1])
         self._check_mixing_widths(data[1])
+        if self._hetero_likelihood():   # (refused before anything touches the device)
+            self.likelihood.check_latents(self.q_mu.shape[1], np.shape(data[1])[-1])
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])
         fused = self._fused_config()
         if fused is not None:
@@ -335,9 +347,12 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         from .. import gradients
         from . import reverse
         lik = self.likelihood
-        quad, switched = isinstance(lik, (ScalarLikelihood, MultiClass, SwitchedLikelihood)), isinstance(lik, SwitchedLikelihood)
+        switched, hetero = isinstance(lik, SwitchedLikelihood), self._hetero_likelihood()
+        quad = isinstance(lik, (ScalarLikelihood, MultiClass, SwitchedLikelihood)) or hetero
         routes, c, separate = reverse.svgp_routes(self, quadrature=quad)
         self._check_mixing_widths(data[1])
+        if hetero:
+            lik.check_latents(self.q_mu.shape[1], np.shape(data[1])[-1])
         X, Y = ops.to_device(data[0]), ops.to_device(data[1])
         from ..kernels import LinearCoregionalization
         if isinstance(self.kernel, LinearCoregionalization):
@@ -345,7 +360,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         kw = dict(jitter=config.default_jitter(), scale=reverse.minibatch_scale(self.num_data, X.shape[0]), mean_const=c)
         if quad:
             kw.update(noise_variance=None,
-                      likelihood=("switched", lik.device_members()) if switched else (lik.device_lik, lik.device_params()))
+                      likelihood=("switched", lik.device_members()) if switched else ("hetero", lik.scale_transform) if hetero
+                      else (lik.device_lik, lik.device_params()))
         else:
             kw["noise_variance"] = lik.noise_for(X)
         fn = gradients.svgp_elbo_and_grad if self.whiten else gradients.svgp_elbo_and_grad_unwhitened
@@ -374,6 +390,8 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
                    (self.q_sqrt, np.concatenate([h["q_sqrt"] for h in hosts], axis=0))]
         if switched:   # (out[1 + t] of the stage: task t's Parameter, a Gaussian member's variance included)
             lik_pairs = [(par, hosts[0][f"likelihood_{t}"]) for t, par in enumerate(lik.device_grad_params()) if par is not None]
+        elif hetero:   # (no trainable Parameter)
+            lik_pairs = []
         elif quad:
             name = getattr(lik, "device_grad_param", None)   # (the Parameter the kernel's out[1] differentiates, if the class has one)
             lik_pairs = [(getattr(lik, name), hosts[0]["likelihood_" + name])] if name else []

@@ -10,7 +10,7 @@ from .. import config, ops
 from ..base import Parameter, triangular
 from ..conditionals import conditional
 from ..kernels import Kernel
-from ..likelihoods import Gaussian, Likelihood, SwitchedLikelihood
+from ..likelihoods import Gaussian, HeteroskedasticTFPConditional, Likelihood, SwitchedLikelihood
 from ..mean_functions import MeanFunction
 from .model import GPModel
 from .training_mixins import InternalDataTrainingLossMixin
@@ -24,11 +24,14 @@ class VGP(GPModel, InternalDataTrainingLossMixin):
 
     Scope (reverse.vgp_scope, refused when the model is built): a single-output kernel, a zero or constant mean, a Gaussian likelihood
     with one noise variance or any likelihood with a `device_lik` (MultiClass: one latent per class, Y one column of labels), or a
-    SwitchedLikelihood (the last column of Y is the task label; at most 16 latents)."""
+    SwitchedLikelihood (the last column of Y is the task label; at most 16 latents), or a HeteroskedasticTFPConditional (two latents, Y one
+    column)."""
 
     def __init__(self, data, kernel: Kernel, likelihood: Likelihood, mean_function: Optional[MeanFunction] = None,
                  num_latent_gps: Optional[int] = None):
         X, Y = data
+        if isinstance(likelihood, HeteroskedasticTFPConditional):   # (two latents per row, Y one column: a ValueError otherwise)
+            likelihood.check_latents(likelihood.latent_dim if num_latent_gps is None else num_latent_gps, np.shape(Y)[-1])
         if num_latent_gps is None:
             num_latent_gps = self.calc_num_latent_gps_from_data(data, kernel, likelihood)
         super().__init__(kernel, likelihood, mean_function, num_latent_gps)
@@ -80,8 +83,10 @@ class VGP(GPModel, InternalDataTrainingLossMixin):
         X, Y = self.data
         _, Xs, _ = route.inputs(None, X)     # active_dims (kernels/base.py:90-109); nothing is differentiated w.r.t. X
         gaussian, switched = isinstance(lik, Gaussian), isinstance(lik, SwitchedLikelihood)
+        hetero = isinstance(lik, HeteroskedasticTFPConditional)
         kw = dict(noise_variance=lik.noise_variance()) if gaussian else \
-            dict(likelihood=("switched", lik.device_members()) if switched else (lik.device_lik, lik.device_params()))
+            dict(likelihood=("switched", lik.device_members()) if switched else ("hetero", lik.scale_transform) if hetero
+                 else (lik.device_lik, lik.device_params()))
         F, g, info = gradients.vgp_elbo_and_grad(Xs, Y, self.q_mu.device_value(), self.q_sqrt.device_value(), kernel_spec=route.spec,
                                                  jitter=config.default_jitter(), mean_const=c, **kw)
         ops.check_info(info)
@@ -89,6 +94,8 @@ class VGP(GPModel, InternalDataTrainingLossMixin):
             lik_pairs = reverse.noise_pairs(lik, X, g["noise_variance"])
         elif switched:   # (out[1 + t] of the stage: task t's Parameter, a Gaussian member's variance included)
             lik_pairs = [(par, g[f"likelihood_{t}"].cpu().numpy()) for t, par in enumerate(lik.device_grad_params()) if par is not None]
+        elif hetero:   # (no trainable Parameter)
+            lik_pairs = []
         else:
             name = getattr(lik, "device_grad_param", None)   # (the Parameter the kernel's out[1] differentiates, if the class has one)
             lik_pairs = [(getattr(lik, name), g["likelihood_" + name].cpu().numpy())] if name else []

@@ -1282,6 +1282,98 @@ def switched_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[to
     return out, rws, dmu, dvar, fvar
 
 
+HETERO_LINKS = {"exp": 0, "softplus": 1}   # GPK_HETERO_LINK_*
+
+
+def _hetero_link(link) -> int:
+    if link not in HETERO_LINKS:
+        raise ValueError(f"unknown scale link {link!r} of the heteroskedastic likelihood: one of {sorted(HETERO_LINKS)}")
+    return HETERO_LINKS[link]
+
+
+def hetero_parts(n: int, device_=None) -> torch.Tensor:
+    """the scratch operand `parts` of gpk_hetero_varexp_sum for n rows: one double per block and the ticket word behind them, at the
+    extent of the "softplus" layout (64 rows per block), which covers the "exp" one (256)"""
+    if n < 0:
+        raise ValueError("hetero_parts: n must be non-negative")
+    nb = int(_lib.load().gpk_hetero_varexp_blocks(int(n), HETERO_LINKS["softplus"])) if n else 0
+    return torch.empty(nb + 1, dtype=torch.float64, device=device() if device_ is None else device_)
+
+
+def hetero_varexp_sum(Y: torch.Tensor, fmean: torch.Tensor, *, s0: Optional[torch.Tensor], ssq: Optional[torch.Tensor],
+                      knn: Sequence[float], link: str, mean_const: float = 0.0, s0_per_latent: bool = False, want_fvar: bool = False,
+                      want_rows: bool = False, want_grads: bool = False, parts: Optional[torch.Tensor] = None):
+    """Variational expectations of the heteroskedastic Normal likelihood over two latents per row (gpk_hetero_varexp_sum): Y [rows, 1],
+    fmean [rows, 2] = (location, unconstrained scale), y ~ N(f, link(g)^2) with link "exp" or "softplus"; fvar = knn - s0 + ssq per
+    latent.  Returns (out [1], rows | None, dmu | None, dvar | None, fvar | None), the tuple of switched_varexp_sum: out[0] = the sum
+    over the rows, rows [rows] its terms, dmu, dvar [rows, 2] = d/dfmean, d/dfvar of every term.  `parts`: the scratch of
+    hetero_parts (allocated here when None)."""
+    code = _hetero_link(link)
+    _chk(Y, "Y", 2)
+    _chk(fmean, "fmean", 2)
+    rows, P = fmean.shape
+    if P != 2 or not fmean.is_contiguous():
+        raise ValueError("fmean must be contiguous [rows, 2]: the location and the scale latent of every row")
+    if Y.shape[0] != rows or Y.shape[1] != 1:
+        raise ValueError("Y must be [rows, 1]: one observation column, one row per row of fmean")
+    for name, t, shape in (("s0", s0, (P, rows) if s0_per_latent else (rows,)), ("ssq", ssq, (P, rows))):
+        if t is not None:
+            _chk(t, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous {shape}")
+    knn = list(np.atleast_1d(np.asarray(knn, dtype=np.float64)))
+    if len(knn) not in (1, P):
+        raise ValueError("knn: one value, or one per latent (2)")
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=Y.device)
+    fvar = new(rows, P) if want_fvar else None
+    rws = new(rows) if want_rows else None
+    dmu, dvar = (new(rows, P), new(rows, P)) if want_grads else (None, None)
+    if rows == 0:   # (no launch)
+        return torch.zeros(1, dtype=torch.float64, device=Y.device), rws, dmu, dvar, fvar
+    lib = _lib.load()
+    out = new(1)
+    need = int(lib.gpk_hetero_varexp_blocks(rows, code)) + 1
+    if parts is None:
+        parts = new(need)
+    else:
+        _chk(parts, "parts", 1)
+        if parts.numel() < need or not parts.is_contiguous():
+            raise ValueError(f"parts must be contiguous with at least {need} entries (hetero_parts)")
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    rc = lib.gpk_hetero_varexp_sum(_stream(), code, Y.data_ptr(), _rowmajor(Y, "Y"), fmean.data_ptr(), rows, ptr(s0),
+                                   int(s0_per_latent), ptr(ssq), _lib.host_doubles(knn), int(len(knn) > 1), float(mean_const),
+                                   ptr(fvar), ptr(rws), ptr(dmu), ptr(dvar), out.data_ptr(), parts.data_ptr())
+    _lib.check(rc, "gpk_hetero_varexp_sum")
+    return out, rws, dmu, dvar, fvar
+
+
+def hetero_predict(fmean: torch.Tensor, fvar: torch.Tensor, Y: Optional[torch.Tensor] = None, *, link: str):
+    """Predictive quantities of the heteroskedastic Normal likelihood (gpk_hetero_predict) from fmean, fvar [rows, 2]: (mean [rows],
+    var [rows], log density [rows] | None).  mean = the location mean, var = fvar[:, 0] + E[link(g)^2]; with Y [rows, 1] the log of
+    the 20-node rule over the scale latent of N(y | mean, fvar[:, 0] + link(g)^2), else None."""
+    code = _hetero_link(link)
+    _chk(fmean, "fmean", 2)
+    _chk(fvar, "fvar", 2)
+    rows = fmean.shape[0]
+    if fmean.shape[1] != 2 or tuple(fvar.shape) != (rows, 2) or not (fmean.is_contiguous() and fvar.is_contiguous()):
+        raise ValueError("fmean and fvar must be contiguous [rows, 2]: the location and the scale latent of every row")
+    if Y is not None:
+        _chk(Y, "Y", 2)
+        if tuple(Y.shape) != (rows, 1):
+            raise ValueError("Y must be [rows, 1]")
+    mean, var = (torch.empty(rows, dtype=torch.float64, device=fmean.device) for _ in range(2))
+    ld = torch.empty(rows, dtype=torch.float64, device=fmean.device) if Y is not None else None
+    if rows == 0:   # (no launch)
+        return mean, var, ld
+    rc = _lib.load().gpk_hetero_predict(_stream(), code, fmean.data_ptr(), fvar.data_ptr(), None if Y is None else Y.data_ptr(),
+                                        1 if Y is None else _rowmajor(Y, "Y"), rows, mean.data_ptr(), var.data_ptr(),
+                                        None if ld is None else ld.data_ptr())
+    _lib.check(rc, "gpk_hetero_predict")
+    return mean, var, ld
+
+
 def gauss_kl_white(q_mu: torch.Tensor, q_sqrt: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     _chk(q_mu, "q_mu", 2)

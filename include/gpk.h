@@ -443,6 +443,49 @@ int gpk_switched_varexp_sum(void* stream, int T, const int* codes_host, const do
                             const double* fmean, int rows, int P, const double* s0, int s0_per_latent, const double* ssq,
                             const double* knn_host, int knn_per_latent, double mean_const, double* fvar_out, double* rows_out,
                             double* dmu_out, double* dvar_out, double* out, double* parts);
+/* The heteroskedastic Normal likelihood over TWO latent GPs per row (likelihoods/multilatent.py HeteroskedasticTFPConditional with the
+ * Normal conditional; csrc/hetero/hetero_varexp.hip): y | f, g ~ N(f, s(g)^2) with s = exp (GPK_HETERO_LINK_EXP) or softplus
+ * (GPK_HETERO_LINK_SOFTPLUS); any other link is GPK_E_ARG, judged before any pointer is looked at.  The operands are those of
+ * gpk_switched_varexp_sum without the member table and the label column, with P = 2 fixed: Y [rows, 1] with row stride ldy >= 1,
+ * fmean contiguous [rows, 2] (column 0 the location latent, column 1 the scale latent), s0 [rows] or [2, rows] (s0_per_latent), ssq
+ * [2, rows], either may be NULL; knn a HOST pointer (2 values if knn_per_latent else 1); mean_const is added to BOTH latents, as a
+ * mean function is.  With m1, m2 = fmean + mean_const, v1, v2 = knn - s0 + ssq (in this order), a = (y - m1)^2 + v1:
+ *     VE_b = -0.5 log 2pi - E1 - 0.5 a E2,          E1 = E_g[log s(g)],  E2 = E_g[s(g)^-2],  g ~ N(m2, v2)
+ *     dmu[b] = { (y - m1) E2,  -dE1/dm2 - 0.5 a dE2/dm2 },    dvar[b] = { -0.5 E2,  -dE1/dv2 - 0.5 a dE2/dv2 }
+ *   exp:      E1 = m2, E2 = exp(2 v2 - 2 m2): closed forms, no nodes; dmu[b,1] = -1 + a E2, dvar[b,1] = -a E2.
+ *   softplus: the 20-node rule E[h] = sum_h (w_h / sqrt pi) h(m2 + sqrt(2 v2) x_h) over the table of gpk_gauss_hermite, and
+ *             dE[h]/dm2 = E[h'], dE[h]/dv2 = E[h''] / 2 by the SAME rule (the derivatives of the integral; nothing is divided by
+ *             sqrt(v2), so v2 = 0 gives the one-point values).  The contract is the rule, not the integral.  Per node, g >= 0:
+ *             s = g + log1p(exp(-g)), which cannot overflow and is g itself from g > 37 on; -37 <= g < 0: s = log1p(exp(g)); g < -37:
+ *             s = exp(g), log s = g, s^-2 = exp(-2 g), (log s)' = 1, (log s)'' = 0 -- each within exp(-37) = 8.6e-17 relative (for
+ *             (log s)'': absolute) of the exact value, below the unit roundoff, so the tail of neither log s nor s^-2 is lost.
+ *   Outputs: out[0] = sum_b VE_b; rows_out[b] = VE_b; dmu_out, dvar_out [rows, 2] as above; fvar_out [rows, 2] = the variances; all
+ *   but out optional.  rows = 0 writes out[0] = 0 and nothing else.
+ *   Non-finite input: a NaN or +-Inf in a row's y, m1, v1, m2 or v2 makes VE_b, all four seeds of the row and out[0] NaN, and changes
+ *   no bit of any other row's outputs.  Overflow of FINITE operands is not clamped: under exp, E2 = +Inf from 2 v2 - 2 m2 > 709.78 on
+ *   (v2 = 400), and the outputs are the IEEE results VE = -Inf, dmu = {+-Inf by the sign of y - m1, +Inf}, dvar = {-Inf, -Inf}, out[0] =
+ *   -Inf (with a = 0 exactly, 0 * Inf: NaN).  A negative v2 is NaN under softplus (sqrt) and enters the closed form as it is under exp.
+ *   Layout: exp one lane per row, 256 rows per block; softplus four lanes per row, 64 rows per block; at most 1024 blocks, i.e.
+ *   gpk_hetero_varexp_blocks(rows, link) = min(1024, ceil(rows / rows per block)) (0 for an unknown link), beyond which a block walks
+ *   on with a stride of 1024 blocks of rows.
+ *   Deterministic: block sums in a fixed order, the last block to finish (an integer ticket) adds them in index order; no
+ *   floating-point atomics; a second call returns the same bits, and a row's outputs do not depend on where the row sits.
+ *   Scratch: parts, gpk_hetero_varexp_blocks(rows, link) + 1 doubles: one per block, and the ticket word behind them, which the call
+ *   resets itself; its contents at entry do not matter and nothing past that extent is touched.
+ * gpk_hetero_predict: per row, from fmean, fvar contiguous [rows, 2] (no mean constant, no s0 / ssq forms) and optionally Y:
+ *     mean_out[b] = m1,   var_out[b] = v1 + E_g[s(g)^2]   (exp: exp(2 m2 + 2 v2); softplus: the 20-node rule)
+ *     logdens_out[b] = log sum_h (w_h / sqrt pi) N(y | m1, v1 + s(g_h)^2),  g_h = m2 + sqrt(2 v2) x_h   (both links: no closed form)
+ *   as a max-shifted log-sum-exp.  Y == NULL: the log density is not computed and logdens_out is not touched; with Y, logdens_out is
+ *   required (GPK_E_ARG).  mean_out and var_out may be NULL.  A NaN term makes the row's log density NaN; a row whose every term is
+ *   -Inf is -Inf.  Lane layouts, rows per block and the grid clamp are those above; rows = 0 launches nothing. */
+#define GPK_HETERO_LINK_EXP 0
+#define GPK_HETERO_LINK_SOFTPLUS 1
+int gpk_hetero_varexp_blocks(int rows, int link);
+int gpk_hetero_varexp_sum(void* stream, int link, const double* Y, long ldy, const double* fmean, int rows, const double* s0,
+                          int s0_per_latent, const double* ssq, const double* knn_host, int knn_per_latent, double mean_const,
+                          double* fvar_out, double* rows_out, double* dmu_out, double* dvar_out, double* out, double* parts);
+int gpk_hetero_predict(void* stream, int link, const double* fmean, const double* fvar, const double* Y, long ldy, int rows,
+                       double* mean_out, double* var_out, double* logdens_out);
 /* Gaussian variational expectations of LINEARLY MIXED latents -- the stage between the latent moments and the likelihood of a
  * LinearCoregionalization model (kernels/multioutput/kernels.py LinearCoregionalization, conditionals/util.py mix_latent_gp):
  * L latent GPs g, P outputs f = W g, W [P, L] row-major on the HOST, 1 <= L, P <= 16.  The latent operands are those of
