@@ -152,6 +152,15 @@ _SIGS = {
     "gpk_conv_kdiag_partials_len": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "gpk_conv_kdiag_adjoint": (c_int, [c_void_p, _dp, c_int, c_long, c_int, c_int, c_int, c_int, c_int, _dp, c_double, c_double, _dp, _dp,
                                        _dp, _dp]),
+    "gpk_multiscale_parts_len": (c_size_t, [c_int, c_int]),
+    "gpk_multiscale_kfu": (c_int, [c_void_p, _dp, c_int, c_long, _dp, _dp, c_int, c_long, c_long, c_int, C.POINTER(c_double), c_int,
+                                   c_double, c_int, _dp, c_long, _dp, c_long]),
+    "gpk_multiscale_kuu": (c_int, [c_void_p, _dp, _dp, c_int, c_long, c_long, c_int, C.POINTER(c_double), c_int, c_double, c_double,
+                                   c_int, _dp, c_long, _dp, c_long]),
+    "gpk_multiscale_kuu_adjoint_stage": (c_int, [c_void_p, _dp, _dp, c_int, c_long, c_long, c_int, C.POINTER(c_double), c_int, c_double,
+                                                 _dp, c_long, _dp, c_long]),
+    "gpk_multiscale_adjoint_tail": (c_int, [c_void_p, c_int, _dp, _dp, c_int, c_long, c_long, c_int, C.POINTER(c_double), c_int, c_double,
+                                            _dp, c_long, c_long, _dp, _dp, c_long, _dp, c_long, _dp]),
     "gpk_tril_product_tiles": (c_int, [c_int]),
     "gpk_tril_product": (c_int, [c_void_p, _dp, c_int, c_long, _dp, c_long, c_long, c_int, _dp, _dp, _dp, _dp, c_long, c_long]),
     "gpk_adam_step": (c_int, [c_void_p, _dp, _dp, _dp, _dp, c_long, c_double, c_double, c_double, c_double, c_int]),

@@ -6,9 +6,9 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from .inducing_variables import (InducingPatches, InducingPoints, SeparateIndependentInducingVariables,
+from .inducing_variables import (InducingPatches, InducingPoints, Multiscale, SeparateIndependentInducingVariables,
                                  SharedIndependentInducingVariables)
-from .kernels import Kernel, LinearCoregionalization, MultioutputKernel, SeparateIndependent, SharedIndependent
+from .kernels import Kernel, LinearCoregionalization, MultioutputKernel, SeparateIndependent, SharedIndependent, SquaredExponential
 
 
 def _pairs(inducing_variable, kernel):
@@ -46,9 +46,49 @@ def patch_pair(inducing_variable, kernel) -> bool:
     return patches
 
 
+def multiscale_pair(inducing_variable, kernel) -> bool:
+    """True for (Multiscale, SquaredExponential) -- the one pair kuus.py / kufs.py register for Multiscale -- and NotImplementedError for
+    Multiscale, bare or inside a multi-output wrapper, with anything else, before the device is touched"""
+    inner = getattr(inducing_variable, "inducing_variables", ())
+    if any(isinstance(v, Multiscale) for v in inner):
+        raise NotImplementedError("Kuu/Kuf: Multiscale inducing variables inside Shared / SeparateIndependentInducingVariables are not built: "
+                                  "the multi-output rows of kuus.py / kufs.py take inducing points")
+    if not isinstance(inducing_variable, Multiscale):
+        return False
+    if type(kernel) is not SquaredExponential:
+        raise NotImplementedError(f"Kuu/Kuf: (Multiscale, {type(kernel).__name__}) -- Multiscale inducing variables go with one "
+                                  "SquaredExponential kernel: no other family, combination, Periodic, Convolutional or multi-output wrapper")
+    return True
+
+
+def multiscale_operands(inducing_variable, kernel, X=None):
+    """(Z, scales, X) on the device as the multiscale builders take them: all three sliced by the kernel's `active_dims`; a width above
+    ops.MAX_D is a ValueError before the device"""
+    dims, D = kernel._active_dims, int(inducing_variable.Z.shape[1])
+    width = len(range(D)[dims]) if isinstance(dims, slice) else len(dims)
+    if width > ops.MAX_D:
+        raise ValueError(f"Multiscale: {width} input columns, the builders take up to {ops.MAX_D}")
+    Zs, Ss = kernel.slice(inducing_variable.Z.device_value(), inducing_variable.scales.device_value())
+    return Zs, Ss, (None if X is None else kernel.slice(ops.to_device(X), None)[0])
+
+
+def multiscale_Kuu(inducing_variable, kernel, out=None, *, jitter: float = 0.0):
+    Zs, Ss, _ = multiscale_operands(inducing_variable, kernel)
+    leaf = kernel.leaf()
+    return ops.multiscale_kuu(Zs, Ss, variance=leaf.variance, lengthscales=leaf.lengthscales, diag_add=jitter, out=out)
+
+
+def multiscale_Kfu(inducing_variable, kernel, Xnew, out=None):
+    Zs, Ss, Xs = multiscale_operands(inducing_variable, kernel, Xnew)
+    leaf = kernel.leaf()
+    return ops.multiscale_kfu(Xs, Zs, Ss, variance=leaf.variance, lengthscales=leaf.lengthscales, out=out)
+
+
 def Kuu(inducing_variable, kernel, *, jitter: float = 0.0) -> torch.Tensor:
-    """[M,M] (InducingPoints x Kernel: kuus.py:24-34; Shared x Shared: multioutput/kuus.py:49-62)
-    or [L,M,M] (any Separate combination: multioutput/kuus.py:65-121)."""
+    """[M,M] (InducingPoints x Kernel: kuus.py:24-34; Multiscale x SquaredExponential: kuus.py:37-57; Shared x Shared:
+    multioutput/kuus.py:49-62) or [L,M,M] (any Separate combination: multioutput/kuus.py:65-121)."""
+    if multiscale_pair(inducing_variable, kernel):
+        return multiscale_Kuu(inducing_variable, kernel, jitter=jitter)
     if patch_pair(inducing_variable, kernel):
         return kernel.Kuu_into(inducing_variable.Z.device_value(), None, diag_add=jitter)
     if isinstance(inducing_variable, InducingPoints) and not isinstance(kernel, MultioutputKernel):
@@ -63,6 +103,8 @@ def Kuu(inducing_variable, kernel, *, jitter: float = 0.0) -> torch.Tensor:
 
 def Kfu(inducing_variable, kernel, Xnew) -> torch.Tensor:
     """K(Xnew, Z): the row-major [N,M] (or [L,N,M]) layout the device solves consume."""
+    if multiscale_pair(inducing_variable, kernel):   # (refused, or its width checked, before Xnew is copied to the device)
+        return multiscale_Kfu(inducing_variable, kernel, Xnew)
     if patch_pair(inducing_variable, kernel):   # (a half pair is refused here, before Xnew is copied to the device)
         return kernel.Kfu_into(ops.to_device(Xnew), inducing_variable.Z.device_value(), None)
     Xnew = ops.to_device(Xnew)

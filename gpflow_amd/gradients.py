@@ -968,6 +968,61 @@ class PatchSpec:
         return {**self.base.kernel_grads(g_var, g_shape), "weights": dw if dw is not None else torch.zeros(self.weights.size, dtype=torch.float64)}
 
 
+class MultiscaleSpec:
+    """A SquaredExponential kernel over inducing_variables.Multiscale as the reverse pass sees it, in the role PatchSpec plays: the calls of
+    `_factorise`, `_knn_terms`, `_covariance_tail` and `kernel_grads`, told apart by ROLE -- `build(Z, None)` / `adjoint(.., symmetric=True)`
+    is Kuu, `build(X, Z)` / `adjoint(Z, X, Kuf_bar, symmetric=False)` is Kfu (ops.multiscale_*); the data side is the plain kernel, so the
+    diagonal is the constant `variance`.  CARRIER of the scales: the spec holds them as a host array [M, D] (already sliced to the kernel's
+    active columns, like the Z it is handed) and `warm()` puts them on the device as `self._S`; Z stays [M, D] in every call.  d/dscales
+    does not fit the per-member lists: the two adjoints add it up on the spec from `warm()` on, and `kernel_grads` hands it out under
+    "scales"."""
+    constant_diagonal = True
+    packable = False
+    n = 1
+
+    def __init__(self, leaf: Leaf, scales):
+        self.base = KernelSpec([leaf])
+        self.scales = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+        self.members, self.tree, self.cols, self.periods, self.nodes = self.base.members, 0, [None], [None], []
+        self._S = self._ds = None
+
+    def _kw(self) -> dict:
+        return dict(variance=self.members[0].variance, lengthscales=self.members[0].lengthscales)
+
+    def warm(self, device, D: int) -> "MultiscaleSpec":
+        self.base.warm(device, D)
+        if self.scales.ndim != 2 or self.scales.shape[1] != D:
+            raise ValueError(f"MultiscaleSpec: scales {self.scales.shape} against Z with {D} columns")
+        self._S, self._ds = ops.to_device(self.scales), None
+        return self
+
+    def build(self, X1, X2, out=None, diag_add: float = 0.0):
+        if X2 is None:
+            return ops.multiscale_kuu(X1, self._S, diag_add=diag_add, out=out, **self._kw())
+        return ops.multiscale_kfu(X1, X2, self._S, out=out, **self._kw())
+
+    def adjoint(self, A, Bm, Kbar, symmetric: bool):
+        if symmetric:
+            dv, dl, dZ, dS = ops.multiscale_kuu_adjoint(A, self._S, Kbar, **self._kw())
+        else:   # (Kbar is Kuf_bar [M, B]; the builder's layout is [B, M])
+            dv, dl, dZ, dS = ops.multiscale_kfu_adjoint(Bm, A, self._S, ops.transpose(Kbar if Kbar.is_contiguous() else Kbar.contiguous()),
+                                                        **self._kw())
+        self._ds = dS if self._ds is None else self._ds + dS
+        return [dv], [dl], dZ
+
+    kdiag = property(lambda self: self.base.kdiag)
+    dkdiag = property(lambda self: self.base.dkdiag)
+    pack = KernelSpec.pack
+    n_variance = property(lambda self: self.base.n_variance)
+    parameter_names = property(lambda self: self.base.parameter_names)
+    n_shape = property(lambda self: self.base.n_shape)
+    split_shape = property(lambda self: self.base.split_shape)
+
+    def kernel_grads(self, g_var, g_shape) -> dict:
+        ds, self._ds = self._ds, None
+        return {**self.base.kernel_grads(g_var, g_shape), "scales": ds if ds is not None else torch.zeros(self.scales.shape, dtype=torch.float64)}
+
+
 class _Seed:
     """The seeds of the data term  scale * sum_bp var_exp(fmean_bp, fvar_bp):  r = dF/dfmean [B, P]  and  c = dF/dfvar  in the form
     the likelihood gives it:

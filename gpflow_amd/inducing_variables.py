@@ -6,7 +6,7 @@ from typing import Sequence
 
 import numpy as np
 
-from .base import Module, Parameter
+from .base import Module, Parameter, positive
 
 
 class InducingVariables(Module):
@@ -37,6 +37,20 @@ class InducingPoints(InducingPointsBase):
 class InducingPatches(InducingPointsBase):
     """Inducing patches Z [M, h w] of kernels.Convolutional (inducing_variables.py `InducingPatches`): points in PATCH space, so
     Kuu is the base kernel over them and Kuf the patch response of an image -- never an InducingPoints, and no other kernel takes them."""
+
+
+class Multiscale(InducingPointsBase):
+    """Inducing points Z [M, D] that each carry a length per column, `scales` [M, D] > 0 (inducing_variables.py `Multiscale`): smoothed
+    evaluations of the GP.  kuus.py / kufs.py register them against the SquaredExponential alone (covariances.multiscale_pair); never an
+    InducingPoints, so every route written for plain points refuses them."""
+
+    def __init__(self, Z, scales, name=None):
+        super().__init__(Z, name)
+        if not isinstance(scales, Parameter):
+            scales = Parameter(np.asarray(scales, dtype=np.float64) if not hasattr(scales, "detach") else scales, transform=positive())
+        if tuple(scales.shape) != tuple(self.Z.shape):
+            raise ValueError(f"Multiscale: scales must have the shape of Z {tuple(self.Z.shape)}, got {tuple(scales.shape)}")
+        self.scales = scales
 
 
 class MultioutputInducingVariables(InducingVariables):

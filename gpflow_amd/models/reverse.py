@@ -73,8 +73,9 @@ class CovarianceRoute:
       a Sum / Product of them, flat or nested: kernels.base.gradient_spec -- the spec slices for its members itself.
     Anything else raises NotImplementedError."""
 
-    def __init__(self, kernel, input_dim=None, patches: bool = False):
+    def __init__(self, kernel, input_dim=None, patches: bool = False, multiscale=None):
         self.kernel = kernel
+        self.multiscale = multiscale   # the Multiscale inducing variable of a (Multiscale, SquaredExponential) pair: gradients.MultiscaleSpec
         self.patch = bool(getattr(kernel, "patch_kernel", False))
         if self.patch and not patches:   # (every caller but svgp_routes: a route over K(X, X) or over InducingPoints)
             raise NotImplementedError("gradients: a Convolutional kernel is built into SVGP.elbo_and_grad over InducingPatches only -- GPR, "
@@ -94,6 +95,10 @@ class CovarianceRoute:
             raise NotImplementedError("gradients: a SquaredExponential / Matern / Exponential / RationalQuadratic / White / Constant / "
                                       "Periodic / Linear / Polynomial / ArcCosine / Coregion kernel, or a Sum / Product (possibly nested) of them")
         leaf, period, params = found
+        if multiscale is not None:   # Kuu and Kfu from the multiscale builders; the scales as the kernel's active columns see them
+            scales = kernel.slice(torch.as_tensor(multiscale.scales.numpy()), None)[0].numpy()
+            self.spec, self.members = gradients.MultiscaleSpec(leaf, scales), [params]
+            return
         self.spec, self.members = gradients.KernelSpec([leaf], periods=[period]), [params]
 
     def inputs(self, Z, X):
@@ -102,7 +107,8 @@ class CovarianceRoute:
             return Z, X.contiguous(), (lambda gz: gz)
         if Z is None:
             return None, self._columns_of.slice(X, None)[0].contiguous(), None
-        return sliced(self._columns_of, Z, X)
+        Zs, Xs, self._scatter = sliced(self._columns_of, Z, X)
+        return Zs, Xs, self._scatter
 
     def spec_at(self, values):
         """the spec with the members' values replaced, each laid out as its `members` entry (the trainer's current values)"""
@@ -133,6 +139,8 @@ class CovarianceRoute:
             pairs += [(loc, gn["locations"].cpu().numpy()), (steep, gn["steepness"].cpu().numpy().reshape(steep.numpy().shape))]
         if self.patch:
             pairs.append((self.kernel.weights, g["weights"].cpu().numpy()))
+        if self.multiscale is not None:   # (back to the columns of Z, by the scatter of the `inputs` call that fed this evaluation)
+            pairs.append((self.multiscale.scales, self._scatter(g["scales"]).cpu().numpy()))
         return pairs
 
 
@@ -189,6 +197,15 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
     A dot-product kernel or member (Linear, Polynomial; `has_row_diagonal`): the plain routes of the first two lines only -- with
     quadrature, narrow, SeparateIndependent or LinearCoregionalization it is refused here, by the limit it breaks."""
     k, iv = model.kernel, model.inducing_variable
+    from ..covariances import multiscale_pair
+    multiscale = multiscale_pair(iv, k)   # (refused here: Multiscale with another kernel, or inside a multi-output wrapper)
+    if multiscale:
+        if narrow:
+            raise NotImplementedError("gradients: Multiscale inducing variables are not built into the natural gradients (the packed one-kernel "
+                                      "reverse pass over InducingPoints)")
+        if not quadrature and isinstance(model.likelihood, Gaussian) and model.likelihood.is_heteroskedastic:
+            raise NotImplementedError("gradients: Multiscale inducing variables with a heteroskedastic Gaussian noise are not built into the "
+                                      "reverse pass (a constant noise variance, or a whitened quadrature likelihood)")
     if isinstance(model.likelihood, HeteroskedasticTFPConditional):   # the scope of the quadrature reverse pass, each limit by name
         no = lambda what: NotImplementedError(f"gradients: HeteroskedasticTFPConditional {what}")   # noqa: E731
         if narrow:
@@ -230,14 +247,14 @@ def svgp_routes(model, *, quadrature: bool = False, narrow: bool = False):
             ok = ok and pairs[0][0].has_default_active_dims
     c = model.mean_function.constant_value()
     # (a Convolutional kernel goes with InducingPatches, every other kernel with InducingPoints: covariances.patch_pair)
-    iv_ok = all(isinstance(v, InducingPatches if getattr(kk, "patch_kernel", False) else InducingPoints) for kk, v in pairs)
+    iv_ok = multiscale or all(isinstance(v, InducingPatches if getattr(kk, "patch_kernel", False) else InducingPoints) for kk, v in pairs)
     if not (ok and lik_ok and c is not None and iv_ok):
         raise NotImplementedError(
             "gradients: SVGP over InducingPoints with a constant mean and a SquaredExponential / Matern kernel (shared by independent "
             "latents, or one per latent with a full q_sqrt) or a Sum / Product of them, and a Gaussian likelihood -- or, whitened with one "
             "kernel over all input columns and at most 16 latents, a Bernoulli / Poisson / StudentT / MultiClass likelihood; natural "
             "gradients: one kernel over all input columns, full q_sqrt, constant noise")
-    return [(CovarianceRoute(kk, int(v.Z.shape[1]), patches=True), v) for kk, v in pairs], float(c), separate
+    return [(CovarianceRoute(kk, int(v.Z.shape[1]), patches=True, multiscale=v if multiscale else None), v) for kk, v in pairs], float(c), separate
 
 
 def _latent_inducing_points(iv, n):

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import config, gradients, ops
-from ..inducing_variables import InducingPoints, inducingpoint_wrapper
+from ..inducing_variables import InducingPoints, Multiscale, inducingpoint_wrapper
 from ..kernels import Kernel
 from ..kernels.base import is_device_leaf
 from ..likelihoods import Gaussian
@@ -141,6 +141,9 @@ class SGPR(GPModel, InternalDataTrainingLossMixin):
         """sgpr.py:46-81.  `sharded=True` (NEW: the reference is single process): `data` is THIS rank's row shard and
         the sufficient statistics are summed over the ranks of `group` (torch.distributed; RCCL on the GPUs)."""
         assert (noise_variance is None) or (likelihood is None), "Cannot set both `noise_variance` and `likelihood`."
+        if isinstance(inducing_variable, Multiscale):
+            raise NotImplementedError("SGPR: Multiscale inducing variables are not built into its statistics (the fused Kuu / Kuf of "
+                                      "InducingPoints); SVGP takes them")
         if likelihood is None:
             likelihood = Gaussian(1.0 if noise_variance is None else noise_variance)
         X, Y = data

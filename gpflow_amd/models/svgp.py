@@ -341,7 +341,9 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
         (Bernoulli, Poisson, StudentT, MultiClass: the reverse pass seeded per (row, latent) by the kernel's own d/dfmean, d/dfvar);
         InducingPoints, full or diagonal q_sqrt; or a LinearCoregionalization kernel (whitened, full q_sqrt, one noise variance: the
         per-latent passes around one mixing stage, `_elbo_and_grad_lcm`); or a Convolutional kernel over InducingPatches (the plain
-        route and the whitened quadrature one, through gradients.PatchSpec; adds its `weights`): the scope of reverse.svgp_routes,
+        route and the whitened quadrature one, through gradients.PatchSpec; adds its `weights`); or a SquaredExponential kernel over
+        Multiscale inducing variables (the same two routes with a constant noise, through gradients.MultiscaleSpec; adds their
+        `scales`): the scope of reverse.svgp_routes,
         refused before anything touches the device.
         For minibatch training keep the variables on the device instead: training.SVGPTrainer."""
         from .. import gradients
@@ -378,7 +380,7 @@ class SVGP(GPModel, ExternalDataTrainingLossMixin):
             Fv += float(F.cpu()[0])
             kernel_pairs += route.kernel_pairs(g)
             # (the kernel's entries went through route.kernel_pairs; in a combination each is a list with one entry per member)
-            kernel_names = {"variance", "lengthscales", "alpha", "period", "offset", "changepoints", "weights", "Z"} \
+            kernel_names = {"variance", "lengthscales", "alpha", "period", "offset", "changepoints", "weights", "scales", "Z"} \
                 | {n for i in range(route.spec.n) for n in route.spec.parameter_names(i)}
             host = {n: g[n].cpu().numpy() for n in g if n not in kernel_names}
             gz = scatter(g["Z"]).cpu().numpy()

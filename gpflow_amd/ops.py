@@ -1944,3 +1944,135 @@ def conv_kdiag_adjoint(X: torch.Tensor, c: torch.Tensor, *, geometry, weights, v
                                     float(lengthscales), c.data_ptr(), parts.data_ptr(), small.data_ptr(), dw.data_ptr())
     _lib.check(rc, "gpk_conv_kdiag_adjoint")
     return small[:1], small[1:], dw
+
+
+# ------------------------------------------------------------------------------------------------ Multiscale inducing variables (multiscale/multiscale.hip)
+MS_TILE, MS_TAIL_ROWS = 64, 256   # include/gpk.h: GPK_MS_TILE, GPK_MS_TAIL_ROWS
+_MS_KFU_OPS = {"k": 0, "mul": 1, "add": 2}
+_MS_KUU_OPS = {"k": 0, "mul": 1}
+
+
+def _ms_operands(name: str, Z, scales, variance, lengthscales):
+    """What every multiscale_* wrapper checks before the library is loaded: Z and scales [M, D] of one shape, D in [1, MAX_D], one
+    lengthscale or D of them, all positive.  Returns (M, D, host lengthscales, ard, variance)."""
+    _chk(Z, "Z", 2)
+    _chk(scales, "scales", 2)
+    M, d = Z.shape
+    if tuple(scales.shape) != (M, d):
+        raise ValueError(f"{name}: scales must have the shape of Z {tuple(Z.shape)}, got {tuple(scales.shape)}")
+    if d < 1 or d > MAX_D:
+        raise ValueError(f"{name}: input dimension {d} outside [1, {MAX_D}]")
+    ls = np.asarray(lengthscales, dtype=np.float64)
+    if ls.ndim > 1 or (ls.ndim == 1 and ls.size not in (1, d)):
+        raise ValueError(f"{name}: lengthscales must be one value or [{d}]")
+    ard = int(ls.ndim == 1 and ls.size == d)   # (one entry per column; a [1] over several columns is the one lengthscale)
+    ls, v = np.atleast_1d(ls), float(variance)
+    if not (np.all(np.isfinite(ls)) and np.all(ls > 0.0) and np.isfinite(v) and v > 0.0):
+        raise ValueError(f"{name}: variance and lengthscales must be finite and positive")
+    return M, d, _lib.host_doubles(ls.tolist()), ard, v
+
+
+def _ms_out(name: str, out, G, shape, dev):
+    if G is not None:
+        _chk(G, "G", 2)
+        if tuple(G.shape) != shape:
+            raise ValueError(f"{name}: G must be {list(shape)}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != shape:
+        raise ValueError(f"{name}: out must be {list(shape)}")
+    return out
+
+
+def multiscale_kfu(X: torch.Tensor, Z: torch.Tensor, scales: torch.Tensor, G: Optional[torch.Tensor] = None, *, variance, lengthscales,
+                   op: str = "k", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Kfu [N, M] of Multiscale(Z, scales) against the SquaredExponential (include/gpk.h: gpk_multiscale_kfu):
+    v prod_j (l_j / (l_j + s_mj)) exp(-1/2 sum_j ((x_nj - z_mj) / (l_j + s_mj))^2).  op "mul" / "add": G .* Kfu / G + Kfu (`out` may be G)."""
+    M, d, ls, ard, v = _ms_operands("multiscale_kfu", Z, scales, variance, lengthscales)
+    _chk(X, "X", 2)
+    _check_op("multiscale_kfu", op, _MS_KFU_OPS)
+    if X.shape[1] != d or (G is None) != (op == "k"):
+        raise ValueError(f"multiscale_kfu: X must be [N, {d}], and G given exactly for op 'mul' / 'add'")
+    n = X.shape[0]
+    out = _ms_out("multiscale_kfu", out, G, (n, M), X.device)
+    if n == 0 or M == 0:
+        return out
+    rc = _lib.load().gpk_multiscale_kfu(_stream(), X.data_ptr(), n, _rowmajor(X, "X"), Z.data_ptr(), scales.data_ptr(), M, _rowmajor(Z, "Z"),
+                                        _rowmajor(scales, "scales"), d, ls, ard, v, _MS_KFU_OPS[op], None if G is None else G.data_ptr(),
+                                        0 if G is None else _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_multiscale_kfu")
+    return out
+
+
+def multiscale_kuu(Z: torch.Tensor, scales: torch.Tensor, G: Optional[torch.Tensor] = None, *, variance, lengthscales, op: str = "k",
+                   diag_add: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Kuu [M, M] of Multiscale(Z, scales) (gpk_multiscale_kuu), + diag_add I: exactly symmetric.  op "mul": G .* Kuu, no diag_add."""
+    M, d, ls, ard, v = _ms_operands("multiscale_kuu", Z, scales, variance, lengthscales)
+    _check_op("multiscale_kuu", op, _MS_KUU_OPS)
+    if (G is None) != (op == "k"):
+        raise ValueError("multiscale_kuu: G is given exactly for op 'mul'")
+    out = _ms_out("multiscale_kuu", out, G, (M, M), Z.device)
+    if M == 0:
+        return out
+    rc = _lib.load().gpk_multiscale_kuu(_stream(), Z.data_ptr(), scales.data_ptr(), M, _rowmajor(Z, "Z"), _rowmajor(scales, "scales"), d, ls,
+                                        ard, v, float(diag_add), _MS_KUU_OPS[op], None if G is None else G.data_ptr(),
+                                        0 if G is None else _rowmajor(G, "G"), out.data_ptr(), _rowmajor(out, "out"))
+    _lib.check(rc, "gpk_multiscale_kuu")
+    return out
+
+
+def multiscale_adjoint_parts(M: int, d: int, device_=None) -> torch.Tensor:
+    """the scratch operand `parts` of the Kuu adjoint stage and its tail: (tr + 1) M (2 d + 1) doubles, tr the tile rows of MS_TILE
+    (include/gpk.h: gpk_multiscale_parts_len); its contents at entry do not matter"""
+    return torch.empty((-(-int(M) // MS_TILE) + 1) * int(M) * (2 * int(d) + 1), dtype=torch.float64, device=device_ or device())
+
+
+def _ms_tail(symmetric: bool, Z, scales, M, d, ls, ard, v, src, ldsrc):
+    dev = Z.device
+    nl = d if ard else 1
+    small = torch.zeros(1 + nl, dtype=torch.float64, device=dev)
+    dZ, dS = torch.zeros((M, d), dtype=torch.float64, device=dev), torch.zeros((M, d), dtype=torch.float64, device=dev)
+    if M:
+        blocks = torch.empty(-(-M // MS_TAIL_ROWS) * (1 + d), dtype=torch.float64, device=dev)
+        rc = _lib.load().gpk_multiscale_adjoint_tail(_stream(), int(symmetric), Z.data_ptr(), scales.data_ptr(), M, _rowmajor(Z, "Z"),
+                                                     _rowmajor(scales, "scales"), d, ls, ard, v, src.data_ptr(), ldsrc, src.numel(),
+                                                     blocks.data_ptr(), dZ.data_ptr(), d, dS.data_ptr(), d, small.data_ptr())
+        _lib.check(rc, "gpk_multiscale_adjoint_tail")
+    return small[:1], small[1:], dZ, dS
+
+
+def multiscale_kuu_adjoint(Z: torch.Tensor, scales: torch.Tensor, Kbar: torch.Tensor, *, variance, lengthscales,
+                           parts: Optional[torch.Tensor] = None):
+    """(d/dvariance [1], d/dlengthscales [1 or D], dZ [M, D], dscales [M, D]) of sum Kbar .* Kuu for any Kbar [M, M]: one recompute stage
+    over the lower tiles (gpk_multiscale_kuu_adjoint_stage) into `parts` (multiscale_adjoint_parts) and the two-launch tail; a second
+    call gives the same bits."""
+    M, d, ls, ard, v = _ms_operands("multiscale_kuu_adjoint", Z, scales, variance, lengthscales)
+    _chk(Kbar, "Kbar", 2)
+    if tuple(Kbar.shape) != (M, M):
+        raise ValueError(f"multiscale_kuu_adjoint: Kbar must be [{M}, {M}]")
+    if parts is None:
+        parts = multiscale_adjoint_parts(M, d, Z.device)
+    _chk(parts, "parts", 1)
+    need = (-(-M // MS_TILE) + 1) * M * (2 * d + 1)
+    if not parts.is_contiguous() or parts.numel() < need:
+        raise ValueError(f"multiscale_kuu_adjoint: parts must be a contiguous [>= {need}] (ops.multiscale_adjoint_parts)")
+    if M:
+        rc = _lib.load().gpk_multiscale_kuu_adjoint_stage(_stream(), Z.data_ptr(), scales.data_ptr(), M, _rowmajor(Z, "Z"),
+                                                          _rowmajor(scales, "scales"), d, ls, ard, v, Kbar.data_ptr(),
+                                                          _rowmajor(Kbar, "Kbar"), parts.data_ptr(), parts.numel())
+        _lib.check(rc, "gpk_multiscale_kuu_adjoint_stage")
+    return _ms_tail(True, Z, scales, M, d, ls, ard, v, parts, 0)
+
+
+def multiscale_kfu_adjoint(X: torch.Tensor, Z: torch.Tensor, scales: torch.Tensor, Gbar: torch.Tensor, *, variance, lengthscales):
+    """(d/dvariance [1], d/dlengthscales [1 or D], dZ [M, D], dscales [M, D]) of sum Gbar .* Kfu for Gbar [N, M]: the seed G = Gbar .* Kfu
+    (op "mul"), the moment rows R [M, 1 + 2 D] = G^T [1, X, X^2] by the split-K MFMA GEMM the stationary adjoint uses, and the tail."""
+    from .gradients import splitk_gemm_nt   # (the contraction's K split lives with the reverse pass)
+    M, d, ls, ard, v = _ms_operands("multiscale_kfu_adjoint", Z, scales, variance, lengthscales)
+    G = multiscale_kfu(X, Z, scales, Gbar, variance=variance, lengthscales=lengthscales, op="mul")
+    if X.shape[0] == 0 or M == 0:
+        R = torch.zeros((M, 1 + 2 * d), dtype=torch.float64, device=Z.device)
+    else:
+        R = splitk_gemm_nt(transpose(G), moment_rows(X if X.is_contiguous() else X.contiguous()))
+    return _ms_tail(False, Z, scales, M, d, ls, ard, v, R, _rowmajor(R, "R"))

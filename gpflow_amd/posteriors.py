@@ -384,7 +384,26 @@ class IndependentPosterior(BasePosterior):
 class IndependentPosteriorSingleOutput(IndependentPosterior):
     """posteriors.py:825-841"""
 
+    def _fused_multiscale(self, Xnew, full_cov: bool):
+        """`_fused_single_kernel` for (Multiscale, SquaredExponential): the trapezoid's Kuu and Kfu from the multiscale builders, Knn the
+        plain kernel's"""
+        kernel, iv = self.kernel, self.X_data
+        Xf, lead = _flatten_rows(Xnew)
+        M, N = iv.num_inducing, Xf.shape[0]
+        T = torch.empty((M + N, M), dtype=torch.float64, device=Xf.device)
+        covariances.multiscale_Kuu(iv, kernel, T[:M], jitter=config.default_jitter())
+        covariances.multiscale_Kfu(iv, kernel, Xf, T[M:])
+        invd, info = ops.potrf_(T, M, zero_upper=True)
+        ops.check_info(info)
+        fac, q_mu, q_sqrt = Factor(T[:M], invd), self.q_mu, self.q_sqrt
+        return tail_over_batches(
+            T[M:], lead, _knn_of(lambda x, fc: kernel(x, full_cov=fc), Xf, lead, full_cov),
+            lambda A, K: conditional_tail(A, fac, K, q_mu, full_cov=full_cov, q_sqrt=q_sqrt, white=self.whiten), full_cov)
+
     def _conditional_fused(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        if covariances.multiscale_pair(self.X_data, self.kernel):   # (Multiscale with another kernel: refused)
+            fmean, fvar = self._fused_multiscale(Xnew, full_cov)
+            return self._post_process_mean_and_cov(fmean, fvar, full_cov, full_output_cov)
         covariances.patch_pair(self.X_data, self.kernel)   # (a Convolutional kernel without InducingPatches, or the reverse: refused)
         fmean, fvar = self._fused_single_kernel(self.kernel, self.X_data.Z.device_value(), Xnew, full_cov)
         return self._post_process_mean_and_cov(fmean, fvar, full_cov, full_output_cov)

@@ -65,7 +65,7 @@ class SVGPTrainer:
         # over SHARED inducing points (BASELINE config C5, separate): P single-output problems that share Z, the likelihood, the mean
         # constant and the minibatch rows; their objectives and shared gradients add up (conditionals/util.py:566-629).  The
         # covariance spec is rebuilt from the trainer's current member values every step (CovarianceRoute.spec_at).
-        from .inducing_variables import SharedIndependentInducingVariables
+        from .inducing_variables import Multiscale, SharedIndependentInducingVariables
         from .kernels import LinearCoregionalization, SeparateIndependent
         from .models import reverse
         if isinstance(model.kernel, LinearCoregionalization):
@@ -79,6 +79,9 @@ class SVGPTrainer:
         if getattr(model.kernel, "patch_kernel", False):
             raise NotImplementedError("SVGPTrainer: a Convolutional kernel is not built into the device-resident training step (its "
                                       "weights are not among the packed variables); train it with optimizers.Scipy")
+        if isinstance(model.inducing_variable, Multiscale):
+            raise NotImplementedError("SVGPTrainer: Multiscale inducing variables are not built into the device-resident training step (their "
+                                      "scales are not among the packed variables); train them with optimizers.Scipy")
         routes, c, self.separate = reverse.svgp_routes(model)
         if any(p is not None for r, _ in routes for p in r.spec.periods):
             raise NotImplementedError("the trainer keeps (variance, lengthscales) per kernel on the device side of its step: no Periodic "

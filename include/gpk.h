@@ -1000,6 +1000,52 @@ size_t gpk_conv_kdiag_partials_len(int N, int H, int W, int C, int h, int w);
 int gpk_conv_kdiag_adjoint(void* stream, const double* X, int N, long ldx, int H, int W, int C, int h, int w, const double* weights,
                            double variance, double lengthscale, const double* c, double* parts, double* dsmall, double* dw);
 
+/* ---- Multiscale inducing variables x SquaredExponential (multiscale/multiscale.hip; gpflow/covariances/kufs.py, kuus.py) -----------
+ * Z [M, d] ldz: inducing points; S [M, d] lds: their scales s_mj >= 0 (the caller's contract; 0 is accepted), both DEVICE operands whose
+ * leading dimension may exceed d.  ls_host: HOST pointer, d lengthscales l_j if ard, else one; variance v: host scalar.
+ *     Kfu[n, m]  = v prod_j (l_j r_mj) exp(-1/2 sum_j ((x_nj - z_mj) r_mj)^2)                  r_mj = 1 / (l_j + s_mj)
+ *     Kuu[m, m'] = v sqrt(prod_j l_j^2 q_j) exp(-1/2 sum_j D_j^2 q_j)    D_j = z_mj - z_m'j,  q_j = 1 / ((a_mj + a_m'j) - l_j^2),  a = (l + s)^2
+ * With S = 0 both are the plain SquaredExponential; the diagonal of Kuu is v prod_j l_j / sqrt(2 a_mj - l_j^2), not v.
+ * Every element is the DIFFERENCE form, an fma chain over ascending columns from 0.0: no |x|^2 + |y|^2 - 2 x.y, no cancellation.  r is
+ * rounded once per staged value (one division per tile, row and column), the column prefactor c_m = v prod_j (l_j r_mj) is multiplied
+ * in column order; q is a true division per element and column and the prefactor of Kuu ONE square root of the running product.
+ * a_m + a_m' and D^2 commute: Kuu is computed on or below the diagonal and mirrored, EXACTLY symmetric.  A NaN or Inf in a row of X makes
+ * that row of Kfu NaN; a NaN in z_m or s_m makes column m of Kfu and row and column m of Kuu NaN, nothing else.  No atomics, no
+ * workspace: typed operands with the extents stated here; a second call gives the same bits.
+ * Every entry point returns GPK_E_ARG, before any pointer is looked at: d outside 1 .. GPK_MAX_D, a negative count, a leading dimension
+ * that is too small, a lengthscale or variance that is not finite or not > 0, an op it does not have, a `parts` that is too short; then
+ * 0 without a launch where n == 0 or M == 0; then GPK_E_ARG for a NULL operand that has elements.
+ *
+ * gpk_multiscale_kfu: out [n, M] ldo, row-major.  op 0: Kfu; 1: G .* Kfu; 2: G + Kfu (G [n, M] ldg; out may alias G).
+ * gpk_multiscale_kuu: out [M, M] ldo.  op 0: Kuu + diag_add I; 1: G .* Kuu (no diag_add; G need not be symmetric; out may alias G).
+ * gpk_multiscale_kuu_adjoint_stage: ONE pass over the tiles on or below the diagonal recomputes Kuu and, with g = (Kbar[m, m'] +
+ *   Kbar[m', m]) Kuu[m, m'] off the diagonal and Kbar[m, m] Kuu[m, m] on it (Kbar [M, M] ldkb, any matrix), leaves per tile and row the
+ *   2 d + 1 sums  sum g,  sum g D_j q_j,  sum g (D_j^2 q_j^2 - q_j)  in
+ *     parts[(slot M + m) (2 d + 1) + {0, 1 + j, 1 + d + j}],   slot 0 .. tr,  tr = ceil(M / GPK_MS_TILE):
+ *   row m of tile row b gets slot c from tile (b, c), c <= b, and -- through the mirror, D with the other sign, the diagonal counted in
+ *   both -- slot r + 1 from tile (r, b), r >= b; entry 0 of a mirror slot is neither written nor read.  parts_len >=
+ *   gpk_multiscale_parts_len(M, d) = (tr + 1) M (2 d + 1) doubles; every entry the tail reads is written by this call.
+ * gpk_multiscale_adjoint_tail: two launches (a workgroup per GPK_MS_TAIL_ROWS rows, then one that adds the blocks in order).
+ *   symmetric != 0, the adjoint of sum Kbar .* Kuu: src = the stage's parts, src_len its length; with V, Wm the slot sums of a row
+ *     dZ = -V      dS = Wm (l + s)      dl_j = F / l_j + sum_m Wm (l_j / 2 + s_mj)      dv = F / v,   F = sum Kbar .* Kuu
+ *   symmetric == 0, the adjoint of sum Gbar .* Kfu: src = R [M, >= 1 + 2 d] ldsrc = (Gbar .* Kfu)^T [1, X, X^2] (columns S0, S1_j, S2_j; the
+ *   caller's contraction), src_len not read:
+ *     dZ = r^2 (S1 - z S0)      dS = r^3 ((S2 - 2 z S1) + z^2 S0) - r S0      dl_j = sum_m dS_mj + (sum S0) / l_j      dv = (sum S0) / v
+ *   (the moment form: S1 - z S0 and the second moment cancel where |x - z| << |z|).  dZ [M, d] lddz, dS [M, d] ldds; dsmall: dv, then dl
+ *   (d entries if ard, else their sum); blocks: scratch of ceil(M / GPK_MS_TAIL_ROWS) (1 + d) doubles, contents at entry do not matter. */
+#define GPK_MS_TILE 64
+#define GPK_MS_TAIL_ROWS 256
+size_t gpk_multiscale_parts_len(int M, int d);
+int gpk_multiscale_kfu(void* stream, const double* X, int n, long ldx, const double* Z, const double* S, int M, long ldz, long lds, int d,
+                       const double* ls_host, int ard, double variance, int op, const double* G, long ldg, double* out, long ldo);
+int gpk_multiscale_kuu(void* stream, const double* Z, const double* S, int M, long ldz, long lds, int d, const double* ls_host, int ard,
+                       double variance, double diag_add, int op, const double* G, long ldg, double* out, long ldo);
+int gpk_multiscale_kuu_adjoint_stage(void* stream, const double* Z, const double* S, int M, long ldz, long lds, int d, const double* ls_host,
+                                     int ard, double variance, const double* Kbar, long ldkb, double* parts, long parts_len);
+int gpk_multiscale_adjoint_tail(void* stream, int symmetric, const double* Z, const double* S, int M, long ldz, long lds, int d,
+                                const double* ls_host, int ard, double variance, const double* src, long ldsrc, long src_len,
+                                double* blocks, double* dZ, long lddz, double* dS, long ldds, double* dsmall);
+
 /* micro-benchmarks used by bench.py / profiles (fp64 MFMA issue rate, HBM write stream) */
 int gpk_bench_mfma_f64(void* stream, int blocks, int iters, double* sink);
 int gpk_bench_stream_store(void* stream, double* out, long n_doubles);
