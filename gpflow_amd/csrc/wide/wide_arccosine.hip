@@ -7,18 +7,11 @@
 //   s(x, y) = sum_j (x_j w_j) y_j + b     p(x) = s(x, x)     c = s / (sqrt p(x) sqrt p(y))     theta = acos(clamp(eps + (1 - 2 eps) c))
 //   K(x, y) = (v / pi) J_order(theta) p(x)^(order/2) p(y)^(order/2)        (J_order and the three contract items: arccosine.hip)
 //
-// Work split (that of wide_stationary.hip, restated: sharing device code moves register counts here).  One T x T output tile per
-// 256-thread workgroup, T = 128 or 64; the four waves (2 x 2) own a square quarter each, WT = T / 2, as NB x NB blocks of
-// v_mfma_f64_16x16x4_f64 (NB = WT / 16; A frag: row = lane & 15, k = lane >> 4, the B^T frag the same; D: col = lane & 15,
-// row = (lane >> 4) + 4 reg).  T = 64 is launched when the 128-tile grid would have fewer workgroups than the device has compute
-// units (arc_tile below: a function of n1, n2 and the symmetric flag alone).
+// The tile -- work split, K loop, LDS layout, symmetric build -- is wide_tile.h's, shared with wide_stationary.hip; this file brings
+// the value arithmetic of the ArcCosine kernel, the row diagonal, the adjoint tail and the entry points.
 //
-// K loop.  A slab is BK = 16 columns of both operands, two LDS buffers, one barrier per slab: the global loads of slab s + 1 are
-// issued before the MFMAs of slab s and written to the other buffer after them.  Thread t stages EPT = T / 16 consecutive columns of
-// tile row t / TPR of each operand (16-byte loads where the operand allows them).  The FIRST operand is staged as x_j w_j -- one
-// rounding, as X * w of the reference -- and the second raw; w is read from the DEVICE (d entries if ard, else one).  Columns past d
-// are zero-filled with a weight of 0.0, rows past n1 / n2 are zero-filled.  LDS rows are LD = 18 doubles apart (+ 2 per 16-row group)
-// and permuted (lds_row_a, lds_row_b) so that a lane's accumulators are neighbours in memory.
+// Staging.  The FIRST operand is staged as x_j w_j -- one rounding, as X * w of the reference -- and the second raw; w is read from
+// the DEVICE (d entries if ard, else one).  A column past d has a weight of 0.0.
 //
 // Norms.  p of the tile's rows and q of its columns are accumulated by the staging threads from the staged values,
 // fma(x_j w_j, x_j, .), one register partial per COLUMN PHASE: phase f holds the columns j with (j % 16) / 4 == f, ascending.  The four
@@ -31,9 +24,6 @@
 // diagonal c = 1 - 1e-15 where X2 == NULL; a NaN / Inf row poisons exactly its row / column).  MODE 0: the build (diag_add,
 // lower_only); 1 / 2: out = G .* k / G + k (out may be G: an element is read and written by the same lane); 3: the adjoint stage.
 //
-// Symmetric build (X2 == NULL, MODE 0): only tiles on or below the diagonal run.  An off-diagonal tile is also written transposed
-// unless lower_only; a diagonal tile writes its lower half and mirrors it inside the tile: K == K^T holds by construction.
-//
 // Adjoint stage (MODE 3): out = Kbar .* dk/ds, and the sums of Kbar .* dk/dp by row, Kbar .* dk/dq by column and Kbar .* k / v go
 // to `parts` in the layout of gpk_arccos_adjoint_stage -- one slot per 64-wide tile row / column / tile (GPK_ARC_TILE).  A lane adds
 // its own elements left to right, the sixteen (four) lanes of a row (column) meet by a butterfly inside the wave, the waves' partials
@@ -45,13 +35,13 @@
 // symmetric) per 256 rows of B; it sums the slots of its rows in slot order into rg, writes its rows of A_bar and leaves its partial
 // column sums for d/dw_j and d/db in `scratch`.  wide_arc_tail_sum_kernel: one workgroup adds the blocks' partials in block order and
 // the tile sums for d/dvariance.
-#include "../gpk_internal.h"
+#include "wide_tile.h"
 #include <cmath>
 
 namespace {
 
-constexpr int BK = 16;    // columns per slab
-constexpr int LD = 18;    // doubles between LDS rows of a slab
+using namespace wide_tile;
+
 constexpr int NPH = 4;    // column phases of the norms: four columns of a slab each
 constexpr int SLOT = GPK_ARC_TILE;
 constexpr double ARC_EPS = 1e-15;
@@ -75,25 +65,13 @@ struct WArcArgs {
   double* parts; int tr, tc;    // MODE 3: the partials and the counts of 64-wide tile rows / columns that lay them out
 };
 
+// What this file keeps in the LDS that the slabs leave free after the K loop, behind the tile's phase partials and norms
+// (wide_tile_front.inc: part [2][T][NPH], nrm [2][T]): the square roots of the norms, and the adjoint stage's partial sums.
 template <int T>
-struct Geo {
-  static constexpr int WT = T / 2, NB = WT / 16, EPT = T / 16, TPR = BK / EPT, PPT = EPT / 4;   // PPT: norm phases per staging thread
-  static constexpr int SLAB = T * LD + 2 * (T / 16);    // doubles of one operand's slab
-  static constexpr size_t LDS = (size_t)4 * SLAB * sizeof(double);   // two operands, two buffers
-  static constexpr int PART = 0, NRM = 2 * T * NPH, ROOT = NRM + 2 * T, RED = ROOT + 2 * T, END = RED + 4 * T + 4;
-  static_assert(END <= 4 * SLAB, "the norm partials, the norms and the stage's partial sums reuse the slabs");
+struct ArcLds {
+  static constexpr int ROOT = 2 * T * NPH + 2 * T, RED = ROOT + 2 * T, END = RED + 4 * T + 4;
+  static_assert(END <= 4 * Geo<T>::SLAB, "the norm partials, the norms and the stage's partial sums reuse the slabs");
 };
-
-__device__ __forceinline__ int lds_off(int lrow) { return lrow * LD + 2 * (lrow >> 4); }
-// tile row of X1 -> LDS row: 16 i + 4 a + b -> 16 i + a + 4 b
-__device__ __forceinline__ int lds_row_a(int r) { return (r & ~15) | ((r >> 2) & 3) | ((r & 3) << 2); }
-// tile column (row of X2's slab) -> LDS row: wave half wc, c = l NB + j -> wc WT + 16 j + l
-template <int T>
-__device__ __forceinline__ int lds_row_b(int c) {
-  constexpr int WT = Geo<T>::WT, NB = Geo<T>::NB;
-  const int wc = c / WT, cc = c % WT;
-  return wc * WT + (cc % NB) * 16 + cc / NB;
-}
 
 // J_ORDER at cos theta = ct, and D = dJ / d(acos argument)   (arccosine.hip, contract item 3: acos and sqrt only)
 template <int ORDER, bool WANT_D>
@@ -123,150 +101,41 @@ __device__ __forceinline__ double lane_sum(double v) {
   return v;
 }
 
-// (two workgroups per CU: one's staging and epilogue under the other's MFMAs)
+// what the tile of wide_tile.h does to values here: the first operand as x w (one rounding), the second raw, fma(x w, x, .) summed
+// as it is staged; a norm is finished by + b, and its square root is kept beside it
+#define WIDE_STAGE(x, w) ((x) * (w))
+#define WIDE_SECOND(staged, raw) (raw)
+#define WIDE_NORM_TERM(staged, raw, acc) fma(staged, raw, acc)
+#define WIDE_NORM_FINISH(sum)       \
+  const double pv = (sum) + p.bias; \
+  nrm[tid] = pv;                    \
+  sm[ArcLds<T>::ROOT + tid] = sqrt(pv)
+#define WIDE_SYM (MODE == 0 && p.sym)   // the mirrored build
+#define WIDE_FIRST_PHASE (scol / 4)
+#define WIDE_PARTIAL_OF(e) ((e) / 4)
+#define WIDE_SCALES p.w
+
 template <int T, int ORDER, int MODE>
 __attribute__((amdgpu_waves_per_eu(2, 2)))
 __global__ __launch_bounds__(256) void wide_arc_kernel(const WArcArgs p) {
-  using G_ = Geo<T>;
-  constexpr int WT = G_::WT, NB = G_::NB, EPT = G_::EPT, TPR = G_::TPR, PPT = G_::PPT, SLAB = G_::SLAB;
   static_assert(MODE != 3 || T == SLOT, "the adjoint stage runs on the 64-tile alone: a tile is one slot of `parts`");
-  extern __shared__ __attribute__((aligned(16))) double sm[];   // [2 buffers][2 operands][SLAB]
-
-  if (MODE == 0 && p.sym && blockIdx.x > blockIdx.y) return;   // strictly upper tile: skipped (lower_only) or written by its mirror
-  const int r0 = blockIdx.y * T, c0 = blockIdx.x * T;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, l15 = lane & 15, lq = lane >> 4;
-  const int d = p.d;
-
-  // ---- staging slots --------------------------------------------------------------------------
-  const int srow = tid / TPR, scol = (tid % TPR) * EPT;
-  const int g1 = r0 + srow, g2 = c0 + srow;
-  const double* __restrict__ x1 = p.X1 + (long)g1 * p.ldx1 + scol;
-  const double* __restrict__ x2 = p.X2 + (long)g2 * p.ldx2 + scol;
-  const bool in1 = g1 < p.n1, in2 = g2 < p.n2;
-  const bool vec1 = in1 && ((p.ldx1 & 1) == 0) && ((reinterpret_cast<uintptr_t>(p.X1) & 15) == 0);
-  const bool vec2 = in2 && ((p.ldx2 & 1) == 0) && ((reinterpret_cast<uintptr_t>(p.X2) & 15) == 0);
-  const int so1 = lds_off(lds_row_a(srow)) + scol, so2 = SLAB + lds_off(lds_row_b<T>(srow)) + scol;
-  const double w0 = p.w[0];
-
-  double ra[EPT], rb[EPT], rw[EPT];
-  auto gload = [&](int ks) {
-    const bool inside = ks + scol + EPT <= d;   // none of this thread's columns is past d
-    if (vec1 && inside) {
-#pragma unroll
-      for (int e = 0; e < EPT; e += 2) {
-        const d2 v = *reinterpret_cast<const d2*>(x1 + ks + e);
-        ra[e] = v[0]; ra[e + 1] = v[1];
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) ra[e] = (in1 && ks + scol + e < d) ? x1[ks + e] : 0.0;
-    }
-    if (vec2 && inside) {
-#pragma unroll
-      for (int e = 0; e < EPT; e += 2) {
-        const d2 v = *reinterpret_cast<const d2*>(x2 + ks + e);
-        rb[e] = v[0]; rb[e + 1] = v[1];
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) rb[e] = (in2 && ks + scol + e < d) ? x2[ks + e] : 0.0;
-    }
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) rw[e] = (ks + scol + e < d) ? (p.ard ? p.w[ks + scol + e] : w0) : 0.0;
-  };
-  // this thread's share of p of row srow of X1 and of q of row srow of X2: one chain per column phase, over every slab
-  double np1[PPT], np2[PPT];
-#pragma unroll
-  for (int f = 0; f < PPT; ++f) np1[f] = np2[f] = 0.0;
-  auto lstore = [&](double* buf) {
-#pragma unroll
-    for (int e = 0; e < EPT; e += 2) {
-      const double a0 = ra[e] * rw[e], a1 = ra[e + 1] * rw[e + 1];   // x_j w_j: one rounding
-      const double b0 = rb[e] * rw[e], b1 = rb[e + 1] * rw[e + 1];
-      np1[e / 4] = fma(a0, ra[e], np1[e / 4]); np1[e / 4] = fma(a1, ra[e + 1], np1[e / 4]);
-      np2[e / 4] = fma(b0, rb[e], np2[e / 4]); np2[e / 4] = fma(b1, rb[e + 1], np2[e / 4]);
-      *reinterpret_cast<d2*>(&buf[so1 + e]) = (d2){a0, a1};
-      *reinterpret_cast<d2*>(&buf[so2 + e]) = (d2){rb[e], rb[e + 1]};
-    }
-  };
-
-  d4 acc[NB][NB];
-#pragma unroll
-  for (int i = 0; i < NB; ++i)
-#pragma unroll
-    for (int j = 0; j < NB; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
-
-  // MFMA fragments: block i of the wave's rows is LDS rows wr WT + 16 i .. + 15 of X1's slab, block j LDS rows wc WT + 16 j .. of X2's
-  int fa[NB], fb[NB];
-#pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    fa[i] = lds_off(wr * WT + i * 16 + l15) + lq;
-    fb[i] = SLAB + lds_off(wc * WT + i * 16 + l15) + lq;
-  }
-
-  const int nslab = (d + BK - 1) / BK;
-  gload(0);
-  lstore(sm);
-  __syncthreads();
-  for (int s = 0; s < nslab; ++s) {
-    const double* cur = sm + (s & 1) * 2 * SLAB;
-    const bool more = s + 1 < nslab;
-    if (more) gload((s + 1) * BK);                     // in flight under this slab's arithmetic
-#pragma unroll
-    for (int kk = 0; kk < BK / 4; ++kk) {
-      double a[NB], b[NB];
-#pragma unroll
-      for (int i = 0; i < NB; ++i) a[i] = cur[fa[i] + kk * 4];
-#pragma unroll
-      for (int j = 0; j < NB; ++j) b[j] = cur[fb[j] + kk * 4];
-#pragma unroll
-      for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    if (more) lstore(sm + ((s + 1) & 1) * 2 * SLAB);   // (its last readers passed the barrier that ended slab s - 1)
-    __syncthreads();
-  }
-
-  // ---- norms: the four phase partials of a row in phase order, then b (the slabs are no longer read) -------
-  double* part = sm + G_::PART;    // [2][T][NPH]
-  double* nrm = sm + G_::NRM;      // [2][T]: p of the rows, then q of the columns, by TILE index
-  double* root = sm + G_::ROOT;    // [2][T]: their square roots
-#pragma unroll
-  for (int f = 0; f < PPT; ++f) {
-    part[srow * NPH + scol / 4 + f] = np1[f];
-    part[(T + srow) * NPH + scol / 4 + f] = np2[f];
-  }
-  __syncthreads();
-  if (tid < 2 * T) {
-    double s = part[tid * NPH];
-#pragma unroll
-    for (int ph = 1; ph < NPH; ++ph) s += part[tid * NPH + ph];
-    const double pv = s + p.bias;
-    nrm[tid] = pv;
-    root[tid] = sqrt(pv);
-  }
-  __syncthreads();
-
-  // ---- epilogue ----------------------------------------------------------------------------------
-  const bool aligned = ((p.ldk & 1) == 0) && ((reinterpret_cast<uintptr_t>(p.K) & 15) == 0);
-  const bool full = (r0 + T <= p.n1) && (c0 + T <= p.n2) && aligned;
-  const bool mirror = MODE == 0 && p.sym && !p.lower_only;
-  const bool diag_mirror = mirror && r0 == c0;   // the lower half and, inside the tile, its transpose
-  const int tc0 = wc * WT + l15 * NB;            // this lane's NB consecutive tile columns
+  constexpr double PAD = 0.0;
+  constexpr bool BUILD = MODE == 0;
+  // (NPH, above: four phases of four columns at both tiles, EPT / 4 partials per staging thread)
+#include "wide_tile_front.inc"
+  double* root = sm + ArcLds<T>::ROOT;   // [2][T]: the square roots of nrm, p of the rows, then q of the columns
   double qc[NB], rqc[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
     qc[j] = nrm[T + tc0 + j];
     rqc[j] = root[T + tc0 + j];
   }
-  bool gvec = false;
-  if constexpr (MODE != 0) gvec = full && ((p.ldg & 1) == 0) && ((reinterpret_cast<uintptr_t>(p.G) & 15) == 0);
+  bool gvec = false;   // (wide_tile_gread.inc)
+  if constexpr (!BUILD) gvec = full && ((p.ldg & 1) == 0) && ((reinterpret_cast<uintptr_t>(p.G) & 15) == 0);
   double cs[NB], ks = 0.0;   // MODE 3: this lane's column sums of Kbar .* dk/dq and its sum of Kbar .* J m
 #pragma unroll
   for (int j = 0; j < NB; ++j) cs[j] = 0.0;
-  double* red_r = sm + G_::RED;          // [2 = wc][T]  MODE 3: a wave's row sums of Kbar .* dk/dp
+  double* red_r = sm + ArcLds<T>::RED;   // [2 = wc][T]  MODE 3: a wave's row sums of Kbar .* dk/dp
   double* red_c = red_r + 2 * T;         // [2 = wr][T]  its column sums
   double* red_k = red_c + 2 * T;         // [4 = w]      its sum of Kbar .* J m
 
@@ -274,19 +143,7 @@ __global__ __launch_bounds__(256) void wide_arc_kernel(const WArcArgs p) {
   auto row_values = [&](int i, int g, int tr, double* out) {
     const int gr = r0 + tr;
     const double pr = nrm[tr], rpr = root[tr];
-    double gv[NB];
-    if constexpr (MODE != 0) {
-      if (gvec) {
-#pragma unroll
-        for (int j = 0; j < NB; j += 2) {
-          const d2 t = *reinterpret_cast<const d2*>(p.G + (long)gr * p.ldg + c0 + tc0 + j);
-          gv[j] = t[0]; gv[j + 1] = t[1];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < NB; ++j) gv[j] = (gr < p.n1 && c0 + tc0 + j < p.n2) ? p.G[(long)gr * p.ldg + c0 + tc0 + j] : 0.0;
-      }
-    }
+#include "wide_tile_gread.inc"
     double rs = 0.0;
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
@@ -328,65 +185,7 @@ __global__ __launch_bounds__(256) void wide_arc_kernel(const WArcArgs p) {
       if (l15 == 0) red_r[wc * T + tr] = rs;
     }
   };
-  auto store_row = [&](int gr, const double* v) {
-    if (full) {
-#pragma unroll
-      for (int j = 0; j < NB; j += 2) *reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + c0 + tc0 + j) = (d2){v[j], v[j + 1]};
-    } else if (gr < p.n1) {
-#pragma unroll
-      for (int j = 0; j < NB; ++j)
-        if (c0 + tc0 + j < p.n2) p.K[(long)gr * p.ldk + c0 + tc0 + j] = v[j];
-    }
-  };
-
-#pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    const int tr0 = wr * WT + i * 16 + 4 * lq;   // this lane's four consecutive tile rows of block row i
-    if constexpr (MODE != 0) {   // no mirror: a row is stored as soon as it is formed
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        double v[NB];
-        row_values(i, g, tr0 + g, v);
-        store_row(r0 + tr0 + g, v);
-      }
-    } else {
-      double v[4][NB];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) row_values(i, g, tr0 + g, v[g]);
-      if (diag_mirror) {   // element by element: (gr, gc) for gc <= gr, and its transpose
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int gr = r0 + tr0 + g;
-#pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            const int gc = c0 + tc0 + j;
-            if (gr < p.n1 && gc <= gr) {
-              p.K[(long)gr * p.ldk + gc] = v[g][j];
-              if (gc < gr) p.K[(long)gc * p.ldk + gr] = v[g][j];
-            }
-          }
-        }
-        continue;
-      }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) store_row(r0 + tr0 + g, v[g]);
-      if (mirror && r0 != c0) {   // transposed copy: rows c0 + tc0 + j, columns r0 + tr0 .. + 3   (sym: n1 == n2)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const int gr = c0 + tc0 + j;
-          if (full) {
-            d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + r0 + tr0);
-            out[0] = (d2){v[0][j], v[1][j]};
-            out[1] = (d2){v[2][j], v[3][j]};
-          } else if (gr < p.n1) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-              if (r0 + tr0 + g < p.n2) p.K[(long)gr * p.ldk + r0 + tr0 + g] = v[g][j];
-          }
-        }
-      }
-    }
-  }
+#include "wide_tile_rows.inc"
 
   if constexpr (MODE == 3) {
     // a wave's column sums: the four lanes that share l15; its sum of Kbar .* J m: every lane
@@ -588,43 +387,16 @@ __global__ __launch_bounds__(SUM_THREADS) void wide_arc_tail_sum_kernel(const WA
 }
 
 // ---- host ---------------------------------------------------------------------------------------
-// The tile: 128, unless the 128-tile grid would run fewer workgroups than the device has compute units.  A function of (n1, n2, sym)
-// alone -- nothing else selects a kernel.
-int arc_tile(int n1, int n2, bool sym, int cus) {
-  const long nb1 = gpk_cdiv(n1, 128), nb2 = gpk_cdiv(n2, 128);
-  const long tiles = sym ? nb1 * (nb1 + 1) / 2 : nb1 * nb2;
-  return tiles < cus ? 64 : 128;
-}
-
-int compute_units(int* cus) {
-  int dev = 0, n = 0;
-  GPK_HIP(hipGetDevice(&dev));
-  GPK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-  *cus = n > 0 ? n : 1;
-  return 0;
-}
-
-template <int T, int ORDER, int MODE>
-int launch_tile(hipStream_t st, const WArcArgs& a) {
-  if (gpk_cdiv(a.n1, T) > 65535) return GPK_E_ARG;   // (grid.y: n1 <= 65535 T rows, include/gpk.h)
-  static const hipError_t at = hipFuncSetAttribute(reinterpret_cast<const void*>(wide_arc_kernel<T, ORDER, MODE>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)Geo<T>::LDS);
-  GPK_HIP(at);
-  dim3 grid((unsigned)gpk_cdiv(a.n2, T), (unsigned)gpk_cdiv(a.n1, T));
-  hipLaunchKernelGGL((wide_arc_kernel<T, ORDER, MODE>), grid, dim3(256), Geo<T>::LDS, st, a);
-  GPK_LAUNCH_CHECK();
-  return 0;
-}
-
 // (the adjoint stage: the 64-tile at every size -- at T = 128 its 64 accumulators per lane, J, D, h and the partial sums spill)
 template <int ORDER, int MODE>
 int launch_order(hipStream_t st, const WArcArgs& a) {
   if constexpr (MODE == 3) {
-    return launch_tile<64, ORDER, MODE>(st, a);
+    return launch_tile<wide_arc_kernel<64, ORDER, MODE>, 64>(st, a);
   } else {
     int cus = 0;
     GPK_TRY(compute_units(&cus));
-    return arc_tile(a.n1, a.n2, a.sym != 0, cus) == 128 ? launch_tile<128, ORDER, MODE>(st, a) : launch_tile<64, ORDER, MODE>(st, a);
+    return tile_size(a.n1, a.n2, a.sym != 0, cus) == 128 ? launch_tile<wide_arc_kernel<128, ORDER, MODE>, 128>(st, a)
+                                                        : launch_tile<wide_arc_kernel<64, ORDER, MODE>, 64>(st, a);
   }
 }
 
@@ -643,9 +415,8 @@ int check_leaf(int order, int d, const double* w_dev, double variance, double bi
 
 void set_operands(WArcArgs& a, const double* X1, int n1, long ldx1, const double* X2, int n2, long ldx2, int d, const double* w_dev,
                   int ard, double variance, double bias, double* out, long ldo, const double* G, long ldg) {
-  a.X1 = X1; a.ldx1 = ldx1; a.n1 = n1;
-  a.X2 = X2 ? X2 : X1; a.ldx2 = X2 ? ldx2 : ldx1; a.n2 = X2 ? n2 : n1;
-  a.d = d; a.w = w_dev; a.ard = ard ? 1 : 0;
+  wide_tile::set_operands(a, X1, n1, ldx1, X2, n2, ldx2, d);
+  a.w = w_dev; a.ard = ard ? 1 : 0;
   a.vpi = variance * ARC_INV_PI; a.bias = bias;
   a.K = out; a.ldk = ldo; a.G = G; a.ldg = ldg;
   a.same = (X2 == nullptr);
