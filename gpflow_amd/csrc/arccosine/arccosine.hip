@@ -18,7 +18,7 @@
 //     only.  (dJ/dtheta)(dtheta/d arg) = 1 / sin theta (order 0), pi - theta (order 1), 4 J_1(theta) (order 2).  Order 0 is singular
 //     where the argument is +-1 (two proportional rows in different positions): the reference's gradient is infinite there as well.
 //
-// Arithmetic.  The same 64 x 64 tile per 256-thread workgroup as dot_kernel (dot.hip).  Both slabs are staged RAW, [d][64] each (64 KB at
+// Arithmetic.  The 64 x 64 tile per 256-thread workgroup of pair_tile.h (its fragments, the PAIR_* macros below).  Both slabs are staged RAW, [d][64] each (64 KB at
 // d = GPK_MAX_D); x_j w_j is formed in registers (one rounding, as X * w of the reference), the sum over j is an fma chain over ascending
 // columns from 0.0, and b is added last.  p of the tile's 64 rows and of its 64 columns comes from the staged slabs with the same chain
 // fma(x_j w_j, x_j, .): no second pass over X, no norm vectors in global memory, and p of row i as a row equals p of row i as a column
@@ -74,6 +74,13 @@ __device__ __forceinline__ void arc_eval(double ct, double& J, double& D) {
 // MODE 0: the build.  1 / 2: out = G .* k / G + k (out may alias G: an element is read and written by the same thread).
 // 3: the adjoint stage -- out = Kbar .* dk/ds and the tile's partial sums of Kbar .* dk/dp (by row), Kbar .* dk/dq (by column) and
 // Kbar .* k / v.  Modes 1 - 3 never mirror.
+#define PAIR_STAGE_LOCALS
+#define PAIR_STAGE_FIRST(x) x
+#define PAIR_STAGE_SECOND(x) x
+#define PAIR_FIRST(x) x * p.w[dd]
+#define PAIR_OUT p.K
+#define PAIR_LDO p.ldk
+#define PAIR_WRITTEN(gr, gc) gc < p.n2
 template <int ORDER, int MODE>
 __global__ __launch_bounds__(256) void arccos_kernel(ArcArgs p) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -87,13 +94,7 @@ __global__ __launch_bounds__(256) void arccos_kernel(ArcArgs p) {
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
 
-  for (int e = tid; e < T * d; e += 256) {   // padding rows are 0.0: p = b there
-    const int row = e / d, dd = e - row * d;
-    const int g1 = r0 + row, g2 = c0 + row;
-    x1t[dd * T + row] = (g1 < p.n1) ? p.X1[(long)g1 * p.ldx1 + dd] : 0.0;
-    x2t[dd * T + row] = (g2 < p.n2) ? p.X2[(long)g2 * p.ldx2 + dd] : 0.0;
-  }
-  __syncthreads();
+#include "../pair_tile_stage.inc"   // (padding rows are 0.0: p = b there)
 
   if (tid < 2 * T) {   // p of the 64 rows (threads 0 .. 63) and of the 64 columns (64 .. 127), with the builder's chain
     const int r = tid & (T - 1);
@@ -109,22 +110,7 @@ __global__ __launch_bounds__(256) void arccos_kernel(ArcArgs p) {
   }
 
   double dot[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dot[i][j] = 0.0;
-  for (int dd = 0; dd < d; ++dd) {
-    const d2* a2 = reinterpret_cast<const d2*>(&x1t[dd * T + ty * 4]);
-    const d2* b2 = reinterpret_cast<const d2*>(&x2t[dd * T + tx * 4]);
-    const d2 a01 = a2[0], a23 = a2[1], b01 = b2[0], b23 = b2[1];
-    const double wd = p.w[dd];
-    const double a[4] = {a01.x * wd, a01.y * wd, a23.x * wd, a23.y * wd};
-    const double b[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) dot[i][j] = fma(a[i], b[j], dot[i][j]);
-  }
+#include "../pair_tile_chain.inc"
   __syncthreads();   // s_p .. s_rq
 
   double pr[4], rpr[4], qc[4], rqc[4];
@@ -136,8 +122,7 @@ __global__ __launch_bounds__(256) void arccos_kernel(ArcArgs p) {
     rqc[i] = s_rq[tx * 4 + i];
   }
 
-  const bool full = (r0 + T <= p.n1) && (c0 + T <= p.n2) && ((p.ldk & 1) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(p.K) & 15) == 0);
+#include "../pair_tile_full.inc"
   double v[4][4];
   double rs[4] = {0.0, 0.0, 0.0, 0.0}, cs[4] = {0.0, 0.0, 0.0, 0.0}, ks[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -184,46 +169,13 @@ __global__ __launch_bounds__(256) void arccos_kernel(ArcArgs p) {
   // written by the mirror of the patch below it, a patch on it (tx == ty) takes its upper entries from its lower ones.
   const bool sym = MODE == 0 && p.sym;
   const bool diag_tile = sym && r0 == c0;
-  if (diag_tile && tx == ty) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = i + 1; j < 4; ++j) v[i][j] = v[j][i];
-  }
+#include "../pair_tile_diag_patch.inc"
   if (!(diag_tile && tx > ty)) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int gr = r0 + ty * 4 + i;
-      if (full) {
-        d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + c0 + tx * 4);
-        out[0] = (d2){v[i][0], v[i][1]};
-        out[1] = (d2){v[i][2], v[i][3]};
-      } else if (gr < p.n1) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int gc = c0 + tx * 4 + j;
-          if (gc < p.n2) p.K[(long)gr * p.ldk + gc] = v[i][j];
-        }
-      }
-    }
+#include "../pair_tile_store_rows.inc"
   }
   const bool mirror = sym && (diag_tile ? tx < ty : !p.lower_only);
-  if (mirror) {  // transposed copy: rows c0 + tx*4 + j, columns r0 + ty*4 + i   (sym: n1 == n2)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int gr = c0 + tx * 4 + j;
-      if (full) {
-        d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + r0 + ty * 4);
-        out[0] = (d2){v[0][j], v[1][j]};
-        out[1] = (d2){v[2][j], v[3][j]};
-      } else if (gr < p.n1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int gc = r0 + ty * 4 + i;
-          if (gc < p.n2) p.K[(long)gr * p.ldk + gc] = v[i][j];
-        }
-      }
-    }
+  if (mirror) {
+#include "../pair_tile_store_mirror.inc"
   }
 
   if constexpr (MODE == 3) {
@@ -262,6 +214,8 @@ __global__ __launch_bounds__(256) void arccos_kernel(ArcArgs p) {
     }
   }
 }
+
+#include "../pair_tile_end.inc"
 
 // The row diagonal, the closed form: kd_i = v jf p_i^order with jf = J_order(0) / pi = 1, 1, 3; pair_tile.h's row_diag, p_i by the
 // builder's chain.  op 0: out = kd; 1: g .* kd; 2: g + kd; 3: g .* dkd/dp.  Order 0 does not depend on p:

@@ -73,6 +73,9 @@ struct CpTileArgs {
   double* parts; int tc;      // MODE 2
 };
 
+#define PAIR_OUT p.out
+#define PAIR_LDO p.ldo
+#define PAIR_WRITTEN(gr, gc) gc < p.n2
 template <int MODE>
 __global__ __launch_bounds__(256) void changepoint_tile_kernel(CpTileArgs p) {
   __shared__ double s_a[T], s_b[T];
@@ -143,21 +146,7 @@ __global__ __launch_bounds__(256) void changepoint_tile_kernel(CpTileArgs p) {
       }
     }
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int gr = r0 + ty * 4 + i;
-    if (full) {
-      d2* out = reinterpret_cast<d2*>(p.out + (long)gr * p.ldo + c0 + tx * 4);
-      out[0] = (d2){v[i][0], v[i][1]};
-      out[1] = (d2){v[i][2], v[i][3]};
-    } else if (gr < p.n1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int gc = c0 + tx * 4 + j;
-        if (gc < p.n2) p.out[(long)gr * p.ldo + gc] = v[i][j];
-      }
-    }
-  }
+#include "../pair_tile_store_rows.inc"
 
   if constexpr (MODE == 2) {
     // The tile's partial sums, each by ONE thread in a fixed order: a thread's four elements left to right (above), then the sixteen
@@ -185,6 +174,7 @@ __global__ __launch_bounds__(256) void changepoint_tile_kernel(CpTileArgs p) {
     }
   }
 }
+#include "../pair_tile_end.inc"
 
 // ---- the adjoint tail -------------------------------------------------------------------------------------------------------
 // Rows: one thread per row r of the switch column.  abar_i[r] = init_i[r] + sum_t parts_i[t n + r] (t ascending), then with

@@ -12,7 +12,7 @@
 //     order), so the symmetric build is exactly symmetric WITHOUT a mirror pass, lower_only is bit for bit the lower triangle of the
 //     full build, and the row diagonal, read from B, is bit for bit the diagonal of K(X, X).
 //
-// The tile.  One 64 x 64 tile per 256-thread workgroup, a 4 x 4 patch per thread, the stores of dot_kernel (dot.hip).  The workgroup
+// The tile.  One 64 x 64 tile per 256-thread workgroup, a 4 x 4 patch per thread, the row stores of pair_tile.h.  The workgroup
 // stages B ([P][P], 32 KB at P = 64) and the labels of its 64 rows and 64 columns in LDS; an element is one LDS gather and one global
 // store.  No atomics, no environment reads, vector or plain C++ stores only.
 #include "../pair_tile.h"
@@ -38,6 +38,9 @@ struct CoArgs {
 };
 
 // MODE 0: the build.  1 / 2: out = G .* k / G + k (out may alias G: an element is read and written by the same thread).
+#define PAIR_OUT p.K
+#define PAIR_LDO p.ldk
+#define PAIR_WRITTEN(gr, gc) gc < p.n2 && !(low && gc > gr)
 template <int MODE>
 __global__ __launch_bounds__(256) void coregion_kernel(CoArgs p) {
   extern __shared__ __attribute__((aligned(16))) double sB[];   // [P][P]
@@ -93,22 +96,9 @@ __global__ __launch_bounds__(256) void coregion_kernel(CoArgs p) {
     }
   }
   // (the whole patch first, then its stores: with the sixteen elements of G in flight together the fold is 8 % faster than row by row)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int gr = r0 + ty * 4 + i;
-    if (full) {
-      d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + c0 + tx * 4);
-      out[0] = (d2){v[i][0], v[i][1]};
-      out[1] = (d2){v[i][2], v[i][3]};
-    } else if (gr < p.n1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int gc = c0 + tx * 4 + j;
-        if (gc < p.n2 && !(low && gc > gr)) p.K[(long)gr * p.ldk + gc] = v[i][j];
-      }
-    }
-  }
+#include "../pair_tile_store_rows.inc"
 }
+#include "../pair_tile_end.inc"
 
 // The row diagonal kd_i = B[l_i, l_i], read from B in global memory (one element per row: nothing to stage).
 // op 0: out = kd; 1: g .* kd; 2: g + kd.

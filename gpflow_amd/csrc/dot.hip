@@ -3,8 +3,8 @@
 //   Linear      K = (X1 * w) X2^T            w: one weight, or one per input column (ARD);   K_diag_i = sum_j w_j x_ij^2
 //   Polynomial  K = (Linear.K + offset)^degree                                                K_diag_i = (Linear.K_diag_i + offset)^degree
 //
-// With s = sum_j (x_j w_j) y_j and base = s + offset.  The same 64 x 64 tile per 256-thread workgroup as rbf_kernel (rbf.hip), restated
-// here with the differences of a dot product: the X1 slab is multiplied by its weight while it is staged (X * variance of the
+// With s = sum_j (x_j w_j) y_j and base = s + offset.  The 64 x 64 tile per 256-thread workgroup of pair_tile.h (its fragments, the
+// PAIR_* macros below) with the differences of a dot product: the X1 slab is multiplied by its weight while it is staged (X * variance of the
 // reference: one rounding), the X2 slab is staged as it is, no squared norms; the fma chain runs over the input columns ascending.
 // The power is a product, base * base * ... left to right (degree in [1, GPK_DOT_MAX_DEGREE], no pow): a negative base comes out as
 // the reference's integer power gives it, and the rounding is (degree - 1) u |k| on top of the error of base.
@@ -55,6 +55,13 @@ __device__ __forceinline__ double dot_ds(double s, double offset, int degree) {
 // COMB = 0: plain build.  COMB = 1 / 2 / 3: out = G .* k / G + k / G .* dk/ds, G read from memory (may alias the output: every
 // element is read and written by the same thread; these never take the symmetric shortcut).  Unlike the stationary op 3 the
 // diagonal is NOT zeroed: s_ii = sum_j w_j x_ij^2 depends on the parameters.
+#define PAIR_STAGE_LOCALS
+#define PAIR_STAGE_FIRST(x) x * p.w[dd]
+#define PAIR_STAGE_SECOND(x) x
+#define PAIR_FIRST(x) x
+#define PAIR_OUT p.K
+#define PAIR_LDO p.ldk
+#define PAIR_WRITTEN(gr, gc) gc < p.n2
 template <int FAMILY, int COMB = 0>
 __global__ __launch_bounds__(256) void dot_kernel(DotArgs p) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -67,34 +74,10 @@ __global__ __launch_bounds__(256) void dot_kernel(DotArgs p) {
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
 
-  // stage: padding rows are 0.0; thread t handles (row t / d, column t % d) and on by 256
-  for (int e = tid; e < T * d; e += 256) {
-    const int row = e / d, dd = e - row * d;
-    const int g1 = r0 + row, g2 = c0 + row;
-    x1t[dd * T + row] = (g1 < p.n1) ? p.X1[(long)g1 * p.ldx1 + dd] * p.w[dd] : 0.0;
-    x2t[dd * T + row] = (g2 < p.n2) ? p.X2[(long)g2 * p.ldx2 + dd] : 0.0;
-  }
-  __syncthreads();
-
+#include "pair_tile_stage.inc"
   double dot[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dot[i][j] = 0.0;
-  for (int dd = 0; dd < d; ++dd) {
-    const d2* a2 = reinterpret_cast<const d2*>(&x1t[dd * T + ty * 4]);
-    const d2* b2 = reinterpret_cast<const d2*>(&x2t[dd * T + tx * 4]);
-    const d2 a01 = a2[0], a23 = a2[1], b01 = b2[0], b23 = b2[1];
-    const double a[4] = {a01.x, a01.y, a23.x, a23.y};
-    const double b[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) dot[i][j] = fma(a[i], b[j], dot[i][j]);
-  }
-
-  const bool full = (r0 + T <= p.n1) && (c0 + T <= p.n2) && ((p.ldk & 1) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(p.K) & 15) == 0);
+#include "pair_tile_chain.inc"
+#include "pair_tile_full.inc"
   double v[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -115,48 +98,16 @@ __global__ __launch_bounds__(256) void dot_kernel(DotArgs p) {
   // The symmetric build keeps the elements on or below the diagonal.  In a diagonal tile: a patch above the diagonal (tx > ty) is
   // written by the mirror of the patch below it, a patch on it (tx == ty) takes its upper entries from its lower ones.
   const bool diag_tile = p.sym && r0 == c0;
-  if (diag_tile && tx == ty) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = i + 1; j < 4; ++j) v[i][j] = v[j][i];
-  }
+#include "pair_tile_diag_patch.inc"
   if (!(diag_tile && tx > ty)) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int gr = r0 + ty * 4 + i;
-      if (full) {
-        d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + c0 + tx * 4);
-        out[0] = (d2){v[i][0], v[i][1]};
-        out[1] = (d2){v[i][2], v[i][3]};
-      } else if (gr < p.n1) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int gc = c0 + tx * 4 + j;
-          if (gc < p.n2) p.K[(long)gr * p.ldk + gc] = v[i][j];
-        }
-      }
-    }
+#include "pair_tile_store_rows.inc"
   }
   const bool mirror = p.sym && (diag_tile ? tx < ty : !p.lower_only);
-  if (mirror) {  // transposed copy: rows c0 + tx*4 + j, columns r0 + ty*4 + i   (sym: n1 == n2)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int gr = c0 + tx * 4 + j;
-      if (full) {
-        d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + r0 + ty * 4);
-        out[0] = (d2){v[0][j], v[1][j]};
-        out[1] = (d2){v[2][j], v[3][j]};
-      } else if (gr < p.n1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int gc = r0 + ty * 4 + i;
-          if (gc < p.n2) p.K[(long)gr * p.ldk + gc] = v[i][j];
-        }
-      }
-    }
+  if (mirror) {
+#include "pair_tile_store_mirror.inc"
   }
 }
+#include "pair_tile_end.inc"
 
 // The row diagonal kd_i = k(x_i, x_i): 64 rows per workgroup, staged into LDS as [d][64] with lanes along the contiguous dimension of X;
 // thread r < 64 then sums row r over the columns ascending with the builder's own chain fma(x w, x, .), so kd is the diagonal of the

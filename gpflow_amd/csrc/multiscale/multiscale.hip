@@ -55,6 +55,8 @@ __device__ __forceinline__ void store_row(double* K, long ldk, int gr, int gc0, 
 }
 
 // OP 0: the build.  1 / 2: out = G .* Kfu / G + Kfu (out may alias G: an element is read and written by the same thread).
+#define PAIR_OUT p.K
+#define PAIR_LDO p.ldk
 template <int OP>
 __global__ __launch_bounds__(256) void ms_kfu_kernel(MsArgs p) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(256) void ms_kfu_kernel(MsArgs p) {
   }
   __syncthreads();   // cm, s_px
 
-  const bool full = (r0 + T <= p.n1) && (c0 + T <= p.n2) && ((p.ldk & 1) == 0) && ((reinterpret_cast<uintptr_t>(p.K) & 15) == 0);
+#include "../pair_tile_full.inc"
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int gr = r0 + ty * 4 + i;
@@ -209,16 +211,12 @@ __global__ __launch_bounds__(256) void ms_kuu_kernel(MsArgs p) {
   }
 
   if constexpr (MODE != 3) {
+    // (its own line: with pair_tile_full.inc's p.n1 / p.n2 for M the two kernels come out with other code)
     const bool full = (r0 + T <= M) && (c0 + T <= M) && ((p.ldk & 1) == 0) && ((reinterpret_cast<uintptr_t>(p.K) & 15) == 0);
     // In a diagonal tile of the build: a patch above the diagonal (tx > ty) is written by the mirror of the patch below it, a patch
     // on it (tx == ty) takes its upper entries from its lower ones.
     const bool diag_tile = MODE == 0 && r0 == c0;
-    if (diag_tile && tx == ty) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = i + 1; j < 4; ++j) v[i][j] = v[j][i];
-    }
+#include "../pair_tile_diag_patch.inc"
     if (!(diag_tile && tx > ty)) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) store_row(p.K, p.ldk, r0 + ty * 4 + i, c0 + tx * 4, M, M, full, v[i][0], v[i][1], v[i][2], v[i][3]);
@@ -302,6 +300,7 @@ __global__ __launch_bounds__(256) void ms_kuu_kernel(MsArgs p) {
     }
   }
 }
+#include "../pair_tile_end.inc"
 
 // The tails.  Stage 1, a workgroup per TAIL_ROWS inducing points: thread t owns column t % d and walks the rows t / d, t / d + rpp, ...
 // of its block; it finishes dZ and dscales of its (row, column)s and leaves the block's sums in blocks[b (1 + d) + {0, 1 + j}]:

@@ -1,7 +1,32 @@
-// What the 64 x 64 pair-tile builders (rbf.hip, dot.hip, arccosine/arccosine.hip) share WITHOUT changing their tile kernels' code:
-// the host side of a launch and the row-diagonal skeleton.  The tile's device pieces (staging, 4 x 4 chain, `full`, the two stores)
-// stay restated in rbf_kernel, dot_kernel and arccos_kernel: as __forceinline__ helpers they compute the same bits, but a helper is
-// simplified before it is inlined and the kernels came out with other register counts -- profiles/pair_tile_refactor.txt.
+// The 64 x 64 pair tile of the narrow builders (d <= GPK_MAX_D columns): one tile per 256-thread workgroup, thread (tx, ty) = (tid & 15,
+// tid >> 4) owns the 4 x 4 patch at rows r0 + ty * 4, columns c0 + tx * 4.  Written here once: the host side of a launch, the
+// row-diagonal skeleton, and the tile's device pieces as textual fragments, pair_tile_*.inc, each a run of statements included inside
+// a file's own kernel.  Fragments and not __forceinline__ helpers: a helper is simplified before it is inlined and the kernels came out
+// with other register counts (profiles/pair_tile_refactor.txt); as text a fragment is the kernel's own tokens, and every kernel of the
+// seven files is instruction for instruction what it was when it restated them (profiles/pair_tile_fragments.txt).
+//
+// A tile kernel `__global__ __launch_bounds__(256)` over an args struct `p` with n1, n2 #defines the macros of the fragments it uses
+// ahead of its template line and includes pair_tile_end.inc, which #undefs them all, behind its closing brace.  Every fragment expects
+// T (below), r0, c0, tx, ty.  In the order of a kernel's body:
+//   pair_tile_stage.inc         expects tid, d, x1t, x2t and p.X1 ldx1 X2 ldx2; fills the two [d][T] slabs (padding rows 0.0), one barrier
+//       PAIR_STAGE_LOCALS           a statement per staged (row, dd), or empty: what the two transforms share (rbf.hip: the lengthscale)
+//       PAIR_STAGE_FIRST(x)         the staged value of an element x of X1;  PAIR_STAGE_SECOND(x): of X2
+//   pair_tile_chain.inc         expects d, x1t, x2t and `double dot[4][4]`; leaves dot[i][j]: two d2 reads per slab and column, 16 fmas
+//       PAIR_FIRST(x)               the first factor from the staged x (arccosine.hip: x * p.w[dd], formed in registers)
+//   pair_tile_full.inc          leaves `const bool full`: the tile is whole, PAIR_LDO even and PAIR_OUT 16-byte aligned
+//       PAIR_OUT, PAIR_LDO          the output and its leading dimension (p.K, p.ldk; changepoints.hip: p.out, p.ldo)
+//   the file's epilogue         `double v[4][4]` from dot: what is particular to each file, with the predicates of its symmetric build
+//   pair_tile_diag_patch.inc    expects `diag_tile`, v; a patch on the diagonal of a diagonal tile takes its upper entries from its lower
+//   pair_tile_store_rows.inc    expects full, v; PAIR_OUT, PAIR_LDO; two 16-byte stores per row where full, else guarded scalar stores
+//       PAIR_WRITTEN(gr, gc)        the scalar store's condition on the column: gc < p.n2 (coregion.hip: and not above the diagonal of
+//                                   a lower_only build)
+//   pair_tile_store_mirror.inc  expects full, v; PAIR_OUT, PAIR_LDO; the transposed copy.  WHEN it runs stays in each file: that is the
+//                               file's contract (rbf.hip: whole tiles off the diagonal; dot.hip, arccosine.hip: also inside a diagonal tile)
+// Users: rbf.hip, dot.hip, arccosine/arccosine.hip all of it (rbf.hip no diag_patch); changepoints/, coregion/ the row stores;
+// multiscale/ `full` (ms_kfu_kernel) and diag_patch (ms_kuu_kernel) -- its store_row helper and ms_kuu_kernel's `full` over M stay:
+// with the fragments in their place its five builders came out with other code (profiles/pair_tile_fragments.txt, section 1).
+// An edit to the tile -- a staged vector more, another store -- is made in one fragment and proved equal once per file
+// (tools/kernel_code_diff.py).
 #pragma once
 #include "gpk_internal.h"
 #include <cmath>

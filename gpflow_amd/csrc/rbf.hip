@@ -13,6 +13,7 @@
 // 4 x 4 patch and stores 32 contiguous bytes per row (16 threads -> 512 B contiguous per row).
 // The expansion formula and the association (-2 x.y) + (|x|^2 + |y|^2) of the reference are kept
 // so rounding has the same structure (the diagonal is exp(-0.5 * ~1e-16), not exactly sigma^2).
+// The tile's staging, chain, `full` and stores are the fragments of pair_tile.h (the PAIR_* macros below); the norms and the epilogue are here.
 #include "pair_tile.h"
 #include "kern_profile.h"
 #include <algorithm>
@@ -52,6 +53,13 @@ constexpr bool kern_static = (family == GPK_KERN_WHITE || family == GPK_KERN_CON
 // COMB = 3: out = G .* (-2 dk/dr2); with comb_diag (X2 is X1) the diagonal is written as exact zeros: r2_ii = 0 for
 // every parameter value, so it carries no gradient (autodiff of the expansion formula gets rounding noise there,
 // amplified by 1/r for Matern12).  COMB = 4 (GPK_KERN_RQ only): out = G .* dk/dalpha, diagonal as for COMB = 3.
+#define PAIR_STAGE_LOCALS const double l = p.ard ? p.ls[dd] : p.ls[0];
+#define PAIR_STAGE_FIRST(x) x / l
+#define PAIR_STAGE_SECOND(x) x / l
+#define PAIR_FIRST(x) x
+#define PAIR_OUT p.K
+#define PAIR_LDO p.ldk
+#define PAIR_WRITTEN(gr, gc) gc < p.n2
 template <int FAMILY, int COMB = 0>
 __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -69,15 +77,7 @@ __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
   double dot[4][4];
   const int tx = tid & 15, ty = tid >> 4;
   if constexpr (!kern_static<FAMILY>) {
-    // stage + scale (true division, as the reference) -- thread t handles (row t>>2, dims (t&3)::4)
-    for (int e = tid; e < T * d; e += 256) {
-      const int row = e / d, dd = e - row * d;
-      const double l = p.ard ? p.ls[dd] : p.ls[0];
-      const int g1 = r0 + row, g2 = c0 + row;
-      x1t[dd * T + row] = (g1 < p.n1) ? p.X1[(long)g1 * p.ldx1 + dd] / l : 0.0;
-      x2t[dd * T + row] = (g2 < p.n2) ? p.X2[(long)g2 * p.ldx2 + dd] / l : 0.0;
-    }
-    __syncthreads();
+#include "pair_tile_stage.inc"   // (scaled while staged: true division, as the reference)
     if (tid < 2 * T) {
       const double* src = (tid < T) ? x1t : x2t;
       const int row = tid & (T - 1);
@@ -90,24 +90,9 @@ __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
     }
     __syncthreads();
 
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) dot[i][j] = 0.0;
-    for (int dd = 0; dd < d; ++dd) {
-      const d2* a2 = reinterpret_cast<const d2*>(&x1t[dd * T + ty * 4]);
-      const d2* b2 = reinterpret_cast<const d2*>(&x2t[dd * T + tx * 4]);
-      const d2 a01 = a2[0], a23 = a2[1], b01 = b2[0], b23 = b2[1];
-      const double a[4] = {a01.x, a01.y, a23.x, a23.y};
-      const double b[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dot[i][j] = fma(a[i], b[j], dot[i][j]);
-    }
+#include "pair_tile_chain.inc"
   }  // !kern_static
-  const bool full = (r0 + T <= p.n1) && (c0 + T <= p.n2) && ((p.ldk & 1) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(p.K) & 15) == 0);
+#include "pair_tile_full.inc"
   double v[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -136,40 +121,13 @@ __global__ __launch_bounds__(256) void rbf_kernel(RbfArgs p) {
       v[i][j] = k;
     }
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int gr = r0 + ty * 4 + i;
-    if (full) {
-      d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + c0 + tx * 4);
-      out[0] = (d2){v[i][0], v[i][1]};
-      out[1] = (d2){v[i][2], v[i][3]};
-    } else if (gr < p.n1) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int gc = c0 + tx * 4 + j;
-        if (gc < p.n2) p.K[(long)gr * p.ldk + gc] = v[i][j];
-      }
-    }
-  }
+#include "pair_tile_store_rows.inc"
   // (full 16384^2 build: mirror tile through LDS 0.479 ms, this register layout 0.422; nt stores 0.455 / 0.429 -- profiles/r02_ab_kernel_builder.log)
-  if (mirror && r0 != c0) {  // transposed copy: rows c0 + tx*4 + j, columns r0 + ty*4 + i
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int gr = c0 + tx * 4 + j;
-      if (full) {
-        d2* out = reinterpret_cast<d2*>(p.K + (long)gr * p.ldk + r0 + ty * 4);
-        out[0] = (d2){v[0][j], v[1][j]};
-        out[1] = (d2){v[2][j], v[3][j]};
-      } else if (gr < p.n1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int gc = r0 + ty * 4 + i;
-          if (gc < p.n2) p.K[(long)gr * p.ldk + gc] = v[i][j];
-        }
-      }
-    }
+  if (mirror && r0 != c0) {
+#include "pair_tile_store_mirror.inc"
   }
 }
+#include "pair_tile_end.inc"
 
 template <int FAMILY, int COMB>
 int launch_family(hipStream_t st, const RbfArgs& a, size_t lds) {
